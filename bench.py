@@ -9,16 +9,24 @@ A *step* = one frame for every stream of the batch (lock-step TrackingBatch); pe
 scaling): streams are independent shards, there is no data-path collective, only a terminal RCCL reduction of counters.
 Inputs (rendered synthetic frames) are resident in HBM before the timed region.
 
+A plain run measures the headline only: set-up, priming and warm-up, the timed steps, the outputs of the last step when
+--dump-outputs names a directory, the line.  --full adds everything else the line can carry: the parity witness, the profiled
+pass, the kernel-only ceiling and the roofline, the CPU baselines, the back-end and next-row blocks, the engine twin and
+the details file.  The terminal exchange goes through a one-rank RCCL group at N = 1 either way.
+
     python bench.py --gpus 1 --steps 40 --warmup 12
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
         bench.py --gpus 8 --steps 40 --warmup 12
 """
 import argparse
+import collections
 import ctypes as C
 import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -270,11 +278,12 @@ def measure_marg_batched(nmb, timeout=180, n_lm=300, n_kf=10):
 
 
 def run_frontend(torch, hip, *, w, h, nfeat, window, B, G, ring, prime, warmup, steps, rank, local_rank, host_threads, host_frames,
-                 profile, barrier, ncpu, hostprof=False, forward=False, host_lib=None, dev_sync=None):
+                 profile, barrier, ncpu, hostprof=False, forward=False, host_lib=None, dev_sync=None, outputs=False):
     """One front-end throughput measurement: B independent synthetic streams in G free-running groups, raw frames resident in HBM,
     `prime` untimed frames per stream in setup, `warmup` untimed steps, EXACTLY `steps` timed lock-step frames per stream.
     forward=True: the streams never turn round (frame k of the run is rendered frame k: `ring` must cover the whole run) — the control for
-    the ping-pong replay, whose motion reverses every ring-1 frames."""
+    the ping-pong replay, whose motion reverses every ring-1 frames.
+    outputs=True: the result carries "outputs", what the timed path handed its caller after the last timed step (step_outputs)."""
     if forward and ring < prime + warmup + steps:
         raise ValueError("forward-only run: ring must hold prime + warmup + steps frames")
     cam = H.camera_for(w, h)
@@ -283,38 +292,54 @@ def run_frontend(torch, hip, *, w, h, nfeat, window, B, G, ring, prime, warmup, 
     selftest = host_lib is not None
     dev_sync = dev_sync or torch.cuda.synchronize
     sb = H.StreamBatch(host_lib or H.HOST_LIB, B, w, h, cam, max_features=nfeat, window=window, device=local_rank, host_threads=host_threads, groups=G)
-    scene = H.SynthScene(sb.lib, w, h, cam, tex_size=2048, threads=max(1, min(16, ncpu)))
+    # one frame per render call: the frames are rendered by a pool of host threads (the renderer releases the GIL), a whole frame per task
+    render_threads = max(1, min(16, ncpu))
+    scene = H.SynthScene(sb.lib, w, h, cam, tex_size=2048, threads=1)
     ctxh = C.c_void_p(sb.ctx_handle(0))
     ctx_all = [C.c_void_p(sb.ctx_handle(g)) for g in range(sb.n_groups())]
     pinned, dev_ptrs = [], []
+    # device frames: one allocation per stream holding its ring, every frame at a page-aligned offset
+    slot = (w * h + 4095) // 4096 * 4096
 
-    def dev_upload(img):
+    def dev_upload_stream(imgs):
         if host_frames:
-            t = torch.from_numpy(img) if selftest else torch.from_numpy(img).pin_memory()
-            pinned.append(t)
-            return t.data_ptr()
+            out = []
+            for img in imgs:
+                t = torch.from_numpy(img) if selftest else torch.from_numpy(img).pin_memory()
+                pinned.append(t)
+                out.append(t.data_ptr())
+            return out
         p = C.c_void_p()
-        assert hip.icg_dev_alloc(ctxh, C.c_size_t(img.nbytes), C.byref(p)) == 0
-        assert hip.icg_dev_upload(ctxh, p, img.ctypes.data_as(C.c_void_p), C.c_size_t(img.nbytes)) == 0
+        assert hip.icg_dev_alloc(ctxh, C.c_size_t(slot * len(imgs)), C.byref(p)) == 0
         dev_ptrs.append(p)
-        return p.value
+        for k, img in enumerate(imgs):
+            assert hip.icg_dev_upload(ctxh, C.c_void_p(p.value + k * slot), img.ctypes.data_as(C.c_void_p), C.c_size_t(img.nbytes)) == 0
+        return [p.value + k * slot for k in range(len(imgs))]
 
     t_setup = time.time()
     sids = sharding.shard_stream_ids(rank, 0, B)
-    dev, host0 = [], []
+    dev, host0, poses = [], [], []
     witness = sorted({0, B - 1})  # streams whose rendered frames are kept on the host for the parity witness (first and last group)
     host_keep = {s: [] for s in witness}
-    for s in range(B):
-        ptrs = []
-        for k in range(ring):
-            img = scene.render(k, stream=sids[s])
+
+    def render_stream(s):
+        return ([scene.render(k, stream=sids[s]) for k in range(ring)],
+                [H.pose12(*scene.ins_pose(k, stream=rank * B + s)) for k in range(ring)])
+
+    # the pool renders ahead (at most two streams per thread in flight) while this thread uploads the streams in order
+    with ThreadPoolExecutor(render_threads) as pool:
+        pending, nxt = collections.deque(), 0
+        for s in range(B):
+            while nxt < B and len(pending) < 2 * render_threads:
+                pending.append(pool.submit(render_stream, nxt))
+                nxt += 1
+            imgs, pose_rows = pending.popleft().result()
             if s == 0:
-                host0.append(img)
+                host0 = imgs
             if s in host_keep:
-                host_keep[s].append(img)
-            ptrs.append(dev_upload(img))
-        dev.append(ptrs)
-    poses = [[H.pose12(*scene.ins_pose(k, stream=rank * B + s)) for k in range(ring)] for s in range(B)]
+                host_keep[s] = imgs
+            dev.append(dev_upload_stream(imgs))
+            poses.append(pose_rows)
     t_setup = time.time() - t_setup
 
     def prepare_steps(k0, K):
@@ -411,6 +436,7 @@ def run_frontend(torch, hip, *, w, h, nfeat, window, B, G, ring, prime, warmup, 
     tracked = sum(s_["tracked_sum"] for s_ in stats) - tracked_before
     rates = event_rates(sb.counters(reset=True), sum(a["keyframes"] - b["keyframes"] for a, b in zip(stats, stats_before)),
                         sum(a["mappoints_created"] - b["mappoints_created"] for a, b in zip(stats, stats_before)), B * steps)
+    step_out = step_outputs(sb, st[-1], stats, sids) if outputs else None
     # the timed region continued to 200 steps (report the long-run rate beside `value` instead of tuning the priming for a
     # 20-step region): the same streams go on from where the timed region stopped; digests / statistics above belong to the timed region
     extended = None
@@ -551,7 +577,43 @@ def run_frontend(torch, hip, *, w, h, nfeat, window, B, G, ring, prime, warmup, 
             "frames_per_stream_at_digest": prime + warmup + steps, "ring": ring, "rates": rates, "cpu_cores_busy": round(cpu_cores_used, 2),
             "elapsed": elapsed, "states_hist": states_hist, "tracked": tracked, "stats": stats, "step_stats": step_stats,
             "host_breakdown": host_breakdown, "kernel_table": kernel_table, "work": work, "n_groups": n_groups, "setup_s": t_setup,
-            "prime_s": t_prime, "host0": host0, "poses0": poses[0], "cam": cam, "extended": extended}
+            "prime_s": t_prime, "host0": host0, "poses0": poses[0], "cam": cam, "extended": extended, "outputs": step_out}
+
+
+OUTPUT_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def step_outputs(sb, states, stats, stream_ids):
+    """What a caller of the timed path holds after its last step, as float32 / float64 arrays: every stream's track state of that step, the
+    features of its current frame (map-point id and distorted key point, in id order) and its running statistics, the 64-bit digest split
+    into two exact 32-bit halves.  Beyond OUTPUT_LIMIT_BYTES a fixed, seeded sample of the streams is kept."""
+    n = len(states)
+    feats = [sb.features(s) for s in range(n)]
+    per_stream = [16 * len(ids) + 8 * 12 for ids, _ in feats]
+    keep, m = np.arange(n), n
+    while sum(per_stream[s] for s in keep) > OUTPUT_LIMIT_BYTES and m > 1:
+        m = max(1, int(0.9 * m * OUTPUT_LIMIT_BYTES / sum(per_stream[s] for s in keep)))
+        keep = np.sort(np.random.RandomState(0).choice(n, m, replace=False))
+    ids = np.concatenate([feats[s][0] for s in keep]) if len(keep) else np.zeros(0, np.uint64)
+    if ids.size and int(ids.max()) >= 1 << 53:
+        raise RuntimeError("map-point id beyond 2^53: not exact in float64")
+    st = np.array([[stats[s][k] for k in ("frames", "keyframes", "tracked_sum", "mappoints_created", "window_keyframes", "landmarks", "last_state")]
+                   for s in keep], np.float64).reshape(-1, 7)
+    dig = np.array([stats[s]["digest"] for s in keep], np.uint64)
+    return {"stream_ids": np.asarray(stream_ids, np.float64)[keep],
+            "track_state": np.asarray(states, np.float64)[keep],
+            "feature_counts": np.array([len(feats[s][0]) for s in keep], np.float64),
+            "feature_ids": ids.astype(np.float64),
+            "feature_px": np.concatenate([feats[s][1] for s in keep]).astype(np.float32).reshape(-1, 2),
+            "stream_stats": st,
+            "stream_digest": np.stack([(dig >> np.uint64(32)).astype(np.float64), (dig & np.uint64(0xffffffff)).astype(np.float64)], 1).reshape(-1, 2)}
+
+
+def write_outputs(directory, outputs, rank, world):
+    """DIR/<name>.npy for every array of step_outputs (with N > 1 every rank writes its own streams: DIR/<name>.rank<r>.npy)"""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(directory, name + (".rank%d" % rank if world > 1 else "") + ".npy"), a)
 
 
 def _pick(d, keys):
@@ -716,7 +778,19 @@ def main():
                          "stream's digest compared between the two)")
     ap.add_argument("--details", default=os.environ.get("ICG_BENCH_DETAILS", ""),
                     help="file for the long per-group / per-step series and notes (default gpurun_out/bench_details.json); the contract line stays compact")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the parity witness, the profiled pass with the 200-step continuation, the kernel-only "
+                         "ceiling and the roofline (with the HBM-peak copy), the CPU baselines, the back-end / next-row blocks, the engine twin, "
+                         "the forward-only and PCIe-inclusive controls and the details file (--details).  "
+                         "Without it a run sets up, primes, warms up, times the steps and prints the line (value unchecked: parity null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy (float32 / float64): "
+                         "per stream the track state, the current frame's features (map-point ids, key points) and the running statistics "
+                         "with the digest; the same arguments give the same inputs in every run")
     args = ap.parse_args()
+    if not args.full:
+        # the headline only: every check and side measurement is a --full item
+        args.no_cpu_baseline = args.no_reproj = args.no_parity = args.no_profile_pass = args.no_engine_twin = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -752,7 +826,9 @@ def main():
     elif not selftest and not args.no_dist:
         # N = 1: the terminal exchange — all-reduce of the counters, all-gather of the digests and of the
         # rank rows — runs through RCCL on cuda:0 with a process group of ONE rank, so the collective leg of the multi-GPU path executes on
-        # the hardware every single-GPU run has.  After the timed region: nothing of it is inside `value`.
+        # the hardware every single-GPU run has.  After the timed region: nothing of it is inside `value`.  A plain run keeps it: without the
+        # group the same run measured 122-125 k instead of 157-167 k frames/s, two of the four groups at 6.0 ms per step and two at 3.6 ms
+        # (one box, GPU_MAX_HW_QUEUES 4 and 20 alike); the cause is not isolated.
         import socket
         import torch.distributed as dist_
         try:
@@ -796,7 +872,7 @@ def main():
         hip = C.CDLL(selftest_lib)  # (the checker build carries the C ABI on the oracle)
     else:
         hip = icgvins.load_library()
-    hbm_peak_measured = measure_hbm_peak(torch, torch.device("cuda", local_rank)) if (rank == 0 and not selftest) else None
+    hbm_peak_measured = measure_hbm_peak(torch, torch.device("cuda", local_rank)) if (rank == 0 and not selftest and args.full) else None
 
     def barrier():
         dev_sync()
@@ -806,7 +882,9 @@ def main():
     fe = run_frontend(torch, hip, w=w, h=h, nfeat=nfeat, window=10, B=B, G=G, ring=args.ring, prime=args.prime, warmup=args.warmup,
                       steps=args.steps, rank=rank, local_rank=local_rank, host_threads=host_threads, host_frames=args.host_frames,
                       profile=(rank == 0 and not args.no_profile_pass), barrier=barrier, ncpu=ncpu,
-                      hostprof=bool(os.environ.get("ICG_HOST_PROF")), host_lib=selftest_lib, dev_sync=dev_sync)
+                      hostprof=bool(os.environ.get("ICG_HOST_PROF")), host_lib=selftest_lib, dev_sync=dev_sync, outputs=bool(args.dump_outputs))
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, fe["outputs"], rank, world)
     elapsed, states_hist, stats = fe["elapsed"], fe["states_hist"], fe["stats"]
     host0, poses0, cam = fe["host0"], fe["poses0"], fe["cam"]
     t_setup, t_prime = fe["setup_s"], fe["prime_s"]
@@ -1495,7 +1573,7 @@ def main():
                        "input_residency": "pinned host frames, uploaded per frame (PCIe-inclusive diagnostic)" if args.host_frames else "raw frames in HBM", "sharding": "independent streams per GPU, no data-path collective",
                        "engine": {"table": "track table (host/track_table.h)", "object": "object graph", "core": "tracker core on the host (host/track_core.h)",
                                   "device": "device-resident tracker (csrc/tracker.hip: state in HBM, one launch chain + one wait per step)"}[args.engine]},
-            "parity": parity if not args.no_parity else {"ok": None, "skipped": "--no-parity (diagnostic run)"},
+            "parity": parity if not args.no_parity else {"ok": None, "skipped": "--no-parity (diagnostic run)" if args.full else "runs with --full"},
             "ranks": ranks_block,
             "exchange": exchange,
             "value_200steps": ((fe.get("extended") or {}).get("frames_per_s") if (world == 1 and (parity_ok or args.no_parity) and not selftest) else None),
@@ -1537,12 +1615,15 @@ def main():
                                 "elapsed_max_s": round(elapsed_max, 4)}
         # the long series, tables and notes go to a side file; the contract line keeps every quoted number and stays well under 8 KB
         details_path = args.details or os.path.join(ROOT, "gpurun_out", "bench_details.json")
-        try:
-            os.makedirs(os.path.dirname(details_path), exist_ok=True)
-            with open(details_path, "w") as f_:
-                json.dump(full, f_)
-        except OSError:
-            details_path = None
+        if not (args.full or args.details):
+            details_path = None  # (a plain run writes no side file)
+        else:
+            try:
+                os.makedirs(os.path.dirname(details_path), exist_ok=True)
+                with open(details_path, "w") as f_:
+                    json.dump(full, f_)
+            except OSError:
+                details_path = None
         C.CDLL(None).fflush(None)  # whatever native libraries left in the C stdout buffer goes out BEFORE the contract line
         sys.stdout.flush()
     if dist is not None:

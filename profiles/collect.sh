@@ -18,9 +18,9 @@ OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ -z "$ENGINE" ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_kt -o kt -- python $R/bench.py --no-cpu-baseline --no-replay --details $OUT/${TAG}${ESUF}_kt_bench_details.json > $OUT/${TAG}${ESUF}_kt_bench.json 2> $OUT/${TAG}${ESUF}_kt.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_kt -o kt -- python $R/bench.py --full --no-cpu-baseline --no-replay --details $OUT/${TAG}${ESUF}_kt_bench_details.json > $OUT/${TAG}${ESUF}_kt_bench.json 2> $OUT/${TAG}${ESUF}_kt.err
 else
-python $R/bench.py $EARG --no-cpu-baseline --no-reproj --no-parity --no-engine-twin --steps 60 --warmup 10 --details $OUT/${TAG}${ESUF}_kt_bench_details.json > $OUT/${TAG}${ESUF}_kt_bench.json 2> $OUT/${TAG}${ESUF}_kt.err
+python $R/bench.py --full $EARG --no-cpu-baseline --no-reproj --no-parity --no-engine-twin --steps 60 --warmup 10 --details $OUT/${TAG}${ESUF}_kt_bench_details.json > $OUT/${TAG}${ESUF}_kt_bench.json 2> $OUT/${TAG}${ESUF}_kt.err
 fi
 # the counter passes run the BENCH CONFIGURATION (default streams / groups of this box), shortened: 24 priming + 2 warm-up + 6 timed frames per stream
 SHORT="$EARG --no-cpu-baseline --no-reproj --no-engine-twin --prime 24 --warmup 2 --steps 6 --no-profile-pass"

@@ -55,7 +55,7 @@ def test_bench_terminal_exchange_runs_through_rccl_on_one_gpu(tmp_path):
     bench = os.path.join(root, "bench.py")
     tiny = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--width", "640", "--height", "480", "--features", "100", "--streams", "8", "--groups", "2",
             "--ring", "6", "--prime", "4", "--no-reproj", "--no-c4", "--no-replay", "--no-cpu-baseline", "--no-engine-twin", "--no-profile-pass",
-            "--force-dist"]
+            "--force-dist", "--full"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     lines = []
     for k, launcher in enumerate(([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",

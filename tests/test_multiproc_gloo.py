@@ -103,14 +103,14 @@ def test_host_plan_scales_the_polling_threads_with_the_rank_share():
     assert sharding.host_plan(16, 1, 0, groups_override=8, streams_override=64)["groups"] == 8
 
 
-def _run_bench_selftest(world, streams, port, details, engine="table"):
+def _run_bench_selftest(world, streams, port, details, engine="table", extra=("--full",)):
     """bench.py's own main() as the driver launches it (python -m torch.distributed.run ... bench.py --gpus N ...), in its CPU plumbing
     self-test mode (ICG_BENCH_SELFTEST_ORACLE=1: gloo + the oracle-backed checker build of the host layer; value is null by construction)"""
     import json
     import subprocess
     env = dict(os.environ, ICG_BENCH_SELFTEST_ORACLE="1", MASTER_ADDR="127.0.0.1")
     tiny = ["--steps", "3", "--warmup", "1", "--width", "320", "--height", "240", "--features", "60", "--streams", str(streams),
-            "--groups", "2", "--ring", "6", "--prime", "4", "--details", details, "--engine", engine]
+            "--groups", "2", "--ring", "6", "--prime", "4", "--details", details, "--engine", engine] + list(extra)
     bench = os.path.join(ROOT, "bench.py")
     if world == 1:
         cmd = [sys.executable, bench, "--gpus", "1"] + tiny
@@ -153,3 +153,30 @@ def test_bench_main_runs_two_ranks_as_the_driver_launches_it(tmp_path):
     # (the gathered digests travel as int64: 63 bits)
     assert two["selftest"]["digests"] == [d & 0x7fffffffffffffff for d in one["selftest"]["digests"]]
     assert two["selftest"]["tracked_mappoints"] == one["selftest"]["tracked_mappoints"]
+
+
+def test_bench_plain_run_dumps_the_outputs_of_its_last_step(tmp_path):
+    """The plain command measures the headline only (no engine twin, no parity witness, no roofline) and, with --dump-outputs DIR, writes
+    what the timed path returned in its last step as float32 / float64 .npy files: the same arguments give the same arrays in every run, and
+    the dumped digests are the streams' digests of the line."""
+    import numpy as np
+    port = 29800 + (os.getpid() % 90)
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("out%d" % k)
+        line = _run_bench_selftest(1, 4, port + k, str(tmp_path / ("d%d.json" % k)), engine="table", extra=("--dump-outputs", str(out)))
+        runs.append((line, {f: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))}))
+    for line, arrays in runs:
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["parity"]["ok"] is None
+        assert line["engine_twin"] is None and line["roofline"] is None and line["exchange"].startswith("local")
+        assert set(arrays) == {"stream_ids.npy", "track_state.npy", "feature_counts.npy", "feature_ids.npy", "feature_px.npy", "stream_stats.npy",
+                               "stream_digest.npy"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["feature_ids.npy"].shape[0] == arrays["feature_px.npy"].shape[0] == int(arrays["feature_counts.npy"].sum()) > 0
+        dig = arrays["stream_digest.npy"].astype(np.uint64)
+        assert [int(d) for d in (dig[:, 0] << np.uint64(32)) | dig[:, 1]] == line["selftest"]["digests"]
+    for name in runs[0][1]:
+        assert np.array_equal(runs[0][1][name], runs[1][1][name]), name
