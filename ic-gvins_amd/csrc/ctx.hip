@@ -154,8 +154,6 @@ extern "C" void icg_ctx_destroy(icg_ctx *ctx) {
                    ctx->d_fwin,   ctx->d_lmwin};
     for (void *p : dev)
         if (p) (void) hipFree(p);
-    if (ctx->d_redS) (void) hipFree(ctx->d_redS);
-    if (ctx->d_hostS) (void) hipFree(ctx->d_hostS);
     for (icg_partition *pt : {&ctx->part_1, &ctx->part_w}) {
         if (pt->plan.d_buf) (void) hipFree(pt->plan.d_buf);
         if (pt->plan.d_part) (void) hipFree(pt->plan.d_part);
@@ -191,8 +189,6 @@ int icg_arena_reserve(icg_ctx *ctx, size_t bytes) {
     if (ctx->arena_off != 0) return icg_fail(ctx, ICG_ERR_NOMEM, "arena grow requested mid-call");
     size_t cap = icg_align_up(bytes + bytes / 2, 1 << 16);
     ICG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // only the staging arena pair is replaced here: the resident reduced systems (d_redS) and the packed host parts (d_hostS) are
-    // independent allocations that live until icg_ctx_destroy
     if (ctx->h_arena) (void) hipHostFree(ctx->h_arena);
     if (ctx->d_arena) (void) hipFree(ctx->d_arena);
     ctx->h_arena = nullptr;

@@ -85,4 +85,16 @@ private:
     std::thread t_; // (last: the loop uses the members above)
 };
 
+// A call on a SideThread that is waited for on every way out of the scope
+struct SideCall {
+    SideThread &t;
+    bool pending = true;
+    template <typename F> SideCall(SideThread &side, F &&f) : t(side) { t.start(std::forward<F>(f)); }
+    void join() {
+        if (pending) t.wait();
+        pending = false;
+    }
+    ~SideCall() { join(); }
+};
+
 } // namespace icg

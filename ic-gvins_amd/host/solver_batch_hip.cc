@@ -16,7 +16,6 @@
 namespace icg {
 
 using solver_detail::choleskySolve;
-using solver_detail::posePlus;
 
 // The per-window host phases of an LM step (host factors, reduced solves, trial bookkeeping) take tens of microseconds per window: they
 // run on a persistent pool — spawning threads per phase (four phases per step) cost more than the phases themselves.
@@ -55,39 +54,21 @@ void WindowSolverBatch::clear() {
     error_.clear();
 }
 
-void WindowSolverBatch::removeResidualBlock(int w, int id) { windows_.at((size_t) w).residuals.at((size_t) id).removed = true; }
+void WindowSolverBatch::removeResidualBlock(int w, int id) { windows_.at((size_t) w).problem.removeResidualBlock(id); }
 
 bool WindowSolverBatch::evaluateResidualBlock(int w, int id, bool apply_loss_function, double *cost) const {
-    return solver_detail::residualCost(windows_.at((size_t) w).residuals.at((size_t) id), apply_loss_function, cost);
+    return windows_.at((size_t) w).problem.evaluateResidualBlock(id, apply_loss_function, cost);
 }
 
 void WindowSolverBatch::addParameterBlock(int w, double *values, int size, bool pose_manifold) {
-    Window &W = windows_.at((size_t) w);
-    if (W.block_of.count(values)) return;
-    if (pose_manifold && size != 7) throw std::runtime_error("WindowSolverBatch: the pose manifold needs a block of size 7");
-    W.block_of[values] = (int) W.blocks.size();
-    W.blocks.push_back({values, size, pose_manifold ? 6 : size, pose_manifold, false, -1, false});
+    windows_.at((size_t) w).problem.addParameterBlock(values, size, pose_manifold);
 }
 
-void WindowSolverBatch::setParameterBlockConstant(int w, double *values) {
-    Window &W = windows_.at((size_t) w);
-    auto it   = W.block_of.find(values);
-    if (it == W.block_of.end()) throw std::runtime_error("WindowSolverBatch: unknown parameter block");
-    W.blocks[(size_t) it->second].constant = true;
-}
+void WindowSolverBatch::setParameterBlockConstant(int w, double *values) { windows_.at((size_t) w).problem.setParameterBlockConstant(values); }
 
 int WindowSolverBatch::addResidualBlock(int w, std::shared_ptr<ceres::CostFunction> cost, std::shared_ptr<ceres::LossFunction> loss,
                                         const std::vector<double *> &blocks) {
-    Window &W         = windows_.at((size_t) w);
-    const auto &sizes = cost->parameter_block_sizes();
-    if (sizes.size() != blocks.size()) throw std::runtime_error("WindowSolverBatch: block count does not match the cost function");
-    for (size_t k = 0; k < blocks.size(); k++) {
-        auto it = W.block_of.find(blocks[k]);
-        if (it == W.block_of.end()) throw std::runtime_error("WindowSolverBatch: residual block uses an unknown parameter block");
-        if (W.blocks[(size_t) it->second].size != sizes[k]) throw std::runtime_error("WindowSolverBatch: parameter block size mismatch");
-    }
-    W.residuals.push_back({std::move(cost), std::move(loss), blocks, false});
-    return (int) W.residuals.size() - 1;
+    return windows_.at((size_t) w).problem.addResidualBlock(std::move(cost), std::move(loss), blocks);
 }
 
 void WindowSolverBatch::addReprojectionFactor(int w, const ReprojectionFactor *factor, double *pose_i, double *pose_j, double *extrinsic, double *invdepth,
@@ -169,36 +150,11 @@ bool WindowSolverBatch::layout() {
     std::vector<std::string> errs(windows_.size());
     forEachWindow(windows_.size(), [&](size_t w) {
         Window &W = windows_[w];
-        for (Block &b : W.blocks) b.landmark = false, b.column = -1;
-        for (double *p : W.landmarks) {
-            auto it = W.block_of.find(p);
-            if (it == W.block_of.end() || W.blocks[(size_t) it->second].constant) {
-                errs[w] = "an inverse-depth block of a reprojection factor was not added to its window (or is constant)";
-                return;
-            }
-            W.blocks[(size_t) it->second].landmark = true;
-        }
-        for (const Residual &R : W.residuals)
-            if (!R.removed)
-                for (double *p : R.blocks)
-                    if (W.blocks[(size_t) W.block_of.at(p)].landmark) {
-                        errs[w] = "host factors on an eliminated inverse-depth block are not supported";
-                        return;
-                    }
-        W.P = 0;
-        for (Block &b : W.blocks)
-            if (!b.constant && !b.landmark) {
-                b.column = W.P;
-                W.P += b.local;
-            }
-        auto col = [&](const double *p) {
-            auto it = W.block_of.find(p);
-            if (it == W.block_of.end()) throw std::runtime_error("WindowSolverBatch: a block of a reprojection factor was not added to its window");
-            return W.blocks[(size_t) it->second].column;
-        };
-        for (size_t k = 0; k < W.poses.size(); k++) col_pose_[(size_t) W.pose_begin + k] = col(W.poses[k]);
-        if (W.ext) col_ext_[w] = col(W.ext);
-        if (W.td) col_td_[w] = col(W.td);
+        W.P       = W.problem.assignColumns(W.landmarks, &errs[w]);
+        if (W.P < 0) return;
+        for (size_t k = 0; k < W.poses.size(); k++) col_pose_[(size_t) W.pose_begin + k] = W.problem.column(W.poses[k]);
+        if (W.ext) col_ext_[w] = W.problem.column(W.ext);
+        if (W.td) col_td_[w] = W.problem.column(W.td);
     });
     for (size_t w = 0; w < windows_.size(); w++) {
         if (!errs[w].empty()) {
@@ -223,16 +179,6 @@ void WindowSolverBatch::gather(std::vector<double> &poses, std::vector<double> &
 }
 
 namespace {
-struct SideCall { // a call on the solver's side thread that is waited for on every way out of the scope
-    SideThread &t;
-    bool pending = true;
-    template <typename F> SideCall(SideThread &side, F &&f) : t(side) { t.start(std::forward<F>(f)); }
-    void join() {
-        if (pending) t.wait();
-        pending = false;
-    }
-    ~SideCall() { join(); }
-};
 struct BatchClock { // ICG_SOLVER_DEBUG=1: wall time per phase of the lock-step loop
     bool on = getenv("ICG_SOLVER_DEBUG") != nullptr;
     double ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -256,33 +202,17 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
     }
     const size_t NW = windows_.size();
     const int P     = P_;
-    // ICG_SOLVER_DEVICE_CHOLESKY=1: the reduced systems stay on the device and are factored there (batched Cholesky in LDS, P <= 88; the host
-    // factors' part goes up as packed lower triangles).  Built for VERDICT r2 item 7 and measured on MI355X, 256 C2 windows (P = 67), two
-    // solves: 26.5 ms against 21.1 ms for the default below — the factorization is not where the time goes (reduced solves 1.2 ms on 16 host
-    // threads vs 3.0 ms for device solve + back-substitution in one call) and the dense host part costs more on the way up (host phase
-    // 1.6 -> 4.3 ms) than the lower tiles it keeps from coming down; the assembly / reduction launches (6.2 ms) dominate either way.
-    // Default: the lower tiles of the reduced systems are read where the reduction kernel writes them (pinned memory) and every window is
-    // factored by a host thread (dense_kernels.cc).
-    const bool want_dev = getenv("ICG_SOLVER_DEVICE_CHOLESKY") != nullptr; // (read per solve: tests switch it)
-    const bool dev_solve       = want_dev && (size_t) P * P + (size_t) P <= (63 * 1024) / sizeof(double);
-    const size_t tri             = (size_t) P * (P + 1) / 2;
-    std::vector<int32_t> Pw_all(NW), upd_idx;
-    for (size_t w = 0; w < NW; w++) Pw_all[w] = windows_[w].P;
-    std::vector<uint8_t> want(NW), okv(NW);
-    std::vector<double> rhs_all, dd_all, packed;
-    if (dev_solve) rhs_all.assign((size_t) NW * P, 0.0), dd_all.assign((size_t) NW * P, 0.0);
+    // The reduced systems: their lower tiles are read where the reduction kernel writes them (pinned memory) and every window is factored by a
+    // host thread (dense_kernels.cc).  A batched Cholesky on the device lost to this on MI355X, 256 C2 windows (P = 67), two solves: 26.5 ms
+    // against 21.1 ms.
     struct State {
-        double radius, dec, cost, new_cost, model;
+        solver_detail::TrustRegion tr;
+        double model;
         bool done, relinearize, redamp, stepped;
         int iters;
         std::vector<double> s, diag, delta_c, dd;
     };
-    std::vector<State> st(NW);
-    std::vector<Summary> sum(NW);
-    for (size_t w = 0; w < NW; w++) {
-        st[w] = State{o.initial_trust_region_radius, 2.0, 0, 0, 0, false, true, false, false, 0, {}, {}, {}, {}};
-        sum[w].termination = "max_num_iterations";
-    }
+    std::vector<State> st(NW, State{solver_detail::TrustRegion(o), 0, false, true, false, false, 0, {}, {}, {}, {}});
     std::vector<double> poses, ext, inv, td, s((size_t) NW * P), diag((size_t) NW * P), cost(NW), delta_c((size_t) NW * P), delta_l((size_t) n_lm_),
         terms(2 * NW), damp(NW);
     const double *S = nullptr; // W x P x P reduced systems, left in the context's pinned staging memory by the reduction kernel (valid until
@@ -299,7 +229,7 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
         bool any_lin = false, any_sys = false;
         for (size_t w = 0; w < NW; w++) {
             reassemble[w] = (!st[w].done && st[w].relinearize) ? 1 : 0;
-            damp[w]       = 1.0 / st[w].radius;
+            damp[w]       = 1.0 / st[w].tr.radius;
             any_lin |= reassemble[w] != 0;
             any_sys |= !st[w].done && (st[w].relinearize || st[w].redamp);
         }
@@ -319,10 +249,8 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
             int dev_rc = ICG_OK;
             if (!side_) side_.reset(new SideThread());
             SideCall dev(*side_, [&] {
-                dev_rc = dev_solve ? icg_reproj_schur_windows_resident(ctx_, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), reassemble.data(),
-                                                                       damp.data(), o.min_lm_diagonal, o.max_lm_diagonal, s.data(), diag.data(), cost.data())
-                                   : icg_reproj_schur_windows_view(ctx_, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), reassemble.data(),
-                                                                   damp.data(), o.min_lm_diagonal, o.max_lm_diagonal, &S, s.data(), diag.data(), cost.data());
+                dev_rc = icg_reproj_schur_windows_view(ctx_, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), reassemble.data(), damp.data(),
+                                                       o.min_lm_diagonal, o.max_lm_diagonal, &S, s.data(), diag.data(), cost.data());
             });
             std::atomic<int> host_failed{0};
             host_cost.assign(NW, 0.0);
@@ -330,97 +258,63 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
                 if (st[w].done || !st[w].relinearize) return;
                 Window &W = windows_[w];
                 W.host_S.assign((size_t) P * P, 0.0), W.host_s.assign((size_t) P, 0.0), W.host_diag.assign((size_t) P, 0.0);
-                if (!solver_detail::hostFactors(W.blocks, W.block_of, W.residuals, P, W.host_S.data(), W.host_s.data(), W.host_diag.data(), &host_cost[w])) host_failed++;
+                if (!solver_detail::hostFactors(W.problem, P, W.host_S.data(), W.host_s.data(), W.host_diag.data(), &host_cost[w])) host_failed++;
             });
             clk.stop(2);
             clk.start();
             dev.join();
             clk.stop(1); // (what is left of the device call once the host half is through)
-            if (dev_rc != ICG_OK) return fail(dev_solve ? "icg_reproj_schur_windows_resident" : "icg_reproj_schur_windows_view");
+            if (dev_rc != ICG_OK) return fail("icg_reproj_schur_windows_view");
             if (host_failed.load()) {
                 error_ = "a host cost function failed to evaluate";
                 return false;
             }
             clk.start();
             forEachWindow(NW, [&](size_t w) {
-                if (st[w].done || !(st[w].relinearize || st[w].redamp)) return;
+                State &T = st[w];
+                if (T.done || !(T.relinearize || T.redamp)) return;
                 Window &W = windows_[w];
                 // the cost at the linearization point initialises the window on the first pass; afterwards it equals the accepted
                 // trial cost and is kept (the same bookkeeping as WindowSolver)
-                if (st[w].relinearize && first) st[w].cost = cost[w] + host_cost[w], sum[w].initial_cost = st[w].cost;
+                if (T.relinearize && first) T.tr.cost = cost[w] + host_cost[w], T.tr.summary.initial_cost = T.tr.cost;
                 // the window's reduced system is used where it arrived (S, s, diag of the batched call) plus the host factors' part: no
                 // per-window copy of the P x P block (9 MB per step at 256 windows)
-                st[w].s.resize((size_t) P), st[w].diag.resize((size_t) P);
+                T.s.resize((size_t) P), T.diag.resize((size_t) P);
                 for (int k = 0; k < P; k++) {
-                    st[w].s[(size_t) k]    = s[w * P + (size_t) k] + W.host_s[(size_t) k];
-                    st[w].diag[(size_t) k] = diag[w * P + (size_t) k] + W.host_diag[(size_t) k];
+                    T.s[(size_t) k]    = s[w * P + (size_t) k] + W.host_s[(size_t) k];
+                    T.diag[(size_t) k] = diag[w * P + (size_t) k] + W.host_diag[(size_t) k];
                 }
-                st[w].relinearize = st[w].redamp = false;
+                T.relinearize = T.redamp = false;
             });
-            if (dev_solve) { // the host factors' part of every window that was just linearized: packed lower triangles, one upload
-                upd_idx.clear();
-                for (size_t w = 0; w < NW; w++)
-                    if (reassemble[w]) upd_idx.push_back((int32_t) w);
-                if (!upd_idx.empty()) {
-                    packed.resize(upd_idx.size() * tri);
-                    forEachWindow(upd_idx.size(), [&](size_t k) {
-                        const double *Hw = windows_[(size_t) upd_idx[k]].host_S.data();
-                        double *dst      = &packed[k * tri];
-                        for (int i = 0; i < P; i++) {
-                            memcpy(dst, Hw + (size_t) i * P, sizeof(double) * (size_t) (i + 1));
-                            dst += i + 1;
-                        }
-                    });
-                    if (icg_reproj_set_host_part_windows(ctx_, P, (int) upd_idx.size(), upd_idx.data(), packed.data()) != ICG_OK)
-                        return fail("icg_reproj_set_host_part_windows");
-                }
-            }
             clk.stop(2);
         }
         first = false;
         // ---- every open window: iteration budget, gradient test, reduced solve ----------------------------------------------------
         clk.start();
         std::fill(delta_c.begin(), delta_c.end(), 0.0);
-        auto failed_factorization = [&](size_t w) { // dense_kernels.cc choleskySolve returned false / the device found a non-positive pivot
-            State &T = st[w];
-            T.radius /= T.dec, T.dec *= 2.0;
-            sum[w].num_unsuccessful_steps++;
-            T.redamp = true;
-            if (T.radius < o.min_trust_region_radius) sum[w].termination = "min_trust_region_radius", T.done = true;
-        };
         forEachWindow(NW, [&](size_t w) {
-            State &T = st[w];
+            State &T  = st[w];
             T.stepped = false;
-            want[w]   = 0;
             if (T.done) return;
             if (T.iters >= o.max_num_iterations) {
                 T.done = true;
                 return;
             }
             T.iters++;
-            double gmax = 0;
-            for (double v : T.s) gmax = std::max(gmax, std::fabs(v));
-            if (gmax < o.gradient_tolerance) {
-                sum[w].termination = "gradient_tolerance";
-                T.done             = true;
+            if (T.tr.gradientConverged(o, T.s)) {
+                T.done = true;
                 return;
             }
-            T.dd.assign((size_t) P, 0.0);
             const int Pw = windows_[w].P; // columns beyond Pw are empty (zero rows): solve the leading block only
-            for (int k = 0; k < Pw; k++) T.dd[(size_t) k] = std::min(std::max(T.diag[(size_t) k], o.min_lm_diagonal), o.max_lm_diagonal) / T.radius;
-            if (dev_solve) {
-                memcpy(&rhs_all[w * (size_t) P], T.s.data(), sizeof(double) * (size_t) P);
-                memcpy(&dd_all[w * (size_t) P], T.dd.data(), sizeof(double) * (size_t) P);
-                want[w] = 1;
-                return;
-            }
+            T.tr.damp(o, T.diag, Pw, T.dd);
             std::vector<double> Ab((size_t) Pw * Pw), bb(T.s.begin(), T.s.begin() + Pw);
             const double *Sw = &S[w * (size_t) P * P], *Hw = windows_[w].host_S.data();
             for (int i = 0; i < Pw; i++) // lower triangle: what the view holds and what choleskySolve reads
                 for (int j = 0; j <= i; j++) Ab[(size_t) i * Pw + j] = Sw[(size_t) i * P + j] + Hw[(size_t) i * P + j];
             for (int k = 0; k < Pw; k++) Ab[(size_t) k * Pw + k] += T.dd[(size_t) k];
             if (!choleskySolve(Pw, Ab, bb)) {
-                failed_factorization(w);
+                T.redamp = true;
+                T.done   = T.tr.reject(o);
                 return;
             }
             T.delta_c.assign((size_t) P, 0.0);
@@ -428,34 +322,14 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
             std::copy(T.delta_c.begin(), T.delta_c.end(), delta_c.begin() + (long) (w * P));
             T.stepped = true;
         });
-        bool any_step = false, any_want = false;
-        for (size_t w = 0; w < NW; w++) any_want |= want[w] != 0;
-        bool backsub_done = false;
-        if (dev_solve && any_want) {
-            // batched factorization + solve + landmark back-substitution in one call; the systems never leave the device
-            if (icg_reproj_solve_backsub_windows(ctx_, P, Pw_all.data(), want.data(), rhs_all.data(), dd_all.data(), delta_c.data(), okv.data(),
-                                                 n_lm_ > 0 ? delta_l.data() : nullptr, terms.data()) != ICG_OK)
-                return fail("icg_reproj_solve_backsub_windows");
-            backsub_done = true;
-            for (size_t w = 0; w < NW; w++) {
-                if (!want[w]) continue;
-                if (!okv[w]) {
-                    failed_factorization(w);
-                    continue;
-                }
-                st[w].delta_c.assign(delta_c.begin() + (long) (w * P), delta_c.begin() + (long) ((w + 1) * P));
-                st[w].stepped = true;
-            }
-        }
-        for (size_t w = 0; w < NW; w++) any_step |= st[w].stepped;
+        bool any_step = false, all_done = true;
+        for (size_t w = 0; w < NW; w++) any_step |= st[w].stepped, all_done &= st[w].done;
         clk.stop(3);
-        bool all_done = true;
-        for (size_t w = 0; w < NW; w++) all_done &= st[w].done;
         if (all_done) break;
         if (!any_step) continue; // only re-damping this round
         // ---- landmark back-substitution for all windows, model decrease, trial points ---------------------------------------------
         clk.start();
-        if (!backsub_done && n_lm_ > 0 && icg_reproj_backsub_windows(ctx_, P, delta_c.data(), delta_l.data(), terms.data()) != ICG_OK)
+        if (n_lm_ > 0 && icg_reproj_backsub_windows(ctx_, P, delta_c.data(), delta_l.data(), terms.data()) != ICG_OK)
             return fail("icg_reproj_backsub_windows");
         clk.stop(4);
         clk.start();
@@ -463,37 +337,18 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
             State &T = st[w];
             if (!T.stepped) return;
             Window &W = windows_[w];
-            double t0 = terms[2 * w], t1 = terms[2 * w + 1];
-            for (int k = 0; k < P; k++) t0 += T.delta_c[(size_t) k] * T.s[(size_t) k], t1 += T.dd[(size_t) k] * T.delta_c[(size_t) k] * T.delta_c[(size_t) k];
-            T.model = 0.5 * (t0 + t1);
+            T.model   = solver_detail::TrustRegion::modelDecrease(&terms[2 * w], T.delta_c, T.s, T.dd);
             if (!(T.model > 0.0)) {
-                T.radius /= T.dec, T.dec *= 2.0;
-                sum[w].num_unsuccessful_steps++;
                 T.redamp = true, T.stepped = false;
-                if (T.radius < o.min_trust_region_radius) sum[w].termination = "min_trust_region_radius", T.done = true;
+                T.done   = T.tr.reject(o);
                 return;
             }
-            double dn = 0, xn = 0;
-            for (double v : T.delta_c) dn += v * v;
-            for (size_t k = 0; k < W.landmarks.size(); k++) dn += delta_l[(size_t) W.lm_begin + k] * delta_l[(size_t) W.lm_begin + k];
-            for (const Block &b : W.blocks)
-                if (!b.constant)
-                    for (int k = 0; k < b.size; k++) xn += b.values[k] * b.values[k];
-            if (std::sqrt(dn) <= o.parameter_tolerance * (std::sqrt(xn) + o.parameter_tolerance)) {
-                sum[w].termination = "parameter_tolerance";
+            if (T.tr.parameterConverged(o, W.problem, T.delta_c, delta_l.data() + W.lm_begin, W.landmarks.size())) {
                 T.done = true, T.stepped = false;
                 return;
             }
-            W.saved.resize(W.blocks.size());
-            for (size_t k = 0; k < W.blocks.size(); k++) W.saved[k].assign(W.blocks[k].values, W.blocks[k].values + W.blocks[k].size);
-            for (Block &b : W.blocks) {
-                if (b.column < 0) continue;
-                const double *d = &T.delta_c[(size_t) b.column];
-                if (b.pose)
-                    posePlus(b.values, d);
-                else
-                    for (int k = 0; k < b.size; k++) b.values[k] += d[k];
-            }
+            W.problem.backup();
+            W.problem.applyCameraStep(T.delta_c.data());
             for (size_t k = 0; k < W.landmarks.size(); k++) *W.landmarks[k] += delta_l[(size_t) W.lm_begin + k];
         });
         bool any_trial = false;
@@ -515,8 +370,7 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
         host_cost.assign(NW, 0.0);
         forEachWindow(NW, [&](size_t w) {
             if (!st[w].stepped) return;
-            Window &W = windows_[w];
-            if (!solver_detail::hostFactors(W.blocks, W.block_of, W.residuals, P, nullptr, nullptr, nullptr, &host_cost[w])) trial_failed++;
+            if (!solver_detail::hostFactors(windows_[w].problem, P, nullptr, nullptr, nullptr, &host_cost[w])) trial_failed++;
         });
         trial.join();
         if (dev_fail) return fail(dev_fail);
@@ -524,31 +378,13 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
         clk.start();
         forEachWindow(NW, [&](size_t w) {
             State &T = st[w];
-            if (!T.stepped) return;
-            Window &W = windows_[w];
-            const double hc = host_cost[w];
-            if (trial_failed.load()) return;
-            T.new_cost       = cost[w] + hc;
-            const double rho = (T.cost - T.new_cost) / T.model;
-            if (rho > o.min_relative_decrease) {
-                const double change = T.cost - T.new_cost;
-                T.cost              = T.new_cost;
-                sum[w].num_successful_steps++;
-                T.radius = std::min(o.max_trust_region_radius, T.radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
-                T.dec    = 2.0;
-                if (std::fabs(change) < o.function_tolerance * T.cost) {
-                    sum[w].termination = "function_tolerance";
-                    T.done             = true;
-                } else {
-                    T.relinearize = true;
-                }
-            } else {
-                for (size_t k = 0; k < W.blocks.size(); k++) memcpy(W.blocks[k].values, W.saved[k].data(), sizeof(double) * (size_t) W.blocks[k].size);
-                T.radius /= T.dec, T.dec *= 2.0;
-                sum[w].num_unsuccessful_steps++;
+            if (!T.stepped || trial_failed.load()) return;
+            bool accepted;
+            T.done = T.tr.trial(o, cost[w] + host_cost[w], T.model, windows_[w].problem, &accepted);
+            if (accepted)
+                T.relinearize = !T.done;
+            else
                 T.redamp = true;
-                if (T.radius < o.min_trust_region_radius) sum[w].termination = "min_trust_region_radius", T.done = true;
-            }
         });
         if (trial_failed.load()) {
             error_ = "a host cost function failed to evaluate";
@@ -561,8 +397,10 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
                         "trial eval+cost %.2f, trial host %.2f ms; whole solve %.2f ms\n",
                 NW, clk.ms[0], clk.ms[1], clk.ms[2], clk.ms[3], clk.ms[4], clk.ms[5], clk.ms[6], clk.ms[7],
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_solve).count());
-    for (size_t w = 0; w < NW; w++) sum[w].final_cost = st[w].cost;
-    if (summaries) *summaries = sum;
+    if (summaries) {
+        summaries->resize(NW);
+        for (size_t w = 0; w < NW; w++) (*summaries)[w] = st[w].tr.summary, (*summaries)[w].final_cost = st[w].tr.cost;
+    }
     return true;
 }
 

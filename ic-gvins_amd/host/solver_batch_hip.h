@@ -4,8 +4,9 @@
 // WindowSolverBatch advances the LM iterations of W independent windows in lock-step on ONE device context: per iteration one
 // evaluation launch for the reprojection factors of all windows, one assembly + elimination launch sequence, one back-substitution
 // launch; each window keeps its own trust-region radius, accepts or rejects its own step and stops by its own tolerances, exactly as
-// a WindowSolver of its own would (tests: identical step sequences and optima).  Host-evaluated factors (preintegration,
-// marginalization prior, priors) and the P x P reduced solves stay per window on the host.
+// a WindowSolver of its own would (tests: identical step sequences and optima): the problem model, the column layout and the step rule of
+// a window are solver_detail.h's, shared with WindowSolver; the lock-step schedule is this class's own.  Host-evaluated factors
+// (preintegration, marginalization prior, priors) and the P x P reduced solves stay per window on the host.
 #pragma once
 #include <memory>
 #include <string>
@@ -22,8 +23,9 @@ public:
     typedef WindowSolver::Options Options;
     typedef WindowSolver::Summary Summary;
     // Widest reduced system of the device path: the assembly (csrc/reproj.hip k_asm_*) keeps no per-window tile in LDS any more — rounds 2-5
-    // held the camera block there (82, then 138 columns) — and the reduction kernel stages 32 landmark rows of 4 ceil(P/4) doubles (64.5 KB at
-    // 512).  A window that can exceed it is the caller's to solve on the host.
+    // held the camera block there (82, then 138 columns).  The reduction kernel k_schur_reduce_w stages its landmark rows of 4 ceil(P/4)
+    // doubles in SCH_PRE * 256 = 3 072 elements per pass (at least one row up to P = 3 072) and keeps two entries of s per thread (t and
+    // t + 256): P <= 512.  A window that can exceed it is the caller's to solve on the host.
     static constexpr int kMaxCameraColumns = 512;
 
     // host_threads: the per-window host phases (host factors, reduced solves, cost bookkeeping) are spread over this many threads
@@ -55,23 +57,18 @@ public:
     const std::string &error() const { return error_; }
 
 private:
-    typedef solver_detail::Block Block;
-    typedef solver_detail::Residual Residual;
     struct VisualFactor {
         double obs[15];
         double *pose_i, *pose_j, *invdepth;
     };
     struct Window {
-        std::vector<Block> blocks;
-        std::unordered_map<const double *, int> block_of;
-        std::vector<Residual> residuals;
+        solver_detail::Problem problem{"WindowSolverBatch"};
         std::vector<VisualFactor> visual;
         double *ext{nullptr}, *td{nullptr};
         std::vector<double *> poses, landmarks; // first-seen order of the visual factors
         std::unordered_map<const double *, int> pose_index, lm_index;
         int P{0};
         int fac_begin{0}, lm_begin{0}, pose_begin{0};
-        std::vector<std::vector<double>> saved;
         std::vector<double> host_S, host_s, host_diag;
     };
     bool finalize();

@@ -1,8 +1,14 @@
-// Pieces shared by WindowSolver (solver_hip.cc) and WindowSolverBatch (solver_batch_hip.cc): the reduced-system solve, the pose
-// manifold step and the accumulation of host-evaluated factors into a window's reduced system.
+// The core shared by WindowSolver (solver_hip.cc) and WindowSolverBatch (solver_batch_hip.cc), which differ only in how they schedule the
+// device and host work of an LM step: the problem model of one window (parameter and residual blocks, the column layout of its reduced
+// camera system, backup / step / restore of the parameters: Problem), the trust-region rule of one window (TrustRegion), the pose manifold
+// step, the reduced-system solve and the accumulation of host-evaluated factors into a window's reduced system.
 #pragma once
+#include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <memory>
+#include <stdexcept>
+#include <string>
 #include <unordered_map>
 #include <vector>
 
@@ -10,6 +16,19 @@
 
 namespace icg {
 namespace solver_detail {
+
+struct Options {
+    int max_num_iterations{50};
+    double initial_trust_region_radius{1e4}, max_trust_region_radius{1e16}, min_trust_region_radius{1e-32};
+    double min_relative_decrease{1e-3}, min_lm_diagonal{1e-6}, max_lm_diagonal{1e32};
+    double function_tolerance{1e-6}, gradient_tolerance{1e-10}, parameter_tolerance{1e-8};
+};
+struct Summary {
+    double initial_cost{0}, final_cost{0};
+    int num_successful_steps{0}, num_unsuccessful_steps{0};
+    std::string termination;
+    std::string BriefReport() const;
+};
 
 struct Block {
     double *values;
@@ -63,11 +82,174 @@ inline bool residualCost(const Residual &R, bool apply_loss_function, double *co
     return true;
 }
 
+// The problem of one window: problem.AddParameterBlock / SetParameterBlockConstant / AddResidualBlock / EvaluateResidualBlock for the
+// host-evaluated factors, the column layout of the reduced camera system and the step of its parameters.  `owner` prefixes the messages.
+struct Problem {
+    const char *owner;
+    std::vector<Block> blocks;
+    std::unordered_map<const double *, int> block_of;
+    std::vector<Residual> residuals;
+    std::vector<std::vector<double>> saved; // backup()
+
+    explicit Problem(const char *owner_) : owner(owner_) {}
+    [[noreturn]] void fail(const char *what) const { throw std::runtime_error(std::string(owner) + ": " + what); }
+
+    // pose blocks are [p3, q4 xyzw], tangent size 6
+    void addParameterBlock(double *values, int size, bool pose_manifold) {
+        if (block_of.count(values)) return;
+        if (pose_manifold && size != 7) fail("the pose manifold needs a block of size 7");
+        block_of[values] = (int) blocks.size();
+        blocks.push_back({values, size, pose_manifold ? 6 : size, pose_manifold, false, -1, false});
+    }
+    void setParameterBlockConstant(double *values) {
+        auto it = block_of.find(values);
+        if (it == block_of.end()) fail("unknown parameter block");
+        blocks[(size_t) it->second].constant = true;
+    }
+    int addResidualBlock(std::shared_ptr<ceres::CostFunction> cost, std::shared_ptr<ceres::LossFunction> loss, const std::vector<double *> &ptrs) {
+        const auto &sizes = cost->parameter_block_sizes();
+        if (sizes.size() != ptrs.size()) fail("block count does not match the cost function");
+        for (size_t k = 0; k < ptrs.size(); k++) {
+            auto it = block_of.find(ptrs[k]);
+            if (it == block_of.end()) fail("residual block uses an unknown parameter block");
+            if (blocks[(size_t) it->second].size != sizes[k]) fail("parameter block size mismatch");
+        }
+        residuals.push_back({std::move(cost), std::move(loss), ptrs, false});
+        return (int) residuals.size() - 1;
+    }
+    void removeResidualBlock(int id) { residuals.at((size_t) id).removed = true; }
+    bool evaluateResidualBlock(int id, bool apply_loss_function, double *cost) const {
+        return residualCost(residuals.at((size_t) id), apply_loss_function, cost);
+    }
+
+    // Column layout of the reduced system: the inverse-depth blocks of the visual factors (`landmarks`) are marked, they are eliminated
+    // on the device; every other non-constant block gets the next columns, in the order the blocks were added.  -> P, or -1 and *error.
+    int assignColumns(const std::vector<double *> &landmarks, std::string *error) {
+        for (Block &b : blocks) b.landmark = false, b.column = -1;
+        for (double *p : landmarks) {
+            auto it = block_of.find(p);
+            if (it == block_of.end()) return *error = "an inverse-depth block of a reprojection factor was not added to the solver", -1;
+            if (blocks[(size_t) it->second].constant) return *error = "constant inverse-depth blocks are not supported", -1;
+            blocks[(size_t) it->second].landmark = true;
+        }
+        for (const Residual &R : residuals)
+            if (!R.removed)
+                for (double *p : R.blocks)
+                    if (blocks[(size_t) block_of.at(p)].landmark) return *error = "host factors on an eliminated inverse-depth block are not supported", -1;
+        int P = 0;
+        for (Block &b : blocks)
+            if (!b.constant && !b.landmark) {
+                b.column = P;
+                P += b.local;
+            }
+        return P;
+    }
+    // the column of a block of a visual factor (after assignColumns)
+    int column(const double *p) const {
+        auto it = block_of.find(p);
+        if (it == block_of.end()) fail("a block of a reprojection factor was not added to the solver");
+        return blocks[(size_t) it->second].column;
+    }
+
+    void backup() {
+        saved.resize(blocks.size());
+        for (size_t k = 0; k < blocks.size(); k++) saved[k].assign(blocks[k].values, blocks[k].values + blocks[k].size);
+    }
+    void restore() {
+        for (size_t k = 0; k < blocks.size(); k++) memcpy(blocks[k].values, saved[k].data(), sizeof(double) * (size_t) blocks[k].size);
+    }
+    // x = x [+] delta_c on the blocks with a column; the caller steps the eliminated inverse depths
+    void applyCameraStep(const double *delta_c) {
+        for (Block &b : blocks) {
+            if (b.column < 0) continue;
+            const double *d = &delta_c[(size_t) b.column];
+            if (b.pose)
+                posePlus(b.values, d);
+            else
+                for (int k = 0; k < b.size; k++) b.values[k] += d[k];
+        }
+    }
+};
+
+// The step rule of one window (solver_hip.h: the Ceres trust-region loop without Jacobi scaling).  The callers decide when to relinearize
+// and when to re-damp; every function that can end the solve sets the summary's termination and returns true when it does.
+struct TrustRegion {
+    double radius, decrease_factor{2.0}, cost{0};
+    Summary summary;
+    explicit TrustRegion(const Options &o) : radius(o.initial_trust_region_radius) { summary.termination = "max_num_iterations"; }
+
+    // dd (the size of diag) = the LM diagonal clamp(diag, min, max) / radius on the leading n columns, zero beyond
+    void damp(const Options &o, const std::vector<double> &diag, int n, std::vector<double> &dd) const {
+        dd.assign(diag.size(), 0.0);
+        for (int k = 0; k < n; k++) dd[(size_t) k] = std::min(std::max(diag[(size_t) k], o.min_lm_diagonal), o.max_lm_diagonal) / radius;
+    }
+    // max norm of J^T r over the camera columns (the landmark part is bounded by it after elimination in practice and is not fetched)
+    bool gradientConverged(const Options &o, const std::vector<double> &s) {
+        double gmax = 0;
+        for (double v : s) gmax = std::max(gmax, std::fabs(v));
+        if (gmax < o.gradient_tolerance) {
+            summary.termination = "gradient_tolerance";
+            return true;
+        }
+        return false;
+    }
+    // an unsuccessful step (failed factorization, non-positive model decrease, rejected trial point)
+    bool reject(const Options &o) {
+        radius /= decrease_factor;
+        decrease_factor *= 2.0;
+        summary.num_unsuccessful_steps++;
+        if (radius < o.min_trust_region_radius) {
+            summary.termination = "min_trust_region_radius";
+            return true;
+        }
+        return false;
+    }
+    // model decrease 0.5 (delta^T b + delta^T D delta) of the FULL damped system; s is the reduced right-hand side, and
+    // delta^T b = delta_c^T s + sum b_l^2/(h_ll+d_l) (lm_terms[0], device), delta^T D delta = delta_c^T Dc delta_c + sum d_l delta_l^2 (lm_terms[1])
+    static double modelDecrease(const double *lm_terms, const std::vector<double> &delta_c, const std::vector<double> &s, const std::vector<double> &dd) {
+        double t0 = lm_terms[0], t1 = lm_terms[1];
+        for (size_t k = 0; k < delta_c.size(); k++) t0 += delta_c[k] * s[k], t1 += dd[k] * delta_c[k] * delta_c[k];
+        return 0.5 * (t0 + t1);
+    }
+    // |delta| <= tol (|x| + tol), x the free blocks of the problem before the step, delta the camera step and the window's n_l landmark steps
+    bool parameterConverged(const Options &o, const Problem &p, const std::vector<double> &delta_c, const double *delta_l, size_t n_l) {
+        double dn = 0, xn = 0;
+        for (double v : delta_c) dn += v * v;
+        for (size_t k = 0; k < n_l; k++) dn += delta_l[k] * delta_l[k];
+        for (const Block &b : p.blocks)
+            if (!b.constant)
+                for (int k = 0; k < b.size; k++) xn += b.values[k] * b.values[k];
+        if (std::sqrt(dn) <= o.parameter_tolerance * (std::sqrt(xn) + o.parameter_tolerance)) {
+            summary.termination = "parameter_tolerance";
+            return true;
+        }
+        return false;
+    }
+    // the cost at the trial point decides: *accepted (the radius grows) or rejected (p.restore(), then reject())
+    bool trial(const Options &o, double new_cost, double model, Problem &p, bool *accepted) {
+        const double rho = (cost - new_cost) / model;
+        *accepted        = rho > o.min_relative_decrease;
+        if (!*accepted) {
+            p.restore();
+            return reject(o);
+        }
+        const double change = cost - new_cost;
+        cost                = new_cost;
+        summary.num_successful_steps++;
+        radius          = std::min(o.max_trust_region_radius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3)));
+        decrease_factor = 2.0;
+        if (std::fabs(change) < o.function_tolerance * cost) {
+            summary.termination = "function_tolerance";
+            return true;
+        }
+        return false;
+    }
+};
+
 // host factors of one window: S += J^T J, s -= J^T r (robust-corrected), diag, cost += 0.5 rho(|r|^2); S == nullptr: cost only.
 // S is P x P with row stride P.
-inline bool hostFactors(const std::vector<Block> &blocks, const std::unordered_map<const double *, int> &block_of, const std::vector<Residual> &residuals,
-                        int P, double *S, double *s, double *diag, double *cost) {
-    for (const Residual &R : residuals) {
+inline bool hostFactors(const Problem &p, int P, double *S, double *s, double *diag, double *cost) {
+    for (const Residual &R : p.residuals) {
         if (R.removed) continue;
         if (!S) {
             double c;
@@ -98,7 +280,7 @@ inline bool hostFactors(const std::vector<Block> &blocks, const std::unordered_m
         thread_local std::vector<int> cols;
         cols.clear();
         for (size_t a = 0; a < R.blocks.size(); a++) {
-            const Block &A = blocks[(size_t) block_of.at(R.blocks[a])];
+            const Block &A = p.blocks[(size_t) p.block_of.at(R.blocks[a])];
             if (A.column < 0) continue;
             for (int x = 0; x < A.local; x++) cols.push_back(A.column + x);
         }
@@ -108,7 +290,7 @@ inline bool hostFactors(const std::vector<Block> &blocks, const std::unordered_m
         {
             int c0 = 0;
             for (size_t a = 0; a < R.blocks.size(); a++) {
-                const Block &A = blocks[(size_t) block_of.at(R.blocks[a])];
+                const Block &A = p.blocks[(size_t) p.block_of.at(R.blocks[a])];
                 if (A.column < 0) continue;
                 const std::vector<double> &Ja = info.jacobians()[a];
                 for (int k = 0; k < nr; k++)

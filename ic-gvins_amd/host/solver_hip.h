@@ -15,7 +15,8 @@
 // radius / max(1/3, 1 - (2 rho - 1)^3) on success, halving with a doubling factor on failure, function / gradient / parameter
 // tolerances 1e-6 / 1e-10 / 1e-8) without Jacobi column scaling; iterates therefore agree with Ceres only to the extent LM
 // implementations do — "parity unpinned" for this row, stated in DESIGN.md.  No CPU fallback for the visual part: a device error
-// fails the solve.
+// fails the solve.  The problem model, the column layout and the step rule are solver_detail.h's, shared with WindowSolverBatch; what
+// is WindowSolver's own is the schedule of one window on the caller's ReprojectionBatch (icg_reproj_schur / icg_reproj_backsub).
 #pragma once
 #include <memory>
 #include <string>
@@ -30,18 +31,8 @@ namespace icg {
 
 class WindowSolver {
 public:
-    struct Options {
-        int max_num_iterations{50};
-        double initial_trust_region_radius{1e4}, max_trust_region_radius{1e16}, min_trust_region_radius{1e-32};
-        double min_relative_decrease{1e-3}, min_lm_diagonal{1e-6}, max_lm_diagonal{1e32};
-        double function_tolerance{1e-6}, gradient_tolerance{1e-10}, parameter_tolerance{1e-8};
-    };
-    struct Summary {
-        double initial_cost{0}, final_cost{0};
-        int num_successful_steps{0}, num_unsuccessful_steps{0};
-        std::string termination;
-        std::string BriefReport() const;
-    };
+    typedef solver_detail::Options Options;
+    typedef solver_detail::Summary Summary;
     typedef int ResidualBlockId;
 
     // visual: the reprojection factors (may be null); huber_delta: their loss (ceres::HuberLoss(delta), 0 = none)
@@ -71,25 +62,17 @@ public:
     const std::string &error() const { return error_; }
 
 private:
-    typedef solver_detail::Block Block;
-    typedef solver_detail::Residual Residual;
     bool layout();
     bool linearize(double damp, bool reassemble, const Options &o, std::vector<double> &S, std::vector<double> &s, std::vector<double> &diag,
                    double *cost);
     bool evaluateCost(double *cost);
-    void applyStep(const std::vector<double> &delta_c, const std::vector<double> &delta_l);
-    void backup();
-    void restore();
 
     ReprojectionBatch *visual_;
     double huber_;
-    std::vector<Block> blocks_;
-    std::unordered_map<const double *, int> block_of_;
-    std::vector<Residual> residuals_;
+    solver_detail::Problem problem_{"WindowSolver"};
     std::vector<uint8_t> active_;
     std::vector<int32_t> col_pose_;
     int col_ext_{-1}, col_td_{-1}, P_{0};
-    std::vector<std::vector<double>> saved_;
     std::vector<double> host_S_, host_s_, host_diag_; // host factors' part of the current linearization (kept for re-damping)
     std::string error_;
 };

@@ -2,8 +2,8 @@
 the MI355X: tests/tools/switch_probe.py — tracker, window refinement, batched solver, batched marginalization — runs in a child process
 per environment, and every combination below must reproduce the digests of the clean environment bit for bit.  The switches that select
 an ENGINE or a solver path have their own tests (ICG_TRACK_ENGINE: test_gpu_device_tracker.py and the probe's second leg here;
-ICG_SOLVER_DEVICE_CHOLESKY: test_gpu_solver.py; ICG_LOCKSTEP_MARG_BATCH: test_gpu_zz_marg_batch.py; ICG_TRACKING_LOG_DIR:
-ref_tracking_utils.py; ICG_HOST_CHECK: conftest.py sets it for every test).  Kernel variants that used to hide behind switches
+ICG_LOCKSTEP_MARG_BATCH: test_gpu_zz_marg_batch.py; ICG_TRACKING_LOG_DIR: ref_tracking_utils.py; ICG_HOST_CHECK: conftest.py sets it
+for every test).  Kernel variants that used to hide behind switches
 (ICG_LK_PAIR, ICG_PYRAMID_TILES, ICG_CLAHE_LEGACY, ICG_LK_REUSE, ICG_RANSAC_DEVICE_LOOP, ICG_MARG_DENSE) were deleted in round 6."""
 import json
 import os
@@ -45,7 +45,7 @@ def switches_in_the_sources():
 
 
 def test_every_switch_of_the_product_is_covered():
-    covered = set(SCHEDULING) | set(DIAGNOSTICS) | {"ICG_TRACK_ENGINE", "ICG_SOLVER_DEVICE_CHOLESKY", "ICG_TRACKING_LOG_DIR", "ICG_HOST_CHECK"}
+    covered = set(SCHEDULING) | set(DIAGNOSTICS) | {"ICG_TRACK_ENGINE", "ICG_TRACKING_LOG_DIR", "ICG_HOST_CHECK"}
     assert switches_in_the_sources() <= covered, sorted(switches_in_the_sources() - covered)
 
 
