@@ -604,6 +604,44 @@ static int ensure_detect_ws(icg_ctx *ctx) {
     return 0;
 }
 
+// the checks every detection grid passes: icg_detect runs them on each call, the tracker once when it is created
+int icg_detect_check_grid(icg_ctx *ctx, const icg_detect_grid *grid) {
+    if (grid->block_cols * grid->block_rows <= 0 || grid->block_w <= 6 || grid->block_h <= 6 || grid->block_cols * grid->block_w > ctx->cfg.width ||
+        grid->block_rows * grid->block_h > ctx->cfg.height || grid->min_dist < 0 || grid->max_per_block <= 0 ||
+        grid->max_per_block > DET_MAX_PER_BLOCK || grid->min_dist > FE_MAX_RADIUS)
+        return icg_fail(ctx, ICG_ERR_INVALID, "bad detection grid");
+    return 0;
+}
+
+// min-eigenvalue response + NMS, selection, sub-pixel refinement of n_roi ROIs, asynchronous on the context's stream; d_roi_max / d_cand_cnt of
+// the context cover n_roi (ensure_roi_state), the picks and their counts are device scratch of n_roi * max_per_block / n_roi entries
+static int detect_launch(icg_ctx *ctx, int n_roi, const icg_detect_grid *grid, const det_roi *d_rois, const int32_t *d_slots, const float2 *d_mask_pts,
+                         const int32_t *d_mask_begin, const int32_t *d_mask_cnt, const int32_t *d_vh, float2 *d_picks, int32_t *d_pick_cnt,
+                         float2 *d_corners, int32_t *d_corner_cnt) {
+    const int w = ctx->cfg.width, h = ctx->cfg.height, pitch = ctx->lv[0].pitch, max_pb = grid->max_per_block;
+    const size_t cand_plane = (size_t) w * h;
+    {
+        icg_prof_scope ps(ctx, "detect_min_eig_nms");
+        const int gx = (grid->block_w + FE_TW - 1) / FE_TW, gy = (grid->block_h + FE_TH * FE_WAVES - 1) / (FE_TH * FE_WAVES);
+        hipLaunchKernelGGL(k_min_eig_nms, dim3(std::min(icg_xcd_grid((gx * gy * n_roi + FE_WAVES - 1) / FE_WAVES), 8 * FE_RESIDENT_PER_XCD)), dim3(64 * FE_WAVES), 0, ctx->stream, d_rois, ctx->d_frames,
+                           ctx->slot_bytes, d_slots, pitch, w, h, d_mask_pts, d_mask_begin, d_mask_cnt, grid->min_dist, d_vh, ctx->d_roi_max, ctx->d_cand,
+                           cand_plane, ctx->d_cand_cnt, gx, gy, gx * gy * n_roi, icg_div_magic(gx * gy), icg_div_magic(gx));
+    }
+    {
+        icg_prof_scope ps(ctx, "detect_select");
+        hipLaunchKernelGGL(k_select, dim3(n_roi), dim3(256), 0, ctx->stream, d_rois, ctx->d_cand, cand_plane, ctx->d_cand_cnt, ctx->d_roi_max, grid->min_dist,
+                           d_picks, d_pick_cnt, d_corner_cnt, max_pb);
+    }
+    {
+        const subpix_mask_t M = subpix_window();
+        icg_prof_scope ps(ctx, "detect_subpix");
+        hipLaunchKernelGGL(k_subpix, dim3(n_roi * max_pb), dim3(64), 0, ctx->stream, d_rois, ctx->d_frames, ctx->slot_bytes, d_slots, pitch,
+                           (const float2 *) d_picks, d_corners, (const int32_t *) d_pick_cnt, max_pb, M);
+    }
+    ICG_HIP(ctx, hipGetLastError());
+    return ICG_OK;
+}
+
 extern "C" int icg_detect(icg_ctx *ctx, int n, const int32_t *slots, const icg_detect_grid *grid, const int32_t *mask_off,
                           const float *mask_pts, const int32_t *quota, int max_per_job, float *out_pts,
                           int32_t *out_count, int32_t *out_block) {
@@ -611,19 +649,15 @@ extern "C" int icg_detect(icg_ctx *ctx, int n, const int32_t *slots, const icg_d
     if (n == 0) return ICG_OK;
     if (!slots || !grid || !mask_off || !quota || !out_pts || !out_count || max_per_job <= 0) return ICG_ERR_INVALID;
     if (n > ctx->cfg.max_batch) return icg_fail(ctx, ICG_ERR_CAPACITY, "detect batch %d > max_batch %d", n, ctx->cfg.max_batch);
-    const int w = ctx->cfg.width, h = ctx->cfg.height, pitch = ctx->lv[0].pitch;
+    int rc = icg_detect_check_grid(ctx, grid);
+    if (rc) return rc;
     const int nblk = grid->block_cols * grid->block_rows;
-    if (nblk <= 0 || grid->block_w <= 6 || grid->block_h <= 6 || grid->block_cols * grid->block_w > w ||
-        grid->block_rows * grid->block_h > h || grid->min_dist < 0 || grid->max_per_block <= 0 ||
-        grid->max_per_block > DET_MAX_PER_BLOCK || grid->min_dist > FE_MAX_RADIUS)
-        return icg_fail(ctx, ICG_ERR_INVALID, "bad detection grid");
     for (int k = 0; k < n; k++)
         if (slots[k] < 0 || slots[k] >= ctx->cfg.n_slots) return icg_fail(ctx, ICG_ERR_INVALID, "bad slot");
     const int n_mask = mask_off[n];
     if (n_mask < 0 || (n_mask > 0 && !mask_pts)) return ICG_ERR_INVALID;
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    int rc = ensure_detect_ws(ctx);
-    if (rc) return rc;
+    if ((rc = ensure_detect_ws(ctx))) return rc;
 
     // ROI list (tracking.cc:629-645)
     std::vector<det_roi> rois;
@@ -677,8 +711,6 @@ extern "C" int icg_detect(icg_ctx *ctx, int n, const int32_t *slots, const icg_d
     const int32_t *d_mcnt  = c.in(mcnt.data(), (size_t) n);
     // [roi_max | cand_cnt] per ROI live in the context and are zero between calls (k_select clears the entries it consumed)
     if ((rc = ensure_roi_state(ctx, n_roi))) return rc;
-    unsigned int *d_rmax = ctx->d_roi_max;
-    int32_t *d_ccnt      = ctx->d_cand_cnt;
     if ((rc = c.seal())) return rc;
     std::vector<float> h_corners((size_t) n_roi * max_pb * 2);
     std::vector<int32_t> h_cnt((size_t) n_roi);
@@ -689,27 +721,8 @@ extern "C" int icg_detect(icg_ctx *ctx, int n, const int32_t *slots, const icg_d
     float2 *z_corners  = (float2 *) c.out_zc(h_corners.data(), (size_t) n_roi * max_pb * 2);
     int32_t *z_cnt     = c.out_zc(h_cnt.data(), (size_t) n_roi);
 
-    const size_t cand_plane = (size_t) w * h;
     ICG_LAUNCH_GUARD(c);
-    {
-        icg_prof_scope ps(ctx, "detect_min_eig_nms");
-        const int gx = (grid->block_w + FE_TW - 1) / FE_TW, gy = (grid->block_h + FE_TH * FE_WAVES - 1) / (FE_TH * FE_WAVES);
-        hipLaunchKernelGGL(k_min_eig_nms, dim3(std::min(icg_xcd_grid((gx * gy * n_roi + FE_WAVES - 1) / FE_WAVES), 8 * FE_RESIDENT_PER_XCD)), dim3(64 * FE_WAVES), 0, ctx->stream, d_rois, ctx->d_frames,
-                           ctx->slot_bytes, d_slots, pitch, w, h, d_mpts, d_moff, d_mcnt, grid->min_dist, d_vh, d_rmax, ctx->d_cand, cand_plane, d_ccnt,
-                           gx, gy, gx * gy * n_roi, icg_div_magic(gx * gy), icg_div_magic(gx));
-    }
-    {
-        icg_prof_scope ps(ctx, "detect_select");
-        hipLaunchKernelGGL(k_select, dim3(n_roi), dim3(256), 0, ctx->stream, d_rois, ctx->d_cand, cand_plane, d_ccnt, d_rmax, grid->min_dist, d_picks, d_pcnt,
-                           z_cnt, max_pb);
-    }
-    {
-        const subpix_mask_t M = subpix_window();
-        icg_prof_scope ps(ctx, "detect_subpix");
-        hipLaunchKernelGGL(k_subpix, dim3(n_roi * max_pb), dim3(64), 0, ctx->stream, d_rois, ctx->d_frames, ctx->slot_bytes, d_slots, pitch,
-                           (const float2 *) d_picks, z_corners, (const int32_t *) d_pcnt, max_pb, M);
-    }
-    ICG_HIP(ctx, hipGetLastError());
+    if ((rc = detect_launch(ctx, n_roi, grid, d_rois, d_slots, d_mpts, d_moff, d_mcnt, d_vh, d_picks, d_pcnt, z_corners, z_cnt))) return rc;
     if ((rc = c.finish())) return rc;
 
     // block-order assembly with the block origin added (tracking.cc:669-685)
@@ -739,35 +752,15 @@ int icg_detect_circle_rows(int radius, std::vector<int32_t> &vh) {
     return circle_row_spans(hw, vh) ? 0 : -1;
 }
 
+// (the grid passed icg_detect_check_grid when the tracker was created)
 int icg_detect_launch_ind(icg_ctx *ctx, int n_jobs, const icg_detect_grid *grid, const void *d_rois, const int32_t *d_slots, const float2 *d_mask_pts,
                           const int32_t *d_mask_begin, const int32_t *d_mask_cnt, const int32_t *d_vh, float2 *d_picks, int32_t *d_pick_cnt,
                           float2 *d_corners, int32_t *d_corner_cnt) {
-    const int w = ctx->cfg.width, h = ctx->cfg.height, pitch = ctx->lv[0].pitch;
-    const int nblk = grid->block_cols * grid->block_rows, n_roi = n_jobs * nblk;
+    const int n_roi = n_jobs * grid->block_cols * grid->block_rows;
     if (n_jobs > ctx->cfg.max_batch) return icg_fail(ctx, ICG_ERR_CAPACITY, "detect batch %d > max_batch %d", n_jobs, ctx->cfg.max_batch);
-    if (grid->max_per_block > DET_MAX_PER_BLOCK || grid->min_dist > FE_MAX_RADIUS) return icg_fail(ctx, ICG_ERR_INVALID, "bad detection grid");
     int rc = ensure_detect_ws(ctx);
     if (rc) return rc;
     if ((rc = ensure_roi_state(ctx, n_roi))) return rc;
-    const size_t cand_plane = (size_t) w * h;
-    {
-        icg_prof_scope ps(ctx, "detect_min_eig_nms");
-        const int gx = (grid->block_w + FE_TW - 1) / FE_TW, gy = (grid->block_h + FE_TH * FE_WAVES - 1) / (FE_TH * FE_WAVES);
-        hipLaunchKernelGGL(k_min_eig_nms, dim3(std::min(icg_xcd_grid((gx * gy * n_roi + FE_WAVES - 1) / FE_WAVES), 8 * FE_RESIDENT_PER_XCD)), dim3(64 * FE_WAVES), 0, ctx->stream, (const det_roi *) d_rois, ctx->d_frames,
-                           ctx->slot_bytes, d_slots, pitch, w, h, d_mask_pts, d_mask_begin, d_mask_cnt, grid->min_dist, d_vh, ctx->d_roi_max, ctx->d_cand,
-                           cand_plane, ctx->d_cand_cnt, gx, gy, gx * gy * n_roi, icg_div_magic(gx * gy), icg_div_magic(gx));
-    }
-    {
-        icg_prof_scope ps(ctx, "detect_select");
-        hipLaunchKernelGGL(k_select, dim3(n_roi), dim3(256), 0, ctx->stream, (const det_roi *) d_rois, ctx->d_cand, cand_plane, ctx->d_cand_cnt, ctx->d_roi_max,
-                           grid->min_dist, d_picks, d_pick_cnt, d_corner_cnt, grid->max_per_block);
-    }
-    {
-        const subpix_mask_t M = subpix_window();
-        icg_prof_scope ps(ctx, "detect_subpix");
-        hipLaunchKernelGGL(k_subpix, dim3(n_roi * grid->max_per_block), dim3(64), 0, ctx->stream, (const det_roi *) d_rois, ctx->d_frames, ctx->slot_bytes,
-                           d_slots, pitch, (const float2 *) d_picks, d_corners, (const int32_t *) d_pick_cnt, grid->max_per_block, M);
-    }
-    ICG_HIP(ctx, hipGetLastError());
-    return ICG_OK;
+    return detect_launch(ctx, n_roi, grid, (const det_roi *) d_rois, d_slots, d_mask_pts, d_mask_begin, d_mask_cnt, d_vh, d_picks, d_pick_cnt, d_corners,
+                         d_corner_cnt);
 }

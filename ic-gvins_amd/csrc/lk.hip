@@ -771,6 +771,22 @@ extern "C" int icg_lk_track(icg_ctx *ctx, int n, const int32_t *prev_slot, const
     return c.finish();
 }
 
+// the forward / backward track and its verdict of n points: k_lk_track_fb + k_lk_finish, asynchronous on the context's stream.  seg_count
+// null: one list of n points; otherwise n = n_seg * seg_cap entries in segments (icg_lk_launch_segments).  bwd_undist: see k_lk_finish.
+static void lk_fb_launch(icg_ctx *ctx, int n, int seg_cap, const int32_t *seg_count, bool want_undist, const int32_t *prev_slot, const int32_t *next_slot,
+                         const float2 *prev, const float2 *guess, float2 *out, uint8_t *status, float2 *bwd_undist) {
+    {
+        icg_prof_scope ps(ctx, "lk_track_fb");
+        hipLaunchKernelGGL(k_lk_track_fb, dim3(icg_xcd_grid(n)), dim3(64), 0, ctx->stream, icg_make_pyr_desc(ctx), n, prev_slot, next_slot, prev, guess, out,
+                           status, bwd_undist, ctx->cfg.width, ctx->cfg.height, seg_cap, seg_count);
+    }
+    {
+        icg_prof_scope ps(ctx, "lk_finish");
+        hipLaunchKernelGGL(k_lk_finish, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, prev, (const float2 *) out, bwd_undist, status,
+                           want_undist ? 1 : 0, ctx->has_cam ? 1 : 0, ctx->cam, ctx->cfg.width, ctx->cfg.height, seg_cap, seg_count);
+    }
+}
+
 extern "C" int icg_lk_track_fb(icg_ctx *ctx, int n, const int32_t *prev_slot, const int32_t *next_slot,
                                const float *prev_pts, const float *guess_pts, float *out_pts, uint8_t *status,
                                float *out_undist, int32_t *keep_idx, int32_t *n_keep) {
@@ -799,16 +815,7 @@ extern "C" int icg_lk_track_fb(icg_ctx *ctx, int n, const int32_t *prev_slot, co
     int32_t *d_keep     = keep_idx ? c.out_zc(keep_idx, (size_t) n) : nullptr;
     int32_t *d_nkeep    = keep_idx ? c.out_zc(n_keep, 1) : nullptr;
     ICG_LAUNCH_GUARD(c);
-    {
-        icg_prof_scope ps(ctx, "lk_track_fb");
-        hipLaunchKernelGGL(k_lk_track_fb, dim3(icg_xcd_grid(n)), dim3(64), 0, ctx->stream, icg_make_pyr_desc(ctx), n, d_ps, d_ns, d_pp, d_gs, d_out,
-                           d_st, d_und, ctx->cfg.width, ctx->cfg.height, 0, (const int32_t *) nullptr);
-    }
-    {
-        icg_prof_scope ps(ctx, "lk_finish");
-        hipLaunchKernelGGL(k_lk_finish, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, d_pp, (const float2 *) d_out, d_und, d_st,
-                           out_undist ? 1 : 0, ctx->has_cam ? 1 : 0, ctx->cam, ctx->cfg.width, ctx->cfg.height, 0, (const int32_t *) nullptr);
-    }
+    lk_fb_launch(ctx, n, 0, nullptr, out_undist != nullptr, d_ps, d_ns, d_pp, d_gs, d_out, d_st, d_und);
     if (keep_idx) {
         icg_prof_scope ps(ctx, "keep_indices");
         hipLaunchKernelGGL(k_keep_indices, dim3(1), dim3(1024), 0, ctx->stream, n, d_st, d_keep, d_nkeep);
@@ -822,17 +829,7 @@ extern "C" int icg_lk_track_fb(icg_ctx *ctx, int n, const int32_t *prev_slot, co
 int icg_lk_launch_segments(icg_ctx *ctx, int n_seg, int seg_cap, const int32_t *d_count, const int32_t *d_prev_slot, const int32_t *d_next_slot,
                            const float2 *d_prev, const float2 *d_guess, float2 *d_out, uint8_t *d_status, float2 *d_undist) {
     if (!ctx->has_cam) return icg_fail(ctx, ICG_ERR_INVALID, "camera not set");
-    const int n = n_seg * seg_cap;
-    {
-        icg_prof_scope ps(ctx, "lk_track_fb");
-        hipLaunchKernelGGL(k_lk_track_fb, dim3(icg_xcd_grid(n)), dim3(64), 0, ctx->stream, icg_make_pyr_desc(ctx), n, d_prev_slot, d_next_slot, d_prev,
-                           d_guess, d_out, d_status, d_undist, ctx->cfg.width, ctx->cfg.height, seg_cap, d_count);
-    }
-    {
-        icg_prof_scope ps(ctx, "lk_finish");
-        hipLaunchKernelGGL(k_lk_finish, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, d_prev, (const float2 *) d_out, d_undist, d_status, 1, 1,
-                           ctx->cam, ctx->cfg.width, ctx->cfg.height, seg_cap, d_count);
-    }
+    lk_fb_launch(ctx, n_seg * seg_cap, seg_cap, d_count, true, d_prev_slot, d_next_slot, d_prev, d_guess, d_out, d_status, d_undist);
     ICG_HIP(ctx, hipGetLastError());
     return ICG_OK;
 }

@@ -3,15 +3,9 @@
 //
 // Algorithm definition: SURVEY.md Appendix B.9/B.10 with the formulation pinned in oracle/orc_ransac.cc
 // (one-sided Jacobi null space, transcendental-free cubic, double scoring with float compare, sequential
-// best/niters replay).  Mapping:
-//   * the hypothesis index stream depends only on cv::RNG's state, not on scores, so it is generated up front on the
-//     host (same LCG as cv::RNG((uint64)-1)) for a chunk of hypotheses;
-//   * k_fm_hypothesis: 32 hypotheses per workgroup.  Solve: a LANE per hypothesis — as cv::SVDecomp does for m < n, the one-sided
-//     Jacobi runs on the 7 full-rank columns of A^T (9x7, REGISTER resident, fully unrolled) and the two null vectors come from
-//     completing the orthonormal basis; only + - * / sqrt are used so results match the CPU restatement bit-for-bit.  Score: a WAVE
-//     per model — 64 points per step, symmetric epipolar distance in double, inlier bits by wave ballot, count by popcount;
-//   * the host replays the `best / niters` recurrence over the score array in hypothesis order, which makes the result
-//     identical to the sequential algorithm; further chunks are generated only if niters demands them.
+// best/niters replay).  F6 runs one point set's whole RANSAC run inside one workgroup (k_fm_ransac_sets); the device-resident tracker
+// launches it on its segments and the C entry points stage their sets as segments and make the same launch.  F8 is a lane per point
+// (k_triangulate_seg), likewise shared by the tracker and icg_triangulate.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -19,14 +13,6 @@
 #include <mutex>
 
 #include "icg_internal.h"
-
-struct fm_set {
-    int pt_begin, n_pts; // range in the concatenated point arrays
-    int hyp_begin;       // first hypothesis slot of this set in this launch
-    int n_hyp;
-    int word_begin; // first u64 word of this set's inlier bit masks (per model: words_per_model)
-    int words_per_model;
-};
 
 __device__ int dev_solve_cubic_real(const double c[4], double roots[3]) {
     double a = c[0], b = c[1], cc = c[2], d = c[3];
@@ -97,13 +83,12 @@ __device__ int dev_solve_cubic_real(const double c[4], double roots[3]) {
 }
 
 // The seven-point solve of ONE hypothesis by the calling lane: up to three fundamental matrices into out27, their number into *n_out.
-__device__ __forceinline__ void seven_point_solve(const fm_set &S, const int32_t *idx /*7, set-local*/, const float2 *pts1, const float2 *pts2,
-                                                  double *out27, int *n_out) {
+__device__ __forceinline__ void seven_point_solve(const int *idx /*7*/, const float2 *pts1, const float2 *pts2, double *out27, int *n_out) {
     // M = A^T (9 x 7) register resident; see oracle/orc_ransac.cc null_space_9x7 for the definition this mirrors.
     double M[9][7];
 #pragma unroll
     for (int i = 0; i < 7; i++) {
-        const float2 a = pts1[S.pt_begin + idx[i]], b = pts2[S.pt_begin + idx[i]];
+        const float2 a = pts1[idx[i]], b = pts2[idx[i]];
         const double x1 = a.x, y1 = a.y, x2 = b.x, y2 = b.y;
         M[0][i] = x2 * x1;
         M[1][i] = x2 * y1;
@@ -233,251 +218,6 @@ __device__ __forceinline__ void seven_point_solve(const fm_set &S, const int32_t
     *n_out = n;
 }
 
-// k_fm_hypothesis: a workgroup of four waves takes FM_HPW hypotheses.  Solve phase: LANE PER HYPOTHESIS in wave 0 — the seven-point
-// solve is a strictly serial FP64 chain per hypothesis (Jacobi sweeps, basis completion, cubic) whose rotations cannot be spread over
-// lanes without changing its rounding, but different hypotheses are independent, so 32 of them advance in the lanes of one wave at the
-// cost of one (round 2: one wave per hypothesis with 63 idle lanes, 23 % of the queue time for < 10 % of the work).  The models pass
-// through LDS; scoring phase: WAVE PER MODEL — the four waves take the (hypothesis, model) pairs in turn, 64 points per step, symmetric
-// epipolar distance in double, inlier bits by wave ballot, count by popcount.  Still one launch per RANSAC round, every input read
-// where the host staged it (pinned memory, zero-copy).  Per hypothesis the arithmetic is the one of round 2: bit-identical masks.
-#define FM_HPW 32
-__global__ __launch_bounds__(256, 1) void k_fm_hypothesis(int n_hyp_total, const fm_set *sets, const int32_t *hyp_set,
-                                                          const int32_t *hyp_idx /*n_hyp x 7 (set-local)*/, const float2 *pts1,
-                                                          const float2 *pts2, float thresh2, int32_t *good /*n_hyp x 3*/,
-                                                          unsigned long long *bits) {
-    __shared__ double Fm[FM_HPW][27];
-    __shared__ int n_sh[FM_HPW];
-    const int hyp0 = blockIdx.x * FM_HPW, t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const int n_here = min(FM_HPW, n_hyp_total - hyp0);
-    if (n_here <= 0) return;
-    if (wave == 0 && lane < n_here) {
-        const int hyp = hyp0 + lane;
-        int n         = 0;
-        seven_point_solve(sets[hyp_set[hyp]], hyp_idx + 7 * (size_t) hyp, pts1, pts2, Fm[lane], &n);
-        n_sh[lane] = n;
-    }
-    __syncthreads();
-    for (int pair = wave; pair < 3 * n_here; pair += 4) {
-        const int hl = pair / 3, model = pair - 3 * hl, hyp = hyp0 + hl;
-        if (model >= n_sh[hl]) {
-            if (lane == 0) good[hyp * 3 + model] = -1;
-            continue;
-        }
-        const fm_set S  = sets[hyp_set[hyp]];
-        const double *F = Fm[hl] + 9 * model;
-        const double F0 = F[0], F1 = F[1], F2 = F[2], F3 = F[3], F4 = F[4], F5 = F[5], F6 = F[6], F7 = F[7], F8 = F[8];
-        unsigned long long *w = bits + S.word_begin + ((size_t) (hyp - S.hyp_begin) * 3 + model) * S.words_per_model;
-        int count = 0;
-        for (int base = 0; base < S.n_pts; base += 64) {
-            const int i = base + lane;
-            bool in     = false;
-            if (i < S.n_pts) {
-                const float2 p1 = pts1[S.pt_begin + i], p2 = pts2[S.pt_begin + i];
-                const double x1 = p1.x, y1 = p1.y, x2 = p2.x, y2 = p2.y;
-                double a = F0 * x1 + F1 * y1 + F2;
-                double b = F3 * x1 + F4 * y1 + F5;
-                double c = F6 * x1 + F7 * y1 + F8;
-                double s2 = 1. / (a * a + b * b);
-                double d2 = x2 * a + y2 * b + c;
-                a         = F0 * x2 + F3 * y2 + F6;
-                b         = F1 * x2 + F4 * y2 + F7;
-                c         = F2 * x2 + F5 * y2 + F8;
-                double s1 = 1. / (a * a + b * b);
-                double d1 = x1 * a + y1 * b + c;
-                float e   = (float) fmax(d1 * d1 * s1, d2 * d2 * s2);
-                in        = e <= thresh2;
-            }
-            const unsigned long long m = __ballot(in);
-            if (lane == 0) w[base >> 6] = m;
-            count += __popcll(m);
-        }
-        if (lane == 0) good[hyp * 3 + model] = count;
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-namespace {
-struct cv_rng { // cv::RNG (core/operations.hpp): MWC generator, coefficient 4164903690
-    uint64_t state;
-    explicit cv_rng(uint64_t s) : state(s ? s : 0xffffffffULL) {}
-    unsigned next() {
-        state = (uint64_t) (unsigned) state * 4164903690U + (unsigned) (state >> 32);
-        return (unsigned) state;
-    }
-    int uniform(int a, int b) { return a == b ? a : (int) (next() % (unsigned) (b - a) + a); }
-};
-
-int ransac_update_num_iters(double p, double ep, int modelPoints, int maxIters) { // ptsetreg.cpp RANSACUpdateNumIters
-    p  = std::max(p, 0.);
-    p  = std::min(p, 1.);
-    ep = std::max(ep, 0.);
-    ep = std::min(ep, 1.);
-    double num   = std::max(1. - p, DBL_MIN);
-    double denom = 1. - std::pow(1. - ep, modelPoints);
-    if (denom < DBL_MIN) return 0;
-    num   = std::log(num);
-    denom = std::log(denom);
-    return denom >= 0 || -num >= maxIters * (-denom) ? maxIters : (int) lrint(num / denom);
-}
-
-// calib3d precomp.hpp haveCollinearPoints(m, 7): the last point of the subset against every pair of the earlier ones
-bool have_collinear_points(const float *pts, const int *idx) {
-    const int i = 6;
-    for (int j = 0; j < i; j++) {
-        double dx1 = pts[2 * idx[j]] - pts[2 * idx[i]];
-        double dy1 = pts[2 * idx[j] + 1] - pts[2 * idx[i] + 1];
-        for (int k = 0; k < j; k++) {
-            double dx2 = pts[2 * idx[k]] - pts[2 * idx[i]];
-            double dy2 = pts[2 * idx[k] + 1] - pts[2 * idx[i] + 1];
-            if (std::fabs(dx2 * dy1 - dy2 * dx1) <= FLT_EPSILON * (std::fabs(dx1) + std::fabs(dy1) + std::fabs(dx2) + std::fabs(dy2)))
-                return true;
-        }
-    }
-    return false;
-}
-
-// RANSACPointSetRegistrator::getSubset (ptsetreg.cpp, OpenCV 4.x) with FMEstimatorCallback::checkSubset (fundam.cpp): a rejected
-// subset has consumed its RNG draws; false after 10000 rejected attempts
-bool get_subset(cv_rng &rng, int n, const float *p1, const float *p2, int idx[7]) {
-    for (int attempt = 0; attempt < 10000; attempt++) {
-        for (int i = 0; i < 7; i++) {
-            int v;
-            for (v = rng.uniform(0, n); std::find(idx, idx + i, v) != idx + i; v = rng.uniform(0, n)) {
-            }
-            idx[i] = v;
-        }
-        if (!have_collinear_points(p1, idx) && !have_collinear_points(p2, idx)) return true;
-    }
-    return false;
-}
-
-struct set_state {
-    int begin, n;
-    cv_rng rng{(uint64_t) -1};
-    int iter = 0, niters = 1000, max_good = 0;
-    bool done = false;
-    std::vector<uint8_t> best;
-};
-} // namespace
-
-extern "C" int icg_fm_ransac(icg_ctx *ctx, int n_sets, const int32_t *offsets, const float *pts1, const float *pts2,
-                             double thresh, double conf, uint8_t *mask) {
-    if (!ctx || n_sets < 0) return ICG_ERR_INVALID;
-    if (n_sets == 0) return ICG_OK;
-    if (!offsets || !pts1 || !pts2 || !mask) return ICG_ERR_INVALID;
-    const int total = offsets[n_sets];
-    if (total > ctx->cfg.max_points) return icg_fail(ctx, ICG_ERR_CAPACITY, "%d points > max_points %d", total, ctx->cfg.max_points);
-    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    if (thresh <= 0) thresh = 3;
-    if (conf < DBL_EPSILON || conf > 1 - DBL_EPSILON) conf = 0.99;
-
-    std::vector<set_state> st((size_t) n_sets);
-    int active = 0;
-    for (int s = 0; s < n_sets; s++) {
-        st[s].begin = offsets[s];
-        st[s].n     = offsets[s + 1] - offsets[s];
-        if (st[s].n < 0) return ICG_ERR_INVALID;
-        if (st[s].n < 15) { // the reference only calls findFundamentalMat with >= 15 points: leave untouched
-            for (int i = 0; i < st[s].n; i++) mask[st[s].begin + i] = 1;
-            st[s].done = true;
-        } else {
-            st[s].best.assign((size_t) st[s].n, 0);
-            active++;
-        }
-    }
-    int chunk = 16;
-    while (active > 0) {
-        // hypotheses of this round: each active set gets min(chunk, niters - iter)
-        std::vector<fm_set> sets;
-        std::vector<int> set_of;       // launch set -> global set
-        std::vector<int32_t> hyp_set;  // per hypothesis -> launch set
-        std::vector<int32_t> hyp_idx;  // 7 per hypothesis
-        int words = 0;
-        for (int s = 0; s < n_sets; s++) {
-            set_state &S = st[s];
-            if (S.done) continue;
-            int nh = std::min(chunk, S.niters - S.iter);
-            fm_set f;
-            f.pt_begin        = S.begin;
-            f.n_pts           = S.n;
-            f.hyp_begin       = (int) hyp_set.size();
-            f.n_hyp           = nh;
-            f.words_per_model = (S.n + 63) / 64;
-            f.word_begin      = words;
-            words += nh * 3 * f.words_per_model;
-            for (int h = 0; h < nh; h++) {
-                int idx[7];
-                if (!get_subset(S.rng, S.n, pts1 + 2 * (size_t) S.begin, pts2 + 2 * (size_t) S.begin, idx)) {
-                    // ptsetreg.cpp run(): no valid subset -> the iterations end here (nothing found if this was the first one)
-                    S.niters = S.iter + h;
-                    nh       = h;
-                    break;
-                }
-                hyp_set.push_back((int32_t) sets.size());
-                hyp_idx.insert(hyp_idx.end(), idx, idx + 7);
-            }
-            f.n_hyp = nh; // (words keeps the planned count: unused tail words are harmless)
-            set_of.push_back(s);
-            sets.push_back(f);
-        }
-        const int nh_total = (int) hyp_set.size();
-        std::vector<int32_t> h_good((size_t) nh_total * 3);
-        std::vector<unsigned long long> h_bits((size_t) words);
-        if (nh_total > 0) { // (no hypothesis at all: every active set ran out of valid subsets)
-        icg_call c(ctx);
-        size_t need = sizeof(fm_set) * sets.size() + sizeof(int32_t) * 8 * (size_t) nh_total + sizeof(float) * 4 * (size_t) total +
-                      (size_t) nh_total * (27 * 8 + 4 + 12) + (size_t) words * 8 + 16384;
-        int rc = c.reserve(need);
-        if (rc) return rc;
-        // everything the launch reads stays where it is staged (pinned memory, read over PCIe): no upload launch
-        const fm_set *d_sets  = c.in_zc(sets.data(), sets.size());
-        const int32_t *d_hset = c.in_zc(hyp_set.data(), (size_t) nh_total);
-        const int32_t *d_hidx = c.in_zc(hyp_idx.data(), 7 * (size_t) nh_total);
-        const float2 *d_p1    = (const float2 *) c.in_zc(pts1, 2 * (size_t) total);
-        const float2 *d_p2    = (const float2 *) c.in_zc(pts2, 2 * (size_t) total);
-        if ((rc = c.seal())) return rc;
-        int32_t *d_good   = c.out_zc(h_good.data(), (size_t) nh_total * 3);
-        unsigned long long *d_bits = c.out_zc(h_bits.data(), (size_t) words);
-        ICG_LAUNCH_GUARD(c);
-        {
-            icg_prof_scope ps(ctx, "fm_hypothesis");
-            hipLaunchKernelGGL(k_fm_hypothesis, dim3((nh_total + FM_HPW - 1) / FM_HPW), dim3(256), 0, ctx->stream, nh_total, d_sets, d_hset, d_hidx, d_p1, d_p2,
-                               (float) (thresh * thresh), d_good, d_bits);
-        }
-        ICG_HIP(ctx, hipGetLastError());
-        if ((rc = c.finish())) return rc;
-        }
-
-        // sequential replay of RANSACPointSetRegistrator::run over the scores (ptsetreg.cpp)
-        for (size_t ls = 0; ls < sets.size(); ls++) {
-            set_state &S    = st[set_of[ls]];
-            const fm_set &f = sets[ls];
-            for (int h = 0; h < f.n_hyp && S.iter < S.niters; h++, S.iter++) {
-                for (int m = 0; m < 3; m++) {
-                    int good = h_good[(size_t) (f.hyp_begin + h) * 3 + m];
-                    if (good < 0) break;
-                    if (good > std::max(S.max_good, 7 - 1)) {
-                        const unsigned long long *w = &h_bits[f.word_begin + ((size_t) h * 3 + m) * f.words_per_model];
-                        for (int i = 0; i < S.n; i++) S.best[i] = (uint8_t) ((w[i >> 6] >> (i & 63)) & 1ull);
-                        S.max_good = good;
-                        S.niters   = ransac_update_num_iters(conf, (double) (S.n - good) / S.n, 7, S.niters);
-                    }
-                }
-            }
-            if (S.iter >= S.niters) {
-                S.done = true;
-                active--;
-                if (S.max_good > 0)
-                    memcpy(mask + S.begin, S.best.data(), (size_t) S.n);
-                else
-                    memset(mask + S.begin, 0, (size_t) S.n);
-            }
-        }
-        if (chunk < 256) chunk *= 2;
-    }
-    return ICG_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // F8: 4x4 DLT, smallest right singular vector by one-sided Jacobi (registers), one lane per point.
 // one point: T0 / T1 its two 3x4 camera matrices, pc0 / pc1 / pw entry i of the arrays
@@ -553,13 +293,6 @@ __device__ __forceinline__ void triangulate_point(int i, const double *T0, const
     pw[3 * i + 2] = v2 / v3;
 }
 
-__global__ void k_triangulate(int n, const int32_t *T0_idx, const int32_t *T1_idx, const double *Tcw12, const double *pc0,
-                              const double *pc1, double *pw) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    triangulate_point(i, Tcw12 + 12 * (size_t) T0_idx[i], Tcw12 + 12 * (size_t) T1_idx[i], pc0, pc1, pw);
-}
-
 // segmented form (device-resident tracker): stream s owns entries [s * seg_cap, s * seg_cap + count[s]) of the point arrays and the
 // camera matrices [s * tcw_cap, ...) — its T0 / T1 indices are local to that table
 __global__ void k_triangulate_seg(int n_seg, int seg_cap, const int32_t *count, const int32_t *T0_idx, const int32_t *T1_idx, int tcw_cap,
@@ -583,8 +316,10 @@ extern "C" int icg_triangulate(icg_ctx *ctx, int n, const int32_t *T0_idx, const
             return icg_fail(ctx, ICG_ERR_INVALID, "pose index out of range at point %d", i);
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     icg_call c(ctx);
-    int rc = c.reserve((size_t) n * (8 + 48 + 24) + (size_t) n_T * 96);
+    int rc = c.reserve((size_t) n * (8 + 48 + 24) + (size_t) n_T * 96 + 64);
     if (rc) return rc;
+    // one segment of n points with the whole camera-matrix table: the tracker's launch
+    const int32_t *d_n  = c.in_zc(&n, 1);
     const int32_t *d_i0 = c.in_zc(T0_idx, (size_t) n);
     const int32_t *d_i1 = c.in_zc(T1_idx, (size_t) n);
     const double *d_T   = c.in_zc(Tcw12, 12 * (size_t) n_T);
@@ -592,27 +327,22 @@ extern "C" int icg_triangulate(icg_ctx *ctx, int n, const int32_t *T0_idx, const
     const double *d_p1  = c.in_zc(pc1, 3 * (size_t) n);
     double *d_pw = c.out_zc(pw, 3 * (size_t) n);
     ICG_LAUNCH_GUARD(c);
-    {
-        icg_prof_scope ps(ctx, "triangulate");
-        hipLaunchKernelGGL(k_triangulate, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, n, d_i0, d_i1, d_T, d_p0, d_p1, d_pw);
-    }
-    ICG_HIP(ctx, hipGetLastError());
+    if ((rc = icg_triangulate_launch_segments(ctx, 1, n, d_n, d_i0, d_i1, n_T, d_T, d_p0, d_p1, d_pw))) return rc;
     return c.finish();
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Device-resident tracker (tracker.hip): cv::findFundamentalMat(FM_RANSAC) of one point set per stream, the WHOLE run in one launch — the
-// host loop of icg_fm_ransac (subset draws, one launch per round, sequential replay of the best / niters recurrence) moves into the
-// workgroup that owns the set:
+// F6: cv::findFundamentalMat(FM_RANSAC) of one point set per workgroup, the WHOLE run in one launch:
 //   round:  wave 0 draws up to FM_HPW subsets from the set's cv::RNG (getSubset + checkSubset with a collinearity test per lane,
 //           RNG-consuming redraws) -> LDS
-//           wave 0, a lane per hypothesis: seven-point solve (the serial FP64 chain of k_fm_hypothesis) -> models in LDS
+//           wave 0, a lane per hypothesis: seven-point solve (a strictly serial FP64 chain per hypothesis whose rotations cannot be spread over
+//           lanes without changing its rounding; different hypotheses advance in different lanes) -> models in LDS
 //           four waves, a wave per (hypothesis, model): inlier bits by ballot + count -> LDS
 //           thread 0 replays the hypotheses in order: best mask, max_good, niters = RANSACUpdateNumIters(...)
-// Any chunking of the hypothesis stream gives the sequential algorithm's result (scores do not depend on one another; hypotheses past
-// the updated niters are discarded) — the argument of icg_fm_ransac.  RANSACUpdateNumIters needs log and pow: their values for every
-// (set size, inlier count) come from a table the HOST computed with the same libm calls the host path makes (fm_denom_table), so the
-// iteration counts are the host path's bit for bit; the comparisons, the division and lrint run on the device in IEEE double.
+// Any chunking of the hypothesis stream gives the sequential algorithm's result: scores do not depend on one another, and hypotheses past
+// the updated niters are discarded.  RANSACUpdateNumIters needs log and pow: their values for every (set size, inlier count) come from a
+// table the HOST computed with OpenCV's libm calls (fm_denom_row), so the iteration counts are the sequential algorithm's bit for bit; the
+// comparisons, the division and lrint run on the device in IEEE double.
 __device__ __forceinline__ unsigned dev_rng_next(unsigned long long &state) {
     state = (unsigned long long) (unsigned) state * 4164903690U + (unsigned) (state >> 32);
     return (unsigned) state;
@@ -622,8 +352,8 @@ __device__ __forceinline__ unsigned dev_rng_next(unsigned long long &state) {
 // independent FP64 tests of calib3d's haveCollinearPoints(m, 7), an OR — runs a test per lane (lanes 30..63 repeat tests of lanes 0..29: every lane stays active, because FP64
 // and the other half-rate VALU instructions take ~5x as long on gfx950 when 16 or fewer lanes are active — under `if (t == 0)` the
 // up-to-32 subsets of a round cost more than the seven-point solves and the scoring together; profiles/ubench/valu_cost_r05.txt).
-// idx_lds: the hypothesis' seven indices in LDS (written here, read by the solve).  Same subsets, same RNG consumption as dev_get_subset's
-// sequential form (k_fm_hypothesis' host twin draws on the host).
+// idx_lds: the hypothesis' seven indices in LDS (written here, read by the solve).  Same subsets, same RNG consumption as OpenCV's getSubset
+// (the sequential form of oracle/orc_ransac.cc).
 __device__ bool dev_get_subset_wave(unsigned long long &rng, int n, const float2 *p1, const float2 *p2, int *idx_lds, int lane) {
     const int pr = lane % 15;
     const int j  = pr < 1 ? 1 : pr < 3 ? 2 : pr < 6 ? 3 : pr < 10 ? 4 : 5; // pairs (j, k), k < j < 6, in the order of haveCollinearPoints
@@ -658,8 +388,32 @@ __device__ bool dev_get_subset_wave(unsigned long long &rng, int n, const float2
     return false;
 }
 
-#define FMS_MAX_WORDS 16 // 64-bit inlier words per model: sets of up to 1024 points
+#define FM_HPW 32 // hypotheses per round
+#define FMS_MAX_WORDS 16 // 64-bit inlier words per model in LDS: the tracker's form takes sets of up to 1024 points
 
+// symmetric epipolar distance of one correspondence under F (double, compared in float): the inlier test of the scoring and of the mask
+__device__ __forceinline__ bool fm_inlier(double F0, double F1, double F2, double F3, double F4, double F5, double F6, double F7, double F8, float2 a0,
+                                          float2 b0, float thresh2) {
+    const double x1 = a0.x, y1 = a0.y, x2 = b0.x, y2 = b0.y;
+    double a = F0 * x1 + F1 * y1 + F2;
+    double b = F3 * x1 + F4 * y1 + F5;
+    double c = F6 * x1 + F7 * y1 + F8;
+    double s2 = 1. / (a * a + b * b);
+    double d2 = x2 * a + y2 * b + c;
+    a         = F0 * x2 + F3 * y2 + F6;
+    b         = F1 * x2 + F4 * y2 + F7;
+    c         = F2 * x2 + F5 * y2 + F8;
+    double s1 = 1. / (a * a + b * b);
+    double d1 = x1 * a + y1 * b + c;
+    float e   = (float) fmax(d1 * d1 * s1, d2 * d2 * s2);
+    return e <= thresh2;
+}
+
+// LARGE = false (the tracker's form): the inlier words of every model of a round and the best mask live in LDS (sets up to 64 * FMS_MAX_WORDS
+// points), denom_tab is the shared table of fm_denom_table (row n = the set size).  LARGE = true (stand-alone calls with a set above that):
+// no inlier words are kept — the replay keeps the best model's nine coefficients and the mask is that model's inlier test re-evaluated per
+// point at the end (the same IEEE operations as the scoring: the same bits); denom_tab is the call's own table, row s = set s.
+template <bool LARGE>
 __global__ __launch_bounds__(256, 1) void k_fm_ransac_sets(int n_sets, int seg_cap, const int32_t *count, const float2 *pts1, const float2 *pts2,
                                                            float thresh2, double log_num, const double *denom_tab, int tab_n, uint8_t *mask) {
     __shared__ double Fm[FM_HPW][27];
@@ -668,6 +422,7 @@ __global__ __launch_bounds__(256, 1) void k_fm_ransac_sets(int n_sets, int seg_c
     __shared__ int good_sh[FM_HPW * 3];
     __shared__ unsigned long long bits_sh[FM_HPW * 3][FMS_MAX_WORDS];
     __shared__ unsigned long long best_sh[FMS_MAX_WORDS];
+    __shared__ double best_F[9];
     __shared__ int nh_sh, iter_sh, niters_sh, max_good_sh;
     const int s = blockIdx.x, t = threadIdx.x, wave = t >> 6, lane = t & 63;
     if (s >= n_sets) return;
@@ -675,16 +430,14 @@ __global__ __launch_bounds__(256, 1) void k_fm_ransac_sets(int n_sets, int seg_c
     if (n <= 0) return; // no set for this stream in this step
     const float2 *p1 = pts1 + (size_t) s * seg_cap, *p2 = pts2 + (size_t) s * seg_cap;
     uint8_t *m       = mask + (size_t) s * seg_cap;
-    if (n < 15 || n > tab_n || n > 64 * FMS_MAX_WORDS) { // the reference only calls findFundamentalMat with >= 15 points: leave untouched
+    if (n < 15 || n > tab_n || (!LARGE && n > 64 * FMS_MAX_WORDS)) { // the reference only calls findFundamentalMat with >= 15 points: leave untouched
         for (int i = t; i < n; i += 256) m[i] = 1;
         return;
     }
     const int words = (n + 63) >> 6;
-    fm_set S;
-    S.pt_begin = 0, S.n_pts = n, S.hyp_begin = 0, S.n_hyp = 0, S.word_begin = 0, S.words_per_model = words;
     unsigned long long rng = 0xffffffffffffffffull; // cv::RNG((uint64) -1): the fixed seed of every findFundamentalMat call
     if (t == 0) iter_sh = 0, niters_sh = 1000, max_good_sh = 0;
-    if (t < FMS_MAX_WORDS) best_sh[t] = 0;
+    if (!LARGE && t < FMS_MAX_WORDS) best_sh[t] = 0;
     __syncthreads();
     for (;;) {
         if (wave == 0) { // all 64 lanes: see dev_get_subset_wave
@@ -705,7 +458,7 @@ __global__ __launch_bounds__(256, 1) void k_fm_ransac_sets(int n_sets, int seg_c
         if (nh <= 0) break;
         if (wave == 0 && lane < nh) {
             int nm = 0;
-            seven_point_solve(S, idx_sh[lane], p1, p2, Fm[lane], &nm);
+            seven_point_solve(idx_sh[lane], p1, p2, Fm[lane], &nm);
             n_sh[lane] = nm;
         }
         __syncthreads();
@@ -721,24 +474,9 @@ __global__ __launch_bounds__(256, 1) void k_fm_ransac_sets(int n_sets, int seg_c
             for (int base = 0; base < n; base += 64) {
                 const int i = base + lane;
                 bool in     = false;
-                if (i < n) {
-                    const float2 a0 = p1[i], b0 = p2[i];
-                    const double x1 = a0.x, y1 = a0.y, x2 = b0.x, y2 = b0.y;
-                    double a = F0 * x1 + F1 * y1 + F2;
-                    double b = F3 * x1 + F4 * y1 + F5;
-                    double c = F6 * x1 + F7 * y1 + F8;
-                    double s2 = 1. / (a * a + b * b);
-                    double d2 = x2 * a + y2 * b + c;
-                    a         = F0 * x2 + F3 * y2 + F6;
-                    b         = F1 * x2 + F4 * y2 + F7;
-                    c         = F2 * x2 + F5 * y2 + F8;
-                    double s1 = 1. / (a * a + b * b);
-                    double d1 = x1 * a + y1 * b + c;
-                    float e   = (float) fmax(d1 * d1 * s1, d2 * d2 * s2);
-                    in        = e <= thresh2;
-                }
+                if (i < n) in = fm_inlier(F0, F1, F2, F3, F4, F5, F6, F7, F8, p1[i], p2[i], thresh2);
                 const unsigned long long mm = __ballot(in);
-                if (lane == 0) bits_sh[pair][base >> 6] = mm;
+                if (!LARGE && lane == 0) bits_sh[pair][base >> 6] = mm;
                 cnt += __popcll(mm);
             }
             if (lane == 0) good_sh[pair] = cnt;
@@ -751,10 +489,13 @@ __global__ __launch_bounds__(256, 1) void k_fm_ransac_sets(int n_sets, int seg_c
                     const int good = good_sh[h * 3 + mdl];
                     if (good < 0) break;
                     if (good > max(max_good, 7 - 1)) {
-                        for (int w = 0; w < words; w++) best_sh[w] = bits_sh[h * 3 + mdl][w];
+                        if constexpr (LARGE)
+                            for (int k = 0; k < 9; k++) best_F[k] = Fm[h][9 * mdl + k];
+                        else
+                            for (int w = 0; w < words; w++) best_sh[w] = bits_sh[h * 3 + mdl][w];
                         max_good = good;
                         // RANSACUpdateNumIters(conf, (n - good) / n, 7, niters) with log(1 - (1 - ep)^7) from the host's table
-                        const double denom = denom_tab[(size_t) n * (tab_n + 1) + good];
+                        const double denom = denom_tab[(size_t) (LARGE ? s : n) * (tab_n + 1) + good];
                         if (denom != denom) { // (NaN marks 1 - (1 - ep)^7 < DBL_MIN: "return 0")
                             niters = 0;
                         } else {
@@ -772,11 +513,27 @@ __global__ __launch_bounds__(256, 1) void k_fm_ransac_sets(int n_sets, int seg_c
         if (stop) break;
     }
     const bool found = max_good_sh > 0;
-    for (int i = t; i < n; i += 256) m[i] = found ? (uint8_t) ((best_sh[i >> 6] >> (i & 63)) & 1ull) : (uint8_t) 0;
+    if constexpr (LARGE) {
+        const double *F = best_F;
+        for (int i = t; i < n; i += 256)
+            m[i] = found ? (uint8_t) fm_inlier(F[0], F[1], F[2], F[3], F[4], F[5], F[6], F[7], F[8], p1[i], p2[i], thresh2) : (uint8_t) 0;
+    } else {
+        for (int i = t; i < n; i += 256) m[i] = found ? (uint8_t) ((best_sh[i >> 6] >> (i & 63)) & 1ull) : (uint8_t) 0;
+    }
 }
 
-// log(1 - (1 - ep)^7) for ep = (n - good) / n, n = 0..tab_n, good = 0..n, with the libm calls of ransac_update_num_iters (NaN where that
-// function returns 0 before taking the logarithm): one table per process and device, shared by every tracker
+// log(1 - (1 - ep)^7) for ep = (n - good) / n, good = 0..n: the libm calls of OpenCV's RANSACUpdateNumIters (NaN where it returns 0 before
+// taking the logarithm)
+static void fm_denom_row(int n, double *row) {
+    for (int good = 0; good <= n; good++) {
+        double ep    = (double) (n - good) / n;
+        ep           = std::min(std::max(ep, 0.), 1.);
+        double denom = 1. - std::pow(1. - ep, 7);
+        row[good]    = denom < DBL_MIN ? std::nan("") : std::log(denom);
+    }
+}
+
+// the rows n = 0..tab_n of the tracker's form: one table per process and device, shared by every tracker
 static int fm_denom_table(icg_ctx *ctx, int tab_n, const double **d_tab) {
     static std::mutex mu;
     static std::map<std::pair<int, int>, double *> tabs;
@@ -785,13 +542,7 @@ static int fm_denom_table(icg_ctx *ctx, int tab_n, const double **d_tab) {
     auto it  = tabs.find(key);
     if (it == tabs.end()) {
         std::vector<double> h((size_t) (tab_n + 1) * (tab_n + 1), 0.0);
-        for (int n = 1; n <= tab_n; n++)
-            for (int good = 0; good <= n; good++) {
-                double ep = (double) (n - good) / n;
-                ep        = std::min(std::max(ep, 0.), 1.);
-                double denom = 1. - std::pow(1. - ep, 7);
-                h[(size_t) n * (tab_n + 1) + good] = denom < DBL_MIN ? std::nan("") : std::log(denom);
-            }
+        for (int n = 1; n <= tab_n; n++) fm_denom_row(n, &h[(size_t) n * (tab_n + 1)]);
         double *d = nullptr;
         ICG_HIP(ctx, hipMalloc((void **) &d, h.size() * sizeof(double)));
         ICG_HIP(ctx, hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -801,21 +552,27 @@ static int fm_denom_table(icg_ctx *ctx, int tab_n, const double **d_tab) {
     return 0;
 }
 
-int icg_fm_ransac_launch_sets(icg_ctx *ctx, int n_sets, int seg_cap, const int32_t *d_count, const float2 *d_p1, const float2 *d_p2, double thresh,
-                              double conf, uint8_t *d_mask) {
+template <bool LARGE>
+static int fm_ransac_launch(icg_ctx *ctx, int n_sets, int seg_cap, const int32_t *d_count, const float2 *d_p1, const float2 *d_p2, double thresh,
+                            double conf, const double *d_tab, int tab_n, uint8_t *d_mask) {
     if (thresh <= 0) thresh = 3;
     if (conf < DBL_EPSILON || conf > 1 - DBL_EPSILON) conf = 0.99;
-    const int tab_n    = std::min(seg_cap, 64 * FMS_MAX_WORDS);
-    const double *d_tab = nullptr;
-    int rc = fm_denom_table(ctx, tab_n, &d_tab);
-    if (rc) return rc;
     double p         = std::min(std::max(conf, 0.), 1.);
     const double num = std::log(std::max(1. - p, DBL_MIN)); // the numerator of RANSACUpdateNumIters
     icg_prof_scope ps(ctx, "fm_ransac_sets");
-    hipLaunchKernelGGL(k_fm_ransac_sets, dim3(n_sets), dim3(256), 0, ctx->stream, n_sets, seg_cap, d_count, d_p1, d_p2, (float) (thresh * thresh), num, d_tab,
-                       tab_n, d_mask);
+    hipLaunchKernelGGL(k_fm_ransac_sets<LARGE>, dim3(n_sets), dim3(256), 0, ctx->stream, n_sets, seg_cap, d_count, d_p1, d_p2, (float) (thresh * thresh), num,
+                       d_tab, tab_n, d_mask);
     ICG_HIP(ctx, hipGetLastError());
     return ICG_OK;
+}
+
+int icg_fm_ransac_launch_sets(icg_ctx *ctx, int n_sets, int seg_cap, const int32_t *d_count, const float2 *d_p1, const float2 *d_p2, double thresh,
+                              double conf, uint8_t *d_mask) {
+    const int tab_n     = std::min(seg_cap, 64 * FMS_MAX_WORDS);
+    const double *d_tab = nullptr;
+    int rc = fm_denom_table(ctx, tab_n, &d_tab);
+    if (rc) return rc;
+    return fm_ransac_launch<false>(ctx, n_sets, seg_cap, d_count, d_p1, d_p2, thresh, conf, d_tab, tab_n, d_mask);
 }
 
 int icg_triangulate_launch_segments(icg_ctx *ctx, int n_seg, int seg_cap, const int32_t *d_count, const int32_t *d_T0, const int32_t *d_T1, int tcw_cap,
@@ -827,10 +584,11 @@ int icg_triangulate_launch_segments(icg_ctx *ctx, int n_seg, int seg_cap, const 
     return ICG_OK;
 }
 
-// The same result as icg_fm_ransac with ONE launch and ONE wait (no host round per RANSAC chunk): the whole run of every set inside the
-// workgroup that owns it (k_fm_ransac_sets).  Sets of more than 64 * FMS_MAX_WORDS points fall back to icg_fm_ransac.
-extern "C" int icg_fm_ransac_device(icg_ctx *ctx, int n_sets, const int32_t *offsets, const float *pts1, const float *pts2, double thresh, double conf,
-                                    uint8_t *mask) {
+// The stand-alone form: the sets are staged as segments of the padded largest set size and run by the tracker's launch, ONE launch and ONE
+// wait for the whole batch.  A batch with a set above 64 * FMS_MAX_WORDS points runs the LARGE form of the kernel instead, with the rows of
+// its own set sizes tabulated here.
+extern "C" int icg_fm_ransac(icg_ctx *ctx, int n_sets, const int32_t *offsets, const float *pts1, const float *pts2, double thresh, double conf,
+                             uint8_t *mask) {
     if (!ctx || n_sets < 0) return ICG_ERR_INVALID;
     if (n_sets == 0) return ICG_OK;
     if (!offsets || !pts1 || !pts2 || !mask) return ICG_ERR_INVALID;
@@ -840,30 +598,42 @@ extern "C" int icg_fm_ransac_device(icg_ctx *ctx, int n_sets, const int32_t *off
         if (n < 0) return ICG_ERR_INVALID;
         seg_cap = std::max(seg_cap, n);
     }
-    if (seg_cap > 64 * FMS_MAX_WORDS) return icg_fm_ransac(ctx, n_sets, offsets, pts1, pts2, thresh, conf, mask);
-    seg_cap = (seg_cap + 63) & ~63;
+    const int total = offsets[n_sets];
+    if (total > ctx->cfg.max_points) return icg_fail(ctx, ICG_ERR_CAPACITY, "%d points > max_points %d", total, ctx->cfg.max_points);
+    const bool large = seg_cap > 64 * FMS_MAX_WORDS;
+    seg_cap          = (seg_cap + 63) & ~63;
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const size_t cells = (size_t) n_sets * seg_cap;
     std::vector<float> a(2 * cells, 0.f), b(2 * cells, 0.f);
     std::vector<int32_t> cnt((size_t) n_sets);
+    std::vector<double> tab(large ? (size_t) n_sets * (seg_cap + 1) : 0, 0.0);
     for (int s = 0; s < n_sets; s++) {
         const int n = offsets[s + 1] - offsets[s];
         cnt[(size_t) s] = n;
         memcpy(a.data() + 2 * (size_t) s * seg_cap, pts1 + 2 * (size_t) offsets[s], sizeof(float) * 2 * (size_t) n);
         memcpy(b.data() + 2 * (size_t) s * seg_cap, pts2 + 2 * (size_t) offsets[s], sizeof(float) * 2 * (size_t) n);
+        if (large && n >= 15) fm_denom_row(n, &tab[(size_t) s * (seg_cap + 1)]);
     }
     std::vector<uint8_t> m(cells, 0);
     icg_call c(ctx);
-    int rc = c.reserve(cells * (16 + 1) + sizeof(int32_t) * (size_t) n_sets + 4096);
+    int rc = c.reserve(cells * (16 + 1) + sizeof(int32_t) * (size_t) n_sets + sizeof(double) * tab.size() + 4096);
     if (rc) return rc;
-    const float2 *d_p1 = (const float2 *) c.in(a.data(), 2 * cells);
-    const float2 *d_p2 = (const float2 *) c.in(b.data(), 2 * cells);
-    const int32_t *d_n = c.in(cnt.data(), (size_t) n_sets);
+    const float2 *d_p1  = (const float2 *) c.in(a.data(), 2 * cells);
+    const float2 *d_p2  = (const float2 *) c.in(b.data(), 2 * cells);
+    const int32_t *d_n  = c.in(cnt.data(), (size_t) n_sets);
+    const double *d_tab = large ? c.in(tab.data(), tab.size()) : nullptr;
     if ((rc = c.seal())) return rc;
     uint8_t *d_m = c.out(m.data(), cells);
     ICG_LAUNCH_GUARD(c);
-    if ((rc = icg_fm_ransac_launch_sets(ctx, n_sets, seg_cap, d_n, d_p1, d_p2, thresh, conf, d_m))) return rc;
-    if ((rc = c.finish())) return rc;
+    rc = large ? fm_ransac_launch<true>(ctx, n_sets, seg_cap, d_n, d_p1, d_p2, thresh, conf, d_tab, seg_cap, d_m)
+               : icg_fm_ransac_launch_sets(ctx, n_sets, seg_cap, d_n, d_p1, d_p2, thresh, conf, d_m);
+    if (rc || (rc = c.finish())) return rc;
     for (int s = 0; s < n_sets; s++) memcpy(mask + offsets[s], m.data() + (size_t) s * seg_cap, (size_t) cnt[(size_t) s]);
     return ICG_OK;
+}
+
+// kept for callers of the earlier one-launch entry point: icg_fm_ransac is that form now
+extern "C" int icg_fm_ransac_device(icg_ctx *ctx, int n_sets, const int32_t *offsets, const float *pts1, const float *pts2, double thresh, double conf,
+                                    uint8_t *mask) {
+    return icg_fm_ransac(ctx, n_sets, offsets, pts1, pts2, thresh, conf, mask);
 }

@@ -363,6 +363,7 @@ extern "C" int icg_tracker_create(icg_ctx *ctx, int n_streams, const icg_tracker
         icg_tracker_destroy(t);
         return rc;
     };
+    if (int rc = icg_detect_check_grid(ctx, &t->grid)) return fail(rc);
     const size_t n = (size_t) n_streams, R = tc::MAX_ROWS;
     if (icg_hip_check(ctx, hipMalloc((void **) &t->d_streams, sizeof(tc::Stream) * n), "hipMalloc tracker blocks")) return fail(ICG_ERR_NOMEM);
     if (icg_hip_check(ctx, hipMemsetAsync(t->d_streams, 0, sizeof(tc::Stream) * n, ctx->stream), "memset blocks")) return fail(ICG_ERR_HIP);

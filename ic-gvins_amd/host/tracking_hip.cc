@@ -150,8 +150,7 @@ void DeviceContext::execute(StageBatch &b, const icg_detect_grid &grid, int max_
         hostprof::Scope hp(hostprof::DEV_RANSAC);
         int n = (int) b.rs_off.size() - 1;
         b.rs_mask.assign((size_t) b.rs_off.back(), 1);
-        // the one-launch form (every set's whole run inside its workgroup — the kernel of the device-resident tracker) rather than one
-        // launch + one wait per RANSAC chunk (icg_fm_ransac): identical masks (tests/test_gpu_geometry.py), one round trip
+        // one launch for every set: each set's whole run inside its workgroup, the kernel of the device-resident tracker
         abi_check(ctx_, icg_fm_ransac_device(ctx_, n, b.rs_off.data(), b.rs_p1.data(), b.rs_p2.data(), b.rs_thresh, b.rs_conf, b.rs_mask.data()),
                   "icg_fm_ransac_device");
     }

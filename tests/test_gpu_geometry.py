@@ -108,9 +108,9 @@ def test_fm_ransac_degenerate_all_identical(oracle, ctx1280):
 
 
 def test_fm_ransac_device_loop_equals_host_loop_and_oracle(oracle, ctx1280):
-    """icg_fm_ransac_device (k_fm_ransac_sets: subset draws from cv::RNG, seven-point solves, scoring and the best / niters recurrence of a
-    whole RANSAC run inside one workgroup — the kernel the device-resident tracker launches on its segments) against the host-looped entry
-    point and the oracle: identical inlier masks for clean and contaminated sets, many rounds (60 % outliers: niters stays in the hundreds),
+    """icg_fm_ransac_device and icg_fm_ransac (k_fm_ransac_sets: subset draws from cv::RNG, seven-point solves, scoring and the best /
+    niters recurrence of a whole RANSAC run inside one workgroup — the kernel the device-resident tracker launches on its segments) against
+    each other and the oracle: identical inlier masks for clean and contaminated sets, many rounds (60 % outliers: niters stays in the hundreds),
     sets below 15 points (left untouched), the degenerate all-identical set and a collinear lattice (checkSubset's RNG-consuming redraws);
     the iteration counts come from log / pow values tabulated by the host's libm (fm_denom_table)."""
     sets = []
@@ -135,6 +135,32 @@ def test_fm_ransac_device_loop_equals_host_loop_and_oracle(oracle, ctx1280):
             continue
         ok, exp, _, iters = oracle.fm_ransac(p1, p2)
         assert np.array_equal(got, exp), (k, iters, got.sum(), exp.sum())
+
+
+def test_fm_ransac_sets_above_1024_points(oracle, ctx1280):
+    """Sets larger than the tracker's 1024-point form (the inlier words no longer fit in LDS) mixed with small ones in one call: 1025,
+    1500 and 4000 points at 30-60 % outliers and a degenerate set of 1100 identical points (no valid subset). Both entry points must give
+    the oracle's mask for every set."""
+    sets = []
+    for seed, n, frac in ((21, 200, 0.3), (22, 10, 0.0), (23, 1025, 0.3), (24, 60, 0.5), (25, 1500, 0.6), (26, 4000, 0.45)):
+        p1, p2, _, _ = two_view(n, seed=seed, outlier_frac=frac, noise=0.3)
+        sets.append((p1, p2))
+    same = np.tile(np.array([[300.0, 150.0]], np.float32), (1100, 1))
+    sets.append((same, same))
+    offsets = np.cumsum([0] + [len(s[0]) for s in sets]).astype(np.int32)
+    assert offsets[-1] <= 8192
+    a, b = np.concatenate([s[0] for s in sets]), np.concatenate([s[1] for s in sets])
+    masks = (ctx1280.fm_ransac(offsets, a, b), ctx1280.fm_ransac_device(offsets, a, b))
+    for k, (p1, p2) in enumerate(sets):
+        if len(p1) < 15:
+            for m in masks:
+                assert np.all(m[offsets[k]:offsets[k + 1]] == 1)
+            continue
+        ok, exp, _, iters = oracle.fm_ransac(p1, p2)
+        for m in masks:
+            got = m[offsets[k]:offsets[k + 1]]
+            assert np.array_equal(got, exp), (k, iters, got.sum(), exp.sum())
+    assert masks[0][offsets[-2]:].sum() == 0
 
 
 def test_triangulate_matches_oracle(oracle, ctx1280):
