@@ -16,6 +16,21 @@
 // samples 1.56 -> 1.30 ms; one 200-sample interval 2.07 -> 1.80 ms) — the rest of a sample is the strictly sequential FP64 navigation update
 // (~1 300 dependent operations incl. six sin/cos and a dozen divisions in the Earth variant), which every lane carries redundantly.
 // Compute/latency bound (72 B in per sample, state on chip): reported as IMU samples/s, not against the HBM roofline.
+//
+// P2: the factor evaluation on an integration result (second half of this file), batched over independent factors, one 64-lane wavefront
+// per factor, two launches per call:
+//   k_preint_sqrt_info   S = LLT(cov^-1).matrixL()^T (preintegration_normal.cc:39-40, preintegration_earth.cc:39-40) with the arithmetic and the
+//                        order of the host layer's Preintegration::updateSqrtInformation: Gauss-Jordan with partial pivoting on the 15 x 30
+//                        augmented matrix in LDS (the entries of one elimination step are independent: lanes own entries; the pivot search is
+//                        a 16-lane reduction), mirrored lower triangle, column Cholesky (lane i owns row i).  Only + - * / sqrt, all correctly
+//                        rounded on both sides: S is bit-identical to the host's.
+//   k_preint_evaluate    residual 15 + Jacobians 15x7 | 15x9 | 15x7 | 15x9 (preintegration_normal.cc:38-142, preintegration_earth.cc:37-164,
+//                        preintegration_factor.h:45-69; quaternion helpers rotation.h:103-119).  Every lane carries the (uniform) geometry
+//                        redundantly, lane 0 lays the unwhitened 15 x 32 Jacobian and the residual out in LDS, then each lane owns 8 of the
+//                        15 + 480 outputs and forms each as the dense 15-term sum over k ascending from zero, as the host's Preintegration::evaluate
+//                        does.  The only primitives that may round differently from the host are sin / cos in rotvec2quat.
+// Latency bound like P1 (~8 KB in, ~4 KB out, a few thousand dependent FP64 operations per factor, no reuse across factors): reported as
+// factors/s, not against the HBM roofline.
 #include "dev_math.h"
 #include "icg_internal.h"
 
@@ -276,6 +291,311 @@ extern "C" int icg_preint_batch(icg_ctx *ctx, int variant, int n_intervals, cons
         icg_prof_scope ps(ctx, "preint");
         hipLaunchKernelGGL(k_preint, dim3(n_intervals), dim3(64), 0, ctx->stream, variant, d_off, d_imu, d_s0, d_par, d_cur, d_del,
                            d_jac, d_cov, d_dt, d_pn);
+    }
+    ICG_HIP(ctx, hipGetLastError());
+    return c.finish();
+}
+
+// ================================================================ P2 ================================================================
+namespace {
+// the host layer's P2 scales the axis by the reciprocal of the angle (dev_math.h's rotvec2quat, used by P1, divides): same order here
+__device__ __forceinline__ dq rotvec2quat_rcp(d3 rv) {
+    double angle = sqrt(rv.x * rv.x + rv.y * rv.y + rv.z * rv.z);
+    d3 axis      = rv;
+    if (angle > 0) axis = scl(1.0 / angle, rv);
+    double s = sin(0.5 * angle), c = cos(0.5 * angle);
+    return dq{s * axis.x, s * axis.y, s * axis.z, c};
+}
+__device__ __forceinline__ d3 q_vec(dq q) { return mk3(q.x, q.y, q.z); }
+// bottom-right 3x3 of quaternionleft(q) / quaternionright(q) (rotation.h:103-119)
+__device__ __forceinline__ m33 qleft_br(dq q) { return m_add(m_scale(m_eye(), q.w), m_skew(q_vec(q))); }
+__device__ __forceinline__ m33 qright_br(dq q) { return m_add(m_scale(m_eye(), q.w), m_scale(m_skew(q_vec(q)), -1.0)); }
+// bottom-right 3x3 of quaternionleft(a) * quaternionright(b): the 4-term sums over k ascending
+__device__ __forceinline__ m33 qleft_qright_br(dq a, dq b) {
+    double L[4][4], R[4][4];
+    L[0][0] = a.w, L[0][1] = -a.x, L[0][2] = -a.y, L[0][3] = -a.z, L[1][0] = a.x, L[2][0] = a.y, L[3][0] = a.z;
+    R[0][0] = b.w, R[0][1] = -b.x, R[0][2] = -b.y, R[0][3] = -b.z, R[1][0] = b.x, R[2][0] = b.y, R[3][0] = b.z;
+    const m33 sa = m_skew(q_vec(a)), sb = m_skew(q_vec(b));
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            L[1 + i][1 + j] = (i == j ? a.w : 0.0) + 1.0 * sa.a[i * 3 + j];
+            R[1 + i][1 + j] = (i == j ? b.w : 0.0) + -1.0 * sb.a[i * 3 + j];
+        }
+    m33 out;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            double s = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) s += L[1 + i][k] * R[k][1 + j];
+            out.a[i * 3 + j] = s;
+        }
+    return out;
+}
+} // namespace
+
+#define PE_W 30         // row length of the augmented matrix
+#define PE_U 33         // row length of the unwhitened block: 32 Jacobian columns (7 | 9 | 7 | 9) + the residual
+#define PE_NOUT (15 + 480)
+
+__global__ __launch_bounds__(64) void k_preint_sqrt_info(int n, const double *cov, double *sqrt_info, int32_t *status) {
+    __shared__ double w[15 * PE_W], L[225], fcol[15];
+    const int f = blockIdx.x, lane = threadIdx.x;
+    if (f >= n) return;
+    const double *C = cov + 225 * (size_t) f;
+    double *S       = sqrt_info + 225 * (size_t) f;
+    for (int e = lane; e < 15 * PE_W; e += 64) {
+        const int i = e / PE_W, j = e - i * PE_W;
+        w[e]        = j < 15 ? C[i * 15 + j] : (i == j - 15 ? 1.0 : 0.0);
+    }
+    for (int e = lane; e < 225; e += 64) L[e] = 0.0;
+    __syncthreads();
+    for (int c = 0; c < 15; c++) {
+        // first row r >= c of maximal |w[r][c]| (ties to the lower index): lanes c..14 hold a candidate, the others one that never wins
+        const bool cand = lane >= c && lane < 15;
+        double best     = cand ? fabs(w[lane * PE_W + c]) : -1.0;
+        int piv         = cand ? lane : 15;
+#pragma unroll
+        for (int m = 8; m >= 1; m >>= 1) {
+            const double ob = __shfl_xor(best, m);
+            const int op    = __shfl_xor(piv, m);
+            if (ob > best || (ob == best && op < piv)) best = ob, piv = op;
+        }
+        piv = __shfl(piv, 0);
+        if (piv < c || piv > 14) piv = c; // (a NaN column compares false everywhere: the host keeps row c)
+        if (w[piv * PE_W + c] == 0.0) {   // uniform: singular covariance
+            for (int e = lane; e < 225; e += 64) S[e] = 0.0;
+            if (lane == 0) status[f] = 1;
+            return;
+        }
+        if (piv != c && lane < PE_W) {
+            const double a = w[c * PE_W + lane], b = w[piv * PE_W + lane];
+            w[c * PE_W + lane] = b, w[piv * PE_W + lane] = a;
+        }
+        __syncthreads();
+        const double d = w[c * PE_W + c];
+        __syncthreads();
+        if (lane < PE_W) w[c * PE_W + lane] /= d;
+        if (lane < 15) fcol[lane] = w[lane * PE_W + c]; // (row c's own entry is not used)
+        __syncthreads();
+        for (int e = lane; e < 15 * PE_W; e += 64) {
+            const int r = e / PE_W, j = e - r * PE_W;
+            const double fr = fcol[r];
+            if (r != c && fr != 0.0) w[e] -= fr * w[c * PE_W + j];
+        }
+        __syncthreads();
+    }
+    // inverse = right half, lower triangle mirrored; column Cholesky, lane i owns row i: t = inv[i][j] - sum_k L[i][k] L[j][k], k ascending
+    const int i = lane < 15 ? lane : 14;
+    for (int j = 0; j < 15; j++) {
+        double t = w[(i >= j ? i : j) * PE_W + 15 + (i >= j ? j : i)];
+        for (int k = 0; k < j; k++) t -= L[i * 15 + k] * L[j * 15 + k];
+        const double ljj = sqrt(__shfl(t, j));
+        if (lane < 15 && lane >= j) L[lane * 15 + j] = lane == j ? ljj : t / ljj;
+        __syncthreads();
+    }
+    for (int e = lane; e < 225; e += 64) S[e] = L[(e % 15) * 15 + e / 15];
+    if (lane == 0) status[f] = 0;
+}
+
+__global__ __launch_bounds__(64) void k_preint_evaluate(int variant, int n, const double *delta_state, const double *jac, const double *delta_time,
+                                                        const double *env, const int32_t *pn_offsets, const double *pn, const double *points,
+                                                        const double *sqrt_info, const int32_t *status, double *residuals, double *jacobians) {
+    __shared__ double S[225], U[15 * PE_U];
+    const int f = blockIdx.x, lane = threadIdx.x;
+    if (f >= n) return;
+    double *r_out = residuals + 15 * (size_t) f;
+    double *J_out = jacobians ? jacobians + 480 * (size_t) f : nullptr;
+    if (status[f] != 0) { // singular covariance: zero rows
+        for (int o = lane; o < PE_NOUT; o += 64) {
+            if (o < 15)
+                r_out[o] = 0.0;
+            else if (J_out)
+                J_out[o - 15] = 0.0;
+        }
+        return;
+    }
+    for (int e = lane; e < 225; e += 64) S[e] = sqrt_info[225 * (size_t) f + e];
+    for (int e = lane; e < 15 * PE_U; e += 64) U[e] = 0.0;
+    __syncthreads();
+
+    const double *J15 = jac + 225 * (size_t) f, *pt = points + 32 * (size_t) f;
+    const nav_state d = load_state(delta_state + 16 * (size_t) f);
+    const d3 p0 = mk3(pt[0], pt[1], pt[2]), p1 = mk3(pt[16], pt[17], pt[18]);
+    const dq q0 = q_from_xyzw(pt + 3), q1 = q_from_xyzw(pt + 19);
+    const d3 v0 = mk3(pt[7], pt[8], pt[9]), bg0 = mk3(pt[10], pt[11], pt[12]), ba0 = mk3(pt[13], pt[14], pt[15]);
+    const d3 v1 = mk3(pt[23], pt[24], pt[25]), bg1 = mk3(pt[26], pt[27], pt[28]), ba1 = mk3(pt[29], pt[30], pt[31]);
+    const d3 gravity = mk3(0, 0, env[4 * (size_t) f]);
+    const d3 iewn    = mk3(env[4 * (size_t) f + 1], env[4 * (size_t) f + 2], env[4 * (size_t) f + 3]);
+    m33 dp_dbg, dp_dba, dv_dbg, dv_dba, dq_dbg;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            dp_dbg.a[i * 3 + j] = J15[PI_IDX(i, 9 + j)];
+            dp_dba.a[i * 3 + j] = J15[PI_IDX(i, 12 + j)];
+            dv_dbg.a[i * 3 + j] = J15[PI_IDX(3 + i, 9 + j)];
+            dv_dba.a[i * 3 + j] = J15[PI_IDX(3 + i, 12 + j)];
+            dq_dbg.a[i * 3 + j] = J15[PI_IDX(6 + i, 9 + j)];
+        }
+    const d3 dbg = sub(bg0, d.bg), dba = sub(ba0, d.ba);
+    const d3 corrected_p = add(add(d.p, m_vec(dp_dba, dba)), m_vec(dp_dbg, dbg));
+    const d3 corrected_v = add(add(d.v, m_vec(dv_dba, dba)), m_vec(dv_dbg, dbg));
+    const dq corrected_q = q_mul(d.q, rotvec2quat_rcp(m_vec(dq_dbg, dbg)));
+    const double T       = delta_time[f];
+    const m33 cnb0       = q_mat(q_inv(q0));
+    const d3 half_g_TT   = scl(T, scl(T, scl(0.5, gravity))); // ((0.5 g) T) T
+    d3 rp, rv;
+    dq qe;
+    // the blocks that differ between the variants: J0(0,0) J0(0,3) J0(3,0) J0(3,3) J0(6,3) | J2(3,0) J2(6,3) | J1(6,3)
+    m33 j0_00, j0_03, j0_30, j0_33, j0_63, j2_30, j2_63, j1_63;
+    if (variant == 0) {
+        const d3 dpn = sub(sub(sub(p1, p0), scl(T, v0)), half_g_TT);
+        const d3 dvn = sub(sub(v1, v0), scl(T, gravity));
+        const d3 rdp = q_rot(q_inv(q0), dpn), rdv = q_rot(q_inv(q0), dvn);
+        rp = sub(rdp, corrected_p), rv = sub(rdv, corrected_v);
+        qe    = q_mul(q_mul(q_inv(corrected_q), q_inv(q0)), q1);
+        j0_00 = m_scale(cnb0, -1.0);
+        j0_03 = m_skew(rdp);
+        j0_33 = m_skew(rdv);
+        j0_63 = m_scale(qleft_qright_br(q_mul(q_inv(q1), q0), corrected_q), -1.0);
+        j2_63 = qleft_br(qe);
+        j1_63 = m_mul(m_scale(qleft_br(q_mul(q_mul(q_inv(q1), q0), d.q)), -1.0), dq_dbg);
+    } else {
+        const m33 iewn_skew = m_skew(iewn);
+        d3 p_cor            = mk3(0, 0, 0);
+        for (int k = pn_offsets[f]; k < pn_offsets[f + 1]; k++) {
+            const double *row = pn + 4 * (size_t) k;
+            p_cor             = add(p_cor, scl(row[0], sub(mk3(row[1], row[2], row[3]), p0)));
+        }
+        p_cor          = m_vec(m_scale(iewn_skew, 2.0), p_cor);
+        const d3 v_cor = m_vec(m_scale(iewn_skew, 2.0), sub(p1, p0));
+        const dq qnn   = rotvec2quat_rcp(scl(T, neg3(iewn)));
+        const d3 dpn   = add(sub(sub(sub(p1, p0), scl(T, v0)), half_g_TT), p_cor);
+        const d3 dvn   = add(sub(sub(v1, v0), scl(T, gravity)), v_cor);
+        const dq qb0b1 = q_mul(q_mul(q_inv(q1), qnn), q0);
+        const d3 rdp = m_vec(cnb0, dpn), rdv = m_vec(cnb0, dvn);
+        rp = sub(rdp, corrected_p), rv = sub(rdv, corrected_v);
+        qe    = q_mul(qb0b1, corrected_q);
+        j0_00 = m_add(m_scale(cnb0, -1.0), m_scale(m_mul(m_scale(cnb0, 2.0), iewn_skew), -T));
+        j0_03 = m_skew(rdp);
+        j0_30 = m_mul(m_scale(cnb0, -2.0), iewn_skew);
+        j0_33 = m_skew(rdv);
+        j0_63 = qleft_qright_br(qb0b1, corrected_q);
+        j2_30 = m_mul(m_scale(cnb0, 2.0), iewn_skew);
+        j2_63 = m_scale(qright_br(qe), -1.0);
+        j1_63 = m_mul(qleft_br(q_mul(qb0b1, d.q)), dq_dbg);
+    }
+    const d3 rbg = sub(bg1, bg0), rba = sub(ba1, ba0);
+    if (lane == 0) {
+        // block (r0, c0) of the 15 x 32 Jacobian [J0 (cols 0..6) | J1 (7..15) | J2 (16..22) | J3 (23..31)]; column 32 = residual
+#define PE_PUT(r0, c0, blk)                                                                                                            \
+    {                                                                                                                                  \
+        const m33 b_ = (blk);                                                                                                          \
+        _Pragma("unroll") for (int i_ = 0; i_ < 3; i_++) _Pragma("unroll") for (int j_ = 0; j_ < 3; j_++)                               \
+            U[((r0) + i_) * PE_U + (c0) + j_] = b_.a[i_ * 3 + j_];                                                                     \
+    }
+        const double rr[15] = {rp.x, rp.y, rp.z, rv.x, rv.y, rv.z, 2 * qe.x, 2 * qe.y, 2 * qe.z, rbg.x, rbg.y, rbg.z, rba.x, rba.y, rba.z};
+#pragma unroll
+        for (int k = 0; k < 15; k++) U[k * PE_U + 32] = rr[k];
+        if (jacobians) {
+            PE_PUT(0, 0, j0_00)
+            PE_PUT(0, 3, j0_03)
+            PE_PUT(3, 3, j0_33)
+            PE_PUT(6, 3, j0_63)
+            PE_PUT(0, 16, cnb0)
+            PE_PUT(6, 16 + 3, j2_63)
+            if (variant != 0) {
+                PE_PUT(3, 0, j0_30)
+                PE_PUT(3, 16, j2_30)
+            }
+            PE_PUT(0, 7, m_scale(cnb0, -T))
+            PE_PUT(0, 7 + 3, m_scale(dp_dbg, -1.0))
+            PE_PUT(0, 7 + 6, m_scale(dp_dba, -1.0))
+            PE_PUT(3, 7, m_scale(cnb0, -1.0))
+            PE_PUT(3, 7 + 3, m_scale(dv_dbg, -1.0))
+            PE_PUT(3, 7 + 6, m_scale(dv_dba, -1.0))
+            PE_PUT(6, 7 + 3, j1_63)
+            PE_PUT(9, 7 + 3, m_scale(m_eye(), -1.0))
+            PE_PUT(12, 7 + 6, m_scale(m_eye(), -1.0))
+            PE_PUT(3, 23, cnb0)
+            PE_PUT(9, 23 + 3, m_eye())
+            PE_PUT(12, 23 + 6, m_eye())
+        }
+#undef PE_PUT
+    }
+    __syncthreads();
+    // whitening: out[i][col] = sum_k S[i][k] U[k][col], dense, k ascending from zero
+    const int n_out = jacobians ? PE_NOUT : 15;
+    for (int o = lane; o < n_out; o += 64) {
+        int i, col;
+        double *dst;
+        if (o < 15) {
+            i = o, col = 32, dst = r_out + o;
+        } else {
+            const int q = o - 15;
+            dst         = J_out + q;
+            if (q < 105)
+                i = q / 7, col = q - i * 7;
+            else if (q < 240)
+                i = (q - 105) / 9, col = 7 + (q - 105) - i * 9;
+            else if (q < 345)
+                i = (q - 240) / 7, col = 16 + (q - 240) - i * 7;
+            else
+                i = (q - 345) / 9, col = 23 + (q - 345) - i * 9;
+        }
+        double s = 0;
+#pragma unroll
+        for (int k = 0; k < 15; k++) s += S[i * 15 + k] * U[k * PE_U + col];
+        *dst = s;
+    }
+}
+
+extern "C" int icg_preint_evaluate_batch(icg_ctx *ctx, int variant, int n_factors, const double *delta_state, const double *jac,
+                                         const double *cov, const double *delta_time, const double *env, const int32_t *pn_offsets,
+                                         const double *pn, const double *points, double *residuals, double *jacobians, double *sqrt_info,
+                                         int32_t *status) {
+    if (!ctx) return ICG_ERR_INVALID;
+    if (variant != 0 && variant != 1) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_evaluate_batch: variant %d is neither 0 (Normal) nor 1 (Earth)", variant);
+    if (n_factors <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_evaluate_batch: n_factors = %d", n_factors);
+    if (!delta_state || !jac || !cov || !delta_time || !env || !points || !residuals || !status)
+        return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_evaluate_batch: NULL argument");
+    int total_pn = 0;
+    if (variant == 1) {
+        if (!pn_offsets) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_evaluate_batch: the Earth variant needs pn_offsets");
+        if (pn_offsets[0] < 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_evaluate_batch: pn_offsets[0] = %d", pn_offsets[0]);
+        for (int k = 0; k < n_factors; k++)
+            if (pn_offsets[k + 1] < pn_offsets[k]) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_evaluate_batch: pn_offsets not monotone at factor %d", k);
+        total_pn = pn_offsets[n_factors];
+        if (total_pn > 0 && !pn) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_evaluate_batch: NULL pn");
+    }
+    const size_t n = (size_t) n_factors;
+    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    icg_call c(ctx);
+    int rc = c.reserve(n * 8 * (16 + 225 + 225 + 1 + 4 + 32 + 15 + 480 + 225 + 1) + (n + 1) * 4 + (size_t) total_pn * 32 + 16 * 256);
+    if (rc) return rc;
+    const double *d_del = c.in(delta_state, 16 * n);
+    const double *d_jac = c.in(jac, 225 * n);
+    const double *d_cov = c.in(cov, 225 * n);
+    const double *d_dt  = c.in(delta_time, n);
+    const double *d_env = c.in(env, 4 * n);
+    const double *d_pts = c.in(points, 32 * n);
+    const int32_t *d_po = variant == 1 ? c.in(pn_offsets, n + 1) : nullptr;
+    const double *d_pn  = variant == 1 ? c.in(pn, 4 * (size_t) total_pn) : nullptr;
+    if ((rc = c.seal())) return rc;
+    double *d_r   = c.out(residuals, 15 * n);
+    double *d_J   = jacobians ? c.out(jacobians, 480 * n) : nullptr;
+    double *d_S   = c.out(sqrt_info, 225 * n); // (kept on the device only when the caller does not ask for it)
+    int32_t *d_st = c.out(status, n);
+    ICG_LAUNCH_GUARD(c);
+    {
+        icg_prof_scope ps(ctx, "preint_eval");
+        hipLaunchKernelGGL(k_preint_sqrt_info, dim3(n_factors), dim3(64), 0, ctx->stream, n_factors, d_cov, d_S, d_st);
+        hipLaunchKernelGGL(k_preint_evaluate, dim3(n_factors), dim3(64), 0, ctx->stream, variant, n_factors, d_del, d_jac, d_dt, d_env, d_po,
+                           d_pn, d_pts, d_S, d_st, d_r, d_J);
     }
     ICG_HIP(ctx, hipGetLastError());
     return c.finish();

@@ -359,7 +359,12 @@ int icgh_core_order_selftest(uint64_t seed, int n_first, int n_more, int rounds)
 } // extern "C"
 
 // ---- back-end test/driver entry points -----------------------------------------------------------------------------------
+#include <algorithm>
+#include <cmath>
+#include <memory>
+
 #include "factors.h"
+#include "host_pool.h"
 #include "object_pool.h"
 #include "misc_hip.h"
 #include "solver_hip.h"
@@ -776,6 +781,201 @@ int icgh_backend_preint(int variant, int n, const int32_t *offsets, const double
             }
         }
         icg_ctx_destroy(ctx);
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -1;
+    }
+}
+
+// The same integration, evaluated twice on the SAME objects: once per factor on the host (PreintegrationFactor::Evaluate) and once through
+// Preintegration::evaluateBatch (icg_preint_evaluate_batch), so both paths can be compared on identical inputs.  Arguments as
+// icgh_backend_preint; outputs per interval for the host / the device path: residuals 15, jacobians 480, sqrt_info 225 (the host's
+// sqrt_information_ / the kernel's), ok (1 = evaluated; 0 = the factor cannot be evaluated, e.g. singular covariance: zero rows).
+// Without the device entry point in the build nothing is computed: -4 and "icg_preint_evaluate_batch is not in this build".
+int icgh_backend_preint_device(int variant, int n, const int32_t *offsets, const double *imu, const double *state0, const double *params9,
+                               const double *eval_point, double *cur_state, double *residuals_host, double *jacobians_host,
+                               double *residuals_dev, double *jacobians_dev, double *sqrt_info_host, double *sqrt_info_dev, int32_t *ok_host,
+                               int32_t *ok_dev, char *err, int errlen) {
+    try {
+        if (!Preintegration::evaluateBatchAvailable()) {
+            set_err(err, errlen, "icg_preint_evaluate_batch is not in this build");
+            return -4;
+        }
+        auto P          = std::make_shared<IntegrationParameters>();
+        P->gyr_arw      = params9[0];
+        P->acc_vrw      = params9[1];
+        P->gyr_bias_std = params9[2];
+        P->acc_bias_std = params9[3];
+        P->corr_time    = params9[4];
+        P->gravity      = params9[5];
+        P->iewn         = Vector3d(params9[6], params9[7], params9[8]);
+        icg_ctx_config cfg{};
+        cfg.device = 0, cfg.width = 64, cfg.height = 64, cfg.n_slots = 1, cfg.max_batch = 1, cfg.max_points = 64;
+        icg_ctx *ctx = nullptr;
+        if (icg_ctx_create(&cfg, &ctx) != ICG_OK) {
+            set_err(err, errlen, icg_last_error(nullptr));
+            return -1;
+        }
+        auto mk_imu = [&](int row) {
+            const double *p = imu + 8 * (size_t) row;
+            IMU s;
+            s.time = p[0], s.dt = p[1];
+            s.dtheta = Vector3d(p[2], p[3], p[4]);
+            s.dvel   = Vector3d(p[5], p[6], p[7]);
+            return s;
+        };
+        vector<std::shared_ptr<Preintegration>> pre;
+        vector<Preintegration *> raw;
+        vector<const Preintegration *> craw;
+        for (int k = 0; k < n; k++) {
+            const double *s = state0 + 16 * (size_t) k;
+            IntegrationState st;
+            st.p = Vector3d(s[0], s[1], s[2]);
+            st.q = Quaterniond{s[3], s[4], s[5], s[6]};
+            st.v = Vector3d(s[7], s[8], s[9]), st.bg = Vector3d(s[10], s[11], s[12]), st.ba = Vector3d(s[13], s[14], s[15]);
+            auto p = std::make_shared<Preintegration>(P, mk_imu(offsets[k]), st, variant ? Preintegration::EARTH : Preintegration::NORMAL);
+            for (int row = offsets[k] + 1; row < offsets[k + 1]; row++) p->addNewImu(mk_imu(row));
+            pre.push_back(p);
+            raw.push_back(p.get());
+            craw.push_back(p.get());
+        }
+        std::string e;
+        if (!Preintegration::integrateBatch(ctx, raw, &e)) {
+            set_err(err, errlen, e.c_str());
+            icg_ctx_destroy(ctx);
+            return -2;
+        }
+        memset(residuals_host, 0, sizeof(double) * 15 * (size_t) n);
+        memset(jacobians_host, 0, sizeof(double) * 480 * (size_t) n);
+        for (int k = 0; k < n; k++) {
+            const IntegrationState &c = pre[(size_t) k]->currentState();
+            double *o = cur_state + 16 * (size_t) k;
+            o[0] = c.p[0], o[1] = c.p[1], o[2] = c.p[2], o[3] = c.q.x, o[4] = c.q.y, o[5] = c.q.z, o[6] = c.q.w;
+            for (int i = 0; i < 3; i++) o[7 + i] = c.v[i], o[10 + i] = c.bg[i], o[13 + i] = c.ba[i];
+            PreintegrationFactor f(pre[(size_t) k]);
+            const double *ep    = eval_point + 32 * (size_t) k;
+            const double *pp[4] = {ep, ep + 7, ep + 16, ep + 23};
+            double *J           = jacobians_host + 480 * (size_t) k;
+            double *jj[4]       = {J, J + 105, J + 240, J + 345};
+            ok_host[k]          = f.Evaluate(pp, residuals_host + 15 * (size_t) k, jj) ? 1 : 0;
+            memcpy(sqrt_info_host + 225 * (size_t) k, pre[(size_t) k]->sqrtInformation().data(), sizeof(double) * 225);
+        }
+        vector<char> ok;
+        const bool done = Preintegration::evaluateBatch(ctx, craw, eval_point, residuals_dev, jacobians_dev, &ok, &e, sqrt_info_dev);
+        icg_ctx_destroy(ctx);
+        if (!done) {
+            set_err(err, errlen, e.c_str());
+            return -3;
+        }
+        for (int k = 0; k < n; k++) ok_dev[k] = ok[(size_t) k];
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -1;
+    }
+}
+
+// Timing of P2 on one set of intervals (profiles/preint_eval_probe.py): integrated once (one icg_preint_batch launch), then evaluated `reps`
+// times (a) by PreintegrationFactor::Evaluate, one call per factor, on a HostPool of `threads` threads and (b) by one
+// Preintegration::evaluateBatch call.  out6: host seconds (best of reps), evaluateBatch wall seconds incl. packing and transfers (best),
+// device time of the two kernels per call [ms] (mean over reps, event-timed), max |r_dev - r_host|, max |J_dev - J_host|, factors evaluated.
+int icgh_backend_preint_eval_time(int variant, int n, const int32_t *offsets, const double *imu, const double *state0, const double *params9,
+                                  const double *eval_point, int threads, int reps, double *out6, char *err, int errlen) {
+    try {
+        if (!Preintegration::evaluateBatchAvailable()) {
+            set_err(err, errlen, "icg_preint_evaluate_batch is not in this build");
+            return -4;
+        }
+        auto P          = std::make_shared<IntegrationParameters>();
+        P->gyr_arw      = params9[0];
+        P->acc_vrw      = params9[1];
+        P->gyr_bias_std = params9[2];
+        P->acc_bias_std = params9[3];
+        P->corr_time    = params9[4];
+        P->gravity      = params9[5];
+        P->iewn         = Vector3d(params9[6], params9[7], params9[8]);
+        icg_ctx_config cfg{};
+        cfg.device = 0, cfg.width = 64, cfg.height = 64, cfg.n_slots = 1, cfg.max_batch = 1, cfg.max_points = 64;
+        icg_ctx *ctx = nullptr;
+        if (icg_ctx_create(&cfg, &ctx) != ICG_OK) {
+            set_err(err, errlen, icg_last_error(nullptr));
+            return -1;
+        }
+        vector<std::shared_ptr<Preintegration>> pre;
+        vector<std::unique_ptr<PreintegrationFactor>> factors;
+        vector<Preintegration *> raw;
+        vector<const Preintegration *> craw;
+        for (int k = 0; k < n; k++) {
+            auto mk_imu = [&](int row) {
+                const double *p = imu + 8 * (size_t) row;
+                IMU s;
+                s.time = p[0], s.dt = p[1];
+                s.dtheta = Vector3d(p[2], p[3], p[4]);
+                s.dvel   = Vector3d(p[5], p[6], p[7]);
+                return s;
+            };
+            const double *s = state0 + 16 * (size_t) k;
+            IntegrationState st;
+            st.p = Vector3d(s[0], s[1], s[2]);
+            st.q = Quaterniond{s[3], s[4], s[5], s[6]};
+            st.v = Vector3d(s[7], s[8], s[9]), st.bg = Vector3d(s[10], s[11], s[12]), st.ba = Vector3d(s[13], s[14], s[15]);
+            auto p = std::make_shared<Preintegration>(P, mk_imu(offsets[k]), st, variant ? Preintegration::EARTH : Preintegration::NORMAL);
+            for (int row = offsets[k] + 1; row < offsets[k + 1]; row++) p->addNewImu(mk_imu(row));
+            pre.push_back(p);
+            raw.push_back(p.get());
+            craw.push_back(p.get());
+            factors.emplace_back(new PreintegrationFactor(p));
+        }
+        std::string e;
+        if (!Preintegration::integrateBatch(ctx, raw, &e)) {
+            set_err(err, errlen, e.c_str());
+            icg_ctx_destroy(ctx);
+            return -2;
+        }
+        const size_t N = (size_t) n;
+        vector<double> rh(15 * N), Jh(480 * N), rd(15 * N), Jd(480 * N);
+        vector<char> okh(N, 0), okd;
+        HostPool pool(threads < 1 ? 1 : threads);
+        double best_host = -1, best_dev = -1;
+        for (int rep = 0; rep < reps + 1; rep++) { // (the first pass pages everything in and is not timed)
+            auto a = std::chrono::steady_clock::now();
+            pool.parallelFor(n, [&](int k) {
+                const double *ep    = eval_point + 32 * (size_t) k;
+                const double *pp[4] = {ep, ep + 7, ep + 16, ep + 23};
+                double *J           = Jh.data() + 480 * (size_t) k;
+                double *jj[4]       = {J, J + 105, J + 240, J + 345};
+                okh[(size_t) k]     = factors[(size_t) k]->Evaluate(pp, rh.data() + 15 * (size_t) k, jj) ? 1 : 0;
+            });
+            const double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count();
+            if (rep > 0 && (best_host < 0 || t < best_host)) best_host = t;
+        }
+        int launches = 0;
+        double ms    = 0;
+        for (int rep = 0; rep < reps + 1; rep++) {
+            if (rep == 1) icg_prof_enable(ctx, 1);
+            auto a = std::chrono::steady_clock::now();
+            if (!Preintegration::evaluateBatch(ctx, craw, eval_point, rd.data(), Jd.data(), &okd, &e)) {
+                set_err(err, errlen, e.c_str());
+                icg_ctx_destroy(ctx);
+                return -3;
+            }
+            const double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count();
+            if (rep > 0 && (best_dev < 0 || t < best_dev)) best_dev = t;
+        }
+        icg_prof_get(ctx, "preint_eval", &launches, &ms);
+        icg_ctx_destroy(ctx);
+        double dr = 0, dJ = 0, evaluated = 0;
+        for (size_t k = 0; k < N; k++) {
+            if (okh[k] != okd[k]) {
+                set_err(err, errlen, ("host and device disagree on whether factor " + std::to_string(k) + " can be evaluated").c_str());
+                return -5;
+            }
+            evaluated += okh[k] ? 1 : 0;
+            for (int i = 0; i < 15; i++) dr = std::max(dr, std::fabs(rd[15 * k + i] - rh[15 * k + i]));
+            for (int i = 0; i < 480; i++) dJ = std::max(dJ, std::fabs(Jd[480 * k + i] - Jh[480 * k + i]));
+        }
+        out6[0] = best_host, out6[1] = best_dev, out6[2] = launches > 0 ? ms / launches : 0.0, out6[3] = dr, out6[4] = dJ, out6[5] = evaluated;
         return 0;
     } catch (const std::exception &e) {
         set_err(err, errlen, e.what());

@@ -243,7 +243,7 @@ private:
 // symmetric eigen-decomposition (Householder tridiagonalisation + implicit QL), eigenvalues ascending, evecs row-major with eigenvectors in columns
 void symmetricEigen(int n, const vector<double> &A, vector<double> &evals, vector<double> &evecs);
 
-// ---- preintegration (P1 on device, P2 on host) -------------------------------------------------------------------------
+// ---- preintegration (P1 on device; P2 on host per factor, or batched on device) -------------------------------------------------------------------------
 struct IMU { // common/types.h:48-56
     double time, dt;
     Vector3d dtheta, dvel;
@@ -279,6 +279,14 @@ public:
     const Vector3d &earthRate() const { return iewn_; }
     // integrate every dirty interval of the list with a single icg_preint_batch launch
     static bool integrateBatch(icg_ctx *ctx, const vector<Preintegration *> &list, std::string *err = nullptr);
+    // P2 on the device: residual 15 (and, unless `jacobians` is null, the Jacobians 480 = 15x7 | 15x9 | 15x7 | 15x9) of every factor of the
+    // list at its evaluation point (points: n x 32 = pose0[7] mix0[9] pose1[7] mix1[9]) through icg_preint_evaluate_batch, one call per
+    // variant present.  ok[k] = 0 (and zero rows) for a factor that is not integrated for its current buffer / start state or whose
+    // covariance is singular: the two conditions under which evaluate() returns false.  sqrt_info (optional, n x 225): the square-root
+    // information the device formed.  Returns false with *err set when a call fails or the entry point is not in this build.
+    static bool evaluateBatch(icg_ctx *ctx, const vector<const Preintegration *> &list, const double *points, double *residuals,
+                              double *jacobians, vector<char> *ok, std::string *err = nullptr, double *sqrt_info = nullptr);
+    static bool evaluateBatchAvailable(); // icg_preint_evaluate_batch is in this build
     const IntegrationState &currentState() const { return current_state_; }
     const IntegrationState &deltaState() const { return delta_state_; }
     double deltaTime() const { return delta_time_; }
@@ -286,6 +294,7 @@ public:
     // PreintegrationFactor::Evaluate body (preintegration_factor.h:45-69): residual 15, Jacobians 15x7,15x9,15x7,15x9
     bool evaluate(const double *const *parameters, double *residuals, double **jacobians) const;
     Variant variant() const { return variant_; }
+    const vector<double> &sqrtInformation() const { return sqrt_information_; } // 15x15 row-major; zeros while the covariance is singular
 
 private:
     std::shared_ptr<IntegrationParameters> parameters_;

@@ -1,12 +1,17 @@
 // Preintegration on the HIP C ABI: P1 (the per-sample inner loop) runs batched on the device through icg_preint_batch;
 // P2 (residual + Jacobians, preintegration_normal.cc:38-142 / preintegration_earth.cc:37-164, wrapped by
 // preintegration_factor.h:45-69) is a handful of 3x3 / 15x15 operations per factor (<= 15 factors per solve) and stays
-// on the host, in the Ceres callback thread that asks for it.
+// on the host, in the Ceres callback thread that asks for it.  evaluateBatch() is the same evaluation for MANY factors at once on the
+// device (icg_preint_evaluate_batch): for callers that hold thousands of integrated intervals, not for the per-factor Ceres callback.
 #include <cmath>
 #include <cstring>
 
 #include "earth.h"
 #include "factors.h"
+
+// A build of this layer on another implementation of the C ABI may not have the entry point: the reference stays weak (null when absent)
+// and evaluateBatch() reports it; the product library links libicgvins_hip.so, which defines it.
+#pragma weak icg_preint_evaluate_batch
 
 namespace icg {
 
@@ -197,6 +202,62 @@ bool Preintegration::integrateBatch(icg_ctx *ctx, const vector<Preintegration *>
             p->pn_.assign(pn.begin() + 4 * (long) b, pn.begin() + 4 * (long) (b + cnt - 1));
             p->updateSqrtInformation();
             p->dirty_ = false;
+        }
+    }
+    return true;
+}
+
+bool Preintegration::evaluateBatchAvailable() { return &icg_preint_evaluate_batch != nullptr; }
+
+bool Preintegration::evaluateBatch(icg_ctx *ctx, const vector<const Preintegration *> &list, const double *points, double *residuals,
+                                   double *jacobians, vector<char> *ok, std::string *err, double *sqrt_info) {
+    if (!evaluateBatchAvailable()) {
+        if (err) *err = "icg_preint_evaluate_batch is not in this build";
+        return false;
+    }
+    const size_t n_all = list.size();
+    if (ok) ok->assign(n_all, 0);
+    memset(residuals, 0, sizeof(double) * 15 * n_all);
+    if (jacobians) memset(jacobians, 0, sizeof(double) * 480 * n_all);
+    if (sqrt_info) memset(sqrt_info, 0, sizeof(double) * 225 * n_all);
+    for (int variant = 0; variant < 2; variant++) {
+        vector<size_t> idx; // the integrated factors of this variant, list order
+        for (size_t k = 0; k < n_all; k++)
+            if ((int) list[k]->variant_ == variant && !list[k]->dirty_) idx.push_back(k);
+        if (idx.empty()) continue;
+        const size_t n = idx.size();
+        vector<double> del(16 * n), jac(225 * n), cov(225 * n), dt(n), env(4 * n), pts(32 * n), pn;
+        vector<int32_t> pn_off{0};
+        for (size_t j = 0; j < n; j++) {
+            const Preintegration &p = *list[idx[j]];
+            stateToArray(p.delta_state_, &del[16 * j]);
+            memcpy(&jac[225 * j], p.jacobian_.data(), sizeof(double) * 225);
+            memcpy(&cov[225 * j], p.covariance_.data(), sizeof(double) * 225);
+            dt[j]          = p.delta_time_;
+            env[4 * j]     = p.parameters_->gravity;
+            env[4 * j + 1] = p.iewn_[0], env[4 * j + 2] = p.iewn_[1], env[4 * j + 3] = p.iewn_[2];
+            memcpy(&pts[32 * j], points + 32 * idx[j], sizeof(double) * 32);
+            if (variant == (int) EARTH) {
+                pn.insert(pn.end(), p.pn_.begin(), p.pn_.begin() + (long) (p.pn_.size() / 4 * 4));
+                pn_off.push_back((int32_t) (pn.size() / 4));
+            }
+        }
+        vector<double> r(15 * n), J(jacobians ? 480 * n : 0), S(sqrt_info ? 225 * n : 0);
+        vector<int32_t> status(n);
+        if (pn.empty()) pn.resize(4); // (a valid pointer for a batch without rows)
+        int rc = icg_preint_evaluate_batch(ctx, variant, (int) n, del.data(), jac.data(), cov.data(), dt.data(), env.data(),
+                                           variant == (int) EARTH ? pn_off.data() : nullptr, variant == (int) EARTH ? pn.data() : nullptr,
+                                           pts.data(), r.data(), jacobians ? J.data() : nullptr, sqrt_info ? S.data() : nullptr, status.data());
+        if (rc != ICG_OK) {
+            if (err) *err = icg_last_error(ctx);
+            return false;
+        }
+        for (size_t j = 0; j < n; j++) {
+            const size_t k = idx[j];
+            memcpy(residuals + 15 * k, &r[15 * j], sizeof(double) * 15);
+            if (jacobians) memcpy(jacobians + 480 * k, &J[480 * j], sizeof(double) * 480);
+            if (sqrt_info) memcpy(sqrt_info + 225 * k, &S[225 * j], sizeof(double) * 225);
+            if (ok) (*ok)[k] = status[j] == 0 ? 1 : 0;
         }
     }
     return true;

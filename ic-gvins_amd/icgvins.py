@@ -17,7 +17,7 @@ EXPORTS = [
     "icg_dev_free", "icg_dev_upload", "icg_dev_download", "icg_frames_preprocess", "icg_frame_download",
     "icg_lk_track", "icg_lk_track_fb", "icg_undistort_points", "icg_distort_points", "icg_predict_mappoints",
     "icg_predict_rotation", "icg_fm_ransac", "icg_fm_ransac_device", "icg_detect", "icg_triangulate", "icg_reproj_eval_batch",
-    "icg_reproj_set_factors", "icg_reproj_stage_factors", "icg_reproj_commit_factors", "icg_reproj_eval_resident", "icg_reproj_accumulate_normal", "icg_preint_batch",
+    "icg_reproj_set_factors", "icg_reproj_stage_factors", "icg_reproj_commit_factors", "icg_reproj_eval_resident", "icg_reproj_accumulate_normal", "icg_preint_batch", "icg_preint_evaluate_batch",
     "icg_ins_mechanize_batch", "icg_ins_camera_pose_batch", "icg_reproj_schur", "icg_reproj_backsub", "icg_reproj_cost", "icg_reproj_landmark_diag",
     "icg_reproj_error_batch", "icg_reproj_set_windows", "icg_reproj_eval_windows", "icg_reproj_schur_windows",
     "icg_reproj_schur_windows_view", "icg_reproj_reserve_windows", "icg_reproj_eval_resident_view", "icg_reproj_backsub_windows", "icg_reproj_cost_windows", "icg_reproj_fetch_residuals", "icg_reproj_chi2_cull",
@@ -427,6 +427,23 @@ class Context:
         self._ck(self.lib.icg_preint_batch(self.h, int(variant), n, _p(offsets), _p(imu), _p(state0), _p(_f64(params)),
                                             _p(cur), _p(delta), _p(jac), _p(cov), _p(dt), _p(pn)), "icg_preint_batch")
         return cur, delta, jac, cov, dt, pn
+
+    # ---- P2
+    def preint_evaluate_batch(self, variant, delta, jac, cov, dt, env, points, pn_offsets=None, pn=None, want_jac=True):
+        """icg_preint_evaluate_batch -> (residuals n x 15, jacobians n x 480 or None, sqrt_info n x 15 x 15, status n)"""
+        points = _f64(points).reshape(-1, 32)
+        n = points.shape[0]
+        delta, jac, cov = _f64(delta).reshape(n, 16), _f64(jac).reshape(n, 225), _f64(cov).reshape(n, 225)
+        dt, env = _f64(dt).reshape(n), _f64(env).reshape(n, 4)
+        po = None if pn_offsets is None else _i32(pn_offsets)
+        pnr = None if pn is None else _f64(pn).reshape(-1, 4)
+        res = np.zeros((n, 15))
+        J = np.zeros((n, 480)) if want_jac else None
+        S = np.zeros((n, 15, 15))
+        status = np.zeros(n, np.int32)
+        self._ck(self.lib.icg_preint_evaluate_batch(self.h, int(variant), n, _p(delta), _p(jac), _p(cov), _p(dt), _p(env), _p(po), _p(pnr),
+                                                     _p(points), _p(res), _p(J), _p(S), _p(status)), "icg_preint_evaluate_batch")
+        return res, J, S, status
 
     # ---- f4
     def ins_mechanize_batch(self, offsets, imu, cfg8, states23, want_traj=True):

@@ -264,6 +264,21 @@ int icg_preint_batch(icg_ctx *ctx, int variant, int n_intervals, const int32_t *
                      const double *state0, const double *params, double *cur_state, double *delta_state, double *jac,
                      double *cov, double *delta_time, double *pn);
 
+/* ---- P2: PreintegrationFactor::Evaluate (preintegration/preintegration_factor.h:45-69 -> PreintegrationNormal::evaluate /
+ * ::residualJacobianPose0..Mix1, preintegration_normal.cc:38-142; PreintegrationEarth, preintegration_earth.cc:37-164), batched over
+ * independent factors: the whitened 15-residual and its four Jacobian blocks at one evaluation point per factor.
+ * Inputs per factor, in the layout icg_preint_batch writes: delta_state 16, jac 225, cov 225, delta_time 1; env 4 = gravity, iewn[3]
+ * (per factor: one call serves intervals of different stations); points 32 = pose0[7] mix0[9] pose1[7] mix1[9] (p3, q4 xyzw | v3, bg3,
+ * ba3).  Earth variant only: factor k owns the rows [pn_offsets[k], pn_offsets[k+1]) of pn (rows of 4: dt, position — the pn_ list,
+ * preintegration_earth.cc:235, summed in row order); pn_offsets and pn may be NULL for variant 0.
+ * Outputs per factor: residuals 15; jacobians 480 = 15x7 | 15x9 | 15x7 | 15x9, each row-major (NULL: residual only);
+ * sqrt_info 225 = LLT(cov^-1).matrixL()^T (NULL: not returned); status 0 ok, 1 singular covariance (a zero pivot in the inversion, e.g.
+ * an interval of a single IMU sample) — the output rows of such a factor are zero. */
+int icg_preint_evaluate_batch(icg_ctx *ctx, int variant, int n_factors, const double *delta_state, const double *jac,
+                              const double *cov, const double *delta_time, const double *env, const int32_t *pn_offsets,
+                              const double *pn, const double *points, double *residuals, double *jacobians, double *sqrt_info,
+                              int32_t *status);
+
 /* ---- f3 (SURVEY.md §8 "next" row): per-observation arithmetic of GVINS::gvinsOutlierCulling (ic_gvins.cc:1035-1128) and
  * GVINS::parametersStatistic (ic_gvins.cc:930-1033).  Observation i = landmark lm_idx[i] (world position pw, n_lm x 3) seen in
  * keyframe pose_idx[i] (poses12: n_poses x 12, R row-major camera->world | t) at the undistorted key point pix[i]:
