@@ -58,6 +58,18 @@ struct icg_partition {
     icg_asm_plan plan;
 };
 
+// Resident marginalization priors (marg.hip): everything icg_marg_prior_evaluate needs besides x.  The buffers grow on demand and are
+// freed with the context; n = 0: no set is resident.
+struct icg_marg_set {
+    int n = 0, n_blocks = 0;
+    int64_t total_r = 0, total_x = 0, total_j = 0, total_jac = 0, max_jac = 0; // elements: residuals, parameters, J0, Jacobian blocks (all / largest window)
+    double *d_J = nullptr;  // 2 x total_j: J0 row-major | J0 transposed
+    double *d_e0 = nullptr, *d_x0 = nullptr;
+    char *d_meta = nullptr; // offsets and block layout (marg.hip marg_view)
+    size_t J_cap = 0, e0_cap = 0, x0_cap = 0, meta_cap = 0; // bytes
+    std::vector<int64_t> h_meta;
+};
+
 struct icg_ctx {
     icg_ctx_config cfg{};
     hipStream_t stream = nullptr;
@@ -122,6 +134,7 @@ struct icg_ctx {
     int32_t *d_lmwin = nullptr; // window of every landmark
     int lmwin_cap = 0;
 
+    icg_marg_set marg;
 
     icg_camera cam{};
     bool has_cam = false;

@@ -983,6 +983,142 @@ int icgh_backend_preint_eval_time(int variant, int n, const int32_t *offsets, co
     }
 }
 
+// M4 on raw arrays, for comparison and timing (profiles/marg_factor_probe.py): the priors of n_windows windows in the layout of
+// icg_marg_prior_set, evaluated at n_points points (x: n_points sets laid out like x0).  mode 0: every window by evaluateMargPrior on a
+// HostPool of host_threads threads, gradient J0^T e and e . e by the same sequential sums as the kernel; mode 1: one
+// MarginalizationPriorSet::set, then one evaluate per point.  Outputs per point, point after point: residuals (sum r), jacobians (sum of
+// r * sum(size), may be NULL), gradient (sum r, may be NULL), sq_norm (n_windows, may be NULL).  The points are evaluated reps + 1 times,
+// the first pass untimed; seconds[0] = the set (mode 1; 0 in mode 0), seconds[1] = the fastest evaluation of one point.
+// Without the device entry points in the build mode 1 computes nothing: -4 and "icg_marg_prior_set is not in this build".
+int icgh_backend_marg_factor(int mode, int n_windows, const int32_t *r, const int32_t *block_off, const int32_t *block_size,
+                             const int32_t *block_index, const double *x0, const double *J0, const double *e0, int n_points, const double *x,
+                             int host_threads, int reps, double *residuals, double *jacobians, double *gradient, double *sq_norm,
+                             double *seconds, char *err, int errlen) {
+    try {
+        if (mode != 0 && mode != 1) {
+            set_err(err, errlen, "icgh_backend_marg_factor: mode is neither 0 (host) nor 1 (device)");
+            return -1;
+        }
+        if (mode == 1 && !MarginalizationPriorSet::available()) {
+            set_err(err, errlen, "icg_marg_prior_set is not in this build");
+            return -4;
+        }
+        if (n_windows <= 0 || n_points <= 0 || !r || !block_off || !block_size || !block_index || !x0 || !J0 || !e0 || !x || !residuals || !seconds) {
+            set_err(err, errlen, "icgh_backend_marg_factor: invalid argument");
+            return -1;
+        }
+        const size_t W = (size_t) n_windows;
+        vector<size_t> e_off(W + 1, 0), x_off(W + 1, 0), j_off(W + 1, 0), jac_off(W + 1, 0);
+        vector<int> size(block_size, block_size + block_off[W]), index(block_index, block_index + block_off[W]);
+        vector<const double *> x0_ptr((size_t) block_off[W]);
+        vector<MargPriorView> views(W);
+        for (size_t w = 0; w < W; w++) {
+            size_t xs = 0;
+            bool ok   = r[w] > 0 && block_off[w + 1] >= block_off[w] && (w > 0 || block_off[0] == 0);
+            for (int b = block_off[w]; ok && b < block_off[w + 1]; b++) {
+                ok = size[(size_t) b] > 0 && index[(size_t) b] >= 0 &&
+                     index[(size_t) b] + MarginalizationInfo::localSize(size[(size_t) b]) <= r[w];
+                x0_ptr[(size_t) b] = x0 + x_off[w] + xs;
+                xs += (size_t) size[(size_t) b];
+            }
+            if (!ok) {
+                set_err(err, errlen, ("icgh_backend_marg_factor: window " + std::to_string(w) + " is not a valid prior").c_str());
+                return -1;
+            }
+            MargPriorView &v = views[w];
+            v.r = r[w], v.n_blocks = block_off[w + 1] - block_off[w];
+            v.size = size.data() + block_off[w], v.index = index.data() + block_off[w], v.x0 = x0_ptr.data() + block_off[w];
+            v.J0 = J0 + j_off[w], v.e0 = e0 + e_off[w];
+            e_off[w + 1] = e_off[w] + (size_t) r[w], x_off[w + 1] = x_off[w] + xs;
+            j_off[w + 1] = j_off[w] + (size_t) r[w] * r[w], jac_off[w + 1] = jac_off[w] + (size_t) r[w] * xs;
+        }
+        const size_t R = e_off[W], X = x_off[W], NJ = jac_off[W];
+        const int passes = (reps > 0 ? reps : 0) + 1;
+        double best = -1;
+        seconds[0] = seconds[1] = 0;
+        auto clock = [] { return std::chrono::steady_clock::now(); };
+        auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(clock() - a).count(); };
+        if (mode == 0) {
+            HostPool pool(host_threads < 1 ? 1 : host_threads);
+            for (int rep = 0; rep < passes; rep++)
+                for (int p = 0; p < n_points; p++) {
+                    const auto a = clock();
+                    pool.parallelFor(n_windows, [&](int wi) {
+                        const size_t w         = (size_t) wi;
+                        const MargPriorView &v = views[w];
+                        vector<const double *> params((size_t) v.n_blocks);
+                        vector<double *> jac((size_t) v.n_blocks, nullptr);
+                        size_t xs = 0;
+                        for (int b = 0; b < v.n_blocks; b++) {
+                            params[(size_t) b] = x + (size_t) p * X + x_off[w] + xs;
+                            if (jacobians) jac[(size_t) b] = jacobians + (size_t) p * NJ + jac_off[w] + (size_t) v.r * xs;
+                            xs += (size_t) v.size[b];
+                        }
+                        double *e = residuals + (size_t) p * R + e_off[w];
+                        evaluateMargPrior(v, params.data(), e, jacobians ? jac.data() : nullptr);
+                        if (gradient)
+                            for (int k = 0; k < v.r; k++) {
+                                double s = 0;
+                                for (int i = 0; i < v.r; i++) s += v.J0[(size_t) i * v.r + k] * e[i];
+                                gradient[(size_t) p * R + e_off[w] + (size_t) k] = s;
+                            }
+                        if (sq_norm) {
+                            double s = 0;
+                            for (int i = 0; i < v.r; i++) s += e[i] * e[i];
+                            sq_norm[(size_t) p * W + w] = s;
+                        }
+                    });
+                    const double t = since(a);
+                    if ((rep > 0 || passes == 1) && (best < 0 || t < best)) best = t;
+                }
+            seconds[1] = best;
+            return 0;
+        }
+        icg_ctx_config cfg{};
+        cfg.device = 0, cfg.width = 64, cfg.height = 64, cfg.n_slots = 1, cfg.max_batch = 1, cfg.max_points = 64;
+        icg_ctx *ctx = nullptr;
+        if (icg_ctx_create(&cfg, &ctx) != ICG_OK) {
+            set_err(err, errlen, icg_last_error(nullptr));
+            return -1;
+        }
+        std::string e;
+        MarginalizationPriorSet set;
+        const auto a0 = clock();
+        if (!set.set(ctx, views, &e)) {
+            set_err(err, errlen, e.c_str());
+            icg_ctx_destroy(ctx);
+            return -2;
+        }
+        seconds[0] = since(a0);
+        vector<vector<const double *>> params(W);
+        vector<const double *const *> plist(W);
+        for (int rep = 0; rep < passes; rep++)
+            for (int p = 0; p < n_points; p++) {
+                const auto a = clock();
+                for (size_t w = 0; w < W; w++) {
+                    params[w].resize((size_t) views[w].n_blocks);
+                    size_t xs = 0;
+                    for (int b = 0; b < views[w].n_blocks; b++) params[w][(size_t) b] = x + (size_t) p * X + x_off[w] + xs, xs += (size_t) views[w].size[b];
+                    plist[w] = params[w].data();
+                }
+                if (!set.evaluate(plist, residuals + (size_t) p * R, jacobians ? jacobians + (size_t) p * NJ : nullptr,
+                                  gradient ? gradient + (size_t) p * R : nullptr, sq_norm ? sq_norm + (size_t) p * W : nullptr, &e)) {
+                    set_err(err, errlen, e.c_str());
+                    icg_ctx_destroy(ctx);
+                    return -3;
+                }
+                const double t = since(a);
+                if ((rep > 0 || passes == 1) && (best < 0 || t < best)) best = t;
+            }
+        seconds[1] = best;
+        icg_ctx_destroy(ctx);
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -1;
+    }
+}
+
 // ---- f3: outlier culling / statistics (culling_hip.h) on the maps the tracker built -------------------------------------------
 // Raw dump of a stream's landmark graph, NO filtering (the test re-derives the reference's filters and decisions from it):
 // landmarks sorted by id: lm_id, lm_pos[3], lm_flags (bit0 outlier), lm_ref_frame (frame id), lm_obs_off[n+1];

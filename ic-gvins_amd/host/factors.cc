@@ -860,17 +860,30 @@ MarginalizationFactor::MarginalizationFactor(std::shared_ptr<MarginalizationInfo
 }
 
 bool MarginalizationFactor::Evaluate(const double *const *parameters, double *residuals, double **jacobians) const {
-    const int marginalizaed_size = marg_info_->marginalizedSize();
-    const int remained_size      = marg_info_->remainedSize();
-    const vector<int> &remained_block_index     = marg_info_->remainedBlockIndex();
-    const vector<int> &remained_block_size      = marg_info_->remainedBlockSize();
-    const vector<double *> &remained_block_data = marg_info_->remainedBlockData();
-    const vector<double> &J0 = marg_info_->linearizedJacobians();
-    const vector<double> &e0 = marg_info_->linearizedResiduals();
+    const int marginalizaed_size            = marg_info_->marginalizedSize();
+    const vector<int> &remained_block_index = marg_info_->remainedBlockIndex();
+    const vector<int> &remained_block_size  = marg_info_->remainedBlockSize();
+    vector<int> index(remained_block_index.size());
+    for (size_t i = 0; i < index.size(); i++) index[i] = remained_block_index[i] - marginalizaed_size;
+    MargPriorView view;
+    view.r        = marg_info_->remainedSize();
+    view.n_blocks = (int) remained_block_size.size();
+    view.size     = remained_block_size.data();
+    view.index    = index.data();
+    view.x0       = marg_info_->remainedBlockData().data();
+    view.J0       = marg_info_->linearizedJacobians().data();
+    view.e0       = marg_info_->linearizedResiduals().data();
+    evaluateMargPrior(view, parameters, residuals, jacobians);
+    return true;
+}
+
+void evaluateMargPrior(const MargPriorView &view, const double *const *parameters, double *residuals, double **jacobians) {
+    const int remained_size = view.r;
+    const double *J0 = view.J0, *e0 = view.e0;
     vector<double> dx((size_t) remained_size, 0.0);
-    for (size_t i = 0; i < remained_block_size.size(); i++) {
-        const int size = remained_block_size[i], index = remained_block_index[i] - marginalizaed_size;
-        const double *x = parameters[i], *x0 = remained_block_data[i];
+    for (int i = 0; i < view.n_blocks; i++) {
+        const int size = view.size[i], index = view.index[i];
+        const double *x = parameters[i], *x0 = view.x0[i];
         if (size == POSE_GLOBAL_SIZE) { // :64-72
             const double n2 = x0[3] * x0[3] + x0[4] * x0[4] + x0[5] * x0[5] + x0[6] * x0[6];
             const double ax = -x0[3] / n2, ay = -x0[4] / n2, az = -x0[5] / n2, aw = x0[6] / n2;
@@ -894,16 +907,15 @@ bool MarginalizationFactor::Evaluate(const double *const *parameters, double *re
         residuals[i] = e0[(size_t) i] + s;
     }
     if (jacobians) {
-        for (size_t b = 0; b < remained_block_size.size(); b++) {
+        for (int b = 0; b < view.n_blocks; b++) {
             if (!jacobians[b]) continue;
-            const int size = remained_block_size[b], index = remained_block_index[b] - marginalizaed_size;
+            const int size = view.size[b], index = view.index[b];
             const int local_size = MarginalizationInfo::localSize(size);
             for (int i = 0; i < remained_size; i++)
                 for (int j = 0; j < size; j++)
                     jacobians[b][(size_t) i * size + j] = j < local_size ? J0[(size_t) i * remained_size + index + j] : 0.0;
         }
     }
-    return true;
 }
 
 } // namespace icg

@@ -240,6 +240,44 @@ private:
     std::shared_ptr<MarginalizationInfo> marg_info_;
 };
 
+// M4 on plain arrays: what MarginalizationFactor::Evaluate reads of a MarginalizationInfo.  index[b] is block b's first local column
+// (the remained block index minus the marginalized size), x0[b] its linearization point (size[b] values).
+struct MargPriorView {
+    int r{0}, n_blocks{0};
+    const int *size{nullptr}, *index{nullptr};
+    const double *const *x0{nullptr};
+    const double *J0{nullptr}, *e0{nullptr}; // r x r row-major, r
+};
+// MarginalizationFactor::Evaluate (marginalization_factor.h:47-101) over a view: residuals r; jacobians (optional, entries may be null):
+// per block an r x size[b] row-major matrix
+void evaluateMargPrior(const MargPriorView &view, const double *const *parameters, double *residuals, double **jacobians);
+
+// The priors of many windows resident on the device (icg_marg_prior_set / icg_marg_prior_evaluate): set() after every marginalization,
+// evaluate() per LM point.  Results are the bits evaluateMargPrior gives.  The two C entries are referenced weakly: in a build of this
+// layer on a C ABI without them available() is false and set() fails by name.
+class MarginalizationPriorSet {
+public:
+    static bool available(); // icg_marg_prior_set and icg_marg_prior_evaluate are in this build
+    // packs and uploads the priors once; x0 is read through the views now (a MarginalizationInfo's remainedBlockData() is the info's own
+    // copy and does not change after marginalization()).  Replaces the set `ctx` held.  false with *err set on failure.
+    bool set(icg_ctx *ctx, const vector<MargPriorView> &views, std::string *err = nullptr);
+    bool set(icg_ctx *ctx, const vector<std::shared_ptr<MarginalizationInfo>> &infos, std::string *err = nullptr);
+    // parameters[w][b]: block b of window w at the evaluation point.  residuals: residualSize() doubles, window after window;
+    // jacobians (optional): jacobianSize() doubles, per window its blocks concatenated, block b r x size[b] row-major;
+    // gradient (optional): J0^T e, residualSize(); sq_norm (optional): e . e per window.
+    bool evaluate(const vector<const double *const *> &parameters, double *residuals, double *jacobians, double *gradient, double *sq_norm,
+                  std::string *err = nullptr);
+    int windows() const { return (int) r_.size(); }
+    size_t residualSize() const { return residual_size_; }
+    size_t jacobianSize() const { return jacobian_size_; }
+
+private:
+    icg_ctx *ctx_{nullptr};
+    vector<int32_t> r_, block_off_, block_size_;
+    vector<double> x_; // the evaluation point, packed like x0
+    size_t residual_size_{0}, jacobian_size_{0};
+};
+
 // symmetric eigen-decomposition (Householder tridiagonalisation + implicit QL), eigenvalues ascending, evecs row-major with eigenvectors in columns
 void symmetricEigen(int n, const vector<double> &A, vector<double> &evals, vector<double> &evecs);
 

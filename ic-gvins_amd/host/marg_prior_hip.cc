@@ -1,0 +1,102 @@
+// M4 on the HIP C ABI: the marginalization priors of many windows resident on the device.  MarginalizationFactor::Evaluate
+// (marginalization_factor.h:47-101) stays what the per-factor Ceres callback runs (factors.cc evaluateMargPrior); MarginalizationPriorSet
+// is the same evaluation for MANY priors per call, for a driver that holds the priors of many windows and evaluates them at every LM point:
+// J0 / e0 / x0 cross the link once per marginalization, an evaluation ships the parameters in and the results out.
+#include <cstring>
+
+#include "factors.h"
+
+// A build of this layer on another implementation of the C ABI may not have the entry points: the references stay weak (null when absent)
+// and set() reports it; the product library links libicgvins_hip.so, which defines them.
+#pragma weak icg_marg_prior_set
+#pragma weak icg_marg_prior_evaluate
+
+namespace icg {
+
+bool MarginalizationPriorSet::available() { return &icg_marg_prior_set != nullptr && &icg_marg_prior_evaluate != nullptr; }
+
+bool MarginalizationPriorSet::set(icg_ctx *ctx, const vector<MargPriorView> &views, std::string *err) {
+    if (!available()) {
+        if (err) *err = "icg_marg_prior_set is not in this build";
+        return false;
+    }
+    ctx_ = nullptr;
+    r_.clear(), block_off_.assign(1, 0), block_size_.clear();
+    residual_size_ = jacobian_size_ = 0;
+    vector<int32_t> index;
+    vector<double> x0, e0;
+    size_t nj = 0;
+    for (const MargPriorView &v : views) nj += (size_t) (v.r > 0 ? v.r : 0) * (size_t) (v.r > 0 ? v.r : 0);
+    vector<double> J0;
+    J0.reserve(nj);
+    for (const MargPriorView &v : views) {
+        r_.push_back(v.r);
+        size_t xs = 0;
+        for (int b = 0; b < v.n_blocks; b++) {
+            block_size_.push_back(v.size[b]);
+            index.push_back(v.index[b]);
+            if (v.size[b] > 0) x0.insert(x0.end(), v.x0[b], v.x0[b] + v.size[b]), xs += (size_t) v.size[b];
+        }
+        block_off_.push_back((int32_t) block_size_.size());
+        if (v.r > 0) {
+            J0.insert(J0.end(), v.J0, v.J0 + (size_t) v.r * v.r);
+            e0.insert(e0.end(), v.e0, v.e0 + v.r);
+            residual_size_ += (size_t) v.r;
+            jacobian_size_ += (size_t) v.r * xs;
+        }
+    }
+    // (valid pointers for empty arrays: the entry checks its arguments and names what is wrong)
+    block_size_.reserve(1), index.reserve(1), x0.reserve(1), J0.reserve(1), e0.reserve(1), r_.reserve(1);
+    const int rc = icg_marg_prior_set(ctx, (int) views.size(), r_.data(), block_off_.data(), block_size_.data(), index.data(), x0.data(), J0.data(), e0.data());
+    if (rc != ICG_OK) {
+        if (err) *err = ctx ? icg_last_error(ctx) : "icg_marg_prior_set: no context";
+        r_.clear();
+        return false;
+    }
+    x_.assign(x0.size(), 0.0);
+    ctx_ = ctx;
+    return true;
+}
+
+bool MarginalizationPriorSet::set(icg_ctx *ctx, const vector<std::shared_ptr<MarginalizationInfo>> &infos, std::string *err) {
+    vector<vector<int>> index(infos.size());
+    vector<MargPriorView> views(infos.size());
+    for (size_t w = 0; w < infos.size(); w++) {
+        const MarginalizationInfo &info = *infos[w];
+        for (int i : info.remainedBlockIndex()) index[w].push_back(i - info.marginalizedSize());
+        MargPriorView &v = views[w];
+        v.r        = info.remainedSize();
+        v.n_blocks = (int) info.remainedBlockSize().size();
+        v.size     = info.remainedBlockSize().data();
+        v.index    = index[w].data();
+        v.x0       = info.remainedBlockData().data();
+        v.J0       = info.linearizedJacobians().data();
+        v.e0       = info.linearizedResiduals().data();
+    }
+    return set(ctx, views, err);
+}
+
+bool MarginalizationPriorSet::evaluate(const vector<const double *const *> &parameters, double *residuals, double *jacobians, double *gradient,
+                                       double *sq_norm, std::string *err) {
+    if (!available()) {
+        if (err) *err = "icg_marg_prior_evaluate is not in this build";
+        return false;
+    }
+    if (!ctx_ || parameters.size() != r_.size()) {
+        if (err) *err = !ctx_ ? "MarginalizationPriorSet::evaluate: no set" : "MarginalizationPriorSet::evaluate: one parameter list per window";
+        return false;
+    }
+    double *x = x_.data();
+    for (size_t w = 0; w < r_.size(); w++)
+        for (int32_t b = block_off_[w]; b < block_off_[w + 1]; b++) {
+            memcpy(x, parameters[w][b - block_off_[w]], sizeof(double) * (size_t) block_size_[(size_t) b]);
+            x += block_size_[(size_t) b];
+        }
+    if (icg_marg_prior_evaluate(ctx_, x_.data(), residuals, jacobians, gradient, sq_norm) != ICG_OK) {
+        if (err) *err = icg_last_error(ctx_);
+        return false;
+    }
+    return true;
+}
+
+} // namespace icg

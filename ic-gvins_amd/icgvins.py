@@ -21,7 +21,11 @@ EXPORTS = [
     "icg_ins_mechanize_batch", "icg_ins_camera_pose_batch", "icg_reproj_schur", "icg_reproj_backsub", "icg_reproj_cost", "icg_reproj_landmark_diag",
     "icg_reproj_error_batch", "icg_reproj_set_windows", "icg_reproj_eval_windows", "icg_reproj_schur_windows",
     "icg_reproj_schur_windows_view", "icg_reproj_reserve_windows", "icg_reproj_eval_resident_view", "icg_reproj_backsub_windows", "icg_reproj_cost_windows", "icg_reproj_fetch_residuals", "icg_reproj_chi2_cull",
+    "icg_marg_prior_set", "icg_marg_prior_evaluate",
 ]
+
+
+MARG_MAX_R = 1024  # ICG_MARG_MAX_R of include/icgvins_hip.h
 
 
 class IcgError(RuntimeError):
@@ -444,6 +448,30 @@ class Context:
         self._ck(self.lib.icg_preint_evaluate_batch(self.h, int(variant), n, _p(delta), _p(jac), _p(cov), _p(dt), _p(env), _p(po), _p(pnr),
                                                      _p(points), _p(res), _p(J), _p(S), _p(status)), "icg_preint_evaluate_batch")
         return res, J, S, status
+
+    # ---- M4
+    def marg_prior_set(self, r, block_off, block_size, block_index, x0, J0, e0):
+        """icg_marg_prior_set: the priors of len(r) windows become resident (x0 / J0 / e0: flat arrays, window after window)"""
+        r, block_off, block_size, block_index = _i32(r).reshape(-1), _i32(block_off).reshape(-1), _i32(block_size).reshape(-1), _i32(block_index).reshape(-1)
+        x0, J0, e0 = _f64(x0).reshape(-1), _f64(J0).reshape(-1), _f64(e0).reshape(-1)
+        self._marg = None
+        self._ck(self.lib.icg_marg_prior_set(self.h, len(r), _p(r), _p(block_off), _p(block_size), _p(block_index), _p(x0), _p(J0), _p(e0)),
+                 "icg_marg_prior_set")
+        xs = np.array([int(block_size[block_off[w]:block_off[w + 1]].sum()) for w in range(len(r))], np.int64)
+        self._marg = (len(r), int(r.sum()), int(xs.sum()), int((r.astype(np.int64) * xs).sum()))
+
+    def marg_prior_evaluate(self, x, want_jac=False, want_grad=False, want_sq_norm=False):
+        """icg_marg_prior_evaluate -> (residuals, jacobians | None, gradient | None, sq_norm | None), flat, window after window"""
+        n, nr, nx, njac = getattr(self, "_marg", None) or (0, 0, 0, 0)
+        x = _f64(x).reshape(-1)
+        if n and x.shape[0] != nx:
+            raise IcgError(f"marg_prior_evaluate: x has {x.shape[0]} values, the resident set takes {nx}")
+        res = np.zeros(nr)
+        jac = np.zeros(njac) if want_jac else None
+        grad = np.zeros(nr) if want_grad else None
+        sq = np.zeros(n) if want_sq_norm else None
+        self._ck(self.lib.icg_marg_prior_evaluate(self.h, _p(x), _p(res), _p(jac), _p(grad), _p(sq)), "icg_marg_prior_evaluate")
+        return res, jac, grad, sq
 
     # ---- f4
     def ins_mechanize_batch(self, offsets, imu, cfg8, states23, want_traj=True):

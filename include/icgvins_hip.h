@@ -279,6 +279,32 @@ int icg_preint_evaluate_batch(icg_ctx *ctx, int variant, int n_factors, const do
                               const double *pn, const double *points, double *residuals, double *jacobians, double *sqrt_info,
                               int32_t *status);
 
+/* ---- M4: MarginalizationFactor::Evaluate (factors/marginalization_factor.h:47-101) for the priors of many windows, RESIDENT on the
+ * device: a prior is constant between two marginalizations while every LM iteration evaluates it at a new point, so the priors are
+ * uploaded once (icg_marg_prior_set) and an evaluation ships only x in and the results out (icg_marg_prior_evaluate).
+ * Window w: retained size r[w] (1 .. ICG_MARG_MAX_R), blocks [block_off[w], block_off[w+1]) (block_off[0] = 0).  Block b: global size
+ * block_size[b] (7 = pose, local size 6; otherwise local = global), first local column block_index[b] (the remained block index minus
+ * the marginalized size).  Blocks may be listed in any column order and need not cover every column (an uncovered column has dx = 0);
+ * they must not overlap.  Windows of one set may differ in r and layout.
+ * x0: linearization point, the blocks' parameters concatenated by global size, window after window; J0: linearized_jacobians, r x r
+ * row-major per window, concatenated; e0: linearized_residuals, r per window.
+ * Replaces the set the context held; the set stays until the next icg_marg_prior_set or icg_ctx_destroy.  ICG_ERR_INVALID (message
+ * names the window): n_windows <= 0, NULL pointer, r <= 0, block_off not monotone, a block with size <= 0, index < 0 or index + local
+ * size > r.  ICG_ERR_CAPACITY: r above ICG_MARG_MAX_R or more than 65535 windows.  After a failed call no set is resident. */
+#define ICG_MARG_MAX_R 1024
+int icg_marg_prior_set(icg_ctx *ctx, int n_windows, const int32_t *r, const int32_t *block_off, const int32_t *block_size,
+                       const int32_t *block_index, const double *x0, const double *J0, const double *e0);
+/* Evaluates every resident prior (factors/marginalization_factor.h:47-101) at x (laid out like x0).  dx per block as :61-77 (pose:
+ * position difference and sign(dq.w) * 2 * vec(q0^-1 * q), a zero-norm q0 yields the reference's inf / NaN, not an error);
+ * residuals (sum of r[w]): e = e0 + J0 * dx, every row summed from 0 in column order with one multiply and one add per term — the same
+ * IEEE value as the host code, in any batch.  Optional outputs, NULL = not computed and not transferred:
+ *   jacobians  per window its blocks concatenated, block b an r x block_size[b] row-major matrix (columns >= local size are 0): the
+ *              blocks Ceres hands to Evaluate (:83-98); r[w] * sum(block_size) doubles per window
+ *   gradient   J0^T e per window (sum of r[w]), every column summed from 0 in row order
+ *   sq_norm    e . e per window (n_windows), summed from 0 in row order (twice the Ceres cost)
+ * ICG_ERR_INVALID without a resident set or with NULL x / residuals. */
+int icg_marg_prior_evaluate(icg_ctx *ctx, const double *x, double *residuals, double *jacobians, double *gradient, double *sq_norm);
+
 /* ---- f3 (SURVEY.md §8 "next" row): per-observation arithmetic of GVINS::gvinsOutlierCulling (ic_gvins.cc:1035-1128) and
  * GVINS::parametersStatistic (ic_gvins.cc:930-1033).  Observation i = landmark lm_idx[i] (world position pw, n_lm x 3) seen in
  * keyframe pose_idx[i] (poses12: n_poses x 12, R row-major camera->world | t) at the undistorted key point pix[i]:
