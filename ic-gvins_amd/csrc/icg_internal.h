@@ -135,6 +135,9 @@ struct icg_ctx {
     int lmwin_cap = 0;
 
     icg_marg_set marg;
+    // M3 (marg_linearize.hip): per-window working memory of icg_marg_linearize_batch for the windows that do not fit in LDS; grows on demand
+    double *d_lin_scratch = nullptr;
+    size_t lin_scratch_cap = 0; // bytes
 
     icg_camera cam{};
     bool has_cam = false;

@@ -1,0 +1,484 @@
+// M3: the Schur step on the marginalized pose / mix block and the linearization of the reduced system (factors/marginalization_info.h:153-192)
+// for many windows at once — one workgroup per window, icg_marg_linearize_batch.
+//
+// The eigen-solver is host/factors.cc symmetricEigen restated for a workgroup: Householder tridiagonalisation, accumulation of the
+// transformations and implicit QL, in place in ONE n x n working matrix (stored transposed, W[j * n + i] = v(i, j), as the host stores it)
+// with d and e beside it.  Every accumulated sum of the host code is a fixed-order chain per output element; here one thread owns a chain and
+// adds its terms in the host's order, one multiply and one add per term (the file is built with -ffp-contract=off), and everything that is
+// element-wise on the host (the rank-2 update, the Givens rotations) is spread over the threads.  The scalar recurrences (scale, h, the c / s
+// sequence of a QL sweep) are computed by every thread redundantly from the same LDS values: uniform by construction, no broadcast needed.
+// The one operation that may round differently from the host is hypot (libm there, the device library here).
+//
+// Working memory: a C2 window (r = 142) is 142^2 + 2 * 142 doubles = 163 584 B, which one workgroup may own on gfx950 (160 KiB of LDS per CU):
+// k_marg_linearize<true>.  A window that does not fit (C4: r = 217) runs the same code on a global scratch block (L2 / Infinity Cache
+// resident), d and e still in LDS: k_marg_linearize<false>.  Which of the two a window takes depends on its own (P, m) only, so its bits
+// are the same alone and in any batch.
+#include "icg_internal.h"
+
+#include <atomic>
+#include <cmath>
+
+#define LIN_THREADS 256
+#define LIN_WAVES (LIN_THREADS / 64)
+#define LIN_SLOTS ((ICG_MARG_LIN_MAX_P + LIN_THREADS - 1) / LIN_THREADS) // elements of a length-n vector one thread owns
+
+namespace {
+
+struct lin_desc {
+    int32_t P, m;
+    int64_t h_off, b_off; // window's H (P x P) and b (P) in the inputs
+    int64_t r_off, rr_off; // window's r-vectors (bp, e0, evals) and r x r matrices (Hp, J0) in the outputs
+    int64_t s_off;         // window's block in the global scratch: bp (r) | working memory (only for a window that does not fit in LDS)
+};
+
+// doubles of working memory a window needs beside d and e: phase (a) holds W (m x m), Hinv (m x m), T (r x m), phase (b) W (r x r)
+__host__ __device__ static inline size_t lin_work(int m, int r) {
+    const size_t a = 2 * (size_t) m * m + (size_t) r * m, b = (size_t) r * r;
+    return a > b ? a : b;
+}
+
+// symmetricEigen (host/factors.cc) on W (n x n, transposed: W[j * n + i] = v(i, j); the lower triangle of the input is what is read).
+// On return d holds the eigenvalues in QL order, the rows of W the eigenvectors (W[x * n + i] = component i of the vector of d[x]) and the
+// memory of e the ascending order as int32: ord[k] = x of the k-th smallest eigenvalue.  Returns true when a QL sweep hit the 60-iteration
+// cap.  Called by all threads of the workgroup (barriers inside); W, d, e must be visible (a barrier after they were written).
+__device__ __forceinline__ bool lin_eigen(const int n, double *W, double *d, double *e, int *s_m) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    bool capped = false;
+    // ---- tridiagonalise
+    for (int j = tid; j < n; j += LIN_THREADS) d[j] = W[(size_t) j * n + n - 1];
+    __syncthreads();
+    for (int i = n - 1; i > 0; i--) {
+        double scale = 0.0, h = 0.0;
+        for (int k = 0; k < i; k++) scale += fabs(d[k]);
+        const double dl = d[i - 1];
+        __syncthreads();
+        if (scale == 0.0) {
+            if (tid == 0) e[i] = dl;
+            for (int j = tid; j < i; j += LIN_THREADS) {
+                d[j]                  = W[(size_t) j * n + i - 1];
+                W[(size_t) j * n + i] = 0.0;
+                W[(size_t) i * n + j] = 0.0;
+            }
+        } else {
+            for (int k = tid; k < i; k += LIN_THREADS) d[k] = d[k] / scale;
+            __syncthreads();
+            for (int k = 0; k < i; k++) h += d[k] * d[k];
+            const double f = d[i - 1];
+            double g       = sqrt(h);
+            if (f > 0) g = -g;
+            h = h - f * g;
+            __syncthreads();
+            if (tid == 0) {
+                e[i]     = scale * g;
+                d[i - 1] = f - g;
+            }
+            __syncthreads();
+            // e[j] = sum_{j' < j} v(j, j') d[j'] + v(j, j) d[j] + sum_{k > j} v(k, j) d[k]: the order in which the host's column loop adds them
+            double *ci = W + (size_t) i * n;
+            for (int j = tid; j < i; j += LIN_THREADS) {
+                ci[j]     = d[j]; // v(j, i) = d[j]
+                double s  = 0.0;
+                for (int jp = 0; jp < j; jp++) s += W[(size_t) jp * n + j] * d[jp];
+                const double *cj = W + (size_t) j * n;
+                s += cj[j] * d[j];
+                for (int k = j + 1; k < i; k++) s += cj[k] * d[k];
+                e[j] = s;
+            }
+            __syncthreads();
+            for (int j = tid; j < i; j += LIN_THREADS) e[j] = e[j] / h;
+            __syncthreads();
+            double f2 = 0.0;
+            for (int j = 0; j < i; j++) f2 += e[j] * d[j];
+            const double hh = f2 / (h + h);
+            __syncthreads();
+            for (int j = tid; j < i; j += LIN_THREADS) e[j] = e[j] - hh * d[j];
+            __syncthreads();
+            for (int jj = wave; jj < i; jj += LIN_WAVES) { // rank-2 update of the lower triangle: element-wise, a wave per column
+                const double fj = d[jj], gj = e[jj];
+                double *cj = W + (size_t) jj * n;
+                for (int k = jj + lane; k < i; k += 64) cj[k] = cj[k] - (fj * e[k] + gj * d[k]);
+            }
+            __syncthreads();
+            for (int jj = tid; jj < i; jj += LIN_THREADS) {
+                d[jj]                  = W[(size_t) jj * n + i - 1];
+                W[(size_t) jj * n + i] = 0.0;
+            }
+        }
+        if (tid == 0) d[i] = h;
+        __syncthreads();
+    }
+    // ---- accumulate the transformations
+    for (int i = 0; i < n - 1; i++) {
+        const double h = d[i + 1];
+        if (tid == 0) {
+            W[(size_t) i * n + n - 1] = W[(size_t) i * n + i];
+            W[(size_t) i * n + i]     = 1.0;
+        }
+        __syncthreads();
+        double *u = W + (size_t) (i + 1) * n;
+        if (h != 0.0) {
+            for (int k = tid; k <= i; k += LIN_THREADS) d[k] = u[k] / h;
+            __syncthreads();
+            for (int j = tid; j <= i; j += LIN_THREADS) {
+                double *cj = W + (size_t) j * n;
+                double g   = 0.0;
+                for (int k = 0; k <= i; k++) g += u[k] * cj[k];
+                for (int k = 0; k <= i; k++) cj[k] = cj[k] - g * d[k];
+            }
+            __syncthreads();
+        }
+        for (int k = tid; k <= i; k += LIN_THREADS) u[k] = 0.0;
+        __syncthreads();
+    }
+    for (int j = tid; j < n; j += LIN_THREADS) {
+        d[j]                      = W[(size_t) j * n + n - 1];
+        W[(size_t) j * n + n - 1] = 0.0;
+    }
+    double shifted[LIN_SLOTS];
+#pragma unroll
+    for (int q = 0; q < LIN_SLOTS; q++) {
+        const int k = tid + q * LIN_THREADS;
+        shifted[q]  = k + 1 < n ? e[k + 1] : 0.0;
+    }
+    __syncthreads();
+    if (tid == 0) W[(size_t) (n - 1) * n + n - 1] = 1.0;
+#pragma unroll
+    for (int q = 0; q < LIN_SLOTS; q++) {
+        const int k = tid + q * LIN_THREADS;
+        if (k < n) e[k] = shifted[q];
+    }
+    __syncthreads();
+    // ---- implicit QL.  A sweep's c / s recurrence is computed by every thread that owns an eigenvector component; the thread applies each
+    // rotation to its component as it goes (the rotations of a sweep chain along the columns, not across components).  d and e are only read
+    // during a sweep: the new values are kept in the registers of one owner thread each and written behind a barrier.
+    double f = 0.0, tst1 = 0.0;
+    const double eps = 2.220446049250313e-16;
+    for (int l = 0; l < n; l++) {
+        {
+            const double t = fabs(d[l]) + fabs(e[l]);
+            if (tst1 < t) tst1 = t;
+        }
+        if (tid == 0) *s_m = n - 1; // (e[n - 1] = 0 ends the host's search there at the latest)
+        __syncthreads();
+        for (int mm = l + tid; mm < n - 1; mm += LIN_THREADS)
+            if (fabs(e[mm]) <= eps * tst1) {
+                atomicMin(s_m, mm);
+                break;
+            }
+        __syncthreads();
+        const int m = *s_m;
+        if (m > l) {
+            int iter = 0;
+            bool more;
+            do {
+                iter++;
+                double g        = d[l];
+                const double el = e[l], el1 = e[l + 1];
+                double p        = (d[l + 1] - g) / (2.0 * el);
+                double r        = hypot(p, 1.0);
+                if (p < 0) r = -r;
+                const double dl0 = el / (p + r), dl1 = el * (p + r);
+                double h         = g - dl0;
+                __syncthreads();
+                if (tid == 0) d[l] = dl0, d[l + 1] = dl1;
+                for (int i = l + 2 + tid; i < n; i += LIN_THREADS) d[i] = d[i] - h;
+                __syncthreads();
+                f += h;
+                double keep_d[LIN_SLOTS], keep_e[LIN_SLOTS], new_dl = 0.0, new_el = 0.0;
+                if (tid < n) {
+                    p        = d[m];
+                    double c = 1.0, c2 = c, c3 = c, s = 0.0, s2 = 0.0;
+                    double cur[LIN_SLOTS];
+#pragma unroll
+                    for (int q = 0; q < LIN_SLOTS; q++) {
+                        const int k = tid + q * LIN_THREADS;
+                        cur[q]      = k < n ? W[(size_t) m * n + k] : 0.0;
+                        keep_d[q] = keep_e[q] = 0.0;
+                    }
+                    for (int i = m - 1; i >= l; i--) {
+                        c3 = c2;
+                        c2 = c;
+                        s2 = s;
+                        const double ei = e[i], di = d[i];
+                        g               = c * ei;
+                        h               = c * p;
+                        r               = hypot(p, ei);
+                        const double en = s * r; // e[i + 1]
+                        s               = ei / r;
+                        c               = p / r;
+                        p               = c * di - s * g;
+                        const double dn = h + s * (c * g + s * di); // d[i + 1]
+#pragma unroll
+                        for (int q = 0; q < LIN_SLOTS; q++) {
+                            const int k = tid + q * LIN_THREADS;
+                            if (k == i + 1) keep_d[q] = dn, keep_e[q] = en;
+                            if (k < n) {
+                                const double a = W[(size_t) i * n + k], b = cur[q];
+                                W[(size_t) (i + 1) * n + k] = s * a + c * b;
+                                cur[q]                      = c * a - s * b;
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int q = 0; q < LIN_SLOTS; q++) {
+                        const int k = tid + q * LIN_THREADS;
+                        if (k < n) W[(size_t) l * n + k] = cur[q];
+                    }
+                    p      = -s * s2 * c3 * el1 * el / dl1;
+                    new_el = s * p;
+                    new_dl = c * p;
+                }
+                __syncthreads();
+                if (tid < n) {
+#pragma unroll
+                    for (int q = 0; q < LIN_SLOTS; q++) {
+                        const int k = tid + q * LIN_THREADS;
+                        if (k > l && k <= m) d[k] = keep_d[q], e[k] = keep_e[q];
+                    }
+                    if (tid == 0) e[l] = new_el, d[l] = new_dl;
+                }
+                __syncthreads();
+                more = fabs(e[l]) > eps * tst1 && iter < 60;
+            } while (more);
+            if (fabs(e[l]) > eps * tst1) capped = true; // (left the loop on the iteration cap)
+        }
+        __syncthreads();
+        if (tid == 0) {
+            d[l] = d[l] + f;
+            e[l] = 0.0;
+        }
+        __syncthreads();
+    }
+    // ---- ascending order (ties by index), kept where e was
+    int rank[LIN_SLOTS];
+#pragma unroll
+    for (int q = 0; q < LIN_SLOTS; q++) {
+        const int x = tid + q * LIN_THREADS;
+        rank[q]     = 0;
+        if (x < n) {
+            const double dx = d[x];
+            for (int y = 0; y < n; y++) {
+                const double dy = d[y];
+                rank[q] += (dy < dx || (dy == dx && y < x)) ? 1 : 0;
+            }
+        }
+    }
+    __syncthreads();
+    int *ord = reinterpret_cast<int *>(e);
+#pragma unroll
+    for (int q = 0; q < LIN_SLOTS; q++) {
+        const int x = tid + q * LIN_THREADS;
+        if (x < n) ord[rank[q]] = x;
+    }
+    __syncthreads();
+    return capped;
+}
+
+template <bool IN_LDS>
+__global__ __launch_bounds__(LIN_THREADS) void k_marg_linearize(int n_items, const int32_t *__restrict__ items, const lin_desc *__restrict__ desc,
+                                                                const double *__restrict__ H, const double *__restrict__ b, double eps, double *Hp,
+                                                                double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status,
+                                                                double *scratch) {
+    extern __shared__ double lin_lds[];
+    __shared__ int s_m;
+    if ((int) blockIdx.x >= n_items) return;
+    const int w = items[blockIdx.x], tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const lin_desc D = desc[w];
+    const int P = D.P, m = D.m, r = P - m, nmax = m > r ? m : r;
+    double *d = lin_lds, *e = lin_lds + nmax;
+    double *S       = IN_LDS ? lin_lds + 2 * (size_t) nmax : scratch + D.s_off + r;
+    double *bpw     = scratch + D.s_off;
+    const double *Hw = H + D.h_off, *bw = b + D.b_off;
+    double *J0w = J0 + D.rr_off;
+    int st       = 0;
+    double minev = INFINITY;
+    double *T    = S + 2 * (size_t) m * m; // r x m
+    if (m > 0) { // ---- (a) :170-192 on the m leading columns
+        double *Wm = S, *Hinv = S + (size_t) m * m;
+        for (int idx = tid; idx < m * m; idx += LIN_THREADS) {
+            const int i = idx / m, j = idx - i * m;
+            Wm[(size_t) j * m + i] = 0.5 * (Hw[(size_t) i * P + j] + Hw[(size_t) j * P + i]);
+        }
+        __syncthreads();
+        if (lin_eigen(m, Wm, d, e, &s_m)) st |= 1;
+        const int *ord = reinterpret_cast<const int *>(e);
+        minev          = d[ord[0]];
+        if (minev <= eps) st |= 2;
+        double *inv = T; // (T is formed after Hinv is complete)
+        for (int k = tid; k < m; k += LIN_THREADS) {
+            const double ev = d[ord[k]];
+            inv[k]          = ev > eps ? 1.0 / ev : 0.0;
+        }
+        __syncthreads();
+        for (int idx = tid; idx < m * m; idx += LIN_THREADS) {
+            const int i = idx / m, j = idx - i * m;
+            if (j > i) continue;
+            double s = 0;
+            for (int k = 0; k < m; k++) {
+                const double *vk = Wm + (size_t) ord[k] * m;
+                const double wv  = vk[i] * inv[k];
+                s += wv * vk[j];
+            }
+            Hinv[(size_t) i * m + j] = Hinv[(size_t) j * m + i] = s;
+        }
+        __syncthreads();
+        for (int idx = tid; idx < r * m; idx += LIN_THREADS) {
+            const int i = idx / m, j = idx - i * m;
+            double s = 0;
+            for (int k = 0; k < m; k++) s += Hw[(size_t) (m + i) * P + k] * Hinv[(size_t) k * m + j];
+            T[idx] = s;
+        }
+        __syncthreads();
+    }
+    // Hp goes to the window's J0 block first (the working matrix may overlap T) and is loaded transposed from there
+    double *Hpw = Hp ? Hp + D.rr_off : nullptr;
+    for (int idx = tid; idx < r * r; idx += LIN_THREADS) {
+        const int i = idx / r, j = idx - i * r;
+        double v = Hw[(size_t) (m + i) * P + m + j];
+        if (m > 0) {
+            double s = 0;
+            for (int k = 0; k < m; k++) s += T[(size_t) i * m + k] * Hw[(size_t) k * P + m + j];
+            v = v - s;
+        }
+        J0w[idx] = v;
+        if (Hpw) Hpw[idx] = v;
+    }
+    for (int i = tid; i < r; i += LIN_THREADS) {
+        double v = bw[m + i];
+        if (m > 0) {
+            double s = 0;
+            for (int k = 0; k < m; k++) s += T[(size_t) i * m + k] * bw[k];
+            v = v - s;
+        }
+        bpw[i] = v;
+        if (bp) bp[D.r_off + i] = v;
+    }
+    __syncthreads();
+    double *Wr = S;
+    for (int idx = tid; idx < r * r; idx += LIN_THREADS) {
+        const int i = idx / r, j = idx - i * r;
+        Wr[(size_t) j * r + i] = J0w[idx];
+    }
+    __syncthreads();
+    // ---- (b) :153-167
+    if (lin_eigen(r, Wr, d, e, &s_m)) st |= 1;
+    const int *ord = reinterpret_cast<const int *>(e);
+    if (d[ord[0]] <= eps) st |= 4;
+    for (int k = tid; k < r; k += LIN_THREADS) {
+        const double ev = d[ord[k]];
+        if (evals) evals[D.r_off + k] = ev;
+        const double Sinv = ev > eps ? 1.0 / ev : 0.0, si = sqrt(Sinv);
+        const double *src = Wr + (size_t) ord[k] * r;
+        double vb         = 0;
+        for (int i = 0; i < r; i++) vb += src[i] * -bpw[i];
+        e0[D.r_off + k] = si * vb;
+    }
+    for (int k = wave; k < r; k += LIN_WAVES) {
+        const double ev = d[ord[k]];
+        const double ss = sqrt(ev > eps ? ev : 0.0);
+        const double *src = Wr + (size_t) ord[k] * r;
+        for (int i = lane; i < r; i += 64) J0w[(size_t) k * r + i] = ss * src[i];
+    }
+    if (tid == 0) {
+        if (min_ev_m) min_ev_m[w] = minev;
+        if (status) status[w] = st;
+    }
+}
+
+size_t lin_lds_limit(icg_ctx *ctx) {
+    static std::atomic<int> per_dev[16];
+    const int dev = ctx->cfg.device & 15;
+    int v         = per_dev[dev].load(std::memory_order_relaxed);
+    if (v == 0) {
+        int optin = 0;
+        if (hipDeviceGetAttribute(&optin, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->cfg.device) != hipSuccess || optin <= 0) optin = 64 * 1024;
+        v = optin;
+        per_dev[dev].store(v, std::memory_order_relaxed);
+    }
+    return (size_t) v - 256; // (- the kernel's static words)
+}
+
+} // namespace
+
+extern "C" int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
+                                        double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status) {
+    if (!ctx) return ICG_ERR_INVALID;
+    if (n_windows <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_linearize_batch: n_windows = %d", n_windows);
+    if (n_windows > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_linearize_batch: %d windows in one call (at most 65535)", n_windows);
+    if (!P || !m || !H || !b || !J0 || !e0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_linearize_batch: NULL argument");
+    if (!(eps >= 0.0)) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_linearize_batch: eps = %g", eps);
+    const size_t n = (size_t) n_windows;
+    for (size_t w = 0; w < n; w++)
+        if (P[w] <= 0 || m[w] < 0 || m[w] >= P[w])
+            return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_linearize_batch: window %zu: P = %d, m = %d (0 <= m < P)", w, P[w], m[w]);
+    for (size_t w = 0; w < n; w++) // (after the argument checks: an invalid batch is invalid whatever its size)
+        if (P[w] > ICG_MARG_LIN_MAX_P)
+            return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_linearize_batch: window %zu: P = %d is above the limit %d", w, P[w], ICG_MARG_LIN_MAX_P);
+    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    const size_t lds_limit = lin_lds_limit(ctx);
+    std::vector<lin_desc> desc(n);
+    std::vector<int32_t> items(n); // the windows that run in LDS first, then the others
+    size_t th = 0, tb = 0, tr = 0, trr = 0, ts = 0, lds_fast = 0, lds_slow = 0;
+    int n_fast = 0;
+    std::vector<char> fast(n);
+    for (size_t w = 0; w < n; w++) {
+        const int r = P[w] - m[w], nmax = m[w] > r ? m[w] : r;
+        const size_t need = (lin_work(m[w], r) + 2 * (size_t) nmax) * sizeof(double);
+        fast[w]           = need <= lds_limit;
+        desc[w]           = {P[w], m[w], (int64_t) th, (int64_t) tb, (int64_t) tr, (int64_t) trr, (int64_t) ts};
+        th += (size_t) P[w] * P[w], tb += (size_t) P[w], tr += (size_t) r, trr += (size_t) r * r;
+        ts += (size_t) r + (fast[w] ? 0 : lin_work(m[w], r));
+        if (fast[w]) {
+            n_fast++;
+            if (need > lds_fast) lds_fast = need;
+        } else if (2 * (size_t) nmax * sizeof(double) > lds_slow) {
+            lds_slow = 2 * (size_t) nmax * sizeof(double);
+        }
+    }
+    {
+        int a = 0, z = n_fast;
+        for (size_t w = 0; w < n; w++) items[(size_t) (fast[w] ? a++ : z++)] = (int32_t) w;
+    }
+    if (ts * sizeof(double) > ctx->lin_scratch_cap) {
+        if (ctx->d_lin_scratch) (void) hipFree(ctx->d_lin_scratch);
+        ctx->d_lin_scratch   = nullptr;
+        ctx->lin_scratch_cap = 0;
+        ICG_HIP(ctx, hipMalloc((void **) &ctx->d_lin_scratch, ts * sizeof(double)));
+        ctx->lin_scratch_cap = ts * sizeof(double);
+    }
+    static std::atomic<size_t> granted[16];
+    const int dev = ctx->cfg.device & 15;
+    if (lds_fast > 48 * 1024 && granted[dev].load(std::memory_order_relaxed) < lds_fast) {
+        ICG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_marg_linearize<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_limit));
+        granted[dev].store(lds_limit, std::memory_order_relaxed);
+    }
+    icg_call c(ctx);
+    const size_t out_doubles = 2 * trr + 3 * tr + n;
+    int rc = c.reserve(sizeof(double) * (th + tb + out_doubles) + n * (sizeof(lin_desc) + 8) + 16 * 256);
+    if (rc) return rc;
+    const double *d_H       = c.in(H, th);
+    const double *d_b       = c.in(b, tb);
+    const lin_desc *d_desc  = c.in(desc.data(), n);
+    const int32_t *d_items  = c.in(items.data(), n);
+    if ((rc = c.seal())) return rc;
+    double *d_J0  = c.out(J0, trr);
+    double *d_e0  = c.out(e0, tr);
+    double *d_Hp  = Hp ? c.out(Hp, trr) : nullptr;
+    double *d_bp  = bp ? c.out(bp, tr) : nullptr;
+    double *d_ev  = evals ? c.out(evals, tr) : nullptr;
+    double *d_min = min_ev_m ? c.out(min_ev_m, n) : nullptr;
+    int32_t *d_st = status ? c.out(status, n) : nullptr;
+    ICG_LAUNCH_GUARD(c);
+    if (n_fast > 0) {
+        icg_prof_scope ps(ctx, "marg_lin_lds");
+        hipLaunchKernelGGL(k_marg_linearize<true>, dim3(n_fast), dim3(LIN_THREADS), lds_fast, ctx->stream, n_fast, d_items, d_desc, d_H, d_b, eps, d_Hp, d_bp,
+                           d_J0, d_e0, d_ev, d_min, d_st, ctx->d_lin_scratch);
+    }
+    if (n_windows - n_fast > 0) {
+        icg_prof_scope ps(ctx, "marg_lin_global");
+        hipLaunchKernelGGL(k_marg_linearize<false>, dim3(n_windows - n_fast), dim3(LIN_THREADS), lds_slow, ctx->stream, n_windows - n_fast, d_items + n_fast,
+                           d_desc, d_H, d_b, eps, d_Hp, d_bp, d_J0, d_e0, d_ev, d_min, d_st, ctx->d_lin_scratch);
+    }
+    ICG_HIP(ctx, hipGetLastError());
+    return c.finish();
+}

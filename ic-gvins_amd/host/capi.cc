@@ -370,6 +370,7 @@ int icgh_core_order_selftest(uint64_t seed, int n_first, int n_more, int rounds)
 #include "solver_hip.h"
 #include "solver_batch_hip.h"
 #include "marg_batch.h"
+#include "marg_linearize_hip.h"
 #include "culling_hip.h"
 #include "window_visual.h"
 
@@ -563,7 +564,7 @@ int icgh_backend_marginalize(int n, const double *obs_soa, const int32_t *idx_i,
 // The marginalizations of n_windows streams (M1-M4 of each: the window of icgh_backend_marginalize, window w > 0 with its poses and inverse
 // depths moved by a deterministic jitter of relative size `jitter`), mode 0: one MarginalizationBatch (marg_batch.h: the windows share
 // their device launches), mode 1: one MarginalizationInfo::marginalization() after the other on a ReprojectionBatch (what a stream on its
-// own does).  dense_window >= 0: that window gets a host factor on one of its inverse depths, which takes it off the landmark-eliminated
+// own does), mode 2: mode 0 with MarginalizationBatch::setDeviceLinearization (M3 + linearization of all windows in one device call).  dense_window >= 0: that window gets a host factor on one of its inverse depths, which takes it off the landmark-eliminated
 // path in both modes.  The whole set is marginalized `reps` times on the SAME batch object (as a group of streams does keyframe after
 // keyframe: the problems are rebuilt each time, outside the clock).  Outputs per window of the last repetition (r = sizes[1], equal for
 // all windows): Hp (r x r), bp, J0 (r x r), e0; counts = windows on the structured / dense path, seconds = wall time of the
@@ -630,17 +631,19 @@ int icgh_backend_marginalize_batch(int mode, int n_windows, int dense_window, do
         double best = -1.0;
         std::unique_ptr<MarginalizationBatch> mb;
         std::unique_ptr<ReprojectionBatch> batch;
-        if (mode == 0)
+        if (mode == 0 || mode == 2) {
             mb.reset(new MarginalizationBatch(0, huber_delta, host_threads));
-        else
+            mb->setDeviceLinearization(mode == 2);
+        } else {
             batch.reset(new ReprojectionBatch(0));
+        }
         for (int rep = 0; rep < std::max(1, reps); rep++) {
             if (mb) mb->clear(); // (before the infos of the last repetition go)
             if (batch) batch->clear();
             build(wins);
             counts[0] = counts[1] = 0;
             double took = 0;
-            if (mode == 0) {
+            if (mb) {
                 for (auto &W : wins) {
                     const int w = mb->addWindow(W->info);
                     for (int k = 0; k < n; k++)
@@ -976,6 +979,75 @@ int icgh_backend_preint_eval_time(int variant, int n, const int32_t *offsets, co
             for (int i = 0; i < 480; i++) dJ = std::max(dJ, std::fabs(Jd[480 * k + i] - Jh[480 * k + i]));
         }
         out6[0] = best_host, out6[1] = best_dev, out6[2] = launches > 0 ? ms / launches : 0.0, out6[3] = dr, out6[4] = dJ, out6[5] = evaluated;
+        return 0;
+    } catch (const std::exception &e) {
+        set_err(err, errlen, e.what());
+        return -1;
+    }
+}
+
+// M3 on raw arrays, for comparison and timing (profiles/marg_linearize_probe.py): the reduced systems of n_windows windows in the layout of
+// icg_marg_linearize_batch.  mode 0: linearizeReduced per window on a HostPool of host_threads threads, mode 1: one
+// icg_marg_linearize_batch call (MarginalizationLinearizer).  J0 and e0 are required, Hp / bp / evals / min_ev_m / status may be NULL.
+// The batch is run reps + 1 times, the first pass untimed: seconds[0] = the fastest call (transfers included), seconds[1] = the device
+// time of the kernels of one call (mode 1; 0 in mode 0).  Without the device entry point in the build mode 1 computes nothing: -4 and
+// "icg_marg_linearize_batch is not in this build".
+int icgh_backend_marg_linearize(int mode, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
+                                int host_threads, int reps, double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m,
+                                int32_t *status, double *seconds, char *err, int errlen) {
+    try {
+        if (mode != 0 && mode != 1) {
+            set_err(err, errlen, "icgh_backend_marg_linearize: mode is neither 0 (host) nor 1 (device)");
+            return -1;
+        }
+        if (mode == 1 && !MarginalizationLinearizer::available()) {
+            set_err(err, errlen, "icg_marg_linearize_batch is not in this build");
+            return -4;
+        }
+        if (n_windows <= 0 || !P || !m || !H || !b || !J0 || !e0 || !seconds) {
+            set_err(err, errlen, "icgh_backend_marg_linearize: invalid argument");
+            return -1;
+        }
+        for (int w = 0; w < n_windows; w++)
+            if (P[w] <= 0 || m[w] < 0 || m[w] >= P[w]) {
+                set_err(err, errlen, ("icgh_backend_marg_linearize: window " + std::to_string(w) + " is not a valid system").c_str());
+                return -1;
+            }
+        icg_ctx *ctx = nullptr;
+        if (mode == 1) {
+            icg_ctx_config cfg{};
+            cfg.device = 0, cfg.width = 64, cfg.height = 64, cfg.n_slots = 1, cfg.max_batch = 1, cfg.max_points = 64;
+            if (icg_ctx_create(&cfg, &ctx) != ICG_OK) {
+                set_err(err, errlen, icg_last_error(nullptr));
+                return -1;
+            }
+        }
+        const int passes = (reps > 0 ? reps : 0) + 1;
+        double best = -1, best_kernel = 0;
+        std::string what;
+        {
+            MarginalizationLinearizer lin(mode == 1, ctx, host_threads < 1 ? 1 : host_threads);
+            for (int rep = 0; rep < passes; rep++) {
+                if (ctx && rep == passes - 1) icg_prof_enable(ctx, 1); // (the last pass carries the event records: its wall time still counts)
+                const auto a = std::chrono::steady_clock::now();
+                if (!lin.linearize(n_windows, P, m, H, b, eps, Hp, bp, J0, e0, evals, min_ev_m, status, &what)) {
+                    set_err(err, errlen, what.c_str());
+                    if (ctx) icg_ctx_destroy(ctx);
+                    return -2;
+                }
+                const double t = std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count();
+                if ((rep > 0 || passes == 1) && (best < 0 || t < best)) best = t;
+            }
+        }
+        if (ctx) {
+            for (const char *name : {"marg_lin_lds", "marg_lin_global"}) {
+                int launches = 0;
+                double ms    = 0;
+                if (icg_prof_get(ctx, name, &launches, &ms) == ICG_OK && launches > 0) best_kernel += 1e-3 * ms / launches;
+            }
+            icg_ctx_destroy(ctx);
+        }
+        seconds[0] = best, seconds[1] = best_kernel;
         return 0;
     } catch (const std::exception &e) {
         set_err(err, errlen, e.what());

@@ -1,6 +1,7 @@
 // Host side of the back-end boundary (see factors.h for the reference lines each class mirrors).
 #include "factors.h"
 
+#include <limits>
 #include <condition_variable>
 #include <deque>
 #include <mutex>
@@ -791,10 +792,12 @@ bool MarginalizationInfo::finishStructured(StructuredPlan &plan, double min_hll)
     return true;
 }
 
-void MarginalizationInfo::schurElimination() { // :170-192
-    const int m = marginalized_size_, r = remained_size_;
-    const size_t L = (size_t) local_size_;
-    auto H = [&](int i, int j) { return H0_[(size_t) i * L + j]; };
+// :170-192 on plain arrays: the m leading columns of the P x P system (H row-major, b) are eliminated
+void schurReduce(int P, int m, const double *H0, const double *b0, double eps, vector<double> &Hp, vector<double> &bp, double *min_ev_m,
+                 int *status) {
+    const int r    = P - m;
+    const size_t L = (size_t) P;
+    auto H = [&](int i, int j) { return H0[(size_t) i * L + j]; };
     vector<double> Hmm((size_t) m * m), ev, V, Hinv((size_t) m * m, 0.0);
     for (int i = 0; i < m; i++)
         for (int j = 0; j < m; j++) Hmm[(size_t) i * m + j] = 0.5 * (H(i, j) + H(j, i));
@@ -802,10 +805,12 @@ void MarginalizationInfo::schurElimination() { // :170-192
     symmetricEigen(m, Hmm, ev, V);
     auto tB = std::chrono::steady_clock::now();
     if (getenv("ICG_MARG_DEBUG")) fprintf(stderr, "[schur] eigen(%d) %.3f ms\n", m, std::chrono::duration<double, std::milli>(tB - tA).count());
+    if (min_ev_m) *min_ev_m = m > 0 ? ev[0] : std::numeric_limits<double>::infinity();
+    if (status && m > 0 && ev[0] <= eps) *status |= 2;
     // Hmm^+ = V diag(1/ev, 0 below EPS) V^T: the thresholded reciprocals once, the scaled copy W = V diag(inv) once, and only the
     // lower triangle of the symmetric product
     vector<double> inv((size_t) m), Wv((size_t) m * m);
-    for (int k = 0; k < m; k++) inv[(size_t) k] = ev[(size_t) k] > EPS ? 1.0 / ev[(size_t) k] : 0.0;
+    for (int k = 0; k < m; k++) inv[(size_t) k] = ev[(size_t) k] > eps ? 1.0 / ev[(size_t) k] : 0.0;
     for (int i = 0; i < m; i++)
         for (int k = 0; k < m; k++) Wv[(size_t) i * m + k] = V[(size_t) i * m + k] * inv[(size_t) k];
     for (int i = 0; i < m; i++)
@@ -821,36 +826,54 @@ void MarginalizationInfo::schurElimination() { // :170-192
             for (int k = 0; k < m; k++) s += H(m + i, k) * Hinv[(size_t) k * m + j];
             T[(size_t) i * m + j] = s;
         }
-    Hp_.assign((size_t) r * r, 0.0);
-    bp_.assign((size_t) r, 0.0);
+    Hp.assign((size_t) r * r, 0.0);
+    bp.assign((size_t) r, 0.0);
     for (int i = 0; i < r; i++) {
         for (int j = 0; j < r; j++) {
             double s = 0;
             for (int k = 0; k < m; k++) s += T[(size_t) i * m + k] * H(k, m + j);
-            Hp_[(size_t) i * r + j] = H(m + i, m + j) - s;
+            Hp[(size_t) i * r + j] = H(m + i, m + j) - s;
         }
         double s = 0;
-        for (int k = 0; k < m; k++) s += T[(size_t) i * m + k] * b0_[(size_t) k];
-        bp_[(size_t) i] = b0_[(size_t) m + i] - s;
+        for (int k = 0; k < m; k++) s += T[(size_t) i * m + k] * b0[(size_t) k];
+        bp[(size_t) i] = b0[(size_t) m + i] - s;
     }
 }
 
-void MarginalizationInfo::linearization() { // :153-167
-    const int r = remained_size_;
+// :153-167 on plain arrays
+void linearizePrior(int r, const vector<double> &Hp, const vector<double> &bp, double eps, vector<double> &J0, vector<double> &e0,
+                    vector<double> *evals, int *status) {
     vector<double> ev, V;
-    symmetricEigen(r, Hp_, ev, V);
-    linearized_jacobians_.assign((size_t) r * r, 0.0);
-    linearized_residuals_.assign((size_t) r, 0.0);
+    symmetricEigen(r, Hp, ev, V);
+    J0.assign((size_t) r * r, 0.0);
+    e0.assign((size_t) r, 0.0);
     for (int k = 0; k < r; k++) {
-        const double S = ev[(size_t) k] > EPS ? ev[(size_t) k] : 0.0, Sinv = ev[(size_t) k] > EPS ? 1.0 / ev[(size_t) k] : 0.0;
+        const double S = ev[(size_t) k] > eps ? ev[(size_t) k] : 0.0, Sinv = ev[(size_t) k] > eps ? 1.0 / ev[(size_t) k] : 0.0;
         const double ss = std::sqrt(S), si = std::sqrt(Sinv);
         double vb = 0;
         for (int i = 0; i < r; i++) {
-            linearized_jacobians_[(size_t) k * r + i] = ss * V[(size_t) i * r + k];
-            vb += V[(size_t) i * r + k] * -bp_[(size_t) i];
+            J0[(size_t) k * r + i] = ss * V[(size_t) i * r + k];
+            vb += V[(size_t) i * r + k] * -bp[(size_t) i];
         }
-        linearized_residuals_[(size_t) k] = si * vb;
+        e0[(size_t) k] = si * vb;
     }
+    if (status && r > 0 && ev[0] <= eps) *status |= 4;
+    if (evals) evals->swap(ev);
+}
+
+void linearizeReduced(int P, int m, const double *H, const double *b, double eps, vector<double> &Hp, vector<double> &bp, vector<double> &J0,
+                      vector<double> &e0, vector<double> *evals, double *min_ev_m, int *status) {
+    if (status) *status = 0;
+    schurReduce(P, m, H, b, eps, Hp, bp, min_ev_m, status);
+    linearizePrior(P - m, Hp, bp, eps, J0, e0, evals, status);
+}
+
+void MarginalizationInfo::schurElimination() { // :170-192
+    schurReduce(local_size_, marginalized_size_, H0_.data(), b0_.data(), EPS, Hp_, bp_, nullptr, nullptr);
+}
+
+void MarginalizationInfo::linearization() { // :153-167
+    linearizePrior(remained_size_, Hp_, bp_, EPS, linearized_jacobians_, linearized_residuals_, nullptr, nullptr);
 }
 
 // ---- MarginalizationFactor (marginalization_factor.h:31-105) ----------------------------------------------------------

@@ -278,6 +278,18 @@ private:
     size_t residual_size_{0}, jacobian_size_{0};
 };
 
+// M3 on plain arrays (marginalization_info.h:153-192), what MarginalizationInfo::schurElimination / linearization run.  schurReduce: the m
+// leading columns of the P x P system (H row-major, b) are eliminated through the eigen-decomposition of Hmm with the eps floor (m = 0:
+// Hp = H, bp = b).  linearizePrior: Hp = J0^T J0, bp = -J0^T e0 on the eigenvalues above eps (J0 r x r row-major).  Optional: evals (of
+// Hp, ascending), min_ev_m (smallest eigenvalue of the m-block, +inf for m = 0), status (bits OR-ed in: 2 = an m-block eigenvalue <= eps,
+// 4 = an Hp eigenvalue <= eps; linearizeReduced clears it first).
+void schurReduce(int P, int m, const double *H, const double *b, double eps, vector<double> &Hp, vector<double> &bp, double *min_ev_m = nullptr,
+                 int *status = nullptr);
+void linearizePrior(int r, const vector<double> &Hp, const vector<double> &bp, double eps, vector<double> &J0, vector<double> &e0,
+                    vector<double> *evals = nullptr, int *status = nullptr);
+void linearizeReduced(int P, int m, const double *H, const double *b, double eps, vector<double> &Hp, vector<double> &bp, vector<double> &J0,
+                      vector<double> &e0, vector<double> *evals = nullptr, double *min_ev_m = nullptr, int *status = nullptr);
+
 // symmetric eigen-decomposition (Householder tridiagonalisation + implicit QL), eigenvalues ascending, evecs row-major with eigenvectors in columns
 void symmetricEigen(int n, const vector<double> &A, vector<double> &evals, vector<double> &evecs);
 

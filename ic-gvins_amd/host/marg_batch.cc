@@ -1,5 +1,6 @@
 // MarginalizationBatch: see marg_batch.h.  Reference: factors/marginalization_info.h:73-101 (marginalization), :153-273 (the steps).
 #include "marg_batch.h"
+#include "marg_linearize_hip.h"
 #include "solver_batch_hip.h"
 
 #include <algorithm>
@@ -293,23 +294,79 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     auto t3 = now();
 
     // ---- 4: guard + M3 on the camera block (or the dense M2 + M3), linearization -------------------------------------------------------------
-    std::vector<char> structured(NW, 0), good(NW, 0);
+    std::vector<char> structured(NW, 0), good(NW, 0), added(NW, 0), on_device(NW, 0);
+    std::vector<double> min_hll(NW, 0.0);
+    // the landmark-eliminated device part joins the window's compact system; the smallest landmark diagonal for the first guard
+    auto addEliminated = [&](size_t w) {
+        const Slice &W                             = *windows_[w];
+        MarginalizationInfo::StructuredPlan &plan = st[w].plan;
+        const int Pw                              = plan.P;
+        const double *Sw = &S[w * (size_t) P * P], *sw = &s[w * (size_t) P];
+        for (int i = 0; i < Pw; i++) {
+            for (int j = 0; j < Pw; j++) plan.H[(size_t) i * Pw + j] += Sw[(size_t) i * P + j];
+            plan.b[(size_t) i] += sw[i];
+        }
+        double mn = W.landmarks.empty() ? 0.0 : hll[(size_t) W.lm_begin];
+        for (size_t l = 0; l < W.landmarks.size(); l++) mn = std::min(mn, hll[(size_t) W.lm_begin + l]);
+        min_hll[w] = mn;
+        added[w]   = 1;
+    };
+    // device M3 (setDeviceLinearization): every planned window that passes the first guard, one call
+    std::vector<double> dev_Hp, dev_bp, dev_J0, dev_e0, dev_min;
+    std::vector<int32_t> dev_status;
+    std::vector<size_t> dev_r_off(NW, 0), dev_rr_off(NW, 0);
+    if (device_linearization_) {
+        const double GUARD = 100.0 * 1e-8; // (finishStructured: 100 x the reference's floor)
+        forEachWindow(NW, [&](size_t w) {
+            if (st[w].alive && st[w].planned) addEliminated(w);
+        });
+        std::vector<int32_t> dP, dm;
+        std::vector<size_t> h_off, who;
+        size_t th = 0, tb = 0, tr = 0, trr = 0;
+        for (size_t w = 0; w < NW; w++) {
+            if (!added[w] || !(min_hll[w] > GUARD)) continue;
+            const MarginalizationInfo::StructuredPlan &plan = st[w].plan;
+            on_device[w] = 1, dev_r_off[w] = tr, dev_rr_off[w] = trr;
+            who.push_back(w), h_off.push_back(th);
+            dP.push_back(plan.P), dm.push_back(plan.m);
+            th += (size_t) plan.P * plan.P, tb += (size_t) plan.P, tr += (size_t) plan.r, trr += (size_t) plan.r * plan.r;
+        }
+        if (!who.empty()) {
+            std::vector<double> dH(th), db(tb);
+            std::vector<size_t> b_off(who.size(), 0);
+            for (size_t k = 1; k < who.size(); k++) b_off[k] = b_off[k - 1] + (size_t) dP[k - 1];
+            forEachWindow(who.size(), [&](size_t k) {
+                const MarginalizationInfo::StructuredPlan &plan = st[who[k]].plan;
+                memcpy(&dH[h_off[k]], plan.H.data(), sizeof(double) * plan.H.size());
+                memcpy(&db[b_off[k]], plan.b.data(), sizeof(double) * plan.b.size());
+            });
+            dev_Hp.resize(trr), dev_bp.resize(tr), dev_J0.resize(trr), dev_e0.resize(tr), dev_min.resize(who.size()), dev_status.resize(who.size());
+            MarginalizationLinearizer lin(true, ctx_);
+            std::string what;
+            if (!lin.linearize((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev_Hp.data(), dev_bp.data(), dev_J0.data(),
+                               dev_e0.data(), nullptr, dev_min.data(), dev_status.data(), &what))
+                return fail(what);
+            for (size_t k = 0; k < who.size(); k++) // second guard of finishStructured, and a solver that did not converge
+                if (!(dev_min[k] > GUARD) || (dev_status[k] & 1)) on_device[who[k]] = 0;
+        }
+    }
     forEachWindow(NW, [&](size_t w) {
         if (!st[w].alive) return;
         Slice &W               = *windows_[w];
         MarginalizationInfo &I = *W.info;
-        bool done              = false;
+        if (on_device[w]) {
+            const size_t r = (size_t) st[w].plan.r;
+            I.Hp_.assign(dev_Hp.begin() + (long) dev_rr_off[w], dev_Hp.begin() + (long) (dev_rr_off[w] + r * r));
+            I.bp_.assign(dev_bp.begin() + (long) dev_r_off[w], dev_bp.begin() + (long) (dev_r_off[w] + r));
+            I.linearized_jacobians_.assign(dev_J0.begin() + (long) dev_rr_off[w], dev_J0.begin() + (long) (dev_rr_off[w] + r * r));
+            I.linearized_residuals_.assign(dev_e0.begin() + (long) dev_r_off[w], dev_e0.begin() + (long) (dev_r_off[w] + r));
+            structured[w] = good[w] = 1;
+            return;
+        }
+        bool done = false;
         if (st[w].planned) {
-            MarginalizationInfo::StructuredPlan &plan = st[w].plan;
-            const int Pw                              = plan.P;
-            const double *Sw = &S[w * (size_t) P * P], *sw = &s[w * (size_t) P];
-            for (int i = 0; i < Pw; i++) {
-                for (int j = 0; j < Pw; j++) plan.H[(size_t) i * Pw + j] += Sw[(size_t) i * P + j];
-                plan.b[(size_t) i] += sw[i];
-            }
-            double mn = W.landmarks.empty() ? 0.0 : hll[(size_t) W.lm_begin];
-            for (size_t l = 0; l < W.landmarks.size(); l++) mn = std::min(mn, hll[(size_t) W.lm_begin + l]);
-            done = I.finishStructured(plan, mn);
+            if (!added[w]) addEliminated(w);
+            done          = I.finishStructured(st[w].plan, min_hll[w]);
             structured[w] = done ? 1 : 0;
         }
         if (!done) {

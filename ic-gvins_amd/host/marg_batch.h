@@ -53,6 +53,14 @@ public:
     // (its dense fallback could not run) has ok[w] == 0 and its message in windowError(); the other windows are unaffected.
     bool marginalize(std::vector<char> *ok);
 
+    // Step 4 on the device (default off): the guard on the landmark diagonals stays on the host, then ALL planned windows go through one
+    // icg_marg_linearize_batch call (M3 on the camera block + linearization, marg_linearize_hip.h); the conditioning guard of the small
+    // block (every eigenvalue > 100 x the floor) is applied to the call's min_ev_m.  A window that fails either guard, or whose QL
+    // iteration hit its cap, takes the host path of the default mode.  The device's hypot may round differently from the host's: results
+    // agree with the default mode to rounding, not bit for bit.  marginalize() fails (error()) when the entry point is not in the build.
+    void setDeviceLinearization(bool on) { device_linearization_ = on; }
+    bool deviceLinearization() const { return device_linearization_; }
+
     // diagnostics of the last marginalize(): windows that took the landmark-eliminated device path / the dense path; wall time of the
     // four phases above [ms]
     int structuredWindows() const { return n_structured_; }
@@ -96,6 +104,7 @@ private:
     std::unique_ptr<HostPool> pool_;
     std::vector<std::unique_ptr<Slice>> windows_;
     bool laid_out_{false};
+    bool device_linearization_{false};
     std::vector<std::shared_ptr<ResidualBlockInfo>> retired_; // factor records of marginalized windows, freed by clear() / the destructor
     int n_factors_{0}, n_poses_{0}, n_lm_{0};
     int n_structured_{0}, n_dense_{0};

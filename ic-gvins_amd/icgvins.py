@@ -21,11 +21,12 @@ EXPORTS = [
     "icg_ins_mechanize_batch", "icg_ins_camera_pose_batch", "icg_reproj_schur", "icg_reproj_backsub", "icg_reproj_cost", "icg_reproj_landmark_diag",
     "icg_reproj_error_batch", "icg_reproj_set_windows", "icg_reproj_eval_windows", "icg_reproj_schur_windows",
     "icg_reproj_schur_windows_view", "icg_reproj_reserve_windows", "icg_reproj_eval_resident_view", "icg_reproj_backsub_windows", "icg_reproj_cost_windows", "icg_reproj_fetch_residuals", "icg_reproj_chi2_cull",
-    "icg_marg_prior_set", "icg_marg_prior_evaluate",
+    "icg_marg_prior_set", "icg_marg_prior_evaluate", "icg_marg_linearize_batch",
 ]
 
 
 MARG_MAX_R = 1024  # ICG_MARG_MAX_R of include/icgvins_hip.h
+MARG_LIN_MAX_P = 512  # ICG_MARG_LIN_MAX_P
 
 
 class IcgError(RuntimeError):
@@ -472,6 +473,25 @@ class Context:
         sq = np.zeros(n) if want_sq_norm else None
         self._ck(self.lib.icg_marg_prior_evaluate(self.h, _p(x), _p(res), _p(jac), _p(grad), _p(sq)), "icg_marg_prior_evaluate")
         return res, jac, grad, sq
+
+    # ---- M3
+    def marg_linearize_batch(self, P, m, H, b, eps=1e-8, want_Hp=True, want_bp=True, want_evals=True, want_min_ev=True, want_status=True):
+        """icg_marg_linearize_batch: H / b flat, window after window -> dict(J0, e0, Hp, bp, evals, min_ev_m, status), flat (None where
+        not asked for)"""
+        P, m = _i32(P).reshape(-1), _i32(m).reshape(-1)
+        H, b = _f64(H).reshape(-1), _f64(b).reshape(-1)
+        n = len(P)
+        if len(m) != n or H.shape[0] != int((P.astype(np.int64) ** 2).sum()) or b.shape[0] != int(P.sum()):
+            raise IcgError("marg_linearize_batch: P, m, H, b do not describe the same windows")
+        r = P.astype(np.int64) - m
+        nr, nrr = int(r.clip(0).sum()), int((r.clip(0) ** 2).sum())
+        out = dict(J0=np.zeros(nrr), e0=np.zeros(nr), Hp=np.zeros(nrr) if want_Hp else None, bp=np.zeros(nr) if want_bp else None,
+                   evals=np.zeros(nr) if want_evals else None, min_ev_m=np.zeros(n) if want_min_ev else None,
+                   status=np.zeros(n, np.int32) if want_status else None)
+        self._ck(self.lib.icg_marg_linearize_batch(self.h, n, _p(P), _p(m), _p(H), _p(b), C.c_double(eps), _p(out["Hp"]), _p(out["bp"]),
+                                                   _p(out["J0"]), _p(out["e0"]), _p(out["evals"]), _p(out["min_ev_m"]), _p(out["status"])),
+                 "icg_marg_linearize_batch")
+        return out
 
     # ---- f4
     def ins_mechanize_batch(self, offsets, imu, cfg8, states23, want_traj=True):

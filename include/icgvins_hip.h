@@ -305,6 +305,27 @@ int icg_marg_prior_set(icg_ctx *ctx, int n_windows, const int32_t *r, const int3
  * ICG_ERR_INVALID without a resident set or with NULL x / residuals. */
 int icg_marg_prior_evaluate(icg_ctx *ctx, const double *x, double *residuals, double *jacobians, double *gradient, double *sq_norm);
 
+/* ---- M3: the Schur step on the marginalized pose / mix block and the linearization (factors/marginalization_info.h:153-192) for the
+ * reduced systems of many windows, one workgroup per window.  Window w: H (P[w] x P[w], row-major) and b (P[w]), concatenated window after
+ * window; the m[w] leading columns are eliminated (0 <= m < P; m = 0: Hp = H, bp = b), r = P - m remain.
+ *   :170-192  Hmm = (H + H^T) / 2 on the m leading columns, its eigen-decomposition, inv_k = ev_k > eps ? 1 / ev_k : 0, Hinv from its
+ *             lower triangle, T = Hrm Hinv, Hp = Hrr - T Hmr, bp = br - T bm
+ *   :153-167  eigen-decomposition of Hp (eigenvalues ascending), J0[k][i] = sqrt(S_k) V[i][k], e0[k] = sqrt(Sinv_k) sum_i V[i][k] (-bp[i])
+ *             with S_k = ev_k > eps ? ev_k : 0, Sinv_k = ev_k > eps ? 1 / ev_k : 0
+ * The eigen-solver is the host layer's (Householder tridiagonalisation, implicit QL, 60 iterations per eigenvalue at most); every sum is
+ * one thread's chain from 0 in the host's index order, one multiply and one add per term.  Only hypot may round differently from the host.
+ * Outputs per window, concatenated: J0 (r x r row-major) and e0 (r) are required.  Optional, NULL = not computed / not transferred:
+ *   Hp (r x r), bp (r), evals (r: the eigenvalues of Hp, ascending), min_ev_m (1: smallest eigenvalue of the m-block, +inf for m = 0),
+ *   status (1, a bit set: 1 = a QL sweep hit its iteration cap, 2 = an eigenvalue of the m-block <= eps, 4 = an eigenvalue of Hp <= eps —
+ *   a rank-deficient Hp is normal, bit 4 is information).
+ * A window's outputs are the same bits alone, in any batch, in any batch order and run after run.
+ * ICG_ERR_INVALID (the message names the window): n_windows <= 0, a NULL required pointer, eps < 0, P <= 0 or m outside [0, P).
+ * ICG_ERR_CAPACITY (window named): P above ICG_MARG_LIN_MAX_P, more than 65535 windows.  After an error nothing was launched and no output
+ * was touched. */
+#define ICG_MARG_LIN_MAX_P 512
+int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
+                             double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status);
+
 /* ---- f3 (SURVEY.md §8 "next" row): per-observation arithmetic of GVINS::gvinsOutlierCulling (ic_gvins.cc:1035-1128) and
  * GVINS::parametersStatistic (ic_gvins.cc:930-1033).  Observation i = landmark lm_idx[i] (world position pw, n_lm x 3) seen in
  * keyframe pose_idx[i] (poses12: n_poses x 12, R row-major camera->world | t) at the undistorted key point pix[i]:
