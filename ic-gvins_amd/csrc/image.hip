@@ -374,7 +374,7 @@ __global__ __launch_bounds__(256) void k_clahe_apply(pre_jobs jobs, clahe_geom g
     // pair range touched by this chunk: p = floor(x*inv_tw - 0.5) + 1
     const int p_lo   = (int) floorf(x_begin * g.inv_tw - 0.5f) + 1;
     const int p_hi   = (int) floorf((x_end - 1) * g.inv_tw - 0.5f) + 1;
-    const int npairs = p_hi - p_lo + 1; // <= CLAHE_MAXCOLS by construction of the launch (checked on host)
+    const int npairs = p_hi - p_lo + 1; // <= ICG_CLAHE_TILES + 1 <= CLAHE_MAXCOLS: x < w <= T * tw gives p in 0 .. T whatever the tile width
     if (npairs <= CLAHE_FCOLS) // workgroup-uniform
         clahe_apply_body<true>(jobs, g, lut, frames, slot_bytes, dpitch, slut, strip, chunk, b, t, dslot, p_lo, npairs, x_begin);
     else
@@ -536,8 +536,10 @@ static int preprocess_impl(icg_ctx *ctx, int n, const int32_t *slots, const int3
     if (g.clip < 1) g.clip = 1;
     g.inv_tw = 1.0f / g.tw;
     g.inv_th = 1.0f / g.th;
-    if (CLAHE_CHUNK / g.tw + 3 > CLAHE_MAXCOLS)
-        return icg_fail(ctx, ICG_ERR_INVALID, "image too small for CLAHE chunking (tile width %d)", g.tw);
+    // (k_clahe_apply stages the LUT pairs a 256-px chunk touches: at most T + 1 of them exist — pair p = floor(x / tw - 0.5) + 1 of a column
+    // x < w <= T * tw lies in 0 .. T — so the byte form's CLAHE_MAXCOLS covers every image icg_ctx_create accepts, down to 32 x 32 with its
+    // 2 x 2 tiles.  A bound on 256 / tw + 3 stood here before and refused every frame narrower than 232 px.)
+    static_assert(ICG_CLAHE_TILES + 1 <= CLAHE_MAXCOLS, "k_clahe_apply's staged LUT must hold every interpolation column pair");
 
     const size_t raw_batch = (size_t) ctx->raw_pitch * h;
     hipMemcpyKind kind     = src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;

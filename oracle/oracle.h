@@ -37,6 +37,19 @@ void orc_lk_track(const uint8_t *prev, const uint8_t *next, int w, int h, int st
                   float *next_pts, uint8_t *status, float *err);
 void orc_lk_track_fb(const uint8_t *prev, const uint8_t *next, int w, int h, int stride, int n, const float *prev_pts,
                      const float *guess_pts, float *out_pts, uint8_t *status);
+// how a point left a pyramid level (orc_lk_track_trace)
+enum {
+    ORC_LK_EXIT_NONE        = 0, // the pyramid has no such level
+    ORC_LK_EXIT_SKIPPED     = 1, // the window of the previous point lies outside the level ("continue" before any sum)
+    ORC_LK_EXIT_WEAK        = 2, // minimum-eigenvalue / determinant test
+    ORC_LK_EXIT_OUT         = 3, // the window in the next image left the level during the iterations
+    ORC_LK_EXIT_CONVERGED   = 4, // |step|^2 <= eps^2
+    ORC_LK_EXIT_OSCILLATION = 5, // step + previous step below 0.01 on both axes
+    ORC_LK_EXIT_CAP         = 6  // 30 iterations
+};
+#define ORC_LK_MAX_LEVELS 4
+int orc_lk_track_trace(const uint8_t *prev, const uint8_t *next, int w, int h, int stride, int n, const float *prev_pts, float *next_pts,
+                       uint8_t *status, float *err, int32_t *exit_kind, int32_t *iters, int32_t *travel, int64_t *A, int64_t *bmax);
 
 // ---- camera model (orc_camera.cc) --------------------------------------------------------------------
 void orc_undistort_points(const double *cam10, int n, float *pts);

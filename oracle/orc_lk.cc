@@ -10,6 +10,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -73,7 +74,14 @@ constexpr int WIN = 21;
 constexpr int HALF = 10;
 constexpr int MAX_ITERS = 30;
 
-void lk_point(const Pyr &P, const Pyr &N, float px, float py, float *nx, float *ny, uint8_t *status, float *err) {
+// What one point did on one pyramid level (orc_lk_track_trace): observation only, nothing below reads it back.
+struct LevelTrace {
+    int exit_kind = ORC_LK_EXIT_NONE, iters = 0, travel = 0;
+    int64_t A11 = 0, A12 = 0, A22 = 0, b1max = 0, b2max = 0;
+};
+
+void lk_point(const Pyr &P, const Pyr &N, float px, float py, float *nx, float *ny, uint8_t *status, float *err,
+              LevelTrace *trace = nullptr) {
     const float FLT_SCALE = 1.f / (1 << 20);
     const double eps2     = 0.01 * 0.01;
     const float minEigThreshold = 1e-4f;
@@ -103,7 +111,9 @@ void lk_point(const Pyr &P, const Pyr &N, float px, float py, float *nx, float *
         prevx -= (float) HALF;
         prevy -= (float) HALF;
         int ipx = (int) floorf(prevx), ipy = (int) floorf(prevy);
+        LevelTrace scratch, &T = trace ? trace[level] : scratch;
         if (ipx < -WIN || ipx >= I.w || ipy < -WIN || ipy >= I.h) {
+            T.exit_kind = ORC_LK_EXIT_SKIPPED;
             if (level == 0) {
                 *status = 0;
                 if (err) *err = 0;
@@ -139,7 +149,9 @@ void lk_point(const Pyr &P, const Pyr &N, float px, float py, float *nx, float *
         float A11 = (float) iA11 * FLT_SCALE, A12 = (float) iA12 * FLT_SCALE, A22 = (float) iA22 * FLT_SCALE;
         float D      = A11 * A22 - A12 * A12;
         float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (2 * WIN * WIN);
+        T.A11 = iA11, T.A12 = iA12, T.A22 = iA22;
         if (minEig < minEigThreshold || D < FLT_EPSILON) {
+            T.exit_kind = ORC_LK_EXIT_WEAK;
             if (level == 0) *status = 0;
             continue;
         }
@@ -147,12 +159,18 @@ void lk_point(const Pyr &P, const Pyr &N, float px, float py, float *nx, float *
         nptx -= (float) HALF;
         npty -= (float) HALF;
         float pdx = 0, pdy = 0;
+        int inx0 = 0, iny0 = 0;
+        T.exit_kind = ORC_LK_EXIT_CAP; // (the loop running out; every break below names its own)
         for (int j = 0; j < MAX_ITERS; j++) {
             int inx = (int) floorf(nptx), iny = (int) floorf(npty);
             if (inx < -WIN || inx >= J.w || iny < -WIN || iny >= J.h) {
+                T.exit_kind = ORC_LK_EXIT_OUT;
                 if (level == 0) *status = 0;
                 break;
             }
+            if (j == 0) inx0 = inx, iny0 = iny;
+            T.iters  = j + 1;
+            T.travel = std::max(T.travel, std::max(std::abs(inx - inx0), std::abs(iny - iny0)));
             a    = nptx - inx;
             b    = npty - iny;
             iw00 = cv_round_f((1.f - a) * (1.f - b) * (1 << 14));
@@ -170,6 +188,8 @@ void lk_point(const Pyr &P, const Pyr &N, float px, float py, float *nx, float *
                     ib1 += (int64_t) diff * dIx[y * WIN + x];
                     ib2 += (int64_t) diff * dIy[y * WIN + x];
                 }
+            T.b1max  = std::max<int64_t>(T.b1max, ib1 < 0 ? -ib1 : ib1);
+            T.b2max  = std::max<int64_t>(T.b2max, ib2 < 0 ? -ib2 : ib2);
             float b1 = (float) ib1 * FLT_SCALE, b2 = (float) ib2 * FLT_SCALE;
             float dx = (float) ((A12 * b2 - A22 * b1) * D);
             float dy = (float) ((A12 * b1 - A11 * b2) * D);
@@ -177,10 +197,14 @@ void lk_point(const Pyr &P, const Pyr &N, float px, float py, float *nx, float *
             npty += dy;
             nextx = nptx + (float) HALF;
             nexty = npty + (float) HALF;
-            if ((double) dx * dx + (double) dy * dy <= eps2) break;
+            if ((double) dx * dx + (double) dy * dy <= eps2) {
+                T.exit_kind = ORC_LK_EXIT_CONVERGED;
+                break;
+            }
             if (j > 0 && std::fabs(dx + pdx) < 0.01 && std::fabs(dy + pdy) < 0.01) {
                 nextx -= dx * 0.5f;
                 nexty -= dy * 0.5f;
+                T.exit_kind = ORC_LK_EXIT_OSCILLATION;
                 break;
             }
             pdx = dx;
@@ -233,6 +257,33 @@ void orc_lk_track(const uint8_t *prev, const uint8_t *next, int w, int h, int st
             if (err) err[i] = e;
         }
     });
+}
+
+// orc_lk_track with a record of what every point did on every pyramid level (tests/test_oracle_lk_edges.py: the edge inputs have to reach
+// the paths and magnitudes they claim to).  Arrays are indexed [point * ORC_LK_MAX_LEVELS + level], level 0 = full resolution; a level the
+// pyramid does not have keeps ORC_LK_EXIT_NONE.  exit_kind: ORC_LK_EXIT_*; iters: Gauss-Newton iterations entered; travel: the largest
+// |inx - inx0| or |iny - iny0| of the integer window position within the level; A: the exact window sums (A11, A12, A22); bmax: the largest
+// |b1| and |b2| over the iterations.  Points, status and err are those of orc_lk_track, byte for byte (same lk_point).  Returns the level count.
+int orc_lk_track_trace(const uint8_t *prev, const uint8_t *next, int w, int h, int stride, int n, const float *prev_pts, float *next_pts,
+                       uint8_t *status, float *err, int32_t *exit_kind, int32_t *iters, int32_t *travel, int64_t *A, int64_t *bmax) {
+    Pyr P, N;
+    build_pyr(prev, w, h, stride, 3, WIN, true, P);
+    build_pyr(next, w, h, stride, 3, WIN, false, N);
+    orc_parallel_chunks(n, [&](int i0, int i1) {
+        for (int i = i0; i < i1; i++) {
+            float e = 0;
+            LevelTrace T[ORC_LK_MAX_LEVELS];
+            lk_point(P, N, prev_pts[2 * i], prev_pts[2 * i + 1], &next_pts[2 * i], &next_pts[2 * i + 1], &status[i], &e, T);
+            if (err) err[i] = e;
+            for (int l = 0; l < ORC_LK_MAX_LEVELS; l++) {
+                const size_t k = (size_t) i * ORC_LK_MAX_LEVELS + l;
+                exit_kind[k] = T[l].exit_kind, iters[k] = T[l].iters, travel[k] = T[l].travel;
+                A[3 * k] = T[l].A11, A[3 * k + 1] = T[l].A12, A[3 * k + 2] = T[l].A22;
+                bmax[2 * k] = T[l].b1max, bmax[2 * k + 1] = T[l].b2max;
+            }
+        }
+    });
+    return (int) P.lv.size();
 }
 
 // Forward + backward + cull exactly as tracking.cc:385-403 (or :487-506):

@@ -101,6 +101,24 @@ class Oracle:
         self.lib.orc_lk_track(_p(prev), _p(nxt), w, h, w, n, _p(prev_pts), _p(out), _p(st), _p(err))
         return out, st, err
 
+    LK_EXITS = {"none": 0, "skipped": 1, "weak": 2, "out": 3, "converged": 4, "oscillation": 5, "cap": 6}  # oracle.h ORC_LK_EXIT_*
+
+    def lk_track_trace(self, prev, nxt, prev_pts, guess):
+        """lk_track plus, per point and pyramid level (axis 1, level 0 = full resolution): exit kind (LK_EXITS), iterations, in-level travel of
+        the integer window position, the exact int64 window sums A (A11, A12, A22) and the largest |b1|, |b2|"""
+        prev, nxt = _u8(prev), _u8(nxt)
+        h, w = prev.shape
+        prev_pts = _f32(prev_pts).reshape(-1, 2)
+        n = prev_pts.shape[0]
+        out = _f32(guess).reshape(-1, 2).copy()
+        st = np.zeros(n, np.uint8)
+        err = np.zeros(n, np.float32)
+        tr = dict(exit=np.zeros((n, 4), np.int32), iters=np.zeros((n, 4), np.int32), travel=np.zeros((n, 4), np.int32),
+                  A=np.zeros((n, 4, 3), np.int64), bmax=np.zeros((n, 4, 2), np.int64))
+        tr["levels"] = self.lib.orc_lk_track_trace(_p(prev), _p(nxt), w, h, w, n, _p(prev_pts), _p(out), _p(st), _p(err), _p(tr["exit"]),
+                                                   _p(tr["iters"]), _p(tr["travel"]), _p(tr["A"]), _p(tr["bmax"]))
+        return out, st, err, tr
+
     def lk_track_fb(self, prev, nxt, prev_pts, guess):
         prev, nxt = _u8(prev), _u8(nxt)
         h, w = prev.shape
