@@ -1,5 +1,5 @@
 """Replay harness (plumbing for tests and bench.py): synthetic camera streams + a ctypes driver for the host
-layer's multi-stream executor (libicgvins_host.so, C entry points in host/capi.cc).
+layer's multi-stream executor (libicgvins_host.so, C entry points in host/capi_batch.cc).
 
 The library path is a parameter: the product path loads ic-gvins_amd/libicgvins_host.so (HIP-backed, no fallback);
 tests and bench.py's cpu_baseline leg may pass oracle/libicgvins_host_oracle.so (same host code linked on the CPU
@@ -96,7 +96,7 @@ def pingpong(k, n):
 
 
 class StreamBatch:
-    """ctypes driver of icgh_batch (host/capi.cc): N independent streams tracked in lock-step on one device."""
+    """ctypes driver of icgh_batch (host/capi_batch.cc): N independent streams tracked in lock-step on one device."""
 
     def __init__(self, lib_path, n_streams, width, height, cam10, max_features=300, window=10, min_parallax=20.0,
                  max_interval=0.5, check_hist=False, reproj_std=1.5, device=0, host_threads=1, groups=1, engine=None):

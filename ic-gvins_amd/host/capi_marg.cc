@@ -1,0 +1,451 @@
+// C entry points of libicgvins_host.so: the marginalization back end (R1, M1-M4) for tests and probes.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <memory>
+
+#include "factors.h"
+#include "host_pool.h"
+#include "marg_batch.h"
+#include "marg_linearize_hip.h"
+#include "capi_util.h"
+
+using namespace icg;
+
+extern "C" {
+
+// R1 through the ceres::CostFunction surface: factors + EvaluationCallback, one Evaluate() per factor.
+// rc: 0 ok, 1 = an unprepared factor did NOT fail (contract violation), <0 = error.
+int icgh_backend_reproj(int n, const double *obs_soa, const int32_t *idx_i, const int32_t *idx_j, const int32_t *idx_lm,
+                        int n_poses, const double *poses, const double *ext, int n_lm, const double *invdepth, double td,
+                        double *out_r, double *out_J, char *err, int errlen) {
+    return guarded(err, errlen, [&] {
+        vector<double> P(poses, poses + 7 * (size_t) n_poses), E(ext, ext + 7), D(invdepth, invdepth + n_lm);
+        double TD = td;
+        vector<std::unique_ptr<ReprojectionFactor>> factors;
+        ReprojectionBatch batch(0);
+        for (int k = 0; k < n; k++) factors.push_back(reproj_factor_from_soa(obs_soa, n, k));
+        // before registration / preparation Evaluate must fail
+        {
+            double r[2];
+            const double *params[5] = {&P[0], &P[0], E.data(), &D[0], &TD};
+            if (n > 0 && factors[0]->Evaluate(params, r, nullptr)) return 1;
+        }
+        for (int k = 0; k < n; k++)
+            batch.add(factors[(size_t) k].get(), &P[7 * (size_t) idx_i[k]], &P[7 * (size_t) idx_j[k]], E.data(), &D[(size_t) idx_lm[k]], &TD);
+        batch.finalize();
+        {
+            double r[2];
+            const double *params[5] = {&P[0], &P[0], E.data(), &D[0], &TD};
+            if (n > 0 && factors[0]->Evaluate(params, r, nullptr)) return 1; // registered but not prepared
+        }
+        batch.PrepareForEvaluation(true, true);
+        for (int k = 0; k < n; k++) {
+            const double *params[5] = {&P[7 * (size_t) idx_i[k]], &P[7 * (size_t) idx_j[k]], E.data(), &D[(size_t) idx_lm[k]], &TD};
+            double *J              = out_J + 46 * (size_t) k;
+            double *jac[5]         = {J, J + 14, J + 28, J + 42, J + 44};
+            if (!factors[(size_t) k]->Evaluate(params, out_r + 2 * (size_t) k, jac)) {
+                set_err(err, errlen, batch.error().c_str());
+                return -2;
+            }
+        }
+        return 0;
+    });
+}
+
+// M1-M4 through the reference's API: marginalize pose 0 and the landmarks it references.  Parameter ids: pose k -> k,
+// landmark l -> 100000 + l, extrinsic -> 900000, td -> 900001.  estimate_ext/td = 0 keeps those blocks out (constant).
+// Outputs: sizes[0..1] = marginalized, remained local sizes; rem_ids/rem_index/rem_size per retained block (caller
+// allocates n_poses + n_lm + 2 entries); Hp, bp, J0, e0 sized by the caller to (6*n_poses + n_lm + 7)^2 etc.
+// Then evaluates MarginalizationFactor at x = current parameters perturbed by `perturb` (applied as p += d, per block by
+// id order of rem_ids) and writes residuals to marg_res.
+int icgh_backend_marginalize(int n, const double *obs_soa, const int32_t *idx_i, const int32_t *idx_j, const int32_t *idx_lm,
+                             int n_poses, const double *poses, const double *ext, int n_lm, const double *invdepth, double td,
+                             double huber_delta, double prior_weight, int estimate_ext, int estimate_td, int32_t *sizes,
+                             int64_t *rem_ids, int32_t *rem_index, int32_t *rem_size, int32_t *n_rem, double *Hp, double *bp,
+                             double *J0, double *e0, const double *x_eval /* concatenated by rem order, may be NULL */,
+                             double *marg_res, char *err, int errlen) {
+    return guarded(err, errlen, [&] {
+        vector<double> P(poses, poses + 7 * (size_t) n_poses), E(ext, ext + 7), D(invdepth, invdepth + n_lm);
+        double TD = td;
+        std::unordered_map<long, long> ids;
+        std::unordered_map<long, double *> address;
+        auto reg = [&](double *p, long id) {
+            ids[reinterpret_cast<long>(p)] = id;
+            address[id]                     = p;
+        };
+        for (int k = 0; k < n_poses; k++) reg(&P[7 * (size_t) k], k);
+        for (int l = 0; l < n_lm; l++) reg(&D[(size_t) l], 100000 + l);
+        reg(E.data(), 900000);
+        reg(&TD, 900001);
+        (void) estimate_ext;
+        (void) estimate_td;
+
+        auto info = std::make_shared<MarginalizationInfo>();
+        info->updateParamtersIds(ids);
+        ReprojectionBatch batch(0);
+        info->setReprojectionBatch(&batch);
+        auto loss = huber_delta > 0 ? std::make_shared<HuberLossHip>(huber_delta) : nullptr;
+        for (int k = 0; k < n; k++) {
+            std::shared_ptr<ReprojectionFactor> f = reproj_factor_from_soa(obs_soa, n, k);
+            double *pi = &P[7 * (size_t) idx_i[k]], *pj = &P[7 * (size_t) idx_j[k]], *lm = &D[(size_t) idx_lm[k]];
+            batch.add(f.get(), pi, pj, E.data(), lm, &TD);
+            // marginalize {pose_ref, invdepth} as ic_gvins.cc:1600-1606 does
+            info->addResidualBlockInfo(std::make_shared<ResidualBlockInfo>(f, loss, vector<double *>{pi, pj, E.data(), lm, &TD}, vector<int>{0, 3}));
+        }
+        batch.finalize();
+        // host-evaluated generic factor on the marginalized pose (stands in for prior/IMU factors of the real window)
+        vector<double> pose0_prior(P.begin(), P.begin() + 7);
+        pose0_prior[0] += 0.01; // non-zero residual
+        info->addResidualBlockInfo(std::make_shared<ResidualBlockInfo>(std::make_shared<PosePriorFactor>(pose0_prior.data(), prior_weight),
+                                                                       nullptr, vector<double *>{&P[0]}, vector<int>{0}));
+        if (!info->marginalization()) {
+            set_err(err, errlen, ("marginalization failed: " + batch.error()).c_str());
+            return -2;
+        }
+        auto blocks = info->getParamterBlocks(address);
+        sizes[0]    = info->marginalizedSize();
+        sizes[1]    = info->remainedSize();
+        *n_rem      = (int32_t) blocks.size();
+        for (size_t b = 0; b < blocks.size(); b++) {
+            rem_ids[b]   = ids[reinterpret_cast<long>(blocks[b])];
+            rem_index[b] = info->remainedBlockIndex()[b];
+            rem_size[b]  = info->remainedBlockSize()[b];
+        }
+        const size_t r = (size_t) info->remainedSize();
+        memcpy(Hp, info->Hp().data(), sizeof(double) * r * r);
+        memcpy(bp, info->bp().data(), sizeof(double) * r);
+        memcpy(J0, info->linearizedJacobians().data(), sizeof(double) * r * r);
+        memcpy(e0, info->linearizedResiduals().data(), sizeof(double) * r);
+        if (x_eval && marg_res) {
+            MarginalizationFactor factor(info);
+            vector<const double *> params;
+            size_t off = 0;
+            for (size_t b = 0; b < blocks.size(); b++) {
+                params.push_back(x_eval + off);
+                off += (size_t) rem_size[b];
+            }
+            if (!factor.Evaluate(params.data(), marg_res, nullptr)) return -3;
+        }
+        return 0;
+    });
+}
+
+// The marginalizations of n_windows streams (M1-M4 of each: the window of icgh_backend_marginalize, window w > 0 with its poses and inverse
+// depths moved by a deterministic jitter of relative size `jitter`), mode 0: one MarginalizationBatch (marg_batch.h: the windows share
+// their device launches), mode 1: one MarginalizationInfo::marginalization() after the other on a ReprojectionBatch (what a stream on its
+// own does), mode 2: mode 0 with MarginalizationBatch::setDeviceLinearization (M3 + linearization of all windows in one device call).  dense_window >= 0: that window gets a host factor on one of its inverse depths, which takes it off the landmark-eliminated
+// path in both modes.  The whole set is marginalized `reps` times on the SAME batch object (as a group of streams does keyframe after
+// keyframe: the problems are rebuilt each time, outside the clock).  Outputs per window of the last repetition (r = sizes[1], equal for
+// all windows): Hp (r x r), bp, J0 (r x r), e0; counts = windows on the structured / dense path, seconds = wall time of the
+// marginalizations alone in the fastest repetition (problem construction excluded).
+int icgh_backend_marginalize_batch(int mode, int n_windows, int dense_window, double jitter, int reps, int n, const double *obs_soa,
+                                   const int32_t *idx_i, const int32_t *idx_j, const int32_t *idx_lm, int n_poses, const double *poses,
+                                   const double *ext, int n_lm, const double *invdepth, double td, double huber_delta, double prior_weight,
+                                   int host_threads, int32_t *sizes, double *Hp, double *bp, double *J0, double *e0, int32_t *counts,
+                                   double *seconds, char *err, int errlen) {
+    return guarded(err, errlen, [&] {
+        struct Win {
+            vector<double> P, E, D;
+            double TD;
+            std::unordered_map<long, long> ids;
+            std::shared_ptr<MarginalizationInfo> info;
+            vector<std::shared_ptr<ReprojectionFactor>> factors;
+            vector<double> pose0_prior;
+        };
+        auto loss = huber_delta > 0 ? std::make_shared<HuberLossHip>(huber_delta) : nullptr;
+        auto build = [&](vector<std::unique_ptr<Win>> &wins) {
+            wins.clear();
+            uint64_t lcg = 0x9E3779B97F4A7C15ull;
+            auto rnd     = [&] { // uniform in [-1, 1)
+                lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+                return (double) ((lcg >> 11) & ((1ull << 53) - 1)) / (double) (1ull << 52) - 1.0;
+            };
+            for (int w = 0; w < n_windows; w++) {
+                std::unique_ptr<Win> W(new Win);
+                W->P.assign(poses, poses + 7 * (size_t) n_poses), W->E.assign(ext, ext + 7), W->D.assign(invdepth, invdepth + n_lm), W->TD = td;
+                if (w > 0) {
+                    for (int k = 0; k < n_poses; k++)
+                        for (int c = 0; c < 3; c++) W->P[7 * (size_t) k + c] += jitter * rnd();
+                    for (int l = 0; l < n_lm; l++) W->D[(size_t) l] *= 1.0 + jitter * rnd();
+                }
+                for (int k = 0; k < n_poses; k++) W->ids[reinterpret_cast<long>(&W->P[7 * (size_t) k])] = k;
+                for (int l = 0; l < n_lm; l++) W->ids[reinterpret_cast<long>(&W->D[(size_t) l])] = 100000 + l;
+                W->ids[reinterpret_cast<long>(W->E.data())] = 900000;
+                W->ids[reinterpret_cast<long>(&W->TD)]       = 900001;
+                W->info = std::make_shared<MarginalizationInfo>();
+                W->info->updateParamtersIds(W->ids);
+                for (int k = 0; k < n; k++) {
+                    W->factors.push_back(reproj_factor_from_soa(obs_soa, n, k));
+                    double *pi = &W->P[7 * (size_t) idx_i[k]], *pj = &W->P[7 * (size_t) idx_j[k]], *lm = &W->D[(size_t) idx_lm[k]];
+                    W->info->addResidualBlockInfo(
+                        std::make_shared<ResidualBlockInfo>(W->factors.back(), loss, vector<double *>{pi, pj, W->E.data(), lm, &W->TD}, vector<int>{0, 3}));
+                }
+                W->pose0_prior.assign(W->P.begin(), W->P.begin() + 7);
+                W->pose0_prior[0] += 0.01;
+                W->info->addResidualBlockInfo(std::make_shared<ResidualBlockInfo>(std::make_shared<PosePriorFactor>(W->pose0_prior.data(), prior_weight),
+                                                                                  nullptr, vector<double *>{&W->P[0]}, vector<int>{0}));
+                if (w == dense_window && n > 0) {
+                    double *lm = &W->D[(size_t) idx_lm[0]];
+                    W->info->addResidualBlockInfo(std::make_shared<ResidualBlockInfo>(std::make_shared<ScalarPriorFactor>(*lm * 1.01, 0.5 * prior_weight),
+                                                                                      nullptr, vector<double *>{lm}, vector<int>{0}));
+                }
+                wins.push_back(std::move(W));
+            }
+        };
+        vector<std::unique_ptr<Win>> wins;
+        vector<char> ok((size_t) n_windows, 0);
+        std::string what;
+        double best = -1.0;
+        std::unique_ptr<MarginalizationBatch> mb;
+        std::unique_ptr<ReprojectionBatch> batch;
+        if (mode == 0 || mode == 2) {
+            mb.reset(new MarginalizationBatch(0, huber_delta, host_threads));
+            mb->setDeviceLinearization(mode == 2);
+        } else {
+            batch.reset(new ReprojectionBatch(0));
+        }
+        for (int rep = 0; rep < std::max(1, reps); rep++) {
+            if (mb) mb->clear(); // (before the infos of the last repetition go)
+            if (batch) batch->clear();
+            build(wins);
+            counts[0] = counts[1] = 0;
+            double took = 0;
+            if (mb) {
+                for (auto &W : wins) {
+                    const int w = mb->addWindow(W->info);
+                    for (int k = 0; k < n; k++)
+                        mb->addReprojectionFactor(w, W->factors[(size_t) k].get(), &W->P[7 * (size_t) idx_i[k]], &W->P[7 * (size_t) idx_j[k]], W->E.data(),
+                                                  &W->D[(size_t) idx_lm[k]], &W->TD);
+                }
+                auto t0         = std::chrono::steady_clock::now();
+                const bool good = mb->marginalize(&ok);
+                took            = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                if (!good) {
+                    set_err(err, errlen, ("batched marginalization failed: " + mb->error()).c_str());
+                    return -2;
+                }
+                what = mb->windowError();
+                counts[0] = mb->structuredWindows(), counts[1] = mb->denseWindows();
+            } else {
+                for (size_t w = 0; w < wins.size(); w++) {
+                    Win &W = *wins[w];
+                    batch->clear();
+                    for (int k = 0; k < n; k++)
+                        batch->add(W.factors[(size_t) k].get(), &W.P[7 * (size_t) idx_i[k]], &W.P[7 * (size_t) idx_j[k]], W.E.data(), &W.D[(size_t) idx_lm[k]], &W.TD);
+                    W.info->setReprojectionBatch(batch.get());
+                    auto a = std::chrono::steady_clock::now();
+                    batch->finalize();
+                    ok[w] = W.info->marginalization() ? 1 : 0;
+                    took += std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count();
+                    if (!ok[w]) what = batch->error();
+                    counts[MarginalizationInfo::lastWasStructured() ? 0 : 1] += ok[w] ? 1 : 0;
+                }
+            }
+            for (int w = 0; w < n_windows; w++)
+                if (!ok[(size_t) w]) {
+                    set_err(err, errlen, ("marginalization of window " + std::to_string(w) + " failed: " + what).c_str());
+                    return -2;
+                }
+            if (best < 0 || took < best) best = took;
+        }
+        *seconds = best;
+        const size_t r = (size_t) wins[0]->info->remainedSize();
+        sizes[0] = wins[0]->info->marginalizedSize(), sizes[1] = (int32_t) r;
+        for (int w = 0; w < n_windows; w++) {
+            const MarginalizationInfo &I = *wins[(size_t) w]->info;
+            if ((size_t) I.remainedSize() != r) {
+                set_err(err, errlen, "windows of different remained size");
+                return -3;
+            }
+            memcpy(Hp + (size_t) w * r * r, I.Hp().data(), sizeof(double) * r * r);
+            memcpy(bp + (size_t) w * r, I.bp().data(), sizeof(double) * r);
+            memcpy(J0 + (size_t) w * r * r, I.linearizedJacobians().data(), sizeof(double) * r * r);
+            memcpy(e0 + (size_t) w * r, I.linearizedResiduals().data(), sizeof(double) * r);
+        }
+        if (mb) mb->clear(); // (the infos die with `wins` before the batch does)
+        if (batch) batch->clear();
+        return 0;
+    });
+}
+
+// phases of the last MarginalizationInfo::marginalization() of this process: evaluate, construct, Schur, linearize [ms]
+void icgh_backend_marginalization_phases(double *out4) { memcpy(out4, MarginalizationInfo::lastPhaseMs(), sizeof(double) * 4); }
+int icgh_backend_marginalization_structured(void) { return MarginalizationInfo::lastWasStructured() ? 1 : 0; }
+void icgh_backend_marginalization_force_dense(int on) { MarginalizationInfo::forceDense(on != 0); }
+
+// M3 on raw arrays, for comparison and timing (profiles/marg_linearize_probe.py): the reduced systems of n_windows windows in the layout of
+// icg_marg_linearize_batch.  mode 0: linearizeReduced per window on a HostPool of host_threads threads, mode 1: one
+// icg_marg_linearize_batch call (MarginalizationLinearizer).  J0 and e0 are required, Hp / bp / evals / min_ev_m / status may be NULL.
+// The batch is run reps + 1 times, the first pass untimed: seconds[0] = the fastest call (transfers included), seconds[1] = the device
+// time of the kernels of one call (mode 1; 0 in mode 0).  Without the device entry point in the build mode 1 computes nothing: -4 and
+// "icg_marg_linearize_batch is not in this build".
+int icgh_backend_marg_linearize(int mode, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
+                                int host_threads, int reps, double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m,
+                                int32_t *status, double *seconds, char *err, int errlen) {
+    return guarded(err, errlen, [&] {
+        if (mode != 0 && mode != 1) {
+            set_err(err, errlen, "icgh_backend_marg_linearize: mode is neither 0 (host) nor 1 (device)");
+            return -1;
+        }
+        if (mode == 1 && !MarginalizationLinearizer::available()) {
+            set_err(err, errlen, "icg_marg_linearize_batch is not in this build");
+            return -4;
+        }
+        if (n_windows <= 0 || !P || !m || !H || !b || !J0 || !e0 || !seconds) {
+            set_err(err, errlen, "icgh_backend_marg_linearize: invalid argument");
+            return -1;
+        }
+        for (int w = 0; w < n_windows; w++)
+            if (P[w] <= 0 || m[w] < 0 || m[w] >= P[w]) {
+                set_err(err, errlen, ("icgh_backend_marg_linearize: window " + std::to_string(w) + " is not a valid system").c_str());
+                return -1;
+            }
+        std::unique_ptr<TempCtx> T(mode == 1 ? new TempCtx(0) : nullptr);
+        icg_ctx *ctx   = T ? T->ctx : nullptr;
+        const int last = reps > 0 ? reps : 0;
+        double best, best_kernel = 0;
+        std::string what;
+        {
+            MarginalizationLinearizer lin(mode == 1, ctx, host_threads < 1 ? 1 : host_threads);
+            best = best_of(reps, [&](int pass) {
+                if (ctx && pass == last) icg_prof_enable(ctx, 1); // (the last pass carries the event records: its wall time still counts)
+                return lin.linearize(n_windows, P, m, H, b, eps, Hp, bp, J0, e0, evals, min_ev_m, status, &what);
+            });
+        }
+        if (best < 0) {
+            set_err(err, errlen, what.c_str());
+            return -2;
+        }
+        for (const char *name : {"marg_lin_lds", "marg_lin_global"}) {
+            int launches = 0;
+            double ms    = 0;
+            if (ctx && icg_prof_get(ctx, name, &launches, &ms) == ICG_OK && launches > 0) best_kernel += 1e-3 * ms / launches;
+        }
+        seconds[0] = best, seconds[1] = best_kernel;
+        return 0;
+    });
+}
+
+// M4 on raw arrays, for comparison and timing (profiles/marg_factor_probe.py): the priors of n_windows windows in the layout of
+// icg_marg_prior_set, evaluated at n_points points (x: n_points sets laid out like x0).  mode 0: every window by evaluateMargPrior on a
+// HostPool of host_threads threads, gradient J0^T e and e . e by the same sequential sums as the kernel; mode 1: one
+// MarginalizationPriorSet::set, then one evaluate per point.  Outputs per point, point after point: residuals (sum r), jacobians (sum of
+// r * sum(size), may be NULL), gradient (sum r, may be NULL), sq_norm (n_windows, may be NULL).  The points are evaluated reps + 1 times,
+// the first pass untimed; seconds[0] = the set (mode 1; 0 in mode 0), seconds[1] = the fastest evaluation of one point.
+// Without the device entry points in the build mode 1 computes nothing: -4 and "icg_marg_prior_set is not in this build".
+int icgh_backend_marg_factor(int mode, int n_windows, const int32_t *r, const int32_t *block_off, const int32_t *block_size,
+                             const int32_t *block_index, const double *x0, const double *J0, const double *e0, int n_points, const double *x,
+                             int host_threads, int reps, double *residuals, double *jacobians, double *gradient, double *sq_norm,
+                             double *seconds, char *err, int errlen) {
+    return guarded(err, errlen, [&] {
+        if (mode != 0 && mode != 1) {
+            set_err(err, errlen, "icgh_backend_marg_factor: mode is neither 0 (host) nor 1 (device)");
+            return -1;
+        }
+        if (mode == 1 && !MarginalizationPriorSet::available()) {
+            set_err(err, errlen, "icg_marg_prior_set is not in this build");
+            return -4;
+        }
+        if (n_windows <= 0 || n_points <= 0 || !r || !block_off || !block_size || !block_index || !x0 || !J0 || !e0 || !x || !residuals || !seconds) {
+            set_err(err, errlen, "icgh_backend_marg_factor: invalid argument");
+            return -1;
+        }
+        const size_t W = (size_t) n_windows;
+        vector<size_t> e_off(W + 1, 0), x_off(W + 1, 0), j_off(W + 1, 0), jac_off(W + 1, 0);
+        vector<int> size(block_size, block_size + block_off[W]), index(block_index, block_index + block_off[W]);
+        vector<const double *> x0_ptr((size_t) block_off[W]);
+        vector<MargPriorView> views(W);
+        for (size_t w = 0; w < W; w++) {
+            size_t xs = 0;
+            bool ok   = r[w] > 0 && block_off[w + 1] >= block_off[w] && (w > 0 || block_off[0] == 0);
+            for (int b = block_off[w]; ok && b < block_off[w + 1]; b++) {
+                ok = size[(size_t) b] > 0 && index[(size_t) b] >= 0 &&
+                     index[(size_t) b] + MarginalizationInfo::localSize(size[(size_t) b]) <= r[w];
+                x0_ptr[(size_t) b] = x0 + x_off[w] + xs;
+                xs += (size_t) size[(size_t) b];
+            }
+            if (!ok) {
+                set_err(err, errlen, ("icgh_backend_marg_factor: window " + std::to_string(w) + " is not a valid prior").c_str());
+                return -1;
+            }
+            MargPriorView &v = views[w];
+            v.r = r[w], v.n_blocks = block_off[w + 1] - block_off[w];
+            v.size = size.data() + block_off[w], v.index = index.data() + block_off[w], v.x0 = x0_ptr.data() + block_off[w];
+            v.J0 = J0 + j_off[w], v.e0 = e0 + e_off[w];
+            e_off[w + 1] = e_off[w] + (size_t) r[w], x_off[w + 1] = x_off[w] + xs;
+            j_off[w + 1] = j_off[w] + (size_t) r[w] * r[w], jac_off[w + 1] = jac_off[w] + (size_t) r[w] * xs;
+        }
+        const size_t R = e_off[W], X = x_off[W], NJ = jac_off[W];
+        double best = -1; // (over the points: each one evaluated reps + 1 times)
+        seconds[0] = seconds[1] = 0;
+        if (mode == 0) {
+            HostPool pool(host_threads < 1 ? 1 : host_threads);
+            for (int p = 0; p < n_points; p++) {
+                const double t = best_of(reps, [&](int) {
+                    pool.parallelFor(n_windows, [&](int wi) {
+                        const size_t w         = (size_t) wi;
+                        const MargPriorView &v = views[w];
+                        vector<const double *> params((size_t) v.n_blocks);
+                        vector<double *> jac((size_t) v.n_blocks, nullptr);
+                        size_t xs = 0;
+                        for (int b = 0; b < v.n_blocks; b++) {
+                            params[(size_t) b] = x + (size_t) p * X + x_off[w] + xs;
+                            if (jacobians) jac[(size_t) b] = jacobians + (size_t) p * NJ + jac_off[w] + (size_t) v.r * xs;
+                            xs += (size_t) v.size[b];
+                        }
+                        double *e = residuals + (size_t) p * R + e_off[w];
+                        evaluateMargPrior(v, params.data(), e, jacobians ? jac.data() : nullptr);
+                        if (gradient)
+                            for (int k = 0; k < v.r; k++) {
+                                double s = 0;
+                                for (int i = 0; i < v.r; i++) s += v.J0[(size_t) i * v.r + k] * e[i];
+                                gradient[(size_t) p * R + e_off[w] + (size_t) k] = s;
+                            }
+                        if (sq_norm) {
+                            double s = 0;
+                            for (int i = 0; i < v.r; i++) s += e[i] * e[i];
+                            sq_norm[(size_t) p * W + w] = s;
+                        }
+                    });
+                    return true;
+                });
+                if (best < 0 || t < best) best = t;
+            }
+            seconds[1] = best;
+            return 0;
+        }
+        TempCtx T(0);
+        std::string e;
+        MarginalizationPriorSet set;
+        const double t_set = best_of(0, [&](int) { return set.set(T.ctx, views, &e); });
+        if (t_set < 0) {
+            set_err(err, errlen, e.c_str());
+            return -2;
+        }
+        seconds[0] = t_set;
+        vector<vector<const double *>> params(W);
+        vector<const double *const *> plist(W);
+        for (int p = 0; p < n_points; p++) {
+            const double t = best_of(reps, [&](int) {
+                for (size_t w = 0; w < W; w++) {
+                    params[w].resize((size_t) views[w].n_blocks);
+                    size_t xs = 0;
+                    for (int b = 0; b < views[w].n_blocks; b++) params[w][(size_t) b] = x + (size_t) p * X + x_off[w] + xs, xs += (size_t) views[w].size[b];
+                    plist[w] = params[w].data();
+                }
+                return set.evaluate(plist, residuals + (size_t) p * R, jacobians ? jacobians + (size_t) p * NJ : nullptr,
+                                    gradient ? gradient + (size_t) p * R : nullptr, sq_norm ? sq_norm + (size_t) p * W : nullptr, &e);
+            });
+            if (t < 0) {
+                set_err(err, errlen, e.c_str());
+                return -3;
+            }
+            if (best < 0 || t < best) best = t;
+        }
+        seconds[1] = best;
+        return 0;
+    });
+}
+
+} // extern "C"

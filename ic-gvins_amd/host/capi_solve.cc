@@ -1,0 +1,303 @@
+// C entry points of libicgvins_host.so: the window optimization (WindowSolver / WindowSolverBatch) for tests and bench.py.
+#include <atomic>
+#include <chrono>
+#include <cstdlib>
+#include <memory>
+#include <thread>
+
+#include "factors.h"
+#include "solver_hip.h"
+#include "solver_batch_hip.h"
+#include "capi_util.h"
+
+using namespace icg;
+
+extern "C" {
+
+// ---- f1: the window optimization flow of GVINS::gvinsOptimization (ic_gvins.cc:1130-1239) on WindowSolver -----------------
+// Reprojection factors from flat arrays (as icgh_backend_reproj) + one PosePriorFactor per pose (weight prior_weight, target
+// prior_poses: fixes the gauge like the reference's marginalization prior / GNSS factors do).  Two solves with the chi-square
+// culling pass in between (chi2 <= 0: one solve of iters1 iterations).  All parameter arrays are updated in place.
+// summary10: initial cost, cost after solve 1, final cost, successful steps 1, unsuccessful 1, successful 2, unsuccessful 2, removed,
+// ms spent in solve + culling, ms spent building the problem (context, factor upload)
+int icgh_backend_solve(int n, const double *obs_soa, const int32_t *idx_i, const int32_t *idx_j, const int32_t *idx_lm, int n_poses,
+                       double *poses, double *ext, int n_lm, double *invdepth, double *td, const double *prior_poses, double prior_weight,
+                       double huber, int ext_constant, int td_constant, int iters1, int iters2, double chi2, double *summary8,
+                       uint8_t *active_out, char *err, int errlen) {
+    return guarded(err, errlen, [&] {
+        auto t_begin = std::chrono::steady_clock::now();
+        vector<std::unique_ptr<ReprojectionFactor>> factors;
+        ReprojectionBatch batch(0);
+        for (int k = 0; k < n; k++) {
+            factors.push_back(reproj_factor_from_soa(obs_soa, n, k));
+            batch.add(factors.back().get(), poses + 7 * (size_t) idx_i[k], poses + 7 * (size_t) idx_j[k], ext, invdepth + idx_lm[k], td);
+        }
+        batch.finalize();
+        auto t_built = std::chrono::steady_clock::now();
+        WindowSolver solver(&batch, huber);
+        for (int k = 0; k < n_poses; k++) solver.addParameterBlock(poses + 7 * (size_t) k, 7, true);
+        solver.addParameterBlock(ext, 7, true);
+        for (int l = 0; l < n_lm; l++) solver.addParameterBlock(invdepth + l, 1);
+        solver.addParameterBlock(td, 1);
+        if (ext_constant) solver.setParameterBlockConstant(ext);
+        if (td_constant) solver.setParameterBlockConstant(td);
+        for (int k = 0; k < n_poses; k++)
+            solver.addResidualBlock(std::make_shared<PosePriorFactor>(prior_poses + 7 * (size_t) k, prior_weight), nullptr,
+                                    {poses + 7 * (size_t) k});
+        WindowSolver::Options opt;
+        WindowSolver::Summary s1, s2;
+        opt.max_num_iterations = iters1;
+        if (!solver.solve(opt, &s1)) {
+            set_err(err, errlen, solver.error().c_str());
+            return -2;
+        }
+        summary8[0] = s1.initial_cost, summary8[1] = s1.final_cost, summary8[2] = s1.final_cost;
+        summary8[3] = s1.num_successful_steps, summary8[4] = s1.num_unsuccessful_steps;
+        summary8[5] = summary8[6] = summary8[7] = 0;
+        if (chi2 > 0) {
+            int removed = solver.removeReprojectionFactorsByChi2(chi2);
+            if (removed < 0) {
+                set_err(err, errlen, solver.error().c_str());
+                return -3;
+            }
+            opt.max_num_iterations = iters2;
+            if (!solver.solve(opt, &s2)) {
+                set_err(err, errlen, solver.error().c_str());
+                return -4;
+            }
+            summary8[2] = s2.final_cost, summary8[5] = s2.num_successful_steps, summary8[6] = s2.num_unsuccessful_steps, summary8[7] = removed;
+        }
+        summary8[8] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_built).count();
+        summary8[9] = std::chrono::duration<double, std::milli>(t_built - t_begin).count();
+        if (active_out) memcpy(active_out, solver.activeReprojectionFactors().data(), (size_t) n);
+        if (getenv("ICG_SOLVER_DEBUG")) fprintf(stderr, "%s\n%s\n", s1.BriefReport().c_str(), s2.BriefReport().c_str());
+        return 0;
+    });
+}
+
+// icgh_backend_solve for W windows at once on WindowSolverBatch (lock-step LM, one launch per phase for all windows).  Arrays are
+// concatenated window-major: window w owns factors [fac_off[w], fac_off[w+1]) (obs_soa is 15 x n_total, idx_* LOCAL to the window),
+// poses [pose_off[w], ..), inverse depths [lm_off[w], ..); ext is W x 7, td has W entries.  summary8 is W x 8 as in icgh_backend_solve.
+// Returns the wall time of the two solves + culling in ms through *solve_ms.
+int icgh_backend_solve_batch(int W, const int32_t *fac_off, const int32_t *pose_off, const int32_t *lm_off, const double *obs_soa, const int32_t *idx_i,
+                             const int32_t *idx_j, const int32_t *idx_lm, double *poses, double *ext, double *invdepth, double *td,
+                             const double *prior_poses, double prior_weight, double huber, int ext_constant, int td_constant, int iters1, int iters2,
+                             double chi2, double *summary8, double *solve_ms, char *err, int errlen) {
+    return guarded(err, errlen, [&] {
+        const int n = fac_off[W];
+        vector<std::unique_ptr<ReprojectionFactor>> factors;
+        WindowSolverBatch solver(0, huber);
+        for (int w = 0; w < W; w++) {
+            const int ww = solver.addWindow();
+            double *P = poses + 7 * (size_t) pose_off[w], *E = ext + 7 * (size_t) w, *D = invdepth + lm_off[w], *TD = td + w;
+            const int K = pose_off[w + 1] - pose_off[w], L = lm_off[w + 1] - lm_off[w];
+            for (int k = 0; k < K; k++) solver.addParameterBlock(ww, P + 7 * (size_t) k, 7, true);
+            solver.addParameterBlock(ww, E, 7, true);
+            for (int l = 0; l < L; l++) solver.addParameterBlock(ww, D + l, 1);
+            solver.addParameterBlock(ww, TD, 1);
+            if (ext_constant) solver.setParameterBlockConstant(ww, E);
+            if (td_constant) solver.setParameterBlockConstant(ww, TD);
+            for (int f = fac_off[w]; f < fac_off[w + 1]; f++) {
+                factors.push_back(reproj_factor_from_soa(obs_soa, n, f));
+                solver.addReprojectionFactor(ww, factors.back().get(), P + 7 * (size_t) idx_i[f], P + 7 * (size_t) idx_j[f], E, D + idx_lm[f], TD);
+            }
+            for (int k = 0; k < K; k++)
+                solver.addResidualBlock(ww, std::make_shared<PosePriorFactor>(prior_poses + 7 * ((size_t) pose_off[w] + k), prior_weight), nullptr,
+                                        {P + 7 * (size_t) k});
+        }
+        if (!solver.prepare()) {
+            set_err(err, errlen, solver.error().c_str());
+            return -5;
+        }
+        auto t0 = std::chrono::steady_clock::now();
+        WindowSolverBatch::Options opt;
+        vector<WindowSolverBatch::Summary> s1, s2;
+        opt.max_num_iterations = iters1;
+        if (!solver.solve(opt, &s1)) {
+            set_err(err, errlen, solver.error().c_str());
+            return -2;
+        }
+        vector<int> removed((size_t) W, 0);
+        if (chi2 > 0) {
+            removed                = solver.removeReprojectionFactorsByChi2(chi2);
+            opt.max_num_iterations = iters2;
+            if (!solver.solve(opt, &s2)) {
+                set_err(err, errlen, solver.error().c_str());
+                return -4;
+            }
+        }
+        if (solve_ms) *solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        for (int w = 0; w < W; w++) {
+            double *o = summary8 + 8 * (size_t) w;
+            o[0] = s1[(size_t) w].initial_cost, o[1] = s1[(size_t) w].final_cost, o[2] = s1[(size_t) w].final_cost;
+            o[3] = s1[(size_t) w].num_successful_steps, o[4] = s1[(size_t) w].num_unsuccessful_steps, o[5] = o[6] = o[7] = 0;
+            if (chi2 > 0)
+                o[2] = s2[(size_t) w].final_cost, o[5] = s2[(size_t) w].num_successful_steps, o[6] = s2[(size_t) w].num_unsuccessful_steps,
+                o[7] = removed[(size_t) w];
+        }
+        return 0;
+    });
+}
+
+// Aggregate solve throughput with many windows in flight: `threads` host threads, each with its own ReprojectionBatch (own icg_ctx
+// and HIP stream, like the stream groups of the front-end) and its own copy of the problem, each solving it `repeat` times from
+// the same start (problem construction outside the timed region).  Returns the wall time in seconds for threads x repeat solves,
+// < 0 on error.  Same flow as icgh_backend_solve (two solves with the chi-square pass).
+double icgh_backend_solve_throughput(int n, const double *obs_soa, const int32_t *idx_i, const int32_t *idx_j, const int32_t *idx_lm, int n_poses,
+                                     const double *poses, const double *ext, int n_lm, const double *invdepth, double td,
+                                     const double *prior_poses, double prior_weight, double huber, int iters1, int iters2, double chi2, int threads,
+                                     int repeat, char *err, int errlen) {
+    return guarded(err, errlen, -1.0, [&] {
+        struct Job {
+            vector<double> P, E, D;
+            double TD;
+            vector<std::unique_ptr<ReprojectionFactor>> factors;
+            std::unique_ptr<ReprojectionBatch> batch;
+        };
+        vector<std::unique_ptr<Job>> jobs;
+        for (int t = 0; t < threads; t++) {
+            std::unique_ptr<Job> J(new Job);
+            J->P.assign(poses, poses + 7 * (size_t) n_poses), J->E.assign(ext, ext + 7), J->D.assign(invdepth, invdepth + n_lm), J->TD = td;
+            J->batch.reset(new ReprojectionBatch(0));
+            if (threads > 4) J->batch->setWaitMode(ICG_WAIT_POLL, 5); // more solvers than spare host cores: do not spin on completion
+            for (int k = 0; k < n; k++) {
+                J->factors.push_back(reproj_factor_from_soa(obs_soa, n, k));
+                J->batch->add(J->factors.back().get(), &J->P[7 * (size_t) idx_i[k]], &J->P[7 * (size_t) idx_j[k]], J->E.data(), &J->D[(size_t) idx_lm[k]],
+                              &J->TD);
+            }
+            J->batch->finalize();
+            jobs.push_back(std::move(J));
+        }
+        std::atomic<int> failed{0};
+        auto work = [&](int t) {
+            Job &J = *jobs[(size_t) t];
+            for (int r = 0; r < repeat; r++) {
+                J.P.assign(poses, poses + 7 * (size_t) n_poses), J.E.assign(ext, ext + 7), J.D.assign(invdepth, invdepth + n_lm), J.TD = td;
+                WindowSolver solver(J.batch.get(), huber);
+                for (int k = 0; k < n_poses; k++) solver.addParameterBlock(&J.P[7 * (size_t) k], 7, true);
+                solver.addParameterBlock(J.E.data(), 7, true);
+                for (int l = 0; l < n_lm; l++) solver.addParameterBlock(&J.D[(size_t) l], 1);
+                solver.addParameterBlock(&J.TD, 1);
+                for (int k = 0; k < n_poses; k++)
+                    solver.addResidualBlock(std::make_shared<PosePriorFactor>(prior_poses + 7 * (size_t) k, prior_weight), nullptr, {&J.P[7 * (size_t) k]});
+                WindowSolver::Options opt;
+                WindowSolver::Summary s1;
+                opt.max_num_iterations = iters1;
+                if (!solver.solve(opt, &s1)) failed++;
+                if (chi2 > 0) {
+                    solver.removeReprojectionFactorsByChi2(chi2);
+                    opt.max_num_iterations = iters2;
+                    if (!solver.solve(opt, &s1)) failed++;
+                }
+            }
+        };
+        auto t0 = std::chrono::steady_clock::now();
+        vector<std::thread> th;
+        for (int t = 1; t < threads; t++) th.emplace_back(work, t);
+        work(0);
+        for (auto &x : th) x.join();
+        double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (failed.load()) {
+            set_err(err, errlen, "a solve failed");
+            return -2.0;
+        }
+        return sec;
+    });
+}
+
+} // extern "C"
+
+namespace {
+// r = w (x - x0) on one 9-vector block (velocity, gyroscope bias, accelerometer bias): stands in for the part of the
+// marginalization prior that anchors the first state's velocity and biases
+class MixPriorFactor : public ceres::SizedCostFunction<9, 9> {
+public:
+    MixPriorFactor(const double *x0, double weight) : w_(weight) { memcpy(x0_, x0, sizeof x0_); }
+    bool Evaluate(const double *const *parameters, double *residuals, double **jacobians) const override {
+        for (int k = 0; k < 9; k++) residuals[k] = w_ * (parameters[0][k] - x0_[k]);
+        if (jacobians && jacobians[0]) {
+            memset(jacobians[0], 0, sizeof(double) * 81);
+            for (int k = 0; k < 9; k++) jacobians[0][k * 9 + k] = w_;
+        }
+        return true;
+    }
+
+private:
+    double x0_[9], w_;
+};
+} // namespace
+
+extern "C" {
+
+// f1 with the factor mix of the real window: K preintegration factors (device P1 + host P2) between K+1 states, reprojection
+// factors on the same pose blocks (device), a pose prior and a velocity/bias prior on state 0 (what the marginalization prior
+// provides in the real window).  states: (K+1) x 16 (p3, q4 xyzw, v3, bg3, ba3) in/out;
+// imu rows of 8, interval k owns rows [offsets[k], offsets[k+1]).  summary4: initial cost, final cost, successful, unsuccessful steps.
+int icgh_backend_solve_vio(int n_intervals, const int32_t *offsets, const double *imu, const double *params9, double *states16, int n,
+                           const double *obs_soa, const int32_t *idx_i, const int32_t *idx_j, const int32_t *idx_lm, double *ext, int n_lm,
+                           double *invdepth, double *td, const double *prior_pose0, const double *prior_mix0, double prior_weight, double huber,
+                           int iters, double *summary4, char *err, int errlen) {
+    return guarded(err, errlen, [&] {
+        const int K = n_intervals + 1;
+        vector<double> pose((size_t) K * 7), mix((size_t) K * 9);
+        for (int k = 0; k < K; k++) {
+            memcpy(&pose[7 * (size_t) k], states16 + 16 * (size_t) k, sizeof(double) * 7);
+            memcpy(&mix[9 * (size_t) k], states16 + 16 * (size_t) k + 7, sizeof(double) * 9);
+        }
+        vector<std::unique_ptr<ReprojectionFactor>> factors;
+        ReprojectionBatch batch(0);
+        for (int f = 0; f < n; f++) {
+            factors.push_back(reproj_factor_from_soa(obs_soa, n, f));
+            batch.add(factors.back().get(), &pose[7 * (size_t) idx_i[f]], &pose[7 * (size_t) idx_j[f]], ext, invdepth + idx_lm[f], td);
+        }
+        batch.finalize();
+        // preintegration of every interval from its start state: one icg_preint_batch launch on a context of its own
+        auto P = preint_params(params9);
+        TempCtx T(0);
+        vector<std::shared_ptr<Preintegration>> pre;
+        vector<Preintegration *> raw;
+        for (int k = 0; k < n_intervals; k++) {
+            auto p = std::make_shared<Preintegration>(P, ins_imu(imu + 8 * (size_t) offsets[k]), preint_state(states16 + 16 * (size_t) k),
+                                                      Preintegration::NORMAL);
+            for (int row = offsets[k] + 1; row < offsets[k + 1]; row++) p->addNewImu(ins_imu(imu + 8 * (size_t) row));
+            pre.push_back(p);
+            raw.push_back(p.get());
+        }
+        std::string e;
+        if (!Preintegration::integrateBatch(T.ctx, raw, &e)) {
+            set_err(err, errlen, e.c_str());
+            return -2;
+        }
+        WindowSolver solver(&batch, huber);
+        for (int k = 0; k < K; k++) {
+            solver.addParameterBlock(&pose[7 * (size_t) k], 7, true);
+            solver.addParameterBlock(&mix[9 * (size_t) k], 9);
+        }
+        solver.addParameterBlock(ext, 7, true);
+        for (int l = 0; l < n_lm; l++) solver.addParameterBlock(invdepth + l, 1);
+        solver.addParameterBlock(td, 1);
+        solver.setParameterBlockConstant(ext); // estimated off-line in the default configuration (optimize_estimate_extrinsic: false)
+        solver.setParameterBlockConstant(td);
+        for (int k = 0; k < n_intervals; k++)
+            solver.addResidualBlock(std::make_shared<PreintegrationFactor>(pre[(size_t) k]), nullptr,
+                                    {&pose[7 * (size_t) k], &mix[9 * (size_t) k], &pose[7 * (size_t) (k + 1)], &mix[9 * (size_t) (k + 1)]});
+        solver.addResidualBlock(std::make_shared<PosePriorFactor>(prior_pose0, prior_weight), nullptr, {&pose[0]});
+        solver.addResidualBlock(std::make_shared<MixPriorFactor>(prior_mix0, prior_weight), nullptr, {&mix[0]});
+        WindowSolver::Options opt;
+        WindowSolver::Summary sum;
+        opt.max_num_iterations = iters;
+        if (!solver.solve(opt, &sum)) {
+            set_err(err, errlen, solver.error().c_str());
+            return -3;
+        }
+        summary4[0] = sum.initial_cost, summary4[1] = sum.final_cost, summary4[2] = sum.num_successful_steps, summary4[3] = sum.num_unsuccessful_steps;
+        for (int k = 0; k < K; k++) {
+            memcpy(states16 + 16 * (size_t) k, &pose[7 * (size_t) k], sizeof(double) * 7);
+            memcpy(states16 + 16 * (size_t) k + 7, &mix[9 * (size_t) k], sizeof(double) * 9);
+        }
+        if (getenv("ICG_SOLVER_DEBUG")) fprintf(stderr, "%s\n", sum.BriefReport().c_str());
+        return 0;
+    });
+}
+
+} // extern "C"

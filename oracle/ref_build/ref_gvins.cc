@@ -35,7 +35,7 @@ static Frame::Ptr ref_make_frame(double stamp, const uint8_t *gray, int w, int h
 // ---- f1 cross-check: one sliding window of reprojection factors + pose priors through the REFERENCE's own factor code
 // (factors/reprojection_factor.h, factors/pose_parameterization.h, preintegration/imu_pose_prior_factor.h, ceres::HuberLoss) and the shim's
 // Levenberg-Marquardt (shim/ceres/problem_shim.h), following GVINS::gvinsOptimization's two solves with the chi-square removal in between
-// (ic_gvins.cc:1178-1221, 1269-1297).  Same argument layout as icgh_backend_solve (ic-gvins_amd/host/capi.cc).
+// (ic_gvins.cc:1178-1221, 1269-1297).  Same argument layout as icgh_backend_solve (ic-gvins_amd/host/capi_solve.cc).
 extern "C" int ref_window_solve(int n, const double *obs_soa, const int32_t *idx_i, const int32_t *idx_j, const int32_t *idx_lm, int n_poses, double *poses,
                                 double *ext, int n_lm, double *invdepth, double *td, const double *prior_poses, double prior_weight, double huber,
                                 int ext_constant, int td_constant, int iters1, int iters2, double chi2, double *summary8, uint8_t *active_out) {

@@ -1,7 +1,7 @@
 // ORACLE / TEST INFRASTRUCTURE ONLY — runs the REFERENCE's own marginalization pipeline (ResidualBlockInfo,
 // MarginalizationInfo, MarginalizationFactor and ReprojectionFactor: /root/reference/ic_gvins/ic_gvins/factors/*.h, compiled
 // unmodified from where they lie) behind the SAME C entry point the product's host layer exposes for its tests
-// (icgh_backend_marginalize, ic-gvins_amd/host/capi.cc), so tests/backend_utils.py can drive either.
+// (icgh_backend_marginalize, ic-gvins_amd/host/capi_marg.cc), so tests/backend_utils.py can drive either.
 // Linear algebra comes from the Eigen-interface shim in shim/ (NOT real Eigen — stated in DESIGN.md).
 // The reference keeps H0/Hp/bp private; Hp and bp are therefore returned as J0^T J0 and -J0^T e0 (identical up to the
 // eigenvalues <= 1e-8 the reference truncates in linearization()).
@@ -19,7 +19,7 @@ using std::vector;
 #include "factors/residual_block_info.h"
 
 namespace {
-// the generic host factor of capi.cc's scenario: residual = w * [p - p0 ; 2 vec(q0^-1 q)] on one pose block
+// the generic host factor of the scenario of capi_marg.cc (PosePriorFactor, capi_util.h): residual = w * [p - p0 ; 2 vec(q0^-1 q)] on one pose block
 class PosePriorFactor : public ceres::SizedCostFunction<6, 7> {
 public:
     PosePriorFactor(const double *pose0, double weight) : w_(weight) { memcpy(x0_, pose0, sizeof x0_); }
@@ -38,7 +38,7 @@ public:
             memset(jacobians[0], 0, sizeof(double) * 42);
             for (int k = 0; k < 3; k++) {
                 jacobians[0][k * 7 + k]           = w_;
-                jacobians[0][(3 + k) * 7 + 3 + k] = w_ * dq[3]; // same scaffolding factor as ic-gvins_amd/host/capi.cc
+                jacobians[0][(3 + k) * 7 + 3 + k] = w_ * dq[3]; // same scaffolding factor as ic-gvins_amd/host/capi_util.h
             }
         }
         return true;

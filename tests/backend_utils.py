@@ -1,4 +1,4 @@
-"""ctypes drivers for the back-end entry points of the host layer (host/capi.cc: icgh_backend_*), plus the shared test
+"""ctypes drivers for the back-end entry points of the host layer (host/capi_*.cc: icgh_backend_*), plus the shared test
 bodies that are run twice: on the oracle-backed host library (CPU, not gpu) and on the product library (gpu)."""
 import ctypes as C
 
@@ -67,13 +67,13 @@ def backend_marginalize(lib, P, huber=1.0, prior_weight=100.0, x_eval=None):
 
 
 def oracle_marginalized_system(oracle, P, w, out, huber=1.0, prior_weight=100.0, scalar_prior=None):
-    """(Hp, bp) of the marginalization scenario of capi.cc (reprojection factors + PosePriorFactor on pose 0 [+ a ScalarPriorFactor
+    """(Hp, bp) of the marginalization scenario of capi_marg.cc (reprojection factors + PosePriorFactor on pose 0 [+ a ScalarPriorFactor
     (landmark, x0, weight)]) at the parameter values `w`, from the ORACLE: orc_reproj per factor, orc_marg's constructEquation and Schur
     complement (factors/marginalization_info.h:170-230), permuted from this file's column layout to the library's retained order
     (`out`: ids / index / size / m of a library run of the same structure)."""
     r_, J_ = oracle.reproj_eval(P["obs"], P["ii"], P["jj"], P["ll"], w["poses"], w["ext"], w["invdepth"], w["td"], huber=huber)
     H, b = oracle.reproj_accumulate_normal(r_, J_, P["ii"], P["jj"], P["ll"], P["col_pose"], P["col_ext"], P["col_lm"], P["col_td"], P["local_size"])
-    # PosePriorFactor of capi.cc: residual w*[dp ; 2 vec(dq)], prior translated by +0.01 in x -> r = (-w*0.01, 0, ...)
+    # PosePriorFactor of capi_util.h: residual w*[dp ; 2 vec(dq)], prior translated by +0.01 in x -> r = (-w*0.01, 0, ...)
     Jp = np.zeros((6, 6))
     Jp[:3, :3] = prior_weight * np.eye(3)
     Jp[3:, 3:] = prior_weight * np.eye(3)
@@ -82,7 +82,7 @@ def oracle_marginalized_system(oracle, P, w, out, huber=1.0, prior_weight=100.0,
     c0 = P["col_pose"][0]
     H[c0:c0 + 6, c0:c0 + 6] += Jp.T @ Jp
     b[c0:c0 + 6] -= Jp.T @ rp
-    if scalar_prior is not None:  # ScalarPriorFactor of capi.cc: r = weight (x - x0)
+    if scalar_prior is not None:  # ScalarPriorFactor of capi_util.h: r = weight (x - x0)
         l, x0, wgt = scalar_prior
         cl = P["col_lm"][l]
         H[cl, cl] += wgt * wgt
@@ -107,8 +107,8 @@ def oracle_marginalized_system(oracle, P, w, out, huber=1.0, prior_weight=100.0,
 
 
 def batch_window_parameters(P, n_windows, jitter=1e-3):
-    """the parameter values icgh_backend_marginalize_batch (capi.cc) gives its n_windows copies of problem P: window 0 as it is, every
-    further window with positions moved by jitter * u and inverse depths scaled by 1 + jitter * u, u from the 64-bit LCG of capi.cc"""
+    """the parameter values icgh_backend_marginalize_batch (capi_marg.cc) gives its n_windows copies of problem P: window 0 as it is, every
+    further window with positions moved by jitter * u and inverse depths scaled by 1 + jitter * u, u from the 64-bit LCG of capi_marg.cc"""
     state, mask = [0x9E3779B97F4A7C15], (1 << 64) - 1
 
     def rnd():
@@ -269,7 +269,7 @@ def check_marginalization_golden(lib, path):
 
 
 def backend_marginalize_batch(lib, P, n_windows, mode, dense_window=-1, jitter=1e-3, huber=1.0, prior_weight=100.0, host_threads=0, reps=1):
-    """icgh_backend_marginalize_batch (capi.cc): the marginalizations of n_windows jittered copies of problem P, mode 0 = one
+    """icgh_backend_marginalize_batch (capi_marg.cc): the marginalizations of n_windows jittered copies of problem P, mode 0 = one
     MarginalizationBatch, mode 1 = one MarginalizationInfo::marginalization() after the other; reps: the set is marginalized that many times on
     the same batch object (seconds = the fastest repetition, outputs of the last)."""
     w = P["w"]

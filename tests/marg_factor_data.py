@@ -9,7 +9,7 @@ import reproj_data as rd
 
 C2_SIZES = [7, 9] * 9 + [7, 1]      # the estimator's window: 9 x (pose, mix) + extrinsic + td, r = 142
 C4_SIZES = [7, 9] * 14 + [7, 1]     # r = 217
-SCENARIO_SIZES = [7] * 5 + [1] * 40 + [7, 1]  # the shape of capi.cc's marginalization scenario: poses, inverse depths, extrinsic, td (r = 77)
+SCENARIO_SIZES = [7] * 5 + [1] * 40 + [7, 1]  # the shape of capi_marg.cc's marginalization scenario: poses, inverse depths, extrinsic, td (r = 77)
 R512_SIZES = [7] * 80 + [1] * 32    # r = 512
 
 

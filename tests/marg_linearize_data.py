@@ -58,7 +58,7 @@ def zero_row_system(seed, P=50, m=8, where=None, name="zero_row"):
 
 
 def golden_system(oracle):
-    """the full normal equations of the scenario behind tests/golden/marg_ref_golden.npz (capi.cc icgh_backend_marginalize: reprojection
+    """the full normal equations of the scenario behind tests/golden/marg_ref_golden.npz (capi_marg.cc icgh_backend_marginalize: reprojection
     factors with Huber 1.0 + the PosePriorFactor of weight 100 on pose 0), assembled by the oracle as backend_utils.oracle_marginalized_system
     does; m = pose 0 + its landmarks.  Returns (system, problem)."""
     import backend_utils as bu

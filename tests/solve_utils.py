@@ -91,7 +91,7 @@ def host_solve_throughput(lib, P, threads, repeat, prior_weight=30.0, huber=1.0,
 
 # ---- independent dense LM -------------------------------------------------------------------------------------------------------
 def _prior_eval(x, x0, w):
-    """PosePriorFactor of host/capi.cc: r = w [p - p0; 2 vec(q0^-1 q)], J (6x6 tangent) = w diag(1,1,1, dq_w, dq_w, dq_w)"""
+    """PosePriorFactor of host/capi_util.h: r = w [p - p0; 2 vec(q0^-1 q)], J (6x6 tangent) = w diag(1,1,1, dq_w, dq_w, dq_w)"""
     n2 = float(x0[3:] @ x0[3:])
     ax, ay, az, aw = -x0[3] / n2, -x0[4] / n2, -x0[5] / n2, x0[6] / n2
     bx, by, bz, bw = x[3:]

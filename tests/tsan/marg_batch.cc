@@ -1,6 +1,6 @@
 // Sanitizer driver 7 (tests/tsan/run.sh): MarginalizationBatch (host/marg_batch.h) — 12 windows, one of them on the dense path, marginalized three
 // times on one batch object with the per-window phases on 4 pool threads — through the C entry point the tests use
-// (icgh_backend_marginalize_batch, capi.cc), on the CPU backend of the C ABI.  Checks the result against the one-by-one mode.
+// (icgh_backend_marginalize_batch, capi_marg.cc), on the CPU backend of the C ABI.  Checks the result against the one-by-one mode.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
