@@ -21,6 +21,7 @@ EXPORTS = [
     "icg_ins_mechanize_batch", "icg_ins_camera_pose_batch", "icg_reproj_schur", "icg_reproj_backsub", "icg_reproj_cost", "icg_reproj_landmark_diag",
     "icg_reproj_error_batch", "icg_reproj_set_windows", "icg_reproj_eval_windows", "icg_reproj_schur_windows",
     "icg_reproj_schur_windows_view", "icg_reproj_reserve_windows", "icg_reproj_eval_resident_view", "icg_reproj_backsub_windows", "icg_reproj_cost_windows", "icg_reproj_fetch_residuals", "icg_reproj_chi2_cull",
+    "icg_reproj_landmark_diag_windows",
     "icg_marg_prior_set", "icg_marg_prior_evaluate", "icg_marg_linearize_batch",
 ]
 
@@ -366,6 +367,26 @@ class Context:
         self._ck(self.lib.icg_reproj_cost(self.h, _p(act), _p(cost)), "icg_reproj_cost")
         return float(cost[0])
 
+    def reproj_landmark_diag(self, n_lm):
+        """icg_reproj_landmark_diag: h_ll of every landmark from the system the last icg_reproj_schur left resident"""
+        h = np.zeros(n_lm)
+        self._ck(self.lib.icg_reproj_landmark_diag(self.h, _p(h)), "icg_reproj_landmark_diag")
+        return h
+
+    def reproj_chi2_cull(self, chi2, active):
+        """icg_reproj_chi2_cull: a copy of `active` with every factor whose r0^2 + r1^2 exceeds chi2 cleared"""
+        act = np.array(active, dtype=np.uint8, order="C").reshape(-1)
+        if act.shape[0] != self._nfac:
+            raise IcgError(f"reproj_chi2_cull: the mask has {act.shape[0]} entries, the resident set {self._nfac} factors")
+        self._ck(self.lib.icg_reproj_chi2_cull(self.h, C.c_double(chi2), _p(act)), "icg_reproj_chi2_cull")
+        return act
+
+    def reproj_fetch_residuals(self):
+        """icg_reproj_fetch_residuals: the resident residuals of the last evaluation (n x 2)"""
+        r = np.zeros((self._nfac, 2))
+        self._ck(self.lib.icg_reproj_fetch_residuals(self.h, _p(r)), "icg_reproj_fetch_residuals")
+        return r
+
     # ---- f1, many windows per launch
     def reproj_set_windows(self, fac_off, lm_off):
         fac_off, lm_off = _i32(fac_off), _i32(lm_off)
@@ -410,6 +431,12 @@ class Context:
         out, terms = np.zeros(n_lm), np.zeros((self._nwin, 2))
         self._ck(self.lib.icg_reproj_backsub_windows(self.h, int(P), _p(_f64(delta_c)), _p(out), _p(terms)), "icg_reproj_backsub_windows")
         return out, terms
+
+    def reproj_landmark_diag_windows(self, n_lm):
+        """icg_reproj_landmark_diag_windows: h_ll of every landmark of the partition, in its global landmark order"""
+        h = np.zeros(n_lm)
+        self._ck(self.lib.icg_reproj_landmark_diag_windows(self.h, _p(h)), "icg_reproj_landmark_diag_windows")
+        return h
 
     def reproj_cost_windows(self, active=None):
         cost = np.zeros(self._nwin)

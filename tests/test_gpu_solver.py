@@ -1,7 +1,8 @@
 """GPU parity for SURVEY.md §8 row f1: the device-side landmark elimination (k_reproj_normal in the Schur layout,
 k_schur_reduce, k_schur_backsub, k_reproj_cost) and icg::WindowSolver on the HIP library, against the same independent numpy
-restatements as the CPU suite (dense elimination 1e-9, dense LM optimum 1e-7).  FP64 atomics make the assembly order free, so
-the comparison is by tolerance, not by bits."""
+restatements as the CPU suite (dense elimination 1e-9, dense LM optimum 1e-7).  The assembly is atomic-free and fixed-order; the
+comparison here is by tolerance because the references are numpy solves (test_gpu_schur_edges.py compares per cell and, device
+against device, bit for bit)."""
 import ctypes as C
 
 import numpy as np
