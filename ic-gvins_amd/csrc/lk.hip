@@ -27,6 +27,11 @@
 //     needs no division (threshold on the numerator) and the square root no range scaling; the verdict on a point (border, forward-backward
 //     distance, undistortion: FP64 that every lane of the wave computed alike) is k_lk_finish's, a thread per point.
 //     6.3 k vector instructions per tracked point (7.1 k in rounds 4-5), 93 VGPRs, no scratch, 5 waves per SIMD.
+//   * (round 7) the level set-up of a window whose 22x22 support lies inside the level differentiates the BLENDED patch: the Q14 blend and the
+//     Scharr stencil are integer linear maps and the descale is the only rounding, so the wave blends the 23x23 grid once (B, 32 bits, through
+//     LDS: two v_perm + two v_dot2 per position) and every lane runs a separable 32-bit Scharr (v_mad_i32_i24) over its 3x9 piece of B — the
+//     same bits as blending Ix, Iy and I separately (tests/test_lk_blend_first_identity.py pins the algebra).  Windows over a border keep the
+//     packed 16-bit form above, where the derivative plane is masked to zero outside the image.
 // Algorithmic HBM bytes per point and direction: 4 levels x (24^2 + 22^2) B; everything else is
 // LDS/VGPR traffic.
 #include <cfloat>
@@ -41,6 +46,8 @@ using namespace icgd;
 #define LK_JT 32   // J tile side
 #define LK_JS 36   // J tile row stride in bytes (9 dwords: 3 aligned dwords cover any 8-byte run)
 #define LK_JM 5    // J tile margin around the 22x22 support
+#define LK_BW 28   // B plane row stride in dwords (23 columns; 16-byte rows for the four-dword stores of the blend)
+#define LK_BH 26   // B plane rows: 23 blended rows + 3 rows of zeros that lane 63 differentiates (it owns no pixels)
 #define LK_MAX_ITERS 30
 #ifndef LK_WAVES_PER_EU
 #define LK_WAVES_PER_EU 5 // second __launch_bounds__ argument of k_lk_track_fb (the resource remarks of the build are quoted in DESIGN.md section 4)
@@ -49,6 +56,7 @@ using namespace icgd;
 struct lk_smem {
     unsigned int I[LK_IT * LK_IS / 4];
     unsigned int J[LK_JT * LK_JS / 4 + 1];
+    int B[LK_BH * LK_BW] __attribute__((aligned(16))); // the unrounded Q14 blend of the I tile (+ 256), interior windows only
 };
 
 // Exact wave-wide integer sums.  The per-lane partials are bounded (see the kernel comment), so the first butterfly
@@ -291,6 +299,18 @@ __device__ __forceinline__ int dot2_zero(unsigned int a, unsigned int b) {
     asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(d) : "v"(a), "v"(b));
     return d;
 }
+// a * 12 + c and a * 40 + c on a signed 24-bit a (v_mad_i32_i24), the accumulator a register or wave-uniform: the Scharr weights x 4 of the
+// 32-bit stencil.  (Left to the compiler, two chained multiply-adds become two multiplications and a v_add3: three half-rate issues for two.)
+__device__ __forceinline__ int mad24_12(int a, int c) {
+    int d;
+    asm("v_mad_i32_i24 %0, %1, 12, %2" : "=v"(d) : "v"(a), "v"(c));
+    return d;
+}
+__device__ __forceinline__ int mad24_40_s(int a, int c_uniform) {
+    int d;
+    asm("v_mad_i32_i24 %0, %1, 40, %2" : "=v"(d) : "v"(a), "s"(c_uniform));
+    return d;
+}
 // (lo16(a), lo16(b)) as one packed register
 __device__ __forceinline__ unsigned int pk_lo16(int a, int b) {
     return __builtin_amdgcn_perm((unsigned int) b, (unsigned int) a, 0x05040100u);
@@ -320,7 +340,15 @@ __device__ __forceinline__ void lk_fetch_J(const lk_smem &S, int row0, int o, un
     }
 }
 
-// One calcOpticalFlowPyrLK point, executed cooperatively by a full wave. Returns status.
+// The three rows of zeros under the B plane (what lane 63, which owns no pixels, differentiates): written once per kernel, before the first
+// level's barriers; no level writes them again.
+__device__ __forceinline__ void lk_zero_rows(lk_smem &S, int lane) {
+    static_assert(3 * LK_BW <= 128, "two stores per lane cover the rows of zeros");
+    S.B[(LK_BH - 3) * LK_BW + lane] = 0;
+    if (lane < 3 * LK_BW - 64) S.B[(LK_BH - 3) * LK_BW + 64 + lane] = 0;
+}
+
+// One calcOpticalFlowPyrLK point, executed cooperatively by a full wave (lk_zero_rows has run). Returns status.
 __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI, const unsigned char *slotJ,
                               float2 prevPt, float2 &nextIO, lk_smem &S, int lane, float *err_out) {
     const float FLT_SCALE = 1.f / (1 << 20);
@@ -393,7 +421,67 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
         unsigned int IXP[4], IYP[4];
         int sA11 = 0, sA12 = 0, sA22 = 0;
         float A11, A12, A22;
-        {
+        // derivative at support position (c = lx0+j, r = ly+rr): 3x3 neighbourhood = tile rows rr..rr+2, cols j..j+2.
+        // The derivative plane is ZERO outside the image: X = ipx+lx0+j in [0,W), Y = ipy+ly+rr in [0,H).
+        const bool all_in = ipx >= 0 && ipx + 22 <= W && ipy >= 0 && ipy + 22 <= H; // wave-uniform
+        if (all_in) {
+            // Interior windows (round 7): the blend and the Scharr stencil are integer linear maps and the only rounding is the final descale, so
+            //   sum_ab w_ab Scharr(I)(x+a, y+b) = Scharr(B)(x, y),  B(x, y) = sum_ab w_ab I(x+a, y+b)  (|B| <= 255 * 2^14; 4 * 16 * |B| < 2^29).
+            // ONE blend of the 23x23 grid shared through LDS and a 32-bit separable Scharr replace three blends of derivative planes that
+            // vertically adjacent lanes computed twice.  (A real branch: the empty asm keeps the compiler from merging the two forms.)
+            asm volatile("" ::: "memory");
+            {
+                // lane -> (row lane/2, 12 columns at (lane&1)*12) of B; lanes 46..63 repeat row 22 (same values to the same addresses: the
+                // wave stays full).  B carries the +256 of the patch sample's rounding; every difference below cancels it.  Column 23
+                // (from the tile row's padding bytes) is written and never read.
+                const int br = min(lane >> 1, 22), bs = lane & 1;
+                const unsigned int *p = &S.I[(br * LK_IS >> 2) + 3 * bs];
+                unsigned int d[2][4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) d[0][q] = p[q], d[1][q] = p[(LK_IS >> 2) + q];
+                int *dst = &S.B[br * LK_BW + 12 * bs];
+#pragma unroll
+                for (int q = 0; q < 3; q++) {
+                    int bv[4];
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const unsigned int sel = 0x0c000c00u | (unsigned int) e | ((unsigned int) (e + 1) << 16); // (byte e, 0, byte e+1, 0)
+                        const unsigned int i1 = __builtin_amdgcn_perm(d[0][e == 3 ? q + 1 : q], d[0][q], sel);
+                        const unsigned int i2 = __builtin_amdgcn_perm(d[1][e == 3 ? q + 1 : q], d[1][q], sel);
+                        bv[e]                 = dot2(i2, W1, dot2_keep_s(i1, W0, rnd8));
+                    }
+                    *reinterpret_cast<int4 *>(dst + 4 * q) = make_int4(bv[0], bv[1], bv[2], bv[3]);
+                }
+            }
+            __syncthreads();
+            // per lane: rows ly..ly+2, columns lx0..lx0+8 of B -> vertical smooth (x 4, as in the border form: the descaled derivative is the
+            // HIGH half of 4 v + 2^15) and vertical difference once each, then the horizontal difference / smooth.  All products are 24-bit:
+            // B + 256 < 2^22, sums of two < 2^23.  The rounding constant of Ix rides in the smooth terms ((j/2) 2^15: S[k+2] - S[k] keeps
+            // one 2^15), that of Iy is the accumulator of its first product.  Lane 63 reads the rows of zeros: (0 + 2^15) >> 16 = 0.
+            int bo = ly * LK_BW + lx0 + ((lane + 1) >> 6) * ((LK_BH - 3) * LK_BW); // lane 63 (ly = lx0 = 0): the rows of zeros
+            asm volatile("" : "+v"(bo)); // (one address register + immediate offsets; folded into the struct offset, every read got its own)
+            const int *bp = &S.B[bo];
+            int Sm[9], Vd[9];
+#pragma unroll
+            for (int jj = 0; jj < 9; jj++) {
+                const int b0 = bp[jj], b1 = bp[LK_BW + jj], b2 = bp[2 * LK_BW + jj];
+                Sm[jj] = mad24_12(b0 + b2, mad24_40_s(b1, (jj >> 1) << 15));
+                Vd[jj] = b2 - b0;
+                if (jj >= 1 && jj <= 7) c0[jj - 1] = 256 - (b1 & ~511); // c0 = 256 - 512 * ((blend + 256) >> 9)
+            }
+            int bx[7], by[7];
+#pragma unroll
+            for (int k = 0; k < 7; k++) {
+                bx[k] = Sm[k + 2] - Sm[k];
+                by[k] = mad24_12(Vd[k] + Vd[k + 2], mad24_40_s(Vd[k + 1], rnd15));
+            }
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                IXP[m] = m < 3 ? pk_hi16(bx[2 * m], bx[2 * m + 1]) : (unsigned int) bx[6] >> 16;
+                IYP[m] = m < 3 ? pk_hi16(by[2 * m], by[2 * m + 1]) : (unsigned int) by[6] >> 16;
+            }
+        } else {
+            // windows that reach over the image border: the derivative plane is zero outside the image, so the identity above does not hold
             const int idx = lx0 >> 2, sh = lx0 & 3;
             unsigned int Pp[4][5]; // pixel pairs (col 2m, 2m+1) of tile rows ly..ly+3, cols lx0..lx0+9
             // pair m = bytes sh + 2m, sh + 2m + 1 of the row's four dwords: for every sh in 0..3 it lies inside ONE pair of adjacent dwords that
@@ -410,9 +498,6 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
                 Pp[r][3] = __builtin_amdgcn_perm(d2, d1, sel1);
                 Pp[r][4] = __builtin_amdgcn_perm(d3, d2, sel0);
             }
-            // derivative at support position (c = lx0+j, r = ly+rr): 3x3 neighbourhood = tile rows rr..rr+2, cols j..j+2.
-            // The derivative plane is ZERO outside the image: X = ipx+lx0+j in [0,W), Y = ipy+ly+rr in [0,H).
-            const bool all_in = ipx >= 0 && ipx + 22 <= W && ipy >= 0 && ipy + 22 <= H; // wave-uniform fast path
             unsigned int DX[2][4], DY[2][4];
 #pragma unroll
             for (int rr = 0; rr < 2; rr++) {
@@ -428,9 +513,7 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
                     DY[rr][m] = pk_add(pk_mul(pk_add(T1[m], T1[m + 1]), 12), pk_mul(pk_shift(T1[m], T1[m + 1]), 40)); // 4 * (3*(t1[j]+t1[j+2]) + 10*t1[j+1])
                 }
             }
-            if (!all_in) { // windows that reach over the image border: a real (wave-uniform) branch — written as masks on the common path the
-                           // compiler turned it into 46 v_cndmask + 16 v_and per level for every window (round 5: the asm statement keeps it a branch)
-                asm volatile("" ::: "memory");
+            { // the derivatives outside the image are zero
 #pragma unroll
                 for (int rr = 0; rr < 2; rr++) {
                     const int Y           = ipy + ly + rr;
@@ -469,6 +552,8 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
                 IXP[m] = m < 3 ? pk_hi16(bx[2 * m], bx[2 * m + 1]) : (unsigned int) bx[6] >> 16;
                 IYP[m] = m < 3 ? pk_hi16(by[2 * m], by[2 * m + 1]) : (unsigned int) by[6] >> 16;
             }
+        }
+        {
             sA11 = dot2(IXP[3], IXP[3], dot2(IXP[2], IXP[2], dot2(IXP[1], IXP[1], dot2(IXP[0], IXP[0], 0))));
             sA12 = dot2(IXP[3], IYP[3], dot2(IXP[2], IYP[2], dot2(IXP[1], IYP[1], dot2(IXP[0], IYP[0], 0))));
             sA22 = dot2(IYP[3], IYP[3], dot2(IYP[2], IYP[2], dot2(IYP[1], IYP[1], dot2(IYP[0], IYP[0], 0))));
@@ -624,6 +709,7 @@ __global__ __launch_bounds__(64) void k_lk_track(icg_pyr_desc P, int n, const in
     const int i = icg_xcd_chunked(blockIdx.x, n);
     if (i >= n) return;
     const int lane = threadIdx.x;
+    lk_zero_rows(S, lane);
     const unsigned char *sI = P.base + (size_t) prev_slot[i] * P.slot_bytes;
     const unsigned char *sJ = P.base + (size_t) next_slot[i] * P.slot_bytes;
     float2 nx = next_pts[i];
@@ -649,6 +735,7 @@ __global__ __launch_bounds__(64, LK_WAVES_PER_EU) void k_lk_track_fb(icg_pyr_des
         if (i - s * seg_cap >= seg_count[s]) return; // wave-uniform
     }
     const int lane = threadIdx.x;
+    lk_zero_rows(S, lane);
     const unsigned char *sP = P.base + (size_t) prev_slot[i] * P.slot_bytes;
     const unsigned char *sN = P.base + (size_t) next_slot[i] * P.slot_bytes;
     const float2 p0 = prev_pts[i];
