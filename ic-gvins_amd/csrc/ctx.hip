@@ -152,7 +152,7 @@ extern "C" void icg_ctx_destroy(icg_ctx *ctx) {
                    ctx->d_roi_max, ctx->d_cand, ctx->d_cand_cnt, ctx->d_arena,    ctx->d_obs,
                    ctx->d_fidx,   ctx->d_rJ,      ctx->d_params,   ctx->d_sys,
                    ctx->d_fwin,   ctx->d_lmwin,   ctx->marg.d_J,   ctx->marg.d_e0,  ctx->marg.d_x0,
-                   ctx->marg.d_meta, ctx->d_lin_scratch};
+                   ctx->marg.d_meta, ctx->d_lin_scratch, ctx->d_red_S, ctx->d_red_H, ctx->d_chol_scratch};
     for (void *p : dev)
         if (p) (void) hipFree(p);
     for (icg_partition *pt : {&ctx->part_1, &ctx->part_w}) {

@@ -138,6 +138,14 @@ struct icg_ctx {
     // M3 (marg_linearize.hip): per-window working memory of icg_marg_linearize_batch for the windows that do not fit in LDS; grows on demand
     double *d_lin_scratch = nullptr;
     size_t lin_scratch_cap = 0; // bytes
+    // Reduced camera solve (chol.hip, reproj.hip): the W x P x P reduced systems icg_reproj_schur_windows_resident leaves on the device, every
+    // window's host-factor part (packed lower triangle, one slot of P (P + 1) / 2 doubles per window, kept until it is replaced) and the
+    // working memory of the systems that do not fit in LDS; all grow on demand
+    double *d_red_S = nullptr, *d_red_H = nullptr, *d_chol_scratch = nullptr;
+    size_t red_S_cap = 0, red_H_cap = 0, chol_scratch_cap = 0; // bytes
+    int red_P = 0, red_W = 0;                                  // shape of the resident reduced systems; red_W = 0: none
+    bool red_S_valid = false;                                  // d_red_S holds the reduction of what d_sys holds now (the back-substitution reads d_sys)
+    std::vector<int32_t> red_H_cols;                           // per window: columns of the resident host part, 0 = none
 
     icg_camera cam{};
     bool has_cam = false;
@@ -355,6 +363,29 @@ struct icg_call {
         return 0;
     }
 };
+
+// ---- batched Cholesky solve (chol.hip): one wave per system ---------------------------------------------------------------------------------
+// A system reads its matrix as A[A_off + i * ldA + k] (k <= i), optionally + the packed host part, optionally + dd on the diagonal, in that
+// order; offsets are in doubles into the arrays of icg_chol_ptrs, -1 = absent.
+#define ICG_CHOL_SOLVE 1    // factor and solve (otherwise only x = 0, status = 0 and the host-part copy below)
+#define ICG_CHOL_PART 2     // add the resident host part at H_off
+#define ICG_CHOL_PART_NEW 4 // the host part arrives at Hnew_off: add that and store it at H_off
+struct icg_chol_desc {
+    int32_t n, ldA, x_len, flags; // x_len >= n: x[n .. x_len) is written as zeros
+    int64_t A_off, H_off, Hnew_off, dd_off, b_off, x_off, L_off, s_off;
+};
+struct icg_chol_ptrs {
+    const double *A, *Hnew, *dd, *b;
+    double *H, *x, *L, *scratch;
+    int32_t *status;
+};
+struct icg_chol_plan {
+    int n_lds = 0, n_glob = 0, wpg = 1, lds_stride = 0; // lds_stride: doubles per wave
+    std::vector<int32_t> items;                         // the systems that run in LDS first, then the others
+};
+// fills desc[].s_off and the plan, grows ctx->d_chol_scratch; then (after the caller staged desc and plan.items) enqueues k_chol_solve
+int icg_chol_plan_build(icg_ctx *ctx, std::vector<icg_chol_desc> &desc, icg_chol_plan &plan);
+int icg_chol_enqueue(icg_ctx *ctx, const icg_chol_plan &plan, const icg_chol_desc *d_desc, const int32_t *d_items, icg_chol_ptrs p);
 
 // ---- device-resident tracker (tracker.hip): segmented / indirect launches of the primitives ----------------------------------------------
 // Everything below is asynchronous on the context's stream and takes DEVICE pointers: the stage kernels of the tracker leave the work

@@ -886,6 +886,21 @@ static int ensure_sys_capacity(icg_ctx *ctx, size_t doubles) {
     return 0;
 }
 
+// a device buffer of the reduced camera solve (d_red_S, d_red_H): grown without keeping its contents
+// (growing d_red_S alone would leave the host parts in d_red_H intact; they are dropped all the same, one rule for both buffers — the host
+// layer ships a window's part again with its next re-linearization, and a caller that solves before that gets A = S + dd, as documented)
+static int ensure_red_capacity(icg_ctx *ctx, double **buf, size_t *cap, size_t bytes) {
+    if (bytes <= *cap) return 0;
+    ICG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (*buf) (void) hipFree(*buf);
+    *buf = nullptr, *cap = 0;
+    ctx->red_W = 0;
+    ctx->red_H_cols.assign(ctx->red_H_cols.size(), 0);
+    ICG_HIP(ctx, hipMalloc((void **) buf, bytes));
+    *cap = bytes;
+    return 0;
+}
+
 // ---- the assembly plan of a partition (host, once per factor set / partition) ---------------------------------------------------------------
 static int asm_plan_build(icg_ctx *ctx, icg_partition &pt) {
     const int W = pt.W, n = ctx->n_factors_resident, n_lm = pt.lm_off[(size_t) W];
@@ -1026,7 +1041,7 @@ static void build_win_desc(const icg_partition &pt, const uint8_t *reassemble, c
 // and *S_view points there — no device-to-host copy and no 9 MB copy-out per LM step at 256 windows; valid until the next call on ctx.
 static int schur_impl(icg_ctx *ctx, icg_partition &pt, int P, const int32_t *col_pose, const int32_t *col_ext, const int32_t *col_td, const uint8_t *active,
                       const uint8_t *reassemble, const double *damp, double min_diag, double max_diag, double *S, const double **S_view,
-                      double *s, double *diag_cc, double *cost) {
+                      double *s, double *diag_cc, double *cost, bool S_resident = false) {
     const bool tdbg = getenv("ICG_ABI_DEBUG") != nullptr;
     auto tnow       = [] { return std::chrono::steady_clock::now(); };
     auto t_begin    = tnow();
@@ -1054,9 +1069,19 @@ static int schur_impl(icg_ctx *ctx, icg_partition &pt, int P, const int32_t *col
     }
     int rc = ensure_sys_capacity(ctx, (size_t) pt.sys_off[(size_t) W] + 8);
     if (rc) return rc;
+    if (S_resident) {
+        // the third destination: the lower tiles stay in a buffer of the context for icg_reproj_solve_windows
+        if (ctx->red_W != W || ctx->red_P != P) {
+            ctx->red_W = 0;
+            ctx->red_H_cols.assign((size_t) W, 0); // (host parts of another shape are not this partition's)
+        }
+        if ((rc = ensure_red_capacity(ctx, &ctx->d_red_S, &ctx->red_S_cap, sizeof(double) * (size_t) W * P * P))) return rc;
+        if ((rc = ensure_red_capacity(ctx, &ctx->d_red_H, &ctx->red_H_cap, sizeof(double) * (size_t) W * ((size_t) P * (P + 1) / 2)))) return rc;
+    }
     icg_partition &other = &pt == &ctx->part_1 ? ctx->part_w : ctx->part_1;
     other.sys_valid      = 0; // (d_sys is shared: whatever the other partition left there is overwritten)
     pt.sys_valid         = 0;
+    ctx->red_S_valid     = false; // (d_red_S was reduced from the d_sys that is rewritten now; the host parts stay)
     // owner of every camera column of every window (k_asm_camera / k_asm_landmarks)
     std::vector<int16_t> owner((size_t) W * P, (int16_t) -1);
     int Lmax = 1;
@@ -1113,7 +1138,7 @@ static int schur_impl(icg_ctx *ctx, icg_partition &pt, int P, const int32_t *col
     for (int w = 0; w < W; w++) std::copy(blk[(size_t) w].begin(), blk[(size_t) w].end(), blocks.begin() + (size_t) w * NBmax);
     icg_call c(ctx);
     rc = c.reserve(sizeof(win_desc) * (size_t) W + sizeof(int16_t) * owner.size() + sizeof(int32_t) * blocks.size() + (size_t) n +
-                   sizeof(double) * ((size_t) W * ((size_t) P * P + 2 * (size_t) P + 1)) + 8192);
+                   sizeof(double) * ((size_t) W * ((S_resident ? 0 : (size_t) P * P) + 2 * (size_t) P + 1)) + 8192);
     if (rc) return rc;
     const win_desc *d_wd = c.in(wd.data(), (size_t) W);
     const int16_t *d_own = c.in(owner.data(), owner.size());
@@ -1124,7 +1149,7 @@ static int schur_impl(icg_ctx *ctx, icg_partition &pt, int P, const int32_t *col
     // (the zero-copy region is allocated LAST: finish() copies ONE device range back that spans all mirrored outputs, and must not run
     // over memory the kernel wrote through the host mapping)
     double *d_cost = c.out(any_new ? cost : (double *) nullptr, (size_t) W);
-    double *d_S    = S_view ? nullptr : c.out(S, (size_t) W * P * P);
+    double *d_S    = S_resident ? ctx->d_red_S : S_view ? nullptr : c.out(S, (size_t) W * P * P);
     double *d_s    = c.out(s, (size_t) W * P);
     double *d_dg   = c.out(diag_cc, (size_t) W * P); // user pointer may be null: still a valid device scratch
     if (S_view) {
@@ -1148,7 +1173,7 @@ static int schur_impl(icg_ctx *ctx, icg_partition &pt, int P, const int32_t *col
         icg_prof_scope ps(ctx, "schur_reduce");
         hipLaunchKernelGGL(k_schur_inv_w, dim3((Lmax + 255) / 256, W), dim3(256), 0, ctx->stream, d_wd, P, ctx->d_sys, min_diag, max_diag);
         hipLaunchKernelGGL(k_schur_reduce_w, dim3((unsigned) ((NT + 255) / 256), W), dim3(256), red_lds, ctx->stream, d_wd, P, red_LT, (const double *) ctx->d_sys, d_S, d_s,
-                           d_dg, S_view ? 1 : 0);
+                           d_dg, S_view || S_resident ? 1 : 0);
         // the cost belongs to the linearization point: only meaningful while the resident residuals are the ones assembled
         if (any_new) hipLaunchKernelGGL(k_reproj_cost_w, dim3(W), dim3(256), 0, ctx->stream, d_wd, d_r, d_act, ctx->last_huber, d_cost);
     }
@@ -1164,6 +1189,7 @@ static int schur_impl(icg_ctx *ctx, icg_partition &pt, int P, const int32_t *col
     }
     pt.sys_P = P, pt.sys_valid = 1;
     ctx->sys_min_diag = min_diag, ctx->sys_max_diag = max_diag;
+    if (S_resident) ctx->red_W = W, ctx->red_P = P, ctx->red_S_valid = true;
     return ICG_OK;
 }
 
@@ -1382,6 +1408,8 @@ extern "C" int icg_reproj_set_windows(icg_ctx *ctx, int n_windows, const int32_t
     pt.fac_off.assign(fac_off, fac_off + n_windows + 1);
     pt.lm_off.assign(lm_off, lm_off + n_windows + 1);
     pt.sys_valid = 0;
+    ctx->red_W   = 0; // (the resident reduced systems and host parts belonged to the partition that is replaced)
+    ctx->red_H_cols.clear();
     const auto t0 = std::chrono::steady_clock::now();
     int rc       = asm_plan_build(ctx, pt);
     if (rc) pt.W = 0;
@@ -1475,6 +1503,92 @@ extern "C" int icg_reproj_schur_windows_view(icg_ctx *ctx, int P, const int32_t 
     if (!S_view) return ICG_ERR_INVALID;
     if (int rc = windows_args_ok(ctx, P, col_pose, col_ext, col_td, reassemble, damp, s)) return rc;
     return schur_impl(ctx, ctx->part_w, P, col_pose, col_ext, col_td, active, reassemble, damp, min_diag, max_diag, nullptr, S_view, s, diag_cc, cost);
+}
+
+extern "C" int icg_reproj_schur_windows_resident(icg_ctx *ctx, int P, const int32_t *col_pose, const int32_t *col_ext, const int32_t *col_td,
+                                                 const uint8_t *active, const uint8_t *reassemble, const double *damp, double min_diag,
+                                                 double max_diag, double *s, double *diag_cc, double *cost) {
+    if (int rc = windows_args_ok(ctx, P, col_pose, col_ext, col_td, reassemble, damp, s)) return rc;
+    return schur_impl(ctx, ctx->part_w, P, col_pose, col_ext, col_td, active, reassemble, damp, min_diag, max_diag, nullptr, nullptr, s, diag_cc, cost, true);
+}
+
+// The reduced camera solve of every window (k_chol_solve, chol.hip: one wave per window, the host's arithmetic bit for bit) and the landmark
+// back-substitution on the delta_c it leaves on the device: the two host phases "reduced solve" and "back-substitution" of an LM step as one
+// call.  Up: dd and rhs (2 W P doubles) and the host parts that changed; down: delta_c, status, delta_l, lm_terms.
+extern "C" int icg_reproj_solve_windows(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *solve, const uint8_t *host_part_new, const double *host_S,
+                                        const double *dd, const double *rhs, double *delta_c, int32_t *status, double *delta_l, double *lm_terms) {
+    if (!ctx) return ICG_ERR_INVALID;
+    if (P <= 0 || !Pw || !solve || !dd || !rhs || !delta_c) return icg_fail(ctx, ICG_ERR_INVALID, "icg_reproj_solve_windows: invalid argument");
+    icg_partition &pt = ctx->part_w;
+    const int W       = pt.W;
+    if (W <= 0 || !ctx->red_S_valid || ctx->red_W != W || ctx->red_P != P || !pt.sys_valid || pt.sys_P != P)
+        return icg_fail(ctx, ICG_ERR_INVALID, "no resident reduced systems of size %d: call icg_reproj_schur_windows_resident first", P);
+    const size_t slot = (size_t) P * (P + 1) / 2;
+    std::vector<icg_chol_desc> desc((size_t) W);
+    std::vector<int32_t> new_cols(ctx->red_H_cols);
+    size_t t_new = 0;
+    for (int w = 0; w < W; w++) {
+        const bool is_new = host_part_new && host_part_new[w];
+        if ((solve[w] || is_new) && (Pw[w] <= 0 || Pw[w] > P))
+            return icg_fail(ctx, ICG_ERR_INVALID, "icg_reproj_solve_windows: window %d: Pw = %d (1 .. %d)", w, Pw[w], P);
+        if (is_new && !host_S) return icg_fail(ctx, ICG_ERR_INVALID, "icg_reproj_solve_windows: window %d: host_part_new without host_S", w);
+        int flags = solve[w] ? ICG_CHOL_SOLVE : 0;
+        if (is_new) {
+            flags |= ICG_CHOL_PART_NEW;
+            new_cols[(size_t) w] = Pw[w];
+        } else if (solve[w] && new_cols[(size_t) w] != 0) {
+            if (new_cols[(size_t) w] != Pw[w])
+                return icg_fail(ctx, ICG_ERR_INVALID, "icg_reproj_solve_windows: window %d: the resident host part has %d columns, not %d", w,
+                                new_cols[(size_t) w], Pw[w]);
+            flags |= ICG_CHOL_PART;
+        }
+        const int nw    = solve[w] || is_new ? Pw[w] : 1;
+        desc[(size_t) w] = {nw, P, P, flags, (int64_t) w * P * P, (int64_t) (w * slot), (int64_t) t_new, (int64_t) w * P, (int64_t) w * P, (int64_t) w * P, -1, 0};
+        if (is_new) t_new += (size_t) Pw[w] * (Pw[w] + 1) / 2;
+    }
+    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    icg_chol_plan plan;
+    int rc = icg_chol_plan_build(ctx, desc, plan);
+    if (rc) return rc;
+    const int n_lm = pt.lm_off[(size_t) W];
+    std::vector<win_desc> wd;
+    build_win_desc(pt, nullptr, nullptr, wd);
+    icg_call c(ctx);
+    if ((rc = c.reserve((sizeof(win_desc) + sizeof(icg_chol_desc) + 8) * (size_t) W + sizeof(double) * (t_new + 3 * (size_t) W * P + 3 * (size_t) n_lm + 2 * (size_t) W) +
+                        16 * 256)))
+        return rc;
+    icg_chol_ptrs p{};
+    const win_desc *d_wd        = c.in(wd.data(), (size_t) W);
+    const icg_chol_desc *d_desc = c.in(desc.data(), (size_t) W);
+    const int32_t *d_items      = c.in(plan.items.data(), (size_t) W);
+    p.dd                        = c.in(dd, (size_t) W * P);
+    p.b                         = c.in(rhs, (size_t) W * P);
+    p.Hnew                      = t_new ? c.in(host_S, t_new) : nullptr;
+    if ((rc = c.seal())) return rc;
+    p.A      = ctx->d_red_S;
+    p.H      = ctx->d_red_H;
+    p.x      = c.out(delta_c, (size_t) W * P);
+    p.status = c.out(status, (size_t) W); // (user pointer may be null: still a valid device scratch)
+    double *d_dl = c.out(n_lm > 0 ? delta_l : (double *) nullptr, (size_t) std::max(n_lm, 1));
+    double *d_tm = c.out(lm_terms, 2 * (size_t) W); // (zeros without landmarks: set below)
+    double *d_lt = c.out((double *) nullptr, 2 * (size_t) std::max(n_lm, 1));
+    ICG_LAUNCH_GUARD(c);
+    // from here on the device copy of the flagged host parts is being replaced: a failure below leaves those windows without one
+    for (int w = 0; w < W; w++)
+        if (host_part_new && host_part_new[w]) ctx->red_H_cols[(size_t) w] = 0;
+    if ((rc = icg_chol_enqueue(ctx, plan, d_desc, d_items, p))) return rc;
+    if (n_lm > 0) {
+        icg_prof_scope ps(ctx, "schur_backsub");
+        hipLaunchKernelGGL(k_schur_backsub_w, dim3(n_lm), dim3(64), 0, ctx->stream, d_wd, W > 1 ? (const int32_t *) ctx->d_lmwin : (const int32_t *) nullptr, 0, P,
+                           (const double *) ctx->d_sys, (const double *) p.x, d_dl, d_lt, ctx->sys_min_diag, ctx->sys_max_diag);
+        hipLaunchKernelGGL(k_terms_reduce_w, dim3(W), dim3(256), 0, ctx->stream, d_wd, (const double *) d_lt, d_tm);
+    } else {
+        ICG_HIP(ctx, hipMemsetAsync(d_tm, 0, sizeof(double) * 2 * (size_t) W, ctx->stream));
+    }
+    ICG_HIP(ctx, hipGetLastError());
+    if ((rc = c.finish())) return rc;
+    ctx->red_H_cols.swap(new_cols);
+    return ICG_OK;
 }
 
 extern "C" int icg_reproj_landmark_diag_windows(icg_ctx *ctx, double *h_ll) {

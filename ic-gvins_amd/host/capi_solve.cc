@@ -79,14 +79,26 @@ int icgh_backend_solve(int n, const double *obs_soa, const int32_t *idx_i, const
 // concatenated window-major: window w owns factors [fac_off[w], fac_off[w+1]) (obs_soa is 15 x n_total, idx_* LOCAL to the window),
 // poses [pose_off[w], ..), inverse depths [lm_off[w], ..); ext is W x 7, td has W entries.  summary8 is W x 8 as in icgh_backend_solve.
 // Returns the wall time of the two solves + culling in ms through *solve_ms.
-int icgh_backend_solve_batch(int W, const int32_t *fac_off, const int32_t *pose_off, const int32_t *lm_off, const double *obs_soa, const int32_t *idx_i,
-                             const int32_t *idx_j, const int32_t *idx_lm, double *poses, double *ext, double *invdepth, double *td,
-                             const double *prior_poses, double prior_weight, double huber, int ext_constant, int td_constant, int iters1, int iters2,
-                             double chi2, double *summary8, double *solve_ms, char *err, int errlen) {
+// reduced_solve_mode: 0 = the reduced camera solves on the host pool, 1 = on the device (WindowSolverBatch::setDeviceReducedSolve; the same
+// bits).  Without the device entry points in the build mode 1 computes nothing: -4 and "icg_reproj_solve_windows is not in this build".
+int icgh_backend_solve_batch_mode(int W, const int32_t *fac_off, const int32_t *pose_off, const int32_t *lm_off, const double *obs_soa,
+                                  const int32_t *idx_i, const int32_t *idx_j, const int32_t *idx_lm, double *poses, double *ext, double *invdepth,
+                                  double *td, const double *prior_poses, double prior_weight, double huber, int ext_constant, int td_constant,
+                                  int iters1, int iters2, double chi2, double *summary8, double *solve_ms, char *err, int errlen,
+                                  int reduced_solve_mode) {
     return guarded(err, errlen, [&] {
+        if (reduced_solve_mode != 0 && reduced_solve_mode != 1) {
+            set_err(err, errlen, "reduced_solve_mode must be 0 (host) or 1 (device)");
+            return -1;
+        }
+        if (reduced_solve_mode == 1 && !WindowSolverBatch::deviceReducedSolveAvailable()) {
+            set_err(err, errlen, "icg_reproj_solve_windows is not in this build");
+            return -4;
+        }
         const int n = fac_off[W];
         vector<std::unique_ptr<ReprojectionFactor>> factors;
         WindowSolverBatch solver(0, huber);
+        solver.setDeviceReducedSolve(reduced_solve_mode == 1);
         for (int w = 0; w < W; w++) {
             const int ww = solver.addWindow();
             double *P = poses + 7 * (size_t) pose_off[w], *E = ext + 7 * (size_t) w, *D = invdepth + lm_off[w], *TD = td + w;
@@ -137,6 +149,14 @@ int icgh_backend_solve_batch(int W, const int32_t *fac_off, const int32_t *pose_
         }
         return 0;
     });
+}
+
+int icgh_backend_solve_batch(int W, const int32_t *fac_off, const int32_t *pose_off, const int32_t *lm_off, const double *obs_soa, const int32_t *idx_i,
+                             const int32_t *idx_j, const int32_t *idx_lm, double *poses, double *ext, double *invdepth, double *td,
+                             const double *prior_poses, double prior_weight, double huber, int ext_constant, int td_constant, int iters1, int iters2,
+                             double chi2, double *summary8, double *solve_ms, char *err, int errlen) {
+    return icgh_backend_solve_batch_mode(W, fac_off, pose_off, lm_off, obs_soa, idx_i, idx_j, idx_lm, poses, ext, invdepth, td, prior_poses, prior_weight,
+                                         huber, ext_constant, td_constant, iters1, iters2, chi2, summary8, solve_ms, err, errlen, 0);
 }
 
 // Aggregate solve throughput with many windows in flight: `threads` host threads, each with its own ReprojectionBatch (own icg_ctx

@@ -13,9 +13,19 @@
 
 #include "../../include/icgvins_hip.h"
 
+// A build of this layer on another implementation of the C ABI may not have the entry points: the references stay weak (null when absent)
+// and solve() reports it; the product library links libicgvins_hip.so, which defines them.
+#pragma weak icg_chol_solve_batch
+#pragma weak icg_reproj_schur_windows_resident
+#pragma weak icg_reproj_solve_windows
+
 namespace icg {
 
 using solver_detail::choleskySolve;
+
+bool WindowSolverBatch::deviceReducedSolveAvailable() {
+    return &icg_chol_solve_batch != nullptr && &icg_reproj_schur_windows_resident != nullptr && &icg_reproj_solve_windows != nullptr;
+}
 
 // The per-window host phases of an LM step (host factors, reduced solves, trial bookkeeping) take tens of microseconds per window: they
 // run on a persistent pool — spawning threads per phase (four phases per step) cost more than the phases themselves.
@@ -202,9 +212,16 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
     }
     const size_t NW = windows_.size();
     const int P     = P_;
+    const bool dev_solve = device_reduced_;
+    if (dev_solve && !deviceReducedSolveAvailable()) {
+        error_ = "icg_reproj_solve_windows is not in this build";
+        return false;
+    }
     // The reduced systems: their lower tiles are read where the reduction kernel writes them (pinned memory) and every window is factored by a
-    // host thread (dense_kernels.cc).  A batched Cholesky on the device lost to this on MI355X, 256 C2 windows (P = 67), two solves: 26.5 ms
-    // against 21.1 ms.
+    // host thread (dense_kernels.cc).  An earlier device form, since deleted (a workgroup per window, three barriers per column, every host
+    // part shipped per re-linearization), lost to this on MI355X, 256 C2 windows (P = 67), two solves: 26.5 ms against 21.1 ms.  With
+    // setDeviceReducedSolve(true) the systems stay on the device instead and one wave per window solves them there without a barrier
+    // (icg_reproj_solve_windows, k_chol_solve), this thread pool only damping and deciding; DESIGN.md section 8 item 3 has the times of both.
     struct State {
         solver_detail::TrustRegion tr;
         double model;
@@ -219,6 +236,16 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
                                // the next call on ctx_: consumed by the reduced solves below, before the back-substitution call)
     std::vector<uint8_t> reassemble(NW);
     std::vector<double> host_cost(NW, 0.0);
+    // device reduced solve: what one icg_reproj_solve_windows call takes and returns
+    std::vector<int32_t> dev_Pw, dev_status;
+    std::vector<uint8_t> dev_solve_flag, dev_part_new;
+    std::vector<double> dev_dd, dev_rhs, dev_parts;
+    std::vector<size_t> dev_part_off;
+    if (dev_solve) {
+        dev_Pw.resize(NW), dev_status.resize(NW), dev_solve_flag.resize(NW), dev_part_new.resize(NW), dev_part_off.resize(NW + 1);
+        dev_dd.resize((size_t) NW * P), dev_rhs.resize((size_t) NW * P);
+        for (size_t w = 0; w < NW; w++) dev_Pw[w] = windows_[w].P, windows_[w].host_part_dirty = false;
+    }
     auto fail = [&](const char *what) {
         error_ = std::string(what) + ": " + icg_last_error(ctx_);
         return false;
@@ -249,8 +276,12 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
             int dev_rc = ICG_OK;
             if (!side_) side_.reset(new SideThread());
             SideCall dev(*side_, [&] {
-                dev_rc = icg_reproj_schur_windows_view(ctx_, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), reassemble.data(), damp.data(),
-                                                       o.min_lm_diagonal, o.max_lm_diagonal, &S, s.data(), diag.data(), cost.data());
+                if (dev_solve)
+                    dev_rc = icg_reproj_schur_windows_resident(ctx_, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), reassemble.data(),
+                                                               damp.data(), o.min_lm_diagonal, o.max_lm_diagonal, s.data(), diag.data(), cost.data());
+                else
+                    dev_rc = icg_reproj_schur_windows_view(ctx_, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), reassemble.data(),
+                                                           damp.data(), o.min_lm_diagonal, o.max_lm_diagonal, &S, s.data(), diag.data(), cost.data());
             });
             std::atomic<int> host_failed{0};
             host_cost.assign(NW, 0.0);
@@ -259,12 +290,13 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
                 Window &W = windows_[w];
                 W.host_S.assign((size_t) P * P, 0.0), W.host_s.assign((size_t) P, 0.0), W.host_diag.assign((size_t) P, 0.0);
                 if (!solver_detail::hostFactors(W.problem, P, W.host_S.data(), W.host_s.data(), W.host_diag.data(), &host_cost[w])) host_failed++;
+                W.host_part_dirty = true;
             });
             clk.stop(2);
             clk.start();
             dev.join();
             clk.stop(1); // (what is left of the device call once the host half is through)
-            if (dev_rc != ICG_OK) return fail("icg_reproj_schur_windows_view");
+            if (dev_rc != ICG_OK) return fail(dev_solve ? "icg_reproj_schur_windows_resident" : "icg_reproj_schur_windows_view");
             if (host_failed.load()) {
                 error_ = "a host cost function failed to evaluate";
                 return false;
@@ -307,6 +339,12 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
             }
             const int Pw = windows_[w].P; // columns beyond Pw are empty (zero rows): solve the leading block only
             T.tr.damp(o, T.diag, Pw, T.dd);
+            if (dev_solve) { // the solve itself follows for all windows at once
+                std::copy(T.dd.begin(), T.dd.end(), dev_dd.begin() + (long) (w * P));
+                std::copy(T.s.begin(), T.s.end(), dev_rhs.begin() + (long) (w * P));
+                T.stepped = true;
+                return;
+            }
             std::vector<double> Ab((size_t) Pw * Pw), bb(T.s.begin(), T.s.begin() + Pw);
             const double *Sw = &S[w * (size_t) P * P], *Hw = windows_[w].host_S.data();
             for (int i = 0; i < Pw; i++) // lower triangle: what the view holds and what choleskySolve reads
@@ -322,6 +360,42 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
             std::copy(T.delta_c.begin(), T.delta_c.end(), delta_c.begin() + (long) (w * P));
             T.stepped = true;
         });
+        bool dev_any = false;
+        if (dev_solve) {
+            // the windows that solve in this step, and of those the host parts a re-linearization rebuilt since they were last shipped
+            size_t total = 0;
+            for (size_t w = 0; w < NW; w++) {
+                dev_solve_flag[w] = st[w].stepped ? 1 : 0;
+                dev_part_new[w]   = st[w].stepped && windows_[w].host_part_dirty ? 1 : 0;
+                dev_part_off[w]   = total;
+                if (dev_part_new[w]) total += (size_t) dev_Pw[w] * ((size_t) dev_Pw[w] + 1) / 2;
+                dev_any |= st[w].stepped;
+            }
+            dev_part_off[NW] = total;
+            dev_parts.resize(total);
+            forEachWindow(NW, [&](size_t w) {
+                if (!dev_part_new[w]) return;
+                const double *Hw = windows_[w].host_S.data();
+                double *dst      = dev_parts.data() + dev_part_off[w];
+                for (int i = 0; i < dev_Pw[w]; i++, dst += i) memcpy(dst, Hw + (size_t) i * P, sizeof(double) * ((size_t) i + 1));
+            });
+        }
+        if (dev_any) {
+            if (icg_reproj_solve_windows(ctx_, P, dev_Pw.data(), dev_solve_flag.data(), dev_part_new.data(), dev_parts.empty() ? nullptr : dev_parts.data(),
+                                         dev_dd.data(), dev_rhs.data(), delta_c.data(), dev_status.data(), delta_l.data(), terms.data()) != ICG_OK)
+                return fail("icg_reproj_solve_windows");
+            for (size_t w = 0; w < NW; w++) {
+                State &T = st[w];
+                if (!T.stepped) continue;
+                windows_[w].host_part_dirty = false;
+                if (dev_status[w] != 0) {
+                    T.stepped = false, T.redamp = true;
+                    T.done = T.tr.reject(o);
+                    continue;
+                }
+                T.delta_c.assign(delta_c.begin() + (long) (w * P), delta_c.begin() + (long) ((w + 1) * P));
+            }
+        }
         bool any_step = false, all_done = true;
         for (size_t w = 0; w < NW; w++) any_step |= st[w].stepped, all_done &= st[w].done;
         clk.stop(3);
@@ -329,7 +403,7 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
         if (!any_step) continue; // only re-damping this round
         // ---- landmark back-substitution for all windows, model decrease, trial points ---------------------------------------------
         clk.start();
-        if (n_lm_ > 0 && icg_reproj_backsub_windows(ctx_, P, delta_c.data(), delta_l.data(), terms.data()) != ICG_OK)
+        if (!dev_solve && n_lm_ > 0 && icg_reproj_backsub_windows(ctx_, P, delta_c.data(), delta_l.data(), terms.data()) != ICG_OK)
             return fail("icg_reproj_backsub_windows");
         clk.stop(4);
         clk.start();

@@ -6,7 +6,8 @@
 // launch; each window keeps its own trust-region radius, accepts or rejects its own step and stops by its own tolerances, exactly as
 // a WindowSolver of its own would (tests: identical step sequences and optima): the problem model, the column layout and the step rule of
 // a window are solver_detail.h's, shared with WindowSolver; the lock-step schedule is this class's own.  Host-evaluated factors
-// (preintegration, marginalization prior, priors) and the P x P reduced solves stay per window on the host.
+// (preintegration, marginalization prior, priors) stay per window on the host, and so do the P x P reduced solves unless
+// setDeviceReducedSolve(true) moves them to the device (icg_reproj_solve_windows: the same bits, off by default).
 #pragma once
 #include <memory>
 #include <string>
@@ -51,6 +52,15 @@ public:
 
     // uploads the factor set and the window partition (done by the first solve() otherwise): problem setup, not part of a solve
     bool prepare();
+    // The reduced camera solves of an LM step on the device: the reduced systems stay resident (icg_reproj_schur_windows_resident) and the
+    // phases "reduced solve" and "back-substitution" become one icg_reproj_solve_windows call; a window's host-factor part is shipped only in
+    // a step that re-linearized it.  The iteration budget, the gradient test, the damping, the reject / re-damp decisions (taken from the
+    // call's status) and the trial handling stay on the host, and delta_c is the host solve's bit for bit: the LM sequence does not change.
+    // Off by default.  The three C entries are referenced weakly: in a build of this layer on a C ABI without them
+    // deviceReducedSolveAvailable() is false and solve() fails by name when the option is on.
+    void setDeviceReducedSolve(bool on) { device_reduced_ = on; }
+    bool deviceReducedSolve() const { return device_reduced_; }
+    static bool deviceReducedSolveAvailable();
     bool solve(const Options &options, std::vector<Summary> *summaries);
     // removeReprojectionFactorsByChi2 (ic_gvins.cc:1269-1297) for every window; returns the number removed per window
     std::vector<int> removeReprojectionFactorsByChi2(double chi2);
@@ -70,6 +80,7 @@ private:
         int P{0};
         int fac_begin{0}, lm_begin{0}, pose_begin{0};
         std::vector<double> host_S, host_s, host_diag;
+        bool host_part_dirty{false}; // host_S was rebuilt since it was last shipped to the device (device reduced solve)
     };
     bool finalize();
     bool layout();
@@ -88,6 +99,7 @@ private:
     std::vector<int32_t> col_pose_, col_ext_, col_td_;
     int P_{0}, n_factors_{0}, n_poses_{0}, n_lm_{0};
     bool finalized_{false};
+    bool device_reduced_{false};
     std::string error_;
 };
 

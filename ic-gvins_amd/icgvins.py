@@ -23,11 +23,13 @@ EXPORTS = [
     "icg_reproj_schur_windows_view", "icg_reproj_reserve_windows", "icg_reproj_eval_resident_view", "icg_reproj_backsub_windows", "icg_reproj_cost_windows", "icg_reproj_fetch_residuals", "icg_reproj_chi2_cull",
     "icg_reproj_landmark_diag_windows",
     "icg_marg_prior_set", "icg_marg_prior_evaluate", "icg_marg_linearize_batch",
+    "icg_chol_solve_batch", "icg_reproj_schur_windows_resident", "icg_reproj_solve_windows",
 ]
 
 
 MARG_MAX_R = 1024  # ICG_MARG_MAX_R of include/icgvins_hip.h
 MARG_LIN_MAX_P = 512  # ICG_MARG_LIN_MAX_P
+CHOL_MAX_N = 512  # ICG_CHOL_MAX_N
 
 
 class IcgError(RuntimeError):
@@ -427,6 +429,30 @@ class Context:
         S = np.ctypeslib.as_array(view, shape=(W, P, P)).copy()
         return S, s, dg, cost
 
+    def reproj_schur_windows_resident(self, P, col_pose, col_ext, col_td, active=None, reassemble=None, damp=None, min_diag=1e-6, max_diag=1e32):
+        """icg_reproj_schur_windows_resident: the reduced systems stay on the device for reproj_solve_windows -> (s, diag_cc, cost)"""
+        W = self._nwin
+        s, dg, cost = np.zeros((W, P)), np.zeros((W, P)), np.zeros(W)
+        act = None if active is None else np.ascontiguousarray(active, np.uint8)
+        re = np.ones(W, np.uint8) if reassemble is None else np.ascontiguousarray(reassemble, np.uint8)
+        dm = np.zeros(W) if damp is None else _f64(damp)
+        self._ck(self.lib.icg_reproj_schur_windows_resident(self.h, int(P), _p(_i32(col_pose)), _p(_i32(col_ext)), _p(_i32(col_td)), _p(act), _p(re),
+                                                             _p(dm), C.c_double(min_diag), C.c_double(max_diag), _p(s), _p(dg), _p(cost)),
+                 "icg_reproj_schur_windows_resident")
+        return s, dg, cost
+
+    def reproj_solve_windows(self, P, Pw, solve, dd, rhs, n_lm, host_part_new=None, host_S=None):
+        """icg_reproj_solve_windows: host_S = the packed lower triangles of the flagged windows, flat -> (delta_c W x P, status, delta_l, lm_terms)"""
+        W = self._nwin
+        Pw, sv = _i32(Pw).reshape(W), np.ascontiguousarray(solve, np.uint8).reshape(W)
+        new = None if host_part_new is None else np.ascontiguousarray(host_part_new, np.uint8).reshape(W)
+        hs = None if host_S is None else _f64(host_S).reshape(-1)
+        dd, rhs = _f64(dd).reshape(W, P), _f64(rhs).reshape(W, P)
+        dc, st, dl, terms = np.zeros((W, P)), np.zeros(W, np.int32), np.zeros(n_lm), np.zeros((W, 2))
+        self._ck(self.lib.icg_reproj_solve_windows(self.h, int(P), _p(Pw), _p(sv), _p(new), _p(hs), _p(dd), _p(rhs), _p(dc), _p(st), _p(dl), _p(terms)),
+                 "icg_reproj_solve_windows")
+        return dc, st, dl, terms
+
     def reproj_backsub_windows(self, P, delta_c, n_lm):
         out, terms = np.zeros(n_lm), np.zeros((self._nwin, 2))
         self._ck(self.lib.icg_reproj_backsub_windows(self.h, int(P), _p(_f64(delta_c)), _p(out), _p(terms)), "icg_reproj_backsub_windows")
@@ -519,6 +545,20 @@ class Context:
                                                    _p(out["J0"]), _p(out["e0"]), _p(out["evals"]), _p(out["min_ev_m"]), _p(out["status"])),
                  "icg_marg_linearize_batch")
         return out
+
+    # ---- the reduced camera solve
+    def chol_solve_batch(self, n, A, b, want_L=True, want_status=True):
+        """icg_chol_solve_batch: A (n[k] x n[k] row-major, lower triangle read) and b flat, system after system -> (x, L | None, status | None),
+        flat; L is zero above the diagonals"""
+        n = _i32(n).reshape(-1)
+        A, b = _f64(A).reshape(-1), _f64(b).reshape(-1)
+        if A.shape[0] != int((n.astype(np.int64).clip(0) ** 2).sum()) or b.shape[0] != int(n.clip(0).sum()):
+            raise IcgError("chol_solve_batch: n, A, b do not describe the same systems")
+        x = np.zeros(b.shape[0])
+        L = np.zeros(A.shape[0]) if want_L else None
+        status = np.zeros(len(n), np.int32) if want_status else None
+        self._ck(self.lib.icg_chol_solve_batch(self.h, len(n), _p(n), _p(A), _p(b), _p(x), _p(L), _p(status)), "icg_chol_solve_batch")
+        return x, L, status
 
     # ---- f4
     def ins_mechanize_batch(self, offsets, imu, cfg8, states23, want_traj=True):

@@ -237,6 +237,30 @@ int icg_reproj_schur_windows(icg_ctx *ctx, int P, const int32_t *col_pose, const
 int icg_reproj_schur_windows_view(icg_ctx *ctx, int P, const int32_t *col_pose, const int32_t *col_ext, const int32_t *col_td, const uint8_t *active,
                                   const uint8_t *reassemble, const double *damp, double min_diag, double max_diag, const double **S_view, double *s,
                                   double *diag_cc, double *cost);
+/* the same call with the reduced systems left RESIDENT: the lower triangles stay in a device buffer of the context (nothing of S crosses
+ * the link) for icg_reproj_solve_windows; s, diag_cc and cost come back as above.  The resident systems are valid until the next
+ * icg_reproj_schur* call of any form (each rewrites the window systems the back-substitution reads) or icg_reproj_set_windows on ctx;
+ * the host parts of icg_reproj_solve_windows outlive the other schur forms. */
+int icg_reproj_schur_windows_resident(icg_ctx *ctx, int P, const int32_t *col_pose, const int32_t *col_ext, const int32_t *col_td,
+                                      const uint8_t *active, const uint8_t *reassemble, const double *damp, double min_diag, double max_diag,
+                                      double *s, double *diag_cc, double *cost);
+/* The reduced camera solve and the landmark back-substitution of an LM step for all windows, on the systems
+ * icg_reproj_schur_windows_resident left on the device.  For every window with solve[w] != 0:
+ *   A = lower(S_w) + lower(host part of w) on the leading Pw[w] columns, then A_kk += dd[w * P + k] — each element (S + H) + dd, the operand
+ *   order of the host loop; A x = rhs[w * P ..] by icg_chol_solve_batch's arithmetic (the host layer's choleskySolve, bit for bit);
+ *   delta_c (W x P): x on the leading Pw[w] columns; zeros beyond Pw[w], for a window that is not solved and for one whose status is 1;
+ *   status (W, optional): 0 ok or not solved, 1 not positive definite / non-finite.
+ * Then icg_reproj_backsub_windows' kernels run on the delta_c that is already on the device: delta_l (n_lm) and lm_terms (W x 2), both
+ * optional.  dd and rhs are W x P.
+ * Host parts: the device keeps one per window (the packed lower triangle of the leading Pw x Pw block: row i holds columns 0 .. i) until it is
+ * replaced.  host_S carries the parts of the windows with host_part_new[w] != 0 only, window after window; host_part_new = NULL or all zero
+ * with host_S = NULL is valid.  A window that never received a part has none (A = S + dd).  Parts are dropped by
+ * icg_reproj_set_windows and when icg_reproj_schur_windows_resident changes W or P.
+ * ICG_ERR_INVALID: no resident systems of this P (icg_reproj_schur_windows_resident of the same P must be the LAST schur call), a NULL required pointer, Pw[w]
+ * outside 1 .. P for a window that is solved or receives a part, a flagged part without host_S, a resident part whose column count is not
+ * Pw[w] (the message names the window).  After an error nothing was launched. */
+int icg_reproj_solve_windows(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *solve, const uint8_t *host_part_new, const double *host_S,
+                             const double *dd, const double *rhs, double *delta_c, int32_t *status, double *delta_l, double *lm_terms);
 /* problem setup: pre-sizes the resident window systems and the staging memory for reduced systems of size P (a hint; optional) */
 int icg_reproj_reserve_windows(icg_ctx *ctx, int P);
 int icg_reproj_backsub_windows(icg_ctx *ctx, int P, const double *delta_c, double *delta_l, double *lm_terms);
@@ -325,6 +349,22 @@ int icg_marg_prior_evaluate(icg_ctx *ctx, const double *x, double *residuals, do
 #define ICG_MARG_LIN_MAX_P 512
 int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
                              double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status);
+
+/* ---- the reduced camera solve: solver_detail::choleskySolve of the host layer (host/dense_kernels.cc) for many systems at once, one wave per
+ * system (csrc/chol.hip).  The systems are concatenated: system k is A (n[k] x n[k], row-major, only the lower triangle is read) and b (n[k]).
+ * The arithmetic is the host's, operation for operation: column tiles of two, every inner product in dot8 order (eight interleaved partial
+ * sums combined as ((p0+p4)+(p2+p6))+((p1+p5)+(p3+p7)), then the tail in order), one multiply and one add per term, IEEE division and square
+ * root — x, L and status are the bits the host produces.
+ *   x       required; sum of n[k] doubles.  The solution, or zeros for a system with status 1.
+ *   L       optional (NULL = not transferred); the factor's lower triangle in A's layout.  Elements above the diagonal are not written, and
+ *           nothing of a system with status 1.
+ *   status  optional; 0 ok, 1 not positive definite or non-finite (a pivot d with !(d > 0) or !isfinite(d), tested in the host's order).
+ * A failed system does not affect the others.  A system's outputs are the same bits alone, in any batch, in any batch order and run after run.
+ * ICG_ERR_INVALID (the message names the system): n_systems <= 0, a NULL required pointer, n <= 0.  ICG_ERR_CAPACITY (system named): n above
+ * ICG_CHOL_MAX_N, more than 65535 systems.  After an error nothing was launched and no output was touched. */
+#define ICG_CHOL_MAX_N 512
+int icg_chol_solve_batch(icg_ctx *ctx, int n_systems, const int32_t *n, const double *A, const double *b, double *x, double *L,
+                         int32_t *status);
 
 /* ---- f3 (SURVEY.md §8 "next" row): per-observation arithmetic of GVINS::gvinsOutlierCulling (ic_gvins.cc:1035-1128) and
  * GVINS::parametersStatistic (ic_gvins.cc:930-1033).  Observation i = landmark lm_idx[i] (world position pw, n_lm x 3) seen in
