@@ -212,10 +212,12 @@ __device__ static inline int icg_xcd_chunked(int b, int n) { return (b & 7) * ((
 #endif
 static inline int icg_xcd_grid(int n) { return 8 * ((n + 7) >> 3); }
 // b / d for workgroup-index decoding without an integer division per thread: q = mulhi(b, ceil(2^32 / d)), exact for
-// b < 2^32 / d (workgroup counts are far below that)
+// b < 2^32 / d (workgroup counts are far below that).  d = 1 has no 32-bit magic (2^32 truncates to 0, and mulhi by 0 gave quotient 0 for
+// every b: a detection grid with one 60 x 64 block per ROI then decoded every block as block 0); 0 is the magic of no other divisor, so it
+// stands for "the quotient is b".  Both arguments are wave-uniform where this is used: a scalar select.
 static inline unsigned int icg_div_magic(int d) { return (unsigned int) ((0x100000000ull + (unsigned int) d - 1u) / (unsigned int) d); }
 #ifdef __HIPCC__
-__device__ static inline int icg_div_by_magic(int b, unsigned int magic) { return (int) __umulhi((unsigned int) b, magic); }
+__device__ static inline int icg_div_by_magic(int b, unsigned int magic) { return magic ? (int) __umulhi((unsigned int) b, magic) : b; }
 #endif
 
 #ifdef __HIPCC__

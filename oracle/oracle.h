@@ -72,6 +72,15 @@ int orc_good_features(const uint8_t *img, int w, int h, int stride, const uint8_
                       int rw, int rh, int max_corners, double quality, double min_dist, float *corners);
 void orc_corner_subpix(const uint8_t *img, int w, int h, int stride, int rx, int ry, int rw, int rh, int n,
                        float *corners);
+// how a corner's cornerSubPix iteration ended (orc_corner_subpix_trace)
+enum {
+    ORC_SUBPIX_EXIT_CONVERGED = 1, // |step|^2 <= eps^2
+    ORC_SUBPIX_EXIT_CAP       = 2, // 20 iterations
+    ORC_SUBPIX_EXIT_OUT       = 3, // the corner left the ROI
+    ORC_SUBPIX_EXIT_SINGULAR  = 4  // |det| <= DBL_EPSILON^2: break before the update
+};
+void orc_corner_subpix_trace(const uint8_t *img, int w, int h, int stride, int rx, int ry, int rw, int rh, int n, float *corners,
+                             int32_t *iters, int32_t *exit_kind, int32_t *reset);
 void orc_circle_halfwidths(int radius, int *hw /* radius+1 */);
 void orc_subpix_mask(float *mask121);
 int orc_detect(const uint8_t *img, int w, int h, int stride, const int *grid6, int n_mask, const float *mask_pts,

@@ -29,6 +29,77 @@ static inline int reflect101(int i, int n) {
     return i;
 }
 static inline int cv_round_f(float v) { return (int) lrintf(v); }
+
+// What one corner did in cornerSubPix (orc_corner_subpix_trace): observation only, nothing below reads it back.
+struct SubpixTrace {
+    int iters = 0, exit_kind = 0, reset = 0;
+};
+
+// cornerSubPix of ONE corner (ROI-local, in place) with the 11x11 mask of orc_subpix_mask
+static void subpix_point(const uint8_t *img, int stride, int rx, int ry, int rw, int rh, const float *mask, float *corner, SubpixTrace *tr) {
+    const int max_iters = 20;
+    const double eps    = 0.01 * 0.01;
+    float patch[13][13];
+    SubpixTrace T;
+    float cTx = corner[0], cTy = corner[1];
+    float cIx = cTx, cIy = cTy;
+    int iter   = 0;
+    double err = 0;
+    do {
+        T.iters++;
+        // getRectSubPix(src, 13x13, cI): origin = cI - 6, bilinear, replicate border inside the ROI
+        float ox = cIx - 6.f, oy = cIy - 6.f;
+        int iox = (int) floorf(ox), ioy = (int) floorf(oy);
+        float fa = ox - iox, fb = oy - ioy;
+        float w00 = (1.f - fa) * (1.f - fb), w01 = fa * (1.f - fb), w10 = (1.f - fa) * fb, w11 = fa * fb;
+        for (int i = 0; i < 13; i++)
+            for (int j = 0; j < 13; j++) {
+                int x0 = std::min(std::max(iox + j, 0), rw - 1), x1 = std::min(std::max(iox + j + 1, 0), rw - 1);
+                int y0 = std::min(std::max(ioy + i, 0), rh - 1), y1 = std::min(std::max(ioy + i + 1, 0), rh - 1);
+                float s00 = img[(size_t) (ry + y0) * stride + rx + x0], s01 = img[(size_t) (ry + y0) * stride + rx + x1];
+                float s10 = img[(size_t) (ry + y1) * stride + rx + x0], s11 = img[(size_t) (ry + y1) * stride + rx + x1];
+                patch[i][j] = s00 * w00 + s01 * w01 + s10 * w10 + s11 * w11;
+            }
+        double a = 0, b = 0, c = 0, bb1 = 0, bb2 = 0;
+        for (int i = 0; i < 11; i++) {
+            double py = i - 5;
+            for (int j = 0; j < 11; j++) {
+                double m   = mask[i * 11 + j];
+                double tgx = patch[i + 1][j + 2] - patch[i + 1][j];
+                double tgy = patch[i + 2][j + 1] - patch[i][j + 1];
+                double gxx = tgx * tgx * m;
+                double gxy = tgx * tgy * m;
+                double gyy = tgy * tgy * m;
+                double px  = j - 5;
+                a += gxx;
+                b += gxy;
+                c += gyy;
+                bb1 += gxx * px + gxy * py;
+                bb2 += gxy * px + gyy * py;
+            }
+        }
+        double det = a * c - b * b;
+        T.exit_kind = ORC_SUBPIX_EXIT_SINGULAR;
+        if (std::fabs(det) <= DBL_EPSILON * DBL_EPSILON) break;
+        double scale = 1.0 / det;
+        float c2x    = (float) (cIx + c * scale * bb1 - b * scale * bb2);
+        float c2y    = (float) (cIy - b * scale * bb1 + a * scale * bb2);
+        err          = (c2x - cIx) * (c2x - cIx) + (c2y - cIy) * (c2y - cIy);
+        cIx          = c2x;
+        cIy          = c2y;
+        T.exit_kind = ORC_SUBPIX_EXIT_OUT;
+        if (cIx < 0 || cIx >= rw || cIy < 0 || cIy >= rh) break;
+        T.exit_kind = err > eps ? ORC_SUBPIX_EXIT_CAP : ORC_SUBPIX_EXIT_CONVERGED; // (which of the two conditions below ends the loop)
+    } while (++iter < max_iters && err > eps);
+    if (std::fabs(cIx - cTx) > 5 || std::fabs(cIy - cTy) > 5) {
+        cIx = cTx;
+        cIy = cTy;
+        T.reset = 1;
+    }
+    corner[0] = cIx;
+    corner[1] = cIy;
+    if (tr) *tr = T;
+}
 } // namespace
 
 extern "C" {
@@ -202,62 +273,21 @@ void orc_corner_subpix(const uint8_t *img, int w, int h, int stride, int rx, int
     (void) h;
     float mask[121];
     orc_subpix_mask(mask);
-    const int max_iters = 20;
-    const double eps    = 0.01 * 0.01;
-    float patch[13][13];
+    for (int p = 0; p < n; p++) subpix_point(img, stride, rx, ry, rw, rh, mask, corners + 2 * p, nullptr);
+}
+
+// orc_corner_subpix (same subpix_point, byte-identical corners) plus, per corner: iterations entered, the way the iteration ended
+// (ORC_SUBPIX_EXIT_*) and whether the result was more than 5 px from the start on an axis and was reset to it.
+void orc_corner_subpix_trace(const uint8_t *img, int w, int h, int stride, int rx, int ry, int rw, int rh, int n, float *corners,
+                             int32_t *iters, int32_t *exit_kind, int32_t *reset) {
+    (void) w;
+    (void) h;
+    float mask[121];
+    orc_subpix_mask(mask);
     for (int p = 0; p < n; p++) {
-        float cTx = corners[2 * p], cTy = corners[2 * p + 1];
-        float cIx = cTx, cIy = cTy;
-        int iter   = 0;
-        double err = 0;
-        do {
-            // getRectSubPix(src, 13x13, cI): origin = cI - 6, bilinear, replicate border inside the ROI
-            float ox = cIx - 6.f, oy = cIy - 6.f;
-            int iox = (int) floorf(ox), ioy = (int) floorf(oy);
-            float fa = ox - iox, fb = oy - ioy;
-            float w00 = (1.f - fa) * (1.f - fb), w01 = fa * (1.f - fb), w10 = (1.f - fa) * fb, w11 = fa * fb;
-            for (int i = 0; i < 13; i++)
-                for (int j = 0; j < 13; j++) {
-                    int x0 = std::min(std::max(iox + j, 0), rw - 1), x1 = std::min(std::max(iox + j + 1, 0), rw - 1);
-                    int y0 = std::min(std::max(ioy + i, 0), rh - 1), y1 = std::min(std::max(ioy + i + 1, 0), rh - 1);
-                    float s00 = img[(size_t) (ry + y0) * stride + rx + x0], s01 = img[(size_t) (ry + y0) * stride + rx + x1];
-                    float s10 = img[(size_t) (ry + y1) * stride + rx + x0], s11 = img[(size_t) (ry + y1) * stride + rx + x1];
-                    patch[i][j] = s00 * w00 + s01 * w01 + s10 * w10 + s11 * w11;
-                }
-            double a = 0, b = 0, c = 0, bb1 = 0, bb2 = 0;
-            for (int i = 0; i < 11; i++) {
-                double py = i - 5;
-                for (int j = 0; j < 11; j++) {
-                    double m   = mask[i * 11 + j];
-                    double tgx = patch[i + 1][j + 2] - patch[i + 1][j];
-                    double tgy = patch[i + 2][j + 1] - patch[i][j + 1];
-                    double gxx = tgx * tgx * m;
-                    double gxy = tgx * tgy * m;
-                    double gyy = tgy * tgy * m;
-                    double px  = j - 5;
-                    a += gxx;
-                    b += gxy;
-                    c += gyy;
-                    bb1 += gxx * px + gxy * py;
-                    bb2 += gxy * px + gyy * py;
-                }
-            }
-            double det = a * c - b * b;
-            if (std::fabs(det) <= DBL_EPSILON * DBL_EPSILON) break;
-            double scale = 1.0 / det;
-            float c2x    = (float) (cIx + c * scale * bb1 - b * scale * bb2);
-            float c2y    = (float) (cIy - b * scale * bb1 + a * scale * bb2);
-            err          = (c2x - cIx) * (c2x - cIx) + (c2y - cIy) * (c2y - cIy);
-            cIx          = c2x;
-            cIy          = c2y;
-            if (cIx < 0 || cIx >= rw || cIy < 0 || cIy >= rh) break;
-        } while (++iter < max_iters && err > eps);
-        if (std::fabs(cIx - cTx) > 5 || std::fabs(cIy - cTy) > 5) {
-            cIx = cTx;
-            cIy = cTy;
-        }
-        corners[2 * p]     = cIx;
-        corners[2 * p + 1] = cIy;
+        SubpixTrace T;
+        subpix_point(img, stride, rx, ry, rw, rh, mask, corners + 2 * p, &T);
+        iters[p] = T.iters, exit_kind[p] = T.exit_kind, reset[p] = T.reset;
     }
 }
 

@@ -196,6 +196,19 @@ class Oracle:
         self.lib.orc_corner_subpix(_p(img), w, h, w, rx, ry, rw, rh, c.shape[0], _p(c))
         return c
 
+    SUBPIX_EXITS = {"converged": 1, "cap": 2, "out": 3, "singular": 4}  # oracle.h ORC_SUBPIX_EXIT_*
+
+    def corner_subpix_trace(self, img, roi, corners):
+        """corner_subpix plus, per corner: iterations entered, exit kind (SUBPIX_EXITS) and whether the 5-px reset fired"""
+        img = _u8(img)
+        h, w = img.shape
+        rx, ry, rw, rh = roi
+        c = _f32(corners).reshape(-1, 2).copy()
+        n = c.shape[0]
+        iters, kind, reset = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self.lib.orc_corner_subpix_trace(_p(img), w, h, w, rx, ry, rw, rh, n, _p(c), _p(iters), _p(kind), _p(reset))
+        return c, iters, kind, reset
+
     def subpix_mask(self):
         m = np.zeros(121, np.float32)
         self.lib.orc_subpix_mask(_p(m))
