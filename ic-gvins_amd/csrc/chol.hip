@@ -1,5 +1,5 @@
 // The reduced camera solve on the device: solver_detail::choleskySolve (host/dense_kernels.cc) for many systems at once, one WAVE per
-// system — icg_chol_solve_batch, and the solve step of icg_reproj_solve_windows (reproj.hip).
+// system — icg_chol_solve_batch, and the solve step of icg_reproj_solve_windows (reproj_schur.hip).
 //
 // The host solve is fixed-order arithmetic: column tiles of two, every element one subtraction of a dot8-ordered inner product of two row
 // prefixes (eight interleaved partial sums combined as ((p0+p4)+(p2+p6))+((p1+p5)+(p3+p7)), then the tail in order), the second column of a
@@ -198,19 +198,6 @@ __global__ __launch_bounds__(64 * CHOL_MAX_WAVES) void k_chol_solve(int n_items,
     if (p.status && lane == 0) p.status[w] = 0;
 }
 
-size_t chol_lds_limit(icg_ctx *ctx) {
-    static std::atomic<int> per_dev[16];
-    const int dev = ctx->cfg.device & 15;
-    int v         = per_dev[dev].load(std::memory_order_relaxed);
-    if (v == 0) {
-        int optin = 0;
-        if (hipDeviceGetAttribute(&optin, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->cfg.device) != hipSuccess || optin <= 0) optin = 64 * 1024;
-        v = optin;
-        per_dev[dev].store(v, std::memory_order_relaxed);
-    }
-    return (size_t) v;
-}
-
 int chol_cu_count(icg_ctx *ctx) {
     static std::atomic<int> per_dev[16];
     const int dev = ctx->cfg.device & 15;
@@ -225,7 +212,7 @@ int chol_cu_count(icg_ctx *ctx) {
 } // namespace
 
 int icg_chol_plan_build(icg_ctx *ctx, std::vector<icg_chol_desc> &desc, icg_chol_plan &plan) {
-    const size_t n = desc.size(), limit = chol_lds_limit(ctx);
+    const size_t n = desc.size(), limit = icg_lds_limit(ctx); // (k_chol_solve has no static LDS)
     plan.items.resize(n);
     plan.n_lds = plan.n_glob = 0;
     size_t stride = 0, scratch = 0;
@@ -251,28 +238,15 @@ int icg_chol_plan_build(icg_ctx *ctx, std::vector<icg_chol_desc> &desc, icg_chol
     const int fit  = stride ? (int) std::min<size_t>(CHOL_MAX_WAVES, limit / (stride * sizeof(double))) : 1;
     const int want = (plan.n_lds + chol_cu_count(ctx) - 1) / chol_cu_count(ctx);
     plan.wpg       = std::max(1, std::min(fit, want));
-    if (scratch * sizeof(double) > ctx->chol_scratch_cap) {
-        ICG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_chol_scratch) (void) hipFree(ctx->d_chol_scratch);
-        ctx->d_chol_scratch   = nullptr;
-        ctx->chol_scratch_cap = 0;
-        ICG_HIP(ctx, hipMalloc((void **) &ctx->d_chol_scratch, scratch * sizeof(double)));
-        ctx->chol_scratch_cap = scratch * sizeof(double);
-    }
-    return ICG_OK;
+    return icg_grow(ctx, (void **) &ctx->d_chol_scratch, &ctx->chol_scratch_cap, scratch * sizeof(double), scratch * sizeof(double));
 }
 
 int icg_chol_enqueue(icg_ctx *ctx, const icg_chol_plan &plan, const icg_chol_desc *d_desc, const int32_t *d_items, icg_chol_ptrs p) {
     p.scratch = ctx->d_chol_scratch;
     if (plan.n_lds > 0) {
         const size_t lds = (size_t) plan.wpg * plan.lds_stride * sizeof(double);
-        static std::atomic<size_t> granted[16];
-        const int dev = ctx->cfg.device & 15;
-        if (lds > 48 * 1024 && granted[dev].load(std::memory_order_relaxed) < lds) {
-            const size_t lim = chol_lds_limit(ctx);
-            ICG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_chol_solve<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lim));
-            granted[dev].store(lim, std::memory_order_relaxed);
-        }
+        static icg_lds_grant granted;
+        if (int rc = icg_allow_lds(ctx, reinterpret_cast<const void *>(k_chol_solve<true>), lds, icg_lds_limit(ctx), granted)) return rc;
         icg_prof_scope ps(ctx, "chol_solve_lds");
         hipLaunchKernelGGL(k_chol_solve<true>, dim3((unsigned) ((plan.n_lds + plan.wpg - 1) / plan.wpg)), dim3(64 * plan.wpg), lds, ctx->stream, plan.n_lds,
                            plan.wpg, plan.lds_stride, d_items, d_desc, p);

@@ -1,4 +1,5 @@
 // Context, memory arenas and per-kernel HIP-event profiling for libicgvins_hip.so.
+#include <algorithm>
 #include <cstdarg>
 
 #include <sys/prctl.h>
@@ -148,18 +149,12 @@ extern "C" void icg_ctx_destroy(icg_ctx *ctx) {
     if (ctx->stream) (void) hipStreamSynchronize(ctx->stream);
     for (auto e : ctx->ev_pool) (void) hipEventDestroy(e);
     if (ctx->ev_wait) (void) hipEventDestroy(ctx->ev_wait);
-    void *dev[] = {ctx->d_frames, ctx->d_raw,     ctx->d_bgr,  ctx->d_lut,      ctx->d_histmean,
-                   ctx->d_roi_max, ctx->d_cand, ctx->d_cand_cnt, ctx->d_arena,    ctx->d_obs,
-                   ctx->d_fidx,   ctx->d_rJ,      ctx->d_params,   ctx->d_sys,
-                   ctx->d_fwin,   ctx->d_lmwin,   ctx->marg.d_J,   ctx->marg.d_e0,  ctx->marg.d_x0,
-                   ctx->marg.d_meta, ctx->d_lin_scratch, ctx->d_red_S, ctx->d_red_H, ctx->d_chol_scratch};
+    // the front-end's fixed and lazily allocated buffers and the arena; the back-end's buffers all come from icg_grow
+    void *dev[] = {ctx->d_frames, ctx->d_raw, ctx->d_bgr, ctx->d_lut, ctx->d_histmean, ctx->d_roi_max, ctx->d_cand, ctx->d_cand_cnt, ctx->d_arena};
     for (void *p : dev)
         if (p) (void) hipFree(p);
-    for (icg_partition *pt : {&ctx->part_1, &ctx->part_w}) {
-        if (pt->plan.d_buf) (void) hipFree(pt->plan.d_buf);
-        if (pt->plan.d_part) (void) hipFree(pt->plan.d_part);
-    }
-
+    for (void **p : ctx->grown)
+        if (*p) (void) hipFree(*p);
     if (ctx->h_arena) (void) hipHostFree(ctx->h_arena);
     if (ctx->h_fstage) (void) hipHostFree(ctx->h_fstage);
     if (ctx->stream) (void) hipStreamDestroy(ctx->stream);
@@ -183,6 +178,42 @@ extern "C" int icg_set_camera(icg_ctx *ctx, const icg_camera *cam) {
 }
 
 extern "C" int icg_pyramid_levels(const icg_ctx *ctx) { return ctx ? ctx->n_levels : 0; }
+
+// ---- growable device buffers, large LDS --------------------------------------------------------------------
+int icg_grow(icg_ctx *ctx, void **p, size_t *cap, size_t want, size_t alloc, bool *replaced) {
+    if (want <= *cap) return 0;
+    ICG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (*p) (void) hipFree(*p);
+    *p   = nullptr;
+    *cap = 0;
+    if (replaced) *replaced = true;
+    if (std::find(ctx->grown.begin(), ctx->grown.end(), p) == ctx->grown.end()) ctx->grown.push_back(p);
+    ICG_HIP(ctx, hipMalloc(p, alloc));
+    *cap = alloc;
+    return 0;
+}
+
+size_t icg_lds_limit(icg_ctx *ctx) {
+    static std::atomic<int> per_dev[16];
+    const int dev = ctx->cfg.device & 15;
+    int v         = per_dev[dev].load(std::memory_order_relaxed);
+    if (v == 0) {
+        int optin = 0;
+        if (hipDeviceGetAttribute(&optin, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->cfg.device) != hipSuccess || optin <= 0) optin = 64 * 1024;
+        v = optin;
+        per_dev[dev].store(v, std::memory_order_relaxed);
+    }
+    return (size_t) v;
+}
+
+int icg_allow_lds(icg_ctx *ctx, const void *kernel, size_t bytes, size_t limit, icg_lds_grant &granted) {
+    if (bytes <= 48 * 1024) return 0;
+    std::atomic<size_t> &g = granted.per_dev[ctx->cfg.device & 15];
+    if (g.load(std::memory_order_relaxed) >= bytes) return 0;
+    ICG_HIP(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) limit));
+    g.store(limit, std::memory_order_relaxed);
+    return 0;
+}
 
 // ---- arena -------------------------------------------------------------------------------------------------
 int icg_arena_reserve(icg_ctx *ctx, size_t bytes) {

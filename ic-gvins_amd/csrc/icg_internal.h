@@ -3,6 +3,7 @@
 #include <utility>
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -27,7 +28,7 @@ struct icg_prof_rec {
     double total_ms = 0;
 };
 
-// Deterministic assembly plan of a partition of the resident reprojection factors (reproj.hip).  The order in which every sum of the
+// Deterministic assembly plan of a partition of the resident reprojection factors (reproj_asm.hip).  The order in which every sum of the
 // normal equations is formed is a function of the window's own factor list only — not of launch geometry, batch composition or timing:
 //   runs    factors of a window grouped by their ordered (reference pose, observer pose) pair, list order kept inside a run; every run
 //           is reduced by one wave into the 20 x 20 block [Ji Jj Je Jtd -r]^T [Ji Jj Je Jtd -r] (k_asm_runs);
@@ -38,7 +39,7 @@ struct icg_asm_plan {
     std::vector<int32_t> pose_off;  // W+1 into pose_glob
     std::vector<int32_t> pose_glob; // local pose number -> global pose index (ascending inside a window)
     char *d_buf = nullptr;          // one allocation for the five index arrays below
-    size_t buf_cap = 0;
+    size_t buf_cap = 0;             // bytes
     int32_t *d_perm = nullptr;      // n: factor indices, run-major
     int32_t *d_runs = nullptr;      // n_runs x 4: first (into d_perm), count, local_i | local_j << 16, window
     int32_t *d_run_off = nullptr;   // W+1
@@ -46,7 +47,7 @@ struct icg_asm_plan {
     int32_t *d_lrec = nullptr;      // n x 4: factor, local_i, local_j, 0 — landmark-major
     int32_t *d_lm_foff = nullptr;   // n_lm+1: landmark l owns d_lrec[lm_foff[l] .. lm_foff[l+1])
     double *d_part = nullptr;       // n_runs x 220: the runs' blocks (upper-triangular 2 x 2 tiles)
-    size_t part_cap = 0;            // doubles
+    size_t part_cap = 0;            // bytes
 };
 struct icg_partition {
     int W = 0;
@@ -113,8 +114,6 @@ struct icg_ctx {
     int n_factors_resident = 0, factors_cap = 0;
     double *d_rJ = nullptr; // n x 48 packed results (r2 + J46)
     int rJ_valid = 0, rJ_has_jac = 0;
-    double *d_params = nullptr; // poses, ext, invdepth, td (device copy)
-    size_t params_cap = 0;
     int last_n_poses = 0, last_n_lm = 0;
     double last_huber = 0.0;
     std::vector<int32_t> h_fidx; // host copy of d_fidx (3 x n): the assembly plans below are derived from it
@@ -127,18 +126,18 @@ struct icg_ctx {
     // factors are one window" behind the single-window entry points — both run through the SAME kernels, so a window's sums are formed in
     // the same order alone and inside a batch.  d_sys holds the systems of whichever partition was assembled last.
     double *d_sys = nullptr;
-    size_t sys_cap = 0; // doubles
+    size_t sys_cap = 0; // bytes
     double sys_min_diag = 0.0, sys_max_diag = 0.0;
     icg_partition part_1, part_w;
     int32_t *d_fwin = nullptr;  // window of every factor (factors_cap), icg_reproj_eval_windows
     int32_t *d_lmwin = nullptr; // window of every landmark
-    int lmwin_cap = 0;
+    size_t lmwin_cap = 0; // bytes
 
     icg_marg_set marg;
     // M3 (marg_linearize.hip): per-window working memory of icg_marg_linearize_batch for the windows that do not fit in LDS; grows on demand
     double *d_lin_scratch = nullptr;
     size_t lin_scratch_cap = 0; // bytes
-    // Reduced camera solve (chol.hip, reproj.hip): the W x P x P reduced systems icg_reproj_schur_windows_resident leaves on the device, every
+    // Reduced camera solve (chol.hip, reproj_schur.hip): the W x P x P reduced systems icg_reproj_schur_windows_resident leaves on the device, every
     // window's host-factor part (packed lower triangle, one slot of P (P + 1) / 2 doubles per window, kept until it is replaced) and the
     // working memory of the systems that do not fit in LDS; all grow on demand
     double *d_red_S = nullptr, *d_red_H = nullptr, *d_chol_scratch = nullptr;
@@ -146,6 +145,9 @@ struct icg_ctx {
     int red_P = 0, red_W = 0;                                  // shape of the resident reduced systems; red_W = 0: none
     bool red_S_valid = false;                                  // d_red_S holds the reduction of what d_sys holds now (the back-substitution reads d_sys)
     std::vector<int32_t> red_H_cols;                           // per window: columns of the resident host part, 0 = none
+
+    // every buffer icg_grow has allocated for this context: what icg_ctx_destroy frees besides the fixed allocations
+    std::vector<void **> grown;
 
     icg_camera cam{};
     bool has_cam = false;
@@ -169,6 +171,26 @@ int icg_hip_check(icg_ctx *ctx, hipError_t e, const char *what);
         int _rc = icg_hip_check((ctx), (call), #call);                                                                 \
         if (_rc) return _rc;                                                                                           \
     } while (0)
+
+// growable device buffers ---------------------------------------------------------------------------------
+// The one way a resident device buffer grows.  *cap >= want (bytes): nothing happens.  Otherwise: wait for the context's stream (work in
+// flight may still use the old buffer), free it, allocate `alloc` >= want bytes — the caller's slack policy: how often a buffer is replaced
+// is part of the speed — and remember the buffer for icg_ctx_destroy.  The contents are not kept.  *replaced (if given) is set as soon as
+// the old buffer is gone, also when the allocation then fails (*p = nullptr, *cap = 0): whatever the caller's state says about the old
+// contents has to be invalidated on it, before the return code is looked at.
+int icg_grow(icg_ctx *ctx, void **p, size_t *cap, size_t want, size_t alloc, bool *replaced = nullptr);
+
+// large LDS --------------------------------------------------------------------------------------------------
+// gfx950 has 160 KiB of LDS per CU and one workgroup may own all of it (MI355X_MICROARCH.md, "LDS"); a launch with more dynamic LDS than the
+// default needs the function attribute.  The limit comes from the device the context runs on, so a build for a part with less LDS takes the
+// global-memory path or reports ICG_ERR_CAPACITY instead of failing at launch.  A user whose kernel has static LDS words of its own subtracts
+// them from the limit it plans with and passes on.
+struct icg_lds_grant {
+    std::atomic<size_t> per_dev[16]; // what the kernel was last allowed on each device; one static table per kernel
+};
+size_t icg_lds_limit(icg_ctx *ctx);
+// before a launch of `kernel` with `bytes` of dynamic LDS: above 48 KiB, raises the kernel's attribute to `limit` (once per device)
+int icg_allow_lds(icg_ctx *ctx, const void *kernel, size_t bytes, size_t limit, icg_lds_grant &granted);
 
 // arena ---------------------------------------------------------------------------------------------------
 int icg_arena_reserve(icg_ctx *ctx, size_t bytes); // ensure capacity (may reallocate; only when arena_off == 0)

@@ -132,16 +132,6 @@ __global__ __launch_bounds__(MARG_THREADS) void k_marg_jacobians(int n_windows, 
     }
 }
 
-int marg_grow(icg_ctx *ctx, void **p, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return 0;
-    if (*p) (void) hipFree(*p);
-    *p   = nullptr;
-    *cap = 0;
-    ICG_HIP(ctx, hipMalloc(p, bytes));
-    *cap = bytes;
-    return 0;
-}
-
 marg_dev marg_view(const icg_marg_set &s) {
     const size_t n = (size_t) s.n, B = (size_t) s.n_blocks;
     marg_dev m;
@@ -218,10 +208,11 @@ extern "C" int icg_marg_prior_set(icg_ctx *ctx, int n_windows, const int32_t *r,
 
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     int rc;
-    if ((rc = marg_grow(ctx, (void **) &s.d_J, &s.J_cap, sizeof(double) * 2 * (size_t) tj))) return rc;
-    if ((rc = marg_grow(ctx, (void **) &s.d_e0, &s.e0_cap, sizeof(double) * (size_t) te))) return rc;
-    if ((rc = marg_grow(ctx, (void **) &s.d_x0, &s.x0_cap, sizeof(double) * (size_t) (tx > 0 ? tx : 1)))) return rc;
-    if ((rc = marg_grow(ctx, (void **) &s.d_meta, &s.meta_cap, s.h_meta.size() * 8))) return rc;
+    const size_t b_J = sizeof(double) * 2 * (size_t) tj, b_e0 = sizeof(double) * (size_t) te, b_x0 = sizeof(double) * (size_t) (tx > 0 ? tx : 1);
+    if ((rc = icg_grow(ctx, (void **) &s.d_J, &s.J_cap, b_J, b_J))) return rc;
+    if ((rc = icg_grow(ctx, (void **) &s.d_e0, &s.e0_cap, b_e0, b_e0))) return rc;
+    if ((rc = icg_grow(ctx, (void **) &s.d_x0, &s.x0_cap, b_x0, b_x0))) return rc;
+    if ((rc = icg_grow(ctx, (void **) &s.d_meta, &s.meta_cap, s.h_meta.size() * 8, s.h_meta.size() * 8))) return rc;
     icg_call c(ctx);
     if ((rc = c.reserve(sizeof(double) * (size_t) (tj + te + tx) + s.h_meta.size() * 8 + 8 * 256))) return rc;
     const double *a_J    = c.in(J0, (size_t) tj);

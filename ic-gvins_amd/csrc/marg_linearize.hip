@@ -15,7 +15,6 @@
 // are the same alone and in any batch.
 #include "icg_internal.h"
 
-#include <atomic>
 #include <cmath>
 
 #define LIN_THREADS 256
@@ -385,19 +384,6 @@ __global__ __launch_bounds__(LIN_THREADS) void k_marg_linearize(int n_items, con
     }
 }
 
-size_t lin_lds_limit(icg_ctx *ctx) {
-    static std::atomic<int> per_dev[16];
-    const int dev = ctx->cfg.device & 15;
-    int v         = per_dev[dev].load(std::memory_order_relaxed);
-    if (v == 0) {
-        int optin = 0;
-        if (hipDeviceGetAttribute(&optin, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->cfg.device) != hipSuccess || optin <= 0) optin = 64 * 1024;
-        v = optin;
-        per_dev[dev].store(v, std::memory_order_relaxed);
-    }
-    return (size_t) v - 256; // (- the kernel's static words)
-}
-
 } // namespace
 
 extern "C" int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
@@ -415,7 +401,7 @@ extern "C" int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32
         if (P[w] > ICG_MARG_LIN_MAX_P)
             return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_linearize_batch: window %zu: P = %d is above the limit %d", w, P[w], ICG_MARG_LIN_MAX_P);
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    const size_t lds_limit = lin_lds_limit(ctx);
+    const size_t lds_limit = icg_lds_limit(ctx) - 256; // (- the kernel's static words)
     std::vector<lin_desc> desc(n);
     std::vector<int32_t> items(n); // the windows that run in LDS first, then the others
     size_t th = 0, tb = 0, tr = 0, trr = 0, ts = 0, lds_fast = 0, lds_slow = 0;
@@ -439,22 +425,13 @@ extern "C" int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32
         int a = 0, z = n_fast;
         for (size_t w = 0; w < n; w++) items[(size_t) (fast[w] ? a++ : z++)] = (int32_t) w;
     }
-    if (ts * sizeof(double) > ctx->lin_scratch_cap) {
-        if (ctx->d_lin_scratch) (void) hipFree(ctx->d_lin_scratch);
-        ctx->d_lin_scratch   = nullptr;
-        ctx->lin_scratch_cap = 0;
-        ICG_HIP(ctx, hipMalloc((void **) &ctx->d_lin_scratch, ts * sizeof(double)));
-        ctx->lin_scratch_cap = ts * sizeof(double);
-    }
-    static std::atomic<size_t> granted[16];
-    const int dev = ctx->cfg.device & 15;
-    if (lds_fast > 48 * 1024 && granted[dev].load(std::memory_order_relaxed) < lds_fast) {
-        ICG_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_marg_linearize<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_limit));
-        granted[dev].store(lds_limit, std::memory_order_relaxed);
-    }
+    int rc = icg_grow(ctx, (void **) &ctx->d_lin_scratch, &ctx->lin_scratch_cap, ts * sizeof(double), ts * sizeof(double));
+    if (rc) return rc;
+    static icg_lds_grant granted;
+    if ((rc = icg_allow_lds(ctx, reinterpret_cast<const void *>(k_marg_linearize<true>), lds_fast, lds_limit, granted))) return rc;
     icg_call c(ctx);
     const size_t out_doubles = 2 * trr + 3 * tr + n;
-    int rc = c.reserve(sizeof(double) * (th + tb + out_doubles) + n * (sizeof(lin_desc) + 8) + 16 * 256);
+    rc = c.reserve(sizeof(double) * (th + tb + out_doubles) + n * (sizeof(lin_desc) + 8) + 16 * 256);
     if (rc) return rc;
     const double *d_H       = c.in(H, th);
     const double *d_b       = c.in(b, tb);

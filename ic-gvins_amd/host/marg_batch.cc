@@ -256,7 +256,7 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     auto t2 = now();
 
     // ---- 3: assembly + landmark elimination of every planned window, one launch sequence; the landmark diagonals --------------------------
-    // (csrc/reproj.hip, schur_impl: reduced systems of up to WindowSolverBatch::kMaxCameraColumns columns; a wider window takes the dense
+    // (csrc/reproj_schur.hip, schur_impl: reduced systems of up to WindowSolverBatch::kMaxCameraColumns columns; a wider window takes the dense
     // path on its own)
     const int max_camera_columns = WindowSolverBatch::kMaxCameraColumns;
     for (size_t w = 0; w < NW; w++) {

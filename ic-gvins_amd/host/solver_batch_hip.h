@@ -23,7 +23,7 @@ class WindowSolverBatch {
 public:
     typedef WindowSolver::Options Options;
     typedef WindowSolver::Summary Summary;
-    // Widest reduced system of the device path: the assembly (csrc/reproj.hip k_asm_*) keeps no per-window tile in LDS any more — rounds 2-5
+    // Widest reduced system of the device path: the assembly (csrc/reproj_asm.hip k_asm_*) keeps no per-window tile in LDS any more — rounds 2-5
     // held the camera block there (82, then 138 columns).  The reduction kernel k_schur_reduce_w stages its landmark rows of 4 ceil(P/4)
     // doubles in SCH_PRE * 256 = 3 072 elements per pass (at least one row up to P = 3 072) and keeps two entries of s per thread (t and
     // t + 256): P <= 512.  A window that can exceed it is the caller's to solve on the host.

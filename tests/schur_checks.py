@@ -92,7 +92,7 @@ def check_schur(ctx, oracle, tol=1e-9):
 
 
 def check_schur_any_factor_order(ctx, oracle, tol=1e-9, refuses_same_block=True):
-    """The assembly makes no assumption about the factor list (csrc/reproj.hip, asm_plan_build sorts by pose pair and by landmark itself):
+    """The assembly makes no assumption about the factor list (csrc/reproj_asm.hip, asm_plan_build sorts by pose pair and by landmark itself):
     a shuffled list, a landmark whose factors name DIFFERENT reference poses, the same (landmark, observer) pair twice, poses used as
     reference by some factors and as observer by others — all equal the numpy assembly of the same list; and a commit through the staged
     upload equals the classic upload bit for bit.  A factor whose reference and observer are the same block is refused."""

@@ -1,5 +1,5 @@
 """Inputs for the Schur-path edge suite (tests/schur_edge_checks.py, test_schur_edges_cpu.py, test_gpu_schur_edges.py): windows that sit on the
-structural edges of the second half of csrc/reproj.hip — the fixed-order assembly (k_asm_runs, k_asm_camera, k_asm_landmarks), the landmark
+structural edges of csrc/reproj_asm.hip and csrc/reproj_schur.hip — the fixed-order assembly (k_asm_runs, k_asm_camera, k_asm_landmarks), the landmark
 elimination (k_schur_inv_w, k_schur_reduce_w, k_schur_backsub_w, k_terms_reduce_w), k_reproj_cost_w, k_lm_diag_w and k_reproj_chi2.
 
 A case is one window: a factor list (ordered pose pairs, duplicates and run lengths are explicit), a column layout (col_pose, col_ext, col_td, P)

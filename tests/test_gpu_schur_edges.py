@@ -1,4 +1,4 @@
-"""The Schur-path edge suite on the HIP library: the second half of csrc/reproj.hip (k_asm_runs, k_asm_camera, k_asm_landmarks, k_schur_inv_w,
+"""The Schur-path edge suite on the HIP library: csrc/reproj_asm.hip and csrc/reproj_schur.hip (k_asm_runs, k_asm_camera, k_asm_landmarks, k_schur_inv_w,
 k_schur_reduce_w, k_schur_backsub_w, k_terms_reduce_w, k_reproj_cost_w, k_lm_diag_w, k_reproj_chi2) on the cases of schur_edge_data.py, every
 output cell against the long-double reference of schur_edge_checks.py within (n_t + 8) 2^-53 A.  test_schur_edges_cpu.py proves that the cases
 reach their edges and that the reference is right.  Device only, bit for bit: S from the copying call is symmetric, a call repeated gives the

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 def test_marginalization_batch_equals_per_window():
     """... and EVERY window of every batch against the oracle (orc_reproj + orc_marg on that window's parameters), bit-equal to the per-window
-    path: the device assembly forms each sum in an order fixed by the window's factor list (csrc/reproj.hip, k_asm_*)"""
+    path: the device assembly forms each sum in an order fixed by the window's factor list (csrc/reproj_asm.hip, k_asm_*)"""
     import oracle_lib
     bu.check_marginalization_batch(C.CDLL(H.HOST_LIB), oracle_lib.load(), bitwise=True)
 
