@@ -333,7 +333,7 @@ extern "C" int icg_triangulate(icg_ctx *ctx, int n, const int32_t *T0_idx, const
 
 // ---------------------------------------------------------------------------------------------------------
 // F6: cv::findFundamentalMat(FM_RANSAC) of one point set per workgroup, the WHOLE run in one launch:
-//   round:  wave 0 draws up to FM_HPW subsets from the set's cv::RNG (getSubset + checkSubset with a collinearity test per lane,
+//   round:  wave 0 draws up to fm_round_size(round) <= FM_HPW subsets from the set's cv::RNG (getSubset + checkSubset with a collinearity test per lane,
 //           RNG-consuming redraws) -> LDS
 //           wave 0, a lane per hypothesis: seven-point solve (a strictly serial FP64 chain per hypothesis whose rotations cannot be spread over
 //           lanes without changing its rounding; different hypotheses advance in different lanes) -> models in LDS
@@ -388,7 +388,11 @@ __device__ bool dev_get_subset_wave(unsigned long long &rng, int n, const float2
     return false;
 }
 
-#define FM_HPW 32 // hypotheses per round
+#define FM_HPW 32 // hypotheses per round at most (the LDS tables)
+// Hypotheses of round r: 8, 8, 16, then FM_HPW.  Every round is also capped by niters - iter.  After the forward-backward LK cull most sets
+// consume fewer than ten hypotheses (FM_HIST below; profiles/r08_ransac_rounds_subpix_groups.txt), so a first round of FM_HPW drew, solved
+// and scored mostly discarded ones; the solve is one serial FP64 chain per round whatever the round's size, so the rounds grow quickly.
+__device__ __forceinline__ int fm_round_size(int r) { return r < 2 ? 8 : r == 2 ? 16 : FM_HPW; }
 #define FMS_MAX_WORDS 16 // 64-bit inlier words per model in LDS: the tracker's form takes sets of up to 1024 points
 
 // symmetric epipolar distance of one correspondence under F (double, compared in float): the inlier test of the scoring and of the mask
@@ -408,6 +412,18 @@ __device__ __forceinline__ bool fm_inlier(double F0, double F1, double F2, doubl
     float e   = (float) fmax(d1 * d1 * s1, d2 * d2 * s2);
     return e <= thresh2;
 }
+
+#if defined(FM_HIST)
+// profiling build (EXTRA_HIPFLAGS=-DFM_HIST, off in the product): consumed hypotheses (iter at exit) of every set since the library was
+// loaded, printed when the process ends
+__device__ unsigned long long g_fm_hist[1024];
+static void fm_hist_dump() {
+    static unsigned long long h[1024];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_fm_hist), sizeof h) != hipSuccess) return;
+    for (int k = 0; k < 1024; k++)
+        if (h[k]) fprintf(stderr, "[fm hist] consumed %4d sets %10llu\n", k, h[k]);
+}
+#endif
 
 // LARGE = false (the tracker's form): the inlier words of every model of a round and the best mask live in LDS (sets up to 64 * FMS_MAX_WORDS
 // points), denom_tab is the shared table of fm_denom_table (row n = the set size).  LARGE = true (stand-alone calls with a set above that):
@@ -439,10 +455,10 @@ __global__ __launch_bounds__(256, 1) void k_fm_ransac_sets(int n_sets, int seg_c
     if (t == 0) iter_sh = 0, niters_sh = 1000, max_good_sh = 0;
     if (!LARGE && t < FMS_MAX_WORDS) best_sh[t] = 0;
     __syncthreads();
-    for (;;) {
+    for (int round = 0;; round++) {
         if (wave == 0) { // all 64 lanes: see dev_get_subset_wave
             const int it0 = iter_sh;
-            int nh        = min(FM_HPW, niters_sh - it0);
+            int nh        = min(fm_round_size(round), niters_sh - it0);
             for (int h = 0; h < nh; h++) {
                 if (!dev_get_subset_wave(rng, n, p1, p2, idx_sh[h], lane)) {
                     // ptsetreg.cpp run(): no valid subset -> the iterations end here (nothing found if this was the first one)
@@ -456,9 +472,11 @@ __global__ __launch_bounds__(256, 1) void k_fm_ransac_sets(int n_sets, int seg_c
         __syncthreads();
         const int nh = nh_sh;
         if (nh <= 0) break;
-        if (wave == 0 && lane < nh) {
+        // FM_HPW lanes solve whatever nh is: lanes nh..FM_HPW-1 repeat hypothesis lane % nh into their own, unread slots of Fm / n_sh (the
+        // FP64 chain issued with 16 or fewer active lanes takes ~5x as long; copies take their original's branches, so nothing diverges more)
+        if (wave == 0 && lane < FM_HPW) {
             int nm = 0;
-            seven_point_solve(idx_sh[lane], p1, p2, Fm[lane], &nm);
+            seven_point_solve(idx_sh[lane % nh], p1, p2, Fm[lane], &nm);
             n_sh[lane] = nm;
         }
         __syncthreads();
@@ -512,6 +530,9 @@ __global__ __launch_bounds__(256, 1) void k_fm_ransac_sets(int n_sets, int seg_c
         __syncthreads();
         if (stop) break;
     }
+#if defined(FM_HIST)
+    if (t == 0) atomicAdd(&g_fm_hist[min(iter_sh, 1023)], 1ull);
+#endif
     const bool found = max_good_sh > 0;
     if constexpr (LARGE) {
         const double *F = best_F;
@@ -559,6 +580,10 @@ static int fm_ransac_launch(icg_ctx *ctx, int n_sets, int seg_cap, const int32_t
     if (conf < DBL_EPSILON || conf > 1 - DBL_EPSILON) conf = 0.99;
     double p         = std::min(std::max(conf, 0.), 1.);
     const double num = std::log(std::max(1. - p, DBL_MIN)); // the numerator of RANSACUpdateNumIters
+#if defined(FM_HIST)
+    static std::once_flag hist_once;
+    std::call_once(hist_once, [] { atexit(fm_hist_dump); });
+#endif
     icg_prof_scope ps(ctx, "fm_ransac_sets");
     hipLaunchKernelGGL(k_fm_ransac_sets<LARGE>, dim3(n_sets), dim3(256), 0, ctx->stream, n_sets, seg_cap, d_count, d_p1, d_p2, (float) (thresh * thresh), num,
                        d_tab, tab_n, d_mask);
