@@ -1,0 +1,315 @@
+// f1: the host-factor part of every window's reduced camera system, built where icg_reproj_solve_windows reads it.
+//
+// A window's host-evaluated factors (preintegration, the marginalization prior, pose / mix / GNSS priors) arrive as blocks: nr residuals,
+// a dense row-major nr x nf Jacobian of the factor's free local columns and the nf columns they occupy in the window's system.  The packed
+// lower triangle of sum_blocks J^T J goes into the window's slot of d_red_H, -J^T r and diag(J^T J) go back to the host; the values are the
+// ones solver_detail::hostFactors forms (host/solver_detail.h), bit for bit: every block value is a sum over the residual index in ascending
+// order from +0.0 (one multiply, one add per term: this file is compiled with -ffp-contract=off like the rest), and every cell receives the
+// block values in block order.  One thread owns a cell through all blocks, so nothing is added atomically and a window's bits do not depend
+// on the batch it is built in.  The Jacobians stay on the device (icg_hp_kept): a block whose Jacobian did not change crosses the link as
+// its residuals only.
+#include "reproj_internal.h"
+
+#define HP_THREADS 256
+#define HP_CPT 16     // cells of the packed triangle per thread: a workgroup owns HP_THREADS * HP_CPT consecutive cells of one window
+#define HP_STAGE 4096 // doubles of a block's Jacobian rows staged in LDS per pass (32 KB)
+#define HP_MAX_KC 64  // rows per pass at the most
+
+struct hp_win {
+    int32_t w, Pw, blk_begin, blk_end, slot, pad; // blocks [blk_begin, blk_end) of the call's block list; slot: index among the rebuilt windows
+    int64_t H_off, out_off;                       // the window's slot in d_red_H and its triangle in part_out
+};
+struct hp_blk {
+    int64_t J_off; // into the kept Jacobians
+    int32_t r_off, cols_off, nr, nf;
+};
+struct hp_copy {
+    int64_t src, dst, n;
+};
+
+// the shipped Jacobians move from the staging arena to their places among the kept ones: one workgroup per shipped block
+__global__ __launch_bounds__(HP_THREADS) void k_host_part_keep(const hp_copy *cp, const double *src, double *dst) {
+    const hp_copy c = cp[blockIdx.x];
+    for (int64_t e = threadIdx.x; e < c.n; e += HP_THREADS) dst[c.dst + e] = src[c.src + e];
+}
+
+// grid (ceil(max cells / (HP_THREADS * HP_CPT)), rebuilt windows).  Thread t of workgroup g owns the cells g * 4096 + t + 256 i (i < 16) of the
+// packed triangle in registers; the window's first workgroup also owns s and diag (columns t and t + 256: P <= 512).  Per block: the column ->
+// local index map of the block in LDS, then its Jacobian rows in passes of at most HP_STAGE doubles, each cell adding J[k][x] J[k][y] for
+// the rows of the pass in ascending k.
+__global__ __launch_bounds__(HP_THREADS) void k_host_part(const hp_win *wins, const hp_blk *blks, const int32_t *cols, const double *J, const double *r, int P,
+                                                          double *H, double *s_out, double *diag_out, double *part_out) {
+    __shared__ double Js[HP_STAGE];
+    __shared__ double rs[HP_MAX_KC];
+    __shared__ int16_t map[512];
+    const hp_win W    = wins[blockIdx.y];
+    const int n_cells = (W.Pw * (W.Pw + 1)) >> 1, base = blockIdx.x * (HP_THREADS * HP_CPT);
+    if (base >= n_cells) return; // (a narrower window than the widest of the call: uniform over the workgroup)
+    const int t      = threadIdx.x;
+    const bool first = blockIdx.x == 0;
+    int ab[HP_CPT]; // row | column << 16 of cell i, -1 beyond the triangle
+    double acc[HP_CPT];
+#pragma unroll
+    for (int i = 0; i < HP_CPT; i++) {
+        const int c = base + t + HP_THREADS * i;
+        int a       = (int) ((sqrtf(8.0f * (float) c + 1.0f) - 1.0f) * 0.5f);
+        while ((a + 1) * (a + 2) / 2 <= c) a++;
+        while (a * (a + 1) / 2 > c) a--;
+        ab[i]  = c < n_cells ? (a | (c - a * (a + 1) / 2) << 16) : -1;
+        acc[i] = 0.0;
+    }
+    double s[2] = {0.0, 0.0}, dg[2] = {0.0, 0.0};
+    for (int b = W.blk_begin; b < W.blk_end; b++) {
+        const hp_blk B = blks[b];
+        const int nf   = B.nf;
+        __syncthreads(); // (the previous block's map and rows have been read)
+        for (int c = t; c < W.Pw; c += HP_THREADS) map[c] = -1;
+        __syncthreads();
+        for (int x = t; x < nf; x += HP_THREADS) map[cols[B.cols_off + x]] = (int16_t) x;
+        __syncthreads();
+        int xy[HP_CPT]; // local indices x | y << 16 of the cells the block holds, -1 for the others
+        double T[HP_CPT];
+        bool any = false;
+#pragma unroll
+        for (int i = 0; i < HP_CPT; i++) {
+            const int x = ab[i] >= 0 ? map[ab[i] & 0xffff] : -1, y = ab[i] >= 0 ? map[ab[i] >> 16] : -1;
+            xy[i]       = x >= 0 && y >= 0 ? (x | y << 16) : -1;
+            any |= xy[i] >= 0;
+            T[i] = 0.0;
+        }
+        int sx[2];
+        double g[2] = {0.0, 0.0}, d[2] = {0.0, 0.0};
+#pragma unroll
+        for (int k = 0; k < 2; k++) sx[k] = first && t + HP_THREADS * k < W.Pw ? map[t + HP_THREADS * k] : -1;
+        const int KC    = min(HP_MAX_KC, HP_STAGE / nf); // nf <= 512: at least 8 rows
+        const double *Jb = J + B.J_off;
+        for (int k0 = 0; k0 < B.nr; k0 += KC) {
+            const int kc = min(KC, B.nr - k0);
+            __syncthreads();
+            for (int e = t; e < kc * nf; e += HP_THREADS) Js[e] = Jb[(size_t) k0 * nf + e];
+            if (t < kc) rs[t] = r[B.r_off + k0 + t];
+            __syncthreads();
+            if (any) {
+                for (int kk = 0; kk < kc; kk++) {
+                    const double *row = Js + kk * nf;
+#pragma unroll
+                    for (int i = 0; i < HP_CPT; i++)
+                        if (xy[i] >= 0) T[i] += row[xy[i] & 0xffff] * row[xy[i] >> 16];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 2; k++)
+                if (sx[k] >= 0)
+                    for (int kk = 0; kk < kc; kk++) {
+                        const double jx = Js[kk * nf + sx[k]];
+                        g[k] += jx * rs[kk];
+                        d[k] += jx * jx;
+                    }
+        }
+#pragma unroll
+        for (int i = 0; i < HP_CPT; i++)
+            if (xy[i] >= 0) acc[i] += T[i];
+#pragma unroll
+        for (int k = 0; k < 2; k++)
+            if (sx[k] >= 0) s[k] -= g[k], dg[k] += d[k];
+    }
+#pragma unroll
+    for (int i = 0; i < HP_CPT; i++) {
+        const int c = base + t + HP_THREADS * i;
+        if (c >= n_cells) continue;
+        H[W.H_off + c] = acc[i];
+        if (part_out) part_out[W.out_off + c] = acc[i];
+    }
+    if (first) {
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const int c = t + HP_THREADS * k;
+            if (c < P) s_out[(size_t) W.slot * P + c] = s[k], diag_out[(size_t) W.slot * P + c] = dg[k]; // (zeros from Pw up to P)
+        }
+    }
+}
+
+extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
+                                           const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s,
+                                           double *host_diag, double *part_out) {
+    if (!ctx) return ICG_ERR_INVALID;
+    const char *me = "icg_reproj_host_parts_build";
+    icg_partition &pt = ctx->part_w;
+    const int W       = pt.W;
+    if (W <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: no window partition: call icg_reproj_set_windows first", me);
+    if (P <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: P = %d", me, P);
+    if (P > 512) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: reduced systems of more than 512 camera columns are not supported (%d)", me, P);
+    if (W > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %d windows in one call (at most 65535)", me, W);
+    if (ctx->red_W != 0 && ctx->red_P != P) return icg_fail(ctx, ICG_ERR_INVALID, "%s: P = %d, the resident reduced systems have %d columns", me, P, ctx->red_P);
+    if (!Pw || !rebuild || !blk_off || !host_s || !host_diag) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", me);
+    if (blk_off[0] != 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window 0: blk_off[0] = %d", me, blk_off[0]);
+    for (int w = 0; w < W; w++)
+        if (blk_off[w + 1] < blk_off[w]) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d: blk_off decreases (%d after %d)", me, w, blk_off[w + 1], blk_off[w]);
+    const int nb = blk_off[W];
+    if (nb > 0 && (!nr || !nf || !cols || !jac_off || !r)) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", me);
+    // the slots of d_red_H follow the P of the resident reduced systems, or of the last call here while there are none: host parts (and
+    // kept Jacobians) of another shape, or of a buffer that is about to be replaced, are dropped before this call's are built
+    const size_t slot    = (size_t) P * (P + 1) / 2, H_bytes = sizeof(double) * (size_t) W * slot;
+    icg_hp_kept &hp      = ctx->hp;
+    const bool drop_all  = ctx->red_H_cols.size() != (size_t) W || (ctx->red_W == 0 && hp.H_P != P) || ctx->red_H_cap < H_bytes;
+    const bool have_kept = !drop_all && hp.win.size() == (size_t) W;
+    // ---- validation: nothing is changed before it is through --------------------------------------------------------------------------------
+    std::vector<int32_t> r_off((size_t) nb + 1, 0), c_off((size_t) nb + 1, 0), seen((size_t) P, -1);
+    size_t ship_doubles = 0, n_ship = 0, out_cells = 0;
+    int n_rebuilt = 0, max_cells = 0;
+    for (int w = 0; w < W; w++) {
+        const std::vector<icg_hp_block> *kept = have_kept ? &hp.win[(size_t) w] : nullptr;
+        const int cnt                         = blk_off[w + 1] - blk_off[w];
+        if (rebuild[w] && (Pw[w] <= 0 || Pw[w] > P)) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d: Pw = %d (1 .. %d)", me, w, Pw[w], P);
+        bool any_keep = false;
+        for (int b = blk_off[w]; b < blk_off[w + 1]; b++) {
+            const int p = b - blk_off[w];
+            if (nr[b] <= 0 || nf[b] <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d x %d", me, w, p, nr[b], nf[b]);
+            if (nr[b] > ICG_HOST_PART_MAX_NR)
+                return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: window %d, block %d: %d residuals (at most %d)", me, w, p, nr[b], ICG_HOST_PART_MAX_NR);
+            if ((int64_t) r_off[(size_t) b] + nr[b] > INT32_MAX || (int64_t) c_off[(size_t) b] + nf[b] > INT32_MAX)
+                return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: window %d, block %d: more than 2^31 residuals or columns in one call", me, w, p);
+            r_off[(size_t) b + 1] = r_off[(size_t) b] + nr[b], c_off[(size_t) b + 1] = c_off[(size_t) b] + nf[b];
+            if (!rebuild[w]) continue;
+            if (nf[b] > Pw[w]) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d columns in a system of %d", me, w, p, nf[b], Pw[w]);
+            for (int x = 0; x < nf[b]; x++) {
+                const int c = cols[(size_t) c_off[(size_t) b] + x];
+                if (c < 0 || c >= Pw[w]) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: column %d outside the system (%d)", me, w, p, c, Pw[w]);
+                if (seen[(size_t) c] == b) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: column %d twice", me, w, p, c);
+                seen[(size_t) c] = b;
+            }
+            if (jac_off[b] >= 0) {
+                if (!J) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a Jacobian offset without J", me, w, p);
+                ship_doubles += (size_t) nr[b] * nf[b], n_ship++;
+            } else if (jac_off[b] == -1) {
+                any_keep = true;
+                if (!kept || (size_t) p >= kept->size()) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no kept Jacobian", me, w, p);
+                const icg_hp_block &k = (*kept)[(size_t) p];
+                if (k.nr != nr[b] || k.nf != nf[b])
+                    return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: the kept Jacobian is %d x %d, not %d x %d", me, w, p, k.nr, k.nf, nr[b], nf[b]);
+            } else {
+                return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: jac_off = %lld", me, w, p, (long long) jac_off[b]);
+            }
+        }
+        if (!rebuild[w]) continue;
+        if (any_keep && (size_t) cnt != kept->size())
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d: %d blocks, %zu kept, and a block keeps its Jacobian", me, w, cnt, kept->size());
+        n_rebuilt++;
+        max_cells = std::max(max_cells, Pw[w] * (Pw[w] + 1) / 2);
+        out_cells += (size_t) Pw[w] * (Pw[w] + 1) / 2;
+    }
+    if (n_rebuilt == 0) return ICG_OK;
+    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    // ---- the kept Jacobians after this call: dense, window after window -----------------------------------------------------------------------
+    std::vector<std::vector<icg_hp_block>> next((size_t) W);
+    int64_t total = 0;
+    bool same     = have_kept;
+    for (int w = 0; w < W; w++) {
+        std::vector<icg_hp_block> &nw = next[(size_t) w];
+        if (rebuild[w])
+            for (int b = blk_off[w]; b < blk_off[w + 1]; b++) nw.push_back({0, nr[b], nf[b]});
+        else if (have_kept)
+            nw = hp.win[(size_t) w];
+        same = same && nw.size() == hp.win[(size_t) w].size();
+        for (size_t p = 0; p < nw.size(); p++) {
+            if (same) same = hp.win[(size_t) w][p].off == total && hp.win[(size_t) w][p].nr == nw[p].nr && hp.win[(size_t) w][p].nf == nw[p].nf;
+            nw[p].off = total;
+            total += (int64_t) nw[p].nr * nw[p].nf;
+        }
+    }
+    int rc;
+    if (drop_all) {
+        icg_red_drop_host_parts(ctx, (size_t) W);
+        if ((rc = icg_red_ensure_capacity(ctx, &ctx->d_red_H, &ctx->red_H_cap, H_bytes))) return rc;
+    }
+    const int dst = same ? hp.cur : 1 - hp.cur;
+    if (!same) {
+        // what stays moves into the other buffer, in runs that are contiguous on both sides
+        const size_t bytes = sizeof(double) * (size_t) std::max<int64_t>(total, 1);
+        if ((rc = icg_grow(ctx, (void **) &hp.d_J[dst], &hp.cap[dst], bytes, bytes + bytes / 4))) return rc;
+        int64_t run_src = 0, run_dst = 0, run_n = 0;
+        auto flush      = [&]() -> int {
+            if (run_n) ICG_HIP(ctx, hipMemcpyAsync(hp.d_J[dst] + run_dst, hp.d_J[hp.cur] + run_src, sizeof(double) * (size_t) run_n, hipMemcpyDeviceToDevice, ctx->stream));
+            run_n = 0;
+            return 0;
+        };
+        for (int w = 0; w < W && have_kept; w++)
+            for (size_t p = 0; p < next[(size_t) w].size(); p++) {
+                if (rebuild[w] && jac_off[(size_t) blk_off[w] + p] >= 0) continue;
+                const icg_hp_block &o = hp.win[(size_t) w][p], &n = next[(size_t) w][p];
+                const int64_t len     = (int64_t) n.nr * n.nf;
+                if (run_n && o.off == run_src + run_n && n.off == run_dst + run_n) {
+                    run_n += len;
+                    continue;
+                }
+                if ((rc = flush())) return rc;
+                run_src = o.off, run_dst = n.off, run_n = len;
+            }
+        if ((rc = flush())) return rc;
+    }
+    // ---- staging ------------------------------------------------------------------------------------------------------------------------------
+    std::vector<hp_win> wins;
+    std::vector<hp_blk> blks((size_t) nb);
+    std::vector<hp_copy> copies;
+    {
+        int64_t out_off = 0, src = 0;
+        for (int w = 0; w < W; w++) {
+            if (!rebuild[w]) continue;
+            wins.push_back({w, Pw[w], blk_off[w], blk_off[w + 1], (int32_t) wins.size(), 0, (int64_t) ((size_t) w * slot), out_off});
+            out_off += (int64_t) Pw[w] * (Pw[w] + 1) / 2;
+            for (int b = blk_off[w]; b < blk_off[w + 1]; b++) {
+                const icg_hp_block &n = next[(size_t) w][(size_t) (b - blk_off[w])];
+                blks[(size_t) b]      = {n.off, r_off[(size_t) b], c_off[(size_t) b], nr[b], nf[b]};
+                if (jac_off[b] >= 0) copies.push_back({src, n.off, (int64_t) nr[b] * nf[b]}), src += (int64_t) nr[b] * nf[b];
+            }
+        }
+    }
+    const size_t n_r = (size_t) r_off[(size_t) nb], n_c = (size_t) c_off[(size_t) nb];
+    icg_call c(ctx);
+    if ((rc = c.reserve(sizeof(hp_win) * wins.size() + sizeof(hp_blk) * blks.size() + sizeof(hp_copy) * copies.size() + sizeof(int32_t) * n_c +
+                        sizeof(double) * (n_r + ship_doubles + 2 * (size_t) n_rebuilt * P + out_cells) + 16 * 256)))
+        return rc;
+    const hp_win *d_wins  = c.in(wins.data(), wins.size());
+    const hp_blk *d_blks  = c.in(blks.data(), blks.size());
+    const hp_copy *d_cp   = c.in(copies.data(), copies.size());
+    const int32_t *d_cols = c.in(cols, n_c);
+    const double *d_r     = c.in(r, n_r);
+    const double *d_Jnew  = nullptr;
+    if (ship_doubles) { // the shipped Jacobians, block after block
+        const size_t off = icg_arena_alloc(ctx, sizeof(double) * ship_doubles);
+        double *h        = icg_h<double>(ctx, off);
+        for (int w = 0; w < W; w++)
+            for (int b = blk_off[w]; rebuild[w] && b < blk_off[w + 1]; b++)
+                if (jac_off[b] >= 0) memcpy(h, J + jac_off[b], sizeof(double) * (size_t) nr[b] * nf[b]), h += (size_t) nr[b] * nf[b];
+        c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * ship_doubles);
+        d_Jnew = icg_d<double>(ctx, off);
+    }
+    if ((rc = c.seal())) return rc;
+    // s and diag of the rebuilt windows only: the rows of the others are not the call's to write
+    double *d_s = c.out((double *) nullptr, (size_t) n_rebuilt * P), *d_dg = c.out((double *) nullptr, (size_t) n_rebuilt * P);
+    for (const hp_win &hw : wins) {
+        c.outs.push_back({(void *) (host_s + (size_t) hw.w * P), (size_t) (reinterpret_cast<char *>(d_s + (size_t) hw.slot * P) - ctx->d_arena), sizeof(double) * (size_t) P, false});
+        c.outs.push_back({(void *) (host_diag + (size_t) hw.w * P), (size_t) (reinterpret_cast<char *>(d_dg + (size_t) hw.slot * P) - ctx->d_arena), sizeof(double) * (size_t) P, false});
+    }
+    double *d_po = part_out ? c.out(part_out, out_cells) : nullptr;
+    ICG_LAUNCH_GUARD(c);
+    // from here on the rebuilt windows' parts and the kept Jacobians are being replaced: a failure below leaves those windows without a part
+    // and no window with a kept Jacobian
+    for (int w = 0; w < W; w++)
+        if (rebuild[w]) ctx->red_H_cols[(size_t) w] = 0;
+    hp.win.clear();
+    {
+        icg_prof_scope ps(ctx, "host_part");
+        if (!copies.empty())
+            hipLaunchKernelGGL(k_host_part_keep, dim3((unsigned) copies.size()), dim3(HP_THREADS), 0, ctx->stream, d_cp, d_Jnew, hp.d_J[dst]);
+        hipLaunchKernelGGL(k_host_part, dim3((unsigned) ((max_cells + HP_THREADS * HP_CPT - 1) / (HP_THREADS * HP_CPT)), (unsigned) n_rebuilt), dim3(HP_THREADS), 0,
+                           ctx->stream, d_wins, d_blks, d_cols, (const double *) hp.d_J[dst], d_r, P, ctx->d_red_H, d_s, d_dg, d_po);
+    }
+    ICG_HIP(ctx, hipGetLastError());
+    if ((rc = c.finish())) return rc;
+    hp.cur = dst, hp.H_P = P;
+    hp.win.swap(next);
+    for (int w = 0; w < W; w++)
+        if (rebuild[w]) ctx->red_H_cols[(size_t) w] = Pw[w];
+    return ICG_OK;
+}

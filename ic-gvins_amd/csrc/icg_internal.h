@@ -71,6 +71,21 @@ struct icg_marg_set {
     std::vector<int64_t> h_meta;
 };
 
+// Host-factor parts built on the device (host_part.hip): the Jacobian of every factor block of every window, kept densely (window after
+// window, block after block) in one of two device buffers until a rebuild replaces it; a call that changes the layout moves what stays
+// into the other buffer.  win is empty while nothing is kept.
+struct icg_hp_block {
+    int64_t off; // into d_J[cur], in doubles
+    int32_t nr, nf;
+};
+struct icg_hp_kept {
+    std::vector<std::vector<icg_hp_block>> win; // per window of the partition: its kept blocks, by position in the window's block list
+    double *d_J[2] = {nullptr, nullptr};
+    size_t cap[2] = {0, 0}; // bytes
+    int cur = 0;
+    int H_P = 0; // the P whose slots of P (P + 1) / 2 doubles the host parts in d_red_H are laid out by
+};
+
 struct icg_ctx {
     icg_ctx_config cfg{};
     hipStream_t stream = nullptr;
@@ -145,6 +160,7 @@ struct icg_ctx {
     int red_P = 0, red_W = 0;                                  // shape of the resident reduced systems; red_W = 0: none
     bool red_S_valid = false;                                  // d_red_S holds the reduction of what d_sys holds now (the back-substitution reads d_sys)
     std::vector<int32_t> red_H_cols;                           // per window: columns of the resident host part, 0 = none
+    icg_hp_kept hp;                                            // what icg_reproj_host_parts_build keeps to rebuild them (dropped with them)
 
     // every buffer icg_grow has allocated for this context: what icg_ctx_destroy frees besides the fixed allocations
     std::vector<void **> grown;
@@ -163,6 +179,12 @@ struct icg_ctx {
     std::vector<pending> prof_pending;
     std::map<std::string, icg_prof_rec> prof;
 };
+
+// every window's resident host part is dropped (n_windows entries of "none"), and with them the Jacobians kept to rebuild them
+static inline void icg_red_drop_host_parts(icg_ctx *ctx, size_t n_windows) {
+    ctx->red_H_cols.assign(n_windows, 0);
+    ctx->hp.win.clear();
+}
 
 int icg_fail(icg_ctx *ctx, int code, const char *fmt, ...);
 int icg_hip_check(icg_ctx *ctx, hipError_t e, const char *what);

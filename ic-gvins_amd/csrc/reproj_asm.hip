@@ -488,7 +488,7 @@ extern "C" int icg_reproj_set_windows(icg_ctx *ctx, int n_windows, const int32_t
     pt.lm_off.assign(lm_off, lm_off + n_windows + 1);
     pt.sys_valid = 0;
     ctx->red_W   = 0; // (the resident reduced systems and host parts belonged to the partition that is replaced)
-    ctx->red_H_cols.clear();
+    icg_red_drop_host_parts(ctx, 0);
     const auto t0 = std::chrono::steady_clock::now();
     int rc       = asm_plan_build(ctx, pt);
     if (rc) pt.W = 0;

@@ -41,3 +41,8 @@ int icg_asm_columns_build(icg_ctx *ctx, const icg_partition &pt, int P, const in
 // enqueues k_asm_runs, k_asm_camera, k_asm_landmarks for the windows of wd with reassemble != 0: their (H | b) in ctx->d_sys from the resident r, J
 void icg_asm_enqueue(icg_ctx *ctx, const icg_partition &pt, int P, int NBmax, const win_desc *d_wd, const int16_t *d_owner, const int32_t *d_blocks,
                      const uint8_t *d_active);
+
+// ---- reproj_schur.hip -----------------------------------------------------------------------------------------------------------------------
+// a device buffer of the reduced camera solve (d_red_S, d_red_H) for `bytes`, grown without keeping its contents: a replaced buffer drops the
+// resident reduced systems and every window's host part
+int icg_red_ensure_capacity(icg_ctx *ctx, double **buf, size_t *cap, size_t bytes);

@@ -228,12 +228,12 @@ static int ensure_sys_capacity(icg_ctx *ctx, size_t doubles) {
 // a device buffer of the reduced camera solve (d_red_S, d_red_H): grown without keeping its contents
 // (growing d_red_S alone would leave the host parts in d_red_H intact; they are dropped all the same, one rule for both buffers — the host
 // layer ships a window's part again with its next re-linearization, and a caller that solves before that gets A = S + dd, as documented)
-static int ensure_red_capacity(icg_ctx *ctx, double **buf, size_t *cap, size_t bytes) {
+int icg_red_ensure_capacity(icg_ctx *ctx, double **buf, size_t *cap, size_t bytes) {
     bool replaced = false;
     const int rc  = icg_grow(ctx, (void **) buf, cap, bytes, bytes, &replaced);
     if (replaced) {
         ctx->red_W = 0;
-        ctx->red_H_cols.assign(ctx->red_H_cols.size(), 0);
+        icg_red_drop_host_parts(ctx, ctx->red_H_cols.size());
     }
     return rc;
 }
@@ -287,10 +287,10 @@ static int schur_impl(icg_ctx *ctx, icg_partition &pt, int P, const int32_t *col
         // the third destination: the lower tiles stay in a buffer of the context for icg_reproj_solve_windows
         if (ctx->red_W != W || ctx->red_P != P) {
             ctx->red_W = 0;
-            ctx->red_H_cols.assign((size_t) W, 0); // (host parts of another shape are not this partition's)
+            icg_red_drop_host_parts(ctx, (size_t) W); // (host parts of another shape are not this partition's)
         }
-        if ((rc = ensure_red_capacity(ctx, &ctx->d_red_S, &ctx->red_S_cap, sizeof(double) * (size_t) W * P * P))) return rc;
-        if ((rc = ensure_red_capacity(ctx, &ctx->d_red_H, &ctx->red_H_cap, sizeof(double) * (size_t) W * ((size_t) P * (P + 1) / 2)))) return rc;
+        if ((rc = icg_red_ensure_capacity(ctx, &ctx->d_red_S, &ctx->red_S_cap, sizeof(double) * (size_t) W * P * P))) return rc;
+        if ((rc = icg_red_ensure_capacity(ctx, &ctx->d_red_H, &ctx->red_H_cap, sizeof(double) * (size_t) W * ((size_t) P * (P + 1) / 2)))) return rc;
     }
     icg_partition &other = &pt == &ctx->part_1 ? ctx->part_w : ctx->part_1;
     other.sys_valid      = 0; // (d_sys is shared: whatever the other partition left there is overwritten)
@@ -341,7 +341,7 @@ static int schur_impl(icg_ctx *ctx, icg_partition &pt, int P, const int32_t *col
     }
     pt.sys_P = P, pt.sys_valid = 1;
     ctx->sys_min_diag = min_diag, ctx->sys_max_diag = max_diag;
-    if (S_resident) ctx->red_W = W, ctx->red_P = P, ctx->red_S_valid = true;
+    if (S_resident) ctx->red_W = W, ctx->red_P = P, ctx->red_S_valid = true, ctx->hp.H_P = P;
     return ICG_OK;
 }
 

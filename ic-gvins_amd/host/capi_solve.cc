@@ -14,6 +14,12 @@ using namespace icg;
 
 extern "C" {
 
+int icgh_backend_solve_batch_parts(int W, const int32_t *fac_off, const int32_t *pose_off, const int32_t *lm_off, const double *obs_soa,
+                                   const int32_t *idx_i, const int32_t *idx_j, const int32_t *idx_lm, double *poses, double *ext, double *invdepth,
+                                   double *td, const double *prior_poses, double prior_weight, double huber, int ext_constant, int td_constant,
+                                   int iters1, int iters2, double chi2, double *summary8, double *solve_ms, char *err, int errlen,
+                                   int reduced_solve_mode, int host_part_mode); // capi_solve_parts.cc
+
 // ---- f1: the window optimization flow of GVINS::gvinsOptimization (ic_gvins.cc:1130-1239) on WindowSolver -----------------
 // Reprojection factors from flat arrays (as icgh_backend_reproj) + one PosePriorFactor per pose (weight prior_weight, target
 // prior_poses: fixes the gauge like the reference's marginalization prior / GNSS factors do).  Two solves with the chi-square
@@ -79,6 +85,7 @@ int icgh_backend_solve(int n, const double *obs_soa, const int32_t *idx_i, const
 // concatenated window-major: window w owns factors [fac_off[w], fac_off[w+1]) (obs_soa is 15 x n_total, idx_* LOCAL to the window),
 // poses [pose_off[w], ..), inverse depths [lm_off[w], ..); ext is W x 7, td has W entries.  summary8 is W x 8 as in icgh_backend_solve.
 // Returns the wall time of the two solves + culling in ms through *solve_ms.
+// (the body is that of icgh_backend_solve_batch_parts, capi_solve_parts.cc, with the host parts formed on the host)
 // reduced_solve_mode: 0 = the reduced camera solves on the host pool, 1 = on the device (WindowSolverBatch::setDeviceReducedSolve; the same
 // bits).  Without the device entry points in the build mode 1 computes nothing: -4 and "icg_reproj_solve_windows is not in this build".
 int icgh_backend_solve_batch_mode(int W, const int32_t *fac_off, const int32_t *pose_off, const int32_t *lm_off, const double *obs_soa,
@@ -86,69 +93,12 @@ int icgh_backend_solve_batch_mode(int W, const int32_t *fac_off, const int32_t *
                                   double *td, const double *prior_poses, double prior_weight, double huber, int ext_constant, int td_constant,
                                   int iters1, int iters2, double chi2, double *summary8, double *solve_ms, char *err, int errlen,
                                   int reduced_solve_mode) {
-    return guarded(err, errlen, [&] {
-        if (reduced_solve_mode != 0 && reduced_solve_mode != 1) {
-            set_err(err, errlen, "reduced_solve_mode must be 0 (host) or 1 (device)");
-            return -1;
-        }
-        if (reduced_solve_mode == 1 && !WindowSolverBatch::deviceReducedSolveAvailable()) {
-            set_err(err, errlen, "icg_reproj_solve_windows is not in this build");
-            return -4;
-        }
-        const int n = fac_off[W];
-        vector<std::unique_ptr<ReprojectionFactor>> factors;
-        WindowSolverBatch solver(0, huber);
-        solver.setDeviceReducedSolve(reduced_solve_mode == 1);
-        for (int w = 0; w < W; w++) {
-            const int ww = solver.addWindow();
-            double *P = poses + 7 * (size_t) pose_off[w], *E = ext + 7 * (size_t) w, *D = invdepth + lm_off[w], *TD = td + w;
-            const int K = pose_off[w + 1] - pose_off[w], L = lm_off[w + 1] - lm_off[w];
-            for (int k = 0; k < K; k++) solver.addParameterBlock(ww, P + 7 * (size_t) k, 7, true);
-            solver.addParameterBlock(ww, E, 7, true);
-            for (int l = 0; l < L; l++) solver.addParameterBlock(ww, D + l, 1);
-            solver.addParameterBlock(ww, TD, 1);
-            if (ext_constant) solver.setParameterBlockConstant(ww, E);
-            if (td_constant) solver.setParameterBlockConstant(ww, TD);
-            for (int f = fac_off[w]; f < fac_off[w + 1]; f++) {
-                factors.push_back(reproj_factor_from_soa(obs_soa, n, f));
-                solver.addReprojectionFactor(ww, factors.back().get(), P + 7 * (size_t) idx_i[f], P + 7 * (size_t) idx_j[f], E, D + idx_lm[f], TD);
-            }
-            for (int k = 0; k < K; k++)
-                solver.addResidualBlock(ww, std::make_shared<PosePriorFactor>(prior_poses + 7 * ((size_t) pose_off[w] + k), prior_weight), nullptr,
-                                        {P + 7 * (size_t) k});
-        }
-        if (!solver.prepare()) {
-            set_err(err, errlen, solver.error().c_str());
-            return -5;
-        }
-        auto t0 = std::chrono::steady_clock::now();
-        WindowSolverBatch::Options opt;
-        vector<WindowSolverBatch::Summary> s1, s2;
-        opt.max_num_iterations = iters1;
-        if (!solver.solve(opt, &s1)) {
-            set_err(err, errlen, solver.error().c_str());
-            return -2;
-        }
-        vector<int> removed((size_t) W, 0);
-        if (chi2 > 0) {
-            removed                = solver.removeReprojectionFactorsByChi2(chi2);
-            opt.max_num_iterations = iters2;
-            if (!solver.solve(opt, &s2)) {
-                set_err(err, errlen, solver.error().c_str());
-                return -4;
-            }
-        }
-        if (solve_ms) *solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        for (int w = 0; w < W; w++) {
-            double *o = summary8 + 8 * (size_t) w;
-            o[0] = s1[(size_t) w].initial_cost, o[1] = s1[(size_t) w].final_cost, o[2] = s1[(size_t) w].final_cost;
-            o[3] = s1[(size_t) w].num_successful_steps, o[4] = s1[(size_t) w].num_unsuccessful_steps, o[5] = o[6] = o[7] = 0;
-            if (chi2 > 0)
-                o[2] = s2[(size_t) w].final_cost, o[5] = s2[(size_t) w].num_successful_steps, o[6] = s2[(size_t) w].num_unsuccessful_steps,
-                o[7] = removed[(size_t) w];
-        }
-        return 0;
-    });
+    if (reduced_solve_mode != 0 && reduced_solve_mode != 1) {
+        set_err(err, errlen, "reduced_solve_mode must be 0 (host) or 1 (device)");
+        return -1;
+    }
+    return icgh_backend_solve_batch_parts(W, fac_off, pose_off, lm_off, obs_soa, idx_i, idx_j, idx_lm, poses, ext, invdepth, td, prior_poses, prior_weight,
+                                          huber, ext_constant, td_constant, iters1, iters2, chi2, summary8, solve_ms, err, errlen, reduced_solve_mode, 0);
 }
 
 int icgh_backend_solve_batch(int W, const int32_t *fac_off, const int32_t *pose_off, const int32_t *lm_off, const double *obs_soa, const int32_t *idx_i,
@@ -224,30 +174,6 @@ double icgh_backend_solve_throughput(int n, const double *obs_soa, const int32_t
         return sec;
     });
 }
-
-} // extern "C"
-
-namespace {
-// r = w (x - x0) on one 9-vector block (velocity, gyroscope bias, accelerometer bias): stands in for the part of the
-// marginalization prior that anchors the first state's velocity and biases
-class MixPriorFactor : public ceres::SizedCostFunction<9, 9> {
-public:
-    MixPriorFactor(const double *x0, double weight) : w_(weight) { memcpy(x0_, x0, sizeof x0_); }
-    bool Evaluate(const double *const *parameters, double *residuals, double **jacobians) const override {
-        for (int k = 0; k < 9; k++) residuals[k] = w_ * (parameters[0][k] - x0_[k]);
-        if (jacobians && jacobians[0]) {
-            memset(jacobians[0], 0, sizeof(double) * 81);
-            for (int k = 0; k < 9; k++) jacobians[0][k * 9 + k] = w_;
-        }
-        return true;
-    }
-
-private:
-    double x0_[9], w_;
-};
-} // namespace
-
-extern "C" {
 
 // f1 with the factor mix of the real window: K preintegration factors (device P1 + host P2) between K+1 states, reprojection
 // factors on the same pose blocks (device), a pose prior and a velocity/bias prior on state 0 (what the marginalization prior

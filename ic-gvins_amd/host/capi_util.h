@@ -172,4 +172,21 @@ public:
 private:
     double x0_, w_;
 };
+// r = w (x - x0) on one 9-vector block (velocity, gyroscope bias, accelerometer bias): stands in for the part of the
+// marginalization prior that anchors the first state's velocity and biases
+class MixPriorFactor : public ceres::SizedCostFunction<9, 9> {
+public:
+    MixPriorFactor(const double *x0, double weight) : w_(weight) { memcpy(x0_, x0, sizeof x0_); }
+    bool Evaluate(const double *const *parameters, double *residuals, double **jacobians) const override {
+        for (int k = 0; k < 9; k++) residuals[k] = w_ * (parameters[0][k] - x0_[k]);
+        if (jacobians && jacobians[0]) {
+            memset(jacobians[0], 0, sizeof(double) * 81);
+            for (int k = 0; k < 9; k++) jacobians[0][k * 9 + k] = w_;
+        }
+        return true;
+    }
+
+private:
+    double x0_[9], w_;
+};
 } // namespace

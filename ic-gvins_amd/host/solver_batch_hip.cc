@@ -18,6 +18,7 @@
 #pragma weak icg_chol_solve_batch
 #pragma weak icg_reproj_schur_windows_resident
 #pragma weak icg_reproj_solve_windows
+#pragma weak icg_reproj_host_parts_build
 
 namespace icg {
 
@@ -26,6 +27,8 @@ using solver_detail::choleskySolve;
 bool WindowSolverBatch::deviceReducedSolveAvailable() {
     return &icg_chol_solve_batch != nullptr && &icg_reproj_schur_windows_resident != nullptr && &icg_reproj_solve_windows != nullptr;
 }
+
+bool WindowSolverBatch::deviceHostPartAvailable() { return &icg_reproj_host_parts_build != nullptr; }
 
 // The per-window host phases of an LM step (host factors, reduced solves, trial bookkeeping) take tens of microseconds per window: they
 // run on a persistent pool — spawning threads per phase (four phases per step) cost more than the phases themselves.
@@ -165,6 +168,18 @@ bool WindowSolverBatch::layout() {
         for (size_t k = 0; k < W.poses.size(); k++) col_pose_[(size_t) W.pose_begin + k] = W.problem.column(W.poses[k]);
         if (W.ext) col_ext_[w] = W.problem.column(W.ext);
         if (W.td) col_td_[w] = W.problem.column(W.td);
+        if (!device_host_part_) return;
+        // the blocks of the window's host part: their shapes and columns follow from the problem, not from an evaluation
+        W.host_blocks.clear(), W.host_cols.clear();
+        std::vector<int> cols;
+        for (size_t id = 0; id < W.problem.residuals.size(); id++) {
+            const solver_detail::Residual &R = W.problem.residuals[id];
+            if (R.removed) continue;
+            solver_detail::hostBlockColumns(W.problem, R, cols);
+            if (cols.empty()) continue;
+            W.host_blocks.push_back({(int) id, R.cost->num_residuals(), (int) cols.size(), 0, 0, 0});
+            W.host_cols.insert(W.host_cols.end(), cols.begin(), cols.end());
+        }
     });
     for (size_t w = 0; w < windows_.size(); w++) {
         if (!errs[w].empty()) {
@@ -172,6 +187,20 @@ bool WindowSolverBatch::layout() {
             return false;
         }
         P_ = std::max(P_, windows_[w].P);
+    }
+    if (device_host_part_) {
+        hp_blk_off_.assign(1, 0), hp_nr_.clear(), hp_nf_.clear(), hp_cols_.clear();
+        hp_J_total_ = hp_r_total_ = 0;
+        for (Window &W : windows_) {
+            W.blk_begin = (int) hp_nr_.size();
+            for (Window::HostBlock &B : W.host_blocks) {
+                B.J_off = hp_J_total_, B.r_off = hp_r_total_, B.c_off = hp_cols_.size();
+                hp_J_total_ += (size_t) B.nr * B.nf, hp_r_total_ += (size_t) B.nr;
+                hp_nr_.push_back(B.nr), hp_nf_.push_back(B.nf);
+            }
+            hp_cols_.insert(hp_cols_.end(), W.host_cols.begin(), W.host_cols.end());
+            hp_blk_off_.push_back((int32_t) hp_nr_.size());
+        }
     }
     return P_ > 0;
 }
@@ -212,9 +241,17 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
     }
     const size_t NW = windows_.size();
     const int P     = P_;
-    const bool dev_solve = device_reduced_;
+    const bool dev_solve = device_reduced_, dev_part = device_host_part_;
     if (dev_solve && !deviceReducedSolveAvailable()) {
         error_ = "icg_reproj_solve_windows is not in this build";
+        return false;
+    }
+    if (dev_part && !deviceHostPartAvailable()) {
+        error_ = "icg_reproj_host_parts_build is not in this build";
+        return false;
+    }
+    if (dev_part && !dev_solve) {
+        error_ = "setDeviceHostPart(true) needs setDeviceReducedSolve(true): the host parts are built where the device solve reads them";
         return false;
     }
     // The reduced systems: their lower tiles are read where the reduction kernel writes them (pinned memory) and every window is factored by a
@@ -245,6 +282,16 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
         dev_Pw.resize(NW), dev_status.resize(NW), dev_solve_flag.resize(NW), dev_part_new.resize(NW), dev_part_off.resize(NW + 1);
         dev_dd.resize((size_t) NW * P), dev_rhs.resize((size_t) NW * P);
         for (size_t w = 0; w < NW; w++) dev_Pw[w] = windows_[w].P, windows_[w].host_part_dirty = false;
+    }
+    // device host part: the buffers of one icg_reproj_host_parts_build call (J and r of every block at the offsets of layout()), the
+    // Jacobians as each block last shipped them in this solve, and what comes back
+    std::vector<double> hp_J, hp_r, hp_shipped, hp_s, hp_diag;
+    std::vector<int64_t> hp_jac_off;
+    std::vector<uint8_t> hp_has_shipped;
+    if (dev_part) {
+        hp_J.resize(hp_J_total_), hp_shipped.resize(hp_J_total_), hp_r.assign(hp_r_total_, 0.0);
+        hp_jac_off.assign(hp_nr_.size(), 0), hp_has_shipped.assign(hp_nr_.size(), 0);
+        hp_s.assign((size_t) NW * P, 0.0), hp_diag.assign((size_t) NW * P, 0.0);
     }
     auto fail = [&](const char *what) {
         error_ = std::string(what) + ": " + icg_last_error(ctx_);
@@ -288,6 +335,35 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
             forEachWindow(NW, [&](size_t w) {
                 if (st[w].done || !st[w].relinearize) return;
                 Window &W = windows_[w];
+                if (dev_part) {
+                    // evaluate and gather only: every block's Jd and res at its place in the call buffers, the cost in residual order
+                    thread_local std::vector<int> cols;
+                    thread_local std::vector<double> none;
+                    size_t next = 0;
+                    for (size_t id = 0; id < W.problem.residuals.size(); id++) {
+                        const solver_detail::Residual &R = W.problem.residuals[id];
+                        if (R.removed) continue;
+                        const bool has = next < W.host_blocks.size() && W.host_blocks[next].residual == (int) id;
+                        double *Jd     = has ? &hp_J[W.host_blocks[next].J_off] : nullptr;
+                        if (solver_detail::gatherHostBlock(W.problem, R, &host_cost[w], cols, none, none, Jd, has ? &hp_r[W.host_blocks[next].r_off] : nullptr) < 0) {
+                            host_failed++;
+                            return;
+                        }
+                        if (!has) continue;
+                        // the same Jacobian as at the window's previous rebuild stays where it is on the device
+                        const Window::HostBlock &B = W.host_blocks[next];
+                        const size_t b = (size_t) W.blk_begin + next, bytes = sizeof(double) * (size_t) B.nr * B.nf;
+                        if (hp_has_shipped[b] && memcmp(Jd, &hp_shipped[B.J_off], bytes) == 0) {
+                            hp_jac_off[b] = -1;
+                        } else {
+                            hp_jac_off[b] = (int64_t) B.J_off;
+                            memcpy(&hp_shipped[B.J_off], Jd, bytes);
+                            hp_has_shipped[b] = 1;
+                        }
+                        next++;
+                    }
+                    return;
+                }
                 W.host_S.assign((size_t) P * P, 0.0), W.host_s.assign((size_t) P, 0.0), W.host_diag.assign((size_t) P, 0.0);
                 if (!solver_detail::hostFactors(W.problem, P, W.host_S.data(), W.host_s.data(), W.host_diag.data(), &host_cost[w])) host_failed++;
                 W.host_part_dirty = true;
@@ -301,6 +377,14 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
                 error_ = "a host cost function failed to evaluate";
                 return false;
             }
+            if (dev_part && any_lin) {
+                // the parts of the re-linearized windows, built in their slots on the device; s and diag of those windows come back
+                clk.start();
+                if (icg_reproj_host_parts_build(ctx_, P, dev_Pw.data(), reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(),
+                                                hp_jac_off.data(), hp_J.data(), hp_r.data(), hp_s.data(), hp_diag.data(), nullptr) != ICG_OK)
+                    return fail("icg_reproj_host_parts_build");
+                clk.stop(8);
+            }
             clk.start();
             forEachWindow(NW, [&](size_t w) {
                 State &T = st[w];
@@ -312,9 +396,10 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
                 // the window's reduced system is used where it arrived (S, s, diag of the batched call) plus the host factors' part: no
                 // per-window copy of the P x P block (9 MB per step at 256 windows)
                 T.s.resize((size_t) P), T.diag.resize((size_t) P);
+                const double *hs = dev_part ? &hp_s[w * P] : W.host_s.data(), *hd = dev_part ? &hp_diag[w * P] : W.host_diag.data();
                 for (int k = 0; k < P; k++) {
-                    T.s[(size_t) k]    = s[w * P + (size_t) k] + W.host_s[(size_t) k];
-                    T.diag[(size_t) k] = diag[w * P + (size_t) k] + W.host_diag[(size_t) k];
+                    T.s[(size_t) k]    = s[w * P + (size_t) k] + hs[(size_t) k];
+                    T.diag[(size_t) k] = diag[w * P + (size_t) k] + hd[(size_t) k];
                 }
                 T.relinearize = T.redamp = false;
             });
@@ -381,7 +466,8 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
             });
         }
         if (dev_any) {
-            if (icg_reproj_solve_windows(ctx_, P, dev_Pw.data(), dev_solve_flag.data(), dev_part_new.data(), dev_parts.empty() ? nullptr : dev_parts.data(),
+            if (icg_reproj_solve_windows(ctx_, P, dev_Pw.data(), dev_solve_flag.data(), dev_part ? nullptr : dev_part_new.data(),
+                                         dev_parts.empty() ? nullptr : dev_parts.data(),
                                          dev_dd.data(), dev_rhs.data(), delta_c.data(), dev_status.data(), delta_l.data(), terms.data()) != ICG_OK)
                 return fail("icg_reproj_solve_windows");
             for (size_t w = 0; w < NW; w++) {
@@ -468,8 +554,8 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
     }
     if (clk.on)
         fprintf(stderr, "[WindowSolverBatch] %zu windows: eval+jac %.2f, schur beyond the host half %.2f, host linearize (beside the device call) %.2f, reduced solves %.2f, backsub %.2f, model+apply %.2f, "
-                        "trial eval+cost %.2f, trial host %.2f ms; whole solve %.2f ms\n",
-                NW, clk.ms[0], clk.ms[1], clk.ms[2], clk.ms[3], clk.ms[4], clk.ms[5], clk.ms[6], clk.ms[7],
+                        "trial eval+cost %.2f, trial host %.2f, host parts on the device %.2f ms; whole solve %.2f ms\n",
+                NW, clk.ms[0], clk.ms[1], clk.ms[2], clk.ms[3], clk.ms[4], clk.ms[5], clk.ms[6], clk.ms[7], clk.ms[8],
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_solve).count());
     if (summaries) {
         summaries->resize(NW);

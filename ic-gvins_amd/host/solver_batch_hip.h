@@ -61,6 +61,15 @@ public:
     void setDeviceReducedSolve(bool on) { device_reduced_ = on; }
     bool deviceReducedSolve() const { return device_reduced_; }
     static bool deviceReducedSolveAvailable();
+    // With the device reduced solve: the host-factor part of every re-linearized window (J^T J of the factors the device does not evaluate) is
+    // built on the device too (icg_reproj_host_parts_build: hostFactors' bits).  The pool threads only evaluate and gather the factors'
+    // residuals and Jacobians into one call buffer; no P x P host part is formed and none is shipped.  A block whose gathered Jacobian equals
+    // (memcmp) what the window shipped at its previous rebuild of this solve goes up as its residuals only: the constant J0 of a linearized
+    // prior crosses the link once per solve.  The trial costs stay on the pool.  Off by default; needs setDeviceReducedSolve(true) (solve()
+    // fails otherwise) and the C entry, which is referenced weakly like the three above.
+    void setDeviceHostPart(bool on) { device_host_part_ = on; }
+    bool deviceHostPart() const { return device_host_part_; }
+    static bool deviceHostPartAvailable();
     bool solve(const Options &options, std::vector<Summary> *summaries);
     // removeReprojectionFactorsByChi2 (ic_gvins.cc:1269-1297) for every window; returns the number removed per window
     std::vector<int> removeReprojectionFactorsByChi2(double chi2);
@@ -81,6 +90,14 @@ private:
         int fac_begin{0}, lm_begin{0}, pose_begin{0};
         std::vector<double> host_S, host_s, host_diag;
         bool host_part_dirty{false}; // host_S was rebuilt since it was last shipped to the device (device reduced solve)
+        // device host part: the factors with a free column, in residual order, and where their pieces lie in the buffers of a call
+        struct HostBlock {
+            int residual, nr, nf;
+            size_t J_off, r_off, c_off;
+        };
+        std::vector<HostBlock> host_blocks;
+        std::vector<int32_t> host_cols; // their columns, block after block
+        int blk_begin{0};
     };
     bool finalize();
     bool layout();
@@ -99,7 +116,10 @@ private:
     std::vector<int32_t> col_pose_, col_ext_, col_td_;
     int P_{0}, n_factors_{0}, n_poses_{0}, n_lm_{0};
     bool finalized_{false};
-    bool device_reduced_{false};
+    bool device_reduced_{false}, device_host_part_{false};
+    // device host part (layout()): the block list of all windows as icg_reproj_host_parts_build takes it, and the sizes of a call's J and r
+    std::vector<int32_t> hp_blk_off_, hp_nr_, hp_nf_, hp_cols_;
+    size_t hp_J_total_{0}, hp_r_total_{0};
     std::string error_;
 };
 

@@ -246,9 +246,84 @@ struct TrustRegion {
     }
 };
 
+// the columns of a host factor inside the window's reduced system: the free local columns of its blocks, in block order (none: every block
+// of the factor is constant)
+inline void hostBlockColumns(const Problem &p, const Residual &R, std::vector<int> &cols) {
+    cols.clear();
+    for (size_t a = 0; a < R.blocks.size(); a++) {
+        const Block &A = p.blocks[(size_t) p.block_of.at(R.blocks[a])];
+        if (A.column < 0) continue;
+        for (int x = 0; x < A.local; x++) cols.push_back(A.column + x);
+    }
+}
+
+// One host factor, evaluated and gathered: *cost += 0.5 rho(|r|^2) from the raw residual, then res (nr, robust-corrected where the factor has a
+// loss), cols (hostBlockColumns) and the dense row-major nr x nf Jacobian Jd of those columns.  Jd and res are written at Jd_at / res_at when
+// given (nr and nf follow from the problem: the caller sized them), into the vectors otherwise.
+// -> -1: the cost function failed; 0: no free column, nothing to accumulate (the cost is counted); 1: the block is there.
+inline int gatherHostBlock(const Problem &p, const Residual &R, double *cost, std::vector<int> &cols, std::vector<double> &Jd, std::vector<double> &res,
+                           double *Jd_at = nullptr, double *res_at = nullptr) {
+    ResidualBlockInfo info(R.cost, nullptr, R.blocks, {});
+    if (!info.Evaluate()) return -1;
+    double sq = 0;
+    for (double v : info.residuals()) sq += v * v;
+    if (R.loss) { // cost from the raw residual, then the Ceres corrector (residual_block_info.h:59-87)
+        double rho[3];
+        R.loss->Evaluate(sq, rho);
+        *cost += 0.5 * rho[0];
+        ResidualBlockInfo corrected(R.cost, R.loss, R.blocks, {});
+        if (!corrected.Evaluate()) return -1;
+        info = corrected;
+    } else {
+        *cost += 0.5 * sq;
+    }
+    // the blocks are gathered into ONE dense row-major Jacobian (nr x n_free): see accumulateHostBlock
+    const int nr      = R.cost->num_residuals();
+    const auto &sizes = R.cost->parameter_block_sizes();
+    hostBlockColumns(p, R, cols);
+    const int nf = (int) cols.size();
+    if (nf == 0) return 0;
+    if (!Jd_at) Jd.resize((size_t) nr * nf), Jd_at = Jd.data();
+    if (!res_at) res.resize((size_t) nr), res_at = res.data();
+    int c0 = 0;
+    for (size_t a = 0; a < R.blocks.size(); a++) {
+        const Block &A = p.blocks[(size_t) p.block_of.at(R.blocks[a])];
+        if (A.column < 0) continue;
+        const std::vector<double> &Ja = info.jacobians()[a];
+        for (int k = 0; k < nr; k++)
+            for (int x = 0; x < A.local; x++) Jd_at[(size_t) k * nf + c0 + x] = Ja[(size_t) k * sizes[a] + x];
+        c0 += A.local;
+    }
+    memcpy(res_at, info.residuals().data(), sizeof(double) * (size_t) nr);
+    return 1;
+}
+
+// S += J^T J, s -= J^T r, diag += diag(J^T J) for one gathered block.  J^T J of the factor's free columns: the triple loop runs with the
+// residual index outermost and a contiguous, independent inner index (vectorizable as written); every cell is the sum over k in ascending
+// order from zero, as in a cell-by-cell inner product, and is then added to S once.  S is P x P with row stride P.
+inline void accumulateHostBlock(int P, const std::vector<int> &cols, int nr, const double *Jd, const double *res, double *S, double *s, double *diag) {
+    const int nf = (int) cols.size();
+    thread_local std::vector<double> T;
+    T.assign((size_t) nf * nf + nf, 0.0);
+    double *g = T.data() + (size_t) nf * nf;
+    accumulateJtJ(nr, nf, Jd, res, T.data(), g);
+    for (int x = 0; x < nf; x++) {
+        s[(size_t) cols[(size_t) x]] -= g[x];
+        diag[(size_t) cols[(size_t) x]] += T[(size_t) x * nf + x];
+        S[(size_t) cols[(size_t) x] * P + cols[(size_t) x]] += T[(size_t) x * nf + x];
+        for (int y = x + 1; y < nf; y++) {
+            const double v = T[(size_t) x * nf + y];
+            S[(size_t) cols[(size_t) x] * P + cols[(size_t) y]] += v;
+            S[(size_t) cols[(size_t) y] * P + cols[(size_t) x]] += v;
+        }
+    }
+}
+
 // host factors of one window: S += J^T J, s -= J^T r (robust-corrected), diag, cost += 0.5 rho(|r|^2); S == nullptr: cost only.
 // S is P x P with row stride P.
 inline bool hostFactors(const Problem &p, int P, double *S, double *s, double *diag, double *cost) {
+    thread_local std::vector<double> Jd, res;
+    thread_local std::vector<int> cols;
     for (const Residual &R : p.residuals) {
         if (R.removed) continue;
         if (!S) {
@@ -257,61 +332,10 @@ inline bool hostFactors(const Problem &p, int P, double *S, double *s, double *d
             *cost += c;
             continue;
         }
-        ResidualBlockInfo info(R.cost, nullptr, R.blocks, {});
-        if (!info.Evaluate()) return false;
-        double sq = 0;
-        for (double v : info.residuals()) sq += v * v;
-        if (R.loss) { // cost from the raw residual, then the Ceres corrector (residual_block_info.h:59-87)
-            double rho[3];
-            R.loss->Evaluate(sq, rho);
-            *cost += 0.5 * rho[0];
-            ResidualBlockInfo corrected(R.cost, R.loss, R.blocks, {});
-            if (!corrected.Evaluate()) return false;
-            info = corrected;
-        } else {
-            *cost += 0.5 * sq;
-        }
-        // J^T J of the factor's free columns: the blocks are gathered into ONE dense row-major Jacobian (nr x n_free) so that the triple
-        // loop runs with the residual index outermost and a contiguous, independent inner index (vectorizable as written); every cell is
-        // the sum over k in ascending order from zero, as in a cell-by-cell inner product, and is then added to S once.
-        const int nr      = R.cost->num_residuals();
-        const auto &sizes = R.cost->parameter_block_sizes();
-        thread_local std::vector<double> Jd, T;
-        thread_local std::vector<int> cols;
-        cols.clear();
-        for (size_t a = 0; a < R.blocks.size(); a++) {
-            const Block &A = p.blocks[(size_t) p.block_of.at(R.blocks[a])];
-            if (A.column < 0) continue;
-            for (int x = 0; x < A.local; x++) cols.push_back(A.column + x);
-        }
-        const int nf = (int) cols.size();
-        if (nf == 0) continue;
-        Jd.resize((size_t) nr * nf);
-        {
-            int c0 = 0;
-            for (size_t a = 0; a < R.blocks.size(); a++) {
-                const Block &A = p.blocks[(size_t) p.block_of.at(R.blocks[a])];
-                if (A.column < 0) continue;
-                const std::vector<double> &Ja = info.jacobians()[a];
-                for (int k = 0; k < nr; k++)
-                    for (int x = 0; x < A.local; x++) Jd[(size_t) k * nf + c0 + x] = Ja[(size_t) k * sizes[a] + x];
-                c0 += A.local;
-            }
-        }
-        const std::vector<double> &res = info.residuals();
-        T.assign((size_t) nf * nf + nf, 0.0);
-        double *g = T.data() + (size_t) nf * nf;
-        accumulateJtJ(nr, nf, Jd.data(), res.data(), T.data(), g);
-        for (int x = 0; x < nf; x++) {
-            s[(size_t) cols[(size_t) x]] -= g[x];
-            diag[(size_t) cols[(size_t) x]] += T[(size_t) x * nf + x];
-            S[(size_t) cols[(size_t) x] * P + cols[(size_t) x]] += T[(size_t) x * nf + x];
-            for (int y = x + 1; y < nf; y++) {
-                const double v = T[(size_t) x * nf + y];
-                S[(size_t) cols[(size_t) x] * P + cols[(size_t) y]] += v;
-                S[(size_t) cols[(size_t) y] * P + cols[(size_t) x]] += v;
-            }
-        }
+        const int got = gatherHostBlock(p, R, cost, cols, Jd, res);
+        if (got < 0) return false;
+        if (got == 0) continue;
+        accumulateHostBlock(P, cols, R.cost->num_residuals(), Jd.data(), res.data(), S, s, diag);
     }
     return true;
 }

@@ -23,13 +23,14 @@ EXPORTS = [
     "icg_reproj_schur_windows_view", "icg_reproj_reserve_windows", "icg_reproj_eval_resident_view", "icg_reproj_backsub_windows", "icg_reproj_cost_windows", "icg_reproj_fetch_residuals", "icg_reproj_chi2_cull",
     "icg_reproj_landmark_diag_windows",
     "icg_marg_prior_set", "icg_marg_prior_evaluate", "icg_marg_linearize_batch",
-    "icg_chol_solve_batch", "icg_reproj_schur_windows_resident", "icg_reproj_solve_windows",
+    "icg_chol_solve_batch", "icg_reproj_schur_windows_resident", "icg_reproj_solve_windows", "icg_reproj_host_parts_build",
 ]
 
 
 MARG_MAX_R = 1024  # ICG_MARG_MAX_R of include/icgvins_hip.h
 MARG_LIN_MAX_P = 512  # ICG_MARG_LIN_MAX_P
 CHOL_MAX_N = 512  # ICG_CHOL_MAX_N
+HOST_PART_MAX_NR = 1024  # ICG_HOST_PART_MAX_NR
 
 
 class IcgError(RuntimeError):
@@ -452,6 +453,40 @@ class Context:
         self._ck(self.lib.icg_reproj_solve_windows(self.h, int(P), _p(Pw), _p(sv), _p(new), _p(hs), _p(dd), _p(rhs), _p(dc), _p(st), _p(dl), _p(terms)),
                  "icg_reproj_solve_windows")
         return dc, st, dl, terms
+
+    def reproj_host_parts_build_raw(self, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out=None):
+        """icg_reproj_host_parts_build on the caller's arrays (None = NULL; host_s, host_diag, part_out are written in place) -> the return code"""
+        return self.lib.icg_reproj_host_parts_build(self.h, int(P), _p(Pw), _p(rebuild), _p(blk_off), _p(nr), _p(nf), _p(cols), _p(jac_off), _p(J), _p(r),
+                                                    _p(host_s), _p(host_diag), _p(part_out))
+
+    def reproj_host_parts_build(self, P, Pw, windows, rebuild=None, host_s=None, host_diag=None):
+        """icg_reproj_host_parts_build.  windows: per window a list of blocks (J nr x nf, r, cols, keep); keep: the block goes up as -1 (J gives
+        its shape only).  -> (host_s W x P, host_diag W x P, the packed parts of the rebuilt windows as a list, None for the others)"""
+        W = self._nwin
+        Pw = _i32(Pw).reshape(W)
+        rb = np.ones(W, np.uint8) if rebuild is None else np.ascontiguousarray(rebuild, np.uint8).reshape(W)
+        blocks = [b for win in windows for b in win]
+        blk_off = _i32(np.concatenate([[0], np.cumsum([len(win) for win in windows])]))
+        nr, nf = _i32([np.shape(b[0])[0] for b in blocks]), _i32([np.shape(b[0])[1] for b in blocks])
+        cols = _i32(np.concatenate([_i32(b[2]).reshape(-1) for b in blocks])) if blocks else _i32([])
+        r = _f64(np.concatenate([_f64(b[1]).reshape(-1) for b in blocks])) if blocks else _f64([])
+        jac_off, Js, at = np.full(len(blocks), -1, np.int64), [], 0
+        for k, b in enumerate(blocks):
+            if not b[3]:
+                jac_off[k] = at
+                Js.append(_f64(b[0]).reshape(-1))
+                at += Js[-1].size
+        J = _f64(np.concatenate(Js)) if Js else None
+        s = np.zeros((W, P)) if host_s is None else host_s
+        dg = np.zeros((W, P)) if host_diag is None else host_diag
+        sizes = [int(Pw[w]) * (int(Pw[w]) + 1) // 2 if rb[w] else 0 for w in range(W)]
+        part = np.zeros(max(1, sum(sizes)))
+        self._ck(self.reproj_host_parts_build_raw(P, Pw, rb, blk_off, nr, nf, cols, jac_off, J, r, s, dg, part), "icg_reproj_host_parts_build")
+        parts, at = [], 0
+        for w in range(W):
+            parts.append(part[at:at + sizes[w]].copy() if rb[w] else None)
+            at += sizes[w]
+        return s, dg, parts
 
     def reproj_backsub_windows(self, P, delta_c, n_lm):
         out, terms = np.zeros(n_lm), np.zeros((self._nwin, 2))

@@ -261,6 +261,35 @@ int icg_reproj_schur_windows_resident(icg_ctx *ctx, int P, const int32_t *col_po
  * Pw[w] (the message names the window).  After an error nothing was launched. */
 int icg_reproj_solve_windows(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *solve, const uint8_t *host_part_new, const double *host_S,
                              const double *dd, const double *rhs, double *delta_c, int32_t *status, double *delta_l, double *lm_terms);
+/* The host-factor part of the windows' reduced systems, built on the device: what the host layer's hostFactors forms from the factors the
+ * device does not evaluate (preintegration, the marginalization prior, pose / mix / GNSS priors), bit for bit.  The partition is the resident
+ * one (the W of icg_reproj_set_windows); window w owns the factor blocks [blk_off[w], blk_off[w+1]) (blk_off[0] = 0), in the order of the
+ * problem's residuals.  Block b: nr[b] residuals (robust-corrected where the factor has a loss), a dense row-major nr[b] x nf[b] Jacobian of
+ * the factor's free local columns, and their nf[b] columns inside the window's system (cols, block after block: distinct within a block,
+ * each below Pw[w], in any order); r holds the residuals of all blocks, block after block.
+ * For every window with rebuild[w] != 0 the call replaces the window's resident host part (the packed lower triangle icg_reproj_solve_windows
+ * reads, of Pw[w] columns) and writes host_s / host_diag (W x P) on the leading Pw[w] columns, zeros up to P.  A window with rebuild[w] == 0 is
+ * not touched, neither on the device nor in the outputs (its blocks are not read beyond nr and nf, which place the others' residuals and
+ * columns).  part_out (NULL = not transferred) receives the packed triangles of the rebuilt windows, window after window.  Afterwards
+ * icg_reproj_solve_windows is called with host_part_new = NULL.
+ * Arithmetic: for a block, T[x][y] = sum_k J[k][x] * J[k][y] and g[x] = sum_k J[k][x] * r[k], k ascending, each sum started from +0.0 (a sum
+ * of negative zeros is +0.0), one multiply and one add per term, no contraction.  Cell (a, b), a >= b, of the part starts at +0.0 and
+ * receives += T[x][y], in block order, from every block that holds both columns; blocks that do not hold both add nothing.  s[c] starts at
+ * +0.0 and receives -= g[x], diag[c] receives += T[x][x], in block order.  One thread owns a cell through all blocks (no atomics): a
+ * window's outputs are the same bits alone, in any batch, in any batch order, and run after run.
+ * Kept Jacobians: the context keeps every block's Jacobian in device memory, addressed by (window, position in the window's block list).
+ * jac_off[b] >= 0: the block's Jacobian is at J + jac_off[b], is copied up and replaces the kept one; jac_off[b] == -1: the kept one is used
+ * (a linearized prior's J0 is constant over a solve).  Only the Jacobians with an offset cross the link; r always does.  The kept Jacobians
+ * are dropped by icg_reproj_set_windows and wherever the resident host parts are dropped (icg_reproj_solve_windows above).
+ * ICG_ERR_INVALID (the message names the window and the block): no window partition, P not the resident reduced systems' P where there are
+ * some, a NULL required pointer, Pw[w] outside 1 .. P, nr <= 0 or nf <= 0, a column outside [0, Pw[w]) or repeated within a block, -1 for a
+ * block with no kept Jacobian or whose kept shape is not nr x nf, a rebuilt window whose block count differs from the kept one while any of
+ * its blocks says -1.  ICG_ERR_CAPACITY: P > 512, nr above ICG_HOST_PART_MAX_NR, more than 65535 windows.  A rebuilt window with zero blocks
+ * is valid: its part is zero.  After an error nothing was launched and no output was touched. */
+#define ICG_HOST_PART_MAX_NR 1024
+int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr, const int32_t *nf,
+                                const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s, double *host_diag,
+                                double *part_out);
 /* problem setup: pre-sizes the resident window systems and the staging memory for reduced systems of size P (a hint; optional) */
 int icg_reproj_reserve_windows(icg_ctx *ctx, int P);
 int icg_reproj_backsub_windows(icg_ctx *ctx, int P, const double *delta_c, double *delta_l, double *lm_terms);
