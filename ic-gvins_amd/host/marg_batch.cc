@@ -1,7 +1,6 @@
 // MarginalizationBatch: see marg_batch.h.  Reference: factors/marginalization_info.h:73-101 (marginalization), :153-273 (the steps).
 #include "marg_batch.h"
 #include "marg_linearize_hip.h"
-#include "solver_batch_hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -9,53 +8,31 @@
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
-#include <thread>
 
 namespace icg {
 
-template <typename F> void MarginalizationBatch::forEachWindow(size_t n, F &&fn) {
-    if (host_threads_ <= 1 || n < 4) {
-        for (size_t w = 0; w < n; w++) fn(w);
-        return;
-    }
-    if (!pool_) pool_.reset(new HostPool(host_threads_));
-    const std::function<void(int)> f = [&](int w) { fn((size_t) w); };
-    pool_->parallelFor((int) n, f);
-}
-
-static icg_ctx *backendContext(int device, const char *who) {
-    icg_ctx_config cfg{};
-    cfg.device = device, cfg.width = 64, cfg.height = 64, cfg.n_slots = 1, cfg.max_batch = 1, cfg.max_points = 64; // (holds no images)
-    icg_ctx *ctx = nullptr;
-    if (icg_ctx_create(&cfg, &ctx) != ICG_OK) throw std::runtime_error(std::string(who) + ": " + icg_last_error(nullptr));
-    return ctx;
-}
-
-MarginalizationBatch::MarginalizationBatch(int device, double huber_delta, int host_threads) : device_(device), huber_(huber_delta) {
-    host_threads_ = host_threads > 0 ? host_threads : (int) std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    if (const char *e = getenv("ICG_SOLVER_THREADS")) host_threads_ = std::max(1, atoi(e)); // diagnostics (shared with WindowSolverBatch)
-    ctx_ = backendContext(device, "MarginalizationBatch");
-}
+MarginalizationBatch::MarginalizationBatch(int device, double huber_delta, int host_threads)
+    : factors_(device, host_threads, "MarginalizationBatch"), device_(device), huber_(huber_delta) {}
 
 MarginalizationBatch::~MarginalizationBatch() {
     clear();
     if (dense_ctx_) icg_ctx_destroy(dense_ctx_);
-    icg_ctx_destroy(ctx_);
 }
 
 void MarginalizationBatch::clear() {
     for (auto &W : windows_)
         if (W->info && W->info->batch_ == W.get()) W->info->batch_ = nullptr; // (an info may outlive the batch: it keeps only its results)
     windows_.clear();
+    factors_.clear();
     retired_.clear(); // (the factor records of the windows marginalized since the last clear())
-    laid_out_  = false;
-    n_factors_ = n_poses_ = n_lm_ = 0;
+    laid_out_ = false;
 }
 
 int MarginalizationBatch::addWindow(const std::shared_ptr<MarginalizationInfo> &info) {
     if (!info) throw std::runtime_error("MarginalizationBatch: null MarginalizationInfo");
     std::unique_ptr<Slice> W(new Slice);
     W->owner = this;
+    W->w     = (size_t) factors_.addWindow();
     W->info  = info;
     info->setDeviceFactors(W.get());
     windows_.push_back(std::move(W));
@@ -67,33 +44,17 @@ void MarginalizationBatch::addReprojectionFactor(int w, const ReprojectionFactor
                                                  double *invdepth, double *td) {
     Slice &W = *windows_.at((size_t) w);
     if (!factor || !pose_i || !pose_j || !extrinsic || !invdepth || !td) throw std::runtime_error("MarginalizationBatch: null block");
-    if (W.ext && (W.ext != extrinsic || W.td != td)) throw std::runtime_error("MarginalizationBatch: one extrinsic / td block per window");
-    W.ext = extrinsic, W.td = td;
-    auto index_of = [](std::unordered_map<const double *, int> &m, std::vector<double *> &v, double *p) {
-        auto it = m.find(p);
-        if (it != m.end()) return it->second;
-        const int k = (int) v.size();
-        v.push_back(p);
-        m[p] = k;
-        return k;
-    };
+    if (!factors_.add(w, factor->observation(), pose_i, pose_j, extrinsic, invdepth, td))
+        throw std::runtime_error("MarginalizationBatch: one extrinsic / td block per window");
     W.members.insert(factor);
-    W.obs.insert(W.obs.end(), factor->observation(), factor->observation() + 15);
-    W.idx_i.push_back(index_of(W.pose_index, W.poses, pose_i));
-    W.idx_j.push_back(index_of(W.pose_index, W.poses, pose_j));
-    W.idx_lm.push_back(index_of(W.lm_index, W.landmarks, invdepth));
     laid_out_ = false;
 }
 
-// the factor set of all windows, sorted by window, with the partition the *_windows calls work on
+// a pose block belongs to one window; then the factor set of all windows goes up
 bool MarginalizationBatch::layout() {
-    n_factors_ = n_poses_ = n_lm_ = 0;
-    std::vector<int32_t> fac_off{0}, lm_off{0};
     std::unordered_map<const double *, size_t> pose_owner;
-    for (size_t w = 0; w < windows_.size(); w++) {
-        Slice &W    = *windows_[w];
-        W.fac_begin = n_factors_, W.pose_begin = n_poses_, W.lm_begin = n_lm_;
-        for (double *p : W.poses) {
+    for (size_t w = 0; w < windows_.size(); w++)
+        for (double *p : factors_.window(w).poses) {
             auto it = pose_owner.find(p);
             if (it != pose_owner.end() && it->second != w) {
                 error_ = "a pose block is used by the reprojection factors of two windows";
@@ -101,39 +62,8 @@ bool MarginalizationBatch::layout() {
             }
             pose_owner[p] = w;
         }
-        n_factors_ += W.size(), n_poses_ += (int) W.poses.size(), n_lm_ += (int) W.landmarks.size();
-        fac_off.push_back(n_factors_), lm_off.push_back(n_lm_);
-    }
-    laid_out_ = true;
-    if (n_factors_ == 0) return true; // (only host factors anywhere: nothing for the device)
-    // the windows' factors are written by the pool's threads straight into the context's pinned staging block (34 MB of observations at
-    // 256 C2 windows: through a pageable vector and hipMemcpy they were most of this function's 13 ms)
-    double *obs = nullptr;
-    int32_t *idx3 = nullptr;
-    if (icg_reproj_stage_factors(ctx_, n_factors_, &obs, &idx3) != ICG_OK) {
-        error_    = icg_last_error(ctx_);
-        laid_out_ = false;
-        return false;
-    }
-    int32_t *ii = idx3, *jj = idx3 + n_factors_, *ll = idx3 + 2 * (size_t) n_factors_;
-    forEachWindow(windows_.size(), [&](size_t w) {
-        const Slice &W = *windows_[w];
-        for (int c = 0; c < 15; c++) { // (component-major: one contiguous destination run per component and window)
-            double *dst = obs + (size_t) c * n_factors_ + (size_t) W.fac_begin;
-            for (int k = 0; k < W.size(); k++) dst[k] = W.obs[(size_t) 15 * k + c];
-        }
-        for (int k = 0; k < W.size(); k++) {
-            const size_t f = (size_t) W.fac_begin + (size_t) k;
-            ii[f] = W.pose_begin + W.idx_i[(size_t) k], jj[f] = W.pose_begin + W.idx_j[(size_t) k], ll[f] = W.lm_begin + W.idx_lm[(size_t) k];
-        }
-    });
-    if (icg_reproj_commit_factors(ctx_) != ICG_OK ||
-        icg_reproj_set_windows(ctx_, (int) windows_.size(), fac_off.data(), lm_off.data()) != ICG_OK) {
-        error_    = icg_last_error(ctx_);
-        laid_out_ = false;
-        return false;
-    }
-    return true;
+    laid_out_ = factors_.upload(&error_); // (no factor anywhere — only host factors: nothing for the device, and that is fine)
+    return laid_out_;
 }
 
 bool MarginalizationBatch::Slice::evaluateCorrected(double huber_delta) {
@@ -159,15 +89,16 @@ bool MarginalizationBatch::Slice::accumulateNormal(const std::unordered_map<cons
 
 // The dense M2 of one window (marginalization_info.h:195-230): its factors alone on a one-window context, evaluated there once more (the
 // batched evaluation lives in the partitioned context, whose dense assembly would mix the windows' shared columns).
-bool MarginalizationBatch::denseNormalOfWindow(Slice &W, const std::unordered_map<const double *, int> &column_of, int local_size, double *H0,
+bool MarginalizationBatch::denseNormalOfWindow(Slice &slice, const std::unordered_map<const double *, int> &column_of, int local_size, double *H0,
                                                double *b0) {
-    const int n = W.size();
+    const WindowFactorSet::Window &W = slice.record();
+    const int n                      = W.size();
     if (n == 0) return true;
     std::lock_guard<std::mutex> lock(dense_mutex_);
     try {
         if (!dense_ctx_) dense_ctx_ = backendContext(device_, "MarginalizationBatch (dense path)");
     } catch (const std::exception &e) {
-        W.err = e.what();
+        slice.err = e.what();
         return false;
     }
     std::vector<double> obs((size_t) 15 * n);
@@ -189,9 +120,56 @@ bool MarginalizationBatch::denseNormalOfWindow(Slice &W, const std::unordered_ma
                                       nullptr, nullptr);
     if (rc == ICG_OK) rc = icg_reproj_accumulate_normal(dense_ctx_, local_size, cp.data(), col(W.ext), cl.data(), col(W.td), H0, b0);
     if (rc != ICG_OK) {
-        W.err = icg_last_error(dense_ctx_);
+        slice.err = icg_last_error(dense_ctx_);
         return false;
     }
+    return true;
+}
+
+struct MarginalizationBatch::State {
+    bool alive{false}, planned{false};
+    MarginalizationInfo::StructuredPlan plan;
+};
+
+struct MarginalizationBatch::DeviceM3 {
+    std::vector<char> on_device; // per window: its prior is in the arrays below
+    std::vector<double> Hp, bp, J0, e0;
+    std::vector<size_t> r_off, rr_off;
+};
+
+// device M3 (setDeviceLinearization): every window whose eliminated part was added and that passes the first guard, one call
+bool MarginalizationBatch::linearizeOnDevice(const std::vector<State> &st, const std::vector<char> &added, const std::vector<double> &min_hll,
+                                             DeviceM3 &dev, std::string *what) {
+    const size_t NW    = st.size();
+    const double GUARD = 100.0 * 1e-8; // (finishStructured: 100 x the reference's floor)
+    std::vector<int32_t> dP, dm;
+    std::vector<size_t> h_off, who;
+    size_t th = 0, tb = 0, tr = 0, trr = 0;
+    for (size_t w = 0; w < NW; w++) {
+        if (!added[w] || !(min_hll[w] > GUARD)) continue;
+        const MarginalizationInfo::StructuredPlan &plan = st[w].plan;
+        dev.on_device[w] = 1, dev.r_off[w] = tr, dev.rr_off[w] = trr;
+        who.push_back(w), h_off.push_back(th);
+        dP.push_back(plan.P), dm.push_back(plan.m);
+        th += (size_t) plan.P * plan.P, tb += (size_t) plan.P, tr += (size_t) plan.r, trr += (size_t) plan.r * plan.r;
+    }
+    if (who.empty()) return true;
+    std::vector<double> dH(th), db(tb), dev_min(who.size());
+    std::vector<int32_t> dev_status(who.size());
+    std::vector<size_t> b_off(who.size(), 0);
+    for (size_t k = 1; k < who.size(); k++) b_off[k] = b_off[k - 1] + (size_t) dP[k - 1];
+    factors_.forEachWindow(who.size(), [&](size_t k) {
+        const MarginalizationInfo::StructuredPlan &plan = st[who[k]].plan;
+        memcpy(&dH[h_off[k]], plan.H.data(), sizeof(double) * plan.H.size());
+        memcpy(&db[b_off[k]], plan.b.data(), sizeof(double) * plan.b.size());
+    });
+    dev.Hp.resize(trr), dev.bp.resize(tr), dev.J0.resize(trr), dev.e0.resize(tr);
+    MarginalizationLinearizer lin(true, factors_.ctx());
+    if (!lin.linearize((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev.Hp.data(), dev.bp.data(), dev.J0.data(), dev.e0.data(),
+                       nullptr, dev_min.data(), dev_status.data(), what))
+        return false;
+    for (size_t k = 0; k < who.size(); k++) // second guard of finishStructured, and a solver that did not converge
+        if (!(dev_min[k] > GUARD) || (dev_status[k] & 1)) dev.on_device[who[k]] = 0;
     return true;
 }
 
@@ -218,32 +196,21 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
 
     // ---- 1: every window's reprojection factors, one launch (residual_block_info.h:44-88 with the corrector :59-87 on the device) -------
     auto t0 = now();
-    if (n_factors_ > 0) {
-        std::vector<double> poses(7 * (size_t) n_poses_), ext(7 * NW, 0.0), inv((size_t) n_lm_), td(NW, 0.0);
-        forEachWindow(NW, [&](size_t w) {
-            const Slice &W = *windows_[w];
-            for (size_t k = 0; k < W.poses.size(); k++) memcpy(&poses[7 * ((size_t) W.pose_begin + k)], W.poses[k], sizeof(double) * 7);
-            for (size_t k = 0; k < W.landmarks.size(); k++) inv[(size_t) W.lm_begin + k] = *W.landmarks[k];
-            if (W.ext)
-                memcpy(&ext[7 * w], W.ext, sizeof(double) * 7);
-            else
-                ext[7 * w + 6] = 1.0; // (a window without reprojection factors: an identity nobody reads)
-            if (W.td) td[w] = *W.td;
-        });
-        if (icg_reproj_eval_windows(ctx_, n_poses_, poses.data(), ext.data(), n_lm_, inv.data(), td.data(), 1, huber_) != ICG_OK)
-            return fail(icg_last_error(ctx_));
+    icg_ctx *ctx      = factors_.ctx();
+    const int n_poses = factors_.numPoses(), n_lm = factors_.numLandmarks();
+    if (factors_.numFactors() > 0) {
+        std::vector<double> poses, ext, inv, td;
+        factors_.gather(poses, ext, inv, td);
+        if (icg_reproj_eval_windows(ctx, n_poses, poses.data(), ext.data(), n_lm, inv.data(), td.data(), 1, huber_) != ICG_OK)
+            return fail(icg_last_error(ctx));
     }
     for (auto &W : windows_) W->evaluated = true;
     auto t1 = now();
 
     // ---- 2: M1 bookkeeping, host factors, compact camera layout per window -------------------------------------------------------------
-    struct State {
-        bool alive{false}, planned{false};
-        MarginalizationInfo::StructuredPlan plan;
-    };
     std::vector<State> st(NW);
     const bool force_dense = MarginalizationInfo::denseForced();
-    forEachWindow(NW, [&](size_t w) {
+    factors_.forEachWindow(NW, [&](size_t w) {
         MarginalizationInfo &I = *windows_[w]->info;
         if (!I.updateParameterBlocksIndex() || !I.preMarginalization()) { // (:75-86: nothing to marginalize / an evaluation failed)
             I.isvalid_ = false;
@@ -256,27 +223,25 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     auto t2 = now();
 
     // ---- 3: assembly + landmark elimination of every planned window, one launch sequence; the landmark diagonals --------------------------
-    // (csrc/reproj_schur.hip, schur_impl: reduced systems of up to WindowSolverBatch::kMaxCameraColumns columns; a wider window takes the dense
-    // path on its own)
-    const int max_camera_columns = WindowSolverBatch::kMaxCameraColumns;
+    // (csrc/reproj_schur.hip, schur_impl: reduced systems of up to kMaxCameraColumns columns; a wider window takes the dense path on its own)
     for (size_t w = 0; w < NW; w++) {
         if (!st[w].planned) continue;
-        const Slice &W = *windows_[w];
-        int V          = 0;
+        const WindowFactorSet::Window &W = factors_.window(w);
+        int V                            = 0;
         for (double *p : W.poses) V += st[w].plan.camera_column_of.count(p) ? 6 : 0;
         V += (W.ext && st[w].plan.camera_column_of.count(W.ext) ? 6 : 0) + (W.td && st[w].plan.camera_column_of.count(W.td) ? 1 : 0);
-        if (V > max_camera_columns) st[w].planned = false;
+        if (V > kMaxCameraColumns) st[w].planned = false;
     }
     int P = 0;
     for (size_t w = 0; w < NW; w++)
         if (st[w].planned) P = std::max(P, st[w].plan.P);
     std::vector<double> S, s, hll;
     if (P > 0) {
-        std::vector<int32_t> col_pose((size_t) n_poses_, -1), col_ext(NW, -1), col_td(NW, -1);
+        std::vector<int32_t> col_pose((size_t) n_poses, -1), col_ext(NW, -1), col_td(NW, -1);
         for (size_t w = 0; w < NW; w++) {
             if (!st[w].planned) continue; // (its columns stay constant: the window adds nothing to any reduced system that is read)
-            const Slice &W = *windows_[w];
-            auto col       = [&](const double *p) {
+            const WindowFactorSet::Window &W = factors_.window(w);
+            auto col                         = [&](const double *p) {
                 auto it = st[w].plan.camera_column_of.find(p);
                 return it == st[w].plan.camera_column_of.end() ? -1 : it->second;
             };
@@ -285,20 +250,20 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
         }
         std::vector<uint8_t> reassemble(NW, 1);
         std::vector<double> damp(NW, 0.0), diag_cc(NW * (size_t) P), cost(NW, 0.0);
-        S.assign(NW * (size_t) P * P, 0.0), s.assign(NW * (size_t) P, 0.0), hll.assign((size_t) std::max(n_lm_, 1), 0.0);
-        if (icg_reproj_schur_windows(ctx_, P, col_pose.data(), col_ext.data(), col_td.data(), nullptr, reassemble.data(), damp.data(), 0.0, 0.0, S.data(),
+        S.assign(NW * (size_t) P * P, 0.0), s.assign(NW * (size_t) P, 0.0), hll.assign((size_t) std::max(n_lm, 1), 0.0);
+        if (icg_reproj_schur_windows(ctx, P, col_pose.data(), col_ext.data(), col_td.data(), nullptr, reassemble.data(), damp.data(), 0.0, 0.0, S.data(),
                                      s.data(), diag_cc.data(), cost.data()) != ICG_OK ||
-            icg_reproj_landmark_diag_windows(ctx_, hll.data()) != ICG_OK)
-            return fail(icg_last_error(ctx_));
+            icg_reproj_landmark_diag_windows(ctx, hll.data()) != ICG_OK)
+            return fail(icg_last_error(ctx));
     }
     auto t3 = now();
 
     // ---- 4: guard + M3 on the camera block (or the dense M2 + M3), linearization -------------------------------------------------------------
-    std::vector<char> structured(NW, 0), good(NW, 0), added(NW, 0), on_device(NW, 0);
+    std::vector<char> structured(NW, 0), good(NW, 0), added(NW, 0);
     std::vector<double> min_hll(NW, 0.0);
     // the landmark-eliminated device part joins the window's compact system; the smallest landmark diagonal for the first guard
     auto addEliminated = [&](size_t w) {
-        const Slice &W                             = *windows_[w];
+        const WindowFactorSet::Window &W          = factors_.window(w);
         MarginalizationInfo::StructuredPlan &plan = st[w].plan;
         const int Pw                              = plan.P;
         const double *Sw = &S[w * (size_t) P * P], *sw = &s[w * (size_t) P];
@@ -311,55 +276,24 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
         min_hll[w] = mn;
         added[w]   = 1;
     };
-    // device M3 (setDeviceLinearization): every planned window that passes the first guard, one call
-    std::vector<double> dev_Hp, dev_bp, dev_J0, dev_e0, dev_min;
-    std::vector<int32_t> dev_status;
-    std::vector<size_t> dev_r_off(NW, 0), dev_rr_off(NW, 0);
+    DeviceM3 dev{std::vector<char>(NW, 0), {}, {}, {}, {}, std::vector<size_t>(NW, 0), std::vector<size_t>(NW, 0)};
     if (device_linearization_) {
-        const double GUARD = 100.0 * 1e-8; // (finishStructured: 100 x the reference's floor)
-        forEachWindow(NW, [&](size_t w) {
+        factors_.forEachWindow(NW, [&](size_t w) {
             if (st[w].alive && st[w].planned) addEliminated(w);
         });
-        std::vector<int32_t> dP, dm;
-        std::vector<size_t> h_off, who;
-        size_t th = 0, tb = 0, tr = 0, trr = 0;
-        for (size_t w = 0; w < NW; w++) {
-            if (!added[w] || !(min_hll[w] > GUARD)) continue;
-            const MarginalizationInfo::StructuredPlan &plan = st[w].plan;
-            on_device[w] = 1, dev_r_off[w] = tr, dev_rr_off[w] = trr;
-            who.push_back(w), h_off.push_back(th);
-            dP.push_back(plan.P), dm.push_back(plan.m);
-            th += (size_t) plan.P * plan.P, tb += (size_t) plan.P, tr += (size_t) plan.r, trr += (size_t) plan.r * plan.r;
-        }
-        if (!who.empty()) {
-            std::vector<double> dH(th), db(tb);
-            std::vector<size_t> b_off(who.size(), 0);
-            for (size_t k = 1; k < who.size(); k++) b_off[k] = b_off[k - 1] + (size_t) dP[k - 1];
-            forEachWindow(who.size(), [&](size_t k) {
-                const MarginalizationInfo::StructuredPlan &plan = st[who[k]].plan;
-                memcpy(&dH[h_off[k]], plan.H.data(), sizeof(double) * plan.H.size());
-                memcpy(&db[b_off[k]], plan.b.data(), sizeof(double) * plan.b.size());
-            });
-            dev_Hp.resize(trr), dev_bp.resize(tr), dev_J0.resize(trr), dev_e0.resize(tr), dev_min.resize(who.size()), dev_status.resize(who.size());
-            MarginalizationLinearizer lin(true, ctx_);
-            std::string what;
-            if (!lin.linearize((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev_Hp.data(), dev_bp.data(), dev_J0.data(),
-                               dev_e0.data(), nullptr, dev_min.data(), dev_status.data(), &what))
-                return fail(what);
-            for (size_t k = 0; k < who.size(); k++) // second guard of finishStructured, and a solver that did not converge
-                if (!(dev_min[k] > GUARD) || (dev_status[k] & 1)) on_device[who[k]] = 0;
-        }
+        std::string what;
+        if (!linearizeOnDevice(st, added, min_hll, dev, &what)) return fail(what);
     }
-    forEachWindow(NW, [&](size_t w) {
+    factors_.forEachWindow(NW, [&](size_t w) {
         if (!st[w].alive) return;
         Slice &W               = *windows_[w];
         MarginalizationInfo &I = *W.info;
-        if (on_device[w]) {
-            const size_t r = (size_t) st[w].plan.r;
-            I.Hp_.assign(dev_Hp.begin() + (long) dev_rr_off[w], dev_Hp.begin() + (long) (dev_rr_off[w] + r * r));
-            I.bp_.assign(dev_bp.begin() + (long) dev_r_off[w], dev_bp.begin() + (long) (dev_r_off[w] + r));
-            I.linearized_jacobians_.assign(dev_J0.begin() + (long) dev_rr_off[w], dev_J0.begin() + (long) (dev_rr_off[w] + r * r));
-            I.linearized_residuals_.assign(dev_e0.begin() + (long) dev_r_off[w], dev_e0.begin() + (long) (dev_r_off[w] + r));
+        if (dev.on_device[w]) {
+            const size_t r = (size_t) st[w].plan.r, at = dev.r_off[w], at2 = dev.rr_off[w];
+            I.Hp_.assign(dev.Hp.begin() + (long) at2, dev.Hp.begin() + (long) (at2 + r * r));
+            I.bp_.assign(dev.bp.begin() + (long) at, dev.bp.begin() + (long) (at + r));
+            I.linearized_jacobians_.assign(dev.J0.begin() + (long) at2, dev.J0.begin() + (long) (at2 + r * r));
+            I.linearized_residuals_.assign(dev.e0.begin() + (long) at, dev.e0.begin() + (long) (at + r));
             structured[w] = good[w] = 1;
             return;
         }

@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "factors.h"
-#include "host_pool.h"
+#include "window_factors.h"
 
 namespace icg {
 
@@ -44,7 +44,7 @@ public:
     // all factors of a window share its extrinsic and td blocks, a pose block belongs to one window
     void addReprojectionFactor(int w, const ReprojectionFactor *factor, double *pose_i, double *pose_j, double *extrinsic, double *invdepth, double *td);
     int numWindows() const { return (int) windows_.size(); }
-    int numReprojectionFactors(int w) const { return (int) windows_.at((size_t) w)->obs.size() / 15; }
+    int numReprojectionFactors(int w) const { return factors_.window((size_t) w).size(); }
     // drops every window, keeps the device context (a batch object lives as long as the group of streams it serves)
     void clear();
 
@@ -73,19 +73,15 @@ private:
     // one window's view of the batch: what MarginalizationInfo asks of its device factors
     struct Slice : public DeviceFactorSet {
         MarginalizationBatch *owner{nullptr};
+        size_t w{0}; // its record in owner->factors_
         std::shared_ptr<MarginalizationInfo> info;
         std::unordered_set<const ReprojectionFactor *> members;
-        std::vector<double> obs; // 15 per factor, factor-major
-        std::vector<int32_t> idx_i, idx_j, idx_lm; // window-local pose / landmark indices
-        std::vector<double *> poses, landmarks;   // first-seen order
-        std::unordered_map<const double *, int> pose_index, lm_index;
-        double *ext{nullptr}, *td{nullptr};
-        int fac_begin{0}, pose_begin{0}, lm_begin{0};
         bool evaluated{false};
         std::string err;
+        const WindowFactorSet::Window &record() const { return owner->factors_.window(w); }
         bool owns(const ReprojectionFactor *factor) const override { return members.count(factor) != 0; }
-        int size() const override { return (int) (obs.size() / 15); }
-        const std::vector<double *> &landmarkBlocks() const override { return landmarks; }
+        int size() const override { return record().size(); }
+        const std::vector<double *> &landmarkBlocks() const override { return record().landmarks; }
         bool evaluateCorrected(double huber_delta) override;
         bool accumulateNormal(const std::unordered_map<const double *, int> &column_of, int local_size, double *H0, double *b0) override;
         bool accumulateLandmarkEliminated(const std::unordered_map<const double *, int> &, int, double *, double *, double *) override;
@@ -93,20 +89,21 @@ private:
     };
     bool layout();
     bool denseNormalOfWindow(Slice &W, const std::unordered_map<const double *, int> &column_of, int local_size, double *H0, double *b0);
-    template <typename F> void forEachWindow(size_t n, F &&fn);
+    // marginalize(): a window's progress through the phases; what the device M3 returns
+    struct State;
+    struct DeviceM3;
+    bool linearizeOnDevice(const std::vector<State> &st, const std::vector<char> &added, const std::vector<double> &min_hll, DeviceM3 &dev,
+                           std::string *what);
 
-    icg_ctx *ctx_{nullptr};
+    WindowFactorSet factors_; // the partitioned context, every window's reprojection factors, the host threads
     icg_ctx *dense_ctx_{nullptr}; // one-window context of the dense path (created on first use)
     std::mutex dense_mutex_;
     int device_{0};
     double huber_{1.0};
-    int host_threads_{1};
-    std::unique_ptr<HostPool> pool_;
     std::vector<std::unique_ptr<Slice>> windows_;
     bool laid_out_{false};
     bool device_linearization_{false};
     std::vector<std::shared_ptr<ResidualBlockInfo>> retired_; // factor records of marginalized windows, freed by clear() / the destructor
-    int n_factors_{0}, n_poses_{0}, n_lm_{0};
     int n_structured_{0}, n_dense_{0};
     double phase_ms_[4]{0, 0, 0, 0};
     std::string error_, window_error_;

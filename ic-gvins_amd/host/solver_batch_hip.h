@@ -16,6 +16,7 @@
 
 #include "host_pool.h"
 #include "solver_hip.h"
+#include "window_factors.h"
 
 namespace icg {
 
@@ -23,11 +24,7 @@ class WindowSolverBatch {
 public:
     typedef WindowSolver::Options Options;
     typedef WindowSolver::Summary Summary;
-    // Widest reduced system of the device path: the assembly (csrc/reproj_asm.hip k_asm_*) keeps no per-window tile in LDS any more — rounds 2-5
-    // held the camera block there (82, then 138 columns).  The reduction kernel k_schur_reduce_w stages its landmark rows of 4 ceil(P/4)
-    // doubles in SCH_PRE * 256 = 3 072 elements per pass (at least one row up to P = 3 072) and keeps two entries of s per thread (t and
-    // t + 256): P <= 512.  A window that can exceed it is the caller's to solve on the host.
-    static constexpr int kMaxCameraColumns = 512;
+    static constexpr int kMaxCameraColumns = icg::kMaxCameraColumns; // (window_factors.h)
 
     // host_threads: the per-window host phases (host factors, reduced solves, cost bookkeeping) are spread over this many threads
     explicit WindowSolverBatch(int device = 0, double huber_delta = 1.0, int host_threads = 0 /* 0 = hardware concurrency, at most 16 */);
@@ -45,7 +42,7 @@ public:
     void removeResidualBlock(int w, int id);
     // problem.EvaluateResidualBlock(id, apply_loss_function, &cost, nullptr, nullptr) for a host factor of window w
     bool evaluateResidualBlock(int w, int id, bool apply_loss_function, double *cost) const;
-    int numReprojectionFactors(int w) const { return (int) windows_.at((size_t) w).visual.size(); }
+    int numReprojectionFactors(int w) const { return factors_.window((size_t) w).size(); }
     // a reprojection factor of window w with the five blocks it would get in AddResidualBlock (only its observation constants are
     // read from `factor`); all factors of a window share its extrinsic and td blocks
     void addReprojectionFactor(int w, const ReprojectionFactor *factor, double *pose_i, double *pose_j, double *extrinsic, double *invdepth, double *td);
@@ -76,18 +73,10 @@ public:
     const std::string &error() const { return error_; }
 
 private:
-    struct VisualFactor {
-        double obs[15];
-        double *pose_i, *pose_j, *invdepth;
-    };
+    // a window beside its record in factors_: the host-evaluated part of its problem and its state across the steps of a solve
     struct Window {
         solver_detail::Problem problem{"WindowSolverBatch"};
-        std::vector<VisualFactor> visual;
-        double *ext{nullptr}, *td{nullptr};
-        std::vector<double *> poses, landmarks; // first-seen order of the visual factors
-        std::unordered_map<const double *, int> pose_index, lm_index;
         int P{0};
-        int fac_begin{0}, lm_begin{0}, pose_begin{0};
         std::vector<double> host_S, host_s, host_diag;
         bool host_part_dirty{false}; // host_S was rebuilt since it was last shipped to the device (device reduced solve)
         // device host part: the factors with a free column, in residual order, and where their pieces lie in the buffers of a call
@@ -99,22 +88,30 @@ private:
         std::vector<int32_t> host_cols; // their columns, block after block
         int blk_begin{0};
     };
+    // how solve() forms and solves the reduced systems: resolved from the two setters at its top
+    enum class ReducedPath { HostSolve, DeviceSolve, DeviceSolveDeviceParts };
+    struct Run; // what one solve() works on (solver_batch_hip.cc)
     bool finalize();
     bool layout();
-    void gather(std::vector<double> &poses, std::vector<double> &ext, std::vector<double> &inv, std::vector<double> &td);
+    bool resolvePath(ReducedPath *path);
+    // the phases of a lock-step LM round, in their order; false: error_ is set
+    bool linearize(Run &R);
+    bool reducedSolves(Run &R);
+    bool trialPoints(Run &R);
+    bool trialCosts(Run &R);
+    // where the paths differ: the host half of a window's linearization, and the reduced solves
+    bool hostHalfOfWindow(Run &R, size_t w);
+    void solveWindowOnHost(Run &R, size_t w);
+    bool solveWindowsOnDevice(Run &R);
+    bool fail(const char *what);
 
-    // fn(w) for every window on the persistent helper threads (created on first use: a batch of one or two windows never needs them)
-    template <typename F> void forEachWindow(size_t n, F &&fn);
-
-    icg_ctx *ctx_{nullptr};
+    WindowFactorSet factors_; // the context, every window's reprojection factors, the host threads
     double huber_;
-    int host_threads_;
-    std::unique_ptr<HostPool> pool_;
     std::unique_ptr<SideThread> side_; // runs the device call of a phase beside the pool's host half
     std::vector<Window> windows_;
     std::vector<uint8_t> active_;
     std::vector<int32_t> col_pose_, col_ext_, col_td_;
-    int P_{0}, n_factors_{0}, n_poses_{0}, n_lm_{0};
+    int P_{0};
     bool finalized_{false};
     bool device_reduced_{false}, device_host_part_{false};
     // device host part (layout()): the block list of all windows as icg_reproj_host_parts_build takes it, and the sizes of a call's J and r

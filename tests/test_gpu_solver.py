@@ -86,3 +86,25 @@ def test_window_solver_batch_equals_single_solvers_on_gpu():
         assert np.array_equal(res[k]["summary"][3:], h["summary"][3:]), (k, res[k]["summary"], h["summary"])
         for key in ("poses", "ext", "invdepth"):
             assert np.abs(res[k][key] - h[key]).max() < 1e-7, (k, key)
+
+
+def test_window_solver_batch_with_an_empty_window_in_the_middle_on_gpu():
+    """a window without reprojection factors between two ordinary ones, host solve / device solve / device solve with device-built host
+    parts: the same bits in the three modes, and in the ordinary windows the bits they have without the empty one"""
+    import harness as H
+    import reduced_solve_utils as ru
+    from test_host_part_cpu import _parts
+    from test_host_solver_cpu import _batch_problems, _without_factors
+    lib = C.CDLL(H.HOST_LIB)
+    a, b, c = _batch_problems()[:3]
+    probs = [a, _without_factors(b), c]
+    results = []
+    for reduced_mode, part_mode in ((0, 0), (1, 0), (1, 1)):
+        rc, msg, res = _parts(lib, probs, reduced_mode, part_mode)
+        assert rc == 0, (reduced_mode, part_mode, msg)
+        results.append(res)
+    ru.assert_same_results(results[1], results[0])
+    ru.assert_same_results(results[2], results[0])
+    rc, msg, pair = _parts(lib, [a, c], 0, 0)
+    assert rc == 0, msg
+    ru.assert_same_results([results[0][0], results[0][2]], pair)

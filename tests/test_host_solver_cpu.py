@@ -98,6 +98,42 @@ def test_window_solver_batch_equals_single_solvers(host_lib):
     assert (True, False) in kinds or (True, True) in kinds  # at least one window had a rejected step
 
 
+def _without_factors(P):
+    """the window with its poses, ext, td and pose priors, but no reprojection factor and no inverse depth"""
+    return dict(P, obs=P["obs"][:, :0], ii=P["ii"][:0], jj=P["jj"][:0], ll=P["ll"][:0], start=dict(P["start"], invdepth=P["start"]["invdepth"][:0]))
+
+
+def test_window_solver_batch_with_a_window_without_reprojection_factors(host_lib):
+    """a window that has only host factors (pose priors), first, in the middle and last in a batch: the other windows get the bits they get
+    without it, and the window gets the same bits wherever it stands — the factor / pose / landmark offsets of the windows around it"""
+    import reduced_solve_utils as ru
+    lib = C.CDLL(host_lib)
+    a, b, c = _batch_problems()[:3]
+    e = _without_factors(b)
+    rc, msg, pair = ru.solve_batch_mode(lib, [a, c], None)
+    assert rc == 0, msg
+    empties = []
+    for at in range(3):
+        probs = [a, c]
+        probs.insert(at, e)
+        rc, msg, res = ru.solve_batch_mode(lib, probs, None)
+        assert rc == 0, (at, msg)
+        empties.append(res.pop(at))
+        ru.assert_same_results(res, pair)
+    for r in empties:
+        for key in ("summary", "poses", "ext", "td"):
+            assert np.array_equal(ru.bits(r[key]), ru.bits(empties[0][key])), (key, r[key], empties[0][key])
+        assert len(r["invdepth"]) == 0
+        assert r["summary"][3] >= 1 and r["summary"][2] < r["summary"][0], r["summary"]
+    rc, msg, alone = ru.solve_batch_mode(lib, [a], None)
+    assert rc == 0, msg
+    rc, msg, res = ru.solve_batch_mode(lib, [e, a, e], None)
+    assert rc == 0, msg
+    ru.assert_same_results(res[1:2], alone)
+    rc, msg, _ = ru.solve_batch_mode(lib, [e], None)
+    assert rc == -5 and "no reprojection factors" in msg, (rc, msg)
+
+
 def test_window_solver_matches_reference_factors_with_independent_lm(host_lib):
     """icg::WindowSolver (landmark elimination + LM of the product, here on the CPU shim) against tests/golden/solve_ref_golden.npz: the same
     three windows solved with the REFERENCE's own factor code and an independently written LM (oracle/ref_build/shim/ceres/problem_shim.h;
