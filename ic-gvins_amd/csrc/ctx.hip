@@ -74,6 +74,14 @@ extern "C" int icg_ctx_create(const icg_ctx_config *cfg, icg_ctx **out) {
         g_create_error = "icg_ctx_create: invalid configuration";
         return ICG_ERR_INVALID;
     }
+    // k_lk_track / k_lk_track_fb address the tiles they load from a level by ONE 32-bit byte offset per lane, row * pitch + col, formed with a
+    // 24-bit multiply (lk.hip, lk_offset): every level's height and pitch stay below 2^24 and its pitch * height below 2^31.  Level 0 is the
+    // largest (pitch = width rounded up to 128, as laid out below).  Checked here, before a device is touched or a byte allocated.
+    if (cfg->width >= (1 << 24) || cfg->height >= (1 << 24) ||
+        (unsigned long long) icg_align_up((size_t) cfg->width, 128) * (unsigned long long) cfg->height >= (1ull << 31)) {
+        g_create_error = "icg_ctx_create: image too large: pitch * height of a pyramid level must stay below 2^31 bytes (32-bit tile offsets of the LK kernels)";
+        return ICG_ERR_INVALID;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device >= ndev) {
         g_create_error = "icg_ctx_create: no HIP device available (this library has no CPU fallback)";

@@ -32,6 +32,10 @@
 //     LDS: two v_perm + two v_dot2 per position) and every lane runs a separable 32-bit Scharr (v_mad_i32_i24) over its 3x9 piece of B — the
 //     same bits as blending Ix, Iy and I separately (tests/test_lk_blend_first_identity.py pins the algebra).  Windows over a border keep the
 //     packed 16-bit form above, where the derivative plane is masked to zero outside the image.
+//   * (round 9) the uniform and address work around that arithmetic: the level scale 2^-level from its bit pattern (was an FP64 division per
+//     level and pass), tile loads inside a level by the level's scalar base + ONE 32-bit lane offset (lk_offset: a 24-bit multiply; bound checked by
+//     icg_ctx_create) instead of a 64-bit address per lane, the segment decode by icg_div_magic.  5.73 k vector instructions per tracked point,
+//     93 VGPRs, no scratch, 5 waves per SIMD (profiles/r09_uniform_prologues.txt).
 // Algorithmic HBM bytes per point and direction: 4 levels x (24^2 + 22^2) B; everything else is
 // LDS/VGPR traffic.
 #include <cfloat>
@@ -206,6 +210,14 @@ __device__ __forceinline__ int lk_byte(unsigned int w, int k) { return (int) ((w
 
 typedef unsigned int __attribute__((aligned(1))) lk_u32u;
 
+// Byte offset of (row, col) inside a level for the tile loads that lie inside the image (round 9): the level's base pointer is wave-uniform
+// and stays in scalar registers, the lane adds ONE 32-bit offset — global_load with a scalar base and a vector offset — instead of a 64-bit
+// address of its own (two v_mad_u64_u32, two v_lshl_add_u64 and the moves between them per load).  0 <= row < h and 0 <= col < pitch on
+// these paths, and icg_ctx_create admits only layouts with h, pitch < 2^24 and pitch * h < 2^31: the 24-bit multiply-add is exact.
+__device__ __forceinline__ unsigned int lk_offset(int row, int pitch, int col) {
+    return __umul24((unsigned int) row, (unsigned int) pitch) + (unsigned int) col;
+}
+
 // Tile loads are split into "issue all global loads into registers" and "write them to LDS", so that the loads of the
 // previous-image tile and of the next-image tile of a level fly together (one HBM/L2 round trip per level instead of
 // two or more back-to-back ones: the wave has few siblings to hide latency behind at 84 VGPRs).
@@ -220,7 +232,7 @@ __device__ __forceinline__ void lk_load_I(unsigned int (&v)[3], const unsigned c
         v[q] = 0;
         if (i < LK_IT * 6) {
             if (inside)
-                v[q] = *reinterpret_cast<const lk_u32u *>(I + (size_t) (ipy - 1 + r) * pitch + (ipx - 1 + 4 * cd));
+                v[q] = *reinterpret_cast<const lk_u32u *>(I + lk_offset(ipy - 1 + r, pitch, ipx - 1 + 4 * cd));
             else
                 v[q] = lk_load4(I + (size_t) icg_reflect101(ipy - 1 + r, H) * pitch, ipx - 1 + 4 * cd, W);
         }
@@ -240,7 +252,7 @@ __device__ __forceinline__ void lk_load_J(unsigned int (&v)[4], const unsigned c
     const int r = lane >> 1, c0 = (lane & 1) * 16;
     const bool inside = jx0 >= 0 && jx0 + LK_JT <= W && jy0 >= 0 && jy0 + LK_JT <= H; // wave-uniform
     if (inside) {
-        const unsigned char *row = J + (size_t) (jy0 + r) * pitch + (jx0 + c0);
+        const unsigned char *row = J + lk_offset(jy0 + r, pitch, jx0 + c0);
 #pragma unroll
         for (int q = 0; q < 4; q++) v[q] = *reinterpret_cast<const lk_u32u *>(row + 4 * q);
     } else {
@@ -326,7 +338,7 @@ __device__ __forceinline__ unsigned int pk_shift(unsigned int a, unsigned int b)
 // byte funnel shift per row), expanded to the 7 horizontally adjacent u16 pixel pairs the bilinear blend consumes
 __device__ __forceinline__ void lk_fetch_J(const lk_smem &S, int row0, int o, unsigned int (&JA)[7], unsigned int (&JB)[7]) {
     const int idx = o >> 2, sh = o & 3;
-    const unsigned int *r0 = &S.J[(row0 * LK_JS >> 2) + idx];
+    const unsigned int *r0 = &S.J[__umul24((unsigned int) row0, LK_JS >> 2) + (unsigned int) idx]; // (row0 < 32: a 24-bit multiply-add, no 64-bit one)
     const unsigned int *r1 = r0 + (LK_JS >> 2);
     const unsigned int d0 = r0[0], d1 = r0[1], d2 = r0[2];
     const unsigned int e0 = r1[0], e1 = r1[1], e2 = r1[2];
@@ -369,7 +381,8 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
         const int W = P.w[level], H = P.h[level], pitch = P.pitch[level];
         const unsigned char *I = slotI + P.off[level];
         const unsigned char *J = slotJ + P.off[level];
-        const float scale      = (float) (1. / (1 << level));
+        // 2^-level from its bit pattern (round 9; (float) (1. / (1 << level)) was an FP64 division at the head of every level: level is a loop variable)
+        const float scale      = __uint_as_float((unsigned int) (127 - level) << 23);
         float prevx = prevPt.x * scale, prevy = prevPt.y * scale;
         float nptx, npty;
         if (level == maxLevel) {
@@ -722,16 +735,18 @@ __global__ __launch_bounds__(64) void k_lk_track(icg_pyr_desc P, int n, const in
 
 __global__ __launch_bounds__(64, LK_WAVES_PER_EU) void k_lk_track_fb(icg_pyr_desc P, int n, const int32_t *prev_slot,
                                                     const int32_t *next_slot, const float2 *prev_pts,
-                                                    const float2 *guess_pts, float2 *out_pts, unsigned char *status,
-                                                    float2 *out_bwd, int img_w, int img_h,
-                                                    int seg_cap, const int32_t *seg_count) {
+                                                    const float2 *guess_pts, int img_w, int img_h,
+                                                    int seg_cap, unsigned int seg_magic, const int32_t *seg_count,
+                                                    float2 *out_pts, unsigned char *status, float2 *out_bwd) {
     __shared__ lk_smem S;
     const int i = icg_xcd_chunked(blockIdx.x, n);
     if (i >= n) return;
     // segmented call (device-resident tracker, tracker.hip): the points of stream s are entries [s * seg_cap, s * seg_cap + seg_count[s])
     // of every array; the stage kernel that ran before this launch left the count in device memory — no host round trip sizes the grid
+    // (seg_magic = icg_div_magic(seg_cap): i and the quotient are wave-uniform, the decode is scalar — the division by a run-time value was a
+    // v_rcp_iflag_f32 and its fix-up sequence in every wave of the grid, the half that leaves here included)
     if (seg_count) {
-        const int s = i / seg_cap;
+        const int s = icg_div_by_magic(i, seg_magic);
         if (i - s * seg_cap >= seg_count[s]) return; // wave-uniform
     }
     const int lane = threadIdx.x;
@@ -779,11 +794,11 @@ __global__ __launch_bounds__(64, LK_WAVES_PER_EU) void k_lk_track_fb(icg_pyr_des
 // array or the caller's).
 __global__ __launch_bounds__(256) void k_lk_finish(int n, const float2 *prev_pts, const float2 *out_pts, float2 *bwd_undist, unsigned char *status,
                                                    int want_undist, int has_cam, icg_camera cam, int img_w, int img_h, int seg_cap,
-                                                   const int32_t *seg_count) {
+                                                   unsigned int seg_magic, const int32_t *seg_count) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     if (seg_count) {
-        const int s = i / seg_cap;
+        const int s = icg_div_by_magic(i, seg_magic);
         if (i - s * seg_cap >= seg_count[s]) return;
     }
     const float2 p0 = prev_pts[i], fwd = out_pts[i], bwd = bwd_undist[i];
@@ -862,15 +877,16 @@ extern "C" int icg_lk_track(icg_ctx *ctx, int n, const int32_t *prev_slot, const
 // null: one list of n points; otherwise n = n_seg * seg_cap entries in segments (icg_lk_launch_segments).  bwd_undist: see k_lk_finish.
 static void lk_fb_launch(icg_ctx *ctx, int n, int seg_cap, const int32_t *seg_count, bool want_undist, const int32_t *prev_slot, const int32_t *next_slot,
                          const float2 *prev, const float2 *guess, float2 *out, uint8_t *status, float2 *bwd_undist) {
+    const unsigned int seg_magic = seg_count ? icg_div_magic(seg_cap) : 0u; // (0: divisor 1, and what an unsegmented call passes)
     {
         icg_prof_scope ps(ctx, "lk_track_fb");
-        hipLaunchKernelGGL(k_lk_track_fb, dim3(icg_xcd_grid(n)), dim3(64), 0, ctx->stream, icg_make_pyr_desc(ctx), n, prev_slot, next_slot, prev, guess, out,
-                           status, bwd_undist, ctx->cfg.width, ctx->cfg.height, seg_cap, seg_count);
+        hipLaunchKernelGGL(k_lk_track_fb, dim3(icg_xcd_grid(n)), dim3(64), 0, ctx->stream, icg_make_pyr_desc(ctx), n, prev_slot, next_slot, prev, guess,
+                           ctx->cfg.width, ctx->cfg.height, seg_cap, seg_magic, seg_count, out, status, bwd_undist);
     }
     {
         icg_prof_scope ps(ctx, "lk_finish");
         hipLaunchKernelGGL(k_lk_finish, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, prev, (const float2 *) out, bwd_undist, status,
-                           want_undist ? 1 : 0, ctx->has_cam ? 1 : 0, ctx->cam, ctx->cfg.width, ctx->cfg.height, seg_cap, seg_count);
+                           want_undist ? 1 : 0, ctx->has_cam ? 1 : 0, ctx->cam, ctx->cfg.width, ctx->cfg.height, seg_cap, seg_magic, seg_count);
     }
 }
 
@@ -916,6 +932,8 @@ extern "C" int icg_lk_track_fb(icg_ctx *ctx, int n, const int32_t *prev_slot, co
 int icg_lk_launch_segments(icg_ctx *ctx, int n_seg, int seg_cap, const int32_t *d_count, const int32_t *d_prev_slot, const int32_t *d_next_slot,
                            const float2 *d_prev, const float2 *d_guess, float2 *d_out, uint8_t *d_status, float2 *d_undist) {
     if (!ctx->has_cam) return icg_fail(ctx, ICG_ERR_INVALID, "camera not set");
+    if (n_seg < 1 || seg_cap < 1 || (unsigned long long) n_seg * seg_cap * seg_cap >= (1ull << 32)) // (icg_div_magic is exact for entry * seg_cap < 2^32)
+        return icg_fail(ctx, ICG_ERR_INVALID, "%d segments of %d entries: the segment decode needs n_seg * seg_cap^2 < 2^32", n_seg, seg_cap);
     lk_fb_launch(ctx, n_seg * seg_cap, seg_cap, d_count, true, d_prev_slot, d_next_slot, d_prev, d_guess, d_out, d_status, d_undist);
     ICG_HIP(ctx, hipGetLastError());
     return ICG_OK;

@@ -161,6 +161,10 @@ class Context:
         hist = np.zeros(n, np.float64) if want_hist else None
         self._ck(self.lib.icg_frames_preprocess(self.h, n, _p(_i32(slots)), ptrs, stride, ch, 0, _p(hist)),
                  "icg_frames_preprocess")
+        # without want_hist the call returns with the upload still in flight: a frame that had to be copied to make it contiguous uint8 is a
+        # temporary of this function and must outlive the upload (a column-major frame came out as garbage from some row on, a different row every run)
+        if hist is None and any(a is not b for a, b in zip(imgs, images)):
+            self.sync()
         return hist
 
     def preprocess_device(self, slots, dev_ptrs, stride, channels=1):
