@@ -167,11 +167,21 @@ class Context:
             self.sync()
         return hist
 
-    def preprocess_device(self, slots, dev_ptrs, stride, channels=1):
+    def preprocess_device(self, slots, dev_ptrs, stride, channels=1, want_hist=False):
+        """dev_ptrs: frames that already live in device memory, rows `stride` bytes apart (stride >= width * channels).
+
+        Allocation contract: gray frames whose stride and pointers are all multiples of 4 are read IN PLACE, as aligned dwords: the kernels
+        then read up to 3 bytes past the last pixel of a row (never selected into a result), so every frame must lie in an allocation that
+        extends at least stride * height + 16 bytes from the frame's pointer, and must stay unchanged until the call's kernels have run
+        (the call is asynchronous unless want_hist).  What lies in the stride gap does not matter: the histogram, the LUTs and the output
+        see the width * height pixels only.  Any other batch (an odd stride, one misaligned pointer, BGR) is first copied, visible pixels
+        only, into the context's own staging planes.  Returns the brightness means (float64 per frame) if want_hist, else None."""
         n = len(slots)
         ptrs = (C.c_void_p * n)(*dev_ptrs)
-        self._ck(self.lib.icg_frames_preprocess(self.h, n, _p(_i32(slots)), ptrs, stride, channels, 1, None),
+        hist = np.zeros(n, np.float64) if want_hist else None
+        self._ck(self.lib.icg_frames_preprocess(self.h, n, _p(_i32(slots)), ptrs, stride, channels, 1, _p(hist)),
                  "icg_frames_preprocess")
+        return hist
 
     def download(self, slot, level=0):
         w, h = self.width, self.height
