@@ -36,9 +36,21 @@
 //     level and pass), tile loads inside a level by the level's scalar base + ONE 32-bit lane offset (lk_offset: a 24-bit multiply; bound checked by
 //     icg_ctx_create) instead of a 64-bit address per lane, the segment decode by icg_div_magic.  5.73 k vector instructions per tracked point,
 //     93 VGPRs, no scratch, 5 waves per SIMD (profiles/r09_uniform_prologues.txt).
+//   * (round 10) tile loads over a border of a level: 3.05 of the 16 tile loads of a point cross one on the bench's frames (a third of them a column
+//     border).  They were a reflect-101 loop, a 64-bit address, a byte load and a shift-or per pixel outside — unrolled at three call sites, 60 % of
+//     the kernel's text.  On levels of at least LK_JT x LK_JT a single reflection is a closed form, and a dword with mirrored pixels is ONE unaligned
+//     dword load inside the row and one v_perm (lk_load4_mirror, as k_pyrdown_rows' edge waves do), and a tile over a row border only is plain
+//     dwords from mirrored rows; smaller levels, which only tests build, go through two loops that are not unrolled (lk_stage_small).
+//     5.60 k vector instructions per tracked point, scalar instructions -7 %, 15 856 -> 10 928 bytes of text, no global_load_ubyte and no 64-bit
+//     lane address outside lk_stage_small, 93 VGPRs, no scratch, 5 waves per SIMD (profiles/r10_lk_border_tiles.txt).
 // Algorithmic HBM bytes per point and direction: 4 levels x (24^2 + 22^2) B; everything else is
 // LDS/VGPR traffic.
 #include <cfloat>
+#if defined(LK_TILE_HIST)
+#include <cstdio>
+#include <cstdlib>
+#include <mutex>
+#endif
 
 #include "dev_camera.h"
 #include "icg_internal.h"
@@ -195,22 +207,11 @@ __device__ __forceinline__ void lk_weights(float a, float b, int &w00, int &w01,
     w11 = (1 << 14) - w00 - w01 - w10;
 }
 
-// 4 consecutive pixels of row `row` starting at image column x (reflect-101 outside the image), packed little-endian
-__device__ __forceinline__ unsigned int lk_load4(const unsigned char *row, int x, int W) {
-    if (x >= 0 && x + 3 < W) {
-        typedef unsigned int __attribute__((aligned(1))) u32u;
-        return *reinterpret_cast<const u32u *>(row + x);
-    }
-    unsigned int v = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) v |= (unsigned int) row[icg_reflect101(x + k, W)] << (8 * k);
-    return v;
-}
 __device__ __forceinline__ int lk_byte(unsigned int w, int k) { return (int) ((w >> (8 * k)) & 0xffu); }
 
 typedef unsigned int __attribute__((aligned(1))) lk_u32u;
 
-// Byte offset of (row, col) inside a level for the tile loads that lie inside the image (round 9): the level's base pointer is wave-uniform
+// Byte offset of (row, col) inside a level for the tile loads (round 9; round 10: the mirrored loads over a border too): the level's base pointer is wave-uniform
 // and stays in scalar registers, the lane adds ONE 32-bit offset — global_load with a scalar base and a vector offset — instead of a 64-bit
 // address of its own (two v_mad_u64_u32, two v_lshl_add_u64 and the moves between them per load).  0 <= row < h and 0 <= col < pitch on
 // these paths, and icg_ctx_create admits only layouts with h, pitch < 2^24 and pitch * h < 2^31: the 24-bit multiply-add is exact.
@@ -218,24 +219,104 @@ __device__ __forceinline__ unsigned int lk_offset(int row, int pitch, int col) {
     return __umul24((unsigned int) row, (unsigned int) pitch) + (unsigned int) col;
 }
 
+// ---- tile loads over a level's border (round 10) ----
+// A window the kernel accepts has -ICG_LK_WIN <= ipx, inx <= W - 1 (and the same on rows: the range tests of lk_track_wave).  The I tile starts
+// one pixel before ipx and is LK_IT wide: it reaches at most ICG_LK_WIN + 1 = 22 positions outside the level on either side.  The J tile
+// starts LK_JM before inx and is LK_JT wide: columns inx - 5 .. inx + 26, at most ICG_LK_WIN + LK_JM = 26 positions outside.  On a level with
+// W - 1 >= 26 ONE reflection therefore lands inside — |c| <= 26 <= W - 1 on the left, 2 (W - 1) - c >= W - 27 >= 0 on the right — and
+// reflect-101 is the closed form r(c) = (W - 1) - |(W - 1) - |c|| (lk_mirror).  Levels of at least LK_JT on both sides take this form;
+// smaller ones, which only tests build, keep the general loops (lk_stage_small).
+static_assert(LK_JT >= ICG_LK_WIN + LK_JM + 1, "one reflection must land inside every level that takes the closed-form border path");
+static_assert(LK_IT - 1 - 1 <= LK_JT - 1 - LK_JM, "the I tile reaches no further outside a level than the J tile");
+__device__ __forceinline__ int lk_mirror(int c, int n) { return (n - 1) - abs((n - 1) - abs(c)); }
+
+// The dword of image columns x .. x + 3 of one row under reflect-101, from ONE unaligned dword load that lies inside the row and one v_perm.
+// The load starts at s = clamp(x, 0, W - 4) when at most two of the columns are outside (x in [-2, W - 2]) and at the mirror image of the
+// dword's last column, r(x + 3) = -3 - x or 2 W - 5 - x, when three or four are (the bytes then come out reversed).  One expression gives all
+// three without a compare: s = min(max(min(x, 2 W - 5 - x), 0, -3 - x), W - 4) — 2 W - 5 - x is below x only right of column W - 2, -3 - x is
+// positive only left of column -2 — and its outer clamp holds for EVERY x, so no load starts before column 0 or ends after column W - 1.
+// The selector is the 4-byte window at offset o = x - s + 2, at most 5, of the byte sequence 2 1 0 1 2 3 2 1 (0) — a dword mirrored at both
+// of its ends; the ninth byte is the zero a right shift fills in: o = 0 and 1 are the straddles of column 0 (x = -2: bytes 2 1 0 1, x = -1:
+// 1 0 1 2), o = 2 the identity, o = 3 and 4 the straddles of column W - 1 (x = W - 3: 1 2 3 2, x = W - 2: 2 3 2 1), o = 5 the reversed dword
+// 3 2 1 0 (x - s is 2 x + 3 <= -3 on the left, a huge unsigned number, and 2 (x - W) + 5 >= 3 on the right).  Straight-line code, the same
+// for every lane, no loop and no byte load; tests/test_lk_mirror_dword.py restates it against a per-byte reflect-101.  The load and the
+// v_perm are two calls: the loads of a tile are issued together and permuted together (lk_mirror_apply) before the load function returns — the
+// one place where the wave waits for a tile before the level's barrier: an I tile over a column border (0.42 per point on the bench's frames) has
+// arrived before the J tile's loads are issued.  (Carried to the stores behind the barrier, the selectors were seven more registers
+// to define on the inside path of every level.)
+__device__ __forceinline__ unsigned int lk_load4_mirror(const unsigned char *img, unsigned int row_off, int x, int W, unsigned int &sel) {
+    const int s           = min(max(max(min(x, 2 * W - 5 - x), 0), -3 - x), W - 4);
+    const unsigned int sh = min((unsigned int) (8 * (x - s) + 16), 40u); // 8 o
+    sel                   = (unsigned int) (0x0102030201000102ull >> sh);
+    return *reinterpret_cast<const lk_u32u *>(img + (row_off + (unsigned int) s));
+}
+__device__ __forceinline__ unsigned int lk_mirror_apply(unsigned int d, unsigned int sel) { return __builtin_amdgcn_perm(0u, d, sel); }
+
+#if defined(LK_TILE_HIST)
+// profiling build (EXTRA_HIPFLAGS=-DLK_TILE_HIST, off in the product): tile loads since the library was loaded by level, tile (0: I at the level
+// start, 1: J at the level start, 2: J re-staged) and path (0: inside, 1: over a row border only, 2: over a column border), the points that
+// k_lk_track_fb tracked and the passes it ran; printed when the process ends (profiles/r10_lk_border_tiles.txt)
+__device__ unsigned long long g_lk_tile_hist[4][3][3];
+__device__ unsigned long long g_lk_tile_points[2];
+static void lk_tile_hist_dump() {
+    static unsigned long long h[4][3][3], p[2];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_lk_tile_hist), sizeof h) != hipSuccess) return;
+    if (hipMemcpyFromSymbol(p, HIP_SYMBOL(g_lk_tile_points), sizeof p) != hipSuccess) return;
+    fprintf(stderr, "LK_TILE_HIST points %llu passes %llu\n", p[0], p[1]);
+    for (int l = 0; l < 4; l++)
+        for (int k = 0; k < 3; k++)
+            fprintf(stderr, "LK_TILE_HIST level %d tile %d inside %llu rows %llu columns %llu\n", l, k, h[l][k][0], h[l][k][1], h[l][k][2]);
+}
+__device__ __forceinline__ void lk_tile_hist(int level, int kind, int x0, int y0, int T, int W, int H, int lane) {
+    const int path = (x0 < 0 || x0 + T > W) ? 2 : (y0 < 0 || y0 + T > H) ? 1 : 0;
+    if (lane == 0) atomicAdd(&g_lk_tile_hist[min(level, 3)][kind][path], 1ull);
+}
+#define LK_HIST(level, kind, x0, y0, T) lk_tile_hist(level, kind, x0, y0, T, W, H, lane)
+#else
+#define LK_HIST(level, kind, x0, y0, T)
+#endif
+
 // Tile loads are split into "issue all global loads into registers" and "write them to LDS", so that the loads of the
 // previous-image tile and of the next-image tile of a level fly together (one HBM/L2 round trip per level instead of
 // two or more back-to-back ones: the wave has few siblings to hide latency behind at 84 VGPRs).
+// Four ways, chosen wave-uniformly: a tile inside the level loads plain dwords (round 9); on a level of at least LK_JT x LK_JT a tile over the
+// top or bottom border only loads plain dwords from mirrored rows (lk_mirror), and a tile over the left or right border mirrored dwords
+// (lk_load4_mirror) — offsets by lk_offset on the same scalar base: no 64-bit address per lane, no byte load, no loop; levels smaller than
+// that are staged by lk_stage_small (the callers test for them).
 // 24x24 I tile: dword i = lane + 64*q -> (row i/6, dword column i%6), tile (r,c) <-> image (ipx-1+c, ipy-1+r)
-__device__ __forceinline__ void lk_load_I(unsigned int (&v)[3], const unsigned char *I, int W, int H, int pitch, int ipx, int ipy,
-                                          int lane) {
-    const bool inside = ipx - 1 >= 0 && ipx - 1 + LK_IT <= W && ipy - 1 >= 0 && ipy - 1 + LK_IT <= H; // wave-uniform
+__device__ __forceinline__ void lk_load_I(unsigned int (&v)[3], const unsigned char *I, int W, int H, int pitch, int ipx, int ipy, int lane) {
+    const bool cols_in = ipx - 1 >= 0 && ipx - 1 + LK_IT <= W, rows_in = ipy - 1 >= 0 && ipy - 1 + LK_IT <= H; // wave-uniform
+    if (cols_in && rows_in) {
 #pragma unroll
-    for (int q = 0; q < 3; q++) {
-        const int i = lane + 64 * q;
-        const int r = i / 6, cd = i - r * 6;
-        v[q] = 0;
-        if (i < LK_IT * 6) {
-            if (inside)
-                v[q] = *reinterpret_cast<const lk_u32u *>(I + lk_offset(ipy - 1 + r, pitch, ipx - 1 + 4 * cd));
-            else
-                v[q] = lk_load4(I + (size_t) icg_reflect101(ipy - 1 + r, H) * pitch, ipx - 1 + 4 * cd, W);
+        for (int q = 0; q < 3; q++) {
+            const int i = lane + 64 * q;
+            const int r = i / 6, cd = i - r * 6;
+            v[q] = 0;
+            if (i < LK_IT * 6) v[q] = *reinterpret_cast<const lk_u32u *>(I + lk_offset(ipy - 1 + r, pitch, ipx - 1 + 4 * cd));
         }
+    } else if (cols_in) {
+        asm volatile(""); // (real branches: left alone, the compiler joins the loads of the forms behind 64-bit addresses for all of them)
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const int i = lane + 64 * q;
+            const int r = i / 6, cd = i - r * 6;
+            v[q] = 0;
+            if (i < LK_IT * 6) v[q] = *reinterpret_cast<const lk_u32u *>(I + lk_offset(lk_mirror(ipy - 1 + r, H), pitch, ipx - 1 + 4 * cd));
+        }
+        asm volatile("");
+    } else {
+        asm volatile("");
+        unsigned int sel[3] = {0, 0, 0}; // (lanes past the tile: perm of 0 by 0 is 0, and nothing stores it)
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const int i = lane + 64 * q;
+            const int r = i / 6, cd = i - r * 6;
+            v[q] = 0;
+            if (i < LK_IT * 6) v[q] = lk_load4_mirror(I, lk_offset(lk_mirror(ipy - 1 + r, H), pitch, 0), ipx - 1 + 4 * cd, W, sel[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 3; q++) v[q] = lk_mirror_apply(v[q], sel[q]);
+        asm volatile("");
     }
 }
 __device__ __forceinline__ void lk_store_I(lk_smem &S, const unsigned int (&v)[3], int lane) {
@@ -247,18 +328,28 @@ __device__ __forceinline__ void lk_store_I(lk_smem &S, const unsigned int (&v)[3
     }
 }
 // 32x32 J tile: lane -> (row lane>>1, 16 pixels at column (lane&1)*16) = 4 packed dwords, tile (r,c) <-> image (jx0+c, jy0+r)
-__device__ __forceinline__ void lk_load_J(unsigned int (&v)[4], const unsigned char *J, int W, int H, int pitch, int jx0, int jy0,
-                                          int lane) {
+__device__ __forceinline__ void lk_load_J(unsigned int (&v)[4], const unsigned char *J, int W, int H, int pitch, int jx0, int jy0, int lane) {
     const int r = lane >> 1, c0 = (lane & 1) * 16;
-    const bool inside = jx0 >= 0 && jx0 + LK_JT <= W && jy0 >= 0 && jy0 + LK_JT <= H; // wave-uniform
-    if (inside) {
+    const bool cols_in = jx0 >= 0 && jx0 + LK_JT <= W, rows_in = jy0 >= 0 && jy0 + LK_JT <= H; // wave-uniform
+    if (cols_in && rows_in) {
         const unsigned char *row = J + lk_offset(jy0 + r, pitch, jx0 + c0);
 #pragma unroll
         for (int q = 0; q < 4; q++) v[q] = *reinterpret_cast<const lk_u32u *>(row + 4 * q);
-    } else {
-        const unsigned char *row = J + (size_t) icg_reflect101(jy0 + r, H) * pitch;
+    } else if (cols_in) {
+        asm volatile(""); // (as in lk_load_I)
+        const unsigned char *row = J + lk_offset(lk_mirror(jy0 + r, H), pitch, jx0 + c0);
 #pragma unroll
-        for (int q = 0; q < 4; q++) v[q] = lk_load4(row, jx0 + c0 + 4 * q, W);
+        for (int q = 0; q < 4; q++) v[q] = *reinterpret_cast<const lk_u32u *>(row + 4 * q);
+        asm volatile("");
+    } else {
+        asm volatile("");
+        const unsigned int row_off = lk_offset(lk_mirror(jy0 + r, H), pitch, 0);
+        unsigned int sel[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) v[q] = lk_load4_mirror(J, row_off, jx0 + c0 + 4 * q, W, sel[q]);
+#pragma unroll
+        for (int q = 0; q < 4; q++) v[q] = lk_mirror_apply(v[q], sel[q]);
+        asm volatile("");
     }
 }
 __device__ __forceinline__ void lk_store_J(lk_smem &S, const unsigned int (&v)[4], int lane) {
@@ -267,11 +358,36 @@ __device__ __forceinline__ void lk_store_J(lk_smem &S, const unsigned int (&v)[4
 #pragma unroll
     for (int q = 0; q < 4; q++) dst[q] = v[q];
 }
+// The general form of a tile load, for levels smaller than LK_JT on a side (a window may then reach further outside than the level is wide,
+// and reflect-101 is a loop): every byte through icg_reflect101, in loops over the tile's dwords and their bytes that are not unrolled — only
+// tests build such levels, and unrolled at its three call sites this form was most of the kernel's text.  It writes straight into LDS: the
+// caller has passed the barrier that the register forms put between their loads and their stores.  ROWS x DPR dwords, SD dwords of LDS row
+// stride; the same bytes at the same places as lk_load_I + lk_store_I (LK_IT, 6) and lk_load_J + lk_store_J (LK_JT, 8).  The trip count is
+// wave-uniform: lanes past the last dword repeat it (the same value to the same address).
+template <int ROWS, int DPR, int SD>
+__device__ __forceinline__ void lk_stage_small(unsigned int *dst, const unsigned char *img, int W, int H, int pitch, int x0, int y0, int lane) {
+#pragma unroll 1
+    for (int base = 0; base < ROWS * DPR; base += 64) {
+        const int i = min(base + lane, ROWS * DPR - 1);
+        const int r = i / DPR, cd = i - r * DPR;
+        const unsigned char *row = img + (size_t) icg_reflect101(y0 + r, H) * pitch;
+        unsigned int v = 0;
+#pragma unroll 1
+        for (int k = 0; k < 4; k++) v |= (unsigned int) row[icg_reflect101(x0 + 4 * cd + k, W)] << (8 * k);
+        dst[r * SD + cd] = v;
+    }
+}
+__device__ __forceinline__ bool lk_small_level(int W, int H) { return min(W, H) < LK_JT; } // wave-uniform
+// (re-)stage the J tile between two barriers of the caller's
 __device__ __forceinline__ void lk_stage_J(lk_smem &S, const unsigned char *J, int W, int H, int pitch, int jx0, int jy0,
                                            int lane) {
-    unsigned int v[4];
-    lk_load_J(v, J, W, H, pitch, jx0, jy0, lane);
-    lk_store_J(S, v, lane);
+    if (lk_small_level(W, H)) {
+        lk_stage_small<LK_JT, LK_JT / 4, LK_JS / 4>(S.J, J, W, H, pitch, jx0, jy0, lane);
+    } else {
+        unsigned int v[4];
+        lk_load_J(v, J, W, H, pitch, jx0, jy0, lane);
+        lk_store_J(S, v, lane);
+    }
 }
 
 typedef short s16x2 __attribute__((ext_vector_type(2)));
@@ -413,16 +529,24 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
         {
             const int inx0 = (int) floorf(nptx - (float) ICG_LK_HALF), iny0 = (int) floorf(npty - (float) ICG_LK_HALF);
             const bool jok = !(inx0 < -ICG_LK_WIN || inx0 >= W || iny0 < -ICG_LK_WIN || iny0 >= H); // else iteration 0 bails out
+            const bool small = lk_small_level(W, H);
             unsigned int vi[3] = {0, 0, 0}, vj[4] = {0, 0, 0, 0};
-            lk_load_I(vi, I, W, H, pitch, ipx, ipy, lane);
+            LK_HIST(level, 0, ipx - 1, ipy - 1, LK_IT);
+            if (!small) lk_load_I(vi, I, W, H, pitch, ipx, ipy, lane);
             if (jok) {
                 jx0 = inx0 - LK_JM;
                 jy0 = iny0 - LK_JM;
-                lk_load_J(vj, J, W, H, pitch, jx0, jy0, lane);
+                LK_HIST(level, 1, jx0, jy0, LK_JT);
+                if (!small) lk_load_J(vj, J, W, H, pitch, jx0, jy0, lane);
             }
             __syncthreads(); // previous level's LDS readers are done
-            lk_store_I(S, vi, lane);
-            if (jok) lk_store_J(S, vj, lane);
+            if (!small) {
+                lk_store_I(S, vi, lane);
+                if (jok) lk_store_J(S, vj, lane);
+            } else {
+                lk_stage_small<LK_IT, LK_IT / 4, LK_IS / 4>(S.I, I, W, H, pitch, ipx - 1, ipy - 1, lane);
+                if (jok) lk_stage_small<LK_JT, LK_JT / 4, LK_JS / 4>(S.J, J, W, H, pitch, jx0, jy0, lane);
+            }
             __syncthreads();
         }
 
@@ -619,6 +743,7 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
             if (!(inx >= jx0 && inx <= jx0 + (LK_JT - 22) && iny >= jy0 && iny <= jy0 + (LK_JT - 22))) {
                 jx0 = inx - LK_JM;
                 jy0 = iny - LK_JM;
+                LK_HIST(level, 2, jx0, jy0, LK_JT);
                 __syncthreads();
                 lk_stage_J(S, J, W, H, pitch, jx0, jy0, lane);
                 __syncthreads();
@@ -733,10 +858,13 @@ __global__ __launch_bounds__(64) void k_lk_track(icg_pyr_desc P, int n, const in
     }
 }
 
+// (Parameter order: inputs first, outputs last, and seg_count ahead of the four integers — the early exit then fetches seg_count, the sizes and
+// the magic without the output pointers, which the compiler otherwise loads with them and parks in VGPR lanes for the whole kernel: 10 SGPRs
+// parked with seg_count behind seg_magic, 2 in this order; profiles/r09_uniform_prologues.txt met the same with another order.)
 __global__ __launch_bounds__(64, LK_WAVES_PER_EU) void k_lk_track_fb(icg_pyr_desc P, int n, const int32_t *prev_slot,
                                                     const int32_t *next_slot, const float2 *prev_pts,
-                                                    const float2 *guess_pts, int img_w, int img_h,
-                                                    int seg_cap, unsigned int seg_magic, const int32_t *seg_count,
+                                                    const float2 *guess_pts, const int32_t *seg_count, int img_w, int img_h,
+                                                    int seg_cap, unsigned int seg_magic,
                                                     float2 *out_pts, unsigned char *status, float2 *out_bwd) {
     __shared__ lk_smem S;
     const int i = icg_xcd_chunked(blockIdx.x, n);
@@ -750,6 +878,9 @@ __global__ __launch_bounds__(64, LK_WAVES_PER_EU) void k_lk_track_fb(icg_pyr_des
         if (i - s * seg_cap >= seg_count[s]) return; // wave-uniform
     }
     const int lane = threadIdx.x;
+#if defined(LK_TILE_HIST)
+    if (lane == 0) atomicAdd(&g_lk_tile_points[0], 1ull);
+#endif
     lk_zero_rows(S, lane);
     const unsigned char *sP = P.base + (size_t) prev_slot[i] * P.slot_bytes;
     const unsigned char *sN = P.base + (size_t) next_slot[i] * P.slot_bytes;
@@ -769,6 +900,9 @@ __global__ __launch_bounds__(64, LK_WAVES_PER_EU) void k_lk_track_fb(icg_pyr_des
         const unsigned char *a = dir ? sN : sP, *b = dir ? sP : sN;
         const float2 from      = dir ? fwd : p0;
         float2 io              = dir ? bwd : fwd;
+#if defined(LK_TILE_HIST)
+        if (lane == 0) atomicAdd(&g_lk_tile_points[1], 1ull);
+#endif
         const bool st          = lk_track_wave(P, a, b, from, io, S, lane, nullptr);
         if (dir) {
             bwd  = io;
@@ -878,10 +1012,14 @@ extern "C" int icg_lk_track(icg_ctx *ctx, int n, const int32_t *prev_slot, const
 static void lk_fb_launch(icg_ctx *ctx, int n, int seg_cap, const int32_t *seg_count, bool want_undist, const int32_t *prev_slot, const int32_t *next_slot,
                          const float2 *prev, const float2 *guess, float2 *out, uint8_t *status, float2 *bwd_undist) {
     const unsigned int seg_magic = seg_count ? icg_div_magic(seg_cap) : 0u; // (0: divisor 1, and what an unsegmented call passes)
+#if defined(LK_TILE_HIST)
+    static std::once_flag hist_once;
+    std::call_once(hist_once, [] { atexit(lk_tile_hist_dump); });
+#endif
     {
         icg_prof_scope ps(ctx, "lk_track_fb");
         hipLaunchKernelGGL(k_lk_track_fb, dim3(icg_xcd_grid(n)), dim3(64), 0, ctx->stream, icg_make_pyr_desc(ctx), n, prev_slot, next_slot, prev, guess,
-                           ctx->cfg.width, ctx->cfg.height, seg_cap, seg_magic, seg_count, out, status, bwd_undist);
+                           seg_count, ctx->cfg.width, ctx->cfg.height, seg_cap, seg_magic, out, status, bwd_undist);
     }
     {
         icg_prof_scope ps(ctx, "lk_finish");
