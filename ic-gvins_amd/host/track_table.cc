@@ -1,5 +1,6 @@
-// Table engine of the front-end (see track_table.h).  Every function names the reference lines it follows; the object-graph twin
-// of each stage body is in tracking_hip.cc.
+// Table engine of the front-end (see track_table.h).  Every function names the reference lines it follows; the stage order and what
+// does not depend on the storage of frames and features is in staged_tracker.h, the object-graph twin of each list-building body in
+// tracking_hip.cc.
 #include "track_table.h"
 
 #include <algorithm>
@@ -295,24 +296,13 @@ void TableTracker::mapRemoveKeyFrame(int h, bool isremovemappoint) { // map.cc:8
     if (at >= 0) map_kf_.erase(map_kf_.begin() + at);
 }
 
-void TableTracker::writeTrackingLog(const double data5[5], int features, double cost_ms) {
-    if (!logfile_) return;
-    for (int k = 0; k < 5; k++) fprintf(logfile_, "%-15.9lf ", data5[k]);
-    fprintf(logfile_, "%-15.9lf %-15.9lf \n", static_cast<double>(features), cost_ms);
-    fflush(logfile_);
-}
-
 // Sliding-window stand-in (WindowKeeper::onFrame; ic_gvins.cc:542, 743, 1391-1410, 445-448, 1675)
 void TableTracker::endFrame() {
     if (core_) { // statistics, digest, window keeper and sweep are the core's (tc::stage_end_frame)
         // tracking.txt (:236-238, 309-315): the decision's numbers were kept by the core; the line is written when the frame ends as TRACKING
         if (logfile_ && core_->log_valid && core_->result == tc::TRACK_TRACKING && core_->mode == tc::M_TRACK && core_->lost_reset != 2) {
-            logging_data_.assign(core_->log_data, core_->log_data + 5);
-            logging_data_.push_back(static_cast<double>(core_->frame[core_->cur].n_rows));
-            logging_data_.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start_).count());
-            for (double v : logging_data_) fprintf(logfile_, "%-15.9lf ", v);
-            fprintf(logfile_, "\n");
-            fflush(logfile_);
+            writeTrackingLine(logfile_, core_->log_data, core_->frame[core_->cur].n_rows,
+                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start_).count());
         }
         tc::stage_end_frame(*core_, core_cfg_);
         core_dirty_ = true;
@@ -352,37 +342,16 @@ void TableTracker::endFrame() {
     sweepFrames();
 }
 
-// ---- construction (tracking.cc:32-86) --------------------------------------------------------------------------------------------
+// ---- construction (tracking.cc:32-86; the geometry of :57-85 is staged_tracker.h's trackGeometry) --------------------------------------
 TableTracker::TableTracker(Camera::Ptr camera, size_t window_size, const TrackingConfig &config, const std::string &outputpath,
                            DeviceContext::Ptr device, std::shared_ptr<IdSpace> ids)
-    : camera_(std::move(camera)), device_(std::move(device)), ids_(std::move(ids)), cfg_(config), window_size_(window_size) {
+    : Base(std::move(camera), config, std::move(device), std::move(ids)), window_size_(window_size) {
     if (cfg_.is_use_visualization) throw std::runtime_error("TableTracker: the drawer hooks need the object engine (icg::Tracking)");
-    if (!outputpath.empty()) {
-        logfile_ = fopen((outputpath + "/tracking.txt").c_str(), "w");
-        if (!logfile_) throw std::runtime_error("Tracking: failed to open " + outputpath + "/tracking.txt");
-    }
-    track_max_interval_ = cfg_.track_max_interval * 0.95; // :57
-    block_cols_ = static_cast<int>(lround(camera_->width() / TRACK_BLOCK_SIZE));  // :66
-    block_rows_ = static_cast<int>(lround(camera_->height() / TRACK_BLOCK_SIZE)); // :67
-    block_cnts_ = block_cols_ * block_rows_;
-    block_h_    = camera_->height() / block_rows_; // :71
-    block_w_    = camera_->width() / block_cols_;  // :72
-    track_max_block_features_ =
-        static_cast<int>(lround(static_cast<double>(cfg_.track_max_features) / static_cast<double>(block_cnts_))); // :81
-    track_min_pixel_distance_ = static_cast<int>(round(TRACK_BLOCK_SIZE / sqrt(track_max_block_features_ * 1.5))); // :85
-    grid_.block_cols    = block_cols_;
-    grid_.block_rows    = block_rows_;
-    grid_.block_w       = block_w_;
-    grid_.block_h       = block_h_;
-    grid_.min_dist      = track_min_pixel_distance_;
-    grid_.max_per_block = track_max_block_features_;
+    openLog(outputpath);
 }
 
 TableTracker::~TableTracker() {
-    if (logfile_) fclose(logfile_);
     for (int s : core_slots_) device_->freeSlot(s);
-    for (int s : owned_slots_) device_->freeSlot(s);
-    if (pending_slot_ >= 0) device_->freeSlot(pending_slot_);
 }
 
 ulong TableTracker::currentFrameId() const {
@@ -392,35 +361,6 @@ ulong TableTracker::currentFrameId() const {
 size_t TableTracker::numCurrentFeatures() const {
     if (core_) return core_->cur >= 0 ? (size_t) core_->frame[core_->cur].n_rows : 0;
     return cur_ >= 0 ? frames_[(size_t) cur_].rows() : 0;
-}
-
-// ---- helpers -------------------------------------------------------------------------------------------------------------------
-template <typename T> void TableTracker::reduceVector(T &vec, const vector<uint8_t> &status) { // :831-839
-    size_t index = 0;
-    for (size_t k = 0; k < vec.size(); k++)
-        if (status[k]) {
-            if (index != k) vec[index] = vec[k];
-            index++;
-        }
-    vec.resize(index);
-}
-
-bool TableTracker::isOnBorder(const Point2f &pts) const { // :847-849
-    return pts.x < 5.0 || pts.y < 5.0 || (pts.x > (camera_->width() - 5.0)) || (pts.y > (camera_->height() - 5.0));
-}
-
-bool TableTracker::isGoodToTrack(const Point2f &pp, const Pose &pose, const Vector3d &pw, double scale, double depth_scale) const { // :813-829
-    Vector3d pc = Camera::world2cam(pw, pose);
-    if (!((pc[2] > MapPoint::NEAREST_DEPTH) && (pc[2] < MapPoint::FARTHEST_DEPTH * depth_scale))) return false; // :247-249
-    if (camera_->reprojectionError(pose, pw, pp).norm() > cfg_.reprojection_error_std * scale) return false;
-    return true;
-}
-
-double TableTracker::keyPointParallax(const Point2f &pp0, const Point2f &pp1, const Matrix3d &R10) const { // :861-871
-    Vector3d pc0  = camera_->pixel2cam(pp0);
-    Vector3d pc1  = camera_->pixel2cam(pp1);
-    Vector3d pc01 = R10 * pc0;
-    return Vector2d(pc01[0] - pc1[0], pc01[1] - pc1[1]).norm() * camera_->focalLength();
 }
 
 // order_idx_ := the rows of f in container order; requests the rows and the map-point records of the first few (see queueTrackMappoint)
@@ -463,320 +403,36 @@ int TableTracker::parallaxFromReferenceMapPoints(double &parallax) { // :873-905
     return counts;
 }
 
-void TableTracker::checkCarriedUndistortion(const char *where) {
-    static const bool on = getenv("ICG_HOST_CHECK") != nullptr;
-    if (!on) return;
-    auto same = [&](const vector<Point2f> &src, const vector<Point2f> &carried, const char *what) {
-        if (src.size() != carried.size())
-            throw std::runtime_error(std::string("carried undistortion size mismatch (") + what + ") at " + where);
-        vector<Point2f> u = src;
-        camera_->undistortPoints(u);
-        for (size_t k = 0; k < u.size(); k++)
-            if (memcmp(&u[k], &carried[k], sizeof(Point2f)) != 0)
-                throw std::runtime_error(std::string("carried undistortion differs (") + what + ") at " + where);
-    };
-    same(pts2d_ref_, pts2d_ref_undis_, "ref");
-    if (where[0] == 't' && where[2] == 'i')
-        same(pts2d_cur_, tr_cur_undis_, "cur");
-    else
-        same(pts2d_new_, pts2d_new_undis_, "new");
-}
-
-int TableTracker::parallaxFromReferenceKeyPoints(const vector<Point2f> &ref, const vector<Point2f> &cur, double &parallax) { // :907-922
-    parallax   = 0;
-    int counts = 0;
-    const Matrix3d R10 = frames_[(size_t) cur_].pose.R.transpose() * frames_[(size_t) ref_].pose.R;
-    for (size_t k = 0; k < pts2d_ref_frame_.size(); k++) {
-        if (pts2d_ref_frame_[k] == ref_) {
-            parallax += keyPointParallax(ref[k], cur[k], R10);
-            counts++;
-        }
-    }
-    if (counts != 0) parallax /= counts;
-    return counts;
-}
-
-double TableTracker::relativeTranslation() const { return (frames_[(size_t) cur_].pose.t - frames_[(size_t) ref_].pose.t).norm(); } // :331-333
-
-double TableTracker::relativeRotation() const { // :335-341
-    Matrix3d R   = frames_[(size_t) cur_].pose.R.transpose() * frames_[(size_t) ref_].pose.R;
-    double pitch = atan(-R(2, 0) / sqrt(R(2, 1) * R(2, 1) + R(2, 2) * R(2, 2)));
-    return fabs(pitch * (180.0 / M_PI));
-}
-
-bool TableTracker::doResetTracking() { // :317-329
-    if (!frames_[(size_t) cur_].rows()) {
-        isinitializing_ = true;
-        ref_            = cur_;
-        pts2d_new_.clear();
-        pts2d_ref_.clear();
-        pts2d_ref_undis_.clear();
-        pts2d_new_undis_.clear();
-        pts2d_ref_frame_.clear();
-        velocity_ref_.clear();
-        cand_lk_idx_.clear();
-        return true;
-    }
-    return false;
-}
-
-void TableTracker::writeLoggingMessage() { // :309-315
-    logging_data_.push_back(static_cast<double>(frames_[(size_t) cur_].rows()));
-    logging_data_.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start_).count());
-    if (logfile_) {
-        for (double v : logging_data_) fprintf(logfile_, "%-15.9lf ", v);
-        fprintf(logfile_, "\n");
-        fflush(logfile_);
-    }
-}
-
-keyFrameState TableTracker::checkKeyFrameSate() { // :263-307
-    keyFrameState keyframe_state = KEYFRAME_NONE;
-    double dt                    = frames_[(size_t) cur_].stamp - frames_[(size_t) last_keyframe_].stamp;
-    if (dt < TRACK_MIN_INTERVAl) return keyframe_state;
-    double parallax = (parallax_map_ * parallax_map_counts_ + parallax_ref_ * parallax_ref_counts_) /
-                      (parallax_map_counts_ + parallax_ref_counts_);
-    if (parallax > cfg_.track_min_parallax) {
-        keyframe_state = mapIsWindowFull() ? KEYFRAME_REMOVE_OLDEST : KEYFRAME_NORMAL;
-    } else if (dt > track_max_interval_) {
-        keyframe_state = KEYFRAME_REMOVE_SECOND_NEW;
-    }
-    if (keyframe_state != KEYFRAME_NONE) {
-        last_keyframe_ = cur_;
-        for (const auto &m : tracked_mappoint_)
-            if (mps_.valid(m.i, m.g)) mps_.hot[m.i].used++;
-        logging_data_.clear();
-        logging_data_.push_back(frames_[(size_t) cur_].stamp);
-        logging_data_.push_back(dt);
-        logging_data_.push_back(parallax);
-        logging_data_.push_back(relativeTranslation());
-        logging_data_.push_back(relativeRotation());
-    }
-    return keyframe_state;
-}
-
-// ---- device slots ------------------------------------------------------------------------------------------------------------
-void TableTracker::assignSlot(int h) {
-    frames_[(size_t) h].slot = pending_slot_;
-    owned_slots_.push_back(pending_slot_);
-    pending_slot_ = -1;
-}
-
-void TableTracker::releaseUnusedSlots() {
-    size_t keep = 0;
-    for (int s : owned_slots_) {
-        bool used = (cur_ >= 0 && frames_[(size_t) cur_].slot == s) || (pre_ >= 0 && frames_[(size_t) pre_].slot == s) ||
-                    (ref_ >= 0 && frames_[(size_t) ref_].slot == s);
-        if (used)
-            owned_slots_[keep++] = s;
-        else
-            device_->freeSlot(s);
-    }
-    owned_slots_.resize(keep);
-}
-
-// ---- stage 0: preprocessing (tracking.cc:107-142) -------------------------------------------------------------------------------
+// ---- the staged interface: the state machine of staged_tracker.h, or the tracker core's (track_table_core.cc) ---------------------
 void TableTracker::beginFrame(const Input &in, StageBatch &next) {
     if (core_) return coreBeginFrame(in, next);
-    t_start_       = std::chrono::steady_clock::now();
-    done_          = false;
-    result_        = TRACK_PASSED;
-    isnewkeyframe_ = false; // :108
-    mode_          = M_NONE;
-    det_job_       = -1;
-    rs_set_        = -1;
-    tri_queued_    = false;
-    lk_map_n_ = lk_ref_n_ = 0;
-    ref_tracked_   = false;
-    pending_       = allocFrame();
-    Frame_ &f      = frames_[(size_t) pending_];
-    f.fid          = ids_->frame_id++; // frame.cc:37-40
-    last_input_fid_ = f.fid;
-    f.stamp        = in.stamp;
-    f.pose         = in.pose;
-    f.image        = in.image;
-    pending_slot_  = device_->allocSlot();
-    next.pre_slots.push_back(pending_slot_);
-    next.pre_imgs.push_back(in.image.data);
-    next.pre_stride   = (int) in.image.step;
-    next.pre_channels = in.image.channels();
-    next.pre_device   = in.image.device;
-    if (cfg_.track_check_histogram) next.pre_want_hist = true;
-    det_job_ = (int) next.pre_slots.size() - 1; // "preprocess job index" until stage 1
+    Base::beginFrame(in, next);
 }
 
 void TableTracker::advance(int stage, StageBatch &done, StageBatch &next) {
     if (core_) return coreAdvance(stage, done, next);
-    if (done_) return;
-    switch (stage) {
-    case 1: onPreprocessDone(done, next); break;
-    case 2: onDetectADone(done, next); break;
-    case 3: onLKDone(done, next); break;
-    case 4: onRansacDone(done, next); break;
-    case 5: onTriangulateDone(done, next); break;
-    case 6: onDetectBDone(done); break;
-    default: break;
-    }
+    Base::advance(stage, done, next);
 }
 
-void TableTracker::finish(TrackState st) {
-    result_ = st;
-    done_   = true;
-}
-
-void TableTracker::onPreprocessDone(StageBatch &done, StageBatch &next) {
-    if (cfg_.track_check_histogram) { // :115-133
-        double hist = done.pre_hist[(size_t) det_job_];
-        if (histogram_ != 0) {
-            double rate = fabs((hist - histogram_) / histogram_);
-            if (rate > 0.1) {
-                passed_cnt_++;
-                if (passed_cnt_ > 1) histogram_ = 0;
-                device_->freeSlot(pending_slot_);
-                pending_slot_ = -1;
-                freeFrame(pending_);
-                pending_ = -1;
-                finish(TRACK_PASSED);
-                return;
-            }
-        }
-        histogram_ = hist;
-    }
-    det_job_ = -1;
-    pre_     = cur_; // :135
-    cur_     = pending_;
-    pending_ = -1;
-    assignSlot(cur_);
-    releaseUnusedSlots();
-
-    if (isinitializing_) {
-        if (ref_ < 0) { // :158-166
-            doResetTracking();
-            ref_  = cur_;
-            mode_ = M_FIRST;
-            queueDetection(ref_, false, next);
-            return;
-        }
-        mode_ = M_INIT;
-        if (pts2d_ref_.empty()) queueDetection(ref_, false, next); // :168-170
-    } else {
-        mode_ = M_TRACK;
-    }
-}
-
-void TableTracker::onDetectADone(StageBatch &done, StageBatch &next) {
-    if (det_job_ >= 0) {
-        hostprof::Scope hp(hostprof::DET_INTEGRATE);
-        integrateDetection(done);
-    }
-    if (mode_ == M_FIRST) {
-        releaseUnusedSlots();
-        finish(TRACK_FIRST_FRAME);
-        return;
-    }
-    if (mode_ == M_TRACK) { // :206
-        hostprof::Scope hp(hostprof::QUEUE_MAP);
-        queueTrackMappoint(next);
-    }
-    hostprof::Scope hp(hostprof::QUEUE_REF);
-    queueTrackReference(next); // :173 / :209
-}
-
-void TableTracker::onLKDone(StageBatch &done, StageBatch &next) {
-    if (mode_ == M_TRACK) finishTrackMappoint(done);
-    ref_tracked_ = midTrackReference(done, next);
-}
-
-void TableTracker::onRansacDone(StageBatch &done, StageBatch &next) {
-    if (ref_tracked_) finishTrackReference(done);
-    if (mode_ == M_INIT) {
-        if (parallax_ref_ < cfg_.track_min_parallax) { // :175-178
-            finish(TRACK_INITIALIZING);
-            return;
-        }
-        queueTriangulation(next); // :182
-        return;
-    }
-    kf_state_ = checkKeyFrameSate(); // :212
-    if ((kf_state_ == KEYFRAME_NORMAL) || (kf_state_ == KEYFRAME_REMOVE_OLDEST)) queueTriangulation(next); // :215-217
-}
-
-void TableTracker::onTriangulateDone(StageBatch &done, StageBatch &next) {
-    if (tri_queued_) finishTriangulation(done);
-    if (mode_ == M_INIT) {
-        if (doResetTracking()) { // :184-190
-            lost_reset_ = 1;
-            makeNewFrameQueue(KEYFRAME_NORMAL, next);
-            return;
-        }
-        lost_reset_ = 0;
-        setKeyFrame(ref_, KEYFRAME_NORMAL);       // :193
-        makeNewFrameQueue(KEYFRAME_NORMAL, next); // :196
-        last_keyframe_  = cur_;
-        isinitializing_ = false;
-        return;
-    }
-    lost_reset_ = 0;
-    if (!frames_[(size_t) cur_].rows()) { // :224 (see tracking_hip.cc for why it may be evaluated before the :220 detection)
-        doResetTracking();
-        lost_reset_ = 2;
-        makeNewFrameQueue(KEYFRAME_NORMAL, next); // :225
-        return;
-    }
-    if ((kf_state_ == KEYFRAME_NORMAL) || (kf_state_ == KEYFRAME_REMOVE_OLDEST)) {
-        makeNewFrameQueue(kf_state_, next); // :230-232
-    } else {
-        queueDetection(cur_, true, next); // :220
-        if (kf_state_ != KEYFRAME_NONE) makeNewFrameQueue(kf_state_, next); // REMOVE_SECOND_NEW: flags only
-    }
-}
-
-void TableTracker::onDetectBDone(StageBatch &done) {
-    if (det_job_ >= 0) integrateDetection(done);
-    releaseUnusedSlots();
-    if (mode_ == M_INIT) {
-        if (lost_reset_ == 1) {
-            finish(TRACK_FIRST_FRAME);
-            return;
-        }
-        finish(TRACK_TRACKING);
-        return;
-    }
-    if (lost_reset_ == 2) {
-        finish(TRACK_LOST);
-        return;
-    }
-    if (kf_state_ != KEYFRAME_NONE) writeLoggingMessage(); // :236-238
-    finish(TRACK_TRACKING);
-}
-
-void TableTracker::makeNewFrameQueue(int state, StageBatch &next) { // :251-261
-    setKeyFrame(cur_, state);
-    isnewkeyframe_ = true;
-    if ((state == KEYFRAME_NORMAL) || (state == KEYFRAME_REMOVE_OLDEST)) {
-        ref_ = cur_;
-        queueDetection(ref_, true, next);
-    }
+// the frame handed to beginFrame (frame.cc:37-40)
+const Mat &TableTracker::setPending(const Input &in) {
+    pending_        = allocFrame();
+    Frame_ &f       = frames_[(size_t) pending_];
+    f.fid           = ids_->frame_id++;
+    last_input_fid_ = f.fid;
+    f.stamp         = in.stamp;
+    f.pose          = in.pose;
+    f.image         = in.image;
+    return in.image;
 }
 
 // ---- featuresDetection (:576-688) ------------------------------------------------------------------------------------------------
-bool TableTracker::queueDetection(int frame, bool ismask, StageBatch &next) {
-    det_job_         = -1;
-    const Frame_ &f  = frames_[(size_t) frame];
-    int num_features = static_cast<int>(f.rows() + pts2d_ref_.size()); // :579
-    if (num_features > (cfg_.track_max_features - 5)) return false;    // :580
+// the job's block counts and work lists; the head (:579-580) is StagedTracker::queueDetection
+void TableTracker::queueDetectionJob(int frame, bool ismask, StageBatch &next) {
+    const Frame_ &f = frames_[(size_t) frame];
     int features_cnts[256];
     if (block_cnts_ > 256) throw std::runtime_error("TableTracker: more than 256 detection blocks");
-    for (int k = 0; k < block_cnts_; k++) features_cnts[k] = 0;
-    auto count = [&](float x, float y) {
-        int col = int(x / (float) block_w_); // :598
-        int row = int(y / (float) block_h_);
-        // hazard H5 (unclamped column of an undistorted key point), reproduced as in tracking_hip.cc
-        const long idx = (long) row * block_cols_ + col;
-        if (idx >= 0 && idx < (long) block_cnts_) features_cnts[idx]++;
-    };
-    for (const Row &r : f.row) count(r.kp.x, r.kp.y);
-    for (auto &pts2d : pts2d_new_) count(pts2d.x, pts2d.y);
+    countBlockFeatures(frame, features_cnts);
     det_job_    = (int) next.det_slots.size();
     det_ismask_ = ismask;
     det_frame_  = frame;
@@ -791,37 +447,6 @@ bool TableTracker::queueDetection(int frame, bool ismask, StageBatch &next) {
     }
     next.det_mask_off.push_back((int32_t) (next.det_mask_pts.size() / 2));
     for (int k = 0; k < block_cnts_; k++) next.det_quota.push_back(track_max_block_features_ - features_cnts[k]); // :629
-    return true;
-}
-
-void TableTracker::integrateDetection(StageBatch &done) { // :659-685
-    if (!det_ismask_) {
-        pts2d_new_.clear();
-        pts2d_ref_.clear();
-        pts2d_ref_undis_.clear();
-        pts2d_new_undis_.clear();
-        pts2d_ref_frame_.clear();
-        velocity_ref_.clear();
-        cand_lk_idx_.clear();
-    }
-    const int max_per_job = maxFeaturesPerJob();
-    const int n           = done.det_count[(size_t) det_job_];
-    const float *p        = done.det_out.data() + (size_t) det_job_ * max_per_job * 2;
-    scratch_a_.resize((size_t) n);
-    for (int i = 0; i < n; i++) scratch_a_[(size_t) i] = Point2f(p[2 * i], p[2 * i + 1]);
-    scratch_b_ = scratch_a_;
-    camera_->undistortPoints(scratch_b_); // the one undistortion a detected corner ever needs
-    for (int i = 0; i < n; i++) {
-        pts2d_ref_.push_back(scratch_a_[(size_t) i]);
-        pts2d_new_.push_back(scratch_a_[(size_t) i]);
-        pts2d_ref_undis_.push_back(scratch_b_[(size_t) i]);
-        pts2d_new_undis_.push_back(scratch_b_[(size_t) i]);
-        pts2d_ref_frame_.push_back(det_frame_);
-        velocity_ref_.emplace_back(0, 0);
-    }
-    cand_lk_idx_.resize(pts2d_new_.size(), -1); // (a list that lost its alignment is padded / cut: hints are hints)
-    det_job_   = -1;
-    det_frame_ = -1;
 }
 
 // ---- trackMappoint (:351-455) ----------------------------------------------------------------------------------------------------

@@ -13,13 +13,16 @@
 // emulates libstdc++'s bucket list), because the parallax averages (tracking.cc:873-905) are floating-point sums in that order.
 // The B2 surface survives as a view: materialize() builds the reference-shaped icg::Map / Frame / Feature / MapPoint objects of a
 // stream on demand (tests compare them with what icg::Tracking built on the same frames).
+//
+// The state machine, the candidate lists and the stage order are staged_tracker.h's; this class is its table engine: the frame and
+// map-point pools, the window bookkeeping, the list-building bodies on rows, the object view and the core mode.
 #pragma once
 #include <cstdio>
 #include <string>
 #include <unordered_map>
 
 #include "tracking.h"
-#include "track_core.h"
+#include "track_core_arena.h"
 
 namespace icg {
 
@@ -87,7 +90,10 @@ private:
     int head_{-1};
 };
 
-class TableTracker {
+class TableTracker : public StagedTracker<TableTracker, int> {
+    typedef StagedTracker<TableTracker, int> Base;
+    friend Base;
+
 public:
     typedef std::shared_ptr<TableTracker> Ptr;
     struct Input {
@@ -115,7 +121,9 @@ public:
     void enableCore(bool device_resident = false);
     // the device-resident tracker's line of tracking.txt (tracking.cc:309-315): the five numbers of the keyframe decision and the feature
     // count come with the step's result (icg_tracker_result), the time cost is the executor's
-    void writeTrackingLog(const double data5[5], int features, double cost_ms);
+    void writeTrackingLog(const double data5[5], int features, double cost_ms) {
+        if (logfile_) writeTrackingLine(logfile_, data5, features, cost_ms);
+    }
     bool coreMode() const { return core_ != nullptr; }
     bool coreDeviceResident() const { return core_device_resident_; }
     // device-resident block: exportCore() ran since the last call (the executor uploads the block then) / the executor restarted the
@@ -159,8 +167,6 @@ public:
     // sliding-window side effects of GVINS on the map after a frame (WindowKeeper::onFrame) + release of dead frames
     void endFrame();
 
-    const icg_detect_grid &grid() const { return grid_; }
-    int maxFeaturesPerJob() const { return grid_.max_per_block * block_cnts_; }
     size_t numTrackedRefPoints() const { return core_ ? (size_t) core_->n_new : pts2d_new_.size(); }
     const vector<Point2f> &trackedRefPoints() const { return syncTable(), pts2d_new_; }
     const vector<Point2f> &referencePoints() const { return syncTable(), pts2d_ref_; }
@@ -282,21 +288,46 @@ private:
     // map (tracking/map.cc) on handles
     void mapInsertKeyFrame(int h);
     void mapRemoveKeyFrame(int h, bool isremovemappoint);
-    bool mapIsWindowFull() const { return is_window_full_; }
     bool mapIsWindowNormal() const { return map_kf_.size() == window_size_; }
     bool mapIsKeyFrameInMap(int h) const;
     int mapFind(ulong kf_id) const;
 
-    // stage bodies (tracking_hip.cc has the object-graph twins)
-    void onPreprocessDone(StageBatch &done, StageBatch &next);
-    void onDetectADone(StageBatch &done, StageBatch &next);
-    void onLKDone(StageBatch &done, StageBatch &next);
-    void onRansacDone(StageBatch &done, StageBatch &next);
-    void onTriangulateDone(StageBatch &done, StageBatch &next);
-    void onDetectBDone(StageBatch &done);
-    void finish(TrackState st);
-    bool queueDetection(int frame, bool ismask, StageBatch &next);
-    void integrateDetection(StageBatch &done);
+    // ---- what the staged state machine asks of its engine (staged_tracker.h) ----
+    static constexpr int nullFrame() { return -1; }
+    int &frameCur() { return cur_; }
+    int &frameRef() { return ref_; }
+    int &framePre() { return pre_; }
+    int &frameLastKey() { return last_keyframe_; }
+    size_t numFeatures(int h) const { return frames_[(size_t) h].rows(); }
+    double stamp(int h) const { return frames_[(size_t) h].stamp; }
+    const Pose &pose(int h) const { return frames_[(size_t) h].pose; }
+    int deviceSlot(int h) const { return frames_[(size_t) h].slot; }
+    void setDeviceSlot(int h, int slot) { frames_[(size_t) h].slot = slot; }
+    template <typename F> void forEachKeyPoint(int h, F &&fn) const {
+        for (const Row &r : frames_[(size_t) h].row) fn(r.kp.x, r.kp.y);
+    }
+    const Mat &setPending(const Input &in);
+    int takePending() {
+        const int h = pending_;
+        pending_    = -1;
+        return h;
+    }
+    void dropPending() { freeFrame(takePending()); }
+    bool isWindowFull() const { return is_window_full_; }
+    void bumpTrackedUsedTimes() {
+        for (const auto &m : tracked_mappoint_)
+            if (mps_.valid(m.i, m.g)) mps_.hot[m.i].used++;
+    }
+    struct ScratchPoints {
+        vector<Point2f> &a, &b;
+    };
+    ScratchPoints detectionScratch() { return {scratch_a_, scratch_b_}; }
+    void detectionIntegrated(int) { cand_lk_idx_.resize(pts2d_new_.size(), -1); } // (a list that lost its alignment is padded / cut: hints are hints)
+    void clearCandidateHints() { cand_lk_idx_.clear(); }
+    typedef hostprof::Scope StageScope;
+
+    // the list-building bodies on rows
+    void queueDetectionJob(int frame, bool ismask, StageBatch &next);
     void queueTrackMappoint(StageBatch &next);
     bool finishTrackMappoint(StageBatch &done);
     void queueTrackReference(StageBatch &next);
@@ -304,30 +335,7 @@ private:
     bool finishTrackReference(StageBatch &done);
     bool queueTriangulation(StageBatch &next);
     void finishTriangulation(StageBatch &done);
-    void makeNewFrameQueue(int state, StageBatch &next);
-    keyFrameState checkKeyFrameSate();
-    void writeLoggingMessage();
-    bool doResetTracking();
-    double relativeTranslation() const;
-    double relativeRotation() const;
-    int parallaxFromReferenceKeyPoints(const vector<Point2f> &ref, const vector<Point2f> &cur, double &parallax);
     int parallaxFromReferenceMapPoints(double &parallax);
-    double keyPointParallax(const Point2f &pp0, const Point2f &pp1, const Matrix3d &R10) const;
-    bool isGoodToTrack(const Point2f &pp, const Pose &pose, const Vector3d &pw, double scale, double depth_scale) const;
-    bool isOnBorder(const Point2f &pts) const;
-    void checkCarriedUndistortion(const char *where);
-    void assignSlot(int h);
-    void releaseUnusedSlots();
-    template <typename T> static void reduceVector(T &vec, const vector<uint8_t> &status);
-
-    const double TRACK_BLOCK_SIZE   = 200.0; // tracking.h:112
-    const double TRACK_MIN_PARALLAX = 10.0;  // tracking.h:114
-    const double TRACK_MIN_INTERVAl = 0.08;  // tracking.h:115
-
-    Camera::Ptr camera_;
-    DeviceContext::Ptr device_;
-    std::shared_ptr<IdSpace> ids_;
-    TrackingConfig cfg_;
 
     vector<Frame_> frames_;
     vector<int> free_frames_;
@@ -350,54 +358,19 @@ private:
     typedef std::unordered_map<ulong, uint32_t, std::hash<ulong>, std::equal_to<ulong>, PoolAllocator<std::pair<const ulong, uint32_t>>> LandmarkOrder;
     LandmarkOrder map_lm_;
 
-    // candidates (tracking.h:129-136)
-    vector<Point2f> pts2d_cur_, pts2d_new_, pts2d_ref_, pts2d_ref_undis_, pts2d_new_undis_;
-    vector<int> pts2d_ref_frame_;
     vector<int32_t> cand_lk_idx_; // per candidate: index of the LK point that produced pts2d_new_[k] in the group's last LK call (-1: detected)
-    vector<Vector2d> velocity_ref_, velocity_cur_;
     struct MpRef {
         uint32_t i, g;
     };
     vector<MpRef> tracked_mappoint_, mappoint_matched_;
 
-    int block_cols_, block_rows_, block_cnts_, block_w_, block_h_, track_max_block_features_;
-    icg_detect_grid grid_{};
-    double parallax_map_{0}, parallax_ref_{0};
-    int parallax_map_counts_{0}, parallax_ref_counts_{0};
-    bool isnewkeyframe_{false}, isinitializing_{true};
-    double histogram_{0};
-    int passed_cnt_{0};
-    int track_min_pixel_distance_;
-    double track_max_interval_;
-    FILE *logfile_{nullptr};
-    std::chrono::steady_clock::time_point t_start_;
-    vector<double> logging_data_;
-
-    // per-frame staged state
-    bool done_{true};
-    TrackState result_{TRACK_PASSED};
-    int pending_slot_{-1};
-    vector<int> owned_slots_;
-    enum Mode { M_NONE, M_FIRST, M_INIT, M_TRACK } mode_{M_NONE};
-    int det_job_{-1};
-    bool det_ismask_{true};
-    int det_frame_{-1};
-    int lk_map_begin_{0}, lk_map_n_{0}, lk_ref_begin_{0}, lk_ref_n_{0};
     vector<Point2f> tm_pts2d_map_, tm_pred_;
     vector<double> tm_pc_;
     vector<int32_t> tm_hint_;
     vector<int> order_idx_; // rows of a frame in container order (scratch)
     static constexpr size_t kAhead = 8; // prefetch distance of the per-row loops, in rows
-    bool ref_tracked_{false};
-    int rs_set_{-1};
-    vector<Point2f> tr_new_undis_, tr_cur_undis_;
-    keyFrameState kf_state_{KEYFRAME_NONE};
-    bool tri_queued_{false};
-    int tri_begin_{0};
-    vector<int> tri_point_index_;
-    vector<uint8_t> tri_status_, status_;
-    vector<Point2f> tri_ref_undis_, tri_cur_undis_, scratch_a_, scratch_b_;
-    int lost_reset_{0};
+    vector<uint8_t> status_;
+    vector<Point2f> scratch_a_, scratch_b_;
     ulong last_input_fid_{0};
     vector<uint8_t> mark_;
 
@@ -414,16 +387,8 @@ private:
     int core_log_applied_{0};      // entries of core_->log already replayed into map_lm_
     vector<int> core_slots_;       // the device slots reserved for this stream (core slot pool)
     Mat core_image_format_;        // rows / cols / channels / step / device flag of the stream's frames (the block keeps addresses only)
-    struct CoreArena {             // this stream's segment of the primitives' work lists (track_core.h Io)
-        int32_t pre_slot{-1}, lk_count{0}, rs_count{0}, tri_count{0}, tri_n_tcw{0}, det_slot{-1}, det_mask_count{0}, det_count{0};
-        double pre_hist{0};
-        vector<int32_t> lk_prev_slot, lk_next_slot, tri_T0, tri_T1, det_quota;
-        vector<tc::P2f> lk_prev, lk_guess, lk_out, lk_undist, rs_p1, rs_p2, det_mask_pts, det_out;
-        vector<uint8_t> lk_status, rs_mask;
-        vector<double> tri_Tcw, tri_pc0, tri_pc1, tri_pw;
-    } arena_;
+    tc::HostArena arena_;          // this stream's segment of the primitives' work lists (track_core.h Io)
     int core_pre_job_{-1}, core_det_job_{-1};
-    tc::Io coreIo(int lk_base);
     void coreBeginFrame(const Input &in, StageBatch &next);
     void coreAdvance(int stage, StageBatch &done, StageBatch &next);
     void coreQueueOutputs(StageBatch &next, bool pre, bool det, bool lk, bool rs, bool tri);

@@ -33,17 +33,10 @@ tc::Cfg TableTracker::makeCoreCfg(const Camera &camera, const TrackingConfig &cf
     C.window_size            = (int) window_size;
     C.track_min_parallax     = cfg.track_min_parallax;
     C.reprojection_error_std = cfg.reprojection_error_std;
-    C.track_max_interval     = cfg.track_max_interval * 0.95; // tracking.cc:57
-    // tracking.cc:66-85
-    const double TRACK_BLOCK_SIZE = 200.0;
-    C.block_cols         = static_cast<int>(lround(camera.width() / TRACK_BLOCK_SIZE));
-    C.block_rows         = static_cast<int>(lround(camera.height() / TRACK_BLOCK_SIZE));
-    C.block_cnts         = C.block_cols * C.block_rows;
-    C.block_h            = camera.height() / C.block_rows;
-    C.block_w            = camera.width() / C.block_cols;
-    C.max_block_features = static_cast<int>(lround(static_cast<double>(cfg.track_max_features) / static_cast<double>(C.block_cnts)));
-    C.min_pixel_distance = static_cast<int>(round(TRACK_BLOCK_SIZE / sqrt(C.max_block_features * 1.5)));
-    C.max_per_job        = C.max_block_features * C.block_cnts;
+    const TrackGeometry g    = trackGeometry(camera, cfg); // tracking.cc:57-85
+    C.track_max_interval     = g.track_max_interval;
+    C.block_cols = g.block_cols, C.block_rows = g.block_rows, C.block_cnts = g.block_cnts, C.block_h = g.block_h, C.block_w = g.block_w;
+    C.max_block_features = g.max_block_features, C.min_pixel_distance = g.min_pixel_distance, C.max_per_job = g.max_per_job;
     if (C.block_cnts > tc::MAX_BLOCKS) throw std::runtime_error("tracker core: more detection blocks than MAX_BLOCKS");
     if ((int) window_size + 2 > tc::MAX_WINDOW) throw std::runtime_error("tracker core: window larger than MAX_WINDOW");
     if (C.max_per_job + 64 > tc::MAX_ROWS) throw std::runtime_error("tracker core: feature budget larger than MAX_ROWS");
@@ -66,31 +59,10 @@ void TableTracker::enableCore(bool device_resident) {
         for (int k = 0; k < tc::MAX_SLOTS; k++) S->free_slots[k] = core_slots_[(size_t) (tc::MAX_SLOTS - 1 - k)];
         S->n_free_slots = tc::MAX_SLOTS;
     }
-    arena_.lk_prev_slot.resize(tc::MAX_ROWS), arena_.lk_next_slot.resize(tc::MAX_ROWS);
-    arena_.lk_prev.resize(tc::MAX_ROWS), arena_.lk_guess.resize(tc::MAX_ROWS), arena_.lk_out.resize(tc::MAX_ROWS), arena_.lk_undist.resize(tc::MAX_ROWS);
-    arena_.lk_status.resize(tc::MAX_ROWS), arena_.rs_mask.resize(tc::MAX_ROWS);
-    arena_.rs_p1.resize(tc::MAX_ROWS), arena_.rs_p2.resize(tc::MAX_ROWS);
-    arena_.tri_T0.resize(tc::MAX_ROWS), arena_.tri_T1.resize(tc::MAX_ROWS);
-    arena_.tri_Tcw.resize(12 * tc::MAX_TCW), arena_.tri_pc0.resize(3 * tc::MAX_ROWS), arena_.tri_pc1.resize(3 * tc::MAX_ROWS), arena_.tri_pw.resize(3 * tc::MAX_ROWS);
-    arena_.det_quota.resize(tc::MAX_BLOCKS), arena_.det_mask_pts.resize(tc::MAX_ROWS), arena_.det_out.resize(tc::MAX_ROWS);
+    arena_.resize();
     core_scratch_.reset(new tc::Scratch);
     core_dirty_       = true;
     core_log_applied_ = 0;
-}
-
-tc::Io TableTracker::coreIo(int lk_base) {
-    tc::Io io;
-    memset(&io, 0, sizeof io);
-    io.pre_slot = &arena_.pre_slot, io.pre_hist = &arena_.pre_hist;
-    io.lk_count = &arena_.lk_count, io.lk_prev_slot = arena_.lk_prev_slot.data(), io.lk_next_slot = arena_.lk_next_slot.data();
-    io.lk_prev = arena_.lk_prev.data(), io.lk_guess = arena_.lk_guess.data(), io.lk_out = arena_.lk_out.data(), io.lk_undist = arena_.lk_undist.data();
-    io.lk_status = arena_.lk_status.data(), io.lk_base = lk_base;
-    io.rs_count = &arena_.rs_count, io.rs_p1 = arena_.rs_p1.data(), io.rs_p2 = arena_.rs_p2.data(), io.rs_mask = arena_.rs_mask.data();
-    io.tri_count = &arena_.tri_count, io.tri_n_tcw = &arena_.tri_n_tcw, io.tri_T0 = arena_.tri_T0.data(), io.tri_T1 = arena_.tri_T1.data();
-    io.tri_Tcw = arena_.tri_Tcw.data(), io.tri_pc0 = arena_.tri_pc0.data(), io.tri_pc1 = arena_.tri_pc1.data(), io.tri_pw = arena_.tri_pw.data();
-    io.det_slot = &arena_.det_slot, io.det_quota = arena_.det_quota.data(), io.det_mask_count = &arena_.det_mask_count;
-    io.det_mask_pts = arena_.det_mask_pts.data(), io.det_count = &arena_.det_count, io.det_out = arena_.det_out.data();
-    return io;
 }
 
 // what the stage body left in the stream's arena goes into the stage batch of the host executor (which concatenates the streams' lists)
@@ -134,7 +106,7 @@ void TableTracker::coreQueueOutputs(StageBatch &next, bool pre, bool det, bool l
 
 void TableTracker::coreBeginFrame(const Input &in, StageBatch &next) {
     t_start_  = std::chrono::steady_clock::now();
-    tc::Io io = coreIo(0);
+    tc::Io io = arena_.io(0);
     tc::Pose pose;
     poseToArray12(in.pose, pose.R); // R row-major then t: the 12 doubles of tc::Pose
     core_image_format_      = in.image;
@@ -156,7 +128,7 @@ void TableTracker::coreAdvance(int stage, StageBatch &done, StageBatch &next) {
     tc::Stream &S = *core_;
     if (S.done) return;
     const uint32_t *ba = bucketsAfterTable();
-    tc::Io io          = coreIo(done.lk_base);
+    tc::Io io          = arena_.io(done.lk_base);
     auto take_detection = [&] {
         if (core_det_job_ < 0) return;
         const int max_per_job = maxFeaturesPerJob();

@@ -165,78 +165,32 @@ void DeviceContext::execute(StageBatch &b, const icg_detect_grid &grid, int max_
     }
 }
 
-// ---- construction (tracking.cc:32-86) ----------------------------------------------------------------------------
-Tracking::Tracking(Camera::Ptr camera, Map::Ptr map, Drawer::Ptr drawer, const std::string &configfile,
-                   const std::string &outputpath)
-    : camera_(std::move(camera)), map_(std::move(map)), drawer_(std::move(drawer)), ids_(IdSpace::global()) {
+// ---- construction (tracking.cc:32-86; the geometry of :57-85 is staged_tracker.h's trackGeometry) -----------------------------------
+static TrackingConfig configFromFile(const std::string &configfile) {
+    TrackingConfig cfg;
     std::string err;
-    if (!TrackingConfig::fromYamlFile(configfile, cfg_, &err)) throw std::runtime_error("Tracking: " + err);
-    device_ = std::make_shared<DeviceContext>(0, camera_->width(), camera_->height(), 1, cfg_.track_max_features);
-    device_->setCamera(*camera_);
-    init(outputpath);
+    if (!TrackingConfig::fromYamlFile(configfile, cfg, &err)) throw std::runtime_error("Tracking: " + err);
+    return cfg;
 }
+
+static DeviceContext::Ptr ownDevice(const Camera &camera, const TrackingConfig &cfg) {
+    auto device = std::make_shared<DeviceContext>(0, camera.width(), camera.height(), 1, cfg.track_max_features);
+    device->setCamera(camera);
+    return device;
+}
+
+Tracking::Tracking(Camera::Ptr camera, Map::Ptr map, Drawer::Ptr drawer, const std::string &configfile, const std::string &outputpath)
+    : Tracking(std::move(camera), std::move(map), std::move(drawer), configFromFile(configfile), outputpath) {}
+
+Tracking::Tracking(Camera::Ptr camera, Map::Ptr map, Drawer::Ptr drawer, const TrackingConfig &config, const std::string &outputpath)
+    : Tracking(camera, std::move(map), std::move(drawer), config, outputpath, ownDevice(*camera, config), IdSpace::global()) {}
 
 Tracking::Tracking(Camera::Ptr camera, Map::Ptr map, Drawer::Ptr drawer, const TrackingConfig &config,
                    const std::string &outputpath, DeviceContext::Ptr device, std::shared_ptr<IdSpace> ids)
-    : camera_(std::move(camera)), map_(std::move(map)), drawer_(std::move(drawer)), device_(std::move(device)),
-      ids_(std::move(ids)), cfg_(config) {
-    init(outputpath);
-}
-
-void Tracking::init(const std::string &outputpath) {
+    : Base(std::move(camera), config, std::move(device), std::move(ids)), map_(std::move(map)), drawer_(std::move(drawer)) {
     if (!drawer_) drawer_ = std::make_shared<Drawer>(); // the reference dereferences it unconditionally (:515,:559)
     if (cfg_.is_use_visualization) Frame::retainRawImages(true); // the drawer reads frame->rawImage()
-    if (!outputpath.empty()) { // :44-50; the reference logs an error and leaves the tracker half-constructed, this one throws
-        logfile_ = fopen((outputpath + "/tracking.txt").c_str(), "w");
-        if (!logfile_) throw std::runtime_error("Tracking: failed to open " + outputpath + "/tracking.txt");
-    }
-    track_max_interval_ = cfg_.track_max_interval * 0.95; // :57
-    block_cols_ = static_cast<int>(lround(camera_->width() / TRACK_BLOCK_SIZE));  // :66
-    block_rows_ = static_cast<int>(lround(camera_->height() / TRACK_BLOCK_SIZE)); // :67
-    block_cnts_ = block_cols_ * block_rows_;
-    block_h_    = camera_->height() / block_rows_; // :71
-    block_w_    = camera_->width() / block_cols_;  // :72
-    track_max_block_features_ =
-        static_cast<int>(lround(static_cast<double>(cfg_.track_max_features) / static_cast<double>(block_cnts_))); // :81
-    track_min_pixel_distance_ = static_cast<int>(round(TRACK_BLOCK_SIZE / sqrt(track_max_block_features_ * 1.5))); // :85
-    grid_.block_cols    = block_cols_;
-    grid_.block_rows    = block_rows_;
-    grid_.block_w       = block_w_;
-    grid_.block_h       = block_h_;
-    grid_.min_dist      = track_min_pixel_distance_;
-    grid_.max_per_block = track_max_block_features_;
-}
-
-Tracking::~Tracking() {
-    if (logfile_) fclose(logfile_);
-    for (int s : owned_slots_) device_->freeSlot(s);
-    if (pending_slot_ >= 0) device_->freeSlot(pending_slot_);
-}
-
-// ---- helpers ---------------------------------------------------------------------------------------------------
-template <typename T> void Tracking::reduceVector(T &vec, const vector<uint8_t> &status) { // :831-839
-    size_t index = 0;
-    for (size_t k = 0; k < vec.size(); k++)
-        if (status[k]) {
-            if (index != k) vec[index] = std::move(vec[k]); // (shared_ptr lists: no reference-count round trip per kept element)
-            index++;
-        }
-    vec.resize(index);
-}
-
-bool Tracking::isOnBorder(const Point2f &pts) { // :847-849
-    return pts.x < 5.0 || pts.y < 5.0 || (pts.x > (camera_->width() - 5.0)) || (pts.y > (camera_->height() - 5.0));
-}
-
-bool Tracking::isGoodDepth(double depth, double scale) { // :247-249
-    return ((depth > MapPoint::NEAREST_DEPTH) && (depth < MapPoint::FARTHEST_DEPTH * scale));
-}
-
-bool Tracking::isGoodToTrack(const Point2f &pp, const Pose &pose, const Vector3d &pw, double scale, double depth_scale) { // :813-829
-    Vector3d pc = Camera::world2cam(pw, pose);
-    if (!isGoodDepth(pc[2], depth_scale)) return false;
-    if (camera_->reprojectionError(pose, pw, pp).norm() > cfg_.reprojection_error_std * scale) return false;
-    return true;
+    openLog(outputpath);
 }
 
 Matrix4d Tracking::pose2Tcw(const Pose &pose) { // :851-859
@@ -249,20 +203,6 @@ Matrix4d Tracking::pose2Tcw(const Pose &pose) { // :851-859
         T(i, 3) = -t[i];
     }
     return T;
-}
-
-double Tracking::keyPointParallax(const Point2f &pp0, const Point2f &pp1, const Pose &pose0, const Pose &pose1) { // :861-871
-    Vector3d pc0  = camera_->pixel2cam(pp0);
-    Vector3d pc1  = camera_->pixel2cam(pp1);
-    Vector3d pc01 = (pose1.R.transpose() * pose0.R) * pc0;
-    return Vector2d(pc01[0] - pc1[0], pc01[1] - pc1[1]).norm() * camera_->focalLength();
-}
-
-double Tracking::keyPointParallax(const Point2f &pp0, const Point2f &pp1, const Matrix3d &R10) {
-    Vector3d pc0  = camera_->pixel2cam(pp0);
-    Vector3d pc1  = camera_->pixel2cam(pp1);
-    Vector3d pc01 = R10 * pc0;
-    return Vector2d(pc01[0] - pc1[0], pc01[1] - pc1[1]).norm() * camera_->focalLength();
 }
 
 int Tracking::parallaxFromReferenceMapPoints(double &parallax) { // :873-905
@@ -294,317 +234,16 @@ static bool debugTriangulation() {
     return on;
 }
 
-// ICG_HOST_CHECK=1: the carried undistorted twins must equal a fresh Camera::undistortPoints of their sources, bit for bit
-void Tracking::checkCarriedUndistortion(const char *where) {
-    static const bool on = getenv("ICG_HOST_CHECK") != nullptr;
-    if (!on) return;
-    auto same = [&](const vector<Point2f> &src, const vector<Point2f> &carried, const char *what) {
-        if (src.size() != carried.size())
-            throw std::runtime_error(std::string("carried undistortion size mismatch (") + what + ") at " + where);
-        vector<Point2f> u = src;
-        camera_->undistortPoints(u);
-        for (size_t k = 0; k < u.size(); k++)
-            if (memcmp(&u[k], &carried[k], sizeof(Point2f)) != 0)
-                throw std::runtime_error(std::string("carried undistortion differs (") + what + ") at " + where);
-    };
-    same(pts2d_ref_, pts2d_ref_undis_, "ref");
-    if (where[0] == 't' && where[2] == 'i') // "triangulation": pts2d_new_ is stale here, pts2d_cur_ is live
-        same(pts2d_cur_, tr_cur_undis_, "cur");
-    else
-        same(pts2d_new_, pts2d_new_undis_, "new");
-}
-
-int Tracking::parallaxFromReferenceKeyPoints(const vector<Point2f> &ref, const vector<Point2f> &cur, double &parallax) { // :907-922
-    parallax   = 0;
-    int counts = 0;
-    const Matrix3d R10 = frame_cur_->pose().R.transpose() * frame_ref_->pose().R;
-    for (size_t k = 0; k < pts2d_ref_frame_.size(); k++) {
-        if (pts2d_ref_frame_[k] == frame_ref_) {
-            parallax += keyPointParallax(ref[k], cur[k], R10);
-            counts++;
-        }
-    }
-    if (counts != 0) parallax /= counts;
-    return counts;
-}
-
-double Tracking::relativeTranslation() { return (frame_cur_->pose().t - frame_ref_->pose().t).norm(); } // :331-333
-
-double Tracking::relativeRotation() { // :335-341 (Rotation::matrix2euler pitch component, common/rotation.h:47)
-    Matrix3d R   = frame_cur_->pose().R.transpose() * frame_ref_->pose().R;
-    double pitch = atan(-R(2, 0) / sqrt(R(2, 1) * R(2, 1) + R(2, 2) * R(2, 2)));
-    return fabs(pitch * (180.0 / M_PI));
-}
-
 void Tracking::showTracking() { // :343-349
     if (!cfg_.is_use_visualization) return;
     drawer_->updateFrame(frame_cur_);
 }
 
-bool Tracking::doResetTracking() { // :317-329
-    if (!frame_cur_->numFeatures()) {
-        isinitializing_ = true;
-        frame_ref_      = frame_cur_;
-        pts2d_new_.clear();
-        pts2d_ref_.clear();
-        pts2d_ref_undis_.clear();
-        pts2d_new_undis_.clear();
-        pts2d_ref_frame_.clear();
-        velocity_ref_.clear();
-        return true;
-    }
-    return false;
-}
-
-void Tracking::writeLoggingMessage() { // :309-315 ; FileSaver text format "%-15.9lf " (fileio/filesaver.cc:51-66)
-    logging_data_.push_back(static_cast<double>(frame_cur_->numFeatures()));
-    logging_data_.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start_).count());
-    if (logfile_) {
-        for (double v : logging_data_) fprintf(logfile_, "%-15.9lf ", v);
-        fprintf(logfile_, "\n");
-        fflush(logfile_);
-    }
-}
-
-keyFrameState Tracking::checkKeyFrameSate() { // :263-307
-    keyFrameState keyframe_state = KEYFRAME_NONE;
-    double dt                    = frame_cur_->stamp() - last_keyframe_->stamp();
-    if (dt < TRACK_MIN_INTERVAl) return keyframe_state;
-    double parallax = (parallax_map_ * parallax_map_counts_ + parallax_ref_ * parallax_ref_counts_) /
-                      (parallax_map_counts_ + parallax_ref_counts_);
-    if (parallax > cfg_.track_min_parallax) {
-        keyframe_state = map_->isWindowFull() ? KEYFRAME_REMOVE_OLDEST : KEYFRAME_NORMAL;
-    } else if (dt > track_max_interval_) {
-        keyframe_state = KEYFRAME_REMOVE_SECOND_NEW;
-    }
-    if (keyframe_state != KEYFRAME_NONE) {
-        last_keyframe_ = frame_cur_;
-        for (auto &mappoint : tracked_mappoint_) mappoint->increaseUsedTimes();
-        logging_data_.clear();
-        logging_data_.push_back(frame_cur_->stamp());
-        logging_data_.push_back(dt);
-        logging_data_.push_back(parallax);
-        logging_data_.push_back(relativeTranslation());
-        logging_data_.push_back(relativeRotation());
-    }
-    return keyframe_state;
-}
-
-// ---- device slots: at most {ref, pre, cur, incoming} are resident per stream ----------------------------------------
-void Tracking::assignSlot(const Frame::Ptr &f) {
-    f->setDeviceSlot(pending_slot_);
-    owned_slots_.push_back(pending_slot_);
-    pending_slot_ = -1;
-}
-
-void Tracking::releaseUnusedSlots() {
-    vector<int> keep;
-    for (int s : owned_slots_) {
-        bool used = (frame_cur_ && frame_cur_->deviceSlot() == s) || (frame_pre_ && frame_pre_->deviceSlot() == s) ||
-                    (frame_ref_ && frame_ref_->deviceSlot() == s);
-        if (used)
-            keep.push_back(s);
-        else
-            device_->freeSlot(s);
-    }
-    owned_slots_.swap(keep);
-}
-
-// ---- stage 0: preprocessing (tracking.cc:107-142) ------------------------------------------------------------------
-void Tracking::beginFrame(Frame::Ptr frame, StageBatch &next) {
-    t_start_       = std::chrono::steady_clock::now(); // timecost_.restart() :147
-    done_          = false;
-    result_        = TRACK_PASSED;
-    isnewkeyframe_ = false; // :108
-    mode_          = M_NONE;
-    det_job_       = -1;
-    rs_set_        = -1;
-    tri_queued_    = false;
-    lk_map_n_ = lk_ref_n_ = 0;
-    ref_tracked_   = false;
-    pending_frame_ = std::move(frame);
-    pending_slot_  = device_->allocSlot();
-    Mat &img       = pending_frame_->image();
-    next.pre_slots.push_back(pending_slot_);
-    next.pre_imgs.push_back(img.data);
-    next.pre_stride   = (int) img.step;
-    next.pre_channels = img.channels(); // BGR->gray on device (:111-113)
-    next.pre_device   = img.device;
-    if (cfg_.track_check_histogram) next.pre_want_hist = true;
-    // remember which job is ours
-    det_job_ = (int) next.pre_slots.size() - 1; // reused as "preprocess job index" until stage 1
-}
-
-void Tracking::advance(int stage, StageBatch &done, StageBatch &next) {
-    if (done_) return;
-    switch (stage) {
-    case 1: onPreprocessDone(done, next); break;
-    case 2: onDetectADone(done, next); break;
-    case 3: onLKDone(done, next); break;
-    case 4: onRansacDone(done, next); break;
-    case 5: onTriangulateDone(done, next); break;
-    case 6: onDetectBDone(done); break;
-    default: break;
-    }
-}
-
-void Tracking::finish(TrackState st) {
-    result_ = st;
-    done_   = true;
-}
-
-void Tracking::onPreprocessDone(StageBatch &done, StageBatch &next) {
-    if (cfg_.track_check_histogram) { // :115-133
-        double hist = done.pre_hist[(size_t) det_job_];
-        if (histogram_ != 0) {
-            double rate = fabs((hist - histogram_) / histogram_);
-            if (rate > 0.1) {
-                passed_cnt_++;
-                if (passed_cnt_ > 1) histogram_ = 0;
-                device_->freeSlot(pending_slot_);
-                pending_slot_ = -1;
-                pending_frame_.reset();
-                finish(TRACK_PASSED);
-                return;
-            }
-        }
-        histogram_ = hist;
-    }
-    det_job_   = -1;
-    frame_pre_ = frame_cur_; // :135
-    frame_cur_ = std::move(pending_frame_);
-    assignSlot(frame_cur_);
-    releaseUnusedSlots();
-
-    if (isinitializing_) {
-        if (frame_ref_ == nullptr) { // :158-166
-            doResetTracking();
-            frame_ref_ = frame_cur_;
-            mode_      = M_FIRST;
-            queueDetection(frame_ref_, false, next);
-            return;
-        }
-        mode_ = M_INIT;
-        if (pts2d_ref_.empty()) queueDetection(frame_ref_, false, next); // :168-170
-    } else {
-        mode_ = M_TRACK;
-    }
-}
-
-void Tracking::onDetectADone(StageBatch &done, StageBatch &next) {
-    if (det_job_ >= 0) integrateDetection(done);
-    if (mode_ == M_FIRST) {
-        releaseUnusedSlots();
-        finish(TRACK_FIRST_FRAME);
-        return;
-    }
-    if (mode_ == M_TRACK) queueTrackMappoint(next); // :206
-    queueTrackReference(next);                      // :173 / :209
-}
-
-void Tracking::onLKDone(StageBatch &done, StageBatch &next) {
-    if (mode_ == M_TRACK) finishTrackMappoint(done);
-    ref_tracked_ = midTrackReference(done, next);
-}
-
-void Tracking::onRansacDone(StageBatch &done, StageBatch &next) {
-    if (ref_tracked_) finishTrackReference(done);
-    if (mode_ == M_INIT) {
-        if (parallax_ref_ < cfg_.track_min_parallax) { // :175-178
-            showTracking();
-            finish(TRACK_INITIALIZING);
-            return;
-        }
-        queueTriangulation(next); // :182
-        return;
-    }
-    kf_state_ = checkKeyFrameSate(); // :212
-    if ((kf_state_ == KEYFRAME_NORMAL) || (kf_state_ == KEYFRAME_REMOVE_OLDEST)) queueTriangulation(next); // :215-217
-}
-
-void Tracking::onTriangulateDone(StageBatch &done, StageBatch &next) {
-    if (tri_queued_) finishTriangulation(done);
-    if (mode_ == M_INIT) {
-        if (doResetTracking()) { // :184-190
-            showTracking();
-            lost_reset_ = 1;
-            makeNewFrameQueue(KEYFRAME_NORMAL, next);
-            return;
-        }
-        lost_reset_ = 0;
-        frame_ref_->setKeyFrame(KEYFRAME_NORMAL); // :193
-        makeNewFrameQueue(KEYFRAME_NORMAL, next); // :196
-        last_keyframe_  = frame_cur_;
-        isinitializing_ = false;
-        return;
-    }
-    // tracking mode (:214-239). featuresDetection never touches frame features, so the lost test (:224) can be
-    // evaluated first: when it fires the results of the :220 detection would be wiped by doResetTracking anyway.
-    lost_reset_ = 0;
-    if (!frame_cur_->numFeatures()) {
-        doResetTracking();
-        lost_reset_ = 2;
-        makeNewFrameQueue(KEYFRAME_NORMAL, next); // :225
-        return;
-    }
-    if ((kf_state_ == KEYFRAME_NORMAL) || (kf_state_ == KEYFRAME_REMOVE_OLDEST)) {
-        makeNewFrameQueue(kf_state_, next); // :230-232
-    } else {
-        queueDetection(frame_cur_, true, next); // :220
-        if (kf_state_ != KEYFRAME_NONE) makeNewFrameQueue(kf_state_, next); // REMOVE_SECOND_NEW: flags only
-    }
-}
-
-void Tracking::onDetectBDone(StageBatch &done) {
-    if (det_job_ >= 0) integrateDetection(done);
-    releaseUnusedSlots();
-    if (mode_ == M_INIT) {
-        if (lost_reset_ == 1) {
-            finish(TRACK_FIRST_FRAME);
-            return;
-        }
-        showTracking();
-        finish(TRACK_TRACKING);
-        return;
-    }
-    if (lost_reset_ == 2) {
-        finish(TRACK_LOST);
-        return;
-    }
-    if (kf_state_ != KEYFRAME_NONE) writeLoggingMessage(); // :236-238
-    showTracking();
-    finish(TRACK_TRACKING);
-}
-
-// makeNewFrame (:251-261) with its detection deferred to the batched stage
-void Tracking::makeNewFrameQueue(int state, StageBatch &next) {
-    frame_cur_->setKeyFrame(state);
-    isnewkeyframe_ = true;
-    if ((state == KEYFRAME_NORMAL) || (state == KEYFRAME_REMOVE_OLDEST)) {
-        frame_ref_ = frame_cur_;
-        queueDetection(frame_ref_, true, next);
-    }
-}
-
 // ---- featuresDetection (:576-688) ------------------------------------------------------------------------------------
-bool Tracking::queueDetection(Frame::Ptr &frame, bool ismask, StageBatch &next) {
-    det_job_ = -1;
-    int num_features = static_cast<int>(frame->numFeatures() + pts2d_ref_.size()); // :579
-    if (num_features > (cfg_.track_max_features - 5)) return false;                     // :580
+// the job's block counts and work lists; the head (:579-580) is StagedTracker::queueDetection
+void Tracking::queueDetectionJob(const Frame::Ptr &frame, bool ismask, StageBatch &next) {
     vector<int> features_cnts((size_t) block_cnts_, 0);
-    auto count = [&](float x, float y) {
-        int col = int(x / (float) block_w_); // :598
-        int row = int(y / (float) block_h_);
-        // SURVEY.md hazard H5: the reference indexes features_cnts[row * block_cols_ + col] with the UNCLAMPED column.  The key
-        // points counted here are undistorted, so near the right edge x can reach block_cols_ * block_w_ and beyond
-        // (col == block_cols_): the reference then counts the feature in the FIRST block of the NEXT row.  That effective
-        // behaviour is reproduced (pinned by tests/golden/tracking_ref_*.npz); only indices outside the array — undefined
-        // behaviour in the reference (stack VLA overrun) — are dropped.
-        const long idx = (long) row * block_cols_ + col;
-        if (idx >= 0 && idx < (long) block_cnts_) features_cnts[(size_t) idx]++;
-    };
-    frame->forEachFeaturePipelined([&](ulong, const Feature::Ptr &feature) { count(feature->keyPoint().x, feature->keyPoint().y); });
-    for (auto &pts2d : pts2d_new_) count(pts2d.x, pts2d.y);
+    countBlockFeatures(frame, features_cnts.data());
     det_job_     = (int) next.det_slots.size();
     det_ismask_  = ismask;
     det_frame_   = frame;
@@ -621,36 +260,10 @@ bool Tracking::queueDetection(Frame::Ptr &frame, bool ismask, StageBatch &next) 
     }
     next.det_mask_off.push_back((int32_t) (next.det_mask_pts.size() / 2));
     for (int k = 0; k < block_cnts_; k++) next.det_quota.push_back(track_max_block_features_ - features_cnts[(size_t) k]); // :629
-    return true;
 }
 
-void Tracking::integrateDetection(StageBatch &done) { // :659-685
-    if (!det_ismask_) {
-        pts2d_new_.clear();
-        pts2d_ref_.clear();
-        pts2d_ref_undis_.clear();
-        pts2d_new_undis_.clear();
-        pts2d_ref_frame_.clear();
-        velocity_ref_.clear();
-    }
-    const int max_per_job = maxFeaturesPerJob();
-    const int n           = done.det_count[(size_t) det_job_];
-    const float *p        = done.det_out.data() + (size_t) det_job_ * max_per_job * 2;
-    vector<Point2f> fresh((size_t) n);
-    for (int i = 0; i < n; i++) fresh[(size_t) i] = Point2f(p[2 * i], p[2 * i + 1]);
-    vector<Point2f> fresh_undis = fresh;
-    camera_->undistortPoints(fresh_undis); // the one undistortion a detected corner ever needs
-    for (int i = 0; i < n; i++) {
-        pts2d_ref_.push_back(fresh[(size_t) i]);
-        pts2d_new_.push_back(fresh[(size_t) i]);
-        pts2d_ref_undis_.push_back(fresh_undis[(size_t) i]);
-        pts2d_new_undis_.push_back(fresh_undis[(size_t) i]);
-        pts2d_ref_frame_.push_back(det_frame_);
-        velocity_ref_.emplace_back(0, 0);
-    }
+void Tracking::detectionIntegrated(int n) {
     if (debugTriangulation()) fprintf(stderr, "[det] Add %d new features (ref list now %zu)\n", n, pts2d_ref_.size());
-    det_job_ = -1;
-    det_frame_.reset();
 }
 
 // ---- trackMappoint (:351-455) ---------------------------------------------------------------------------------------
@@ -960,6 +573,11 @@ void Tracking::finishTriangulation(StageBatch &done) {
     pts2d_new_       = pts2d_cur_;
     pts2d_new_undis_ = tr_cur_undis_;
 }
+
+// ---- the staged interface: the state machine of staged_tracker.h, instantiated here ------------------------------------------------
+void Tracking::beginFrame(Frame::Ptr frame, StageBatch &next) { Base::beginFrame(std::move(frame), next); }
+
+void Tracking::advance(int stage, StageBatch &done, StageBatch &next) { Base::advance(stage, done, next); }
 
 // ---- single-stream synchronous API (tracking.cc:144) ------------------------------------------------------------------
 TrackState Tracking::track(Frame::Ptr frame) {

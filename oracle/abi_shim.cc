@@ -576,7 +576,7 @@ int icg_ins_camera_pose_batch(icg_ctx *, int n, const double *brackets16, const 
 // (ic-gvins_amd/host/track_core.h, here compiled by g++) between the shim's primitives, stream after stream.  With it the host executor of
 // the device engine (TrackingBatch::stepDevice: download / import / view / absorb / upload, log drains, statistics) runs in the CPU suite,
 // and the GPU tests have a checker that speaks the same ABI.
-#include "../ic-gvins_amd/host/track_core.h"
+#include "../ic-gvins_amd/host/track_core_arena.h"
 
 static_assert(sizeof(icg_tracker_config) == sizeof(tc::Cfg), "icg_tracker_config mirrors tc::Cfg");
 
@@ -587,32 +587,9 @@ struct icg_tracker {
     icg_detect_grid grid;
     std::vector<uint32_t> buckets;
     std::vector<tc::Stream *> streams;
-    struct Arena {
-        int32_t pre_slot = -1, lk_count = 0, rs_count = 0, tri_count = 0, tri_n_tcw = 0, det_slot = -1, det_mask_count = 0, det_count = 0;
-        double pre_hist = 0;
-        std::vector<int32_t> lk_prev_slot, lk_next_slot, tri_T0, tri_T1, det_quota;
-        std::vector<tc::P2f> lk_prev, lk_guess, lk_out, lk_undist, rs_p1, rs_p2, det_mask_pts, det_out;
-        std::vector<uint8_t> lk_status, rs_mask;
-        std::vector<double> tri_Tcw, tri_pc0, tri_pc1, tri_pw;
-    };
-    std::vector<Arena> arena;
+    std::vector<tc::HostArena> arena; // per stream
     tc::Scratch scratch;
 };
-
-static tc::Io shim_io(icg_tracker::Arena &a, int lk_base) {
-    tc::Io io;
-    memset(&io, 0, sizeof io);
-    io.pre_slot = &a.pre_slot, io.pre_hist = &a.pre_hist;
-    io.lk_count = &a.lk_count, io.lk_prev_slot = a.lk_prev_slot.data(), io.lk_next_slot = a.lk_next_slot.data();
-    io.lk_prev = a.lk_prev.data(), io.lk_guess = a.lk_guess.data(), io.lk_out = a.lk_out.data(), io.lk_undist = a.lk_undist.data();
-    io.lk_status = a.lk_status.data(), io.lk_base = lk_base;
-    io.rs_count = &a.rs_count, io.rs_p1 = a.rs_p1.data(), io.rs_p2 = a.rs_p2.data(), io.rs_mask = a.rs_mask.data();
-    io.tri_count = &a.tri_count, io.tri_n_tcw = &a.tri_n_tcw, io.tri_T0 = a.tri_T0.data(), io.tri_T1 = a.tri_T1.data();
-    io.tri_Tcw = a.tri_Tcw.data(), io.tri_pc0 = a.tri_pc0.data(), io.tri_pc1 = a.tri_pc1.data(), io.tri_pw = a.tri_pw.data();
-    io.det_slot = &a.det_slot, io.det_quota = a.det_quota.data(), io.det_mask_count = &a.det_mask_count;
-    io.det_mask_pts = a.det_mask_pts.data(), io.det_count = &a.det_count, io.det_out = a.det_out.data();
-    return io;
-}
 
 extern "C" {
 
@@ -642,12 +619,7 @@ int icg_tracker_create(icg_ctx *ctx, int n_streams, const icg_tracker_config *cf
         }
         tc::stream_init(*S, s * tc::MAX_SLOTS);
         t->streams.push_back(S);
-        auto &a = t->arena[(size_t) s];
-        const size_t R = tc::MAX_ROWS;
-        a.lk_prev_slot.resize(R), a.lk_next_slot.resize(R), a.lk_prev.resize(R), a.lk_guess.resize(R), a.lk_out.resize(R), a.lk_undist.resize(R);
-        a.lk_status.resize(R), a.rs_mask.resize(R), a.rs_p1.resize(R), a.rs_p2.resize(R), a.tri_T0.resize(R), a.tri_T1.resize(R);
-        a.tri_Tcw.resize(12 * tc::MAX_TCW), a.tri_pc0.resize(3 * R), a.tri_pc1.resize(3 * R), a.tri_pw.resize(3 * R);
-        a.det_quota.resize(tc::MAX_BLOCKS), a.det_mask_pts.resize(R), a.det_out.resize(R);
+        t->arena[(size_t) s].resize();
     }
     *out = t;
     return ICG_OK;
@@ -666,7 +638,7 @@ int icg_tracker_step(icg_tracker *t, const uint8_t *const *images, int stride, i
         memset(&r, 0, sizeof r);
         int work[4] = {0, 0, 0, 0};
         if (images[s]) {
-            tc::Io io = shim_io(a, s * tc::MAX_ROWS);
+            tc::Io io = a.io(s * tc::MAX_ROWS);
             tc::Pose pose;
             memcpy(pose.R, poses12 + 12 * (size_t) s, sizeof(double) * 12);
             tc::stage_begin_frame(S, io, stamps[s], pose, (tc::u64) (uintptr_t) images[s]);

@@ -84,6 +84,24 @@ def test_table_engine_state_equals_object_engine(name):
     assert stats_t["mappoints_created"] > 40
 
 
+def test_engines_agree_under_the_carried_undistortion_check(monkeypatch):
+    """ICG_HOST_CHECK=1 makes both engines re-derive the carried undistorted candidate lists on the host before every reference
+    tracking and every triangulation (StagedTracker::checkCarriedUndistortion, which throws on the first differing bit or on the wrong
+    list for the call site).  Both engines must get through lost-and-reinit with it on, and still agree."""
+    monkeypatch.setenv("ICG_HOST_CHECK", "1")
+    name = "c1_lost_and_reinit"
+    w, h, nfeat, n, stream, blank, hist, slow = CASES[name]
+    frames, poses = _scene(w, h, n, stream, blank=blank, slow_after=slow)
+    st_t, d_t, stats_t = _drive("table", w, h, nfeat, n, frames, poses)
+    st_o, d_o, stats_o = _drive("object", w, h, nfeat, n, frames, poses)
+    assert st_t == st_o and len(st_t) == n
+    assert stats_t == stats_o
+    assert 2 in st_t and 4 in st_t  # tracked (reference tracking and triangulation ran), lost and re-initialized
+    for (k, full_t, _, _), (_, full_o, _, _) in zip(d_t, d_o):
+        i, lt, lo = _first_difference(full_t, full_o)
+        assert full_t == full_o, f"engines differ after frame {k}, dump line {i}:\n table : {lt}\n object: {lo}"
+
+
 def test_hash_order_equals_std_unordered_map():
     lib = C.CDLL(ensure_oracle_host())
     lib.icgh_hashorder_selftest.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int]
