@@ -7,13 +7,18 @@
 // order from +0.0 (one multiply, one add per term: this file is compiled with -ffp-contract=off like the rest), and every cell receives the
 // block values in block order.  One thread owns a cell through all blocks, so nothing is added atomically and a window's bits do not depend
 // on the batch it is built in.  The Jacobians stay on the device (icg_hp_kept): a block whose Jacobian did not change crosses the link as
-// its residuals only.
+// its residuals only.  A block that is a marginalization prior resident on the device (marg.hip) crosses it not at all
+// (icg_reproj_host_parts_build_prior): k_host_part_prior copies its residuals of the last resident evaluation and the free columns of its J0
+// to the places k_host_part reads.
 #include "reproj_internal.h"
 
 #define HP_THREADS 256
 #define HP_CPT 16     // cells of the packed triangle per thread: a workgroup owns HP_THREADS * HP_CPT consecutive cells of one window
 #define HP_STAGE 4096 // doubles of a block's Jacobian rows staged in LDS per pass (32 KB)
 #define HP_MAX_KC 64  // rows per pass at the most
+#define HP_MAX_P 512  // columns of a reduced system at the most: what the entry admits (nf <= Pw <= P) and the column tables in LDS hold
+static_assert(HP_MAX_P <= 2 * HP_THREADS, "the first workgroup of a window owns s and diag in two columns per thread");
+static_assert(HP_STAGE / HP_MAX_P >= 1, "a staging pass holds at least one row of the widest block");
 
 struct hp_win {
     int32_t w, Pw, blk_begin, blk_end, slot, pad; // blocks [blk_begin, blk_end) of the call's block list; slot: index among the rebuilt windows
@@ -25,6 +30,12 @@ struct hp_blk {
 };
 struct hp_copy {
     int64_t src, dst, n;
+};
+#define HP_PRIOR_ROWS 16 // rows of a prior block per workgroup of k_host_part_prior
+struct hp_prior {
+    int64_t J0_off, Jd_off;           // the prior's J0 in the resident set; the block's place among the kept Jacobians
+    int32_t e_off, r_off, pc_off, nr; // its residuals in the set; the block's place in the staged r; its columns of J0 in prior_cols
+    int32_t nf, fill;                 // fill != 0: the kept Jacobian is gathered from J0 (ICG_HP_JAC_FROM_PRIOR)
 };
 
 // the shipped Jacobians move from the staging arena to their places among the kept ones: one workgroup per shipped block
@@ -41,7 +52,7 @@ __global__ __launch_bounds__(HP_THREADS) void k_host_part(const hp_win *wins, co
                                                           double *H, double *s_out, double *diag_out, double *part_out) {
     __shared__ double Js[HP_STAGE];
     __shared__ double rs[HP_MAX_KC];
-    __shared__ int16_t map[512];
+    __shared__ int16_t map[HP_MAX_P];
     const hp_win W    = wins[blockIdx.y];
     const int n_cells = (W.Pw * (W.Pw + 1)) >> 1, base = blockIdx.x * (HP_THREADS * HP_CPT);
     if (base >= n_cells) return; // (a narrower window than the widest of the call: uniform over the workgroup)
@@ -129,16 +140,44 @@ __global__ __launch_bounds__(HP_THREADS) void k_host_part(const hp_win *wins, co
     }
 }
 
+// A block that is a resident marginalization prior (icg_marg_prior_set), for the row tile blockIdx.x of the prior block blockIdx.y: the kept
+// Jacobian is gathered from the prior's row-major J0 where the block asks for it (Jd[k][y] = J0[k][pc[y]]: the elements of a tile are
+// consecutive in Jd, so the writes are contiguous along y and across the rows of the tile), and the residuals of the last resident evaluation
+// are copied to the block's place in the staged r.  A plain copy without atomics, ahead of k_host_part.
+__global__ __launch_bounds__(HP_THREADS) void k_host_part_prior(const hp_prior *pr, const int32_t *pcols, const double *J0, const double *res, double *Jd, double *r) {
+    __shared__ int32_t pc[HP_MAX_P]; // (nf <= HP_MAX_P: the entry's capacity check)
+    const hp_prior B = pr[blockIdx.y];
+    const int k0 = blockIdx.x * HP_PRIOR_ROWS, t = threadIdx.x;
+    if (k0 >= B.nr) return; // (a shorter prior than the longest of the call: uniform over the workgroup)
+    const int kc = min(HP_PRIOR_ROWS, B.nr - k0);
+    if (t < kc) r[B.r_off + k0 + t] = res[B.e_off + k0 + t];
+    if (!B.fill) return;
+    for (int y = t; y < B.nf; y += HP_THREADS) pc[y] = pcols[B.pc_off + y];
+    __syncthreads();
+    const double *src = J0 + B.J0_off + (size_t) k0 * B.nr; // (J0 is nr x nr)
+    double *dst       = Jd + B.Jd_off + (size_t) k0 * B.nf;
+    for (int e = t; e < kc * B.nf; e += HP_THREADS) {
+        const int k = e / B.nf, y = e - k * B.nf;
+        dst[e]      = src[(size_t) k * B.nr + pc[y]];
+    }
+}
+
 extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
                                            const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s,
                                            double *host_diag, double *part_out) {
+    return icg_reproj_host_parts_build_prior(ctx, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, nullptr, nullptr);
+}
+
+extern "C" int icg_reproj_host_parts_build_prior(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
+                                                 const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r,
+                                                 double *host_s, double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols) {
     if (!ctx) return ICG_ERR_INVALID;
-    const char *me = "icg_reproj_host_parts_build";
+    const char *me = prior_of ? "icg_reproj_host_parts_build_prior" : "icg_reproj_host_parts_build";
     icg_partition &pt = ctx->part_w;
     const int W       = pt.W;
     if (W <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: no window partition: call icg_reproj_set_windows first", me);
     if (P <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: P = %d", me, P);
-    if (P > 512) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: reduced systems of more than 512 camera columns are not supported (%d)", me, P);
+    if (P > HP_MAX_P) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: reduced systems of more than %d camera columns are not supported (%d)", me, HP_MAX_P, P);
     if (W > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %d windows in one call (at most 65535)", me, W);
     if (ctx->red_W != 0 && ctx->red_P != P) return icg_fail(ctx, ICG_ERR_INVALID, "%s: P = %d, the resident reduced systems have %d columns", me, P, ctx->red_P);
     if (!Pw || !rebuild || !blk_off || !host_s || !host_diag) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", me);
@@ -157,6 +196,12 @@ extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *P
     std::vector<int32_t> r_off((size_t) nb + 1, 0), c_off((size_t) nb + 1, 0), seen((size_t) P, -1);
     size_t ship_doubles = 0, n_ship = 0, out_cells = 0;
     int n_rebuilt = 0, max_cells = 0;
+    // prior blocks: pc_at walks prior_cols over the prior blocks of ALL windows (a window that is not rebuilt still places the others')
+    const icg_marg_set &ms = ctx->marg;
+    std::vector<hp_prior> priors;               // of the rebuilt windows
+    std::vector<std::pair<int, int>> prior_at;  // their (window, position in the window's block list)
+    size_t pc_at = 0;
+    int max_prior_nr = 0;
     for (int w = 0; w < W; w++) {
         const std::vector<icg_hp_block> *kept = have_kept ? &hp.win[(size_t) w] : nullptr;
         const int cnt                         = blk_off[w + 1] - blk_off[w];
@@ -170,6 +215,9 @@ extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *P
             if ((int64_t) r_off[(size_t) b] + nr[b] > INT32_MAX || (int64_t) c_off[(size_t) b] + nf[b] > INT32_MAX)
                 return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: window %d, block %d: more than 2^31 residuals or columns in one call", me, w, p);
             r_off[(size_t) b + 1] = r_off[(size_t) b] + nr[b], c_off[(size_t) b + 1] = c_off[(size_t) b] + nf[b];
+            const int pp     = prior_of ? prior_of[b] : -1; // >= 0: the block is prior pp of the resident set
+            const size_t pc0 = pc_at;
+            if (pp >= 0) pc_at += (size_t) nf[b]; // (at most the columns of all blocks: below 2^31)
             if (!rebuild[w]) continue;
             if (nf[b] > Pw[w]) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d columns in a system of %d", me, w, p, nf[b], Pw[w]);
             for (int x = 0; x < nf[b]; x++) {
@@ -178,9 +226,28 @@ extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *P
                 if (seen[(size_t) c] == b) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: column %d twice", me, w, p, c);
                 seen[(size_t) c] = b;
             }
+            if (pp >= 0) {
+                if (!prior_cols) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a prior block without prior_cols", me, w, p);
+                if (ms.n <= 0 || !ms.res_valid)
+                    return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no prior set is resident and evaluated (icg_marg_prior_set, then icg_marg_prior_evaluate_resident)",
+                                    me, w, p);
+                if (pp >= ms.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: prior %d outside the resident set of %d", me, w, p, pp, ms.n);
+                const int pr = ms.h_r[(size_t) pp];
+                if (nr[b] != pr) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, prior %d has %d", me, w, p, nr[b], pp, pr);
+                for (int x = 0; x < nf[b]; x++) {
+                    const int c = prior_cols[pc0 + (size_t) x];
+                    if (c < 0 || c >= pr) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: prior column %d outside the prior (%d)", me, w, p, c, pr);
+                }
+                priors.push_back({ms.h_j_off[(size_t) pp], 0 /* its place among the kept Jacobians follows below */, ms.h_e_off[(size_t) pp],
+                                  r_off[(size_t) b], (int32_t) pc0, nr[b], nf[b], jac_off[b] == ICG_HP_JAC_FROM_PRIOR ? 1 : 0});
+                prior_at.push_back({w, p});
+                max_prior_nr = std::max(max_prior_nr, nr[b]);
+            }
             if (jac_off[b] >= 0) {
                 if (!J) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a Jacobian offset without J", me, w, p);
                 ship_doubles += (size_t) nr[b] * nf[b], n_ship++;
+            } else if (jac_off[b] == ICG_HP_JAC_FROM_PRIOR && pp >= 0) {
+                // gathered from the prior's J0 on the device
             } else if (jac_off[b] == -1) {
                 any_keep = true;
                 if (!kept || (size_t) p >= kept->size()) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no kept Jacobian", me, w, p);
@@ -198,6 +265,7 @@ extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *P
         max_cells = std::max(max_cells, Pw[w] * (Pw[w] + 1) / 2);
         out_cells += (size_t) Pw[w] * (Pw[w] + 1) / 2;
     }
+    if (priors.size() > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %zu prior blocks in one call (at most 65535)", me, priors.size());
     if (n_rebuilt == 0) return ICG_OK;
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     // ---- the kept Jacobians after this call: dense, window after window -----------------------------------------------------------------------
@@ -235,7 +303,7 @@ extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *P
         };
         for (int w = 0; w < W && have_kept; w++)
             for (size_t p = 0; p < next[(size_t) w].size(); p++) {
-                if (rebuild[w] && jac_off[(size_t) blk_off[w] + p] >= 0) continue;
+                if (rebuild[w] && jac_off[(size_t) blk_off[w] + p] != -1) continue; // (shipped, or gathered from a prior's J0)
                 const icg_hp_block &o = hp.win[(size_t) w][p], &n = next[(size_t) w][p];
                 const int64_t len     = (int64_t) n.nr * n.nf;
                 if (run_n && o.off == run_src + run_n && n.off == run_dst + run_n) {
@@ -263,17 +331,34 @@ extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *P
                 if (jac_off[b] >= 0) copies.push_back({src, n.off, (int64_t) nr[b] * nf[b]}), src += (int64_t) nr[b] * nf[b];
             }
         }
+        for (size_t k = 0; k < priors.size(); k++) priors[k].Jd_off = next[(size_t) prior_at[k].first][(size_t) prior_at[k].second].off;
     }
     const size_t n_r = (size_t) r_off[(size_t) nb], n_c = (size_t) c_off[(size_t) nb];
     icg_call c(ctx);
-    if ((rc = c.reserve(sizeof(hp_win) * wins.size() + sizeof(hp_blk) * blks.size() + sizeof(hp_copy) * copies.size() + sizeof(int32_t) * n_c +
-                        sizeof(double) * (n_r + ship_doubles + 2 * (size_t) n_rebuilt * P + out_cells) + 16 * 256)))
+    if ((rc = c.reserve(sizeof(hp_win) * wins.size() + sizeof(hp_blk) * blks.size() + sizeof(hp_copy) * copies.size() + sizeof(hp_prior) * priors.size() +
+                        sizeof(int32_t) * (n_c + pc_at) + sizeof(double) * (n_r + ship_doubles + 2 * (size_t) n_rebuilt * P + out_cells) + 20 * 256)))
         return rc;
     const hp_win *d_wins  = c.in(wins.data(), wins.size());
     const hp_blk *d_blks  = c.in(blks.data(), blks.size());
     const hp_copy *d_cp   = c.in(copies.data(), copies.size());
     const int32_t *d_cols = c.in(cols, n_c);
-    const double *d_r     = c.in(r, n_r);
+    const hp_prior *d_pr  = c.in(priors.data(), priors.size());
+    const int32_t *d_pc   = priors.empty() ? nullptr : c.in(prior_cols, pc_at);
+    double *d_r           = nullptr;
+    if (!prior_of) {
+        d_r = c.in(r, n_r);
+    } else {
+        // The slots of the prior blocks (of every window, rebuilt or not) are placed but not read from the caller: staged block by block,
+        // like the shipped Jacobians below.  Whatever bytes the arena holds there go up with the rest; for the rebuilt windows
+        // k_host_part_prior overwrites them on the device, in stream order behind the upload and ahead of k_host_part, and the blocks of
+        // the other windows are not consumed.
+        const size_t off = icg_arena_alloc(ctx, sizeof(double) * n_r);
+        double *h        = icg_h<double>(ctx, off);
+        for (int b = 0; b < nb; b++)
+            if (prior_of[b] < 0) memcpy(h + r_off[(size_t) b], r + r_off[(size_t) b], sizeof(double) * (size_t) nr[b]);
+        c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * n_r);
+        d_r = icg_d<double>(ctx, off);
+    }
     const double *d_Jnew  = nullptr;
     if (ship_doubles) { // the shipped Jacobians, block after block
         const size_t off = icg_arena_alloc(ctx, sizeof(double) * ship_doubles);
@@ -298,6 +383,11 @@ extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *P
     for (int w = 0; w < W; w++)
         if (rebuild[w]) ctx->red_H_cols[(size_t) w] = 0;
     hp.win.clear();
+    if (!priors.empty()) { // (its places among the kept Jacobians and in r are not the shipped blocks')
+        icg_prof_scope ps(ctx, "host_part_prior");
+        hipLaunchKernelGGL(k_host_part_prior, dim3((unsigned) ((max_prior_nr + HP_PRIOR_ROWS - 1) / HP_PRIOR_ROWS), (unsigned) priors.size()), dim3(HP_THREADS), 0,
+                           ctx->stream, d_pr, d_pc, (const double *) ms.d_J, (const double *) ms.d_res, hp.d_J[dst], d_r);
+    }
     {
         icg_prof_scope ps(ctx, "host_part");
         if (!copies.empty())

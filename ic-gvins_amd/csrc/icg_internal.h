@@ -69,6 +69,14 @@ struct icg_marg_set {
     char *d_meta = nullptr; // offsets and block layout (marg.hip marg_view)
     size_t J_cap = 0, e0_cap = 0, x0_cap = 0, meta_cap = 0; // bytes
     std::vector<int64_t> h_meta;
+    // the residuals of the last icg_marg_prior_evaluate_resident (total_r), read in place by icg_reproj_host_parts_build_prior
+    double *d_res = nullptr;
+    size_t res_cap = 0;     // bytes
+    bool res_valid = false; // evaluated since the set was made resident
+    // what the host-part entry validates and places a prior block by (n entries each, written by icg_marg_prior_set beside h_meta): the
+    // retained size of window w, its first residual and the first element of its J0
+    std::vector<int32_t> h_r, h_e_off;
+    std::vector<int64_t> h_j_off;
 };
 
 // Host-factor parts built on the device (host_part.hip): the Jacobian of every factor block of every window, kept densely (window after

@@ -1,7 +1,8 @@
 // M4: MarginalizationFactor::Evaluate (factors/marginalization_factor.h:47-101) for many priors at once, with the priors RESIDENT on the
 // device.  A prior (x0, J0, e0 and its block layout) is constant between two marginalizations while every LM iteration evaluates it at a
 // new x: icg_marg_prior_set uploads the priors of many windows once, icg_marg_prior_evaluate ships only x in and e (optionally the
-// Jacobian blocks, J0^T e and |e|^2) out.  FP64, no contraction; every sum is formed in the host's order (host/factors.cc
+// Jacobian blocks, J0^T e and |e|^2) out; icg_marg_prior_evaluate_resident keeps e on the device for the host-part kernel (host_part.hip) and
+// ships |e|^2 only.  FP64, no contraction; every sum is formed in the host's order (host/factors.cc
 // evaluateMargPrior, oracle/orc_marg.cc), so the residuals and Jacobian blocks are the same IEEE values bit for bit, alone or in a batch.
 #include "icg_internal.h"
 
@@ -158,6 +159,7 @@ extern "C" int icg_marg_prior_set(icg_ctx *ctx, int n_windows, const int32_t *r,
     if (!ctx) return ICG_ERR_INVALID;
     icg_marg_set &s = ctx->marg;
     s.n             = 0; // whatever set the context held is gone, also when this call fails
+    s.res_valid     = false; // and so are the residuals it kept
     if (n_windows <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_set: n_windows = %d", n_windows);
     if (n_windows > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_prior_set: %d windows in one set (at most 65535)", n_windows);
     if (!r || !block_off || !block_size || !block_index || !x0 || !J0 || !e0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_set: NULL argument");
@@ -204,6 +206,7 @@ extern "C" int icg_marg_prior_set(icg_ctx *ctx, int n_windows, const int32_t *r,
     }
     if (max_jac > (int64_t) 1 << 30) return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_prior_set: %lld Jacobian elements in one window", (long long) max_jac);
     if (te > (int64_t) 1 << 30) return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_prior_set: %lld residuals in one set", (long long) te);
+    s.h_r.assign(m_r, m_r + n), s.h_e_off.assign(m_eoff, m_eoff + n), s.h_j_off.assign(j_off, j_off + n); // (for host_part.hip)
     m_boff[n] = block_off[n], m_eoff[n] = (int32_t) te, m_xoff[n] = (int32_t) tx, j_off[n] = tj, jac_off[n] = tjac;
 
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
@@ -267,4 +270,34 @@ extern "C" int icg_marg_prior_evaluate(icg_ctx *ctx, const double *x, double *re
     }
     ICG_HIP(ctx, hipGetLastError());
     return c.finish();
+}
+
+// The same evaluation with the residuals left where icg_reproj_host_parts_build_prior reads them (the set's own buffer): x up, one squared
+// norm per window back.  k_marg_evaluate as above, so sq_norm[w] is the value icg_marg_prior_evaluate returns, bit for bit.
+extern "C" int icg_marg_prior_evaluate_resident(icg_ctx *ctx, const double *x, double *sq_norm) {
+    if (!ctx) return ICG_ERR_INVALID;
+    icg_marg_set &s = ctx->marg;
+    if (s.n <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_evaluate_resident: no prior set is resident (icg_marg_prior_set first)");
+    if (!sq_norm || (!x && s.total_x > 0)) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_evaluate_resident: NULL argument");
+    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    const size_t n = (size_t) s.n, b_res = sizeof(double) * (size_t) s.total_r;
+    bool replaced = false;
+    int rc        = icg_grow(ctx, (void **) &s.d_res, &s.res_cap, b_res, b_res, &replaced);
+    if (replaced) s.res_valid = false;
+    if (rc) return rc;
+    icg_call c(ctx);
+    if ((rc = c.reserve(sizeof(double) * (size_t) (s.total_x + (int64_t) n) + 4 * 256))) return rc;
+    const double *d_x = c.in(x, (size_t) s.total_x);
+    if ((rc = c.seal())) return rc;
+    double *d_sq = c.out(sq_norm, n);
+    ICG_LAUNCH_GUARD(c);
+    s.res_valid = false; // (until the kernel below is through)
+    {
+        icg_prof_scope ps(ctx, "marg_eval");
+        hipLaunchKernelGGL(k_marg_evaluate, dim3(s.n), dim3(MARG_THREADS), 0, ctx->stream, s.n, marg_view(s), d_x, s.d_res, (double *) nullptr, d_sq);
+    }
+    ICG_HIP(ctx, hipGetLastError());
+    if ((rc = c.finish())) return rc;
+    s.res_valid = true;
+    return ICG_OK;
 }

@@ -880,23 +880,25 @@ void MarginalizationInfo::linearization() { // :153-167
 MarginalizationFactor::MarginalizationFactor(std::shared_ptr<MarginalizationInfo> marg_info) : marg_info_(std::move(marg_info)) {
     for (auto size : marg_info_->remainedBlockSize()) mutable_parameter_block_sizes()->push_back(size);
     set_num_residuals(marg_info_->remainedSize());
+    // The view Evaluate reads, fixed here like the block sizes above.  The remained-block lists are COPIED: getParamterBlocks() clears and
+    // refills them in the info, and the factor keeps describing the blocks it was built for.  The linearization points they name, J0 and e0
+    // stay the info's own arrays, which change only in marginalization(): a factor is built from an info after its marginalization() and
+    // getParamterBlocks(), as the estimator does, and the info is not marginalized again while a factor reads it.
+    const int marginalizaed_size = marg_info_->marginalizedSize();
+    size_                        = marg_info_->remainedBlockSize();
+    for (int i : marg_info_->remainedBlockIndex()) index_.push_back(i - marginalizaed_size);
+    x0_.assign(marg_info_->remainedBlockData().begin(), marg_info_->remainedBlockData().end());
+    view_.r        = marg_info_->remainedSize();
+    view_.n_blocks = (int) size_.size();
+    view_.size     = size_.data();
+    view_.index    = index_.data();
+    view_.x0       = x0_.data();
+    view_.J0       = marg_info_->linearizedJacobians().data();
+    view_.e0       = marg_info_->linearizedResiduals().data();
 }
 
 bool MarginalizationFactor::Evaluate(const double *const *parameters, double *residuals, double **jacobians) const {
-    const int marginalizaed_size            = marg_info_->marginalizedSize();
-    const vector<int> &remained_block_index = marg_info_->remainedBlockIndex();
-    const vector<int> &remained_block_size  = marg_info_->remainedBlockSize();
-    vector<int> index(remained_block_index.size());
-    for (size_t i = 0; i < index.size(); i++) index[i] = remained_block_index[i] - marginalizaed_size;
-    MargPriorView view;
-    view.r        = marg_info_->remainedSize();
-    view.n_blocks = (int) remained_block_size.size();
-    view.size     = remained_block_size.data();
-    view.index    = index.data();
-    view.x0       = marg_info_->remainedBlockData().data();
-    view.J0       = marg_info_->linearizedJacobians().data();
-    view.e0       = marg_info_->linearizedResiduals().data();
-    evaluateMargPrior(view, parameters, residuals, jacobians);
+    evaluateMargPrior(view_, parameters, residuals, jacobians);
     return true;
 }
 

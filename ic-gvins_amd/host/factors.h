@@ -230,16 +230,6 @@ private:
     DeviceFactorSet *batch_{nullptr};
 };
 
-class MarginalizationFactor : public ceres::CostFunction {
-public:
-    MarginalizationFactor() = delete;
-    explicit MarginalizationFactor(std::shared_ptr<MarginalizationInfo> marg_info);
-    bool Evaluate(const double *const *parameters, double *residuals, double **jacobians) const override;
-
-private:
-    std::shared_ptr<MarginalizationInfo> marg_info_;
-};
-
 // M4 on plain arrays: what MarginalizationFactor::Evaluate reads of a MarginalizationInfo.  index[b] is block b's first local column
 // (the remained block index minus the marginalized size), x0[b] its linearization point (size[b] values).
 struct MargPriorView {
@@ -247,6 +237,31 @@ struct MargPriorView {
     const int *size{nullptr}, *index{nullptr};
     const double *const *x0{nullptr};
     const double *J0{nullptr}, *e0{nullptr}; // r x r row-major, r
+};
+
+// A cost function that IS a linearized marginalization prior says so: its Evaluate is evaluateMargPrior over the view, block b of the view
+// being parameter block b of the cost function.  A solver that keeps the priors of its windows resident on the device
+// (WindowSolverBatch::setDevicePrior) recognises the prior through this interface; the view stays valid and unchanged while the cost
+// function lives.
+class MargPriorSource {
+public:
+    virtual ~MargPriorSource() = default;
+    virtual const MargPriorView &margPriorView() const = 0;
+};
+
+class MarginalizationFactor : public ceres::CostFunction, public MargPriorSource {
+public:
+    MarginalizationFactor() = delete;
+    MarginalizationFactor(const MarginalizationFactor &) = delete; // (the view points into this object)
+    explicit MarginalizationFactor(std::shared_ptr<MarginalizationInfo> marg_info);
+    bool Evaluate(const double *const *parameters, double *residuals, double **jacobians) const override;
+    const MargPriorView &margPriorView() const override { return view_; }
+
+private:
+    std::shared_ptr<MarginalizationInfo> marg_info_;
+    vector<int> size_, index_;  // the remained blocks' global sizes; their indices minus the marginalized size
+    vector<const double *> x0_; // their linearization points (the info's arrays)
+    MargPriorView view_;
 };
 // MarginalizationFactor::Evaluate (marginalization_factor.h:47-101) over a view: residuals r; jacobians (optional, entries may be null):
 // per block an r x size[b] row-major matrix
@@ -267,6 +282,14 @@ public:
     // gradient (optional): J0^T e, residualSize(); sq_norm (optional): e . e per window.
     bool evaluate(const vector<const double *const *> &parameters, double *residuals, double *jacobians, double *gradient, double *sq_norm,
                   std::string *err = nullptr);
+    // The resident evaluation (icg_marg_prior_evaluate_resident): the residuals stay on the device for
+    // icg_reproj_host_parts_build_prior, only sq_norm (e . e per window) comes back.  pack(w, ...) copies window w's parameter blocks to
+    // their place in the set's evaluation point (any thread, before the call; a window that is not packed keeps its last point, zeros
+    // after set()); evaluateResident() makes the one device call.  The entry is referenced weakly like the two above:
+    // residentAvailable() is false in a build of this layer on a C ABI without it, and evaluateResident() then fails by name.
+    static bool residentAvailable();
+    void pack(size_t w, const double *const *parameters);
+    bool evaluateResident(double *sq_norm, std::string *err = nullptr);
     int windows() const { return (int) r_.size(); }
     size_t residualSize() const { return residual_size_; }
     size_t jacobianSize() const { return jacobian_size_; }
@@ -274,6 +297,7 @@ public:
 private:
     icg_ctx *ctx_{nullptr};
     vector<int32_t> r_, block_off_, block_size_;
+    vector<size_t> x_off_; // first parameter of window w in x_
     vector<double> x_; // the evaluation point, packed like x0
     size_t residual_size_{0}, jacobian_size_{0};
 };

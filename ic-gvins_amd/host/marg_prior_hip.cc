@@ -10,10 +10,13 @@
 // and set() reports it; the product library links libicgvins_hip.so, which defines them.
 #pragma weak icg_marg_prior_set
 #pragma weak icg_marg_prior_evaluate
+#pragma weak icg_marg_prior_evaluate_resident
 
 namespace icg {
 
 bool MarginalizationPriorSet::available() { return &icg_marg_prior_set != nullptr && &icg_marg_prior_evaluate != nullptr; }
+
+bool MarginalizationPriorSet::residentAvailable() { return available() && &icg_marg_prior_evaluate_resident != nullptr; }
 
 bool MarginalizationPriorSet::set(icg_ctx *ctx, const vector<MargPriorView> &views, std::string *err) {
     if (!available()) {
@@ -21,7 +24,7 @@ bool MarginalizationPriorSet::set(icg_ctx *ctx, const vector<MargPriorView> &vie
         return false;
     }
     ctx_ = nullptr;
-    r_.clear(), block_off_.assign(1, 0), block_size_.clear();
+    r_.clear(), block_off_.assign(1, 0), block_size_.clear(), x_off_.clear();
     residual_size_ = jacobian_size_ = 0;
     vector<int32_t> index;
     vector<double> x0, e0;
@@ -31,6 +34,7 @@ bool MarginalizationPriorSet::set(icg_ctx *ctx, const vector<MargPriorView> &vie
     J0.reserve(nj);
     for (const MargPriorView &v : views) {
         r_.push_back(v.r);
+        x_off_.push_back(x0.size());
         size_t xs = 0;
         for (int b = 0; b < v.n_blocks; b++) {
             block_size_.push_back(v.size[b]);
@@ -86,13 +90,32 @@ bool MarginalizationPriorSet::evaluate(const vector<const double *const *> &para
         if (err) *err = !ctx_ ? "MarginalizationPriorSet::evaluate: no set" : "MarginalizationPriorSet::evaluate: one parameter list per window";
         return false;
     }
-    double *x = x_.data();
-    for (size_t w = 0; w < r_.size(); w++)
-        for (int32_t b = block_off_[w]; b < block_off_[w + 1]; b++) {
-            memcpy(x, parameters[w][b - block_off_[w]], sizeof(double) * (size_t) block_size_[(size_t) b]);
-            x += block_size_[(size_t) b];
-        }
+    for (size_t w = 0; w < r_.size(); w++) pack(w, parameters[w]);
     if (icg_marg_prior_evaluate(ctx_, x_.data(), residuals, jacobians, gradient, sq_norm) != ICG_OK) {
+        if (err) *err = icg_last_error(ctx_);
+        return false;
+    }
+    return true;
+}
+
+void MarginalizationPriorSet::pack(size_t w, const double *const *parameters) {
+    double *x = x_.data() + x_off_[w];
+    for (int32_t b = block_off_[w]; b < block_off_[w + 1]; b++) {
+        memcpy(x, parameters[b - block_off_[w]], sizeof(double) * (size_t) block_size_[(size_t) b]);
+        x += block_size_[(size_t) b];
+    }
+}
+
+bool MarginalizationPriorSet::evaluateResident(double *sq_norm, std::string *err) {
+    if (!residentAvailable()) {
+        if (err) *err = "icg_marg_prior_evaluate_resident is not in this build";
+        return false;
+    }
+    if (!ctx_) {
+        if (err) *err = "MarginalizationPriorSet::evaluateResident: no set";
+        return false;
+    }
+    if (icg_marg_prior_evaluate_resident(ctx_, x_.data(), sq_norm) != ICG_OK) {
         if (err) *err = icg_last_error(ctx_);
         return false;
     }

@@ -19,6 +19,7 @@
 #pragma weak icg_reproj_schur_windows_resident
 #pragma weak icg_reproj_solve_windows
 #pragma weak icg_reproj_host_parts_build
+#pragma weak icg_reproj_host_parts_build_prior
 
 namespace icg {
 
@@ -29,6 +30,8 @@ bool WindowSolverBatch::deviceReducedSolveAvailable() {
 }
 
 bool WindowSolverBatch::deviceHostPartAvailable() { return &icg_reproj_host_parts_build != nullptr; }
+
+bool WindowSolverBatch::devicePriorAvailable() { return &icg_reproj_host_parts_build_prior != nullptr && MarginalizationPriorSet::residentAvailable(); }
 
 WindowSolverBatch::WindowSolverBatch(int device, double huber_delta, int host_threads)
     : factors_(device, host_threads, "WindowSolverBatch"), huber_(huber_delta) {}
@@ -113,12 +116,27 @@ bool WindowSolverBatch::layout() {
         if (!device_host_part_) return;
         // the blocks of the window's host part: their shapes and columns follow from the problem, not from an evaluation
         W.host_blocks.clear(), W.host_cols.clear();
+        W.prior_residual = W.prior_in_set = W.prior_block = -1;
         std::vector<int> cols;
         for (size_t id = 0; id < W.problem.residuals.size(); id++) {
             const solver_detail::Residual &R = W.problem.residuals[id];
             if (R.removed) continue;
+            // device prior: the window's first prior without a loss (a robustified prior and a second prior stay on the pool)
+            const MargPriorSource *src = device_prior_ && W.prior_residual < 0 && !R.loss ? dynamic_cast<const MargPriorSource *>(R.cost.get()) : nullptr;
+            if (src) {
+                const MargPriorView &v = src->margPriorView();
+                const auto &sizes      = R.cost->parameter_block_sizes();
+                bool fits              = v.r == R.cost->num_residuals() && v.n_blocks == (int) sizes.size();
+                for (int b = 0; fits && b < v.n_blocks; b++) fits = v.size[b] == sizes[(size_t) b];
+                if (!fits) {
+                    errs[w] = "a marginalization prior's view does not describe its residual block";
+                    return;
+                }
+                W.prior_residual = (int) id;
+            }
             solver_detail::hostBlockColumns(W.problem, R, cols);
             if (cols.empty()) continue;
+            if ((int) id == W.prior_residual) W.prior_block = (int) W.host_blocks.size();
             W.host_blocks.push_back({(int) id, R.cost->num_residuals(), (int) cols.size(), 0, 0, 0});
             W.host_cols.insert(W.host_cols.end(), cols.begin(), cols.end());
         }
@@ -142,6 +160,24 @@ bool WindowSolverBatch::layout() {
             }
             hp_cols_.insert(hp_cols_.end(), W.host_cols.begin(), W.host_cols.end());
             hp_blk_off_.push_back((int32_t) hp_nr_.size());
+        }
+        // device prior: the resident set holds the windows that have a prior, in window order; a prior block's columns of J0 are the free
+        // local columns of its non-constant parameter blocks in block order, the columns gatherHostBlock selects
+        prior_views_.clear(), hp_prior_cols_.clear();
+        hp_prior_of_.assign(hp_nr_.size(), -1);
+        for (Window &W : windows_) {
+            if (W.prior_residual < 0) continue;
+            const solver_detail::Residual &R = W.problem.residuals[(size_t) W.prior_residual];
+            const MargPriorView &v           = dynamic_cast<const MargPriorSource *>(R.cost.get())->margPriorView();
+            W.prior_in_set                   = (int) prior_views_.size();
+            prior_views_.push_back(v);
+            if (W.prior_block < 0) continue;
+            hp_prior_of_[(size_t) (W.blk_begin + W.prior_block)] = W.prior_in_set;
+            for (size_t a = 0; a < R.blocks.size(); a++) {
+                const solver_detail::Block &A = W.problem.blocks[(size_t) W.problem.block_of.at(R.blocks[a])];
+                if (A.column < 0) continue;
+                for (int x = 0; x < A.local; x++) hp_prior_cols_.push_back(v.index[a] + x);
+            }
         }
     }
     return P_ > 0;
@@ -190,6 +226,15 @@ struct WindowSolverBatch::Run {
         std::vector<int64_t> jac_off;
         std::vector<uint8_t> has_shipped;
     };
+    // device prior: e . e of every resident prior at the last evaluated point, the cost of every residual of every window as the pool
+    // recorded it (the prior's comes from sq), and the windows whose prior Jacobian was gathered on the device in this solve
+    struct DevicePrior {
+        bool on = false;
+        std::vector<double> sq;
+        std::vector<std::vector<double>> res_cost;
+        std::vector<uint8_t> gathered;
+        std::string err;
+    };
 
     const Options &o;
     const ReducedPath path;
@@ -203,6 +248,7 @@ struct WindowSolverBatch::Run {
     std::vector<double> host_cost;
     DeviceSolve dev;
     DeviceParts hp;
+    DevicePrior prior;
     bool first = true;                                         // no window has its initial cost yet
     bool all_done = false, any_step = false, any_trial = false; // what solve() decides on after a phase
     BatchClock clk;
@@ -233,6 +279,14 @@ bool WindowSolverBatch::resolvePath(ReducedPath *path) {
         error_ = "setDeviceHostPart(true) needs setDeviceReducedSolve(true): the host parts are built where the device solve reads them";
         return false;
     }
+    if (device_prior_ && !devicePriorAvailable()) {
+        error_ = std::string(MarginalizationPriorSet::residentAvailable() ? "icg_reproj_host_parts_build_prior" : "icg_marg_prior_evaluate_resident") + " is not in this build";
+        return false;
+    }
+    if (device_prior_ && !device_host_part_) {
+        error_ = "setDevicePrior(true) needs setDeviceHostPart(true): the resident prior is read where the host parts are built";
+        return false;
+    }
     *path = device_host_part_ ? ReducedPath::DeviceSolveDeviceParts : device_reduced_ ? ReducedPath::DeviceSolve : ReducedPath::HostSolve;
     return true;
 }
@@ -259,6 +313,14 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
         H.J.resize(hp_J_total_), H.shipped.resize(hp_J_total_), H.r.assign(hp_r_total_, 0.0);
         H.jac_off.assign(hp_nr_.size(), 0), H.has_shipped.assign(hp_nr_.size(), 0);
         H.s.assign(NW * R.P, 0.0), H.diag.assign(NW * R.P, 0.0);
+    }
+    if (device_prior_ && !prior_views_.empty()) {
+        // the priors become resident once per solve: J0 crosses the link here and not again
+        Run::DevicePrior &D = R.prior;
+        if (!prior_set_.set(factors_.ctx(), prior_views_, &error_)) return false;
+        D.on = true;
+        D.sq.assign(prior_views_.size(), 0.0), D.gathered.assign(NW, 0), D.res_cost.resize(NW);
+        for (size_t w = 0; w < NW; w++) D.res_cost[w].assign(windows_[w].problem.residuals.size(), 0.0);
     }
     for (;;) {
         if (!linearize(R) || !reducedSolves(R)) return false;
@@ -310,12 +372,15 @@ bool WindowSolverBatch::linearize(Run &R) {
         // runHalves); the sums that need both are formed after the join.
         R.clk.start();
         int dev_rc = ICG_OK;
+        bool prior_ok = true;
+        if (R.prior.on && any_lin) packPriors();
         if (!side_) side_.reset(new SideThread());
         SideCall dev(*side_, [&] {
-            if (R.deviceSolve())
+            if (R.deviceSolve()) {
                 dev_rc = icg_reproj_schur_windows_resident(ctx, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), R.reassemble.data(),
                                                            R.damp.data(), o.min_lm_diagonal, o.max_lm_diagonal, R.s.data(), R.diag.data(), R.cost.data());
-            else
+                if (dev_rc == ICG_OK && R.prior.on && any_lin) prior_ok = evaluatePriors(R);
+            } else
                 dev_rc = icg_reproj_schur_windows_view(ctx, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), R.reassemble.data(),
                                                        R.damp.data(), o.min_lm_diagonal, o.max_lm_diagonal, &R.S, R.s.data(), R.diag.data(), R.cost.data());
         });
@@ -330,6 +395,10 @@ bool WindowSolverBatch::linearize(Run &R) {
         dev.join();
         R.clk.stop(PH_SCHUR_TAIL); // (what is left of the device call once the host half is through)
         if (dev_rc != ICG_OK) return fail(R.deviceSolve() ? "icg_reproj_schur_windows_resident" : "icg_reproj_schur_windows_view");
+        if (!prior_ok) {
+            error_ = R.prior.err;
+            return false;
+        }
         if (host_failed.load()) {
             error_ = "a host cost function failed to evaluate";
             return false;
@@ -337,8 +406,15 @@ bool WindowSolverBatch::linearize(Run &R) {
         if (R.deviceParts() && any_lin) {
             // the parts of the re-linearized windows, built in their slots on the device; s and diag of those windows come back
             R.clk.start();
-            if (icg_reproj_host_parts_build(ctx, P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(),
-                                            R.hp.jac_off.data(), R.hp.J.data(), R.hp.r.data(), R.hp.s.data(), R.hp.diag.data(), nullptr) != ICG_OK)
+            if (R.prior.on) {
+                // the resident priors' blocks take their residuals, and at a window's first rebuild their Jacobians, where they are
+                if (icg_reproj_host_parts_build_prior(ctx, P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(),
+                                                      R.hp.jac_off.data(), R.hp.J.data(), R.hp.r.data(), R.hp.s.data(), R.hp.diag.data(), nullptr, hp_prior_of_.data(),
+                                                      hp_prior_cols_.data()) != ICG_OK)
+                    return fail("icg_reproj_host_parts_build_prior");
+                for (size_t w = 0; w < NW; w++) R.prior.gathered[w] |= R.reassemble[w];
+            } else if (icg_reproj_host_parts_build(ctx, P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(),
+                                                   R.hp.jac_off.data(), R.hp.J.data(), R.hp.r.data(), R.hp.s.data(), R.hp.diag.data(), nullptr) != ICG_OK)
                 return fail("icg_reproj_host_parts_build");
             R.clk.stop(PH_HOST_PARTS);
         }
@@ -347,6 +423,7 @@ bool WindowSolverBatch::linearize(Run &R) {
             Run::State &T = R.st[w];
             if (T.done || !(T.relinearize || T.redamp)) return;
             Window &W = windows_[w];
+            if (R.prior.on && T.relinearize) sumHostCosts(R, w); // (the device value has arrived)
             // the cost at the linearization point initialises the window on the first pass; afterwards it equals the accepted
             // trial cost and is kept (the same bookkeeping as WindowSolver)
             if (T.relinearize && R.first) T.tr.cost = R.cost[w] + R.host_cost[w], T.tr.summary.initial_cost = T.tr.cost;
@@ -388,8 +465,16 @@ bool WindowSolverBatch::hostHalfOfWindow(Run &R, size_t w) {
             const solver_detail::Residual &Res = W.problem.residuals[id];
             if (Res.removed) continue;
             const bool has = next < W.host_blocks.size() && W.host_blocks[next].residual == (int) id;
-            double *Jd     = has ? &H.J[W.host_blocks[next].J_off] : nullptr;
-            if (solver_detail::gatherHostBlock(W.problem, Res, &R.host_cost[w], cols, none, none, Jd, has ? &H.r[W.host_blocks[next].r_off] : nullptr) < 0)
+            double *cost   = &R.host_cost[w];
+            if (R.prior.on) cost = &R.prior.res_cost[w][id], *cost = 0.0; // per residual: the window's sum waits for the device value
+            if (R.prior.on && (int) id == W.prior_residual) {
+                // evaluated where it is resident: the block's slots in r are placed only, its Jacobian is gathered from J0 on the device at
+                // the window's first rebuild of the solve and kept afterwards
+                if (has) H.jac_off[(size_t) W.blk_begin + next] = R.prior.gathered[w] ? -1 : ICG_HP_JAC_FROM_PRIOR, next++;
+                continue;
+            }
+            double *Jd = has ? &H.J[W.host_blocks[next].J_off] : nullptr;
+            if (solver_detail::gatherHostBlock(W.problem, Res, cost, cols, none, none, Jd, has ? &H.r[W.host_blocks[next].r_off] : nullptr) < 0)
                 return false;
             if (!has) continue;
             // the same Jacobian as at the window's previous rebuild stays where it is on the device
@@ -408,6 +493,26 @@ bool WindowSolverBatch::hostHalfOfWindow(Run &R, size_t w) {
     }
     }
     return false;
+}
+
+// device prior: every window's prior blocks at their places in the set's evaluation point (on the driving thread, before the phase's device call)
+void WindowSolverBatch::packPriors() {
+    for (const Window &W : windows_)
+        if (W.prior_residual >= 0) prior_set_.pack((size_t) W.prior_in_set, W.problem.residuals[(size_t) W.prior_residual].blocks.data());
+}
+
+bool WindowSolverBatch::evaluatePriors(Run &R) { return prior_set_.evaluateResident(R.prior.sq.data(), &R.prior.err); }
+
+// device prior: the window's host cost from the costs the pool recorded per residual and the device's squared norm in the prior's place,
+// added up from zero in residual order: hostFactors' sum
+void WindowSolverBatch::sumHostCosts(Run &R, size_t w) {
+    const Window &W = windows_[w];
+    double cost     = 0.0;
+    for (size_t id = 0; id < W.problem.residuals.size(); id++) {
+        if (W.problem.residuals[id].removed) continue;
+        cost += (int) id == W.prior_residual ? 0.5 * R.prior.sq[(size_t) W.prior_in_set] : R.prior.res_cost[w][id];
+    }
+    R.host_cost[w] = cost;
 }
 
 // ---- every open window: iteration budget, gradient test, reduced solve --------------------------------------------------------------------
@@ -552,6 +657,8 @@ bool WindowSolverBatch::trialCosts(Run &R) {
     R.clk.start();
     factors_.gather(R.poses, R.ext, R.inv, R.td);
     const char *dev_fail = nullptr;
+    bool prior_ok        = true;
+    if (R.prior.on) packPriors();
     if (!side_) side_.reset(new SideThread());
     SideCall trial(*side_, [&] {
         if (icg_reproj_eval_windows(ctx, factors_.numPoses(), R.poses.data(), R.ext.data(), factors_.numLandmarks(), R.inv.data(), R.td.data(), 0, huber_) !=
@@ -559,20 +666,40 @@ bool WindowSolverBatch::trialCosts(Run &R) {
             dev_fail = "icg_reproj_eval_windows";
         else if (icg_reproj_cost_windows(ctx, active_.data(), R.cost.data()) != ICG_OK)
             dev_fail = "icg_reproj_cost_windows";
+        else if (R.prior.on)
+            prior_ok = evaluatePriors(R);
     });
     std::atomic<int> trial_failed{0};
     R.host_cost.assign(NW, 0.0);
     factors_.forEachWindow(NW, [&](size_t w) {
         if (!R.st[w].stepped) return;
-        if (!solver_detail::hostFactors(windows_[w].problem, R.P, nullptr, nullptr, nullptr, &R.host_cost[w])) trial_failed++;
+        if (!R.prior.on) {
+            if (!solver_detail::hostFactors(windows_[w].problem, R.P, nullptr, nullptr, nullptr, &R.host_cost[w])) trial_failed++;
+            return;
+        }
+        // the cost-only pass of hostFactors per residual, the resident prior left to the device
+        const Window &W = windows_[w];
+        for (size_t id = 0; id < W.problem.residuals.size(); id++) {
+            const solver_detail::Residual &Res = W.problem.residuals[id];
+            if (Res.removed || (int) id == W.prior_residual) continue;
+            if (!solver_detail::residualCost(Res, true, &R.prior.res_cost[w][id])) {
+                trial_failed++;
+                return;
+            }
+        }
     });
     trial.join();
     if (dev_fail) return fail(dev_fail);
+    if (!prior_ok) {
+        error_ = R.prior.err;
+        return false;
+    }
     R.clk.stop(PH_TRIAL_EVAL);
     R.clk.start();
     factors_.forEachWindow(NW, [&](size_t w) {
         Run::State &T = R.st[w];
         if (!T.stepped || trial_failed.load()) return;
+        if (R.prior.on) sumHostCosts(R, w);
         bool accepted;
         T.done = T.tr.trial(R.o, R.cost[w] + R.host_cost[w], T.model, windows_[w].problem, &accepted);
         if (accepted)

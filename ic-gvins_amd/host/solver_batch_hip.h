@@ -67,6 +67,18 @@ public:
     void setDeviceHostPart(bool on) { device_host_part_ = on; }
     bool deviceHostPart() const { return device_host_part_; }
     static bool deviceHostPartAvailable();
+    // With the device host part: every window's marginalization prior is RESIDENT on the device for the solve (MarginalizationPriorSet: J0 goes
+    // up once per solve()) and evaluated there at every linearization and every trial point (icg_marg_prior_evaluate_resident, on the side
+    // thread that makes the phase's device call: after the Schur call, beside the trial evaluation).  Its residual and its Jacobian reach the
+    // host-part kernel without crossing the link (icg_reproj_host_parts_build_prior: the first rebuild of a window in a solve gathers the
+    // Jacobian from J0 on the device, the later ones keep it); per evaluation only x goes up and one squared norm per window comes back, and
+    // 0.5 * that norm takes the prior's place in the window's host cost, summed in residual order as hostFactors sums it: states, inverse
+    // depths and summaries are the host's bit for bit.  The prior of a window is its first residual block whose cost function implements
+    // MargPriorSource (factors.h) and has no loss function; a robustified prior and a second prior in a window stay on the pool.  Off by
+    // default; needs setDeviceHostPart(true) (solve() fails otherwise) and the two C entries, referenced weakly like the ones above.
+    void setDevicePrior(bool on) { device_prior_ = on; }
+    bool devicePrior() const { return device_prior_; }
+    static bool devicePriorAvailable();
     bool solve(const Options &options, std::vector<Summary> *summaries);
     // removeReprojectionFactorsByChi2 (ic_gvins.cc:1269-1297) for every window; returns the number removed per window
     std::vector<int> removeReprojectionFactorsByChi2(double chi2);
@@ -87,6 +99,9 @@ private:
         std::vector<HostBlock> host_blocks;
         std::vector<int32_t> host_cols; // their columns, block after block
         int blk_begin{0};
+        // device prior (layout()): the residual that is the window's resident prior (-1: none), its index in the resident set, its position
+        // among host_blocks (-1: every block of the prior is constant: it has a cost but no host block)
+        int prior_residual{-1}, prior_in_set{-1}, prior_block{-1};
     };
     // how solve() forms and solves the reduced systems: resolved from the two setters at its top
     enum class ReducedPath { HostSolve, DeviceSolve, DeviceSolveDeviceParts };
@@ -101,6 +116,11 @@ private:
     bool trialCosts(Run &R);
     // where the paths differ: the host half of a window's linearization, and the reduced solves
     bool hostHalfOfWindow(Run &R, size_t w);
+    // device prior: the evaluation point of every resident prior (driving thread), the resident evaluation of a phase (side thread), and
+    // a window's host cost once the device value is there
+    void packPriors();
+    bool evaluatePriors(Run &R);
+    void sumHostCosts(Run &R, size_t w);
     void solveWindowOnHost(Run &R, size_t w);
     bool solveWindowsOnDevice(Run &R);
     bool fail(const char *what);
@@ -113,10 +133,14 @@ private:
     std::vector<int32_t> col_pose_, col_ext_, col_td_;
     int P_{0};
     bool finalized_{false};
-    bool device_reduced_{false}, device_host_part_{false};
+    bool device_reduced_{false}, device_host_part_{false}, device_prior_{false};
     // device host part (layout()): the block list of all windows as icg_reproj_host_parts_build takes it, and the sizes of a call's J and r
     std::vector<int32_t> hp_blk_off_, hp_nr_, hp_nf_, hp_cols_;
     size_t hp_J_total_{0}, hp_r_total_{0};
+    // device prior (layout()): per block of that list the prior it is (-1: none) and the prior blocks' columns of J0; the resident set
+    std::vector<int32_t> hp_prior_of_, hp_prior_cols_;
+    std::vector<MargPriorView> prior_views_;
+    MarginalizationPriorSet prior_set_;
     std::string error_;
 };
 

@@ -24,6 +24,7 @@ EXPORTS = [
     "icg_reproj_landmark_diag_windows",
     "icg_marg_prior_set", "icg_marg_prior_evaluate", "icg_marg_linearize_batch",
     "icg_chol_solve_batch", "icg_reproj_schur_windows_resident", "icg_reproj_solve_windows", "icg_reproj_host_parts_build",
+    "icg_marg_prior_evaluate_resident", "icg_reproj_host_parts_build_prior",
 ]
 
 
@@ -31,6 +32,7 @@ MARG_MAX_R = 1024  # ICG_MARG_MAX_R of include/icgvins_hip.h
 MARG_LIN_MAX_P = 512  # ICG_MARG_LIN_MAX_P
 CHOL_MAX_N = 512  # ICG_CHOL_MAX_N
 HOST_PART_MAX_NR = 1024  # ICG_HOST_PART_MAX_NR
+HP_JAC_FROM_PRIOR = -2  # ICG_HP_JAC_FROM_PRIOR
 
 
 class IcgError(RuntimeError):
@@ -502,6 +504,50 @@ class Context:
             at += sizes[w]
         return s, dg, parts
 
+    def reproj_host_parts_build_prior_raw(self, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, prior_of, prior_cols):
+        """icg_reproj_host_parts_build_prior on the caller's arrays (None = NULL; the outputs are written in place) -> the return code"""
+        return self.lib.icg_reproj_host_parts_build_prior(self.h, int(P), _p(Pw), _p(rebuild), _p(blk_off), _p(nr), _p(nf), _p(cols), _p(jac_off), _p(J), _p(r),
+                                                          _p(host_s), _p(host_diag), _p(part_out), _p(prior_of), _p(prior_cols))
+
+    def reproj_host_parts_build_prior(self, P, Pw, windows, rebuild=None, host_s=None, host_diag=None):
+        """icg_reproj_host_parts_build_prior.  windows: per window a list of blocks; an ordinary block is (J nr x nf, r, cols, keep) as in
+        reproj_host_parts_build, a prior block is ("prior", p, prior_cols, cols, how): prior p of the resident set (marg_prior_set), how =
+        "gather" (ICG_HP_JAC_FROM_PRIOR), "keep" (-1) or the Jacobian to upload.  The prior blocks' slots in r are filled with NaN: they
+        are not read.  -> (host_s, host_diag, parts) as reproj_host_parts_build"""
+        W = self._nwin
+        Pw = _i32(Pw).reshape(W)
+        rb = np.ones(W, np.uint8) if rebuild is None else np.ascontiguousarray(rebuild, np.uint8).reshape(W)
+        blocks = [b for win in windows for b in win]
+        blk_off = _i32(np.concatenate([[0], np.cumsum([len(win) for win in windows])]))
+        is_prior = [isinstance(b[0], str) for b in blocks]
+        nr = _i32([self._marg_r[b[1]] if pr else np.shape(b[0])[0] for b, pr in zip(blocks, is_prior)])
+        nf = _i32([len(b[3]) if pr else np.shape(b[0])[1] for b, pr in zip(blocks, is_prior)])
+        cols = _i32(np.concatenate([_i32(b[3] if pr else b[2]).reshape(-1) for b, pr in zip(blocks, is_prior)])) if blocks else _i32([])
+        r = _f64(np.concatenate([np.full(n, np.nan) if pr else _f64(b[1]).reshape(-1) for b, pr, n in zip(blocks, is_prior, nr)])) if blocks else _f64([])
+        prior_of = _i32([b[1] if pr else -1 for b, pr in zip(blocks, is_prior)])
+        pcs = [_i32(b[2]).reshape(-1) for b, pr in zip(blocks, is_prior) if pr]
+        prior_cols = _i32(np.concatenate(pcs)) if pcs else None
+        jac_off, Js, at = np.full(len(blocks), -1, np.int64), [], 0
+        for k, (b, pr) in enumerate(zip(blocks, is_prior)):
+            if pr and isinstance(b[4], str):
+                jac_off[k] = HP_JAC_FROM_PRIOR if b[4] == "gather" else -1
+            elif pr or not b[3]:
+                jac_off[k] = at
+                Js.append(_f64(b[4] if pr else b[0]).reshape(-1))
+                at += Js[-1].size
+        J = _f64(np.concatenate(Js)) if Js else None
+        s = np.zeros((W, P)) if host_s is None else host_s
+        dg = np.zeros((W, P)) if host_diag is None else host_diag
+        sizes = [int(Pw[w]) * (int(Pw[w]) + 1) // 2 if rb[w] else 0 for w in range(W)]
+        part = np.zeros(max(1, sum(sizes)))
+        self._ck(self.reproj_host_parts_build_prior_raw(P, Pw, rb, blk_off, nr, nf, cols, jac_off, J, r, s, dg, part, prior_of, prior_cols),
+                 "icg_reproj_host_parts_build_prior")
+        parts, at = [], 0
+        for w in range(W):
+            parts.append(part[at:at + sizes[w]].copy() if rb[w] else None)
+            at += sizes[w]
+        return s, dg, parts
+
     def reproj_backsub_windows(self, P, delta_c, n_lm):
         out, terms = np.zeros(n_lm), np.zeros((self._nwin, 2))
         self._ck(self.lib.icg_reproj_backsub_windows(self.h, int(P), _p(_f64(delta_c)), _p(out), _p(terms)), "icg_reproj_backsub_windows")
@@ -562,6 +608,7 @@ class Context:
                  "icg_marg_prior_set")
         xs = np.array([int(block_size[block_off[w]:block_off[w + 1]].sum()) for w in range(len(r))], np.int64)
         self._marg = (len(r), int(r.sum()), int(xs.sum()), int((r.astype(np.int64) * xs).sum()))
+        self._marg_r = r.copy()
 
     def marg_prior_evaluate(self, x, want_jac=False, want_grad=False, want_sq_norm=False):
         """icg_marg_prior_evaluate -> (residuals, jacobians | None, gradient | None, sq_norm | None), flat, window after window"""
@@ -575,6 +622,16 @@ class Context:
         sq = np.zeros(n) if want_sq_norm else None
         self._ck(self.lib.icg_marg_prior_evaluate(self.h, _p(x), _p(res), _p(jac), _p(grad), _p(sq)), "icg_marg_prior_evaluate")
         return res, jac, grad, sq
+
+    def marg_prior_evaluate_resident(self, x):
+        """icg_marg_prior_evaluate_resident: the residuals stay on the device for reproj_host_parts_build_prior -> sq_norm (e . e per window)"""
+        n, nr, nx, njac = getattr(self, "_marg", None) or (0, 0, 0, 0)
+        x = _f64(x).reshape(-1)
+        if n and x.shape[0] != nx:
+            raise IcgError(f"marg_prior_evaluate_resident: x has {x.shape[0]} values, the resident set takes {nx}")
+        sq = np.zeros(max(n, 1))
+        self._ck(self.lib.icg_marg_prior_evaluate_resident(self.h, _p(x), _p(sq)), "icg_marg_prior_evaluate_resident")
+        return sq[:n]
 
     # ---- M3
     def marg_linearize_batch(self, P, m, H, b, eps=1e-8, want_Hp=True, want_bp=True, want_evals=True, want_min_ev=True, want_status=True):

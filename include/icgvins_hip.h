@@ -290,6 +290,29 @@ int icg_reproj_solve_windows(icg_ctx *ctx, int P, const int32_t *Pw, const uint8
 int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr, const int32_t *nf,
                                 const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s, double *host_diag,
                                 double *part_out);
+/* The same call for windows whose marginalization prior is resident on the device (icg_marg_prior_set) and was evaluated there
+ * (icg_marg_prior_evaluate_resident): neither the prior's residual nor its Jacobian crosses the link.  The arguments of
+ * icg_reproj_host_parts_build, then
+ *   prior_of    one entry per block: -1 (any negative value) = the block is fed as above; p >= 0 = the block is prior p of the resident set (the
+ *               set's window index, which need not be the partition's).  NULL: exactly icg_reproj_host_parts_build.
+ *   prior_cols  for the prior blocks only, block after block in the order of the block list (the prior blocks of windows that are not rebuilt
+ *               included: their nf places the others'): nf[b] column indices into that prior's J0, each in [0, r[p]).
+ * A prior block of a rebuilt window has nr[b] == r[p].  Its residual is the resident one of the last icg_marg_prior_evaluate_resident; its
+ * slots in r are placed by nr[b] like every block's but are not read.  Its Jacobian: jac_off[b] == ICG_HP_JAC_FROM_PRIOR fills the kept
+ * Jacobian on the device, Jd[k][y] = J0[k][prior_cols[y]] (a copy: the values hostFactors gathers from the prior's Jacobian blocks when
+ * prior_cols lists the free local columns of its blocks); -1 uses the kept one (J0 is constant between two marginalizations: the first
+ * rebuild of a solve gathers, the later ones keep); an offset >= 0 uploads as above.  The gather and the copy of the residuals are one kernel
+ * ahead of the unchanged accumulation (no atomics, a plain copy): the outputs are the bits icg_reproj_host_parts_build gives when it is fed
+ * the same residuals and gathered columns, and a window's outputs are the same bits alone, in any batch, and run after run.
+ * ICG_ERR_INVALID beyond the cases above (the message names the window and the block), for a block of a rebuilt window: prior_of[b] outside
+ * the resident set, nr[b] != r[p], a prior_cols entry outside [0, r[p]), no set resident or none evaluated since it was set (icg_marg_prior_set
+ * invalidates the kept residuals), prior blocks without prior_cols, ICG_HP_JAC_FROM_PRIOR for a block with prior_of[b] < 0 (or without
+ * prior_of).  ICG_ERR_CAPACITY: more than 65535 prior blocks in the rebuilt windows.  After an error nothing was launched and no output was
+ * touched. */
+#define ICG_HP_JAC_FROM_PRIOR (-2)
+int icg_reproj_host_parts_build_prior(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
+                                      const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s,
+                                      double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols);
 /* problem setup: pre-sizes the resident window systems and the staging memory for reduced systems of size P (a hint; optional) */
 int icg_reproj_reserve_windows(icg_ctx *ctx, int P);
 int icg_reproj_backsub_windows(icg_ctx *ctx, int P, const double *delta_c, double *delta_l, double *lm_terms);
@@ -357,6 +380,11 @@ int icg_marg_prior_set(icg_ctx *ctx, int n_windows, const int32_t *r, const int3
  *   sq_norm    e . e per window (n_windows), summed from 0 in row order (twice the Ceres cost)
  * ICG_ERR_INVALID without a resident set or with NULL x / residuals. */
 int icg_marg_prior_evaluate(icg_ctx *ctx, const double *x, double *residuals, double *jacobians, double *gradient, double *sq_norm);
+/* The same evaluation of every resident prior at x (laid out like x0) with the residuals LEFT on the device, in a buffer the set owns, for
+ * icg_reproj_host_parts_build_prior: only x crosses the link on the way in and sq_norm (n_windows: e . e per window) on the way out.  The
+ * arithmetic is icg_marg_prior_evaluate's: sq_norm[w] has the bits that call returns.  The kept residuals are those of the last call;
+ * icg_marg_prior_set invalidates them.  ICG_ERR_INVALID without a resident set or with a NULL x / sq_norm: nothing is launched. */
+int icg_marg_prior_evaluate_resident(icg_ctx *ctx, const double *x, double *sq_norm);
 
 /* ---- M3: the Schur step on the marginalized pose / mix block and the linearization (factors/marginalization_info.h:153-192) for the
  * reduced systems of many windows, one workgroup per window.  Window w: H (P[w] x P[w], row-major) and b (P[w]), concatenated window after
