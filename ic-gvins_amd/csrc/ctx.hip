@@ -1,6 +1,7 @@
 // Context, memory arenas and per-kernel HIP-event profiling for libicgvins_hip.so.
 #include <algorithm>
 #include <cstdarg>
+#include <mutex>
 
 #include <sys/prctl.h>
 #include <time.h>
@@ -151,8 +152,44 @@ extern "C" int icg_ctx_create(const icg_ctx_config *cfg, icg_ctx **out) {
     return ICG_OK;
 }
 
+// ---- kept linearizations: the live ids of the process ----------------------------------------------------------
+namespace {
+// (never destroyed: a context may be destroyed from another library's static teardown, after this library's own)
+std::mutex &g_kept_mutex          = *new std::mutex;
+std::map<uint64_t, icg_ctx *> &g_kept = *new std::map<uint64_t, icg_ctx *>;
+std::atomic<uint64_t> g_kept_next{1};
+} // namespace
+
+uint64_t icg_kept_register(icg_ctx *ctx) {
+    const uint64_t id = g_kept_next.fetch_add(1, std::memory_order_relaxed);
+    std::lock_guard<std::mutex> lock(g_kept_mutex);
+    g_kept[id]       = ctx;
+    ctx->lin_kept.id = id;
+    return id;
+}
+
+void icg_kept_drop(icg_ctx *ctx) {
+    if (ctx->lin_kept.id == 0) return;
+    std::lock_guard<std::mutex> lock(g_kept_mutex);
+    g_kept.erase(ctx->lin_kept.id);
+    ctx->lin_kept.id = 0;
+}
+
+icg_ctx *icg_kept_lookup(uint64_t id) {
+    std::lock_guard<std::mutex> lock(g_kept_mutex);
+    auto it = g_kept.find(id);
+    return it == g_kept.end() ? nullptr : it->second;
+}
+
+extern "C" int icg_marg_linearized_release(icg_ctx *ctx) {
+    if (!ctx) return ICG_ERR_INVALID;
+    icg_kept_drop(ctx);
+    return ICG_OK;
+}
+
 extern "C" void icg_ctx_destroy(icg_ctx *ctx) {
     if (!ctx) return;
+    icg_kept_drop(ctx); // (before its buffer is freed below)
     (void) hipSetDevice(ctx->cfg.device);
     if (ctx->stream) (void) hipStreamSynchronize(ctx->stream);
     for (auto e : ctx->ev_pool) (void) hipEventDestroy(e);

@@ -79,6 +79,18 @@ struct icg_marg_set {
     std::vector<int64_t> h_j_off;
 };
 
+// The linearization icg_marg_linearize_batch_keep left on the device (marg_linearize.hip): J0 of every window (r x r row-major, window after
+// window), then e0 of every window, in one buffer the context owns.  id = 0: nothing is kept.  A live id is listed in the process-wide table
+// of ctx.hip (icg_kept_register / icg_kept_drop / icg_kept_lookup), through which icg_marg_prior_set_from_kept of any context finds it.
+struct icg_lin_kept {
+    uint64_t id = 0;
+    double *d_buf = nullptr;
+    size_t cap = 0; // bytes
+    int64_t total_rr = 0, total_r = 0;
+    std::vector<int32_t> r;             // per kept window
+    std::vector<int64_t> rr_off, r_off; // its J0 in d_buf; its e0 in d_buf + total_rr
+};
+
 // Host-factor parts built on the device (host_part.hip): the Jacobian of every factor block of every window, kept densely (window after
 // window, block after block) in one of two device buffers until a rebuild replaces it; a call that changes the layout moves what stays
 // into the other buffer.  win is empty while nothing is kept.
@@ -160,6 +172,7 @@ struct icg_ctx {
     // M3 (marg_linearize.hip): per-window working memory of icg_marg_linearize_batch for the windows that do not fit in LDS; grows on demand
     double *d_lin_scratch = nullptr;
     size_t lin_scratch_cap = 0; // bytes
+    icg_lin_kept lin_kept;      // what icg_marg_linearize_batch_keep left for icg_marg_prior_set_from_kept
     // Reduced camera solve (chol.hip, reproj_schur.hip): the W x P x P reduced systems icg_reproj_schur_windows_resident leaves on the device, every
     // window's host-factor part (packed lower triangle, one slot of P (P + 1) / 2 doubles per window, kept until it is replaced) and the
     // working memory of the systems that do not fit in LDS; all grow on demand
@@ -193,6 +206,13 @@ static inline void icg_red_drop_host_parts(icg_ctx *ctx, size_t n_windows) {
     ctx->red_H_cols.assign(n_windows, 0);
     ctx->hp.win.clear();
 }
+
+// kept linearizations (ctx.hip): a mutex-protected process-wide table of the live ids and their contexts, so that a consumer never follows
+// an id to a buffer that is gone.  register: ctx->lin_kept gets a new id (non-zero, never reused) and is listed; drop: ctx's kept set, if
+// any, is unlisted and its id cleared (the buffer stays allocated for the next one); lookup: the owner of a live id, nullptr otherwise.
+uint64_t icg_kept_register(icg_ctx *ctx);
+void icg_kept_drop(icg_ctx *ctx);
+icg_ctx *icg_kept_lookup(uint64_t id);
 
 int icg_fail(icg_ctx *ctx, int code, const char *fmt, ...);
 int icg_hip_check(icg_ctx *ctx, hipError_t e, const char *what);

@@ -57,6 +57,45 @@ __global__ __launch_bounds__(MARG_THREADS) void k_marg_store(int n_windows, cons
     }
 }
 
+// The same store for a set whose windows come from different places (icg_marg_prior_set_from_kept): window w's row-major J0 is read at
+// src_J[w] and its e0 at src_e[w] — a window of a kept linearization (icg_lin_kept, this context's or another's on the device) or of the part
+// the host shipped.  Tiles as above: the source is read and J written along rows, JT written along rows from the padded tile; the workgroups
+// of tile 0 also gather the window's e0.
+__global__ __launch_bounds__(MARG_THREADS) void k_marg_store_from(int n_windows, const int32_t *__restrict__ r_of, const int64_t *__restrict__ j_off,
+                                                                  const int32_t *__restrict__ e_off, const double *const *__restrict__ src_J,
+                                                                  const double *const *__restrict__ src_e, double *__restrict__ J, double *__restrict__ JT,
+                                                                  double *__restrict__ e0) {
+    __shared__ double tile[MARG_TILE][MARG_TILE + 1];
+    const int w = blockIdx.y;
+    if (w >= n_windows) return;
+    const int r = r_of[w], nt = (r + MARG_TILE - 1) / MARG_TILE;
+    const double *s = src_J[w];
+    double *d = J + j_off[w], *dt = JT + j_off[w];
+    if (blockIdx.x == 0) {
+        const double *se = src_e[w];
+        double *de       = e0 + e_off[w];
+        for (int i = threadIdx.x; i < r; i += MARG_THREADS) de[i] = se[i];
+    }
+    const int tx = threadIdx.x & (MARG_TILE - 1), ty = threadIdx.x / MARG_TILE; // 32 x 8
+    for (int t = blockIdx.x; t < nt * nt; t += gridDim.x) {                      // (uniform per workgroup)
+        const int ti = t / nt, tj = t - ti * nt;
+        for (int y = ty; y < MARG_TILE; y += MARG_THREADS / MARG_TILE) {
+            const int i = ti * MARG_TILE + y, k = tj * MARG_TILE + tx;
+            if (i < r && k < r) {
+                const double v = s[(size_t) i * r + k];
+                d[(size_t) i * r + k] = v;
+                tile[y][tx]           = v;
+            }
+        }
+        __syncthreads();
+        for (int y = ty; y < MARG_TILE; y += MARG_THREADS / MARG_TILE) {
+            const int k = tj * MARG_TILE + y, i = ti * MARG_TILE + tx;
+            if (i < r && k < r) dt[(size_t) k * r + i] = tile[tx][y];
+        }
+        __syncthreads();
+    }
+}
+
 // One workgroup per window.  dx (a thread per block) and e (a thread per row) live in LDS; a row's sum is one thread's chain of r
 // dependent multiply-add pairs in k order — latency-bound by construction, the window count is what fills the chip.
 __global__ __launch_bounds__(MARG_THREADS) void k_marg_evaluate(int n_windows, marg_dev m, const double *__restrict__ x, double *__restrict__ residuals,
@@ -152,37 +191,66 @@ marg_dev marg_view(const icg_marg_set &s) {
     return m;
 }
 
-} // namespace
-
-extern "C" int icg_marg_prior_set(icg_ctx *ctx, int n_windows, const int32_t *r, const int32_t *block_off, const int32_t *block_size,
-                                  const int32_t *block_index, const double *x0, const double *J0, const double *e0) {
+// Both set entries.  from_kept: window w takes J0 / e0 from window src[w] of the kept linearization keep_id (src[w] >= 0) or from the next
+// window of J0 / e0 (src[w] == -1), which then hold only those windows; otherwise J0 / e0 hold every window and src is not read.
+int marg_set(const char *fn, bool from_kept, icg_ctx *ctx, uint64_t keep_id, int n_windows, const int32_t *src, const int32_t *r, const int32_t *block_off,
+             const int32_t *block_size, const int32_t *block_index, const double *x0, const double *J0, const double *e0) {
     if (!ctx) return ICG_ERR_INVALID;
     icg_marg_set &s = ctx->marg;
     s.n             = 0; // whatever set the context held is gone, also when this call fails
     s.res_valid     = false; // and so are the residuals it kept
-    if (n_windows <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_set: n_windows = %d", n_windows);
-    if (n_windows > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_prior_set: %d windows in one set (at most 65535)", n_windows);
-    if (!r || !block_off || !block_size || !block_index || !x0 || !J0 || !e0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_set: NULL argument");
-    if (block_off[0] != 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_set: window 0: block_off[0] = %d", block_off[0]);
+    if (n_windows <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: n_windows = %d", fn, n_windows);
+    if (n_windows > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %d windows in one set (at most 65535)", fn, n_windows);
+    if (!r || !block_off || !block_size || !block_index || !x0 || (from_kept ? !src : (!J0 || !e0))) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", fn);
+    if (block_off[0] != 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window 0: block_off[0] = %d", fn, block_off[0]);
     const size_t n = (size_t) n_windows;
     for (size_t w = 0; w < n; w++) {
-        if (r[w] <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_set: window %zu: r = %d", w, r[w]);
-        if (block_off[w + 1] < block_off[w]) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_set: window %zu: block_off not monotone", w);
+        if (r[w] <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: r = %d", fn, w, r[w]);
+        if (block_off[w + 1] < block_off[w]) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: block_off not monotone", fn, w);
         for (int b = block_off[w]; b < block_off[w + 1]; b++) {
             const int size = block_size[b], index = block_index[b], local = size == 7 ? 6 : size;
             if (size <= 0 || index < 0 || (int64_t) index + local > r[w])
-                return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_set: window %zu: block %d (size %d, index %d) does not fit r = %d", w,
+                return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: block %d (size %d, index %d) does not fit r = %d", fn, w,
                                 b - block_off[w], size, index, r[w]);
+        }
+    }
+    const icg_lin_kept *K = nullptr;
+    size_t host_j = 0, host_e = 0; // elements of J0 / e0 (from_kept: of the windows the host ships)
+    if (from_kept) {
+        bool any_kept = false;
+        for (size_t w = 0; w < n; w++) {
+            if (src[w] < -1) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: src = %d", fn, w, src[w]);
+            any_kept |= src[w] >= 0;
+        }
+        // (the id is looked at whenever a window names it; a set of shipped windows alone needs none)
+        const icg_ctx *owner = any_kept ? icg_kept_lookup(keep_id) : nullptr;
+        if (any_kept && !owner)
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: the kept linearization %llu is gone (released, replaced by a later linearize call, or its context destroyed)", fn,
+                            (unsigned long long) keep_id);
+        if (owner && owner->cfg.device != ctx->cfg.device)
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: the kept linearization %llu lives on device %d, this context on device %d", fn, (unsigned long long) keep_id,
+                            owner->cfg.device, ctx->cfg.device);
+        K = owner ? &owner->lin_kept : nullptr;
+        for (size_t w = 0; w < n; w++) {
+            if (src[w] < 0) {
+                if (!J0 || !e0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: src = -1 and no host J0 / e0", fn, w);
+                host_j += (size_t) r[w] * r[w], host_e += (size_t) r[w];
+                continue;
+            }
+            if ((size_t) src[w] >= K->r.size())
+                return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: src = %d, the kept linearization has %zu windows", fn, w, src[w], K->r.size());
+            if (K->r[(size_t) src[w]] != r[w])
+                return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: r = %d, kept window %d has r = %d", fn, w, r[w], src[w], K->r[(size_t) src[w]]);
         }
     }
     for (size_t w = 0; w < n; w++) // (after the argument checks: an invalid set is invalid whatever its size)
         if (r[w] > ICG_MARG_MAX_R)
-            return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_prior_set: window %zu: r = %d is above the limit %d", w, r[w], ICG_MARG_MAX_R);
+            return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: window %zu: r = %d is above the limit %d", fn, w, r[w], ICG_MARG_MAX_R);
     // layout: int64 j_off, jac_off (n+1 each) | int32 r, blk_off, e_off, x_off, blk_size, blk_index, blk_xoff, x_blk
     const size_t B = (size_t) block_off[n];
     size_t X       = 0;
     for (size_t b = 0; b < B; b++) X += (size_t) block_size[b];
-    if (X > (size_t) 1 << 30) return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_prior_set: %zu parameters in one set", X);
+    if (X > (size_t) 1 << 30) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %zu parameters in one set", fn, X);
     const size_t meta_bytes = 2 * (n + 1) * 8 + (n + 3 * (n + 1) + 3 * B + X) * 4;
     s.h_meta.assign((meta_bytes + 7) / 8, 0);
     int64_t *j_off = s.h_meta.data(), *jac_off = j_off + (n + 1);
@@ -204,8 +272,8 @@ extern "C" int icg_marg_prior_set(icg_ctx *ctx, int n_windows, const int32_t *r,
         if ((int64_t) r[w] * xs > max_jac) max_jac = (int64_t) r[w] * xs;
         if (r[w] > max_r) max_r = r[w];
     }
-    if (max_jac > (int64_t) 1 << 30) return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_prior_set: %lld Jacobian elements in one window", (long long) max_jac);
-    if (te > (int64_t) 1 << 30) return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_prior_set: %lld residuals in one set", (long long) te);
+    if (max_jac > (int64_t) 1 << 30) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %lld Jacobian elements in one window", fn, (long long) max_jac);
+    if (te > (int64_t) 1 << 30) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %lld residuals in one set", fn, (long long) te);
     s.h_r.assign(m_r, m_r + n), s.h_e_off.assign(m_eoff, m_eoff + n), s.h_j_off.assign(j_off, j_off + n); // (for host_part.hip)
     m_boff[n] = block_off[n], m_eoff[n] = (int32_t) te, m_xoff[n] = (int32_t) tx, j_off[n] = tj, jac_off[n] = tjac;
 
@@ -217,27 +285,63 @@ extern "C" int icg_marg_prior_set(icg_ctx *ctx, int n_windows, const int32_t *r,
     if ((rc = icg_grow(ctx, (void **) &s.d_x0, &s.x0_cap, b_x0, b_x0))) return rc;
     if ((rc = icg_grow(ctx, (void **) &s.d_meta, &s.meta_cap, s.h_meta.size() * 8, s.h_meta.size() * 8))) return rc;
     icg_call c(ctx);
-    if ((rc = c.reserve(sizeof(double) * (size_t) (tj + te + tx) + s.h_meta.size() * 8 + 8 * 256))) return rc;
-    const double *a_J    = c.in(J0, (size_t) tj);
-    const double *a_e0   = c.in(e0, (size_t) te);
+    if (!from_kept) host_j = (size_t) tj, host_e = (size_t) te;
+    if ((rc = c.reserve(sizeof(double) * (host_j + host_e + (size_t) tx) + s.h_meta.size() * 8 + (from_kept ? 2 * n * sizeof(double *) : 0) + 8 * 256))) return rc;
+    const double *a_J    = c.in(J0, host_j);
+    const double *a_e0   = c.in(e0, host_e);
     const double *a_x0   = c.in(x0, (size_t) tx);
     const int64_t *a_met = c.in(s.h_meta.data(), s.h_meta.size());
+    const double *const *a_src = nullptr;
+    if (from_kept) { // where window w's J0 (n entries) and e0 (n more) lie on the device
+        std::vector<const double *> from(2 * n);
+        size_t hj = 0, he = 0;
+        for (size_t w = 0; w < n; w++) {
+            if (src[w] < 0) {
+                from[w] = a_J + hj, from[n + w] = a_e0 + he;
+                hj += (size_t) r[w] * r[w], he += (size_t) r[w];
+            } else {
+                from[w] = K->d_buf + K->rr_off[(size_t) src[w]], from[n + w] = K->d_buf + K->total_rr + K->r_off[(size_t) src[w]];
+            }
+        }
+        a_src = c.in(from.data(), 2 * n);
+    }
     if ((rc = c.seal())) return rc;
     ICG_LAUNCH_GUARD(c);
     ICG_HIP(ctx, hipMemcpyAsync(s.d_meta, a_met, s.h_meta.size() * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    ICG_HIP(ctx, hipMemcpyAsync(s.d_e0, a_e0, sizeof(double) * (size_t) te, hipMemcpyDeviceToDevice, ctx->stream));
+    if (!from_kept) ICG_HIP(ctx, hipMemcpyAsync(s.d_e0, a_e0, sizeof(double) * (size_t) te, hipMemcpyDeviceToDevice, ctx->stream));
     if (tx > 0) ICG_HIP(ctx, hipMemcpyAsync(s.d_x0, a_x0, sizeof(double) * (size_t) tx, hipMemcpyDeviceToDevice, ctx->stream));
     {
-        icg_prof_scope ps(ctx, "marg_set");
-        const int nt = (max_r + MARG_TILE - 1) / MARG_TILE;
-        hipLaunchKernelGGL(k_marg_store, dim3(nt * nt, n_windows), dim3(MARG_THREADS), 0, ctx->stream, n_windows, reinterpret_cast<const int32_t *>(a_met + 2 * (n + 1)),
-                           a_met, a_J, s.d_J, s.d_J + tj);
+        const int nt         = (max_r + MARG_TILE - 1) / MARG_TILE;
+        const int32_t *a_r32 = reinterpret_cast<const int32_t *>(a_met + 2 * (n + 1));
+        if (from_kept) {
+            icg_prof_scope ps(ctx, "marg_set_from");
+            hipLaunchKernelGGL(k_marg_store_from, dim3(nt * nt, n_windows), dim3(MARG_THREADS), 0, ctx->stream, n_windows, a_r32, a_met, a_r32 + n + (n + 1),
+                               a_src, a_src + n, s.d_J, s.d_J + tj, s.d_e0);
+        } else {
+            icg_prof_scope ps(ctx, "marg_set");
+            hipLaunchKernelGGL(k_marg_store, dim3(nt * nt, n_windows), dim3(MARG_THREADS), 0, ctx->stream, n_windows, a_r32, a_met, a_J, s.d_J, s.d_J + tj);
+        }
     }
     ICG_HIP(ctx, hipGetLastError());
     if ((rc = c.finish())) return rc;
     s.n_blocks = (int) B, s.total_r = te, s.total_x = tx, s.total_j = tj, s.total_jac = tjac, s.max_jac = max_jac;
     s.n = n_windows;
     return ICG_OK;
+}
+
+} // namespace
+
+extern "C" int icg_marg_prior_set(icg_ctx *ctx, int n_windows, const int32_t *r, const int32_t *block_off, const int32_t *block_size,
+                                  const int32_t *block_index, const double *x0, const double *J0, const double *e0) {
+    return marg_set("icg_marg_prior_set", false, ctx, 0, n_windows, nullptr, r, block_off, block_size, block_index, x0, J0, e0);
+}
+
+// The same set with J0 / e0 taken where icg_marg_linearize_batch_keep left them (factors/marginalization_info.h:153-192 →
+// factors/marginalization_factor.h:47-101 without the detour through the host).
+extern "C" int icg_marg_prior_set_from_kept(icg_ctx *ctx, uint64_t keep_id, int n_windows, const int32_t *src, const int32_t *r, const int32_t *block_off,
+                                            const int32_t *block_size, const int32_t *block_index, const double *x0, const double *J0_host,
+                                            const double *e0_host) {
+    return marg_set("icg_marg_prior_set_from_kept", true, ctx, keep_id, n_windows, src, r, block_off, block_size, block_index, x0, J0_host, e0_host);
 }
 
 extern "C" int icg_marg_prior_evaluate(icg_ctx *ctx, const double *x, double *residuals, double *jacobians, double *gradient, double *sq_norm) {

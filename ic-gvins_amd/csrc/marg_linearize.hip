@@ -384,22 +384,25 @@ __global__ __launch_bounds__(LIN_THREADS) void k_marg_linearize(int n_items, con
     }
 }
 
-} // namespace
-
-extern "C" int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
-                                        double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status) {
+// Both entries.  keep: J0 / e0 are written into the context's kept buffer (icg_lin_kept) instead of the arena's outgoing slots, which a
+// device-to-device copy then feeds where the host asked for them — the kernels and their launches are the same either way.
+int lin_batch(const char *fn, bool keep, icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
+              double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status, uint64_t *keep_id) {
     if (!ctx) return ICG_ERR_INVALID;
-    if (n_windows <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_linearize_batch: n_windows = %d", n_windows);
-    if (n_windows > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_linearize_batch: %d windows in one call (at most 65535)", n_windows);
-    if (!P || !m || !H || !b || !J0 || !e0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_linearize_batch: NULL argument");
-    if (!(eps >= 0.0)) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_linearize_batch: eps = %g", eps);
+    icg_kept_drop(ctx); // whatever linearization the context kept is gone, also when this call fails
+    if (keep && !keep_id) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", fn);
+    if (keep) *keep_id = 0;
+    if (n_windows <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: n_windows = %d", fn, n_windows);
+    if (n_windows > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %d windows in one call (at most 65535)", fn, n_windows);
+    if (!P || !m || !H || !b || (!keep && (!J0 || !e0))) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", fn);
+    if (!(eps >= 0.0)) return icg_fail(ctx, ICG_ERR_INVALID, "%s: eps = %g", fn, eps);
     const size_t n = (size_t) n_windows;
     for (size_t w = 0; w < n; w++)
         if (P[w] <= 0 || m[w] < 0 || m[w] >= P[w])
-            return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_linearize_batch: window %zu: P = %d, m = %d (0 <= m < P)", w, P[w], m[w]);
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: P = %d, m = %d (0 <= m < P)", fn, w, P[w], m[w]);
     for (size_t w = 0; w < n; w++) // (after the argument checks: an invalid batch is invalid whatever its size)
         if (P[w] > ICG_MARG_LIN_MAX_P)
-            return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_marg_linearize_batch: window %zu: P = %d is above the limit %d", w, P[w], ICG_MARG_LIN_MAX_P);
+            return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: window %zu: P = %d is above the limit %d", fn, w, P[w], ICG_MARG_LIN_MAX_P);
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const size_t lds_limit = icg_lds_limit(ctx) - 256; // (- the kernel's static words)
     std::vector<lin_desc> desc(n);
@@ -427,6 +430,8 @@ extern "C" int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32
     }
     int rc = icg_grow(ctx, (void **) &ctx->d_lin_scratch, &ctx->lin_scratch_cap, ts * sizeof(double), ts * sizeof(double));
     if (rc) return rc;
+    icg_lin_kept &K = ctx->lin_kept;
+    if (keep && (rc = icg_grow(ctx, (void **) &K.d_buf, &K.cap, (trr + tr) * sizeof(double), (trr + tr) * sizeof(double)))) return rc;
     static icg_lds_grant granted;
     if ((rc = icg_allow_lds(ctx, reinterpret_cast<const void *>(k_marg_linearize<true>), lds_fast, lds_limit, granted))) return rc;
     icg_call c(ctx);
@@ -438,8 +443,9 @@ extern "C" int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32
     const lin_desc *d_desc  = c.in(desc.data(), n);
     const int32_t *d_items  = c.in(items.data(), n);
     if ((rc = c.seal())) return rc;
-    double *d_J0  = c.out(J0, trr);
-    double *d_e0  = c.out(e0, tr);
+    // (keep: the outgoing slots are still laid out — the arena offsets of the other outputs do not depend on the entry)
+    double *a_J0 = c.out(J0, trr), *a_e0 = c.out(e0, tr);
+    double *d_J0 = keep ? K.d_buf : a_J0, *d_e0 = keep ? K.d_buf + trr : a_e0;
     double *d_Hp  = Hp ? c.out(Hp, trr) : nullptr;
     double *d_bp  = bp ? c.out(bp, tr) : nullptr;
     double *d_ev  = evals ? c.out(evals, tr) : nullptr;
@@ -457,5 +463,29 @@ extern "C" int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32
                            d_desc, d_H, d_b, eps, d_Hp, d_bp, d_J0, d_e0, d_ev, d_min, d_st, ctx->d_lin_scratch);
     }
     ICG_HIP(ctx, hipGetLastError());
-    return c.finish();
+    if (keep && J0) ICG_HIP(ctx, hipMemcpyAsync(a_J0, d_J0, trr * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    if (keep && e0) ICG_HIP(ctx, hipMemcpyAsync(a_e0, d_e0, tr * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = c.finish())) return rc;
+    if (keep) {
+        K.total_rr = (int64_t) trr, K.total_r = (int64_t) tr;
+        K.r.resize(n), K.rr_off.resize(n), K.r_off.resize(n);
+        for (size_t w = 0; w < n; w++) K.r[w] = P[w] - m[w], K.rr_off[w] = desc[w].rr_off, K.r_off[w] = desc[w].r_off;
+        *keep_id = icg_kept_register(ctx);
+    }
+    return ICG_OK;
+}
+
+} // namespace
+
+extern "C" int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
+                                        double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status) {
+    return lin_batch("icg_marg_linearize_batch", false, ctx, n_windows, P, m, H, b, eps, Hp, bp, J0, e0, evals, min_ev_m, status, nullptr);
+}
+
+// The same call with J0 / e0 of every window also left on the device for icg_marg_prior_set_from_kept (factors/marginalization_info.h:153-192
+// feeding factors/marginalization_factor.h:47-101 without the detour through the host).
+extern "C" int icg_marg_linearize_batch_keep(icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
+                                             double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status,
+                                             uint64_t *keep_id) {
+    return lin_batch("icg_marg_linearize_batch_keep", true, ctx, n_windows, P, m, H, b, eps, Hp, bp, J0, e0, evals, min_ev_m, status, keep_id);
 }

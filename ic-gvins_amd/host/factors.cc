@@ -874,6 +874,7 @@ void MarginalizationInfo::schurElimination() { // :170-192
 
 void MarginalizationInfo::linearization() { // :153-167
     linearizePrior(remained_size_, Hp_, bp_, EPS, linearized_jacobians_, linearized_residuals_, nullptr, nullptr);
+    keep_id_ = 0, keep_slot_ = -1; // (a linearization made here lies on the host only)
 }
 
 // ---- MarginalizationFactor (marginalization_factor.h:31-105) ----------------------------------------------------------
@@ -895,6 +896,7 @@ MarginalizationFactor::MarginalizationFactor(std::shared_ptr<MarginalizationInfo
     view_.x0       = x0_.data();
     view_.J0       = marg_info_->linearizedJacobians().data();
     view_.e0       = marg_info_->linearizedResiduals().data();
+    view_.keep_id = marg_info_->keptId(), view_.keep_slot = marg_info_->keptSlot();
 }
 
 bool MarginalizationFactor::Evaluate(const double *const *parameters, double *residuals, double **jacobians) const {

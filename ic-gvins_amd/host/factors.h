@@ -174,6 +174,12 @@ public:
     // exposed for tests: the Schur complement before linearization
     const vector<double> &Hp() const { return Hp_; }
     const vector<double> &bp() const { return bp_; }
+    // Where this linearization also lies on the device: window `slot` of the kept linearization `id` (icg_marg_linearize_batch_keep), set by
+    // MarginalizationBatch::setKeepLinearized for a window whose prior came from the device call; id 0 = nowhere.  A tag may outlive the
+    // kept buffer: MarginalizationPriorSet::set then ships the host arrays, which are always complete.
+    void setKeptLinearization(uint64_t id, int slot) { keep_id_ = id, keep_slot_ = slot; }
+    uint64_t keptId() const { return keep_id_; }
+    int keptSlot() const { return keep_slot_; }
 
 private:
     bool updateParameterBlocksIndex();
@@ -228,6 +234,8 @@ private:
     vector<double> linearized_jacobians_, linearized_residuals_;
     bool isvalid_{true};
     DeviceFactorSet *batch_{nullptr};
+    uint64_t keep_id_{0};
+    int keep_slot_{-1};
 };
 
 // M4 on plain arrays: what MarginalizationFactor::Evaluate reads of a MarginalizationInfo.  index[b] is block b's first local column
@@ -237,6 +245,9 @@ struct MargPriorView {
     const int *size{nullptr}, *index{nullptr};
     const double *const *x0{nullptr};
     const double *J0{nullptr}, *e0{nullptr}; // r x r row-major, r
+    // the same J0 / e0 on the device: window keep_slot of the kept linearization keep_id (MarginalizationInfo::keptId); 0 / -1: host only
+    uint64_t keep_id{0};
+    int keep_slot{-1};
 };
 
 // A cost function that IS a linearized marginalization prior says so: its Evaluate is evaluateMargPrior over the view, block b of the view
@@ -291,6 +302,12 @@ public:
     void pack(size_t w, const double *const *parameters);
     bool evaluateResident(double *sq_norm, std::string *err = nullptr);
     int windows() const { return (int) r_.size(); }
+    // The hand-off: when every tagged view of a set() names the same live kept linearization (MargPriorView::keep_id), the tagged windows
+    // take J0 / e0 where the linearize call left them on the device (icg_marg_prior_set_from_kept, weakly referenced) and only the untagged
+    // windows' arrays are packed and shipped.  Without the entry, with differing ids or with a linearization that is gone, set() ships
+    // every window as before.  handedOff(): the windows of the last set() that took the hand-off.
+    static bool handOffAvailable();
+    int handedOff() const { return handed_off_; }
     size_t residualSize() const { return residual_size_; }
     size_t jacobianSize() const { return jacobian_size_; }
 
@@ -300,6 +317,7 @@ private:
     vector<size_t> x_off_; // first parameter of window w in x_
     vector<double> x_; // the evaluation point, packed like x0
     size_t residual_size_{0}, jacobian_size_{0};
+    int handed_off_{0};
 };
 
 // M3 on plain arrays (marginalization_info.h:153-192), what MarginalizationInfo::schurElimination / linearization run.  schurReduce: the m

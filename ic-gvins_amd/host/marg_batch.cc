@@ -14,7 +14,15 @@ namespace icg {
 MarginalizationBatch::MarginalizationBatch(int device, double huber_delta, int host_threads)
     : factors_(device, host_threads, "MarginalizationBatch"), device_(device), huber_(huber_delta) {}
 
+bool MarginalizationBatch::keepLinearizedAvailable() { return MarginalizationLinearizer::keepAvailable(); }
+
+void MarginalizationBatch::releaseKept() {
+    if (kept_id_ != 0) MarginalizationLinearizer::releaseKept(factors_.ctx());
+    kept_id_ = 0;
+}
+
 MarginalizationBatch::~MarginalizationBatch() {
+    releaseKept();
     clear();
     if (dense_ctx_) icg_ctx_destroy(dense_ctx_);
 }
@@ -135,6 +143,8 @@ struct MarginalizationBatch::DeviceM3 {
     std::vector<char> on_device; // per window: its prior is in the arrays below
     std::vector<double> Hp, bp, J0, e0;
     std::vector<size_t> r_off, rr_off;
+    std::vector<int> slot; // per window: its index in the device call
+    uint64_t keep_id{0};   // setKeepLinearized: the call's kept linearization
 };
 
 // device M3 (setDeviceLinearization): every window whose eliminated part was added and that passes the first guard, one call
@@ -149,6 +159,7 @@ bool MarginalizationBatch::linearizeOnDevice(const std::vector<State> &st, const
         if (!added[w] || !(min_hll[w] > GUARD)) continue;
         const MarginalizationInfo::StructuredPlan &plan = st[w].plan;
         dev.on_device[w] = 1, dev.r_off[w] = tr, dev.rr_off[w] = trr;
+        dev.slot[w] = (int) who.size();
         who.push_back(w), h_off.push_back(th);
         dP.push_back(plan.P), dm.push_back(plan.m);
         th += (size_t) plan.P * plan.P, tb += (size_t) plan.P, tr += (size_t) plan.r, trr += (size_t) plan.r * plan.r;
@@ -165,9 +176,14 @@ bool MarginalizationBatch::linearizeOnDevice(const std::vector<State> &st, const
     });
     dev.Hp.resize(trr), dev.bp.resize(tr), dev.J0.resize(trr), dev.e0.resize(tr);
     MarginalizationLinearizer lin(true, factors_.ctx());
-    if (!lin.linearize((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev.Hp.data(), dev.bp.data(), dev.J0.data(), dev.e0.data(),
-                       nullptr, dev_min.data(), dev_status.data(), what))
+    if (keep_linearized_) {
+        dev.keep_id = lin.linearizeKeep((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev.Hp.data(), dev.bp.data(), dev.J0.data(),
+                                        dev.e0.data(), nullptr, dev_min.data(), dev_status.data(), what);
+        if (dev.keep_id == 0) return false;
+    } else if (!lin.linearize((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev.Hp.data(), dev.bp.data(), dev.J0.data(),
+                              dev.e0.data(), nullptr, dev_min.data(), dev_status.data(), what)) {
         return false;
+    }
     for (size_t k = 0; k < who.size(); k++) // second guard of finishStructured, and a solver that did not converge
         if (!(dev_min[k] > GUARD) || (dev_status[k] & 1)) dev.on_device[who[k]] = 0;
     return true;
@@ -180,7 +196,16 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     phase_ms_[0] = phase_ms_[1] = phase_ms_[2] = phase_ms_[3] = 0;
     error_.clear();
     window_error_.clear();
+    if (keep_linearized_ && !device_linearization_) {
+        error_ = "setKeepLinearized(true) needs setDeviceLinearization(true): what is kept is the device call's linearization";
+        return false;
+    }
+    if (keep_linearized_ && !keepLinearizedAvailable()) {
+        error_ = "icg_marg_linearize_batch_keep is not in this build";
+        return false;
+    }
     if (NW == 0) return true;
+    releaseKept(); // (the last marginalize()'s; this one keeps its own below)
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms  = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
         return std::chrono::duration<double, std::milli>(b - a).count();
@@ -276,13 +301,14 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
         min_hll[w] = mn;
         added[w]   = 1;
     };
-    DeviceM3 dev{std::vector<char>(NW, 0), {}, {}, {}, {}, std::vector<size_t>(NW, 0), std::vector<size_t>(NW, 0)};
+    DeviceM3 dev{std::vector<char>(NW, 0), {}, {}, {}, {}, std::vector<size_t>(NW, 0), std::vector<size_t>(NW, 0), std::vector<int>(NW, -1), 0};
     if (device_linearization_) {
         factors_.forEachWindow(NW, [&](size_t w) {
             if (st[w].alive && st[w].planned) addEliminated(w);
         });
         std::string what;
         if (!linearizeOnDevice(st, added, min_hll, dev, &what)) return fail(what);
+        kept_id_ = dev.keep_id;
     }
     factors_.forEachWindow(NW, [&](size_t w) {
         if (!st[w].alive) return;
@@ -294,6 +320,7 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
             I.bp_.assign(dev.bp.begin() + (long) at, dev.bp.begin() + (long) (at + r));
             I.linearized_jacobians_.assign(dev.J0.begin() + (long) at2, dev.J0.begin() + (long) (at2 + r * r));
             I.linearized_residuals_.assign(dev.e0.begin() + (long) at, dev.e0.begin() + (long) (at + r));
+            I.setKeptLinearization(dev.keep_id, dev.keep_id ? dev.slot[w] : -1); // (what the device call kept is this window's prior)
             structured[w] = good[w] = 1;
             return;
         }

@@ -60,6 +60,20 @@ public:
     // agree with the default mode to rounding, not bit for bit.  marginalize() fails (error()) when the entry point is not in the build.
     void setDeviceLinearization(bool on) { device_linearization_ = on; }
     bool deviceLinearization() const { return device_linearization_; }
+    // With the device linearization (default off; marginalize() fails with a message without setDeviceLinearization(true), or when
+    // icg_marg_linearize_batch_keep is not in the build): the device call also KEEPS J0 / e0 of its windows on the device
+    // (MarginalizationLinearizer::linearizeKeep), and every window whose prior is taken from the device arrays — it passed both guards —
+    // is tagged with the kept linearization's id and its index in that call (MarginalizationInfo::keptId / keptSlot).  A
+    // MarginalizationFactor built from a tagged info carries the tag in its view, and MarginalizationPriorSet::set /
+    // WindowSolverBatch::setDevicePrior then take J0 / e0 where they lie instead of packing and uploading them.  Windows on the host or
+    // dense path stay untagged and are shipped.  The results are those of the device linearization, bit for bit.
+    // Resident cost: sum r^2 + sum r doubles in the batch's context (41 MB for 256 C2-estimator windows, r = 142) from marginalize() until
+    // the next marginalize() or the destructor releases it.  clear() does NOT release it — the caller clears before it solves.
+    void setKeepLinearized(bool on) { keep_linearized_ = on; }
+    bool keepLinearized() const { return keep_linearized_; }
+    static bool keepLinearizedAvailable();
+    uint64_t keptId() const { return kept_id_; } // of the last marginalize(); 0: nothing is kept
+    void releaseKept();                          // drops the kept linearization now (tags that name it fall back to shipping)
 
     // diagnostics of the last marginalize(): windows that took the landmark-eliminated device path / the dense path; wall time of the
     // four phases above [ms]
@@ -102,7 +116,8 @@ private:
     double huber_{1.0};
     std::vector<std::unique_ptr<Slice>> windows_;
     bool laid_out_{false};
-    bool device_linearization_{false};
+    bool device_linearization_{false}, keep_linearized_{false};
+    uint64_t kept_id_{0};
     std::vector<std::shared_ptr<ResidualBlockInfo>> retired_; // factor records of marginalized windows, freed by clear() / the destructor
     int n_structured_{0}, n_dense_{0};
     double phase_ms_[4]{0, 0, 0, 0};

@@ -8,10 +8,34 @@
 // A build of this layer on another implementation of the C ABI may not have the entry point: the reference stays weak (null when absent)
 // and linearize() reports it; the product library links libicgvins_hip.so, which defines it.
 #pragma weak icg_marg_linearize_batch
+#pragma weak icg_marg_linearize_batch_keep
+#pragma weak icg_marg_linearized_release
 
 namespace icg {
 
 bool MarginalizationLinearizer::available() { return &icg_marg_linearize_batch != nullptr; }
+
+bool MarginalizationLinearizer::keepAvailable() { return &icg_marg_linearize_batch_keep != nullptr && &icg_marg_linearized_release != nullptr; }
+
+void MarginalizationLinearizer::releaseKept(icg_ctx *ctx) {
+    if (ctx && keepAvailable()) (void) icg_marg_linearized_release(ctx);
+}
+
+uint64_t MarginalizationLinearizer::linearizeKeep(int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
+                                                  double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status,
+                                                  std::string *err) {
+    auto fail = [&](const std::string &what) {
+        if (err) *err = what;
+        return (uint64_t) 0;
+    };
+    if (!device_) return fail("MarginalizationLinearizer::linearizeKeep: device mode only");
+    if (!keepAvailable()) return fail("icg_marg_linearize_batch_keep is not in this build");
+    if (!ctx_) return fail("MarginalizationLinearizer: no context");
+    uint64_t id = 0;
+    if (icg_marg_linearize_batch_keep(ctx_, n_windows, P, m, H, b, eps, Hp, bp, J0, e0, evals, min_ev_m, status, &id) != ICG_OK)
+        return fail(icg_last_error(ctx_));
+    return id;
+}
 
 MarginalizationLinearizer::MarginalizationLinearizer(bool device, icg_ctx *ctx, int host_threads) : device_(device), ctx_(ctx) {
     host_threads_ = host_threads > 0 ? host_threads : (int) std::min(16u, std::max(1u, std::thread::hardware_concurrency()));

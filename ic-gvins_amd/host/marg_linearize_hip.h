@@ -23,6 +23,14 @@ public:
     // cap) is reported by the device only.  false with *err set on failure; nothing is written then.
     bool linearize(int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps, double *Hp, double *bp,
                    double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status, std::string *err = nullptr);
+    // Device mode only: the same call through icg_marg_linearize_batch_keep, which also leaves J0 / e0 of every window on the device for
+    // MarginalizationPriorSet::set (icg_marg_prior_set_from_kept).  Returns the id of the kept linearization, 0 with *err set on failure.
+    // The kept buffer (sum r^2 + sum r doubles) lives until the context's next linearize call of either kind, releaseKept(ctx) or the
+    // context's destruction.  The entries are referenced weakly like the one above: keepAvailable() is false on a C ABI without them.
+    static bool keepAvailable();
+    uint64_t linearizeKeep(int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps, double *Hp, double *bp,
+                           double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status, std::string *err = nullptr);
+    static void releaseKept(icg_ctx *ctx); // icg_marg_linearized_release; nothing without the entry or a context
 
 private:
     bool device_;

@@ -79,6 +79,9 @@ public:
     void setDevicePrior(bool on) { device_prior_ = on; }
     bool devicePrior() const { return device_prior_; }
     static bool devicePriorAvailable();
+    // windows of the last solve() whose resident prior took J0 / e0 from a kept device linearization instead of the host arrays
+    // (MarginalizationPriorSet::handedOff: priors tagged by MarginalizationBatch::setKeepLinearized); needs no switch of its own
+    int priorsHandedOff() const { return prior_set_.handedOff(); }
     bool solve(const Options &options, std::vector<Summary> *summaries);
     // removeReprojectionFactorsByChi2 (ic_gvins.cc:1269-1297) for every window; returns the number removed per window
     std::vector<int> removeReprojectionFactorsByChi2(double chi2);

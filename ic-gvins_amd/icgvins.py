@@ -25,6 +25,7 @@ EXPORTS = [
     "icg_marg_prior_set", "icg_marg_prior_evaluate", "icg_marg_linearize_batch",
     "icg_chol_solve_batch", "icg_reproj_schur_windows_resident", "icg_reproj_solve_windows", "icg_reproj_host_parts_build",
     "icg_marg_prior_evaluate_resident", "icg_reproj_host_parts_build_prior",
+    "icg_marg_linearize_batch_keep", "icg_marg_linearized_release", "icg_marg_prior_set_from_kept",
 ]
 
 
@@ -651,6 +652,45 @@ class Context:
                                                    _p(out["J0"]), _p(out["e0"]), _p(out["evals"]), _p(out["min_ev_m"]), _p(out["status"])),
                  "icg_marg_linearize_batch")
         return out
+
+    def marg_linearize_batch_keep(self, P, m, H, b, eps=1e-8, want_J0=True, want_e0=True, want_Hp=True, want_bp=True, want_evals=True,
+                                  want_min_ev=True, want_status=True):
+        """icg_marg_linearize_batch_keep: marg_linearize_batch with J0 / e0 also left on the device -> (dict as there, keep id); J0 / e0
+        are None when not asked for (not transferred)"""
+        P, m = _i32(P).reshape(-1), _i32(m).reshape(-1)
+        H, b = _f64(H).reshape(-1), _f64(b).reshape(-1)
+        n = len(P)
+        if len(m) != n or H.shape[0] != int((P.astype(np.int64) ** 2).sum()) or b.shape[0] != int(P.sum()):
+            raise IcgError("marg_linearize_batch_keep: P, m, H, b do not describe the same windows")
+        r = P.astype(np.int64) - m
+        nr, nrr = int(r.clip(0).sum()), int((r.clip(0) ** 2).sum())
+        out = dict(J0=np.zeros(nrr) if want_J0 else None, e0=np.zeros(nr) if want_e0 else None, Hp=np.zeros(nrr) if want_Hp else None,
+                   bp=np.zeros(nr) if want_bp else None, evals=np.zeros(nr) if want_evals else None,
+                   min_ev_m=np.zeros(n) if want_min_ev else None, status=np.zeros(n, np.int32) if want_status else None)
+        keep = C.c_uint64(0)
+        self._ck(self.lib.icg_marg_linearize_batch_keep(self.h, n, _p(P), _p(m), _p(H), _p(b), C.c_double(eps), _p(out["Hp"]), _p(out["bp"]),
+                                                        _p(out["J0"]), _p(out["e0"]), _p(out["evals"]), _p(out["min_ev_m"]), _p(out["status"]),
+                                                        C.byref(keep)), "icg_marg_linearize_batch_keep")
+        return out, int(keep.value)
+
+    def marg_linearized_release(self):
+        """icg_marg_linearized_release: the linearization this context keeps is dropped"""
+        self._ck(self.lib.icg_marg_linearized_release(self.h), "icg_marg_linearized_release")
+
+    def marg_prior_set_from_kept(self, keep_id, src, r, block_off, block_size, block_index, x0, J0_host=None, e0_host=None):
+        """icg_marg_prior_set_from_kept: marg_prior_set with window w's J0 / e0 taken from window src[w] of the kept linearization
+        keep_id (any context of this device), or, for src[w] == -1, from J0_host / e0_host (those windows only, in set order)"""
+        src, r = _i32(src).reshape(-1), _i32(r).reshape(-1)
+        block_off, block_size, block_index = _i32(block_off).reshape(-1), _i32(block_size).reshape(-1), _i32(block_index).reshape(-1)
+        x0 = _f64(x0).reshape(-1)
+        J0_host = None if J0_host is None else _f64(J0_host).reshape(-1)
+        e0_host = None if e0_host is None else _f64(e0_host).reshape(-1)
+        self._marg = None
+        self._ck(self.lib.icg_marg_prior_set_from_kept(self.h, C.c_uint64(keep_id), len(r), _p(src), _p(r), _p(block_off), _p(block_size),
+                                                       _p(block_index), _p(x0), _p(J0_host), _p(e0_host)), "icg_marg_prior_set_from_kept")
+        xs = np.array([int(block_size[block_off[w]:block_off[w + 1]].sum()) for w in range(len(r))], np.int64)
+        self._marg = (len(r), int(r.sum()), int(xs.sum()), int((r.astype(np.int64) * xs).sum()))
+        self._marg_r = r.copy()
 
     # ---- the reduced camera solve
     def chol_solve_batch(self, n, A, b, want_L=True, want_status=True):

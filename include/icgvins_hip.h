@@ -407,6 +407,35 @@ int icg_marg_prior_evaluate_resident(icg_ctx *ctx, const double *x, double *sq_n
 int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
                              double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status);
 
+/* ---- M3 -> M4 on the device: the linearization (factors/marginalization_info.h:153-192) stays where the prior evaluation
+ * (factors/marginalization_factor.h:47-101) reads it.
+ * icg_marg_linearize_batch_keep is icg_marg_linearize_batch — the same kernels, launches, argument checks and the same bits in every
+ * output — and also leaves J0 / e0 of every window in a buffer the context owns (sum r^2 + sum r doubles: 41 MB for 256 windows of
+ * r = 142).  J0 and e0 may be NULL here (not transferred).  *keep_id receives the id of the kept linearization: non-zero, unique in the
+ * process and never reused; 0 after a failed call.  The kept linearization lives until the first of: the next icg_marg_linearize_batch or
+ * icg_marg_linearize_batch_keep call on the context (whether that call succeeds or not), icg_marg_linearized_release, icg_ctx_destroy.
+ * ICG_ERR_INVALID also for a NULL keep_id. */
+int icg_marg_linearize_batch_keep(icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
+                                  double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status,
+                                  uint64_t *keep_id);
+/* Drops the linearization the context keeps, if any (its id is no longer known; the memory is reused by the next kept one). */
+int icg_marg_linearized_release(icg_ctx *ctx);
+/* icg_marg_prior_set (factors/marginalization_factor.h:47-101) with J0 / e0 taken from a kept linearization
+ * (factors/marginalization_info.h:153-192): the same metadata, the same resident J / J^T / e0 / x0, the same replacement and invalidation
+ * rules, the same bits in every later evaluation.  Window w takes J0 / e0 from window src[w] of linearization keep_id when src[w] >= 0 (a
+ * kept window may serve several windows of the set, in any order) and from J0_host / e0_host when src[w] == -1: these hold only the -1
+ * windows, concatenated in set order, and may be NULL when there are none (keep_id is not looked at when every window is -1).
+ * The kept linearization may belong to ctx itself or to another context on the same device; the CALLER guarantees that the owning context
+ * is inside no call (and is not destroyed) while this one runs.  A live id is never followed to freed memory: an id whose linearization is
+ * gone is refused.
+ * ICG_ERR_INVALID (message names the window where there is one): everything icg_marg_prior_set reports; NULL src; src[w] outside
+ * [-1, kept windows); keep_id unknown or expired ("the kept linearization ... is gone"); r[w] != the kept window's r; a -1 window with NULL
+ * host arrays; the owning context on another device.  ICG_ERR_CAPACITY as there.  After a failed call nothing was launched and no set is
+ * resident. */
+int icg_marg_prior_set_from_kept(icg_ctx *ctx, uint64_t keep_id, int n_windows, const int32_t *src, const int32_t *r, const int32_t *block_off,
+                                 const int32_t *block_size, const int32_t *block_index, const double *x0, const double *J0_host,
+                                 const double *e0_host);
+
 /* ---- the reduced camera solve: solver_detail::choleskySolve of the host layer (host/dense_kernels.cc) for many systems at once, one wave per
  * system (csrc/chol.hip).  The systems are concatenated: system k is A (n[k] x n[k], row-major, only the lower triangle is read) and b (n[k]).
  * The arithmetic is the host's, operation for operation: column tiles of two, every inner product in dot8 order (eight interleaved partial
