@@ -1,6 +1,7 @@
 // M4: MarginalizationFactor::Evaluate (factors/marginalization_factor.h:47-101) for many priors at once, with the priors RESIDENT on the
 // device.  A prior (x0, J0, e0 and its block layout) is constant between two marginalizations while every LM iteration evaluates it at a
-// new x: icg_marg_prior_set uploads the priors of many windows once, icg_marg_prior_evaluate ships only x in and e (optionally the
+// new x: icg_marg_prior_set uploads the priors of many windows once (icg_marg_prior_set_from_kept takes them where a kept linearization
+// left them; both through one store kernel that reads each window at a pointer of its own), icg_marg_prior_evaluate ships only x in and e (optionally the
 // Jacobian blocks, J0^T e and |e|^2) out; icg_marg_prior_evaluate_resident keeps e on the device for the host-part kernel (host_part.hip) and
 // ships |e|^2 only.  FP64, no contraction; every sum is formed in the host's order (host/factors.cc
 // evaluateMargPrior, oracle/orc_marg.cc), so the residuals and Jacobian blocks are the same IEEE values bit for bit, alone or in a batch.
@@ -28,39 +29,10 @@ struct marg_dev {
     const double *e0, *x0;
 };
 
-// set time: the uploaded row-major J0 of every window into its two resident forms
-__global__ __launch_bounds__(MARG_THREADS) void k_marg_store(int n_windows, const int32_t *__restrict__ r_of, const int64_t *__restrict__ j_off,
-                                                             const double *__restrict__ src, double *__restrict__ J, double *__restrict__ JT) {
-    __shared__ double tile[MARG_TILE][MARG_TILE + 1];
-    const int w = blockIdx.y;
-    if (w >= n_windows) return;
-    const int r = r_of[w], nt = (r + MARG_TILE - 1) / MARG_TILE;
-    const double *s = src + j_off[w];
-    double *d = J + j_off[w], *dt = JT + j_off[w];
-    const int tx = threadIdx.x & (MARG_TILE - 1), ty = threadIdx.x / MARG_TILE; // 32 x 8
-    for (int t = blockIdx.x; t < nt * nt; t += gridDim.x) {                      // (uniform per workgroup)
-        const int ti = t / nt, tj = t - ti * nt;
-        for (int y = ty; y < MARG_TILE; y += MARG_THREADS / MARG_TILE) {
-            const int i = ti * MARG_TILE + y, k = tj * MARG_TILE + tx;
-            if (i < r && k < r) {
-                const double v = s[(size_t) i * r + k];
-                d[(size_t) i * r + k] = v;
-                tile[y][tx]           = v;
-            }
-        }
-        __syncthreads();
-        for (int y = ty; y < MARG_TILE; y += MARG_THREADS / MARG_TILE) {
-            const int k = tj * MARG_TILE + y, i = ti * MARG_TILE + tx;
-            if (i < r && k < r) dt[(size_t) k * r + i] = tile[tx][y];
-        }
-        __syncthreads();
-    }
-}
-
-// The same store for a set whose windows come from different places (icg_marg_prior_set_from_kept): window w's row-major J0 is read at
-// src_J[w] and its e0 at src_e[w] — a window of a kept linearization (icg_lin_kept, this context's or another's on the device) or of the part
-// the host shipped.  Tiles as above: the source is read and J written along rows, JT written along rows from the padded tile; the workgroups
-// of tile 0 also gather the window's e0.
+// Set time: the row-major J0 of every window into its two resident forms, and its e0.  The windows of a set may come from different places:
+// window w's J0 is read at src_J[w] and its e0 at src_e[w] — a window of a kept linearization (icg_lin_kept, this context's or another's on
+// the device; icg_marg_prior_set_from_kept) or of the part the host shipped (every window of icg_marg_prior_set).  32 x 32 tiles: the source
+// is read and J written along rows, JT written along rows from the padded tile; the workgroups of tile 0 also gather the window's e0.
 __global__ __launch_bounds__(MARG_THREADS) void k_marg_store_from(int n_windows, const int32_t *__restrict__ r_of, const int64_t *__restrict__ j_off,
                                                                   const int32_t *__restrict__ e_off, const double *const *__restrict__ src_J,
                                                                   const double *const *__restrict__ src_e, double *__restrict__ J, double *__restrict__ JT,
@@ -191,8 +163,8 @@ marg_dev marg_view(const icg_marg_set &s) {
     return m;
 }
 
-// Both set entries.  from_kept: window w takes J0 / e0 from window src[w] of the kept linearization keep_id (src[w] >= 0) or from the next
-// window of J0 / e0 (src[w] == -1), which then hold only those windows; otherwise J0 / e0 hold every window and src is not read.
+// Both set entries.  Window w takes J0 / e0 from window src[w] of the kept linearization keep_id (src[w] >= 0) or from the next window of
+// J0 / e0 (src[w] == -1), which hold only those windows.  src == NULL (icg_marg_prior_set): every window is a -1; from_kept only picks the entry's argument check and profiler scope.
 int marg_set(const char *fn, bool from_kept, icg_ctx *ctx, uint64_t keep_id, int n_windows, const int32_t *src, const int32_t *r, const int32_t *block_off,
              const int32_t *block_size, const int32_t *block_index, const double *x0, const double *J0, const double *e0) {
     if (!ctx) return ICG_ERR_INVALID;
@@ -215,12 +187,13 @@ int marg_set(const char *fn, bool from_kept, icg_ctx *ctx, uint64_t keep_id, int
         }
     }
     const icg_lin_kept *K = nullptr;
-    size_t host_j = 0, host_e = 0; // elements of J0 / e0 (from_kept: of the windows the host ships)
-    if (from_kept) {
+    const auto src_of = [&](size_t w) { return src ? src[w] : -1; };
+    size_t host_j = 0, host_e = 0; // elements of J0 / e0: the windows the host ships
+    {
         bool any_kept = false;
         for (size_t w = 0; w < n; w++) {
-            if (src[w] < -1) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: src = %d", fn, w, src[w]);
-            any_kept |= src[w] >= 0;
+            if (src_of(w) < -1) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: src = %d", fn, w, src[w]);
+            any_kept |= src_of(w) >= 0;
         }
         // (the id is looked at whenever a window names it; a set of shipped windows alone needs none)
         const icg_ctx *owner = any_kept ? icg_kept_lookup(keep_id) : nullptr;
@@ -232,7 +205,7 @@ int marg_set(const char *fn, bool from_kept, icg_ctx *ctx, uint64_t keep_id, int
                             owner->cfg.device, ctx->cfg.device);
         K = owner ? &owner->lin_kept : nullptr;
         for (size_t w = 0; w < n; w++) {
-            if (src[w] < 0) {
+            if (src_of(w) < 0) {
                 if (!J0 || !e0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: src = -1 and no host J0 / e0", fn, w);
                 host_j += (size_t) r[w] * r[w], host_e += (size_t) r[w];
                 continue;
@@ -285,18 +258,17 @@ int marg_set(const char *fn, bool from_kept, icg_ctx *ctx, uint64_t keep_id, int
     if ((rc = icg_grow(ctx, (void **) &s.d_x0, &s.x0_cap, b_x0, b_x0))) return rc;
     if ((rc = icg_grow(ctx, (void **) &s.d_meta, &s.meta_cap, s.h_meta.size() * 8, s.h_meta.size() * 8))) return rc;
     icg_call c(ctx);
-    if (!from_kept) host_j = (size_t) tj, host_e = (size_t) te;
-    if ((rc = c.reserve(sizeof(double) * (host_j + host_e + (size_t) tx) + s.h_meta.size() * 8 + (from_kept ? 2 * n * sizeof(double *) : 0) + 8 * 256))) return rc;
+    if ((rc = c.reserve(sizeof(double) * (host_j + host_e + (size_t) tx) + s.h_meta.size() * 8 + 2 * n * sizeof(double *) + 8 * 256))) return rc;
     const double *a_J    = c.in(J0, host_j);
     const double *a_e0   = c.in(e0, host_e);
     const double *a_x0   = c.in(x0, (size_t) tx);
     const int64_t *a_met = c.in(s.h_meta.data(), s.h_meta.size());
-    const double *const *a_src = nullptr;
-    if (from_kept) { // where window w's J0 (n entries) and e0 (n more) lie on the device
+    const double *const *a_src;
+    { // where window w's J0 (n entries) and e0 (n more) lie on the device
         std::vector<const double *> from(2 * n);
         size_t hj = 0, he = 0;
         for (size_t w = 0; w < n; w++) {
-            if (src[w] < 0) {
+            if (src_of(w) < 0) {
                 from[w] = a_J + hj, from[n + w] = a_e0 + he;
                 hj += (size_t) r[w] * r[w], he += (size_t) r[w];
             } else {
@@ -308,19 +280,13 @@ int marg_set(const char *fn, bool from_kept, icg_ctx *ctx, uint64_t keep_id, int
     if ((rc = c.seal())) return rc;
     ICG_LAUNCH_GUARD(c);
     ICG_HIP(ctx, hipMemcpyAsync(s.d_meta, a_met, s.h_meta.size() * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    if (!from_kept) ICG_HIP(ctx, hipMemcpyAsync(s.d_e0, a_e0, sizeof(double) * (size_t) te, hipMemcpyDeviceToDevice, ctx->stream));
     if (tx > 0) ICG_HIP(ctx, hipMemcpyAsync(s.d_x0, a_x0, sizeof(double) * (size_t) tx, hipMemcpyDeviceToDevice, ctx->stream));
     {
         const int nt         = (max_r + MARG_TILE - 1) / MARG_TILE;
         const int32_t *a_r32 = reinterpret_cast<const int32_t *>(a_met + 2 * (n + 1));
-        if (from_kept) {
-            icg_prof_scope ps(ctx, "marg_set_from");
-            hipLaunchKernelGGL(k_marg_store_from, dim3(nt * nt, n_windows), dim3(MARG_THREADS), 0, ctx->stream, n_windows, a_r32, a_met, a_r32 + n + (n + 1),
-                               a_src, a_src + n, s.d_J, s.d_J + tj, s.d_e0);
-        } else {
-            icg_prof_scope ps(ctx, "marg_set");
-            hipLaunchKernelGGL(k_marg_store, dim3(nt * nt, n_windows), dim3(MARG_THREADS), 0, ctx->stream, n_windows, a_r32, a_met, a_J, s.d_J, s.d_J + tj);
-        }
+        icg_prof_scope ps(ctx, from_kept ? "marg_set_from" : "marg_set");
+        hipLaunchKernelGGL(k_marg_store_from, dim3(nt * nt, n_windows), dim3(MARG_THREADS), 0, ctx->stream, n_windows, a_r32, a_met, a_r32 + n + (n + 1), a_src,
+                           a_src + n, s.d_J, s.d_J + tj, s.d_e0);
     }
     ICG_HIP(ctx, hipGetLastError());
     if ((rc = c.finish())) return rc;

@@ -14,7 +14,7 @@
 #include "solver_batch_hip.h"
 #include "culling_hip.h"
 #include "window_visual.h"
-#include "capi_util.h"
+#include "capi_windows.h"
 
 using namespace icg;
 
@@ -427,14 +427,12 @@ int icgh_batch_refine_windows(icgh_batch *b, const double *pose_b_c12, double td
             if (lockstep) {
                 slot[(size_t) s] = batch.addWindow();
                 win.addTo(batch, slot[(size_t) s]);
-                for (int k = 0; k < win.numKeyFrames(); k++)
-                    batch.addResidualBlock(slot[(size_t) s], std::make_shared<PosePriorFactor>(priors[(size_t) s][(size_t) k].data(), prior_weight), nullptr,
-                                           {win.pose(k)});
+                const OnBatchWindow on{batch, slot[(size_t) s]};
+                for (int k = 0; k < win.numKeyFrames(); k++) pose_prior(on, win.pose(k), priors[(size_t) s][(size_t) k].data(), prior_weight);
             } else {
                 WindowSolver solver(win.batch(), 1.0);
                 win.addTo(solver);
-                for (int k = 0; k < win.numKeyFrames(); k++)
-                    solver.addResidualBlock(std::make_shared<PosePriorFactor>(priors[(size_t) s][(size_t) k].data(), prior_weight), nullptr, {win.pose(k)});
+                for (int k = 0; k < win.numKeyFrames(); k++) pose_prior(solver, win.pose(k), priors[(size_t) s][(size_t) k].data(), prior_weight);
                 WindowSolver::Options opt;
                 WindowSolver::Summary s1, s2;
                 opt.max_num_iterations = iters1;

@@ -8,7 +8,7 @@
 #include "host_pool.h"
 #include "marg_batch.h"
 #include "marg_linearize_hip.h"
-#include "capi_util.h"
+#include "capi_windows.h"
 
 using namespace icg;
 
@@ -66,49 +66,26 @@ int icgh_backend_marginalize(int n, const double *obs_soa, const int32_t *idx_i,
                              double *J0, double *e0, const double *x_eval /* concatenated by rem order, may be NULL */,
                              double *marg_res, char *err, int errlen) {
     return guarded(err, errlen, [&] {
-        vector<double> P(poses, poses + 7 * (size_t) n_poses), E(ext, ext + 7), D(invdepth, invdepth + n_lm);
-        double TD = td;
-        std::unordered_map<long, long> ids;
-        std::unordered_map<long, double *> address;
-        auto reg = [&](double *p, long id) {
-            ids[reinterpret_cast<long>(p)] = id;
-            address[id]                     = p;
-        };
-        for (int k = 0; k < n_poses; k++) reg(&P[7 * (size_t) k], k);
-        for (int l = 0; l < n_lm; l++) reg(&D[(size_t) l], 100000 + l);
-        reg(E.data(), 900000);
-        reg(&TD, 900001);
         (void) estimate_ext;
         (void) estimate_td;
-
-        auto info = std::make_shared<MarginalizationInfo>();
-        info->updateParamtersIds(ids);
+        const MargArgs args{n, obs_soa, idx_i, idx_j, idx_lm, n_poses, poses, ext, n_lm, invdepth, td, huber_delta, prior_weight};
+        auto wins = marg_windows(args, 1, -1, 0.0);
+        MargWindow &W = *wins[0];
+        auto &info    = W.info;
         ReprojectionBatch batch(0);
         info->setReprojectionBatch(&batch);
-        auto loss = huber_delta > 0 ? std::make_shared<HuberLossHip>(huber_delta) : nullptr;
-        for (int k = 0; k < n; k++) {
-            std::shared_ptr<ReprojectionFactor> f = reproj_factor_from_soa(obs_soa, n, k);
-            double *pi = &P[7 * (size_t) idx_i[k]], *pj = &P[7 * (size_t) idx_j[k]], *lm = &D[(size_t) idx_lm[k]];
-            batch.add(f.get(), pi, pj, E.data(), lm, &TD);
-            // marginalize {pose_ref, invdepth} as ic_gvins.cc:1600-1606 does
-            info->addResidualBlockInfo(std::make_shared<ResidualBlockInfo>(f, loss, vector<double *>{pi, pj, E.data(), lm, &TD}, vector<int>{0, 3}));
-        }
+        marg_reprojections(args, W, batch_add(batch));
         batch.finalize();
-        // host-evaluated generic factor on the marginalized pose (stands in for prior/IMU factors of the real window)
-        vector<double> pose0_prior(P.begin(), P.begin() + 7);
-        pose0_prior[0] += 0.01; // non-zero residual
-        info->addResidualBlockInfo(std::make_shared<ResidualBlockInfo>(std::make_shared<PosePriorFactor>(pose0_prior.data(), prior_weight),
-                                                                       nullptr, vector<double *>{&P[0]}, vector<int>{0}));
         if (!info->marginalization()) {
             set_err(err, errlen, ("marginalization failed: " + batch.error()).c_str());
             return -2;
         }
-        auto blocks = info->getParamterBlocks(address);
+        auto blocks = info->getParamterBlocks(W.address);
         sizes[0]    = info->marginalizedSize();
         sizes[1]    = info->remainedSize();
         *n_rem      = (int32_t) blocks.size();
         for (size_t b = 0; b < blocks.size(); b++) {
-            rem_ids[b]   = ids[reinterpret_cast<long>(blocks[b])];
+            rem_ids[b]   = W.ids[reinterpret_cast<long>(blocks[b])];
             rem_index[b] = info->remainedBlockIndex()[b];
             rem_size[b]  = info->remainedBlockSize()[b];
         }
@@ -145,55 +122,8 @@ int icgh_backend_marginalize_batch(int mode, int n_windows, int dense_window, do
                                    int host_threads, int32_t *sizes, double *Hp, double *bp, double *J0, double *e0, int32_t *counts,
                                    double *seconds, char *err, int errlen) {
     return guarded(err, errlen, [&] {
-        struct Win {
-            vector<double> P, E, D;
-            double TD;
-            std::unordered_map<long, long> ids;
-            std::shared_ptr<MarginalizationInfo> info;
-            vector<std::shared_ptr<ReprojectionFactor>> factors;
-            vector<double> pose0_prior;
-        };
-        auto loss = huber_delta > 0 ? std::make_shared<HuberLossHip>(huber_delta) : nullptr;
-        auto build = [&](vector<std::unique_ptr<Win>> &wins) {
-            wins.clear();
-            uint64_t lcg = 0x9E3779B97F4A7C15ull;
-            auto rnd     = [&] { // uniform in [-1, 1)
-                lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
-                return (double) ((lcg >> 11) & ((1ull << 53) - 1)) / (double) (1ull << 52) - 1.0;
-            };
-            for (int w = 0; w < n_windows; w++) {
-                std::unique_ptr<Win> W(new Win);
-                W->P.assign(poses, poses + 7 * (size_t) n_poses), W->E.assign(ext, ext + 7), W->D.assign(invdepth, invdepth + n_lm), W->TD = td;
-                if (w > 0) {
-                    for (int k = 0; k < n_poses; k++)
-                        for (int c = 0; c < 3; c++) W->P[7 * (size_t) k + c] += jitter * rnd();
-                    for (int l = 0; l < n_lm; l++) W->D[(size_t) l] *= 1.0 + jitter * rnd();
-                }
-                for (int k = 0; k < n_poses; k++) W->ids[reinterpret_cast<long>(&W->P[7 * (size_t) k])] = k;
-                for (int l = 0; l < n_lm; l++) W->ids[reinterpret_cast<long>(&W->D[(size_t) l])] = 100000 + l;
-                W->ids[reinterpret_cast<long>(W->E.data())] = 900000;
-                W->ids[reinterpret_cast<long>(&W->TD)]       = 900001;
-                W->info = std::make_shared<MarginalizationInfo>();
-                W->info->updateParamtersIds(W->ids);
-                for (int k = 0; k < n; k++) {
-                    W->factors.push_back(reproj_factor_from_soa(obs_soa, n, k));
-                    double *pi = &W->P[7 * (size_t) idx_i[k]], *pj = &W->P[7 * (size_t) idx_j[k]], *lm = &W->D[(size_t) idx_lm[k]];
-                    W->info->addResidualBlockInfo(
-                        std::make_shared<ResidualBlockInfo>(W->factors.back(), loss, vector<double *>{pi, pj, W->E.data(), lm, &W->TD}, vector<int>{0, 3}));
-                }
-                W->pose0_prior.assign(W->P.begin(), W->P.begin() + 7);
-                W->pose0_prior[0] += 0.01;
-                W->info->addResidualBlockInfo(std::make_shared<ResidualBlockInfo>(std::make_shared<PosePriorFactor>(W->pose0_prior.data(), prior_weight),
-                                                                                  nullptr, vector<double *>{&W->P[0]}, vector<int>{0}));
-                if (w == dense_window && n > 0) {
-                    double *lm = &W->D[(size_t) idx_lm[0]];
-                    W->info->addResidualBlockInfo(std::make_shared<ResidualBlockInfo>(std::make_shared<ScalarPriorFactor>(*lm * 1.01, 0.5 * prior_weight),
-                                                                                      nullptr, vector<double *>{lm}, vector<int>{0}));
-                }
-                wins.push_back(std::move(W));
-            }
-        };
-        vector<std::unique_ptr<Win>> wins;
+        const MargArgs args{n, obs_soa, idx_i, idx_j, idx_lm, n_poses, poses, ext, n_lm, invdepth, td, huber_delta, prior_weight};
+        vector<std::unique_ptr<MargWindow>> wins;
         vector<char> ok((size_t) n_windows, 0);
         std::string what;
         double best = -1.0;
@@ -208,16 +138,12 @@ int icgh_backend_marginalize_batch(int mode, int n_windows, int dense_window, do
         for (int rep = 0; rep < std::max(1, reps); rep++) {
             if (mb) mb->clear(); // (before the infos of the last repetition go)
             if (batch) batch->clear();
-            build(wins);
+            wins.clear();
+            wins = marg_windows(args, n_windows, dense_window, jitter);
             counts[0] = counts[1] = 0;
             double took = 0;
             if (mb) {
-                for (auto &W : wins) {
-                    const int w = mb->addWindow(W->info);
-                    for (int k = 0; k < n; k++)
-                        mb->addReprojectionFactor(w, W->factors[(size_t) k].get(), &W->P[7 * (size_t) idx_i[k]], &W->P[7 * (size_t) idx_j[k]], W->E.data(),
-                                                  &W->D[(size_t) idx_lm[k]], &W->TD);
-                }
+                for (auto &W : wins) marg_reprojections(args, *W, window_add(*mb, mb->addWindow(W->info)));
                 auto t0         = std::chrono::steady_clock::now();
                 const bool good = mb->marginalize(&ok);
                 took            = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -229,10 +155,9 @@ int icgh_backend_marginalize_batch(int mode, int n_windows, int dense_window, do
                 counts[0] = mb->structuredWindows(), counts[1] = mb->denseWindows();
             } else {
                 for (size_t w = 0; w < wins.size(); w++) {
-                    Win &W = *wins[w];
+                    MargWindow &W = *wins[w];
                     batch->clear();
-                    for (int k = 0; k < n; k++)
-                        batch->add(W.factors[(size_t) k].get(), &W.P[7 * (size_t) idx_i[k]], &W.P[7 * (size_t) idx_j[k]], W.E.data(), &W.D[(size_t) idx_lm[k]], &W.TD);
+                    marg_reprojections(args, W, batch_add(*batch));
                     W.info->setReprojectionBatch(batch.get());
                     auto a = std::chrono::steady_clock::now();
                     batch->finalize();
@@ -352,29 +277,21 @@ int icgh_backend_marg_factor(int mode, int n_windows, const int32_t *r, const in
             return -1;
         }
         const size_t W = (size_t) n_windows;
-        vector<size_t> e_off(W + 1, 0), x_off(W + 1, 0), j_off(W + 1, 0), jac_off(W + 1, 0);
-        vector<int> size(block_size, block_size + block_off[W]), index(block_index, block_index + block_off[W]);
-        vector<const double *> x0_ptr((size_t) block_off[W]);
+        const FlatPriors flat(W, r, block_off, block_size, block_index, x0);
+        const vector<size_t> &e_off = flat.e_off, &x_off = flat.x_off;
+        vector<size_t> jac_off(W + 1, 0);
         vector<MargPriorView> views(W);
         for (size_t w = 0; w < W; w++) {
-            size_t xs = 0;
-            bool ok   = r[w] > 0 && block_off[w + 1] >= block_off[w] && (w > 0 || block_off[0] == 0);
-            for (int b = block_off[w]; ok && b < block_off[w + 1]; b++) {
-                ok = size[(size_t) b] > 0 && index[(size_t) b] >= 0 &&
-                     index[(size_t) b] + MarginalizationInfo::localSize(size[(size_t) b]) <= r[w];
-                x0_ptr[(size_t) b] = x0 + x_off[w] + xs;
-                xs += (size_t) size[(size_t) b];
-            }
+            bool ok = r[w] > 0 && block_off[w + 1] >= block_off[w] && (w > 0 || block_off[0] == 0);
+            for (int b = block_off[w]; ok && b < block_off[w + 1]; b++)
+                ok = flat.size[(size_t) b] > 0 && flat.index[(size_t) b] >= 0 &&
+                     flat.index[(size_t) b] + MarginalizationInfo::localSize(flat.size[(size_t) b]) <= r[w];
             if (!ok) {
                 set_err(err, errlen, ("icgh_backend_marg_factor: window " + std::to_string(w) + " is not a valid prior").c_str());
                 return -1;
             }
-            MargPriorView &v = views[w];
-            v.r = r[w], v.n_blocks = block_off[w + 1] - block_off[w];
-            v.size = size.data() + block_off[w], v.index = index.data() + block_off[w], v.x0 = x0_ptr.data() + block_off[w];
-            v.J0 = J0 + j_off[w], v.e0 = e0 + e_off[w];
-            e_off[w + 1] = e_off[w] + (size_t) r[w], x_off[w + 1] = x_off[w] + xs;
-            j_off[w + 1] = j_off[w] + (size_t) r[w] * r[w], jac_off[w + 1] = jac_off[w] + (size_t) r[w] * xs;
+            views[w]       = flat.view(w, J0, e0);
+            jac_off[w + 1] = jac_off[w] + (size_t) r[w] * (x_off[w + 1] - x_off[w]);
         }
         const size_t R = e_off[W], X = x_off[W], NJ = jac_off[W];
         double best = -1; // (over the points: each one evaluated reps + 1 times)

@@ -9,7 +9,7 @@
 #include "marg_batch.h"
 #include "marg_linearize_hip.h"
 #include "solver_batch_hip.h"
-#include "capi_util.h"
+#include "capi_windows.h"
 
 using namespace icg;
 
@@ -43,55 +43,10 @@ int icgh_backend_marg_handoff(int mode, int n_windows, int dense_window, double 
             return -1;
         }
         const bool keep = (mode & 1) != 0, release_first = (mode & 2) != 0;
-        struct Win {
-            vector<double> P, E, D, pose_prior;
-            double TD;
-            std::unordered_map<long, long> ids;
-            std::unordered_map<long, double *> address;
-            std::shared_ptr<MarginalizationInfo> info;
-            vector<std::shared_ptr<ReprojectionFactor>> factors;
-            vector<double> pose0_prior;
-        };
-        auto loss = huber_delta > 0 ? std::make_shared<HuberLossHip>(huber_delta) : nullptr;
-        vector<std::unique_ptr<Win>> wins;
-        uint64_t lcg = 0x9E3779B97F4A7C15ull;
-        auto rnd     = [&] { // uniform in [-1, 1)
-            lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
-            return (double) ((lcg >> 11) & ((1ull << 53) - 1)) / (double) (1ull << 52) - 1.0;
-        };
-        for (int w = 0; w < n_windows; w++) {
-            std::unique_ptr<Win> W(new Win);
-            W->P.assign(poses, poses + 7 * (size_t) n_poses), W->E.assign(ext, ext + 7), W->D.assign(invdepth, invdepth + n_lm), W->TD = td;
-            if (w > 0) {
-                for (int k = 0; k < n_poses; k++)
-                    for (int c = 0; c < 3; c++) W->P[7 * (size_t) k + c] += jitter * rnd();
-                for (int l = 0; l < n_lm; l++) W->D[(size_t) l] *= 1.0 + jitter * rnd();
-            }
-            auto reg = [&](double *p, long id) { W->ids[reinterpret_cast<long>(p)] = id, W->address[id] = p; };
-            for (int k = 0; k < n_poses; k++) reg(&W->P[7 * (size_t) k], k);
-            for (int l = 0; l < n_lm; l++) reg(&W->D[(size_t) l], 100000 + l);
-            reg(W->E.data(), 900000);
-            reg(&W->TD, 900001);
-            W->pose_prior = W->P;
-            W->info       = std::make_shared<MarginalizationInfo>();
-            W->info->updateParamtersIds(W->ids);
-            for (int k = 0; k < n; k++) {
-                W->factors.push_back(reproj_factor_from_soa(obs_soa, n, k));
-                double *pi = &W->P[7 * (size_t) idx_i[k]], *pj = &W->P[7 * (size_t) idx_j[k]], *lm = &W->D[(size_t) idx_lm[k]];
-                W->info->addResidualBlockInfo(
-                    std::make_shared<ResidualBlockInfo>(W->factors.back(), loss, vector<double *>{pi, pj, W->E.data(), lm, &W->TD}, vector<int>{0, 3}));
-            }
-            W->pose0_prior.assign(W->P.begin(), W->P.begin() + 7);
-            W->pose0_prior[0] += 0.01;
-            W->info->addResidualBlockInfo(std::make_shared<ResidualBlockInfo>(std::make_shared<PosePriorFactor>(W->pose0_prior.data(), prior_weight), nullptr,
-                                                                              vector<double *>{&W->P[0]}, vector<int>{0}));
-            if (w == dense_window && n > 0) {
-                double *lm = &W->D[(size_t) idx_lm[0]];
-                W->info->addResidualBlockInfo(std::make_shared<ResidualBlockInfo>(std::make_shared<ScalarPriorFactor>(*lm * 1.01, 0.5 * prior_weight), nullptr,
-                                                                                  vector<double *>{lm}, vector<int>{0}));
-            }
-            wins.push_back(std::move(W));
-        }
+        const MargArgs args{n, obs_soa, idx_i, idx_j, idx_lm, n_poses, poses, ext, n_lm, invdepth, td, huber_delta, prior_weight};
+        auto wins = marg_windows(args, n_windows, dense_window, jitter);
+        vector<vector<double>> pose_prior; // the poses each window starts from: the targets of its solve's pose priors
+        for (auto &W : wins) pose_prior.push_back(W->P);
         auto now = [] { return std::chrono::steady_clock::now(); };
         auto ms  = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
             return std::chrono::duration<double, std::milli>(b - a).count();
@@ -103,12 +58,7 @@ int icgh_backend_marg_handoff(int mode, int n_windows, int dense_window, double 
         MarginalizationBatch mb(0, huber_delta, host_threads);
         mb.setDeviceLinearization(true);
         mb.setKeepLinearized(keep);
-        for (auto &W : wins) {
-            const int w = mb.addWindow(W->info);
-            for (int k = 0; k < n; k++)
-                mb.addReprojectionFactor(w, W->factors[(size_t) k].get(), &W->P[7 * (size_t) idx_i[k]], &W->P[7 * (size_t) idx_j[k]], W->E.data(),
-                                         &W->D[(size_t) idx_lm[k]], &W->TD);
-        }
+        for (auto &W : wins) marg_reprojections(args, *W, window_add(mb, mb.addWindow(W->info)));
         vector<char> ok;
         auto t0 = now();
         if (!mb.marginalize(&ok)) {
@@ -125,7 +75,7 @@ int icgh_backend_marg_handoff(int mode, int n_windows, int dense_window, double 
         vector<vector<double *>> blocks;
         for (int w = 0; w < n_windows; w++) {
             if (!ok[(size_t) w]) continue;
-            Win &W = *wins[(size_t) w];
+            MargWindow &W = *wins[(size_t) w];
             good.push_back(w);
             blocks.push_back(W.info->getParamterBlocks(W.address));
             priors.push_back(std::make_shared<MarginalizationFactor>(W.info));
@@ -153,11 +103,7 @@ int icgh_backend_marg_handoff(int mode, int n_windows, int dense_window, double 
             }
             timers_ms[1] = ms(t0, now());
             counts[1] = (int32_t) set.residualSize(), counts[2] = set.handedOff();
-            uint64_t s2 = seed * 2862933555777941757ull + 3037000493ull;
-            auto rnd2   = [&] {
-                s2 = s2 * 6364136223846793005ull + 1442695040888963407ull;
-                return (double) ((s2 >> 11) & ((1ull << 53) - 1)) / (double) (1ull << 52) - 1.0;
-            };
+            Uniform rnd = point_stream(seed);
             vector<vector<double>> xs(views.size());
             vector<vector<const double *>> params(views.size());
             vector<const double *const *> plist(views.size());
@@ -167,7 +113,7 @@ int icgh_backend_marg_handoff(int mode, int n_windows, int dense_window, double 
                 for (int b = 0; b < v.n_blocks; b++) total += (size_t) v.size[b];
                 xs[p].reserve(total);
                 for (int b = 0; b < v.n_blocks; b++)
-                    for (int k = 0; k < v.size[b]; k++) xs[p].push_back(v.x0[b][k] + perturb * rnd2());
+                    for (int k = 0; k < v.size[b]; k++) xs[p].push_back(v.x0[b][k] + perturb * rnd());
                 size_t at = 0;
                 for (int b = 0; b < v.n_blocks; b++) params[p].push_back(xs[p].data() + at), at += (size_t) v.size[b];
                 plist[p] = params[p].data();
@@ -200,20 +146,12 @@ int icgh_backend_marg_handoff(int mode, int n_windows, int dense_window, double 
         solver.setDeviceHostPart(true);
         solver.setDevicePrior(true);
         for (size_t g = 0; g < good.size(); g++) {
-            Win &W       = *wins[(size_t) good[g]];
-            const int ww = solver.addWindow();
-            for (int k = 0; k < n_poses; k++) solver.addParameterBlock(ww, &W.P[7 * (size_t) k], 7, true);
-            solver.addParameterBlock(ww, W.E.data(), 7, true);
-            for (int l = 0; l < n_lm; l++) solver.addParameterBlock(ww, &W.D[(size_t) l], 1);
-            solver.addParameterBlock(ww, &W.TD, 1);
-            solver.setParameterBlockConstant(ww, W.E.data());
-            solver.setParameterBlockConstant(ww, &W.TD);
-            for (int k = 0; k < n; k++)
-                solver.addReprojectionFactor(ww, W.factors[(size_t) k].get(), &W.P[7 * (size_t) idx_i[k]], &W.P[7 * (size_t) idx_j[k]], W.E.data(),
-                                             &W.D[(size_t) idx_lm[k]], &W.TD);
-            for (int k = 0; k < n_poses; k++)
-                solver.addResidualBlock(ww, std::make_shared<PosePriorFactor>(&W.pose_prior[7 * (size_t) k], prior_weight), nullptr, {&W.P[7 * (size_t) k]});
-            solver.addResidualBlock(ww, priors[g], nullptr, blocks[g]);
+            MargWindow &W = *wins[(size_t) good[g]];
+            const OnBatchWindow win{solver, solver.addWindow()};
+            visual_blocks(win, n_poses, W.P.data(), W.E.data(), n_lm, W.D.data(), &W.TD, true, true);
+            marg_reprojections(args, W, window_add(solver, win.w));
+            pose_priors(win, n_poses, W.P.data(), pose_prior[(size_t) good[g]].data(), prior_weight);
+            solver.addResidualBlock(win.w, priors[g], nullptr, blocks[g]);
         }
         if (!solver.prepare()) {
             set_err(err, errlen, solver.error().c_str());
@@ -230,11 +168,10 @@ int icgh_backend_marg_handoff(int mode, int n_windows, int dense_window, double 
         timers_ms[4] = ms(t0, now());
         counts[6]    = solver.priorsHandedOff();
         for (size_t g = 0; g < good.size(); g++) {
-            const Win &W = *wins[(size_t) good[g]];
+            const MargWindow &W = *wins[(size_t) good[g]];
             memcpy(states + g * 7 * (size_t) n_poses, W.P.data(), sizeof(double) * 7 * (size_t) n_poses);
             memcpy(invdepth_out + g * (size_t) n_lm, W.D.data(), sizeof(double) * (size_t) n_lm);
-            double *o = summary4 + 4 * g;
-            o[0] = sum[g].initial_cost, o[1] = sum[g].final_cost, o[2] = sum[g].num_successful_steps, o[3] = sum[g].num_unsuccessful_steps;
+            put_summary4(sum[g], summary4 + 4 * g);
         }
         return 0;
     });
@@ -266,26 +203,20 @@ int icgh_backend_marg_handoff_chain(int mode, int n_windows, const int32_t *P, c
             return -4;
         }
         const size_t W = (size_t) n_windows;
-        vector<size_t> r_off(W + 1, 0), rr_off(W + 1, 0), x_off(W + 1, 0);
-        vector<int> size(block_size, block_size + block_off[W]), index(block_index, block_index + block_off[W]);
-        vector<const double *> x0_ptr((size_t) block_off[W]), x_ptr((size_t) block_off[W]);
-        for (size_t w = 0; w < W; w++) {
+        for (size_t w = 0; w < W; w++)
             if (P[w] <= 0 || m[w] < 0 || m[w] >= P[w] || block_off[w + 1] < block_off[w]) {
                 set_err(err, errlen, ("icgh_backend_marg_handoff_chain: window " + std::to_string(w) + " is not a valid system").c_str());
                 return -1;
             }
-            const size_t r = (size_t) (P[w] - m[w]);
-            size_t xs      = 0;
-            for (int bk = block_off[w]; bk < block_off[w + 1]; bk++) {
-                x0_ptr[(size_t) bk] = x0 + x_off[w] + xs, x_ptr[(size_t) bk] = x + x_off[w] + xs;
-                xs += (size_t) size[(size_t) bk];
-            }
-            r_off[w + 1] = r_off[w] + r, rr_off[w + 1] = rr_off[w] + r * r, x_off[w + 1] = x_off[w] + xs;
-        }
+        vector<int32_t> r(W);
+        for (size_t w = 0; w < W; w++) r[w] = P[w] - m[w];
+        const FlatPriors flat(W, r.data(), block_off, block_size, block_index, x0);
+        vector<const double *> x_ptr(flat.x0_ptr.size()); // x laid out like x0
+        for (size_t bk = 0; bk < x_ptr.size(); bk++) x_ptr[bk] = x + (flat.x0_ptr[bk] - x0);
         TempCtx Tlin(0), Tset(0);
         MarginalizationLinearizer lin(true, Tlin.ctx);
         MarginalizationPriorSet set;
-        vector<double> J0(rr_off[W]), e0(r_off[W]);
+        vector<double> J0(flat.j_off[W]), e0(flat.e_off[W]);
         vector<MargPriorView> views(W);
         auto now = [] { return std::chrono::steady_clock::now(); };
         auto took = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point z) {
@@ -309,13 +240,7 @@ int icgh_backend_marg_handoff_chain(int mode, int n_windows, const int32_t *P, c
             }
             auto z = now();
             if (t) t[0] = took(a, z);
-            for (size_t w = 0; w < W; w++) {
-                MargPriorView &v = views[w];
-                v.r = P[w] - m[w], v.n_blocks = block_off[w + 1] - block_off[w];
-                v.size = size.data() + block_off[w], v.index = index.data() + block_off[w], v.x0 = x0_ptr.data() + block_off[w];
-                v.J0 = J0.data() + rr_off[w], v.e0 = e0.data() + r_off[w];
-                v.keep_id = id, v.keep_slot = id ? (int) w : -1;
-            }
+            for (size_t w = 0; w < W; w++) views[w] = flat.view(w, J0.data(), e0.data(), id, id ? (int) w : -1);
             if (profiled) icg_prof_enable(Tset.ctx, 1);
             a = now();
             if (!set.set(Tset.ctx, views, &e)) {

@@ -20,9 +20,7 @@ struct Intervals {
     Intervals(int variant, int n, const int32_t *offsets, const double *imu, const double *state0, const double *params9) {
         auto P = preint_params(params9);
         for (int k = 0; k < n; k++) {
-            auto p = std::make_shared<Preintegration>(P, ins_imu(imu + 8 * (size_t) offsets[k]), preint_state(state0 + 16 * (size_t) k),
-                                                      variant ? Preintegration::EARTH : Preintegration::NORMAL);
-            for (int row = offsets[k] + 1; row < offsets[k + 1]; row++) p->addNewImu(ins_imu(imu + 8 * (size_t) row));
+            auto p = preint_interval(variant, P, offsets, imu, k, state0 + 16 * (size_t) k);
             pre.push_back(p);
             raw.push_back(p.get());
             craw.push_back(p.get());

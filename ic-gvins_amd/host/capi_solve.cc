@@ -8,7 +8,7 @@
 #include "factors.h"
 #include "solver_hip.h"
 #include "solver_batch_hip.h"
-#include "capi_util.h"
+#include "capi_windows.h"
 
 using namespace icg;
 
@@ -34,22 +34,12 @@ int icgh_backend_solve(int n, const double *obs_soa, const int32_t *idx_i, const
         auto t_begin = std::chrono::steady_clock::now();
         vector<std::unique_ptr<ReprojectionFactor>> factors;
         ReprojectionBatch batch(0);
-        for (int k = 0; k < n; k++) {
-            factors.push_back(reproj_factor_from_soa(obs_soa, n, k));
-            batch.add(factors.back().get(), poses + 7 * (size_t) idx_i[k], poses + 7 * (size_t) idx_j[k], ext, invdepth + idx_lm[k], td);
-        }
+        reprojections_from_soa(obs_soa, n, 0, n, idx_i, idx_j, idx_lm, poses, ext, invdepth, td, factors, batch_add(batch));
         batch.finalize();
         auto t_built = std::chrono::steady_clock::now();
         WindowSolver solver(&batch, huber);
-        for (int k = 0; k < n_poses; k++) solver.addParameterBlock(poses + 7 * (size_t) k, 7, true);
-        solver.addParameterBlock(ext, 7, true);
-        for (int l = 0; l < n_lm; l++) solver.addParameterBlock(invdepth + l, 1);
-        solver.addParameterBlock(td, 1);
-        if (ext_constant) solver.setParameterBlockConstant(ext);
-        if (td_constant) solver.setParameterBlockConstant(td);
-        for (int k = 0; k < n_poses; k++)
-            solver.addResidualBlock(std::make_shared<PosePriorFactor>(prior_poses + 7 * (size_t) k, prior_weight), nullptr,
-                                    {poses + 7 * (size_t) k});
+        visual_blocks(solver, n_poses, poses, ext, n_lm, invdepth, td, ext_constant != 0, td_constant != 0);
+        pose_priors(solver, n_poses, poses, prior_poses, prior_weight);
         WindowSolver::Options opt;
         WindowSolver::Summary s1, s2;
         opt.max_num_iterations = iters1;
@@ -57,9 +47,7 @@ int icgh_backend_solve(int n, const double *obs_soa, const int32_t *idx_i, const
             set_err(err, errlen, solver.error().c_str());
             return -2;
         }
-        summary8[0] = s1.initial_cost, summary8[1] = s1.final_cost, summary8[2] = s1.final_cost;
-        summary8[3] = s1.num_successful_steps, summary8[4] = s1.num_unsuccessful_steps;
-        summary8[5] = summary8[6] = summary8[7] = 0;
+        put_summary8(s1, nullptr, 0, summary8);
         if (chi2 > 0) {
             int removed = solver.removeReprojectionFactorsByChi2(chi2);
             if (removed < 0) {
@@ -71,7 +59,7 @@ int icgh_backend_solve(int n, const double *obs_soa, const int32_t *idx_i, const
                 set_err(err, errlen, solver.error().c_str());
                 return -4;
             }
-            summary8[2] = s2.final_cost, summary8[5] = s2.num_successful_steps, summary8[6] = s2.num_unsuccessful_steps, summary8[7] = removed;
+            put_summary8(s1, &s2, removed, summary8);
         }
         summary8[8] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_built).count();
         summary8[9] = std::chrono::duration<double, std::milli>(t_built - t_begin).count();
@@ -130,11 +118,7 @@ double icgh_backend_solve_throughput(int n, const double *obs_soa, const int32_t
             J->P.assign(poses, poses + 7 * (size_t) n_poses), J->E.assign(ext, ext + 7), J->D.assign(invdepth, invdepth + n_lm), J->TD = td;
             J->batch.reset(new ReprojectionBatch(0));
             if (threads > 4) J->batch->setWaitMode(ICG_WAIT_POLL, 5); // more solvers than spare host cores: do not spin on completion
-            for (int k = 0; k < n; k++) {
-                J->factors.push_back(reproj_factor_from_soa(obs_soa, n, k));
-                J->batch->add(J->factors.back().get(), &J->P[7 * (size_t) idx_i[k]], &J->P[7 * (size_t) idx_j[k]], J->E.data(), &J->D[(size_t) idx_lm[k]],
-                              &J->TD);
-            }
+            reprojections_from_soa(obs_soa, n, 0, n, idx_i, idx_j, idx_lm, J->P.data(), J->E.data(), J->D.data(), &J->TD, J->factors, batch_add(*J->batch));
             J->batch->finalize();
             jobs.push_back(std::move(J));
         }
@@ -144,12 +128,8 @@ double icgh_backend_solve_throughput(int n, const double *obs_soa, const int32_t
             for (int r = 0; r < repeat; r++) {
                 J.P.assign(poses, poses + 7 * (size_t) n_poses), J.E.assign(ext, ext + 7), J.D.assign(invdepth, invdepth + n_lm), J.TD = td;
                 WindowSolver solver(J.batch.get(), huber);
-                for (int k = 0; k < n_poses; k++) solver.addParameterBlock(&J.P[7 * (size_t) k], 7, true);
-                solver.addParameterBlock(J.E.data(), 7, true);
-                for (int l = 0; l < n_lm; l++) solver.addParameterBlock(&J.D[(size_t) l], 1);
-                solver.addParameterBlock(&J.TD, 1);
-                for (int k = 0; k < n_poses; k++)
-                    solver.addResidualBlock(std::make_shared<PosePriorFactor>(prior_poses + 7 * (size_t) k, prior_weight), nullptr, {&J.P[7 * (size_t) k]});
+                visual_blocks(solver, n_poses, J.P.data(), J.E.data(), n_lm, J.D.data(), &J.TD, false, false);
+                pose_priors(solver, n_poses, J.P.data(), prior_poses, prior_weight);
                 WindowSolver::Options opt;
                 WindowSolver::Summary s1;
                 opt.max_num_iterations = iters1;
@@ -184,51 +164,23 @@ int icgh_backend_solve_vio(int n_intervals, const int32_t *offsets, const double
                            double *invdepth, double *td, const double *prior_pose0, const double *prior_mix0, double prior_weight, double huber,
                            int iters, double *summary4, char *err, int errlen) {
     return guarded(err, errlen, [&] {
-        const int K = n_intervals + 1;
-        vector<double> pose((size_t) K * 7), mix((size_t) K * 9);
-        for (int k = 0; k < K; k++) {
-            memcpy(&pose[7 * (size_t) k], states16 + 16 * (size_t) k, sizeof(double) * 7);
-            memcpy(&mix[9 * (size_t) k], states16 + 16 * (size_t) k + 7, sizeof(double) * 9);
-        }
         vector<std::unique_ptr<ReprojectionFactor>> factors;
         ReprojectionBatch batch(0);
-        for (int f = 0; f < n; f++) {
-            factors.push_back(reproj_factor_from_soa(obs_soa, n, f));
-            batch.add(factors.back().get(), &pose[7 * (size_t) idx_i[f]], &pose[7 * (size_t) idx_j[f]], ext, invdepth + idx_lm[f], td);
-        }
-        batch.finalize();
         // preintegration of every interval from its start state: one icg_preint_batch launch on a context of its own
-        auto P = preint_params(params9);
         TempCtx T(0);
-        vector<std::shared_ptr<Preintegration>> pre;
         vector<Preintegration *> raw;
-        for (int k = 0; k < n_intervals; k++) {
-            auto p = std::make_shared<Preintegration>(P, ins_imu(imu + 8 * (size_t) offsets[k]), preint_state(states16 + 16 * (size_t) k),
-                                                      Preintegration::NORMAL);
-            for (int row = offsets[k] + 1; row < offsets[k + 1]; row++) p->addNewImu(ins_imu(imu + 8 * (size_t) row));
-            pre.push_back(p);
-            raw.push_back(p.get());
-        }
+        VioWindow W = vio_window(n_intervals, offsets, imu, preint_params(params9), states16, raw);
+        reprojections_from_soa(obs_soa, n, 0, n, idx_i, idx_j, idx_lm, W.pose.data(), ext, invdepth, td, factors, batch_add(batch));
+        batch.finalize();
         std::string e;
         if (!Preintegration::integrateBatch(T.ctx, raw, &e)) {
             set_err(err, errlen, e.c_str());
             return -2;
         }
         WindowSolver solver(&batch, huber);
-        for (int k = 0; k < K; k++) {
-            solver.addParameterBlock(&pose[7 * (size_t) k], 7, true);
-            solver.addParameterBlock(&mix[9 * (size_t) k], 9);
-        }
-        solver.addParameterBlock(ext, 7, true);
-        for (int l = 0; l < n_lm; l++) solver.addParameterBlock(invdepth + l, 1);
-        solver.addParameterBlock(td, 1);
-        solver.setParameterBlockConstant(ext); // estimated off-line in the default configuration (optimize_estimate_extrinsic: false)
-        solver.setParameterBlockConstant(td);
-        for (int k = 0; k < n_intervals; k++)
-            solver.addResidualBlock(std::make_shared<PreintegrationFactor>(pre[(size_t) k]), nullptr,
-                                    {&pose[7 * (size_t) k], &mix[9 * (size_t) k], &pose[7 * (size_t) (k + 1)], &mix[9 * (size_t) (k + 1)]});
-        solver.addResidualBlock(std::make_shared<PosePriorFactor>(prior_pose0, prior_weight), nullptr, {&pose[0]});
-        solver.addResidualBlock(std::make_shared<MixPriorFactor>(prior_mix0, prior_weight), nullptr, {&mix[0]});
+        vio_blocks(solver, W, ext, n_lm, invdepth, td);
+        vio_motion_factors(solver, W, prior_pose0, prior_weight);
+        vio_mix_prior(solver, W, prior_mix0, prior_weight);
         WindowSolver::Options opt;
         WindowSolver::Summary sum;
         opt.max_num_iterations = iters;
@@ -236,11 +188,8 @@ int icgh_backend_solve_vio(int n_intervals, const int32_t *offsets, const double
             set_err(err, errlen, solver.error().c_str());
             return -3;
         }
-        summary4[0] = sum.initial_cost, summary4[1] = sum.final_cost, summary4[2] = sum.num_successful_steps, summary4[3] = sum.num_unsuccessful_steps;
-        for (int k = 0; k < K; k++) {
-            memcpy(states16 + 16 * (size_t) k, &pose[7 * (size_t) k], sizeof(double) * 7);
-            memcpy(states16 + 16 * (size_t) k + 7, &mix[9 * (size_t) k], sizeof(double) * 9);
-        }
+        put_summary4(sum, summary4);
+        W.put(states16);
         if (getenv("ICG_SOLVER_DEBUG")) fprintf(stderr, "%s\n", sum.BriefReport().c_str());
         return 0;
     });

@@ -9,7 +9,7 @@
 
 #include "factors.h"
 #include "solver_batch_hip.h"
-#include "capi_util.h"
+#include "capi_windows.h"
 
 using namespace icg;
 
@@ -109,22 +109,12 @@ int icgh_backend_solve_batch_parts(int W, const int32_t *fac_off, const int32_t 
         solver.setDeviceReducedSolve(reduced_solve_mode == 1);
         solver.setDeviceHostPart(host_part_mode == 1);
         for (int w = 0; w < W; w++) {
-            const int ww = solver.addWindow();
+            const OnBatchWindow win{solver, solver.addWindow()};
             double *P = poses + 7 * (size_t) pose_off[w], *E = ext + 7 * (size_t) w, *D = invdepth + lm_off[w], *TD = td + w;
             const int K = pose_off[w + 1] - pose_off[w], L = lm_off[w + 1] - lm_off[w];
-            for (int k = 0; k < K; k++) solver.addParameterBlock(ww, P + 7 * (size_t) k, 7, true);
-            solver.addParameterBlock(ww, E, 7, true);
-            for (int l = 0; l < L; l++) solver.addParameterBlock(ww, D + l, 1);
-            solver.addParameterBlock(ww, TD, 1);
-            if (ext_constant) solver.setParameterBlockConstant(ww, E);
-            if (td_constant) solver.setParameterBlockConstant(ww, TD);
-            for (int f = fac_off[w]; f < fac_off[w + 1]; f++) {
-                factors.push_back(reproj_factor_from_soa(obs_soa, n, f));
-                solver.addReprojectionFactor(ww, factors.back().get(), P + 7 * (size_t) idx_i[f], P + 7 * (size_t) idx_j[f], E, D + idx_lm[f], TD);
-            }
-            for (int k = 0; k < K; k++)
-                solver.addResidualBlock(ww, std::make_shared<PosePriorFactor>(prior_poses + 7 * ((size_t) pose_off[w] + k), prior_weight), nullptr,
-                                        {P + 7 * (size_t) k});
+            visual_blocks(win, K, P, E, L, D, TD, ext_constant != 0, td_constant != 0);
+            reprojections_from_soa(obs_soa, n, fac_off[w], fac_off[w + 1], idx_i, idx_j, idx_lm, P, E, D, TD, factors, window_add(solver, win.w));
+            pose_priors(win, K, P, prior_poses + 7 * (size_t) pose_off[w], prior_weight);
         }
         if (!solver.prepare()) {
             set_err(err, errlen, solver.error().c_str());
@@ -148,14 +138,8 @@ int icgh_backend_solve_batch_parts(int W, const int32_t *fac_off, const int32_t 
             }
         }
         if (solve_ms) *solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        for (int w = 0; w < W; w++) {
-            double *o = summary8 + 8 * (size_t) w;
-            o[0] = s1[(size_t) w].initial_cost, o[1] = s1[(size_t) w].final_cost, o[2] = s1[(size_t) w].final_cost;
-            o[3] = s1[(size_t) w].num_successful_steps, o[4] = s1[(size_t) w].num_unsuccessful_steps, o[5] = o[6] = o[7] = 0;
-            if (chi2 > 0)
-                o[2] = s2[(size_t) w].final_cost, o[5] = s2[(size_t) w].num_successful_steps, o[6] = s2[(size_t) w].num_unsuccessful_steps,
-                o[7] = removed[(size_t) w];
-        }
+        for (int w = 0; w < W; w++)
+            put_summary8(s1[(size_t) w], chi2 > 0 ? &s2[(size_t) w] : nullptr, removed[(size_t) w], summary8 + 8 * (size_t) w);
         return 0;
     });
 }
@@ -188,26 +172,11 @@ int icgh_backend_solve_vio_batch(int W, const int32_t *n_intervals, const int32_
         }
         auto params = preint_params(params9);
         TempCtx T(0);
-        vector<vector<double>> pose((size_t) W), mix((size_t) W);
         vector<std::unique_ptr<ReprojectionFactor>> factors;
-        vector<vector<std::shared_ptr<Preintegration>>> pre((size_t) W);
+        vector<VioWindow> wins;
         vector<Preintegration *> raw;
-        for (int w = 0; w < W; w++) {
-            const int K = n_intervals[w] + 1;
-            pose[(size_t) w].resize((size_t) K * 7), mix[(size_t) w].resize((size_t) K * 9);
-            for (int k = 0; k < K; k++) {
-                memcpy(&pose[(size_t) w][7 * (size_t) k], states16[w] + 16 * (size_t) k, sizeof(double) * 7);
-                memcpy(&mix[(size_t) w][9 * (size_t) k], states16[w] + 16 * (size_t) k + 7, sizeof(double) * 9);
-            }
-            // preintegration of every interval from its start state: one icg_preint_batch launch for all windows
-            for (int k = 0; k < n_intervals[w]; k++) {
-                auto p = std::make_shared<Preintegration>(params, ins_imu(imu[w] + 8 * (size_t) offsets[w][k]), preint_state(states16[w] + 16 * (size_t) k),
-                                                          Preintegration::NORMAL);
-                for (int row = offsets[w][k] + 1; row < offsets[w][k + 1]; row++) p->addNewImu(ins_imu(imu[w] + 8 * (size_t) row));
-                pre[(size_t) w].push_back(p);
-                raw.push_back(p.get());
-            }
-        }
+        // preintegration of every interval from its start state: one icg_preint_batch launch for all windows
+        for (int w = 0; w < W; w++) wins.push_back(vio_window(n_intervals[w], offsets[w], imu[w], params, states16[w], raw));
         std::string e;
         if (!Preintegration::integrateBatch(T.ctx, raw, &e)) {
             set_err(err, errlen, e.c_str());
@@ -217,31 +186,17 @@ int icgh_backend_solve_vio_batch(int W, const int32_t *n_intervals, const int32_
         solver.setDeviceReducedSolve(mode >= 1);
         solver.setDeviceHostPart(mode == 2);
         for (int w = 0; w < W; w++) {
-            const int ww = solver.addWindow(), K = n_intervals[w] + 1;
-            double *P = pose[(size_t) w].data(), *M = mix[(size_t) w].data();
-            for (int k = 0; k < K; k++) {
-                solver.addParameterBlock(ww, P + 7 * (size_t) k, 7, true);
-                solver.addParameterBlock(ww, M + 9 * (size_t) k, 9);
-            }
-            solver.addParameterBlock(ww, ext[w], 7, true);
-            for (int l = 0; l < n_lm[w]; l++) solver.addParameterBlock(ww, invdepth[w] + l, 1);
-            solver.addParameterBlock(ww, td + w, 1);
-            solver.setParameterBlockConstant(ww, ext[w]);
-            solver.setParameterBlockConstant(ww, td + w);
-            for (int f = 0; f < n_fac[w]; f++) {
-                factors.push_back(reproj_factor_from_soa(obs_soa[w], n_fac[w], f));
-                solver.addReprojectionFactor(ww, factors.back().get(), P + 7 * (size_t) idx_i[w][f], P + 7 * (size_t) idx_j[w][f], ext[w],
-                                             invdepth[w] + idx_lm[w][f], td + w);
-            }
-            for (int k = 0; k + 1 < K; k++)
-                solver.addResidualBlock(ww, std::make_shared<PreintegrationFactor>(pre[(size_t) w][(size_t) k]), nullptr,
-                                        {P + 7 * (size_t) k, M + 9 * (size_t) k, P + 7 * (size_t) (k + 1), M + 9 * (size_t) (k + 1)});
-            solver.addResidualBlock(ww, std::make_shared<PosePriorFactor>(prior_pose0[w], prior_weight), nullptr, {P});
-            solver.addResidualBlock(ww, std::make_shared<MixPriorFactor>(prior_mix0[w], prior_weight), nullptr, {M});
+            const OnBatchWindow win{solver, solver.addWindow()};
+            VioWindow &V = wins[(size_t) w];
+            vio_blocks(win, V, ext[w], n_lm[w], invdepth[w], td + w);
+            reprojections_from_soa(obs_soa[w], n_fac[w], 0, n_fac[w], idx_i[w], idx_j[w], idx_lm[w], V.pose.data(), ext[w], invdepth[w], td + w, factors,
+                                   window_add(solver, win.w));
+            vio_motion_factors(win, V, prior_pose0[w], prior_weight);
+            vio_mix_prior(win, V, prior_mix0[w], prior_weight);
             if (dense && dense[w]) {
                 vector<double *> blocks;
-                for (int k = 0; k < K; k++) blocks.push_back(M + 9 * (size_t) k);
-                solver.addResidualBlock(ww, std::make_shared<DenseLinearFactor>(K, blocks.data(), dense_weight, dense_seed + (uint32_t) w), nullptr, blocks);
+                for (int k = 0; k < V.K; k++) blocks.push_back(&V.mix[9 * (size_t) k]);
+                win.addResidualBlock(std::make_shared<DenseLinearFactor>(V.K, blocks.data(), dense_weight, dense_seed + (uint32_t) w), nullptr, blocks);
             }
         }
         if (!solver.prepare()) {
@@ -258,13 +213,8 @@ int icgh_backend_solve_vio_batch(int W, const int32_t *n_intervals, const int32_
         }
         if (solve_ms) *solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         for (int w = 0; w < W; w++) {
-            double *o = summary4 + 4 * (size_t) w;
-            o[0] = sum[(size_t) w].initial_cost, o[1] = sum[(size_t) w].final_cost, o[2] = sum[(size_t) w].num_successful_steps,
-            o[3] = sum[(size_t) w].num_unsuccessful_steps;
-            for (int k = 0; k <= n_intervals[w]; k++) {
-                memcpy(states16[w] + 16 * (size_t) k, &pose[(size_t) w][7 * (size_t) k], sizeof(double) * 7);
-                memcpy(states16[w] + 16 * (size_t) k + 7, &mix[(size_t) w][9 * (size_t) k], sizeof(double) * 9);
-            }
+            put_summary4(sum[(size_t) w], summary4 + 4 * (size_t) w);
+            wins[(size_t) w].put(states16[w]);
         }
         return 0;
     });

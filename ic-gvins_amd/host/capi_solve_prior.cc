@@ -6,7 +6,7 @@
 
 #include "factors.h"
 #include "solver_batch_hip.h"
-#include "capi_util.h"
+#include "capi_windows.h"
 
 using namespace icg;
 
@@ -86,25 +86,10 @@ int icgh_backend_solve_prior_batch(int W, const int32_t *n_intervals, const int3
         }
         auto params = preint_params(params9);
         TempCtx T(0);
-        vector<vector<double>> pose((size_t) W), mix((size_t) W);
         vector<std::unique_ptr<ReprojectionFactor>> factors;
-        vector<vector<std::shared_ptr<Preintegration>>> pre((size_t) W);
+        vector<VioWindow> wins;
         vector<Preintegration *> raw;
-        for (int w = 0; w < W; w++) {
-            const int K = n_intervals[w] + 1;
-            pose[(size_t) w].resize((size_t) K * 7), mix[(size_t) w].resize((size_t) K * 9);
-            for (int k = 0; k < K; k++) {
-                memcpy(&pose[(size_t) w][7 * (size_t) k], states16[w] + 16 * (size_t) k, sizeof(double) * 7);
-                memcpy(&mix[(size_t) w][9 * (size_t) k], states16[w] + 16 * (size_t) k + 7, sizeof(double) * 9);
-            }
-            for (int k = 0; k < n_intervals[w]; k++) {
-                auto p = std::make_shared<Preintegration>(params, ins_imu(imu[w] + 8 * (size_t) offsets[w][k]), preint_state(states16[w] + 16 * (size_t) k),
-                                                          Preintegration::NORMAL);
-                for (int row = offsets[w][k] + 1; row < offsets[w][k + 1]; row++) p->addNewImu(ins_imu(imu[w] + 8 * (size_t) row));
-                pre[(size_t) w].push_back(p);
-                raw.push_back(p.get());
-            }
-        }
+        for (int w = 0; w < W; w++) wins.push_back(vio_window(n_intervals[w], offsets[w], imu[w], params, states16[w], raw));
         std::string e;
         if (!Preintegration::integrateBatch(T.ctx, raw, &e)) {
             set_err(err, errlen, e.c_str());
@@ -116,28 +101,16 @@ int icgh_backend_solve_prior_batch(int W, const int32_t *n_intervals, const int3
         solver.setDevicePrior(mode == 3);
         vector<int> prior_id((size_t) W, -1);
         for (int w = 0; w < W; w++) {
-            const int ww = solver.addWindow(), K = n_intervals[w] + 1;
-            double *P = pose[(size_t) w].data(), *M = mix[(size_t) w].data();
-            for (int k = 0; k < K; k++) {
-                solver.addParameterBlock(ww, P + 7 * (size_t) k, 7, true);
-                solver.addParameterBlock(ww, M + 9 * (size_t) k, 9);
-            }
-            solver.addParameterBlock(ww, ext[w], 7, true);
-            for (int l = 0; l < n_lm[w]; l++) solver.addParameterBlock(ww, invdepth[w] + l, 1);
-            solver.addParameterBlock(ww, td + w, 1);
-            solver.setParameterBlockConstant(ww, ext[w]);
-            solver.setParameterBlockConstant(ww, td + w);
+            const OnBatchWindow win{solver, solver.addWindow()};
+            VioWindow &V = wins[(size_t) w];
+            const int K  = V.K;
+            double *P = V.pose.data(), *M = V.mix.data();
+            vio_blocks(win, V, ext[w], n_lm[w], invdepth[w], td + w);
             for (int k = 0; state_const && state_const[w] && k < K; k++)
-                if (state_const[w][k]) solver.setParameterBlockConstant(ww, P + 7 * (size_t) k), solver.setParameterBlockConstant(ww, M + 9 * (size_t) k);
-            for (int f = 0; f < n_fac[w]; f++) {
-                factors.push_back(reproj_factor_from_soa(obs_soa[w], n_fac[w], f));
-                solver.addReprojectionFactor(ww, factors.back().get(), P + 7 * (size_t) idx_i[w][f], P + 7 * (size_t) idx_j[w][f], ext[w],
-                                             invdepth[w] + idx_lm[w][f], td + w);
-            }
-            for (int k = 0; k + 1 < K; k++)
-                solver.addResidualBlock(ww, std::make_shared<PreintegrationFactor>(pre[(size_t) w][(size_t) k]), nullptr,
-                                        {P + 7 * (size_t) k, M + 9 * (size_t) k, P + 7 * (size_t) (k + 1), M + 9 * (size_t) (k + 1)});
-            solver.addResidualBlock(ww, std::make_shared<PosePriorFactor>(prior_pose0[w], prior_weight), nullptr, {P});
+                if (state_const[w][k]) win.setParameterBlockConstant(P + 7 * (size_t) k), win.setParameterBlockConstant(M + 9 * (size_t) k);
+            reprojections_from_soa(obs_soa[w], n_fac[w], 0, n_fac[w], idx_i[w], idx_j[w], idx_lm[w], P, ext[w], invdepth[w], td + w, factors,
+                                   window_add(solver, win.w));
+            vio_motion_factors(win, V, prior_pose0[w], prior_weight);
             if (prior_r && prior_r[w] > 0) {
                 // (between the two ordinary priors: a resident prior is not the window's last host block)
                 vector<double *> blocks;
@@ -151,10 +124,10 @@ int icgh_backend_solve_prior_batch(int W, const int32_t *n_intervals, const int3
                 }
                 std::shared_ptr<ceres::LossFunction> loss;
                 if (prior_robust && prior_robust[w] != 0) loss = std::make_shared<HuberLossHip>(prior_robust[w]);
-                prior_id[(size_t) w] = solver.addResidualBlock(
-                    ww, std::make_shared<ArrayPriorFactor>(prior_r[w], prior_nb[w], prior_size[w], prior_index[w], prior_x0[w], prior_J0[w], prior_e0[w]), loss, blocks);
+                prior_id[(size_t) w] = win.addResidualBlock(
+                    std::make_shared<ArrayPriorFactor>(prior_r[w], prior_nb[w], prior_size[w], prior_index[w], prior_x0[w], prior_J0[w], prior_e0[w]), loss, blocks);
             }
-            solver.addResidualBlock(ww, std::make_shared<MixPriorFactor>(prior_mix0[w], prior_weight), nullptr, {M});
+            vio_mix_prior(win, V, prior_mix0[w], prior_weight);
         }
         auto prior_costs = [&](int at) {
             for (int w = 0; w < W && prior_cost; w++) {
@@ -181,13 +154,8 @@ int icgh_backend_solve_prior_batch(int W, const int32_t *n_intervals, const int3
             return -5;
         }
         for (int w = 0; w < W; w++) {
-            double *o = summary4 + 4 * (size_t) w;
-            o[0] = sum[(size_t) w].initial_cost, o[1] = sum[(size_t) w].final_cost, o[2] = sum[(size_t) w].num_successful_steps,
-            o[3] = sum[(size_t) w].num_unsuccessful_steps;
-            for (int k = 0; k <= n_intervals[w]; k++) {
-                memcpy(states16[w] + 16 * (size_t) k, &pose[(size_t) w][7 * (size_t) k], sizeof(double) * 7);
-                memcpy(states16[w] + 16 * (size_t) k + 7, &mix[(size_t) w][9 * (size_t) k], sizeof(double) * 9);
-            }
+            put_summary4(sum[(size_t) w], summary4 + 4 * (size_t) w);
+            wins[(size_t) w].put(states16[w]);
         }
         return 0;
     });

@@ -120,6 +120,15 @@ std::shared_ptr<icg::IntegrationParameters> preint_params(const double *params9)
     P->iewn         = icg::Vector3d(params9[6], params9[7], params9[8]);
     return P;
 }
+// interval k of the imu rows (it owns rows [offsets[k], offsets[k+1])) as a Preintegration object from its start state, a row of 16: the first
+// sample in the constructor, the rest through addNewImu.  variant: 0 = NORMAL, otherwise EARTH
+std::shared_ptr<icg::Preintegration> preint_interval(int variant, const std::shared_ptr<icg::IntegrationParameters> &params, const int32_t *offsets,
+                                                     const double *imu, int k, const double *state16) {
+    auto p = std::make_shared<icg::Preintegration>(params, ins_imu(imu + 8 * (size_t) offsets[k]), preint_state(state16),
+                                                   variant ? icg::Preintegration::EARTH : icg::Preintegration::NORMAL);
+    for (int row = offsets[k] + 1; row < offsets[k + 1]; row++) p->addNewImu(ins_imu(imu + 8 * (size_t) row));
+    return p;
+}
 // factor k of the 15 x n observation table (column c of factor k at obs_soa[c * n + k])
 std::unique_ptr<icg::ReprojectionFactor> reproj_factor_from_soa(const double *obs_soa, int n, int k) {
     using icg::Vector3d;

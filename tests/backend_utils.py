@@ -41,12 +41,19 @@ def check_reproj_costfunction_surface(lib, oracle):
     assert np.abs(J - J_exp).max() < 1e-9 * max(1, np.abs(J_exp).max())
 
 
-def backend_marginalize(lib, P, huber=1.0, prior_weight=100.0, x_eval=None):
+def marg_problem_args(P, huber, prior_weight):
+    """the arguments n .. prior_weight of the marginalization entries (icgh_backend_marginalize, icgh_backend_marginalize_batch,
+    icgh_backend_marg_handoff) for problem P (marg_data.make_problem) -> (args, K poses, L landmarks); every pointer keeps its array alive"""
     w = P["w"]
-    obs = _f64(P["obs"])
-    n = obs.shape[1]
-    poses, inv = _f64(w["poses"]), _f64(w["invdepth"])
+    obs, poses, inv = _f64(P["obs"]), _f64(w["poses"]), _f64(w["invdepth"])
     K, L = poses.shape[0], inv.shape[0]
+    args = [obs.shape[1], _p(obs), _p(_i32(P["ii"])), _p(_i32(P["jj"])), _p(_i32(P["ll"])), K, _p(poses), _p(_f64(w["ext"])), L, _p(inv),
+            C.c_double(w["td"]), C.c_double(huber), C.c_double(prior_weight)]
+    return args, K, L
+
+
+def backend_marginalize(lib, P, huber=1.0, prior_weight=100.0, x_eval=None):
+    args, K, L = marg_problem_args(P, huber, prior_weight)
     cap = 6 * K + L + 7
     sizes = np.zeros(2, np.int32)
     rem_ids, rem_index, rem_size = np.zeros(K + L + 2, np.int64), np.zeros(K + L + 2, np.int32), np.zeros(K + L + 2, np.int32)
@@ -55,9 +62,7 @@ def backend_marginalize(lib, P, huber=1.0, prior_weight=100.0, x_eval=None):
     res = np.zeros(cap)
     err = C.create_string_buffer(512)
     xe = None if x_eval is None else _f64(x_eval)
-    rc = lib.icgh_backend_marginalize(n, _p(obs), _p(_i32(P["ii"])), _p(_i32(P["jj"])), _p(_i32(P["ll"])), K, _p(poses), _p(_f64(w["ext"])), L,
-                                      _p(inv), C.c_double(w["td"]), C.c_double(huber), C.c_double(prior_weight), 1, 1, _p(sizes),
-                                      _p(rem_ids), _p(rem_index), _p(rem_size), _p(n_rem), _p(Hp), _p(bp), _p(J0), _p(e0), _p(xe),
+    rc = lib.icgh_backend_marginalize(*args, 1, 1, _p(sizes), _p(rem_ids), _p(rem_index), _p(rem_size), _p(n_rem), _p(Hp), _p(bp), _p(J0), _p(e0), _p(xe),
                                       _p(res) if xe is not None else None, err, 512)
     assert rc == 0, (rc, err.value)
     m, r = int(sizes[0]), int(sizes[1])
@@ -108,7 +113,8 @@ def oracle_marginalized_system(oracle, P, w, out, huber=1.0, prior_weight=100.0,
 
 def batch_window_parameters(P, n_windows, jitter=1e-3):
     """the parameter values icgh_backend_marginalize_batch (capi_marg.cc) gives its n_windows copies of problem P: window 0 as it is, every
-    further window with positions moved by jitter * u and inverse depths scaled by 1 + jitter * u, u from the 64-bit LCG of capi_marg.cc"""
+    further window with positions moved by jitter * u and inverse depths scaled by 1 + jitter * u, u from the 64-bit LCG of capi_windows.h
+    (Uniform, seeded as marg_windows seeds it)"""
     state, mask = [0x9E3779B97F4A7C15], (1 << 64) - 1
 
     def rnd():
@@ -272,19 +278,13 @@ def backend_marginalize_batch(lib, P, n_windows, mode, dense_window=-1, jitter=1
     """icgh_backend_marginalize_batch (capi_marg.cc): the marginalizations of n_windows jittered copies of problem P, mode 0 = one
     MarginalizationBatch, mode 1 = one MarginalizationInfo::marginalization() after the other; reps: the set is marginalized that many times on
     the same batch object (seconds = the fastest repetition, outputs of the last)."""
-    w = P["w"]
-    obs = _f64(P["obs"])
-    n = obs.shape[1]
-    poses, inv = _f64(w["poses"]), _f64(w["invdepth"])
-    K, L = poses.shape[0], inv.shape[0]
+    args, K, L = marg_problem_args(P, huber, prior_weight)
     cap = 6 * K + L + 7
     sizes, counts, seconds = np.zeros(2, np.int32), np.zeros(2, np.int32), np.zeros(1)
     Hp, bp, J0, e0 = (np.zeros(n_windows * cap * cap), np.zeros(n_windows * cap), np.zeros(n_windows * cap * cap), np.zeros(n_windows * cap))
     err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_marginalize_batch(mode, n_windows, dense_window, C.c_double(jitter), reps, n, _p(obs), _p(_i32(P["ii"])), _p(_i32(P["jj"])),
-                                            _p(_i32(P["ll"])), K, _p(poses), _p(_f64(w["ext"])), L, _p(inv), C.c_double(w["td"]),
-                                            C.c_double(huber), C.c_double(prior_weight), host_threads, _p(sizes), _p(Hp), _p(bp), _p(J0), _p(e0),
-                                            _p(counts), _p(seconds), err, 512)
+    rc = lib.icgh_backend_marginalize_batch(mode, n_windows, dense_window, C.c_double(jitter), reps, *args, host_threads, _p(sizes), _p(Hp), _p(bp), _p(J0),
+                                            _p(e0), _p(counts), _p(seconds), err, 512)
     assert rc == 0, (rc, err.value)
     r = int(sizes[1])
     W = n_windows

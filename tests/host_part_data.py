@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from preint_data import PARAMS
+from vio_data import batch_leading_args
 
 P_BATCH = 157
 
@@ -110,26 +110,14 @@ def restate(P, win):
     return np.array([v for row in part for v in row], np.float64), np.array(s, np.float64), np.array(dg, np.float64)
 
 
-def _ptrs(arrays):
-    return (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
-
-
 def solve_vio_batch(lib, wins, starts, dense, mode, iters=25, prior_weight=100.0, huber=1.0, dense_weight=1.0, dense_seed=7, timer=None):
     """icgh_backend_solve_vio_batch on vio_data windows from the given (states, invdepth) starts -> (rc, message, states, invdepth, summary W x 4);
     a list given as timer receives the entry's own time of the solve in ms"""
-    W = len(wins)
-    i32, f64 = (lambda a: np.ascontiguousarray(a, np.int32)), (lambda a: np.ascontiguousarray(a, np.float64))
-    st, inv = [f64(s).copy() for s, _ in starts], [f64(v).copy() for _, v in starts]
-    offsets, imu = [i32(w["offsets"]) for w in wins], [f64(w["imu"]) for w in wins]
-    obs, ii, jj, ll = ([f64(w["obs"]) for w in wins], [i32(w["ii"]) for w in wins], [i32(w["jj"]) for w in wins], [i32(w["ll"]) for w in wins])
-    ext, td = [f64(w["ext"]).copy() for w in wins], f64([w["td"] for w in wins])
-    pose0, mix0 = [f64(w["states"][0, :7]) for w in wins], [f64(w["states"][0, 7:]) for w in wins]
-    n_int, n_fac, n_lm = i32([len(o) - 1 for o in offsets]), i32([o.shape[1] for o in obs]), i32([len(v) for v in inv])
-    summ, ms, err = np.zeros((W, 4)), C.c_double(0), C.create_string_buffer(512)
+    args, st, inv, keep = batch_leading_args(wins, starts, iters, prior_weight, huber)
+    summ, ms, err = np.zeros((len(wins), 4)), C.c_double(0), C.create_string_buffer(512)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    rc = lib.icgh_backend_solve_vio_batch(W, p(n_int), _ptrs(offsets), _ptrs(imu), p(f64(PARAMS)), _ptrs(st), p(n_fac), _ptrs(obs), _ptrs(ii), _ptrs(jj), _ptrs(ll),
-                                          _ptrs(ext), p(n_lm), _ptrs(inv), p(td), _ptrs(pose0), _ptrs(mix0), C.c_double(prior_weight), C.c_double(huber), int(iters),
-                                          p(i32(dense)), C.c_double(dense_weight), C.c_uint32(dense_seed), p(summ), C.byref(ms), int(mode), err, 512)
+    rc = lib.icgh_backend_solve_vio_batch(*args, p(np.ascontiguousarray(dense, np.int32)), C.c_double(dense_weight), C.c_uint32(dense_seed), p(summ), C.byref(ms),
+                                          int(mode), err, 512)
     if timer is not None:
         timer.append(ms.value)
     return rc, err.value.decode(), st, inv, summ

@@ -81,11 +81,13 @@ def dq_w(prior, x):
 
 
 def batch():
-    """the heterogeneous batch of the tests, in this order: C2, C4, scenario, r = 1, r = 512, out of column order with a gap, non-unit x0.
-    Returns (priors, points); in every prior with at least two 7-blocks, two of them take the dq.w < 0 branch."""
+    """the heterogeneous batch of the tests, in this order: C2, C4, scenario, r = 1, r = 512, out of column order with a gap, non-unit x0,
+    r = 32 and r = 33 (the set's store kernel transposes J0 in 32 x 32 tiles: exactly one tile, and one tile with a row and a column of
+    slivers).  Returns (priors, points); in every prior with at least two 7-blocks, two of them take the dq.w < 0 branch."""
     priors = [make_prior(C2_SIZES, 11), make_prior(C4_SIZES, 12), make_prior(SCENARIO_SIZES, 13), make_prior([1], 14),
               make_prior(R512_SIZES, 15), make_prior([7, 3, 1, 9, 7], 16, order=[3, 0, 4, 1, 2], gap_after=1, gap=4),
-              make_prior([7, 9, 7, 1], 17, quat_scale=1.01)]
+              make_prior([7, 9, 7, 1], 17, quat_scale=1.01), make_prior([9, 9, 9, 1, 1, 1, 1, 1], 18), make_prior([9, 9, 9, 3, 3], 19)]
+    assert [p["r"] for p in priors[7:]] == [32, 33]
     points = [make_x(p, 100 + k, negate=(0, 1)) for k, p in enumerate(priors)]
     return priors, points
 

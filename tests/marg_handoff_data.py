@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 import marg_factor_data as mf
+from backend_utils import marg_problem_args
 import marg_linearize_data as ml
 
 # (P, m) of the kept batch: r = 1, 6, 61, 142 (the last size whose working matrix fits LDS) and 143 (the first on global scratch), a
@@ -54,21 +55,16 @@ def backend_marg_handoff(lib, P, n_windows, mode, dense_window=-1, jitter=1e-3, 
                          solve_iters=0):
     """icgh_backend_marg_handoff (capi_marg_handoff.cc) on n_windows jittered copies of problem P (marg_data.make_problem).  mode 0: the
     priors are shipped, 1: kept and handed off, 3: kept, released before the set.  Returns (rc, message, dict of outputs)."""
-    w = P["w"]
-    f64 = lambda a: np.ascontiguousarray(a, np.float64)
-    i32 = lambda a: np.ascontiguousarray(a, np.int32)
-    obs, poses, inv = f64(P["obs"]), f64(w["poses"]), f64(w["invdepth"])
-    n, K, L = obs.shape[1], poses.shape[0], inv.shape[0]
+    args, K, L = marg_problem_args(P, huber, prior_weight)
     cap = 6 * K + L + 7
     counts, timers = np.zeros(7, np.int32), np.zeros(5)
     res, grad = np.zeros(n_windows * cap), np.zeros(n_windows * cap)
     sq, sq_res = np.zeros(n_windows), np.zeros(n_windows)
     states, inv_out, summ = np.zeros((n_windows, K, 7)), np.zeros((n_windows, L)), np.zeros((n_windows, 4))
     err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_marg_handoff(int(mode), int(n_windows), int(dense_window), C.c_double(jitter), n, _p(obs), _p(i32(P["ii"])), _p(i32(P["jj"])),
-                                       _p(i32(P["ll"])), K, _p(poses), _p(f64(w["ext"])), L, _p(inv), C.c_double(w["td"]), C.c_double(huber),
-                                       C.c_double(prior_weight), int(host_threads), C.c_uint64(seed), C.c_double(perturb), int(solve_iters), _p(counts),
-                                       _p(res), _p(grad), _p(sq), _p(sq_res), _p(states), _p(inv_out), _p(summ), _p(timers), err, 512)
+    rc = lib.icgh_backend_marg_handoff(int(mode), int(n_windows), int(dense_window), C.c_double(jitter), *args, int(host_threads), C.c_uint64(seed),
+                                       C.c_double(perturb), int(solve_iters), _p(counts), _p(res), _p(grad), _p(sq), _p(sq_res), _p(states), _p(inv_out), _p(summ),
+                                       _p(timers), err, 512)
     g, R = int(counts[0]), int(counts[1])
     out = dict(priors=g, residuals=res[:R], gradient=grad[:R], sq_norm=sq[:g], sq_norm_resident=sq_res[:g], handed_off=int(counts[2]), tagged=int(counts[3]),
                structured=int(counts[4]), dense=int(counts[5]), solver_handed_off=int(counts[6]), states=states[:g], invdepth=inv_out[:g], summary=summ[:g],

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from preint_data import PARAMS
+from vio_data import _ptrs, batch_leading_args
 
 
 def bits(a):
@@ -48,22 +48,13 @@ def prior_cost(prior, states):
     return 0.5 * float(e @ e)
 
 
-def _ptrs(arrays):
-    return (C.c_void_p * len(arrays))(*[a.ctypes.data if a is not None else None for a in arrays])
-
-
 def solve_prior_batch(lib, wins, starts, priors, mode, state_const=None, robust=None, iters=25, prior_weight=100.0, huber=1.0, timer=None):
     """icgh_backend_solve_prior_batch on vio_data windows from the given (states, invdepth) starts; priors[w]: make_prior's dict or None;
     state_const[w]: flags per state or None; robust[w]: the Huber delta of the prior's loss, 0 = none
     -> (rc, message, states, invdepth, summary W x 4, prior cost W x 2)"""
     W = len(wins)
     i32, f64 = (lambda a: np.ascontiguousarray(a, np.int32)), (lambda a: np.ascontiguousarray(a, np.float64))
-    st, inv = [f64(s).copy() for s, _ in starts], [f64(v).copy() for _, v in starts]
-    offsets, imu = [i32(w["offsets"]) for w in wins], [f64(w["imu"]) for w in wins]
-    obs, ii, jj, ll = ([f64(w["obs"]) for w in wins], [i32(w["ii"]) for w in wins], [i32(w["jj"]) for w in wins], [i32(w["ll"]) for w in wins])
-    ext, td = [f64(w["ext"]).copy() for w in wins], f64([w["td"] for w in wins])
-    pose0, mix0 = [f64(w["states"][0, :7]) for w in wins], [f64(w["states"][0, 7:]) for w in wins]
-    n_int, n_fac, n_lm = i32([len(o) - 1 for o in offsets]), i32([o.shape[1] for o in obs]), i32([len(v) for v in inv])
+    args, st, inv, keep = batch_leading_args(wins, starts, iters, prior_weight, huber)
     pr = lambda key, conv: [None if p is None else conv(p[key]) for p in priors]
     p_r, p_nb = i32([0 if p is None else p["r"] for p in priors]), i32([0 if p is None else len(p["size"]) for p in priors])
     p_size, p_index, p_param, p_x0, p_J0, p_e0 = pr("size", i32), pr("index", i32), pr("param", i32), pr("x0", f64), pr("J0", f64), pr("e0", f64)
@@ -71,10 +62,8 @@ def solve_prior_batch(lib, wins, starts, priors, mode, state_const=None, robust=
     sc = [None] * W if state_const is None else [None if c is None else i32(c) for c in state_const]
     summ, pcost, ms, err = np.zeros((W, 4)), np.zeros((W, 2)), C.c_double(0), C.create_string_buffer(512)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
-    rc = lib.icgh_backend_solve_prior_batch(W, p(n_int), _ptrs(offsets), _ptrs(imu), p(f64(PARAMS)), _ptrs(st), p(n_fac), _ptrs(obs), _ptrs(ii), _ptrs(jj), _ptrs(ll),
-                                            _ptrs(ext), p(n_lm), _ptrs(inv), p(td), _ptrs(pose0), _ptrs(mix0), C.c_double(prior_weight), C.c_double(huber), int(iters),
-                                            p(p_r), p(p_nb), _ptrs(p_size), _ptrs(p_index), _ptrs(p_param), _ptrs(p_x0), _ptrs(p_J0), _ptrs(p_e0), p(rob), _ptrs(sc),
-                                            p(summ), p(pcost), C.byref(ms), int(mode), err, 512)
+    rc = lib.icgh_backend_solve_prior_batch(*args, p(p_r), p(p_nb), _ptrs(p_size), _ptrs(p_index), _ptrs(p_param), _ptrs(p_x0), _ptrs(p_J0), _ptrs(p_e0), p(rob),
+                                            _ptrs(sc), p(summ), p(pcost), C.byref(ms), int(mode), err, 512)
     if timer is not None:
         timer.append(ms.value)
     return rc, err.value.decode(), st, inv, summ, pcost

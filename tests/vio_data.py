@@ -12,6 +12,26 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _ptrs(arrays):
+    return (C.c_void_p * len(arrays))(*[None if a is None else a.ctypes.data for a in arrays])
+
+
+def batch_leading_args(wins, starts, iters, prior_weight, huber):
+    """The arguments W .. iters that icgh_backend_solve_vio_batch and icgh_backend_solve_prior_batch share, for windows of make_vio_window from the
+    given (states, invdepth) starts -> (args, states, invdepth, keep): states / invdepth are the copies the entry updates in place; keep holds
+    every array a pointer table in args names and has to live until the call returns"""
+    i32, f64 = (lambda a: np.ascontiguousarray(a, np.int32)), (lambda a: np.ascontiguousarray(a, np.float64))
+    st, inv = [f64(s).copy() for s, _ in starts], [f64(v).copy() for _, v in starts]
+    offsets, imu = [i32(w["offsets"]) for w in wins], [f64(w["imu"]) for w in wins]
+    obs, ii, jj, ll = ([f64(w["obs"]) for w in wins], [i32(w["ii"]) for w in wins], [i32(w["jj"]) for w in wins], [i32(w["ll"]) for w in wins])
+    ext, td = [f64(w["ext"]).copy() for w in wins], f64([w["td"] for w in wins])
+    pose0, mix0 = [f64(w["states"][0, :7]) for w in wins], [f64(w["states"][0, 7:]) for w in wins]
+    n_int, n_fac, n_lm = i32([len(o) - 1 for o in offsets]), i32([o.shape[1] for o in obs]), i32([len(v) for v in inv])
+    args = [len(wins), _p(n_int), _ptrs(offsets), _ptrs(imu), _p(f64(pd.PARAMS)), _ptrs(st), _p(n_fac), _ptrs(obs), _ptrs(ii), _ptrs(jj), _ptrs(ll), _ptrs(ext),
+            _p(n_lm), _ptrs(inv), _p(td), _ptrs(pose0), _ptrs(mix0), C.c_double(prior_weight), C.c_double(huber), int(iters)]
+    return args, st, inv, [offsets, imu, obs, ii, jj, ll, ext, pose0, mix0]
+
+
 def make_vio_window(oracle, n_intervals=6, per=40, n_lm=120, seed=0, pixel_noise=0.3, f=787.0):
     rng = np.random.RandomState(seed)
     imu_all = pd.make_interval(n_intervals * per + 1, seed=seed, noise=True)
