@@ -172,6 +172,8 @@ struct icg_ctx {
     // M3 (marg_linearize.hip): per-window working memory of icg_marg_linearize_batch for the windows that do not fit in LDS; grows on demand
     double *d_lin_scratch = nullptr;
     size_t lin_scratch_cap = 0; // bytes
+    double *d_lin_H = nullptr;  // the systems icg_marg_linearize_resident forms from the resident halves below (sum Pw^2 doubles); grows on demand
+    size_t lin_H_cap = 0;       // bytes
     icg_lin_kept lin_kept;      // what icg_marg_linearize_batch_keep left for icg_marg_prior_set_from_kept
     // Reduced camera solve (chol.hip, reproj_schur.hip): the W x P x P reduced systems icg_reproj_schur_windows_resident leaves on the device, every
     // window's host-factor part (packed lower triangle, one slot of P (P + 1) / 2 doubles per window, kept until it is replaced) and the

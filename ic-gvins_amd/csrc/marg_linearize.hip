@@ -13,6 +13,13 @@
 // k_marg_linearize<true>.  A window that does not fit (C4: r = 217) runs the same code on a global scratch block (L2 / Infinity Cache
 // resident), d and e still in LDS: k_marg_linearize<false>.  Which of the two a window takes depends on its own (P, m) only, so its bits
 // are the same alone and in any batch.
+//
+// icg_marg_linearize_resident is the same M3 on systems that never left the device: M2 (factors/marginalization_info.h:195-230) is the sum of
+// the host-evaluated factors' J^T J and the landmark-eliminated visual part, and both halves are resident after
+// icg_reproj_host_parts_build (packed lower triangle `part`, ctx->d_red_H) and icg_reproj_schur_windows_resident (lower triangle of S, row
+// stride P, ctx->d_red_S).  k_marg_form_h writes, for every cell i >= j of a selected window,
+//     H[i][j] = H[j][i] = part[i (i + 1) / 2 + j] + S_w[i * P + j]        (part first, then S: the host's plan.H += S; no part: +0.0 + S)
+// into a buffer of the context, and k_marg_linearize (M3, :153-192) runs unchanged on that buffer.
 #include "icg_internal.h"
 
 #include <cmath>
@@ -384,19 +391,87 @@ __global__ __launch_bounds__(LIN_THREADS) void k_marg_linearize(int n_items, con
     }
 }
 
-// Both entries.  keep: J0 / e0 are written into the context's kept buffer (icg_lin_kept) instead of the arena's outgoing slots, which a
+// ---- the reduced systems formed where their halves lie (icg_marg_linearize_resident)
+#define FORM_TILE 32
+#define FORM_THREADS 256
+struct form_desc {
+    int32_t Pw, has_part;
+    int64_t S_off, part_off, h_off; // the window's S (row stride P) in d_red_S, its packed part in d_red_H, its H (Pw x Pw) in the formed buffer
+};
+
+// grid (tiles of the widest window's lower triangle, selected windows); a workgroup owns the 32 x 32 tile (ti, tj), tj <= ti, of one window.
+// The cells i >= j of the tile are summed and stored along their rows (part, S and H contiguous in j), kept in a padded LDS tile and stored
+// once more transposed, again along rows of H: both stores are contiguous.  The diagonal is written by the first store only.
+__global__ __launch_bounds__(FORM_THREADS) void k_marg_form_h(const form_desc *__restrict__ desc, int P, const double *__restrict__ S,
+                                                             const double *__restrict__ part, double *__restrict__ H) {
+    __shared__ double tile[FORM_TILE][FORM_TILE + 1];
+    const form_desc D = desc[blockIdx.y];
+    const int Pw = D.Pw, nt = (Pw + FORM_TILE - 1) / FORM_TILE, t = blockIdx.x;
+    if (t >= nt * (nt + 1) / 2) return; // (a narrower window than the widest of the call: uniform over the workgroup)
+    int ti = (int) ((sqrtf(8.0f * (float) t + 1.0f) - 1.0f) * 0.5f);
+    while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
+    while (ti * (ti + 1) / 2 > t) ti--;
+    const int tj = t - ti * (ti + 1) / 2;
+    const double *Sw = S + D.S_off, *pw = part + D.part_off;
+    double *Hw = H + D.h_off;
+    const int tx = threadIdx.x & (FORM_TILE - 1), ty = threadIdx.x / FORM_TILE; // 32 x 8
+    for (int y = ty; y < FORM_TILE; y += FORM_THREADS / FORM_TILE) {
+        const int i = ti * FORM_TILE + y, j = tj * FORM_TILE + tx;
+        if (i < Pw && j <= i) {
+            const double a = D.has_part ? pw[(size_t) i * (i + 1) / 2 + j] : 0.0;
+            const double v = a + Sw[(size_t) i * P + j];
+            Hw[(size_t) i * Pw + j] = v;
+            tile[y][tx]             = v;
+        }
+    }
+    __syncthreads();
+    for (int y = ty; y < FORM_TILE; y += FORM_THREADS / FORM_TILE) {
+        const int j = tj * FORM_TILE + y, i = ti * FORM_TILE + tx; // the cell (i, j), i > j, goes to H[j][i]
+        if (i < Pw && j < i) Hw[(size_t) j * Pw + i] = tile[tx][y];
+    }
+}
+
+// where icg_marg_linearize_resident takes its systems from: system k is window win[k] of the resident partition (common stride P)
+struct lin_resident {
+    int P;
+    const int32_t *win;
+    double *H_out; // optional: the formed systems, for tests and diagnostics
+};
+
+// All entries.  H comes from the caller (R == nullptr: uploaded with b) or is formed on the device from the resident halves (R); the
+// descriptors, the LDS / global-scratch split, the outputs and the keep logic are one path.
+// keep: J0 / e0 are written into the context's kept buffer (icg_lin_kept) instead of the arena's outgoing slots, which a
 // device-to-device copy then feeds where the host asked for them — the kernels and their launches are the same either way.
 int lin_batch(const char *fn, bool keep, icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
-              double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status, uint64_t *keep_id) {
+              double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status, uint64_t *keep_id,
+              const lin_resident *R = nullptr) {
     if (!ctx) return ICG_ERR_INVALID;
     icg_kept_drop(ctx); // whatever linearization the context kept is gone, also when this call fails
     if (keep && !keep_id) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", fn);
     if (keep) *keep_id = 0;
-    if (n_windows <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: n_windows = %d", fn, n_windows);
+    if (n_windows <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: %s = %d", fn, R ? "n_sel" : "n_windows", n_windows);
     if (n_windows > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %d windows in one call (at most 65535)", fn, n_windows);
-    if (!P || !m || !H || !b || (!keep && (!J0 || !e0))) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", fn);
+    if (!P || !m || (R ? !R->win : !H) || !b || (!keep && (!J0 || !e0))) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", fn);
     if (!(eps >= 0.0)) return icg_fail(ctx, ICG_ERR_INVALID, "%s: eps = %g", fn, eps);
     const size_t n = (size_t) n_windows;
+    if (R) {
+        const int W = ctx->part_w.W;
+        if (W <= 0 || !ctx->red_S_valid || ctx->red_W != W || ctx->red_P != R->P || R->P <= 0)
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: no resident reduced systems of %d columns: call icg_reproj_schur_windows_resident first", fn, R->P);
+        std::vector<char> listed((size_t) W, 0);
+        for (size_t k = 0; k < n; k++) {
+            const int w = R->win[k];
+            if (w < 0 || w >= W) return icg_fail(ctx, ICG_ERR_INVALID, "%s: position %zu: window %d outside the partition of %d", fn, k, w, W);
+            if (listed[(size_t) w]) return icg_fail(ctx, ICG_ERR_INVALID, "%s: position %zu: window %d is listed twice", fn, k, w);
+            listed[(size_t) w] = 1;
+            if (P[k] <= 0 || P[k] > R->P) return icg_fail(ctx, ICG_ERR_INVALID, "%s: position %zu, window %d: Pw = %d (1 .. %d)", fn, k, w, P[k], R->P);
+            const int have = (size_t) w < ctx->red_H_cols.size() ? ctx->red_H_cols[(size_t) w] : 0;
+            if (have != 0 && have != P[k])
+                return icg_fail(ctx, ICG_ERR_INVALID, "%s: position %zu, window %d: the resident host part has %d columns, not %d", fn, k, w, have, P[k]);
+            if (m[k] < 0 || m[k] >= P[k])
+                return icg_fail(ctx, ICG_ERR_INVALID, "%s: position %zu, window %d: m = %d (0 <= m < Pw = %d)", fn, k, w, m[k], P[k]);
+        }
+    }
     for (size_t w = 0; w < n; w++)
         if (P[w] <= 0 || m[w] < 0 || m[w] >= P[w])
             return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %zu: P = %d, m = %d (0 <= m < P)", fn, w, P[w], m[w]);
@@ -430,18 +505,28 @@ int lin_batch(const char *fn, bool keep, icg_ctx *ctx, int n_windows, const int3
     }
     int rc = icg_grow(ctx, (void **) &ctx->d_lin_scratch, &ctx->lin_scratch_cap, ts * sizeof(double), ts * sizeof(double));
     if (rc) return rc;
+    if (R && (rc = icg_grow(ctx, (void **) &ctx->d_lin_H, &ctx->lin_H_cap, th * sizeof(double), th * sizeof(double)))) return rc;
+    std::vector<form_desc> form(R ? n : 0);
+    int form_tiles = 0;
+    for (size_t k = 0; k < form.size(); k++) {
+        const size_t w = (size_t) R->win[k], slot = (size_t) R->P * (R->P + 1) / 2;
+        const int nt = (P[k] + FORM_TILE - 1) / FORM_TILE;
+        form[k]      = {P[k], w < ctx->red_H_cols.size() && ctx->red_H_cols[w] != 0 ? 1 : 0, (int64_t) (w * (size_t) R->P * R->P), (int64_t) (w * slot), desc[k].h_off};
+        form_tiles   = std::max(form_tiles, nt * (nt + 1) / 2);
+    }
     icg_lin_kept &K = ctx->lin_kept;
     if (keep && (rc = icg_grow(ctx, (void **) &K.d_buf, &K.cap, (trr + tr) * sizeof(double), (trr + tr) * sizeof(double)))) return rc;
     static icg_lds_grant granted;
     if ((rc = icg_allow_lds(ctx, reinterpret_cast<const void *>(k_marg_linearize<true>), lds_fast, lds_limit, granted))) return rc;
     icg_call c(ctx);
     const size_t out_doubles = 2 * trr + 3 * tr + n;
-    rc = c.reserve(sizeof(double) * (th + tb + out_doubles) + n * (sizeof(lin_desc) + 8) + 16 * 256);
+    rc = c.reserve(sizeof(double) * ((R && !R->H_out ? 0 : th) + tb + out_doubles) + n * (sizeof(lin_desc) + sizeof(form_desc) + 8) + 20 * 256);
     if (rc) return rc;
-    const double *d_H       = c.in(H, th);
+    const double *d_H       = R ? ctx->d_lin_H : c.in(H, th);
     const double *d_b       = c.in(b, tb);
     const lin_desc *d_desc  = c.in(desc.data(), n);
     const int32_t *d_items  = c.in(items.data(), n);
+    const form_desc *d_form = R ? c.in(form.data(), n) : nullptr;
     if ((rc = c.seal())) return rc;
     // (keep: the outgoing slots are still laid out — the arena offsets of the other outputs do not depend on the entry)
     double *a_J0 = c.out(J0, trr), *a_e0 = c.out(e0, tr);
@@ -451,7 +536,14 @@ int lin_batch(const char *fn, bool keep, icg_ctx *ctx, int n_windows, const int3
     double *d_ev  = evals ? c.out(evals, tr) : nullptr;
     double *d_min = min_ev_m ? c.out(min_ev_m, n) : nullptr;
     int32_t *d_st = status ? c.out(status, n) : nullptr;
+    double *a_H   = R && R->H_out ? c.out(R->H_out, th) : nullptr;
     ICG_LAUNCH_GUARD(c);
+    if (R) {
+        icg_prof_scope ps(ctx, "marg_form_h");
+        hipLaunchKernelGGL(k_marg_form_h, dim3((unsigned) form_tiles, (unsigned) n), dim3(FORM_THREADS), 0, ctx->stream, d_form, R->P, (const double *) ctx->d_red_S,
+                           (const double *) ctx->d_red_H, ctx->d_lin_H);
+    }
+    if (a_H) ICG_HIP(ctx, hipMemcpyAsync(a_H, ctx->d_lin_H, th * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     if (n_fast > 0) {
         icg_prof_scope ps(ctx, "marg_lin_lds");
         hipLaunchKernelGGL(k_marg_linearize<true>, dim3(n_fast), dim3(LIN_THREADS), lds_fast, ctx->stream, n_fast, d_items, d_desc, d_H, d_b, eps, d_Hp, d_bp,
@@ -488,4 +580,13 @@ extern "C" int icg_marg_linearize_batch_keep(icg_ctx *ctx, int n_windows, const 
                                              double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status,
                                              uint64_t *keep_id) {
     return lin_batch("icg_marg_linearize_batch_keep", true, ctx, n_windows, P, m, H, b, eps, Hp, bp, J0, e0, evals, min_ev_m, status, keep_id);
+}
+
+// M3 on the reduced systems the context holds (see the head of this file): system k is window win[k] of the resident partition, formed on the
+// device from its host-factor part and its S (M2, factors/marginalization_info.h:195-230), then linearized (:153-192) by the same kernels.
+extern "C" int icg_marg_linearize_resident(icg_ctx *ctx, int P, int n_sel, const int32_t *win, const int32_t *Pw, const int32_t *m, const double *b,
+                                           double eps, double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status,
+                                           double *H_out, uint64_t *keep_id) {
+    const lin_resident R{P, win, H_out};
+    return lin_batch("icg_marg_linearize_resident", keep_id != nullptr, ctx, n_sel, Pw, m, nullptr, b, eps, Hp, bp, J0, e0, evals, min_ev_m, status, keep_id, &R);
 }

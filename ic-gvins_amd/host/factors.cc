@@ -678,6 +678,12 @@ bool MarginalizationInfo::constructAndEliminateStructured() {
 }
 
 bool MarginalizationInfo::planStructured(StructuredPlan &plan) {
+    if (!planLayout(plan)) return false;
+    planAccumulate(plan);
+    return true;
+}
+
+bool MarginalizationInfo::planLayout(StructuredPlan &plan) {
     if (!batch_ || batch_->size() == 0) return false;
     // landmark blocks of the batch: all marginalized, size 1, and touched by batch factors only
     std::unordered_map<long, char> is_lm;
@@ -697,7 +703,8 @@ bool MarginalizationInfo::planStructured(StructuredPlan &plan) {
     }
     // compact camera columns: every non-landmark column of the local ordering, order kept (marginalized ones first)
     const int L = local_size_;
-    vector<int> compact((size_t) L, -1);
+    vector<int> &compact = plan.compact;
+    compact.assign((size_t) L, -1);
     {
         vector<char> lm_col((size_t) L, 0);
         for (const auto &kv : is_lm) lm_col[(size_t) parameter_block_index_[kv.first]] = 1;
@@ -709,17 +716,23 @@ bool MarginalizationInfo::planStructured(StructuredPlan &plan) {
     const int P = L - n_lm, m = marginalized_size_ - n_lm, r = remained_size_;
     if (m < 0 || P != m + r) return false;
     plan.P = P, plan.m = m, plan.r = r;
-    plan.H.assign((size_t) P * P, 0.0), plan.b.assign((size_t) P, 0.0);
     plan.camera_column_of.clear();
+    for (const auto &factor : factors_) {
+        if (!onBatch(factor, batch_)) continue;
+        for (double *p : factor->parameterBlocks())
+            if (!is_lm.count(idOf(p))) plan.camera_column_of[p] = compact[(size_t) parameter_block_index_[idOf(p)]];
+    }
+    return true;
+}
+
+void MarginalizationInfo::planAccumulate(StructuredPlan &plan) {
+    const int P = plan.P;
+    const vector<int> &compact = plan.compact;
+    plan.H.assign((size_t) P * P, 0.0), plan.b.assign((size_t) P, 0.0);
     vector<double> &H = plan.H, &b = plan.b;
-    std::unordered_map<const double *, int> &camera_column_of = plan.camera_column_of;
     for (const auto &factor : factors_) {
         const auto &blocks = factor->parameterBlocks();
-        if (onBatch(factor, batch_)) {
-            for (double *p : blocks)
-                if (!is_lm.count(idOf(p))) camera_column_of[p] = compact[(size_t) parameter_block_index_[idOf(p)]];
-            continue;
-        }
+        if (onBatch(factor, batch_)) continue;
         const int nr = (int) factor->residuals().size(); // host factors: J^T J / J^T e straight into the compact system (:195-230)
         for (size_t i = 0; i < blocks.size(); i++) {
             const int row0 = compact[(size_t) parameter_block_index_[idOf(blocks[i])]];
@@ -746,6 +759,59 @@ bool MarginalizationInfo::planStructured(StructuredPlan &plan) {
             }
         }
     }
+}
+
+bool MarginalizationInfo::gatherHostBlocks(const StructuredPlan &plan, HostFactorBlocks &out) {
+    size_t n_blocks = 0, n_J = 0, n_r = 0, n_c = 0;
+    for (const auto &factor : factors_) {
+        if (onBatch(factor, batch_)) continue;
+        const auto &blocks = factor->parameterBlocks();
+        const size_t nr    = factor->residuals().size();
+        if (nr > (size_t) ICG_HOST_PART_MAX_NR) return false;
+        size_t nf = 0;
+        for (size_t i = 0; i < blocks.size(); i++) {
+            for (size_t j = 0; j < i; j++)
+                if (blocks[j] == blocks[i]) return false; // (planAccumulate's mirror store is not a block's J^T J for such a factor)
+            nf += (size_t) localSize(parameter_block_size_[idOf(blocks[i])]);
+        }
+        if (nr == 0 || nf == 0) continue;
+        n_blocks++, n_J += nr * nf, n_r += nr, n_c += nf;
+    }
+    out.nr.reserve(out.nr.size() + n_blocks), out.nf.reserve(out.nf.size() + n_blocks), out.jac_off.reserve(out.jac_off.size() + n_blocks);
+    out.cols.reserve(out.cols.size() + n_c), out.r.reserve(out.r.size() + n_r);
+    size_t at = out.J.size();
+    out.J.resize(at + n_J);
+    for (const auto &factor : factors_) {
+        if (onBatch(factor, batch_)) continue;
+        const auto &blocks = factor->parameterBlocks();
+        const int nr       = (int) factor->residuals().size();
+        int nf             = 0;
+        for (double *p : blocks) nf += localSize(parameter_block_size_[idOf(p)]);
+        if (nr == 0 || nf == 0) continue;
+        int c0 = 0;
+        for (size_t i = 0; i < blocks.size(); i++) {
+            const long id   = idOf(blocks[i]);
+            const int size  = parameter_block_size_[id], local = localSize(size);
+            const int first = plan.compact[(size_t) parameter_block_index_[id]];
+            for (int x = 0; x < local; x++) out.cols.push_back(first + x);
+            gatherJacobianColumns(nr, size, local, factor->jacobians()[i].data(), nf, c0, &out.J[at]);
+            c0 += local;
+        }
+        out.nr.push_back(nr), out.nf.push_back(nf), out.jac_off.push_back((int64_t) at);
+        out.r.insert(out.r.end(), factor->residuals().begin(), factor->residuals().end());
+        at += (size_t) nr * nf;
+    }
+    return true;
+}
+
+bool MarginalizationInfo::planWithBlocks(int *P, int *m, vector<double> *H, vector<double> *b, HostFactorBlocks *blocks) {
+    if (!updateParameterBlocksIndex() || !preMarginalization()) return false;
+    StructuredPlan plan;
+    if (!planStructured(plan)) return false;
+    blocks->clear();
+    if (!gatherHostBlocks(plan, *blocks)) return false;
+    *P = plan.P, *m = plan.m;
+    H->swap(plan.H), b->swap(plan.b);
     return true;
 }
 

@@ -145,6 +145,22 @@ private:
     vector<double> residuals_;
 };
 
+// The host-evaluated factors of one window as blocks, in the flat layout icg_reproj_host_parts_build takes: per block nr residuals
+// (robust-corrected, as ResidualBlockInfo holds them), the nf columns of the window's compact camera system its free local columns occupy
+// and the dense row-major nr x nf Jacobian of those columns at J + jac_off.
+struct HostFactorBlocks {
+    vector<int32_t> nr, nf, cols;
+    vector<int64_t> jac_off;
+    vector<double> J, r;
+    void clear() { nr.clear(), nf.clear(), cols.clear(), jac_off.clear(), J.clear(), r.clear(); }
+};
+// the leading `local` columns of one parameter block's row-major nr x size Jacobian into columns [c0, c0 + local) of a dense row-major
+// nr x nf Jacobian (a 7-wide pose block contributes its first 6 columns)
+inline void gatherJacobianColumns(int nr, int size, int local, const double *Ja, int nf, int c0, double *Jd) {
+    for (int k = 0; k < nr; k++)
+        for (int x = 0; x < local; x++) Jd[(size_t) k * nf + c0 + x] = Ja[(size_t) k * size + x];
+}
+
 class MarginalizationInfo {
 public:
     MarginalizationInfo() = default;
@@ -180,6 +196,11 @@ public:
     void setKeptLinearization(uint64_t id, int slot) { keep_id_ = id, keep_slot_ = slot; }
     uint64_t keptId() const { return keep_id_; }
     int keptSlot() const { return keep_slot_; }
+    // Diagnostics / tests: M1 bookkeeping, the evaluation of every factor and the structured plan of this window as marginalization()
+    // forms it on the landmark-eliminated path, before the device part is added: H (P x P) and b as planStructured accumulates them, and
+    // the same host factors gathered as blocks.  false: the window is not planned (it would take the dense path), or its factors cannot
+    // be gathered as blocks.
+    bool planWithBlocks(int *P, int *m, vector<double> *H, vector<double> *b, HostFactorBlocks *blocks);
 
 private:
     bool updateParameterBlocksIndex();
@@ -192,13 +213,23 @@ private:
     bool constructAndEliminateStructured();
     // the two host halves of it, either side of the device step (MarginalizationBatch runs that step for many windows in one launch):
     // planStructured checks the structure, lays out the compact camera system and adds the host factors; finishStructured takes the
-    // system with the landmark-eliminated device part added and runs the conditioning guard and the small M3
+    // system with the landmark-eliminated device part added and runs the conditioning guard and the small M3.
+    // planStructured is planLayout (the structure checks, the compact columns, P, m, r, camera_column_of) followed by planAccumulate (J^T J
+    // and J^T e of the host factors into H and b); MarginalizationBatch::setDeviceReducedSystem calls planLayout alone and ships the host
+    // factors as blocks instead (gatherHostBlocks).
     struct StructuredPlan {
         int P{0}, m{0}, r{0};
         vector<double> H, b;
         std::unordered_map<const double *, int> camera_column_of;
+        vector<int> compact; // local column -> column of the compact camera system, -1 for an inverse depth
     };
     bool planStructured(StructuredPlan &plan);
+    bool planLayout(StructuredPlan &plan);
+    void planAccumulate(StructuredPlan &plan);
+    // The window's host factors (factors_ order, the factors on the device batch skipped), appended to `out` as one block each.  false —
+    // `out` is then as it was — when a factor lists a parameter block twice (its J^T J is not one block's) or has more than
+    // ICG_HOST_PART_MAX_NR residuals: the caller treats the window as not planned.
+    bool gatherHostBlocks(const StructuredPlan &plan, HostFactorBlocks &out);
     bool finishStructured(StructuredPlan &plan, double min_hll);
     friend class MarginalizationBatch;
     void linearization();

@@ -9,7 +9,23 @@
 #include <cstring>
 #include <stdexcept>
 
+// A build of this layer on another implementation of the C ABI may not have the entries of the device-resident reduced system: the
+// references stay weak (null when absent) and marginalize() refuses by name; the product library links libicgvins_hip.so, which defines them.
+#pragma weak icg_marg_linearize_resident
+#pragma weak icg_reproj_schur_windows_resident
+#pragma weak icg_reproj_host_parts_build
+
 namespace icg {
+
+// the first of the three entries setDeviceReducedSystem needs that this build lacks, nullptr when all are there
+static const char *missingReducedSystemEntry() {
+    if (&icg_marg_linearize_resident == nullptr) return "icg_marg_linearize_resident";
+    if (&icg_reproj_schur_windows_resident == nullptr) return "icg_reproj_schur_windows_resident";
+    if (&icg_reproj_host_parts_build == nullptr) return "icg_reproj_host_parts_build";
+    return nullptr;
+}
+
+bool MarginalizationBatch::deviceReducedSystemAvailable() { return missingReducedSystemEntry() == nullptr; }
 
 MarginalizationBatch::MarginalizationBatch(int device, double huber_delta, int host_threads)
     : factors_(device, host_threads, "MarginalizationBatch"), device_(device), huber_(huber_delta) {}
@@ -137,6 +153,12 @@ bool MarginalizationBatch::denseNormalOfWindow(Slice &slice, const std::unordere
 struct MarginalizationBatch::State {
     bool alive{false}, planned{false};
     MarginalizationInfo::StructuredPlan plan;
+    HostFactorBlocks blocks; // setDeviceReducedSystem: the window's host factors, instead of their J^T J in plan.H
+};
+
+struct MarginalizationBatch::ReducedRhs {
+    int P;
+    const std::vector<double> &s, &host_s;
 };
 
 struct MarginalizationBatch::DeviceM3 {
@@ -147,9 +169,10 @@ struct MarginalizationBatch::DeviceM3 {
     uint64_t keep_id{0};   // setKeepLinearized: the call's kept linearization
 };
 
-// device M3 (setDeviceLinearization): every window whose eliminated part was added and that passes the first guard, one call
+// device M3 (setDeviceLinearization): every window whose eliminated part was added and that passes the first guard, one call.  resident
+// (setDeviceReducedSystem): the windows' systems are formed on the device from what steps 3 left there; only b = host_s + s goes up.
 bool MarginalizationBatch::linearizeOnDevice(const std::vector<State> &st, const std::vector<char> &added, const std::vector<double> &min_hll,
-                                             DeviceM3 &dev, std::string *what) {
+                                             DeviceM3 &dev, std::string *what, const ReducedRhs *resident) {
     const size_t NW    = st.size();
     const double GUARD = 100.0 * 1e-8; // (finishStructured: 100 x the reference's floor)
     std::vector<int32_t> dP, dm;
@@ -165,16 +188,35 @@ bool MarginalizationBatch::linearizeOnDevice(const std::vector<State> &st, const
         th += (size_t) plan.P * plan.P, tb += (size_t) plan.P, tr += (size_t) plan.r, trr += (size_t) plan.r * plan.r;
     }
     if (who.empty()) return true;
-    std::vector<double> dH(th), db(tb), dev_min(who.size());
+    std::vector<double> dH(resident ? 0 : th), db(tb), dev_min(who.size());
     std::vector<int32_t> dev_status(who.size());
     std::vector<size_t> b_off(who.size(), 0);
     for (size_t k = 1; k < who.size(); k++) b_off[k] = b_off[k - 1] + (size_t) dP[k - 1];
+    dev.Hp.resize(trr), dev.bp.resize(tr), dev.J0.resize(trr), dev.e0.resize(tr);
+    if (resident) {
+        std::vector<int32_t> win(who.size());
+        for (size_t k = 0; k < who.size(); k++) {
+            const size_t w = who[k], at = w * (size_t) resident->P;
+            win[k]         = (int32_t) w;
+            for (int i = 0; i < dP[k]; i++) db[b_off[k] + (size_t) i] = resident->host_s[at + (size_t) i] + resident->s[at + (size_t) i]; // (plan.b += s)
+        }
+        uint64_t id = 0;
+        if (icg_marg_linearize_resident(factors_.ctx(), resident->P, (int) who.size(), win.data(), dP.data(), dm.data(), db.data(), 1e-8, dev.Hp.data(),
+                                        dev.bp.data(), dev.J0.data(), dev.e0.data(), nullptr, dev_min.data(), dev_status.data(), nullptr,
+                                        keep_linearized_ ? &id : nullptr) != ICG_OK) {
+            *what = icg_last_error(factors_.ctx());
+            return false;
+        }
+        dev.keep_id = id;
+        for (size_t k = 0; k < who.size(); k++) // second guard of finishStructured, and a solver that did not converge
+            if (!(dev_min[k] > GUARD) || (dev_status[k] & 1)) dev.on_device[who[k]] = 0;
+        return true;
+    }
     factors_.forEachWindow(who.size(), [&](size_t k) {
         const MarginalizationInfo::StructuredPlan &plan = st[who[k]].plan;
         memcpy(&dH[h_off[k]], plan.H.data(), sizeof(double) * plan.H.size());
         memcpy(&db[b_off[k]], plan.b.data(), sizeof(double) * plan.b.size());
     });
-    dev.Hp.resize(trr), dev.bp.resize(tr), dev.J0.resize(trr), dev.e0.resize(tr);
     MarginalizationLinearizer lin(true, factors_.ctx());
     if (keep_linearized_) {
         dev.keep_id = lin.linearizeKeep((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev.Hp.data(), dev.bp.data(), dev.J0.data(),
@@ -196,6 +238,15 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     phase_ms_[0] = phase_ms_[1] = phase_ms_[2] = phase_ms_[3] = 0;
     error_.clear();
     window_error_.clear();
+    if (device_reduced_system_ && !device_linearization_) {
+        error_ = "setDeviceReducedSystem(true) needs setDeviceLinearization(true): the resident reduced systems are read by the device call's linearization";
+        return false;
+    }
+    if (device_reduced_system_ && !deviceReducedSystemAvailable()) {
+        error_ = std::string(missingReducedSystemEntry()) + " is not in this build";
+        return false;
+    }
+    const bool resident = device_reduced_system_;
     if (keep_linearized_ && !device_linearization_) {
         error_ = "setKeepLinearized(true) needs setDeviceLinearization(true): what is kept is the device call's linearization";
         return false;
@@ -242,8 +293,11 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
             I.releaseMemory();
             return;
         }
-        st[w].alive   = true;
-        st[w].planned = !force_dense && I.planStructured(st[w].plan);
+        st[w].alive = true;
+        if (resident) // (layout and gather only: the blocks' J^T J is formed on the device in step 3)
+            st[w].planned = !force_dense && I.planLayout(st[w].plan) && I.gatherHostBlocks(st[w].plan, st[w].blocks);
+        else
+            st[w].planned = !force_dense && I.planStructured(st[w].plan);
     });
     auto t2 = now();
 
@@ -260,7 +314,7 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     int P = 0;
     for (size_t w = 0; w < NW; w++)
         if (st[w].planned) P = std::max(P, st[w].plan.P);
-    std::vector<double> S, s, hll;
+    std::vector<double> S, s, hll, host_s;
     if (P > 0) {
         std::vector<int32_t> col_pose((size_t) n_poses, -1), col_ext(NW, -1), col_td(NW, -1);
         for (size_t w = 0; w < NW; w++) {
@@ -275,11 +329,38 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
         }
         std::vector<uint8_t> reassemble(NW, 1);
         std::vector<double> damp(NW, 0.0), diag_cc(NW * (size_t) P), cost(NW, 0.0);
-        S.assign(NW * (size_t) P * P, 0.0), s.assign(NW * (size_t) P, 0.0), hll.assign((size_t) std::max(n_lm, 1), 0.0);
-        if (icg_reproj_schur_windows(ctx, P, col_pose.data(), col_ext.data(), col_td.data(), nullptr, reassemble.data(), damp.data(), 0.0, 0.0, S.data(),
-                                     s.data(), diag_cc.data(), cost.data()) != ICG_OK ||
-            icg_reproj_landmark_diag_windows(ctx, hll.data()) != ICG_OK)
-            return fail(icg_last_error(ctx));
+        s.assign(NW * (size_t) P, 0.0), hll.assign((size_t) std::max(n_lm, 1), 0.0);
+        if (resident) {
+            // S stays on the device; the host-factor part of every planned window is built beside it from the window's blocks
+            std::vector<int32_t> Pw(NW, 1), blk_off(NW + 1, 0), nr, nf, cols;
+            std::vector<uint8_t> rebuild(NW, 0);
+            std::vector<int64_t> jac_off;
+            std::vector<double> J, r, host_diag(NW * (size_t) P, 0.0);
+            host_s.assign(NW * (size_t) P, 0.0);
+            for (size_t w = 0; w < NW; w++) {
+                if (st[w].planned) {
+                    const HostFactorBlocks &B = st[w].blocks;
+                    Pw[w] = st[w].plan.P, rebuild[w] = 1;
+                    for (int64_t off : B.jac_off) jac_off.push_back((int64_t) J.size() + off);
+                    nr.insert(nr.end(), B.nr.begin(), B.nr.end()), nf.insert(nf.end(), B.nf.begin(), B.nf.end());
+                    cols.insert(cols.end(), B.cols.begin(), B.cols.end());
+                    J.insert(J.end(), B.J.begin(), B.J.end()), r.insert(r.end(), B.r.begin(), B.r.end());
+                }
+                blk_off[w + 1] = (int32_t) nr.size();
+            }
+            if (icg_reproj_schur_windows_resident(ctx, P, col_pose.data(), col_ext.data(), col_td.data(), nullptr, reassemble.data(), damp.data(), 0.0, 0.0,
+                                                  s.data(), diag_cc.data(), cost.data()) != ICG_OK ||
+                icg_reproj_host_parts_build(ctx, P, Pw.data(), rebuild.data(), blk_off.data(), nr.data(), nf.data(), cols.data(), jac_off.data(), J.data(),
+                                            r.data(), host_s.data(), host_diag.data(), nullptr) != ICG_OK ||
+                icg_reproj_landmark_diag_windows(ctx, hll.data()) != ICG_OK)
+                return fail(icg_last_error(ctx));
+        } else {
+            S.assign(NW * (size_t) P * P, 0.0);
+            if (icg_reproj_schur_windows(ctx, P, col_pose.data(), col_ext.data(), col_td.data(), nullptr, reassemble.data(), damp.data(), 0.0, 0.0, S.data(),
+                                         s.data(), diag_cc.data(), cost.data()) != ICG_OK ||
+                icg_reproj_landmark_diag_windows(ctx, hll.data()) != ICG_OK)
+                return fail(icg_last_error(ctx));
+        }
     }
     auto t3 = now();
 
@@ -291,10 +372,12 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
         const WindowFactorSet::Window &W          = factors_.window(w);
         MarginalizationInfo::StructuredPlan &plan = st[w].plan;
         const int Pw                              = plan.P;
-        const double *Sw = &S[w * (size_t) P * P], *sw = &s[w * (size_t) P];
-        for (int i = 0; i < Pw; i++) {
-            for (int j = 0; j < Pw; j++) plan.H[(size_t) i * Pw + j] += Sw[(size_t) i * P + j];
-            plan.b[(size_t) i] += sw[i];
+        if (!resident) { // (resident: the sum is formed on the device, icg_marg_linearize_resident)
+            const double *Sw = &S[w * (size_t) P * P], *sw = &s[w * (size_t) P];
+            for (int i = 0; i < Pw; i++) {
+                for (int j = 0; j < Pw; j++) plan.H[(size_t) i * Pw + j] += Sw[(size_t) i * P + j];
+                plan.b[(size_t) i] += sw[i];
+            }
         }
         double mn = W.landmarks.empty() ? 0.0 : hll[(size_t) W.lm_begin];
         for (size_t l = 0; l < W.landmarks.size(); l++) mn = std::min(mn, hll[(size_t) W.lm_begin + l]);
@@ -307,7 +390,8 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
             if (st[w].alive && st[w].planned) addEliminated(w);
         });
         std::string what;
-        if (!linearizeOnDevice(st, added, min_hll, dev, &what)) return fail(what);
+        const ReducedRhs rhs{P, s, host_s};
+        if (!linearizeOnDevice(st, added, min_hll, dev, &what, resident ? &rhs : nullptr)) return fail(what);
         kept_id_ = dev.keep_id;
     }
     factors_.forEachWindow(NW, [&](size_t w) {
@@ -325,7 +409,7 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
             return;
         }
         bool done = false;
-        if (st[w].planned) {
+        if (st[w].planned && !resident) { // (resident: there is no H on the host to finish from — the window takes the dense path)
             if (!added[w]) addEliminated(w);
             done          = I.finishStructured(st[w].plan, min_hll[w]);
             structured[w] = done ? 1 : 0;

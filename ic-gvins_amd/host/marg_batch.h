@@ -75,11 +75,26 @@ public:
     uint64_t keptId() const { return kept_id_; } // of the last marginalize(); 0: nothing is kept
     void releaseKept();                          // drops the kept linearization now (tags that name it fall back to shipping)
 
+    // With the device linearization (default off; marginalize() fails with a message without setDeviceLinearization(true), or — naming the
+    // entry — when icg_marg_linearize_resident, icg_reproj_schur_windows_resident or icg_reproj_host_parts_build is not in the build): the
+    // reduced system H of a window never crosses the link.  Step 2 lays the compact system out and gathers the host factors as blocks (no
+    // J^T J on the pool); step 3 leaves S on the device (icg_reproj_schur_windows_resident), builds the host-factor parts there
+    // (icg_reproj_host_parts_build: planStructured's arithmetic, bit for bit) and reads the landmark diagonals; step 4 applies the first
+    // guard on the host and hands the windows that pass it to ONE icg_marg_linearize_resident call, which forms H = part + S on the
+    // device and runs the kernels of icg_marg_linearize_batch on it, with b = host_s + s.  Up: the factor blocks and b; down: s, host_s, the
+    // landmark diagonals and the prior.  Every output bit is the one setDeviceLinearization(true) alone gives, and it composes with
+    // setKeepLinearized.  The one difference: a window whose QL sweep hit its iteration cap takes the DENSE path here — the device
+    // linearization alone finishes it on the host from the H it holds there, which this mode never has.
+    void setDeviceReducedSystem(bool on) { device_reduced_system_ = on; }
+    bool deviceReducedSystem() const { return device_reduced_system_; }
+    static bool deviceReducedSystemAvailable();
+
     // diagnostics of the last marginalize(): windows that took the landmark-eliminated device path / the dense path; wall time of the
     // four phases above [ms]
     int structuredWindows() const { return n_structured_; }
     int denseWindows() const { return n_dense_; }
     const double *lastPhaseMs() const { return phase_ms_; }
+    icg_ctx *context() const { return factors_.ctx(); } // the batch's partitioned context (its profiler: icg_prof_enable / icg_prof_get)
     const std::string &error() const { return error_; }
     const std::string &windowError() const { return window_error_; } // first per-window failure of the last marginalize()
 
@@ -106,8 +121,9 @@ private:
     // marginalize(): a window's progress through the phases; what the device M3 returns
     struct State;
     struct DeviceM3;
+    struct ReducedRhs; // setDeviceReducedSystem: s and host_s of every window (W x P), what b is formed from
     bool linearizeOnDevice(const std::vector<State> &st, const std::vector<char> &added, const std::vector<double> &min_hll, DeviceM3 &dev,
-                           std::string *what);
+                           std::string *what, const ReducedRhs *resident = nullptr);
 
     WindowFactorSet factors_; // the partitioned context, every window's reprojection factors, the host threads
     icg_ctx *dense_ctx_{nullptr}; // one-window context of the dense path (created on first use)
@@ -116,7 +132,7 @@ private:
     double huber_{1.0};
     std::vector<std::unique_ptr<Slice>> windows_;
     bool laid_out_{false};
-    bool device_linearization_{false}, keep_linearized_{false};
+    bool device_linearization_{false}, keep_linearized_{false}, device_reduced_system_{false};
     uint64_t kept_id_{0};
     std::vector<std::shared_ptr<ResidualBlockInfo>> retired_; // factor records of marginalized windows, freed by clear() / the destructor
     int n_structured_{0}, n_dense_{0};

@@ -289,9 +289,7 @@ inline int gatherHostBlock(const Problem &p, const Residual &R, double *cost, st
     for (size_t a = 0; a < R.blocks.size(); a++) {
         const Block &A = p.blocks[(size_t) p.block_of.at(R.blocks[a])];
         if (A.column < 0) continue;
-        const std::vector<double> &Ja = info.jacobians()[a];
-        for (int k = 0; k < nr; k++)
-            for (int x = 0; x < A.local; x++) Jd_at[(size_t) k * nf + c0 + x] = Ja[(size_t) k * sizes[a] + x];
+        gatherJacobianColumns(nr, sizes[a], A.local, info.jacobians()[a].data(), nf, c0, Jd_at);
         c0 += A.local;
     }
     memcpy(res_at, info.residuals().data(), sizeof(double) * (size_t) nr);

@@ -25,7 +25,7 @@ EXPORTS = [
     "icg_marg_prior_set", "icg_marg_prior_evaluate", "icg_marg_linearize_batch",
     "icg_chol_solve_batch", "icg_reproj_schur_windows_resident", "icg_reproj_solve_windows", "icg_reproj_host_parts_build",
     "icg_marg_prior_evaluate_resident", "icg_reproj_host_parts_build_prior",
-    "icg_marg_linearize_batch_keep", "icg_marg_linearized_release", "icg_marg_prior_set_from_kept",
+    "icg_marg_linearize_batch_keep", "icg_marg_linearized_release", "icg_marg_prior_set_from_kept", "icg_marg_linearize_resident",
 ]
 
 
@@ -672,6 +672,27 @@ class Context:
                                                         _p(out["J0"]), _p(out["e0"]), _p(out["evals"]), _p(out["min_ev_m"]), _p(out["status"]),
                                                         C.byref(keep)), "icg_marg_linearize_batch_keep")
         return out, int(keep.value)
+
+    def marg_linearize_resident(self, P, win, Pw, m, b, eps=1e-8, keep=False, want_J0=True, want_e0=True, want_Hp=True, want_bp=True, want_evals=True,
+                                want_min_ev=True, want_status=True, want_H=True):
+        """icg_marg_linearize_resident: system k is window win[k] of the resident reduced systems (reproj_schur_windows_resident, common width
+        P) plus its resident host part; b flat -> dict(J0, e0, Hp, bp, evals, min_ev_m, status, H), flat in list order; keep: -> (dict, keep id)"""
+        win, Pw, m = _i32(win).reshape(-1), _i32(Pw).reshape(-1), _i32(m).reshape(-1)
+        b = _f64(b).reshape(-1)
+        n = len(win)
+        if len(Pw) != n or len(m) != n or b.shape[0] != int(Pw.sum()):
+            raise IcgError("marg_linearize_resident: win, Pw, m, b do not describe the same systems")
+        r = Pw.astype(np.int64) - m
+        nr, nrr = int(r.clip(0).sum()), int((r.clip(0) ** 2).sum())
+        out = dict(J0=np.zeros(nrr) if want_J0 or not keep else None, e0=np.zeros(nr) if want_e0 or not keep else None,
+                   Hp=np.zeros(nrr) if want_Hp else None, bp=np.zeros(nr) if want_bp else None, evals=np.zeros(nr) if want_evals else None,
+                   min_ev_m=np.zeros(n) if want_min_ev else None, status=np.zeros(n, np.int32) if want_status else None,
+                   H=np.zeros(int((Pw.astype(np.int64) ** 2).sum())) if want_H else None)
+        kid = C.c_uint64(0)
+        self._ck(self.lib.icg_marg_linearize_resident(self.h, int(P), n, _p(win), _p(Pw), _p(m), _p(b), C.c_double(eps), _p(out["Hp"]), _p(out["bp"]),
+                                                      _p(out["J0"]), _p(out["e0"]), _p(out["evals"]), _p(out["min_ev_m"]), _p(out["status"]),
+                                                      _p(out["H"]), C.byref(kid) if keep else None), "icg_marg_linearize_resident")
+        return (out, int(kid.value)) if keep else out
 
     def marg_linearized_release(self):
         """icg_marg_linearized_release: the linearization this context keeps is dropped"""

@@ -418,6 +418,24 @@ int icg_marg_linearize_batch(icg_ctx *ctx, int n_windows, const int32_t *P, cons
 int icg_marg_linearize_batch_keep(icg_ctx *ctx, int n_windows, const int32_t *P, const int32_t *m, const double *H, const double *b, double eps,
                                   double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status,
                                   uint64_t *keep_id);
+/* ---- M2 -> M3 on the device: M3 (factors/marginalization_info.h:153-192) on reduced systems that never left the device.  The M2 system of a
+ * window (factors/marginalization_info.h:195-230, landmark-eliminated) is the sum of its host-evaluated factors' J^T J, resident as a packed
+ * lower triangle after icg_reproj_host_parts_build, and of S, whose lower triangle is resident after icg_reproj_schur_windows_resident
+ * (P columns, row stride P).  For k in [0, n_sel) system k is window win[k] of the partition, Pw[k] x Pw[k]; one kernel forms, for i >= j,
+ *     H[i][j] = H[j][i] = part[i (i + 1) / 2 + j] + S_w[i * P + j]
+ * (the part first, then S; a window without a resident part takes +0.0 as its part and the addition is still made) in a buffer of the
+ * context, and the kernels of icg_marg_linearize_batch run unchanged on it: every output holds the bits that call returns for these H and b.
+ * b: the Pw[k] right-hand sides, concatenated (the caller adds host_s + s).  Outputs: as icg_marg_linearize_batch, concatenated in list
+ * order; H_out (optional, sum Pw^2 doubles): the formed systems.  keep_id == NULL: the plain form, J0 / e0 are required.  keep_id != NULL: the
+ * keep form, J0 / e0 may be NULL, system k is kept window k; lifetime and id rules are icg_marg_linearize_batch_keep's.
+ * The resident S and parts are only read: icg_reproj_solve_windows works afterwards as before.
+ * ICG_ERR_INVALID (the message names the list position and the window): no resident reduced systems of P columns, a NULL required pointer,
+ * n_sel <= 0, win[k] outside the partition or listed twice, Pw[k] outside 1 .. P, a resident part whose column count is not Pw[k], m[k]
+ * outside [0, Pw[k]), eps < 0.  ICG_ERR_CAPACITY as icg_marg_linearize_batch.  After an error nothing was launched and no output was
+ * touched; the linearization the context kept is dropped by every call, failed or not. */
+int icg_marg_linearize_resident(icg_ctx *ctx, int P, int n_sel, const int32_t *win, const int32_t *Pw, const int32_t *m, const double *b,
+                                double eps, double *Hp, double *bp, double *J0, double *e0, double *evals, double *min_ev_m, int32_t *status,
+                                double *H_out, uint64_t *keep_id);
 /* Drops the linearization the context keeps, if any (its id is no longer known; the memory is reused by the next kept one). */
 int icg_marg_linearized_release(icg_ctx *ctx);
 /* icg_marg_prior_set (factors/marginalization_factor.h:47-101) with J0 / e0 taken from a kept linearization
