@@ -8,6 +8,7 @@
 #include <cstdlib>
 
 #include "reproj_internal.h"
+#include "../host/lm_min_rule.h"
 
 __global__ void k_schur_inv_w(const win_desc *wd, int P, double *sys, double min_diag, double max_diag) {
     const win_desc W = wd[blockIdx.y];
@@ -195,6 +196,22 @@ __global__ void k_lm_diag_w(const win_desc *wd, int P, const double *sys, double
     if (l >= W.L) return;
     const size_t N = (size_t) P + W.L;
     h_ll[W.lm_begin + l] = sys[W.sys_off + (size_t) (P + l) * N + P + l];
+}
+
+// The smallest of those diagonals per window, the value of the batched M3's first guard (host/lm_min_rule.h: the host loop's result as a
+// value), so that one double per window comes back instead of one per landmark.  One wave per window: lane t takes landmarks t, t + 64, ...
+// (a window of 300 makes five passes), the lanes are joined by the xor butterfly; a window without landmarks gives 0.0.
+// grid (W), block 64
+__global__ __launch_bounds__(64) void k_lm_min_w(const win_desc *wd, int P, const double *sys, double *min_hll) {
+    const win_desc W = wd[blockIdx.x];
+    const int t      = threadIdx.x;
+    const size_t N   = (size_t) P + W.L;
+    const double *d  = sys + W.sys_off + (size_t) P * N + P; // (P + l, P + l) is d[l (N + 1)]
+    double m = icg_lm_min::start();
+    for (int l = t; l < W.L; l += icg_lm_min::kLanes) m = icg_lm_min::take(m, d[(size_t) l * (N + 1)]);
+#pragma unroll
+    for (int k = icg_lm_min::kLanes / 2; k >= 1; k >>= 1) m = icg_lm_min::take(m, __shfl_xor(m, k, icg_lm_min::kLanes));
+    if (t == 0) min_hll[blockIdx.x] = W.L > 0 ? icg_lm_min::finish(d[0], m) : 0.0;
 }
 
 // Window w's block of d_sys at width P: H (N x N, N = P + L_w) | b (N) | inv (L_w).  Returns the doubles the partition's systems take; off
@@ -410,6 +427,29 @@ static int landmark_diag_impl(icg_ctx *ctx, icg_partition &pt, double *h_ll) {
     {
         icg_prof_scope ps(ctx, "schur_reduce");
         hipLaunchKernelGGL(k_lm_diag_w, dim3((Lmax + 255) / 256, W), dim3(256), 0, ctx->stream, d_wd, P, (const double *) ctx->d_sys, d_out);
+    }
+    ICG_HIP(ctx, hipGetLastError());
+    return c.finish();
+}
+
+static int landmark_min_impl(icg_ctx *ctx, icg_partition &pt, double *min_hll) {
+    const int W = pt.W, P = pt.sys_P;
+    if (pt.lm_off[(size_t) W] == 0) { // (no landmark anywhere: nothing to read on the device)
+        std::fill(min_hll, min_hll + W, 0.0);
+        return ICG_OK;
+    }
+    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    const std::vector<win_desc> wd = build_win_desc(pt, nullptr, nullptr);
+    icg_call c(ctx);
+    int rc = c.reserve((sizeof(win_desc) + sizeof(double)) * (size_t) W + 4096);
+    if (rc) return rc;
+    const win_desc *d_wd = c.in(wd.data(), (size_t) W);
+    if ((rc = c.seal())) return rc;
+    double *d_out = c.out(min_hll, (size_t) W);
+    ICG_LAUNCH_GUARD(c);
+    {
+        icg_prof_scope ps(ctx, "lm_min");
+        hipLaunchKernelGGL(k_lm_min_w, dim3(W), dim3(icg_lm_min::kLanes), 0, ctx->stream, d_wd, P, (const double *) ctx->d_sys, d_out);
     }
     ICG_HIP(ctx, hipGetLastError());
     return c.finish();
@@ -638,6 +678,12 @@ extern "C" int icg_reproj_landmark_diag_windows(icg_ctx *ctx, double *h_ll) {
     if (!ctx || !h_ll) return ICG_ERR_INVALID;
     if (!ctx->part_w.sys_valid) return icg_fail(ctx, ICG_ERR_INVALID, "no resident window systems: call icg_reproj_schur_windows first");
     return landmark_diag_impl(ctx, ctx->part_w, h_ll);
+}
+
+extern "C" int icg_reproj_landmark_min_windows(icg_ctx *ctx, double *min_hll) {
+    if (!ctx || !min_hll) return ICG_ERR_INVALID;
+    if (!ctx->part_w.sys_valid) return icg_fail(ctx, ICG_ERR_INVALID, "no resident window systems: call icg_reproj_schur_windows first");
+    return landmark_min_impl(ctx, ctx->part_w, min_hll);
 }
 
 extern "C" int icg_reproj_backsub_windows(icg_ctx *ctx, int P, const double *delta_c, double *delta_l, double *lm_terms) {

@@ -9,7 +9,7 @@
 #include "factors.h"
 #include "marg_batch.h"
 #include "marg_linearize_hip.h"
-#include "capi_windows.h"
+#include "capi_marg_cases.h"
 
 using namespace icg;
 
@@ -30,25 +30,6 @@ struct VioArgs {
     double *const *invdepth;
     double *td;
     const double *const *prior_pose0, *const *prior_mix0;
-};
-
-// One window to marginalize, whatever built it: the info with every factor added, the addresses of its parameter ids, and its
-// reprojection factors with their five blocks for MarginalizationBatch::addReprojectionFactor / ReprojectionBatch::add.
-struct Case {
-    std::shared_ptr<MarginalizationInfo> info;
-    std::unordered_map<long, long> ids;
-    std::unordered_map<long, double *> address;
-    struct Reproj {
-        ReprojectionFactor *factor;
-        double *blocks[5];
-    };
-    vector<Reproj> reproj;
-    vector<std::shared_ptr<ReprojectionFactor>> owned;
-    vector<std::shared_ptr<void>> keep; // whatever else has to live as long as the window (the family's own parameter arrays)
-    template <class Add>
-    void addReprojections(Add &&add) {
-        for (Reproj &R : reproj) add(R.factor, R.blocks[0], R.blocks[1], R.blocks[2], R.blocks[3], R.blocks[4]);
-    }
 };
 
 // a MarginalizationInfo behind the calls the window builders of capi_windows.h make on a solver: a parameter block gets the next id, a
@@ -72,54 +53,6 @@ struct OnInfo {
         return 0;
     }
 };
-
-// family 0: the jittered visual windows of icgh_backend_marginalize_batch
-vector<std::unique_ptr<Case>> visual_cases(const MargArgs &a, vector<std::unique_ptr<MargWindow>> &wins) {
-    vector<std::unique_ptr<Case>> out;
-    for (auto &W : wins) {
-        std::unique_ptr<Case> c(new Case);
-        c->info = W->info, c->ids = W->ids, c->address = W->address;
-        for (int k = 0; k < a.n; k++)
-            c->reproj.push_back({W->factors[(size_t) k].get(),
-                                 {&W->P[7 * (size_t) a.idx_i[k]], &W->P[7 * (size_t) a.idx_j[k]], W->E.data(), &W->D[(size_t) a.idx_lm[k]], &W->TD}});
-        out.push_back(std::move(c));
-    }
-    return out;
-}
-
-// family 2: the windows of family 0 one keyframe later.  Generation 1 (`wins`, marginalized by the caller) left a prior on the retained
-// blocks; now keyframe 1 leaves: the MarginalizationFactor of generation 1 is a host factor over all of its blocks, and the reprojection
-// factors are the ones anchored in keyframe 1 (the second factor table, indices into the same poses and inverse depths).  The positions of
-// the retained keyframes are moved by `jitter` first, so that the prior is evaluated away from its linearization point.
-vector<std::unique_ptr<Case>> second_generation(const MargArgs &a, vector<std::unique_ptr<MargWindow>> &wins, int n2, const double *obs2_soa, const int32_t *idx2_i,
-                                                const int32_t *idx2_j, const int32_t *idx2_lm, double jitter) {
-    auto loss = a.huber_delta > 0 ? std::make_shared<HuberLossHip>(a.huber_delta) : nullptr;
-    vector<std::unique_ptr<Case>> out;
-    Uniform rnd{kJitterSeed ^ 0x5DEECE66Dull};
-    for (auto &W : wins) {
-        std::unique_ptr<Case> c(new Case);
-        c->ids = W->ids, c->address = W->address;
-        const vector<double *> blocks = W->info->getParamterBlocks(W->address);
-        auto prior                    = std::make_shared<MarginalizationFactor>(W->info);
-        for (int k = 1; k < a.n_poses; k++)
-            for (int x = 0; x < 3; x++) W->P[7 * (size_t) k + x] += jitter * rnd();
-        c->info = std::make_shared<MarginalizationInfo>();
-        c->info->updateParamtersIds(c->ids);
-        vector<int> drop;
-        for (size_t k = 0; k < blocks.size(); k++)
-            if (blocks[k] == &W->P[7]) drop.push_back((int) k);
-        c->info->addResidualBlockInfo(std::make_shared<ResidualBlockInfo>(prior, nullptr, blocks, drop));
-        for (int k = 0; k < n2; k++) {
-            c->owned.push_back(reproj_factor_from_soa(obs2_soa, n2, k));
-            double *pi = &W->P[7 * (size_t) idx2_i[k]], *pj = &W->P[7 * (size_t) idx2_j[k]], *lm = &W->D[(size_t) idx2_lm[k]];
-            c->info->addResidualBlockInfo(
-                std::make_shared<ResidualBlockInfo>(c->owned.back(), loss, vector<double *>{pi, pj, W->E.data(), lm, &W->TD}, vector<int>{0, 3}));
-            c->reproj.push_back({c->owned.back().get(), {pi, pj, W->E.data(), lm, &W->TD}});
-        }
-        out.push_back(std::move(c));
-    }
-    return out;
-}
 
 // family 1: visual-inertial windows (vio_window / vio_blocks / vio_motion_factors / vio_mix_prior) that marginalize the pose and the mix
 // block of state 0 (m = 15) and the inverse depths anchored there; only the reprojection factors anchored in state 0 take part
@@ -285,51 +218,7 @@ int icgh_backend_marg_resident(int mode, int family, int n_windows, int dense_wi
         }
         counts[0] = mb.structuredWindows(), counts[1] = mb.denseWindows();
         for (int k = 0; k < 4; k++) phase_ms[k] = mb.lastPhaseMs()[k];
-        vector<std::shared_ptr<MarginalizationFactor>> priors;
-        size_t at = 0, at2 = 0;
-        for (int w = 0; w < n_windows; w++) {
-            ok_out[w] = ok[(size_t) w] ? 1 : 0;
-            if (!ok[(size_t) w]) continue;
-            Case &c                      = *cases[(size_t) w];
-            const MarginalizationInfo &I = *c.info;
-            const size_t r               = (size_t) I.remainedSize();
-            r_out[w]                     = (int32_t) r;
-            memcpy(Hp + at2, I.Hp().data(), sizeof(double) * r * r), memcpy(J0 + at2, I.linearizedJacobians().data(), sizeof(double) * r * r);
-            memcpy(bp + at, I.bp().data(), sizeof(double) * r), memcpy(e0 + at, I.linearizedResiduals().data(), sizeof(double) * r);
-            at += r, at2 += r * r;
-            if (I.keptId() != 0) tag_slot[w] = I.keptSlot(), counts[2]++;
-            (void) c.info->getParamterBlocks(c.address); // (fills the remained-block lists the factor copies)
-            priors.push_back(std::make_shared<MarginalizationFactor>(c.info));
-        }
-        mb.clear();
-        if (priors.empty()) return 0;
-        TempCtx T(0);
-        MarginalizationPriorSet set;
-        vector<MargPriorView> views;
-        for (auto &f : priors) views.push_back(f->margPriorView());
-        std::string e;
-        if (!set.set(T.ctx, views, &e)) {
-            set_err(err, errlen, e.c_str());
-            return -3;
-        }
-        counts[3]   = set.handedOff();
-        Uniform rnd = point_stream(seed);
-        vector<vector<double>> xs(views.size());
-        vector<vector<const double *>> params(views.size());
-        vector<const double *const *> plist(views.size());
-        for (size_t p = 0; p < views.size(); p++) {
-            const MargPriorView &v = views[p];
-            for (int b = 0; b < v.n_blocks; b++)
-                for (int k = 0; k < v.size[b]; k++) xs[p].push_back(v.x0[b][k] + perturb * rnd());
-            size_t off = 0;
-            for (int b = 0; b < v.n_blocks; b++) params[p].push_back(xs[p].data() + off), off += (size_t) v.size[b];
-            plist[p] = params[p].data();
-        }
-        if (!set.evaluate(plist, residuals, nullptr, nullptr, nullptr, &e)) {
-            set_err(err, errlen, e.c_str());
-            return -3;
-        }
-        return 0;
+        return marg_case_outputs(cases, ok, mb, seed, perturb, ok_out, r_out, tag_slot, Hp, bp, J0, e0, residuals, &counts[2], &counts[3], err, errlen);
     });
 }
 

@@ -591,7 +591,27 @@ static bool onBatch(const std::shared_ptr<ResidualBlockInfo> &f, DeviceFactorSet
     return f->lossFunction() == nullptr || dynamic_cast<HuberLossHip *>(f->lossFunction().get()) != nullptr;
 }
 
-bool MarginalizationInfo::preMarginalization() { // :256-273
+const ResidualBlockInfo *MarginalizationInfo::devicePriorCandidate() const {
+    for (const auto &factor : factors_) {
+        if (onBatch(factor, batch_) || factor->lossFunction()) continue;
+        const auto *src = dynamic_cast<const MargPriorSource *>(factor->costFunction().get());
+        if (!src) continue;
+        const MargPriorView &v = src->margPriorView();
+        const auto &sizes      = factor->parameterBlockSizes();
+        bool fits              = v.r > 0 && v.r == factor->costFunction()->num_residuals() && v.n_blocks == (int) sizes.size();
+        for (int b = 0; fits && b < v.n_blocks; b++) fits = v.size[b] == sizes[(size_t) b];
+        if (fits) return factor.get(); // (the window's FIRST such prior; a second one stays a host factor)
+    }
+    return nullptr;
+}
+
+bool MarginalizationInfo::evaluateDeferred() {
+    ResidualBlockInfo *f = deferred_;
+    deferred_            = nullptr;
+    return f == nullptr || f->Evaluate();
+}
+
+bool MarginalizationInfo::preMarginalization(const ResidualBlockInfo *defer) { // :256-273
     // every reprojection factor of the batch: ONE device launch incl. the robust correction
     double delta = 0;
     for (const auto &factor : factors_)
@@ -601,8 +621,12 @@ bool MarginalizationInfo::preMarginalization() { // :256-273
             break;
         }
     if (batch_ && batch_->size() > 0 && !batch_->evaluateCorrected(delta)) return false;
+    deferred_ = nullptr;
     for (const auto &factor : factors_) {
-        if (!onBatch(factor, batch_) && !factor->Evaluate()) return false;
+        if (factor.get() == defer) // (its blocks are snapshot below like every factor's; evaluateDeferred() runs the evaluation if it is needed)
+            deferred_ = factor.get();
+        else if (!onBatch(factor, batch_) && !factor->Evaluate())
+            return false;
         const vector<int32_t> &block_sizes = factor->parameterBlockSizes();
         for (size_t k = 0; k < block_sizes.size(); k++) {
             long id  = idOf(factor->parameterBlocks()[k]);
@@ -761,12 +785,17 @@ void MarginalizationInfo::planAccumulate(StructuredPlan &plan) {
     }
 }
 
-bool MarginalizationInfo::gatherHostBlocks(const StructuredPlan &plan, HostFactorBlocks &out) {
+bool MarginalizationInfo::gatherHostBlocks(const StructuredPlan &plan, HostFactorBlocks &out, const ResidualBlockInfo *prior) {
     size_t n_blocks = 0, n_J = 0, n_r = 0, n_c = 0;
+    const size_t first_block = out.nr.size();
+    // (the deferred prior has not been evaluated: its residual count is the cost function's, its Jacobian takes no room in J)
+    auto residualsOf = [&](const std::shared_ptr<ResidualBlockInfo> &f) {
+        return f.get() == prior ? (size_t) f->costFunction()->num_residuals() : f->residuals().size();
+    };
     for (const auto &factor : factors_) {
         if (onBatch(factor, batch_)) continue;
         const auto &blocks = factor->parameterBlocks();
-        const size_t nr    = factor->residuals().size();
+        const size_t nr    = residualsOf(factor);
         if (nr > (size_t) ICG_HOST_PART_MAX_NR) return false;
         size_t nf = 0;
         for (size_t i = 0; i < blocks.size(); i++) {
@@ -775,7 +804,7 @@ bool MarginalizationInfo::gatherHostBlocks(const StructuredPlan &plan, HostFacto
             nf += (size_t) localSize(parameter_block_size_[idOf(blocks[i])]);
         }
         if (nr == 0 || nf == 0) continue;
-        n_blocks++, n_J += nr * nf, n_r += nr, n_c += nf;
+        n_blocks++, n_J += factor.get() == prior ? 0 : nr * nf, n_r += nr, n_c += nf;
     }
     out.nr.reserve(out.nr.size() + n_blocks), out.nf.reserve(out.nf.size() + n_blocks), out.jac_off.reserve(out.jac_off.size() + n_blocks);
     out.cols.reserve(out.cols.size() + n_c), out.r.reserve(out.r.size() + n_r);
@@ -784,10 +813,22 @@ bool MarginalizationInfo::gatherHostBlocks(const StructuredPlan &plan, HostFacto
     for (const auto &factor : factors_) {
         if (onBatch(factor, batch_)) continue;
         const auto &blocks = factor->parameterBlocks();
-        const int nr       = (int) factor->residuals().size();
+        const int nr       = (int) residualsOf(factor);
         int nf             = 0;
         for (double *p : blocks) nf += localSize(parameter_block_size_[idOf(p)]);
         if (nr == 0 || nf == 0) continue;
+        if (factor.get() == prior) { // its place in the block list, its columns and its slots in r; J0's columns instead of a Jacobian
+            const MargPriorView &v = dynamic_cast<const MargPriorSource *>(factor->costFunction().get())->margPriorView();
+            for (size_t i = 0; i < blocks.size(); i++) {
+                const long id   = idOf(blocks[i]);
+                const int local = localSize(parameter_block_size_[id]), first = plan.compact[(size_t) parameter_block_index_[id]];
+                for (int x = 0; x < local; x++) out.cols.push_back(first + x), out.prior_cols.push_back(v.index[i] + x);
+            }
+            out.prior_block = (int) (out.nr.size() - first_block);
+            out.nr.push_back(nr), out.nf.push_back(nf), out.jac_off.push_back(HostFactorBlocks::kFromPrior);
+            out.r.insert(out.r.end(), (size_t) nr, 0.0);
+            continue;
+        }
         int c0 = 0;
         for (size_t i = 0; i < blocks.size(); i++) {
             const long id   = idOf(blocks[i]);
@@ -813,6 +854,18 @@ bool MarginalizationInfo::planWithBlocks(int *P, int *m, vector<double> *H, vect
     *P = plan.P, *m = plan.m;
     H->swap(plan.H), b->swap(plan.b);
     return true;
+}
+
+bool MarginalizationInfo::planWithDeferredPrior(HostFactorBlocks *deferred, HostFactorBlocks *eager, const ResidualBlockInfo **prior_out) {
+    if (!updateParameterBlocksIndex()) return false;
+    const ResidualBlockInfo *prior = devicePriorCandidate();
+    if (prior_out) *prior_out = prior;
+    if (!prior || !preMarginalization(prior)) return false;
+    StructuredPlan plan;
+    if (!planLayout(plan)) return false;
+    deferred->clear(), eager->clear();
+    if (!prior->residuals().empty() || !gatherHostBlocks(plan, *deferred, prior)) return false; // (deferred: nothing was evaluated)
+    return evaluateDeferred() && gatherHostBlocks(plan, *eager);
 }
 
 bool MarginalizationInfo::finishStructured(StructuredPlan &plan, double min_hll) {

@@ -152,7 +152,14 @@ struct HostFactorBlocks {
     vector<int32_t> nr, nf, cols;
     vector<int64_t> jac_off;
     vector<double> J, r;
-    void clear() { nr.clear(), nf.clear(), cols.clear(), jac_off.clear(), J.clear(), r.clear(); }
+    // gatherHostBlocks with a deferred prior (MarginalizationBatch::setDevicePrior): that factor's block stands in its place with
+    // jac_off == kFromPrior, its slots in r reserved (zeros) and nothing in J; prior_block is its position among the blocks gathered by that
+    // call (-1: none, or the prior has no residual / no free column), prior_cols the free local columns of its parameter blocks in block
+    // order, view.index[a] + x: column y of the block is column prior_cols[y] of the prior's J0
+    static constexpr int64_t kFromPrior = ICG_HP_JAC_FROM_PRIOR;
+    int prior_block{-1};
+    vector<int32_t> prior_cols;
+    void clear() { nr.clear(), nf.clear(), cols.clear(), jac_off.clear(), J.clear(), r.clear(), prior_cols.clear(), prior_block = -1; }
 };
 // the leading `local` columns of one parameter block's row-major nr x size Jacobian into columns [c0, c0 + local) of a dense row-major
 // nr x nf Jacobian (a 7-wide pose block contributes its first 6 columns)
@@ -201,10 +208,21 @@ public:
     // the same host factors gathered as blocks.  false: the window is not planned (it would take the dense path), or its factors cannot
     // be gathered as blocks.
     bool planWithBlocks(int *P, int *m, vector<double> *H, vector<double> *b, HostFactorBlocks *blocks);
+    // Diagnostics / tests of MarginalizationBatch::setDevicePrior's host side: the same steps with the window's prior (devicePriorCandidate,
+    // *prior_out) deferred — `deferred` is gathered while that factor has not been evaluated, then the deferred evaluation runs and `eager`
+    // is what gatherHostBlocks packs from the evaluated factor.  false: no such prior, or the window is not planned.
+    bool planWithDeferredPrior(HostFactorBlocks *deferred, HostFactorBlocks *eager, const ResidualBlockInfo **prior_out = nullptr);
+    // The host factor MarginalizationBatch::setDevicePrior hands to the device: the first one (factors_ order) whose cost function is a
+    // MargPriorSource, that has no loss function and whose view describes the residual block (r residuals, the blocks' global sizes) — the
+    // test WindowSolverBatch::layout applies.  nullptr: the window has none (a robustified prior stays a host factor).
+    const ResidualBlockInfo *devicePriorCandidate() const;
 
 private:
     bool updateParameterBlocksIndex();
-    bool preMarginalization();
+    // defer (one of this window's factors, or nullptr): that factor is NOT evaluated — its blocks are snapshot like every factor's — until
+    // evaluateDeferred() is called (true when there was nothing to do).  A window that stays on the structured device path never calls it.
+    bool preMarginalization(const ResidualBlockInfo *defer = nullptr);
+    bool evaluateDeferred();
     bool constructEquation();
     void schurElimination();
     // M2 + M3 in one step when the marginalized set is {a few pose / mix blocks} + {inverse depths seen only by the device batch}:
@@ -229,7 +247,10 @@ private:
     // The window's host factors (factors_ order, the factors on the device batch skipped), appended to `out` as one block each.  false —
     // `out` is then as it was — when a factor lists a parameter block twice (its J^T J is not one block's) or has more than
     // ICG_HOST_PART_MAX_NR residuals: the caller treats the window as not planned.
-    bool gatherHostBlocks(const StructuredPlan &plan, HostFactorBlocks &out);
+    // prior (the factor preMarginalization deferred): its block is emitted in its place — the block order is factors_ order, the device
+    // sums follow it — with nr = r, its nf window columns, its slots in r reserved, HostFactorBlocks::kFromPrior for a Jacobian offset, and
+    // out.prior_block / out.prior_cols say where J0's columns go.
+    bool gatherHostBlocks(const StructuredPlan &plan, HostFactorBlocks &out, const ResidualBlockInfo *prior = nullptr);
     bool finishStructured(StructuredPlan &plan, double min_hll);
     friend class MarginalizationBatch;
     void linearization();
@@ -265,6 +286,7 @@ private:
     vector<double> linearized_jacobians_, linearized_residuals_;
     bool isvalid_{true};
     DeviceFactorSet *batch_{nullptr};
+    ResidualBlockInfo *deferred_{nullptr}; // preMarginalization(defer): not evaluated yet
     uint64_t keep_id_{0};
     int keep_slot_{-1};
 };

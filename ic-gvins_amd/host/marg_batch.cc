@@ -3,6 +3,7 @@
 #include "marg_linearize_hip.h"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -14,6 +15,8 @@
 #pragma weak icg_marg_linearize_resident
 #pragma weak icg_reproj_schur_windows_resident
 #pragma weak icg_reproj_host_parts_build
+#pragma weak icg_reproj_host_parts_build_prior
+#pragma weak icg_reproj_landmark_min_windows
 
 namespace icg {
 
@@ -26,6 +29,17 @@ static const char *missingReducedSystemEntry() {
 }
 
 bool MarginalizationBatch::deviceReducedSystemAvailable() { return missingReducedSystemEntry() == nullptr; }
+
+// the same for setDevicePrior (icg_marg_prior_set_from_kept is not among them: without it the set ships every prior)
+static const char *missingDevicePriorEntry() {
+    if (!MarginalizationPriorSet::available()) return "icg_marg_prior_set";
+    if (!MarginalizationPriorSet::residentAvailable()) return "icg_marg_prior_evaluate_resident";
+    if (&icg_reproj_host_parts_build_prior == nullptr) return "icg_reproj_host_parts_build_prior";
+    if (&icg_reproj_landmark_min_windows == nullptr) return "icg_reproj_landmark_min_windows";
+    return nullptr;
+}
+
+bool MarginalizationBatch::devicePriorAvailable() { return missingDevicePriorEntry() == nullptr; }
 
 MarginalizationBatch::MarginalizationBatch(int device, double huber_delta, int host_threads)
     : factors_(device, host_threads, "MarginalizationBatch"), device_(device), huber_(huber_delta) {}
@@ -236,8 +250,17 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     if (ok) ok->assign(NW, 0);
     n_structured_ = n_dense_ = 0;
     phase_ms_[0] = phase_ms_[1] = phase_ms_[2] = phase_ms_[3] = 0;
+    n_device_priors_ = n_priors_from_kept_ = n_deferred_evaluations_ = 0;
     error_.clear();
     window_error_.clear();
+    if (device_prior_ && !device_reduced_system_) {
+        error_ = "setDevicePrior(true) needs setDeviceReducedSystem(true): the resident prior is read by the device call that builds the host-factor parts";
+        return false;
+    }
+    if (device_prior_ && !devicePriorAvailable()) {
+        error_ = std::string(missingDevicePriorEntry()) + " is not in this build";
+        return false;
+    }
     if (device_reduced_system_ && !device_linearization_) {
         error_ = "setDeviceReducedSystem(true) needs setDeviceLinearization(true): the resident reduced systems are read by the device call's linearization";
         return false;
@@ -256,7 +279,9 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
         return false;
     }
     if (NW == 0) return true;
-    releaseKept(); // (the last marginalize()'s; this one keeps its own below)
+    const bool dev_prior = device_prior_;
+    // (the last marginalize()'s; this one keeps its own below.  setDevicePrior: the resident set is built from it first, in phase 1)
+    if (!dev_prior) releaseKept();
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms  = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
         return std::chrono::duration<double, std::milli>(b - a).count();
@@ -274,6 +299,27 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     auto t0 = now();
     icg_ctx *ctx      = factors_.ctx();
     const int n_poses = factors_.numPoses(), n_lm = factors_.numLandmarks();
+    // setDevicePrior: the prior each window hands over and its index in the resident set (window order).  The set copies J0 / e0 — from the
+    // kept linearization where the views are tagged with it — so it is built before anything drops that linearization: the release here,
+    // and icg_marg_linearize_resident in step 4.
+    std::vector<const ResidualBlockInfo *> taken(NW, nullptr);
+    std::vector<int32_t> prior_in_set(NW, -1);
+    if (dev_prior) {
+        std::vector<MargPriorView> views;
+        for (size_t w = 0; w < NW; w++) {
+            const ResidualBlockInfo *f = windows_[w]->info->devicePriorCandidate();
+            if (!f) continue;
+            const MargPriorView &v = dynamic_cast<const MargPriorSource *>(f->costFunction().get())->margPriorView();
+            if (v.r > ICG_MARG_MAX_R) continue; // (wider than a resident prior may be: it stays a host factor)
+            taken[w] = f, prior_in_set[w] = (int32_t) views.size();
+            views.push_back(v);
+        }
+        std::string what;
+        if (!views.empty() && !prior_set_.set(ctx, views, &what)) return fail(what);
+        n_device_priors_    = (int) views.size();
+        n_priors_from_kept_ = views.empty() ? 0 : prior_set_.handedOff();
+        releaseKept();
+    }
     if (factors_.numFactors() > 0) {
         std::vector<double> poses, ext, inv, td;
         factors_.gather(poses, ext, inv, td);
@@ -288,14 +334,17 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     const bool force_dense = MarginalizationInfo::denseForced();
     factors_.forEachWindow(NW, [&](size_t w) {
         MarginalizationInfo &I = *windows_[w]->info;
-        if (!I.updateParameterBlocksIndex() || !I.preMarginalization()) { // (:75-86: nothing to marginalize / an evaluation failed)
+        // (setDevicePrior: the point the taken prior is evaluated at on the device — the values its Evaluate() would read here; the factor
+        // itself is deferred, its blocks are still snapshot)
+        if (taken[w]) prior_set_.pack((size_t) prior_in_set[w], taken[w]->parameterBlocks().data());
+        if (!I.updateParameterBlocksIndex() || !I.preMarginalization(taken[w])) { // (:75-86: nothing to marginalize / an evaluation failed)
             I.isvalid_ = false;
             I.releaseMemory();
             return;
         }
         st[w].alive = true;
         if (resident) // (layout and gather only: the blocks' J^T J is formed on the device in step 3)
-            st[w].planned = !force_dense && I.planLayout(st[w].plan) && I.gatherHostBlocks(st[w].plan, st[w].blocks);
+            st[w].planned = !force_dense && I.planLayout(st[w].plan) && I.gatherHostBlocks(st[w].plan, st[w].blocks, taken[w]);
         else
             st[w].planned = !force_dense && I.planStructured(st[w].plan);
     });
@@ -314,7 +363,7 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     int P = 0;
     for (size_t w = 0; w < NW; w++)
         if (st[w].planned) P = std::max(P, st[w].plan.P);
-    std::vector<double> S, s, hll, host_s;
+    std::vector<double> S, s, hll, host_s, min_dev;
     if (P > 0) {
         std::vector<int32_t> col_pose((size_t) n_poses, -1), col_ext(NW, -1), col_td(NW, -1);
         for (size_t w = 0; w < NW; w++) {
@@ -332,7 +381,7 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
         s.assign(NW * (size_t) P, 0.0), hll.assign((size_t) std::max(n_lm, 1), 0.0);
         if (resident) {
             // S stays on the device; the host-factor part of every planned window is built beside it from the window's blocks
-            std::vector<int32_t> Pw(NW, 1), blk_off(NW + 1, 0), nr, nf, cols;
+            std::vector<int32_t> Pw(NW, 1), blk_off(NW + 1, 0), nr, nf, cols, prior_of, prior_cols;
             std::vector<uint8_t> rebuild(NW, 0);
             std::vector<int64_t> jac_off;
             std::vector<double> J, r, host_diag(NW * (size_t) P, 0.0);
@@ -341,7 +390,12 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
                 if (st[w].planned) {
                     const HostFactorBlocks &B = st[w].blocks;
                     Pw[w] = st[w].plan.P, rebuild[w] = 1;
-                    for (int64_t off : B.jac_off) jac_off.push_back((int64_t) J.size() + off);
+                    for (int64_t off : B.jac_off) jac_off.push_back(off < 0 ? off : (int64_t) J.size() + off); // (< 0: ICG_HP_JAC_FROM_PRIOR)
+                    if (dev_prior) {
+                        prior_of.insert(prior_of.end(), B.nr.size(), -1);
+                        if (B.prior_block >= 0) prior_of[nr.size() + (size_t) B.prior_block] = prior_in_set[w];
+                        prior_cols.insert(prior_cols.end(), B.prior_cols.begin(), B.prior_cols.end());
+                    }
                     nr.insert(nr.end(), B.nr.begin(), B.nr.end()), nf.insert(nf.end(), B.nf.begin(), B.nf.end());
                     cols.insert(cols.end(), B.cols.begin(), B.cols.end());
                     J.insert(J.end(), B.J.begin(), B.J.end()), r.insert(r.end(), B.r.begin(), B.r.end());
@@ -349,10 +403,23 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
                 blk_off[w + 1] = (int32_t) nr.size();
             }
             if (icg_reproj_schur_windows_resident(ctx, P, col_pose.data(), col_ext.data(), col_td.data(), nullptr, reassemble.data(), damp.data(), 0.0, 0.0,
-                                                  s.data(), diag_cc.data(), cost.data()) != ICG_OK ||
-                icg_reproj_host_parts_build(ctx, P, Pw.data(), rebuild.data(), blk_off.data(), nr.data(), nf.data(), cols.data(), jac_off.data(), J.data(),
-                                            r.data(), host_s.data(), host_diag.data(), nullptr) != ICG_OK ||
-                icg_reproj_landmark_diag_windows(ctx, hll.data()) != ICG_OK)
+                                                  s.data(), diag_cc.data(), cost.data()) != ICG_OK)
+                return fail(icg_last_error(ctx));
+            if (dev_prior) {
+                // the taken priors are evaluated where they lie (e = e0 + J0 dx at the packed point), their blocks take residual and Jacobian
+                // columns from there, and the first guard's minimum comes back as one double per window
+                std::vector<double> sq((size_t) std::max(n_device_priors_, 1));
+                std::string what;
+                if (n_device_priors_ > 0 && !prior_set_.evaluateResident(sq.data(), &what)) return fail(what);
+                min_dev.assign(NW, 0.0);
+                if (icg_reproj_host_parts_build_prior(ctx, P, Pw.data(), rebuild.data(), blk_off.data(), nr.data(), nf.data(), cols.data(), jac_off.data(),
+                                                      J.data(), r.data(), host_s.data(), host_diag.data(), nullptr,
+                                                      n_device_priors_ > 0 ? prior_of.data() : nullptr, prior_cols.data()) != ICG_OK ||
+                    icg_reproj_landmark_min_windows(ctx, min_dev.data()) != ICG_OK)
+                    return fail(icg_last_error(ctx));
+            } else if (icg_reproj_host_parts_build(ctx, P, Pw.data(), rebuild.data(), blk_off.data(), nr.data(), nf.data(), cols.data(), jac_off.data(),
+                                                   J.data(), r.data(), host_s.data(), host_diag.data(), nullptr) != ICG_OK ||
+                       icg_reproj_landmark_diag_windows(ctx, hll.data()) != ICG_OK)
                 return fail(icg_last_error(ctx));
         } else {
             S.assign(NW * (size_t) P * P, 0.0);
@@ -379,9 +446,13 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
                 plan.b[(size_t) i] += sw[i];
             }
         }
-        double mn = W.landmarks.empty() ? 0.0 : hll[(size_t) W.lm_begin];
-        for (size_t l = 0; l < W.landmarks.size(); l++) mn = std::min(mn, hll[(size_t) W.lm_begin + l]);
-        min_hll[w] = mn;
+        if (dev_prior) { // (reduced on the device, icg_reproj_landmark_min_windows: the value of the loop below)
+            min_hll[w] = min_dev[w];
+        } else {
+            double mn = W.landmarks.empty() ? 0.0 : hll[(size_t) W.lm_begin];
+            for (size_t l = 0; l < W.landmarks.size(); l++) mn = std::min(mn, hll[(size_t) W.lm_begin + l]);
+            min_hll[w] = mn;
+        }
         added[w]   = 1;
     };
     DeviceM3 dev{std::vector<char>(NW, 0), {}, {}, {}, {}, std::vector<size_t>(NW, 0), std::vector<size_t>(NW, 0), std::vector<int>(NW, -1), 0};
@@ -394,6 +465,7 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
         if (!linearizeOnDevice(st, added, min_hll, dev, &what, resident ? &rhs : nullptr)) return fail(what);
         kept_id_ = dev.keep_id;
     }
+    std::atomic<int> n_deferred{0};
     factors_.forEachWindow(NW, [&](size_t w) {
         if (!st[w].alive) return;
         Slice &W               = *windows_[w];
@@ -415,6 +487,15 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
             structured[w] = done ? 1 : 0;
         }
         if (!done) {
+            // (setDevicePrior: the window left the structured device path, so its prior is evaluated on the pool after all — only here)
+            if (taken[w]) {
+                n_deferred++;
+                if (!I.evaluateDeferred()) {
+                    I.isvalid_ = false;
+                    I.releaseMemory();
+                    return;
+                }
+            }
             if (!I.constructEquation()) { // (:88-92 with the window's own dense assembly on the device)
                 I.isvalid_ = false;
                 I.releaseMemory();
@@ -430,6 +511,7 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     for (size_t w = 0; w < NW; w++)
         if (good[w]) windows_[w]->info->releaseMemoryInto(retired_);
     auto t4 = now();
+    n_deferred_evaluations_ = n_deferred.load();
     for (size_t w = 0; w < NW; w++) {
         windows_[w]->evaluated = false;
         if (good[w]) (structured[w] ? n_structured_ : n_dense_)++;

@@ -17,6 +17,10 @@
 // A window whose marginalized set does not have the structure of gvinsMarginalization, or that fails the conditioning guard, takes the
 // reference's dense M2 + M3 on its own (a one-window context created on first use) — the same rule MarginalizationInfo applies alone.
 // Results per window are those of MarginalizationInfo::marginalization() on a ReprojectionBatch of its own (tests: Hp, bp, J0, e0).
+//
+// Options, all off by default, each pinned bit for bit against the one before it: setDeviceLinearization (step 4 in one device call),
+// setKeepLinearized (J0 / e0 stay on the device), setDeviceReducedSystem (S and the host factors' J^T J stay on the device), setDevicePrior
+// (the previous marginalization's prior is evaluated and gathered on the device; the first guard's minimum is reduced there).
 #pragma once
 #include <memory>
 #include <mutex>
@@ -89,10 +93,34 @@ public:
     bool deviceReducedSystem() const { return device_reduced_system_; }
     static bool deviceReducedSystemAvailable();
 
+    // With the device-resident reduced system (default off; marginalize() fails with a message without setDeviceReducedSystem(true), or —
+    // naming the entry — when icg_marg_prior_set, icg_marg_prior_evaluate_resident, icg_reproj_host_parts_build_prior or
+    // icg_reproj_landmark_min_windows is not in the build): the prior the previous marginalization left is read from the device.  Each
+    // window hands over its first host factor whose cost function is a MargPriorSource, that has no loss function and whose view describes
+    // the residual block (WindowSolverBatch::layout's test); a robustified prior and a second prior stay on the pool.  The views of the
+    // taken priors form ONE resident MarginalizationPriorSet on the batch's context — tagged views take J0 / e0 from the linearization
+    // setKeepLinearized kept (it is released only after the set is built), untagged ones are shipped once.  Step 2 snapshots the prior's
+    // blocks but does not evaluate it and emits its block without Jacobian or residual; step 3 evaluates the set at the blocks' current
+    // values (icg_marg_prior_evaluate_resident, between the Schur call and the host parts), builds the host parts with the prior's block
+    // gathered from J0 on the device (icg_reproj_host_parts_build_prior, ICG_HP_JAC_FROM_PRIOR) and takes the first guard's minimum per window
+    // from the device (icg_reproj_landmark_min_windows) instead of reading every landmark diagonal back.  A window that leaves the
+    // structured device path (not planned, a failed guard, the QL cap, forced dense) runs the deferred Evaluate() on the pool before its
+    // dense path; no other window does.  Up: x and the other host factors' blocks; the prior's residual and r x r Jacobian cross nothing.
+    // Every output bit, ok, the tags and the structured / dense counts are those of setDeviceReducedSystem(true) alone, and it composes
+    // with setKeepLinearized.  Resident cost: the set's copy (2 r^2 + r doubles per prior) in the batch's context until the next set
+    // replaces it or the batch is destroyed.
+    void setDevicePrior(bool on) { device_prior_ = on; }
+    bool devicePrior() const { return device_prior_; }
+    static bool devicePriorAvailable();
+
     // diagnostics of the last marginalize(): windows that took the landmark-eliminated device path / the dense path; wall time of the
-    // four phases above [ms]
+    // four phases above [ms]; setDevicePrior: priors handed to the device, those of them the set took from the kept linearization, and
+    // deferred host evaluations that ran
     int structuredWindows() const { return n_structured_; }
     int denseWindows() const { return n_dense_; }
+    int devicePriors() const { return n_device_priors_; }
+    int devicePriorsFromKept() const { return n_priors_from_kept_; }
+    int deferredPriorEvaluations() const { return n_deferred_evaluations_; }
     const double *lastPhaseMs() const { return phase_ms_; }
     icg_ctx *context() const { return factors_.ctx(); } // the batch's partitioned context (its profiler: icg_prof_enable / icg_prof_get)
     const std::string &error() const { return error_; }
@@ -132,8 +160,10 @@ private:
     double huber_{1.0};
     std::vector<std::unique_ptr<Slice>> windows_;
     bool laid_out_{false};
-    bool device_linearization_{false}, keep_linearized_{false}, device_reduced_system_{false};
+    bool device_linearization_{false}, keep_linearized_{false}, device_reduced_system_{false}, device_prior_{false};
     uint64_t kept_id_{0};
+    MarginalizationPriorSet prior_set_; // setDevicePrior: the taken priors of the last marginalize(), resident in factors_'s context
+    int n_device_priors_{0}, n_priors_from_kept_{0}, n_deferred_evaluations_{0};
     std::vector<std::shared_ptr<ResidualBlockInfo>> retired_; // factor records of marginalized windows, freed by clear() / the destructor
     int n_structured_{0}, n_dense_{0};
     double phase_ms_[4]{0, 0, 0, 0};

@@ -26,6 +26,7 @@ EXPORTS = [
     "icg_chol_solve_batch", "icg_reproj_schur_windows_resident", "icg_reproj_solve_windows", "icg_reproj_host_parts_build",
     "icg_marg_prior_evaluate_resident", "icg_reproj_host_parts_build_prior",
     "icg_marg_linearize_batch_keep", "icg_marg_linearized_release", "icg_marg_prior_set_from_kept", "icg_marg_linearize_resident",
+    "icg_reproj_landmark_min_windows",
 ]
 
 
@@ -559,6 +560,16 @@ class Context:
         h = np.zeros(n_lm)
         self._ck(self.lib.icg_reproj_landmark_diag_windows(self.h, _p(h)), "icg_reproj_landmark_diag_windows")
         return h
+
+    def reproj_landmark_min_windows_raw(self, out):
+        """icg_reproj_landmark_min_windows into the caller's array (one double per window) -> the return code"""
+        return self.lib.icg_reproj_landmark_min_windows(self.h, _p(out))
+
+    def reproj_landmark_min_windows(self):
+        """icg_reproj_landmark_min_windows: the smallest h_ll of every window of the partition (0.0 for a window without landmarks)"""
+        mn = np.zeros(self._nwin)
+        self._ck(self.reproj_landmark_min_windows_raw(mn), "icg_reproj_landmark_min_windows")
+        return mn
 
     def reproj_cost_windows(self, active=None):
         cost = np.zeros(self._nwin)

@@ -321,6 +321,14 @@ int icg_reproj_cost_windows(icg_ctx *ctx, const uint8_t *active, double *cost);
  * icg_reproj_schur_windows*: icg_reproj_landmark_diag for many windows — the conditioning guard of the batched M3
  * (factors/marginalization_info.h:170-192 for the marginalizations of many streams, host/marg_batch.h). */
 int icg_reproj_landmark_diag_windows(icg_ctx *ctx, double *h_ll);
+/* The smallest of those diagonals per window (min_hll: W doubles), reduced on the device: the value the first conditioning guard of the
+ * batched M3 tests (factors/marginalization_info.h:170-192, host/marg_batch.h step 4), so that one double per window crosses the link
+ * instead of one per landmark.  Defined by the host loop over the window's landmarks in order,
+ *     mn = h_ll[first];  mn = (h_ll[l] < mn) ? h_ll[l] : mn;
+ * a NaN in the first landmark yields NaN, a NaN elsewhere is ignored, a window without landmarks gives 0.0.  Equal to that loop as a value;
+ * the sign of a zero minimum is not specified.  ICG_ERR_INVALID as icg_reproj_landmark_diag_windows (no partition, no resident window
+ * systems): nothing is launched and min_hll is not touched. */
+int icg_reproj_landmark_min_windows(icg_ctx *ctx, double *min_hll);
 /* the resident residuals of the last evaluation (n x 2 doubles): per-factor tests (chi-square culling) after a resident evaluation */
 int icg_reproj_fetch_residuals(icg_ctx *ctx, double *out_r);
 /* GVINS::removeReprojectionFactorsByChi2 (ic_gvins.cc:1269-1297) on the resident residuals of a want_jac = 0, huber = 0 evaluation:
