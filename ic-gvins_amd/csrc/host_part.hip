@@ -9,7 +9,8 @@
 // on the batch it is built in.  The Jacobians stay on the device (icg_hp_kept): a block whose Jacobian did not change crosses the link as
 // its residuals only.  A block that is a marginalization prior resident on the device (marg.hip) crosses it not at all
 // (icg_reproj_host_parts_build_prior): k_host_part_prior copies its residuals of the last resident evaluation and the free columns of its J0
-// to the places k_host_part reads.
+// to the places k_host_part reads.  The same kernel serves a block that is a preintegration factor of the resident P2 set (preint.hip,
+// icg_reproj_host_parts_build_preint): its source matrix is the factor's whitened 15 x 32 Jacobian, its row stride 32.
 #include "reproj_internal.h"
 
 #define HP_THREADS 256
@@ -31,11 +32,14 @@ struct hp_blk {
 struct hp_copy {
     int64_t src, dst, n;
 };
-#define HP_PRIOR_ROWS 16 // rows of a prior block per workgroup of k_host_part_prior
+#define HP_PRIOR_ROWS 16 // rows of a resident block per workgroup of k_host_part_prior
+// A block whose residual and Jacobian are resident on the device: a marginalization prior (J = its J0, row stride r) or a preintegration factor
+// of the resident P2 set (J = its whitened 15 x 32 Jacobian, row stride 32).
 struct hp_prior {
-    int64_t J0_off, Jd_off;           // the prior's J0 in the resident set; the block's place among the kept Jacobians
-    int32_t e_off, r_off, pc_off, nr; // its residuals in the set; the block's place in the staged r; its columns of J0 in prior_cols
-    int32_t nf, fill;                 // fill != 0: the kept Jacobian is gathered from J0 (ICG_HP_JAC_FROM_PRIOR)
+    const double *J, *res;        // the block's source matrix and residuals on the device
+    int64_t Jd_off;               // the block's place among the kept Jacobians
+    int32_t stride, r_off, pc_off; // row stride of J; the block's place in the staged r; its columns of J in the staged column list
+    int32_t nr, nf, fill;         // fill != 0: the kept Jacobian is gathered from J (ICG_HP_JAC_FROM_PRIOR / ICG_HP_JAC_FROM_PREINT)
 };
 
 // the shipped Jacobians move from the staging arena to their places among the kept ones: one workgroup per shipped block
@@ -140,25 +144,26 @@ __global__ __launch_bounds__(HP_THREADS) void k_host_part(const hp_win *wins, co
     }
 }
 
-// A block that is a resident marginalization prior (icg_marg_prior_set), for the row tile blockIdx.x of the prior block blockIdx.y: the kept
-// Jacobian is gathered from the prior's row-major J0 where the block asks for it (Jd[k][y] = J0[k][pc[y]]: the elements of a tile are
-// consecutive in Jd, so the writes are contiguous along y and across the rows of the tile), and the residuals of the last resident evaluation
-// are copied to the block's place in the staged r.  A plain copy without atomics, ahead of k_host_part.
-__global__ __launch_bounds__(HP_THREADS) void k_host_part_prior(const hp_prior *pr, const int32_t *pcols, const double *J0, const double *res, double *Jd, double *r) {
+// A block that is resident on the device (a marginalization prior of icg_marg_prior_set, a factor of icg_preint_set), for the row tile
+// blockIdx.x of the resident block blockIdx.y: the kept Jacobian is gathered from the block's row-major source matrix where the block asks for it
+// (Jd[k][y] = J[k][pc[y]]: the elements of a tile are consecutive in Jd, so the writes are contiguous along y and across the rows of the tile),
+// and the residuals of the last resident evaluation are copied to the block's place in the staged r.  A plain copy without atomics, ahead of
+// k_host_part.
+__global__ __launch_bounds__(HP_THREADS) void k_host_part_prior(const hp_prior *pr, const int32_t *pcols, double *Jd, double *r) {
     __shared__ int32_t pc[HP_MAX_P]; // (nf <= HP_MAX_P: the entry's capacity check)
     const hp_prior B = pr[blockIdx.y];
     const int k0 = blockIdx.x * HP_PRIOR_ROWS, t = threadIdx.x;
-    if (k0 >= B.nr) return; // (a shorter prior than the longest of the call: uniform over the workgroup)
+    if (k0 >= B.nr) return; // (a shorter block than the longest of the call: uniform over the workgroup)
     const int kc = min(HP_PRIOR_ROWS, B.nr - k0);
-    if (t < kc) r[B.r_off + k0 + t] = res[B.e_off + k0 + t];
+    if (t < kc) r[B.r_off + k0 + t] = B.res[k0 + t];
     if (!B.fill) return;
     for (int y = t; y < B.nf; y += HP_THREADS) pc[y] = pcols[B.pc_off + y];
     __syncthreads();
-    const double *src = J0 + B.J0_off + (size_t) k0 * B.nr; // (J0 is nr x nr)
+    const double *src = B.J + (size_t) k0 * B.stride;
     double *dst       = Jd + B.Jd_off + (size_t) k0 * B.nf;
     for (int e = t; e < kc * B.nf; e += HP_THREADS) {
         const int k = e / B.nf, y = e - k * B.nf;
-        dst[e]      = src[(size_t) k * B.nr + pc[y]];
+        dst[e]      = src[(size_t) k * B.stride + pc[y]];
     }
 }
 
@@ -171,8 +176,16 @@ extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *P
 extern "C" int icg_reproj_host_parts_build_prior(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
                                                  const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r,
                                                  double *host_s, double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols) {
+    return icg_reproj_host_parts_build_preint(ctx, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, prior_of, prior_cols, nullptr,
+                                              nullptr);
+}
+
+extern "C" int icg_reproj_host_parts_build_preint(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
+                                                  const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r,
+                                                  double *host_s, double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols,
+                                                  const int32_t *preint_of, const int32_t *preint_cols) {
     if (!ctx) return ICG_ERR_INVALID;
-    const char *me = prior_of ? "icg_reproj_host_parts_build_prior" : "icg_reproj_host_parts_build";
+    const char *me = preint_of ? "icg_reproj_host_parts_build_preint" : prior_of ? "icg_reproj_host_parts_build_prior" : "icg_reproj_host_parts_build";
     icg_partition &pt = ctx->part_w;
     const int W       = pt.W;
     if (W <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: no window partition: call icg_reproj_set_windows first", me);
@@ -202,6 +215,11 @@ extern "C" int icg_reproj_host_parts_build_prior(icg_ctx *ctx, int P, const int3
     std::vector<std::pair<int, int>> prior_at;  // their (window, position in the window's block list)
     size_t pc_at = 0;
     int max_prior_nr = 0;
+    // preintegration blocks: the same walk over preint_cols; their entries follow prior_cols in the staged column list (ppc_at counts from 0
+    // here, the kernel's offsets are shifted once pc_at is known)
+    const icg_preint_resident &ps = ctx->preint;
+    std::vector<size_t> preint_idx; // positions in `priors` of the blocks that are preintegration factors
+    size_t ppc_at = 0;
     for (int w = 0; w < W; w++) {
         const std::vector<icg_hp_block> *kept = have_kept ? &hp.win[(size_t) w] : nullptr;
         const int cnt                         = blk_off[w + 1] - blk_off[w];
@@ -218,6 +236,9 @@ extern "C" int icg_reproj_host_parts_build_prior(icg_ctx *ctx, int P, const int3
             const int pp     = prior_of ? prior_of[b] : -1; // >= 0: the block is prior pp of the resident set
             const size_t pc0 = pc_at;
             if (pp >= 0) pc_at += (size_t) nf[b]; // (at most the columns of all blocks: below 2^31)
+            const int fp      = preint_of ? preint_of[b] : -1; // >= 0: the block is factor fp of the resident P2 set
+            const size_t ppc0 = ppc_at;
+            if (fp >= 0) ppc_at += (size_t) nf[b];
             if (!rebuild[w]) continue;
             if (nf[b] > Pw[w]) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d columns in a system of %d", me, w, p, nf[b], Pw[w]);
             for (int x = 0; x < nf[b]; x++) {
@@ -238,16 +259,40 @@ extern "C" int icg_reproj_host_parts_build_prior(icg_ctx *ctx, int P, const int3
                     const int c = prior_cols[pc0 + (size_t) x];
                     if (c < 0 || c >= pr) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: prior column %d outside the prior (%d)", me, w, p, c, pr);
                 }
-                priors.push_back({ms.h_j_off[(size_t) pp], 0 /* its place among the kept Jacobians follows below */, ms.h_e_off[(size_t) pp],
-                                  r_off[(size_t) b], (int32_t) pc0, nr[b], nf[b], jac_off[b] == ICG_HP_JAC_FROM_PRIOR ? 1 : 0});
+                priors.push_back({ms.d_J + ms.h_j_off[(size_t) pp], ms.d_res + ms.h_e_off[(size_t) pp], 0 /* its place among the kept Jacobians follows below */,
+                                  pr /* J0 is r x r */, r_off[(size_t) b], (int32_t) pc0, nr[b], nf[b], jac_off[b] == ICG_HP_JAC_FROM_PRIOR ? 1 : 0});
                 prior_at.push_back({w, p});
                 max_prior_nr = std::max(max_prior_nr, nr[b]);
+            }
+            if (fp >= 0) {
+                if (pp >= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both a prior (%d) and a preintegration factor (%d)", me, w, p, pp, fp);
+                if (!preint_cols) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a preintegration block without preint_cols", me, w, p);
+                const bool fill = jac_off[b] == ICG_HP_JAC_FROM_PREINT;
+                if (ps.n <= 0 || !ps.res_valid || (fill && !ps.jac_valid))
+                    return icg_fail(ctx, ICG_ERR_INVALID,
+                                    "%s: window %d, block %d: no preintegration set is resident and evaluated%s (icg_preint_set, then icg_preint_evaluate_resident)", me, w,
+                                    p, fill ? " with Jacobians" : "");
+                if (fp >= ps.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: factor %d outside the resident set of %d", me, w, p, fp, ps.n);
+                if (nr[b] != 15) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, a preintegration factor has 15", me, w, p, nr[b]);
+                for (int x = 0; x < nf[b]; x++) {
+                    const int c = preint_cols[ppc0 + (size_t) x];
+                    if (c < 0 || c >= 32 || c == 6 || c == 22)
+                        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: preintegration column %d (0 .. 31 without 6 and 22)", me, w, p, c);
+                }
+                preint_idx.push_back(priors.size());
+                priors.push_back({ps.d_jac ? ps.d_jac + 480 * (size_t) fp : nullptr, ps.d_res + 15 * (size_t) fp, 0, 32, r_off[(size_t) b], (int32_t) ppc0, 15, nf[b], fill ? 1 : 0});
+                prior_at.push_back({w, p});
+                max_prior_nr = std::max(max_prior_nr, 15);
             }
             if (jac_off[b] >= 0) {
                 if (!J) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a Jacobian offset without J", me, w, p);
                 ship_doubles += (size_t) nr[b] * nf[b], n_ship++;
             } else if (jac_off[b] == ICG_HP_JAC_FROM_PRIOR && pp >= 0) {
                 // gathered from the prior's J0 on the device
+            } else if (jac_off[b] == ICG_HP_JAC_FROM_PREINT && fp >= 0) {
+                // gathered from the factor's resident Jacobian on the device
+            } else if (jac_off[b] == ICG_HP_JAC_FROM_PREINT) {
+                return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: ICG_HP_JAC_FROM_PREINT for a block that is no preintegration factor", me, w, p);
             } else if (jac_off[b] == -1) {
                 any_keep = true;
                 if (!kept || (size_t) p >= kept->size()) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no kept Jacobian", me, w, p);
@@ -332,20 +377,27 @@ extern "C" int icg_reproj_host_parts_build_prior(icg_ctx *ctx, int P, const int3
             }
         }
         for (size_t k = 0; k < priors.size(); k++) priors[k].Jd_off = next[(size_t) prior_at[k].first][(size_t) prior_at[k].second].off;
+        for (size_t k : preint_idx) priors[k].pc_off += (int32_t) (prior_cols ? pc_at : 0); // (preint_cols is staged behind prior_cols)
     }
     const size_t n_r = (size_t) r_off[(size_t) nb], n_c = (size_t) c_off[(size_t) nb];
     icg_call c(ctx);
     if ((rc = c.reserve(sizeof(hp_win) * wins.size() + sizeof(hp_blk) * blks.size() + sizeof(hp_copy) * copies.size() + sizeof(hp_prior) * priors.size() +
-                        sizeof(int32_t) * (n_c + pc_at) + sizeof(double) * (n_r + ship_doubles + 2 * (size_t) n_rebuilt * P + out_cells) + 20 * 256)))
+                        sizeof(int32_t) * (n_c + pc_at + ppc_at) + sizeof(double) * (n_r + ship_doubles + 2 * (size_t) n_rebuilt * P + out_cells) + 20 * 256)))
         return rc;
     const hp_win *d_wins  = c.in(wins.data(), wins.size());
     const hp_blk *d_blks  = c.in(blks.data(), blks.size());
     const hp_copy *d_cp   = c.in(copies.data(), copies.size());
     const int32_t *d_cols = c.in(cols, n_c);
     const hp_prior *d_pr  = c.in(priors.data(), priors.size());
-    const int32_t *d_pc   = priors.empty() ? nullptr : c.in(prior_cols, pc_at);
+    const int32_t *d_pc   = nullptr;
+    if (!priors.empty()) { // prior_cols | preint_cols, of all windows (either may be absent)
+        std::vector<int32_t> pcs;
+        if (prior_cols) pcs.assign(prior_cols, prior_cols + pc_at);
+        if (preint_cols) pcs.insert(pcs.end(), preint_cols, preint_cols + ppc_at);
+        d_pc = c.in(pcs.data(), pcs.size());
+    }
     double *d_r           = nullptr;
-    if (!prior_of) {
+    if (!prior_of && !preint_of) {
         d_r = c.in(r, n_r);
     } else {
         // The slots of the prior blocks (of every window, rebuilt or not) are placed but not read from the caller: staged block by block,
@@ -355,7 +407,8 @@ extern "C" int icg_reproj_host_parts_build_prior(icg_ctx *ctx, int P, const int3
         const size_t off = icg_arena_alloc(ctx, sizeof(double) * n_r);
         double *h        = icg_h<double>(ctx, off);
         for (int b = 0; b < nb; b++)
-            if (prior_of[b] < 0) memcpy(h + r_off[(size_t) b], r + r_off[(size_t) b], sizeof(double) * (size_t) nr[b]);
+            if ((!prior_of || prior_of[b] < 0) && (!preint_of || preint_of[b] < 0))
+                memcpy(h + r_off[(size_t) b], r + r_off[(size_t) b], sizeof(double) * (size_t) nr[b]);
         c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * n_r);
         d_r = icg_d<double>(ctx, off);
     }
@@ -386,7 +439,7 @@ extern "C" int icg_reproj_host_parts_build_prior(icg_ctx *ctx, int P, const int3
     if (!priors.empty()) { // (its places among the kept Jacobians and in r are not the shipped blocks')
         icg_prof_scope ps(ctx, "host_part_prior");
         hipLaunchKernelGGL(k_host_part_prior, dim3((unsigned) ((max_prior_nr + HP_PRIOR_ROWS - 1) / HP_PRIOR_ROWS), (unsigned) priors.size()), dim3(HP_THREADS), 0,
-                           ctx->stream, d_pr, d_pc, (const double *) ms.d_J, (const double *) ms.d_res, hp.d_J[dst], d_r);
+                           ctx->stream, d_pr, d_pc, hp.d_J[dst], d_r);
     }
     {
         icg_prof_scope ps(ctx, "host_part");

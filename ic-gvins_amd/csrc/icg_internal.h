@@ -79,6 +79,19 @@ struct icg_marg_set {
     std::vector<int64_t> h_j_off;
 };
 
+// Resident preintegration factors (preint.hip): everything icg_preint_evaluate_resident needs besides the evaluation points and the
+// correction quaternions, in one buffer that grows on demand and is freed with the context; n = 0: no set is resident.  The results of the
+// last evaluation stay in d_res (15 per factor) and d_jac (15 x 32 row-major per factor).
+struct icg_preint_resident {
+    int n = 0;
+    int64_t total_pn = 0; // rows of pn
+    char *d_set = nullptr; // delta_state 16n | jac 225n | sqrt_info 225n | delta_time n | env 4n | q_nn 4n | pn 4 total_pn | pn_offsets n+1 | variant n
+    size_t set_cap = 0;    // bytes
+    double *d_res = nullptr, *d_jac = nullptr;
+    size_t res_cap = 0, jac_cap = 0; // bytes
+    bool res_valid = false, jac_valid = false; // evaluated (with Jacobians) since the set was made resident
+};
+
 // The linearization icg_marg_linearize_batch_keep left on the device (marg_linearize.hip): J0 of every window (r x r row-major, window after
 // window), then e0 of every window, in one buffer the context owns.  id = 0: nothing is kept.  A live id is listed in the process-wide table
 // of ctx.hip (icg_kept_register / icg_kept_drop / icg_kept_lookup), through which icg_marg_prior_set_from_kept of any context finds it.
@@ -169,6 +182,7 @@ struct icg_ctx {
     size_t lmwin_cap = 0; // bytes
 
     icg_marg_set marg;
+    icg_preint_resident preint;
     // M3 (marg_linearize.hip): per-window working memory of icg_marg_linearize_batch for the windows that do not fit in LDS; grows on demand
     double *d_lin_scratch = nullptr;
     size_t lin_scratch_cap = 0; // bytes

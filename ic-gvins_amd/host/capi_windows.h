@@ -169,14 +169,14 @@ struct VioWindow {
     }
 };
 // the window's states and its preintegration objects (imu rows of 8, interval k owns rows [offsets[k], offsets[k+1])), each also appended to
-// `raw` for the one Preintegration::integrateBatch of the entry
+// `raw` for the one Preintegration::integrateBatch of the entry; variant: 0 Normal, 1 Earth, for every interval
 VioWindow vio_window(int n_intervals, const int32_t *offsets, const double *imu, const std::shared_ptr<icg::IntegrationParameters> &params,
-                     const double *states16, std::vector<icg::Preintegration *> &raw) {
+                     const double *states16, std::vector<icg::Preintegration *> &raw, int variant = 0) {
     VioWindow W;
     W.K = n_intervals + 1;
     W.take(states16);
     for (int k = 0; k < n_intervals; k++) {
-        W.pre.push_back(preint_interval(0, params, offsets, imu, k, states16 + 16 * (size_t) k));
+        W.pre.push_back(preint_interval(variant, params, offsets, imu, k, states16 + 16 * (size_t) k));
         raw.push_back(W.pre.back().get());
     }
     return W;
@@ -196,12 +196,12 @@ void vio_blocks(S &&s, VioWindow &W, double *ext, int n_lm, double *invdepth, do
     s.setParameterBlockConstant(td);
 }
 // The window's host factors come in two parts, so that an entry can put a block of its own between them or behind them: the preintegration
-// factors and the pose prior on state 0, ...
+// factors (optionally behind a loss function) and the pose prior on state 0, ...
 template <class S>
-void vio_motion_factors(S &&s, VioWindow &W, const double *prior_pose0, double prior_weight) {
+void vio_motion_factors(S &&s, VioWindow &W, const double *prior_pose0, double prior_weight, std::shared_ptr<ceres::LossFunction> preint_loss = nullptr) {
     using icg::PreintegrationFactor;
     for (int k = 0; k + 1 < W.K; k++)
-        s.addResidualBlock(std::make_shared<PreintegrationFactor>(W.pre[(size_t) k]), nullptr,
+        s.addResidualBlock(std::make_shared<PreintegrationFactor>(W.pre[(size_t) k]), preint_loss,
                            {&W.pose[7 * (size_t) k], &W.mix[9 * (size_t) k], &W.pose[7 * (size_t) (k + 1)], &W.mix[9 * (size_t) (k + 1)]});
     pose_prior(s, &W.pose[0], prior_pose0, prior_weight);
 }

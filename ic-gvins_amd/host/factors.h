@@ -438,8 +438,22 @@ public:
     const vector<IMU> &imuBuffer() const { return imu_buffer_; }
     // PreintegrationFactor::Evaluate body (preintegration_factor.h:45-69): residual 15, Jacobians 15x7,15x9,15x7,15x9
     bool evaluate(const double *const *parameters, double *residuals, double **jacobians) const;
+    // The only two places of evaluate() where sin / cos / sqrt enter, as unit quaternions (x, y, z, w), formed with evaluate()'s own
+    // expressions: the bias correction of delta q at mix0 (v3, bg3, ba3), rotvec2quat(dq_dbg (bg0 - delta.bg)), and the Earth variant's
+    // rotvec2quat(-iewn T), a constant of the integration result (identity, and unused, for the Normal variant).
+    void correctionQuaternion(const double *mix0, double q_xyzw[4]) const;
+    void earthRateQuaternion(double q_xyzw[4]) const;
+    // evaluate() with the two quaternions given: everything that is left is + - * / in a fixed order.  evaluate() is
+    // correctionQuaternion + earthRateQuaternion + evaluateGiven; a caller that evaluates on the device (icg_preint_set /
+    // icg_preint_evaluate_resident) ships the quaternions instead of calling sin / cos there.
+    bool evaluateGiven(const double *const *parameters, const double q_corr[4], const double q_nn[4], double *residuals, double **jacobians) const;
     Variant variant() const { return variant_; }
     const vector<double> &sqrtInformation() const { return sqrt_information_; } // 15x15 row-major; zeros while the covariance is singular
+    // what a resident set packs besides deltaState(), deltaTime(), sqrtInformation() and earthRate()
+    bool ready() const { return !dirty_ && sqrt_information_ok_; } // integrated for the current buffer / start state, covariance not singular
+    const vector<double> &jacobian() const { return jacobian_; }   // 15x15 row-major
+    double gravity() const { return parameters_->gravity; }
+    const vector<double> &pnRows() const { return pn_; }           // Earth variant: rows of 4 (dt, position); evaluate() sums the complete rows
 
 private:
     std::shared_ptr<IntegrationParameters> parameters_;
@@ -461,9 +475,34 @@ public:
     bool Evaluate(const double *const *parameters, double *residuals, double **jacobians) const override {
         return preintegration_->evaluate(parameters, residuals, jacobians);
     }
+    // what a solver that evaluates the factor on the device (WindowSolverBatch::setDevicePreintegration) packs its resident set from
+    const Preintegration &preintegration() const { return *preintegration_; }
 
 private:
     std::shared_ptr<Preintegration> preintegration_;
+};
+
+// The preintegration factors of many windows resident on the device for a solve (icg_preint_set / icg_preint_evaluate_resident): set() at the
+// head of the solve, pack() + evaluateResident() per LM point.  The device gets the host's square-root information and the two quaternions
+// of Preintegration::evaluate that need sin / cos (earthRateQuaternion with the set, correctionQuaternion with every point); its residuals,
+// Jacobians and squared norms are then the bits of Preintegration::evaluate.  The results stay on the device for
+// icg_reproj_host_parts_build_preint; only one squared norm per factor comes back.  The C entries are referenced weakly: in a build of this
+// layer on a C ABI without them available() is false, missingEntry() names the first that is absent and set() fails by that name.
+class PreintegrationSet {
+public:
+    static bool available();
+    static const char *missingEntry(); // nullptr when available()
+    // every factor must be ready() (integrated, covariance not singular); the objects must outlive the set's use
+    bool set(icg_ctx *ctx, const vector<const Preintegration *> &list, std::string *err = nullptr);
+    // factor f's evaluation point (pose0, mix0, pose1, mix1) and its correction quaternion to their places (any thread, before the call)
+    void pack(size_t f, const double *const *parameters);
+    bool evaluateResident(bool want_jac, double *sq_norm, std::string *err = nullptr);
+    int factors() const { return (int) list_.size(); }
+
+private:
+    icg_ctx *ctx_{nullptr};
+    vector<const Preintegration *> list_;
+    vector<double> points_, q_corr_;
 };
 
 } // namespace icg

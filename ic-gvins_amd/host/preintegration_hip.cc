@@ -3,6 +3,9 @@
 // preintegration_factor.h:45-69) is a handful of 3x3 / 15x15 operations per factor (<= 15 factors per solve) and stays
 // on the host, in the Ceres callback thread that asks for it.  evaluateBatch() is the same evaluation for MANY factors at once on the
 // device (icg_preint_evaluate_batch): for callers that hold thousands of integrated intervals, not for the per-factor Ceres callback.
+// evaluate() is split at its two rotvec2quat calls (correctionQuaternion, earthRateQuaternion) from the rest (evaluateGiven): a driver that
+// keeps the factors resident on the device for a solve (PreintegrationSet, preint_set_hip.cc) ships the two quaternions, and the device
+// result has evaluate()'s bits.
 #include <cmath>
 #include <cstring>
 
@@ -313,9 +316,39 @@ void Preintegration::updateSqrtInformation() {
     sqrt_information_ok_ = true;
 }
 
+void Preintegration::correctionQuaternion(const double *mix0, double q_xyzw[4]) const {
+    M3 dq_dbg;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) dq_dbg.m[i][j] = jacobian_[(size_t) (6 + i) * 15 + 9 + j];
+    V3 bg0{mix0[3], mix0[4], mix0[5]}, dbg0{delta_state_.bg[0], delta_state_.bg[1], delta_state_.bg[2]};
+    V3 dbg = bg0 - dbg0;
+    Q4 q   = rotvec2quat(mv(dq_dbg, dbg));
+    q_xyzw[0] = q.x, q_xyzw[1] = q.y, q_xyzw[2] = q.z, q_xyzw[3] = q.w;
+}
+
+void Preintegration::earthRateQuaternion(double q_xyzw[4]) const {
+    Q4 q{0, 0, 0, 1};
+    if (variant_ == EARTH) {
+        V3 iewn{iewn_[0], iewn_[1], iewn_[2]};
+        const double T = delta_time_;
+        q              = rotvec2quat(-iewn * T);
+    }
+    q_xyzw[0] = q.x, q_xyzw[1] = q.y, q_xyzw[2] = q.z, q_xyzw[3] = q.w;
+}
+
 bool Preintegration::evaluate(const double *const *parameters, double *residuals, double **jacobians) const {
     if (dirty_) return false; // not integrated for the current buffer/start state: evaluation failed, loudly
     if (!sqrt_information_ok_) return false; // singular covariance
+    double q_corr[4], q_nn[4];
+    correctionQuaternion(parameters[1], q_corr);
+    earthRateQuaternion(q_nn);
+    return evaluateGiven(parameters, q_corr, q_nn, residuals, jacobians);
+}
+
+bool Preintegration::evaluateGiven(const double *const *parameters, const double q_corr[4], const double q_nn[4], double *residuals,
+                                   double **jacobians) const {
+    if (dirty_) return false;
+    if (!sqrt_information_ok_) return false;
     typedef double M15[15][15];
     M15 jac, S;
     memcpy(jac, jacobian_.data(), sizeof jac);
@@ -341,7 +374,7 @@ bool Preintegration::evaluate(const double *const *parameters, double *residuals
     V3 dbg = bg0 - dbg0, dba = ba0 - dba0;
     V3 corrected_p = dp + mv(dp_dba, dba) + mv(dp_dbg, dbg);
     V3 corrected_v = dv + mv(dv_dba, dba) + mv(dv_dbg, dbg);
-    Q4 corrected_q = qmul(dq, rotvec2quat(mv(dq_dbg, dbg)));
+    Q4 corrected_q = qmul(dq, Q4{q_corr[0], q_corr[1], q_corr[2], q_corr[3]});
     const double T = delta_time_;
 
     double r[15];
@@ -380,7 +413,7 @@ bool Preintegration::evaluate(const double *const *parameters, double *residuals
         for (size_t k = 0; k + 3 < pn_.size(); k += 4) p_cor = p_cor + (V3{pn_[k + 1], pn_[k + 2], pn_[k + 3]} - p0) * pn_[k];
         p_cor    = mv(scale(iewn_skew, 2.0), p_cor);
         V3 v_cor = mv(scale(iewn_skew, 2.0), p1 - p0);
-        Q4 qnn   = rotvec2quat(-iewn * T);
+        Q4 qnn   = Q4{q_nn[0], q_nn[1], q_nn[2], q_nn[3]};
         V3 dpn   = p1 - p0 - v0 * T - 0.5 * gravity * T * T + p_cor;
         V3 dvn   = v1 - v0 - gravity * T + v_cor;
         Q4 qb0b1 = qmul(qmul(qinv(q1), qnn), q0);

@@ -20,8 +20,16 @@
 #pragma weak icg_reproj_solve_windows
 #pragma weak icg_reproj_host_parts_build
 #pragma weak icg_reproj_host_parts_build_prior
+#pragma weak icg_reproj_host_parts_build_preint
 
 namespace icg {
+
+const char *WindowSolverBatch::devicePreintegrationMissing() {
+    if (!PreintegrationSet::available()) return PreintegrationSet::missingEntry();
+    return &icg_reproj_host_parts_build_preint == nullptr ? "icg_reproj_host_parts_build_preint" : nullptr;
+}
+
+bool WindowSolverBatch::devicePreintegrationAvailable() { return devicePreintegrationMissing() == nullptr; }
 
 using solver_detail::choleskySolve;
 
@@ -117,6 +125,8 @@ bool WindowSolverBatch::layout() {
         // the blocks of the window's host part: their shapes and columns follow from the problem, not from an evaluation
         W.host_blocks.clear(), W.host_cols.clear();
         W.prior_residual = W.prior_in_set = W.prior_block = -1;
+        W.preint_of_residual.assign(device_preint_ ? W.problem.residuals.size() : 0, -1), W.preint_of_block.clear(), W.preint_cols.clear();
+        int n_preint = 0; // (the window's own count: the set index follows once all windows are laid out)
         std::vector<int> cols;
         for (size_t id = 0; id < W.problem.residuals.size(); id++) {
             const solver_detail::Residual &R = W.problem.residuals[id];
@@ -134,9 +144,23 @@ bool WindowSolverBatch::layout() {
                 }
                 W.prior_residual = (int) id;
             }
+            // device preintegration: a factor without a loss whose integration result is there and can be whitened
+            const PreintegrationFactor *pf = device_preint_ && !R.loss ? dynamic_cast<const PreintegrationFactor *>(R.cost.get()) : nullptr;
+            const bool resident            = pf && pf->preintegration().ready() && R.blocks.size() == 4;
+            if (resident) W.preint_of_residual[id] = n_preint++;
             solver_detail::hostBlockColumns(W.problem, R, cols);
             if (cols.empty()) continue;
             if ((int) id == W.prior_residual) W.prior_block = (int) W.host_blocks.size();
+            W.preint_of_block.push_back(resident ? W.preint_of_residual[id] : -1);
+            if (resident) {
+                // the block's columns of the factor's 15 x 32 Jacobian (7 | 9 | 7 | 9): the free local columns of its non-constant blocks
+                static const int first[4] = {0, 7, 16, 23};
+                for (size_t a = 0; a < 4; a++) {
+                    const solver_detail::Block &A = W.problem.blocks[(size_t) W.problem.block_of.at(R.blocks[a])];
+                    if (A.column < 0) continue;
+                    for (int x = 0; x < A.local; x++) W.preint_cols.push_back(first[a] + x);
+                }
+            }
             W.host_blocks.push_back({(int) id, R.cost->num_residuals(), (int) cols.size(), 0, 0, 0});
             W.host_cols.insert(W.host_cols.end(), cols.begin(), cols.end());
         }
@@ -178,6 +202,22 @@ bool WindowSolverBatch::layout() {
                 if (A.column < 0) continue;
                 for (int x = 0; x < A.local; x++) hp_prior_cols_.push_back(v.index[a] + x);
             }
+        }
+        // device preintegration: the resident set holds the factors in window and residual order
+        preint_list_.clear(), preint_where_.clear(), hp_preint_cols_.clear();
+        hp_preint_of_.assign(hp_nr_.size(), -1);
+        for (size_t w = 0; w < windows_.size(); w++) {
+            Window &W      = windows_[w];
+            const int base = (int) preint_list_.size();
+            for (size_t id = 0; id < W.preint_of_residual.size(); id++) {
+                if (W.preint_of_residual[id] < 0) continue;
+                W.preint_of_residual[id] += base;
+                preint_list_.push_back(&static_cast<const PreintegrationFactor *>(W.problem.residuals[id].cost.get())->preintegration());
+                preint_where_.push_back({(int) w, (int) id});
+            }
+            for (size_t k = 0; k < W.preint_of_block.size(); k++)
+                if (W.preint_of_block[k] >= 0) hp_preint_of_[(size_t) W.blk_begin + k] = (W.preint_of_block[k] += base);
+            hp_preint_cols_.insert(hp_preint_cols_.end(), W.preint_cols.begin(), W.preint_cols.end());
         }
     }
     return P_ > 0;
@@ -235,6 +275,12 @@ struct WindowSolverBatch::Run {
         std::vector<uint8_t> gathered;
         std::string err;
     };
+    // device preintegration: r . r of every resident factor at the last evaluated point (their costs join DevicePrior::res_cost's sum)
+    struct DevicePreint {
+        bool on = false;
+        std::vector<double> sq;
+        std::string err;
+    };
 
     const Options &o;
     const ReducedPath path;
@@ -249,7 +295,9 @@ struct WindowSolverBatch::Run {
     DeviceSolve dev;
     DeviceParts hp;
     DevicePrior prior;
-    bool first = true;                                         // no window has its initial cost yet
+    DevicePreint preint;
+    bool deferred() const { return prior.on || preint.on; } // a device value takes a residual's place in the host cost: the pool records per residual
+    bool first = true;                                        // no window has its initial cost yet
     bool all_done = false, any_step = false, any_trial = false; // what solve() decides on after a phase
     BatchClock clk;
 
@@ -287,6 +335,14 @@ bool WindowSolverBatch::resolvePath(ReducedPath *path) {
         error_ = "setDevicePrior(true) needs setDeviceHostPart(true): the resident prior is read where the host parts are built";
         return false;
     }
+    if (device_preint_ && !devicePreintegrationAvailable()) {
+        error_ = std::string(devicePreintegrationMissing()) + " is not in this build";
+        return false;
+    }
+    if (device_preint_ && !device_host_part_) {
+        error_ = "setDevicePreintegration(true) needs setDeviceHostPart(true): the resident factors are read where the host parts are built";
+        return false;
+    }
     *path = device_host_part_ ? ReducedPath::DeviceSolveDeviceParts : device_reduced_ ? ReducedPath::DeviceSolve : ReducedPath::HostSolve;
     return true;
 }
@@ -319,8 +375,17 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
         Run::DevicePrior &D = R.prior;
         if (!prior_set_.set(factors_.ctx(), prior_views_, &error_)) return false;
         D.on = true;
-        D.sq.assign(prior_views_.size(), 0.0), D.gathered.assign(NW, 0), D.res_cost.resize(NW);
-        for (size_t w = 0; w < NW; w++) D.res_cost[w].assign(windows_[w].problem.residuals.size(), 0.0);
+        D.sq.assign(prior_views_.size(), 0.0), D.gathered.assign(NW, 0);
+    }
+    if (device_preint_ && !preint_list_.empty()) {
+        // the integration results become resident once per solve
+        if (!preint_set_.set(factors_.ctx(), preint_list_, &error_)) return false;
+        R.preint.on = true;
+        R.preint.sq.assign(preint_list_.size(), 0.0);
+    }
+    if (R.deferred()) {
+        R.prior.res_cost.resize(NW);
+        for (size_t w = 0; w < NW; w++) R.prior.res_cost[w].assign(windows_[w].problem.residuals.size(), 0.0);
     }
     for (;;) {
         if (!linearize(R) || !reducedSolves(R)) return false;
@@ -372,14 +437,16 @@ bool WindowSolverBatch::linearize(Run &R) {
         // runHalves); the sums that need both are formed after the join.
         R.clk.start();
         int dev_rc = ICG_OK;
-        bool prior_ok = true;
+        bool prior_ok = true, preint_ok = true;
         if (R.prior.on && any_lin) packPriors();
+        if (R.preint.on && any_lin) packPreintegrations();
         if (!side_) side_.reset(new SideThread());
         SideCall dev(*side_, [&] {
             if (R.deviceSolve()) {
                 dev_rc = icg_reproj_schur_windows_resident(ctx, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), R.reassemble.data(),
                                                            R.damp.data(), o.min_lm_diagonal, o.max_lm_diagonal, R.s.data(), R.diag.data(), R.cost.data());
                 if (dev_rc == ICG_OK && R.prior.on && any_lin) prior_ok = evaluatePriors(R);
+                if (dev_rc == ICG_OK && prior_ok && R.preint.on && any_lin) preint_ok = evaluatePreintegrations(R, true);
             } else
                 dev_rc = icg_reproj_schur_windows_view(ctx, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), R.reassemble.data(),
                                                        R.damp.data(), o.min_lm_diagonal, o.max_lm_diagonal, &R.S, R.s.data(), R.diag.data(), R.cost.data());
@@ -395,8 +462,8 @@ bool WindowSolverBatch::linearize(Run &R) {
         dev.join();
         R.clk.stop(PH_SCHUR_TAIL); // (what is left of the device call once the host half is through)
         if (dev_rc != ICG_OK) return fail(R.deviceSolve() ? "icg_reproj_schur_windows_resident" : "icg_reproj_schur_windows_view");
-        if (!prior_ok) {
-            error_ = R.prior.err;
+        if (!prior_ok || !preint_ok) {
+            error_ = !prior_ok ? R.prior.err : R.preint.err;
             return false;
         }
         if (host_failed.load()) {
@@ -406,7 +473,15 @@ bool WindowSolverBatch::linearize(Run &R) {
         if (R.deviceParts() && any_lin) {
             // the parts of the re-linearized windows, built in their slots on the device; s and diag of those windows come back
             R.clk.start();
-            if (R.prior.on) {
+            if (R.preint.on) {
+                // the resident factors' blocks take their residuals and Jacobians where they are (and so do the resident priors', if any)
+                if (icg_reproj_host_parts_build_preint(ctx, P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(),
+                                                       R.hp.jac_off.data(), R.hp.J.data(), R.hp.r.data(), R.hp.s.data(), R.hp.diag.data(), nullptr,
+                                                       R.prior.on ? hp_prior_of_.data() : nullptr, R.prior.on ? hp_prior_cols_.data() : nullptr, hp_preint_of_.data(),
+                                                       hp_preint_cols_.data()) != ICG_OK)
+                    return fail("icg_reproj_host_parts_build_preint");
+                for (size_t w = 0; w < NW && R.prior.on; w++) R.prior.gathered[w] |= R.reassemble[w];
+            } else if (R.prior.on) {
                 // the resident priors' blocks take their residuals, and at a window's first rebuild their Jacobians, where they are
                 if (icg_reproj_host_parts_build_prior(ctx, P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(),
                                                       R.hp.jac_off.data(), R.hp.J.data(), R.hp.r.data(), R.hp.s.data(), R.hp.diag.data(), nullptr, hp_prior_of_.data(),
@@ -423,7 +498,7 @@ bool WindowSolverBatch::linearize(Run &R) {
             Run::State &T = R.st[w];
             if (T.done || !(T.relinearize || T.redamp)) return;
             Window &W = windows_[w];
-            if (R.prior.on && T.relinearize) sumHostCosts(R, w); // (the device value has arrived)
+            if (R.deferred() && T.relinearize) sumHostCosts(R, w); // (the device values have arrived)
             // the cost at the linearization point initialises the window on the first pass; afterwards it equals the accepted
             // trial cost and is kept (the same bookkeeping as WindowSolver)
             if (T.relinearize && R.first) T.tr.cost = R.cost[w] + R.host_cost[w], T.tr.summary.initial_cost = T.tr.cost;
@@ -466,11 +541,16 @@ bool WindowSolverBatch::hostHalfOfWindow(Run &R, size_t w) {
             if (Res.removed) continue;
             const bool has = next < W.host_blocks.size() && W.host_blocks[next].residual == (int) id;
             double *cost   = &R.host_cost[w];
-            if (R.prior.on) cost = &R.prior.res_cost[w][id], *cost = 0.0; // per residual: the window's sum waits for the device value
+            if (R.deferred()) cost = &R.prior.res_cost[w][id], *cost = 0.0; // per residual: the window's sum waits for the device values
             if (R.prior.on && (int) id == W.prior_residual) {
                 // evaluated where it is resident: the block's slots in r are placed only, its Jacobian is gathered from J0 on the device at
                 // the window's first rebuild of the solve and kept afterwards
                 if (has) H.jac_off[(size_t) W.blk_begin + next] = R.prior.gathered[w] ? -1 : ICG_HP_JAC_FROM_PRIOR, next++;
+                continue;
+            }
+            if (R.preint.on && W.preint_of_residual[id] >= 0) {
+                // a resident preintegration factor: placed only; its Jacobian changes with the point and is gathered at every rebuild
+                if (has) H.jac_off[(size_t) W.blk_begin + next] = ICG_HP_JAC_FROM_PREINT, next++;
                 continue;
             }
             double *Jd = has ? &H.J[W.host_blocks[next].J_off] : nullptr;
@@ -503,6 +583,14 @@ void WindowSolverBatch::packPriors() {
 
 bool WindowSolverBatch::evaluatePriors(Run &R) { return prior_set_.evaluateResident(R.prior.sq.data(), &R.prior.err); }
 
+// device preintegration: every resident factor's evaluation point and correction quaternion (on the driving thread, before the phase's device call)
+void WindowSolverBatch::packPreintegrations() {
+    for (size_t f = 0; f < preint_where_.size(); f++)
+        preint_set_.pack(f, windows_[(size_t) preint_where_[f].first].problem.residuals[(size_t) preint_where_[f].second].blocks.data());
+}
+
+bool WindowSolverBatch::evaluatePreintegrations(Run &R, bool want_jac) { return preint_set_.evaluateResident(want_jac, R.preint.sq.data(), &R.preint.err); }
+
 // device prior: the window's host cost from the costs the pool recorded per residual and the device's squared norm in the prior's place,
 // added up from zero in residual order: hostFactors' sum
 void WindowSolverBatch::sumHostCosts(Run &R, size_t w) {
@@ -510,7 +598,12 @@ void WindowSolverBatch::sumHostCosts(Run &R, size_t w) {
     double cost     = 0.0;
     for (size_t id = 0; id < W.problem.residuals.size(); id++) {
         if (W.problem.residuals[id].removed) continue;
-        cost += (int) id == W.prior_residual ? 0.5 * R.prior.sq[(size_t) W.prior_in_set] : R.prior.res_cost[w][id];
+        if (R.prior.on && (int) id == W.prior_residual)
+            cost += 0.5 * R.prior.sq[(size_t) W.prior_in_set];
+        else if (R.preint.on && W.preint_of_residual[id] >= 0)
+            cost += 0.5 * R.preint.sq[(size_t) W.preint_of_residual[id]];
+        else
+            cost += R.prior.res_cost[w][id];
     }
     R.host_cost[w] = cost;
 }
@@ -657,8 +750,9 @@ bool WindowSolverBatch::trialCosts(Run &R) {
     R.clk.start();
     factors_.gather(R.poses, R.ext, R.inv, R.td);
     const char *dev_fail = nullptr;
-    bool prior_ok        = true;
+    bool prior_ok = true, preint_ok = true;
     if (R.prior.on) packPriors();
+    if (R.preint.on) packPreintegrations();
     if (!side_) side_.reset(new SideThread());
     SideCall trial(*side_, [&] {
         if (icg_reproj_eval_windows(ctx, factors_.numPoses(), R.poses.data(), R.ext.data(), factors_.numLandmarks(), R.inv.data(), R.td.data(), 0, huber_) !=
@@ -666,14 +760,16 @@ bool WindowSolverBatch::trialCosts(Run &R) {
             dev_fail = "icg_reproj_eval_windows";
         else if (icg_reproj_cost_windows(ctx, active_.data(), R.cost.data()) != ICG_OK)
             dev_fail = "icg_reproj_cost_windows";
-        else if (R.prior.on)
-            prior_ok = evaluatePriors(R);
+        else {
+            if (R.prior.on) prior_ok = evaluatePriors(R);
+            if (prior_ok && R.preint.on) preint_ok = evaluatePreintegrations(R, false); // (residual only: the cost is all a trial point needs)
+        }
     });
     std::atomic<int> trial_failed{0};
     R.host_cost.assign(NW, 0.0);
     factors_.forEachWindow(NW, [&](size_t w) {
         if (!R.st[w].stepped) return;
-        if (!R.prior.on) {
+        if (!R.deferred()) {
             if (!solver_detail::hostFactors(windows_[w].problem, R.P, nullptr, nullptr, nullptr, &R.host_cost[w])) trial_failed++;
             return;
         }
@@ -681,7 +777,7 @@ bool WindowSolverBatch::trialCosts(Run &R) {
         const Window &W = windows_[w];
         for (size_t id = 0; id < W.problem.residuals.size(); id++) {
             const solver_detail::Residual &Res = W.problem.residuals[id];
-            if (Res.removed || (int) id == W.prior_residual) continue;
+            if (Res.removed || (R.prior.on && (int) id == W.prior_residual) || (R.preint.on && W.preint_of_residual[id] >= 0)) continue;
             if (!solver_detail::residualCost(Res, true, &R.prior.res_cost[w][id])) {
                 trial_failed++;
                 return;
@@ -690,8 +786,8 @@ bool WindowSolverBatch::trialCosts(Run &R) {
     });
     trial.join();
     if (dev_fail) return fail(dev_fail);
-    if (!prior_ok) {
-        error_ = R.prior.err;
+    if (!prior_ok || !preint_ok) {
+        error_ = !prior_ok ? R.prior.err : R.preint.err;
         return false;
     }
     R.clk.stop(PH_TRIAL_EVAL);
@@ -699,7 +795,7 @@ bool WindowSolverBatch::trialCosts(Run &R) {
     factors_.forEachWindow(NW, [&](size_t w) {
         Run::State &T = R.st[w];
         if (!T.stepped || trial_failed.load()) return;
-        if (R.prior.on) sumHostCosts(R, w);
+        if (R.deferred()) sumHostCosts(R, w);
         bool accepted;
         T.done = T.tr.trial(R.o, R.cost[w] + R.host_cost[w], T.model, windows_[w].problem, &accepted);
         if (accepted)

@@ -82,6 +82,21 @@ public:
     // windows of the last solve() whose resident prior took J0 / e0 from a kept device linearization instead of the host arrays
     // (MarginalizationPriorSet::handedOff: priors tagged by MarginalizationBatch::setKeepLinearized); needs no switch of its own
     int priorsHandedOff() const { return prior_set_.handedOff(); }
+    // With the device host part: the preintegration factors of every window are RESIDENT on the device for the solve (PreintegrationSet: the
+    // integration results go up once per solve()) and evaluated there at every linearization (with Jacobians) and every trial point (residual
+    // only), on the side thread like the resident priors.  The driving thread packs the evaluation points and the correction quaternions
+    // (Preintegration::correctionQuaternion: the device calls no sin / cos); residual and Jacobian reach the host-part kernel without crossing
+    // the link (icg_reproj_host_parts_build_preint gathers the free columns at every rebuild: the Jacobian changes with the point), one
+    // squared norm per factor comes back and 0.5 * that norm takes the factor's place in the window's host cost, summed in residual order:
+    // states, inverse depths and summaries are the host's bit for bit.  A residual block joins the set when it has no loss function, its cost
+    // is a PreintegrationFactor and its Preintegration is ready() at the head of the solve; a robustified, unintegrated or singular factor
+    // stays on the pool and behaves as without the switch.  Independent of setDevicePrior.  Off by default; needs setDeviceHostPart(true)
+    // (solve() fails otherwise) and the C entries, referenced weakly like the ones above.
+    void setDevicePreintegration(bool on) { device_preint_ = on; }
+    bool devicePreintegration() const { return device_preint_; }
+    static bool devicePreintegrationAvailable();
+    static const char *devicePreintegrationMissing(); // the first entry the build lacks for it, nullptr when available
+    int preintegrationsOnDevice() const { return (int) preint_list_.size(); } // factors of the last layout that joined the resident set
     bool solve(const Options &options, std::vector<Summary> *summaries);
     // removeReprojectionFactorsByChi2 (ic_gvins.cc:1269-1297) for every window; returns the number removed per window
     std::vector<int> removeReprojectionFactorsByChi2(double chi2);
@@ -105,6 +120,10 @@ private:
         // device prior (layout()): the residual that is the window's resident prior (-1: none), its index in the resident set, its position
         // among host_blocks (-1: every block of the prior is constant: it has a cost but no host block)
         int prior_residual{-1}, prior_in_set{-1}, prior_block{-1};
+        // device preintegration (layout()): per residual its index in the resident set (-1: not in it; empty while the switch is off), and
+        // per block of host_blocks the same index (-1: an ordinary block)
+        std::vector<int> preint_of_residual, preint_of_block;
+        std::vector<int32_t> preint_cols; // the resident blocks' columns of the 15 x 32 Jacobian, block after block
     };
     // how solve() forms and solves the reduced systems: resolved from the two setters at its top
     enum class ReducedPath { HostSolve, DeviceSolve, DeviceSolveDeviceParts };
@@ -123,6 +142,9 @@ private:
     // a window's host cost once the device value is there
     void packPriors();
     bool evaluatePriors(Run &R);
+    // device preintegration: the same two steps for the resident factors
+    void packPreintegrations();
+    bool evaluatePreintegrations(Run &R, bool want_jac);
     void sumHostCosts(Run &R, size_t w);
     void solveWindowOnHost(Run &R, size_t w);
     bool solveWindowsOnDevice(Run &R);
@@ -144,6 +166,13 @@ private:
     std::vector<int32_t> hp_prior_of_, hp_prior_cols_;
     std::vector<MargPriorView> prior_views_;
     MarginalizationPriorSet prior_set_;
+    // device preintegration (layout()): per block of the list the set factor it is (-1: none), the resident blocks' columns, the factors of
+    // the set in window and residual order with their parameter blocks, and the set
+    bool device_preint_{false};
+    std::vector<int32_t> hp_preint_of_, hp_preint_cols_;
+    std::vector<const Preintegration *> preint_list_;
+    std::vector<std::pair<int, int>> preint_where_; // (window, residual) of every factor of the set
+    PreintegrationSet preint_set_;
     std::string error_;
 };
 

@@ -27,6 +27,7 @@ EXPORTS = [
     "icg_marg_prior_evaluate_resident", "icg_reproj_host_parts_build_prior",
     "icg_marg_linearize_batch_keep", "icg_marg_linearized_release", "icg_marg_prior_set_from_kept", "icg_marg_linearize_resident",
     "icg_reproj_landmark_min_windows",
+    "icg_preint_set", "icg_preint_evaluate_resident", "icg_preint_fetch_resident", "icg_reproj_host_parts_build_preint",
 ]
 
 
@@ -35,6 +36,8 @@ MARG_LIN_MAX_P = 512  # ICG_MARG_LIN_MAX_P
 CHOL_MAX_N = 512  # ICG_CHOL_MAX_N
 HOST_PART_MAX_NR = 1024  # ICG_HOST_PART_MAX_NR
 HP_JAC_FROM_PRIOR = -2  # ICG_HP_JAC_FROM_PRIOR
+HP_JAC_FROM_PREINT = -3  # ICG_HP_JAC_FROM_PREINT
+PREINT_SET_MAX = 65535 * 16  # ICG_PREINT_SET_MAX
 
 
 class IcgError(RuntimeError):
@@ -511,6 +514,12 @@ class Context:
         return self.lib.icg_reproj_host_parts_build_prior(self.h, int(P), _p(Pw), _p(rebuild), _p(blk_off), _p(nr), _p(nf), _p(cols), _p(jac_off), _p(J), _p(r),
                                                           _p(host_s), _p(host_diag), _p(part_out), _p(prior_of), _p(prior_cols))
 
+    def reproj_host_parts_build_preint_raw(self, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, prior_of, prior_cols,
+                                           preint_of, preint_cols):
+        """icg_reproj_host_parts_build_preint on the caller's arrays (None = NULL; the outputs are written in place) -> the return code"""
+        return self.lib.icg_reproj_host_parts_build_preint(self.h, int(P), _p(Pw), _p(rebuild), _p(blk_off), _p(nr), _p(nf), _p(cols), _p(jac_off), _p(J), _p(r),
+                                                           _p(host_s), _p(host_diag), _p(part_out), _p(prior_of), _p(prior_cols), _p(preint_of), _p(preint_cols))
+
     def reproj_host_parts_build_prior(self, P, Pw, windows, rebuild=None, host_s=None, host_diag=None):
         """icg_reproj_host_parts_build_prior.  windows: per window a list of blocks; an ordinary block is (J nr x nf, r, cols, keep) as in
         reproj_host_parts_build, a prior block is ("prior", p, prior_cols, cols, how): prior p of the resident set (marg_prior_set), how =
@@ -609,6 +618,37 @@ class Context:
         self._ck(self.lib.icg_preint_evaluate_batch(self.h, int(variant), n, _p(delta), _p(jac), _p(cov), _p(dt), _p(env), _p(po), _p(pnr),
                                                      _p(points), _p(res), _p(J), _p(S), _p(status)), "icg_preint_evaluate_batch")
         return res, J, S, status
+
+    def preint_set(self, variant, delta, jac, sqrt_info, dt, env, q_nn, pn_offsets=None, pn=None):
+        """icg_preint_set: len(variant) factors become resident (variant per factor; sqrt_info and q_nn are the host's)"""
+        variant = _i32(variant).reshape(-1)
+        n = len(variant)
+        delta, jac, sqrt_info = _f64(delta).reshape(n, 16), _f64(jac).reshape(n, 225), _f64(sqrt_info).reshape(n, 225)
+        dt, env, q_nn = _f64(dt).reshape(n), _f64(env).reshape(n, 4), _f64(q_nn).reshape(n, 4)
+        po = None if pn_offsets is None else _i32(pn_offsets)
+        pnr = None if pn is None else _f64(pn).reshape(-1, 4)
+        self._preint_n = 0
+        self._ck(self.lib.icg_preint_set(self.h, n, _p(variant), _p(delta), _p(jac), _p(sqrt_info), _p(dt), _p(env), _p(q_nn), _p(po), _p(pnr)),
+                 "icg_preint_set")
+        self._preint_n = n
+
+    def preint_evaluate_resident(self, points, q_corr, want_jac=True):
+        """icg_preint_evaluate_resident: residuals (and Jacobians) stay on the device -> sq_norm (r . r per factor)"""
+        n = getattr(self, "_preint_n", 0)
+        points, q_corr = _f64(points).reshape(-1, 32), _f64(q_corr).reshape(-1, 4)
+        if n and (points.shape[0] != n or q_corr.shape[0] != n):
+            raise IcgError(f"preint_evaluate_resident: {points.shape[0]} points and {q_corr.shape[0]} quaternions, the resident set has {n} factors")
+        sq = np.zeros(max(n, 1))
+        self._ck(self.lib.icg_preint_evaluate_resident(self.h, _p(points), _p(q_corr), 1 if want_jac else 0, _p(sq)), "icg_preint_evaluate_resident")
+        return sq[:n]
+
+    def preint_fetch_resident(self, want_jac=True):
+        """icg_preint_fetch_resident -> (residuals n x 15, jacobians n x 480 or None) of the last resident evaluation"""
+        n = max(getattr(self, "_preint_n", 0), 1)
+        res = np.zeros((n, 15))
+        J = np.zeros((n, 480)) if want_jac else None
+        self._ck(self.lib.icg_preint_fetch_resident(self.h, _p(res), _p(J)), "icg_preint_fetch_resident")
+        return res, J
 
     # ---- M4
     def marg_prior_set(self, r, block_off, block_size, block_index, x0, J0, e0):

@@ -313,6 +313,28 @@ int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *Pw, const ui
 int icg_reproj_host_parts_build_prior(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
                                       const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s,
                                       double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols);
+/* icg_reproj_host_parts_build_prior with blocks that are factors of the resident P2 set (icg_preint_set) at the point of its last
+ * icg_preint_evaluate_resident: neither the factor's residual nor its 15 x 30 Jacobian crosses the link.  The arguments of
+ * icg_reproj_host_parts_build_prior, plus:
+ *   preint_of    per block of the call: >= 0 = the block is factor preint_of[b] of the resident set (in any order), < 0 = it is not
+ *   preint_cols  for the preintegration blocks, in block order (those of windows that are not rebuilt included), nf[b] indices into the 32
+ *                columns of the factor's resident Jacobian (7 | 9 | 7 | 9): the free local columns of its non-constant parameter blocks,
+ *                0-5, 7-15, 16-21, 23-31 when all four are free
+ * Such a block of a rebuilt window has nr[b] == 15.  Its residual is the resident one; its slots in r are placed but not read.  Its
+ * Jacobian: jac_off[b] == ICG_HP_JAC_FROM_PREINT fills the kept Jacobian with Jd[k][y] = Jf[k][preint_cols[y]] on the device (what every
+ * rebuild asks for: the Jacobian changes with the point; it needs the last evaluation to have kept Jacobians), -1 keeps the previous
+ * gather, an offset >= 0 uploads as for any block.  preint_of == NULL is icg_reproj_host_parts_build_prior; prior_of may be NULL.
+ * ICG_ERR_INVALID beyond the cases there (the message names the window and the block), for a block of a rebuilt window: preint_of[b] outside
+ * the resident set, nr[b] != 15, a preint_cols entry outside [0, 32) or 6 or 22 (the seventh pose columns), no set resident or not evaluated
+ * since it was set (for ICG_HP_JAC_FROM_PREINT: not evaluated with want_jac by its last evaluation), preintegration blocks without
+ * preint_cols, a block that is both prior and preintegration factor, ICG_HP_JAC_FROM_PREINT for a block with preint_of[b] < 0 (or without
+ * preint_of).  ICG_ERR_CAPACITY: more than 65535 prior and preintegration blocks in the rebuilt windows.  After an error nothing was
+ * launched and no output was touched. */
+#define ICG_HP_JAC_FROM_PREINT (-3)
+int icg_reproj_host_parts_build_preint(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
+                                       const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s,
+                                       double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols, const int32_t *preint_of,
+                                       const int32_t *preint_cols);
 /* problem setup: pre-sizes the resident window systems and the staging memory for reduced systems of size P (a hint; optional) */
 int icg_reproj_reserve_windows(icg_ctx *ctx, int P);
 int icg_reproj_backsub_windows(icg_ctx *ctx, int P, const double *delta_c, double *delta_l, double *lm_terms);
@@ -362,6 +384,37 @@ int icg_preint_evaluate_batch(icg_ctx *ctx, int variant, int n_factors, const do
                               const double *cov, const double *delta_time, const double *env, const int32_t *pn_offsets,
                               const double *pn, const double *points, double *residuals, double *jacobians, double *sqrt_info,
                               int32_t *status);
+
+/* ---- P2 on a RESIDENT set of factors: what an integration result contributes to its factor is constant over a solve while every LM
+ * iteration evaluates it at a new point, so it is uploaded once (icg_preint_set) and an evaluation ships the points up and one squared norm
+ * per factor back (icg_preint_evaluate_resident); the whitened residuals and Jacobians stay on the device.
+ * The device calls no sin / cos / sqrt here: the two quaternions of Preintegration::evaluate that need them come from the host
+ * (Preintegration::earthRateQuaternion with the set, Preintegration::correctionQuaternion with every point), and what is left is + - * /
+ * in the host's order, compiled without contraction on both sides: residuals, Jacobians and sq_norm have the bits of
+ * Preintegration::evaluate given the same sqrt_info.
+ * Per factor f, in the layout of icg_preint_evaluate_batch: variant[f] (0 Normal, 1 Earth: one set serves mixed windows), delta_state 16,
+ * jac 225, delta_time 1, env 4; sqrt_info 225 is the host's square-root information (shipped, not recomputed: a factor with a singular
+ * covariance does not belong in a set); q_nn 4 = rotvec2quat(-iewn T) as (x, y, z, w), read for Earth factors only; Earth factor f owns the
+ * rows [pn_offsets[f], pn_offsets[f+1]) of pn (the rows of a Normal factor are not read).  pn_offsets / pn may be NULL when no factor is Earth.
+ * Replaces the set the context held; the set stays until the next icg_preint_set or icg_ctx_destroy.  ICG_ERR_INVALID (the message names the
+ * factor where there is one): n_factors <= 0, a NULL required pointer, a variant outside {0, 1}, pn_offsets[0] < 0 or not monotone, an Earth
+ * factor without pn_offsets, rows without pn.  ICG_ERR_CAPACITY: more than ICG_PREINT_SET_MAX factors.  After a failed call no set is
+ * resident. */
+#define ICG_PREINT_SET_MAX (65535 * 16)
+int icg_preint_set(icg_ctx *ctx, int n_factors, const int32_t *variant, const double *delta_state, const double *jac, const double *sqrt_info,
+                   const double *delta_time, const double *env, const double *q_nn, const int32_t *pn_offsets, const double *pn);
+/* Evaluates every factor of the resident set: points 32 per factor (pose0[7] mix0[9] pose1[7] mix1[9]), q_corr 4 per factor =
+ * rotvec2quat(dq_dbg (bg0 - delta.bg)) as (x, y, z, w), used in place of the device's own.  Kept on the device, in buffers the set owns,
+ * until the next evaluation or icg_preint_set: the whitened residuals (15 per factor) and, with want_jac != 0, the whitened Jacobian as ONE
+ * row-major 15 x 32 matrix per factor, columns 7 | 9 | 7 | 9 (columns 6 and 22, the seventh pose columns, are +0.0).  Returned:
+ * sq_norm[f] = sum_k r[k]^2, k ascending from +0.0 (twice the Ceres cost of a factor without a loss).  An evaluation with want_jac == 0
+ * invalidates the kept Jacobians.  ICG_ERR_INVALID without a resident set or with a NULL argument: nothing is launched. */
+int icg_preint_evaluate_resident(icg_ctx *ctx, const double *points, const double *q_corr, int want_jac, double *sq_norm);
+/* The kept results of the last icg_preint_evaluate_resident in the layout of icg_preint_evaluate_batch: residuals 15 per factor, jacobians
+ * 480 per factor = 15x7 | 15x9 | 15x7 | 15x9 (NULL: not fetched).  For tests and callers that want them (as icg_reproj_fetch_residuals).
+ * ICG_ERR_INVALID: no resident set, NULL residuals, nothing evaluated since icg_preint_set, or Jacobians asked for after an evaluation with
+ * want_jac == 0. */
+int icg_preint_fetch_resident(icg_ctx *ctx, double *residuals, double *jacobians);
 
 /* ---- M4: MarginalizationFactor::Evaluate (factors/marginalization_factor.h:47-101) for the priors of many windows, RESIDENT on the
  * device: a prior is constant between two marginalizations while every LM iteration evaluates it at a new point, so the priors are
