@@ -150,10 +150,11 @@ def test_camera_point_ops_bit_exact(oracle, ctx1280):
     got = ctx1280.predict_mappoints(pw, 0, pose)
     assert np.array_equal(got.view(np.uint32), exp.view(np.uint32))
     R_pre = np.eye(3)
-    exp = oracle.predict_rotation(cam, R, R_pre, pts)
-    got = ctx1280.predict_rotation(pts, 0, (R.T @ R_pre).ravel())
-    # r_cur_pre is formed by the caller here (numpy matmul) vs inside the oracle: same ops, same order -> exact
-    assert np.abs(got - exp).max() < 1e-3
+    r_cur_pre = R.T @ R_pre
+    exp = oracle.predict_rotation(cam, np.eye(3), r_cur_pre, pts)
+    got = ctx1280.predict_rotation(pts, 0, r_cur_pre.ravel())
+    # the oracle forms I^T r_cur_pre, which is r_cur_pre exactly: both sides rotate by the same matrix -> same bits
+    assert np.array_equal(got.view(np.uint32), exp.view(np.uint32))
 
 
 def test_camera_point_kernels_match_reference_golden():
