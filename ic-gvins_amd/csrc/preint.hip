@@ -11,7 +11,7 @@
 // The products are evaluated SPARSELY and stay bit-identical to the dense ones: phi = I + F dt has at most 7 structural non-zeros per
 // row (rows of p: 2, v: 7, attitude: 4, bg / ba: 1) and G Q G^T is block diagonal; a dense sum  a = 0; a += phi[i][k] * x[k]  visits
 // the same non-zero terms in the same ascending-k order, and the skipped terms are exact zeros (x finite), which leave every partial sum
-// unchanged.  Entries are dealt to the lanes sorted by the cost of their row (first pass) / column (second pass), so a wave's lanes
+// unchanged (pinned bit for bit against the oracle's dense products by tests/test_gpu_preint_edges.py).  Entries are dealt to the lanes sorted by the cost of their row (first pass) / column (second pass), so a wave's lanes
 // run the same straight-line code: ~21 term-iterations per product pass instead of 60.  Measured: -15 % per launch (3 840 intervals x 40
 // samples 1.56 -> 1.30 ms; one 200-sample interval 2.07 -> 1.80 ms) — the rest of a sample is the strictly sequential FP64 navigation update
 // (~1 300 dependent operations incl. six sin/cos and a dozen divisions in the Earth variant), which every lane carries redundantly.
@@ -273,6 +273,7 @@ extern "C" int icg_preint_batch(icg_ctx *ctx, int variant, int n_intervals, cons
     if (n_intervals == 0) return ICG_OK;
     if (!offsets || !imu || !state0 || !params || !cur_state || !delta_state || !jac || !cov || !delta_time) return ICG_ERR_INVALID;
     const int total = offsets[n_intervals];
+    if (offsets[0] < 0) return icg_fail(ctx, ICG_ERR_INVALID, "offsets[0] = %d", offsets[0]);
     for (int s = 0; s < n_intervals; s++)
         if (offsets[s + 1] - offsets[s] < 1) return icg_fail(ctx, ICG_ERR_INVALID, "interval %d has no IMU sample", s);
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
@@ -289,8 +290,15 @@ extern "C" int icg_preint_batch(icg_ctx *ctx, int variant, int n_intervals, cons
     double *d_jac = c.out_zc(jac, 225 * (size_t) n_intervals);
     double *d_cov = c.out_zc(cov, 225 * (size_t) n_intervals);
     double *d_dt  = c.out_zc(delta_time, (size_t) n_intervals);
-    double *d_pn  = pn ? c.out_zc(pn, 4 * (size_t) total) : nullptr;
+    // pn is written by the Earth variant only, rows begin .. begin + n - 2 of every interval: the Normal variant gets no buffer, and the one
+    // row per interval that the kernel leaves alone is staged from the caller's, so that the copy back returns it unchanged
+    double *d_pn  = (pn && variant == 1) ? c.out_zc(pn, 4 * (size_t) total) : nullptr;
     ICG_LAUNCH_GUARD(c);
+    if (d_pn)
+        for (int s = 0; s < n_intervals; s++) {
+            const size_t last = 4 * ((size_t) offsets[s + 1] - 1);
+            memcpy(d_pn + last, pn + last, 4 * sizeof(double));
+        }
     {
         icg_prof_scope ps(ctx, "preint");
         hipLaunchKernelGGL(k_preint, dim3(n_intervals), dim3(64), 0, ctx->stream, variant, d_off, d_imu, d_s0, d_par, d_cur, d_del,

@@ -587,7 +587,8 @@ class Context:
         return cost
 
     # ---- P1
-    def preint_batch(self, variant, offsets, imu, state0, params):
+    def preint_batch(self, variant, offsets, imu, state0, params, want_pn=True):
+        """icg_preint_batch -> (cur n x 16, delta n x 16, jac n x 15 x 15, cov n x 15 x 15, dt n, pn total x 4 or None without want_pn)"""
         offsets = _i32(offsets)
         n = len(offsets) - 1
         imu = _f64(imu).reshape(-1, 8)
@@ -597,7 +598,7 @@ class Context:
         jac = np.zeros((n, 15, 15))
         cov = np.zeros((n, 15, 15))
         dt = np.zeros(n)
-        pn = np.zeros((imu.shape[0], 4))
+        pn = np.zeros((imu.shape[0], 4)) if want_pn else None
         self._ck(self.lib.icg_preint_batch(self.h, int(variant), n, _p(offsets), _p(imu), _p(state0), _p(_f64(params)),
                                             _p(cur), _p(delta), _p(jac), _p(cov), _p(dt), _p(pn)), "icg_preint_batch")
         return cur, delta, jac, cov, dt, pn

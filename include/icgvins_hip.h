@@ -365,7 +365,10 @@ int icg_reproj_chi2_cull(icg_ctx *ctx, double chi2, uint8_t *active);
  * (gyr_arw, acc_vrw, gyr_bias_std, acc_bias_std, corr_time, gravity, iewn[3]).  variant: 0 Normal, 1 Earth.
  * outputs per interval: cur_state 16, delta_state 16, jac 225, cov 225, delta_time 1.
  * pn (optional, total x 4): the Earth variant's pn_ list (preintegration_earth.cc:235) — (dt, position) after sample
- * index of interval s is stored at row offsets[s] + index - 1. */
+ * index of interval s is stored at row offsets[s] + index - 1.  Exactly those rows are written: the last row of every interval, and
+ * every row in the Normal variant, keep what the caller put there.
+ * ICG_ERR_INVALID (no output is touched): variant not 0 or 1, n_intervals < 0, a NULL required pointer, offsets[0] < 0, an interval
+ * without a sample.  n_intervals == 0 is ICG_OK and touches nothing. */
 int icg_preint_batch(icg_ctx *ctx, int variant, int n_intervals, const int32_t *offsets, const double *imu,
                      const double *state0, const double *params, double *cur_state, double *delta_state, double *jac,
                      double *cov, double *delta_time, double *pn);

@@ -533,7 +533,7 @@ int icg_preint_batch(icg_ctx *, int variant, int n_intervals, const int32_t *off
         std::vector<double> pnl((size_t) 4 * std::max(n - 1, 1));
         orc_preint_integrate(variant, n, imu + 8 * (size_t) b, state0 + 16 * (size_t) s, params, cur_state + 16 * (size_t) s,
                              delta_state + 16 * (size_t) s, jac + 225 * (size_t) s, cov + 225 * (size_t) s, delta_time + s, pnl.data());
-        if (pn && n > 1) memcpy(pn + 4 * (size_t) b, pnl.data(), sizeof(double) * 4 * (size_t) (n - 1));
+        if (pn && variant == 1 && n > 1) memcpy(pn + 4 * (size_t) b, pnl.data(), sizeof(double) * 4 * (size_t) (n - 1));
     }
     return ICG_OK;
 }

@@ -67,6 +67,7 @@ def test_oracle_preintegration_matches_reference_golden(oracle):
     """Integration (state, 15x15 Jacobian, covariance) to 1e-12; factor residual/Jacobians to 1e-9 relative: they contain
     the inverse + Cholesky of the covariance, where the shim's and the oracle's factorizations round differently."""
     import preint_data as pd
+    import preint_edge_data as ed
     n = 0
     for k, c in preint_golden_cases():
         v = int(c["variant"])
@@ -76,6 +77,10 @@ def test_oracle_preintegration_matches_reference_golden(oracle):
         assert _rel(pre["jac"], c["jac"]) < 1e-12, k
         assert _rel(pre["cov"], c["cov"]) < 1e-12, k
         assert abs(pre["dt"] - float(c["dt"])) < 1e-15, k
+        for name in ("jac", "cov"):  # per 3x3 block: the covariance blocks span seven orders of magnitude
+            assert ed.block_rel(pre[name], c[name])[0] <= ed.TOL, (k, name, ed.block_rel(pre[name], c[name]))
+        for name in ("cur", "delta"):
+            assert ed.field_rel(pre[name], c[name])[0] <= ed.TOL, (k, name, ed.field_rel(pre[name], c[name]))
         pose0, mix0 = pd.split(c["s0"])
         pose1, mix1 = pd.split(c["s1"])
         r, J = oracle.preint_evaluate(v, pre, [0, 0, c["params"][5]], c["params"][6:9], pose0, mix0, pose1, mix1)
@@ -94,6 +99,7 @@ REF_PREINT_SO = os.path.join(ROOT, "oracle", "_ref", "libref_preint.so")
 @pytest.mark.skipif(not os.path.exists(REF_PREINT_SO), reason="oracle/_ref not built (needs /root/reference)")
 def test_oracle_preintegration_matches_reference_library_on_fresh_inputs(oracle):
     import preint_data as pd
+    import preint_edge_data as ed
     lib = C.CDLL(REF_PREINT_SO)
     p = lambda a: np.ascontiguousarray(a, np.float64).ctypes.data_as(C.c_void_p)
     station = np.array([0.7, -1.2, 350.0])
@@ -113,6 +119,8 @@ def test_oracle_preintegration_matches_reference_library_on_fresh_inputs(oracle)
             pre = oracle.preint_integrate(variant, imu, s0, par)
             for name, ref in (("cur", cur), ("delta", delta), ("jac", jac), ("cov", cov)):
                 assert _rel(pre[name], ref) < 1e-12, (seed, variant, name)
+                measure = ed.block_rel if name in ("jac", "cov") else ed.field_rel
+                assert measure(pre[name], ref)[0] <= ed.TOL, (seed, variant, name, measure(pre[name], ref))
 
 
 # ---- marginalization (R2, M1-M4): reference sources factors/{residual_block_info,marginalization_info,marginalization_factor}.h
