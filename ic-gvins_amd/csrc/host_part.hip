@@ -11,6 +11,8 @@
 // (icg_reproj_host_parts_build_prior): k_host_part_prior copies its residuals of the last resident evaluation and the free columns of its J0
 // to the places k_host_part reads.  The same kernel serves a block that is a preintegration factor of the resident P2 set (preint.hip,
 // icg_reproj_host_parts_build_preint): its source matrix is the factor's whitened 15 x 32 Jacobian, its row stride 32.
+#include <array>
+
 #include "reproj_internal.h"
 
 #define HP_THREADS 256
@@ -167,6 +169,326 @@ __global__ __launch_bounds__(HP_THREADS) void k_host_part_prior(const hp_prior *
     }
 }
 
+// ---- the entry, in stages: hp_validate (a plan; nothing is changed) -> hp_place_kept -> hp_stage -> hp_launch (launch and commit) -------------------------
+struct hp_args { // the arguments of a call as the stages read them; me: the entry a message names, W: the windows of the partition
+    const char *me;
+    int P, W;
+    const int32_t *Pw, *blk_off, *nr, *nf, *cols;
+    const uint8_t *rebuild;
+    const int64_t *jac_off;
+    const double *J, *r;
+    double *host_s, *host_diag, *part_out;
+};
+// A family of device-resident blocks.  Its rules: may member idx of the family's resident set be block p of window w, B.nr residuals whose kept Jacobian
+// holds the columns pc[0 .. B.nf) of the member's source matrix (B.fill: gathered in this call)?  They fill in the member's source, residuals and row stride.
+typedef int hp_rules(icg_ctx *ctx, const char *me, int w, int p, int idx, const int32_t *pc, hp_prior &B);
+struct hp_family {
+    hp_rules *rules;
+    const int32_t *of, *cols; // per block of the call its member of the set (< 0: none; NULL: no block of the call); the members' columns, block after block
+    int64_t gather;           // the jac_off that asks for the kept Jacobian to be gathered from the member's source
+    size_t at;                // walks cols over the family's blocks of ALL windows (a window that is not rebuilt still places the others')
+};
+
+static int hp_rules_prior(icg_ctx *ctx, const char *me, int w, int p, int pp, const int32_t *pc, hp_prior &B) {
+    const icg_marg_set &ms = ctx->marg;
+    if (!pc) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a prior block without prior_cols", me, w, p);
+    if (ms.n <= 0 || !ms.res_valid)
+        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no prior set is resident and evaluated (icg_marg_prior_set, then icg_marg_prior_evaluate_resident)",
+                        me, w, p);
+    if (pp >= ms.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: prior %d outside the resident set of %d", me, w, p, pp, ms.n);
+    const int pr = ms.h_r[(size_t) pp];
+    if (B.nr != pr) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, prior %d has %d", me, w, p, B.nr, pp, pr);
+    for (int x = 0; x < B.nf; x++)
+        if (pc[x] < 0 || pc[x] >= pr) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: prior column %d outside the prior (%d)", me, w, p, pc[x], pr);
+    B.J = ms.d_J + ms.h_j_off[(size_t) pp], B.res = ms.d_res + ms.h_e_off[(size_t) pp], B.stride = pr; // (J0 is r x r)
+    return ICG_OK;
+}
+
+static int hp_rules_preint(icg_ctx *ctx, const char *me, int w, int p, int fp, const int32_t *pc, hp_prior &B) {
+    const icg_preint_resident &ps = ctx->preint;
+    if (!pc) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a preintegration block without preint_cols", me, w, p);
+    if (ps.n <= 0 || !ps.res_valid || (B.fill && !ps.jac_valid))
+        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no preintegration set is resident and evaluated%s (icg_preint_set, then icg_preint_evaluate_resident)",
+                        me, w, p, B.fill ? " with Jacobians" : "");
+    if (fp >= ps.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: factor %d outside the resident set of %d", me, w, p, fp, ps.n);
+    if (B.nr != 15) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, a preintegration factor has 15", me, w, p, B.nr);
+    for (int x = 0; x < B.nf; x++)
+        if (pc[x] < 0 || pc[x] >= 32 || pc[x] == 6 || pc[x] == 22)
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: preintegration column %d (0 .. 31 without 6 and 22)", me, w, p, pc[x]);
+    B.J = ps.d_jac ? ps.d_jac + 480 * (size_t) fp : nullptr, B.res = ps.d_res + 15 * (size_t) fp, B.stride = 32; // (the whitened 15 x 32 Jacobian)
+    return ICG_OK;
+}
+
+struct hp_plan { // what validation leaves for the stages behind it
+    bool drop_all, have_kept;
+    std::vector<int32_t> r_off, c_off; // every block's place in the staged r and cols
+    std::vector<hp_prior> res;                // the resident blocks of the rebuilt windows ...
+    std::vector<std::array<int, 3>> res_at;   // ... their (window, position in the window's block list, family)
+    std::vector<int32_t> res_cols; // the staged column list their pc_off counts in: prior_cols | preint_cols of all windows (either may be absent)
+    size_t n_res_cols = 0, ship_doubles = 0, out_cells = 0; // (n_res_cols: what the families' cursors walked)
+    int n_rebuilt = 0, max_cells = 0, max_prior_nr = 0;
+};
+
+// block b of the rebuilt window w behind its shape and capacity: nf > Pw, columns, the rules of its family (idx[f] >= 0: member idx[f], columns from c0[f]), jac_off
+static int hp_validate_block(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[2], const int (&idx)[2], const size_t (&c0)[2], int w, int b,
+                             const std::vector<icg_hp_block> *kept, std::vector<int32_t> &seen, bool &any_keep, hp_plan &plan) {
+    const char *me = a.me;
+    const int p = b - a.blk_off[w], nr = a.nr[b], nf = a.nf[b], Pw = a.Pw[w];
+    if (nf > Pw) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d columns in a system of %d", me, w, p, nf, Pw);
+    for (int x = 0; x < nf; x++) {
+        const int c = a.cols[(size_t) plan.c_off[(size_t) b] + x];
+        if (c < 0 || c >= Pw) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: column %d outside the system (%d)", me, w, p, c, Pw);
+        if (seen[(size_t) c] == b) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: column %d twice", me, w, p, c);
+        seen[(size_t) c] = b;
+    }
+    int fam = -1; // the family the block is resident in
+    for (int f = 0; f < 2; f++) {
+        if (idx[f] < 0) continue;
+        if (fam >= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both a prior (%d) and a preintegration factor (%d)", me, w, p, idx[0], idx[1]);
+        fam = f;
+        hp_prior B{nullptr, nullptr, 0 /* its place among the kept Jacobians: hp_stage */, 0, plan.r_off[(size_t) b], (int32_t) c0[f], nr, nf, a.jac_off[b] == F[f].gather ? 1 : 0};
+        if (int rc = F[f].rules(ctx, me, w, p, idx[f], F[f].cols ? F[f].cols + c0[f] : nullptr, B)) return rc;
+        plan.res.push_back(B), plan.res_at.push_back({w, p, f});
+        plan.max_prior_nr = std::max(plan.max_prior_nr, nr);
+    }
+    if (a.jac_off[b] >= 0) {
+        if (!a.J) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a Jacobian offset without J", me, w, p);
+        plan.ship_doubles += (size_t) nr * nf;
+    } else if (fam >= 0 && a.jac_off[b] == F[fam].gather) {
+        // gathered on the device: from the prior's J0, from the factor's resident Jacobian
+    } else if (a.jac_off[b] == ICG_HP_JAC_FROM_PREINT) {
+        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: ICG_HP_JAC_FROM_PREINT for a block that is no preintegration factor", me, w, p);
+    } else if (a.jac_off[b] == -1) {
+        any_keep = true;
+        if (!kept || (size_t) p >= kept->size()) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no kept Jacobian", me, w, p);
+        const icg_hp_block &k = (*kept)[(size_t) p];
+        if (k.nr != nr || k.nf != nf)
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: the kept Jacobian is %d x %d, not %d x %d", me, w, p, k.nr, k.nf, nr, nf);
+    } else {
+        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: jac_off = %lld", me, w, p, (long long) a.jac_off[b]);
+    }
+    return ICG_OK;
+}
+
+// Stage 1.  Nothing is changed before validation is through: no field of ctx is written here and nothing is allocated on the device.
+static int hp_validate(icg_ctx *ctx, const hp_args &a, hp_family (&F)[2], hp_plan &plan) {
+    const char *me = a.me;
+    const int P = a.P, W = a.W;
+    if (W <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: no window partition: call icg_reproj_set_windows first", me);
+    if (P <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: P = %d", me, P);
+    if (P > HP_MAX_P) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: reduced systems of more than %d camera columns are not supported (%d)", me, HP_MAX_P, P);
+    if (W > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %d windows in one call (at most 65535)", me, W);
+    if (ctx->red_W != 0 && ctx->red_P != P) return icg_fail(ctx, ICG_ERR_INVALID, "%s: P = %d, the resident reduced systems have %d columns", me, P, ctx->red_P);
+    if (!a.Pw || !a.rebuild || !a.blk_off || !a.host_s || !a.host_diag) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", me);
+    if (a.blk_off[0] != 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window 0: blk_off[0] = %d", me, a.blk_off[0]);
+    for (int w = 0; w < W; w++)
+        if (a.blk_off[w + 1] < a.blk_off[w])
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d: blk_off decreases (%d after %d)", me, w, a.blk_off[w + 1], a.blk_off[w]);
+    const int nb = a.blk_off[W];
+    if (nb > 0 && (!a.nr || !a.nf || !a.cols || !a.jac_off || !a.r)) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", me);
+    // the slots of d_red_H follow the P of the resident reduced systems, or of the last call here while there are none: host parts (and
+    // kept Jacobians) of another shape, or of a buffer that is about to be replaced, are dropped before this call's are built
+    const size_t H_bytes = sizeof(double) * (size_t) W * ((size_t) P * (P + 1) / 2);
+    plan.drop_all        = ctx->red_H_cols.size() != (size_t) W || (ctx->red_W == 0 && ctx->hp.H_P != P) || ctx->red_H_cap < H_bytes;
+    plan.have_kept       = !plan.drop_all && ctx->hp.win.size() == (size_t) W;
+    std::vector<int32_t> &r_off = plan.r_off, &c_off = plan.c_off, seen((size_t) P, -1);
+    r_off.assign((size_t) nb + 1, 0), c_off.assign((size_t) nb + 1, 0);
+    for (int w = 0; w < W; w++) {
+        const std::vector<icg_hp_block> *kept = plan.have_kept ? &ctx->hp.win[(size_t) w] : nullptr;
+        const int cnt = a.blk_off[w + 1] - a.blk_off[w], Pw = a.Pw[w];
+        if (a.rebuild[w] && (Pw <= 0 || Pw > P)) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d: Pw = %d (1 .. %d)", me, w, Pw, P);
+        bool any_keep = false;
+        for (int b = a.blk_off[w]; b < a.blk_off[w + 1]; b++) {
+            const int p = b - a.blk_off[w], nr = a.nr[b], nf = a.nf[b];
+            if (nr <= 0 || nf <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d x %d", me, w, p, nr, nf);
+            if (nr > ICG_HOST_PART_MAX_NR)
+                return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: window %d, block %d: %d residuals (at most %d)", me, w, p, nr, ICG_HOST_PART_MAX_NR);
+            if ((int64_t) r_off[(size_t) b] + nr > INT32_MAX || (int64_t) c_off[(size_t) b] + nf > INT32_MAX)
+                return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: window %d, block %d: more than 2^31 residuals or columns in one call", me, w, p);
+            r_off[(size_t) b + 1] = r_off[(size_t) b] + nr, c_off[(size_t) b + 1] = c_off[(size_t) b] + nf;
+            int idx[2]; // >= 0: the block is that member of the family's resident set
+            size_t c0[2];
+            for (int f = 0; f < 2; f++) {
+                idx[f] = F[f].of ? F[f].of[b] : -1, c0[f] = F[f].at;
+                if (idx[f] >= 0) F[f].at += (size_t) nf; // (at most the columns of all blocks: below 2^31)
+            }
+            if (!a.rebuild[w]) continue;
+            if (int rc = hp_validate_block(ctx, a, F, idx, c0, w, b, kept, seen, any_keep, plan)) return rc;
+        }
+        if (!a.rebuild[w]) continue;
+        if (any_keep && (size_t) cnt != kept->size())
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d: %d blocks, %zu kept, and a block keeps its Jacobian", me, w, cnt, kept->size());
+        plan.n_rebuilt++, plan.out_cells += (size_t) Pw * (Pw + 1) / 2;
+        plan.max_cells = std::max(plan.max_cells, Pw * (Pw + 1) / 2);
+    }
+    if (plan.res.size() > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %zu prior blocks in one call (at most 65535)", me, plan.res.size());
+    // the staged column list: one family's columns behind the other's, the blocks' offsets shifted to match
+    size_t base[2];
+    for (int f = 0; f < 2; f++) {
+        base[f] = plan.res_cols.size(), plan.n_res_cols += F[f].at;
+        if (F[f].cols && !plan.res.empty()) plan.res_cols.insert(plan.res_cols.end(), F[f].cols, F[f].cols + F[f].at);
+    }
+    for (size_t k = 0; k < plan.res.size(); k++) plan.res[k].pc_off += (int32_t) base[plan.res_at[k][2]];
+    return ICG_OK;
+}
+
+// Stage 2.  The kept Jacobians after this call (`next`: dense, window after window) and their buffer (*dst_out); what stays moves there, device to device.
+static int hp_place_kept(icg_ctx *ctx, const hp_args &a, const hp_plan &plan, std::vector<std::vector<icg_hp_block>> &next, int *dst_out) {
+    const int W     = a.W;
+    icg_hp_kept &hp = ctx->hp;
+    next.assign((size_t) W, {});
+    int64_t total = 0;
+    bool same     = plan.have_kept;
+    for (int w = 0; w < W; w++) {
+        std::vector<icg_hp_block> &nw = next[(size_t) w];
+        if (a.rebuild[w])
+            for (int b = a.blk_off[w]; b < a.blk_off[w + 1]; b++) nw.push_back({0, a.nr[b], a.nf[b]});
+        else if (plan.have_kept)
+            nw = hp.win[(size_t) w];
+        same = same && nw.size() == hp.win[(size_t) w].size();
+        for (size_t p = 0; p < nw.size(); p++) {
+            if (same) same = hp.win[(size_t) w][p].off == total && hp.win[(size_t) w][p].nr == nw[p].nr && hp.win[(size_t) w][p].nf == nw[p].nf;
+            nw[p].off = total;
+            total += (int64_t) nw[p].nr * nw[p].nf;
+        }
+    }
+    int rc;
+    if (plan.drop_all) {
+        icg_red_drop_host_parts(ctx, (size_t) W);
+        if ((rc = icg_red_ensure_capacity(ctx, &ctx->d_red_H, &ctx->red_H_cap, sizeof(double) * (size_t) W * ((size_t) a.P * (a.P + 1) / 2)))) return rc;
+    }
+    const int dst = *dst_out = same ? hp.cur : 1 - hp.cur;
+    if (same) return ICG_OK;
+    // what stays moves into the other buffer, in runs that are contiguous on both sides
+    const size_t bytes = sizeof(double) * (size_t) std::max<int64_t>(total, 1);
+    if ((rc = icg_grow(ctx, (void **) &hp.d_J[dst], &hp.cap[dst], bytes, bytes + bytes / 4))) return rc;
+    int64_t run_src = 0, run_dst = 0, run_n = 0;
+    auto flush      = [&]() -> int {
+        if (run_n) ICG_HIP(ctx, hipMemcpyAsync(hp.d_J[dst] + run_dst, hp.d_J[hp.cur] + run_src, sizeof(double) * (size_t) run_n, hipMemcpyDeviceToDevice, ctx->stream));
+        run_n = 0;
+        return 0;
+    };
+    for (int w = 0; w < W && plan.have_kept; w++)
+        for (size_t p = 0; p < next[(size_t) w].size(); p++) {
+            if (a.rebuild[w] && a.jac_off[(size_t) a.blk_off[w] + p] != -1) continue; // (shipped, or gathered from a resident block's source)
+            const icg_hp_block &o = hp.win[(size_t) w][p], &n = next[(size_t) w][p];
+            const int64_t len     = (int64_t) n.nr * n.nf;
+            if (run_n && o.off == run_src + run_n && n.off == run_dst + run_n) {
+                run_n += len;
+                continue;
+            }
+            if ((rc = flush())) return rc;
+            run_src = o.off, run_dst = n.off, run_n = len;
+        }
+    return flush();
+}
+
+struct hp_staged { // what hp_stage uploaded, as hp_launch passes it on
+    std::vector<hp_win> wins;
+    size_t n_copies;
+    const hp_win *d_wins;
+    const hp_blk *d_blks;
+    const hp_copy *d_cp;
+    const int32_t *d_cols, *d_pc;
+    const hp_prior *d_pr;
+    double *d_r;
+    const double *d_Jnew = nullptr;
+};
+
+// Stage 3.  The tables of the kernels, the columns, r and the shipped Jacobians into the arena, and up in one copy.
+static int hp_stage(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[2], hp_plan &plan, const std::vector<std::vector<icg_hp_block>> &next, icg_call &c, hp_staged &S) {
+    const int W = a.W, nb = a.blk_off[W];
+    const size_t slot = (size_t) a.P * (a.P + 1) / 2;
+    std::vector<hp_blk> blks((size_t) nb);
+    std::vector<hp_copy> copies;
+    int64_t out_off = 0, src = 0;
+    for (int w = 0; w < W; w++) {
+        if (!a.rebuild[w]) continue;
+        S.wins.push_back({w, a.Pw[w], a.blk_off[w], a.blk_off[w + 1], (int32_t) S.wins.size(), 0, (int64_t) ((size_t) w * slot), out_off});
+        out_off += (int64_t) a.Pw[w] * (a.Pw[w] + 1) / 2;
+        for (int b = a.blk_off[w]; b < a.blk_off[w + 1]; b++) {
+            const icg_hp_block &n = next[(size_t) w][(size_t) (b - a.blk_off[w])];
+            blks[(size_t) b]      = {n.off, plan.r_off[(size_t) b], plan.c_off[(size_t) b], a.nr[b], a.nf[b]};
+            if (a.jac_off[b] >= 0) copies.push_back({src, n.off, (int64_t) a.nr[b] * a.nf[b]}), src += (int64_t) a.nr[b] * a.nf[b];
+        }
+    }
+    for (size_t k = 0; k < plan.res.size(); k++) plan.res[k].Jd_off = next[(size_t) plan.res_at[k][0]][(size_t) plan.res_at[k][1]].off;
+    const size_t n_r = (size_t) plan.r_off[(size_t) nb], n_c = (size_t) plan.c_off[(size_t) nb], ship_doubles = plan.ship_doubles;
+    int rc;
+    if ((rc = c.reserve(sizeof(hp_win) * S.wins.size() + sizeof(hp_blk) * blks.size() + sizeof(hp_copy) * copies.size() + sizeof(hp_prior) * plan.res.size() +
+                        sizeof(int32_t) * (n_c + plan.n_res_cols) + sizeof(double) * (n_r + ship_doubles + 2 * (size_t) plan.n_rebuilt * a.P + plan.out_cells) + 20 * 256)))
+        return rc;
+    S.n_copies = copies.size();
+    S.d_wins   = c.in(S.wins.data(), S.wins.size());
+    S.d_blks   = c.in(blks.data(), blks.size());
+    S.d_cp     = c.in(copies.data(), copies.size());
+    S.d_cols   = c.in(a.cols, n_c);
+    S.d_pr     = c.in(plan.res.data(), plan.res.size());
+    S.d_pc     = plan.res.empty() ? nullptr : c.in(plan.res_cols.data(), plan.res_cols.size());
+    if (!F[0].of && !F[1].of) {
+        S.d_r = c.in(a.r, n_r);
+    } else {
+        // The slots of the resident blocks (of every window, rebuilt or not) are placed but not read from the caller: staged block by block,
+        // like the shipped Jacobians below.  Whatever bytes the arena holds there go up with the rest; for the rebuilt windows
+        // k_host_part_prior overwrites them on the device, in stream order behind the upload and ahead of k_host_part, and the blocks of
+        // the other windows are not consumed.
+        const size_t off = icg_arena_alloc(ctx, sizeof(double) * n_r);
+        double *h        = icg_h<double>(ctx, off);
+        for (int b = 0; b < nb; b++)
+            if ((!F[0].of || F[0].of[b] < 0) && (!F[1].of || F[1].of[b] < 0))
+                memcpy(h + plan.r_off[(size_t) b], a.r + plan.r_off[(size_t) b], sizeof(double) * (size_t) a.nr[b]);
+        c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * n_r);
+        S.d_r = icg_d<double>(ctx, off);
+    }
+    if (ship_doubles) { // the shipped Jacobians, block after block
+        const size_t off = icg_arena_alloc(ctx, sizeof(double) * ship_doubles);
+        double *h        = icg_h<double>(ctx, off);
+        for (int w = 0; w < W; w++)
+            for (int b = a.blk_off[w]; a.rebuild[w] && b < a.blk_off[w + 1]; b++)
+                if (a.jac_off[b] >= 0) memcpy(h, a.J + a.jac_off[b], sizeof(double) * (size_t) a.nr[b] * a.nf[b]), h += (size_t) a.nr[b] * a.nf[b];
+        c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * ship_doubles);
+        S.d_Jnew = icg_d<double>(ctx, off);
+    }
+    return c.seal();
+}
+
+// Stage 4.  The outputs, the three kernels, and once they are through the call's kept Jacobians and parts become the context's.
+static int hp_launch(icg_ctx *ctx, const hp_args &a, const hp_plan &plan, std::vector<std::vector<icg_hp_block>> &next, int dst, icg_call &c, const hp_staged &S) {
+    const int W = a.W, P = a.P;
+    icg_hp_kept &hp = ctx->hp;
+    // s and diag of the rebuilt windows only: the rows of the others are not the call's to write
+    double *d_s = c.out((double *) nullptr, (size_t) plan.n_rebuilt * P), *d_dg = c.out((double *) nullptr, (size_t) plan.n_rebuilt * P);
+    for (const hp_win &hw : S.wins) {
+        c.outs.push_back({(void *) (a.host_s + (size_t) hw.w * P), (size_t) (reinterpret_cast<char *>(d_s + (size_t) hw.slot * P) - ctx->d_arena), sizeof(double) * (size_t) P, false});
+        c.outs.push_back({(void *) (a.host_diag + (size_t) hw.w * P), (size_t) (reinterpret_cast<char *>(d_dg + (size_t) hw.slot * P) - ctx->d_arena), sizeof(double) * (size_t) P, false});
+    }
+    double *d_po = a.part_out ? c.out(a.part_out, plan.out_cells) : nullptr;
+    ICG_LAUNCH_GUARD(c);
+    // from here on the rebuilt windows' parts and the kept Jacobians are being replaced: a failure below leaves those windows without a part
+    // and no window with a kept Jacobian
+    for (int w = 0; w < W; w++)
+        if (a.rebuild[w]) ctx->red_H_cols[(size_t) w] = 0;
+    hp.win.clear();
+    if (!plan.res.empty()) { // (its places among the kept Jacobians and in r are not the shipped blocks')
+        icg_prof_scope ps(ctx, "host_part_prior");
+        hipLaunchKernelGGL(k_host_part_prior, dim3((unsigned) ((plan.max_prior_nr + HP_PRIOR_ROWS - 1) / HP_PRIOR_ROWS), (unsigned) plan.res.size()), dim3(HP_THREADS), 0,
+                           ctx->stream, S.d_pr, S.d_pc, hp.d_J[dst], S.d_r);
+    }
+    {
+        icg_prof_scope ps(ctx, "host_part");
+        if (S.n_copies) hipLaunchKernelGGL(k_host_part_keep, dim3((unsigned) S.n_copies), dim3(HP_THREADS), 0, ctx->stream, S.d_cp, S.d_Jnew, hp.d_J[dst]);
+        hipLaunchKernelGGL(k_host_part, dim3((unsigned) ((plan.max_cells + HP_THREADS * HP_CPT - 1) / (HP_THREADS * HP_CPT)), (unsigned) plan.n_rebuilt), dim3(HP_THREADS), 0,
+                           ctx->stream, S.d_wins, S.d_blks, S.d_cols, (const double *) hp.d_J[dst], S.d_r, P, ctx->d_red_H, d_s, d_dg, d_po);
+    }
+    ICG_HIP(ctx, hipGetLastError());
+    if (int rc = c.finish()) return rc;
+    hp.cur = dst, hp.H_P = P;
+    hp.win.swap(next);
+    for (int w = 0; w < W; w++)
+        if (a.rebuild[w]) ctx->red_H_cols[(size_t) w] = a.Pw[w];
+    return ICG_OK;
+}
+
 extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
                                            const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s,
                                            double *host_diag, double *part_out) {
@@ -186,273 +508,18 @@ extern "C" int icg_reproj_host_parts_build_preint(icg_ctx *ctx, int P, const int
                                                   const int32_t *preint_of, const int32_t *preint_cols) {
     if (!ctx) return ICG_ERR_INVALID;
     const char *me = preint_of ? "icg_reproj_host_parts_build_preint" : prior_of ? "icg_reproj_host_parts_build_prior" : "icg_reproj_host_parts_build";
-    icg_partition &pt = ctx->part_w;
-    const int W       = pt.W;
-    if (W <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: no window partition: call icg_reproj_set_windows first", me);
-    if (P <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: P = %d", me, P);
-    if (P > HP_MAX_P) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: reduced systems of more than %d camera columns are not supported (%d)", me, HP_MAX_P, P);
-    if (W > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %d windows in one call (at most 65535)", me, W);
-    if (ctx->red_W != 0 && ctx->red_P != P) return icg_fail(ctx, ICG_ERR_INVALID, "%s: P = %d, the resident reduced systems have %d columns", me, P, ctx->red_P);
-    if (!Pw || !rebuild || !blk_off || !host_s || !host_diag) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", me);
-    if (blk_off[0] != 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window 0: blk_off[0] = %d", me, blk_off[0]);
-    for (int w = 0; w < W; w++)
-        if (blk_off[w + 1] < blk_off[w]) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d: blk_off decreases (%d after %d)", me, w, blk_off[w + 1], blk_off[w]);
-    const int nb = blk_off[W];
-    if (nb > 0 && (!nr || !nf || !cols || !jac_off || !r)) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", me);
-    // the slots of d_red_H follow the P of the resident reduced systems, or of the last call here while there are none: host parts (and
-    // kept Jacobians) of another shape, or of a buffer that is about to be replaced, are dropped before this call's are built
-    const size_t slot    = (size_t) P * (P + 1) / 2, H_bytes = sizeof(double) * (size_t) W * slot;
-    icg_hp_kept &hp      = ctx->hp;
-    const bool drop_all  = ctx->red_H_cols.size() != (size_t) W || (ctx->red_W == 0 && hp.H_P != P) || ctx->red_H_cap < H_bytes;
-    const bool have_kept = !drop_all && hp.win.size() == (size_t) W;
-    // ---- validation: nothing is changed before it is through --------------------------------------------------------------------------------
-    std::vector<int32_t> r_off((size_t) nb + 1, 0), c_off((size_t) nb + 1, 0), seen((size_t) P, -1);
-    size_t ship_doubles = 0, n_ship = 0, out_cells = 0;
-    int n_rebuilt = 0, max_cells = 0;
-    // prior blocks: pc_at walks prior_cols over the prior blocks of ALL windows (a window that is not rebuilt still places the others')
-    const icg_marg_set &ms = ctx->marg;
-    std::vector<hp_prior> priors;               // of the rebuilt windows
-    std::vector<std::pair<int, int>> prior_at;  // their (window, position in the window's block list)
-    size_t pc_at = 0;
-    int max_prior_nr = 0;
-    // preintegration blocks: the same walk over preint_cols; their entries follow prior_cols in the staged column list (ppc_at counts from 0
-    // here, the kernel's offsets are shifted once pc_at is known)
-    const icg_preint_resident &ps = ctx->preint;
-    std::vector<size_t> preint_idx; // positions in `priors` of the blocks that are preintegration factors
-    size_t ppc_at = 0;
-    for (int w = 0; w < W; w++) {
-        const std::vector<icg_hp_block> *kept = have_kept ? &hp.win[(size_t) w] : nullptr;
-        const int cnt                         = blk_off[w + 1] - blk_off[w];
-        if (rebuild[w] && (Pw[w] <= 0 || Pw[w] > P)) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d: Pw = %d (1 .. %d)", me, w, Pw[w], P);
-        bool any_keep = false;
-        for (int b = blk_off[w]; b < blk_off[w + 1]; b++) {
-            const int p = b - blk_off[w];
-            if (nr[b] <= 0 || nf[b] <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d x %d", me, w, p, nr[b], nf[b]);
-            if (nr[b] > ICG_HOST_PART_MAX_NR)
-                return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: window %d, block %d: %d residuals (at most %d)", me, w, p, nr[b], ICG_HOST_PART_MAX_NR);
-            if ((int64_t) r_off[(size_t) b] + nr[b] > INT32_MAX || (int64_t) c_off[(size_t) b] + nf[b] > INT32_MAX)
-                return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: window %d, block %d: more than 2^31 residuals or columns in one call", me, w, p);
-            r_off[(size_t) b + 1] = r_off[(size_t) b] + nr[b], c_off[(size_t) b + 1] = c_off[(size_t) b] + nf[b];
-            const int pp     = prior_of ? prior_of[b] : -1; // >= 0: the block is prior pp of the resident set
-            const size_t pc0 = pc_at;
-            if (pp >= 0) pc_at += (size_t) nf[b]; // (at most the columns of all blocks: below 2^31)
-            const int fp      = preint_of ? preint_of[b] : -1; // >= 0: the block is factor fp of the resident P2 set
-            const size_t ppc0 = ppc_at;
-            if (fp >= 0) ppc_at += (size_t) nf[b];
-            if (!rebuild[w]) continue;
-            if (nf[b] > Pw[w]) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d columns in a system of %d", me, w, p, nf[b], Pw[w]);
-            for (int x = 0; x < nf[b]; x++) {
-                const int c = cols[(size_t) c_off[(size_t) b] + x];
-                if (c < 0 || c >= Pw[w]) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: column %d outside the system (%d)", me, w, p, c, Pw[w]);
-                if (seen[(size_t) c] == b) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: column %d twice", me, w, p, c);
-                seen[(size_t) c] = b;
-            }
-            if (pp >= 0) {
-                if (!prior_cols) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a prior block without prior_cols", me, w, p);
-                if (ms.n <= 0 || !ms.res_valid)
-                    return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no prior set is resident and evaluated (icg_marg_prior_set, then icg_marg_prior_evaluate_resident)",
-                                    me, w, p);
-                if (pp >= ms.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: prior %d outside the resident set of %d", me, w, p, pp, ms.n);
-                const int pr = ms.h_r[(size_t) pp];
-                if (nr[b] != pr) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, prior %d has %d", me, w, p, nr[b], pp, pr);
-                for (int x = 0; x < nf[b]; x++) {
-                    const int c = prior_cols[pc0 + (size_t) x];
-                    if (c < 0 || c >= pr) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: prior column %d outside the prior (%d)", me, w, p, c, pr);
-                }
-                priors.push_back({ms.d_J + ms.h_j_off[(size_t) pp], ms.d_res + ms.h_e_off[(size_t) pp], 0 /* its place among the kept Jacobians follows below */,
-                                  pr /* J0 is r x r */, r_off[(size_t) b], (int32_t) pc0, nr[b], nf[b], jac_off[b] == ICG_HP_JAC_FROM_PRIOR ? 1 : 0});
-                prior_at.push_back({w, p});
-                max_prior_nr = std::max(max_prior_nr, nr[b]);
-            }
-            if (fp >= 0) {
-                if (pp >= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both a prior (%d) and a preintegration factor (%d)", me, w, p, pp, fp);
-                if (!preint_cols) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a preintegration block without preint_cols", me, w, p);
-                const bool fill = jac_off[b] == ICG_HP_JAC_FROM_PREINT;
-                if (ps.n <= 0 || !ps.res_valid || (fill && !ps.jac_valid))
-                    return icg_fail(ctx, ICG_ERR_INVALID,
-                                    "%s: window %d, block %d: no preintegration set is resident and evaluated%s (icg_preint_set, then icg_preint_evaluate_resident)", me, w,
-                                    p, fill ? " with Jacobians" : "");
-                if (fp >= ps.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: factor %d outside the resident set of %d", me, w, p, fp, ps.n);
-                if (nr[b] != 15) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, a preintegration factor has 15", me, w, p, nr[b]);
-                for (int x = 0; x < nf[b]; x++) {
-                    const int c = preint_cols[ppc0 + (size_t) x];
-                    if (c < 0 || c >= 32 || c == 6 || c == 22)
-                        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: preintegration column %d (0 .. 31 without 6 and 22)", me, w, p, c);
-                }
-                preint_idx.push_back(priors.size());
-                priors.push_back({ps.d_jac ? ps.d_jac + 480 * (size_t) fp : nullptr, ps.d_res + 15 * (size_t) fp, 0, 32, r_off[(size_t) b], (int32_t) ppc0, 15, nf[b], fill ? 1 : 0});
-                prior_at.push_back({w, p});
-                max_prior_nr = std::max(max_prior_nr, 15);
-            }
-            if (jac_off[b] >= 0) {
-                if (!J) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a Jacobian offset without J", me, w, p);
-                ship_doubles += (size_t) nr[b] * nf[b], n_ship++;
-            } else if (jac_off[b] == ICG_HP_JAC_FROM_PRIOR && pp >= 0) {
-                // gathered from the prior's J0 on the device
-            } else if (jac_off[b] == ICG_HP_JAC_FROM_PREINT && fp >= 0) {
-                // gathered from the factor's resident Jacobian on the device
-            } else if (jac_off[b] == ICG_HP_JAC_FROM_PREINT) {
-                return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: ICG_HP_JAC_FROM_PREINT for a block that is no preintegration factor", me, w, p);
-            } else if (jac_off[b] == -1) {
-                any_keep = true;
-                if (!kept || (size_t) p >= kept->size()) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no kept Jacobian", me, w, p);
-                const icg_hp_block &k = (*kept)[(size_t) p];
-                if (k.nr != nr[b] || k.nf != nf[b])
-                    return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: the kept Jacobian is %d x %d, not %d x %d", me, w, p, k.nr, k.nf, nr[b], nf[b]);
-            } else {
-                return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: jac_off = %lld", me, w, p, (long long) jac_off[b]);
-            }
-        }
-        if (!rebuild[w]) continue;
-        if (any_keep && (size_t) cnt != kept->size())
-            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d: %d blocks, %zu kept, and a block keeps its Jacobian", me, w, cnt, kept->size());
-        n_rebuilt++;
-        max_cells = std::max(max_cells, Pw[w] * (Pw[w] + 1) / 2);
-        out_cells += (size_t) Pw[w] * (Pw[w] + 1) / 2;
-    }
-    if (priors.size() > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %zu prior blocks in one call (at most 65535)", me, priors.size());
-    if (n_rebuilt == 0) return ICG_OK;
+    const hp_args a{me, P, ctx->part_w.W, Pw, blk_off, nr, nf, cols, rebuild, jac_off, J, r, host_s, host_diag, part_out};
+    hp_family F[2] = {{hp_rules_prior, prior_of, prior_cols, ICG_HP_JAC_FROM_PRIOR, 0}, {hp_rules_preint, preint_of, preint_cols, ICG_HP_JAC_FROM_PREINT, 0}};
+    hp_plan plan;
+    int rc, dst;
+    if ((rc = hp_validate(ctx, a, F, plan))) return rc;
+    if (plan.n_rebuilt == 0) return ICG_OK;
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    // ---- the kept Jacobians after this call: dense, window after window -----------------------------------------------------------------------
-    std::vector<std::vector<icg_hp_block>> next((size_t) W);
-    int64_t total = 0;
-    bool same     = have_kept;
-    for (int w = 0; w < W; w++) {
-        std::vector<icg_hp_block> &nw = next[(size_t) w];
-        if (rebuild[w])
-            for (int b = blk_off[w]; b < blk_off[w + 1]; b++) nw.push_back({0, nr[b], nf[b]});
-        else if (have_kept)
-            nw = hp.win[(size_t) w];
-        same = same && nw.size() == hp.win[(size_t) w].size();
-        for (size_t p = 0; p < nw.size(); p++) {
-            if (same) same = hp.win[(size_t) w][p].off == total && hp.win[(size_t) w][p].nr == nw[p].nr && hp.win[(size_t) w][p].nf == nw[p].nf;
-            nw[p].off = total;
-            total += (int64_t) nw[p].nr * nw[p].nf;
-        }
-    }
-    int rc;
-    if (drop_all) {
-        icg_red_drop_host_parts(ctx, (size_t) W);
-        if ((rc = icg_red_ensure_capacity(ctx, &ctx->d_red_H, &ctx->red_H_cap, H_bytes))) return rc;
-    }
-    const int dst = same ? hp.cur : 1 - hp.cur;
-    if (!same) {
-        // what stays moves into the other buffer, in runs that are contiguous on both sides
-        const size_t bytes = sizeof(double) * (size_t) std::max<int64_t>(total, 1);
-        if ((rc = icg_grow(ctx, (void **) &hp.d_J[dst], &hp.cap[dst], bytes, bytes + bytes / 4))) return rc;
-        int64_t run_src = 0, run_dst = 0, run_n = 0;
-        auto flush      = [&]() -> int {
-            if (run_n) ICG_HIP(ctx, hipMemcpyAsync(hp.d_J[dst] + run_dst, hp.d_J[hp.cur] + run_src, sizeof(double) * (size_t) run_n, hipMemcpyDeviceToDevice, ctx->stream));
-            run_n = 0;
-            return 0;
-        };
-        for (int w = 0; w < W && have_kept; w++)
-            for (size_t p = 0; p < next[(size_t) w].size(); p++) {
-                if (rebuild[w] && jac_off[(size_t) blk_off[w] + p] != -1) continue; // (shipped, or gathered from a prior's J0)
-                const icg_hp_block &o = hp.win[(size_t) w][p], &n = next[(size_t) w][p];
-                const int64_t len     = (int64_t) n.nr * n.nf;
-                if (run_n && o.off == run_src + run_n && n.off == run_dst + run_n) {
-                    run_n += len;
-                    continue;
-                }
-                if ((rc = flush())) return rc;
-                run_src = o.off, run_dst = n.off, run_n = len;
-            }
-        if ((rc = flush())) return rc;
-    }
-    // ---- staging ------------------------------------------------------------------------------------------------------------------------------
-    std::vector<hp_win> wins;
-    std::vector<hp_blk> blks((size_t) nb);
-    std::vector<hp_copy> copies;
-    {
-        int64_t out_off = 0, src = 0;
-        for (int w = 0; w < W; w++) {
-            if (!rebuild[w]) continue;
-            wins.push_back({w, Pw[w], blk_off[w], blk_off[w + 1], (int32_t) wins.size(), 0, (int64_t) ((size_t) w * slot), out_off});
-            out_off += (int64_t) Pw[w] * (Pw[w] + 1) / 2;
-            for (int b = blk_off[w]; b < blk_off[w + 1]; b++) {
-                const icg_hp_block &n = next[(size_t) w][(size_t) (b - blk_off[w])];
-                blks[(size_t) b]      = {n.off, r_off[(size_t) b], c_off[(size_t) b], nr[b], nf[b]};
-                if (jac_off[b] >= 0) copies.push_back({src, n.off, (int64_t) nr[b] * nf[b]}), src += (int64_t) nr[b] * nf[b];
-            }
-        }
-        for (size_t k = 0; k < priors.size(); k++) priors[k].Jd_off = next[(size_t) prior_at[k].first][(size_t) prior_at[k].second].off;
-        for (size_t k : preint_idx) priors[k].pc_off += (int32_t) (prior_cols ? pc_at : 0); // (preint_cols is staged behind prior_cols)
-    }
-    const size_t n_r = (size_t) r_off[(size_t) nb], n_c = (size_t) c_off[(size_t) nb];
+    std::vector<std::vector<icg_hp_block>> next;
+    if ((rc = hp_place_kept(ctx, a, plan, next, &dst))) return rc;
     icg_call c(ctx);
-    if ((rc = c.reserve(sizeof(hp_win) * wins.size() + sizeof(hp_blk) * blks.size() + sizeof(hp_copy) * copies.size() + sizeof(hp_prior) * priors.size() +
-                        sizeof(int32_t) * (n_c + pc_at + ppc_at) + sizeof(double) * (n_r + ship_doubles + 2 * (size_t) n_rebuilt * P + out_cells) + 20 * 256)))
-        return rc;
-    const hp_win *d_wins  = c.in(wins.data(), wins.size());
-    const hp_blk *d_blks  = c.in(blks.data(), blks.size());
-    const hp_copy *d_cp   = c.in(copies.data(), copies.size());
-    const int32_t *d_cols = c.in(cols, n_c);
-    const hp_prior *d_pr  = c.in(priors.data(), priors.size());
-    const int32_t *d_pc   = nullptr;
-    if (!priors.empty()) { // prior_cols | preint_cols, of all windows (either may be absent)
-        std::vector<int32_t> pcs;
-        if (prior_cols) pcs.assign(prior_cols, prior_cols + pc_at);
-        if (preint_cols) pcs.insert(pcs.end(), preint_cols, preint_cols + ppc_at);
-        d_pc = c.in(pcs.data(), pcs.size());
-    }
-    double *d_r           = nullptr;
-    if (!prior_of && !preint_of) {
-        d_r = c.in(r, n_r);
-    } else {
-        // The slots of the prior blocks (of every window, rebuilt or not) are placed but not read from the caller: staged block by block,
-        // like the shipped Jacobians below.  Whatever bytes the arena holds there go up with the rest; for the rebuilt windows
-        // k_host_part_prior overwrites them on the device, in stream order behind the upload and ahead of k_host_part, and the blocks of
-        // the other windows are not consumed.
-        const size_t off = icg_arena_alloc(ctx, sizeof(double) * n_r);
-        double *h        = icg_h<double>(ctx, off);
-        for (int b = 0; b < nb; b++)
-            if ((!prior_of || prior_of[b] < 0) && (!preint_of || preint_of[b] < 0))
-                memcpy(h + r_off[(size_t) b], r + r_off[(size_t) b], sizeof(double) * (size_t) nr[b]);
-        c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * n_r);
-        d_r = icg_d<double>(ctx, off);
-    }
-    const double *d_Jnew  = nullptr;
-    if (ship_doubles) { // the shipped Jacobians, block after block
-        const size_t off = icg_arena_alloc(ctx, sizeof(double) * ship_doubles);
-        double *h        = icg_h<double>(ctx, off);
-        for (int w = 0; w < W; w++)
-            for (int b = blk_off[w]; rebuild[w] && b < blk_off[w + 1]; b++)
-                if (jac_off[b] >= 0) memcpy(h, J + jac_off[b], sizeof(double) * (size_t) nr[b] * nf[b]), h += (size_t) nr[b] * nf[b];
-        c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * ship_doubles);
-        d_Jnew = icg_d<double>(ctx, off);
-    }
-    if ((rc = c.seal())) return rc;
-    // s and diag of the rebuilt windows only: the rows of the others are not the call's to write
-    double *d_s = c.out((double *) nullptr, (size_t) n_rebuilt * P), *d_dg = c.out((double *) nullptr, (size_t) n_rebuilt * P);
-    for (const hp_win &hw : wins) {
-        c.outs.push_back({(void *) (host_s + (size_t) hw.w * P), (size_t) (reinterpret_cast<char *>(d_s + (size_t) hw.slot * P) - ctx->d_arena), sizeof(double) * (size_t) P, false});
-        c.outs.push_back({(void *) (host_diag + (size_t) hw.w * P), (size_t) (reinterpret_cast<char *>(d_dg + (size_t) hw.slot * P) - ctx->d_arena), sizeof(double) * (size_t) P, false});
-    }
-    double *d_po = part_out ? c.out(part_out, out_cells) : nullptr;
-    ICG_LAUNCH_GUARD(c);
-    // from here on the rebuilt windows' parts and the kept Jacobians are being replaced: a failure below leaves those windows without a part
-    // and no window with a kept Jacobian
-    for (int w = 0; w < W; w++)
-        if (rebuild[w]) ctx->red_H_cols[(size_t) w] = 0;
-    hp.win.clear();
-    if (!priors.empty()) { // (its places among the kept Jacobians and in r are not the shipped blocks')
-        icg_prof_scope ps(ctx, "host_part_prior");
-        hipLaunchKernelGGL(k_host_part_prior, dim3((unsigned) ((max_prior_nr + HP_PRIOR_ROWS - 1) / HP_PRIOR_ROWS), (unsigned) priors.size()), dim3(HP_THREADS), 0,
-                           ctx->stream, d_pr, d_pc, hp.d_J[dst], d_r);
-    }
-    {
-        icg_prof_scope ps(ctx, "host_part");
-        if (!copies.empty())
-            hipLaunchKernelGGL(k_host_part_keep, dim3((unsigned) copies.size()), dim3(HP_THREADS), 0, ctx->stream, d_cp, d_Jnew, hp.d_J[dst]);
-        hipLaunchKernelGGL(k_host_part, dim3((unsigned) ((max_cells + HP_THREADS * HP_CPT - 1) / (HP_THREADS * HP_CPT)), (unsigned) n_rebuilt), dim3(HP_THREADS), 0,
-                           ctx->stream, d_wins, d_blks, d_cols, (const double *) hp.d_J[dst], d_r, P, ctx->d_red_H, d_s, d_dg, d_po);
-    }
-    ICG_HIP(ctx, hipGetLastError());
-    if ((rc = c.finish())) return rc;
-    hp.cur = dst, hp.H_P = P;
-    hp.win.swap(next);
-    for (int w = 0; w < W; w++)
-        if (rebuild[w]) ctx->red_H_cols[(size_t) w] = Pw[w];
-    return ICG_OK;
+    hp_staged S;
+    if ((rc = hp_stage(ctx, a, F, plan, next, c, S))) return rc;
+    return hp_launch(ctx, a, plan, next, dst, c, S);
 }
+

@@ -170,11 +170,6 @@ struct MarginalizationBatch::State {
     HostFactorBlocks blocks; // setDeviceReducedSystem: the window's host factors, instead of their J^T J in plan.H
 };
 
-struct MarginalizationBatch::ReducedRhs {
-    int P;
-    const std::vector<double> &s, &host_s;
-};
-
 struct MarginalizationBatch::DeviceM3 {
     std::vector<char> on_device; // per window: its prior is in the arrays below
     std::vector<double> Hp, bp, J0, e0;
@@ -183,17 +178,62 @@ struct MarginalizationBatch::DeviceM3 {
     uint64_t keep_id{0};   // setKeepLinearized: the call's kept linearization
 };
 
+// what one marginalize() works on, handed from phase to phase
+struct MarginalizationBatch::Run {
+    const size_t NW;
+    std::vector<State> st;
+    std::vector<const ResidualBlockInfo *> taken; // setDevicePrior: the prior each window hands over ...
+    std::vector<int32_t> prior_in_set;            // ... and its index in the resident set (window order)
+    int P = 0;                                        // columns of the widest planned window's reduced system
+    std::vector<double> S, s, hll, host_s, min_dev;   // what phase 3 reads back (S and hll, or host_s and min_dev, by the switches)
+    std::vector<char> added, structured, good;        // per window: its eliminated part was added; it took the structured path; it has a prior
+    std::vector<double> min_hll;                      // the smallest landmark diagonal of a window, for the first guard
+    DeviceM3 dev;
+    std::chrono::steady_clock::time_point t0, t1, t2, t3, t4;
+    // setDeviceReducedSystem: the block lists of the planned windows, concatenated as one icg_reproj_host_parts_build(_prior) call takes them
+    struct HostPartCall {
+        std::vector<int32_t> Pw, blk_off, nr, nf, cols, prior_of, prior_cols;
+        std::vector<uint8_t> rebuild;
+        std::vector<int64_t> jac_off;
+        std::vector<double> J, r;
+    };
+    explicit Run(size_t n) : NW(n), st(n), taken(n, nullptr), prior_in_set(n, -1), added(n, 0), structured(n, 0), good(n, 0), min_hll(n, 0.0),
+          dev{std::vector<char>(n, 0), {}, {}, {}, {}, std::vector<size_t>(n, 0), std::vector<size_t>(n, 0), std::vector<int>(n, -1), 0} {}
+    HostPartCall hostPartCall(bool dev_prior) const {
+        HostPartCall C{std::vector<int32_t>(NW, 1), std::vector<int32_t>(NW + 1, 0), {}, {}, {}, {}, {}, std::vector<uint8_t>(NW, 0), {}, {}, {}};
+        for (size_t w = 0; w < NW; w++) {
+            if (st[w].planned) {
+                const HostFactorBlocks &B = st[w].blocks;
+                C.Pw[w] = st[w].plan.P, C.rebuild[w] = 1;
+                for (int64_t off : B.jac_off) C.jac_off.push_back(off < 0 ? off : (int64_t) C.J.size() + off); // (< 0: ICG_HP_JAC_FROM_PRIOR)
+                if (dev_prior) {
+                    C.prior_of.insert(C.prior_of.end(), B.nr.size(), -1);
+                    if (B.prior_block >= 0) C.prior_of[C.nr.size() + (size_t) B.prior_block] = prior_in_set[w];
+                    C.prior_cols.insert(C.prior_cols.end(), B.prior_cols.begin(), B.prior_cols.end());
+                }
+                C.nr.insert(C.nr.end(), B.nr.begin(), B.nr.end()), C.nf.insert(C.nf.end(), B.nf.begin(), B.nf.end());
+                C.cols.insert(C.cols.end(), B.cols.begin(), B.cols.end());
+                C.J.insert(C.J.end(), B.J.begin(), B.J.end()), C.r.insert(C.r.end(), B.r.begin(), B.r.end());
+            }
+            C.blk_off[w + 1] = (int32_t) C.nr.size();
+        }
+        return C;
+    }
+};
+
 // device M3 (setDeviceLinearization): every window whose eliminated part was added and that passes the first guard, one call.  resident
 // (setDeviceReducedSystem): the windows' systems are formed on the device from what steps 3 left there; only b = host_s + s goes up.
-bool MarginalizationBatch::linearizeOnDevice(const std::vector<State> &st, const std::vector<char> &added, const std::vector<double> &min_hll,
-                                             DeviceM3 &dev, std::string *what, const ReducedRhs *resident) {
+bool MarginalizationBatch::linearizeOnDevice(Run &R, std::string *what) {
+    const std::vector<State> &st = R.st;
+    DeviceM3 &dev                = R.dev;
+    const bool resident          = device_reduced_system_;
     const size_t NW    = st.size();
     const double GUARD = 100.0 * 1e-8; // (finishStructured: 100 x the reference's floor)
     std::vector<int32_t> dP, dm;
     std::vector<size_t> h_off, who;
     size_t th = 0, tb = 0, tr = 0, trr = 0;
     for (size_t w = 0; w < NW; w++) {
-        if (!added[w] || !(min_hll[w] > GUARD)) continue;
+        if (!R.added[w] || !(R.min_hll[w] > GUARD)) continue;
         const MarginalizationInfo::StructuredPlan &plan = st[w].plan;
         dev.on_device[w] = 1, dev.r_off[w] = tr, dev.rr_off[w] = trr;
         dev.slot[w] = (int) who.size();
@@ -210,108 +250,66 @@ bool MarginalizationBatch::linearizeOnDevice(const std::vector<State> &st, const
     if (resident) {
         std::vector<int32_t> win(who.size());
         for (size_t k = 0; k < who.size(); k++) {
-            const size_t w = who[k], at = w * (size_t) resident->P;
+            const size_t w = who[k], at = w * (size_t) R.P;
             win[k]         = (int32_t) w;
-            for (int i = 0; i < dP[k]; i++) db[b_off[k] + (size_t) i] = resident->host_s[at + (size_t) i] + resident->s[at + (size_t) i]; // (plan.b += s)
+            for (int i = 0; i < dP[k]; i++) db[b_off[k] + (size_t) i] = R.host_s[at + (size_t) i] + R.s[at + (size_t) i]; // (plan.b += s)
         }
         uint64_t id = 0;
-        if (icg_marg_linearize_resident(factors_.ctx(), resident->P, (int) who.size(), win.data(), dP.data(), dm.data(), db.data(), 1e-8, dev.Hp.data(),
+        if (icg_marg_linearize_resident(factors_.ctx(), R.P, (int) who.size(), win.data(), dP.data(), dm.data(), db.data(), 1e-8, dev.Hp.data(),
                                         dev.bp.data(), dev.J0.data(), dev.e0.data(), nullptr, dev_min.data(), dev_status.data(), nullptr,
                                         keep_linearized_ ? &id : nullptr) != ICG_OK) {
             *what = icg_last_error(factors_.ctx());
             return false;
         }
         dev.keep_id = id;
-        for (size_t k = 0; k < who.size(); k++) // second guard of finishStructured, and a solver that did not converge
-            if (!(dev_min[k] > GUARD) || (dev_status[k] & 1)) dev.on_device[who[k]] = 0;
-        return true;
-    }
-    factors_.forEachWindow(who.size(), [&](size_t k) {
-        const MarginalizationInfo::StructuredPlan &plan = st[who[k]].plan;
-        memcpy(&dH[h_off[k]], plan.H.data(), sizeof(double) * plan.H.size());
-        memcpy(&db[b_off[k]], plan.b.data(), sizeof(double) * plan.b.size());
-    });
-    MarginalizationLinearizer lin(true, factors_.ctx());
-    if (keep_linearized_) {
-        dev.keep_id = lin.linearizeKeep((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev.Hp.data(), dev.bp.data(), dev.J0.data(),
-                                        dev.e0.data(), nullptr, dev_min.data(), dev_status.data(), what);
-        if (dev.keep_id == 0) return false;
-    } else if (!lin.linearize((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev.Hp.data(), dev.bp.data(), dev.J0.data(),
-                              dev.e0.data(), nullptr, dev_min.data(), dev_status.data(), what)) {
-        return false;
+    } else {
+        factors_.forEachWindow(who.size(), [&](size_t k) {
+            const MarginalizationInfo::StructuredPlan &plan = st[who[k]].plan;
+            memcpy(&dH[h_off[k]], plan.H.data(), sizeof(double) * plan.H.size());
+            memcpy(&db[b_off[k]], plan.b.data(), sizeof(double) * plan.b.size());
+        });
+        MarginalizationLinearizer lin(true, factors_.ctx());
+        if (keep_linearized_) {
+            dev.keep_id = lin.linearizeKeep((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev.Hp.data(), dev.bp.data(), dev.J0.data(),
+                                            dev.e0.data(), nullptr, dev_min.data(), dev_status.data(), what);
+            if (dev.keep_id == 0) return false;
+        } else if (!lin.linearize((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev.Hp.data(), dev.bp.data(), dev.J0.data(),
+                                  dev.e0.data(), nullptr, dev_min.data(), dev_status.data(), what)) {
+            return false;
+        }
     }
     for (size_t k = 0; k < who.size(); k++) // second guard of finishStructured, and a solver that did not converge
         if (!(dev_min[k] > GUARD) || (dev_status[k] & 1)) dev.on_device[who[k]] = 0;
     return true;
 }
 
-bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
-    const size_t NW = windows_.size();
-    if (ok) ok->assign(NW, 0);
-    n_structured_ = n_dense_ = 0;
-    phase_ms_[0] = phase_ms_[1] = phase_ms_[2] = phase_ms_[3] = 0;
-    n_device_priors_ = n_priors_from_kept_ = n_deferred_evaluations_ = 0;
-    error_.clear();
-    window_error_.clear();
-    if (device_prior_ && !device_reduced_system_) {
-        error_ = "setDevicePrior(true) needs setDeviceReducedSystem(true): the resident prior is read by the device call that builds the host-factor parts";
-        return false;
-    }
-    if (device_prior_ && !devicePriorAvailable()) {
-        error_ = std::string(missingDevicePriorEntry()) + " is not in this build";
-        return false;
-    }
-    if (device_reduced_system_ && !device_linearization_) {
-        error_ = "setDeviceReducedSystem(true) needs setDeviceLinearization(true): the resident reduced systems are read by the device call's linearization";
-        return false;
-    }
-    if (device_reduced_system_ && !deviceReducedSystemAvailable()) {
-        error_ = std::string(missingReducedSystemEntry()) + " is not in this build";
-        return false;
-    }
-    const bool resident = device_reduced_system_;
-    if (keep_linearized_ && !device_linearization_) {
-        error_ = "setKeepLinearized(true) needs setDeviceLinearization(true): what is kept is the device call's linearization";
-        return false;
-    }
-    if (keep_linearized_ && !keepLinearizedAvailable()) {
-        error_ = "icg_marg_linearize_batch_keep is not in this build";
-        return false;
-    }
-    if (NW == 0) return true;
-    const bool dev_prior = device_prior_;
-    // (the last marginalize()'s; this one keeps its own below.  setDevicePrior: the resident set is built from it first, in phase 1)
-    if (!dev_prior) releaseKept();
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms  = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-        return std::chrono::duration<double, std::milli>(b - a).count();
-    };
-    const auto t_layout = now();
-    if (!laid_out_ && !layout()) return false;
-    const double layout_ms = ms(t_layout, now());
-    auto fail = [&](const std::string &what) {
-        error_ = what;
-        for (auto &W : windows_) W->evaluated = false;
-        return false;
-    };
+// a window that has no valid prior after this call
+void MarginalizationBatch::invalidate(MarginalizationInfo &I) {
+    I.isvalid_ = false;
+    I.releaseMemory();
+}
 
-    // ---- 1: every window's reprojection factors, one launch (residual_block_info.h:44-88 with the corrector :59-87 on the device) -------
-    auto t0 = now();
-    icg_ctx *ctx      = factors_.ctx();
-    const int n_poses = factors_.numPoses(), n_lm = factors_.numLandmarks();
-    // setDevicePrior: the prior each window hands over and its index in the resident set (window order).  The set copies J0 / e0 — from the
-    // kept linearization where the views are tagged with it — so it is built before anything drops that linearization: the release here,
-    // and icg_marg_linearize_resident in step 4.
-    std::vector<const ResidualBlockInfo *> taken(NW, nullptr);
-    std::vector<int32_t> prior_in_set(NW, -1);
-    if (dev_prior) {
+// a device call all windows share failed: no window stays evaluated
+bool MarginalizationBatch::fail(const std::string &what) {
+    error_ = what;
+    for (auto &W : windows_) W->evaluated = false;
+    return false;
+}
+
+// ---- 1: every window's reprojection factors, one launch (residual_block_info.h:44-88 with the corrector :59-87 on the device) -------------
+bool MarginalizationBatch::evaluateWindows(Run &R) {
+    icg_ctx *ctx = factors_.ctx();
+    // setDevicePrior: the resident set of the priors the windows hand over.  The set copies J0 / e0 — from the kept linearization where the
+    // views are tagged with it — so it is built before anything drops that linearization: the release here, and
+    // icg_marg_linearize_resident in step 4.
+    if (device_prior_) {
         std::vector<MargPriorView> views;
-        for (size_t w = 0; w < NW; w++) {
+        for (size_t w = 0; w < R.NW; w++) {
             const ResidualBlockInfo *f = windows_[w]->info->devicePriorCandidate();
             if (!f) continue;
             const MargPriorView &v = dynamic_cast<const MargPriorSource *>(f->costFunction().get())->margPriorView();
             if (v.r > ICG_MARG_MAX_R) continue; // (wider than a resident prior may be: it stays a host factor)
-            taken[w] = f, prior_in_set[w] = (int32_t) views.size();
+            R.taken[w] = f, R.prior_in_set[w] = (int32_t) views.size();
             views.push_back(v);
         }
         std::string what;
@@ -323,35 +321,37 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
     if (factors_.numFactors() > 0) {
         std::vector<double> poses, ext, inv, td;
         factors_.gather(poses, ext, inv, td);
-        if (icg_reproj_eval_windows(ctx, n_poses, poses.data(), ext.data(), n_lm, inv.data(), td.data(), 1, huber_) != ICG_OK)
+        if (icg_reproj_eval_windows(ctx, factors_.numPoses(), poses.data(), ext.data(), factors_.numLandmarks(), inv.data(), td.data(), 1, huber_) != ICG_OK)
             return fail(icg_last_error(ctx));
     }
     for (auto &W : windows_) W->evaluated = true;
-    auto t1 = now();
+    return true;
+}
 
-    // ---- 2: M1 bookkeeping, host factors, compact camera layout per window -------------------------------------------------------------
-    std::vector<State> st(NW);
+// ---- 2: M1 bookkeeping, host factors, compact camera layout per window -------------------------------------------------------------------
+void MarginalizationBatch::bookkeeping(Run &R) {
     const bool force_dense = MarginalizationInfo::denseForced();
-    factors_.forEachWindow(NW, [&](size_t w) {
+    factors_.forEachWindow(R.NW, [&](size_t w) {
         MarginalizationInfo &I = *windows_[w]->info;
+        State &T               = R.st[w];
         // (setDevicePrior: the point the taken prior is evaluated at on the device — the values its Evaluate() would read here; the factor
         // itself is deferred, its blocks are still snapshot)
-        if (taken[w]) prior_set_.pack((size_t) prior_in_set[w], taken[w]->parameterBlocks().data());
-        if (!I.updateParameterBlocksIndex() || !I.preMarginalization(taken[w])) { // (:75-86: nothing to marginalize / an evaluation failed)
-            I.isvalid_ = false;
-            I.releaseMemory();
-            return;
-        }
-        st[w].alive = true;
-        if (resident) // (layout and gather only: the blocks' J^T J is formed on the device in step 3)
-            st[w].planned = !force_dense && I.planLayout(st[w].plan) && I.gatherHostBlocks(st[w].plan, st[w].blocks, taken[w]);
+        if (R.taken[w]) prior_set_.pack((size_t) R.prior_in_set[w], R.taken[w]->parameterBlocks().data());
+        if (!I.updateParameterBlocksIndex() || !I.preMarginalization(R.taken[w])) return invalidate(I); // (:75-86: nothing to marginalize / an evaluation failed)
+        T.alive = true;
+        if (device_reduced_system_) // (layout and gather only: the blocks' J^T J is formed on the device in step 3)
+            T.planned = !force_dense && I.planLayout(T.plan) && I.gatherHostBlocks(T.plan, T.blocks, R.taken[w]);
         else
-            st[w].planned = !force_dense && I.planStructured(st[w].plan);
+            T.planned = !force_dense && I.planStructured(T.plan);
     });
-    auto t2 = now();
+}
 
-    // ---- 3: assembly + landmark elimination of every planned window, one launch sequence; the landmark diagonals --------------------------
-    // (csrc/reproj_schur.hip, schur_impl: reduced systems of up to kMaxCameraColumns columns; a wider window takes the dense path on its own)
+// ---- 3: assembly + landmark elimination of every planned window, one launch sequence; the landmark diagonals ------------------------------
+// (csrc/reproj_schur.hip, schur_impl: reduced systems of up to kMaxCameraColumns columns; a wider window takes the dense path on its own)
+bool MarginalizationBatch::assembleAndEliminate(Run &R) {
+    const size_t NW   = R.NW;
+    std::vector<State> &st = R.st;
+    icg_ctx *ctx      = factors_.ctx();
     for (size_t w = 0; w < NW; w++) {
         if (!st[w].planned) continue;
         const WindowFactorSet::Window &W = factors_.window(w);
@@ -360,116 +360,97 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
         V += (W.ext && st[w].plan.camera_column_of.count(W.ext) ? 6 : 0) + (W.td && st[w].plan.camera_column_of.count(W.td) ? 1 : 0);
         if (V > kMaxCameraColumns) st[w].planned = false;
     }
-    int P = 0;
     for (size_t w = 0; w < NW; w++)
-        if (st[w].planned) P = std::max(P, st[w].plan.P);
-    std::vector<double> S, s, hll, host_s, min_dev;
-    if (P > 0) {
-        std::vector<int32_t> col_pose((size_t) n_poses, -1), col_ext(NW, -1), col_td(NW, -1);
-        for (size_t w = 0; w < NW; w++) {
-            if (!st[w].planned) continue; // (its columns stay constant: the window adds nothing to any reduced system that is read)
-            const WindowFactorSet::Window &W = factors_.window(w);
-            auto col                         = [&](const double *p) {
-                auto it = st[w].plan.camera_column_of.find(p);
-                return it == st[w].plan.camera_column_of.end() ? -1 : it->second;
-            };
-            for (size_t k = 0; k < W.poses.size(); k++) col_pose[(size_t) W.pose_begin + k] = col(W.poses[k]);
-            col_ext[w] = col(W.ext), col_td[w] = col(W.td);
-        }
-        std::vector<uint8_t> reassemble(NW, 1);
-        std::vector<double> damp(NW, 0.0), diag_cc(NW * (size_t) P), cost(NW, 0.0);
-        s.assign(NW * (size_t) P, 0.0), hll.assign((size_t) std::max(n_lm, 1), 0.0);
-        if (resident) {
-            // S stays on the device; the host-factor part of every planned window is built beside it from the window's blocks
-            std::vector<int32_t> Pw(NW, 1), blk_off(NW + 1, 0), nr, nf, cols, prior_of, prior_cols;
-            std::vector<uint8_t> rebuild(NW, 0);
-            std::vector<int64_t> jac_off;
-            std::vector<double> J, r, host_diag(NW * (size_t) P, 0.0);
-            host_s.assign(NW * (size_t) P, 0.0);
-            for (size_t w = 0; w < NW; w++) {
-                if (st[w].planned) {
-                    const HostFactorBlocks &B = st[w].blocks;
-                    Pw[w] = st[w].plan.P, rebuild[w] = 1;
-                    for (int64_t off : B.jac_off) jac_off.push_back(off < 0 ? off : (int64_t) J.size() + off); // (< 0: ICG_HP_JAC_FROM_PRIOR)
-                    if (dev_prior) {
-                        prior_of.insert(prior_of.end(), B.nr.size(), -1);
-                        if (B.prior_block >= 0) prior_of[nr.size() + (size_t) B.prior_block] = prior_in_set[w];
-                        prior_cols.insert(prior_cols.end(), B.prior_cols.begin(), B.prior_cols.end());
-                    }
-                    nr.insert(nr.end(), B.nr.begin(), B.nr.end()), nf.insert(nf.end(), B.nf.begin(), B.nf.end());
-                    cols.insert(cols.end(), B.cols.begin(), B.cols.end());
-                    J.insert(J.end(), B.J.begin(), B.J.end()), r.insert(r.end(), B.r.begin(), B.r.end());
-                }
-                blk_off[w + 1] = (int32_t) nr.size();
-            }
-            if (icg_reproj_schur_windows_resident(ctx, P, col_pose.data(), col_ext.data(), col_td.data(), nullptr, reassemble.data(), damp.data(), 0.0, 0.0,
-                                                  s.data(), diag_cc.data(), cost.data()) != ICG_OK)
-                return fail(icg_last_error(ctx));
-            if (dev_prior) {
-                // the taken priors are evaluated where they lie (e = e0 + J0 dx at the packed point), their blocks take residual and Jacobian
-                // columns from there, and the first guard's minimum comes back as one double per window
-                std::vector<double> sq((size_t) std::max(n_device_priors_, 1));
-                std::string what;
-                if (n_device_priors_ > 0 && !prior_set_.evaluateResident(sq.data(), &what)) return fail(what);
-                min_dev.assign(NW, 0.0);
-                if (icg_reproj_host_parts_build_prior(ctx, P, Pw.data(), rebuild.data(), blk_off.data(), nr.data(), nf.data(), cols.data(), jac_off.data(),
-                                                      J.data(), r.data(), host_s.data(), host_diag.data(), nullptr,
-                                                      n_device_priors_ > 0 ? prior_of.data() : nullptr, prior_cols.data()) != ICG_OK ||
-                    icg_reproj_landmark_min_windows(ctx, min_dev.data()) != ICG_OK)
-                    return fail(icg_last_error(ctx));
-            } else if (icg_reproj_host_parts_build(ctx, P, Pw.data(), rebuild.data(), blk_off.data(), nr.data(), nf.data(), cols.data(), jac_off.data(),
-                                                   J.data(), r.data(), host_s.data(), host_diag.data(), nullptr) != ICG_OK ||
-                       icg_reproj_landmark_diag_windows(ctx, hll.data()) != ICG_OK)
-                return fail(icg_last_error(ctx));
-        } else {
-            S.assign(NW * (size_t) P * P, 0.0);
-            if (icg_reproj_schur_windows(ctx, P, col_pose.data(), col_ext.data(), col_td.data(), nullptr, reassemble.data(), damp.data(), 0.0, 0.0, S.data(),
-                                         s.data(), diag_cc.data(), cost.data()) != ICG_OK ||
-                icg_reproj_landmark_diag_windows(ctx, hll.data()) != ICG_OK)
-                return fail(icg_last_error(ctx));
+        if (st[w].planned) R.P = std::max(R.P, st[w].plan.P);
+    const int P = R.P;
+    if (P == 0) return true;
+    std::vector<int32_t> col_pose((size_t) factors_.numPoses(), -1), col_ext(NW, -1), col_td(NW, -1);
+    for (size_t w = 0; w < NW; w++) {
+        if (!st[w].planned) continue; // (its columns stay constant: the window adds nothing to any reduced system that is read)
+        const WindowFactorSet::Window &W = factors_.window(w);
+        auto col                         = [&](const double *p) {
+            auto it = st[w].plan.camera_column_of.find(p);
+            return it == st[w].plan.camera_column_of.end() ? -1 : it->second;
+        };
+        for (size_t k = 0; k < W.poses.size(); k++) col_pose[(size_t) W.pose_begin + k] = col(W.poses[k]);
+        col_ext[w] = col(W.ext), col_td[w] = col(W.td);
+    }
+    std::vector<uint8_t> reassemble(NW, 1);
+    std::vector<double> damp(NW, 0.0), diag_cc(NW * (size_t) P), cost(NW, 0.0);
+    R.s.assign(NW * (size_t) P, 0.0), R.hll.assign((size_t) std::max(factors_.numLandmarks(), 1), 0.0);
+    if (!device_reduced_system_) {
+        R.S.assign(NW * (size_t) P * P, 0.0);
+        if (icg_reproj_schur_windows(ctx, P, col_pose.data(), col_ext.data(), col_td.data(), nullptr, reassemble.data(), damp.data(), 0.0, 0.0, R.S.data(),
+                                     R.s.data(), diag_cc.data(), cost.data()) != ICG_OK ||
+            icg_reproj_landmark_diag_windows(ctx, R.hll.data()) != ICG_OK)
+            return fail(icg_last_error(ctx));
+        return true;
+    }
+    // S stays on the device; the host-factor part of every planned window is built beside it from the window's blocks
+    Run::HostPartCall C = R.hostPartCall(device_prior_);
+    std::vector<double> host_diag(NW * (size_t) P, 0.0);
+    R.host_s.assign(NW * (size_t) P, 0.0);
+    if (icg_reproj_schur_windows_resident(ctx, P, col_pose.data(), col_ext.data(), col_td.data(), nullptr, reassemble.data(), damp.data(), 0.0, 0.0,
+                                          R.s.data(), diag_cc.data(), cost.data()) != ICG_OK)
+        return fail(icg_last_error(ctx));
+    if (device_prior_) {
+        // the taken priors are evaluated where they lie (e = e0 + J0 dx at the packed point, between the Schur call and the host parts), their
+        // blocks take residual and Jacobian columns from there, and the first guard's minimum comes back as one double per window
+        std::vector<double> sq((size_t) std::max(n_device_priors_, 1));
+        std::string what;
+        if (n_device_priors_ > 0 && !prior_set_.evaluateResident(sq.data(), &what)) return fail(what);
+        R.min_dev.assign(NW, 0.0);
+        if (icg_reproj_host_parts_build_prior(ctx, P, C.Pw.data(), C.rebuild.data(), C.blk_off.data(), C.nr.data(), C.nf.data(), C.cols.data(), C.jac_off.data(),
+                                              C.J.data(), C.r.data(), R.host_s.data(), host_diag.data(), nullptr,
+                                              n_device_priors_ > 0 ? C.prior_of.data() : nullptr, C.prior_cols.data()) != ICG_OK ||
+            icg_reproj_landmark_min_windows(ctx, R.min_dev.data()) != ICG_OK)
+            return fail(icg_last_error(ctx));
+    } else if (icg_reproj_host_parts_build(ctx, P, C.Pw.data(), C.rebuild.data(), C.blk_off.data(), C.nr.data(), C.nf.data(), C.cols.data(), C.jac_off.data(),
+                                           C.J.data(), C.r.data(), R.host_s.data(), host_diag.data(), nullptr) != ICG_OK ||
+               icg_reproj_landmark_diag_windows(ctx, R.hll.data()) != ICG_OK)
+        return fail(icg_last_error(ctx));
+    return true;
+}
+
+// the landmark-eliminated device part joins the window's compact system; the smallest landmark diagonal for the first guard
+void MarginalizationBatch::addEliminated(Run &R, size_t w) {
+    const WindowFactorSet::Window &W          = factors_.window(w);
+    MarginalizationInfo::StructuredPlan &plan = R.st[w].plan;
+    const int Pw = plan.P, P = R.P;
+    if (!device_reduced_system_) { // (resident: the sum is formed on the device, icg_marg_linearize_resident)
+        const double *Sw = &R.S[w * (size_t) P * P], *sw = &R.s[w * (size_t) P];
+        for (int i = 0; i < Pw; i++) {
+            for (int j = 0; j < Pw; j++) plan.H[(size_t) i * Pw + j] += Sw[(size_t) i * P + j];
+            plan.b[(size_t) i] += sw[i];
         }
     }
-    auto t3 = now();
+    if (device_prior_) { // (reduced on the device, icg_reproj_landmark_min_windows: the value of the loop below)
+        R.min_hll[w] = R.min_dev[w];
+    } else {
+        double mn = W.landmarks.empty() ? 0.0 : R.hll[(size_t) W.lm_begin];
+        for (size_t l = 0; l < W.landmarks.size(); l++) mn = std::min(mn, R.hll[(size_t) W.lm_begin + l]);
+        R.min_hll[w] = mn;
+    }
+    R.added[w] = 1;
+}
 
-    // ---- 4: guard + M3 on the camera block (or the dense M2 + M3), linearization -------------------------------------------------------------
-    std::vector<char> structured(NW, 0), good(NW, 0), added(NW, 0);
-    std::vector<double> min_hll(NW, 0.0);
-    // the landmark-eliminated device part joins the window's compact system; the smallest landmark diagonal for the first guard
-    auto addEliminated = [&](size_t w) {
-        const WindowFactorSet::Window &W          = factors_.window(w);
-        MarginalizationInfo::StructuredPlan &plan = st[w].plan;
-        const int Pw                              = plan.P;
-        if (!resident) { // (resident: the sum is formed on the device, icg_marg_linearize_resident)
-            const double *Sw = &S[w * (size_t) P * P], *sw = &s[w * (size_t) P];
-            for (int i = 0; i < Pw; i++) {
-                for (int j = 0; j < Pw; j++) plan.H[(size_t) i * Pw + j] += Sw[(size_t) i * P + j];
-                plan.b[(size_t) i] += sw[i];
-            }
-        }
-        if (dev_prior) { // (reduced on the device, icg_reproj_landmark_min_windows: the value of the loop below)
-            min_hll[w] = min_dev[w];
-        } else {
-            double mn = W.landmarks.empty() ? 0.0 : hll[(size_t) W.lm_begin];
-            for (size_t l = 0; l < W.landmarks.size(); l++) mn = std::min(mn, hll[(size_t) W.lm_begin + l]);
-            min_hll[w] = mn;
-        }
-        added[w]   = 1;
-    };
-    DeviceM3 dev{std::vector<char>(NW, 0), {}, {}, {}, {}, std::vector<size_t>(NW, 0), std::vector<size_t>(NW, 0), std::vector<int>(NW, -1), 0};
+// ---- 4: guard + M3 on the camera block (or the dense M2 + M3), linearization --------------------------------------------------------------
+bool MarginalizationBatch::guardAndLinearize(Run &R) {
+    const size_t NW        = R.NW;
+    std::vector<State> &st = R.st;
+    const DeviceM3 &dev    = R.dev;
     if (device_linearization_) {
         factors_.forEachWindow(NW, [&](size_t w) {
-            if (st[w].alive && st[w].planned) addEliminated(w);
+            if (st[w].alive && st[w].planned) addEliminated(R, w);
         });
         std::string what;
-        const ReducedRhs rhs{P, s, host_s};
-        if (!linearizeOnDevice(st, added, min_hll, dev, &what, resident ? &rhs : nullptr)) return fail(what);
+        if (!linearizeOnDevice(R, &what)) return fail(what);
         kept_id_ = dev.keep_id;
     }
     std::atomic<int> n_deferred{0};
     factors_.forEachWindow(NW, [&](size_t w) {
         if (!st[w].alive) return;
-        Slice &W               = *windows_[w];
-        MarginalizationInfo &I = *W.info;
+        MarginalizationInfo &I = *windows_[w]->info;
         if (dev.on_device[w]) {
             const size_t r = (size_t) st[w].plan.r, at = dev.r_off[w], at2 = dev.rr_off[w];
             I.Hp_.assign(dev.Hp.begin() + (long) at2, dev.Hp.begin() + (long) (at2 + r * r));
@@ -477,51 +458,76 @@ bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
             I.linearized_jacobians_.assign(dev.J0.begin() + (long) at2, dev.J0.begin() + (long) (at2 + r * r));
             I.linearized_residuals_.assign(dev.e0.begin() + (long) at, dev.e0.begin() + (long) (at + r));
             I.setKeptLinearization(dev.keep_id, dev.keep_id ? dev.slot[w] : -1); // (what the device call kept is this window's prior)
-            structured[w] = good[w] = 1;
+            R.structured[w] = R.good[w] = 1;
             return;
         }
         bool done = false;
-        if (st[w].planned && !resident) { // (resident: there is no H on the host to finish from — the window takes the dense path)
-            if (!added[w]) addEliminated(w);
-            done          = I.finishStructured(st[w].plan, min_hll[w]);
-            structured[w] = done ? 1 : 0;
+        if (st[w].planned && !device_reduced_system_) { // (resident: there is no H on the host to finish from — the window takes the dense path)
+            if (!R.added[w]) addEliminated(R, w);
+            done            = I.finishStructured(st[w].plan, R.min_hll[w]);
+            R.structured[w] = done ? 1 : 0;
         }
         if (!done) {
             // (setDevicePrior: the window left the structured device path, so its prior is evaluated on the pool after all — only here)
-            if (taken[w]) {
-                n_deferred++;
-                if (!I.evaluateDeferred()) {
-                    I.isvalid_ = false;
-                    I.releaseMemory();
-                    return;
-                }
-            }
-            if (!I.constructEquation()) { // (:88-92 with the window's own dense assembly on the device)
-                I.isvalid_ = false;
-                I.releaseMemory();
-                return;
-            }
+            if (R.taken[w] && (n_deferred++, !I.evaluateDeferred())) return invalidate(I);
+            if (!I.constructEquation()) return invalidate(I); // (:88-92 with the window's own dense assembly on the device)
             I.schurElimination();
         }
         I.linearization();
-        good[w] = 1;
+        R.good[w] = 1;
     });
     // (:99) the factor records of the windows that went through are retired: kept by this batch until clear() / destruction (factors.h
     // MarginalizationInfo::releaseMemory: freeing ~3 300 heap blocks per window in line is 45 of the 90 ms of 256 C2 windows)
     for (size_t w = 0; w < NW; w++)
-        if (good[w]) windows_[w]->info->releaseMemoryInto(retired_);
-    auto t4 = now();
+        if (R.good[w]) windows_[w]->info->releaseMemoryInto(retired_);
     n_deferred_evaluations_ = n_deferred.load();
+    return true;
+}
+
+bool MarginalizationBatch::marginalize(std::vector<char> *ok) {
+    const size_t NW = windows_.size();
+    if (ok) ok->assign(NW, 0);
+    n_structured_ = n_dense_ = 0;
+    phase_ms_[0] = phase_ms_[1] = phase_ms_[2] = phase_ms_[3] = 0;
+    n_device_priors_ = n_priors_from_kept_ = n_deferred_evaluations_ = 0;
+    error_.clear();
+    window_error_.clear();
+    // what the switches need of each other and of the build, in this order (no window is evaluated yet: fail() only sets the message)
+    if (device_prior_ && !device_reduced_system_)
+        return fail("setDevicePrior(true) needs setDeviceReducedSystem(true): the resident prior is read by the device call that builds the host-factor parts");
+    if (device_prior_ && !devicePriorAvailable()) return fail(std::string(missingDevicePriorEntry()) + " is not in this build");
+    if (device_reduced_system_ && !device_linearization_)
+        return fail("setDeviceReducedSystem(true) needs setDeviceLinearization(true): the resident reduced systems are read by the device call's linearization");
+    if (device_reduced_system_ && !deviceReducedSystemAvailable()) return fail(std::string(missingReducedSystemEntry()) + " is not in this build");
+    if (keep_linearized_ && !device_linearization_)
+        return fail("setKeepLinearized(true) needs setDeviceLinearization(true): what is kept is the device call's linearization");
+    if (keep_linearized_ && !keepLinearizedAvailable()) return fail("icg_marg_linearize_batch_keep is not in this build");
+    if (NW == 0) return true;
+    // (the last marginalize()'s; this one keeps its own below.  setDevicePrior: the resident set is built from it first, in phase 1)
+    if (!device_prior_) releaseKept();
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms  = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto t_layout = now();
+    if (!laid_out_ && !layout()) return false;
+    const double layout_ms = ms(t_layout, now());
+    Run R(NW);
+    R.t0 = now();
+    if (!evaluateWindows(R)) return false;
+    R.t1 = now(), bookkeeping(R), R.t2 = now();
+    if (!assembleAndEliminate(R)) return false;
+    R.t3 = now();
+    if (!guardAndLinearize(R)) return false;
+    R.t4 = now();
     for (size_t w = 0; w < NW; w++) {
         windows_[w]->evaluated = false;
-        if (good[w]) (structured[w] ? n_structured_ : n_dense_)++;
-        if (ok) (*ok)[w] = good[w];
+        if (R.good[w]) (R.structured[w] ? n_structured_ : n_dense_)++;
+        if (ok) (*ok)[w] = R.good[w];
         // (a window that failed on its own — its dense path left a message — is reported through ok[w] and windowError() only: the other
         // windows' priors are good, as they are when every stream marginalizes alone and one of them logs "no valid prior")
-        if (!good[w] && st[w].alive && window_error_.empty() && !windows_[w]->err.empty())
+        if (!R.good[w] && R.st[w].alive && window_error_.empty() && !windows_[w]->err.empty())
             window_error_ = "window " + std::to_string(w) + ": " + windows_[w]->err;
     }
-    phase_ms_[0] = ms(t0, t1), phase_ms_[1] = ms(t1, t2), phase_ms_[2] = ms(t2, t3), phase_ms_[3] = ms(t3, t4);
+    phase_ms_[0] = ms(R.t0, R.t1), phase_ms_[1] = ms(R.t1, R.t2), phase_ms_[2] = ms(R.t2, R.t3), phase_ms_[3] = ms(R.t3, R.t4);
     if (getenv("ICG_MARG_DEBUG"))
         fprintf(stderr, "[marginalization batch] %zu windows (%d structured, %d dense): evaluate %.3f ms, bookkeeping + host factors %.3f ms, assemble + eliminate %.3f ms, M3 + linearize %.3f ms; layout (factor upload + partition) %.3f ms\n",
                 NW, n_structured_, n_dense_, phase_ms_[0], phase_ms_[1], phase_ms_[2], phase_ms_[3], layout_ms);

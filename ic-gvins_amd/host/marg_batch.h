@@ -146,12 +146,15 @@ private:
     };
     bool layout();
     bool denseNormalOfWindow(Slice &W, const std::unordered_map<const double *, int> &column_of, int local_size, double *H0, double *b0);
-    // marginalize(): a window's progress through the phases; what the device M3 returns
+    // marginalize(): a window's progress through the phases; what the device M3 returns; what one call works on (marg_batch.cc)
     struct State;
     struct DeviceM3;
-    struct ReducedRhs; // setDeviceReducedSystem: s and host_s of every window (W x P), what b is formed from
-    bool linearizeOnDevice(const std::vector<State> &st, const std::vector<char> &added, const std::vector<double> &min_hll, DeviceM3 &dev,
-                           std::string *what, const ReducedRhs *resident = nullptr);
+    struct Run;
+    // the four phases above, in their order; false: a device call all windows share failed (fail(): error_ is set, no window stays evaluated)
+    bool evaluateWindows(Run &R), assembleAndEliminate(Run &R), guardAndLinearize(Run &R), fail(const std::string &what);
+    void bookkeeping(Run &R), addEliminated(Run &R, size_t w);
+    static void invalidate(MarginalizationInfo &I);
+    bool linearizeOnDevice(Run &R, std::string *what);
 
     WindowFactorSet factors_; // the partitioned context, every window's reprojection factors, the host threads
     icg_ctx *dense_ctx_{nullptr}; // one-window context of the dense path (created on first use)

@@ -89,10 +89,7 @@ void WindowSolverBatch::addReprojectionFactor(int w, const ReprojectionFactor *f
 // uploads the factors of all windows (window-major) and the partition
 bool WindowSolverBatch::finalize() {
     if (!factors_.upload(&error_)) return false;
-    if (factors_.numFactors() == 0) {
-        error_ = "no reprojection factors";
-        return false;
-    }
+    if (factors_.numFactors() == 0) return refuse("no reprojection factors");
     active_.assign((size_t) factors_.numFactors(), 1);
     finalized_ = true;
     return true;
@@ -124,52 +121,47 @@ bool WindowSolverBatch::layout() {
         if (!device_host_part_) return;
         // the blocks of the window's host part: their shapes and columns follow from the problem, not from an evaluation
         W.host_blocks.clear(), W.host_cols.clear();
-        W.prior_residual = W.prior_in_set = W.prior_block = -1;
-        W.preint_of_residual.assign(device_preint_ ? W.problem.residuals.size() : 0, -1), W.preint_of_block.clear(), W.preint_cols.clear();
-        int n_preint = 0; // (the window's own count: the set index follows once all windows are laid out)
+        W.resident_of_residual.assign(W.problem.residuals.size(), {}), W.resident_of_block.clear();
+        for (std::vector<int32_t> &c : W.resident_cols) c.clear();
+        int count[kFamilies] = {0, 0}; // (the window's own: the set indices follow once all windows are laid out)
         std::vector<int> cols;
         for (size_t id = 0; id < W.problem.residuals.size(); id++) {
             const solver_detail::Residual &R = W.problem.residuals[id];
             if (R.removed) continue;
+            Window::Resident &res = W.resident_of_residual[id];
             // device prior: the window's first prior without a loss (a robustified prior and a second prior stay on the pool)
-            const MargPriorSource *src = device_prior_ && W.prior_residual < 0 && !R.loss ? dynamic_cast<const MargPriorSource *>(R.cost.get()) : nullptr;
-            if (src) {
-                const MargPriorView &v = src->margPriorView();
-                const auto &sizes      = R.cost->parameter_block_sizes();
-                bool fits              = v.r == R.cost->num_residuals() && v.n_blocks == (int) sizes.size();
-                for (int b = 0; fits && b < v.n_blocks; b++) fits = v.size[b] == sizes[(size_t) b];
+            const MargPriorSource *src = device_prior_ && count[kPrior] == 0 && !R.loss ? dynamic_cast<const MargPriorSource *>(R.cost.get()) : nullptr;
+            const MargPriorView *v     = src ? &src->margPriorView() : nullptr;
+            if (v) {
+                const auto &sizes = R.cost->parameter_block_sizes();
+                bool fits         = v->r == R.cost->num_residuals() && v->n_blocks == (int) sizes.size();
+                for (int b = 0; fits && b < v->n_blocks; b++) fits = v->size[b] == sizes[(size_t) b];
                 if (!fits) {
                     errs[w] = "a marginalization prior's view does not describe its residual block";
                     return;
                 }
-                W.prior_residual = (int) id;
+                res = {kPrior, count[kPrior]++};
             }
             // device preintegration: a factor without a loss whose integration result is there and can be whitened
             const PreintegrationFactor *pf = device_preint_ && !R.loss ? dynamic_cast<const PreintegrationFactor *>(R.cost.get()) : nullptr;
-            const bool resident            = pf && pf->preintegration().ready() && R.blocks.size() == 4;
-            if (resident) W.preint_of_residual[id] = n_preint++;
+            if (pf && pf->preintegration().ready() && R.blocks.size() == 4) res = {kPreint, count[kPreint]++};
             solver_detail::hostBlockColumns(W.problem, R, cols);
             if (cols.empty()) continue;
-            if ((int) id == W.prior_residual) W.prior_block = (int) W.host_blocks.size();
-            W.preint_of_block.push_back(resident ? W.preint_of_residual[id] : -1);
-            if (resident) {
-                // the block's columns of the factor's 15 x 32 Jacobian (7 | 9 | 7 | 9): the free local columns of its non-constant blocks
-                static const int first[4] = {0, 7, 16, 23};
-                for (size_t a = 0; a < 4; a++) {
-                    const solver_detail::Block &A = W.problem.blocks[(size_t) W.problem.block_of.at(R.blocks[a])];
-                    if (A.column < 0) continue;
-                    for (int x = 0; x < A.local; x++) W.preint_cols.push_back(first[a] + x);
-                }
+            W.resident_of_block.push_back(res);
+            // a resident block's columns of its source matrix: the free local columns of its non-constant parameter blocks in block order, the
+            // columns gatherHostBlock selects, counted in the prior's J0 or in the factor's 15 x 32 Jacobian (7 | 9 | 7 | 9)
+            static const int preint_first[4] = {0, 7, 16, 23};
+            for (size_t a = 0; res.family != kNone && a < R.blocks.size(); a++) {
+                const solver_detail::Block &A = W.problem.blocks[(size_t) W.problem.block_of.at(R.blocks[a])];
+                if (A.column < 0) continue;
+                for (int x = 0; x < A.local; x++) W.resident_cols[res.family].push_back((res.family == kPrior ? v->index[a] : preint_first[a]) + x);
             }
             W.host_blocks.push_back({(int) id, R.cost->num_residuals(), (int) cols.size(), 0, 0, 0});
             W.host_cols.insert(W.host_cols.end(), cols.begin(), cols.end());
         }
     });
     for (size_t w = 0; w < windows_.size(); w++) {
-        if (!errs[w].empty()) {
-            error_ = errs[w];
-            return false;
-        }
+        if (!errs[w].empty()) return refuse(errs[w]);
         P_ = std::max(P_, windows_[w].P);
     }
     if (device_host_part_) {
@@ -185,39 +177,29 @@ bool WindowSolverBatch::layout() {
             hp_cols_.insert(hp_cols_.end(), W.host_cols.begin(), W.host_cols.end());
             hp_blk_off_.push_back((int32_t) hp_nr_.size());
         }
-        // device prior: the resident set holds the windows that have a prior, in window order; a prior block's columns of J0 are the free
-        // local columns of its non-constant parameter blocks in block order, the columns gatherHostBlock selects
-        prior_views_.clear(), hp_prior_cols_.clear();
-        hp_prior_of_.assign(hp_nr_.size(), -1);
-        for (Window &W : windows_) {
-            if (W.prior_residual < 0) continue;
-            const solver_detail::Residual &R = W.problem.residuals[(size_t) W.prior_residual];
-            const MargPriorView &v           = dynamic_cast<const MargPriorSource *>(R.cost.get())->margPriorView();
-            W.prior_in_set                   = (int) prior_views_.size();
-            prior_views_.push_back(v);
-            if (W.prior_block < 0) continue;
-            hp_prior_of_[(size_t) (W.blk_begin + W.prior_block)] = W.prior_in_set;
-            for (size_t a = 0; a < R.blocks.size(); a++) {
-                const solver_detail::Block &A = W.problem.blocks[(size_t) W.problem.block_of.at(R.blocks[a])];
-                if (A.column < 0) continue;
-                for (int x = 0; x < A.local; x++) hp_prior_cols_.push_back(v.index[a] + x);
-            }
-        }
-        // device preintegration: the resident set holds the factors in window and residual order
+        // the resident sets: the windows' priors in window order, the preintegration factors in window and residual order
+        prior_views_.clear(), prior_where_.clear(), hp_prior_cols_.clear();
         preint_list_.clear(), preint_where_.clear(), hp_preint_cols_.clear();
-        hp_preint_of_.assign(hp_nr_.size(), -1);
+        hp_prior_of_.assign(hp_nr_.size(), -1), hp_preint_of_.assign(hp_nr_.size(), -1);
         for (size_t w = 0; w < windows_.size(); w++) {
-            Window &W      = windows_[w];
-            const int base = (int) preint_list_.size();
-            for (size_t id = 0; id < W.preint_of_residual.size(); id++) {
-                if (W.preint_of_residual[id] < 0) continue;
-                W.preint_of_residual[id] += base;
-                preint_list_.push_back(&static_cast<const PreintegrationFactor *>(W.problem.residuals[id].cost.get())->preintegration());
-                preint_where_.push_back({(int) w, (int) id});
+            Window &W                  = windows_[w];
+            const int base[kFamilies] = {(int) prior_views_.size(), (int) preint_list_.size()};
+            for (size_t id = 0; id < W.resident_of_residual.size(); id++) {
+                Window::Resident &res = W.resident_of_residual[id];
+                if (res.family == kNone) continue;
+                res.index += base[res.family];
+                const ceres::CostFunction *cost = W.problem.residuals[id].cost.get();
+                if (res.family == kPrior)
+                    prior_views_.push_back(dynamic_cast<const MargPriorSource *>(cost)->margPriorView()), prior_where_.push_back({(int) w, (int) id});
+                else
+                    preint_list_.push_back(&static_cast<const PreintegrationFactor *>(cost)->preintegration()), preint_where_.push_back({(int) w, (int) id});
             }
-            for (size_t k = 0; k < W.preint_of_block.size(); k++)
-                if (W.preint_of_block[k] >= 0) hp_preint_of_[(size_t) W.blk_begin + k] = (W.preint_of_block[k] += base);
-            hp_preint_cols_.insert(hp_preint_cols_.end(), W.preint_cols.begin(), W.preint_cols.end());
+            for (size_t k = 0; k < W.resident_of_block.size(); k++) {
+                Window::Resident &res = W.resident_of_block[k];
+                if (res.family != kNone) (res.family == kPrior ? hp_prior_of_ : hp_preint_of_)[(size_t) W.blk_begin + k] = (res.index += base[res.family]);
+            }
+            hp_prior_cols_.insert(hp_prior_cols_.end(), W.resident_cols[kPrior].begin(), W.resident_cols[kPrior].end());
+            hp_preint_cols_.insert(hp_preint_cols_.end(), W.resident_cols[kPreint].begin(), W.resident_cols[kPreint].end());
         }
     }
     return P_ > 0;
@@ -266,21 +248,6 @@ struct WindowSolverBatch::Run {
         std::vector<int64_t> jac_off;
         std::vector<uint8_t> has_shipped;
     };
-    // device prior: e . e of every resident prior at the last evaluated point, the cost of every residual of every window as the pool
-    // recorded it (the prior's comes from sq), and the windows whose prior Jacobian was gathered on the device in this solve
-    struct DevicePrior {
-        bool on = false;
-        std::vector<double> sq;
-        std::vector<std::vector<double>> res_cost;
-        std::vector<uint8_t> gathered;
-        std::string err;
-    };
-    // device preintegration: r . r of every resident factor at the last evaluated point (their costs join DevicePrior::res_cost's sum)
-    struct DevicePreint {
-        bool on = false;
-        std::vector<double> sq;
-        std::string err;
-    };
 
     const Options &o;
     const ReducedPath path;
@@ -294,9 +261,13 @@ struct WindowSolverBatch::Run {
     std::vector<double> host_cost;
     DeviceSolve dev;
     DeviceParts hp;
-    DevicePrior prior;
-    DevicePreint preint;
-    bool deferred() const { return prior.on || preint.on; } // a device value takes a residual's place in the host cost: the pool records per residual
+    // per family of resident residuals: on for this solve (its switch is set and its set has members); r . r of every member at the last evaluated point
+    bool on[kFamilies] = {false, false};
+    std::vector<double> sq[kFamilies];
+    std::vector<std::vector<double>> res_cost; // deferred(): the cost of every residual of every window as the pool recorded it (a resident one's comes from sq)
+    std::vector<uint8_t> gathered;             // the windows whose prior Jacobian was gathered on the device in this solve
+    std::string resident_err;                  // what the evaluation of a family failed with (side thread: error_ takes it after the join)
+    bool deferred() const { return on[kPrior] || on[kPreint]; } // a device value takes a residual's place in the host cost: the pool records per residual
     bool first = true;                                        // no window has its initial cost yet
     bool all_done = false, any_step = false, any_trial = false; // what solve() decides on after a phase
     BatchClock clk;
@@ -315,34 +286,17 @@ bool WindowSolverBatch::fail(const char *what) {
 }
 
 bool WindowSolverBatch::resolvePath(ReducedPath *path) {
-    if (device_reduced_ && !deviceReducedSolveAvailable()) {
-        error_ = "icg_reproj_solve_windows is not in this build";
-        return false;
-    }
-    if (device_host_part_ && !deviceHostPartAvailable()) {
-        error_ = "icg_reproj_host_parts_build is not in this build";
-        return false;
-    }
-    if (device_host_part_ && !device_reduced_) {
-        error_ = "setDeviceHostPart(true) needs setDeviceReducedSolve(true): the host parts are built where the device solve reads them";
-        return false;
-    }
-    if (device_prior_ && !devicePriorAvailable()) {
-        error_ = std::string(MarginalizationPriorSet::residentAvailable() ? "icg_reproj_host_parts_build_prior" : "icg_marg_prior_evaluate_resident") + " is not in this build";
-        return false;
-    }
-    if (device_prior_ && !device_host_part_) {
-        error_ = "setDevicePrior(true) needs setDeviceHostPart(true): the resident prior is read where the host parts are built";
-        return false;
-    }
-    if (device_preint_ && !devicePreintegrationAvailable()) {
-        error_ = std::string(devicePreintegrationMissing()) + " is not in this build";
-        return false;
-    }
-    if (device_preint_ && !device_host_part_) {
-        error_ = "setDevicePreintegration(true) needs setDeviceHostPart(true): the resident factors are read where the host parts are built";
-        return false;
-    }
+    if (device_reduced_ && !deviceReducedSolveAvailable()) return refuse("icg_reproj_solve_windows is not in this build");
+    if (device_host_part_ && !deviceHostPartAvailable()) return refuse("icg_reproj_host_parts_build is not in this build");
+    if (device_host_part_ && !device_reduced_)
+        return refuse("setDeviceHostPart(true) needs setDeviceReducedSolve(true): the host parts are built where the device solve reads them");
+    if (device_prior_ && !devicePriorAvailable())
+        return refuse(std::string(MarginalizationPriorSet::residentAvailable() ? "icg_reproj_host_parts_build_prior" : "icg_marg_prior_evaluate_resident") + " is not in this build");
+    if (device_prior_ && !device_host_part_)
+        return refuse("setDevicePrior(true) needs setDeviceHostPart(true): the resident prior is read where the host parts are built");
+    if (device_preint_ && !devicePreintegrationAvailable()) return refuse(std::string(devicePreintegrationMissing()) + " is not in this build");
+    if (device_preint_ && !device_host_part_)
+        return refuse("setDevicePreintegration(true) needs setDeviceHostPart(true): the resident factors are read where the host parts are built");
     *path = device_host_part_ ? ReducedPath::DeviceSolveDeviceParts : device_reduced_ ? ReducedPath::DeviceSolve : ReducedPath::HostSolve;
     return true;
 }
@@ -372,20 +326,19 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
     }
     if (device_prior_ && !prior_views_.empty()) {
         // the priors become resident once per solve: J0 crosses the link here and not again
-        Run::DevicePrior &D = R.prior;
         if (!prior_set_.set(factors_.ctx(), prior_views_, &error_)) return false;
-        D.on = true;
-        D.sq.assign(prior_views_.size(), 0.0), D.gathered.assign(NW, 0);
+        R.on[kPrior] = true;
+        R.sq[kPrior].assign(prior_views_.size(), 0.0), R.gathered.assign(NW, 0);
     }
     if (device_preint_ && !preint_list_.empty()) {
         // the integration results become resident once per solve
         if (!preint_set_.set(factors_.ctx(), preint_list_, &error_)) return false;
-        R.preint.on = true;
-        R.preint.sq.assign(preint_list_.size(), 0.0);
+        R.on[kPreint] = true;
+        R.sq[kPreint].assign(preint_list_.size(), 0.0);
     }
     if (R.deferred()) {
-        R.prior.res_cost.resize(NW);
-        for (size_t w = 0; w < NW; w++) R.prior.res_cost[w].assign(windows_[w].problem.residuals.size(), 0.0);
+        R.res_cost.resize(NW);
+        for (size_t w = 0; w < NW; w++) R.res_cost[w].assign(windows_[w].problem.residuals.size(), 0.0);
     }
     for (;;) {
         if (!linearize(R) || !reducedSolves(R)) return false;
@@ -437,16 +390,14 @@ bool WindowSolverBatch::linearize(Run &R) {
         // runHalves); the sums that need both are formed after the join.
         R.clk.start();
         int dev_rc = ICG_OK;
-        bool prior_ok = true, preint_ok = true;
-        if (R.prior.on && any_lin) packPriors();
-        if (R.preint.on && any_lin) packPreintegrations();
+        bool resident_ok = true;
+        if (any_lin) packResident(R);
         if (!side_) side_.reset(new SideThread());
         SideCall dev(*side_, [&] {
             if (R.deviceSolve()) {
                 dev_rc = icg_reproj_schur_windows_resident(ctx, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), R.reassemble.data(),
                                                            R.damp.data(), o.min_lm_diagonal, o.max_lm_diagonal, R.s.data(), R.diag.data(), R.cost.data());
-                if (dev_rc == ICG_OK && R.prior.on && any_lin) prior_ok = evaluatePriors(R);
-                if (dev_rc == ICG_OK && prior_ok && R.preint.on && any_lin) preint_ok = evaluatePreintegrations(R, true);
+                if (dev_rc == ICG_OK && any_lin) resident_ok = evaluateResident(R, true);
             } else
                 dev_rc = icg_reproj_schur_windows_view(ctx, P, col_pose_.data(), col_ext_.data(), col_td_.data(), active_.data(), R.reassemble.data(),
                                                        R.damp.data(), o.min_lm_diagonal, o.max_lm_diagonal, &R.S, R.s.data(), R.diag.data(), R.cost.data());
@@ -462,35 +413,12 @@ bool WindowSolverBatch::linearize(Run &R) {
         dev.join();
         R.clk.stop(PH_SCHUR_TAIL); // (what is left of the device call once the host half is through)
         if (dev_rc != ICG_OK) return fail(R.deviceSolve() ? "icg_reproj_schur_windows_resident" : "icg_reproj_schur_windows_view");
-        if (!prior_ok || !preint_ok) {
-            error_ = !prior_ok ? R.prior.err : R.preint.err;
-            return false;
-        }
-        if (host_failed.load()) {
-            error_ = "a host cost function failed to evaluate";
-            return false;
-        }
+        if (!resident_ok) return refuse(R.resident_err);
+        if (host_failed.load()) return refuse("a host cost function failed to evaluate");
         if (R.deviceParts() && any_lin) {
             // the parts of the re-linearized windows, built in their slots on the device; s and diag of those windows come back
             R.clk.start();
-            if (R.preint.on) {
-                // the resident factors' blocks take their residuals and Jacobians where they are (and so do the resident priors', if any)
-                if (icg_reproj_host_parts_build_preint(ctx, P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(),
-                                                       R.hp.jac_off.data(), R.hp.J.data(), R.hp.r.data(), R.hp.s.data(), R.hp.diag.data(), nullptr,
-                                                       R.prior.on ? hp_prior_of_.data() : nullptr, R.prior.on ? hp_prior_cols_.data() : nullptr, hp_preint_of_.data(),
-                                                       hp_preint_cols_.data()) != ICG_OK)
-                    return fail("icg_reproj_host_parts_build_preint");
-                for (size_t w = 0; w < NW && R.prior.on; w++) R.prior.gathered[w] |= R.reassemble[w];
-            } else if (R.prior.on) {
-                // the resident priors' blocks take their residuals, and at a window's first rebuild their Jacobians, where they are
-                if (icg_reproj_host_parts_build_prior(ctx, P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(),
-                                                      R.hp.jac_off.data(), R.hp.J.data(), R.hp.r.data(), R.hp.s.data(), R.hp.diag.data(), nullptr, hp_prior_of_.data(),
-                                                      hp_prior_cols_.data()) != ICG_OK)
-                    return fail("icg_reproj_host_parts_build_prior");
-                for (size_t w = 0; w < NW; w++) R.prior.gathered[w] |= R.reassemble[w];
-            } else if (icg_reproj_host_parts_build(ctx, P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(),
-                                                   R.hp.jac_off.data(), R.hp.J.data(), R.hp.r.data(), R.hp.s.data(), R.hp.diag.data(), nullptr) != ICG_OK)
-                return fail("icg_reproj_host_parts_build");
+            if (!buildHostParts(R)) return false;
             R.clk.stop(PH_HOST_PARTS);
         }
         R.clk.start();
@@ -541,16 +469,10 @@ bool WindowSolverBatch::hostHalfOfWindow(Run &R, size_t w) {
             if (Res.removed) continue;
             const bool has = next < W.host_blocks.size() && W.host_blocks[next].residual == (int) id;
             double *cost   = &R.host_cost[w];
-            if (R.deferred()) cost = &R.prior.res_cost[w][id], *cost = 0.0; // per residual: the window's sum waits for the device values
-            if (R.prior.on && (int) id == W.prior_residual) {
-                // evaluated where it is resident: the block's slots in r are placed only, its Jacobian is gathered from J0 on the device at
-                // the window's first rebuild of the solve and kept afterwards
-                if (has) H.jac_off[(size_t) W.blk_begin + next] = R.prior.gathered[w] ? -1 : ICG_HP_JAC_FROM_PRIOR, next++;
-                continue;
-            }
-            if (R.preint.on && W.preint_of_residual[id] >= 0) {
-                // a resident preintegration factor: placed only; its Jacobian changes with the point and is gathered at every rebuild
-                if (has) H.jac_off[(size_t) W.blk_begin + next] = ICG_HP_JAC_FROM_PREINT, next++;
+            if (R.deferred()) cost = &R.res_cost[w][id], *cost = 0.0; // per residual: the window's sum waits for the device values
+            if (const int family = W.resident_of_residual[id].family; family != kNone) {
+                // evaluated where it is resident: placed only.  A prior's Jacobian is gathered from J0 at the window's first rebuild of the solve and kept, a factor's at every rebuild
+                if (has) H.jac_off[(size_t) W.blk_begin + next] = family == kPreint ? ICG_HP_JAC_FROM_PREINT : R.gathered[w] ? -1 : ICG_HP_JAC_FROM_PRIOR, next++;
                 continue;
             }
             double *Jd = has ? &H.J[W.host_blocks[next].J_off] : nullptr;
@@ -575,35 +497,48 @@ bool WindowSolverBatch::hostHalfOfWindow(Run &R, size_t w) {
     return false;
 }
 
-// device prior: every window's prior blocks at their places in the set's evaluation point (on the driving thread, before the phase's device call)
-void WindowSolverBatch::packPriors() {
-    for (const Window &W : windows_)
-        if (W.prior_residual >= 0) prior_set_.pack((size_t) W.prior_in_set, W.problem.residuals[(size_t) W.prior_residual].blocks.data());
+// resident residuals: every member's parameter blocks at their places in its set's evaluation point (a preintegration factor's with its correction
+// quaternion), on the driving thread before the phase's device call
+void WindowSolverBatch::packResident(const Run &R) {
+    auto blocks = [&](const std::pair<int, int> &at) { return windows_[(size_t) at.first].problem.residuals[(size_t) at.second].blocks.data(); };
+    for (size_t k = 0; R.on[kPrior] && k < prior_where_.size(); k++) prior_set_.pack(k, blocks(prior_where_[k]));
+    for (size_t k = 0; R.on[kPreint] && k < preint_where_.size(); k++) preint_set_.pack(k, blocks(preint_where_[k]));
 }
 
-bool WindowSolverBatch::evaluatePriors(Run &R) { return prior_set_.evaluateResident(R.prior.sq.data(), &R.prior.err); }
-
-// device preintegration: every resident factor's evaluation point and correction quaternion (on the driving thread, before the phase's device call)
-void WindowSolverBatch::packPreintegrations() {
-    for (size_t f = 0; f < preint_where_.size(); f++)
-        preint_set_.pack(f, windows_[(size_t) preint_where_[f].first].problem.residuals[(size_t) preint_where_[f].second].blocks.data());
+// the resident evaluation of a phase (side thread), one squared norm per member: the priors, then, unless that failed, the preintegration factors,
+// with Jacobians at a linearization and the residual only at a trial point (the cost is all it needs)
+bool WindowSolverBatch::evaluateResident(Run &R, bool want_jac) {
+    if (R.on[kPrior] && !prior_set_.evaluateResident(R.sq[kPrior].data(), &R.resident_err)) return false;
+    return !R.on[kPreint] || preint_set_.evaluateResident(want_jac, R.sq[kPreint].data(), &R.resident_err);
 }
 
-bool WindowSolverBatch::evaluatePreintegrations(Run &R, bool want_jac) { return preint_set_.evaluateResident(want_jac, R.preint.sq.data(), &R.preint.err); }
+// The host-part call of a linearization, by the narrowest entry that serves the families that are on (a C ABI without the wider ones keeps working with the
+// narrower switches).  The resident blocks take their residuals where they are, and their Jacobians at every rebuild (factors) or a window's first (priors).
+bool WindowSolverBatch::buildHostParts(Run &R) {
+    Run::DeviceParts &H     = R.hp;
+    const bool prior = R.on[kPrior], preint = R.on[kPreint];
+    const int32_t *prior_of = prior ? hp_prior_of_.data() : nullptr, *prior_cols = prior ? hp_prior_cols_.data() : nullptr;
+    auto call               = [&](auto entry, auto... resident) { // (every entry takes the narrowest one's arguments first)
+        return entry(factors_.ctx(), R.P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(), H.jac_off.data(),
+                     H.J.data(), H.r.data(), H.s.data(), H.diag.data(), nullptr, resident...);
+    };
+    const int rc = preint  ? call(icg_reproj_host_parts_build_preint, prior_of, prior_cols, hp_preint_of_.data(), hp_preint_cols_.data())
+                   : prior ? call(icg_reproj_host_parts_build_prior, prior_of, prior_cols)
+                           : call(icg_reproj_host_parts_build);
+    if (rc != ICG_OK) return fail(preint ? "icg_reproj_host_parts_build_preint" : prior ? "icg_reproj_host_parts_build_prior" : "icg_reproj_host_parts_build");
+    for (size_t w = 0; w < R.NW && prior; w++) R.gathered[w] |= R.reassemble[w];
+    return true;
+}
 
-// device prior: the window's host cost from the costs the pool recorded per residual and the device's squared norm in the prior's place,
+// the window's host cost from the costs the pool recorded per residual and half the device's squared norm in a resident residual's place,
 // added up from zero in residual order: hostFactors' sum
 void WindowSolverBatch::sumHostCosts(Run &R, size_t w) {
     const Window &W = windows_[w];
     double cost     = 0.0;
     for (size_t id = 0; id < W.problem.residuals.size(); id++) {
         if (W.problem.residuals[id].removed) continue;
-        if (R.prior.on && (int) id == W.prior_residual)
-            cost += 0.5 * R.prior.sq[(size_t) W.prior_in_set];
-        else if (R.preint.on && W.preint_of_residual[id] >= 0)
-            cost += 0.5 * R.preint.sq[(size_t) W.preint_of_residual[id]];
-        else
-            cost += R.prior.res_cost[w][id];
+        const Window::Resident &res = W.resident_of_residual[id];
+        cost += res.family != kNone ? 0.5 * R.sq[res.family][(size_t) res.index] : R.res_cost[w][id];
     }
     R.host_cost[w] = cost;
 }
@@ -750,9 +685,8 @@ bool WindowSolverBatch::trialCosts(Run &R) {
     R.clk.start();
     factors_.gather(R.poses, R.ext, R.inv, R.td);
     const char *dev_fail = nullptr;
-    bool prior_ok = true, preint_ok = true;
-    if (R.prior.on) packPriors();
-    if (R.preint.on) packPreintegrations();
+    bool resident_ok = true;
+    packResident(R);
     if (!side_) side_.reset(new SideThread());
     SideCall trial(*side_, [&] {
         if (icg_reproj_eval_windows(ctx, factors_.numPoses(), R.poses.data(), R.ext.data(), factors_.numLandmarks(), R.inv.data(), R.td.data(), 0, huber_) !=
@@ -760,10 +694,8 @@ bool WindowSolverBatch::trialCosts(Run &R) {
             dev_fail = "icg_reproj_eval_windows";
         else if (icg_reproj_cost_windows(ctx, active_.data(), R.cost.data()) != ICG_OK)
             dev_fail = "icg_reproj_cost_windows";
-        else {
-            if (R.prior.on) prior_ok = evaluatePriors(R);
-            if (prior_ok && R.preint.on) preint_ok = evaluatePreintegrations(R, false); // (residual only: the cost is all a trial point needs)
-        }
+        else
+            resident_ok = evaluateResident(R, false);
     });
     std::atomic<int> trial_failed{0};
     R.host_cost.assign(NW, 0.0);
@@ -773,12 +705,12 @@ bool WindowSolverBatch::trialCosts(Run &R) {
             if (!solver_detail::hostFactors(windows_[w].problem, R.P, nullptr, nullptr, nullptr, &R.host_cost[w])) trial_failed++;
             return;
         }
-        // the cost-only pass of hostFactors per residual, the resident prior left to the device
+        // the cost-only pass of hostFactors per residual, the resident ones left to the device
         const Window &W = windows_[w];
         for (size_t id = 0; id < W.problem.residuals.size(); id++) {
             const solver_detail::Residual &Res = W.problem.residuals[id];
-            if (Res.removed || (R.prior.on && (int) id == W.prior_residual) || (R.preint.on && W.preint_of_residual[id] >= 0)) continue;
-            if (!solver_detail::residualCost(Res, true, &R.prior.res_cost[w][id])) {
+            if (Res.removed || W.resident_of_residual[id].family != kNone) continue;
+            if (!solver_detail::residualCost(Res, true, &R.res_cost[w][id])) {
                 trial_failed++;
                 return;
             }
@@ -786,10 +718,7 @@ bool WindowSolverBatch::trialCosts(Run &R) {
     });
     trial.join();
     if (dev_fail) return fail(dev_fail);
-    if (!prior_ok || !preint_ok) {
-        error_ = !prior_ok ? R.prior.err : R.preint.err;
-        return false;
-    }
+    if (!resident_ok) return refuse(R.resident_err);
     R.clk.stop(PH_TRIAL_EVAL);
     R.clk.start();
     factors_.forEachWindow(NW, [&](size_t w) {
@@ -803,10 +732,7 @@ bool WindowSolverBatch::trialCosts(Run &R) {
         else
             T.redamp = true;
     });
-    if (trial_failed.load()) {
-        error_ = "a host cost function failed to evaluate";
-        return false;
-    }
+    if (trial_failed.load()) return refuse("a host cost function failed to evaluate");
     R.clk.stop(PH_TRIAL_HOST);
     return true;
 }

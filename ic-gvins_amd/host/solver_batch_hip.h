@@ -103,6 +103,8 @@ public:
     const std::string &error() const { return error_; }
 
 private:
+    // the families of residuals that may be resident on the device for a solve (setDevicePrior, setDevicePreintegration), in the order they are evaluated
+    enum Family { kNone = -1, kPrior = 0, kPreint = 1, kFamilies = 2 };
     // a window beside its record in factors_: the host-evaluated part of its problem and its state across the steps of a solve
     struct Window {
         solver_detail::Problem problem{"WindowSolverBatch"};
@@ -117,13 +119,12 @@ private:
         std::vector<HostBlock> host_blocks;
         std::vector<int32_t> host_cols; // their columns, block after block
         int blk_begin{0};
-        // device prior (layout()): the residual that is the window's resident prior (-1: none), its index in the resident set, its position
-        // among host_blocks (-1: every block of the prior is constant: it has a cost but no host block)
-        int prior_residual{-1}, prior_in_set{-1}, prior_block{-1};
-        // device preintegration (layout()): per residual its index in the resident set (-1: not in it; empty while the switch is off), and
-        // per block of host_blocks the same index (-1: an ordinary block)
-        std::vector<int> preint_of_residual, preint_of_block;
-        std::vector<int32_t> preint_cols; // the resident blocks' columns of the 15 x 32 Jacobian, block after block
+        // resident residuals (layout()): per residual and per block of host_blocks the family it is resident in on the device (kNone: evaluated on
+        // the pool; a resident residual whose blocks are all constant has a cost but no host block) and its index in that family's set; per family
+        // the columns of the members' source matrices (a prior's J0, a factor's 15 x 32 Jacobian) its blocks take, block after block
+        struct Resident { int family{kNone}, index{-1}; };
+        std::vector<Resident> resident_of_residual, resident_of_block;
+        std::vector<int32_t> resident_cols[kFamilies];
     };
     // how solve() forms and solves the reduced systems: resolved from the two setters at its top
     enum class ReducedPath { HostSolve, DeviceSolve, DeviceSolveDeviceParts };
@@ -138,17 +139,17 @@ private:
     bool trialCosts(Run &R);
     // where the paths differ: the host half of a window's linearization, and the reduced solves
     bool hostHalfOfWindow(Run &R, size_t w);
-    // device prior: the evaluation point of every resident prior (driving thread), the resident evaluation of a phase (side thread), and
-    // a window's host cost once the device value is there
-    void packPriors();
-    bool evaluatePriors(Run &R);
-    // device preintegration: the same two steps for the resident factors
-    void packPreintegrations();
-    bool evaluatePreintegrations(Run &R, bool want_jac);
+    // resident residuals: the evaluation point of every member of the families that are on (driving thread), their evaluation in a phase (side
+    // thread: priors, then preintegration factors; Jacobians at a linearization only), the host-part call of the narrowest entry that serves
+    // them, and a window's host cost once the device values are there
+    void packResident(const Run &R);
+    bool evaluateResident(Run &R, bool want_jac);
+    bool buildHostParts(Run &R);
     void sumHostCosts(Run &R, size_t w);
     void solveWindowOnHost(Run &R, size_t w);
     bool solveWindowsOnDevice(Run &R);
-    bool fail(const char *what);
+    bool fail(const char *what); // (error_ = what: the context's last error)
+    bool refuse(const std::string &what) { return error_ = what, false; }
 
     WindowFactorSet factors_; // the context, every window's reprojection factors, the host threads
     double huber_;
@@ -158,20 +159,17 @@ private:
     std::vector<int32_t> col_pose_, col_ext_, col_td_;
     int P_{0};
     bool finalized_{false};
-    bool device_reduced_{false}, device_host_part_{false}, device_prior_{false};
+    bool device_reduced_{false}, device_host_part_{false}, device_prior_{false}, device_preint_{false};
     // device host part (layout()): the block list of all windows as icg_reproj_host_parts_build takes it, and the sizes of a call's J and r
     std::vector<int32_t> hp_blk_off_, hp_nr_, hp_nf_, hp_cols_;
     size_t hp_J_total_{0}, hp_r_total_{0};
-    // device prior (layout()): per block of that list the prior it is (-1: none) and the prior blocks' columns of J0; the resident set
-    std::vector<int32_t> hp_prior_of_, hp_prior_cols_;
+    // resident residuals (layout()): per block of that list the prior / the factor of the resident sets it is (-1: none) and the resident blocks' columns
+    // of J0 / of the 15 x 32 Jacobian; the sets, their members (priors in window order, factors in window and residual order) and where each is
+    std::vector<int32_t> hp_prior_of_, hp_prior_cols_, hp_preint_of_, hp_preint_cols_;
     std::vector<MargPriorView> prior_views_;
-    MarginalizationPriorSet prior_set_;
-    // device preintegration (layout()): per block of the list the set factor it is (-1: none), the resident blocks' columns, the factors of
-    // the set in window and residual order with their parameter blocks, and the set
-    bool device_preint_{false};
-    std::vector<int32_t> hp_preint_of_, hp_preint_cols_;
     std::vector<const Preintegration *> preint_list_;
-    std::vector<std::pair<int, int>> preint_where_; // (window, residual) of every factor of the set
+    std::vector<std::pair<int, int>> prior_where_, preint_where_; // (window, residual)
+    MarginalizationPriorSet prior_set_;
     PreintegrationSet preint_set_;
     std::string error_;
 };
