@@ -108,6 +108,55 @@ int icgh_backend_marginalize(int n, const double *obs_soa, const int32_t *idx_i,
     });
 }
 
+// The first guard of MarginalizationInfo::finishStructured on a real window: the window of icgh_backend_marginalize marginalized on a device
+// factor set that is a ReprojectionBatch in everything but the smallest landmark diagonal it reports, which is the caller's `min_hll`.
+// flags[0] = lastWasStructured(); flags[1] = the sizes of Hp() + bp() when the dense assembly started (-1: the dense path did not run) —
+// they are empty before marginalization(), so 0 says that the refusal left them as they were.  Hp (r x r), bp (r), sizes[0..1] = m, r.
+int icgh_backend_marginalize_min_hll(int n, const double *obs_soa, const int32_t *idx_i, const int32_t *idx_j, const int32_t *idx_lm, int n_poses,
+                                     const double *poses, const double *ext, int n_lm, const double *invdepth, double td, double huber_delta,
+                                     double prior_weight, double min_hll, int32_t *flags, int32_t *sizes, double *Hp, double *bp, char *err, int errlen) {
+    struct ReportedMinimum : DeviceFactorSet {
+        ReprojectionBatch batch{0};
+        const MarginalizationInfo *info{nullptr};
+        double min_hll{0};
+        int at_dense{-1};
+        bool owns(const ReprojectionFactor *f) const override { return batch.owns(f); }
+        int size() const override { return batch.size(); }
+        const vector<double *> &landmarkBlocks() const override { return batch.landmarkBlocks(); }
+        bool evaluateCorrected(double delta) override { return batch.evaluateCorrected(delta); }
+        bool accumulateNormal(const std::unordered_map<const double *, int> &column_of, int local_size, double *H0, double *b0) override {
+            at_dense = (int) (info->Hp().size() + info->bp().size());
+            return batch.accumulateNormal(column_of, local_size, H0, b0);
+        }
+        bool accumulateLandmarkEliminated(const std::unordered_map<const double *, int> &columns, int P, double *H, double *b, double *mn) override {
+            const bool ok = batch.accumulateLandmarkEliminated(columns, P, H, b, nullptr);
+            *mn           = min_hll;
+            return ok;
+        }
+        const std::string &error() const override { return batch.error(); }
+    };
+    return guarded(err, errlen, [&] {
+        const MargArgs args{n, obs_soa, idx_i, idx_j, idx_lm, n_poses, poses, ext, n_lm, invdepth, td, huber_delta, prior_weight};
+        auto wins = marg_windows(args, 1, -1, 0.0);
+        MargWindow &W = *wins[0];
+        ReportedMinimum set;
+        set.info = W.info.get(), set.min_hll = min_hll;
+        W.info->setDeviceFactors(&set);
+        // (a factor's batch() is the ReprojectionBatch inside the set, so owns() holds for exactly the factors added here)
+        marg_reprojections(args, W, batch_add(set.batch));
+        set.batch.finalize();
+        if (!W.info->marginalization()) {
+            set_err(err, errlen, ("marginalization failed: " + set.batch.error()).c_str());
+            return -2;
+        }
+        flags[0] = MarginalizationInfo::lastWasStructured() ? 1 : 0, flags[1] = set.at_dense;
+        sizes[0] = W.info->marginalizedSize(), sizes[1] = W.info->remainedSize();
+        const size_t r = (size_t) W.info->remainedSize();
+        memcpy(Hp, W.info->Hp().data(), sizeof(double) * r * r), memcpy(bp, W.info->bp().data(), sizeof(double) * r);
+        return 0;
+    });
+}
+
 // The marginalizations of n_windows streams (M1-M4 of each: the window of icgh_backend_marginalize, window w > 0 with its poses and inverse
 // depths moved by a deterministic jitter of relative size `jitter`), mode 0: one MarginalizationBatch (marg_batch.h: the windows share
 // their device launches), mode 1: one MarginalizationInfo::marginalization() after the other on a ReprojectionBatch (what a stream on its

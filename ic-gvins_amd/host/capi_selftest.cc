@@ -108,6 +108,19 @@ int icgh_symmetric_eigen(int n, const double *A, double *evals, double *evecs) {
     return 0;
 }
 
+// schurReduceGuarded (marg_m3.h) on a caller's system: H is P x P row-major, the m leading columns are eliminated.  Hp (r x r, r = P - m)
+// and bp (r) go IN as well: they are what the function finds in its output arrays and come back as it left them, so a caller sees that a
+// refusal touched nothing.  Returns 1 = reduced, 0 = refused (an m-block eigenvalue at or below `guard`), -1 = invalid arguments.
+int icgh_schur_reduce_guarded(int P, int m, const double *H, const double *b, double guard, double *Hp, double *bp) {
+    if (P < 1 || m < 0 || m >= P || !H || !b || !Hp || !bp) return -1;
+    const size_t r = (size_t) (P - m);
+    std::vector<double> hp(Hp, Hp + r * r), bpv(bp, bp + r);
+    const bool ok = schurReduceGuarded(P, m, H, b, guard, hp, bpv);
+    if (hp.size() != r * r || bpv.size() != r) return -1;
+    memcpy(Hp, hp.data(), sizeof(double) * r * r), memcpy(bp, bpv.data(), sizeof(double) * r);
+    return ok ? 1 : 0;
+}
+
 // BlockPool / PoolAllocator (object_pool.h) under cross-thread traffic, for tests: `threads` workers each allocate `iters` blocks of two
 // size classes, stamp them, hand every second one to the next worker through a mailbox (freed on a thread other than the allocating one:
 // the spill / refill path of the per-thread lists) and free the rest themselves; every block is checked for its stamp before it is freed.

@@ -228,7 +228,7 @@ bool MarginalizationBatch::linearizeOnDevice(Run &R, std::string *what) {
     DeviceM3 &dev                = R.dev;
     const bool resident          = device_reduced_system_;
     const size_t NW    = st.size();
-    const double GUARD = 100.0 * 1e-8; // (finishStructured: 100 x the reference's floor)
+    const double GUARD = MarginalizationInfo::STRUCTURED_GUARD, EPS = MarginalizationInfo::EPS; // (finishStructured's guard; the floor)
     std::vector<int32_t> dP, dm;
     std::vector<size_t> h_off, who;
     size_t th = 0, tb = 0, tr = 0, trr = 0;
@@ -255,7 +255,7 @@ bool MarginalizationBatch::linearizeOnDevice(Run &R, std::string *what) {
             for (int i = 0; i < dP[k]; i++) db[b_off[k] + (size_t) i] = R.host_s[at + (size_t) i] + R.s[at + (size_t) i]; // (plan.b += s)
         }
         uint64_t id = 0;
-        if (icg_marg_linearize_resident(factors_.ctx(), R.P, (int) who.size(), win.data(), dP.data(), dm.data(), db.data(), 1e-8, dev.Hp.data(),
+        if (icg_marg_linearize_resident(factors_.ctx(), R.P, (int) who.size(), win.data(), dP.data(), dm.data(), db.data(), EPS, dev.Hp.data(),
                                         dev.bp.data(), dev.J0.data(), dev.e0.data(), nullptr, dev_min.data(), dev_status.data(), nullptr,
                                         keep_linearized_ ? &id : nullptr) != ICG_OK) {
             *what = icg_last_error(factors_.ctx());
@@ -270,10 +270,10 @@ bool MarginalizationBatch::linearizeOnDevice(Run &R, std::string *what) {
         });
         MarginalizationLinearizer lin(true, factors_.ctx());
         if (keep_linearized_) {
-            dev.keep_id = lin.linearizeKeep((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev.Hp.data(), dev.bp.data(), dev.J0.data(),
+            dev.keep_id = lin.linearizeKeep((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), EPS, dev.Hp.data(), dev.bp.data(), dev.J0.data(),
                                             dev.e0.data(), nullptr, dev_min.data(), dev_status.data(), what);
             if (dev.keep_id == 0) return false;
-        } else if (!lin.linearize((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), 1e-8, dev.Hp.data(), dev.bp.data(), dev.J0.data(),
+        } else if (!lin.linearize((int) who.size(), dP.data(), dm.data(), dH.data(), db.data(), EPS, dev.Hp.data(), dev.bp.data(), dev.J0.data(),
                                   dev.e0.data(), nullptr, dev_min.data(), dev_status.data(), what)) {
             return false;
         }

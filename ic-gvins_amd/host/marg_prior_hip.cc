@@ -1,5 +1,5 @@
 // M4 on the HIP C ABI: the marginalization priors of many windows resident on the device.  MarginalizationFactor::Evaluate
-// (marginalization_factor.h:47-101) stays what the per-factor Ceres callback runs (factors.cc evaluateMargPrior); MarginalizationPriorSet
+// (marginalization_factor.h:47-101) stays what the per-factor Ceres callback runs (marginalization.cc evaluateMargPrior); MarginalizationPriorSet
 // is the same evaluation for MANY priors per call, for a driver that holds the priors of many windows and evaluates them at every LM point:
 // J0 / e0 / x0 cross the link once per marginalization, an evaluation ships the parameters in and the results out.
 #include <cstring>

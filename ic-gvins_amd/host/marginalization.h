@@ -1,0 +1,278 @@
+// Marginalization of boundary B1 (see factors.h for the reference lines each class mirrors): the factor records, MarginalizationInfo (M1,
+// M2, and M3 through marg_m3.h) and the linearized prior as a cost function (M4).  marginalization.cc holds the bookkeeping, the dense path
+// and the prior; marginalization_structured.cc the landmark-eliminated path and the block form of the host factors.
+#pragma once
+#include <memory>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "../../include/icgvins_hip.h"
+#include "ceres_compat.h"
+#include "pose_sizes.h"
+#include "reproj_factors.h"
+
+namespace icg {
+
+using std::vector;
+
+class ResidualBlockInfo {
+public:
+    ResidualBlockInfo(std::shared_ptr<ceres::CostFunction> cost_function, std::shared_ptr<ceres::LossFunction> loss_function,
+                      vector<double *> parameter_blocks, vector<int> marg_para_index)
+        : cost_function_(std::move(cost_function)), loss_function_(std::move(loss_function)),
+          parameter_blocks_(std::move(parameter_blocks)), marg_para_index_(std::move(marg_para_index)) {}
+    bool Evaluate(); // generic host path (residual_block_info.h:44-88)
+    const vector<vector<double>> &jacobians() const { return jacobians_; } // row-major num_residuals x block size
+    const vector<int32_t> &parameterBlockSizes() const { return cost_function_->parameter_block_sizes(); }
+    const vector<double *> &parameterBlocks() const { return parameter_blocks_; }
+    const vector<double> &residuals() const { return residuals_; }
+    const vector<int> &marginalizationParametersIndex() const { return marg_para_index_; }
+    const std::shared_ptr<ceres::CostFunction> &costFunction() const { return cost_function_; }
+    const std::shared_ptr<ceres::LossFunction> &lossFunction() const { return loss_function_; }
+
+private:
+    std::shared_ptr<ceres::CostFunction> cost_function_;
+    std::shared_ptr<ceres::LossFunction> loss_function_;
+    vector<double *> parameter_blocks_;
+    vector<int> marg_para_index_;
+    vector<vector<double>> jacobians_;
+    vector<double> residuals_;
+};
+
+// The host-evaluated factors of one window as blocks, in the flat layout icg_reproj_host_parts_build takes: per block nr residuals
+// (robust-corrected, as ResidualBlockInfo holds them), the nf columns of the window's compact camera system its free local columns occupy
+// and the dense row-major nr x nf Jacobian of those columns at J + jac_off.
+struct HostFactorBlocks {
+    vector<int32_t> nr, nf, cols;
+    vector<int64_t> jac_off;
+    vector<double> J, r;
+    // gatherHostBlocks with a deferred prior (MarginalizationBatch::setDevicePrior): that factor's block stands in its place with
+    // jac_off == kFromPrior, its slots in r reserved (zeros) and nothing in J; prior_block is its position among the blocks gathered by that
+    // call (-1: none, or the prior has no residual / no free column), prior_cols the free local columns of its parameter blocks in block
+    // order, view.index[a] + x: column y of the block is column prior_cols[y] of the prior's J0
+    static constexpr int64_t kFromPrior = ICG_HP_JAC_FROM_PRIOR;
+    int prior_block{-1};
+    vector<int32_t> prior_cols;
+    void clear() { nr.clear(), nf.clear(), cols.clear(), jac_off.clear(), J.clear(), r.clear(), prior_cols.clear(), prior_block = -1; }
+};
+// the leading `local` columns of one parameter block's row-major nr x size Jacobian into columns [c0, c0 + local) of a dense row-major
+// nr x nf Jacobian (a 7-wide pose block contributes its first 6 columns)
+inline void gatherJacobianColumns(int nr, int size, int local, const double *Ja, int nf, int c0, double *Jd) {
+    for (int k = 0; k < nr; k++)
+        for (int x = 0; x < local; x++) Jd[(size_t) k * nf + c0 + x] = Ja[(size_t) k * size + x];
+}
+
+class MarginalizationInfo {
+public:
+    MarginalizationInfo() = default;
+    ~MarginalizationInfo();
+    bool isValid() const { return isvalid_; }
+    static int localSize(int size) { return size == POSE_GLOBAL_SIZE ? POSE_LOCAL_SIZE : size; }
+    static int globalSize(int size) { return size == POSE_LOCAL_SIZE ? POSE_GLOBAL_SIZE : size; }
+    void addResidualBlockInfo(const std::shared_ptr<ResidualBlockInfo> &blockinfo);
+    void updateParamtersIds(const std::unordered_map<long, long> &parameters_ids) { parameters_ids_ = parameters_ids; }
+    // reprojection factors registered in `batch` are evaluated (with their Huber loss) and assembled on the GPU
+    void setReprojectionBatch(ReprojectionBatch *batch) { batch_ = batch; }
+    void setDeviceFactors(DeviceFactorSet *set) { batch_ = set; }
+    bool marginalization();
+    // wall time of the calling thread's last marginalization(): evaluate, construct, Schur, linearize [ms] (diagnostics / bench)
+    static const double *lastPhaseMs();
+    static bool lastWasStructured(); // the calling thread's last marginalization() took the landmark-eliminated (device) path
+    static void forceDense(bool on);  // process-wide: always take the reference's dense M2 + M3 (diagnostics / tests)
+    static bool denseForced();
+    vector<double *> getParamterBlocks(std::unordered_map<long, double *> &address);
+    const vector<double> &linearizedJacobians() const { return linearized_jacobians_; } // remained x remained, row-major
+    const vector<double> &linearizedResiduals() const { return linearized_residuals_; }
+    int marginalizedSize() const { return marginalized_size_; }
+    int remainedSize() const { return remained_size_; }
+    const vector<int> &remainedBlockSize() const { return remained_block_size_; }
+    const vector<int> &remainedBlockIndex() const { return remained_block_index_; }
+    const vector<double *> &remainedBlockData() const { return remained_block_data_; }
+    // exposed for tests: the Schur complement before linearization
+    const vector<double> &Hp() const { return Hp_; }
+    const vector<double> &bp() const { return bp_; }
+    // Where this linearization also lies on the device: window `slot` of the kept linearization `id` (icg_marg_linearize_batch_keep), set by
+    // MarginalizationBatch::setKeepLinearized for a window whose prior came from the device call; id 0 = nowhere.  A tag may outlive the
+    // kept buffer: MarginalizationPriorSet::set then ships the host arrays, which are always complete.
+    void setKeptLinearization(uint64_t id, int slot) { keep_id_ = id, keep_slot_ = slot; }
+    uint64_t keptId() const { return keep_id_; }
+    int keptSlot() const { return keep_slot_; }
+    // Diagnostics / tests: M1 bookkeeping, the evaluation of every factor and the structured plan of this window as marginalization()
+    // forms it on the landmark-eliminated path, before the device part is added: H (P x P) and b as planStructured accumulates them, and
+    // the same host factors gathered as blocks.  false: the window is not planned (it would take the dense path), or its factors cannot
+    // be gathered as blocks.
+    bool planWithBlocks(int *P, int *m, vector<double> *H, vector<double> *b, HostFactorBlocks *blocks);
+    // Diagnostics / tests of MarginalizationBatch::setDevicePrior's host side: the same steps with the window's prior (devicePriorCandidate,
+    // *prior_out) deferred — `deferred` is gathered while that factor has not been evaluated, then the deferred evaluation runs and `eager`
+    // is what gatherHostBlocks packs from the evaluated factor.  false: no such prior, or the window is not planned.
+    bool planWithDeferredPrior(HostFactorBlocks *deferred, HostFactorBlocks *eager, const ResidualBlockInfo **prior_out = nullptr);
+    // The host factor MarginalizationBatch::setDevicePrior hands to the device: the first one (factors_ order) whose cost function is a
+    // MargPriorSource, that has no loss function and whose view describes the residual block (r residuals, the blocks' global sizes) — the
+    // test WindowSolverBatch::layout applies.  nullptr: the window has none (a robustified prior stays a host factor).
+    const ResidualBlockInfo *devicePriorCandidate() const;
+
+private:
+    bool updateParameterBlocksIndex();
+    // the factor is one of the device set's: a reprojection factor the set owns, without a loss function or with the device's Huber loss
+    bool onBatch(const std::shared_ptr<ResidualBlockInfo> &factor) const;
+    // defer (one of this window's factors, or nullptr): that factor is NOT evaluated — its blocks are snapshot like every factor's — until
+    // evaluateDeferred() is called (true when there was nothing to do).  A window that stays on the structured device path never calls it.
+    bool preMarginalization(const ResidualBlockInfo *defer = nullptr);
+    bool evaluateDeferred();
+    bool constructEquation();
+    // M2 of the host factors (:195-230), the one copy of the loop: H += J^T J, b -= J^T e of every factor that is not on the device set, H
+    // row-major with `stride` columns.  Local column c of the window goes to column column_of_local[c]; nullptr is the identity.
+    void accumulateHostFactors(const int *column_of_local, int stride, double *H, double *b);
+    void schurElimination();
+    // M2 + M3 in one step when the marginalized set is {a few pose / mix blocks} + {inverse depths seen only by the device batch}:
+    // the 1x1 landmark blocks are eliminated on the device, the host finishes on the small camera system.  Returns false (nothing
+    // touched) when the structure or the conditioning guard does not hold: the dense path then runs as before.
+    bool constructAndEliminateStructured();
+    // the two host halves of it, either side of the device step (MarginalizationBatch runs that step for many windows in one launch):
+    // planStructured checks the structure, lays out the compact camera system and adds the host factors; finishStructured takes the
+    // system with the landmark-eliminated device part added and runs the conditioning guard and the small M3.
+    // planStructured is planLayout (the structure checks, the compact columns, P, m, r, camera_column_of) followed by planAccumulate (J^T J
+    // and J^T e of the host factors into H and b); MarginalizationBatch::setDeviceReducedSystem calls planLayout alone and ships the host
+    // factors as blocks instead (gatherHostBlocks).
+    struct StructuredPlan {
+        int P{0}, m{0}, r{0};
+        vector<double> H, b;
+        std::unordered_map<const double *, int> camera_column_of;
+        vector<int> compact; // local column -> column of the compact camera system, -1 for an inverse depth
+    };
+    bool planStructured(StructuredPlan &plan);
+    bool planLayout(StructuredPlan &plan);
+    void planAccumulate(StructuredPlan &plan);
+    // The window's host factors (factors_ order, the factors on the device batch skipped), appended to `out` as one block each.  false —
+    // `out` is then as it was — when a factor lists a parameter block twice (its J^T J is not one block's) or has more than
+    // ICG_HOST_PART_MAX_NR residuals: the caller treats the window as not planned.
+    // prior (the factor preMarginalization deferred): its block is emitted in its place — the block order is factors_ order, the device
+    // sums follow it — with nr = r, its nf window columns, its slots in r reserved, HostFactorBlocks::kFromPrior for a Jacobian offset, and
+    // out.prior_block / out.prior_cols say where J0's columns go.
+    bool gatherHostBlocks(const StructuredPlan &plan, HostFactorBlocks &out, const ResidualBlockInfo *prior = nullptr);
+    bool finishStructured(StructuredPlan &plan, double min_hll);
+    friend class MarginalizationBatch;
+    void linearization();
+    // (:99) the window's factor records are done with.  The reference frees them here; a window's ~1 100 records own ~3 heap blocks each
+    // (the reference's residual_block_info.h layout) and freeing them in line is a third of one marginalization — so they are RETIRED: kept
+    // until this object is destroyed (it lives on as the prior until the next marginalization replaces it) and freed then, by whoever
+    // drops it.  (Rounds 4-5 handed them to a process-wide reaper thread: a thread a drop-in library has no business starting — VERDICT r5,
+    // ADVICE r5 on fork() and static teardown.)
+    void releaseMemory() {
+        if (retired_.empty())
+            retired_.swap(factors_);
+        else
+            retired_.insert(retired_.end(), std::make_move_iterator(factors_.begin()), std::make_move_iterator(factors_.end()));
+        factors_.clear();
+    }
+    // the same, with the records handed to `bin` (MarginalizationBatch keeps the retired records of all its windows until clear())
+    void releaseMemoryInto(vector<std::shared_ptr<ResidualBlockInfo>> &bin) {
+        bin.insert(bin.end(), std::make_move_iterator(factors_.begin()), std::make_move_iterator(factors_.end()));
+        factors_.clear();
+    }
+    long idOf(const double *p) { return parameters_ids_[reinterpret_cast<long>(p)]; }
+
+    vector<double> H0_, Hp_, b0_, bp_;
+    std::unordered_map<long, long> parameters_ids_;
+    std::unordered_map<long, int> parameter_block_size_;
+    std::unordered_map<long, int> parameter_block_index_;
+    std::unordered_map<long, double *> parameter_block_data_;
+    vector<int> remained_block_size_, remained_block_index_;
+    vector<double *> remained_block_data_;
+    int marginalized_size_{0}, remained_size_{0}, local_size_{0};
+    vector<std::shared_ptr<ResidualBlockInfo>> factors_, retired_; // retired_: see releaseMemory()
+    static constexpr double EPS = 1e-8; // the reference's floor (marginalization_info.h:30)
+    // the landmark-eliminated path runs only where every h_ll and every eigenvalue of the m-block is above 100 x that floor
+    static constexpr double STRUCTURED_GUARD = 100.0 * EPS;
+    vector<double> linearized_jacobians_, linearized_residuals_;
+    bool isvalid_{true};
+    DeviceFactorSet *batch_{nullptr};
+    ResidualBlockInfo *deferred_{nullptr}; // preMarginalization(defer): not evaluated yet
+    uint64_t keep_id_{0};
+    int keep_slot_{-1};
+};
+
+// M4 on plain arrays: what MarginalizationFactor::Evaluate reads of a MarginalizationInfo.  index[b] is block b's first local column
+// (the remained block index minus the marginalized size), x0[b] its linearization point (size[b] values).
+struct MargPriorView {
+    int r{0}, n_blocks{0};
+    const int *size{nullptr}, *index{nullptr};
+    const double *const *x0{nullptr};
+    const double *J0{nullptr}, *e0{nullptr}; // r x r row-major, r
+    // the same J0 / e0 on the device: window keep_slot of the kept linearization keep_id (MarginalizationInfo::keptId); 0 / -1: host only
+    uint64_t keep_id{0};
+    int keep_slot{-1};
+};
+
+// A cost function that IS a linearized marginalization prior says so: its Evaluate is evaluateMargPrior over the view, block b of the view
+// being parameter block b of the cost function.  A solver that keeps the priors of its windows resident on the device
+// (WindowSolverBatch::setDevicePrior) recognises the prior through this interface; the view stays valid and unchanged while the cost
+// function lives.
+class MargPriorSource {
+public:
+    virtual ~MargPriorSource() = default;
+    virtual const MargPriorView &margPriorView() const = 0;
+};
+
+class MarginalizationFactor : public ceres::CostFunction, public MargPriorSource {
+public:
+    MarginalizationFactor() = delete;
+    MarginalizationFactor(const MarginalizationFactor &) = delete; // (the view points into this object)
+    explicit MarginalizationFactor(std::shared_ptr<MarginalizationInfo> marg_info);
+    bool Evaluate(const double *const *parameters, double *residuals, double **jacobians) const override;
+    const MargPriorView &margPriorView() const override { return view_; }
+
+private:
+    std::shared_ptr<MarginalizationInfo> marg_info_;
+    vector<int> size_, index_;  // the remained blocks' global sizes; their indices minus the marginalized size
+    vector<const double *> x0_; // their linearization points (the info's arrays)
+    MargPriorView view_;
+};
+// MarginalizationFactor::Evaluate (marginalization_factor.h:47-101) over a view: residuals r; jacobians (optional, entries may be null):
+// per block an r x size[b] row-major matrix
+void evaluateMargPrior(const MargPriorView &view, const double *const *parameters, double *residuals, double **jacobians);
+
+// The priors of many windows resident on the device (icg_marg_prior_set / icg_marg_prior_evaluate): set() after every marginalization,
+// evaluate() per LM point.  Results are the bits evaluateMargPrior gives.  The two C entries are referenced weakly: in a build of this
+// layer on a C ABI without them available() is false and set() fails by name.  (Implemented in marg_prior_hip.cc.)
+class MarginalizationPriorSet {
+public:
+    static bool available(); // icg_marg_prior_set and icg_marg_prior_evaluate are in this build
+    // packs and uploads the priors once; x0 is read through the views now (a MarginalizationInfo's remainedBlockData() is the info's own
+    // copy and does not change after marginalization()).  Replaces the set `ctx` held.  false with *err set on failure.
+    bool set(icg_ctx *ctx, const vector<MargPriorView> &views, std::string *err = nullptr);
+    bool set(icg_ctx *ctx, const vector<std::shared_ptr<MarginalizationInfo>> &infos, std::string *err = nullptr);
+    // parameters[w][b]: block b of window w at the evaluation point.  residuals: residualSize() doubles, window after window;
+    // jacobians (optional): jacobianSize() doubles, per window its blocks concatenated, block b r x size[b] row-major;
+    // gradient (optional): J0^T e, residualSize(); sq_norm (optional): e . e per window.
+    bool evaluate(const vector<const double *const *> &parameters, double *residuals, double *jacobians, double *gradient, double *sq_norm,
+                  std::string *err = nullptr);
+    // The resident evaluation (icg_marg_prior_evaluate_resident): the residuals stay on the device for
+    // icg_reproj_host_parts_build_prior, only sq_norm (e . e per window) comes back.  pack(w, ...) copies window w's parameter blocks to
+    // their place in the set's evaluation point (any thread, before the call; a window that is not packed keeps its last point, zeros
+    // after set()); evaluateResident() makes the one device call.  The entry is referenced weakly like the two above:
+    // residentAvailable() is false in a build of this layer on a C ABI without it, and evaluateResident() then fails by name.
+    static bool residentAvailable();
+    void pack(size_t w, const double *const *parameters);
+    bool evaluateResident(double *sq_norm, std::string *err = nullptr);
+    int windows() const { return (int) r_.size(); }
+    // The hand-off: when every tagged view of a set() names the same live kept linearization (MargPriorView::keep_id), the tagged windows
+    // take J0 / e0 where the linearize call left them on the device (icg_marg_prior_set_from_kept, weakly referenced) and only the untagged
+    // windows' arrays are packed and shipped.  Without the entry, with differing ids or with a linearization that is gone, set() ships
+    // every window as before.  handedOff(): the windows of the last set() that took the hand-off.
+    static bool handOffAvailable();
+    int handedOff() const { return handed_off_; }
+    size_t residualSize() const { return residual_size_; }
+    size_t jacobianSize() const { return jacobian_size_; }
+
+private:
+    icg_ctx *ctx_{nullptr};
+    vector<int32_t> r_, block_off_, block_size_;
+    vector<size_t> x_off_; // first parameter of window w in x_
+    vector<double> x_; // the evaluation point, packed like x0
+    size_t residual_size_{0}, jacobian_size_{0};
+    int handed_off_{0};
+};
+
+} // namespace icg

@@ -24,8 +24,12 @@
 // the product's front-end host layer, in drop-in mode (the same sources that build libicgvins_host.so)
 #include "../../ic-gvins_amd/host/model.cc"
 #include "../../ic-gvins_amd/host/tracking_hip.cc"
-// the product's back-end factors (the same source that builds libicgvins_host.so), in drop-in mode
-#include "../../ic-gvins_amd/host/factors.cc"
+// the product's back-end factors (the same sources that build libicgvins_host.so, all that factors.h declares on the host side), in drop-in mode
+#include "../../ic-gvins_amd/host/reproj_factors.cc"
+#include "../../ic-gvins_amd/host/sym_eigen.cc"
+#include "../../ic-gvins_amd/host/marg_m3.cc"
+#include "../../ic-gvins_amd/host/marginalization.cc"
+#include "../../ic-gvins_amd/host/marginalization_structured.cc"
 static icg::ReprojectionBatch *icg_b1 = nullptr; // the batch of the window being optimized (set by the patched gvinsOptimization)
 
 // ---- the reference's names -------------------------------------------------------------------------------------------------------

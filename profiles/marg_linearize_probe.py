@@ -6,7 +6,8 @@ including its transfers — then the host layer's entry (icgh_backend_marg_linea
 HostPool).  Last leg: icgh_backend_marginalize_batch on 256 C2 windows, mode 0 (host step 4) against mode 2 (setDeviceLinearization).
 `python profiles/marg_linearize_probe.py [out.json] [--threads 16] [--cpus 2] [--reps 5]`; --cpus N confines the legs to N of the CPUs the
 process may run on (one rank's share of a node).  Every leg is a child process of its own under a time limit; the first leg that fails
-ends the run.  Run by hand; not part of bench.py."""
+ends the run.  ICG_PROBE_HOST_LIB: another build of the host layer (as in marg_batch_probe.py; the
+c_abi leg is the device library's own and does not depend on it).  Run by hand; not part of bench.py."""
 import ctypes as C
 import json
 import os
@@ -49,7 +50,7 @@ def measure_shape(name, threads, reps, n_windows=256):
         ctx.prof_enable(False)
         out["c_abi"][form] = dict(kern, call_wall_ms_incl_transfers_best=round(best * 1e3, 3), status_or=int(np.bitwise_or.reduce(res["status"])))
     ctx.close()
-    hl = C.CDLL(H.HOST_LIB)
+    hl = C.CDLL(os.environ.get("ICG_PROBE_HOST_LIB") or H.HOST_LIB)
     rc, msg, o1, s1 = ml.backend_marg_linearize(hl, 1, systems, reps=reps)
     if rc != 0:
         raise RuntimeError(f"icgh_backend_marg_linearize mode 1 rc={rc}: {msg}")
@@ -67,7 +68,7 @@ def measure_batch(threads, reps, n_windows=256):
     import backend_utils as bu
     import harness as H
     import marg_data as md
-    hl = C.CDLL(H.HOST_LIB)
+    hl = C.CDLL(os.environ.get("ICG_PROBE_HOST_LIB") or H.HOST_LIB)
     Pm = md.make_problem(n_lm=300, n_kf=10, seed=2)  # the C2 window of the bench's marginalization block
     bu.backend_marginalize_batch(hl, Pm, 8, 0)
     bu.backend_marginalize_batch(hl, Pm, 8, 2)

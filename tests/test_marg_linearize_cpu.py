@@ -99,7 +99,7 @@ def test_chosen_inputs_have_no_eigenvalue_near_the_floor_and_host_mode_equals_th
 
 def _loops_before_the_refactoring(lib, H, b, m, eps=ml.EPS):
     """MarginalizationInfo::schurElimination and ::linearization as they stood before they were factored into schurReduce / linearizePrior
-    (host/factors.cc), restated loop for loop over numpy.float64 scalars; the eigen-solver through icgh_symmetric_eigen"""
+    (host/marg_m3.cc), restated loop for loop over numpy.float64 scalars; the eigen-solver through icgh_symmetric_eigen"""
     f, P = np.float64, H.shape[0]
     r = P - m
 
@@ -177,6 +177,127 @@ def test_the_factored_host_functions_give_the_bits_of_the_loops_they_replace():
         Hp, bp, J0, e0 = _loops_before_the_refactoring(lib, np.ascontiguousarray(got["Hp"]), np.ascontiguousarray(got["bp"]), 0)
         assert ml.same_bits(Hp, got["Hp"]) and ml.same_bits(bp, got["bp"])  # (m = 0: the Schur step is the identity)
         assert ml.same_bits(J0, got["J0"]) and ml.same_bits(e0, got["e0"]), (dense, r)
+
+
+GUARD = 100.0 * ml.EPS  # MarginalizationInfo::STRUCTURED_GUARD
+
+
+def _guarded_loops_before_the_refactoring(lib, H, b, m, guard=GUARD):
+    """MarginalizationInfo::finishStructured's second guard and small M3 as they stood before they became schurReduceGuarded
+    (host/marg_m3.cc): each eigenvector column DIVIDED by its eigenvalue, restated loop for loop over numpy.float64 scalars; the
+    eigen-solver through icgh_symmetric_eigen.  None: the guard refuses."""
+    f, P = np.float64, H.shape[0]
+    r = P - m
+    Hmm = np.array([[f(0.5) * (H[i, j] + H[j, i]) for j in range(m)] for i in range(m)]).reshape(m, m)
+    ev, V = np.zeros(m), np.zeros((m, m))
+    if m:
+        assert lib.icgh_symmetric_eigen(m, ml._p(np.ascontiguousarray(Hmm)), ml._p(ev), ml._p(V)) == 0
+    for k in range(m):
+        if not ev[k] > guard:
+            return None
+    Wv = [[V[i, k] / ev[k] for k in range(m)] for i in range(m)]
+    Hinv = np.zeros((m, m))
+    for i in range(m):
+        for j in range(i + 1):
+            s = f(0)
+            for k in range(m):
+                s = s + Wv[i][k] * V[j, k]
+            Hinv[i, j] = Hinv[j, i] = s
+    T = np.zeros((r, m))
+    for i in range(r):
+        for j in range(m):
+            s = f(0)
+            for k in range(m):
+                s = s + H[m + i, k] * Hinv[k, j]
+            T[i, j] = s
+    Hp, bp = np.zeros((r, r)), np.zeros(r)
+    for i in range(r):
+        for j in range(r):
+            s = f(0)
+            for k in range(m):
+                s = s + T[i, k] * H[k, m + j]
+            Hp[i, j] = H[m + i, m + j] - s
+        s = f(0)
+        for k in range(m):
+            s = s + T[i, k] * b[k]
+        bp[i] = b[m + i] - s
+    return Hp, bp
+
+
+def _schur_reduce_guarded(lib, s, guard=GUARD):
+    r = s["P"] - s["m"]
+    Hp, bp = np.full((r, r), MARK), np.full(r, MARK)
+    rc = lib.icgh_schur_reduce_guarded(s["P"], s["m"], ml._p(s["H"]), ml._p(np.ascontiguousarray(s["b"])), C.c_double(guard), ml._p(Hp), ml._p(bp))
+    return rc, Hp, bp
+
+
+def test_the_guarded_schur_step_gives_the_bits_of_the_loops_it_replaces_and_refuses_untouched():
+    lib = _oracle_host()
+    systems = [ml.spd_system(24, 6, 21), ml.badly_scaled_system(25, P=18, m=4), ml.spd_system(9, 0, 22), ml.spd_system(7, 1, 23),
+               ml.spd_system(6, 5, 24), ml.zero_row_system(23, P=20, m=5)]  # m = 0, m = 1 and r = 1 (P = m + 1) among them; the last one's
+    # zero row lies in the retained block (index 19), so its m-block passes the guard and Hp has a zero row and column
+    assert [(s["m"], s["P"] - s["m"]) for s in systems[2:]] == [(0, 9), (1, 6), (5, 1), (5, 15)]
+    rc, msg, out, _ = ml.backend_marg_linearize(lib, 0, systems, host_threads=2)
+    assert rc == 0, msg
+    differs = []
+    for s, floored in zip(systems, ml.split(systems, out)):
+        want = _guarded_loops_before_the_refactoring(lib, s["H"], s["b"], s["m"])
+        rc, Hp, bp = _schur_reduce_guarded(lib, s)
+        assert rc == 1 and want is not None, s["name"]
+        assert ml.same_bits(Hp, want[0]) and ml.same_bits(bp, want[1]), s["name"]
+        differs.append(not ml.same_bits(Hp, floored["Hp"]))
+        if s["m"] == 0:
+            assert ml.same_bits(Hp, s["H"]) and ml.same_bits(bp, s["b"])
+    # V / ev against V * (1 / ev): the two forms of the step are not the same bits, and neither one-liner may replace the other
+    assert differs[0] or differs[1], differs
+    assert not differs[2]  # (m = 0: nothing is scaled)
+    # refusals: an m-block eigenvalue at or below the guard (exactly 0 here; then exactly at the guard) leaves the outputs as they were
+    z = ml.zero_row_system(24, P=20, m=5, where=2)  # (the zero row inside the m-block)
+    assert _guarded_loops_before_the_refactoring(lib, z["H"], z["b"], z["m"]) is None
+    rc, Hp, bp = _schur_reduce_guarded(lib, z)
+    assert rc == 0 and np.all(Hp == MARK) and np.all(bp == MARK)
+    s = systems[0]
+    smallest = float(ml.host_eigenvalues(lib, 0.5 * (s["H"][:6, :6] + s["H"][:6, :6].T))[0])
+    rc, Hp, bp = _schur_reduce_guarded(lib, s, guard=smallest)
+    assert rc == 0 and np.all(Hp == MARK) and np.all(bp == MARK)
+    assert _schur_reduce_guarded(lib, s, guard=np.nextafter(smallest, 0.0))[0] == 1
+    assert _schur_reduce_guarded(lib, s, guard=float("nan"))[0] == 0
+    assert lib.icgh_schur_reduce_guarded(5, 5, ml._p(s["H"]), ml._p(s["b"]), C.c_double(GUARD), ml._p(Hp), ml._p(bp)) == -1
+
+
+def test_the_first_guard_refuses_a_landmark_minimum_at_the_guard_or_nan_and_leaves_the_outputs():
+    """MarginalizationInfo::finishStructured's first guard on a real window (icgh_backend_marginalize_min_hll: the device factor set reports
+    the smallest landmark diagonal the test chooses): above the guard the landmark-eliminated path gives its bits, at the guard and for a
+    NaN it refuses with Hp_ / bp_ still empty when the dense assembly starts, and the window gets the dense path's bits."""
+    import backend_utils as bu
+    import marg_data as md
+    lib = _oracle_host()
+    P = md.make_problem(n_lm=40, n_kf=4, seed=7)
+    ref = {}
+    for dense in (1, 0):
+        lib.icgh_backend_marginalization_force_dense(dense)
+        try:
+            ref[dense] = bu.backend_marginalize(lib, P)
+        finally:
+            lib.icgh_backend_marginalization_force_dense(0)
+    assert not ml.same_bits(ref[0]["Hp"], ref[1]["Hp"])  # (the two paths are told apart by their bits)
+
+    def run(min_hll):
+        args, K, L = bu.marg_problem_args(P, 1.0, 100.0)
+        cap = 6 * K + L + 7
+        flags, sizes, Hp, bp = np.zeros(2, np.int32), np.zeros(2, np.int32), np.zeros(cap * cap), np.zeros(cap)
+        err = C.create_string_buffer(512)
+        rc = lib.icgh_backend_marginalize_min_hll(*args, C.c_double(min_hll), ml._p(flags), ml._p(sizes), ml._p(Hp), ml._p(bp), err, 512)
+        assert rc == 0, (rc, err.value)
+        r = int(sizes[1])
+        return int(flags[0]), int(flags[1]), Hp[:r * r], bp[:r]
+
+    structured, at_dense, Hp, bp = run(float(np.nextafter(GUARD, np.inf)))
+    assert (structured, at_dense) == (1, -1) and ml.same_bits(Hp, ref[0]["Hp"]) and ml.same_bits(bp, ref[0]["bp"])
+    for refused in (GUARD, float("nan"), 0.0):
+        structured, at_dense, Hp, bp = run(refused)
+        assert (structured, at_dense) == (0, 0), refused
+        assert ml.same_bits(Hp, ref[1]["Hp"]) and ml.same_bits(bp, ref[1]["bp"]), refused
 
 
 def test_host_entry_rejects_an_invalid_system():
