@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from ctypes_util import ErrBuf, ptr
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB = os.path.join(_HERE, "libicgvins_host.so")
 # estimator port + replay harness + scene renderer (ic-gvins_amd/tools/): NOT part of the product libraries; it links on top of them,
@@ -82,9 +84,8 @@ class SynthScene:
         R, t = self.pose(k, fps, stream)
         pose12 = np.concatenate([R.ravel(), t]).astype(np.float64)
         out = np.zeros((self.h, self.w), np.uint8)
-        p = lambda a: a.ctypes.data_as(C.c_void_p)
-        self.lib.icgs_render(p(self.tex), self.tex_size, C.c_double(self.texels_per_m), p(self.rays), self.w, self.h, p(pose12),
-                             p(self.plane), p(self.e1), p(self.e2), p(out), self.w, self.threads)
+        self.lib.icgs_render(ptr(self.tex), self.tex_size, C.c_double(self.texels_per_m), ptr(self.rays), self.w, self.h, ptr(pose12),
+                             ptr(self.plane), ptr(self.e1), ptr(self.e2), ptr(out), self.w, self.threads)
         return out
 
 
@@ -114,18 +115,18 @@ class StreamBatch:
         self.lib.icgh_batch_ctx.argtypes = [C.c_void_p, C.c_int]
         self.lib.icgh_batch_destroy.argtypes = [C.c_void_p]
         self.n, self.w, self.h = n_streams, width, height
-        err = C.create_string_buffer(512)
+        err = ErrBuf()
         cam = np.asarray(cam10, np.float64)
         self.h_ = self.lib.icgh_batch_create(device, n_streams, cam.ctypes.data_as(C.c_void_p), width, height, max_features,
                                              C.c_double(min_parallax), C.c_double(max_interval), 1 if check_hist else 0,
-                                             C.c_double(reproj_std), window, host_threads, groups, err, 512)
+                                             C.c_double(reproj_std), window, host_threads, groups, *err.args)
         if engine is not None:
             if old_engine is None:
                 del os.environ["ICG_TRACK_ENGINE"]
             else:
                 os.environ["ICG_TRACK_ENGINE"] = old_engine
         if not self.h_:
-            raise RuntimeError("icgh_batch_create failed: " + err.value.decode())
+            raise RuntimeError("icgh_batch_create failed: " + err.text())
         self._err = err
 
     def engine(self):
@@ -139,9 +140,9 @@ class StreamBatch:
         n = self.lib.icgh_batch_dump(C.c_void_p(self.h_), stream, kind, None, C.c_long(0))
         if n < 0:
             raise RuntimeError(f"icgh_batch_dump failed: {n}")
-        buf = C.create_string_buffer(n + 1)
-        self.lib.icgh_batch_dump(C.c_void_p(self.h_), stream, kind, buf, C.c_long(n + 1))
-        return buf.value.decode()
+        buf = ErrBuf(n + 1)
+        self.lib.icgh_batch_dump(C.c_void_p(self.h_), stream, kind, buf.buf, C.c_long(n + 1))
+        return buf.text()
 
     def close(self):
         if getattr(self, "h_", None):
@@ -168,9 +169,9 @@ class StreamBatch:
         states = np.zeros(self.n, np.int32)
         rc = self.lib.icgh_batch_step(C.c_void_p(self.h_), ptrs, stride, channels, 1 if on_device else 0,
                                       stamps.ctypes.data_as(C.c_void_p), poses12.ctypes.data_as(C.c_void_p),
-                                      states.ctypes.data_as(C.c_void_p), self._err, 512)
+                                      states.ctypes.data_as(C.c_void_p), *self._err.args)
         if rc != 0:
-            raise RuntimeError("icgh_batch_step failed: " + self._err.value.decode())
+            raise RuntimeError("icgh_batch_step failed: " + self._err.text())
         return states
 
     def run(self, image_ptrs, stride, stamps, poses12, on_device=False, channels=1):
@@ -183,9 +184,9 @@ class StreamBatch:
         states = np.zeros((K, self.n), np.int32)
         rc = self.lib.icgh_batch_run(C.c_void_p(self.h_), K, ptrs, stride, channels, 1 if on_device else 0,
                                      stamps.ctypes.data_as(C.c_void_p), poses12.ctypes.data_as(C.c_void_p),
-                                     states.ctypes.data_as(C.c_void_p), self._err, 512)
+                                     states.ctypes.data_as(C.c_void_p), *self._err.args)
         if rc != 0:
-            raise RuntimeError("icgh_batch_run failed: " + self._err.value.decode())
+            raise RuntimeError("icgh_batch_run failed: " + self._err.text())
         return states
 
     def stats(self, stream):

@@ -8,6 +8,9 @@ import os
 
 import numpy as np
 
+from ctypes_util import ErrBuf, f32, f64, i32, u8
+from ctypes_util import ptr as _p  # (Context's methods have parameters named ptr)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libicgvins_hip.so")
 
@@ -72,24 +75,6 @@ def load_library(path=LIB_PATH):
     return lib
 
 
-def _p(a, t=None):
-    if a is None:
-        return None
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _f32(a):
-    return np.ascontiguousarray(a, dtype=np.float32)
-
-
-def _i32(a):
-    return np.ascontiguousarray(a, dtype=np.int32)
-
-
-def _f64(a):
-    return np.ascontiguousarray(a, dtype=np.float64)
-
-
 class Context:
     """One icg_ctx: a HIP stream + resident frame slots on one MI355X."""
 
@@ -134,10 +119,10 @@ class Context:
         self._ck(self.lib.icg_prof_enable(self.h, 1 if on else 0), "icg_prof_enable")
 
     def prof(self):
-        buf = C.create_string_buffer(4096)
-        self._ck(self.lib.icg_prof_names(self.h, buf, 4096), "icg_prof_names")
+        buf = ErrBuf(4096)
+        self._ck(self.lib.icg_prof_names(self.h, *buf.args), "icg_prof_names")
         out = {}
-        for name in buf.value.decode().split("\n"):
+        for name in buf.text().split("\n"):
             if not name:
                 continue
             n, ms = C.c_int(), C.c_double()
@@ -166,7 +151,7 @@ class Context:
         stride = imgs[0].strides[0]
         ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
         hist = np.zeros(n, np.float64) if want_hist else None
-        self._ck(self.lib.icg_frames_preprocess(self.h, n, _p(_i32(slots)), ptrs, stride, ch, 0, _p(hist)),
+        self._ck(self.lib.icg_frames_preprocess(self.h, n, _p(i32(slots)), ptrs, stride, ch, 0, _p(hist)),
                  "icg_frames_preprocess")
         # without want_hist the call returns with the upload still in flight: a frame that had to be copied to make it contiguous uint8 is a
         # temporary of this function and must outlive the upload (a column-major frame came out as garbage from some row on, a different row every run)
@@ -186,7 +171,7 @@ class Context:
         n = len(slots)
         ptrs = (C.c_void_p * n)(*dev_ptrs)
         hist = np.zeros(n, np.float64) if want_hist else None
-        self._ck(self.lib.icg_frames_preprocess(self.h, n, _p(_i32(slots)), ptrs, stride, channels, 1, _p(hist)),
+        self._ck(self.lib.icg_frames_preprocess(self.h, n, _p(i32(slots)), ptrs, stride, channels, 1, _p(hist)),
                  "icg_frames_preprocess")
         return hist
 
@@ -200,27 +185,27 @@ class Context:
 
     # ---- F2/F3
     def lk_track(self, prev_slot, next_slot, prev_pts, guess, want_err=True):
-        prev_pts = _f32(prev_pts).reshape(-1, 2)
+        prev_pts = f32(prev_pts).reshape(-1, 2)
         n = prev_pts.shape[0]
-        nxt = _f32(guess).reshape(-1, 2).copy()
+        nxt = f32(guess).reshape(-1, 2).copy()
         st = np.zeros(n, np.uint8)
         err = np.zeros(n, np.float32) if want_err else None
-        ps = _i32(np.broadcast_to(prev_slot, (n,)))
-        ns = _i32(np.broadcast_to(next_slot, (n,)))
+        ps = i32(np.broadcast_to(prev_slot, (n,)))
+        ns = i32(np.broadcast_to(next_slot, (n,)))
         self._ck(self.lib.icg_lk_track(self.h, n, _p(ps), _p(ns), _p(prev_pts), _p(nxt), _p(st), _p(err)), "icg_lk_track")
         return nxt, st, err
 
     def lk_track_fb(self, prev_slot, next_slot, prev_pts, guess, want_undist=False, want_keep=False):
-        prev_pts = _f32(prev_pts).reshape(-1, 2)
-        guess = _f32(guess).reshape(-1, 2)
+        prev_pts = f32(prev_pts).reshape(-1, 2)
+        guess = f32(guess).reshape(-1, 2)
         n = prev_pts.shape[0]
         out = np.zeros((n, 2), np.float32)
         st = np.zeros(n, np.uint8)
         und = np.zeros((n, 2), np.float32) if want_undist else None
         keep = np.zeros(max(n, 1), np.int32) if want_keep else None
         nkeep = np.zeros(1, np.int32) if want_keep else None
-        ps = _i32(np.broadcast_to(prev_slot, (n,)))
-        ns = _i32(np.broadcast_to(next_slot, (n,)))
+        ps = i32(np.broadcast_to(prev_slot, (n,)))
+        ns = i32(np.broadcast_to(next_slot, (n,)))
         self._ck(self.lib.icg_lk_track_fb(self.h, n, _p(ps), _p(ns), _p(prev_pts), _p(guess), _p(out), _p(st), _p(und),
                                            _p(keep), _p(nkeep)), "icg_lk_track_fb")
         res = [out, st]
@@ -232,38 +217,38 @@ class Context:
 
     # ---- F4/F5
     def undistort(self, pts):
-        p = _f32(pts).reshape(-1, 2).copy()
+        p = f32(pts).reshape(-1, 2).copy()
         self._ck(self.lib.icg_undistort_points(self.h, p.shape[0], _p(p)), "icg_undistort_points")
         return p
 
     def distort(self, pts):
-        p = _f32(pts).reshape(-1, 2).copy()
+        p = f32(pts).reshape(-1, 2).copy()
         self._ck(self.lib.icg_distort_points(self.h, p.shape[0], _p(p)), "icg_distort_points")
         return p
 
     def predict_mappoints(self, pw, pose_idx, poses12):
-        pw = _f64(pw).reshape(-1, 3)
-        poses12 = _f64(poses12).reshape(-1, 12)
+        pw = f64(pw).reshape(-1, 3)
+        poses12 = f64(poses12).reshape(-1, 12)
         n = pw.shape[0]
         out = np.zeros((n, 2), np.float32)
-        self._ck(self.lib.icg_predict_mappoints(self.h, n, _p(pw), _p(_i32(np.broadcast_to(pose_idx, (n,)))),
+        self._ck(self.lib.icg_predict_mappoints(self.h, n, _p(pw), _p(i32(np.broadcast_to(pose_idx, (n,)))),
                                                  poses12.shape[0], _p(poses12), _p(out)), "icg_predict_mappoints")
         return out
 
     def predict_rotation(self, pts, rot_idx, rots9):
-        pts = _f32(pts).reshape(-1, 2)
-        rots9 = _f64(rots9).reshape(-1, 9)
+        pts = f32(pts).reshape(-1, 2)
+        rots9 = f64(rots9).reshape(-1, 9)
         n = pts.shape[0]
         out = np.zeros((n, 2), np.float32)
-        self._ck(self.lib.icg_predict_rotation(self.h, n, _p(pts), _p(_i32(np.broadcast_to(rot_idx, (n,)))),
+        self._ck(self.lib.icg_predict_rotation(self.h, n, _p(pts), _p(i32(np.broadcast_to(rot_idx, (n,)))),
                                                 rots9.shape[0], _p(rots9), _p(out)), "icg_predict_rotation")
         return out
 
     # ---- F6
     def fm_ransac(self, offsets, pts1, pts2, thresh=1.5, conf=0.99):
-        offsets = _i32(offsets)
-        pts1 = _f32(pts1).reshape(-1, 2)
-        pts2 = _f32(pts2).reshape(-1, 2)
+        offsets = i32(offsets)
+        pts1 = f32(pts1).reshape(-1, 2)
+        pts2 = f32(pts2).reshape(-1, 2)
         mask = np.ones(pts1.shape[0], np.uint8)
         self._ck(self.lib.icg_fm_ransac(self.h, len(offsets) - 1, _p(offsets), _p(pts1), _p(pts2), C.c_double(thresh),
                                          C.c_double(conf), _p(mask)), "icg_fm_ransac")
@@ -271,9 +256,9 @@ class Context:
 
     def fm_ransac_device(self, offsets, pts1, pts2, thresh=1.5, conf=0.99):
         """icg_fm_ransac_device: the whole RANSAC run of every set in one launch (the kernel the device-resident tracker uses)"""
-        offsets = _i32(offsets)
-        pts1 = _f32(pts1).reshape(-1, 2)
-        pts2 = _f32(pts2).reshape(-1, 2)
+        offsets = i32(offsets)
+        pts1 = f32(pts1).reshape(-1, 2)
+        pts2 = f32(pts2).reshape(-1, 2)
         mask = np.ones(pts1.shape[0], np.uint8)
         self._ck(self.lib.icg_fm_ransac_device(self.h, len(offsets) - 1, _p(offsets), _p(pts1), _p(pts2), C.c_double(thresh),
                                                 C.c_double(conf), _p(mask)), "icg_fm_ransac_device")
@@ -281,12 +266,12 @@ class Context:
 
     # ---- F7
     def detect(self, slots, grid, mask_off, mask_pts, quota, max_per_job):
-        slots = _i32(slots)
+        slots = i32(slots)
         n = len(slots)
         g = DetectGrid(*[int(v) for v in grid])
-        mask_off = _i32(mask_off)
-        mask_pts = _f32(mask_pts).reshape(-1, 2)
-        quota = _i32(quota)
+        mask_off = i32(mask_off)
+        mask_pts = f32(mask_pts).reshape(-1, 2)
+        quota = i32(quota)
         out = np.zeros((n, max_per_job, 2), np.float32)
         cnt = np.zeros(n, np.int32)
         blk = np.zeros((n, max_per_job), np.int32)
@@ -296,58 +281,58 @@ class Context:
 
     # ---- F8
     def triangulate(self, T0_idx, T1_idx, Tcw12, pc0, pc1):
-        Tcw12 = _f64(Tcw12).reshape(-1, 12)
-        pc0 = _f64(pc0).reshape(-1, 3)
-        pc1 = _f64(pc1).reshape(-1, 3)
+        Tcw12 = f64(Tcw12).reshape(-1, 12)
+        pc0 = f64(pc0).reshape(-1, 3)
+        pc1 = f64(pc1).reshape(-1, 3)
         n = pc0.shape[0]
         pw = np.zeros((n, 3), np.float64)
-        self._ck(self.lib.icg_triangulate(self.h, n, _p(_i32(np.broadcast_to(T0_idx, (n,)))),
-                                           _p(_i32(np.broadcast_to(T1_idx, (n,)))), Tcw12.shape[0], _p(Tcw12), _p(pc0),
+        self._ck(self.lib.icg_triangulate(self.h, n, _p(i32(np.broadcast_to(T0_idx, (n,)))),
+                                           _p(i32(np.broadcast_to(T1_idx, (n,)))), Tcw12.shape[0], _p(Tcw12), _p(pc0),
                                            _p(pc1), _p(pw)), "icg_triangulate")
         return pw
 
     # ---- R1/R2
     def reproj_eval(self, obs_soa, idx_i, idx_j, idx_lm, poses, ext, invdepth, td, want_jac=True, huber=0.0):
-        obs_soa = _f64(obs_soa)
+        obs_soa = f64(obs_soa)
         n = obs_soa.shape[1]
-        poses = _f64(poses).reshape(-1, 7)
-        invdepth = _f64(invdepth).reshape(-1)
+        poses = f64(poses).reshape(-1, 7)
+        invdepth = f64(invdepth).reshape(-1)
         r = np.zeros((n, 2))
         J = np.zeros((n, 46)) if want_jac else None
-        self._ck(self.lib.icg_reproj_eval_batch(self.h, n, _p(obs_soa), _p(_i32(idx_i)), _p(_i32(idx_j)), _p(_i32(idx_lm)),
-                                                 poses.shape[0], _p(poses), _p(_f64(ext)), invdepth.shape[0], _p(invdepth),
+        self._ck(self.lib.icg_reproj_eval_batch(self.h, n, _p(obs_soa), _p(i32(idx_i)), _p(i32(idx_j)), _p(i32(idx_lm)),
+                                                 poses.shape[0], _p(poses), _p(f64(ext)), invdepth.shape[0], _p(invdepth),
                                                  C.c_double(td), 1 if want_jac else 0, C.c_double(huber), _p(r), _p(J)),
                  "icg_reproj_eval_batch")
         return r, J
 
     def reproj_set_factors(self, obs_soa, idx_i, idx_j, idx_lm):
-        obs_soa = _f64(obs_soa)
+        obs_soa = f64(obs_soa)
         n = obs_soa.shape[1]
-        self._ck(self.lib.icg_reproj_set_factors(self.h, n, _p(obs_soa), _p(_i32(idx_i)), _p(_i32(idx_j)), _p(_i32(idx_lm))),
+        self._ck(self.lib.icg_reproj_set_factors(self.h, n, _p(obs_soa), _p(i32(idx_i)), _p(i32(idx_j)), _p(i32(idx_lm))),
                  "icg_reproj_set_factors")
         self._nfac = n
 
     def reproj_set_factors_staged(self, obs_soa, idx_i, idx_j, idx_lm):
         """the same upload through icg_reproj_stage_factors / icg_reproj_commit_factors: the factor set is written into the context's pinned
         staging block in place (what the host layer does from its pool threads)"""
-        obs_soa = _f64(obs_soa)
+        obs_soa = f64(obs_soa)
         n = obs_soa.shape[1]
         po, pi = C.c_void_p(), C.c_void_p()
         self._ck(self.lib.icg_reproj_stage_factors(self.h, n, C.byref(po), C.byref(pi)), "icg_reproj_stage_factors")
         if n:
             np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_double)), shape=(15, n))[:] = obs_soa
             idx = np.ctypeslib.as_array(C.cast(pi, C.POINTER(C.c_int32)), shape=(3, n))
-            idx[0], idx[1], idx[2] = _i32(idx_i), _i32(idx_j), _i32(idx_lm)
+            idx[0], idx[1], idx[2] = i32(idx_i), i32(idx_j), i32(idx_lm)
         self._ck(self.lib.icg_reproj_commit_factors(self.h), "icg_reproj_commit_factors")
         self._nfac = n
 
     def reproj_eval_resident(self, poses, ext, invdepth, td, want_jac=True, huber=0.0, fetch=True):
-        poses = _f64(poses).reshape(-1, 7)
-        invdepth = _f64(invdepth).reshape(-1)
+        poses = f64(poses).reshape(-1, 7)
+        invdepth = f64(invdepth).reshape(-1)
         n = self._nfac
         r = np.zeros((n, 2)) if fetch else None
         J = np.zeros((n, 46)) if (fetch and want_jac) else None
-        self._ck(self.lib.icg_reproj_eval_resident(self.h, poses.shape[0], _p(poses), _p(_f64(ext)), invdepth.shape[0],
+        self._ck(self.lib.icg_reproj_eval_resident(self.h, poses.shape[0], _p(poses), _p(f64(ext)), invdepth.shape[0],
                                                     _p(invdepth), C.c_double(td), 1 if want_jac else 0, C.c_double(huber),
                                                     _p(r), _p(J)), "icg_reproj_eval_resident")
         return r, J
@@ -355,18 +340,18 @@ class Context:
     def reproj_accumulate_normal(self, local_size, col_pose, col_ext, col_lm, col_td):
         H = np.zeros((local_size, local_size))
         b = np.zeros(local_size)
-        self._ck(self.lib.icg_reproj_accumulate_normal(self.h, local_size, _p(_i32(col_pose)), int(col_ext), _p(_i32(col_lm)),
+        self._ck(self.lib.icg_reproj_accumulate_normal(self.h, local_size, _p(i32(col_pose)), int(col_ext), _p(i32(col_lm)),
                                                         int(col_td), _p(H), _p(b)), "icg_reproj_accumulate_normal")
         return H, b
 
     # ---- f3
     def reproj_error_batch(self, pose_idx, lm_idx, poses12, pw, pix, max_error, min_depth=1.0, max_depth=200.0):
-        poses12 = _f64(poses12).reshape(-1, 12)
-        pw = _f64(pw).reshape(-1, 3)
-        pix = _f32(pix).reshape(-1, 2)
+        poses12 = f64(poses12).reshape(-1, 12)
+        pw = f64(pw).reshape(-1, 3)
+        pix = f32(pix).reshape(-1, 2)
         n = pix.shape[0]
         err, good = np.zeros(n), np.zeros(n, np.uint8)
-        self._ck(self.lib.icg_reproj_error_batch(self.h, n, _p(_i32(pose_idx)), _p(_i32(lm_idx)), poses12.shape[0], _p(poses12), pw.shape[0],
+        self._ck(self.lib.icg_reproj_error_batch(self.h, n, _p(i32(pose_idx)), _p(i32(lm_idx)), poses12.shape[0], _p(poses12), pw.shape[0],
                                                   _p(pw), _p(pix), C.c_double(max_error), C.c_double(min_depth), C.c_double(max_depth), _p(err),
                                                   _p(good)), "icg_reproj_error_batch")
         return err, good
@@ -374,20 +359,20 @@ class Context:
     # ---- f1
     def reproj_schur(self, P, col_pose, col_ext, col_td, active=None, reassemble=True, damp=0.0, min_diag=1e-6, max_diag=1e32):
         S, s, dg, cost = np.zeros((P, P)), np.zeros(P), np.zeros(P), np.zeros(1)
-        act = None if active is None else np.ascontiguousarray(active, np.uint8)
-        self._ck(self.lib.icg_reproj_schur(self.h, int(P), _p(_i32(col_pose)), int(col_ext), int(col_td), _p(act), 1 if reassemble else 0,
+        act = None if active is None else u8(active)
+        self._ck(self.lib.icg_reproj_schur(self.h, int(P), _p(i32(col_pose)), int(col_ext), int(col_td), _p(act), 1 if reassemble else 0,
                                             C.c_double(damp), C.c_double(min_diag), C.c_double(max_diag), _p(S), _p(s), _p(dg), _p(cost)),
                  "icg_reproj_schur")
         return S, s, dg, float(cost[0])
 
     def reproj_backsub(self, P, delta_c, n_lm):
         out, terms = np.zeros(n_lm), np.zeros(2)
-        self._ck(self.lib.icg_reproj_backsub(self.h, int(P), _p(_f64(delta_c)), _p(out), _p(terms)), "icg_reproj_backsub")
+        self._ck(self.lib.icg_reproj_backsub(self.h, int(P), _p(f64(delta_c)), _p(out), _p(terms)), "icg_reproj_backsub")
         return out, terms
 
     def reproj_cost(self, active=None):
         cost = np.zeros(1)
-        act = None if active is None else np.ascontiguousarray(active, np.uint8)
+        act = None if active is None else u8(active)
         self._ck(self.lib.icg_reproj_cost(self.h, _p(act), _p(cost)), "icg_reproj_cost")
         return float(cost[0])
 
@@ -413,22 +398,27 @@ class Context:
 
     # ---- f1, many windows per launch
     def reproj_set_windows(self, fac_off, lm_off):
-        fac_off, lm_off = _i32(fac_off), _i32(lm_off)
+        fac_off, lm_off = i32(fac_off), i32(lm_off)
         self._nwin = len(fac_off) - 1
         self._ck(self.lib.icg_reproj_set_windows(self.h, self._nwin, _p(fac_off), _p(lm_off)), "icg_reproj_set_windows")
 
     def reproj_eval_windows(self, poses, ext, invdepth, td, want_jac=True, huber=0.0):
-        poses, ext, invdepth, td = _f64(poses).reshape(-1, 7), _f64(ext).reshape(-1, 7), _f64(invdepth).reshape(-1), _f64(td).reshape(-1)
+        poses, ext, invdepth, td = f64(poses).reshape(-1, 7), f64(ext).reshape(-1, 7), f64(invdepth).reshape(-1), f64(td).reshape(-1)
         self._ck(self.lib.icg_reproj_eval_windows(self.h, poses.shape[0], _p(poses), _p(ext), invdepth.shape[0], _p(invdepth), _p(td),
                                                    1 if want_jac else 0, C.c_double(huber)), "icg_reproj_eval_windows")
+
+    def _window_flags(self, active, reassemble, damp):
+        """the per-factor mask (None = NULL: every factor) and the per-window reassemble flags (None: all) and dampings (None: 0) of the
+        reproj_schur_windows* entries as the arrays they take"""
+        W = self._nwin
+        return (None if active is None else u8(active), np.ones(W, np.uint8) if reassemble is None else u8(reassemble),
+                np.zeros(W) if damp is None else f64(damp))
 
     def reproj_schur_windows(self, P, col_pose, col_ext, col_td, active=None, reassemble=None, damp=None, min_diag=1e-6, max_diag=1e32):
         W = self._nwin
         S, s, dg, cost = np.zeros((W, P, P)), np.zeros((W, P)), np.zeros((W, P)), np.zeros(W)
-        act = None if active is None else np.ascontiguousarray(active, np.uint8)
-        re = np.ones(W, np.uint8) if reassemble is None else np.ascontiguousarray(reassemble, np.uint8)
-        dm = np.zeros(W) if damp is None else _f64(damp)
-        self._ck(self.lib.icg_reproj_schur_windows(self.h, int(P), _p(_i32(col_pose)), _p(_i32(col_ext)), _p(_i32(col_td)), _p(act), _p(re), _p(dm),
+        act, re, dm = self._window_flags(active, reassemble, damp)
+        self._ck(self.lib.icg_reproj_schur_windows(self.h, int(P), _p(i32(col_pose)), _p(i32(col_ext)), _p(i32(col_td)), _p(act), _p(re), _p(dm),
                                                     C.c_double(min_diag), C.c_double(max_diag), _p(S), _p(s), _p(dg), _p(cost)),
                  "icg_reproj_schur_windows")
         return S, s, dg, cost
@@ -441,11 +431,9 @@ class Context:
         16 x 16 tiles on and below the diagonal are defined)"""
         W = self._nwin
         s, dg, cost = np.zeros((W, P)), np.zeros((W, P)), np.zeros(W)
-        act = None if active is None else np.ascontiguousarray(active, np.uint8)
-        re = np.ones(W, np.uint8) if reassemble is None else np.ascontiguousarray(reassemble, np.uint8)
-        dm = np.zeros(W) if damp is None else _f64(damp)
+        act, re, dm = self._window_flags(active, reassemble, damp)
         view = C.POINTER(C.c_double)()
-        self._ck(self.lib.icg_reproj_schur_windows_view(self.h, int(P), _p(_i32(col_pose)), _p(_i32(col_ext)), _p(_i32(col_td)), _p(act), _p(re), _p(dm),
+        self._ck(self.lib.icg_reproj_schur_windows_view(self.h, int(P), _p(i32(col_pose)), _p(i32(col_ext)), _p(i32(col_td)), _p(act), _p(re), _p(dm),
                                                          C.c_double(min_diag), C.c_double(max_diag), C.byref(view), _p(s), _p(dg), _p(cost)),
                  "icg_reproj_schur_windows_view")
         S = np.ctypeslib.as_array(view, shape=(W, P, P)).copy()
@@ -455,10 +443,8 @@ class Context:
         """icg_reproj_schur_windows_resident: the reduced systems stay on the device for reproj_solve_windows -> (s, diag_cc, cost)"""
         W = self._nwin
         s, dg, cost = np.zeros((W, P)), np.zeros((W, P)), np.zeros(W)
-        act = None if active is None else np.ascontiguousarray(active, np.uint8)
-        re = np.ones(W, np.uint8) if reassemble is None else np.ascontiguousarray(reassemble, np.uint8)
-        dm = np.zeros(W) if damp is None else _f64(damp)
-        self._ck(self.lib.icg_reproj_schur_windows_resident(self.h, int(P), _p(_i32(col_pose)), _p(_i32(col_ext)), _p(_i32(col_td)), _p(act), _p(re),
+        act, re, dm = self._window_flags(active, reassemble, damp)
+        self._ck(self.lib.icg_reproj_schur_windows_resident(self.h, int(P), _p(i32(col_pose)), _p(i32(col_ext)), _p(i32(col_td)), _p(act), _p(re),
                                                              _p(dm), C.c_double(min_diag), C.c_double(max_diag), _p(s), _p(dg), _p(cost)),
                  "icg_reproj_schur_windows_resident")
         return s, dg, cost
@@ -466,10 +452,10 @@ class Context:
     def reproj_solve_windows(self, P, Pw, solve, dd, rhs, n_lm, host_part_new=None, host_S=None):
         """icg_reproj_solve_windows: host_S = the packed lower triangles of the flagged windows, flat -> (delta_c W x P, status, delta_l, lm_terms)"""
         W = self._nwin
-        Pw, sv = _i32(Pw).reshape(W), np.ascontiguousarray(solve, np.uint8).reshape(W)
-        new = None if host_part_new is None else np.ascontiguousarray(host_part_new, np.uint8).reshape(W)
-        hs = None if host_S is None else _f64(host_S).reshape(-1)
-        dd, rhs = _f64(dd).reshape(W, P), _f64(rhs).reshape(W, P)
+        Pw, sv = i32(Pw).reshape(W), u8(solve).reshape(W)
+        new = None if host_part_new is None else u8(host_part_new).reshape(W)
+        hs = None if host_S is None else f64(host_S).reshape(-1)
+        dd, rhs = f64(dd).reshape(W, P), f64(rhs).reshape(W, P)
         dc, st, dl, terms = np.zeros((W, P)), np.zeros(W, np.int32), np.zeros(n_lm), np.zeros((W, 2))
         self._ck(self.lib.icg_reproj_solve_windows(self.h, int(P), _p(Pw), _p(sv), _p(new), _p(hs), _p(dd), _p(rhs), _p(dc), _p(st), _p(dl), _p(terms)),
                  "icg_reproj_solve_windows")
@@ -480,34 +466,49 @@ class Context:
         return self.lib.icg_reproj_host_parts_build(self.h, int(P), _p(Pw), _p(rebuild), _p(blk_off), _p(nr), _p(nf), _p(cols), _p(jac_off), _p(J), _p(r),
                                                     _p(host_s), _p(host_diag), _p(part_out))
 
-    def reproj_host_parts_build(self, P, Pw, windows, rebuild=None, host_s=None, host_diag=None):
-        """icg_reproj_host_parts_build.  windows: per window a list of blocks (J nr x nf, r, cols, keep); keep: the block goes up as -1 (J gives
-        its shape only).  -> (host_s W x P, host_diag W x P, the packed parts of the rebuilt windows as a list, None for the others)"""
-        W = self._nwin
-        Pw = _i32(Pw).reshape(W)
-        rb = np.ones(W, np.uint8) if rebuild is None else np.ascontiguousarray(rebuild, np.uint8).reshape(W)
+    def _pack_host_blocks(self, windows):
+        """the flat block arrays of the host-parts entries from per-window lists of blocks: (J nr x nf, r, cols, keep) or
+        ("prior", p, prior_cols, cols, how) as reproj_host_parts_build_prior describes them
+        -> (blk_off, nr, nf, cols, jac_off, J | None, r, prior_of, prior_cols | None)"""
         blocks = [b for win in windows for b in win]
-        blk_off = _i32(np.concatenate([[0], np.cumsum([len(win) for win in windows])]))
-        nr, nf = _i32([np.shape(b[0])[0] for b in blocks]), _i32([np.shape(b[0])[1] for b in blocks])
-        cols = _i32(np.concatenate([_i32(b[2]).reshape(-1) for b in blocks])) if blocks else _i32([])
-        r = _f64(np.concatenate([_f64(b[1]).reshape(-1) for b in blocks])) if blocks else _f64([])
+        blk_off = i32(np.concatenate([[0], np.cumsum([len(win) for win in windows])]))
+        is_prior = [isinstance(b[0], str) for b in blocks]
+        nr = i32([self._marg_r[b[1]] if pr else np.shape(b[0])[0] for b, pr in zip(blocks, is_prior)])
+        nf = i32([len(b[3]) if pr else np.shape(b[0])[1] for b, pr in zip(blocks, is_prior)])
+        cols = i32(np.concatenate([i32(b[3] if pr else b[2]).reshape(-1) for b, pr in zip(blocks, is_prior)])) if blocks else i32([])
+        r = f64(np.concatenate([np.full(n, np.nan) if pr else f64(b[1]).reshape(-1) for b, pr, n in zip(blocks, is_prior, nr)])) if blocks else f64([])
+        prior_of = i32([b[1] if pr else -1 for b, pr in zip(blocks, is_prior)])
+        pcs = [i32(b[2]).reshape(-1) for b, pr in zip(blocks, is_prior) if pr]
+        prior_cols = i32(np.concatenate(pcs)) if pcs else None
         jac_off, Js, at = np.full(len(blocks), -1, np.int64), [], 0
-        for k, b in enumerate(blocks):
-            if not b[3]:
+        for k, (b, pr) in enumerate(zip(blocks, is_prior)):
+            if pr and isinstance(b[4], str):
+                jac_off[k] = HP_JAC_FROM_PRIOR if b[4] == "gather" else -1
+            elif pr or not b[3]:
                 jac_off[k] = at
-                Js.append(_f64(b[0]).reshape(-1))
+                Js.append(f64(b[4] if pr else b[0]).reshape(-1))
                 at += Js[-1].size
-        J = _f64(np.concatenate(Js)) if Js else None
+        J = f64(np.concatenate(Js)) if Js else None
+        return blk_off, nr, nf, cols, jac_off, J, r, prior_of, prior_cols
+
+    def _host_parts_build(self, entry, what, P, Pw, windows, rebuild, host_s, host_diag, with_priors):
+        """the list forms of reproj_host_parts_build / _prior: pack the blocks, call entry, cut the packed parts of the rebuilt windows apart"""
+        W = self._nwin
+        Pw = i32(Pw).reshape(W)
+        rb = np.ones(W, np.uint8) if rebuild is None else u8(rebuild).reshape(W)
+        *flat, prior_of, prior_cols = self._pack_host_blocks(windows)
         s = np.zeros((W, P)) if host_s is None else host_s
         dg = np.zeros((W, P)) if host_diag is None else host_diag
         sizes = [int(Pw[w]) * (int(Pw[w]) + 1) // 2 if rb[w] else 0 for w in range(W)]
         part = np.zeros(max(1, sum(sizes)))
-        self._ck(self.reproj_host_parts_build_raw(P, Pw, rb, blk_off, nr, nf, cols, jac_off, J, r, s, dg, part), "icg_reproj_host_parts_build")
-        parts, at = [], 0
-        for w in range(W):
-            parts.append(part[at:at + sizes[w]].copy() if rb[w] else None)
-            at += sizes[w]
-        return s, dg, parts
+        self._ck(entry(P, Pw, rb, *flat, s, dg, part, *((prior_of, prior_cols) if with_priors else ())), what)
+        ends = np.cumsum(sizes)
+        return s, dg, [part[e - n:e].copy() if rb[w] else None for w, (n, e) in enumerate(zip(sizes, ends))]
+
+    def reproj_host_parts_build(self, P, Pw, windows, rebuild=None, host_s=None, host_diag=None):
+        """icg_reproj_host_parts_build.  windows: per window a list of blocks (J nr x nf, r, cols, keep); keep: the block goes up as -1 (J gives
+        its shape only).  -> (host_s W x P, host_diag W x P, the packed parts of the rebuilt windows as a list, None for the others)"""
+        return self._host_parts_build(self.reproj_host_parts_build_raw, "icg_reproj_host_parts_build", P, Pw, windows, rebuild, host_s, host_diag, False)
 
     def reproj_host_parts_build_prior_raw(self, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, prior_of, prior_cols):
         """icg_reproj_host_parts_build_prior on the caller's arrays (None = NULL; the outputs are written in place) -> the return code"""
@@ -525,43 +526,12 @@ class Context:
         reproj_host_parts_build, a prior block is ("prior", p, prior_cols, cols, how): prior p of the resident set (marg_prior_set), how =
         "gather" (ICG_HP_JAC_FROM_PRIOR), "keep" (-1) or the Jacobian to upload.  The prior blocks' slots in r are filled with NaN: they
         are not read.  -> (host_s, host_diag, parts) as reproj_host_parts_build"""
-        W = self._nwin
-        Pw = _i32(Pw).reshape(W)
-        rb = np.ones(W, np.uint8) if rebuild is None else np.ascontiguousarray(rebuild, np.uint8).reshape(W)
-        blocks = [b for win in windows for b in win]
-        blk_off = _i32(np.concatenate([[0], np.cumsum([len(win) for win in windows])]))
-        is_prior = [isinstance(b[0], str) for b in blocks]
-        nr = _i32([self._marg_r[b[1]] if pr else np.shape(b[0])[0] for b, pr in zip(blocks, is_prior)])
-        nf = _i32([len(b[3]) if pr else np.shape(b[0])[1] for b, pr in zip(blocks, is_prior)])
-        cols = _i32(np.concatenate([_i32(b[3] if pr else b[2]).reshape(-1) for b, pr in zip(blocks, is_prior)])) if blocks else _i32([])
-        r = _f64(np.concatenate([np.full(n, np.nan) if pr else _f64(b[1]).reshape(-1) for b, pr, n in zip(blocks, is_prior, nr)])) if blocks else _f64([])
-        prior_of = _i32([b[1] if pr else -1 for b, pr in zip(blocks, is_prior)])
-        pcs = [_i32(b[2]).reshape(-1) for b, pr in zip(blocks, is_prior) if pr]
-        prior_cols = _i32(np.concatenate(pcs)) if pcs else None
-        jac_off, Js, at = np.full(len(blocks), -1, np.int64), [], 0
-        for k, (b, pr) in enumerate(zip(blocks, is_prior)):
-            if pr and isinstance(b[4], str):
-                jac_off[k] = HP_JAC_FROM_PRIOR if b[4] == "gather" else -1
-            elif pr or not b[3]:
-                jac_off[k] = at
-                Js.append(_f64(b[4] if pr else b[0]).reshape(-1))
-                at += Js[-1].size
-        J = _f64(np.concatenate(Js)) if Js else None
-        s = np.zeros((W, P)) if host_s is None else host_s
-        dg = np.zeros((W, P)) if host_diag is None else host_diag
-        sizes = [int(Pw[w]) * (int(Pw[w]) + 1) // 2 if rb[w] else 0 for w in range(W)]
-        part = np.zeros(max(1, sum(sizes)))
-        self._ck(self.reproj_host_parts_build_prior_raw(P, Pw, rb, blk_off, nr, nf, cols, jac_off, J, r, s, dg, part, prior_of, prior_cols),
-                 "icg_reproj_host_parts_build_prior")
-        parts, at = [], 0
-        for w in range(W):
-            parts.append(part[at:at + sizes[w]].copy() if rb[w] else None)
-            at += sizes[w]
-        return s, dg, parts
+        return self._host_parts_build(self.reproj_host_parts_build_prior_raw, "icg_reproj_host_parts_build_prior", P, Pw, windows, rebuild, host_s, host_diag,
+                                      True)
 
     def reproj_backsub_windows(self, P, delta_c, n_lm):
         out, terms = np.zeros(n_lm), np.zeros((self._nwin, 2))
-        self._ck(self.lib.icg_reproj_backsub_windows(self.h, int(P), _p(_f64(delta_c)), _p(out), _p(terms)), "icg_reproj_backsub_windows")
+        self._ck(self.lib.icg_reproj_backsub_windows(self.h, int(P), _p(f64(delta_c)), _p(out), _p(terms)), "icg_reproj_backsub_windows")
         return out, terms
 
     def reproj_landmark_diag_windows(self, n_lm):
@@ -582,36 +552,36 @@ class Context:
 
     def reproj_cost_windows(self, active=None):
         cost = np.zeros(self._nwin)
-        act = None if active is None else np.ascontiguousarray(active, np.uint8)
+        act = None if active is None else u8(active)
         self._ck(self.lib.icg_reproj_cost_windows(self.h, _p(act), _p(cost)), "icg_reproj_cost_windows")
         return cost
 
     # ---- P1
     def preint_batch(self, variant, offsets, imu, state0, params, want_pn=True):
         """icg_preint_batch -> (cur n x 16, delta n x 16, jac n x 15 x 15, cov n x 15 x 15, dt n, pn total x 4 or None without want_pn)"""
-        offsets = _i32(offsets)
+        offsets = i32(offsets)
         n = len(offsets) - 1
-        imu = _f64(imu).reshape(-1, 8)
-        state0 = _f64(state0).reshape(n, 16)
+        imu = f64(imu).reshape(-1, 8)
+        state0 = f64(state0).reshape(n, 16)
         cur = np.zeros((n, 16))
         delta = np.zeros((n, 16))
         jac = np.zeros((n, 15, 15))
         cov = np.zeros((n, 15, 15))
         dt = np.zeros(n)
         pn = np.zeros((imu.shape[0], 4)) if want_pn else None
-        self._ck(self.lib.icg_preint_batch(self.h, int(variant), n, _p(offsets), _p(imu), _p(state0), _p(_f64(params)),
+        self._ck(self.lib.icg_preint_batch(self.h, int(variant), n, _p(offsets), _p(imu), _p(state0), _p(f64(params)),
                                             _p(cur), _p(delta), _p(jac), _p(cov), _p(dt), _p(pn)), "icg_preint_batch")
         return cur, delta, jac, cov, dt, pn
 
     # ---- P2
     def preint_evaluate_batch(self, variant, delta, jac, cov, dt, env, points, pn_offsets=None, pn=None, want_jac=True):
         """icg_preint_evaluate_batch -> (residuals n x 15, jacobians n x 480 or None, sqrt_info n x 15 x 15, status n)"""
-        points = _f64(points).reshape(-1, 32)
+        points = f64(points).reshape(-1, 32)
         n = points.shape[0]
-        delta, jac, cov = _f64(delta).reshape(n, 16), _f64(jac).reshape(n, 225), _f64(cov).reshape(n, 225)
-        dt, env = _f64(dt).reshape(n), _f64(env).reshape(n, 4)
-        po = None if pn_offsets is None else _i32(pn_offsets)
-        pnr = None if pn is None else _f64(pn).reshape(-1, 4)
+        delta, jac, cov = f64(delta).reshape(n, 16), f64(jac).reshape(n, 225), f64(cov).reshape(n, 225)
+        dt, env = f64(dt).reshape(n), f64(env).reshape(n, 4)
+        po = None if pn_offsets is None else i32(pn_offsets)
+        pnr = None if pn is None else f64(pn).reshape(-1, 4)
         res = np.zeros((n, 15))
         J = np.zeros((n, 480)) if want_jac else None
         S = np.zeros((n, 15, 15))
@@ -622,12 +592,12 @@ class Context:
 
     def preint_set(self, variant, delta, jac, sqrt_info, dt, env, q_nn, pn_offsets=None, pn=None):
         """icg_preint_set: len(variant) factors become resident (variant per factor; sqrt_info and q_nn are the host's)"""
-        variant = _i32(variant).reshape(-1)
+        variant = i32(variant).reshape(-1)
         n = len(variant)
-        delta, jac, sqrt_info = _f64(delta).reshape(n, 16), _f64(jac).reshape(n, 225), _f64(sqrt_info).reshape(n, 225)
-        dt, env, q_nn = _f64(dt).reshape(n), _f64(env).reshape(n, 4), _f64(q_nn).reshape(n, 4)
-        po = None if pn_offsets is None else _i32(pn_offsets)
-        pnr = None if pn is None else _f64(pn).reshape(-1, 4)
+        delta, jac, sqrt_info = f64(delta).reshape(n, 16), f64(jac).reshape(n, 225), f64(sqrt_info).reshape(n, 225)
+        dt, env, q_nn = f64(dt).reshape(n), f64(env).reshape(n, 4), f64(q_nn).reshape(n, 4)
+        po = None if pn_offsets is None else i32(pn_offsets)
+        pnr = None if pn is None else f64(pn).reshape(-1, 4)
         self._preint_n = 0
         self._ck(self.lib.icg_preint_set(self.h, n, _p(variant), _p(delta), _p(jac), _p(sqrt_info), _p(dt), _p(env), _p(q_nn), _p(po), _p(pnr)),
                  "icg_preint_set")
@@ -636,7 +606,7 @@ class Context:
     def preint_evaluate_resident(self, points, q_corr, want_jac=True):
         """icg_preint_evaluate_resident: residuals (and Jacobians) stay on the device -> sq_norm (r . r per factor)"""
         n = getattr(self, "_preint_n", 0)
-        points, q_corr = _f64(points).reshape(-1, 32), _f64(q_corr).reshape(-1, 4)
+        points, q_corr = f64(points).reshape(-1, 32), f64(q_corr).reshape(-1, 4)
         if n and (points.shape[0] != n or q_corr.shape[0] != n):
             raise IcgError(f"preint_evaluate_resident: {points.shape[0]} points and {q_corr.shape[0]} quaternions, the resident set has {n} factors")
         sq = np.zeros(max(n, 1))
@@ -654,8 +624,8 @@ class Context:
     # ---- M4
     def marg_prior_set(self, r, block_off, block_size, block_index, x0, J0, e0):
         """icg_marg_prior_set: the priors of len(r) windows become resident (x0 / J0 / e0: flat arrays, window after window)"""
-        r, block_off, block_size, block_index = _i32(r).reshape(-1), _i32(block_off).reshape(-1), _i32(block_size).reshape(-1), _i32(block_index).reshape(-1)
-        x0, J0, e0 = _f64(x0).reshape(-1), _f64(J0).reshape(-1), _f64(e0).reshape(-1)
+        r, block_off, block_size, block_index = i32(r).reshape(-1), i32(block_off).reshape(-1), i32(block_size).reshape(-1), i32(block_index).reshape(-1)
+        x0, J0, e0 = f64(x0).reshape(-1), f64(J0).reshape(-1), f64(e0).reshape(-1)
         self._marg = None
         self._ck(self.lib.icg_marg_prior_set(self.h, len(r), _p(r), _p(block_off), _p(block_size), _p(block_index), _p(x0), _p(J0), _p(e0)),
                  "icg_marg_prior_set")
@@ -666,7 +636,7 @@ class Context:
     def marg_prior_evaluate(self, x, want_jac=False, want_grad=False, want_sq_norm=False):
         """icg_marg_prior_evaluate -> (residuals, jacobians | None, gradient | None, sq_norm | None), flat, window after window"""
         n, nr, nx, njac = getattr(self, "_marg", None) or (0, 0, 0, 0)
-        x = _f64(x).reshape(-1)
+        x = f64(x).reshape(-1)
         if n and x.shape[0] != nx:
             raise IcgError(f"marg_prior_evaluate: x has {x.shape[0]} values, the resident set takes {nx}")
         res = np.zeros(nr)
@@ -679,7 +649,7 @@ class Context:
     def marg_prior_evaluate_resident(self, x):
         """icg_marg_prior_evaluate_resident: the residuals stay on the device for reproj_host_parts_build_prior -> sq_norm (e . e per window)"""
         n, nr, nx, njac = getattr(self, "_marg", None) or (0, 0, 0, 0)
-        x = _f64(x).reshape(-1)
+        x = f64(x).reshape(-1)
         if n and x.shape[0] != nx:
             raise IcgError(f"marg_prior_evaluate_resident: x has {x.shape[0]} values, the resident set takes {nx}")
         sq = np.zeros(max(n, 1))
@@ -690,8 +660,8 @@ class Context:
     def marg_linearize_batch(self, P, m, H, b, eps=1e-8, want_Hp=True, want_bp=True, want_evals=True, want_min_ev=True, want_status=True):
         """icg_marg_linearize_batch: H / b flat, window after window -> dict(J0, e0, Hp, bp, evals, min_ev_m, status), flat (None where
         not asked for)"""
-        P, m = _i32(P).reshape(-1), _i32(m).reshape(-1)
-        H, b = _f64(H).reshape(-1), _f64(b).reshape(-1)
+        P, m = i32(P).reshape(-1), i32(m).reshape(-1)
+        H, b = f64(H).reshape(-1), f64(b).reshape(-1)
         n = len(P)
         if len(m) != n or H.shape[0] != int((P.astype(np.int64) ** 2).sum()) or b.shape[0] != int(P.sum()):
             raise IcgError("marg_linearize_batch: P, m, H, b do not describe the same windows")
@@ -709,8 +679,8 @@ class Context:
                                   want_min_ev=True, want_status=True):
         """icg_marg_linearize_batch_keep: marg_linearize_batch with J0 / e0 also left on the device -> (dict as there, keep id); J0 / e0
         are None when not asked for (not transferred)"""
-        P, m = _i32(P).reshape(-1), _i32(m).reshape(-1)
-        H, b = _f64(H).reshape(-1), _f64(b).reshape(-1)
+        P, m = i32(P).reshape(-1), i32(m).reshape(-1)
+        H, b = f64(H).reshape(-1), f64(b).reshape(-1)
         n = len(P)
         if len(m) != n or H.shape[0] != int((P.astype(np.int64) ** 2).sum()) or b.shape[0] != int(P.sum()):
             raise IcgError("marg_linearize_batch_keep: P, m, H, b do not describe the same windows")
@@ -729,8 +699,8 @@ class Context:
                                 want_min_ev=True, want_status=True, want_H=True):
         """icg_marg_linearize_resident: system k is window win[k] of the resident reduced systems (reproj_schur_windows_resident, common width
         P) plus its resident host part; b flat -> dict(J0, e0, Hp, bp, evals, min_ev_m, status, H), flat in list order; keep: -> (dict, keep id)"""
-        win, Pw, m = _i32(win).reshape(-1), _i32(Pw).reshape(-1), _i32(m).reshape(-1)
-        b = _f64(b).reshape(-1)
+        win, Pw, m = i32(win).reshape(-1), i32(Pw).reshape(-1), i32(m).reshape(-1)
+        b = f64(b).reshape(-1)
         n = len(win)
         if len(Pw) != n or len(m) != n or b.shape[0] != int(Pw.sum()):
             raise IcgError("marg_linearize_resident: win, Pw, m, b do not describe the same systems")
@@ -753,11 +723,11 @@ class Context:
     def marg_prior_set_from_kept(self, keep_id, src, r, block_off, block_size, block_index, x0, J0_host=None, e0_host=None):
         """icg_marg_prior_set_from_kept: marg_prior_set with window w's J0 / e0 taken from window src[w] of the kept linearization
         keep_id (any context of this device), or, for src[w] == -1, from J0_host / e0_host (those windows only, in set order)"""
-        src, r = _i32(src).reshape(-1), _i32(r).reshape(-1)
-        block_off, block_size, block_index = _i32(block_off).reshape(-1), _i32(block_size).reshape(-1), _i32(block_index).reshape(-1)
-        x0 = _f64(x0).reshape(-1)
-        J0_host = None if J0_host is None else _f64(J0_host).reshape(-1)
-        e0_host = None if e0_host is None else _f64(e0_host).reshape(-1)
+        src, r = i32(src).reshape(-1), i32(r).reshape(-1)
+        block_off, block_size, block_index = i32(block_off).reshape(-1), i32(block_size).reshape(-1), i32(block_index).reshape(-1)
+        x0 = f64(x0).reshape(-1)
+        J0_host = None if J0_host is None else f64(J0_host).reshape(-1)
+        e0_host = None if e0_host is None else f64(e0_host).reshape(-1)
         self._marg = None
         self._ck(self.lib.icg_marg_prior_set_from_kept(self.h, C.c_uint64(keep_id), len(r), _p(src), _p(r), _p(block_off), _p(block_size),
                                                        _p(block_index), _p(x0), _p(J0_host), _p(e0_host)), "icg_marg_prior_set_from_kept")
@@ -769,8 +739,8 @@ class Context:
     def chol_solve_batch(self, n, A, b, want_L=True, want_status=True):
         """icg_chol_solve_batch: A (n[k] x n[k] row-major, lower triangle read) and b flat, system after system -> (x, L | None, status | None),
         flat; L is zero above the diagonals"""
-        n = _i32(n).reshape(-1)
-        A, b = _f64(A).reshape(-1), _f64(b).reshape(-1)
+        n = i32(n).reshape(-1)
+        A, b = f64(A).reshape(-1), f64(b).reshape(-1)
         if A.shape[0] != int((n.astype(np.int64).clip(0) ** 2).sum()) or b.shape[0] != int(n.clip(0).sum()):
             raise IcgError("chol_solve_batch: n, A, b do not describe the same systems")
         x = np.zeros(b.shape[0])
@@ -781,19 +751,19 @@ class Context:
 
     # ---- f4
     def ins_mechanize_batch(self, offsets, imu, cfg8, states23, want_traj=True):
-        offsets = _i32(offsets)
+        offsets = i32(offsets)
         n = len(offsets) - 1
-        imu = _f64(imu).reshape(-1, 8)
-        st = _f64(states23).reshape(n, 23).copy()
+        imu = f64(imu).reshape(-1, 8)
+        st = f64(states23).reshape(n, 23).copy()
         traj = np.zeros((imu.shape[0], 23)) if want_traj else None
-        self._ck(self.lib.icg_ins_mechanize_batch(self.h, n, _p(offsets), _p(imu), _p(_f64(cfg8)), _p(st), _p(traj)),
+        self._ck(self.lib.icg_ins_mechanize_batch(self.h, n, _p(offsets), _p(imu), _p(f64(cfg8)), _p(st), _p(traj)),
                  "icg_ins_mechanize_batch")
         return st, traj
 
     def ins_camera_pose_batch(self, brackets16, interp, pose_b_c12, times):
-        b = _f64(brackets16).reshape(-1, 16)
+        b = f64(brackets16).reshape(-1, 16)
         n = b.shape[0]
         out = np.zeros((n, 12))
-        self._ck(self.lib.icg_ins_camera_pose_batch(self.h, n, _p(b), _p(_i32(interp)), _p(_f64(pose_b_c12)), _p(_f64(times)), _p(out)),
+        self._ck(self.lib.icg_ins_camera_pose_batch(self.h, n, _p(b), _p(i32(interp)), _p(f64(pose_b_c12)), _p(f64(times)), _p(out)),
                  "icg_ins_camera_pose_batch")
         return out

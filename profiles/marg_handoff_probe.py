@@ -7,34 +7,29 @@ set goes through icg_marg_prior_set_from_kept.  The two modes ALTERNATE in one p
 run behind an untimed one; per phase best and median over the runs, and the device time of the set's store kernel from the context's
 profiler.  By the project's rule a margin below the scatter (max - min over the runs) of either mode is "not a result".
 `python profiles/marg_handoff_probe.py [out.json] [--cpus 2] [--runs 3]`; --cpus N confines the process to N of the CPUs it may run on
-before any library is loaded.  Run by hand; not part of bench.py."""
+before any library is loaded.  Every shape is a leg: a child process of its own under a time limit; the first leg that fails ends the run.
+Run by hand; not part of bench.py."""
 import ctypes as C
-import json
-import os
-import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "ic-gvins_amd"), ROOT]
+import probe_common as pc
+from ctypes_util import ErrBuf, bits, ptr
 
 PHASES = ("linearize_ms", "set_ms", "resident_evaluate_ms")
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+SHAPES = {"C2": ("C2: P = 157, m = 15; 9 x (7, 9) + 7 + 1", 157, 15, "C2_SIZES"), "C4": ("C4: P = 232, m = 15; 14 x (7, 9) + 7 + 1", 232, 15, "C4_SIZES")}
+LEG_LIMIT_S = 60  # the whole probe, both shapes in one process at its defaults, took 4.7 s: twice that, rounded up to a full minute
 
 
 def chain(lib, mode, lin_args, set_args, x, n):
     P, m, H, b = lin_args
     block_off, block_size, block_index, x0 = set_args
     sq, handed, ms, kern = np.zeros(n), np.zeros(1, np.int32), np.zeros(3), np.zeros(1)
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_marg_handoff_chain(mode, n, _p(P), _p(m), _p(H), _p(b), C.c_double(1e-8), _p(block_off), _p(block_size), _p(block_index),
-                                             _p(x0), _p(x), 1, _p(sq), _p(handed), _p(ms), _p(kern), err, 512)
+    err = ErrBuf()
+    rc = lib.icgh_backend_marg_handoff_chain(mode, n, ptr(P), ptr(m), ptr(H), ptr(b), C.c_double(1e-8), ptr(block_off), ptr(block_size), ptr(block_index),
+                                             ptr(x0), ptr(x), 1, ptr(sq), ptr(handed), ptr(ms), ptr(kern), *err.args)
     if rc != 0:
-        raise RuntimeError(f"icgh_backend_marg_handoff_chain mode {mode} rc={rc}: {err.value.decode()}")
+        raise RuntimeError(f"icgh_backend_marg_handoff_chain mode {mode} rc={rc}: {err.text()}")
     return sq, int(handed[0]), ms, float(kern[0])
 
 
@@ -56,44 +51,30 @@ def measure_shape(lib, name, P, m, sizes, runs, n_windows=256):
             sq, handed, ms, kern = chain(lib, mode, lin_args, set_args, x, n_windows)
             assert handed == (n_windows if mode else 0), (key, handed)
             sq_ref = sq if sq_ref is None else sq_ref
-            assert np.array_equal(sq.view(np.uint64), sq_ref.view(np.uint64)), key  # the same priors whichever way they came
+            assert np.array_equal(bits(sq), bits(sq_ref)), key  # the same priors whichever way they came
             rec[key].append(dict(zip(PHASES, ms), chain_ms=float(ms.sum()), store_kernel_ms=kern))
     for key, rows in rec.items():
-        out[key] = {}
-        for k in PHASES + ("chain_ms", "store_kernel_ms"):
-            v = [row[k] for row in rows]
-            out[key][k] = {"best": round(min(v), 3), "median": round(statistics.median(v), 3), "scatter": round(max(v) - min(v), 3)}
+        out[key] = {k: pc.stats([row[k] for row in rows]) for k in PHASES + ("chain_ms", "store_kernel_ms")}
     verdict = {}
     for k in ("set_ms", "chain_ms"):
         s, h = out["shipped"][k], out["handed_off"][k]
         margin = s["median"] - h["median"]
         verdict[k] = {"margin_ms_median": round(margin, 3),
-                      "result": "handed off is faster" if margin > max(s["scatter"], h["scatter"]) else
-                                ("shipped is faster" if -margin > max(s["scatter"], h["scatter"]) else "not a result")}
+                      "result": pc.verdict(margin, max(s["scatter"], h["scatter"]), "handed off is faster", "shipped is faster", "not a result")}
     out["shipped_minus_handed_off"] = verdict
     return out
 
 
-def measure(runs=3):
+def run_leg(leg, opt):
     import harness as H
     import marg_factor_data as mf
-    lib = C.CDLL(H.HOST_LIB)
-    return {"cpus": len(os.sched_getaffinity(0)), "runs_per_mode": runs,
-            "shapes": [measure_shape(lib, "C2: P = 157, m = 15; 9 x (7, 9) + 7 + 1", 157, 15, mf.C2_SIZES, runs),
-                       measure_shape(lib, "C4: P = 232, m = 15; 14 x (7, 9) + 7 + 1", 232, 15, mf.C4_SIZES, runs)]}
+    name, P, m, sizes = SHAPES[leg]
+    return measure_shape(C.CDLL(H.HOST_LIB), name, P, m, getattr(mf, sizes), opt["--runs"])
+
+
+def assemble(opt, cpus, legs):
+    return {"cpus": cpus, "runs_per_mode": opt["--runs"], "shapes": list(legs.values())}
 
 
 if __name__ == "__main__":
-    argv = sys.argv[1:]
-    opt = {"--cpus": 0, "--runs": 3}
-    for flag in list(opt):
-        if flag in argv:
-            k = argv.index(flag)
-            opt[flag] = int(argv[k + 1])
-            del argv[k:k + 2]
-    if opt["--cpus"] > 0:
-        os.sched_setaffinity(0, sorted(os.sched_getaffinity(0))[:opt["--cpus"]])
-    txt = json.dumps(measure(runs=opt["--runs"]))
-    print(txt)
-    if argv:
-        open(argv[0], "w").write(txt + "\n")
+    pc.main(__file__, {"--cpus": 0, "--runs": 3}, list(SHAPES), LEG_LIMIT_S, run_leg, assemble)

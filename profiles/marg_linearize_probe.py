@@ -9,16 +9,11 @@ process may run on (one rank's share of a node).  Every leg is a child process o
 ends the run.  ICG_PROBE_HOST_LIB: another build of the host layer (as in marg_batch_probe.py; the
 c_abi leg is the device library's own and does not depend on it).  Run by hand; not part of bench.py."""
 import ctypes as C
-import json
 import os
-import subprocess
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "ic-gvins_amd"), ROOT]
+import probe_common as pc
 
 SHAPES = {"C2": (157, 15), "C4": (232, 15)}
 LEG_LIMIT_S = {"C2": 240, "C4": 300, "batch": 240}
@@ -40,12 +35,7 @@ def measure_shape(name, threads, reps, n_windows=256):
         kw = dict(want_Hp=want, want_bp=want, want_evals=want, want_min_ev=want, want_status=True)
         res = ctx.marg_linearize_batch(*packed, **kw)  # (the first call also grows the staging arena and the scratch)
         ctx.prof_enable(True)
-        best = None
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            ctx.marg_linearize_batch(*packed, **kw)
-            t = time.perf_counter() - t0
-            best = t if best is None else min(best, t)
+        best = pc.best_of(reps, lambda: ctx.marg_linearize_batch(*packed, **kw))
         kern = {key + "_ms": round(ms / n, 3) for key, (n, ms) in ctx.prof().items() if key.startswith("marg_lin") and n}
         ctx.prof_enable(False)
         out["c_abi"][form] = dict(kern, call_wall_ms_incl_transfers_best=round(best * 1e3, 3), status_or=int(np.bitwise_or.reduce(res["status"])))
@@ -80,39 +70,13 @@ def measure_batch(threads, reps, n_windows=256):
             "max_abs_Hp_difference_over_scale": float(np.abs(a["Hp"] - b["Hp"]).max() / np.abs(a["Hp"]).max())}
 
 
+def run_leg(leg, opt):
+    return measure_batch(opt["--threads"], opt["--reps"]) if leg == "batch" else measure_shape(leg, opt["--threads"], opt["--reps"])
+
+
+def assemble(opt, cpus, legs):
+    return {"cpus": cpus, "host_pool_threads": opt["--threads"], "shapes": [legs[name] for name in SHAPES], "marginalize_batch": legs["batch"]}
+
+
 if __name__ == "__main__":
-    argv = sys.argv[1:]
-    opt = {"--threads": 16, "--cpus": 0, "--reps": 5}
-    leg = None
-    if "--leg" in argv:
-        k = argv.index("--leg")
-        leg = argv[k + 1]
-        del argv[k:k + 2]
-    for flag in list(opt):
-        if flag in argv:
-            k = argv.index(flag)
-            opt[flag] = int(argv[k + 1])
-            del argv[k:k + 2]
-    if opt["--cpus"] > 0:
-        os.sched_setaffinity(0, sorted(os.sched_getaffinity(0))[:opt["--cpus"]])
-    if leg is not None:  # a child: one leg, its result on the last line
-        res = measure_batch(opt["--threads"], opt["--reps"]) if leg == "batch" else measure_shape(leg, opt["--threads"], opt["--reps"])
-        print(json.dumps(res))
-        sys.exit(0)
-    result = {"cpus": len(os.sched_getaffinity(0)), "host_pool_threads": opt["--threads"], "shapes": []}
-    for name in ("C2", "C4", "batch"):
-        cmd = ["timeout", "-k", "10", str(LEG_LIMIT_S[name]), sys.executable, os.path.abspath(__file__), "--leg", name, "--threads", str(opt["--threads"]),
-               "--reps", str(opt["--reps"])]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        if r.returncode != 0:
-            sys.stderr.write(f"leg {name} ended with status {r.returncode}; nothing further is started\n{r.stdout[-2000:]}\n")
-            sys.exit(r.returncode)
-        res = json.loads(r.stdout.strip().splitlines()[-1])
-        if name == "batch":
-            result["marginalize_batch"] = res
-        else:
-            result["shapes"].append(res)
-    txt = json.dumps(result)
-    print(txt)
-    if argv:
-        open(argv[0], "w").write(txt + "\n")
+    pc.main(__file__, {"--threads": 16, "--cpus": 0, "--reps": 5}, list(LEG_LIMIT_S), LEG_LIMIT_S, run_leg, assemble)

@@ -10,20 +10,21 @@ the context's profiler in a pass of its own, and the bytes each mode moves for t
 Every output of the two modes is compared bit for bit.  By the project's rule a margin below the scatter of either mode's repetitions is
 "not a result".
 `python profiles/marg_prior_resident_probe.py [out.json] [--cpus 2] [--runs 3] [--windows 256]`; --cpus N confines the process to N of the
-CPUs it may run on before any library is loaded (the pool is sized to them).  Run by hand; not part of bench.py."""
+CPUs it may run on before any library is loaded (the pool is sized to them).  Every shape is a leg: a child process of its own under a
+time limit; the first leg that fails ends the run.  Run by hand; not part of bench.py."""
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "ic-gvins_amd"), ROOT]
+import probe_common as pc
+from ctypes_util import bits
 
 PHASES = ("evaluate_ms", "bookkeeping_host_factors_ms", "assemble_eliminate_ms", "m3_linearize_ms", "marginalize_ms")
 KERNELS = ("marg_eval", "host_part_prior", "host_part", "lm_min")
+SHAPES = {"bench": ("bench marginalization shape, second generation: prior r = 61", 10), "estimator": ("estimator width, second generation: prior r = 151", 25)}  # keyframes
+LEG_LIMIT_S = 60  # the whole probe, both shapes in one process at its defaults, took 16.2 s: twice that, rounded up to a full minute
 
 
 def bytes_moved(n, r, n_lm, x_doubles):
@@ -37,7 +38,6 @@ def bytes_moved(n, r, n_lm, x_doubles):
 
 def measure_shape(lib, name, P, n, runs, threads):
     import marg_prior_data as mp
-    import marg_resident_data as mr
     rec, ref, shape = {2: [], 3: []}, None, None
     for _ in range(runs):
         for mode in (2, 3):
@@ -48,7 +48,7 @@ def measure_shape(lib, name, P, n, runs, threads):
             assert (got["device_priors"], got["from_kept"]) == ((n, n) if mode == 3 else (0, 0)), (mode, got["device_priors"], got["from_kept"])
             ref = got if ref is None else ref
             for k in ("Hp", "bp", "J0", "e0", "residuals"):
-                assert np.array_equal(mr.bits(got[k]), mr.bits(ref[k])), (mode, k)  # the same priors wherever the previous one was read
+                assert np.array_equal(bits(got[k]), bits(ref[k])), (mode, k)  # the same priors wherever the previous one was read
             rec[mode].append(dict(zip(PHASES, list(got["phase_ms"]) + [float(got["wall_ms"][1])])))
             print(f"{name}: mode {mode}: {rec[mode][-1]['marginalize_ms']:.2f} ms", file=sys.stderr, flush=True)
             shape = int(got["r"][0])
@@ -58,8 +58,7 @@ def measure_shape(lib, name, P, n, runs, threads):
     out = {"shape": name, "windows": n, "prior_r": r_prior, "r_after": shape, "second_table_factors_per_window": n2,
            "bytes": bytes_moved(n, r_prior, n * len(set(P["w"]["idx_lm"][P["w"]["idx_i"] == 1])), 7 * (K - 1) + 7 + 1)}
     for mode, key in ((2, "off"), (3, "on")):
-        out[key] = {k: {"best": round(min(v), 3), "median": round(statistics.median(v), 3), "scatter": round(max(v) - min(v), 3)}
-                    for k in PHASES for v in [[row[k] for row in rec[mode]]]}
+        out[key] = {k: pc.stats([row[k] for row in rec[mode]]) for k in PHASES}
     out["kernel_ms"] = {}
     for mode, key in ((2, "off"), (3, "on")):
         rc, msg, got = mp.backend_marg_prior_resident(lib, mode, mp.CHAIN_A, n, P, host_threads=threads, passes=2, profile=True)
@@ -71,32 +70,21 @@ def measure_shape(lib, name, P, n, runs, threads):
         a, b = out["off"][k], out["on"][k]
         margin, noise = a["median"] - b["median"], max(a["scatter"], b["scatter"])
         verdict[k] = {"margin_ms_median": round(margin, 3), "best_ratio_off_over_on": round(a["best"] / b["best"], 3),
-                      "result": "device prior is faster" if margin > noise else ("pool prior is faster" if -margin > noise else "not a result")}
+                      "result": pc.verdict(margin, noise, "device prior is faster", "pool prior is faster", "not a result")}
     out["off_minus_on"] = verdict
     return out
 
 
-def measure(runs=3, n=256):
+def run_leg(leg, opt):
     import harness as H
     import marg_data as md
-    lib = C.CDLL(H.HOST_LIB)
-    threads = min(16, len(os.sched_getaffinity(0)))
-    return {"cpus": len(os.sched_getaffinity(0)), "pool_threads": threads, "runs_per_mode": runs,
-            "shapes": [measure_shape(lib, "bench marginalization shape, second generation: prior r = 61", md.make_problem(n_lm=300, n_kf=10, seed=2), n, runs, threads),
-                       measure_shape(lib, "estimator width, second generation: prior r = 151", md.make_problem(n_lm=300, n_kf=25, seed=2), n, runs, threads)]}
+    name, n_kf = SHAPES[leg]
+    return measure_shape(C.CDLL(H.HOST_LIB), name, md.make_problem(n_lm=300, n_kf=n_kf, seed=2), opt["--windows"], opt["--runs"], min(16, len(os.sched_getaffinity(0))))
+
+
+def assemble(opt, cpus, legs):
+    return {"cpus": cpus, "pool_threads": min(16, cpus), "runs_per_mode": opt["--runs"], "shapes": list(legs.values())}
 
 
 if __name__ == "__main__":
-    argv = sys.argv[1:]
-    opt = {"--cpus": 0, "--runs": 3, "--windows": 256}
-    for flag in list(opt):
-        if flag in argv:
-            k = argv.index(flag)
-            opt[flag] = int(argv[k + 1])
-            del argv[k:k + 2]
-    if opt["--cpus"] > 0:
-        os.sched_setaffinity(0, sorted(os.sched_getaffinity(0))[:opt["--cpus"]])
-    txt = json.dumps(measure(runs=opt["--runs"], n=opt["--windows"]))
-    print(txt)
-    if argv:
-        open(argv[0], "w").write(txt + "\n")
+    pc.main(__file__, {"--cpus": 0, "--runs": 3, "--windows": 256}, list(SHAPES), LEG_LIMIT_S, run_leg, assemble)

@@ -8,19 +8,19 @@ call best, median and scatter (max - min) over the runs, the device time of marg
 pass of its own, and the bytes each mode moves for the reduced systems, computed from the shapes.  Every output of the two modes is
 compared bit for bit.  By the project's rule a margin below the scatter of either mode's repetitions is "not a result".
 `python profiles/marg_resident_probe.py [out.json] [--cpus 2] [--runs 3] [--windows 256]`; --cpus N confines the process to N of the CPUs
-it may run on before any library is loaded (the pool is sized to them).  Run by hand; not part of bench.py."""
+it may run on before any library is loaded (the pool is sized to them).  Every shape is a leg: a child process of its own under a time
+limit; the first leg that fails ends the run.  Run by hand; not part of bench.py."""
 import ctypes as C
-import json
 import os
-import statistics
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "ic-gvins_amd"), ROOT]
+import probe_common as pc
+from ctypes_util import bits
 
 PHASES = ("evaluate_ms", "bookkeeping_host_factors_ms", "assemble_eliminate_ms", "m3_linearize_ms", "marginalize_ms")
+LEGS = ("bench", "estimator")
+LEG_LIMIT_S = 60  # the whole probe, both shapes in one process at its defaults, took 7.4 s: twice that, rounded up to a full minute
 
 
 def bytes_moved(n, P, m, blocks):
@@ -50,11 +50,10 @@ def measure_shape(lib, name, family, n, runs, threads, width, m, blocks, **kw):
             assert got["structured"] == n and got["dense"] == 0 and (got["r"] == width - m).all(), (got["structured"], got["dense"])
             ref = got if ref is None else ref
             for k in ("Hp", "bp", "J0", "e0", "residuals"):
-                assert np.array_equal(mr.bits(got[k]), mr.bits(ref[k])), (mode, k)  # the same priors whichever way H travelled
+                assert np.array_equal(bits(got[k]), bits(ref[k])), (mode, k)  # the same priors whichever way H travelled
             rec[mode].append(dict(zip(PHASES, got["pass_ms"][1])))
     for mode in (0, 1):
-        out[f"mode{mode}"] = {k: {"best": round(min(v), 3), "median": round(statistics.median(v), 3), "scatter": round(max(v) - min(v), 3)}
-                              for k in PHASES for v in [[row[k] for row in rec[mode]]]}
+        out[f"mode{mode}"] = {k: pc.stats([row[k] for row in rec[mode]]) for k in PHASES}
     rc, msg, got = mr.backend_marg_resident(lib, 1, family, n, host_threads=threads, passes=2, profile=True, **kw)
     if rc != 0:
         raise RuntimeError(msg)
@@ -64,40 +63,28 @@ def measure_shape(lib, name, family, n, runs, threads, width, m, blocks, **kw):
         a, b = out["mode0"][k], out["mode1"][k]
         margin, noise = a["median"] - b["median"], max(a["scatter"], b["scatter"])
         verdict[k] = {"margin_ms_median": round(margin, 3), "best_ratio_mode0_over_mode1": round(a["best"] / b["best"], 3),
-                      "result": "resident is faster" if margin > noise else ("shipping is faster" if -margin > noise else "not a result")}
+                      "result": pc.verdict(margin, noise, "resident is faster", "shipping is faster", "not a result")}
     out["mode0_minus_mode1"] = verdict
     return out
 
 
-def measure(runs=3, n=256):
+def run_leg(leg, opt):
     import harness as H
     import marg_data as md
-    import marg_resident_data as mr
     import oracle_lib
     import vio_data as vd
-    lib = C.CDLL(H.HOST_LIB)
+    lib, n, runs = C.CDLL(H.HOST_LIB), opt["--windows"], opt["--runs"]
     threads = min(16, len(os.sched_getaffinity(0)))
-    visual = md.make_problem(n_lm=300, n_kf=10, seed=2)
-    orc = oracle_lib.load()
-    base = [vd.make_vio_window(orc, n_intervals=9, per=20, n_lm=120, seed=40 + k) for k in range(4)]
-    vio = [base[w % len(base)] for w in range(n)]
-    return {"cpus": len(os.sched_getaffinity(0)), "pool_threads": threads, "runs_per_mode": runs,
-            "shapes": [measure_shape(lib, "bench marginalization shape: P = 67, m = 6", 0, n, runs, threads, 67, 6, [(6, 6)], P=visual),
-                       measure_shape(lib, "visual-inertial, estimator width: P = 157, m = 15", 1, n, runs, threads, 157, 15,
-                                     [(15, 30)] * 9 + [(6, 6), (9, 9)], vio=vio)]}
+    if leg == "bench":
+        return measure_shape(lib, "bench marginalization shape: P = 67, m = 6", 0, n, runs, threads, 67, 6, [(6, 6)], P=md.make_problem(n_lm=300, n_kf=10, seed=2))
+    base = [vd.make_vio_window(oracle_lib.load(), n_intervals=9, per=20, n_lm=120, seed=40 + k) for k in range(4)]
+    return measure_shape(lib, "visual-inertial, estimator width: P = 157, m = 15", 1, n, runs, threads, 157, 15, [(15, 30)] * 9 + [(6, 6), (9, 9)],
+                         vio=[base[w % len(base)] for w in range(n)])
+
+
+def assemble(opt, cpus, legs):
+    return {"cpus": cpus, "pool_threads": min(16, cpus), "runs_per_mode": opt["--runs"], "shapes": list(legs.values())}
 
 
 if __name__ == "__main__":
-    argv = sys.argv[1:]
-    opt = {"--cpus": 0, "--runs": 3, "--windows": 256}
-    for flag in list(opt):
-        if flag in argv:
-            k = argv.index(flag)
-            opt[flag] = int(argv[k + 1])
-            del argv[k:k + 2]
-    if opt["--cpus"] > 0:
-        os.sched_setaffinity(0, sorted(os.sched_getaffinity(0))[:opt["--cpus"]])
-    txt = json.dumps(measure(runs=opt["--runs"], n=opt["--windows"]))
-    print(txt)
-    if argv:
-        open(argv[0], "w").write(txt + "\n")
+    pc.main(__file__, {"--cpus": 0, "--runs": 3, "--windows": 256}, LEGS, LEG_LIMIT_S, run_leg, assemble)

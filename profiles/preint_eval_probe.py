@@ -3,17 +3,18 @@ bench.py's C4 preintegration shape (256 streams x 15 intervals x 40 samples, Ear
 evaluated (a) by one icg_preint_evaluate_batch call (device time of its two kernels from the context's profiler; wall time of the call
 including packing and transfers) and (b) by one PreintegrationFactor::Evaluate per factor on a HostPool.
 `python profiles/preint_eval_probe.py [out.json] [--threads 16] [--cpus 2] [--reps 5]`; --cpus N confines the process to N of the CPUs it
-may run on (one rank's share of a node) before any library is loaded.  Run by hand; not part of bench.py."""
+may run on (one rank's share of a node) before any library is loaded.  The one shape is one leg: a child process under a time limit.
+Run by hand; not part of bench.py."""
 import ctypes as C
-import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "ic-gvins_amd"), ROOT]
+import probe_common as pc
+from ctypes_util import ErrBuf, ptr
+
+LEG_LIMIT_S = 60  # the whole probe at its defaults took 0.9 s: twice that, rounded up to a full minute
 
 
 def measure(threads=16, reps=5, n_streams=256, n_int=15, n_samples=40):
@@ -54,12 +55,10 @@ def measure(threads=16, reps=5, n_streams=256, n_int=15, n_samples=40):
                      "factors_per_s_kernels": round(n / (ms * 1e-3 / launches), 1), "singular": int(status.sum())}}
     # --- the host layer: the same objects on both paths
     hl = C.CDLL(H.HOST_LIB)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    out6 = np.zeros(6)
-    err = C.create_string_buffer(512)
-    rc = hl.icgh_backend_preint_eval_time(1, n, p(off), p(imu), p(s0), p(params), p(points), int(threads), int(reps), p(out6), err, 512)
+    out6, err = np.zeros(6), ErrBuf()
+    rc = hl.icgh_backend_preint_eval_time(1, n, ptr(off), ptr(imu), ptr(s0), ptr(params), ptr(points), int(threads), int(reps), ptr(out6), *err.args)
     if rc != 0:
-        raise RuntimeError(f"icgh_backend_preint_eval_time rc={rc}: {err.value.decode()}")
+        raise RuntimeError(f"icgh_backend_preint_eval_time rc={rc}: {err.text()}")
     out["host_layer"] = {"host_pool_threads": int(threads), "host_evaluate_us": round(out6[0] * 1e6, 1),
                          "host_factors_per_s": round(n / out6[0], 1), "evaluate_batch_wall_us_incl_packing_and_transfers": round(out6[1] * 1e6, 1),
                          "evaluate_batch_kernels_us": round(out6[2] * 1e3, 1), "max_abs_diff_residual": float(out6[3]),
@@ -68,16 +67,5 @@ def measure(threads=16, reps=5, n_streams=256, n_int=15, n_samples=40):
 
 
 if __name__ == "__main__":
-    argv = sys.argv[1:]
-    opt = {"--threads": 16, "--cpus": 0, "--reps": 5}
-    for flag in list(opt):
-        if flag in argv:
-            k = argv.index(flag)
-            opt[flag] = int(argv[k + 1])
-            del argv[k:k + 2]
-    if opt["--cpus"] > 0:
-        os.sched_setaffinity(0, sorted(os.sched_getaffinity(0))[:opt["--cpus"]])
-    txt = json.dumps(measure(threads=opt["--threads"], reps=opt["--reps"]))
-    print(txt)
-    if argv:
-        open(argv[0], "w").write(txt + "\n")
+    pc.main(__file__, {"--threads": 16, "--cpus": 0, "--reps": 5}, ["all"], LEG_LIMIT_S, lambda leg, opt: measure(threads=opt["--threads"], reps=opt["--reps"]),
+            lambda opt, cpus, legs: legs["all"])

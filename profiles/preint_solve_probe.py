@@ -11,16 +11,11 @@ the link bytes per linearization that follow from the shapes.
 (one rank's share of a node; the host pool then has N threads).  Every leg is a child process of its own under a time limit; the first leg
 that fails ends the run.  Run by hand; not part of bench.py."""
 import ctypes as C
-import json
-import os
-import subprocess
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "ic-gvins_amd"), ROOT]
+import probe_common as pc
+from ctypes_util import bits, i32
 
 SHAPES = {"small": 4, "estimator": 10}  # states
 LEG_LIMIT_S = 500
@@ -38,12 +33,7 @@ def measure_kernels(states, n_windows, reps):
     n = per * W
     imus, st0 = sd.intervals([21] * per, seed0=70)
     off = (np.arange(n + 1) * 21).astype(np.int32)
-    w = rd.make_window(3, 2, seed=5)
-    nf, K, L = w["obs_soa"].shape[1], w["poses"].shape[0], len(w["invdepth"])
-    rep = lambda a, step: np.concatenate([a + k * step for k in range(W)]).astype(np.int32)
-    ctx = icgvins.Context(64, 64, n_slots=1, max_batch=1, max_points=64, max_factors=W * nf)
-    ctx.reproj_set_factors(np.tile(w["obs_soa"], (1, W)), rep(w["idx_i"], K), rep(w["idx_j"], K), rep(w["idx_lm"], L))
-    ctx.reproj_set_windows(np.arange(W + 1, dtype=np.int32) * nf, np.arange(W + 1, dtype=np.int32) * L)
+    ctx = pc.resident_windows(rd.make_window(3, 2, seed=5), W)
     cur, delta, jac, cov, dt, pn = ctx.preint_batch(0, off, np.concatenate(imus * W), np.stack(st0 * W), pd.PARAMS)
     env = np.tile(pd.PARAMS[5:9], (n, 1))
     pts = np.stack([sd.eval_point("perturbed", (st0 * W)[i], cur[i]) for i in range(n)])
@@ -51,7 +41,6 @@ def measure_kernels(states, n_windows, reps):
     ident = np.tile([0.0, 0.0, 0.0, 1.0], (n, 1))
     ctx.preint_set(np.zeros(n, np.int32), delta, jac, S, dt, env, ident)
     Pw = 15 * states
-    i32 = lambda a: np.ascontiguousarray(a, np.int32)
     cols = i32(np.concatenate([np.arange(15 * k, 15 * k + 30) for k in range(per)] * W))
     s, dg = np.zeros((W, Pw)), np.zeros((W, Pw))
     args = (Pw, i32(np.full(W, Pw)), np.ones(W, np.uint8), i32(np.arange(W + 1) * per), i32(np.full(n, 15)), i32(np.full(n, 30)), cols,
@@ -59,20 +48,7 @@ def measure_kernels(states, n_windows, reps):
     out = {}
 
     def timed(name, scopes, call):
-        call()
-        ctx.prof_enable(True)
-        best = None
-        for _ in range(reps):
-            ctx.lib.icg_ctx_sync(ctx.h)
-            t0 = time.perf_counter()
-            call()
-            best = min(best or 1e9, time.perf_counter() - t0)
-        prof = ctx.prof()
-        ctx.prof_enable(False)
-        out[name] = {"python_call_ms": round(best * 1e3, 3)}
-        for scope in scopes:
-            k, ms = prof.get(scope, (0, 0.0))
-            out[name][scope + "_ms"] = round(ms / max(k, 1), 4)
+        out[name] = pc.timed_call(ctx, reps, call, scopes)
 
     def build():
         if ctx.reproj_host_parts_build_preint_raw(*args) != 0:
@@ -100,72 +76,47 @@ def measure_shape(name, reps, n_windows=256):
     priors = [base_prior[w % 8] for w in range(n_windows)]
     starts = [vd.perturbed_start(wins[w], seed=w % 8) for w in range(n_windows)]
     modes = (2, 4, 3, 5)
-    ms, res = {m: [] for m in modes}, {}
-    for _ in range(reps + 1):  # (the first round also sizes the context's buffers: it is not counted)
-        for mode in modes:
-            rc, msg, st, inv, summ, _, n_dev = qs.solve_preint_batch(lib, wins, starts, priors, mode, iters=12, timer=ms[mode])
-            if rc != 0:
-                raise RuntimeError(f"icgh_backend_solve_preint_batch mode {mode} rc={rc}: {msg}")
-            assert n_dev == (n_fac if mode >= 4 else 0), (mode, n_dev)
-            res[mode] = (st, inv, summ)
-    for mode in modes[1:]:
-        for a, b in zip(res[mode][0] + res[mode][1] + [res[mode][2]], res[2][0] + res[2][1] + [res[2][2]]):
-            assert np.array_equal(ps.bits(a), ps.bits(b)), f"mode {mode} differs from mode 2"
+    ms = {m: [] for m in modes}
+
+    def run(mode, counted):
+        rc, msg, st, inv, summ, _, n_dev = qs.solve_preint_batch(lib, wins, starts, priors, mode, iters=12, timer=ms[mode] if counted else None)
+        if rc != 0:
+            raise RuntimeError(f"icgh_backend_solve_preint_batch mode {mode} rc={rc}: {msg}")
+        assert n_dev == (n_fac if mode >= 4 else 0), (mode, n_dev)
+        return st + inv + [summ]
+
+    def compare(mode, got, ref):
+        for a, b in zip(got, ref):
+            assert np.array_equal(bits(a), bits(b)), f"mode {mode} differs from mode 2"
+
+    summ = pc.alternate_modes(modes, reps, run, compare)[2][-1]
     names = {2: "mode2_device_solve_and_host_part", 3: "mode3_device_prior", 4: "mode4_mode2_and_device_preintegration", 5: "mode5_mode3_and_device_preintegration"}
-    best = {m: min(ms[m][1:]) for m in modes}
-    scatter = {m: max(ms[m][1:]) - min(ms[m][1:]) for m in modes}
+    best = {m: min(ms[m]) for m in modes}
+    scatter = {m: max(ms[m]) - min(ms[m]) for m in modes}
 
     def pair(with_, without):
         margin = best[without] - best[with_]
         worst  = max(scatter[with_], scatter[without])
         return {"best_ms_saved": round(margin, 3), f"scatter_ms_mode{without}": round(scatter[without], 3), f"scatter_ms_mode{with_}": round(scatter[with_], 3),
-                "verdict": f"mode {with_} faster" if margin > worst else f"mode {with_} slower" if -margin > worst else
-                           "not a result: the margin is below the scatter of the repetitions"}
+                "verdict": pc.verdict(margin, worst, f"mode {with_} faster", f"mode {with_} slower",
+                                      "not a result: the margin is below the scatter of the repetitions")}
 
     per = states - 1
     return {"shape": f"{name}: {states} states, {per} preintegration factors per window, a prior over all states", "windows": n_windows,
-            "lm_steps": [float(res[2][2][:, 2].mean()), float(res[2][2][:, 3].mean())], "kernels": kernels,
+            "lm_steps": [float(summ[:, 2].mean()), float(summ[:, 3].mean())], "kernels": kernels,
             "link_bytes_per_linearization_from_the_shapes": {
                 "pool_path_up": n_windows * per * (15 * 30 + 15) * 8,  # every factor's gathered 15 x 30 Jacobian and its residual
                 "resident_path_up": n_windows * per * (32 + 4) * 8,  # evaluation point and correction quaternion
                 "resident_path_down": n_windows * per * 8},  # one squared norm
-            "solve_ms": {names[m]: [round(t, 3) for t in ms[m][1:]] for m in modes},
+            "solve_ms": {names[m]: [round(t, 3) for t in ms[m]] for m in modes},
             "solve_ms_best": {names[m]: round(best[m], 3) for m in modes},
-            "solve_ms_median": {names[m]: round(float(np.median(ms[m][1:])), 3) for m in modes},
+            "solve_ms_median": {names[m]: round(float(np.median(ms[m])), 3) for m in modes},
             "mode5_against_mode3": pair(5, 3), "mode4_against_mode2": pair(4, 2), "results_bit_identical": True}
 
 
+def assemble(opt, cpus, legs):
+    return {"cpus": cpus, "host_pool_threads": min(16, cpus), "shapes": list(legs.values())}
+
+
 if __name__ == "__main__":
-    argv = sys.argv[1:]
-    opt = {"--cpus": 0, "--reps": 3}
-    leg = None
-    if "--leg" in argv:
-        k = argv.index("--leg")
-        leg = argv[k + 1]
-        del argv[k:k + 2]
-    for flag in list(opt):
-        if flag in argv:
-            k = argv.index(flag)
-            opt[flag] = int(argv[k + 1])
-            del argv[k:k + 2]
-    if opt["--cpus"] > 0:
-        os.sched_setaffinity(0, sorted(os.sched_getaffinity(0))[:opt["--cpus"]])
-    cpus = len(os.sched_getaffinity(0))
-    os.environ["ICG_SOLVER_THREADS"] = str(min(16, cpus))  # the host pool of every mode: one thread per CPU the process may use
-    if leg is not None:  # a child: one leg, its result on the last line
-        print(json.dumps(measure_shape(leg, opt["--reps"])))
-        sys.exit(0)
-    result = {"cpus": cpus, "host_pool_threads": min(16, cpus), "shapes": []}
-    for name in SHAPES:
-        cmd = ["timeout", "-k", "10", str(LEG_LIMIT_S), sys.executable, os.path.abspath(__file__), "--leg", name, "--reps", str(opt["--reps"])]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        if r.returncode != 0:
-            sys.stderr.write(f"leg {name} ended with status {r.returncode}; nothing further is started\n{r.stdout[-2000:]}\n")
-            sys.exit(r.returncode)
-        result["shapes"].append(json.loads(r.stdout.strip().splitlines()[-1]))
-        sys.stderr.write(f"leg {name} done\n")
-        sys.stderr.flush()
-    txt = json.dumps(result)
-    print(txt)
-    if argv:
-        open(argv[0], "w").write(txt + "\n")
+    pc.main(__file__, {"--cpus": 0, "--reps": 3}, list(SHAPES), LEG_LIMIT_S, lambda leg, opt: measure_shape(leg, opt["--reps"]), assemble, solver_threads=True)

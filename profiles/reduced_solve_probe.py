@@ -9,42 +9,23 @@ own timer around solve + culling + solve), results compared bit for bit.
 (one rank's share of a node; the host pool then has N threads).  Every leg is a child process of its own under a time limit; the first leg
 that fails ends the run.  Run by hand; not part of bench.py."""
 import ctypes as C
-import json
-import os
-import subprocess
-import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "ic-gvins_amd"), ROOT]
+import probe_common as pc
 
 SHAPES = {"C2": (300, 10), "estimator": (300, 25), "C4": (300, 34)}  # landmarks, keyframes: P = 6 keyframes + 7
 LEG_LIMIT_S = 300
 
 
-def best_of(reps, fn):
-    best = None
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        t = time.perf_counter() - t0
-        best = t if best is None else min(best, t)
-    return round(best * 1e3, 3)
-
-
 def measure_call(n_lm, n_kf, n_windows, reps):
     """the C entries on n_windows copies of one window's factor set: kernel time and call wall time"""
-    import icgvins
     import reproj_data as rd
     w = rd.make_window(n_lm, n_kf, seed=0, pixel_noise=0.3)
-    K, L, n = w["poses"].shape[0], len(w["invdepth"]), w["obs_soa"].shape[1]
+    K, L = w["poses"].shape[0], len(w["invdepth"])
     W, P = n_windows, 6 * K + 7
-    rep = lambda a, step: np.concatenate([a + k * step for k in range(W)]).astype(np.int32)
-    ctx = icgvins.Context(64, 64, n_slots=1, max_batch=1, max_points=64, max_factors=W * n)
-    ctx.reproj_set_factors(np.tile(w["obs_soa"], (1, W)), rep(w["idx_i"], K), rep(w["idx_j"], K), rep(w["idx_lm"], L))
-    ctx.reproj_set_windows(np.arange(W + 1, dtype=np.int32) * n, np.arange(W + 1, dtype=np.int32) * L)
+    best_of = lambda reps, fn: round(pc.best_of(reps, fn) * 1e3, 3)
+    ctx = pc.resident_windows(w, W)
     ctx.reproj_eval_windows(np.tile(w["poses"], (W, 1)), np.tile(w["ext"], (W, 1)), np.tile(w["invdepth"], W), np.full(W, w["td"]), huber=1.0)
     cols = (np.tile(6 * np.arange(K), W), np.full(W, 6 * K), np.full(W, 6 * K + 6))
     s, dg, _ = ctx.reproj_schur_windows_resident(P, *cols, damp=np.full(W, 1e-4))
@@ -76,51 +57,26 @@ def measure_shape(name, reps, n_windows=256):
     P, call = measure_call(n_lm, n_kf, n_windows, reps)
     lib = C.CDLL(H.HOST_LIB)
     probs = [su.make_problem(n_lm, n_kf, seed=w % 8, n_outliers=10) for w in range(n_windows)]
-    ms, res = {0: [], 1: []}, {}
-    for _ in range(reps + 1):  # (the first round also sizes the context's buffers: it is not counted)
-        for mode in (0, 1):
-            rc, msg, res[mode] = ru.solve_batch_mode(lib, probs, mode, solve_ms=ms[mode])
-            if rc != 0:
-                raise RuntimeError(f"icgh_backend_solve_batch_mode {mode} rc={rc}: {msg}")
-    ru.assert_same_results(res[1], res[0])
+    ms = {0: [], 1: []}
+
+    def run(mode, counted):
+        rc, msg, res = ru.solve_batch_mode(lib, probs, mode, solve_ms=ms[mode] if counted else None)
+        if rc != 0:
+            raise RuntimeError(f"icgh_backend_solve_batch_mode {mode} rc={rc}: {msg}")
+        return res
+
+    pc.alternate_modes((0, 1), reps, run, lambda mode, got, ref: ru.assert_same_results(got, ref))
     return {"shape": f"{name}: {n_lm} landmarks, {n_kf} keyframes, P = {P}", "windows": n_windows, "c_abi": call,
-            "two_solves_ms": {"mode0_host": [round(t, 3) for t in ms[0][1:]], "mode1_device": [round(t, 3) for t in ms[1][1:]]},
-            "two_solves_ms_best": {"mode0_host": round(min(ms[0][1:]), 3), "mode1_device": round(min(ms[1][1:]), 3)},
-            "two_solves_ms_median": {"mode0_host": round(float(np.median(ms[0][1:])), 3), "mode1_device": round(float(np.median(ms[1][1:])), 3)},
+            "two_solves_ms": {"mode0_host": [round(t, 3) for t in ms[0]], "mode1_device": [round(t, 3) for t in ms[1]]},
+            "two_solves_ms_best": {"mode0_host": round(min(ms[0]), 3), "mode1_device": round(min(ms[1]), 3)},
+            "two_solves_ms_median": {"mode0_host": round(float(np.median(ms[0])), 3), "mode1_device": round(float(np.median(ms[1])), 3)},
             "results_bit_identical": True}
 
 
+def assemble(opt, cpus, legs):
+    return {"cpus": cpus, "host_pool_threads": min(16, cpus), "shapes": list(legs.values())}
+
+
 if __name__ == "__main__":
-    argv = sys.argv[1:]
-    opt = {"--cpus": 0, "--reps": 3}
-    leg = None
-    if "--leg" in argv:
-        k = argv.index("--leg")
-        leg = argv[k + 1]
-        del argv[k:k + 2]
-    for flag in list(opt):
-        if flag in argv:
-            k = argv.index(flag)
-            opt[flag] = int(argv[k + 1])
-            del argv[k:k + 2]
-    if opt["--cpus"] > 0:
-        os.sched_setaffinity(0, sorted(os.sched_getaffinity(0))[:opt["--cpus"]])
-    cpus = len(os.sched_getaffinity(0))
-    os.environ["ICG_SOLVER_THREADS"] = str(min(16, cpus))  # the host pool of both modes: one thread per CPU the process may use
-    if leg is not None:  # a child: one leg, its result on the last line
-        print(json.dumps(measure_shape(leg, opt["--reps"])))
-        sys.exit(0)
-    result = {"cpus": cpus, "host_pool_threads": min(16, cpus), "shapes": []}
-    for name in SHAPES:
-        cmd = ["timeout", "-k", "10", str(LEG_LIMIT_S), sys.executable, os.path.abspath(__file__), "--leg", name, "--reps", str(opt["--reps"])]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        if r.returncode != 0:
-            sys.stderr.write(f"leg {name} ended with status {r.returncode}; nothing further is started\n{r.stdout[-2000:]}\n")
-            sys.exit(r.returncode)
-        result["shapes"].append(json.loads(r.stdout.strip().splitlines()[-1]))
-        sys.stderr.write(f"leg {name} done\n")
-        sys.stderr.flush()
-    txt = json.dumps(result)
-    print(txt)
-    if argv:
-        open(argv[0], "w").write(txt + "\n")
+    pc.main(__file__, {"--cpus": 0, "--reps": 3}, list(SHAPES), LEG_LIMIT_S, lambda leg, opt: measure_shape(leg, opt["--reps"]), assemble,
+            solver_threads=True)

@@ -14,6 +14,7 @@ import numpy as np  # noqa: E402
 
 import harness as H  # noqa: E402
 from stream_utils import ensure_oracle_host  # noqa: E402
+from ctypes_util import ErrBuf  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 60
@@ -31,9 +32,9 @@ for k in range(warm + N):
     if k == warm:
         sb.lib.icgh_hostprof(hp.ctypes.data_as(C.c_void_p), 32, None, 0, 1)
     sb.step([f.ctypes.data for f in ring[kk]], w, np.full(B, 100.0 + k / 20.0), poses)
-nm = C.create_string_buffer(1024)
-n = sb.lib.icgh_hostprof(hp.ctypes.data_as(C.c_void_p), 32, nm, 1024, 0)
-for k, name in enumerate(nm.value.decode().split(";")[:n]):
+nm = ErrBuf(1024)
+n = sb.lib.icgh_hostprof(hp.ctypes.data_as(C.c_void_p), 32, *nm.args, 0)
+for k, name in enumerate(nm.text().split(";")[:n]):
     if hp[2 * k + 1] > 0:
         print(f"{name:18s} {1e6 * hp[2 * k] / (B * N):8.2f} us/frame   calls/frame {hp[2 * k + 1] / (B * N):.3f}")
 print("states", [sb.stats(s)["landmarks"] for s in range(B)])

@@ -7,28 +7,17 @@ import numpy as np
 import marg_data as md
 import preint_data as pd
 import reproj_data as rd
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _f64(a):
-    return np.ascontiguousarray(a, np.float64)
-
-
-def _i32(a):
-    return np.ascontiguousarray(a, np.int32)
+from ctypes_util import ErrBuf, f64, i32, ptr
 
 
 def backend_reproj(lib, w):
-    obs = _f64(w["obs_soa"])
+    obs = f64(w["obs_soa"])
     n = obs.shape[1]
     r, J = np.zeros((n, 2)), np.zeros((n, 46))
-    err = C.create_string_buffer(512)
-    poses, inv = _f64(w["poses"]), _f64(w["invdepth"])
-    rc = lib.icgh_backend_reproj(n, _p(obs), _p(_i32(w["idx_i"])), _p(_i32(w["idx_j"])), _p(_i32(w["idx_lm"])), poses.shape[0],
-                                 _p(poses), _p(_f64(w["ext"])), inv.shape[0], _p(inv), C.c_double(w["td"]), _p(r), _p(J), err, 512)
+    err = ErrBuf()
+    poses, inv = f64(w["poses"]), f64(w["invdepth"])
+    rc = lib.icgh_backend_reproj(n, ptr(obs), ptr(i32(w["idx_i"])), ptr(i32(w["idx_j"])), ptr(i32(w["idx_lm"])), poses.shape[0],
+                                 ptr(poses), ptr(f64(w["ext"])), inv.shape[0], ptr(inv), C.c_double(w["td"]), ptr(r), ptr(J), *err.args)
     assert rc == 0, (rc, err.value)
     return r, J
 
@@ -45,9 +34,9 @@ def marg_problem_args(P, huber, prior_weight):
     """the arguments n .. prior_weight of the marginalization entries (icgh_backend_marginalize, icgh_backend_marginalize_batch,
     icgh_backend_marg_handoff) for problem P (marg_data.make_problem) -> (args, K poses, L landmarks); every pointer keeps its array alive"""
     w = P["w"]
-    obs, poses, inv = _f64(P["obs"]), _f64(w["poses"]), _f64(w["invdepth"])
+    obs, poses, inv = f64(P["obs"]), f64(w["poses"]), f64(w["invdepth"])
     K, L = poses.shape[0], inv.shape[0]
-    args = [obs.shape[1], _p(obs), _p(_i32(P["ii"])), _p(_i32(P["jj"])), _p(_i32(P["ll"])), K, _p(poses), _p(_f64(w["ext"])), L, _p(inv),
+    args = [obs.shape[1], ptr(obs), ptr(i32(P["ii"])), ptr(i32(P["jj"])), ptr(i32(P["ll"])), K, ptr(poses), ptr(f64(w["ext"])), L, ptr(inv),
             C.c_double(w["td"]), C.c_double(huber), C.c_double(prior_weight)]
     return args, K, L
 
@@ -60,10 +49,10 @@ def backend_marginalize(lib, P, huber=1.0, prior_weight=100.0, x_eval=None):
     n_rem = np.zeros(1, np.int32)
     Hp, bp, J0, e0 = np.zeros(cap * cap), np.zeros(cap), np.zeros(cap * cap), np.zeros(cap)
     res = np.zeros(cap)
-    err = C.create_string_buffer(512)
-    xe = None if x_eval is None else _f64(x_eval)
-    rc = lib.icgh_backend_marginalize(*args, 1, 1, _p(sizes), _p(rem_ids), _p(rem_index), _p(rem_size), _p(n_rem), _p(Hp), _p(bp), _p(J0), _p(e0), _p(xe),
-                                      _p(res) if xe is not None else None, err, 512)
+    err = ErrBuf()
+    xe = None if x_eval is None else f64(x_eval)
+    rc = lib.icgh_backend_marginalize(*args, 1, 1, ptr(sizes), ptr(rem_ids), ptr(rem_index), ptr(rem_size), ptr(n_rem), ptr(Hp), ptr(bp), ptr(J0), ptr(e0), ptr(xe),
+                                      ptr(res) if xe is not None else None, *err.args)
     assert rc == 0, (rc, err.value)
     m, r = int(sizes[0]), int(sizes[1])
     nb = int(n_rem[0])
@@ -191,10 +180,10 @@ def check_preintegration(lib, oracle):
             evalp.append(np.concatenate([pose0, mix0, pose1, mix1]))
         n = len(lens)
         cur, res, jac = np.zeros((n, 16)), np.zeros((n, 15)), np.zeros((n, 480))
-        err = C.create_string_buffer(512)
-        imu = _f64(np.concatenate(imus))
-        rc = lib.icgh_backend_preint(variant, n, _p(offsets), _p(imu), _p(_f64(np.stack(states))), _p(_f64(pd.PARAMS)),
-                                     _p(_f64(np.stack(evalp))), _p(cur), _p(res), _p(jac), err, 512)
+        err = ErrBuf()
+        imu = f64(np.concatenate(imus))
+        rc = lib.icgh_backend_preint(variant, n, ptr(offsets), ptr(imu), ptr(f64(np.stack(states))), ptr(f64(pd.PARAMS)),
+                                     ptr(f64(np.stack(evalp))), ptr(cur), ptr(res), ptr(jac), *err.args)
         assert rc == 0, (rc, err.value)
         for i in range(n):
             ep = evalp[i]
@@ -217,9 +206,9 @@ def check_preintegration_golden(lib):
         pose1, mix1 = pd.split(c["s1"])
         ep = np.concatenate([pose0, mix0, pose1, mix1])
         cur, res, jac = np.zeros((1, 16)), np.zeros((1, 15)), np.zeros((1, 480))
-        err = C.create_string_buffer(512)
-        rc = lib.icgh_backend_preint(variant, 1, _p(offsets), _p(_f64(c["imu"])), _p(_f64(c["s0"][None, :])), _p(_f64(c["params"])),
-                                     _p(_f64(ep[None, :])), _p(cur), _p(res), _p(jac), err, 512)
+        err = ErrBuf()
+        rc = lib.icgh_backend_preint(variant, 1, ptr(offsets), ptr(f64(c["imu"])), ptr(f64(c["s0"][None, :])), ptr(f64(c["params"])),
+                                     ptr(f64(ep[None, :])), ptr(cur), ptr(res), ptr(jac), *err.args)
         assert rc == 0, (rc, err.value)
         assert np.abs(cur[0] - c["cur"]).max() < 1e-9 * np.abs(c["cur"]).max(), k
         assert np.abs(res[0] - c["r"]).max() < 1e-6 * max(1.0, np.abs(c["r"]).max()), k
@@ -282,9 +271,9 @@ def backend_marginalize_batch(lib, P, n_windows, mode, dense_window=-1, jitter=1
     cap = 6 * K + L + 7
     sizes, counts, seconds = np.zeros(2, np.int32), np.zeros(2, np.int32), np.zeros(1)
     Hp, bp, J0, e0 = (np.zeros(n_windows * cap * cap), np.zeros(n_windows * cap), np.zeros(n_windows * cap * cap), np.zeros(n_windows * cap))
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_marginalize_batch(mode, n_windows, dense_window, C.c_double(jitter), reps, *args, host_threads, _p(sizes), _p(Hp), _p(bp), _p(J0),
-                                            _p(e0), _p(counts), _p(seconds), err, 512)
+    err = ErrBuf()
+    rc = lib.icgh_backend_marginalize_batch(mode, n_windows, dense_window, C.c_double(jitter), reps, *args, host_threads, ptr(sizes), ptr(Hp), ptr(bp), ptr(J0),
+                                            ptr(e0), ptr(counts), ptr(seconds), *err.args)
     assert rc == 0, (rc, err.value)
     r = int(sizes[1])
     W = n_windows

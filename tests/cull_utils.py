@@ -6,15 +6,13 @@ import os
 
 import numpy as np
 
+from ctypes_util import ErrBuf, ptr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "cull_ref_golden.npz")
 REPROJ_STD = 1.5
 SCALES = [(1.0, 1.0), (3.0, 1.0), (1.0, 3.0)]  # (scale, depth_scale): triangulation gate, culling gate, wide depth gate
 NEAREST, FARTHEST = 1.0, 200.0
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def make_observations(n_poses=6, n_lm=240, seed=3):
@@ -49,8 +47,8 @@ def make_observations(n_poses=6, n_lm=240, seed=3):
 def oracle_eval(oracle, d, scale, dscale):
     n = len(d["pose_idx"])
     err, good = np.zeros(n), np.zeros(n, np.uint8)
-    oracle.lib.orc_reproj_error_batch(_p(d["cam"]), n, _p(d["pose_idx"]), _p(d["lm_idx"]), _p(d["poses12"]), _p(d["pw"]), _p(d["pix"]),
-                                      C.c_double(REPROJ_STD * scale), C.c_double(NEAREST), C.c_double(FARTHEST * dscale), _p(err), _p(good))
+    oracle.lib.orc_reproj_error_batch(ptr(d["cam"]), n, ptr(d["pose_idx"]), ptr(d["lm_idx"]), ptr(d["poses12"]), ptr(d["pw"]), ptr(d["pix"]),
+                                      C.c_double(REPROJ_STD * scale), C.c_double(NEAREST), C.c_double(FARTHEST * dscale), ptr(err), ptr(good))
     return err, good
 
 
@@ -61,8 +59,8 @@ def landmark_table(sb, stream, max_lm=4096, max_obs=200000):
     lm_flags, lm_ref, lm_off = np.zeros(max_lm, np.int32), np.zeros(max_lm, np.uint64), np.zeros(max_lm + 1, np.int32)
     ob_frame, ob_flags = np.zeros(max_obs, np.uint64), np.zeros(max_obs, np.int32)
     ob_pose, ob_pix = np.zeros((max_obs, 12)), np.zeros((max_obs, 2), np.float32)
-    n = lib.icgh_batch_landmark_table(C.c_void_p(sb.h_), stream, max_lm, max_obs, _p(lm_id), _p(lm_pos), _p(lm_flags), _p(lm_ref), _p(lm_off),
-                                      _p(ob_frame), _p(ob_flags), _p(ob_pose), _p(ob_pix))
+    n = lib.icgh_batch_landmark_table(C.c_void_p(sb.h_), stream, max_lm, max_obs, ptr(lm_id), ptr(lm_pos), ptr(lm_flags), ptr(lm_ref), ptr(lm_off),
+                                      ptr(ob_frame), ptr(ob_flags), ptr(ob_pose), ptr(ob_pix))
     assert n >= 0, n
     no = int(lm_off[n])
     return dict(id=lm_id[:n].copy(), pos=lm_pos[:n].copy(), outlier=(lm_flags[:n] & 1).astype(bool), ref_frame=lm_ref[:n].copy(), off=lm_off[:n + 1].copy(),
@@ -74,8 +72,8 @@ def run_culling(sb, mode, lists, std=REPROJ_STD):
     off = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int32)
     flat = np.ascontiguousarray(np.concatenate(lists) if off[-1] else np.zeros(1), np.uint64)
     out5, stats5 = np.zeros((n, 5), np.int32), np.zeros((n, 5))
-    err = C.create_string_buffer(512)
-    rc = sb.lib.icgh_batch_culling(C.c_void_p(sb.h_), int(mode), _p(off), _p(flat), C.c_double(std), _p(out5), _p(stats5), err, 512)
+    err = ErrBuf()
+    rc = sb.lib.icgh_batch_culling(C.c_void_p(sb.h_), int(mode), ptr(off), ptr(flat), C.c_double(std), ptr(out5), ptr(stats5), *err.args)
     assert rc == 0, (rc, err.value)
     return out5 if mode == 0 else stats5
 

@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, os.path.join(ROOT, "ic-gvins_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import solve_utils as su  # noqa: E402
+from ctypes_util import i32, ptr  # noqa: E402
 
 CASES = [(60, 6, 4), (300, 10, 10), (120, 8, 0)]  # landmarks, keyframes, gross outliers; seed = index
 GOLDEN = os.path.join(ROOT, "tests", "golden", "solve_ref_golden.npz")
@@ -24,11 +25,10 @@ def reference_solve(ref, P, prior_weight=30.0, huber=1.0, iters1=6, iters2=18, c
     poses, ext, inv, td = s["poses"].copy(), s["ext"].copy(), s["invdepth"].copy(), np.array([s["td"]])
     n = P["obs"].shape[1]
     summ, act, obs = np.zeros(10), np.zeros(n, np.uint8), np.ascontiguousarray(P["obs"])
-    i32 = lambda a: np.ascontiguousarray(a, np.int32)
     ii, jj, ll = i32(P["ii"]), i32(P["jj"]), i32(P["ll"])
-    rc = ref.ref_window_solve(n, su._p(obs), su._p(ii), su._p(jj), su._p(ll), poses.shape[0], su._p(poses), su._p(ext), len(inv), su._p(inv), su._p(td),
-                              su._p(np.ascontiguousarray(P["prior"])), C.c_double(prior_weight), C.c_double(huber), 0, 0, iters1, iters2, C.c_double(chi2),
-                              su._p(summ), su._p(act))
+    rc = ref.ref_window_solve(n, ptr(obs), ptr(ii), ptr(jj), ptr(ll), poses.shape[0], ptr(poses), ptr(ext), len(inv), ptr(inv), ptr(td),
+                              ptr(np.ascontiguousarray(P["prior"])), C.c_double(prior_weight), C.c_double(huber), 0, 0, iters1, iters2, C.c_double(chi2),
+                              ptr(summ), ptr(act))
     assert rc == 0
     return dict(poses=poses, ext=ext, invdepth=inv, td=td, summary=summ[:8], active=act)
 

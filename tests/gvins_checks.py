@@ -10,6 +10,7 @@ import harness as H
 
 import gvins_data as gd
 import reproj_data as rd
+from ctypes_util import ErrBuf
 
 STATE_TRACKING_NORMAL = 4
 SUMMARY_KEYS = ["imu", "gnss", "gnss_dropped", "frames", "frames_tracked", "keyframes", "optimizations", "marginalizations", "ins_launches", "lost",
@@ -18,10 +19,10 @@ SUMMARY_KEYS = ["imu", "gnss", "gnss_dropped", "frames", "frames_tracked", "keyf
 
 def run_replay(lib, files, start=0.0, end=0.0):
     summ = np.zeros(16)
-    err = C.create_string_buffer(1024)
+    err = ErrBuf(1024)
     rc = lib.icgh_replay_run(files["config"].encode(), None, files["imu"].encode(), files["gnss"].encode(), files["images"].encode(), 0, C.c_double(start),
-                             C.c_double(end), summ.ctypes.data_as(C.c_void_p), err, 1024)
-    assert rc == 0, (rc, err.value.decode())
+                             C.c_double(end), summ.ctypes.data_as(C.c_void_p), *err.args)
+    assert rc == 0, (rc, err.text())
     return dict(zip(SUMMARY_KEYS, summ))
 
 
@@ -154,10 +155,10 @@ def run_replay_many(lib, files, outputs, wait_poll_us=0):
     arr = (C.c_char_p * n)(*[o.encode() for o in outputs])
     summ = np.zeros((n, 16))
     wall = C.c_double(0)
-    err = C.create_string_buffer(1024)
+    err = ErrBuf(1024)
     rc = lib.icgh_replay_run_many(n, files["config"].encode(), arr, files["imu"].encode(), files["gnss"].encode(), files["images"].encode(), 0,
-                                  int(wait_poll_us), summ.ctypes.data_as(C.c_void_p), C.byref(wall), err, 1024)
-    assert rc == 0, (rc, err.value.decode())
+                                  int(wait_poll_us), summ.ctypes.data_as(C.c_void_p), C.byref(wall), *err.args)
+    assert rc == 0, (rc, err.text())
     return [dict(zip(SUMMARY_KEYS, row)) for row in summ], wall.value
 
 
@@ -247,9 +248,9 @@ def check_replay_input_formats(lib_path, tmp_root):
             f.write("%.9f %s\n" % (to_unix(float(t)), out))
     files2 = dict(files, imu=os.path.join(root, "imu_rate_unix.txt"), gnss=os.path.join(root, "gnss_unix.txt"), images=os.path.join(root, "cam1", "images.txt"))
     summ = np.zeros(16)
-    err = C.create_string_buffer(1024)
+    err = ErrBuf(1024)
     rc = lib.icgh_replay_run(files2["config"].encode(), None, files2["imu"].encode(), files2["gnss"].encode(), files2["images"].encode(), 1, C.c_double(0),
-                             C.c_double(0), summ.ctypes.data_as(C.c_void_p), err, 1024)
+                             C.c_double(0), summ.ctypes.data_as(C.c_void_p), *err.args)
     assert rc == 0, err.value
     S2 = dict(zip(SUMMARY_KEYS, summ))
     # the first IMU line only initialises dt in both flavours; the rate file was derived with a 5 ms first interval
@@ -362,10 +363,10 @@ def run_replay_lockstep(lib, files, outputs, groups=1):
     summ = np.zeros((n, 16))
     wall = C.c_double(0)
     shared = np.zeros(3, np.int64)
-    err = C.create_string_buffer(1024)
+    err = ErrBuf(1024)
     rc = lib.icgh_replay_run_lockstep(n, files["config"].encode(), arr, files["imu"].encode(), files["gnss"].encode(), files["images"].encode(), 0,
-                                      int(groups), summ.ctypes.data_as(C.c_void_p), C.byref(wall), shared.ctypes.data_as(C.c_void_p), err, 1024)
-    assert rc == 0, (rc, err.value.decode())
+                                      int(groups), summ.ctypes.data_as(C.c_void_p), C.byref(wall), shared.ctypes.data_as(C.c_void_p), *err.args)
+    assert rc == 0, (rc, err.text())
     return [dict(zip(SUMMARY_KEYS, row)) for row in summ], wall.value, [int(v) for v in shared]
 
 
@@ -422,9 +423,9 @@ def check_replay_lockstep_different_streams(lib_path, tmp_root):
     for o in outs:
         os.makedirs(o, exist_ok=True)
     arr = lambda key: (C.c_char_p * n)(*[f[key].encode() for f in sets])
-    summ, wall, shared, err = np.zeros((n, 16)), C.c_double(0), np.zeros(3, np.int64), C.create_string_buffer(1024)
+    summ, wall, shared, err = np.zeros((n, 16)), C.c_double(0), np.zeros(3, np.int64), ErrBuf(1024)
     rc = lib.icgh_replay_run_lockstep_files(n, arr("config"), (C.c_char_p * n)(*[o.encode() for o in outs]), arr("imu"), arr("gnss"), arr("images"), 1,
-                                            summ.ctypes.data_as(C.c_void_p), C.byref(wall), shared.ctypes.data_as(C.c_void_p), err, 1024)
+                                            summ.ctypes.data_as(C.c_void_p), C.byref(wall), shared.ctypes.data_as(C.c_void_p), *err.args)
     assert rc == 0, err.value
     solves = sum(int(a[0]["optimizations"]) - 1 for a in alone)
     assert shared[0] == solves and shared[1] < solves and 2 <= shared[2] <= n, shared  # some ticks batch several windows, not all of them all

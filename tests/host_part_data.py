@@ -6,13 +6,10 @@ import ctypes as C
 
 import numpy as np
 
-from vio_data import batch_leading_args
+from ctypes_util import ErrBuf, i32, ptr, ptr_or_null as p
+from prior_solve_data import call_batch
 
 P_BATCH = 157
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
 def _block(rng, nr, cols, scale=1.0):
@@ -65,19 +62,15 @@ def flat(P, wins):
     return f
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
-
-
 def twin(lib, P, wins):
     """icgh_host_part_from_blocks -> (rc, message, packed parts as a list, s W x P, diag W x P)"""
     f = flat(P, wins)
     part, s, dg = np.zeros(max(1, sum(f["cells"]))), np.full((f["W"], P), 7.0), np.full((f["W"], P), 7.0)
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_host_part_from_blocks(f["W"], int(P), _p(f["Pw"]), _p(f["blk_off"]), _p(f["nr"]), _p(f["nf"]), _p(f["cols"]), _p(f["jac_off"]), _p(f["J"]),
-                                        _p(f["r"]), _p(part), _p(s), _p(dg), err, 512)
+    err = ErrBuf()
+    rc = lib.icgh_host_part_from_blocks(f["W"], int(P), p(f["Pw"]), p(f["blk_off"]), p(f["nr"]), p(f["nf"]), p(f["cols"]), p(f["jac_off"]), p(f["J"]),
+                                        p(f["r"]), p(part), p(s), p(dg), *err.args)
     off = np.concatenate([[0], np.cumsum(f["cells"])])
-    return rc, err.value.decode(), [part[off[w]:off[w + 1]].copy() for w in range(f["W"])], s, dg
+    return rc, err.text(), [part[off[w]:off[w + 1]].copy() for w in range(f["W"])], s, dg
 
 
 def restate(P, win):
@@ -113,11 +106,5 @@ def restate(P, win):
 def solve_vio_batch(lib, wins, starts, dense, mode, iters=25, prior_weight=100.0, huber=1.0, dense_weight=1.0, dense_seed=7, timer=None):
     """icgh_backend_solve_vio_batch on vio_data windows from the given (states, invdepth) starts -> (rc, message, states, invdepth, summary W x 4);
     a list given as timer receives the entry's own time of the solve in ms"""
-    args, st, inv, keep = batch_leading_args(wins, starts, iters, prior_weight, huber)
-    summ, ms, err = np.zeros((len(wins), 4)), C.c_double(0), C.create_string_buffer(512)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    rc = lib.icgh_backend_solve_vio_batch(*args, p(np.ascontiguousarray(dense, np.int32)), C.c_double(dense_weight), C.c_uint32(dense_seed), p(summ), C.byref(ms),
-                                          int(mode), err, 512)
-    if timer is not None:
-        timer.append(ms.value)
-    return rc, err.value.decode(), st, inv, summ
+    return call_batch(lib.icgh_backend_solve_vio_batch, wins, starts, mode, iters, prior_weight, huber, timer,
+                      before=[ptr(i32(dense)), C.c_double(dense_weight), C.c_uint32(dense_seed)])[:5]

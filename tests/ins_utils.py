@@ -12,21 +12,11 @@ import tempfile
 
 import numpy as np
 
+from ctypes_util import ErrBuf, f64, ptr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_misc.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "ins_ref_golden.npz")
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _f64(a):
-    return np.ascontiguousarray(a, np.float64)
-
-
-def _i32(a):
-    return np.ascontiguousarray(a, np.int32)
 
 
 # ---- data ---------------------------------------------------------------------------------------------------------------
@@ -150,32 +140,32 @@ class RefMisc(_Flat):
         self.lib.ref_ins_window_index.restype = C.c_size_t
 
     def mechanize(self, cfg8, imu, s0):
-        imu, st = _f64(imu), _f64(s0).copy()
+        imu, st = f64(imu), f64(s0).copy()
         traj = np.zeros((max(len(imu) - 1, 0), 23))
-        self.lib.ref_ins_mechanize(_p(_f64(cfg8)), len(imu), _p(imu), _p(st), _p(traj) if len(traj) else None)
+        self.lib.ref_ins_mechanize(ptr(f64(cfg8)), len(imu), ptr(imu), ptr(st), ptr(traj) if len(traj) else None)
         return st, traj
 
     def window_index(self, imu, time):
-        return int(self.lib.ref_ins_window_index(len(imu), _p(_f64(imu)), C.c_double(time)))
+        return int(self.lib.ref_ins_window_index(len(imu), ptr(f64(imu)), C.c_double(time)))
 
     def camera_pose(self, imu, states, pbc, time):
         out = np.zeros(12)
-        ok = self.lib.ref_ins_camera_pose(len(imu), _p(_f64(imu)), _p(_f64(states)), _p(_f64(pbc)), C.c_double(time), _p(out))
+        ok = self.lib.ref_ins_camera_pose(len(imu), ptr(f64(imu)), ptr(f64(states)), ptr(f64(pbc)), C.c_double(time), ptr(out))
         return out, int(ok)
 
     def imu_series(self, imu, start, end):
         out = np.zeros((len(imu) + 4, 8))
-        n = self.lib.ref_imu_series(len(imu), _p(_f64(imu)), C.c_double(start), C.c_double(end), len(out), _p(out))
+        n = self.lib.ref_imu_series(len(imu), ptr(f64(imu)), C.c_double(start), C.c_double(end), len(out), ptr(out))
         return None if n < 0 else out[:n].copy()
 
     def nav_rows(self, cfg8, origin, state23, sodo):
         d = tempfile.mkdtemp(prefix="refnav_")
-        assert self.lib.ref_write_nav_result(_p(_f64(cfg8)), _p(_f64(origin)), _p(_f64(state23)), C.c_double(sodo), d.encode(), 10) == 0
+        assert self.lib.ref_write_nav_result(ptr(f64(cfg8)), ptr(f64(origin)), ptr(f64(state23)), C.c_double(sodo), d.encode(), 10) == 0
         return _read_rows(d)
 
     def redo(self, cfg8, updated, reserved, imu, states):
-        imu, states = _f64(imu).copy(), _f64(states).copy()
-        n = self.lib.ref_redo_ins(_p(_f64(cfg8)), _p(_f64(updated)), int(reserved), len(imu), _p(imu), _p(states))
+        imu, states = f64(imu).copy(), f64(states).copy()
+        n = self.lib.ref_redo_ins(ptr(f64(cfg8)), ptr(f64(updated)), int(reserved), len(imu), ptr(imu), ptr(states))
         return imu[:n], states[:n]
 
 
@@ -185,33 +175,33 @@ class OrcMisc(_Flat):
         self.lib.orc_ins_window_index.restype = C.c_int64
 
     def mechanize(self, cfg8, imu, s0):
-        imu, st = _f64(imu), _f64(s0).copy()
+        imu, st = f64(imu), f64(s0).copy()
         traj = np.zeros((max(len(imu) - 1, 0), 23))
-        self.lib.orc_ins_mechanize(_p(_f64(cfg8)), len(imu), _p(imu), _p(st), _p(traj) if len(traj) else None)
+        self.lib.orc_ins_mechanize(ptr(f64(cfg8)), len(imu), ptr(imu), ptr(st), ptr(traj) if len(traj) else None)
         return st, traj
 
     def window_index(self, imu, time):
-        return int(self.lib.orc_ins_window_index(len(imu), _p(_f64(imu)), C.c_double(time)))
+        return int(self.lib.orc_ins_window_index(len(imu), ptr(f64(imu)), C.c_double(time)))
 
     def camera_pose(self, imu, states, pbc, time):
         out = np.zeros(12)
-        ok = self.lib.orc_ins_camera_pose(len(imu), _p(_f64(imu)), _p(_f64(states)), _p(_f64(pbc)), C.c_double(time), _p(out))
+        ok = self.lib.orc_ins_camera_pose(len(imu), ptr(f64(imu)), ptr(f64(states)), ptr(f64(pbc)), C.c_double(time), ptr(out))
         return out, int(ok)
 
     def imu_series(self, imu, start, end):
         out = np.zeros((len(imu) + 4, 8))
-        n = self.lib.orc_imu_series(len(imu), _p(_f64(imu)), C.c_double(start), C.c_double(end), len(out), _p(out))
+        n = self.lib.orc_imu_series(len(imu), ptr(f64(imu)), C.c_double(start), C.c_double(end), len(out), ptr(out))
         return None if n < 0 else out[:n].copy()
 
     def nav_rows(self, cfg8, origin, state23, sodo):
         nav, errrow, traj = np.zeros(11), np.zeros(14), np.zeros(8)
-        n = self.lib.orc_nav_result_rows(_p(_f64(origin)), int(cfg8[7] != 0), _p(_f64(state23)), C.c_double(sodo), _p(nav), _p(errrow), _p(traj))
+        n = self.lib.orc_nav_result_rows(ptr(f64(origin)), int(cfg8[7] != 0), ptr(f64(state23)), C.c_double(sodo), ptr(nav), ptr(errrow), ptr(traj))
         fmt = lambda row: "".join("%-15.9f " % v for v in row)
         return np.array([fmt(nav), fmt(errrow[:n]), fmt(traj)], dtype=str)
 
     def redo(self, cfg8, updated, reserved, imu, states):
-        imu, states = _f64(imu).copy(), _f64(states).copy()
-        n = self.lib.orc_redo_ins(_p(_f64(cfg8)), _p(_f64(updated)), int(reserved), len(imu), _p(imu), _p(states))
+        imu, states = f64(imu).copy(), f64(states).copy()
+        n = self.lib.orc_redo_ins(ptr(f64(cfg8)), ptr(f64(updated)), int(reserved), len(imu), ptr(imu), ptr(states))
         return imu[:n], states[:n]
 
 
@@ -221,17 +211,17 @@ class HostMisc(_Flat):
     def __init__(self, lib):
         self.lib = lib
         self.lib.icgh_ins_window_index.restype = C.c_long
-        self.err = C.create_string_buffer(512)
+        self.err = ErrBuf()
 
     def _ck(self, rc):
         assert rc == 0, (rc, self.err.value)
 
     def mechanize_batch(self, cfg8, imus, s0s):
         off = np.concatenate([[0], np.cumsum([len(i) for i in imus])]).astype(np.int32)
-        imu = _f64(np.concatenate(imus)) if off[-1] else np.zeros((1, 8))
-        st = _f64(np.stack(s0s)).copy()
+        imu = f64(np.concatenate(imus)) if off[-1] else np.zeros((1, 8))
+        st = f64(np.stack(s0s)).copy()
         traj = np.zeros((max(int(off[-1]), 1), 23))
-        self._ck(self.lib.icgh_ins_mechanize(len(imus), _p(off), _p(imu), _p(_f64(cfg8)), _p(st), _p(traj), self.err, 512))
+        self._ck(self.lib.icgh_ins_mechanize(len(imus), ptr(off), ptr(imu), ptr(f64(cfg8)), ptr(st), ptr(traj), *self.err.args))
         return st, [traj[off[s] + 1:off[s + 1]].copy() for s in range(len(imus))]
 
     def mechanize(self, cfg8, imu, s0):
@@ -239,13 +229,13 @@ class HostMisc(_Flat):
         return st[0], tr[0]
 
     def window_index(self, imu, time):
-        return int(self.lib.icgh_ins_window_index(len(imu), _p(_f64(imu)), C.c_double(time)))
+        return int(self.lib.icgh_ins_window_index(len(imu), ptr(f64(imu)), C.c_double(time)))
 
     def camera_pose_batch(self, imus, states, pbc, times):
         off = np.concatenate([[0], np.cumsum([len(i) for i in imus])]).astype(np.int32)
         out, found = np.zeros((len(imus), 12)), np.zeros(len(imus), np.uint8)
-        self._ck(self.lib.icgh_ins_camera_pose(len(imus), _p(off), _p(_f64(np.concatenate(imus))), _p(_f64(np.concatenate(states))),
-                                               _p(_f64(pbc)), _p(_f64(times)), _p(out), _p(found), self.err, 512))
+        self._ck(self.lib.icgh_ins_camera_pose(len(imus), ptr(off), ptr(f64(np.concatenate(imus))), ptr(f64(np.concatenate(states))),
+                                               ptr(f64(pbc)), ptr(f64(times)), ptr(out), ptr(found), *self.err.args))
         return out, found
 
     def camera_pose(self, imu, states, pbc, time):
@@ -254,20 +244,20 @@ class HostMisc(_Flat):
 
     def imu_series(self, imu, start, end):
         out = np.zeros((len(imu) + 4, 8))
-        n = self.lib.icgh_ins_imu_series(len(imu), _p(_f64(imu)), C.c_double(start), C.c_double(end), len(out), _p(out))
+        n = self.lib.icgh_ins_imu_series(len(imu), ptr(f64(imu)), C.c_double(start), C.c_double(end), len(out), ptr(out))
         return None if n < 0 else out[:n].copy()
 
     def nav_rows(self, cfg8, origin, state23, sodo):
         d = tempfile.mkdtemp(prefix="icgnav_")
-        assert self.lib.icgh_ins_write_nav_result(_p(_f64(cfg8)), _p(_f64(origin)), _p(_f64(state23)), C.c_double(sodo), d.encode(), 10) == 0
+        assert self.lib.icgh_ins_write_nav_result(ptr(f64(cfg8)), ptr(f64(origin)), ptr(f64(state23)), C.c_double(sodo), d.encode(), 10) == 0
         return _read_rows(d)
 
     def redo_batch(self, cfg8, updated, reserved, imus, states):
         off = np.concatenate([[0], np.cumsum([len(i) for i in imus])]).astype(np.int32)
-        imu, st = _f64(np.concatenate(imus)).copy(), _f64(np.concatenate(states)).copy()
+        imu, st = f64(np.concatenate(imus)).copy(), f64(np.concatenate(states)).copy()
         nl = np.zeros(len(imus), np.int32)
-        self._ck(self.lib.icgh_ins_redo(len(imus), _p(_f64(cfg8)), _p(_f64(np.stack(updated))), int(reserved), _p(off), _p(imu), _p(st),
-                                        _p(nl), self.err, 512))
+        self._ck(self.lib.icgh_ins_redo(len(imus), ptr(f64(cfg8)), ptr(f64(np.stack(updated))), int(reserved), ptr(off), ptr(imu), ptr(st),
+                                        ptr(nl), *self.err.args))
         return [(imu[off[s]:off[s] + nl[s]].copy(), st[off[s]:off[s] + nl[s]].copy()) for s in range(len(imus))]
 
     def redo(self, cfg8, updated, reserved, imu, states):

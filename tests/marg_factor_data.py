@@ -1,11 +1,11 @@
 """Marginalization priors for the M4 tests (icg_marg_prior_set / icg_marg_prior_evaluate, icgh_backend_marg_factor): block layouts, seeded
 priors, evaluation points, the packing of many priors into the entry's arrays and the plain-Python sums the device's optional outputs are
 held to."""
-import ctypes as C
 
 import numpy as np
 
 import reproj_data as rd
+from ctypes_util import ErrBuf, ptr
 
 C2_SIZES = [7, 9] * 9 + [7, 1]      # the estimator's window: 9 x (pose, mix) + extrinsic + td, r = 142
 C4_SIZES = [7, 9] * 14 + [7, 1]     # r = 217
@@ -136,20 +136,6 @@ def sequential_sq_norm(e):
     return float(s)
 
 
-def same_bits(a, b):
-    """bit patterns equal on every non-NaN entry, NaN in the same places (the sign and payload of a NaN are not results of IEEE arithmetic
-    and differ between an x86 host and the device)"""
-    a, b = np.ascontiguousarray(a, np.float64).ravel(), np.ascontiguousarray(b, np.float64).ravel()
-    if a.shape != b.shape:
-        return False
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a[~na].view(np.uint64), b[~nb].view(np.uint64)))
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def backend_marg_factor(lib, mode, priors, points, want=(True, True, True), host_threads=4, reps=0, mark=None):
     """icgh_backend_marg_factor.  points: list of evaluation points, each a list of per-window x.  Returns (rc, message, residuals,
     jacobians, gradient, sq_norm, seconds), outputs shaped (n_points, ...); `mark` fills the outputs beforehand."""
@@ -164,8 +150,8 @@ def backend_marg_factor(lib, mode, priors, points, want=(True, True, True), host
     grad = np.full((npt, R), fill) if want[1] else None
     sq = np.full((npt, n), fill) if want[2] else None
     sec = np.full(2, fill)
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_marg_factor(int(mode), n, _p(a["r"]), _p(a["block_off"]), _p(a["block_size"]), _p(a["block_index"]), _p(a["x0"]),
-                                      _p(a["J0"]), _p(a["e0"]), npt, _p(x), int(host_threads), int(reps), _p(res), _p(jac), _p(grad), _p(sq),
-                                      _p(sec), err, 512)
-    return rc, err.value.decode(), res, jac, grad, sq, sec
+    err = ErrBuf()
+    rc = lib.icgh_backend_marg_factor(int(mode), n, ptr(a["r"]), ptr(a["block_off"]), ptr(a["block_size"]), ptr(a["block_index"]), ptr(a["x0"]),
+                                      ptr(a["J0"]), ptr(a["e0"]), npt, ptr(x), int(host_threads), int(reps), ptr(res), ptr(jac), ptr(grad), ptr(sq),
+                                      ptr(sec), *err.args)
+    return rc, err.text(), res, jac, grad, sq, sec

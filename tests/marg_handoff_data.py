@@ -8,6 +8,7 @@ import numpy as np
 import marg_factor_data as mf
 from backend_utils import marg_problem_args
 import marg_linearize_data as ml
+from ctypes_util import ErrBuf, ptr
 
 # (P, m) of the kept batch: r = 1, 6, 61, 142 (the last size whose working matrix fits LDS) and 143 (the first on global scratch), a
 # rank-deficient window (r = 142) and a second window with m = 0 (r = 30)
@@ -43,14 +44,6 @@ def set_points(priors, seed):
     return pts
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).ravel().view(np.uint64)
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def backend_marg_handoff(lib, P, n_windows, mode, dense_window=-1, jitter=1e-3, huber=1.0, prior_weight=100.0, host_threads=4, seed=5, perturb=1e-3,
                          solve_iters=0):
     """icgh_backend_marg_handoff (capi_marg_handoff.cc) on n_windows jittered copies of problem P (marg_data.make_problem).  mode 0: the
@@ -61,12 +54,12 @@ def backend_marg_handoff(lib, P, n_windows, mode, dense_window=-1, jitter=1e-3, 
     res, grad = np.zeros(n_windows * cap), np.zeros(n_windows * cap)
     sq, sq_res = np.zeros(n_windows), np.zeros(n_windows)
     states, inv_out, summ = np.zeros((n_windows, K, 7)), np.zeros((n_windows, L)), np.zeros((n_windows, 4))
-    err = C.create_string_buffer(512)
+    err = ErrBuf()
     rc = lib.icgh_backend_marg_handoff(int(mode), int(n_windows), int(dense_window), C.c_double(jitter), *args, int(host_threads), C.c_uint64(seed),
-                                       C.c_double(perturb), int(solve_iters), _p(counts), _p(res), _p(grad), _p(sq), _p(sq_res), _p(states), _p(inv_out), _p(summ),
-                                       _p(timers), err, 512)
+                                       C.c_double(perturb), int(solve_iters), ptr(counts), ptr(res), ptr(grad), ptr(sq), ptr(sq_res), ptr(states), ptr(inv_out), ptr(summ),
+                                       ptr(timers), *err.args)
     g, R = int(counts[0]), int(counts[1])
     out = dict(priors=g, residuals=res[:R], gradient=grad[:R], sq_norm=sq[:g], sq_norm_resident=sq_res[:g], handed_off=int(counts[2]), tagged=int(counts[3]),
                structured=int(counts[4]), dense=int(counts[5]), solver_handed_off=int(counts[6]), states=states[:g], invdepth=inv_out[:g], summary=summ[:g],
                timers_ms=timers)
-    return rc, err.value.decode(), out
+    return rc, err.text(), out

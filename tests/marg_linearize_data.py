@@ -5,8 +5,12 @@ not depend on the eigen-solver's sign / basis choices.
 Every b is -H x for a modest x, so b lies in the range of H: the prior's cost and J0^T e0 are then well conditioned however badly H is
 scaled, and rank decisions are the only place where rounding could flip a result — the tests assert that no eigenvalue is near the floor."""
 import ctypes as C
+import functools
 
 import numpy as np
+
+import ctypes_util
+from ctypes_util import ErrBuf, ptr
 
 EPS = 1e-8  # the reference's floor (marginalization_info.h:30)
 
@@ -118,10 +122,6 @@ def split(systems, out):
     return res
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def backend_marg_linearize(lib, mode, systems, eps=EPS, want=(True, True, True, True, True), host_threads=4, reps=0, mark=None):
     """icgh_backend_marg_linearize.  want: Hp, bp, evals, min_ev_m, status.  Returns (rc, message, flat outputs dict, seconds); `mark`
     fills the outputs beforehand."""
@@ -134,11 +134,11 @@ def backend_marg_linearize(lib, mode, systems, eps=EPS, want=(True, True, True, 
                evals=np.full(nr, fill) if want[2] else None, min_ev_m=np.full(n, fill) if want[3] else None,
                status=np.full(n, int(fill), np.int32) if want[4] else None)
     sec = np.full(2, fill)
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_marg_linearize(int(mode), n, _p(P), _p(m), _p(H), _p(b), C.c_double(eps), int(host_threads), int(reps), _p(out["Hp"]),
-                                         _p(out["bp"]), _p(out["J0"]), _p(out["e0"]), _p(out["evals"]), _p(out["min_ev_m"]), _p(out["status"]),
-                                         _p(sec), err, 512)
-    return rc, err.value.decode(), out, sec
+    err = ErrBuf()
+    rc = lib.icgh_backend_marg_linearize(int(mode), n, ptr(P), ptr(m), ptr(H), ptr(b), C.c_double(eps), int(host_threads), int(reps), ptr(out["Hp"]),
+                                         ptr(out["bp"]), ptr(out["J0"]), ptr(out["e0"]), ptr(out["evals"]), ptr(out["min_ev_m"]), ptr(out["status"]),
+                                         ptr(sec), *err.args)
+    return rc, err.text(), out, sec
 
 
 def host_eigenvalues(lib, A):
@@ -146,7 +146,7 @@ def host_eigenvalues(lib, A):
     A = np.ascontiguousarray(A, np.float64)
     n = A.shape[0]
     ev, V = np.zeros(n), np.zeros((n, n))
-    assert lib.icgh_symmetric_eigen(n, _p(A), _p(ev), _p(V)) == 0
+    assert lib.icgh_symmetric_eigen(n, ptr(A), ptr(ev), ptr(V)) == 0
     return ev
 
 
@@ -173,6 +173,4 @@ def invariants(system, d):
     return dict(JtJ=d["J0"].T @ d["J0"], Jte=d["J0"].T @ d["e0"], cost=0.5 * float(e @ e))
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, np.float64).ravel(), np.ascontiguousarray(b, np.float64).ravel()
-    return a.shape == b.shape and bool(np.array_equal(a.view(np.uint64), b.view(np.uint64)))
+same_bits = functools.partial(ctypes_util.same_bits, nan_payload=True)  # M3's outputs are held to every bit, those of a NaN too

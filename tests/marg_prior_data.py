@@ -6,14 +6,11 @@ import numpy as np
 
 import marg_resident_data as mr
 from backend_utils import marg_problem_args
+from ctypes_util import ErrBuf, ptr
 
 CHAIN_A, CHAIN_B = 0, 1
 # a mixed batch (capi_marg_prior.cc): the windows that are not ordinary second-generation windows
 NO_PRIOR, DENSE, ROBUST, WEAK = 1, 2, 3, 4
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def backend_marg_prior_resident(lib, mode, chain, n_windows, P, mixed=False, jitter=1e-3, huber=1.0, prior_weight=100.0, host_threads=4, seed=5, perturb=1e-3,
@@ -27,25 +24,25 @@ def backend_marg_prior_resident(lib, mode, chain, n_windows, P, mixed=False, jit
     Hp, bp, J0, e0 = np.zeros(n_windows * cap * cap), np.zeros(n_windows * cap), np.zeros(n_windows * cap * cap), np.zeros(n_windows * cap)
     res, counts, phase = np.zeros(n_windows * cap), np.zeros(7, np.int32), np.zeros(4)
     kernel_ms, wall_ms = (np.zeros(4) if profile else None), np.zeros(passes)
-    err = C.create_string_buffer(512)
+    err = ErrBuf()
     rc = lib.icgh_backend_marg_prior_resident(int(mode), int(chain), int(n_windows), int(bool(mixed)), C.c_double(jitter), *vargs, *second, int(host_threads),
-                                              C.c_uint64(seed), C.c_double(perturb), int(passes), _p(ok), _p(r_out), _p(tag), _p(Hp), _p(bp), _p(J0), _p(e0),
-                                              _p(res), _p(counts), _p(phase), _p(kernel_ms), _p(wall_ms), err, 512)
+                                              C.c_uint64(seed), C.c_double(perturb), int(passes), ptr(ok), ptr(r_out), ptr(tag), ptr(Hp), ptr(bp), ptr(J0), ptr(e0),
+                                              ptr(res), ptr(counts), ptr(phase), ptr(kernel_ms), ptr(wall_ms), *err.args)
     del keep2
     R, RR = int(r_out.sum()), int((r_out.astype(np.int64) ** 2).sum())
     out = dict(ok=ok, r=r_out, tag_slot=tag, Hp=Hp[:RR], bp=bp[:R], J0=J0[:RR], e0=e0[:R], residuals=res[:R], structured=int(counts[0]), dense=int(counts[1]),
                tagged=int(counts[2]), handed_off=int(counts[3]), device_priors=int(counts[4]), from_kept=int(counts[5]), deferred=int(counts[6]),
                phase_ms=phase, kernel_ms=kernel_ms, wall_ms=wall_ms)
-    return rc, err.value.decode(), out
+    return rc, err.text(), out
 
 
 def switch_alone(lib, P, huber=1.0, prior_weight=100.0):
     """icgh_backend_marg_prior_switch_alone -> (rc, message, kernel launches the batch's profiler counted)"""
     vargs, _, _ = marg_problem_args(P, huber, prior_weight)
     launches = np.full(1, -1, np.int32)
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_marg_prior_switch_alone(*vargs, _p(launches), err, 512)
-    return rc, err.value.decode(), int(launches[0])
+    err = ErrBuf()
+    rc = lib.icgh_backend_marg_prior_switch_alone(*vargs, ptr(launches), *err.args)
+    return rc, err.text(), int(launches[0])
 
 
 def _blocks(nb, nr, nf, jac_off, cols, J, r):
@@ -72,12 +69,12 @@ def gather(lib, which, P, jitter=1e-3, huber=1.0, prior_weight=100.0):
                 np.zeros(caps[3]))
     D, E = block_arrays(), block_arrays()
     prior_cols, J0, prior_res, def_eval, eag_eval = np.zeros(caps[1], np.int32), np.zeros(caps[2]), np.zeros(caps[3]), np.zeros(caps[2]), np.zeros(caps[2])
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_marg_prior_gather(int(which), C.c_double(jitter), *vargs, *second, _p(caps), _p(sizes), *[_p(a) for a in D], *[_p(a) for a in E],
-                                            _p(prior_cols), _p(J0), _p(prior_res), _p(def_eval), _p(eag_eval), err, 512)
+    err = ErrBuf()
+    rc = lib.icgh_backend_marg_prior_gather(int(which), C.c_double(jitter), *vargs, *second, ptr(caps), ptr(sizes), *[ptr(a) for a in D], *[ptr(a) for a in E],
+                                            ptr(prior_cols), ptr(J0), ptr(prior_res), ptr(def_eval), ptr(eag_eval), *err.args)
     del keep2
     if rc != 0:
-        return rc, err.value.decode(), None
+        return rc, err.text(), None
     nb, pb, r, ne = int(sizes[0]), int(sizes[5]), int(sizes[6]), int(sizes[7])
     deferred, eager = _blocks(nb, *D), _blocks(nb, *E)
     n_pc = deferred[pb]["nf"] if pb >= 0 else 0

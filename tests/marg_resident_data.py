@@ -8,16 +8,9 @@ import numpy as np
 import marg_data as md
 import vio_data as vd
 from backend_utils import marg_problem_args
+from ctypes_util import bits, ErrBuf, ptr
 
 VISUAL = dict(n_lm=40, n_kf=4, seed=7)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).ravel().view(np.uint64)
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def visual_problem():
@@ -31,7 +24,7 @@ def second_table(P):
     obs = np.ascontiguousarray(w["obs_soa"][:, keep])
     ii, jj, ll = (np.ascontiguousarray(w[k][keep], np.int32) for k in ("idx_i", "idx_j", "idx_lm"))
     assert obs.shape[1] > 0
-    return [obs.shape[1], _p(obs), _p(ii), _p(jj), _p(ll)], [obs, ii, jj, ll]
+    return [obs.shape[1], ptr(obs), ptr(ii), ptr(jj), ptr(ll)], [obs, ii, jj, ll]
 
 
 def _first_states(w, K):
@@ -84,15 +77,15 @@ def backend_marg_resident(lib, mode, family, n_windows, P=None, vio=None, dense_
     Hp, bp, J0, e0 = np.zeros(n_windows * cap * cap), np.zeros(n_windows * cap), np.zeros(n_windows * cap * cap), np.zeros(n_windows * cap)
     res, counts, phase = np.zeros(n_windows * cap), np.zeros(4, np.int32), np.zeros(4)
     pass_ms, kernel_ms = np.zeros((passes, 5)), np.zeros(2) if profile else None
-    err = C.create_string_buffer(512)
+    err = ErrBuf()
     rc = lib.icgh_backend_marg_resident(int(mode), int(family), int(n_windows), int(dense_window), C.c_double(jitter), *vargs, *second, *vio_args,
-                                        int(host_threads), C.c_uint64(seed), C.c_double(perturb), _p(ok), _p(r_out), _p(tag), _p(Hp), _p(bp), _p(J0), _p(e0),
-                                        _p(res), _p(counts), _p(phase), int(passes), _p(pass_ms), _p(kernel_ms), err, 512)
+                                        int(host_threads), C.c_uint64(seed), C.c_double(perturb), ptr(ok), ptr(r_out), ptr(tag), ptr(Hp), ptr(bp), ptr(J0), ptr(e0),
+                                        ptr(res), ptr(counts), ptr(phase), int(passes), ptr(pass_ms), ptr(kernel_ms), *err.args)
     del keep2, keep_v
     R, RR = int(r_out.sum()), int((r_out.astype(np.int64) ** 2).sum())
     out = dict(ok=ok, r=r_out, tag_slot=tag, Hp=Hp[:RR], bp=bp[:R], J0=J0[:RR], e0=e0[:R], residuals=res[:R], structured=int(counts[0]),
                dense=int(counts[1]), tagged=int(counts[2]), handed_off=int(counts[3]), phase_ms=phase, pass_ms=pass_ms, kernel_ms=kernel_ms)
-    return rc, err.value.decode(), out
+    return rc, err.text(), out
 
 
 def plan_blocks(lib, family, which, P=None, vio=None, huber=1.0, prior_weight=100.0):
@@ -104,12 +97,12 @@ def plan_blocks(lib, family, which, P=None, vio=None, huber=1.0, prior_weight=10
     H, b = np.zeros(caps[0]), np.zeros(512)
     nr, nf, jac_off = np.zeros(caps[1], np.int32), np.zeros(caps[1], np.int32), np.zeros(caps[1], np.int64)
     cols, J, r = np.zeros(caps[2], np.int32), np.zeros(caps[3]), np.zeros(caps[4])
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_marg_plan_blocks(int(family), int(which), *vargs, *vio_args, _p(caps), _p(sizes), _p(H), _p(b), _p(nr), _p(nf), _p(jac_off), _p(cols),
-                                           _p(J), _p(r), err, 512)
+    err = ErrBuf()
+    rc = lib.icgh_backend_marg_plan_blocks(int(family), int(which), *vargs, *vio_args, ptr(caps), ptr(sizes), ptr(H), ptr(b), ptr(nr), ptr(nf), ptr(jac_off), ptr(cols),
+                                           ptr(J), ptr(r), *err.args)
     del keep_v
     if rc != 0:
-        return rc, err.value.decode(), None
+        return rc, err.text(), None
     Pw, m, nb = int(sizes[0]), int(sizes[1]), int(sizes[2])
     blocks, c_at, r_at = [], 0, 0
     for k in range(nb):

@@ -6,14 +6,12 @@ import os
 
 import numpy as np
 
+from ctypes_util import ptr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "nav_ref_golden.npz")
 D2R = np.pi / 180.0
 SHAPES = {0: (3, 7), 1: (6, 9), 2: (6, 7), 3: (9, 9)}  # residuals x block size per factor kind
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _quat(rng, n):
@@ -76,18 +74,18 @@ def evaluate(lib, prefix):
         nr, nb = SHAPES[kind]
         r, J = np.zeros(nr), np.zeros((nr, nb))
         aux, x = np.ascontiguousarray(aux, np.float64), np.ascontiguousarray(x, np.float64)
-        assert fn_factor(kind, _p(aux), _p(x), _p(r), _p(J)) == 0
+        assert fn_factor(kind, ptr(aux), ptr(x), ptr(r), ptr(J)) == 0
         r2 = np.zeros(nr)
-        assert fn_factor(kind, _p(aux), _p(x), _p(r2), None) == 0 and np.array_equal(r, r2)
+        assert fn_factor(kind, ptr(aux), ptr(x), ptr(r2), None) == 0 and np.array_equal(r, r2)
         out[f"factor_{i}_r"], out[f"factor_{i}_J"] = r, J
     for i, (what, a, b) in enumerate(helper_cases()):
         a = np.ascontiguousarray(np.concatenate([a, np.zeros(4)])[:4] if what == 5 else np.concatenate([a, np.zeros(3)])[:3], np.float64)
         b = None if b is None else np.ascontiguousarray(b, np.float64)
         o = np.zeros(4)
-        assert fn_helper(what, _p(a), _p(b), _p(o)) == 0
+        assert fn_helper(what, ptr(a), ptr(b), ptr(o)) == 0
         out[f"helper_{i}"] = o
     for i, rows in enumerate(zero_velocity_cases()):
         avg = np.zeros(6)
-        z = fn_zv(len(rows), _p(rows), C.c_double(200.0), _p(avg))
+        z = fn_zv(len(rows), ptr(rows), C.c_double(200.0), ptr(avg))
         out[f"zv_{i}"] = np.concatenate([[float(z)], avg])
     return out

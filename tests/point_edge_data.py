@@ -6,6 +6,7 @@ import numpy as np
 
 import ins_utils as iu
 import synth
+from ctypes_util import ptr
 
 W, H = 1280, 720
 MAX_POINTS = 1024
@@ -165,7 +166,7 @@ def oracle_reproj(oracle, d, max_error):
     import ctypes as C
     n = len(d["pose_idx"])
     err, good = np.zeros(n), np.zeros(n, np.uint8)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    p = ptr
     oracle.lib.orc_reproj_error_batch(p(d["cam"]), n, p(d["pose_idx"]), p(d["lm_idx"]), p(d["poses12"]), p(d["pw"]), p(d["pix"]), C.c_double(max_error),
                                       C.c_double(MIN_DEPTH), C.c_double(MAX_DEPTH), p(err), p(good))
     return err, good

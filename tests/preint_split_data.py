@@ -1,29 +1,13 @@
 """Shared by the tests of the split preintegration evaluation (Preintegration::evaluateGiven on the host, icg_preint_set /
 icg_preint_evaluate_resident on the device): the intervals, the four evaluation points and the call of icgh_backend_preint_eval_split."""
-import ctypes as C
 
 import numpy as np
 
 import preint_data as pd
 import reproj_data as rd
+from ctypes_util import ErrBuf, ptr
 
 POINT_KINDS = ("end_state", "perturbed", "bias_equal", "large_bias_step")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
-
-
-def same_bits(a, b):
-    """bit patterns equal on every non-NaN entry, NaN in the same places (sign and payload of a NaN are not results of IEEE arithmetic and
-    differ between an x86 host and the device; on one machine the patterns are equal anyway)"""
-    a, b = np.ascontiguousarray(a, np.float64).ravel(), np.ascontiguousarray(b, np.float64).ravel()
-    na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a.view(np.uint64)[~na], b.view(np.uint64)[~nb])
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def intervals(lens, seed0=20):
@@ -69,11 +53,11 @@ def eval_split(lib, variant, imus, states, points, q_corr_in=None):
     o = dict(cur=np.zeros((n, 16)), r_eval=np.zeros((n, 15)), J_eval=np.zeros((n, 480)), r_given=np.zeros((n, 15)), J_given=np.zeros((n, 480)), q_corr=np.zeros((n, 4)),
              q_nn=np.zeros((n, 4)), sqrt_info=np.zeros((n, 225)), delta=np.zeros((n, 16)), jac=np.zeros((n, 225)), dt=np.zeros(n), env=np.zeros((n, 4)),
              pn_off=np.zeros(n + 1, np.int32), pn=np.zeros((max(total, 1), 4)), ok=np.full(n, -1, np.int32))
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_preint_eval_split(int(variant), n, _p(offsets), _p(imu), _p(s0), _p(np.ascontiguousarray(pd.PARAMS, np.float64)), _p(pts), _p(qin),
-                                            _p(o["cur"]), _p(o["r_eval"]), _p(o["J_eval"]), _p(o["r_given"]), _p(o["J_given"]), _p(o["q_corr"]), _p(o["q_nn"]),
-                                            _p(o["sqrt_info"]), _p(o["delta"]), _p(o["jac"]), _p(o["dt"]), _p(o["env"]), _p(o["pn_off"]), _p(o["pn"]),
-                                            max(total, 1), _p(o["ok"]), err, 512)
+    err = ErrBuf()
+    rc = lib.icgh_backend_preint_eval_split(int(variant), n, ptr(offsets), ptr(imu), ptr(s0), ptr(np.ascontiguousarray(pd.PARAMS, np.float64)), ptr(pts), ptr(qin),
+                                            ptr(o["cur"]), ptr(o["r_eval"]), ptr(o["J_eval"]), ptr(o["r_given"]), ptr(o["J_given"]), ptr(o["q_corr"]), ptr(o["q_nn"]),
+                                            ptr(o["sqrt_info"]), ptr(o["delta"]), ptr(o["jac"]), ptr(o["dt"]), ptr(o["env"]), ptr(o["pn_off"]), ptr(o["pn"]),
+                                            max(total, 1), ptr(o["ok"]), *err.args)
     assert rc == 0, (rc, err.value)
     o["pn"] = o["pn"][:int(o["pn_off"][-1])]
     o["points"] = pts

@@ -4,11 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from vio_data import _ptrs, batch_leading_args
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+from ctypes_util import ErrBuf, f64, i32, ptr, ptrs
+from vio_data import batch_leading_args
 
 
 def make_prior(win, states, seed, weight=10.0, e0_scale=0.5):
@@ -48,25 +45,36 @@ def prior_cost(prior, states):
     return 0.5 * float(e @ e)
 
 
+def call_batch(entry, wins, starts, mode, iters, prior_weight, huber, timer, priors=None, state_const=None, robust=None, before=(), after=()):
+    """One of the host layer's batch solves on vio_data windows from the given (states, invdepth) starts:
+    entry(W .. iters, *before, [prior_r .. state_const,] summary, [prior cost,] &ms, *after, mode, err, errlen); the bracketed arguments
+    when priors (a list of make_prior's dicts or None) is given.  A list given as timer receives the entry's own time of the solve in ms
+    -> (rc, message, states, invdepth, summary W x 4, prior cost W x 2 or None)"""
+    W = len(wins)
+    args, st, inv, keep = batch_leading_args(wins, starts, iters, prior_weight, huber)
+    args += before
+    summ, pcost, ms, err = np.zeros((W, 4)), None, C.c_double(0), ErrBuf()
+    if priors is not None:
+        pr = lambda key, conv: [None if p is None else conv(p[key]) for p in priors]
+        p_r, p_nb = i32([0 if p is None else p["r"] for p in priors]), i32([0 if p is None else len(p["size"]) for p in priors])
+        tables = [pr("size", i32), pr("index", i32), pr("param", i32), pr("x0", f64), pr("J0", f64), pr("e0", f64)]
+        rob = f64(np.zeros(W) if robust is None else robust)
+        tables.append([None] * W if state_const is None else [None if c is None else i32(c) for c in state_const])
+        pcost = np.zeros((W, 2))
+        args += [ptr(p_r), ptr(p_nb), *[ptrs(t) for t in tables[:6]], ptr(rob), ptrs(tables[6]), ptr(summ), ptr(pcost)]
+    else:
+        args.append(ptr(summ))
+    rc = entry(*args, C.byref(ms), *after, int(mode), *err.args)
+    if timer is not None:
+        timer.append(ms.value)
+    return rc, err.text(), st, inv, summ, pcost
+
+
 def solve_prior_batch(lib, wins, starts, priors, mode, state_const=None, robust=None, iters=25, prior_weight=100.0, huber=1.0, timer=None):
     """icgh_backend_solve_prior_batch on vio_data windows from the given (states, invdepth) starts; priors[w]: make_prior's dict or None;
     state_const[w]: flags per state or None; robust[w]: the Huber delta of the prior's loss, 0 = none
     -> (rc, message, states, invdepth, summary W x 4, prior cost W x 2)"""
-    W = len(wins)
-    i32, f64 = (lambda a: np.ascontiguousarray(a, np.int32)), (lambda a: np.ascontiguousarray(a, np.float64))
-    args, st, inv, keep = batch_leading_args(wins, starts, iters, prior_weight, huber)
-    pr = lambda key, conv: [None if p is None else conv(p[key]) for p in priors]
-    p_r, p_nb = i32([0 if p is None else p["r"] for p in priors]), i32([0 if p is None else len(p["size"]) for p in priors])
-    p_size, p_index, p_param, p_x0, p_J0, p_e0 = pr("size", i32), pr("index", i32), pr("param", i32), pr("x0", f64), pr("J0", f64), pr("e0", f64)
-    rob = f64(np.zeros(W) if robust is None else robust)
-    sc = [None] * W if state_const is None else [None if c is None else i32(c) for c in state_const]
-    summ, pcost, ms, err = np.zeros((W, 4)), np.zeros((W, 2)), C.c_double(0), C.create_string_buffer(512)
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
-    rc = lib.icgh_backend_solve_prior_batch(*args, p(p_r), p(p_nb), _ptrs(p_size), _ptrs(p_index), _ptrs(p_param), _ptrs(p_x0), _ptrs(p_J0), _ptrs(p_e0), p(rob),
-                                            _ptrs(sc), p(summ), p(pcost), C.byref(ms), int(mode), err, 512)
-    if timer is not None:
-        timer.append(ms.value)
-    return rc, err.value.decode(), st, inv, summ, pcost
+    return call_batch(lib.icgh_backend_solve_prior_batch, wins, starts, mode, iters, prior_weight, huber, timer, priors, state_const, robust)
 
 
 def _first_states(W, K):

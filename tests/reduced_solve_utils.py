@@ -4,11 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from solve_utils import _p
+from ctypes_util import bits, ErrBuf, ptr
 
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).view(np.uint64)
 
 
 def spd(n, seed):
@@ -56,15 +53,15 @@ def solve_batch_mode(lib, problems, mode, prior_weight=30.0, huber=1.0, iters1=6
     inv = np.ascontiguousarray(np.concatenate([P["start"]["invdepth"] for P in problems]))
     td = np.array([P["start"]["td"] for P in problems], np.float64)
     prior = np.ascontiguousarray(np.concatenate([P["prior"] for P in problems]))
-    summ, ms, err = np.zeros((W, 8)), C.c_double(0), C.create_string_buffer(512)
-    args = [W, _p(fac_off), _p(pose_off), _p(lm_off), _p(obs), _p(ii), _p(jj), _p(ll), _p(poses), _p(ext), _p(inv), _p(td), _p(prior),
-            C.c_double(prior_weight), C.c_double(huber), 0, 0, int(iters1), int(iters2), C.c_double(chi2), _p(summ), C.byref(ms), err, 512]
+    summ, ms, err = np.zeros((W, 8)), C.c_double(0), ErrBuf()
+    args = [W, ptr(fac_off), ptr(pose_off), ptr(lm_off), ptr(obs), ptr(ii), ptr(jj), ptr(ll), ptr(poses), ptr(ext), ptr(inv), ptr(td), ptr(prior),
+            C.c_double(prior_weight), C.c_double(huber), 0, 0, int(iters1), int(iters2), C.c_double(chi2), ptr(summ), C.byref(ms), *err.args]
     rc = lib.icgh_backend_solve_batch(*args) if mode is None else lib.icgh_backend_solve_batch_mode(*args, int(mode))
     if solve_ms is not None:
         solve_ms.append(ms.value)
     out = [dict(poses=poses[pose_off[w]:pose_off[w + 1]], ext=ext[w], invdepth=inv[lm_off[w]:lm_off[w + 1]], td=td[w:w + 1], summary=summ[w])
            for w in range(W)]
-    return rc, err.value.decode(), out
+    return rc, err.text(), out
 
 
 def assert_same_results(a, b):

@@ -7,6 +7,7 @@ import os
 import numpy as np
 
 import gvins_data as gd
+from ctypes_util import ptr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libref_gvins.so")
@@ -20,10 +21,6 @@ SCENARIOS = {
     "small_window_calibration": (os.path.join(ROOT, "tests", "golden", "gvins_ref_small_window_golden.npz"),
                                  dict(optimize_windows_size=6, estimate_extrinsic=True, estimate_td=True, with_earth=True, track_max_features=150), None),
 }
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def read_inputs(files, w, h):
@@ -46,5 +43,5 @@ def run_reference(files, out_dir, w, h, slowdown=2.0):
     lib = C.CDLL(REF_SO)
     imu, gn, stamps, imgs = read_inputs(files, w, h)
     os.makedirs(out_dir, exist_ok=True)
-    return lib.ref_gvins_run(files["config"].encode(), out_dir.encode(), len(imu), _p(imu), len(gn), _p(gn), len(stamps), _p(stamps), _p(imgs), w, h,
+    return lib.ref_gvins_run(files["config"].encode(), out_dir.encode(), len(imu), ptr(imu), len(gn), ptr(gn), len(stamps), ptr(stamps), ptr(imgs), w, h,
                              C.c_double(slowdown))

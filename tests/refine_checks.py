@@ -4,18 +4,15 @@ import ctypes as C
 import numpy as np
 
 import ins_utils as iu
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+from ctypes_util import ErrBuf, ptr
 
 
 def refine(sb, pose_b_c12, prior_weight=50.0, std=1.5, iters1=6, iters2=18, chi2=5.991, max_kf=16):
     n = sb.n
     out7, kf = np.zeros((n, 7)), np.zeros((n, max_kf, 14))
-    err = C.create_string_buffer(512)
-    rc = sb.lib.icgh_batch_refine_windows(C.c_void_p(sb.h_), _p(np.ascontiguousarray(pose_b_c12, np.float64)), C.c_double(0.0), C.c_double(std),
-                                          C.c_double(prior_weight), iters1, iters2, C.c_double(chi2), _p(out7), max_kf, _p(kf), err, 512)
+    err = ErrBuf()
+    rc = sb.lib.icgh_batch_refine_windows(C.c_void_p(sb.h_), ptr(np.ascontiguousarray(pose_b_c12, np.float64)), C.c_double(0.0), C.c_double(std),
+                                          C.c_double(prior_weight), iters1, iters2, C.c_double(chi2), ptr(out7), max_kf, ptr(kf), *err.args)
     assert rc == 0, (rc, err.value)
     return out7, kf
 

@@ -10,10 +10,7 @@ import ctypes as C
 import numpy as np
 
 import reproj_data as rd
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+from ctypes_util import ErrBuf, ptr
 
 
 def make_problem(n_lm=60, n_kf=6, seed=0, n_outliers=0, perturb=1.0):
@@ -36,12 +33,12 @@ def host_solve(lib, P, prior_weight=30.0, huber=1.0, ext_const=False, td_const=F
     poses, ext, inv, td = s["poses"].copy(), s["ext"].copy(), s["invdepth"].copy(), np.array([s["td"]])
     n = P["obs"].shape[1]
     summ, active = np.zeros(10), np.zeros(n, np.uint8)
-    err = C.create_string_buffer(512)
+    err = ErrBuf()
     obs = np.ascontiguousarray(P["obs"])
-    rc = lib.icgh_backend_solve(n, _p(obs), _p(np.ascontiguousarray(P["ii"], np.int32)), _p(np.ascontiguousarray(P["jj"], np.int32)),
-                                _p(np.ascontiguousarray(P["ll"], np.int32)), poses.shape[0], _p(poses), _p(ext), len(inv), _p(inv), _p(td),
-                                _p(np.ascontiguousarray(P["prior"])), C.c_double(prior_weight), C.c_double(huber), int(ext_const), int(td_const),
-                                int(iters1), int(iters2), C.c_double(chi2), _p(summ), _p(active), err, 512)
+    rc = lib.icgh_backend_solve(n, ptr(obs), ptr(np.ascontiguousarray(P["ii"], np.int32)), ptr(np.ascontiguousarray(P["jj"], np.int32)),
+                                ptr(np.ascontiguousarray(P["ll"], np.int32)), poses.shape[0], ptr(poses), ptr(ext), len(inv), ptr(inv), ptr(td),
+                                ptr(np.ascontiguousarray(P["prior"])), C.c_double(prior_weight), C.c_double(huber), int(ext_const), int(td_const),
+                                int(iters1), int(iters2), C.c_double(chi2), ptr(summ), ptr(active), *err.args)
     assert rc == 0, (rc, err.value)
     return dict(poses=poses, ext=ext, invdepth=inv, td=float(td[0]), summary=summ[:8], active=active, solve_ms=float(summ[8]), setup_ms=float(summ[9]))
 
@@ -62,10 +59,10 @@ def host_solve_batch(lib, problems, prior_weight=30.0, huber=1.0, ext_const=Fals
     td = np.array([P["start"]["td"] for P in problems], np.float64)
     prior = np.ascontiguousarray(np.concatenate([P["prior"] for P in problems]))
     summ, ms = np.zeros((W, 8)), C.c_double(0)
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_solve_batch(W, _p(fac_off), _p(pose_off), _p(lm_off), _p(obs), _p(ii), _p(jj), _p(ll), _p(poses), _p(ext), _p(inv), _p(td),
-                                      _p(prior), C.c_double(prior_weight), C.c_double(huber), int(ext_const), int(td_const), int(iters1), int(iters2),
-                                      C.c_double(chi2), _p(summ), C.byref(ms), err, 512)
+    err = ErrBuf()
+    rc = lib.icgh_backend_solve_batch(W, ptr(fac_off), ptr(pose_off), ptr(lm_off), ptr(obs), ptr(ii), ptr(jj), ptr(ll), ptr(poses), ptr(ext), ptr(inv), ptr(td),
+                                      ptr(prior), C.c_double(prior_weight), C.c_double(huber), int(ext_const), int(td_const), int(iters1), int(iters2),
+                                      C.c_double(chi2), ptr(summ), C.byref(ms), *err.args)
     assert rc == 0, (rc, err.value)
     out = []
     for w in range(W):
@@ -77,14 +74,14 @@ def host_solve_throughput(lib, P, threads, repeat, prior_weight=30.0, huber=1.0,
     """-> windows per second with `threads` solvers in flight (each its own device context), problem construction excluded"""
     s = P["start"]
     n = P["obs"].shape[1]
-    err = C.create_string_buffer(512)
+    err = ErrBuf()
     lib.icgh_backend_solve_throughput.restype = C.c_double
-    sec = lib.icgh_backend_solve_throughput(n, _p(np.ascontiguousarray(P["obs"])), _p(np.ascontiguousarray(P["ii"], np.int32)),
-                                            _p(np.ascontiguousarray(P["jj"], np.int32)), _p(np.ascontiguousarray(P["ll"], np.int32)), s["poses"].shape[0],
-                                            _p(np.ascontiguousarray(s["poses"])), _p(np.ascontiguousarray(s["ext"])), len(s["invdepth"]),
-                                            _p(np.ascontiguousarray(s["invdepth"])), C.c_double(s["td"]), _p(np.ascontiguousarray(P["prior"])),
+    sec = lib.icgh_backend_solve_throughput(n, ptr(np.ascontiguousarray(P["obs"])), ptr(np.ascontiguousarray(P["ii"], np.int32)),
+                                            ptr(np.ascontiguousarray(P["jj"], np.int32)), ptr(np.ascontiguousarray(P["ll"], np.int32)), s["poses"].shape[0],
+                                            ptr(np.ascontiguousarray(s["poses"])), ptr(np.ascontiguousarray(s["ext"])), len(s["invdepth"]),
+                                            ptr(np.ascontiguousarray(s["invdepth"])), C.c_double(s["td"]), ptr(np.ascontiguousarray(P["prior"])),
                                             C.c_double(prior_weight), C.c_double(huber), int(iters1), int(iters2), C.c_double(chi2), int(threads), int(repeat),
-                                            err, 512)
+                                            *err.args)
     assert sec > 0, (sec, err.value)
     return threads * repeat / sec
 

@@ -9,6 +9,7 @@ import numpy as np
 import marg_factor_data as mf
 import marg_linearize_data as ml
 import preint_data as pd
+from ctypes_util import ErrBuf, ptr
 
 MARK = -7.25
 
@@ -16,10 +17,6 @@ MARK = -7.25
 def _lib():
     from stream_utils import ORACLE_HOST
     return C.CDLL(ORACLE_HOST)
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def _one_interval():
@@ -34,13 +31,13 @@ def test_preintegration_device_entries_refuse_with_minus_4():
     off, imu, s0, params, ep = _one_interval()
     out = [np.full(k, MARK) for k in (16, 15, 480, 15, 480, 225, 225)]
     ok = [np.full(1, 77, np.int32), np.full(1, 77, np.int32)]
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_preint_device(1, 1, _p(off), _p(imu), _p(s0), _p(params), _p(ep), *[_p(a) for a in out], _p(ok[0]), _p(ok[1]), err, 512)
+    err = ErrBuf()
+    rc = lib.icgh_backend_preint_device(1, 1, ptr(off), ptr(imu), ptr(s0), ptr(params), ptr(ep), *[ptr(a) for a in out], ptr(ok[0]), ptr(ok[1]), *err.args)
     assert rc == -4 and err.value == b"icg_preint_evaluate_batch is not in this build", (rc, err.value)
     assert all(np.all(a == MARK) for a in out) and ok[0][0] == 77 and ok[1][0] == 77
     out6 = np.full(6, MARK)
-    err = C.create_string_buffer(512)
-    rc = lib.icgh_backend_preint_eval_time(1, 1, _p(off), _p(imu), _p(s0), _p(params), _p(ep), 1, 1, _p(out6), err, 512)
+    err = ErrBuf()
+    rc = lib.icgh_backend_preint_eval_time(1, 1, ptr(off), ptr(imu), ptr(s0), ptr(params), ptr(ep), 1, 1, ptr(out6), *err.args)
     assert rc == -4 and err.value == b"icg_preint_evaluate_batch is not in this build", (rc, err.value)
     assert np.all(out6 == MARK)
 
@@ -57,11 +54,11 @@ def test_marg_linearize_return_codes():
         assert np.all(out["J0"] == MARK) and np.all(sec == MARK)
     P, m, H, b = ml.pack(one)
     J0, e0, sec = np.full(1, MARK), np.full(1, MARK), np.full(2, MARK)
-    err = C.create_string_buffer(512)
+    err = ErrBuf()
 
     def call(n, J0_):
-        return lib.icgh_backend_marg_linearize(0, n, _p(P), _p(m), _p(H), _p(b), C.c_double(ml.EPS), 1, 0, None, None, _p(J0_), _p(e0), None, None, None,
-                                               _p(sec), err, 512)
+        return lib.icgh_backend_marg_linearize(0, n, ptr(P), ptr(m), ptr(H), ptr(b), C.c_double(ml.EPS), 1, 0, None, None, ptr(J0_), ptr(e0), None, None, None,
+                                               ptr(sec), *err.args)
 
     assert call(0, J0) == -1 and err.value == b"icgh_backend_marg_linearize: invalid argument", err.value  # n_windows = 0
     assert call(1, None) == -1 and err.value == b"icgh_backend_marg_linearize: invalid argument", err.value  # a required output missing
@@ -85,11 +82,11 @@ def test_marg_factor_return_codes():
         assert np.all(res == MARK) and np.all(sec == MARK)
     a = mf.pack([p])
     xs, res, sec = np.ascontiguousarray(x[0][0], np.float64), np.full(1, MARK), np.full(2, MARK)
-    err = C.create_string_buffer(512)
+    err = ErrBuf()
 
     def call(n, n_points):
-        return lib.icgh_backend_marg_factor(0, n, _p(a["r"]), _p(a["block_off"]), _p(a["block_size"]), _p(a["block_index"]), _p(a["x0"]), _p(a["J0"]),
-                                            _p(a["e0"]), n_points, _p(xs), 1, 0, _p(res), None, None, None, _p(sec), err, 512)
+        return lib.icgh_backend_marg_factor(0, n, ptr(a["r"]), ptr(a["block_off"]), ptr(a["block_size"]), ptr(a["block_index"]), ptr(a["x0"]), ptr(a["J0"]),
+                                            ptr(a["e0"]), n_points, ptr(xs), 1, 0, ptr(res), None, None, None, ptr(sec), *err.args)
 
     assert call(0, 1) == -1 and err.value == b"icgh_backend_marg_factor: invalid argument", err.value  # n_windows = 0
     assert call(1, 0) == -1 and err.value == b"icgh_backend_marg_factor: invalid argument", err.value  # n_points = 0
@@ -104,8 +101,8 @@ def test_marg_factor_return_codes():
 def test_batch_entries_reject_a_null_batch():
     lib = _lib()
     lib.icgh_batch_dump.restype = C.c_long
-    err = C.create_string_buffer(64)
+    err = ErrBuf(64)
     assert lib.icgh_batch_dump(None, 0, 0, None, C.c_long(0)) == -1
-    assert lib.icgh_batch_replay(None, 1, err, 64) == -1 and lib.icgh_batch_replay_concurrent(None, 1, err, 64) == -1
+    assert lib.icgh_batch_replay(None, 1, *err.args) == -1 and lib.icgh_batch_replay_concurrent(None, 1, *err.args) == -1
     assert lib.icgh_batch_stats(None, 0, None) == -1 and lib.icgh_batch_engine(None) == -1 and lib.icgh_batch_groups(None) == 0
     assert err.value == b""

@@ -15,6 +15,7 @@ import reduced_solve_utils as ru
 import schur_edge_checks as K
 import schur_edge_data as D
 import test_schur_edges_cpu as T
+from ctypes_util import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +50,7 @@ def _assert_same(got, exp, what):
     else:
         a, b = np.asarray(got), np.asarray(exp)
         assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape)
-        same = np.array_equal(ru.bits(a), ru.bits(b)) if a.dtype == np.float64 else np.array_equal(a, b)
+        same = np.array_equal(bits(a), bits(b)) if a.dtype == np.float64 else np.array_equal(a, b)
         assert same, (what, "differs from the same call on a fresh context")
 
 
@@ -168,7 +169,7 @@ def test_cholesky_scratch_and_lds_opt_in():
             rc, x, L = ru.host_cholesky(hostlib, A, b)
             assert rc == 0, n
             (dx, dL, st), = ru.device_cholesky(ctx, [(A, b)])
-            assert st == 0 and np.array_equal(ru.bits(dx), ru.bits(x)) and np.array_equal(ru.bits(np.tril(dL)), ru.bits(L)), n
+            assert st == 0 and np.array_equal(bits(dx), bits(x)) and np.array_equal(bits(np.tril(dL)), bits(L)), n
     finally:
         ctx.close()
 

@@ -8,6 +8,7 @@ import pytest
 
 import reduced_solve_utils as ru
 import reproj_data as rd
+from ctypes_util import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +44,7 @@ def host(hostlib, systems):
 
 def _same(dev, ref):
     x, L, st = dev
-    return st == 0 and np.array_equal(ru.bits(x), ru.bits(ref[1])) and np.array_equal(ru.bits(np.tril(L)), ru.bits(ref[2]))
+    return st == 0 and np.array_equal(bits(x), bits(ref[1])) and np.array_equal(bits(np.tril(L)), bits(ref[2]))
 
 
 def test_spd_systems_equal_the_host_bit_for_bit(ctx, systems, host):
@@ -51,8 +52,8 @@ def test_spd_systems_equal_the_host_bit_for_bit(ctx, systems, host):
     dev = ru.device_cholesky(ctx, systems)
     for n, d, h in zip(SIZES, dev, host):
         assert d[2] == 0, n
-        assert np.array_equal(ru.bits(d[0]), ru.bits(h[1])), (n, np.abs(d[0] - h[1]).max())
-        assert np.array_equal(ru.bits(np.tril(d[1])), ru.bits(h[2])), (n, np.abs(np.tril(d[1]) - h[2]).max())
+        assert np.array_equal(bits(d[0]), bits(h[1])), (n, np.abs(d[0] - h[1]).max())
+        assert np.array_equal(bits(np.tril(d[1])), bits(h[2])), (n, np.abs(np.tril(d[1]) - h[2]).max())
         assert not np.triu(d[1], 1).any(), n  # nothing is written above the diagonal
 
 
@@ -170,7 +171,7 @@ def test_solve_windows_equals_host_step(hostlib):
         dc, st, dl, terms = got
         assert np.array_equal(st, ref_st)
         for name, a, b in (("delta_c", dc, ref_dc), ("delta_l", dl, ref_dl), ("lm_terms", terms, ref_terms)):
-            assert np.array_equal(ru.bits(a), ru.bits(b)), (name, np.abs(a - b).max())
+            assert np.array_equal(bits(a), bits(b)), (name, np.abs(a - b).max())
 
     # step 1: both windows solve, both host parts arrive
     S, s, dg, _ = ctx.reproj_schur_windows_view(P, g["col_pose"], g["col_ext"], g["col_td"], damp=damp)
@@ -180,7 +181,7 @@ def test_solve_windows_equals_host_step(hostlib):
     with pytest.raises(icgvins.IcgError, match="rc=-1"):  # the view form leaves nothing resident either
         ctx.reproj_solve_windows(P, Pw, [1, 1], dd1, rhs1, n_lm)
     s_r, dg_r, _ = ctx.reproj_schur_windows_resident(P, g["col_pose"], g["col_ext"], g["col_td"], damp=damp)
-    assert np.array_equal(ru.bits(s_r), ru.bits(s)) and np.array_equal(ru.bits(dg_r), ru.bits(dg))
+    assert np.array_equal(bits(s_r), bits(s)) and np.array_equal(bits(dg_r), bits(dg))
     got = ctx.reproj_solve_windows(P, Pw, [1, 1], dd1, rhs1, n_lm, host_part_new=[1, 1], host_S=np.concatenate([packed(0), packed(1)]))
     compare(got, dc1, st1, dl1, terms1)
     # step 2 (a re-damped step): smaller radius, no part is shipped (the resident ones are reused), window 1 does not solve

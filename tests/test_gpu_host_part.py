@@ -9,6 +9,7 @@ import pytest
 import host_part_data as hp
 import reduced_solve_utils as ru
 import reproj_data as rd
+from ctypes_util import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -52,8 +53,8 @@ def build(ctx, P, wins, keep=None, rebuild=None, s=None, dg=None):
 def same(got, parts, s, dg, order):
     gs, gd, gp = got
     for k, w in enumerate(order):
-        assert np.array_equal(hp.bits(gp[k]), hp.bits(parts[w])), ("part", k, w)
-        assert np.array_equal(hp.bits(gs[k]), hp.bits(s[w])) and np.array_equal(hp.bits(gd[k]), hp.bits(dg[w])), ("s / diag", k, w)
+        assert np.array_equal(bits(gp[k]), bits(parts[w])), ("part", k, w)
+        assert np.array_equal(bits(gs[k]), bits(s[w])) and np.array_equal(bits(gd[k]), bits(dg[w])), ("s / diag", k, w)
 
 
 @pytest.fixture()
@@ -72,7 +73,7 @@ def test_batch_in_one_call_reversed_and_alone(ctx, reference):
     same(build(ctx, P, wins), parts, s, dg, range(W))  # run after run (and in place: the kept layout did not change)
     rev = list(range(W))[::-1]
     same(build(ctx, P, [wins[w] for w in rev]), parts, s, dg, rev)
-    assert hp.bits(parts[3])[1] == 0 and hp.bits(s[3])[0] == 0  # the -0.0 window: the reference itself holds +0.0
+    assert bits(parts[3])[1] == 0 and bits(s[3])[0] == 0  # the -0.0 window: the reference itself holds +0.0
     partition(ctx, 1)
     for w in range(W):
         same(build(ctx, P, [wins[w]]), parts, s, dg, [w])
@@ -102,7 +103,7 @@ def test_one_column_and_nan(ctx, hostlib):
     for got, ref in ((gp[0], parts[0]), (gs[0], s[0]), (gd[0], dg[0])):
         assert np.array_equal(np.isnan(got), np.isnan(ref)) and np.isnan(ref).any()
         ok = ~np.isnan(ref)
-        assert np.array_equal(hp.bits(got[ok]), hp.bits(ref[ok]))
+        assert np.array_equal(bits(got[ok]), bits(ref[ok]))
 
 
 def _keep_windows(rng, Pw):
@@ -169,12 +170,12 @@ def test_kept_jacobians_untouched_windows_and_the_solve(hostlib):
     gs, gd, gp = build(ctx, P, sent3, keep={(1, 1)}, rebuild=[0, 1], s=s3, dg=dg3)
     assert gp[0] is None and (gs[0] == FILL).all() and (gd[0] == FILL).all()
     parts3, sr3, dr3 = ref["third"]
-    assert np.array_equal(hp.bits(gp[1]), hp.bits(parts3[1])) and np.array_equal(hp.bits(gs[1]), hp.bits(sr3[1])) and np.array_equal(hp.bits(gd[1]), hp.bits(dr3[1]))
+    assert np.array_equal(bits(gp[1]), bits(parts3[1])) and np.array_equal(bits(gs[1]), bits(sr3[1])) and np.array_equal(bits(gd[1]), bits(dr3[1]))
     # both resident parts as icg_reproj_solve_windows reads them: window 0's survived the third call
     dc, st, _, _ = ctx.reproj_solve_windows(P, Pw, [1, 1], dd, rhs, n_lm)
     assert not st.any()
     for w in range(W):
-        assert np.array_equal(hp.bits(dc[w, :Pw[w]]), hp.bits(solved[w][0])), w
+        assert np.array_equal(bits(dc[w, :Pw[w]]), bits(solved[w][0])), w
         assert not dc[w, Pw[w]:].any()
     # a kept Jacobian of another shape, and a block count that differs from the kept one
     wrong = [sent3[0], dict(Pw=sent3[1]["Pw"], blocks=[sent3[1]["blocks"][0], (np.zeros((8, 9)),) + (np.zeros(8), sent3[1]["blocks"][1][2])])]
@@ -188,7 +189,7 @@ def test_kept_jacobians_untouched_windows_and_the_solve(hostlib):
         build(ctx, P + 1, third)
     # and nothing of that changed what is resident
     dc2, _, _, _ = ctx.reproj_solve_windows(P, Pw, [1, 1], dd, rhs, n_lm)
-    assert np.array_equal(hp.bits(dc2), hp.bits(dc))
+    assert np.array_equal(bits(dc2), bits(dc))
     ctx.close()
 
 
@@ -230,4 +231,4 @@ def test_argument_errors(ctx, hostlib):
     assert rc == 0, msg
     rc, msg, parts, sr, dr = hp.twin(hostlib, P, good)
     assert rc == 0, msg
-    assert np.array_equal(hp.bits(part), hp.bits(np.concatenate(parts))) and np.array_equal(hp.bits(s), hp.bits(sr)) and np.array_equal(hp.bits(dg), hp.bits(dr))
+    assert np.array_equal(bits(part), bits(np.concatenate(parts))) and np.array_equal(bits(s), bits(sr)) and np.array_equal(bits(dg), bits(dr))

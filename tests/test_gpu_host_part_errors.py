@@ -9,12 +9,12 @@ prior of r = 7 (a 7-block and one uncovered column) and a resident P2 set of two
 import numpy as np
 import pytest
 
-import host_part_data as hp
 import marg_factor_data as mf
 import preint_data as pd
 import preint_split_data as sd
 from test_gpu_host_part_preint import _arrays, _unit
 from test_gpu_marg_prior_resident import _partition
+from ctypes_util import bits, i32
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +53,6 @@ def _layout():
     ordinary, prior.  The resident blocks of window 1 only advance the cursors of prior_cols and preint_cols."""
     rng = np.random.RandomState(11)
     mk = lambda nr, cols: ("ord", rng.normal(0, 1.0, (nr, len(cols))), rng.normal(0, 1.0, nr), np.asarray(cols, np.int32))
-    i32 = lambda a: np.asarray(a, np.int32)
     return [[mk(3, [0, 1, 2]), ("prior", 0, i32(range(6)), i32(range(2, 8)), "gather", 7), ("preint", 1, i32([0, 7, 16, 23]), i32([0, 3, 5, 7]), "gather")],
             [mk(2, [4, 0, 2]), ("prior", 0, i32([5, 0, 3]), i32([1, 2, 3]), "gather", 7), ("preint", 0, i32([31, 8]), i32([0, 4]), "gather")],
             [("preint", 0, i32([1, 2, 24, 25, 30]), i32([5, 4, 3, 2, 1]), "gather"), mk(3, [0, 5]), ("prior", 0, i32([6, 2]), i32([0, 1]), "gather", 7)]]
@@ -149,5 +148,5 @@ def test_the_first_defect_in_the_entry_s_order_is_the_one_reported(ctx):
         rc, msg, again = _call(ctx, good, **over)
         assert rc == 0, msg
         for k in first:
-            assert np.array_equal(hp.bits(again[k]), hp.bits(first[k])), k
+            assert np.array_equal(bits(again[k]), bits(first[k])), k
     ctx.prof_enable(False)

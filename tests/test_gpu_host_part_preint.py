@@ -9,11 +9,11 @@ host's: what is compared here is the gather, not the evaluation (tests/test_gpu_
 import numpy as np
 import pytest
 
-import host_part_data as hp
 import marg_factor_data as mf
 import preint_data as pd
 import preint_split_data as sd
 from test_gpu_marg_prior_resident import _columns, _gathered, _partition
+from ctypes_util import bits, i32
 
 pytestmark = pytest.mark.gpu
 
@@ -61,7 +61,6 @@ def _arrays(layout, Pw, rebuild):
     """the raw arguments of icg_reproj_host_parts_build_preint.  A block is ("ord", J, r, cols), ("prior", p, prior_cols, cols, how) or
     ("preint", f, preint_cols, cols, how), how = "gather" / "keep"; the resident blocks' slots in r are NaN"""
     blocks = [b for win in layout for b in win]
-    i32 = lambda a: np.ascontiguousarray(a, np.int32)
     a = dict(Pw=i32(Pw), rebuild=np.ascontiguousarray(rebuild, np.uint8), blk_off=i32(np.concatenate([[0], np.cumsum([len(w) for w in layout])])))
     nr, nf, cols, r, prior_of, preint_of, pc, qc, jac_off, Js, at = [], [], [], [], [], [], [], [], [], [], 0
     for b in blocks:
@@ -100,8 +99,8 @@ def _call(ctx, a, W, entry="preint", **over):
 def _same(got, ref, rebuilt):
     (gs, gd, gp), (rs, rdg, rp) = got, ref
     for w in rebuilt:
-        assert np.array_equal(hp.bits(gp[w]), hp.bits(rp[w])), ("part", w)
-        assert np.array_equal(hp.bits(gs[w]), hp.bits(rs[w])) and np.array_equal(hp.bits(gd[w]), hp.bits(rdg[w])), ("s / diag", w)
+        assert np.array_equal(bits(gp[w]), bits(rp[w])), ("part", w)
+        assert np.array_equal(bits(gs[w]), bits(rs[w])) and np.array_equal(bits(gd[w]), bits(rdg[w])), ("s / diag", w)
 
 
 def _layout(rng, prior, how):
@@ -164,9 +163,9 @@ def test_build_from_resident_factors_equals_build_from_fetched_ones(ctx):
     ref2 = _reference(ctx, layout, Pw, rebuild, r2, J1, prior, res, jac)
     _same(got1, ref1, rebuilt)
     _same(got2, ref2, rebuilt)
-    assert not np.array_equal(hp.bits(r1), hp.bits(r2))
+    assert not np.array_equal(bits(r1), bits(r2))
     for w in (0, 1, 2, 5):
-        assert np.array_equal(hp.bits(got1[2][w]), hp.bits(got2[2][w])) and not np.array_equal(hp.bits(got1[0][w]), hp.bits(got2[0][w])), w
+        assert np.array_equal(bits(got1[2][w]), bits(got2[2][w])) and not np.array_equal(bits(got1[0][w]), bits(got2[0][w])), w
     assert not got1[2][3].any() and not got1[0][3].any()  # the window without host blocks: a zero part
     for got in (got1, got2):  # the window that is not rebuilt: nothing of it was written
         assert got[2][4] is None and (got[0][4] == FILL).all() and (got[1][4] == FILL).all()

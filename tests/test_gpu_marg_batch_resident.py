@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import marg_resident_data as mr
+from ctypes_util import ErrBuf
 
 pytestmark = pytest.mark.gpu
 
@@ -72,6 +73,6 @@ def test_reduced_system_on_the_device_equals_the_device_linearization(lib, vio, 
 
 
 def test_switch_alone_is_refused_by_message(lib):
-    err = C.create_string_buffer(512)
-    assert lib.icgh_backend_marg_resident_switch_alone(err, 512) == 1, err.value
-    assert "setDeviceReducedSystem(true) needs setDeviceLinearization(true)" in err.value.decode()
+    err = ErrBuf()
+    assert lib.icgh_backend_marg_resident_switch_alone(*err.args) == 1, err.value
+    assert "setDeviceReducedSystem(true) needs setDeviceLinearization(true)" in err.text()

@@ -15,6 +15,7 @@ import pytest
 import backend_utils as bu
 import marg_data as md
 import marg_factor_data as mf
+from ctypes_util import ptr, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -69,8 +70,8 @@ def test_heterogeneous_batch_equals_the_oracle_bit_for_bit(ctx, oracle, cases):
     for w, (p, x) in enumerate(zip(priors, points)):
         e, J = oracle.marg_factor_eval(p["size"], p["index"], p["x0"], x, p["J0"], p["e0"])
         assert np.all(np.isfinite(e))
-        assert mf.same_bits(res_w[w], e), w
-        assert mf.same_bits(jac_w[w], J), w
+        assert same_bits(res_w[w], e), w
+        assert same_bits(jac_w[w], J), w
 
 
 def test_zero_norm_linearization_quaternion_gives_the_oracles_non_finite_values(ctx, oracle):
@@ -81,7 +82,7 @@ def test_zero_norm_linearization_quaternion_gives_the_oracles_non_finite_values(
     e, J = oracle.marg_factor_eval(p["size"], p["index"], p["x0"], x, p["J0"], p["e0"])
     assert not np.all(np.isfinite(e))
     assert np.array_equal(np.isnan(res), np.isnan(e)) and np.array_equal(np.isinf(res), np.isinf(e))
-    assert mf.same_bits(res, e) and mf.same_bits(jac, J)
+    assert same_bits(res, e) and same_bits(jac, J)
 
 
 def test_a_window_evaluates_to_the_same_bits_alone_and_in_any_batch(ctx, cases):
@@ -90,14 +91,14 @@ def test_a_window_evaluates_to_the_same_bits_alone_and_in_any_batch(ctx, cases):
     res_w, jac_w, grad_w = mf.split(priors, res, "r"), mf.split(priors, jac, "jac"), mf.split(priors, grad, "r")
     for w, (p, x) in enumerate(zip(priors, points)):
         r1, j1, g1, s1 = _evaluate(ctx, [p], [x], want_jac=True, want_grad=True, want_sq_norm=True)
-        assert mf.same_bits(r1, res_w[w]) and mf.same_bits(j1, jac_w[w]) and mf.same_bits(g1, grad_w[w]) and mf.same_bits(s1, sq[w]), w
+        assert same_bits(r1, res_w[w]) and same_bits(j1, jac_w[w]) and same_bits(g1, grad_w[w]) and same_bits(s1, sq[w]), w
     rp, rx = priors[::-1], points[::-1]
     res_r, jac_r, grad_r, sq_r = _evaluate(ctx, rp, rx, want_jac=True, want_grad=True, want_sq_norm=True)
     rr, jr, gr = mf.split(rp, res_r, "r"), mf.split(rp, jac_r, "jac"), mf.split(rp, grad_r, "r")
     n = len(priors)
     for w in range(n):
-        assert mf.same_bits(rr[n - 1 - w], res_w[w]) and mf.same_bits(jr[n - 1 - w], jac_w[w]) and mf.same_bits(gr[n - 1 - w], grad_w[w]), w
-        assert mf.same_bits(sq_r[n - 1 - w], sq[w]), w
+        assert same_bits(rr[n - 1 - w], res_w[w]) and same_bits(jr[n - 1 - w], jac_w[w]) and same_bits(gr[n - 1 - w], grad_w[w]), w
+        assert same_bits(sq_r[n - 1 - w], sq[w]), w
 
 
 def test_the_set_stays_resident_and_a_new_set_replaces_it(ctx, cases):
@@ -112,7 +113,7 @@ def test_the_set_stays_resident_and_a_new_set_replaces_it(ctx, cases):
             c.close()
 
     def same(a, b):
-        return all(mf.same_bits(u, v) for u, v in zip(a, b))
+        return all(same_bits(u, v) for u, v in zip(a, b))
 
     ctx.marg_prior_set(*mf.set_args(priors))
     for k in range(3):  # one set, three points
@@ -135,7 +136,7 @@ def test_optional_outputs_in_every_combination(ctx, cases):
     x = np.ascontiguousarray(np.concatenate(points))
     R, NJ, n = int(a["r"].sum()), int(sum(p["r"] * int(p["size"].sum()) for p in priors)), len(priors)
     ctx.marg_prior_set(*mf.set_args(priors))
-    p_ = lambda arr: arr.ctypes.data_as(C.c_void_p)
+    p_ = ptr
     ref = None
     for wj, wg, ws in itertools.product((False, True), repeat=3):
         res, jac, grad, sq = np.full(R, MARK), np.full(NJ, MARK), np.full(R, MARK), np.full(n, MARK)
@@ -143,7 +144,7 @@ def test_optional_outputs_in_every_combination(ctx, cases):
         assert rc == 0, ctx.lib.icg_last_error(ctx.h)
         if ref is None:
             ref = res.copy()
-        assert mf.same_bits(res, ref), (wj, wg, ws)
+        assert same_bits(res, ref), (wj, wg, ws)
         assert wj or np.all(jac == MARK)
         assert wg or np.all(grad == MARK)
         assert ws or np.all(sq == MARK)
@@ -152,8 +153,8 @@ def test_optional_outputs_in_every_combination(ctx, cases):
     jac, grad, sq = full
     res_w, grad_w = mf.split(priors, ref, "r"), mf.split(priors, grad, "r")
     for w, p in enumerate(priors):
-        assert mf.same_bits(grad_w[w], mf.sequential_gradient(p["J0"], res_w[w])), w
-        assert mf.same_bits(sq[w], mf.sequential_sq_norm(res_w[w])), w
+        assert same_bits(grad_w[w], mf.sequential_gradient(p["J0"], res_w[w])), w
+        assert same_bits(sq[w], mf.sequential_sq_norm(res_w[w])), w
 
 
 def test_reference_golden(ctx, hostlib):
@@ -178,7 +179,7 @@ def test_reference_golden(ctx, hostlib):
     index = out["index"] - out["m"]
     ctx.marg_prior_set([out["r"]], [0, len(ids)], out["size"], index, x0, out["J0"], out["e0"])
     res, _, grad, sq = ctx.marg_prior_evaluate(x, want_grad=True, want_sq_norm=True)
-    assert mf.same_bits(res, out["res"])
+    assert same_bits(res, out["res"])
     cols = []
     for k in np.argsort(out["ids"]):
         c0 = int(index[k])
@@ -199,7 +200,7 @@ def test_host_layer_device_mode_equals_host_mode_bit_for_bit(hostlib):
     rc1, msg1, res1, jac1, grad1, sq1, sec = mf.backend_marg_factor(hostlib, 1, priors, points, mark=MARK)
     assert rc1 == 0, msg1
     assert sec[0] > 0 and sec[1] > 0
-    assert mf.same_bits(res1, res0) and mf.same_bits(jac1, jac0) and mf.same_bits(grad1, grad0) and mf.same_bits(sq1, sq0)
+    assert same_bits(res1, res0) and same_bits(jac1, jac0) and same_bits(grad1, grad0) and same_bits(sq1, sq0)
     assert not np.array_equal(res0[0], res0[1]) and not np.array_equal(res0[1], res0[2])
 
 
@@ -209,7 +210,7 @@ def test_errors_leave_the_outputs_and_the_context_intact(oracle, cases):
     c = _new_ctx()
     try:
         c.prof_enable(True)
-        lib, p_ = c.lib, (lambda arr: arr.ctypes.data_as(C.c_void_p))
+        lib, p_ = c.lib, ptr
         msg = lambda: lib.icg_last_error(c.h).decode()
         good = priors[0]
         x = np.ascontiguousarray(points[0])
@@ -246,7 +247,7 @@ def test_errors_leave_the_outputs_and_the_context_intact(oracle, cases):
         c.marg_prior_set(*mf.set_args([good]))
         res, jac, _, _ = c.marg_prior_evaluate(x, want_jac=True)
         e, J = oracle.marg_factor_eval(good["size"], good["index"], good["x0"], x, good["J0"], good["e0"])
-        assert mf.same_bits(res, e) and mf.same_bits(jac, J)
+        assert same_bits(res, e) and same_bits(jac, J)
         assert c.prof()["marg_eval"][0] == 1
     finally:
         c.close()

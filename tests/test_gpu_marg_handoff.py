@@ -12,11 +12,9 @@ import pytest
 import marg_factor_data as mf
 import marg_handoff_data as mh
 import marg_linearize_data as ml
+from ctypes_util import bits, ptr
 
 pytestmark = pytest.mark.gpu
-
-bits = mh.bits
-
 
 def _ctx():
     import icgvins
@@ -119,7 +117,7 @@ def test_lifetime_and_errors(ctx, kept_ref):
     e0_host = np.concatenate([p["e0"].ravel() for p in host])
     x = np.concatenate(mh.set_points(priors, 100))
     res = np.zeros(int(a["r"].sum()))
-    p_ = icgvins._p
+    p_ = ptr
 
     def call(c, kid, **over):
         v = dict(src=src, r=a["r"], block_off=a["block_off"], block_size=a["block_size"], block_index=a["block_index"], x0=a["x0"], J0=J0_host, e0=e0_host)

@@ -18,6 +18,7 @@ import backend_utils as bu
 import marg_data as md
 import marg_factor_data as mf
 import marg_linearize_data as ml
+from ctypes_util import ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -161,7 +162,7 @@ def test_optional_outputs_in_every_combination(ctx, systems):
     P, m, H, b = ml.pack(some)
     r = P.astype(np.int64) - m
     nr, nrr, n = int(r.sum()), int((r * r).sum()), len(some)
-    p_ = lambda a: a.ctypes.data_as(C.c_void_p)
+    p_ = ptr
     ref = ctx.marg_linearize_batch(P, m, H, b, eps=ml.EPS)
     for want in itertools.product((False, True), repeat=5):
         bufs = dict(Hp=np.full(nrr, MARK), bp=np.full(nr, MARK), evals=np.full(nr, MARK), min_ev_m=np.full(n, MARK),

@@ -10,6 +10,7 @@ import pytest
 
 import marg_factor_data as mf
 import reproj_data as rd
+from ctypes_util import bits, ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -23,10 +24,6 @@ P = 151
 NO_PART = 3  # this window never receives a host part: +0.0 + S
 WIDE = 6     # the 151-column window: m = 6 only (about 40 ms a run)
 OUT_KEYS = ("J0", "e0", "Hp", "bp", "evals", "min_ev_m", "status")
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float64).ravel().view(np.uint64)
 
 
 def _group():
@@ -240,7 +237,7 @@ def test_keep_form_feeds_a_prior_set(world, plain):
 def test_argument_errors_name_position_and_window(world):
     import icgvins
     c = world["ctx"]
-    p_ = icgvins._p
+    p_ = ptr
     FILL = 7.25
     wins0, Pw0, m0 = np.array([4, 1, 2], np.int32), np.array([43, 7, 31], np.int32), np.array([6, 0, 15], np.int32)
     b0 = np.concatenate([world["b"][w] for w in wins0])

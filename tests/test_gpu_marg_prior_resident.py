@@ -5,9 +5,9 @@ local columns that icg_marg_prior_evaluate ships; the argument errors launch not
 import numpy as np
 import pytest
 
-import host_part_data as hp
 import marg_factor_data as mf
 import reproj_data as rd
+from ctypes_util import bits, ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -75,16 +75,16 @@ def test_resident_squared_norms_are_the_evaluate_entry_s_bits(ctx):
         x = np.concatenate(_points(priors, seed))
         res, _, _, sq = ctx.marg_prior_evaluate(x, want_sq_norm=True)
         got = ctx.marg_prior_evaluate_resident(x)
-        assert np.array_equal(hp.bits(got), hp.bits(sq)), (seed, got, sq)
+        assert np.array_equal(bits(got), bits(sq)), (seed, got, sq)
         for w, e in enumerate(mf.split(priors, res, "r")):
-            assert hp.bits(np.array([mf.sequential_sq_norm(e)]))[0] == hp.bits(got)[w], w
+            assert bits(np.array([mf.sequential_sq_norm(e)]))[0] == bits(got)[w], w
 
 
 def _same(got, ref, rebuilt):
     (gs, gd, gp), (rs, rdg, rp) = got, ref
     for w in rebuilt:
-        assert np.array_equal(hp.bits(gp[w]), hp.bits(rp[w])), ("part", w)
-        assert np.array_equal(hp.bits(gs[w]), hp.bits(rs[w])) and np.array_equal(hp.bits(gd[w]), hp.bits(rdg[w])), ("s / diag", w)
+        assert np.array_equal(bits(gp[w]), bits(rp[w])), ("part", w)
+        assert np.array_equal(bits(gs[w]), bits(rs[w])) and np.array_equal(bits(gd[w]), bits(rdg[w])), ("s / diag", w)
 
 
 def test_build_from_resident_priors_equals_build_from_shipped_ones(ctx):
@@ -132,7 +132,7 @@ def test_build_from_resident_priors_equals_build_from_shipped_ones(ctx):
     ref2 = shipped(*ref_in[1], r2)
     _same(got1, ref1, rebuilt)
     _same(got2, ref2, rebuilt)
-    assert any(not np.array_equal(hp.bits(got1[2][w]), hp.bits(got2[2][w])) or not np.array_equal(hp.bits(got1[0][w]), hp.bits(got2[0][w])) for w in (0, 1, 4))
+    assert any(not np.array_equal(bits(got1[2][w]), bits(got2[2][w])) or not np.array_equal(bits(got1[0][w]), bits(got2[0][w])) for w in (0, 1, 4))
     for got in (got1, got2):  # the window that is not rebuilt: nothing of it was written
         assert got[2][3] is None and (got[0][3] == FILL).all() and (got[1][3] == FILL).all()
     # run after run, and a gather over a kept layout: the same bits
@@ -173,7 +173,7 @@ def test_argument_errors_launch_nothing(ctx):
 
     # no set is resident
     before = ctx.prof()
-    assert ctx.lib.icg_marg_prior_evaluate_resident(ctx.h, icgvins._p(x), icgvins._p(sq)) == -1 and b"no prior set" in ctx.lib.icg_last_error(ctx.h)
+    assert ctx.lib.icg_marg_prior_evaluate_resident(ctx.h, ptr(x), ptr(sq)) == -1 and b"no prior set" in ctx.lib.icg_last_error(ctx.h)
     rc, msg = call()
     assert rc == -1 and "window 0, block 1: no prior set is resident and evaluated" in msg and untouched(), (rc, msg)
     assert nothing_launched(before) and not sq.any()
@@ -183,9 +183,9 @@ def test_argument_errors_launch_nothing(ctx):
     # a set, but not evaluated since it was set; NULL arguments of the resident evaluation
     rc, msg = call()
     assert rc == -1 and "window 0, block 1: no prior set is resident and evaluated" in msg and untouched(), (rc, msg)
-    assert ctx.lib.icg_marg_prior_evaluate_resident(ctx.h, None, icgvins._p(sq)) == -1 and b"NULL" in ctx.lib.icg_last_error(ctx.h)
-    assert ctx.lib.icg_marg_prior_evaluate_resident(ctx.h, icgvins._p(x), None) == -1 and b"NULL" in ctx.lib.icg_last_error(ctx.h)
-    assert ctx.lib.icg_marg_prior_evaluate_resident(None, icgvins._p(x), icgvins._p(sq)) == -1
+    assert ctx.lib.icg_marg_prior_evaluate_resident(ctx.h, None, ptr(sq)) == -1 and b"NULL" in ctx.lib.icg_last_error(ctx.h)
+    assert ctx.lib.icg_marg_prior_evaluate_resident(ctx.h, ptr(x), None) == -1 and b"NULL" in ctx.lib.icg_last_error(ctx.h)
+    assert ctx.lib.icg_marg_prior_evaluate_resident(None, ptr(x), ptr(sq)) == -1
     assert nothing_launched(before) and not sq.any()
     ctx.marg_prior_evaluate_resident(x)
     ctx.sync()
@@ -216,6 +216,6 @@ def test_argument_errors_launch_nothing(ctx):
     wins = [[(good["J"].reshape(3, 3), good["r"][:3], [1, 5, 2], False), (_gathered(priors[1], jac_w[1], _columns(priors[1])[1]), res_w[1], np.arange(6, 12), False)],
             [(_gathered(priors[2], jac_w[2], _columns(priors[2])[1]), res_w[2], np.arange(61), False)]]
     rs, rdg, rp = ctx.reproj_host_parts_build(70, good["Pw"], wins)
-    assert np.array_equal(hp.bits(part), hp.bits(np.concatenate(rp))) and np.array_equal(hp.bits(s), hp.bits(rs)) and np.array_equal(hp.bits(dg), hp.bits(rdg))
+    assert np.array_equal(bits(part), bits(np.concatenate(rp))) and np.array_equal(bits(s), bits(rs)) and np.array_equal(bits(dg), bits(rdg))
     after = ctx.prof()
     assert after["host_part_prior"][0] == 1 and after["host_part"][0] == 2 and after["marg_eval"][0] == before.get("marg_eval", (0, 0))[0] + 2

@@ -11,6 +11,7 @@ import pytest
 
 import ins_utils as iu
 import point_edge_data as D
+from ctypes_util import ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +42,7 @@ def test_undistort_distort_bit_exact(oracle, ctx, name):
     assert ctx.undistort(empty).shape == (0, 2) and ctx.distort(empty).shape == (0, 2)
     sentinel = np.float32([[12.5, -7.0]])  # n = 0 with a real buffer: left as it is
     buf = sentinel.copy()
-    assert ctx.lib.icg_undistort_points(ctx.h, 0, icgvins._p(buf)) == 0 and ctx.lib.icg_distort_points(ctx.h, 0, icgvins._p(buf)) == 0
+    assert ctx.lib.icg_undistort_points(ctx.h, 0, ptr(buf)) == 0 and ctx.lib.icg_distort_points(ctx.h, 0, ptr(buf)) == 0
     assert np.array_equal(buf, sentinel)
     over = D.point_set(D.MAX_POINTS + 1)
     for f in (ctx.undistort, ctx.distort):

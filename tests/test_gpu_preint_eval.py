@@ -17,6 +17,7 @@ import pytest
 
 import preint_data as pd
 import reproj_data as rd
+from ctypes_util import ErrBuf, f64, ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -36,14 +37,6 @@ def ctx():
 def hostlib():
     import harness
     return C.CDLL(harness.HOST_LIB)
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _f64(a):
-    return np.ascontiguousarray(a, np.float64)
 
 
 def _bound(exp):
@@ -165,10 +158,10 @@ def _backend_preint_device(hostlib, variant, imus, states, points):
     rh, rd_, Jh, Jd = np.zeros((n, 15)), np.zeros((n, 15)), np.zeros((n, 480)), np.zeros((n, 480))
     Sh, Sd = np.zeros((n, 225)), np.zeros((n, 225))
     okh, okd = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
-    err = C.create_string_buffer(512)
-    rc = hostlib.icgh_backend_preint_device(variant, n, _p(offsets), _p(_f64(np.concatenate(imus))), _p(_f64(np.stack(states))), _p(_f64(pd.PARAMS)),
-                                            _p(_f64(np.stack(points))), _p(cur), _p(rh), _p(Jh), _p(rd_), _p(Jd), _p(Sh), _p(Sd), _p(okh), _p(okd),
-                                            err, 512)
+    err = ErrBuf()
+    rc = hostlib.icgh_backend_preint_device(variant, n, ptr(offsets), ptr(f64(np.concatenate(imus))), ptr(f64(np.stack(states))), ptr(f64(pd.PARAMS)),
+                                            ptr(f64(np.stack(points))), ptr(cur), ptr(rh), ptr(Jh), ptr(rd_), ptr(Jd), ptr(Sh), ptr(Sd), ptr(okh), ptr(okd),
+                                            *err.args)
     assert rc == 0, (rc, err.value)
     return dict(cur=cur, rh=rh, rd=rd_, Jh=Jh, Jd=Jd, Sh=Sh, Sd=Sd, okh=okh, okd=okd)
 
@@ -264,8 +257,8 @@ def test_argument_errors_launch_nothing(oracle, ctx):
     lib = ctx.lib
 
     def call(variant=1, n_factors=n, delta=delta, cov=cov, points=points, pn_off=pn_off, pn=pn, res=res, status=status):
-        return lib.icg_preint_evaluate_batch(ctx.h, variant, n_factors, _p(delta), _p(jac), _p(cov), _p(dt), _p(env), _p(pn_off), _p(pn), _p(points),
-                                             _p(res), _p(J), _p(S), _p(status))
+        return lib.icg_preint_evaluate_batch(ctx.h, variant, n_factors, ptr(delta), ptr(jac), ptr(cov), ptr(dt), ptr(env), ptr(pn_off), ptr(pn), ptr(points),
+                                             ptr(res), ptr(J), ptr(S), ptr(status))
 
     bad_off = pn_off.copy()
     bad_off[2] = bad_off[1] - 1

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import preint_split_data as sd
+from ctypes_util import bits, ptr, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -99,14 +100,14 @@ def test_resident_evaluation_has_the_hosts_bits(ctx, host, name, kind):
     m, order = host[kind], SETS[name]
     with np.errstate(invalid="ignore"):
         r, J, sq = _run(ctx, m, order)
-        assert sd.same_bits(r, m["r_eval"][order])
-        assert sd.same_bits(J, m["J_eval"][order])
-        assert sd.same_bits(sq, _sq_norm(m["r_eval"][order]))
+        assert same_bits(r, m["r_eval"][order])
+        assert same_bits(J, m["J_eval"][order])
+        assert same_bits(sq, _sq_norm(m["r_eval"][order]))
         fin = np.isfinite(m["r_eval"][order]).all(axis=1) & (m["ok"][order] == 1)
         assert fin.any() and np.abs(J[fin]).max() > 1.0 and np.all(sq[fin] > 0)
         # residual only: the same residual and squared-norm bits, and the Jacobians of the evaluation before are no longer offered
         r0, J0, sq0 = _run(ctx, m, order, want_jac=False)
-        assert J0 is None and sd.same_bits(r0, r) and sd.same_bits(sq0, sq)
+        assert J0 is None and same_bits(r0, r) and same_bits(sq0, sq)
         res = np.zeros((len(order), 15))
         Jb = np.zeros((len(order), 480))
         assert ctx.lib.icg_preint_fetch_resident(ctx.h, res.ctypes.data_as(C.c_void_p), Jb.ctypes.data_as(C.c_void_p)) == -1
@@ -118,7 +119,7 @@ def test_the_seventh_pose_columns_are_positive_zero(ctx, host):
     for f in range(2):
         for base in (0, 240):
             blk = J[f, base:base + 105].reshape(15, 7)
-            assert np.array_equal(sd.bits(blk[:, 6]), np.zeros(15, np.uint64)) and np.abs(blk[:, :6]).max() > 0
+            assert np.array_equal(bits(blk[:, 6]), np.zeros(15, np.uint64)) and np.abs(blk[:, :6]).max() > 0
 
 
 def test_a_factor_does_not_depend_on_the_set_around_it(ctx, host):
@@ -126,11 +127,11 @@ def test_a_factor_does_not_depend_on_the_set_around_it(ctx, host):
     with np.errstate(invalid="ignore"):
         r, J, sq = _run(ctx, m, SETS["tiled_130"])
         rr, Jr, sqr = _run(ctx, m, SETS["tiled_130"][::-1])
-        assert sd.same_bits(rr[::-1], r) and sd.same_bits(Jr[::-1], J) and sd.same_bits(sqr[::-1], sq)
+        assert same_bits(rr[::-1], r) and same_bits(Jr[::-1], J) and same_bits(sqr[::-1], sq)
         for i in range(5):
             r1, J1, sq1 = _run(ctx, m, [i])
             for k in (i, 125 + i):
-                assert sd.same_bits(r1[0], r[k]) and sd.same_bits(J1[0], J[k]) and sd.same_bits(sq1[0], sq[k]), (i, k)
+                assert same_bits(r1[0], r[k]) and same_bits(J1[0], J[k]) and same_bits(sq1[0], sq[k]), (i, k)
 
 
 def test_a_second_evaluation_replaces_the_first(ctx, host):
@@ -144,8 +145,8 @@ def test_a_second_evaluation_replaces_the_first(ctx, host):
         ra, Ja = ctx.preint_fetch_resident()
         sq_b = ctx.preint_evaluate_resident(pts_b, qc_b)
         rb, Jb = ctx.preint_fetch_resident()
-        assert sd.same_bits(ra, a["r_eval"][order]) and sd.same_bits(rb, b["r_eval"][order]) and sd.same_bits(Jb, b["J_eval"][order])
-        assert not sd.same_bits(ra, rb) and sd.same_bits(sq_b, _sq_norm(b["r_eval"][order]))
+        assert same_bits(ra, a["r_eval"][order]) and same_bits(rb, b["r_eval"][order]) and same_bits(Jb, b["J_eval"][order])
+        assert not same_bits(ra, rb) and same_bits(sq_b, _sq_norm(b["r_eval"][order]))
 
 
 def test_the_given_quaternions_are_used(ctx, host):
@@ -156,16 +157,15 @@ def test_the_given_quaternions_are_used(ctx, host):
     ctx.preint_set(*set_args)
     ctx.preint_evaluate_resident(pts, ident)
     r, _ = ctx.preint_fetch_resident()
-    assert not sd.same_bits(r[0], m["r_eval"][0]) and not sd.same_bits(r[1], m["r_eval"][4])
+    assert not same_bits(r[0], m["r_eval"][0]) and not same_bits(r[1], m["r_eval"][4])
     ctx.preint_set(*(set_args[:6] + (ident,) + set_args[7:]))
     ctx.preint_evaluate_resident(pts, qc)
     r, _ = ctx.preint_fetch_resident()
-    assert sd.same_bits(r[0], m["r_eval"][0]) and not sd.same_bits(r[1], m["r_eval"][4])  # (q_nn is not read for a Normal factor)
+    assert same_bits(r[0], m["r_eval"][0]) and not same_bits(r[1], m["r_eval"][4])  # (q_nn is not read for a Normal factor)
 
 
 def test_argument_errors_launch_nothing(ctx, host):
     import icgvins
-    _p = icgvins._p
     lib = ctx.lib
     m = host["perturbed"]
     order = SETS["mixed"]
@@ -177,13 +177,13 @@ def test_argument_errors_launch_nothing(ctx, host):
     ctx.prof_enable(True)
 
     def set_(n_factors=n, variant=variant, delta=delta, jac=jac, S=S, dt=dt, env=env, qnn=qnn, pn_off=pn_off, pn=pn):
-        return lib.icg_preint_set(ctx.h, n_factors, _p(variant), _p(delta), _p(jac), _p(S), _p(dt), _p(env), _p(qnn), _p(pn_off), _p(pn))
+        return lib.icg_preint_set(ctx.h, n_factors, ptr(variant), ptr(delta), ptr(jac), ptr(S), ptr(dt), ptr(env), ptr(qnn), ptr(pn_off), ptr(pn))
 
     def eval_(pts=pts, qc=qc, want_jac=1, sq=sq):
-        return lib.icg_preint_evaluate_resident(ctx.h, _p(pts), _p(qc), want_jac, _p(sq))
+        return lib.icg_preint_evaluate_resident(ctx.h, ptr(pts), ptr(qc), want_jac, ptr(sq))
 
     def fetch(res=res, J=J):
-        return lib.icg_preint_fetch_resident(ctx.h, _p(res), _p(J))
+        return lib.icg_preint_fetch_resident(ctx.h, ptr(res), ptr(J))
 
     def nothing_launched(before):
         ctx.sync()
@@ -231,5 +231,5 @@ def test_argument_errors_launch_nothing(ctx, host):
     assert set_(n_factors=1, pn_off=None, pn=None) == 0
     assert eval_() == 0 and fetch() == 0
     with np.errstate(invalid="ignore"):
-        assert sd.same_bits(res[0], m["r_eval"][0]) and sd.same_bits(J[0], m["J_eval"][0])
+        assert same_bits(res[0], m["r_eval"][0]) and same_bits(J[0], m["J_eval"][0])
     ctx.prof_enable(False)

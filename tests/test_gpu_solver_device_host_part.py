@@ -12,6 +12,7 @@ import test_host_part_cpu as thp
 import test_host_solver_cpu as ths
 import vio_data as vd
 from host_part_data import solve_vio_batch
+from ctypes_util import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -56,9 +57,9 @@ def test_three_modes_give_identical_bits_on_visual_inertial_windows(oracle):
     assert (summ0[:, 2] > 0).all() and (summ0[:, 1] < summ0[:, 0]).all(), summ0
     for mode in (1, 2):
         st, inv, summ = res[mode]
-        assert np.array_equal(ru.bits(summ), ru.bits(summ0)), (mode, summ, summ0)
+        assert np.array_equal(bits(summ), bits(summ0)), (mode, summ, summ0)
         for w in range(len(wins)):
-            assert np.array_equal(ru.bits(st[w]), ru.bits(st0[w])) and np.array_equal(ru.bits(inv[w]), ru.bits(inv0[w])), (mode, w)
+            assert np.array_equal(bits(st[w]), bits(st0[w])) and np.array_equal(bits(inv[w]), bits(inv0[w])), (mode, w)
 
 
 def test_batch_problems_with_both_device_switches():

@@ -10,6 +10,7 @@ import pytest
 
 import preint_solve_data as qs
 import prior_solve_data as ps
+from ctypes_util import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -37,10 +38,10 @@ def host_solve(request, lib, five):
 
 def _same(a, b, n_windows):
     for w in range(n_windows):
-        assert np.array_equal(ps.bits(a[2][w]), ps.bits(b[2][w])), ("states", w)
-        assert np.array_equal(ps.bits(a[3][w]), ps.bits(b[3][w])), ("inverse depths", w)
-    assert np.array_equal(ps.bits(a[4]), ps.bits(b[4])), ("summaries", a[4], b[4])
-    assert np.array_equal(ps.bits(a[5]), ps.bits(b[5])), ("prior costs", a[5], b[5])
+        assert np.array_equal(bits(a[2][w]), bits(b[2][w])), ("states", w)
+        assert np.array_equal(bits(a[3][w]), bits(b[3][w])), ("inverse depths", w)
+    assert np.array_equal(bits(a[4]), bits(b[4])), ("summaries", a[4], b[4])
+    assert np.array_equal(bits(a[5]), bits(b[5])), ("prior costs", a[5], b[5])
 
 
 @pytest.mark.parametrize("mode", [2, 3, 4, 5])
@@ -59,7 +60,7 @@ def test_the_earth_variant_is_another_solve(lib, five):
     a = qs.solve_preint_batch(lib, wins[:2], starts[:2], priors[:2], 4, variant=0)
     b = qs.solve_preint_batch(lib, wins[:2], starts[:2], priors[:2], 4, variant=1)
     assert a[0] == 0 and b[0] == 0, (a[1], b[1])
-    assert not np.array_equal(ps.bits(a[2][0]), ps.bits(b[2][0]))
+    assert not np.array_equal(bits(a[2][0]), bits(b[2][0]))
 
 
 def test_preintegration_switch_without_the_host_part_is_refused(lib, five):
@@ -80,5 +81,5 @@ def test_a_robustified_factor_stays_on_the_pool(lib, five, variant):
     _same(out, ref, len(wins))
     assert out[6] == sum(len(w["offsets"]) - 1 for k, w in enumerate(wins) if k != 1), out[6]
     plain = qs.solve_preint_batch(lib, wins, starts, priors, 0, variant=variant, state_const=const)
-    assert not np.array_equal(ps.bits(plain[2][1]), ps.bits(ref[2][1]))  # (the loss is in window 1's solve)
-    assert np.array_equal(ps.bits(plain[2][0]), ps.bits(ref[2][0]))
+    assert not np.array_equal(bits(plain[2][1]), bits(ref[2][1]))  # (the loss is in window 1's solve)
+    assert np.array_equal(bits(plain[2][0]), bits(ref[2][0]))

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import prior_solve_data as ps
+from ctypes_util import bits
 
 pytestmark = pytest.mark.gpu
 
@@ -34,10 +35,10 @@ def test_four_modes_give_identical_bits(lib, five):
     ps.check_conditions(summ0, pcost0, priors)
     for mode in (1, 2, 3):
         st, inv, summ, pcost = res[mode]
-        assert np.array_equal(ps.bits(summ), ps.bits(summ0)), (mode, summ, summ0)
-        assert np.array_equal(ps.bits(pcost), ps.bits(pcost0)), (mode, pcost, pcost0)
+        assert np.array_equal(bits(summ), bits(summ0)), (mode, summ, summ0)
+        assert np.array_equal(bits(pcost), bits(pcost0)), (mode, pcost, pcost0)
         for w in range(len(wins)):
-            assert np.array_equal(ps.bits(st[w]), ps.bits(st0[w])) and np.array_equal(ps.bits(inv[w]), ps.bits(inv0[w])), (mode, w)
+            assert np.array_equal(bits(st[w]), bits(st0[w])) and np.array_equal(bits(inv[w]), bits(inv0[w])), (mode, w)
 
 
 def test_robust_prior_and_constant_prior_stay_bit_equal(lib, five):
@@ -54,9 +55,9 @@ def test_robust_prior_and_constant_prior_stay_bit_equal(lib, five):
         out[mode] = (st, inv, summ, pcost)
     assert (out[0][2][:, 2] > 0).all() and (out[0][3][:, 0] > 0).all(), out[0][2:]
     assert out[0][3][2, 0] == out[0][3][2, 1]  # the constant prior's cost does not move
-    assert np.array_equal(ps.bits(out[3][2]), ps.bits(out[0][2])), (out[3][2], out[0][2])
+    assert np.array_equal(bits(out[3][2]), bits(out[0][2])), (out[3][2], out[0][2])
     for w in range(3):
-        assert np.array_equal(ps.bits(out[3][0][w]), ps.bits(out[0][0][w])) and np.array_equal(ps.bits(out[3][1][w]), ps.bits(out[0][1][w])), w
+        assert np.array_equal(bits(out[3][0][w]), bits(out[0][0][w])) and np.array_equal(bits(out[3][1][w]), bits(out[0][1][w])), w
 
 
 def test_prior_switch_needs_the_host_part_switch(lib, five):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import gvins_checks as gc
+from ctypes_util import ErrBuf
 
 
 @pytest.fixture(scope="module")
@@ -90,27 +91,27 @@ def test_icg_replay_command_line(host_lib, tmp_path):
 
 def test_replay_input_errors(host_lib, tmp_path):
     lib = C.CDLL(host_lib)
-    err = C.create_string_buffer(512)
+    err = ErrBuf()
     summ = np.zeros(16)
     p = lambda s: str(s).encode()
     # missing configuration / IMU file: an error string, no crash
     rc = lib.icgh_replay_run(p(tmp_path / "none.yaml"), p(tmp_path), p(tmp_path / "imu.txt"), None, None, 0, C.c_double(0), C.c_double(0),
-                             summ.ctypes.data_as(C.c_void_p), err, 512)
+                             summ.ctypes.data_as(C.c_void_p), *err.args)
     assert rc != 0 and b"cannot open" in err.value
     # a configuration value that is not a number is refused (yaml-cpp would throw BadConversion), it is not read as 0
     cfg = tmp_path / "bad.yaml"
     cfg.write_text("outputpath: \"%s\"\ninitlength: 1\nimudatarate: fast\n" % tmp_path)
     (tmp_path / "imu.txt").write_text("100000.0 0 0 0 0 0 0\n100000.005 0 0 0 0 0 -0.049\n")
-    rc = lib.icgh_replay_run(p(cfg), None, p(tmp_path / "imu.txt"), None, None, 0, C.c_double(0), C.c_double(0), summ.ctypes.data_as(C.c_void_p), err, 512)
+    rc = lib.icgh_replay_run(p(cfg), None, p(tmp_path / "imu.txt"), None, None, 0, C.c_double(0), C.c_double(0), summ.ctypes.data_as(C.c_void_p), *err.args)
     assert rc != 0 and b"not a number" in err.value, err.value
     # a truncated image is reported with its path
     img = tmp_path / "x.pgm"
     img.write_bytes(b"P5\n8 8\n255\n" + bytes(10))
     lib.icgh_replay_load_pnm.restype = C.c_int
     dims = np.zeros(3, np.int32)
-    rc = lib.icgh_replay_load_pnm(p(img), dims.ctypes.data_as(C.c_void_p), None, 0, err, 512)
+    rc = lib.icgh_replay_load_pnm(p(img), dims.ctypes.data_as(C.c_void_p), None, 0, *err.args)
     assert rc != 0 and b"truncated" in err.value
     img.write_bytes(b"P6\n# comment\n2 1\n255\n" + bytes([1, 2, 3, 4, 5, 6]))
     out = np.zeros(6, np.uint8)
-    rc = lib.icgh_replay_load_pnm(p(img), dims.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), 6, err, 512)
+    rc = lib.icgh_replay_load_pnm(p(img), dims.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), 6, *err.args)
     assert rc == 0 and list(dims) == [1, 2, 3] and list(out) == [3, 2, 1, 6, 5, 4]  # RGB -> BGR8, as the reference's colour input

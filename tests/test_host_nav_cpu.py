@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import nav_utils as nu
+from ctypes_util import ptr
 
 
 @pytest.fixture(scope="module")
@@ -45,11 +46,11 @@ def test_nav_factor_jacobians_by_finite_differences(host):
         def res(xx):
             r = np.zeros(nr)
             xx = np.ascontiguousarray(xx)
-            assert host.icgh_nav_factor(kind, nu._p(aux), nu._p(xx), nu._p(r), None) == 0
+            assert host.icgh_nav_factor(kind, ptr(aux), ptr(xx), ptr(r), None) == 0
             return r
 
         r0, J = np.zeros(nr), np.zeros((nr, nb))
-        assert host.icgh_nav_factor(kind, nu._p(aux), nu._p(x), nu._p(r0), nu._p(J)) == 0
+        assert host.icgh_nav_factor(kind, ptr(aux), ptr(x), ptr(r0), ptr(J)) == 0
         nloc = 6 if nb == 7 else nb
         for c in range(nloc):
             h = 1e-6

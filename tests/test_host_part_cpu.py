@@ -8,7 +8,7 @@ import numpy as np
 import host_part_data as hp
 import reduced_solve_utils as ru
 import test_host_solver_cpu as ths
-from solve_utils import _p
+from ctypes_util import bits, ErrBuf, ptr
 
 NOT_BUILT = "icg_reproj_host_parts_build is not in this build"
 
@@ -28,17 +28,17 @@ def test_twin_equals_the_contract_restated():
     assert rc == 0, msg
     for w, win in enumerate(wins):
         part, sr, dr = hp.restate(hp.P_BATCH, win)
-        assert np.array_equal(hp.bits(parts[w]), hp.bits(part)), w
-        assert np.array_equal(hp.bits(s[w]), hp.bits(sr)) and np.array_equal(hp.bits(dg[w]), hp.bits(dr)), w
+        assert np.array_equal(bits(parts[w]), bits(part)), w
+        assert np.array_equal(bits(s[w]), bits(sr)) and np.array_equal(bits(dg[w]), bits(dr)), w
     # the batch sees the order of the blocks: the window built for it changes its bits when its blocks are permuted
     ow = hp.order_window()
     _, _, (a,), sa, _ = hp.twin(lib, 5, [ow])
     _, _, (b,), sb, _ = hp.twin(lib, 5, [dict(Pw=5, blocks=[ow["blocks"][k] for k in (0, 2, 1, 3)])])
-    assert not np.array_equal(hp.bits(a), hp.bits(b))
+    assert not np.array_equal(bits(a), bits(b))
     assert 0.0 < a[1] < 1e-15 and 0.9 < b[1] < 1.1  # cell (1, 0): ((1e16 + ~1) - 1e16) + 1e-16 against ((1e16 - 1e16) + ~1) + 1e-16
     # -0.0 products leave +0.0 (bit pattern 0) in the cell and in s
     rc, _, parts, s, _ = hp.twin(lib, 2, [wins[3]])
-    assert hp.bits(parts[0])[1] == 0 and hp.bits(s[0])[0] == 0
+    assert bits(parts[0])[1] == 0 and bits(s[0])[0] == 0
 
 
 def _parts(lib, problems, reduced_mode, part_mode):
@@ -55,13 +55,13 @@ def _parts(lib, problems, reduced_mode, part_mode):
     inv = np.ascontiguousarray(np.concatenate([P["start"]["invdepth"] for P in problems]))
     td = np.array([P["start"]["td"] for P in problems], np.float64)
     prior = np.ascontiguousarray(np.concatenate([P["prior"] for P in problems]))
-    summ, ms, err = np.zeros((W, 8)), C.c_double(0), C.create_string_buffer(512)
-    rc = lib.icgh_backend_solve_batch_parts(W, _p(fac_off), _p(pose_off), _p(lm_off), _p(obs), _p(ii), _p(jj), _p(ll), _p(poses), _p(ext), _p(inv), _p(td),
-                                            _p(prior), C.c_double(30.0), C.c_double(1.0), 0, 0, 6, 18, C.c_double(5.991), _p(summ), C.byref(ms), err, 512,
+    summ, ms, err = np.zeros((W, 8)), C.c_double(0), ErrBuf()
+    rc = lib.icgh_backend_solve_batch_parts(W, ptr(fac_off), ptr(pose_off), ptr(lm_off), ptr(obs), ptr(ii), ptr(jj), ptr(ll), ptr(poses), ptr(ext), ptr(inv), ptr(td),
+                                            ptr(prior), C.c_double(30.0), C.c_double(1.0), 0, 0, 6, 18, C.c_double(5.991), ptr(summ), C.byref(ms), *err.args,
                                             int(reduced_mode), int(part_mode))
     out = [dict(poses=poses[pose_off[w]:pose_off[w + 1]], ext=ext[w], invdepth=inv[lm_off[w]:lm_off[w + 1]], td=td[w:w + 1], summary=summ[w])
            for w in range(W)]
-    return rc, err.value.decode(), out
+    return rc, err.text(), out
 
 
 def test_split_of_host_factors_moved_nothing_and_missing_entry_is_named():

@@ -8,6 +8,7 @@ import pytest
 
 import schur_checks as sc
 import solve_utils as su
+from ctypes_util import bits
 
 
 @pytest.fixture(scope="module")
@@ -122,7 +123,7 @@ def test_window_solver_batch_with_a_window_without_reprojection_factors(host_lib
         ru.assert_same_results(res, pair)
     for r in empties:
         for key in ("summary", "poses", "ext", "td"):
-            assert np.array_equal(ru.bits(r[key]), ru.bits(empties[0][key])), (key, r[key], empties[0][key])
+            assert np.array_equal(bits(r[key]), bits(empties[0][key])), (key, r[key], empties[0][key])
         assert len(r["invdepth"]) == 0
         assert r["summary"][3] >= 1 and r["summary"][2] < r["summary"][0], r["summary"]
     rc, msg, alone = ru.solve_batch_mode(lib, [a], None)

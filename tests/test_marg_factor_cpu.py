@@ -9,6 +9,7 @@ import re
 import numpy as np
 
 import marg_factor_data as mf
+from ctypes_util import same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -62,14 +63,14 @@ def test_host_evaluation_equals_the_oracle_bit_for_bit():
     res_w, jac_w, grad_w = mf.split(priors, res[0], "r"), mf.split(priors, jac[0], "jac"), mf.split(priors, grad[0], "r")
     for w, (p, x) in enumerate(zip(priors, points)):
         e, J = orc.marg_factor_eval(p["size"], p["index"], p["x0"], x, p["J0"], p["e0"])
-        assert mf.same_bits(res_w[w], e), w
-        assert mf.same_bits(jac_w[w], J), w
-        assert mf.same_bits(grad_w[w], mf.sequential_gradient(p["J0"], e)), w
-        assert mf.same_bits(sq[0, w], mf.sequential_sq_norm(e)), w
+        assert same_bits(res_w[w], e), w
+        assert same_bits(jac_w[w], J), w
+        assert same_bits(grad_w[w], mf.sequential_gradient(p["J0"], e)), w
+        assert same_bits(sq[0, w], mf.sequential_sq_norm(e)), w
     # without the optional outputs the residuals are the same
     rc, msg, res2, jac2, grad2, sq2, _ = mf.backend_marg_factor(lib, 0, priors, [points], want=(False, False, False))
     assert rc == 0 and jac2 is None and grad2 is None and sq2 is None
-    assert mf.same_bits(res2, res)
+    assert same_bits(res2, res)
 
 
 def test_host_entry_rejects_an_invalid_prior():

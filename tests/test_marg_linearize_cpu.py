@@ -9,6 +9,7 @@ import re
 import numpy as np
 
 import marg_linearize_data as ml
+from ctypes_util import ErrBuf, f64, i32, ptr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MARK = -7.25
@@ -57,12 +58,12 @@ def test_host_layer_without_the_entry_point_loads_and_refuses():
     cap = 6 * poses.shape[0] + inv.shape[0] + 7
     sizes, counts, seconds = np.zeros(2, np.int32), np.zeros(2, np.int32), np.zeros(1)
     big = [np.zeros(2 * cap * cap) for _ in range(4)]
-    err = C.create_string_buffer(512)
-    p_ = bu._p
-    rc = lib.icgh_backend_marginalize_batch(2, 2, -1, C.c_double(1e-3), 1, obs.shape[1], p_(obs), p_(bu._i32(P["ii"])), p_(bu._i32(P["jj"])),
-                                            p_(bu._i32(P["ll"])), poses.shape[0], p_(poses), p_(bu._f64(w["ext"])), inv.shape[0], p_(inv),
+    err = ErrBuf()
+    p_ = ptr
+    rc = lib.icgh_backend_marginalize_batch(2, 2, -1, C.c_double(1e-3), 1, obs.shape[1], p_(obs), p_(i32(P["ii"])), p_(i32(P["jj"])),
+                                            p_(i32(P["ll"])), poses.shape[0], p_(poses), p_(f64(w["ext"])), inv.shape[0], p_(inv),
                                             C.c_double(w["td"]), C.c_double(1.0), C.c_double(100.0), 2, p_(sizes), *[p_(a) for a in big],
-                                            p_(counts), p_(seconds), err, 512)
+                                            p_(counts), p_(seconds), *err.args)
     assert rc != 0 and b"icg_marg_linearize_batch is not in this build" in err.value, (rc, err.value)
 
 
@@ -107,7 +108,7 @@ def _loops_before_the_refactoring(lib, H, b, m, eps=ml.EPS):
         n = A.shape[0]
         ev, V = np.zeros(n), np.zeros((n, n))
         if n:
-            assert lib.icgh_symmetric_eigen(n, ml._p(np.ascontiguousarray(A)), ml._p(ev), ml._p(V)) == 0
+            assert lib.icgh_symmetric_eigen(n, ptr(np.ascontiguousarray(A)), ptr(ev), ptr(V)) == 0
         return ev, V
 
     Hmm = np.array([[f(0.5) * (H[i, j] + H[j, i]) for j in range(m)] for i in range(m)]).reshape(m, m)
@@ -191,7 +192,7 @@ def _guarded_loops_before_the_refactoring(lib, H, b, m, guard=GUARD):
     Hmm = np.array([[f(0.5) * (H[i, j] + H[j, i]) for j in range(m)] for i in range(m)]).reshape(m, m)
     ev, V = np.zeros(m), np.zeros((m, m))
     if m:
-        assert lib.icgh_symmetric_eigen(m, ml._p(np.ascontiguousarray(Hmm)), ml._p(ev), ml._p(V)) == 0
+        assert lib.icgh_symmetric_eigen(m, ptr(np.ascontiguousarray(Hmm)), ptr(ev), ptr(V)) == 0
     for k in range(m):
         if not ev[k] > guard:
             return None
@@ -227,7 +228,7 @@ def _guarded_loops_before_the_refactoring(lib, H, b, m, guard=GUARD):
 def _schur_reduce_guarded(lib, s, guard=GUARD):
     r = s["P"] - s["m"]
     Hp, bp = np.full((r, r), MARK), np.full(r, MARK)
-    rc = lib.icgh_schur_reduce_guarded(s["P"], s["m"], ml._p(s["H"]), ml._p(np.ascontiguousarray(s["b"])), C.c_double(guard), ml._p(Hp), ml._p(bp))
+    rc = lib.icgh_schur_reduce_guarded(s["P"], s["m"], ptr(s["H"]), ptr(np.ascontiguousarray(s["b"])), C.c_double(guard), ptr(Hp), ptr(bp))
     return rc, Hp, bp
 
 
@@ -262,7 +263,7 @@ def test_the_guarded_schur_step_gives_the_bits_of_the_loops_it_replaces_and_refu
     assert rc == 0 and np.all(Hp == MARK) and np.all(bp == MARK)
     assert _schur_reduce_guarded(lib, s, guard=np.nextafter(smallest, 0.0))[0] == 1
     assert _schur_reduce_guarded(lib, s, guard=float("nan"))[0] == 0
-    assert lib.icgh_schur_reduce_guarded(5, 5, ml._p(s["H"]), ml._p(s["b"]), C.c_double(GUARD), ml._p(Hp), ml._p(bp)) == -1
+    assert lib.icgh_schur_reduce_guarded(5, 5, ptr(s["H"]), ptr(s["b"]), C.c_double(GUARD), ptr(Hp), ptr(bp)) == -1
 
 
 def test_the_first_guard_refuses_a_landmark_minimum_at_the_guard_or_nan_and_leaves_the_outputs():
@@ -286,8 +287,8 @@ def test_the_first_guard_refuses_a_landmark_minimum_at_the_guard_or_nan_and_leav
         args, K, L = bu.marg_problem_args(P, 1.0, 100.0)
         cap = 6 * K + L + 7
         flags, sizes, Hp, bp = np.zeros(2, np.int32), np.zeros(2, np.int32), np.zeros(cap * cap), np.zeros(cap)
-        err = C.create_string_buffer(512)
-        rc = lib.icgh_backend_marginalize_min_hll(*args, C.c_double(min_hll), ml._p(flags), ml._p(sizes), ml._p(Hp), ml._p(bp), err, 512)
+        err = ErrBuf()
+        rc = lib.icgh_backend_marginalize_min_hll(*args, C.c_double(min_hll), ptr(flags), ptr(sizes), ptr(Hp), ptr(bp), *err.args)
         assert rc == 0, (rc, err.value)
         r = int(sizes[1])
         return int(flags[0]), int(flags[1]), Hp[:r * r], bp[:r]

@@ -14,6 +14,7 @@ import pytest
 
 import marg_prior_data as mp
 import marg_resident_data as mr
+from ctypes_util import bits
 
 
 def _oracle_host():
@@ -52,7 +53,7 @@ def test_deferred_gather_yields_the_block_list_of_gather_host_blocks(gathered, w
             shift = e["nr"] * e["nf"]
             continue
         assert d["jac_off"] == e["jac_off"] - shift, k
-        assert np.array_equal(mr.bits(d["J"]), mr.bits(e["J"])) and np.array_equal(mr.bits(d["r"]), mr.bits(e["r"])), k
+        assert np.array_equal(bits(d["J"]), bits(e["J"])) and np.array_equal(bits(d["r"]), bits(e["r"])), k
     assert g["sizes"][2] == g["sizes"][3] - E[pb]["nr"] * E[pb]["nf"]  # J is shorter by exactly the prior's Jacobian
 
 
@@ -62,11 +63,11 @@ def test_j0_gathered_by_prior_cols_is_the_prior_block_and_its_residual_is_evalua
     e = g["eager"][g["prior_block"]]
     pc = g["prior_cols"]
     assert len(pc) == e["nf"] and len(set(pc)) == len(pc) and pc.min() >= 0 and pc.max() < g["r"]
-    assert np.array_equal(mr.bits(g["J0"][:, pc]), mr.bits(e["J"]))  # Jd[k][y] = J0[k][prior_cols[y]]: a copy
-    assert np.array_equal(mr.bits(g["prior_res"]), mr.bits(e["r"]))
+    assert np.array_equal(bits(g["J0"][:, pc]), bits(e["J"]))  # Jd[k][y] = J0[k][prior_cols[y]]: a copy
+    assert np.array_equal(bits(g["prior_res"]), bits(e["r"]))
     assert e["J"].any() and e["r"].any()
     if which == 2:
-        assert not np.array_equal(mr.bits(gathered[0]["prior_res"]), mr.bits(g["prior_res"]))  # (another window, another point)
+        assert not np.array_equal(bits(gathered[0]["prior_res"]), bits(g["prior_res"]))  # (another window, another point)
 
 
 @pytest.mark.parametrize("which", [0, 2])
@@ -74,8 +75,8 @@ def test_deferred_evaluation_equals_an_eager_evaluate(gathered, which):
     g = gathered[which]
     r = g["r"]
     assert len(g["def_eval"]) == len(g["eag_eval"]) > r + r * r  # residuals, then a Jacobian block per parameter block (a pose block is 7 wide)
-    assert np.array_equal(mr.bits(g["def_eval"]), mr.bits(g["eag_eval"]))
-    assert np.array_equal(mr.bits(g["def_eval"][:r]), mr.bits(g["prior_res"]))
+    assert np.array_equal(bits(g["def_eval"]), bits(g["eag_eval"]))
+    assert np.array_equal(bits(g["def_eval"][:r]), bits(g["prior_res"]))
 
 
 def test_prerequisites_are_refused_by_message_and_a_build_without_the_entries_says_so():

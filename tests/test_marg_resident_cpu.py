@@ -11,6 +11,7 @@ import numpy as np
 
 import host_part_data as hp
 import marg_resident_data as mr
+from ctypes_util import bits, ErrBuf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY = "icg_marg_linearize_resident"
@@ -62,9 +63,9 @@ def test_host_layer_without_the_entry_loads_and_refuses_by_name():
 
 def test_switch_without_the_device_linearization_is_refused_by_message():
     lib = _oracle_host()  # (a batch owns a context: on the product library this is checked with the GPU tests)
-    err = C.create_string_buffer(512)
-    assert lib.icgh_backend_marg_resident_switch_alone(err, 512) == 1, err.value
-    msg = err.value.decode()
+    err = ErrBuf()
+    assert lib.icgh_backend_marg_resident_switch_alone(*err.args) == 1, err.value
+    msg = err.text()
     assert "setDeviceReducedSystem(true) needs setDeviceLinearization(true)" in msg, msg
 
 
@@ -81,9 +82,9 @@ def _check_blocks_form_the_plan(got, twin_lib):
     assert win["blocks"], "the window has host factors"
     rc, msg, (part,), s, _ = hp.twin(twin_lib, n, [win])
     assert rc == 0, msg
-    assert np.array_equal(mr.bits(_mirror(part, n)), mr.bits(got["H"]))
-    assert np.array_equal(mr.bits(s[0]), mr.bits(got["b"]))
-    assert np.array_equal(mr.bits(got["H"]), mr.bits(got["H"].T)) and got["H"].any() and got["b"].any()
+    assert np.array_equal(bits(_mirror(part, n)), bits(got["H"]))
+    assert np.array_equal(bits(s[0]), bits(got["b"]))
+    assert np.array_equal(bits(got["H"]), bits(got["H"].T)) and got["H"].any() and got["b"].any()
 
 
 def test_gathered_blocks_form_plan_h_and_b_bit_for_bit_visual():

@@ -8,6 +8,7 @@ import re
 import numpy as np
 
 import preint_data as pd
+from ctypes_util import ErrBuf, ptr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -30,7 +31,7 @@ def test_host_layer_without_the_entry_point_loads_and_refuses():
     from stream_utils import ORACLE_HOST
     lib = C.CDLL(ORACLE_HOST)
     assert hasattr(lib, "icgh_backend_preint") and hasattr(lib, "icgh_backend_preint_device")
-    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    p = ptr
     imu = np.ascontiguousarray(pd.make_interval(21, seed=3))
     s0 = np.ascontiguousarray(pd.state()[None, :])
     ep = np.ascontiguousarray(np.concatenate([s0[0], s0[0]])[None, :])
@@ -40,9 +41,9 @@ def test_host_layer_without_the_entry_point_loads_and_refuses():
     Jh, Jd = np.full((1, 480), mark), np.full((1, 480), mark)
     Sh, Sd = np.full((1, 225), mark), np.full((1, 225), mark)
     okh, okd = np.full(1, 77, np.int32), np.full(1, 77, np.int32)
-    err = C.create_string_buffer(512)
+    err = ErrBuf()
     rc = lib.icgh_backend_preint_device(1, 1, p(offsets), p(imu), p(s0), p(np.ascontiguousarray(pd.PARAMS)), p(ep), p(cur), p(rh), p(Jh), p(rd),
-                                        p(Jd), p(Sh), p(Sd), p(okh), p(okd), err, 512)
+                                        p(Jd), p(Sh), p(Sd), p(okh), p(okd), *err.args)
     assert rc != 0
     assert b"icg_preint_evaluate_batch is not in this build" in err.value
     for a in (cur, rh, rd, Jh, Jd, Sh, Sd):

@@ -8,6 +8,7 @@ import pytest
 
 import preint_solve_data as qs
 import prior_solve_data as ps
+from ctypes_util import bits
 
 
 @pytest.fixture(scope="module")
@@ -35,8 +36,8 @@ def test_mode0_normal_variant_is_the_prior_entrys_mode0(lib, five, normal):
     assert rc0 == 0, msg0
     ps.check_conditions(summ, pcost, priors)
     for w in range(len(wins)):
-        assert np.array_equal(ps.bits(st[w]), ps.bits(st0[w])) and np.array_equal(ps.bits(inv[w]), ps.bits(inv0[w])), w
-    assert np.array_equal(ps.bits(summ), ps.bits(summ0)) and np.array_equal(ps.bits(pcost), ps.bits(pcost0))
+        assert np.array_equal(bits(st[w]), bits(st0[w])) and np.array_equal(bits(inv[w]), bits(inv0[w])), w
+    assert np.array_equal(bits(summ), bits(summ0)) and np.array_equal(bits(pcost), bits(pcost0))
 
 
 def test_mode0_earth_variant_solves_another_problem(lib, five, normal):
@@ -45,8 +46,8 @@ def test_mode0_earth_variant_solves_another_problem(lib, five, normal):
     assert rc == 0, msg
     assert (summ[:, 2] > 0).all() and (summ[:, 1] < summ[:, 0]).all(), summ  # every window's cost went down
     for w in range(len(wins)):
-        assert not np.array_equal(ps.bits(st[w]), ps.bits(normal[2][w])), w
-    assert np.array_equal(ps.bits(st[3][1]), ps.bits(starts[3][0][1]))  # a constant state did not move
+        assert not np.array_equal(bits(st[w]), bits(normal[2][w])), w
+    assert np.array_equal(bits(st[3][1]), bits(starts[3][0][1]))  # a constant state did not move
 
 
 def test_device_modes_name_the_missing_entry(lib, five):

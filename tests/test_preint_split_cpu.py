@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import preint_split_data as sd
+from ctypes_util import bits
 
 LENS = {0: [41, 17], 1: [2, 41]}  # Earth: intervals of 2 and of 41 samples (1 and 40 rows of pn)
 
@@ -31,8 +32,8 @@ def test_evaluate_given_is_evaluate_in_every_bit(lib, case, kind):
     points = [sd.eval_point(kind, states[i], cur[i]) for i in range(len(imus))]
     o = sd.eval_split(lib, variant, imus, states, points)
     assert np.all(o["ok"] == 1)
-    assert np.array_equal(sd.bits(o["r_given"]), sd.bits(o["r_eval"]))
-    assert np.array_equal(sd.bits(o["J_given"]), sd.bits(o["J_eval"]))
+    assert np.array_equal(bits(o["r_given"]), bits(o["r_eval"]))
+    assert np.array_equal(bits(o["J_given"]), bits(o["J_eval"]))
     # the evaluation is not trivial: finite, non-zero rows for the 17- and 41-sample intervals (the 2-sample interval's information is not
     # positive definite: NaN in every entry, on both paths)
     for i, n in enumerate(LENS[variant]):
@@ -60,8 +61,8 @@ def test_the_given_quaternion_is_used(lib, case):
     i = LENS[variant].index(41)
     assert np.all(o["ok"] == 1)
     assert not np.array_equal(o["q_corr"][i], wrong[i])
-    assert not np.array_equal(sd.bits(o["r_given"][i]), sd.bits(o["r_eval"][i]))
-    assert not np.array_equal(sd.bits(o["J_given"][i]), sd.bits(o["J_eval"][i]))
+    assert not np.array_equal(bits(o["r_given"][i]), bits(o["r_eval"][i]))
+    assert not np.array_equal(bits(o["J_given"][i]), bits(o["J_eval"][i]))
     assert np.abs(o["r_given"][i] - o["r_eval"][i]).max() > 1e-3  # (a correction of about 0.02 rad is missing, not an ulp)
 
 

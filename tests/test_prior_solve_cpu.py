@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import prior_solve_data as ps
+from ctypes_util import bits
 
 
 @pytest.fixture(scope="module")
@@ -37,12 +38,12 @@ def test_mode0_final_cost_is_what_the_priors_evaluate_predicts(lib, five):
     # the same windows without their priors reach another optimum: the prior took part in the solve
     rc, msg, st_n, _, summ_n, _ = ps.solve_prior_batch(lib, wins, starts, [None] * len(wins), 0, state_const=const)
     assert rc == 0, msg
-    assert np.array_equal(ps.bits(st_n[1]), ps.bits(st[1])) and summ_n[1, 1] == summ[1, 1]  # (the window without a prior: the same solve)
+    assert np.array_equal(bits(st_n[1]), bits(st[1])) and summ_n[1, 1] == summ[1, 1]  # (the window without a prior: the same solve)
     for w, p in enumerate(priors):
         if p is not None:
-            assert summ_n[w, 1] < summ[w, 1] and not np.array_equal(ps.bits(st_n[w]), ps.bits(st[w])), w
+            assert summ_n[w, 1] < summ[w, 1] and not np.array_equal(bits(st_n[w]), bits(st[w])), w
     # a constant state did not move
-    assert np.array_equal(ps.bits(st[3][1]), ps.bits(starts[3][0][1]))
+    assert np.array_equal(bits(st[3][1]), bits(starts[3][0][1]))
 
 
 def test_device_modes_name_the_missing_entry(lib, five):

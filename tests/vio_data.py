@@ -6,29 +6,21 @@ import numpy as np
 
 import preint_data as pd
 import reproj_data as rd
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _ptrs(arrays):
-    return (C.c_void_p * len(arrays))(*[None if a is None else a.ctypes.data for a in arrays])
+from ctypes_util import ErrBuf, f64, i32, ptr, ptrs
 
 
 def batch_leading_args(wins, starts, iters, prior_weight, huber):
     """The arguments W .. iters that icgh_backend_solve_vio_batch and icgh_backend_solve_prior_batch share, for windows of make_vio_window from the
     given (states, invdepth) starts -> (args, states, invdepth, keep): states / invdepth are the copies the entry updates in place; keep holds
     every array a pointer table in args names and has to live until the call returns"""
-    i32, f64 = (lambda a: np.ascontiguousarray(a, np.int32)), (lambda a: np.ascontiguousarray(a, np.float64))
     st, inv = [f64(s).copy() for s, _ in starts], [f64(v).copy() for _, v in starts]
     offsets, imu = [i32(w["offsets"]) for w in wins], [f64(w["imu"]) for w in wins]
     obs, ii, jj, ll = ([f64(w["obs"]) for w in wins], [i32(w["ii"]) for w in wins], [i32(w["jj"]) for w in wins], [i32(w["ll"]) for w in wins])
     ext, td = [f64(w["ext"]).copy() for w in wins], f64([w["td"] for w in wins])
     pose0, mix0 = [f64(w["states"][0, :7]) for w in wins], [f64(w["states"][0, 7:]) for w in wins]
     n_int, n_fac, n_lm = i32([len(o) - 1 for o in offsets]), i32([o.shape[1] for o in obs]), i32([len(v) for v in inv])
-    args = [len(wins), _p(n_int), _ptrs(offsets), _ptrs(imu), _p(f64(pd.PARAMS)), _ptrs(st), _p(n_fac), _ptrs(obs), _ptrs(ii), _ptrs(jj), _ptrs(ll), _ptrs(ext),
-            _p(n_lm), _ptrs(inv), _p(td), _ptrs(pose0), _ptrs(mix0), C.c_double(prior_weight), C.c_double(huber), int(iters)]
+    args = [len(wins), ptr(n_int), ptrs(offsets), ptrs(imu), ptr(f64(pd.PARAMS)), ptrs(st), ptr(n_fac), ptrs(obs), ptrs(ii), ptrs(jj), ptrs(ll), ptrs(ext),
+            ptr(n_lm), ptrs(inv), ptr(td), ptrs(pose0), ptrs(mix0), C.c_double(prior_weight), C.c_double(huber), int(iters)]
     return args, st, inv, [offsets, imu, obs, ii, jj, ll, ext, pose0, mix0]
 
 
@@ -89,10 +81,10 @@ def host_solve_vio(lib, W, states, inv, prior_weight=100.0, huber=1.0, iters=25)
     st, inv = np.ascontiguousarray(states).copy(), np.ascontiguousarray(inv).copy()
     ext, td = W["ext"].copy(), np.array([W["td"]])
     summ = np.zeros(4)
-    err = C.create_string_buffer(512)
+    err = ErrBuf()
     n = W["obs"].shape[1]
-    rc = lib.icgh_backend_solve_vio(len(W["offsets"]) - 1, _p(W["offsets"]), _p(W["imu"]), _p(np.ascontiguousarray(pd.PARAMS)), _p(st), n, _p(W["obs"]),
-                                    _p(W["ii"]), _p(W["jj"]), _p(W["ll"]), _p(ext), len(inv), _p(inv), _p(td),
-                                    _p(np.ascontiguousarray(W["states"][0, :7])), _p(np.ascontiguousarray(W["states"][0, 7:])), C.c_double(prior_weight), C.c_double(huber), int(iters), _p(summ), err, 512)
+    rc = lib.icgh_backend_solve_vio(len(W["offsets"]) - 1, ptr(W["offsets"]), ptr(W["imu"]), ptr(np.ascontiguousarray(pd.PARAMS)), ptr(st), n, ptr(W["obs"]),
+                                    ptr(W["ii"]), ptr(W["jj"]), ptr(W["ll"]), ptr(ext), len(inv), ptr(inv), ptr(td),
+                                    ptr(np.ascontiguousarray(W["states"][0, :7])), ptr(np.ascontiguousarray(W["states"][0, 7:])), C.c_double(prior_weight), C.c_double(huber), int(iters), ptr(summ), *err.args)
     assert rc == 0, (rc, err.value)
     return st, inv, summ
