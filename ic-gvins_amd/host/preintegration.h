@@ -28,7 +28,8 @@ struct IntegrationState { // preintegration/integration_state.h:35-52 (fields us
     Quaterniond q;
     Vector3d v, bg, ba;
     Vector3d sg, sa; // gyroscope / accelerometer scale factors (used by MISC::insMechanization when iswithscale)
-    double sodo{0};  // odometer scale factor (only written out by MISC::writeNavResult)
+    double sodo{0};  // odometer scale factor (written out by MISC::writeNavResult; estimated by the odometer variants, preintegration_odo.h)
+    Vector3d s;      // preintegrated distance of the odometer variants (integration_state.h:45); zero elsewhere
 };
 struct IntegrationParameters { // integration_state.h:67-88
     double acc_vrw{0}, gyr_arw{0}, gyr_bias_std{0}, acc_bias_std{0}, corr_time{1}, gravity{9.8};
@@ -37,6 +38,11 @@ struct IntegrationParameters { // integration_state.h:67-88
     // PreintegrationEarth::resetState does (preintegration_earth.cc:319-321); otherwise `iewn` above is used as given
     bool has_station{false};
     Vector3d station;
+    // the odometer variants only (preintegration_odo.h; integration_state.h:82-86): white noise of the odometer [m/s], random walk of its scale
+    // factor, installation angles between the body and the vehicle frame [rad], lever arm of the odometer in the body frame [m]
+    Vector3d odo_std;
+    double odo_srw{0};
+    Vector3d abv, lodo;
 };
 
 // One IMU interval between two time nodes.  (Re)integration of many intervals is ONE batched device call.

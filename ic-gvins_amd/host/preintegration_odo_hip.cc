@@ -1,0 +1,494 @@
+// Odometer preintegration on the HIP C ABI: P1 (the per-sample inner loop of PreintegrationOdo / PreintegrationEarthOdo) runs batched on the
+// device through icg_preint_odo_batch; P2 (residual 19 + Jacobians, preintegration_odo.cc:40-159 / preintegration_earth_odo.cc:41-183,
+// wrapped by preintegration_factor.h:45-69) is evaluated on the host per factor (evaluate) or for many factors at once on the device
+// (evaluateBatch, icg_preint_odo_evaluate_batch).  The 19-state twin of preintegration_hip.cc, which stays as it is: the small-matrix helpers
+// below repeat that file's (same expressions, same order) so that nothing the 15-state bit-for-bit tests rest on moves.
+#include <cmath>
+#include <cstring>
+
+#include "earth.h"
+#include "preintegration_odo.h"
+
+// A build of this layer on another implementation of the C ABI (the CPU checker library) does not have the entry points: the references stay
+// weak (null when absent) and the callers report it; the product library links libicgvins_hip.so, which defines them.
+#pragma weak icg_preint_odo_batch
+#pragma weak icg_preint_odo_evaluate_batch
+
+namespace icg {
+
+namespace {
+constexpr int N = PreintegrationOdo::NUM_STATE, NN = N * N;
+
+struct V3 {
+    double x, y, z;
+};
+struct Q4 {
+    double x, y, z, w;
+};
+struct M3 {
+    double m[3][3];
+};
+inline V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+inline V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+inline V3 operator*(V3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
+inline V3 operator*(double s, V3 a) { return {a.x * s, a.y * s, a.z * s}; }
+inline V3 operator-(V3 a) { return {-a.x, -a.y, -a.z}; }
+inline V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+inline Q4 qinv(Q4 q) {
+    double n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
+    return {-q.x / n2, -q.y / n2, -q.z / n2, q.w / n2};
+}
+inline Q4 qmul(Q4 a, Q4 b) {
+    return {a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z,
+            a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
+}
+inline V3 qrot(Q4 q, V3 v) {
+    V3 qv{q.x, q.y, q.z};
+    V3 uv = cross(qv, v);
+    uv    = uv + uv;
+    return v + q.w * uv + cross(qv, uv);
+}
+inline M3 qmat(Q4 q) {
+    double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z, twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
+    double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x, tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
+    return M3{{{1 - (tyy + tzz), txy - twz, txz + twy}, {txy + twz, 1 - (txx + tzz), tyz - twx}, {txz - twy, tyz + twx, 1 - (txx + tyy)}}};
+}
+inline Q4 rotvec2quat(V3 rv) {
+    double angle = std::sqrt(rv.x * rv.x + rv.y * rv.y + rv.z * rv.z);
+    V3 axis      = rv;
+    if (angle > 0) axis = rv * (1.0 / angle);
+    double s = std::sin(0.5 * angle), c = std::cos(0.5 * angle);
+    return {s * axis.x, s * axis.y, s * axis.z, c};
+}
+inline M3 skew(V3 v) { return M3{{{0, -v.z, v.y}, {v.z, 0, -v.x}, {-v.y, v.x, 0}}}; }
+inline M3 eye() { return M3{{{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}}; }
+inline M3 scale(const M3 &a, double s) {
+    M3 r;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) r.m[i][j] = a.m[i][j] * s;
+    return r;
+}
+inline M3 add(const M3 &a, const M3 &b) {
+    M3 r;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) r.m[i][j] = a.m[i][j] + b.m[i][j];
+    return r;
+}
+inline M3 mul(const M3 &a, const M3 &b) {
+    M3 r;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) r.m[i][j] = a.m[i][0] * b.m[0][j] + a.m[i][1] * b.m[1][j] + a.m[i][2] * b.m[2][j];
+    return r;
+}
+inline V3 mv(const M3 &a, V3 v) {
+    return {a.m[0][0] * v.x + a.m[0][1] * v.y + a.m[0][2] * v.z, a.m[1][0] * v.x + a.m[1][1] * v.y + a.m[1][2] * v.z,
+            a.m[2][0] * v.x + a.m[2][1] * v.y + a.m[2][2] * v.z};
+}
+inline M3 qleft_br(Q4 q) { return add(scale(eye(), q.w), skew({q.x, q.y, q.z})); }
+inline M3 qright_br(Q4 q) { return add(scale(eye(), q.w), scale(skew({q.x, q.y, q.z}), -1.0)); }
+M3 qleft_qright_br(Q4 a, Q4 b) { // bottom-right 3x3 of quaternionleft(a) * quaternionright(b), rotation.h:103-119
+    double L[4][4], R[4][4];
+    auto fill = [](double M[4][4], Q4 q, double sgn) {
+        M[0][0] = q.w;
+        M[0][1] = -q.x, M[0][2] = -q.y, M[0][3] = -q.z;
+        M[1][0] = q.x, M[2][0] = q.y, M[3][0] = q.z;
+        M3 s = skew({q.x, q.y, q.z});
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) M[1 + i][1 + j] = (i == j ? q.w : 0.0) + sgn * s.m[i][j];
+    };
+    fill(L, a, 1.0);
+    fill(R, b, -1.0);
+    M3 out;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            double s = 0;
+            for (int k = 0; k < 4; k++) s += L[1 + i][k] * R[k][1 + j];
+            out.m[i][j] = s;
+        }
+    return out;
+}
+
+// rows of icg_preint_odo_batch: state0 17 (p3, q4 xyzw, v3, bg3, ba3, sodo), cur_state 16, delta_state 20 (the 16, s3, sodo)
+void stateToArray16(const IntegrationState &s, double *a) {
+    a[0] = s.p[0], a[1] = s.p[1], a[2] = s.p[2];
+    a[3] = s.q.x, a[4] = s.q.y, a[5] = s.q.z, a[6] = s.q.w;
+    for (int i = 0; i < 3; i++) {
+        a[7 + i]  = s.v[i];
+        a[10 + i] = s.bg[i];
+        a[13 + i] = s.ba[i];
+    }
+}
+void stateFromArray16(const double *a, IntegrationState &s) {
+    s.p  = Vector3d(a[0], a[1], a[2]);
+    s.q  = Quaterniond{a[3], a[4], a[5], a[6]};
+    s.v  = Vector3d(a[7], a[8], a[9]);
+    s.bg = Vector3d(a[10], a[11], a[12]);
+    s.ba = Vector3d(a[13], a[14], a[15]);
+}
+void deltaToArray20(const IntegrationState &s, double *a) {
+    stateToArray16(s, a);
+    a[16] = s.s[0], a[17] = s.s[1], a[18] = s.s[2], a[19] = s.sodo;
+}
+void deltaFromArray20(const double *a, IntegrationState &s) {
+    stateFromArray16(a, s);
+    s.s    = Vector3d(a[16], a[17], a[18]);
+    s.sodo = a[19];
+}
+
+// preintegration_earth_odo.cc:364-366 (resetState, run by the constructor and by every reintegration)
+void refreshEarthRate(const IntegrationParameters &P, const IntegrationState &state, Vector3d &iewn) {
+    iewn = P.has_station ? Earth::iewn(P.station, state.p) : P.iewn;
+}
+} // namespace
+
+void PreintegrationOdo::vehicleRotation(const Vector3d &abv, double cvb[9]) {
+    // R = Rz(abv[2]) Ry(abv[1]) Rx(abv[0]); cvb = R^T
+    const double sx = std::sin(abv[0]), cx = std::cos(abv[0]), sy = std::sin(abv[1]), cy = std::cos(abv[1]), sz = std::sin(abv[2]), cz = std::cos(abv[2]);
+    const double R[3][3] = {{cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx}, {sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx}, {-sy, cy * sx, cy * cx}};
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) cvb[i * 3 + j] = R[j][i];
+}
+
+PreintegrationOdo::PreintegrationOdo(std::shared_ptr<IntegrationParameters> parameters, const IMU &imu0, const IntegrationState &state, Variant v)
+    : parameters_(std::move(parameters)), variant_(v), start_state_(state), current_state_(state) {
+    imu_buffer_.push_back(imu0);
+    delta_state_.bg   = state.bg;
+    delta_state_.ba   = state.ba;
+    delta_state_.sodo = state.sodo;
+    jacobian_.assign(NN, 0.0);
+    covariance_.assign(NN, 0.0);
+    sqrt_information_.assign(NN, 0.0);
+    for (int i = 0; i < N; i++) jacobian_[(size_t) i * (N + 1)] = 1.0;
+    refreshEarthRate(*parameters_, state, iewn_);
+}
+
+void PreintegrationOdo::reintegration(const IntegrationState &state) {
+    start_state_ = state;
+    dirty_       = true;
+    if (variant_ == EARTH_ODO) refreshEarthRate(*parameters_, state, iewn_);
+}
+
+bool PreintegrationOdo::integrateBatchAvailable() { return &icg_preint_odo_batch != nullptr; }
+bool PreintegrationOdo::evaluateBatchAvailable() { return &icg_preint_odo_evaluate_batch != nullptr; }
+
+void PreintegrationOdo::setIntegrationResult(const double *cur16, const double *delta20, const double *jac361, const double *cov361,
+                                             double delta_time, const double *pn, int pn_rows, const Vector3d &iewn) {
+    stateFromArray16(cur16, current_state_);
+    current_state_.sodo = start_state_.sodo;
+    current_state_.time = imu_buffer_.back().time;
+    deltaFromArray20(delta20, delta_state_);
+    jacobian_.assign(jac361, jac361 + NN);
+    covariance_.assign(cov361, cov361 + NN);
+    delta_time_ = delta_time;
+    pn_.assign(pn, pn + (pn ? 4 * (size_t) (pn_rows > 0 ? pn_rows : 0) : 0));
+    iewn_ = iewn;
+    updateSqrtInformation();
+    dirty_ = false;
+}
+
+bool PreintegrationOdo::integrateBatch(icg_ctx *ctx, const vector<PreintegrationOdo *> &list, std::string *err) {
+    if (!integrateBatchAvailable()) {
+        if (err) *err = "icg_preint_odo_batch is not in this build";
+        return false;
+    }
+    // one launch per (variant, parameter values): icg_preint_odo_batch takes one parameter vector per call, and every interval must be
+    // integrated with ITS OWN Earth rate (the one evaluate() uses).  Intervals of one estimator share their values in practice.
+    auto paramsOf = [](const PreintegrationOdo *p, double *out25) {
+        const IntegrationParameters &P = *p->parameters_;
+        const double v[13] = {P.gyr_arw, P.acc_vrw, P.gyr_bias_std, P.acc_bias_std, P.corr_time, P.gravity, p->iewn_[0], p->iewn_[1], p->iewn_[2],
+                              P.odo_std[0], P.odo_std[1], P.odo_std[2], P.odo_srw};
+        memcpy(out25, v, sizeof v);
+        vehicleRotation(P.abv, out25 + 13);
+        out25[22] = P.lodo[0], out25[23] = P.lodo[1], out25[24] = P.lodo[2];
+    };
+    vector<PreintegrationOdo *> pending;
+    for (auto *p : list)
+        if (p->dirty_) pending.push_back(p);
+    while (!pending.empty()) {
+        double params[25];
+        paramsOf(pending[0], params);
+        const int variant = (int) pending[0]->variant_;
+        vector<PreintegrationOdo *> todo, rest;
+        for (auto *p : pending) {
+            double q[25];
+            paramsOf(p, q);
+            ((int) p->variant_ == variant && memcmp(q, params, sizeof q) == 0 ? todo : rest).push_back(p);
+        }
+        pending.swap(rest);
+        vector<int32_t> offsets{0};
+        vector<double> imu, state0;
+        for (auto *p : todo) {
+            for (const IMU &s : p->imu_buffer_) {
+                const double row[9] = {s.time, s.dt, s.dtheta[0], s.dtheta[1], s.dtheta[2], s.dvel[0], s.dvel[1], s.dvel[2], s.odovel};
+                imu.insert(imu.end(), row, row + 9);
+            }
+            offsets.push_back((int32_t) (imu.size() / 9));
+            double a[17];
+            stateToArray16(p->start_state_, a);
+            a[16] = p->start_state_.sodo;
+            state0.insert(state0.end(), a, a + 17);
+        }
+        const size_t n = todo.size(), total = imu.size() / 9;
+        vector<double> cur(16 * n), del(20 * n), jac((size_t) NN * n), cov((size_t) NN * n), dt(n), pn(4 * total);
+        int rc = icg_preint_odo_batch(ctx, variant, (int) n, offsets.data(), imu.data(), state0.data(), params, cur.data(), del.data(),
+                                      jac.data(), cov.data(), dt.data(), pn.data());
+        if (rc != ICG_OK) {
+            if (err) *err = icg_last_error(ctx);
+            return false;
+        }
+        for (size_t k = 0; k < n; k++) {
+            PreintegrationOdo *p = todo[k];
+            const int b = offsets[k], cnt = offsets[k + 1] - offsets[k];
+            p->setIntegrationResult(&cur[16 * k], &del[20 * k], &jac[(size_t) NN * k], &cov[(size_t) NN * k], dt[k],
+                                    variant == (int) EARTH_ODO ? &pn[4 * (size_t) b] : nullptr, cnt - 1, p->iewn_);
+        }
+    }
+    return true;
+}
+
+bool PreintegrationOdo::evaluateBatch(icg_ctx *ctx, const vector<const PreintegrationOdo *> &list, const double *points, double *residuals,
+                                      double *jacobians, vector<char> *ok, std::string *err, double *sqrt_info) {
+    if (!evaluateBatchAvailable()) {
+        if (err) *err = "icg_preint_odo_evaluate_batch is not in this build";
+        return false;
+    }
+    const size_t n_all = list.size();
+    if (ok) ok->assign(n_all, 0);
+    memset(residuals, 0, sizeof(double) * N * n_all);
+    if (jacobians) memset(jacobians, 0, sizeof(double) * NUM_JAC * n_all);
+    if (sqrt_info) memset(sqrt_info, 0, sizeof(double) * NN * n_all);
+    for (int variant = (int) ODO; variant <= (int) EARTH_ODO; variant++) {
+        vector<size_t> idx; // the integrated factors of this variant, list order
+        for (size_t k = 0; k < n_all; k++)
+            if ((int) list[k]->variant_ == variant && !list[k]->dirty_) idx.push_back(k);
+        if (idx.empty()) continue;
+        const size_t n = idx.size();
+        vector<double> del(20 * n), jac(NN * n), cov(NN * n), dt(n), env(4 * n), pts(34 * n), pn;
+        vector<int32_t> pn_off{0};
+        for (size_t j = 0; j < n; j++) {
+            const PreintegrationOdo &p = *list[idx[j]];
+            deltaToArray20(p.delta_state_, &del[20 * j]);
+            memcpy(&jac[NN * j], p.jacobian_.data(), sizeof(double) * NN);
+            memcpy(&cov[NN * j], p.covariance_.data(), sizeof(double) * NN);
+            dt[j]          = p.delta_time_;
+            env[4 * j]     = p.parameters_->gravity;
+            env[4 * j + 1] = p.iewn_[0], env[4 * j + 2] = p.iewn_[1], env[4 * j + 3] = p.iewn_[2];
+            memcpy(&pts[34 * j], points + 34 * idx[j], sizeof(double) * 34);
+            if (variant == (int) EARTH_ODO) {
+                pn.insert(pn.end(), p.pn_.begin(), p.pn_.begin() + (long) (p.pn_.size() / 4 * 4));
+                pn_off.push_back((int32_t) (pn.size() / 4));
+            }
+        }
+        vector<double> r(N * n), J(jacobians ? NUM_JAC * n : 0), S(sqrt_info ? NN * n : 0);
+        vector<int32_t> status(n);
+        if (pn.empty()) pn.resize(4); // (a valid pointer for a batch without rows)
+        const bool earth = variant == (int) EARTH_ODO;
+        int rc = icg_preint_odo_evaluate_batch(ctx, variant, (int) n, del.data(), jac.data(), cov.data(), dt.data(), env.data(),
+                                               earth ? pn_off.data() : nullptr, earth ? pn.data() : nullptr, pts.data(), r.data(),
+                                               jacobians ? J.data() : nullptr, sqrt_info ? S.data() : nullptr, status.data());
+        if (rc != ICG_OK) {
+            if (err) *err = icg_last_error(ctx);
+            return false;
+        }
+        for (size_t j = 0; j < n; j++) {
+            const size_t k = idx[j];
+            memcpy(residuals + N * k, &r[N * j], sizeof(double) * N);
+            if (jacobians) memcpy(jacobians + NUM_JAC * k, &J[NUM_JAC * j], sizeof(double) * NUM_JAC);
+            if (sqrt_info) memcpy(sqrt_info + NN * k, &S[NN * j], sizeof(double) * NN);
+            if (ok) (*ok)[k] = status[j] == 0 ? 1 : 0;
+        }
+    }
+    return true;
+}
+
+// sqrt_information = LLT(cov^-1).matrixL().transpose()  (odo :42-43, earth_odo :43-44).  The reference forms it inside every evaluate(); it
+// only depends on the covariance, so it is formed once when an integration result arrives.  Preintegration::updateSqrtInformation at 19:
+// Gauss-Jordan with partial pivoting on the 19 x 38 augmented matrix, mirrored lower triangle, column Cholesky (k_preint_odo_sqrt_info
+// repeats this arithmetic in this order).
+void PreintegrationOdo::updateSqrtInformation() {
+    typedef double MN[N][N];
+    MN cov, inv, L;
+    memcpy(cov, covariance_.data(), sizeof cov);
+    sqrt_information_ok_ = false;
+    sqrt_information_.assign(NN, 0.0);
+    double w[N][2 * N];
+    for (int i = 0; i < N; i++)
+        for (int j = 0; j < N; j++) {
+            w[i][j]     = cov[i][j];
+            w[i][N + j] = (i == j) ? 1.0 : 0.0;
+        }
+    for (int c = 0; c < N; c++) {
+        int piv = c;
+        for (int r = c + 1; r < N; r++)
+            if (std::fabs(w[r][c]) > std::fabs(w[piv][c])) piv = r;
+        if (w[piv][c] == 0.0) return;
+        if (piv != c)
+            for (int j = 0; j < 2 * N; j++) std::swap(w[c][j], w[piv][j]);
+        double d = w[c][c];
+        for (int j = 0; j < 2 * N; j++) w[c][j] /= d;
+        for (int r = 0; r < N; r++)
+            if (r != c) {
+                double f = w[r][c];
+                if (f != 0.0)
+                    for (int j = 0; j < 2 * N; j++) w[r][j] -= f * w[c][j];
+            }
+    }
+    for (int i = 0; i < N; i++)
+        for (int j = 0; j < N; j++) inv[i][j] = w[i][N + j];
+    for (int i = 0; i < N; i++)
+        for (int j = 0; j < i; j++) inv[j][i] = inv[i][j];
+    memset(L, 0, sizeof L);
+    for (int j = 0; j < N; j++) {
+        double s = inv[j][j];
+        for (int k = 0; k < j; k++) s -= L[j][k] * L[j][k];
+        L[j][j] = std::sqrt(s);
+        for (int i = j + 1; i < N; i++) {
+            double t = inv[i][j];
+            for (int k = 0; k < j; k++) t -= L[i][k] * L[j][k];
+            L[i][j] = t / L[j][j];
+        }
+    }
+    for (int i = 0; i < N; i++)
+        for (int j = 0; j < N; j++) sqrt_information_[(size_t) i * N + j] = L[j][i];
+    sqrt_information_ok_ = true;
+}
+
+bool PreintegrationOdo::evaluate(const double *const *parameters, double *residuals, double **jacobians) const {
+    if (dirty_) return false;                // not integrated for the current buffer/start state: evaluation failed, loudly
+    if (!sqrt_information_ok_) return false; // singular covariance
+    typedef double MN[N][N];
+    MN jac, S;
+    memcpy(jac, jacobian_.data(), sizeof jac);
+    memcpy(S, sqrt_information_.data(), sizeof S);
+    // constructState (odo :185-204)
+    const double *pose0 = parameters[0], *mix0 = parameters[1], *pose1 = parameters[2], *mix1 = parameters[3];
+    V3 p0{pose0[0], pose0[1], pose0[2]}, p1{pose1[0], pose1[1], pose1[2]};
+    Q4 q0{pose0[3], pose0[4], pose0[5], pose0[6]}, q1{pose1[3], pose1[4], pose1[5], pose1[6]};
+    V3 v0{mix0[0], mix0[1], mix0[2]}, bg0{mix0[3], mix0[4], mix0[5]}, ba0{mix0[6], mix0[7], mix0[8]};
+    V3 v1{mix1[0], mix1[1], mix1[2]}, bg1{mix1[3], mix1[4], mix1[5]}, ba1{mix1[6], mix1[7], mix1[8]};
+    const double sodo0 = mix0[9], sodo1 = mix1[9];
+    V3 gravity{0, 0, parameters_->gravity};
+    V3 iewn{iewn_[0], iewn_[1], iewn_[2]};
+    const IntegrationState &d = delta_state_;
+    V3 dp{d.p[0], d.p[1], d.p[2]}, dv{d.v[0], d.v[1], d.v[2]}, dbg0{d.bg[0], d.bg[1], d.bg[2]}, dba0{d.ba[0], d.ba[1], d.ba[2]};
+    V3 dsd{d.s[0], d.s[1], d.s[2]};
+    Q4 dq{d.q.x, d.q.y, d.q.z, d.q.w};
+    auto blk = [&](int r, int c) {
+        M3 b;
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) b.m[i][j] = jac[r + i][c + j];
+        return b;
+    };
+    M3 dp_dbg = blk(0, 9), dp_dba = blk(0, 12), dv_dbg = blk(3, 9), dv_dba = blk(3, 12), dq_dbg = blk(6, 9), ds_dbg = blk(15, 9);
+    V3 ds_dsodo{jac[15][18], jac[16][18], jac[17][18]};
+    V3 dbg = bg0 - dbg0, dba = ba0 - dba0;
+    const double dsodo = sodo0 - d.sodo;
+    V3 corrected_p = dp + mv(dp_dba, dba) + mv(dp_dbg, dbg);
+    V3 corrected_v = dv + mv(dv_dba, dba) + mv(dv_dbg, dbg);
+    Q4 corrected_q = qmul(dq, rotvec2quat(mv(dq_dbg, dbg)));
+    V3 corrected_s = dsd + mv(ds_dbg, dbg) + dsodo * ds_dsodo;
+    const double T = delta_time_;
+
+    double r[N];
+    double J0[N][7], J1[N][10], J2[N][7], J3[N][10];
+    memset(J0, 0, sizeof J0);
+    memset(J1, 0, sizeof J1);
+    memset(J2, 0, sizeof J2);
+    memset(J3, 0, sizeof J3);
+    auto put = [](auto &J, int r0, int c0, const M3 &b) {
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) J[r0 + i][c0 + j] = b.m[i][j];
+    };
+    M3 cnb0 = qmat(qinv(q0));
+    V3 rds;
+    if (variant_ == ODO) {
+        V3 dpn = p1 - p0 - v0 * T - 0.5 * gravity * T * T;
+        V3 dvn = v1 - v0 - gravity * T;
+        V3 rdp = qrot(qinv(q0), dpn), rdv = qrot(qinv(q0), dvn);
+        rds    = qrot(qinv(q0), p1 - p0);
+        V3 rp = rdp - corrected_p, rv = rdv - corrected_v;
+        Q4 qe = qmul(qmul(qinv(corrected_q), qinv(q0)), q1);
+        r[0] = rp.x, r[1] = rp.y, r[2] = rp.z, r[3] = rv.x, r[4] = rv.y, r[5] = rv.z, r[6] = 2 * qe.x, r[7] = 2 * qe.y, r[8] = 2 * qe.z;
+        put(J0, 0, 0, scale(cnb0, -1.0));
+        put(J0, 0, 3, skew(rdp));
+        put(J0, 3, 3, skew(rdv));
+        put(J0, 6, 3, scale(qleft_qright_br(qmul(qinv(q1), q0), corrected_q), -1.0));
+        put(J2, 0, 0, cnb0);
+        put(J2, 6, 3, qleft_br(qe));
+        put(J1, 6, 3, mul(scale(qleft_br(qmul(qmul(qinv(q1), q0), dq)), -1.0), dq_dbg));
+    } else {
+        M3 iewn_skew = skew(iewn);
+        V3 p_cor{0, 0, 0};
+        for (size_t k = 0; k + 3 < pn_.size(); k += 4) p_cor = p_cor + (V3{pn_[k + 1], pn_[k + 2], pn_[k + 3]} - p0) * pn_[k];
+        p_cor    = mv(scale(iewn_skew, 2.0), p_cor);
+        V3 v_cor = mv(scale(iewn_skew, 2.0), p1 - p0);
+        Q4 qnn   = rotvec2quat(-iewn * T);
+        V3 dpn   = p1 - p0 - v0 * T - 0.5 * gravity * T * T + p_cor;
+        V3 dvn   = v1 - v0 - gravity * T + v_cor;
+        Q4 qb0b1 = qmul(qmul(qinv(q1), qnn), q0);
+        V3 rdp = mv(cnb0, dpn), rdv = mv(cnb0, dvn);
+        rds    = mv(cnb0, p1 - p0);
+        V3 rp = rdp - corrected_p, rv = rdv - corrected_v;
+        Q4 qe = qmul(qb0b1, corrected_q);
+        r[0] = rp.x, r[1] = rp.y, r[2] = rp.z, r[3] = rv.x, r[4] = rv.y, r[5] = rv.z, r[6] = 2 * qe.x, r[7] = 2 * qe.y, r[8] = 2 * qe.z;
+        put(J0, 0, 0, add(scale(cnb0, -1.0), scale(mul(scale(cnb0, 2.0), iewn_skew), -T)));
+        put(J0, 0, 3, skew(rdp));
+        put(J0, 3, 0, mul(scale(cnb0, -2.0), iewn_skew));
+        put(J0, 3, 3, skew(rdv));
+        put(J0, 6, 3, qleft_qright_br(qb0b1, corrected_q));
+        put(J2, 0, 0, cnb0);
+        put(J2, 3, 0, mul(scale(cnb0, 2.0), iewn_skew));
+        put(J2, 6, 3, scale(qright_br(qe), -1.0));
+        put(J1, 6, 3, mul(qleft_br(qmul(qb0b1, dq)), dq_dbg));
+    }
+    put(J0, 15, 0, scale(cnb0, -1.0));
+    put(J0, 15, 3, skew(rds));
+    put(J2, 15, 0, cnb0);
+    put(J1, 0, 0, scale(cnb0, -T));
+    put(J1, 0, 3, scale(dp_dbg, -1.0));
+    put(J1, 0, 6, scale(dp_dba, -1.0));
+    put(J1, 3, 0, scale(cnb0, -1.0));
+    put(J1, 3, 3, scale(dv_dbg, -1.0));
+    put(J1, 3, 6, scale(dv_dba, -1.0));
+    put(J1, 9, 3, scale(eye(), -1.0));
+    put(J1, 12, 6, scale(eye(), -1.0));
+    put(J1, 15, 3, scale(ds_dbg, -1.0));
+    J1[15][9] = ds_dsodo.x * -1.0, J1[16][9] = ds_dsodo.y * -1.0, J1[17][9] = ds_dsodo.z * -1.0;
+    J1[18][9] = -1.0;
+    put(J3, 3, 0, cnb0);
+    put(J3, 9, 3, eye());
+    put(J3, 12, 6, eye());
+    J3[18][9] = 1.0;
+    V3 rbg = bg1 - bg0, rba = ba1 - ba0, rs = rds - corrected_s;
+    r[9] = rbg.x, r[10] = rbg.y, r[11] = rbg.z, r[12] = rba.x, r[13] = rba.y, r[14] = rba.z;
+    r[15] = rs.x, r[16] = rs.y, r[17] = rs.z, r[18] = sodo1 - sodo0;
+    for (int i = 0; i < N; i++) {
+        double s = 0;
+        for (int k = 0; k < N; k++) s += S[i][k] * r[k];
+        residuals[i] = s;
+    }
+    if (jacobians) {
+        auto emit = [&](auto &J, int cols, double *out) {
+            if (!out) return;
+            for (int i = 0; i < N; i++)
+                for (int j = 0; j < cols; j++) {
+                    double s = 0;
+                    for (int k = 0; k < N; k++) s += S[i][k] * J[k][j];
+                    out[i * cols + j] = s;
+                }
+        };
+        emit(J0, 7, jacobians[0]);
+        emit(J1, 10, jacobians[1]);
+        emit(J2, 7, jacobians[2]);
+        emit(J3, 10, jacobians[3]);
+    }
+    return true;
+}
+
+PreintegrationOdoFactor::PreintegrationOdoFactor(std::shared_ptr<PreintegrationOdo> preintegration)
+    : preintegration_(std::move(preintegration)) {
+    *mutable_parameter_block_sizes() = std::vector<int32_t>{7, 10, 7, 10}; // numBlocksParameters (odo :165-167)
+    set_num_residuals(PreintegrationOdo::NUM_STATE);
+}
+
+} // namespace icg

@@ -31,6 +31,7 @@ EXPORTS = [
     "icg_marg_linearize_batch_keep", "icg_marg_linearized_release", "icg_marg_prior_set_from_kept", "icg_marg_linearize_resident",
     "icg_reproj_landmark_min_windows",
     "icg_preint_set", "icg_preint_evaluate_resident", "icg_preint_fetch_resident", "icg_reproj_host_parts_build_preint",
+    "icg_preint_odo_batch", "icg_preint_odo_evaluate_batch",
 ]
 
 
@@ -588,6 +589,40 @@ class Context:
         status = np.zeros(n, np.int32)
         self._ck(self.lib.icg_preint_evaluate_batch(self.h, int(variant), n, _p(delta), _p(jac), _p(cov), _p(dt), _p(env), _p(po), _p(pnr),
                                                      _p(points), _p(res), _p(J), _p(S), _p(status)), "icg_preint_evaluate_batch")
+        return res, J, S, status
+
+    # ---- P1 / P2 of the odometer variants (2 = Odo, 3 = EarthOdo)
+    def preint_odo_batch(self, variant, offsets, imu9, state0, params25, want_pn=True):
+        """icg_preint_odo_batch -> (cur n x 16, delta n x 20, jac n x 19 x 19, cov n x 19 x 19, dt n, pn total x 4 or None without want_pn)"""
+        offsets = i32(offsets)
+        n = len(offsets) - 1
+        imu9 = f64(imu9).reshape(-1, 9)
+        state0 = f64(state0).reshape(n, 17)
+        params25 = f64(params25).reshape(25)
+        cur = np.zeros((n, 16))
+        delta = np.zeros((n, 20))
+        jac = np.zeros((n, 19, 19))
+        cov = np.zeros((n, 19, 19))
+        dt = np.zeros(n)
+        pn = np.zeros((imu9.shape[0], 4)) if want_pn else None
+        self._ck(self.lib.icg_preint_odo_batch(self.h, int(variant), n, _p(offsets), _p(imu9), _p(state0), _p(params25),
+                                                _p(cur), _p(delta), _p(jac), _p(cov), _p(dt), _p(pn)), "icg_preint_odo_batch")
+        return cur, delta, jac, cov, dt, pn
+
+    def preint_odo_evaluate_batch(self, variant, delta, jac, cov, dt, env, points, pn_offsets=None, pn=None, want_jac=True):
+        """icg_preint_odo_evaluate_batch -> (residuals n x 19, jacobians n x 646 or None, sqrt_info n x 19 x 19, status n)"""
+        points = f64(points).reshape(-1, 34)
+        n = points.shape[0]
+        delta, jac, cov = f64(delta).reshape(n, 20), f64(jac).reshape(n, 361), f64(cov).reshape(n, 361)
+        dt, env = f64(dt).reshape(n), f64(env).reshape(n, 4)
+        po = None if pn_offsets is None else i32(pn_offsets)
+        pnr = None if pn is None else f64(pn).reshape(-1, 4)
+        res = np.zeros((n, 19))
+        J = np.zeros((n, 646)) if want_jac else None
+        S = np.zeros((n, 19, 19))
+        status = np.zeros(n, np.int32)
+        self._ck(self.lib.icg_preint_odo_evaluate_batch(self.h, int(variant), n, _p(delta), _p(jac), _p(cov), _p(dt), _p(env), _p(po), _p(pnr),
+                                                         _p(points), _p(res), _p(J), _p(S), _p(status)), "icg_preint_odo_evaluate_batch")
         return res, J, S, status
 
     def preint_set(self, variant, delta, jac, sqrt_info, dt, env, q_nn, pn_offsets=None, pn=None):

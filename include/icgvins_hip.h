@@ -388,6 +388,38 @@ int icg_preint_evaluate_batch(icg_ctx *ctx, int variant, int n_factors, const do
                               const double *pn, const double *points, double *residuals, double *jacobians, double *sqrt_info,
                               int32_t *status);
 
+/* ---- P1 of the odometer variants (PreintegrationOdo::integrationProcess / updateJacobianAndCovariance, preintegration_odo.cc:206-272;
+ * PreintegrationEarthOdo, preintegration_earth_odo.cc:230-346; noise :289-301 / :371-383; on the two-sample integration of
+ * preintegration_base.cc:39-70,86-92), batched over independent intervals like icg_preint_batch.  The error state is 19 wide
+ * (dp, dv, dq, dbg, dba, ds, dsodo: s the preintegrated distance, sodo the odometer scale factor), the noise has 16 channels.
+ * variant: 2 Odo, 3 EarthOdo (0 and 1 keep meaning Normal and Earth in icg_preint_batch).
+ * imu9: total x 9 doubles (time, dt, dtheta[3], dvel[3], odovel: the distance increment of the sample).  state0: n x 17 (p3, q4 xyzw,
+ * v3, bg3, ba3, sodo).  params25: [0..8] as icg_preint_batch, [9..11] odo_std, [12] odo_srw, [13..21] cvb = euler2matrix(abv)^T row-major
+ * (formed by the caller: the installation angles themselves are not passed), [22..24] lodo.
+ * Outputs per interval: cur_state 16; delta_state 20 = the 16 of icg_preint_batch, then s[3], then sodo; jac 361 and cov 361 (19 x 19
+ * row-major); delta_time 1.  pn (optional, total x 4) as in icg_preint_batch, written by variant 3 only (preintegration_earth_odo.cc:261).
+ * ICG_ERR_INVALID (no output is touched): variant not 2 or 3, n_intervals < 0, a NULL required pointer, offsets[0] < 0, an interval
+ * without a sample.  n_intervals == 0 is ICG_OK and touches nothing. */
+int icg_preint_odo_batch(icg_ctx *ctx, int variant, int n_intervals, const int32_t *offsets, const double *imu9,
+                         const double *state0, const double *params25, double *cur_state, double *delta_state, double *jac,
+                         double *cov, double *delta_time, double *pn);
+
+/* ---- P2 of the odometer variants: PreintegrationFactor::Evaluate (preintegration_factor.h:45-69) -> PreintegrationOdo::evaluate /
+ * ::residualJacobianPose0..Mix1 (preintegration_odo.cc:40-159); PreintegrationEarthOdo (preintegration_earth_odo.cc:41-183): the 19-state
+ * twin of icg_preint_evaluate_batch.  variant: 2 Odo, 3 EarthOdo.
+ * Inputs per factor, in the layout icg_preint_odo_batch writes: delta_state 20, jac 361, cov 361, delta_time 1; env 4 = gravity, iewn[3];
+ * points 34 = pose0[7] mix0[10] pose1[7] mix1[10] (p3, q4 xyzw | v3, bg3, ba3, sodo: the odometer scale factor is mix[9],
+ * preintegration_odo.cc:169-183).  EarthOdo only: pn_offsets / pn as in icg_preint_evaluate_batch (NULL for variant 2).
+ * Outputs per factor: residuals 19; jacobians 646 = 19x7 | 19x10 | 19x7 | 19x10, each row-major (NULL: residual only); sqrt_info 361 =
+ * LLT(cov^-1).matrixL()^T (NULL: not returned); status 0 ok, 1 singular covariance (a zero pivot in the inversion, e.g. odo_srw = 0 or an
+ * interval of a single IMU sample) — the output rows of such a factor are zero.
+ * ICG_ERR_INVALID (nothing is launched): variant not 2 or 3, n_factors <= 0, a NULL required pointer, pn_offsets missing, negative or not
+ * monotone for variant 3, rows without pn. */
+int icg_preint_odo_evaluate_batch(icg_ctx *ctx, int variant, int n_factors, const double *delta_state, const double *jac,
+                                  const double *cov, const double *delta_time, const double *env, const int32_t *pn_offsets,
+                                  const double *pn, const double *points, double *residuals, double *jacobians, double *sqrt_info,
+                                  int32_t *status);
+
 /* ---- P2 on a RESIDENT set of factors: what an integration result contributes to its factor is constant over a solve while every LM
  * iteration evaluates it at a new point, so it is uploaded once (icg_preint_set) and an evaluation ships the points up and one squared norm
  * per factor back (icg_preint_evaluate_resident); the whitened residuals and Jacobians stay on the device.
