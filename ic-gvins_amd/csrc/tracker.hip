@@ -19,6 +19,7 @@
 //
 // (stage 1 -> detection -> stage 2 replaces stage 12 in the rare steps in which a stream starts with a detection: first frame,
 // initialization without candidates — the host knows from the previous step's results.)  The host issues the launches and waits ONCE.
+// "k_trk_stage N" is the instance k_trk_stage<N> of one kernel template: each launch runs code compiled for its own stage alone.
 //
 // Parallelism: streams are independent — a wave per stream, all streams of the group in one launch.  Inside a stream the data-parallel loops
 // (prediction of every map point, feature rows, velocities, parallax terms, the compactions of reduceVector, detection lists, the digest)
@@ -174,92 +175,98 @@ __device__ void begin_frame(int s, tc::Stream *streams, const TrkArena &A, const
     tc::stage_begin_frame(streams[s], io, I.stamp, pose, I.image);
 }
 
-// stage: 0 (new frame), 1, 2, 12 (1 then 2 in one launch: no stream queued a detection), 120 (0 then 12: additionally no histogram gate, so
-// nothing of the preprocessing is needed before the prediction), 3, 4, 5, 6 (+ end of frame + results)
-// TRK_WAVES streams per workgroup (a wave each, no workgroup barrier).  Measured (profiles/r04_device_tracker.md): 8 per workgroup — tried to
-// keep the ~115 KB of stage code off most CUs' instruction caches — is SLOWER than one (12 x 64: 74.3 k vs 84.8 k frames/s; 2 confined CPUs
-// 63.9 k vs 72.9 k): the stage bodies are latency chains, and eight of them sharing one CU's LDS and memory pipeline lengthen every chain.
+// STAGE: 0 (new frame), 1, 2, 12 (1 then 2 in one launch: no stream queued a detection), 120 (0 then 12: additionally no histogram gate, so
+// nothing of the preprocessing is needed before the prediction), 3, 4, 5, 6 (+ end of frame + results).  One instantiation per value: a launch
+// is compiled for — and brings into the instruction caches — the body of its own stage only, so its registers and its LDS are that body's and
+// not the largest body's (`make resources` prints them per instance; profiles/r12_tracker_stage_kernels.txt).  The bodies are the same code
+// in the same order whichever instance runs them.
+// TRK_WAVES streams per workgroup (a wave each, no workgroup barrier).  Measured on the one kernel that held every body
+// (profiles/r04_device_tracker.md): 8 per workgroup is SLOWER than one (12 x 64: 74.3 k vs 84.8 k frames/s; 2 confined CPUs 63.9 k vs 72.9 k):
+// the stage bodies are latency chains, and eight of them sharing one CU's LDS and memory pipeline lengthen every chain.
 #define TRK_WAVES 1
-__global__ __launch_bounds__(64 * TRK_WAVES) void k_trk_stage(int stage, int n, tc::Stream *streams, TrkArena A, tc::Cfg C, const uint32_t *buckets_after,
+// the body that follows the begin-frame part of an instance (none for 0)
+constexpr int trk_body_of(int stage) { return stage == 120 ? 12 : stage; }
+// tc::Scratch (33.8 KB of LDS per wave) is declared in the instances whose body takes it: not by new frame (0) and end of frame (6)
+constexpr bool trk_uses_scratch(int stage) { return stage != 0 && stage != 6; }
+// No instance carries a register cap.  128 registers would let a stage wave sit beside four 96-register LK waves, and 120 (130) and 5 (142)
+// are just above; but __launch_bounds__(64, 4), amdgpu_waves_per_eu(4) and amdgpu_num_vgpr(128) all leave their remarks as they are: with
+// 33.8 KB of LDS per wave the compiler counts one wave of this kernel per SIMD and sizes the register budget to that
+// (profiles/r12_tracker_stage_kernels.txt).
+template <int STAGE>
+__global__ __launch_bounds__(64 * TRK_WAVES) void k_trk_stage(int n, tc::Stream *streams, TrkArena A, tc::Cfg C, const uint32_t *buckets_after,
                                                               icg_tracker_result *results, const TrkInput *in) {
-    __shared__ tc::Scratch XS[TRK_WAVES];
+    constexpr int BODY = trk_body_of(STAGE);
     const int wave = (int) (threadIdx.x >> 6);
-    tc::Scratch &X = XS[wave];
     const int s = blockIdx.x * TRK_WAVES + wave;
     if (s >= n) return; // all 64 lanes run the stage body (track_core.h "execution model"): redundantly where it is sequential
     tc::Stream &S = streams[s];
     TC_MARK_START();
-    if (stage == 0 || stage == 120) {
+    if constexpr (STAGE == 0 || STAGE == 120) {
         begin_frame(s, streams, A, in);
         tc::sync();
         TC_MARK(1);
-        if (stage == 0) return;
-        stage = 12;
     }
+    if constexpr (STAGE == 0) return;
     const bool active = A.active[s] != 0;
     tc::Io io = io_of(A, C, s);
     bool log_ok  = false;
     int log_rows = 0;
-    if (active) {
-        switch (stage) {
-        case 1:
-            tc::stage_on_preprocess(S, C, io, X);
-            build_rois(A, C, s);
-            A.work[4 * s + 1] += A.det_slot[s] >= 0 ? 1 : 0;
-            break;
-        case 2:
-            assemble_corners(A, C, s);
-            tc::stage_on_detect_a(S, C, io, X);
-            A.work[4 * s] = A.lk_count[s];
-            break;
-        case 12:
-            tc::stage_on_preprocess(S, C, io, X);
-            TC_MARK(10);
-            if (!S.done && A.det_slot[s] >= 0) { // a detection was queued but this step runs without the detection-A launches
-                S.overflow |= tc::OVF_INTERNAL;
-                A.det_slot[s] = -1;
-                S.det_job     = -1;
+    if constexpr (trk_uses_scratch(STAGE)) {
+        __shared__ tc::Scratch XS[TRK_WAVES];
+        tc::Scratch &X = XS[wave];
+        if (active) {
+            if constexpr (BODY == 1) {
+                tc::stage_on_preprocess(S, C, io, X);
+                build_rois(A, C, s);
+                A.work[4 * s + 1] += A.det_slot[s] >= 0 ? 1 : 0;
+            } else if constexpr (BODY == 2) {
+                assemble_corners(A, C, s);
+                tc::stage_on_detect_a(S, C, io, X);
+                A.work[4 * s] = A.lk_count[s];
+            } else if constexpr (BODY == 12) {
+                tc::stage_on_preprocess(S, C, io, X);
+                TC_MARK(10);
+                if (!S.done && A.det_slot[s] >= 0) { // a detection was queued but this step runs without the detection-A launches
+                    S.overflow |= tc::OVF_INTERNAL;
+                    A.det_slot[s] = -1;
+                    S.det_job     = -1;
+                }
+                A.det_count[s] = 0;
+                tc::stage_on_detect_a(S, C, io, X);
+                TC_MARK(13);
+                A.work[4 * s] = A.lk_count[s];
+            } else if constexpr (BODY == 3) {
+                tc::stage_on_lk(S, C, io, buckets_after, X);
+                A.work[4 * s + 2] = A.rs_count[s] > 0 ? 1 : 0;
+            } else if constexpr (BODY == 4) {
+                tc::stage_on_ransac(S, C, io, X);
+                TC_MARK(32);
+                A.work[4 * s + 3] = A.tri_count[s];
+            } else {
+                static_assert(BODY == 5, "k_trk_stage: no such stage");
+                tc::stage_on_triangulate(S, C, io, buckets_after, X);
+                TC_MARK(46);
+                build_rois(A, C, s);
+                TC_MARK(47);
+                A.work[4 * s + 1] += A.det_slot[s] >= 0 ? 1 : 0;
             }
-            A.det_count[s] = 0;
-            tc::stage_on_detect_a(S, C, io, X);
-            TC_MARK(13);
-            A.work[4 * s] = A.lk_count[s];
-            break;
-        case 3:
-            tc::stage_on_lk(S, C, io, buckets_after, X);
-            A.work[4 * s + 2] = A.rs_count[s] > 0 ? 1 : 0;
-            break;
-        case 4:
-            tc::stage_on_ransac(S, C, io, X);
-            TC_MARK(32);
-            A.work[4 * s + 3] = A.tri_count[s];
-            break;
-        case 5:
-            tc::stage_on_triangulate(S, C, io, buckets_after, X);
-            TC_MARK(46);
-            build_rois(A, C, s);
-            TC_MARK(47);
-            A.work[4 * s + 1] += A.det_slot[s] >= 0 ? 1 : 0;
-            break;
-        case 6:
-            assemble_corners(A, C, s);
-            TC_MARK(50);
-            tc::stage_on_detect_b(S, C, io);
-            TC_MARK(51);
-            // the frame's tracking.txt line (TableTracker::endFrame writes it before the window keeper runs: same condition, same count)
-            tc::sync();
-            log_ok   = S.log_valid && S.result == tc::TRACK_TRACKING && S.mode == tc::M_TRACK && S.lost_reset != 2;
-            log_rows = S.cur >= 0 ? S.frame[S.cur].n_rows : 0;
-            tc::stage_end_frame(S, C);
-            break;
-        default: break;
+        } else if constexpr (BODY == 1 || BODY == 5) {
+            build_rois(A, C, s); // (an idle stream's table entries must read "inactive")
         }
-    } else if (stage == 1 || stage == 5) {
-        build_rois(A, C, s); // (an idle stream's table entries must read "inactive")
+    } else if (STAGE == 6 && active) {
+        assemble_corners(A, C, s);
+        TC_MARK(50);
+        tc::stage_on_detect_b(S, C, io);
+        TC_MARK(51);
+        // the frame's tracking.txt line (TableTracker::endFrame writes it before the window keeper runs: same condition, same count)
+        tc::sync();
+        log_ok   = S.log_valid && S.result == tc::TRACK_TRACKING && S.mode == tc::M_TRACK && S.lost_reset != 2;
+        log_rows = S.cur >= 0 ? S.frame[S.cur].n_rows : 0;
+        tc::stage_end_frame(S, C);
     }
     tc::sync();
-    TC_MARK(100 + (stage > 9 ? 2 : stage));
-    if (stage == 6) {
+    TC_MARK(100 + (BODY > 9 ? 2 : BODY));
+    if constexpr (STAGE == 6) {
         icg_tracker_result r;
         r.active          = active ? 1 : 0;
         r.state           = S.result;
@@ -423,11 +430,28 @@ extern "C" int icg_tracker_create(icg_ctx *ctx, int n_streams, const icg_tracker
     return ICG_OK;
 }
 
+template <int STAGE> static void launch_stage_instance(icg_tracker *t) {
+    hipLaunchKernelGGL(k_trk_stage<STAGE>, dim3((t->n + TRK_WAVES - 1) / TRK_WAVES), dim3(64 * TRK_WAVES), 0, t->ctx->stream, t->n, t->d_streams, t->A, t->cfg,
+                       (const uint32_t *) t->d_buckets, t->h_res, (const TrkInput *) t->h_in);
+}
+
 static int launch_stage(icg_tracker *t, int stage, const char *name) {
     icg_ctx *ctx = t->ctx;
+    void (*launch)(icg_tracker *) = nullptr;
+    switch (stage) {
+    case 0: launch = launch_stage_instance<0>; break;
+    case 1: launch = launch_stage_instance<1>; break;
+    case 2: launch = launch_stage_instance<2>; break;
+    case 12: launch = launch_stage_instance<12>; break;
+    case 120: launch = launch_stage_instance<120>; break;
+    case 3: launch = launch_stage_instance<3>; break;
+    case 4: launch = launch_stage_instance<4>; break;
+    case 5: launch = launch_stage_instance<5>; break;
+    case 6: launch = launch_stage_instance<6>; break;
+    default: return ICG_ERR_INVALID;
+    }
     icg_prof_scope ps(ctx, name);
-    hipLaunchKernelGGL(k_trk_stage, dim3((t->n + TRK_WAVES - 1) / TRK_WAVES), dim3(64 * TRK_WAVES), 0, ctx->stream, stage, t->n, t->d_streams, t->A, t->cfg, (const uint32_t *) t->d_buckets, t->h_res,
-                       (const TrkInput *) t->h_in);
+    launch(t);
     ICG_HIP(ctx, hipGetLastError());
     return ICG_OK;
 }
