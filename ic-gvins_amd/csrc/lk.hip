@@ -43,6 +43,15 @@
 //     dwords from mirrored rows; smaller levels, which only tests build, go through two loops that are not unrolled (lk_stage_small).
 //     5.60 k vector instructions per tracked point, scalar instructions -7 %, 15 856 -> 10 928 bytes of text, no global_load_ubyte and no 64-bit
 //     lane address outside lk_stage_small, 93 VGPRs, no scratch, 5 waves per SIMD (profiles/r10_lk_border_tiles.txt).
+//   * (round 13) the pixel pairs of the two Q14 blends that read two adjacent rows are taken VERTICALLY: with VP[c] = (row r, row r + 1) at
+//     column c and the weights packed by columns, Wl = (w00, w10), Wr = (w01, w11), a blend is dot2(VP[k+1], Wr, dot2(VP[k], Wl, c)) — the same
+//     four products and the same 32-bit sum as with the horizontal pairs (tests/test_lk_vertical_pairs_identity.py), and neighbouring positions
+//     share a pair: the lane's 7 pixels of an iteration need 8 pairs instead of 14 (lk_fetch_J: 8 v_perm per fetch and 8 registers held through
+//     the iterations), the 12 positions of an interior set-up lane 13 instead of 24.  The border set-up keeps its horizontal pairs (converted, it
+//     pays in v_perm what it saves in v_alignbit).  The iteration's tail: the level's result is formed once behind the loops, not in every
+//     iteration; one compare decides "not converged" on the common path; the previous step is one packed register.  85 vector instructions per
+//     iteration in the text (92 before), 87 VGPRs in both kernels (k_lk_track: 100 before, now 5 waves per SIMD too), no scratch
+//     (profiles/r13_lk_vertical_pairs.txt: fetches, set-ups and iterations per point, counters and times against round 12).
 // Algorithmic HBM bytes per point and direction: 4 levels x (24^2 + 22^2) B; everything else is
 // LDS/VGPR traffic.
 #include <cfloat>
@@ -188,13 +197,16 @@ __device__ __forceinline__ int lk_descale(int v, int n) { return (v + (1 << (n -
 // 0 <= x < 2^22 the low 16 bits of bits(x + 1.5 * 2^23) are rint(x) (the addition rounds to nearest even on an integer grid and the
 // constant is even) — one full-rate v_add_f32 instead of v_rndne_f32 + v_cvt_i32_f32; w11 = 2^14 - w00 - w01 - w10 is formed on the biased
 // bit patterns modulo 2^16 (the three biases 0x4B400000 have zero low halves) and v_perm picks the low halves.  Same weights, bit for bit.
+// (round 13) VERTICAL = true packs the same four weights by columns, Wl = (w00, w10), Wr = (w01, w11), for the blends that consume vertical
+// pixel pairs (lk_fetch_J, the interior set-up): the same two v_perm with other operands.
+template <bool VERTICAL = false>
 __device__ __forceinline__ void lk_weights_pk(float a, float b, unsigned int &W0, unsigned int &W1) {
     const float A = a * (float) (1 << 14), A1 = (float) (1 << 14) - A, b1 = 1.f - b;
     const unsigned int r00 = __float_as_uint(A1 * b1 + 12582912.f), r01 = __float_as_uint(A * b1 + 12582912.f);
     const unsigned int r10 = __float_as_uint(A1 * b + 12582912.f);
     const unsigned int r11 = 0x4000u - (r00 + r01 + r10);
-    W0 = __builtin_amdgcn_perm(r01, r00, 0x05040100u);
-    W1 = __builtin_amdgcn_perm(r11, r10, 0x05040100u);
+    W0 = __builtin_amdgcn_perm(VERTICAL ? r10 : r01, r00, 0x05040100u);
+    W1 = __builtin_amdgcn_perm(r11, VERTICAL ? r01 : r10, 0x05040100u);
 }
 
 __device__ __forceinline__ void lk_weights(float a, float b, int &w00, int &w01, int &w10, int &w11) {
@@ -257,12 +269,15 @@ __device__ __forceinline__ unsigned int lk_mirror_apply(unsigned int d, unsigned
 // start, 1: J at the level start, 2: J re-staged) and path (0: inside, 1: over a row border only, 2: over a column border), the points that
 // k_lk_track_fb tracked and the passes it ran; printed when the process ends (profiles/r10_lk_border_tiles.txt)
 __device__ unsigned long long g_lk_tile_hist[4][3][3];
-__device__ unsigned long long g_lk_tile_points[2];
+// (round 13) and, of both kernels: fetches of the lane's pixel pairs (epochs of constant integer window position), interior and border level
+// set-ups, Gauss-Newton iterations (profiles/r13_lk_vertical_pairs.txt)
+__device__ unsigned long long g_lk_tile_points[6];
 static void lk_tile_hist_dump() {
-    static unsigned long long h[4][3][3], p[2];
+    static unsigned long long h[4][3][3], p[6];
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_lk_tile_hist), sizeof h) != hipSuccess) return;
     if (hipMemcpyFromSymbol(p, HIP_SYMBOL(g_lk_tile_points), sizeof p) != hipSuccess) return;
     fprintf(stderr, "LK_TILE_HIST points %llu passes %llu\n", p[0], p[1]);
+    fprintf(stderr, "LK_TILE_HIST fetches %llu interior_setups %llu border_setups %llu iterations %llu\n", p[2], p[3], p[4], p[5]);
     for (int l = 0; l < 4; l++)
         for (int k = 0; k < 3; k++)
             fprintf(stderr, "LK_TILE_HIST level %d tile %d inside %llu rows %llu columns %llu\n", l, k, h[l][k][0], h[l][k][1], h[l][k][2]);
@@ -272,8 +287,10 @@ __device__ __forceinline__ void lk_tile_hist(int level, int kind, int x0, int y0
     if (lane == 0) atomicAdd(&g_lk_tile_hist[min(level, 3)][kind][path], 1ull);
 }
 #define LK_HIST(level, kind, x0, y0, T) lk_tile_hist(level, kind, x0, y0, T, W, H, lane)
+#define LK_COUNT(what) do { if (lane == 0) atomicAdd(&g_lk_tile_points[what], 1ull); } while (0)
 #else
 #define LK_HIST(level, kind, x0, y0, T)
+#define LK_COUNT(what)
 #endif
 
 // Tile loads are split into "issue all global loads into registers" and "write them to LDS", so that the loads of the
@@ -450,9 +467,15 @@ __device__ __forceinline__ unsigned int pk_hi16(int a, int b) {
 // the pair one 16-bit element further: (a.hi, b.lo)
 __device__ __forceinline__ unsigned int pk_shift(unsigned int a, unsigned int b) { return __builtin_amdgcn_alignbit(b, a, 16); }
 
+// (upper, 0, lower, 0): byte c & 3 of the upper row's dword and of the lower row's dword as one u16 pair (v_perm_b32 of lower : upper)
+__device__ __forceinline__ constexpr unsigned int lk_vpair_sel(int c) { return 0x0c000c00u | (unsigned int) (c & 3) | ((unsigned int) (4 + (c & 3)) << 16); }
+
 // the lane's two 8-pixel rows of the window at integer position (inx, iny), from the staged tile (3 aligned dwords + a
-// byte funnel shift per row), expanded to the 7 horizontally adjacent u16 pixel pairs the bilinear blend consumes
-__device__ __forceinline__ void lk_fetch_J(const lk_smem &S, int row0, int o, unsigned int (&JA)[7], unsigned int (&JB)[7]) {
+// byte funnel shift per row), expanded to the 8 VERTICALLY adjacent u16 pixel pairs the bilinear blend consumes (round 13):
+// VP[k] = (J[row0][o + k], J[row0 + 1][o + k]).  blend_k = dot2(VP[k + 1], Wr, dot2(VP[k], Wl, c)) is the four products and the 32-bit sum
+// of the horizontal pairs' dot2(JB[k], W1, dot2(JA[k], W0, c)) — 8 v_perm and 8 registers per fetch instead of 14 and 14
+// (tests/test_lk_vertical_pairs_identity.py restates both chains and the byte selection).
+__device__ __forceinline__ void lk_fetch_J(const lk_smem &S, int row0, int o, unsigned int (&VP)[8]) {
     const int idx = o >> 2, sh = o & 3;
     const unsigned int *r0 = &S.J[__umul24((unsigned int) row0, LK_JS >> 2) + (unsigned int) idx]; // (row0 < 32: a 24-bit multiply-add, no 64-bit one)
     const unsigned int *r1 = r0 + (LK_JS >> 2);
@@ -461,11 +484,7 @@ __device__ __forceinline__ void lk_fetch_J(const lk_smem &S, int row0, int o, un
     const unsigned int a0 = __builtin_amdgcn_alignbyte(d1, d0, sh), a1 = __builtin_amdgcn_alignbyte(d2, d1, sh);
     const unsigned int b0 = __builtin_amdgcn_alignbyte(e1, e0, sh), b1 = __builtin_amdgcn_alignbyte(e2, e1, sh);
 #pragma unroll
-    for (int k = 0; k < 7; k++) {
-        const unsigned int sel = 0x0c000c00u | (unsigned int) k | ((unsigned int) (k + 1) << 16); // (byte k, 0, byte k+1, 0)
-        JA[k] = __builtin_amdgcn_perm(a1, a0, sel);
-        JB[k] = __builtin_amdgcn_perm(b1, b0, sel);
-    }
+    for (int k = 0; k < 8; k++) VP[k] = __builtin_amdgcn_perm(k < 4 ? b0 : b1, k < 4 ? a0 : a1, lk_vpair_sel(k));
 }
 
 // The three rows of zeros under the B plane (what lane 63, which owns no pixels, differentiates): written once per kernel, before the first
@@ -520,8 +539,8 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
             }
             continue;
         }
-        unsigned int W0, W1;
-        lk_weights_pk(prevx - ipx, prevy - ipy, W0, W1);
+        unsigned int W0, W1; // the interior set-up and the iterations: Wl = (w00, w10), Wr = (w01, w11); the border set-up: (w00, w01), (w10, w11)
+        const float pax = prevx - ipx, pay = prevy - ipy;
 
         // ---- stage the 24x24 neighbourhood of the previous image AND the 32x32 tile of the next image around the
         //      level's starting estimate in one go (both address sets are known here) ----
@@ -567,6 +586,8 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
             // ONE blend of the 23x23 grid shared through LDS and a 32-bit separable Scharr replace three blends of derivative planes that
             // vertically adjacent lanes computed twice.  (A real branch: the empty asm keeps the compiler from merging the two forms.)
             asm volatile("" ::: "memory");
+            LK_COUNT(3);
+            lk_weights_pk<true>(pax, pay, W0, W1);
             {
                 // lane -> (row lane/2, 12 columns at (lane&1)*12) of B; lanes 46..63 repeat row 22 (same values to the same addresses: the
                 // wave stays full).  B carries the +256 of the patch sample's rounding; every difference below cancels it.  Column 23
@@ -577,16 +598,15 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
 #pragma unroll
                 for (int q = 0; q < 4; q++) d[0][q] = p[q], d[1][q] = p[(LK_IS >> 2) + q];
                 int *dst = &S.B[br * LK_BW + 12 * bs];
+                // (round 13) the 13 vertical pairs (I[br][c], I[br + 1][c]) of the lane's 12 positions, one v_perm each (were 24 horizontal pairs)
+                unsigned int VP[13];
+#pragma unroll
+                for (int c = 0; c < 13; c++) VP[c] = __builtin_amdgcn_perm(d[1][c >> 2], d[0][c >> 2], lk_vpair_sel(c));
 #pragma unroll
                 for (int q = 0; q < 3; q++) {
                     int bv[4];
 #pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const unsigned int sel = 0x0c000c00u | (unsigned int) e | ((unsigned int) (e + 1) << 16); // (byte e, 0, byte e+1, 0)
-                        const unsigned int i1 = __builtin_amdgcn_perm(d[0][e == 3 ? q + 1 : q], d[0][q], sel);
-                        const unsigned int i2 = __builtin_amdgcn_perm(d[1][e == 3 ? q + 1 : q], d[1][q], sel);
-                        bv[e]                 = dot2(i2, W1, dot2_keep_s(i1, W0, rnd8));
-                    }
+                    for (int e = 0; e < 4; e++) bv[e] = dot2(VP[4 * q + e + 1], W1, dot2_keep_s(VP[4 * q + e], W0, rnd8));
                     *reinterpret_cast<int4 *>(dst + 4 * q) = make_int4(bv[0], bv[1], bv[2], bv[3]);
                 }
             }
@@ -619,6 +639,8 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
             }
         } else {
             // windows that reach over the image border: the derivative plane is zero outside the image, so the identity above does not hold
+            LK_COUNT(4);
+            lk_weights_pk(pax, pay, W0, W1);
             const int idx = lx0 >> 2, sh = lx0 & 3;
             unsigned int Pp[4][5]; // pixel pairs (col 2m, 2m+1) of tile rows ly..ly+3, cols lx0..lx0+9
             // pair m = bytes sh + 2m, sh + 2m + 1 of the row's four dwords: for every sh in 0..3 it lies inside ONE pair of adjacent dwords that
@@ -717,14 +739,14 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
         nptx -= (float) ICG_LK_HALF;
         npty -= (float) ICG_LK_HALF;
         float pdx = 0.f, pdy = 0.f;
-        int cinx = -1000000, ciny = -1000000; // integer window position whose pixel pairs are cached in JA/JB
-        unsigned int JA[7], JB[7];
+        int cinx = -1000000, ciny = -1000000; // integer window position whose pixel pairs are cached in VP
+        unsigned int VP[8];
 #pragma unroll
-        for (int k = 0; k < 7; k++) JA[k] = JB[k] = 0;
+        for (int k = 0; k < 8; k++) VP[k] = 0;
 
-        // The Gauss-Newton iterations, as EPOCHS of constant integer window position: the lane's pixel pairs JA/JB are fetched once per epoch
+        // The Gauss-Newton iterations, as EPOCHS of constant integer window position: the lane's pixel pairs VP are fetched once per epoch
         // and are loop-invariant inside it (written as one loop with a conditional re-fetch, they were loop-carried through the condition
-        // and the compiler copied all 14 registers twice per iteration: 28 of ~130 VALU instructions).  Same checks in the same order.
+        // and the compiler copied all of them twice per iteration: 28 of ~130 VALU instructions with the 14 horizontal pairs of rounds 4-12).  Same checks in the same order.
         // Round 5 (instruction diet by the measured issue costs, profiles/ubench: conversions, roundings, compares, DPP, dot2, FP64 and
         // everything VOP3 cost twice a plain add / mul): the fractional position a = npt - floor(npt) is carried from
         // the epoch test of the previous iteration (the window stays in the epoch iff 0 <= a < 1 on both axes: one subtraction and one
@@ -732,7 +754,7 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
         // c0[k] is read in place (dot2_keep), b1 and b2 come out of ONE reduction tree, the oscillation test compares in f32
         // (|s| < 0.01 in double  <=>  |s| <= 0.01f for a float s: 0.01f < 0.01 < nextafter(0.01f)).
         int j = 0;
-        bool more = true;
+        bool more = true, osc = false;
         while (more) {
             const float fx = floorf(nptx), fy = floorf(npty);
             const int inx = (int) fx, iny = (int) fy;
@@ -748,15 +770,17 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
                 lk_stage_J(S, J, W, H, pitch, jx0, jy0, lane);
                 __syncthreads();
             }
-            lk_fetch_J(S, iny - jy0 + ly, (inx - jx0) + lx0, JA, JB);
+            LK_COUNT(2);
+            lk_fetch_J(S, iny - jy0 + ly, (inx - jx0) + lx0, VP);
             cinx = inx;
             ciny = iny;
             float ax = nptx - fx, ay = npty - fy; // == nptx - (float) inx
             for (;;) {
-                lk_weights_pk(ax, ay, W0, W1);
+                LK_COUNT(5);
+                lk_weights_pk<true>(ax, ay, W0, W1);
                 int diff[7];
 #pragma unroll
-                for (int k = 0; k < 7; k++) diff[k] = dot2(JB[k], W1, dot2_keep(JA[k], W0, c0[k])) >> 9;
+                for (int k = 0; k < 7; k++) diff[k] = dot2(VP[k + 1], W1, dot2_keep(VP[k], W0, c0[k])) >> 9;
                 int sb1 = 0, sb2 = 0;
 #pragma unroll
                 for (int m = 0; m < 4; m++) {
@@ -771,28 +795,29 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
                 const float dy = (float) ((A12 * b1 - A11 * b2) * Ds);
                 nptx += dx;
                 npty += dy;
-                nextStore = make_float2(nptx + (float) ICG_LK_HALF, npty + (float) ICG_LK_HALF);
                 // ddx^2 + ddy^2 <= eps^2 in double (dx^2 is exact in double, so the fused form rounds the same sum once, as the two-step form
                 // does).  Round 6: the float sum of the float squares is within 2^-22 of it, relatively — outside a band of 1e-5 around eps^2
                 // it decides the test, and only inside the band the FP64 form runs (four half-rate instructions of every iteration before).
+                // Round 13: n2 above the band is every iteration but a level's last, so that ONE compare is the common path; the other compare
+                // and the FP64 form sit behind it.  nextStore = npt + half window is formed once behind the loops, not in every iteration.
                 const float n2 = dx * dx + dy * dy;
-                bool converged = n2 < 9.9999e-5f;
-                if (!converged && !(n2 > 1.00001e-4f)) { // wave-uniform; a real branch (the empty asm keeps the compiler from computing both forms always)
+                if (!(n2 > 1.00001e-4f)) { // wave-uniform; a real branch (the empty asm keeps the compiler from computing both forms always)
                     asm volatile("");
-                    converged = __builtin_fma((double) dx, (double) dx, (double) dy * (double) dy) <= eps2;
+                    bool converged = n2 < 9.9999e-5f;
+                    if (!converged) converged = __builtin_fma((double) dx, (double) dx, (double) dy * (double) dy) <= eps2;
+                    if (converged) {
+                        more = false;
+                        break;
+                    }
                 }
-                if (converged) {
-                    more = false;
-                    break;
-                }
-                if (j > 0 && fabsf(dx + pdx) <= 0.01f && fabsf(dy + pdy) <= 0.01f) {
-                    nextStore.x -= dx * 0.5f;
-                    nextStore.y -= dy * 0.5f;
-                    more = false;
-                    break;
-                }
+                const float sx = dx + pdx, sy = dy + pdy;
                 pdx = dx;
                 pdy = dy;
+                if (j > 0 && fabsf(sx) <= 0.01f && fabsf(sy) <= 0.01f) {
+                    osc  = true; // (pdx, pdy hold this iteration's step: half of it is taken back behind the loops)
+                    more = false;
+                    break;
+                }
                 if (++j >= LK_MAX_ITERS) {
                     more = false;
                     break;
@@ -803,6 +828,13 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
                 // when a rounding makes a == 1.0f for a position still inside the pixel, the next epoch finds the same pixels again
                 if (!(__float_as_uint(ax) < 0x3f800000u && __float_as_uint(ay) < 0x3f800000u)) break; // next epoch: bounds test, tile, fetch
             }
+        }
+        // (round 13) the level's result, once: the position after the last step — when the bounds test ended the level before any step, the
+        // level's start as it came — and on the oscillation exit half of the last step back
+        if (j > 0 || !more) nextStore = make_float2(nptx + (float) ICG_LK_HALF, npty + (float) ICG_LK_HALF);
+        if (osc) {
+            nextStore.x -= pdx * 0.5f;
+            nextStore.y -= pdy * 0.5f;
         }
 
         if (status && level == 0) {
@@ -822,13 +854,13 @@ __device__ bool lk_track_wave(const icg_pyr_desc &P, const unsigned char *slotI,
                         lk_stage_J(S, J, W, H, pitch, jx0, jy0, lane);
                         __syncthreads();
                     }
-                    lk_fetch_J(S, iny - jy0 + ly, (inx - jx0) + lx0, JA, JB);
+                    lk_fetch_J(S, iny - jy0 + ly, (inx - jx0) + lx0, VP);
                 }
-                lk_weights_pk(ex - inx, ey - iny, W0, W1);
+                lk_weights_pk<true>(ex - inx, ey - iny, W0, W1);
                 int se = 0;
 #pragma unroll
                 for (int k = 0; k < 7; k++) {
-                    const int diff = dot2(JB[k], W1, dot2_keep(JA[k], W0, c0[k])) >> 9;
+                    const int diff = dot2(VP[k + 1], W1, dot2_keep(VP[k], W0, c0[k])) >> 9;
                     se += diff < 0 ? -diff : diff;
                 }
                 se &= (int) am; // lane 63 owns no pixels
