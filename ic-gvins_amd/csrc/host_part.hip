@@ -10,7 +10,8 @@
 // its residuals only.  A block that is a marginalization prior resident on the device (marg.hip) crosses it not at all
 // (icg_reproj_host_parts_build_prior): k_host_part_prior copies its residuals of the last resident evaluation and the free columns of its J0
 // to the places k_host_part reads.  The same kernel serves a block that is a preintegration factor of the resident P2 set (preint.hip,
-// icg_reproj_host_parts_build_preint): its source matrix is the factor's whitened 15 x 32 Jacobian, its row stride 32.
+// icg_reproj_host_parts_build_preint): its source matrix is the factor's whitened 15 x 32 Jacobian, its row stride 32; and a factor of the
+// resident odometer P2 set (preint_odo.hip, icg_reproj_host_parts_build_preint_odo): 19 x 34, row stride 34.
 #include <array>
 
 #include "reproj_internal.h"
@@ -36,12 +37,12 @@ struct hp_copy {
 };
 #define HP_PRIOR_ROWS 16 // rows of a resident block per workgroup of k_host_part_prior
 // A block whose residual and Jacobian are resident on the device: a marginalization prior (J = its J0, row stride r) or a preintegration factor
-// of the resident P2 set (J = its whitened 15 x 32 Jacobian, row stride 32).
+// of the resident P2 set (J = its whitened 15 x 32 Jacobian, row stride 32) or of the resident odometer P2 set (19 x 34, row stride 34).
 struct hp_prior {
     const double *J, *res;        // the block's source matrix and residuals on the device
     int64_t Jd_off;               // the block's place among the kept Jacobians
     int32_t stride, r_off, pc_off; // row stride of J; the block's place in the staged r; its columns of J in the staged column list
-    int32_t nr, nf, fill;         // fill != 0: the kept Jacobian is gathered from J (ICG_HP_JAC_FROM_PRIOR / ICG_HP_JAC_FROM_PREINT)
+    int32_t nr, nf, fill;         // fill != 0: the kept Jacobian is gathered from J (ICG_HP_JAC_FROM_PRIOR / _PREINT / _PREINT_ODO)
 };
 
 // the shipped Jacobians move from the staging arena to their places among the kept ones: one workgroup per shipped block
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(HP_THREADS) void k_host_part(const hp_win *wins, co
     }
 }
 
-// A block that is resident on the device (a marginalization prior of icg_marg_prior_set, a factor of icg_preint_set), for the row tile
+// A block that is resident on the device (a marginalization prior of icg_marg_prior_set, a factor of icg_preint_set or icg_preint_odo_set), for the row tile
 // blockIdx.x of the resident block blockIdx.y: the kept Jacobian is gathered from the block's row-major source matrix where the block asks for it
 // (Jd[k][y] = J[k][pc[y]]: the elements of a tile are consecutive in Jd, so the writes are contiguous along y and across the rows of the tile),
 // and the residuals of the last resident evaluation are copied to the block's place in the staged r.  A plain copy without atomics, ahead of
@@ -219,18 +220,35 @@ static int hp_rules_preint(icg_ctx *ctx, const char *me, int w, int p, int fp, c
     return ICG_OK;
 }
 
+static int hp_rules_preint_odo(icg_ctx *ctx, const char *me, int w, int p, int fp, const int32_t *pc, hp_prior &B) {
+    const icg_preint_odo_resident &ps = ctx->preint_odo;
+    if (!pc) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: an odometer preintegration block without preint_odo_cols", me, w, p);
+    if (ps.n <= 0 || !ps.res_valid || (B.fill && !ps.jac_valid))
+        return icg_fail(ctx, ICG_ERR_INVALID,
+                        "%s: window %d, block %d: no odometer preintegration set is resident and evaluated%s (icg_preint_odo_set, then icg_preint_odo_evaluate_resident)", me,
+                        w, p, B.fill ? " with Jacobians" : "");
+    if (fp >= ps.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: factor %d outside the resident odometer set of %d", me, w, p, fp, ps.n);
+    if (B.nr != 19) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, an odometer preintegration factor has 19", me, w, p, B.nr);
+    for (int x = 0; x < B.nf; x++)
+        if (pc[x] < 0 || pc[x] >= 34 || pc[x] == 6 || pc[x] == 23)
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: odometer preintegration column %d (0 .. 33 without 6 and 23)", me, w, p, pc[x]);
+    B.J = ps.d_jac ? ps.d_jac + 646 * (size_t) fp : nullptr, B.res = ps.d_res + 19 * (size_t) fp, B.stride = 34; // (the whitened 19 x 34 Jacobian)
+    return ICG_OK;
+}
+
+#define HP_FAMILIES 3 // marginalization priors, preintegration factors, odometer preintegration factors
 struct hp_plan { // what validation leaves for the stages behind it
     bool drop_all, have_kept;
     std::vector<int32_t> r_off, c_off; // every block's place in the staged r and cols
     std::vector<hp_prior> res;                // the resident blocks of the rebuilt windows ...
     std::vector<std::array<int, 3>> res_at;   // ... their (window, position in the window's block list, family)
-    std::vector<int32_t> res_cols; // the staged column list their pc_off counts in: prior_cols | preint_cols of all windows (either may be absent)
+    std::vector<int32_t> res_cols; // the staged column list their pc_off counts in: prior_cols | preint_cols | preint_odo_cols of all windows (each may be absent)
     size_t n_res_cols = 0, ship_doubles = 0, out_cells = 0; // (n_res_cols: what the families' cursors walked)
     int n_rebuilt = 0, max_cells = 0, max_prior_nr = 0;
 };
 
 // block b of the rebuilt window w behind its shape and capacity: nf > Pw, columns, the rules of its family (idx[f] >= 0: member idx[f], columns from c0[f]), jac_off
-static int hp_validate_block(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[2], const int (&idx)[2], const size_t (&c0)[2], int w, int b,
+static int hp_validate_block(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[HP_FAMILIES], const int (&idx)[HP_FAMILIES], const size_t (&c0)[HP_FAMILIES], int w, int b,
                              const std::vector<icg_hp_block> *kept, std::vector<int32_t> &seen, bool &any_keep, hp_plan &plan) {
     const char *me = a.me;
     const int p = b - a.blk_off[w], nr = a.nr[b], nf = a.nf[b], Pw = a.Pw[w];
@@ -242,9 +260,12 @@ static int hp_validate_block(icg_ctx *ctx, const hp_args &a, const hp_family (&F
         seen[(size_t) c] = b;
     }
     int fam = -1; // the family the block is resident in
-    for (int f = 0; f < 2; f++) {
+    for (int f = 0; f < HP_FAMILIES; f++) {
         if (idx[f] < 0) continue;
-        if (fam >= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both a prior (%d) and a preintegration factor (%d)", me, w, p, idx[0], idx[1]);
+        if (fam >= 0 && f == 1) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both a prior (%d) and a preintegration factor (%d)", me, w, p, idx[0], idx[1]);
+        if (fam >= 0)
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both %s (%d) and an odometer preintegration factor (%d)", me, w, p,
+                            fam == 0 ? "a prior" : "a preintegration factor", idx[fam], idx[f]);
         fam = f;
         hp_prior B{nullptr, nullptr, 0 /* its place among the kept Jacobians: hp_stage */, 0, plan.r_off[(size_t) b], (int32_t) c0[f], nr, nf, a.jac_off[b] == F[f].gather ? 1 : 0};
         if (int rc = F[f].rules(ctx, me, w, p, idx[f], F[f].cols ? F[f].cols + c0[f] : nullptr, B)) return rc;
@@ -258,6 +279,8 @@ static int hp_validate_block(icg_ctx *ctx, const hp_args &a, const hp_family (&F
         // gathered on the device: from the prior's J0, from the factor's resident Jacobian
     } else if (a.jac_off[b] == ICG_HP_JAC_FROM_PREINT) {
         return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: ICG_HP_JAC_FROM_PREINT for a block that is no preintegration factor", me, w, p);
+    } else if (a.jac_off[b] == ICG_HP_JAC_FROM_PREINT_ODO) {
+        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: ICG_HP_JAC_FROM_PREINT_ODO for a block that is no odometer preintegration factor", me, w, p);
     } else if (a.jac_off[b] == -1) {
         any_keep = true;
         if (!kept || (size_t) p >= kept->size()) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no kept Jacobian", me, w, p);
@@ -271,7 +294,7 @@ static int hp_validate_block(icg_ctx *ctx, const hp_args &a, const hp_family (&F
 }
 
 // Stage 1.  Nothing is changed before validation is through: no field of ctx is written here and nothing is allocated on the device.
-static int hp_validate(icg_ctx *ctx, const hp_args &a, hp_family (&F)[2], hp_plan &plan) {
+static int hp_validate(icg_ctx *ctx, const hp_args &a, hp_family (&F)[HP_FAMILIES], hp_plan &plan) {
     const char *me = a.me;
     const int P = a.P, W = a.W;
     if (W <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: no window partition: call icg_reproj_set_windows first", me);
@@ -306,9 +329,9 @@ static int hp_validate(icg_ctx *ctx, const hp_args &a, hp_family (&F)[2], hp_pla
             if ((int64_t) r_off[(size_t) b] + nr > INT32_MAX || (int64_t) c_off[(size_t) b] + nf > INT32_MAX)
                 return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: window %d, block %d: more than 2^31 residuals or columns in one call", me, w, p);
             r_off[(size_t) b + 1] = r_off[(size_t) b] + nr, c_off[(size_t) b + 1] = c_off[(size_t) b] + nf;
-            int idx[2]; // >= 0: the block is that member of the family's resident set
-            size_t c0[2];
-            for (int f = 0; f < 2; f++) {
+            int idx[HP_FAMILIES]; // >= 0: the block is that member of the family's resident set
+            size_t c0[HP_FAMILIES];
+            for (int f = 0; f < HP_FAMILIES; f++) {
                 idx[f] = F[f].of ? F[f].of[b] : -1, c0[f] = F[f].at;
                 if (idx[f] >= 0) F[f].at += (size_t) nf; // (at most the columns of all blocks: below 2^31)
             }
@@ -323,8 +346,8 @@ static int hp_validate(icg_ctx *ctx, const hp_args &a, hp_family (&F)[2], hp_pla
     }
     if (plan.res.size() > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %zu prior blocks in one call (at most 65535)", me, plan.res.size());
     // the staged column list: one family's columns behind the other's, the blocks' offsets shifted to match
-    size_t base[2];
-    for (int f = 0; f < 2; f++) {
+    size_t base[HP_FAMILIES];
+    for (int f = 0; f < HP_FAMILIES; f++) {
         base[f] = plan.res_cols.size(), plan.n_res_cols += F[f].at;
         if (F[f].cols && !plan.res.empty()) plan.res_cols.insert(plan.res_cols.end(), F[f].cols, F[f].cols + F[f].at);
     }
@@ -396,7 +419,7 @@ struct hp_staged { // what hp_stage uploaded, as hp_launch passes it on
 };
 
 // Stage 3.  The tables of the kernels, the columns, r and the shipped Jacobians into the arena, and up in one copy.
-static int hp_stage(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[2], hp_plan &plan, const std::vector<std::vector<icg_hp_block>> &next, icg_call &c, hp_staged &S) {
+static int hp_stage(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[HP_FAMILIES], hp_plan &plan, const std::vector<std::vector<icg_hp_block>> &next, icg_call &c, hp_staged &S) {
     const int W = a.W, nb = a.blk_off[W];
     const size_t slot = (size_t) a.P * (a.P + 1) / 2;
     std::vector<hp_blk> blks((size_t) nb);
@@ -425,7 +448,7 @@ static int hp_stage(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[2], hp_
     S.d_cols   = c.in(a.cols, n_c);
     S.d_pr     = c.in(plan.res.data(), plan.res.size());
     S.d_pc     = plan.res.empty() ? nullptr : c.in(plan.res_cols.data(), plan.res_cols.size());
-    if (!F[0].of && !F[1].of) {
+    if (!F[0].of && !F[1].of && !F[2].of) {
         S.d_r = c.in(a.r, n_r);
     } else {
         // The slots of the resident blocks (of every window, rebuilt or not) are placed but not read from the caller: staged block by block,
@@ -435,7 +458,7 @@ static int hp_stage(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[2], hp_
         const size_t off = icg_arena_alloc(ctx, sizeof(double) * n_r);
         double *h        = icg_h<double>(ctx, off);
         for (int b = 0; b < nb; b++)
-            if ((!F[0].of || F[0].of[b] < 0) && (!F[1].of || F[1].of[b] < 0))
+            if ((!F[0].of || F[0].of[b] < 0) && (!F[1].of || F[1].of[b] < 0) && (!F[2].of || F[2].of[b] < 0))
                 memcpy(h + plan.r_off[(size_t) b], a.r + plan.r_off[(size_t) b], sizeof(double) * (size_t) a.nr[b]);
         c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * n_r);
         S.d_r = icg_d<double>(ctx, off);
@@ -506,10 +529,24 @@ extern "C" int icg_reproj_host_parts_build_preint(icg_ctx *ctx, int P, const int
                                                   const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r,
                                                   double *host_s, double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols,
                                                   const int32_t *preint_of, const int32_t *preint_cols) {
+    return icg_reproj_host_parts_build_preint_odo(ctx, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, prior_of, prior_cols, preint_of,
+                                                  preint_cols, nullptr, nullptr);
+}
+
+extern "C" int icg_reproj_host_parts_build_preint_odo(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
+                                                      const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r,
+                                                      double *host_s, double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols,
+                                                      const int32_t *preint_of, const int32_t *preint_cols, const int32_t *preint_odo_of,
+                                                      const int32_t *preint_odo_cols) {
     if (!ctx) return ICG_ERR_INVALID;
-    const char *me = preint_of ? "icg_reproj_host_parts_build_preint" : prior_of ? "icg_reproj_host_parts_build_prior" : "icg_reproj_host_parts_build";
+    const char *me = preint_odo_of ? "icg_reproj_host_parts_build_preint_odo"
+                     : preint_of   ? "icg_reproj_host_parts_build_preint"
+                     : prior_of    ? "icg_reproj_host_parts_build_prior"
+                                   : "icg_reproj_host_parts_build";
     const hp_args a{me, P, ctx->part_w.W, Pw, blk_off, nr, nf, cols, rebuild, jac_off, J, r, host_s, host_diag, part_out};
-    hp_family F[2] = {{hp_rules_prior, prior_of, prior_cols, ICG_HP_JAC_FROM_PRIOR, 0}, {hp_rules_preint, preint_of, preint_cols, ICG_HP_JAC_FROM_PREINT, 0}};
+    hp_family F[HP_FAMILIES] = {{hp_rules_prior, prior_of, prior_cols, ICG_HP_JAC_FROM_PRIOR, 0},
+                                {hp_rules_preint, preint_of, preint_cols, ICG_HP_JAC_FROM_PREINT, 0},
+                                {hp_rules_preint_odo, preint_odo_of, preint_odo_cols, ICG_HP_JAC_FROM_PREINT_ODO, 0}};
     hp_plan plan;
     int rc, dst;
     if ((rc = hp_validate(ctx, a, F, plan))) return rc;

@@ -92,6 +92,18 @@ struct icg_preint_resident {
     bool res_valid = false, jac_valid = false; // evaluated (with Jacobians) since the set was made resident
 };
 
+// Resident odometer preintegration factors (preint_odo.hip): the 19-state twin of icg_preint_resident, beside it (a context may hold one set
+// of each at once).  The results of the last evaluation stay in d_res (19 per factor) and d_jac (19 x 34 row-major per factor).
+struct icg_preint_odo_resident {
+    int n = 0;
+    int64_t total_pn = 0; // rows of pn
+    char *d_set = nullptr; // delta_state 20n | jac 361n | sqrt_info 361n | delta_time n | env 4n | q_nn 4n | pn 4 total_pn | pn_offsets n+1 | variant n
+    size_t set_cap = 0;    // bytes
+    double *d_res = nullptr, *d_jac = nullptr;
+    size_t res_cap = 0, jac_cap = 0; // bytes
+    bool res_valid = false, jac_valid = false; // evaluated (with Jacobians) since the set was made resident
+};
+
 // The linearization icg_marg_linearize_batch_keep left on the device (marg_linearize.hip): J0 of every window (r x r row-major, window after
 // window), then e0 of every window, in one buffer the context owns.  id = 0: nothing is kept.  A live id is listed in the process-wide table
 // of ctx.hip (icg_kept_register / icg_kept_drop / icg_kept_lookup), through which icg_marg_prior_set_from_kept of any context finds it.
@@ -183,6 +195,7 @@ struct icg_ctx {
 
     icg_marg_set marg;
     icg_preint_resident preint;
+    icg_preint_odo_resident preint_odo;
     // M3 (marg_linearize.hip): per-window working memory of icg_marg_linearize_batch for the windows that do not fit in LDS; grows on demand
     double *d_lin_scratch = nullptr;
     size_t lin_scratch_cap = 0; // bytes

@@ -23,6 +23,10 @@
 // lower triangle, column Cholesky: the arithmetic and order of the host's PreintegrationOdo::updateSqrtInformation, S bit-identical) and
 // k_preint_odo_evaluate (residual 19 + Jacobians 19x7 | 19x10 | 19x7 | 19x10, each output the dense 19-term sum over ascending k;
 // preintegration_odo.cc:40-159, preintegration_earth_odo.cc:41-183, preintegration_factor.h:45-69).  One wavefront per factor.
+//   k_preint_odo_evaluate_given  the same body for a set of factors RESIDENT on the device (icg_preint_odo_set, last part of this file):
+//                                the two quaternions that need sin / cos / sqrt and the square-root information come from the host, the
+//                                variant is the factor's own, the Jacobian is one 19 x 34 matrix and one lane adds r . r: the host's bits.
+//                                215 VGPRs, no scratch, 8 376 B of LDS, two waves per SIMD.
 #include "dev_math.h"
 #include "icg_internal.h"
 
@@ -429,16 +433,24 @@ __global__ __launch_bounds__(64) void k_preint_odo_sqrt_info(int n, const double
     if (lane == 0) status[f] = 0;
 }
 
-__global__ __launch_bounds__(64) void k_preint_odo_evaluate(int variant, int n, const double *delta_state, const double *jac,
-                                                            const double *delta_time, const double *env, const int32_t *pn_offsets,
-                                                            const double *pn, const double *points, const double *sqrt_info,
-                                                            const int32_t *status, double *residuals, double *jacobians) {
+// The one evaluation body (preint.hip's precedent).  GIVEN = false: icg_preint_odo_evaluate_batch (status from k_preint_odo_sqrt_info,
+// rotvec2quat on the device, Jacobians in the four blocks).  GIVEN = true: icg_preint_odo_evaluate_resident — the two quaternions that need
+// sin / cos / sqrt arrive from the host (q_corr per evaluation point, q_nn with the set), so what is left is + - * / in the host's order;
+// the Jacobian is one row-major 19 x 34 matrix per factor (the columns of U; 6 and 23 are sums of +-0 from +0.0, i.e. +0.0, like the host's
+// seventh pose columns) and lane 0 adds sq_norm = sum_k r[k]^2, k ascending from +0.0.  status / sq_norm / q_corr / q_nn are not read by
+// the instantiation that does not use them.
+template <bool GIVEN>
+__device__ __forceinline__ void preint_odo_evaluate_body(int variant, int n, const double *delta_state, const double *jac,
+                                                         const double *delta_time, const double *env, const int32_t *pn_offsets,
+                                                         const double *pn, const double *points, const double *sqrt_info,
+                                                         const int32_t *status, const double *q_corr, const double *q_nn, double *residuals,
+                                                         double *jacobians, double *sq_norm) {
     __shared__ double S[PO_NN], U[PO_N * POE_U];
     const int f = blockIdx.x, lane = threadIdx.x;
     if (f >= n) return;
     double *r_out = residuals + PO_N * (size_t) f;
     double *J_out = jacobians ? jacobians + 646 * (size_t) f : nullptr;
-    if (status[f] != 0) { // singular covariance: zero rows
+    if (!GIVEN && status[f] != 0) { // singular covariance: zero rows
         for (int o = lane; o < POE_NOUT; o += 64) {
             if (o < PO_N)
                 r_out[o] = 0.0;
@@ -480,7 +492,12 @@ __global__ __launch_bounds__(64) void k_preint_odo_evaluate(int variant, int n, 
     const double dsodo   = sodo0 - d_sodo;
     const d3 corrected_p = add(add(d_p, m_vec(dp_dba, dba)), m_vec(dp_dbg, dbg));
     const d3 corrected_v = add(add(d_v, m_vec(dv_dba, dba)), m_vec(dv_dbg, dbg));
-    const dq corrected_q = q_mul(d_q, rotvec2quat_rcp(m_vec(dq_dbg, dbg)));
+    dq q_c;
+    if (GIVEN)
+        q_c = q_from_xyzw(q_corr + 4 * (size_t) f);
+    else
+        q_c = rotvec2quat_rcp(m_vec(dq_dbg, dbg));
+    const dq corrected_q = q_mul(d_q, q_c);
     const d3 corrected_s = add(add(d_s, m_vec(ds_dbg, dbg)), scl(dsodo, ds_dsodo));
     const double T       = delta_time[f];
     const m33 cnb0       = q_mat(q_inv(q0));
@@ -512,7 +529,11 @@ __global__ __launch_bounds__(64) void k_preint_odo_evaluate(int variant, int n, 
         }
         p_cor          = m_vec(m_scale(iewn_skew, 2.0), p_cor);
         const d3 v_cor = m_vec(m_scale(iewn_skew, 2.0), sub(p1, p0));
-        const dq qnn   = rotvec2quat_rcp(scl(T, neg3(iewn)));
+        dq qnn;
+        if (GIVEN)
+            qnn = q_from_xyzw(q_nn + 4 * (size_t) f);
+        else
+            qnn = rotvec2quat_rcp(scl(T, neg3(iewn)));
         const d3 dpn   = add(sub(sub(sub(p1, p0), scl(T, v0)), half_g_TT), p_cor);
         const d3 dvn   = add(sub(sub(v1, v0), scl(T, gravity)), v_cor);
         const dq qb0b1 = q_mul(q_mul(q_inv(q1), qnn), q0);
@@ -578,6 +599,7 @@ __global__ __launch_bounds__(64) void k_preint_odo_evaluate(int variant, int n, 
     __syncthreads();
     // whitening: out[i][col] = sum_k S[i][k] U[k][col], dense, k ascending from zero
     const int n_out = jacobians ? POE_NOUT : PO_N;
+    double r_mine   = 0;
     for (int o = lane; o < n_out; o += 64) {
         int i, col;
         double *dst;
@@ -586,7 +608,9 @@ __global__ __launch_bounds__(64) void k_preint_odo_evaluate(int variant, int n, 
         } else {
             const int q = o - PO_N;
             dst         = J_out + q;
-            if (q < 133)
+            if (GIVEN)
+                i = q / 34, col = q - i * 34;
+            else if (q < 133)
                 i = q / 7, col = q - i * 7;
             else if (q < 323)
                 i = (q - 133) / 10, col = 7 + (q - 133) - i * 10;
@@ -599,7 +623,36 @@ __global__ __launch_bounds__(64) void k_preint_odo_evaluate(int variant, int n, 
 #pragma unroll
         for (int k = 0; k < PO_N; k++) s += S[i * PO_N + k] * U[k * POE_U + col];
         *dst = s;
+        if (GIVEN && o < PO_N) r_mine = s; // (o == lane: the first pass of lanes 0 .. 18)
     }
+    if (GIVEN) {
+        __shared__ double R[PO_N];
+        if (lane < PO_N) R[lane] = r_mine;
+        __syncthreads();
+        if (lane == 0) {
+            double s = 0;
+            for (int k = 0; k < PO_N; k++) s += R[k] * R[k];
+            sq_norm[f] = s;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_preint_odo_evaluate(int variant, int n, const double *delta_state, const double *jac,
+                                                            const double *delta_time, const double *env, const int32_t *pn_offsets,
+                                                            const double *pn, const double *points, const double *sqrt_info,
+                                                            const int32_t *status, double *residuals, double *jacobians) {
+    preint_odo_evaluate_body<false>(variant, n, delta_state, jac, delta_time, env, pn_offsets, pn, points, sqrt_info, status, nullptr, nullptr,
+                                    residuals, jacobians, nullptr);
+}
+
+// the resident set's instantiation: the variant is the factor's own
+__global__ __launch_bounds__(64) void k_preint_odo_evaluate_given(int n, const int32_t *variant, const double *delta_state, const double *jac,
+                                                                  const double *delta_time, const double *env, const int32_t *pn_offsets,
+                                                                  const double *pn, const double *points, const double *sqrt_info,
+                                                                  const double *q_corr, const double *q_nn, double *residuals,
+                                                                  double *jacobians, double *sq_norm) {
+    preint_odo_evaluate_body<true>(blockIdx.x < (unsigned) n ? variant[blockIdx.x] : 2, n, delta_state, jac, delta_time, env, pn_offsets, pn,
+                                   points, sqrt_info, nullptr, q_corr, q_nn, residuals, jacobians, sq_norm);
 }
 
 extern "C" int icg_preint_odo_evaluate_batch(icg_ctx *ctx, int variant, int n_factors, const double *delta_state, const double *jac,
@@ -649,4 +702,161 @@ extern "C" int icg_preint_odo_evaluate_batch(icg_ctx *ctx, int variant, int n_fa
     }
     ICG_HIP(ctx, hipGetLastError());
     return c.finish();
+}
+
+// ============================================ P2 on a resident set of odometer factors ============================================
+// The 19-state twin of icg_preint_set / icg_preint_evaluate_resident / icg_preint_fetch_resident (preint.hip), with a resident struct of
+// its own (ctx->preint_odo): both sets may be resident in one context at once.  An evaluation ships 34 + 4 doubles per factor up and one
+// squared norm back, and leaves the whitened residuals (19) and the whitened 19 x 34 Jacobian where the set owns them.
+namespace {
+struct preint_odo_view {
+    const double *delta, *jac, *S, *dt, *env, *qnn, *pn;
+    const int32_t *pn_off, *variant;
+};
+preint_odo_view preint_odo_set_view(const icg_preint_odo_resident &s) {
+    const size_t n = (size_t) s.n;
+    preint_odo_view v;
+    const double *p = reinterpret_cast<const double *>(s.d_set);
+    v.delta = p, p += 20 * n;
+    v.jac = p, p += PO_NN * n;
+    v.S = p, p += PO_NN * n;
+    v.dt = p, p += n;
+    v.env = p, p += 4 * n;
+    v.qnn = p, p += 4 * n;
+    v.pn = p, p += 4 * (size_t) s.total_pn;
+    v.pn_off  = reinterpret_cast<const int32_t *>(p);
+    v.variant = v.pn_off + (n + 1);
+    return v;
+}
+} // namespace
+
+extern "C" int icg_preint_odo_set(icg_ctx *ctx, int n_factors, const int32_t *variant, const double *delta_state, const double *jac,
+                                  const double *sqrt_info, const double *delta_time, const double *env, const double *q_nn,
+                                  const int32_t *pn_offsets, const double *pn) {
+    if (!ctx) return ICG_ERR_INVALID;
+    icg_preint_odo_resident &s = ctx->preint_odo;
+    s.n                        = 0; // whatever odometer set the context held is gone, also when this call fails
+    s.res_valid = s.jac_valid = false;
+    if (n_factors <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_set: n_factors = %d", n_factors);
+    if (n_factors > ICG_PREINT_SET_MAX) // (before any array is read: the arrays of such a set are not looked at)
+        return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_preint_odo_set: %d factors in one set (at most %d)", n_factors, ICG_PREINT_SET_MAX);
+    if (!variant || !delta_state || !jac || !sqrt_info || !delta_time || !env || !q_nn)
+        return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_set: NULL argument");
+    const size_t n = (size_t) n_factors;
+    bool any_earth = false;
+    for (size_t f = 0; f < n; f++) {
+        if (variant[f] != 2 && variant[f] != 3)
+            return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_set: factor %zu: variant %d is neither 2 (Odo) nor 3 (EarthOdo)", f, variant[f]);
+        any_earth |= variant[f] == 3;
+    }
+    int64_t total_pn = 0;
+    if (pn_offsets) {
+        if (pn_offsets[0] < 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_set: factor 0: pn_offsets[0] = %d", pn_offsets[0]);
+        for (size_t f = 0; f < n; f++)
+            if (pn_offsets[f + 1] < pn_offsets[f]) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_set: factor %zu: pn_offsets not monotone", f);
+        total_pn = pn_offsets[n];
+        if (total_pn > 0 && !pn) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_set: NULL pn for %lld rows", (long long) total_pn);
+    } else if (any_earth) {
+        return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_set: an EarthOdo factor needs pn_offsets");
+    }
+    const size_t n_dbl = (20 + PO_NN + PO_NN + 1 + 4 + 4) * n + 4 * (size_t) total_pn, bytes = 8 * n_dbl + 4 * (2 * n + 1);
+    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    int rc;
+    if ((rc = icg_grow(ctx, (void **) &s.d_set, &s.set_cap, bytes, bytes + bytes / 4))) return rc;
+    icg_call c(ctx);
+    if ((rc = c.reserve(bytes + 4 * 256))) return rc;
+    const size_t off = icg_arena_alloc(ctx, bytes);
+    if ((rc = c.overflowed())) return rc; // (nothing may be written through an allocation that did not fit)
+    {
+        double *p = icg_h<double>(ctx, off);
+        memcpy(p, delta_state, 8 * 20 * n), p += 20 * n;
+        memcpy(p, jac, 8 * PO_NN * n), p += PO_NN * n;
+        memcpy(p, sqrt_info, 8 * PO_NN * n), p += PO_NN * n;
+        memcpy(p, delta_time, 8 * n), p += n;
+        memcpy(p, env, 8 * 4 * n), p += 4 * n;
+        memcpy(p, q_nn, 8 * 4 * n), p += 4 * n;
+        if (total_pn > 0) memcpy(p, pn, 8 * 4 * (size_t) total_pn), p += 4 * (size_t) total_pn;
+        int32_t *q = reinterpret_cast<int32_t *>(p);
+        if (pn_offsets)
+            memcpy(q, pn_offsets, 4 * (n + 1));
+        else
+            memset(q, 0, 4 * (n + 1));
+        memcpy(q + (n + 1), variant, 4 * n);
+    }
+    c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + bytes);
+    if ((rc = c.seal())) return rc;
+    ICG_LAUNCH_GUARD(c);
+    {
+        icg_prof_scope ps(ctx, "preint_odo_set");
+        ICG_HIP(ctx, hipMemcpyAsync(s.d_set, icg_d<char>(ctx, off), bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if ((rc = c.finish())) return rc;
+    s.total_pn = total_pn;
+    s.n        = n_factors;
+    return ICG_OK;
+}
+
+extern "C" int icg_preint_odo_evaluate_resident(icg_ctx *ctx, const double *points, const double *q_corr, int want_jac, double *sq_norm) {
+    if (!ctx) return ICG_ERR_INVALID;
+    icg_preint_odo_resident &s = ctx->preint_odo;
+    if (s.n <= 0)
+        return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_evaluate_resident: no odometer preintegration set is resident (icg_preint_odo_set first)");
+    if (!points || !q_corr || !sq_norm) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_evaluate_resident: NULL argument");
+    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    const size_t n = (size_t) s.n;
+    bool replaced  = false;
+    int rc         = icg_grow(ctx, (void **) &s.d_res, &s.res_cap, 8 * PO_N * n, 8 * PO_N * n, &replaced);
+    if (replaced) s.res_valid = false;
+    if (rc) return rc;
+    if (want_jac) {
+        replaced = false;
+        rc       = icg_grow(ctx, (void **) &s.d_jac, &s.jac_cap, 8 * 646 * n, 8 * 646 * n, &replaced);
+        if (replaced) s.jac_valid = false;
+        if (rc) return rc;
+    }
+    icg_call c(ctx);
+    if ((rc = c.reserve(8 * (34 + 4 + 1) * n + 4 * 256))) return rc;
+    const double *d_pts = c.in(points, 34 * n);
+    const double *d_qc  = c.in(q_corr, 4 * n);
+    if ((rc = c.seal())) return rc;
+    double *d_sq = c.out(sq_norm, n);
+    ICG_LAUNCH_GUARD(c);
+    s.res_valid = s.jac_valid = false; // (until the kernel below is through)
+    const preint_odo_view v = preint_odo_set_view(s);
+    {
+        icg_prof_scope ps(ctx, "preint_odo_eval_given");
+        hipLaunchKernelGGL(k_preint_odo_evaluate_given, dim3(s.n), dim3(64), 0, ctx->stream, s.n, v.variant, v.delta, v.jac, v.dt, v.env, v.pn_off, v.pn,
+                           d_pts, v.S, d_qc, v.qnn, s.d_res, want_jac ? s.d_jac : (double *) nullptr, d_sq);
+    }
+    ICG_HIP(ctx, hipGetLastError());
+    if ((rc = c.finish())) return rc;
+    s.res_valid = true;
+    s.jac_valid = want_jac != 0;
+    return ICG_OK;
+}
+
+extern "C" int icg_preint_odo_fetch_resident(icg_ctx *ctx, double *residuals, double *jacobians) {
+    if (!ctx) return ICG_ERR_INVALID;
+    const icg_preint_odo_resident &s = ctx->preint_odo;
+    if (s.n <= 0)
+        return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_fetch_resident: no odometer preintegration set is resident (icg_preint_odo_set first)");
+    if (!residuals) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_fetch_resident: NULL residuals");
+    if (!s.res_valid) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_fetch_resident: nothing was evaluated since the set was made resident");
+    if (jacobians && !s.jac_valid)
+        return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_fetch_resident: the last evaluation kept no Jacobians (want_jac = 0)");
+    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    const size_t n = (size_t) s.n;
+    std::vector<double> J34(jacobians ? 646 * n : 0);
+    ICG_HIP(ctx, hipMemcpyAsync(residuals, s.d_res, 8 * PO_N * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (jacobians) ICG_HIP(ctx, hipMemcpyAsync(J34.data(), s.d_jac, 8 * 646 * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = icg_stream_wait(ctx)) return rc;
+    if (jacobians) { // 19 x 34 row-major -> 19x7 | 19x10 | 19x7 | 19x10
+        static const int c0[5] = {0, 7, 17, 24, 34}, o0[4] = {0, 133, 323, 456};
+        for (size_t f = 0; f < n; f++)
+            for (int b = 0; b < 4; b++) {
+                const int w = c0[b + 1] - c0[b];
+                for (int i = 0; i < PO_N; i++) memcpy(jacobians + 646 * f + o0[b] + i * w, &J34[646 * f + 34 * i + c0[b]], 8 * (size_t) w);
+            }
+    }
+    return ICG_OK;
 }

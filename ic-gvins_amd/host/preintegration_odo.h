@@ -58,6 +58,15 @@ public:
     // PreintegrationFactor::Evaluate body (preintegration_factor.h:45-69): residual 19, Jacobians 19x7, 19x10, 19x7, 19x10.  false (and
     // nothing written) while the interval is not integrated or its covariance is singular.
     bool evaluate(const double *const *parameters, double *residuals, double **jacobians) const;
+    // The only two places of evaluate() where sin / cos / sqrt enter, as unit quaternions (x, y, z, w), formed with evaluate()'s own
+    // expressions: the bias correction of delta q at mix0 (v3, bg3, ba3, sodo), rotvec2quat(dq_dbg (bg0 - delta.bg)), and the EarthOdo
+    // variant's rotvec2quat(-iewn T), a constant of the integration result (identity, and unused, for the Odo variant).
+    void correctionQuaternion(const double *mix0, double q_xyzw[4]) const;
+    void earthRateQuaternion(double q_xyzw[4]) const;
+    // evaluate() with the two quaternions given: everything that is left is + - * / in a fixed order.  evaluate() is
+    // correctionQuaternion + earthRateQuaternion + evaluateGiven; a caller that evaluates on the device (icg_preint_odo_set /
+    // icg_preint_odo_evaluate_resident) ships the quaternions instead of calling sin / cos there.
+    bool evaluateGiven(const double *const *parameters, const double q_corr[4], const double q_nn[4], double *residuals, double **jacobians) const;
     Variant variant() const { return variant_; }
     const vector<double> &sqrtInformation() const { return sqrt_information_; } // 19x19 row-major; zeros while the covariance is singular
     bool ready() const { return !dirty_ && sqrt_information_ok_; }
@@ -92,6 +101,30 @@ public:
 
 private:
     std::shared_ptr<PreintegrationOdo> preintegration_;
+};
+
+// The odometer preintegration factors of many windows resident on the device (icg_preint_odo_set / icg_preint_odo_evaluate_resident): the
+// 19-state twin of PreintegrationSet, with its own resident set in the context (both may be resident at once).  set() once, pack() +
+// evaluateResident() per evaluation point.  The device gets the host's square-root information and the two quaternions of
+// PreintegrationOdo::evaluate that need sin / cos (earthRateQuaternion with the set, correctionQuaternion with every point); its residuals,
+// Jacobians and squared norms are then the bits of PreintegrationOdo::evaluate, and only one squared norm per factor comes back.  The C
+// entries are referenced weakly: in a build of this layer on a C ABI without them available() is false, missingEntry() names the first
+// that is absent and set() fails by that name.
+class PreintegrationOdoSet {
+public:
+    static bool available();
+    static const char *missingEntry(); // nullptr when available()
+    // every factor must be ready() (integrated, covariance not singular); the objects must outlive the set's use
+    bool set(icg_ctx *ctx, const vector<const PreintegrationOdo *> &list, std::string *err = nullptr);
+    // factor f's evaluation point (pose0[7], mix0[10], pose1[7], mix1[10]) and its correction quaternion to their places (any thread)
+    void pack(size_t f, const double *const *parameters);
+    bool evaluateResident(bool want_jac, double *sq_norm, std::string *err = nullptr);
+    int factors() const { return (int) list_.size(); }
+
+private:
+    icg_ctx *ctx_{nullptr};
+    vector<const PreintegrationOdo *> list_;
+    vector<double> points_, q_corr_;
 };
 
 } // namespace icg

@@ -3,6 +3,9 @@
 // wrapped by preintegration_factor.h:45-69) is evaluated on the host per factor (evaluate) or for many factors at once on the device
 // (evaluateBatch, icg_preint_odo_evaluate_batch).  The 19-state twin of preintegration_hip.cc, which stays as it is: the small-matrix helpers
 // below repeat that file's (same expressions, same order) so that nothing the 15-state bit-for-bit tests rest on moves.
+// evaluate() is split at its two rotvec2quat calls (correctionQuaternion, earthRateQuaternion) from the rest (evaluateGiven), as
+// Preintegration::evaluate is: a driver that keeps the factors resident on the device (PreintegrationOdoSet, preint_odo_set_hip.cc) ships
+// the two quaternions, and the device is left with + - * / in this file's order.
 #include <cmath>
 #include <cstring>
 
@@ -353,9 +356,39 @@ void PreintegrationOdo::updateSqrtInformation() {
     sqrt_information_ok_ = true;
 }
 
+void PreintegrationOdo::correctionQuaternion(const double *mix0, double q_xyzw[4]) const {
+    M3 dq_dbg;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) dq_dbg.m[i][j] = jacobian_[(size_t) (6 + i) * N + 9 + j];
+    V3 bg0{mix0[3], mix0[4], mix0[5]}, dbg0{delta_state_.bg[0], delta_state_.bg[1], delta_state_.bg[2]};
+    V3 dbg = bg0 - dbg0;
+    Q4 q   = rotvec2quat(mv(dq_dbg, dbg));
+    q_xyzw[0] = q.x, q_xyzw[1] = q.y, q_xyzw[2] = q.z, q_xyzw[3] = q.w;
+}
+
+void PreintegrationOdo::earthRateQuaternion(double q_xyzw[4]) const {
+    Q4 q{0, 0, 0, 1};
+    if (variant_ == EARTH_ODO) {
+        V3 iewn{iewn_[0], iewn_[1], iewn_[2]};
+        const double T = delta_time_;
+        q              = rotvec2quat(-iewn * T);
+    }
+    q_xyzw[0] = q.x, q_xyzw[1] = q.y, q_xyzw[2] = q.z, q_xyzw[3] = q.w;
+}
+
 bool PreintegrationOdo::evaluate(const double *const *parameters, double *residuals, double **jacobians) const {
     if (dirty_) return false;                // not integrated for the current buffer/start state: evaluation failed, loudly
     if (!sqrt_information_ok_) return false; // singular covariance
+    double q_corr[4], q_nn[4];
+    correctionQuaternion(parameters[1], q_corr);
+    earthRateQuaternion(q_nn);
+    return evaluateGiven(parameters, q_corr, q_nn, residuals, jacobians);
+}
+
+bool PreintegrationOdo::evaluateGiven(const double *const *parameters, const double q_corr[4], const double q_nn[4], double *residuals,
+                                      double **jacobians) const {
+    if (dirty_) return false;
+    if (!sqrt_information_ok_) return false;
     typedef double MN[N][N];
     MN jac, S;
     memcpy(jac, jacobian_.data(), sizeof jac);
@@ -385,7 +418,7 @@ bool PreintegrationOdo::evaluate(const double *const *parameters, double *residu
     const double dsodo = sodo0 - d.sodo;
     V3 corrected_p = dp + mv(dp_dba, dba) + mv(dp_dbg, dbg);
     V3 corrected_v = dv + mv(dv_dba, dba) + mv(dv_dbg, dbg);
-    Q4 corrected_q = qmul(dq, rotvec2quat(mv(dq_dbg, dbg)));
+    Q4 corrected_q = qmul(dq, Q4{q_corr[0], q_corr[1], q_corr[2], q_corr[3]});
     V3 corrected_s = dsd + mv(ds_dbg, dbg) + dsodo * ds_dsodo;
     const double T = delta_time_;
 
@@ -422,7 +455,7 @@ bool PreintegrationOdo::evaluate(const double *const *parameters, double *residu
         for (size_t k = 0; k + 3 < pn_.size(); k += 4) p_cor = p_cor + (V3{pn_[k + 1], pn_[k + 2], pn_[k + 3]} - p0) * pn_[k];
         p_cor    = mv(scale(iewn_skew, 2.0), p_cor);
         V3 v_cor = mv(scale(iewn_skew, 2.0), p1 - p0);
-        Q4 qnn   = rotvec2quat(-iewn * T);
+        Q4 qnn{q_nn[0], q_nn[1], q_nn[2], q_nn[3]};
         V3 dpn   = p1 - p0 - v0 * T - 0.5 * gravity * T * T + p_cor;
         V3 dvn   = v1 - v0 - gravity * T + v_cor;
         Q4 qb0b1 = qmul(qmul(qinv(q1), qnn), q0);

@@ -21,12 +21,18 @@
 #pragma weak icg_reproj_host_parts_build
 #pragma weak icg_reproj_host_parts_build_prior
 #pragma weak icg_reproj_host_parts_build_preint
+#pragma weak icg_reproj_host_parts_build_preint_odo
 
 namespace icg {
 
 const char *WindowSolverBatch::devicePreintegrationMissing() {
     if (!PreintegrationSet::available()) return PreintegrationSet::missingEntry();
     return &icg_reproj_host_parts_build_preint == nullptr ? "icg_reproj_host_parts_build_preint" : nullptr;
+}
+
+const char *WindowSolverBatch::devicePreintegrationOdoMissing() {
+    if (!PreintegrationOdoSet::available()) return PreintegrationOdoSet::missingEntry();
+    return &icg_reproj_host_parts_build_preint_odo == nullptr ? "icg_reproj_host_parts_build_preint_odo" : nullptr;
 }
 
 bool WindowSolverBatch::devicePreintegrationAvailable() { return devicePreintegrationMissing() == nullptr; }
@@ -123,7 +129,7 @@ bool WindowSolverBatch::layout() {
         W.host_blocks.clear(), W.host_cols.clear();
         W.resident_of_residual.assign(W.problem.residuals.size(), {}), W.resident_of_block.clear();
         for (std::vector<int32_t> &c : W.resident_cols) c.clear();
-        int count[kFamilies] = {0, 0}; // (the window's own: the set indices follow once all windows are laid out)
+        int count[kFamilies] = {0, 0, 0}; // (the window's own: the set indices follow once all windows are laid out)
         std::vector<int> cols;
         for (size_t id = 0; id < W.problem.residuals.size(); id++) {
             const solver_detail::Residual &R = W.problem.residuals[id];
@@ -145,16 +151,20 @@ bool WindowSolverBatch::layout() {
             // device preintegration: a factor without a loss whose integration result is there and can be whitened
             const PreintegrationFactor *pf = device_preint_ && !R.loss ? dynamic_cast<const PreintegrationFactor *>(R.cost.get()) : nullptr;
             if (pf && pf->preintegration().ready() && R.blocks.size() == 4) res = {kPreint, count[kPreint]++};
+            // the odometer variants behind the same switch: their own resident set (19 residuals, a 19 x 34 Jacobian)
+            const PreintegrationOdoFactor *of = device_preint_ && !R.loss && !pf ? dynamic_cast<const PreintegrationOdoFactor *>(R.cost.get()) : nullptr;
+            if (of && of->preintegration().ready() && R.blocks.size() == 4) res = {kPreintOdo, count[kPreintOdo]++};
             solver_detail::hostBlockColumns(W.problem, R, cols);
             if (cols.empty()) continue;
             W.resident_of_block.push_back(res);
             // a resident block's columns of its source matrix: the free local columns of its non-constant parameter blocks in block order, the
-            // columns gatherHostBlock selects, counted in the prior's J0 or in the factor's 15 x 32 Jacobian (7 | 9 | 7 | 9)
-            static const int preint_first[4] = {0, 7, 16, 23};
+            // columns gatherHostBlock selects, counted in the prior's J0 or in the factor's 15 x 32 (7 | 9 | 7 | 9) or 19 x 34 (7 | 10 | 7 | 10) Jacobian
+            static const int preint_first[4] = {0, 7, 16, 23}, preint_odo_first[4] = {0, 7, 17, 24};
             for (size_t a = 0; res.family != kNone && a < R.blocks.size(); a++) {
                 const solver_detail::Block &A = W.problem.blocks[(size_t) W.problem.block_of.at(R.blocks[a])];
                 if (A.column < 0) continue;
-                for (int x = 0; x < A.local; x++) W.resident_cols[res.family].push_back((res.family == kPrior ? v->index[a] : preint_first[a]) + x);
+                const int first = res.family == kPrior ? v->index[a] : res.family == kPreint ? preint_first[a] : preint_odo_first[a];
+                for (int x = 0; x < A.local; x++) W.resident_cols[res.family].push_back(first + x);
             }
             W.host_blocks.push_back({(int) id, R.cost->num_residuals(), (int) cols.size(), 0, 0, 0});
             W.host_cols.insert(W.host_cols.end(), cols.begin(), cols.end());
@@ -180,10 +190,11 @@ bool WindowSolverBatch::layout() {
         // the resident sets: the windows' priors in window order, the preintegration factors in window and residual order
         prior_views_.clear(), prior_where_.clear(), hp_prior_cols_.clear();
         preint_list_.clear(), preint_where_.clear(), hp_preint_cols_.clear();
-        hp_prior_of_.assign(hp_nr_.size(), -1), hp_preint_of_.assign(hp_nr_.size(), -1);
+        preint_odo_list_.clear(), preint_odo_where_.clear(), hp_preint_odo_cols_.clear();
+        hp_prior_of_.assign(hp_nr_.size(), -1), hp_preint_of_.assign(hp_nr_.size(), -1), hp_preint_odo_of_.assign(hp_nr_.size(), -1);
         for (size_t w = 0; w < windows_.size(); w++) {
             Window &W                  = windows_[w];
-            const int base[kFamilies] = {(int) prior_views_.size(), (int) preint_list_.size()};
+            const int base[kFamilies] = {(int) prior_views_.size(), (int) preint_list_.size(), (int) preint_odo_list_.size()};
             for (size_t id = 0; id < W.resident_of_residual.size(); id++) {
                 Window::Resident &res = W.resident_of_residual[id];
                 if (res.family == kNone) continue;
@@ -191,15 +202,20 @@ bool WindowSolverBatch::layout() {
                 const ceres::CostFunction *cost = W.problem.residuals[id].cost.get();
                 if (res.family == kPrior)
                     prior_views_.push_back(dynamic_cast<const MargPriorSource *>(cost)->margPriorView()), prior_where_.push_back({(int) w, (int) id});
-                else
+                else if (res.family == kPreint)
                     preint_list_.push_back(&static_cast<const PreintegrationFactor *>(cost)->preintegration()), preint_where_.push_back({(int) w, (int) id});
+                else
+                    preint_odo_list_.push_back(&static_cast<const PreintegrationOdoFactor *>(cost)->preintegration()), preint_odo_where_.push_back({(int) w, (int) id});
             }
             for (size_t k = 0; k < W.resident_of_block.size(); k++) {
                 Window::Resident &res = W.resident_of_block[k];
-                if (res.family != kNone) (res.family == kPrior ? hp_prior_of_ : hp_preint_of_)[(size_t) W.blk_begin + k] = (res.index += base[res.family]);
+                if (res.family == kNone) continue;
+                std::vector<int32_t> &of = res.family == kPrior ? hp_prior_of_ : res.family == kPreint ? hp_preint_of_ : hp_preint_odo_of_;
+                of[(size_t) W.blk_begin + k] = (res.index += base[res.family]);
             }
             hp_prior_cols_.insert(hp_prior_cols_.end(), W.resident_cols[kPrior].begin(), W.resident_cols[kPrior].end());
             hp_preint_cols_.insert(hp_preint_cols_.end(), W.resident_cols[kPreint].begin(), W.resident_cols[kPreint].end());
+            hp_preint_odo_cols_.insert(hp_preint_odo_cols_.end(), W.resident_cols[kPreintOdo].begin(), W.resident_cols[kPreintOdo].end());
         }
     }
     return P_ > 0;
@@ -262,12 +278,12 @@ struct WindowSolverBatch::Run {
     DeviceSolve dev;
     DeviceParts hp;
     // per family of resident residuals: on for this solve (its switch is set and its set has members); r . r of every member at the last evaluated point
-    bool on[kFamilies] = {false, false};
+    bool on[kFamilies] = {false, false, false};
     std::vector<double> sq[kFamilies];
     std::vector<std::vector<double>> res_cost; // deferred(): the cost of every residual of every window as the pool recorded it (a resident one's comes from sq)
     std::vector<uint8_t> gathered;             // the windows whose prior Jacobian was gathered on the device in this solve
     std::string resident_err;                  // what the evaluation of a family failed with (side thread: error_ takes it after the join)
-    bool deferred() const { return on[kPrior] || on[kPreint]; } // a device value takes a residual's place in the host cost: the pool records per residual
+    bool deferred() const { return on[kPrior] || on[kPreint] || on[kPreintOdo]; } // a device value takes a residual's place in the host cost: the pool records per residual
     bool first = true;                                        // no window has its initial cost yet
     bool all_done = false, any_step = false, any_trial = false; // what solve() decides on after a phase
     BatchClock clk;
@@ -335,6 +351,13 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
         if (!preint_set_.set(factors_.ctx(), preint_list_, &error_)) return false;
         R.on[kPreint] = true;
         R.sq[kPreint].assign(preint_list_.size(), 0.0);
+    }
+    if (device_preint_ && !preint_odo_list_.empty()) {
+        // the odometer factors' integration results likewise, in their own set; a build without its entries refuses by name
+        if (devicePreintegrationOdoMissing()) return refuse(std::string(devicePreintegrationOdoMissing()) + " is not in this build");
+        if (!preint_odo_set_.set(factors_.ctx(), preint_odo_list_, &error_)) return false;
+        R.on[kPreintOdo] = true;
+        R.sq[kPreintOdo].assign(preint_odo_list_.size(), 0.0);
     }
     if (R.deferred()) {
         R.res_cost.resize(NW);
@@ -472,7 +495,12 @@ bool WindowSolverBatch::hostHalfOfWindow(Run &R, size_t w) {
             if (R.deferred()) cost = &R.res_cost[w][id], *cost = 0.0; // per residual: the window's sum waits for the device values
             if (const int family = W.resident_of_residual[id].family; family != kNone) {
                 // evaluated where it is resident: placed only.  A prior's Jacobian is gathered from J0 at the window's first rebuild of the solve and kept, a factor's at every rebuild
-                if (has) H.jac_off[(size_t) W.blk_begin + next] = family == kPreint ? ICG_HP_JAC_FROM_PREINT : R.gathered[w] ? -1 : ICG_HP_JAC_FROM_PRIOR, next++;
+                if (has)
+                    H.jac_off[(size_t) W.blk_begin + next] = family == kPreint      ? ICG_HP_JAC_FROM_PREINT
+                                                             : family == kPreintOdo ? ICG_HP_JAC_FROM_PREINT_ODO
+                                                             : R.gathered[w]        ? -1
+                                                                                    : ICG_HP_JAC_FROM_PRIOR,
+                                                    next++;
                 continue;
             }
             double *Jd = has ? &H.J[W.host_blocks[next].J_off] : nullptr;
@@ -503,29 +531,37 @@ void WindowSolverBatch::packResident(const Run &R) {
     auto blocks = [&](const std::pair<int, int> &at) { return windows_[(size_t) at.first].problem.residuals[(size_t) at.second].blocks.data(); };
     for (size_t k = 0; R.on[kPrior] && k < prior_where_.size(); k++) prior_set_.pack(k, blocks(prior_where_[k]));
     for (size_t k = 0; R.on[kPreint] && k < preint_where_.size(); k++) preint_set_.pack(k, blocks(preint_where_[k]));
+    for (size_t k = 0; R.on[kPreintOdo] && k < preint_odo_where_.size(); k++) preint_odo_set_.pack(k, blocks(preint_odo_where_[k]));
 }
 
 // the resident evaluation of a phase (side thread), one squared norm per member: the priors, then, unless that failed, the preintegration factors,
 // with Jacobians at a linearization and the residual only at a trial point (the cost is all it needs)
 bool WindowSolverBatch::evaluateResident(Run &R, bool want_jac) {
     if (R.on[kPrior] && !prior_set_.evaluateResident(R.sq[kPrior].data(), &R.resident_err)) return false;
-    return !R.on[kPreint] || preint_set_.evaluateResident(want_jac, R.sq[kPreint].data(), &R.resident_err);
+    if (R.on[kPreint] && !preint_set_.evaluateResident(want_jac, R.sq[kPreint].data(), &R.resident_err)) return false;
+    return !R.on[kPreintOdo] || preint_odo_set_.evaluateResident(want_jac, R.sq[kPreintOdo].data(), &R.resident_err);
 }
 
 // The host-part call of a linearization, by the narrowest entry that serves the families that are on (a C ABI without the wider ones keeps working with the
 // narrower switches).  The resident blocks take their residuals where they are, and their Jacobians at every rebuild (factors) or a window's first (priors).
 bool WindowSolverBatch::buildHostParts(Run &R) {
     Run::DeviceParts &H     = R.hp;
-    const bool prior = R.on[kPrior], preint = R.on[kPreint];
+    const bool prior = R.on[kPrior], preint = R.on[kPreint], odo = R.on[kPreintOdo];
     const int32_t *prior_of = prior ? hp_prior_of_.data() : nullptr, *prior_cols = prior ? hp_prior_cols_.data() : nullptr;
+    const int32_t *preint_of = preint ? hp_preint_of_.data() : nullptr, *preint_cols = preint ? hp_preint_cols_.data() : nullptr;
     auto call               = [&](auto entry, auto... resident) { // (every entry takes the narrowest one's arguments first)
         return entry(factors_.ctx(), R.P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(), H.jac_off.data(),
                      H.J.data(), H.r.data(), H.s.data(), H.diag.data(), nullptr, resident...);
     };
-    const int rc = preint  ? call(icg_reproj_host_parts_build_preint, prior_of, prior_cols, hp_preint_of_.data(), hp_preint_cols_.data())
-                   : prior ? call(icg_reproj_host_parts_build_prior, prior_of, prior_cols)
-                           : call(icg_reproj_host_parts_build);
-    if (rc != ICG_OK) return fail(preint ? "icg_reproj_host_parts_build_preint" : prior ? "icg_reproj_host_parts_build_prior" : "icg_reproj_host_parts_build");
+    const int rc = odo      ? call(icg_reproj_host_parts_build_preint_odo, prior_of, prior_cols, preint_of, preint_cols, hp_preint_odo_of_.data(), hp_preint_odo_cols_.data())
+                   : preint ? call(icg_reproj_host_parts_build_preint, prior_of, prior_cols, preint_of, preint_cols)
+                   : prior  ? call(icg_reproj_host_parts_build_prior, prior_of, prior_cols)
+                            : call(icg_reproj_host_parts_build);
+    if (rc != ICG_OK)
+        return fail(odo      ? "icg_reproj_host_parts_build_preint_odo"
+                    : preint ? "icg_reproj_host_parts_build_preint"
+                    : prior  ? "icg_reproj_host_parts_build_prior"
+                             : "icg_reproj_host_parts_build");
     for (size_t w = 0; w < R.NW && prior; w++) R.gathered[w] |= R.reassemble[w];
     return true;
 }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "host_pool.h"
+#include "preintegration_odo.h"
 #include "solver_hip.h"
 #include "window_factors.h"
 
@@ -97,6 +98,13 @@ public:
     static bool devicePreintegrationAvailable();
     static const char *devicePreintegrationMissing(); // the first entry the build lacks for it, nullptr when available
     int preintegrationsOnDevice() const { return (int) preint_list_.size(); } // factors of the last layout that joined the resident set
+    // The same switch serves the odometer variants: a residual block without a loss, with four parameter blocks, whose cost is a
+    // PreintegrationOdoFactor with preintegration().ready() joins the resident ODOMETER set (PreintegrationOdoSet; 19 residuals, a 19 x 34
+    // Jacobian, icg_reproj_host_parts_build_preint_odo) under the same rules and with the same place in the host cost.  A solve without such a
+    // factor issues exactly the calls it issued before; one that holds such a factor needs the odometer entries (solve() names the first that
+    // is missing).  The number of odometer factors of the last layout that joined their resident set:
+    int odometerPreintegrationsOnDevice() const { return (int) preint_odo_list_.size(); }
+    static const char *devicePreintegrationOdoMissing(); // the first entry the build lacks for the odometer factors, nullptr when none
     bool solve(const Options &options, std::vector<Summary> *summaries);
     // removeReprojectionFactorsByChi2 (ic_gvins.cc:1269-1297) for every window; returns the number removed per window
     std::vector<int> removeReprojectionFactorsByChi2(double chi2);
@@ -104,7 +112,7 @@ public:
 
 private:
     // the families of residuals that may be resident on the device for a solve (setDevicePrior, setDevicePreintegration), in the order they are evaluated
-    enum Family { kNone = -1, kPrior = 0, kPreint = 1, kFamilies = 2 };
+    enum Family { kNone = -1, kPrior = 0, kPreint = 1, kPreintOdo = 2, kFamilies = 3 };
     // a window beside its record in factors_: the host-evaluated part of its problem and its state across the steps of a solve
     struct Window {
         solver_detail::Problem problem{"WindowSolverBatch"};
@@ -121,7 +129,7 @@ private:
         int blk_begin{0};
         // resident residuals (layout()): per residual and per block of host_blocks the family it is resident in on the device (kNone: evaluated on
         // the pool; a resident residual whose blocks are all constant has a cost but no host block) and its index in that family's set; per family
-        // the columns of the members' source matrices (a prior's J0, a factor's 15 x 32 Jacobian) its blocks take, block after block
+        // the columns of the members' source matrices (a prior's J0, a factor's 15 x 32 or 19 x 34 Jacobian) its blocks take, block after block
         struct Resident { int family{kNone}, index{-1}; };
         std::vector<Resident> resident_of_residual, resident_of_block;
         std::vector<int32_t> resident_cols[kFamilies];
@@ -165,12 +173,14 @@ private:
     size_t hp_J_total_{0}, hp_r_total_{0};
     // resident residuals (layout()): per block of that list the prior / the factor of the resident sets it is (-1: none) and the resident blocks' columns
     // of J0 / of the 15 x 32 Jacobian; the sets, their members (priors in window order, factors in window and residual order) and where each is
-    std::vector<int32_t> hp_prior_of_, hp_prior_cols_, hp_preint_of_, hp_preint_cols_;
+    std::vector<int32_t> hp_prior_of_, hp_prior_cols_, hp_preint_of_, hp_preint_cols_, hp_preint_odo_of_, hp_preint_odo_cols_;
     std::vector<MargPriorView> prior_views_;
     std::vector<const Preintegration *> preint_list_;
-    std::vector<std::pair<int, int>> prior_where_, preint_where_; // (window, residual)
+    std::vector<const PreintegrationOdo *> preint_odo_list_;
+    std::vector<std::pair<int, int>> prior_where_, preint_where_, preint_odo_where_; // (window, residual)
     MarginalizationPriorSet prior_set_;
     PreintegrationSet preint_set_;
+    PreintegrationOdoSet preint_odo_set_;
     std::string error_;
 };
 

@@ -32,6 +32,7 @@ EXPORTS = [
     "icg_reproj_landmark_min_windows",
     "icg_preint_set", "icg_preint_evaluate_resident", "icg_preint_fetch_resident", "icg_reproj_host_parts_build_preint",
     "icg_preint_odo_batch", "icg_preint_odo_evaluate_batch",
+    "icg_preint_odo_set", "icg_preint_odo_evaluate_resident", "icg_preint_odo_fetch_resident", "icg_reproj_host_parts_build_preint_odo",
 ]
 
 
@@ -41,6 +42,7 @@ CHOL_MAX_N = 512  # ICG_CHOL_MAX_N
 HOST_PART_MAX_NR = 1024  # ICG_HOST_PART_MAX_NR
 HP_JAC_FROM_PRIOR = -2  # ICG_HP_JAC_FROM_PRIOR
 HP_JAC_FROM_PREINT = -3  # ICG_HP_JAC_FROM_PREINT
+HP_JAC_FROM_PREINT_ODO = -4  # ICG_HP_JAC_FROM_PREINT_ODO
 PREINT_SET_MAX = 65535 * 16  # ICG_PREINT_SET_MAX
 
 
@@ -522,6 +524,13 @@ class Context:
         return self.lib.icg_reproj_host_parts_build_preint(self.h, int(P), _p(Pw), _p(rebuild), _p(blk_off), _p(nr), _p(nf), _p(cols), _p(jac_off), _p(J), _p(r),
                                                            _p(host_s), _p(host_diag), _p(part_out), _p(prior_of), _p(prior_cols), _p(preint_of), _p(preint_cols))
 
+    def reproj_host_parts_build_preint_odo_raw(self, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, prior_of, prior_cols,
+                                               preint_of, preint_cols, preint_odo_of, preint_odo_cols):
+        """icg_reproj_host_parts_build_preint_odo on the caller's arrays (None = NULL; the outputs are written in place) -> the return code"""
+        return self.lib.icg_reproj_host_parts_build_preint_odo(self.h, int(P), _p(Pw), _p(rebuild), _p(blk_off), _p(nr), _p(nf), _p(cols), _p(jac_off), _p(J),
+                                                               _p(r), _p(host_s), _p(host_diag), _p(part_out), _p(prior_of), _p(prior_cols), _p(preint_of),
+                                                               _p(preint_cols), _p(preint_odo_of), _p(preint_odo_cols))
+
     def reproj_host_parts_build_prior(self, P, Pw, windows, rebuild=None, host_s=None, host_diag=None):
         """icg_reproj_host_parts_build_prior.  windows: per window a list of blocks; an ordinary block is (J nr x nf, r, cols, keep) as in
         reproj_host_parts_build, a prior block is ("prior", p, prior_cols, cols, how): prior p of the resident set (marg_prior_set), how =
@@ -654,6 +663,38 @@ class Context:
         res = np.zeros((n, 15))
         J = np.zeros((n, 480)) if want_jac else None
         self._ck(self.lib.icg_preint_fetch_resident(self.h, _p(res), _p(J)), "icg_preint_fetch_resident")
+        return res, J
+
+    def preint_odo_set(self, variant, delta, jac, sqrt_info, dt, env, q_nn, pn_offsets=None, pn=None):
+        """icg_preint_odo_set: len(variant) odometer factors become resident (variant 2 / 3 per factor; sqrt_info and q_nn are the host's)"""
+        variant = i32(variant).reshape(-1)
+        n = len(variant)
+        delta, jac, sqrt_info = f64(delta).reshape(n, 20), f64(jac).reshape(n, 361), f64(sqrt_info).reshape(n, 361)
+        dt, env, q_nn = f64(dt).reshape(n), f64(env).reshape(n, 4), f64(q_nn).reshape(n, 4)
+        po = None if pn_offsets is None else i32(pn_offsets)
+        pnr = None if pn is None else f64(pn).reshape(-1, 4)
+        self._preint_odo_n = 0
+        self._ck(self.lib.icg_preint_odo_set(self.h, n, _p(variant), _p(delta), _p(jac), _p(sqrt_info), _p(dt), _p(env), _p(q_nn), _p(po), _p(pnr)),
+                 "icg_preint_odo_set")
+        self._preint_odo_n = n
+
+    def preint_odo_evaluate_resident(self, points, q_corr, want_jac=True):
+        """icg_preint_odo_evaluate_resident: residuals (and Jacobians) stay on the device -> sq_norm (r . r per factor)"""
+        n = getattr(self, "_preint_odo_n", 0)
+        points, q_corr = f64(points).reshape(-1, 34), f64(q_corr).reshape(-1, 4)
+        if n and (points.shape[0] != n or q_corr.shape[0] != n):
+            raise IcgError(f"preint_odo_evaluate_resident: {points.shape[0]} points and {q_corr.shape[0]} quaternions, the resident set has {n} factors")
+        sq = np.zeros(max(n, 1))
+        self._ck(self.lib.icg_preint_odo_evaluate_resident(self.h, _p(points), _p(q_corr), 1 if want_jac else 0, _p(sq)),
+                 "icg_preint_odo_evaluate_resident")
+        return sq[:n]
+
+    def preint_odo_fetch_resident(self, want_jac=True):
+        """icg_preint_odo_fetch_resident -> (residuals n x 19, jacobians n x 646 or None) of the last resident evaluation"""
+        n = max(getattr(self, "_preint_odo_n", 0), 1)
+        res = np.zeros((n, 19))
+        J = np.zeros((n, 646)) if want_jac else None
+        self._ck(self.lib.icg_preint_odo_fetch_resident(self.h, _p(res), _p(J)), "icg_preint_odo_fetch_resident")
         return res, J
 
     # ---- M4

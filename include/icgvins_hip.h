@@ -335,6 +335,26 @@ int icg_reproj_host_parts_build_preint(icg_ctx *ctx, int P, const int32_t *Pw, c
                                        const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s,
                                        double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols, const int32_t *preint_of,
                                        const int32_t *preint_cols);
+/* icg_reproj_host_parts_build_preint with blocks that are factors of the resident ODOMETER P2 set (icg_preint_odo_set) at the point of its
+ * last icg_preint_odo_evaluate_resident, as a third family beside the priors and the 15-state factors: neither such a factor's residual nor
+ * its 19 x 32 Jacobian crosses the link.  The arguments of icg_reproj_host_parts_build_preint, plus:
+ *   preint_odo_of    per block of the call: >= 0 = the block is factor preint_odo_of[b] of the resident odometer set, < 0 = it is not
+ *   preint_odo_cols  for those blocks, in block order (those of windows that are not rebuilt included), nf[b] indices into the 34 columns of
+ *                    the factor's resident Jacobian (7 | 10 | 7 | 10): 0-5, 7-16, 17-22, 24-33 when all four parameter blocks are free
+ * Such a block of a rebuilt window has nr[b] == 19; the row stride of its source is 34.  jac_off[b] == ICG_HP_JAC_FROM_PREINT_ODO gathers
+ * Jd[k][y] = Jf[k][preint_odo_cols[y]] on the device, -1 keeps the previous gather, an offset >= 0 uploads.  The three entries above are
+ * this one with NULL for the arguments they do not have; the accumulation kernel is the same.
+ * ICG_ERR_INVALID beyond the cases there (the message names the window and the block), for a block of a rebuilt window: preint_odo_of[b]
+ * outside the resident set, nr[b] != 19, a preint_odo_cols entry outside [0, 34) or 6 or 23, no odometer set resident or not evaluated since
+ * it was set (for the gather: not evaluated with want_jac), such blocks without preint_odo_cols, a block that is also a prior or a 15-state
+ * factor, ICG_HP_JAC_FROM_PREINT_ODO for a block with preint_odo_of[b] < 0 (or without preint_odo_of).  ICG_ERR_CAPACITY: more than 65535
+ * resident blocks of the three families in the rebuilt windows.  After an error nothing was launched and no output was touched. */
+#define ICG_HP_JAC_FROM_PREINT_ODO (-4)
+int icg_reproj_host_parts_build_preint_odo(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
+                                           const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r,
+                                           double *host_s, double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols,
+                                           const int32_t *preint_of, const int32_t *preint_cols, const int32_t *preint_odo_of,
+                                           const int32_t *preint_odo_cols);
 /* problem setup: pre-sizes the resident window systems and the staging memory for reduced systems of size P (a hint; optional) */
 int icg_reproj_reserve_windows(icg_ctx *ctx, int P);
 int icg_reproj_backsub_windows(icg_ctx *ctx, int P, const double *delta_c, double *delta_l, double *lm_terms);
@@ -450,6 +470,33 @@ int icg_preint_evaluate_resident(icg_ctx *ctx, const double *points, const doubl
  * ICG_ERR_INVALID: no resident set, NULL residuals, nothing evaluated since icg_preint_set, or Jacobians asked for after an evaluation with
  * want_jac == 0. */
 int icg_preint_fetch_resident(icg_ctx *ctx, double *residuals, double *jacobians);
+
+/* ---- P2 of the odometer variants on a RESIDENT set of factors: the 19-state twins of the three entries above, with a resident set of their
+ * own (a context may hold a 15-state set and an odometer set at once; neither entry touches the other's).  The device calls no sin / cos /
+ * sqrt: the two quaternions come from the host (PreintegrationOdo::earthRateQuaternion with the set, PreintegrationOdo::correctionQuaternion
+ * with every point), and what is left is + - * / in the host's order without contraction: residuals, Jacobians and sq_norm have the bits of
+ * PreintegrationOdo::evaluate given the same sqrt_info.
+ * Per factor f, in the layout icg_preint_odo_batch writes: variant[f] (2 Odo, 3 EarthOdo: one set serves mixed windows), delta_state 20,
+ * jac 361, delta_time 1, env 4 = gravity, iewn[3]; sqrt_info 361 is the host's square-root information (shipped, not recomputed); q_nn 4 =
+ * rotvec2quat(-iewn T) as (x, y, z, w), read for EarthOdo factors only; EarthOdo factor f owns the rows [pn_offsets[f], pn_offsets[f+1]) of
+ * pn (the rows of an Odo factor are not read).  pn_offsets / pn may be NULL when no factor is EarthOdo.
+ * Replaces the odometer set the context held; it stays until the next icg_preint_odo_set or icg_ctx_destroy.  ICG_ERR_INVALID (the message
+ * names the factor where there is one): n_factors <= 0, a NULL required pointer, a variant outside {2, 3}, pn_offsets[0] < 0 or not
+ * monotone, an EarthOdo factor without pn_offsets, rows without pn.  ICG_ERR_CAPACITY: more than ICG_PREINT_SET_MAX factors.  After a failed
+ * call no odometer set is resident. */
+int icg_preint_odo_set(icg_ctx *ctx, int n_factors, const int32_t *variant, const double *delta_state, const double *jac, const double *sqrt_info,
+                       const double *delta_time, const double *env, const double *q_nn, const int32_t *pn_offsets, const double *pn);
+/* Evaluates every factor of the resident odometer set: points 34 per factor (pose0[7] mix0[10] pose1[7] mix1[10]), q_corr 4 per factor =
+ * rotvec2quat(dq_dbg (bg0 - delta.bg)) as (x, y, z, w).  Kept on the device until the next evaluation or icg_preint_odo_set: the whitened
+ * residuals (19 per factor) and, with want_jac != 0, the whitened Jacobian as ONE row-major 19 x 34 matrix per factor, columns
+ * 7 | 10 | 7 | 10 (columns 6 and 23, the seventh pose columns, are +0.0).  Returned: sq_norm[f] = sum_k r[k]^2, k ascending from +0.0.  An
+ * evaluation with want_jac == 0 invalidates the kept Jacobians.  ICG_ERR_INVALID without a resident set or with a NULL argument: nothing is
+ * launched. */
+int icg_preint_odo_evaluate_resident(icg_ctx *ctx, const double *points, const double *q_corr, int want_jac, double *sq_norm);
+/* The kept results of the last icg_preint_odo_evaluate_resident in the layout of icg_preint_odo_evaluate_batch: residuals 19 per factor,
+ * jacobians 646 per factor = 19x7 | 19x10 | 19x7 | 19x10 (NULL: not fetched).  For tests.  ICG_ERR_INVALID: no resident set, NULL residuals,
+ * nothing evaluated since icg_preint_odo_set, or Jacobians asked for after an evaluation with want_jac == 0. */
+int icg_preint_odo_fetch_resident(icg_ctx *ctx, double *residuals, double *jacobians);
 
 /* ---- M4: MarginalizationFactor::Evaluate (factors/marginalization_factor.h:47-101) for the priors of many windows, RESIDENT on the
  * device: a prior is constant between two marginalizations while every LM iteration evaluates it at a new point, so the priors are
