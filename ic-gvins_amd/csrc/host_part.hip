@@ -11,7 +11,8 @@
 // (icg_reproj_host_parts_build_prior): k_host_part_prior copies its residuals of the last resident evaluation and the free columns of its J0
 // to the places k_host_part reads.  The same kernel serves a block that is a preintegration factor of the resident P2 set (preint.hip,
 // icg_reproj_host_parts_build_preint): its source matrix is the factor's whitened 15 x 32 Jacobian, its row stride 32; and a factor of the
-// resident odometer P2 set (preint_odo.hip, icg_reproj_host_parts_build_preint_odo): 19 x 34, row stride 34.
+// resident odometer P2 set (preint_odo.hip, icg_reproj_host_parts_build_preint_odo): 19 x 34, row stride 34; and a member of the resident nav set
+// (nav.hip, icg_reproj_host_parts_build_nav): nr x width, row stride the member's block width.
 #include <array>
 
 #include "reproj_internal.h"
@@ -236,13 +237,33 @@ static int hp_rules_preint_odo(icg_ctx *ctx, const char *me, int w, int p, int f
     return ICG_OK;
 }
 
-#define HP_FAMILIES 3 // marginalization priors, preintegration factors, odometer preintegration factors
+static int hp_rules_nav(icg_ctx *ctx, const char *me, int w, int p, int fp, const int32_t *pc, hp_prior &B) {
+    const icg_nav_resident &ns = ctx->nav;
+    if (!pc) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a navigation block without nav_cols", me, w, p);
+    if (ns.n <= 0 || !ns.res_valid || (B.fill && !ns.jac_valid))
+        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no nav set is resident and evaluated%s (icg_nav_set, then icg_nav_evaluate_resident)", me, w, p,
+                        B.fill ? " with Jacobians" : "");
+    if (B.fill && ns.any_robust && !ns.corrected)
+        return icg_fail(ctx, ICG_ERR_INVALID,
+                        "%s: window %d, block %d: the nav set has robustified members and its last evaluation is not corrected (icg_nav_correct_resident first)", me, w, p);
+    if (fp >= ns.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: member %d outside the resident nav set of %d", me, w, p, fp, ns.n);
+    const int kind = ns.h_kind[(size_t) fp], width = icg_nav_width(kind);
+    if (B.nr != icg_nav_nr(kind))
+        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, nav member %d (kind %d) has %d", me, w, p, B.nr, fp, kind, icg_nav_nr(kind));
+    for (int x = 0; x < B.nf; x++)
+        if (pc[x] < 0 || pc[x] >= width || (width == 7 && pc[x] == 6))
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: navigation column %d (0 .. %d%s)", me, w, p, pc[x], width - 1, width == 7 ? " without 6" : "");
+    B.J = ns.d_jac ? ns.d_jac + ns.h_j_off[(size_t) fp] : nullptr, B.res = ns.d_res + ns.h_r_off[(size_t) fp], B.stride = width; // (row-major nr x width)
+    return ICG_OK;
+}
+
+#define HP_FAMILIES 4 // marginalization priors, preintegration factors, odometer preintegration factors, navigation factors
 struct hp_plan { // what validation leaves for the stages behind it
     bool drop_all, have_kept;
     std::vector<int32_t> r_off, c_off; // every block's place in the staged r and cols
     std::vector<hp_prior> res;                // the resident blocks of the rebuilt windows ...
     std::vector<std::array<int, 3>> res_at;   // ... their (window, position in the window's block list, family)
-    std::vector<int32_t> res_cols; // the staged column list their pc_off counts in: prior_cols | preint_cols | preint_odo_cols of all windows (each may be absent)
+    std::vector<int32_t> res_cols; // the staged column list their pc_off counts in: prior_cols | preint_cols | preint_odo_cols | nav_cols of all windows (each may be absent)
     size_t n_res_cols = 0, ship_doubles = 0, out_cells = 0; // (n_res_cols: what the families' cursors walked)
     int n_rebuilt = 0, max_cells = 0, max_prior_nr = 0;
 };
@@ -264,8 +285,9 @@ static int hp_validate_block(icg_ctx *ctx, const hp_args &a, const hp_family (&F
         if (idx[f] < 0) continue;
         if (fam >= 0 && f == 1) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both a prior (%d) and a preintegration factor (%d)", me, w, p, idx[0], idx[1]);
         if (fam >= 0)
-            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both %s (%d) and an odometer preintegration factor (%d)", me, w, p,
-                            fam == 0 ? "a prior" : "a preintegration factor", idx[fam], idx[f]);
+            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both %s (%d) and %s (%d)", me, w, p,
+                            fam == 0 ? "a prior" : fam == 1 ? "a preintegration factor" : "an odometer preintegration factor", idx[fam],
+                            f == 2 ? "an odometer preintegration factor" : "a navigation factor", idx[f]);
         fam = f;
         hp_prior B{nullptr, nullptr, 0 /* its place among the kept Jacobians: hp_stage */, 0, plan.r_off[(size_t) b], (int32_t) c0[f], nr, nf, a.jac_off[b] == F[f].gather ? 1 : 0};
         if (int rc = F[f].rules(ctx, me, w, p, idx[f], F[f].cols ? F[f].cols + c0[f] : nullptr, B)) return rc;
@@ -281,6 +303,8 @@ static int hp_validate_block(icg_ctx *ctx, const hp_args &a, const hp_family (&F
         return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: ICG_HP_JAC_FROM_PREINT for a block that is no preintegration factor", me, w, p);
     } else if (a.jac_off[b] == ICG_HP_JAC_FROM_PREINT_ODO) {
         return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: ICG_HP_JAC_FROM_PREINT_ODO for a block that is no odometer preintegration factor", me, w, p);
+    } else if (a.jac_off[b] == ICG_HP_JAC_FROM_NAV && F[3].of) { // (an entry without nav_of reports the value, as it always did)
+        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: ICG_HP_JAC_FROM_NAV for a block that is no navigation factor", me, w, p);
     } else if (a.jac_off[b] == -1) {
         any_keep = true;
         if (!kept || (size_t) p >= kept->size()) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no kept Jacobian", me, w, p);
@@ -448,7 +472,7 @@ static int hp_stage(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[HP_FAMI
     S.d_cols   = c.in(a.cols, n_c);
     S.d_pr     = c.in(plan.res.data(), plan.res.size());
     S.d_pc     = plan.res.empty() ? nullptr : c.in(plan.res_cols.data(), plan.res_cols.size());
-    if (!F[0].of && !F[1].of && !F[2].of) {
+    if (!F[0].of && !F[1].of && !F[2].of && !F[3].of) {
         S.d_r = c.in(a.r, n_r);
     } else {
         // The slots of the resident blocks (of every window, rebuilt or not) are placed but not read from the caller: staged block by block,
@@ -458,7 +482,7 @@ static int hp_stage(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[HP_FAMI
         const size_t off = icg_arena_alloc(ctx, sizeof(double) * n_r);
         double *h        = icg_h<double>(ctx, off);
         for (int b = 0; b < nb; b++)
-            if ((!F[0].of || F[0].of[b] < 0) && (!F[1].of || F[1].of[b] < 0) && (!F[2].of || F[2].of[b] < 0))
+            if ((!F[0].of || F[0].of[b] < 0) && (!F[1].of || F[1].of[b] < 0) && (!F[2].of || F[2].of[b] < 0) && (!F[3].of || F[3].of[b] < 0))
                 memcpy(h + plan.r_off[(size_t) b], a.r + plan.r_off[(size_t) b], sizeof(double) * (size_t) a.nr[b]);
         c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * n_r);
         S.d_r = icg_d<double>(ctx, off);
@@ -538,15 +562,26 @@ extern "C" int icg_reproj_host_parts_build_preint_odo(icg_ctx *ctx, int P, const
                                                       double *host_s, double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols,
                                                       const int32_t *preint_of, const int32_t *preint_cols, const int32_t *preint_odo_of,
                                                       const int32_t *preint_odo_cols) {
+    return icg_reproj_host_parts_build_nav(ctx, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, prior_of, prior_cols, preint_of,
+                                           preint_cols, preint_odo_of, preint_odo_cols, nullptr, nullptr);
+}
+
+extern "C" int icg_reproj_host_parts_build_nav(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
+                                               const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s,
+                                               double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols, const int32_t *preint_of,
+                                               const int32_t *preint_cols, const int32_t *preint_odo_of, const int32_t *preint_odo_cols, const int32_t *nav_of,
+                                               const int32_t *nav_cols) {
     if (!ctx) return ICG_ERR_INVALID;
-    const char *me = preint_odo_of ? "icg_reproj_host_parts_build_preint_odo"
-                     : preint_of   ? "icg_reproj_host_parts_build_preint"
-                     : prior_of    ? "icg_reproj_host_parts_build_prior"
-                                   : "icg_reproj_host_parts_build";
+    const char *me = nav_of          ? "icg_reproj_host_parts_build_nav"
+                     : preint_odo_of ? "icg_reproj_host_parts_build_preint_odo"
+                     : preint_of     ? "icg_reproj_host_parts_build_preint"
+                     : prior_of      ? "icg_reproj_host_parts_build_prior"
+                                     : "icg_reproj_host_parts_build";
     const hp_args a{me, P, ctx->part_w.W, Pw, blk_off, nr, nf, cols, rebuild, jac_off, J, r, host_s, host_diag, part_out};
     hp_family F[HP_FAMILIES] = {{hp_rules_prior, prior_of, prior_cols, ICG_HP_JAC_FROM_PRIOR, 0},
                                 {hp_rules_preint, preint_of, preint_cols, ICG_HP_JAC_FROM_PREINT, 0},
-                                {hp_rules_preint_odo, preint_odo_of, preint_odo_cols, ICG_HP_JAC_FROM_PREINT_ODO, 0}};
+                                {hp_rules_preint_odo, preint_odo_of, preint_odo_cols, ICG_HP_JAC_FROM_PREINT_ODO, 0},
+                                {hp_rules_nav, nav_of, nav_cols, ICG_HP_JAC_FROM_NAV, 0}};
     hp_plan plan;
     int rc, dst;
     if ((rc = hp_validate(ctx, a, F, plan))) return rc;
@@ -559,4 +594,3 @@ extern "C" int icg_reproj_host_parts_build_preint_odo(icg_ctx *ctx, int P, const
     if ((rc = hp_stage(ctx, a, F, plan, next, c, S))) return rc;
     return hp_launch(ctx, a, plan, next, dst, c, S);
 }
-

@@ -104,6 +104,25 @@ struct icg_preint_odo_resident {
     bool res_valid = false, jac_valid = false; // evaluated (with Jacobians) since the set was made resident
 };
 
+// Resident navigation factors (nav.hip): kinds, offsets and constants of the members in one buffer that grows on demand and is freed with the
+// context; n = 0: no set is resident.  The results of the last evaluation stay in d_res (nr per member) and d_jac (nr x width row-major per
+// member), both concatenated in member order.
+struct icg_nav_resident {
+    int n = 0;
+    int64_t total_aux = 0;
+    char *d_set = nullptr; // aux total_aux | kind n | aux_off n | r_off n+1 | j_off n+1 | p_off n+1
+    size_t set_cap = 0;    // bytes
+    std::vector<int32_t> h_kind, h_r_off, h_j_off, h_p_off; // host copies: widths place the points, offsets place a member for the host-part entry
+    double *d_res = nullptr, *d_jac = nullptr;
+    size_t res_cap = 0, jac_cap = 0; // bytes
+    bool res_valid = false, jac_valid = false; // evaluated (with Jacobians) since the set was made resident
+    bool corrected = false;                    // icg_nav_correct_resident ran on what the last evaluation kept
+    bool any_robust = false;                   // a correction of this set has marked a member: the host-part gather then waits for every evaluation's correction
+};
+// residuals and block width of a navigation factor by kind 0..5: {3, 6, 6, 9, 7, 10} and {7, 9, 7, 9, 10, 10}, a nibble each
+__host__ __device__ static inline int icg_nav_nr(int kind) { return (0xA79663 >> (4 * kind)) & 15; }
+__host__ __device__ static inline int icg_nav_width(int kind) { return (0xAA9797 >> (4 * kind)) & 15; }
+
 // The linearization icg_marg_linearize_batch_keep left on the device (marg_linearize.hip): J0 of every window (r x r row-major, window after
 // window), then e0 of every window, in one buffer the context owns.  id = 0: nothing is kept.  A live id is listed in the process-wide table
 // of ctx.hip (icg_kept_register / icg_kept_drop / icg_kept_lookup), through which icg_marg_prior_set_from_kept of any context finds it.
@@ -196,6 +215,7 @@ struct icg_ctx {
     icg_marg_set marg;
     icg_preint_resident preint;
     icg_preint_odo_resident preint_odo;
+    icg_nav_resident nav;
     // M3 (marg_linearize.hip): per-window working memory of icg_marg_linearize_batch for the windows that do not fit in LDS; grows on demand
     double *d_lin_scratch = nullptr;
     size_t lin_scratch_cap = 0; // bytes

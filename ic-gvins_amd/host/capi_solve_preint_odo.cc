@@ -11,49 +11,6 @@
 
 using namespace icg;
 
-namespace {
-// the velocity / bias / scale-factor prior on a 10-wide mix block (MixPriorFactor at 10)
-class OdoMixPriorFactor : public ceres::SizedCostFunction<10, 10> {
-public:
-    OdoMixPriorFactor(const double *x0, double weight) : w_(weight) { memcpy(x0_, x0, sizeof x0_); }
-    bool Evaluate(const double *const *parameters, double *residuals, double **jacobians) const override {
-        for (int k = 0; k < 10; k++) residuals[k] = w_ * (parameters[0][k] - x0_[k]);
-        if (jacobians && jacobians[0]) {
-            memset(jacobians[0], 0, sizeof(double) * 100);
-            for (int k = 0; k < 10; k++) jacobians[0][k * 10 + k] = w_;
-        }
-        return true;
-    }
-
-private:
-    double x0_[10], w_;
-};
-
-std::shared_ptr<IntegrationParameters> odo_params19(const double *params19) {
-    auto P     = preint_params(params19);
-    P->odo_std = Vector3d(params19[9], params19[10], params19[11]);
-    P->odo_srw = params19[12];
-    P->abv     = Vector3d(params19[13], params19[14], params19[15]);
-    P->lodo    = Vector3d(params19[16], params19[17], params19[18]);
-    return P;
-}
-
-// a PreintegrationOdo as if integrateBatch had returned the given result (no device, no IMU samples)
-std::shared_ptr<PreintegrationOdo> odo_from_result(const std::shared_ptr<IntegrationParameters> &P, int variant, const double *delta20, const double *jac361,
-                                                   const double *cov361, double delta_time, const double *pn, int pn_rows, const double *iewn3) {
-    IntegrationState st;
-    st.bg   = Vector3d(delta20[10], delta20[11], delta20[12]);
-    st.ba   = Vector3d(delta20[13], delta20[14], delta20[15]);
-    st.sodo = delta20[19];
-    auto p  = std::make_shared<PreintegrationOdo>(P, IMU(), st, variant == 2 ? PreintegrationOdo::ODO : PreintegrationOdo::EARTH_ODO);
-    double cur16[16];
-    preint_put_state(st, cur16);
-    p->setIntegrationResult(cur16, delta20, jac361, cov361, delta_time, pn_rows > 0 ? pn : nullptr, pn_rows > 0 ? pn_rows : 0,
-                            Vector3d(iewn3[0], iewn3[1], iewn3[2]));
-    return p;
-}
-} // namespace
-
 extern "C" {
 
 // n factors built from GIVEN integration results (setIntegrationResult; no device is touched): per factor variant (2 Odo, 3 EarthOdo),

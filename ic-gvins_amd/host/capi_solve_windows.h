@@ -1,6 +1,6 @@
-// Shared by capi_solve_prior.cc and capi_solve_preint.cc (internal linkage, like capi_windows.h): the batch of visual-inertial windows with
-// optional marginalization priors on plain arrays, built and solved once for both entries.  The entries differ in the modes they admit and
-// in the switches they set.
+// Shared by capi_solve_prior.cc, capi_solve_preint.cc, capi_solve_preint_odo.cc and capi_solve_nav.cc (internal linkage, like
+// capi_windows.h): the batch of visual-inertial windows with optional marginalization priors on plain arrays, built and solved once for the
+// first two entries, which differ in the modes they admit and in the switches they set; and what the odometer windows of the last two share.
 #pragma once
 #include <chrono>
 #include <cstdlib>
@@ -39,6 +39,34 @@ private:
     std::vector<const double *> x0_ptr_;
     icg::MargPriorView view_;
 };
+
+// ---- the odometer windows (capi_solve_preint_odo.cc, capi_solve_nav.cc): parameters of 19 and objects from GIVEN integration results
+std::shared_ptr<icg::IntegrationParameters> odo_params19(const double *params19) {
+    using icg::Vector3d;
+    auto P     = preint_params(params19);
+    P->odo_std = Vector3d(params19[9], params19[10], params19[11]);
+    P->odo_srw = params19[12];
+    P->abv     = Vector3d(params19[13], params19[14], params19[15]);
+    P->lodo    = Vector3d(params19[16], params19[17], params19[18]);
+    return P;
+}
+
+// a PreintegrationOdo as if integrateBatch had returned the given result (no device, no IMU samples)
+std::shared_ptr<icg::PreintegrationOdo> odo_from_result(const std::shared_ptr<icg::IntegrationParameters> &P, int variant, const double *delta20,
+                                                        const double *jac361, const double *cov361, double delta_time, const double *pn, int pn_rows,
+                                                        const double *iewn3) {
+    using namespace icg;
+    IntegrationState st;
+    st.bg   = Vector3d(delta20[10], delta20[11], delta20[12]);
+    st.ba   = Vector3d(delta20[13], delta20[14], delta20[15]);
+    st.sodo = delta20[19];
+    auto p  = std::make_shared<PreintegrationOdo>(P, IMU(), st, variant == 2 ? PreintegrationOdo::ODO : PreintegrationOdo::EARTH_ODO);
+    double cur16[16];
+    preint_put_state(st, cur16);
+    p->setIntegrationResult(cur16, delta20, jac361, cov361, delta_time, pn_rows > 0 ? pn : nullptr, pn_rows > 0 ? pn_rows : 0,
+                            Vector3d(iewn3[0], iewn3[1], iewn3[2]));
+    return p;
+}
 
 // the arguments icgh_backend_solve_prior_batch and icgh_backend_solve_preint_batch share (documented at the first)
 struct PriorWindowArgs {

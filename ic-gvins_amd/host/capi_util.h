@@ -198,4 +198,20 @@ public:
 private:
     double x0_[9], w_;
 };
+// the velocity / bias / scale-factor prior on a 10-wide mix block (MixPriorFactor at 10)
+class OdoMixPriorFactor : public ceres::SizedCostFunction<10, 10> {
+public:
+    OdoMixPriorFactor(const double *x0, double weight) : w_(weight) { memcpy(x0_, x0, sizeof x0_); }
+    bool Evaluate(const double *const *parameters, double *residuals, double **jacobians) const override {
+        for (int k = 0; k < 10; k++) residuals[k] = w_ * (parameters[0][k] - x0_[k]);
+        if (jacobians && jacobians[0]) {
+            memset(jacobians[0], 0, sizeof(double) * 100);
+            for (int k = 0; k < 10; k++) jacobians[0][k * 10 + k] = w_;
+        }
+        return true;
+    }
+
+private:
+    double x0_[10], w_;
+};
 } // namespace

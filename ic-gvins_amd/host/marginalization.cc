@@ -27,17 +27,8 @@ bool ResidualBlockInfo::Evaluate() {
         double sq_norm = 0, rho[3];
         for (double v : residuals_) sq_norm += v * v;
         loss_function_->Evaluate(sq_norm, rho);
-        const double sqrt_rho1 = std::sqrt(rho[1]);
-        double residual_scaling, alpha_sq_norm;
-        if ((sq_norm == 0.0) || (rho[2] <= 0.0)) {
-            residual_scaling = sqrt_rho1;
-            alpha_sq_norm    = 0.0;
-        } else {
-            const double D     = 1.0 + 2.0 * sq_norm * rho[2] / rho[1];
-            const double alpha = 1.0 - std::sqrt(D);
-            residual_scaling   = sqrt_rho1 / (1 - alpha);
-            alpha_sq_norm      = alpha / sq_norm;
-        }
+        const CorrectorScalars cs = correctorScalars(sq_norm, rho);
+        const double sqrt_rho1 = cs.sqrt_rho1, alpha_sq_norm = cs.alpha_sq_norm, residual_scaling = cs.residual_scaling;
         for (size_t i = 0; i < jacobians_.size(); i++) {
             const int nc = block_sizes[i];
             for (int c = 0; c < nc; c++) {

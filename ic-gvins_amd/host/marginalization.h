@@ -2,6 +2,7 @@
 // M2, and M3 through marg_m3.h) and the linearized prior as a cost function (M4).  marginalization.cc holds the bookkeeping, the dense path
 // and the prior; marginalization_structured.cc the landmark-eliminated path and the block form of the host factors.
 #pragma once
+#include <cmath>
 #include <memory>
 #include <string>
 #include <unordered_map>
@@ -15,6 +16,27 @@
 namespace icg {
 
 using std::vector;
+
+// The scalar part of the Ceres corrector (residual_block_info.h:59-75) from a loss's rho at sq_norm: a Jacobian entry becomes
+// sqrt_rho1 * (j - alpha_sq_norm * r[k] * rtj), a residual r * residual_scaling.  One function for ResidualBlockInfo::Evaluate and for a
+// solver that has the correction applied where the factor was evaluated.
+struct CorrectorScalars {
+    double sqrt_rho1, alpha_sq_norm, residual_scaling;
+};
+inline CorrectorScalars correctorScalars(double sq_norm, const double rho[3]) {
+    CorrectorScalars c;
+    c.sqrt_rho1 = std::sqrt(rho[1]);
+    if ((sq_norm == 0.0) || (rho[2] <= 0.0)) {
+        c.residual_scaling = c.sqrt_rho1;
+        c.alpha_sq_norm    = 0.0;
+    } else {
+        const double D     = 1.0 + 2.0 * sq_norm * rho[2] / rho[1];
+        const double alpha = 1.0 - std::sqrt(D);
+        c.residual_scaling = c.sqrt_rho1 / (1 - alpha);
+        c.alpha_sq_norm    = alpha / sq_norm;
+    }
+    return c;
+}
 
 class ResidualBlockInfo {
 public:

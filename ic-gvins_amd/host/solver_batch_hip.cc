@@ -22,6 +22,7 @@
 #pragma weak icg_reproj_host_parts_build_prior
 #pragma weak icg_reproj_host_parts_build_preint
 #pragma weak icg_reproj_host_parts_build_preint_odo
+#pragma weak icg_reproj_host_parts_build_nav
 
 namespace icg {
 
@@ -33,6 +34,11 @@ const char *WindowSolverBatch::devicePreintegrationMissing() {
 const char *WindowSolverBatch::devicePreintegrationOdoMissing() {
     if (!PreintegrationOdoSet::available()) return PreintegrationOdoSet::missingEntry();
     return &icg_reproj_host_parts_build_preint_odo == nullptr ? "icg_reproj_host_parts_build_preint_odo" : nullptr;
+}
+
+const char *WindowSolverBatch::deviceNavFactorsMissing() {
+    if (!NavFactorSet::available()) return NavFactorSet::missingEntry();
+    return &icg_reproj_host_parts_build_nav == nullptr ? "icg_reproj_host_parts_build_nav" : nullptr;
 }
 
 bool WindowSolverBatch::devicePreintegrationAvailable() { return devicePreintegrationMissing() == nullptr; }
@@ -129,7 +135,7 @@ bool WindowSolverBatch::layout() {
         W.host_blocks.clear(), W.host_cols.clear();
         W.resident_of_residual.assign(W.problem.residuals.size(), {}), W.resident_of_block.clear();
         for (std::vector<int32_t> &c : W.resident_cols) c.clear();
-        int count[kFamilies] = {0, 0, 0}; // (the window's own: the set indices follow once all windows are laid out)
+        int count[kFamilies] = {0, 0, 0, 0}; // (the window's own: the set indices follow once all windows are laid out)
         std::vector<int> cols;
         for (size_t id = 0; id < W.problem.residuals.size(); id++) {
             const solver_detail::Residual &R = W.problem.residuals[id];
@@ -154,6 +160,11 @@ bool WindowSolverBatch::layout() {
             // the odometer variants behind the same switch: their own resident set (19 residuals, a 19 x 34 Jacobian)
             const PreintegrationOdoFactor *of = device_preint_ && !R.loss && !pf ? dynamic_cast<const PreintegrationOdoFactor *>(R.cost.get()) : nullptr;
             if (of && of->preintegration().ready() && R.blocks.size() == 4) res = {kPreintOdo, count[kPreintOdo]++};
+            // device navigation factors: one parameter block of the factor's own width; a loss is allowed (corrected where the factor is evaluated)
+            const NavFactor *nf = device_nav_ && res.family == kNone ? dynamic_cast<const NavFactor *>(R.cost.get()) : nullptr;
+            if (nf && R.blocks.size() == 1 && R.cost->parameter_block_sizes().size() == 1 && R.cost->parameter_block_sizes()[0] == nf->navWidth() &&
+                R.cost->num_residuals() == nf->navResiduals())
+                res = {kNav, count[kNav]++};
             solver_detail::hostBlockColumns(W.problem, R, cols);
             if (cols.empty()) continue;
             W.resident_of_block.push_back(res);
@@ -163,7 +174,7 @@ bool WindowSolverBatch::layout() {
             for (size_t a = 0; res.family != kNone && a < R.blocks.size(); a++) {
                 const solver_detail::Block &A = W.problem.blocks[(size_t) W.problem.block_of.at(R.blocks[a])];
                 if (A.column < 0) continue;
-                const int first = res.family == kPrior ? v->index[a] : res.family == kPreint ? preint_first[a] : preint_odo_first[a];
+                const int first = res.family == kPrior ? v->index[a] : res.family == kPreint ? preint_first[a] : res.family == kPreintOdo ? preint_odo_first[a] : 0;
                 for (int x = 0; x < A.local; x++) W.resident_cols[res.family].push_back(first + x);
             }
             W.host_blocks.push_back({(int) id, R.cost->num_residuals(), (int) cols.size(), 0, 0, 0});
@@ -191,10 +202,12 @@ bool WindowSolverBatch::layout() {
         prior_views_.clear(), prior_where_.clear(), hp_prior_cols_.clear();
         preint_list_.clear(), preint_where_.clear(), hp_preint_cols_.clear();
         preint_odo_list_.clear(), preint_odo_where_.clear(), hp_preint_odo_cols_.clear();
+        nav_list_.clear(), nav_where_.clear(), hp_nav_cols_.clear();
         hp_prior_of_.assign(hp_nr_.size(), -1), hp_preint_of_.assign(hp_nr_.size(), -1), hp_preint_odo_of_.assign(hp_nr_.size(), -1);
+        hp_nav_of_.assign(hp_nr_.size(), -1);
         for (size_t w = 0; w < windows_.size(); w++) {
             Window &W                  = windows_[w];
-            const int base[kFamilies] = {(int) prior_views_.size(), (int) preint_list_.size(), (int) preint_odo_list_.size()};
+            const int base[kFamilies] = {(int) prior_views_.size(), (int) preint_list_.size(), (int) preint_odo_list_.size(), (int) nav_list_.size()};
             for (size_t id = 0; id < W.resident_of_residual.size(); id++) {
                 Window::Resident &res = W.resident_of_residual[id];
                 if (res.family == kNone) continue;
@@ -204,18 +217,21 @@ bool WindowSolverBatch::layout() {
                     prior_views_.push_back(dynamic_cast<const MargPriorSource *>(cost)->margPriorView()), prior_where_.push_back({(int) w, (int) id});
                 else if (res.family == kPreint)
                     preint_list_.push_back(&static_cast<const PreintegrationFactor *>(cost)->preintegration()), preint_where_.push_back({(int) w, (int) id});
-                else
+                else if (res.family == kPreintOdo)
                     preint_odo_list_.push_back(&static_cast<const PreintegrationOdoFactor *>(cost)->preintegration()), preint_odo_where_.push_back({(int) w, (int) id});
+                else
+                    nav_list_.push_back(dynamic_cast<const NavFactor *>(cost)), nav_where_.push_back({(int) w, (int) id});
             }
             for (size_t k = 0; k < W.resident_of_block.size(); k++) {
                 Window::Resident &res = W.resident_of_block[k];
                 if (res.family == kNone) continue;
-                std::vector<int32_t> &of = res.family == kPrior ? hp_prior_of_ : res.family == kPreint ? hp_preint_of_ : hp_preint_odo_of_;
+                std::vector<int32_t> &of = res.family == kPrior ? hp_prior_of_ : res.family == kPreint ? hp_preint_of_ : res.family == kPreintOdo ? hp_preint_odo_of_ : hp_nav_of_;
                 of[(size_t) W.blk_begin + k] = (res.index += base[res.family]);
             }
             hp_prior_cols_.insert(hp_prior_cols_.end(), W.resident_cols[kPrior].begin(), W.resident_cols[kPrior].end());
             hp_preint_cols_.insert(hp_preint_cols_.end(), W.resident_cols[kPreint].begin(), W.resident_cols[kPreint].end());
             hp_preint_odo_cols_.insert(hp_preint_odo_cols_.end(), W.resident_cols[kPreintOdo].begin(), W.resident_cols[kPreintOdo].end());
+            hp_nav_cols_.insert(hp_nav_cols_.end(), W.resident_cols[kNav].begin(), W.resident_cols[kNav].end());
         }
     }
     return P_ > 0;
@@ -278,12 +294,17 @@ struct WindowSolverBatch::Run {
     DeviceSolve dev;
     DeviceParts hp;
     // per family of resident residuals: on for this solve (its switch is set and its set has members); r . r of every member at the last evaluated point
-    bool on[kFamilies] = {false, false, false};
-    std::vector<double> sq[kFamilies];
+    bool on[kFamilies] = {false, false, false, false};
+    std::vector<double> sq[kFamilies]; // (a navigation factor with a loss: rho[0] of its r . r, what its place in the host cost takes)
+    // navigation factors: the members that carry a loss and, at a linearization, their three corrector scalars
+    std::vector<uint8_t> nav_robust;
+    std::vector<const ceres::LossFunction *> nav_loss;
+    std::vector<double> nav_corr;
+    bool any_nav_robust = false;
     std::vector<std::vector<double>> res_cost; // deferred(): the cost of every residual of every window as the pool recorded it (a resident one's comes from sq)
     std::vector<uint8_t> gathered;             // the windows whose prior Jacobian was gathered on the device in this solve
     std::string resident_err;                  // what the evaluation of a family failed with (side thread: error_ takes it after the join)
-    bool deferred() const { return on[kPrior] || on[kPreint] || on[kPreintOdo]; } // a device value takes a residual's place in the host cost: the pool records per residual
+    bool deferred() const { return on[kPrior] || on[kPreint] || on[kPreintOdo] || on[kNav]; } // a device value takes a residual's place in the host cost: the pool records per residual
     bool first = true;                                        // no window has its initial cost yet
     bool all_done = false, any_step = false, any_trial = false; // what solve() decides on after a phase
     BatchClock clk;
@@ -313,6 +334,9 @@ bool WindowSolverBatch::resolvePath(ReducedPath *path) {
     if (device_preint_ && !devicePreintegrationAvailable()) return refuse(std::string(devicePreintegrationMissing()) + " is not in this build");
     if (device_preint_ && !device_host_part_)
         return refuse("setDevicePreintegration(true) needs setDeviceHostPart(true): the resident factors are read where the host parts are built");
+    if (device_nav_ && !device_host_part_)
+        return refuse("setDeviceNavFactors(true) needs setDeviceHostPart(true): the resident factors are read where the host parts are built");
+    if (device_nav_ && deviceNavFactorsMissing()) return refuse(std::string(deviceNavFactorsMissing()) + " is not in this build");
     *path = device_host_part_ ? ReducedPath::DeviceSolveDeviceParts : device_reduced_ ? ReducedPath::DeviceSolve : ReducedPath::HostSolve;
     return true;
 }
@@ -358,6 +382,18 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
         if (!preint_odo_set_.set(factors_.ctx(), preint_odo_list_, &error_)) return false;
         R.on[kPreintOdo] = true;
         R.sq[kPreintOdo].assign(preint_odo_list_.size(), 0.0);
+    }
+    if (device_nav_ && !nav_list_.empty()) {
+        // the navigation factors' kinds and constants become resident once per solve; the members with a loss are marked for the corrector
+        if (!nav_set_.set(factors_.ctx(), nav_list_, &error_)) return false;
+        R.on[kNav] = true;
+        const size_t n = nav_list_.size();
+        R.sq[kNav].assign(n, 0.0), R.nav_robust.assign(n, 0), R.nav_loss.assign(n, nullptr), R.nav_corr.assign(3 * n, 0.0);
+        for (size_t k = 0; k < n; k++) {
+            R.nav_loss[k]   = windows_[(size_t) nav_where_[k].first].problem.residuals[(size_t) nav_where_[k].second].loss.get();
+            R.nav_robust[k] = R.nav_loss[k] ? 1 : 0;
+            R.any_nav_robust |= R.nav_loss[k] != nullptr;
+        }
     }
     if (R.deferred()) {
         R.res_cost.resize(NW);
@@ -498,6 +534,7 @@ bool WindowSolverBatch::hostHalfOfWindow(Run &R, size_t w) {
                 if (has)
                     H.jac_off[(size_t) W.blk_begin + next] = family == kPreint      ? ICG_HP_JAC_FROM_PREINT
                                                              : family == kPreintOdo ? ICG_HP_JAC_FROM_PREINT_ODO
+                                                             : family == kNav       ? ICG_HP_JAC_FROM_NAV
                                                              : R.gathered[w]        ? -1
                                                                                     : ICG_HP_JAC_FROM_PRIOR,
                                                     next++;
@@ -532,6 +569,7 @@ void WindowSolverBatch::packResident(const Run &R) {
     for (size_t k = 0; R.on[kPrior] && k < prior_where_.size(); k++) prior_set_.pack(k, blocks(prior_where_[k]));
     for (size_t k = 0; R.on[kPreint] && k < preint_where_.size(); k++) preint_set_.pack(k, blocks(preint_where_[k]));
     for (size_t k = 0; R.on[kPreintOdo] && k < preint_odo_where_.size(); k++) preint_odo_set_.pack(k, blocks(preint_odo_where_[k]));
+    for (size_t k = 0; R.on[kNav] && k < nav_where_.size(); k++) nav_set_.pack(k, blocks(nav_where_[k])[0]);
 }
 
 // the resident evaluation of a phase (side thread), one squared norm per member: the priors, then, unless that failed, the preintegration factors,
@@ -539,26 +577,45 @@ void WindowSolverBatch::packResident(const Run &R) {
 bool WindowSolverBatch::evaluateResident(Run &R, bool want_jac) {
     if (R.on[kPrior] && !prior_set_.evaluateResident(R.sq[kPrior].data(), &R.resident_err)) return false;
     if (R.on[kPreint] && !preint_set_.evaluateResident(want_jac, R.sq[kPreint].data(), &R.resident_err)) return false;
-    return !R.on[kPreintOdo] || preint_odo_set_.evaluateResident(want_jac, R.sq[kPreintOdo].data(), &R.resident_err);
+    if (R.on[kPreintOdo] && !preint_odo_set_.evaluateResident(want_jac, R.sq[kPreintOdo].data(), &R.resident_err)) return false;
+    if (!R.on[kNav]) return true;
+    // the navigation factors last.  A member with a loss: rho on the host from its squared norm; rho[0] takes its place in the cost, and at a
+    // linearization the corrector's scalars go up for one correction of what the evaluation kept
+    std::vector<double> &sq = R.sq[kNav];
+    if (!nav_set_.evaluateResident(want_jac, sq.data(), &R.resident_err)) return false;
+    for (size_t k = 0; R.any_nav_robust && k < sq.size(); k++) {
+        if (!R.nav_loss[k]) continue;
+        double rho[3];
+        R.nav_loss[k]->Evaluate(sq[k], rho);
+        if (want_jac) {
+            const CorrectorScalars cs = correctorScalars(sq[k], rho);
+            R.nav_corr[3 * k] = cs.sqrt_rho1, R.nav_corr[3 * k + 1] = cs.alpha_sq_norm, R.nav_corr[3 * k + 2] = cs.residual_scaling;
+        }
+        sq[k] = rho[0];
+    }
+    return !(want_jac && R.any_nav_robust) || nav_set_.correct(R.nav_robust.data(), R.nav_corr.data(), &R.resident_err);
 }
 
 // The host-part call of a linearization, by the narrowest entry that serves the families that are on (a C ABI without the wider ones keeps working with the
 // narrower switches).  The resident blocks take their residuals where they are, and their Jacobians at every rebuild (factors) or a window's first (priors).
 bool WindowSolverBatch::buildHostParts(Run &R) {
     Run::DeviceParts &H     = R.hp;
-    const bool prior = R.on[kPrior], preint = R.on[kPreint], odo = R.on[kPreintOdo];
+    const bool prior = R.on[kPrior], preint = R.on[kPreint], odo = R.on[kPreintOdo], nav = R.on[kNav];
     const int32_t *prior_of = prior ? hp_prior_of_.data() : nullptr, *prior_cols = prior ? hp_prior_cols_.data() : nullptr;
     const int32_t *preint_of = preint ? hp_preint_of_.data() : nullptr, *preint_cols = preint ? hp_preint_cols_.data() : nullptr;
     auto call               = [&](auto entry, auto... resident) { // (every entry takes the narrowest one's arguments first)
         return entry(factors_.ctx(), R.P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(), H.jac_off.data(),
                      H.J.data(), H.r.data(), H.s.data(), H.diag.data(), nullptr, resident...);
     };
-    const int rc = odo      ? call(icg_reproj_host_parts_build_preint_odo, prior_of, prior_cols, preint_of, preint_cols, hp_preint_odo_of_.data(), hp_preint_odo_cols_.data())
+    const int32_t *odo_of = odo ? hp_preint_odo_of_.data() : nullptr, *odo_cols = odo ? hp_preint_odo_cols_.data() : nullptr;
+    const int rc = nav      ? call(icg_reproj_host_parts_build_nav, prior_of, prior_cols, preint_of, preint_cols, odo_of, odo_cols, hp_nav_of_.data(), hp_nav_cols_.data())
+                   : odo    ? call(icg_reproj_host_parts_build_preint_odo, prior_of, prior_cols, preint_of, preint_cols, hp_preint_odo_of_.data(), hp_preint_odo_cols_.data())
                    : preint ? call(icg_reproj_host_parts_build_preint, prior_of, prior_cols, preint_of, preint_cols)
                    : prior  ? call(icg_reproj_host_parts_build_prior, prior_of, prior_cols)
                             : call(icg_reproj_host_parts_build);
     if (rc != ICG_OK)
-        return fail(odo      ? "icg_reproj_host_parts_build_preint_odo"
+        return fail(nav      ? "icg_reproj_host_parts_build_nav"
+                    : odo    ? "icg_reproj_host_parts_build_preint_odo"
                     : preint ? "icg_reproj_host_parts_build_preint"
                     : prior  ? "icg_reproj_host_parts_build_prior"
                              : "icg_reproj_host_parts_build");

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "host_pool.h"
+#include "nav_factor_set.h"
 #include "preintegration_odo.h"
 #include "solver_hip.h"
 #include "window_factors.h"
@@ -105,14 +106,29 @@ public:
     // is missing).  The number of odometer factors of the last layout that joined their resident set:
     int odometerPreintegrationsOnDevice() const { return (int) preint_odo_list_.size(); }
     static const char *devicePreintegrationOdoMissing(); // the first entry the build lacks for the odometer factors, nullptr when none
+    // With the device host part: the navigation factors of every window (nav_factors.h: GnssFactor, ImuErrorFactor, ImuPosePriorFactor,
+    // ImuMixPriorFactor, in both widths) are RESIDENT on the device for the solve (NavFactorSet: kinds and constants go up once per solve())
+    // and evaluated there at every linearization (with Jacobians) and every trial point (residual only), last of the resident families.  A
+    // residual block joins the set when its cost is a NavFactor with exactly one parameter block of the factor's width; a loss function is
+    // allowed: at a linearization rho is evaluated on the host from the returned squared norm (no sqrt on the device), the three corrector
+    // scalars of the members with a loss go up in one NavFactorSet::correct call, and the host-part kernel reads what
+    // ResidualBlockInfo::Evaluate would hold.  0.5 rho[0] (0.5 times the squared norm without a loss) takes the factor's place in the window's
+    // host cost, summed in residual order: states, inverse depths and summaries are the host's bit for bit.  Independent of setDevicePrior
+    // and setDevicePreintegration.  Off by default; needs setDeviceHostPart(true) (solve() fails otherwise) and the C entries, referenced
+    // weakly like the ones above (solve() names the first that is missing).
+    void setDeviceNavFactors(bool on) { device_nav_ = on; }
+    bool deviceNavFactors() const { return device_nav_; }
+    static const char *deviceNavFactorsMissing();                       // the first entry the build lacks for it, nullptr when available
+    int navFactorsOnDevice() const { return (int) nav_list_.size(); } // factors of the last layout that joined the resident set
     bool solve(const Options &options, std::vector<Summary> *summaries);
     // removeReprojectionFactorsByChi2 (ic_gvins.cc:1269-1297) for every window; returns the number removed per window
     std::vector<int> removeReprojectionFactorsByChi2(double chi2);
     const std::string &error() const { return error_; }
 
 private:
-    // the families of residuals that may be resident on the device for a solve (setDevicePrior, setDevicePreintegration), in the order they are evaluated
-    enum Family { kNone = -1, kPrior = 0, kPreint = 1, kPreintOdo = 2, kFamilies = 3 };
+    // the families of residuals that may be resident on the device for a solve (setDevicePrior, setDevicePreintegration, setDeviceNavFactors), in the order they
+    // are evaluated
+    enum Family { kNone = -1, kPrior = 0, kPreint = 1, kPreintOdo = 2, kNav = 3, kFamilies = 4 };
     // a window beside its record in factors_: the host-evaluated part of its problem and its state across the steps of a solve
     struct Window {
         solver_detail::Problem problem{"WindowSolverBatch"};
@@ -129,7 +145,7 @@ private:
         int blk_begin{0};
         // resident residuals (layout()): per residual and per block of host_blocks the family it is resident in on the device (kNone: evaluated on
         // the pool; a resident residual whose blocks are all constant has a cost but no host block) and its index in that family's set; per family
-        // the columns of the members' source matrices (a prior's J0, a factor's 15 x 32 or 19 x 34 Jacobian) its blocks take, block after block
+        // the columns of the members' source matrices (a prior's J0, a factor's 15 x 32 or 19 x 34 Jacobian, a navigation factor's nr x width one) its blocks take, block after block
         struct Resident { int family{kNone}, index{-1}; };
         std::vector<Resident> resident_of_residual, resident_of_block;
         std::vector<int32_t> resident_cols[kFamilies];
@@ -148,7 +164,8 @@ private:
     // where the paths differ: the host half of a window's linearization, and the reduced solves
     bool hostHalfOfWindow(Run &R, size_t w);
     // resident residuals: the evaluation point of every member of the families that are on (driving thread), their evaluation in a phase (side
-    // thread: priors, then preintegration factors; Jacobians at a linearization only), the host-part call of the narrowest entry that serves
+    // thread: priors, then preintegration factors, then navigation factors with the correction of the robustified ones; Jacobians at a
+    // linearization only), the host-part call of the narrowest entry that serves
     // them, and a window's host cost once the device values are there
     void packResident(const Run &R);
     bool evaluateResident(Run &R, bool want_jac);
@@ -167,20 +184,22 @@ private:
     std::vector<int32_t> col_pose_, col_ext_, col_td_;
     int P_{0};
     bool finalized_{false};
-    bool device_reduced_{false}, device_host_part_{false}, device_prior_{false}, device_preint_{false};
+    bool device_reduced_{false}, device_host_part_{false}, device_prior_{false}, device_preint_{false}, device_nav_{false};
     // device host part (layout()): the block list of all windows as icg_reproj_host_parts_build takes it, and the sizes of a call's J and r
     std::vector<int32_t> hp_blk_off_, hp_nr_, hp_nf_, hp_cols_;
     size_t hp_J_total_{0}, hp_r_total_{0};
     // resident residuals (layout()): per block of that list the prior / the factor of the resident sets it is (-1: none) and the resident blocks' columns
     // of J0 / of the 15 x 32 Jacobian; the sets, their members (priors in window order, factors in window and residual order) and where each is
-    std::vector<int32_t> hp_prior_of_, hp_prior_cols_, hp_preint_of_, hp_preint_cols_, hp_preint_odo_of_, hp_preint_odo_cols_;
+    std::vector<int32_t> hp_prior_of_, hp_prior_cols_, hp_preint_of_, hp_preint_cols_, hp_preint_odo_of_, hp_preint_odo_cols_, hp_nav_of_, hp_nav_cols_;
     std::vector<MargPriorView> prior_views_;
     std::vector<const Preintegration *> preint_list_;
     std::vector<const PreintegrationOdo *> preint_odo_list_;
-    std::vector<std::pair<int, int>> prior_where_, preint_where_, preint_odo_where_; // (window, residual)
+    std::vector<const NavFactor *> nav_list_;
+    std::vector<std::pair<int, int>> prior_where_, preint_where_, preint_odo_where_, nav_where_; // (window, residual)
     MarginalizationPriorSet prior_set_;
     PreintegrationSet preint_set_;
     PreintegrationOdoSet preint_odo_set_;
+    NavFactorSet nav_set_;
     std::string error_;
 };
 

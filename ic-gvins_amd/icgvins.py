@@ -33,6 +33,7 @@ EXPORTS = [
     "icg_preint_set", "icg_preint_evaluate_resident", "icg_preint_fetch_resident", "icg_reproj_host_parts_build_preint",
     "icg_preint_odo_batch", "icg_preint_odo_evaluate_batch",
     "icg_preint_odo_set", "icg_preint_odo_evaluate_resident", "icg_preint_odo_fetch_resident", "icg_reproj_host_parts_build_preint_odo",
+    "icg_nav_set", "icg_nav_evaluate_resident", "icg_nav_correct_resident", "icg_nav_fetch_resident", "icg_reproj_host_parts_build_nav",
 ]
 
 
@@ -43,7 +44,10 @@ HOST_PART_MAX_NR = 1024  # ICG_HOST_PART_MAX_NR
 HP_JAC_FROM_PRIOR = -2  # ICG_HP_JAC_FROM_PRIOR
 HP_JAC_FROM_PREINT = -3  # ICG_HP_JAC_FROM_PREINT
 HP_JAC_FROM_PREINT_ODO = -4  # ICG_HP_JAC_FROM_PREINT_ODO
+HP_JAC_FROM_NAV = -5  # ICG_HP_JAC_FROM_NAV
 PREINT_SET_MAX = 65535 * 16  # ICG_PREINT_SET_MAX
+NAV_SET_MAX = 65535  # ICG_NAV_SET_MAX
+NAV_SHAPES = {0: (3, 7), 1: (6, 9), 2: (6, 7), 3: (9, 9), 4: (7, 10), 5: (10, 10)}  # residuals x block width by kind of navigation factor
 
 
 class IcgError(RuntimeError):
@@ -531,6 +535,13 @@ class Context:
                                                                _p(r), _p(host_s), _p(host_diag), _p(part_out), _p(prior_of), _p(prior_cols), _p(preint_of),
                                                                _p(preint_cols), _p(preint_odo_of), _p(preint_odo_cols))
 
+    def reproj_host_parts_build_nav_raw(self, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, prior_of=None, prior_cols=None,
+                                        preint_of=None, preint_cols=None, preint_odo_of=None, preint_odo_cols=None, nav_of=None, nav_cols=None):
+        """icg_reproj_host_parts_build_nav on the caller's arrays (None = NULL; the outputs are written in place) -> the return code"""
+        return self.lib.icg_reproj_host_parts_build_nav(self.h, int(P), _p(Pw), _p(rebuild), _p(blk_off), _p(nr), _p(nf), _p(cols), _p(jac_off), _p(J), _p(r),
+                                                        _p(host_s), _p(host_diag), _p(part_out), _p(prior_of), _p(prior_cols), _p(preint_of), _p(preint_cols),
+                                                        _p(preint_odo_of), _p(preint_odo_cols), _p(nav_of), _p(nav_cols))
+
     def reproj_host_parts_build_prior(self, P, Pw, windows, rebuild=None, host_s=None, host_diag=None):
         """icg_reproj_host_parts_build_prior.  windows: per window a list of blocks; an ordinary block is (J nr x nf, r, cols, keep) as in
         reproj_host_parts_build, a prior block is ("prior", p, prior_cols, cols, how): prior p of the resident set (marg_prior_set), how =
@@ -695,6 +706,56 @@ class Context:
         res = np.zeros((n, 19))
         J = np.zeros((n, 646)) if want_jac else None
         self._ck(self.lib.icg_preint_odo_fetch_resident(self.h, _p(res), _p(J)), "icg_preint_odo_fetch_resident")
+        return res, J
+
+    # ---- navigation factors (host/nav_factors.h), resident
+    def nav_set(self, kind, aux_off, aux):
+        """icg_nav_set: len(kind) navigation factors become resident (kind 0..5; constants aux[aux_off[f]:aux_off[f + 1]])"""
+        kind, aux_off, aux = i32(kind).reshape(-1), i32(aux_off).reshape(-1), f64(aux).reshape(-1)
+        n = len(kind)
+        if len(aux_off) != n + 1:
+            raise IcgError(f"nav_set: {len(aux_off)} offsets for {n} members (n + 1 are needed)")
+        if len(aux) == 0:
+            aux = np.zeros(1)  # (a set of error factors reads no constant; the entry still wants a pointer)
+        self._nav_kind = None
+        self._ck(self.lib.icg_nav_set(self.h, n, _p(kind), _p(aux_off), _p(aux)), "icg_nav_set")
+        self._nav_kind = kind.copy()
+
+    def _nav_totals(self):
+        kind = getattr(self, "_nav_kind", None)
+        if kind is None:
+            return 0, 1, 1
+        return len(kind), sum(NAV_SHAPES[int(k)][0] for k in kind), sum(NAV_SHAPES[int(k)][0] * NAV_SHAPES[int(k)][1] for k in kind)
+
+    def nav_evaluate_resident(self, points, point_off, want_jac=True):
+        """icg_nav_evaluate_resident: member f is evaluated at points[point_off[f]:][:width]; residuals (and Jacobians) stay on the device
+        -> sq_norm (r . r per member)"""
+        points, point_off = f64(points).reshape(-1), i32(point_off).reshape(-1)
+        n = self._nav_totals()[0]
+        if n:
+            if len(point_off) != n:
+                raise IcgError(f"nav_evaluate_resident: {len(point_off)} offsets, the resident set has {n} members")
+            for f in range(n):
+                if point_off[f] >= 0 and point_off[f] + NAV_SHAPES[int(self._nav_kind[f])][1] > len(points):
+                    raise IcgError(f"nav_evaluate_resident: member {f} reads past the {len(points)} values of points")
+        sq = np.zeros(max(n, 1))
+        self._ck(self.lib.icg_nav_evaluate_resident(self.h, _p(points), _p(point_off), 1 if want_jac else 0, _p(sq)), "icg_nav_evaluate_resident")
+        return sq[:n]
+
+    def nav_correct_resident(self, robust, corr):
+        """icg_nav_correct_resident: the corrector of the members with robust[f] != 0; corr n x 3 = sqrt_rho1, alpha_sq_norm, residual_scaling"""
+        n = self._nav_totals()[0]
+        robust, corr = np.ascontiguousarray(robust, np.uint8).reshape(-1), f64(corr).reshape(-1, 3)
+        if n and (len(robust) != n or corr.shape[0] != n):
+            raise IcgError(f"nav_correct_resident: {len(robust)} marks and {corr.shape[0]} scalar triples, the resident set has {n} members")
+        self._ck(self.lib.icg_nav_correct_resident(self.h, _p(robust), _p(corr)), "icg_nav_correct_resident")
+
+    def nav_fetch_resident(self, want_jac=True):
+        """icg_nav_fetch_resident -> (residuals, jacobians or None) of the last resident evaluation, flat, member after member"""
+        _, nr, nj = self._nav_totals()
+        res = np.zeros(nr)
+        J = np.zeros(nj) if want_jac else None
+        self._ck(self.lib.icg_nav_fetch_resident(self.h, _p(res), _p(J)), "icg_nav_fetch_resident")
         return res, J
 
     # ---- M4

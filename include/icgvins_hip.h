@@ -355,6 +355,27 @@ int icg_reproj_host_parts_build_preint_odo(icg_ctx *ctx, int P, const int32_t *P
                                            double *host_s, double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols,
                                            const int32_t *preint_of, const int32_t *preint_cols, const int32_t *preint_odo_of,
                                            const int32_t *preint_odo_cols);
+/* icg_reproj_host_parts_build_preint_odo with blocks that are members of the resident NAV set (icg_nav_set) at the point of its last
+ * icg_nav_evaluate_resident, as a fourth family: neither such a member's residual nor its Jacobian crosses the link.  The arguments of
+ * icg_reproj_host_parts_build_preint_odo, plus:
+ *   nav_of    per block of the call: >= 0 = the block is member nav_of[b] of the resident nav set, < 0 = it is not
+ *   nav_cols  for those blocks, in block order (those of windows that are not rebuilt included), nf[b] indices into the member's block
+ *             width (7, 9 or 10); index 6 of a 7-wide member (the +0.0 seventh pose column) is refused
+ * Such a block of a rebuilt window has nr[b] == the member's number of residuals; the row stride of its source is the member's width.
+ * jac_off[b] == ICG_HP_JAC_FROM_NAV gathers Jd[k][y] = Jm[k][nav_cols[y]] on the device, -1 keeps the previous gather, an offset >= 0
+ * uploads.  The four entries above are this one with NULL for the arguments they do not have; the accumulation kernel is the same.
+ * ICG_ERR_INVALID beyond the cases there (the message names the window and the block), for a block of a rebuilt window: nav_of[b] outside
+ * the resident set, nr[b] != the member's, a nav_cols entry outside the width or 6 for a 7-wide member, no nav set resident or not evaluated
+ * since it was set (for the gather: not evaluated with want_jac; and, once a correction of the set has marked a member, not corrected since
+ * that evaluation), such blocks without nav_cols, a block that is also a member of another family, ICG_HP_JAC_FROM_NAV for a block with
+ * nav_of[b] < 0 (without nav_of the value is refused as any unknown jac_off).  ICG_ERR_CAPACITY: more than 65535 resident blocks of the four families in the rebuilt windows.  After
+ * an error nothing was launched and no output was touched. */
+#define ICG_HP_JAC_FROM_NAV (-5)
+int icg_reproj_host_parts_build_nav(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
+                                    const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s,
+                                    double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols, const int32_t *preint_of,
+                                    const int32_t *preint_cols, const int32_t *preint_odo_of, const int32_t *preint_odo_cols, const int32_t *nav_of,
+                                    const int32_t *nav_cols);
 /* problem setup: pre-sizes the resident window systems and the staging memory for reduced systems of size P (a hint; optional) */
 int icg_reproj_reserve_windows(icg_ctx *ctx, int P);
 int icg_reproj_backsub_windows(icg_ctx *ctx, int P, const double *delta_c, double *delta_l, double *lm_terms);
@@ -497,6 +518,37 @@ int icg_preint_odo_evaluate_resident(icg_ctx *ctx, const double *points, const d
  * jacobians 646 per factor = 19x7 | 19x10 | 19x7 | 19x10 (NULL: not fetched).  For tests.  ICG_ERR_INVALID: no resident set, NULL residuals,
  * nothing evaluated since icg_preint_odo_set, or Jacobians asked for after an evaluation with want_jac == 0. */
 int icg_preint_odo_fetch_resident(icg_ctx *ctx, double *residuals, double *jacobians);
+
+/* ---- The small navigation factors (host/nav_factors.h), RESIDENT on the device for a whole solve, beside the prior, the 15-state and the
+ * odometer sets (a context may hold one of each; none of these entries touches another set).  Member f has a kind and one parameter block:
+ *   kind 0 GnssFactor          3 x 7    constants blh3, std3, lever3 (9)      kind 3 ImuMixPriorFactor       9 x 9    mix9, std9 (18)
+ *   kind 1 ImuErrorFactor      6 x 9    none                                  kind 4 ImuErrorFactor, odo     7 x 10   none
+ *   kind 2 ImuPosePriorFactor  6 x 7    pose7, std6 (13)                      kind 5 ImuMixPriorFactor, odo  10 x 10  mix10, std10 (20)
+ * icg_nav_set: n members; the constants of member f are aux[aux_off[f] .. aux_off[f + 1]) (aux_off has n + 1 entries; a member may own
+ * more doubles than its kind reads, never fewer).  Replaces the nav set the context held.  ICG_ERR_INVALID (the message names the member
+ * where there is one): n <= 0, a NULL argument, a kind outside 0..5, aux_off[0] < 0 or offsets that are not monotone, fewer constants than
+ * the kind reads.  ICG_ERR_CAPACITY: more than ICG_NAV_SET_MAX members.  After a failed call no nav set is resident. */
+#define ICG_NAV_SET_MAX 65535
+int icg_nav_set(icg_ctx *ctx, int n, const int32_t *kind, const int32_t *aux_off, const double *aux);
+/* Evaluates every member at its parameter block points[point_off[f] ..] (7, 9 or 10 doubles; point_off[f] >= 0).  Kept on the device until
+ * the next evaluation or icg_nav_set: the residuals, concatenated (nr[f] each, member after member), and with want_jac != 0 one row-major
+ * nr x width Jacobian per member, concatenated; every element of it is written by every such evaluation, zeros as the host writes them
+ * (the seventh pose columns are +0.0).  Returned: sq_norm[f] = sum_k r[k]^2, k ascending from +0.0.  The arithmetic is the classes'
+ * Evaluate, operation for operation without contraction: the host's bit patterns.  want_jac == 0 invalidates the kept Jacobians.
+ * ICG_ERR_INVALID without a resident set, with a NULL argument or a negative point_off: nothing is launched. */
+int icg_nav_evaluate_resident(icg_ctx *ctx, const double *points, const int32_t *point_off, int want_jac, double *sq_norm);
+/* The Ceres corrector of the robustified members (ResidualBlockInfo::Evaluate, host/marginalization.cc) applied to what the last evaluation
+ * kept.  robust[f] != 0 marks a member; corr holds 3 doubles per member (read for the marked ones): sqrt_rho1, alpha_sq_norm,
+ * residual_scaling — the host's (host/marginalization.h correctorScalars), no sqrt is taken on the device.  For a marked member, per column c:
+ * rtj = sum_k r[k] J[k][c], k ascending from +0.0; J[k][c] = sqrt_rho1 * (J[k][c] - alpha_sq_norm * r[k] * rtj); then r[k] *= residual_scaling.
+ * Unmarked members keep their bits.  A call that marks a member makes the set one with robustified members until the next icg_nav_set: the
+ * host-part gather (icg_reproj_host_parts_build_nav) then waits for the correction of every evaluation.  Allowed once per evaluation with Jacobians: ICG_ERR_INVALID (nothing launched) for a second call, after a
+ * residual-only evaluation, without a resident set or an evaluation, or with a NULL argument. */
+int icg_nav_correct_resident(icg_ctx *ctx, const uint8_t *robust, const double *corr);
+/* The kept residuals (sum nr) and Jacobians (sum nr x width; NULL: not fetched) of the last evaluation, corrected where a correction ran.
+ * For tests.  ICG_ERR_INVALID: no resident set, NULL residuals, nothing evaluated since icg_nav_set, or Jacobians asked for after an
+ * evaluation with want_jac == 0. */
+int icg_nav_fetch_resident(icg_ctx *ctx, double *residuals, double *jacobians);
 
 /* ---- M4: MarginalizationFactor::Evaluate (factors/marginalization_factor.h:47-101) for the priors of many windows, RESIDENT on the
  * device: a prior is constant between two marginalizations while every LM iteration evaluates it at a new point, so the priors are
