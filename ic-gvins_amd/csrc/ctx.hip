@@ -195,7 +195,7 @@ extern "C" void icg_ctx_destroy(icg_ctx *ctx) {
     for (auto e : ctx->ev_pool) (void) hipEventDestroy(e);
     if (ctx->ev_wait) (void) hipEventDestroy(ctx->ev_wait);
     // the front-end's fixed and lazily allocated buffers and the arena; the back-end's buffers all come from icg_grow
-    void *dev[] = {ctx->d_frames, ctx->d_raw, ctx->d_bgr, ctx->d_lut, ctx->d_histmean, ctx->d_roi_max, ctx->d_cand, ctx->d_cand_cnt, ctx->d_arena};
+    void *dev[] = {ctx->d_frames, ctx->d_raw, ctx->d_bgr, ctx->d_lut, ctx->d_histmean, ctx->d_roi_max, ctx->d_cand, ctx->d_cand_cnt, ctx->d_arena, ctx->d_cams};
     for (void *p : dev)
         if (p) (void) hipFree(p);
     for (void **p : ctx->grown)
@@ -219,6 +219,25 @@ extern "C" int icg_set_camera(icg_ctx *ctx, const icg_camera *cam) {
     if (!ctx || !cam) return ICG_ERR_INVALID;
     ctx->cam     = *cam;
     ctx->has_cam = true;
+    return ICG_OK;
+}
+
+// The camera table of the *_cams entries: one icg_camera per stream of the context, resident on the device.  The table is replaced as a
+// whole (a new allocation; work queued on the stream with the old one is waited for first).
+extern "C" int icg_set_cameras(icg_ctx *ctx, int n_cams, const icg_camera *cams) {
+    if (!ctx) return ICG_ERR_INVALID;
+    if (n_cams <= 0 || !cams) return icg_fail(ctx, ICG_ERR_INVALID, "icg_set_cameras: %d cameras, table %s", n_cams, cams ? "given" : "NULL");
+    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    icg_camera *d = nullptr;
+    ICG_HIP(ctx, hipMalloc((void **) &d, sizeof(icg_camera) * (size_t) n_cams));
+    if (icg_hip_check(ctx, hipMemcpy(d, cams, sizeof(icg_camera) * (size_t) n_cams, hipMemcpyHostToDevice), "copy camera table") ||
+        icg_hip_check(ctx, hipStreamSynchronize(ctx->stream), "icg_set_cameras")) {
+        (void) hipFree(d);
+        return ICG_ERR_HIP;
+    }
+    if (ctx->d_cams) (void) hipFree(ctx->d_cams);
+    ctx->d_cams = d;
+    ctx->cams.assign(cams, cams + n_cams);
     return ICG_OK;
 }
 

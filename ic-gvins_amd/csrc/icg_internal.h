@@ -237,6 +237,10 @@ struct icg_ctx {
 
     icg_camera cam{};
     bool has_cam = false;
+    // camera table (icg_set_cameras): n_cams entries resident on the device, indexed per stream by the *_cams entries; the host copy serves
+    // the argument checks.  d_cams is replaced, never grown in place: a tracker copies what it needs at creation.
+    icg_camera *d_cams = nullptr;
+    std::vector<icg_camera> cams;
 
     // profiling
     bool prof_on = false;
@@ -519,7 +523,8 @@ struct det_roi {
 int icg_preprocess_launch_ind(icg_ctx *ctx, int n, const int32_t *d_slot_ind, const uint8_t *const *images, int stride, int channels, int src_on_device,
                               double *d_hist_mean);
 int icg_lk_launch_segments(icg_ctx *ctx, int n_seg, int seg_cap, const int32_t *d_count, const int32_t *d_prev_slot, const int32_t *d_next_slot,
-                           const float2 *d_prev, const float2 *d_guess, float2 *d_out, uint8_t *d_status, float2 *d_undist);
+                           const float2 *d_prev, const float2 *d_guess, float2 *d_out, uint8_t *d_status, float2 *d_undist,
+                           const icg_camera *d_seg_cams = nullptr); // d_seg_cams: one camera per segment (null: the context's camera)
 int icg_fm_ransac_launch_sets(icg_ctx *ctx, int n_sets, int seg_cap, const int32_t *d_count, const float2 *d_p1, const float2 *d_p2, double thresh,
                               double conf, uint8_t *d_mask);
 int icg_triangulate_launch_segments(icg_ctx *ctx, int n_seg, int seg_cap, const int32_t *d_count, const int32_t *d_T0, const int32_t *d_T1, int tcw_cap,

@@ -955,16 +955,18 @@ __global__ __launch_bounds__(64, LK_WAVES_PER_EU) void k_lk_track_fb(icg_pyr_des
 }
 
 // isOnBorder (tracking.cc:847-849) and ptsDistance (tracking.cc:841-845) on the forward / backward results of k_lk_track_fb, then
-// undistortPoints of the forward result; one thread per point.  bwd_undist holds the backward result on entry and, when the caller asked for
+// undistortPoints of the forward result (Camera::undistortPoints, camera.cc:72-74, of the point's own camera where a table is given); one
+// thread per point.  bwd_undist holds the backward result on entry and, when the caller asked for
 // undistorted points, the undistorted point on exit (the segmented tracker passes its undistorted-point array; the C entry point a scratch
 // array or the caller's).
 __global__ __launch_bounds__(256) void k_lk_finish(int n, const float2 *prev_pts, const float2 *out_pts, float2 *bwd_undist, unsigned char *status,
                                                    int want_undist, int has_cam, icg_camera cam, int img_w, int img_h, int seg_cap,
-                                                   unsigned int seg_magic, const int32_t *seg_count) {
+                                                   unsigned int seg_magic, const int32_t *seg_count, const icg_camera *cams, const int32_t *cam_idx) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    int s = 0;
     if (seg_count) {
-        const int s = icg_div_by_magic(i, seg_magic);
+        s = icg_div_by_magic(i, seg_magic);
         if (i - s * seg_cap >= seg_count[s]) return;
     }
     const float2 p0 = prev_pts[i], fwd = out_pts[i], bwd = bwd_undist[i];
@@ -972,7 +974,14 @@ __global__ __launch_bounds__(256) void k_lk_finish(int n, const float2 *prev_pts
     const double ddx = (double) (bwd.x - p0.x), ddy = (double) (bwd.y - p0.y);
     const double dist = sqrt(ddx * ddx + ddy * ddy);
     status[i] = (unsigned char) ((status[i] && !border && dist < 0.5) ? 1u : 0u);
-    if (want_undist) bwd_undist[i] = has_cam ? cam_undistort(cam, fwd) : fwd;
+    if (!want_undist) return;
+    // camera table (icg_set_cameras): the camera of the point's segment — its stream — in the tracker's launch, of cam_idx[i] in the
+    // unsegmented one; without a table the by-value camera, the code of the single-camera entries as it was
+    if (cams) {
+        const icg_camera c = cams[seg_count ? s : cam_idx[i]];
+        bwd_undist[i]      = cam_undistort(c, fwd);
+    } else
+        bwd_undist[i] = has_cam ? cam_undistort(cam, fwd) : fwd;
 }
 
 // order-preserving compaction indices (what reduceVector keeps, tracking.cc:831-839); single workgroup scan.
@@ -1041,8 +1050,10 @@ extern "C" int icg_lk_track(icg_ctx *ctx, int n, const int32_t *prev_slot, const
 
 // the forward / backward track and its verdict of n points: k_lk_track_fb + k_lk_finish, asynchronous on the context's stream.  seg_count
 // null: one list of n points; otherwise n = n_seg * seg_cap entries in segments (icg_lk_launch_segments).  bwd_undist: see k_lk_finish.
+// cams / cam_idx: k_lk_finish's camera table and per-point index (null: the context's camera by value).
 static void lk_fb_launch(icg_ctx *ctx, int n, int seg_cap, const int32_t *seg_count, bool want_undist, const int32_t *prev_slot, const int32_t *next_slot,
-                         const float2 *prev, const float2 *guess, float2 *out, uint8_t *status, float2 *bwd_undist) {
+                         const float2 *prev, const float2 *guess, float2 *out, uint8_t *status, float2 *bwd_undist, const icg_camera *cams = nullptr,
+                         const int32_t *cam_idx = nullptr) {
     const unsigned int seg_magic = seg_count ? icg_div_magic(seg_cap) : 0u; // (0: divisor 1, and what an unsegmented call passes)
 #if defined(LK_TILE_HIST)
     static std::once_flag hist_once;
@@ -1056,31 +1067,37 @@ static void lk_fb_launch(icg_ctx *ctx, int n, int seg_cap, const int32_t *seg_co
     {
         icg_prof_scope ps(ctx, "lk_finish");
         hipLaunchKernelGGL(k_lk_finish, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, prev, (const float2 *) out, bwd_undist, status,
-                           want_undist ? 1 : 0, ctx->has_cam ? 1 : 0, ctx->cam, ctx->cfg.width, ctx->cfg.height, seg_cap, seg_magic, seg_count);
+                           want_undist ? 1 : 0, ctx->has_cam ? 1 : 0, ctx->cam, ctx->cfg.width, ctx->cfg.height, seg_cap, seg_magic, seg_count, cams,
+                           cam_idx);
     }
 }
 
-extern "C" int icg_lk_track_fb(icg_ctx *ctx, int n, const int32_t *prev_slot, const int32_t *next_slot,
-                               const float *prev_pts, const float *guess_pts, float *out_pts, uint8_t *status,
-                               float *out_undist, int32_t *keep_idx, int32_t *n_keep) {
-    if (!ctx || n < 0) return ICG_ERR_INVALID;
+// icg_lk_track_fb and icg_lk_track_fb_cams: one body; cam_idx null is the single-camera entry
+static int lk_track_fb_entry(icg_ctx *ctx, int n, const int32_t *prev_slot, const int32_t *next_slot, const float *prev_pts, const float *guess_pts,
+                             const int32_t *cam_idx, float *out_pts, uint8_t *status, float *out_undist, int32_t *keep_idx, int32_t *n_keep) {
     if (n == 0) {
         if (n_keep) *n_keep = 0;
         return ICG_OK;
     }
     if (!prev_slot || !next_slot || !prev_pts || !guess_pts || !out_pts || !status) return ICG_ERR_INVALID;
     if ((keep_idx == nullptr) != (n_keep == nullptr)) return ICG_ERR_INVALID;
-    if (out_undist && !ctx->has_cam) return icg_fail(ctx, ICG_ERR_INVALID, "out_undist requested but camera not set");
+    if (!cam_idx && out_undist && !ctx->has_cam) return icg_fail(ctx, ICG_ERR_INVALID, "out_undist requested but camera not set");
+    if (cam_idx) {
+        const int n_cams = (int) ctx->cams.size();
+        for (int i = 0; i < n; i++)
+            if (cam_idx[i] < 0 || cam_idx[i] >= n_cams) return icg_fail(ctx, ICG_ERR_INVALID, "cam_idx[%d] = %d outside the table of %d cameras", i, cam_idx[i], n_cams);
+    }
     if (n > ctx->cfg.max_points) return icg_fail(ctx, ICG_ERR_CAPACITY, "%d points > max_points %d", n, ctx->cfg.max_points);
     int rc = check_slots(ctx, n, prev_slot, next_slot);
     if (rc) return rc;
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     icg_call c(ctx);
-    if ((rc = c.reserve((size_t) n * 104))) return rc;
+    if ((rc = c.reserve((size_t) n * (cam_idx ? 112 : 104)))) return rc;
     const int32_t *d_ps = c.in_zc(prev_slot, (size_t) n);
     const int32_t *d_ns = c.in_zc(next_slot, (size_t) n);
     const float2 *d_pp  = (const float2 *) c.in_zc(prev_pts, 2 * (size_t) n);
     const float2 *d_gs  = (const float2 *) c.in_zc(guess_pts, 2 * (size_t) n);
+    const int32_t *d_ci = cam_idx ? c.in_zc(cam_idx, (size_t) n) : nullptr;
     float2 *d_out       = (float2 *) c.out_zc(out_pts, 2 * (size_t) n);
     unsigned char *d_st = c.out_zc(status, (size_t) n);
     // (the backward results travel from k_lk_track_fb to k_lk_finish in the undistorted-point array, or in device scratch when none was asked for)
@@ -1088,7 +1105,7 @@ extern "C" int icg_lk_track_fb(icg_ctx *ctx, int n, const int32_t *prev_slot, co
     int32_t *d_keep     = keep_idx ? c.out_zc(keep_idx, (size_t) n) : nullptr;
     int32_t *d_nkeep    = keep_idx ? c.out_zc(n_keep, 1) : nullptr;
     ICG_LAUNCH_GUARD(c);
-    lk_fb_launch(ctx, n, 0, nullptr, out_undist != nullptr, d_ps, d_ns, d_pp, d_gs, d_out, d_st, d_und);
+    lk_fb_launch(ctx, n, 0, nullptr, out_undist != nullptr, d_ps, d_ns, d_pp, d_gs, d_out, d_st, d_und, cam_idx ? ctx->d_cams : nullptr, d_ci);
     if (keep_idx) {
         icg_prof_scope ps(ctx, "keep_indices");
         hipLaunchKernelGGL(k_keep_indices, dim3(1), dim3(1024), 0, ctx->stream, n, d_st, d_keep, d_nkeep);
@@ -1097,14 +1114,32 @@ extern "C" int icg_lk_track_fb(icg_ctx *ctx, int n, const int32_t *prev_slot, co
     return c.finish();
 }
 
+extern "C" int icg_lk_track_fb(icg_ctx *ctx, int n, const int32_t *prev_slot, const int32_t *next_slot,
+                               const float *prev_pts, const float *guess_pts, float *out_pts, uint8_t *status,
+                               float *out_undist, int32_t *keep_idx, int32_t *n_keep) {
+    if (!ctx || n < 0) return ICG_ERR_INVALID;
+    return lk_track_fb_entry(ctx, n, prev_slot, next_slot, prev_pts, guess_pts, nullptr, out_pts, status, out_undist, keep_idx, n_keep);
+}
+
+// out_undist[i] under camera cam_idx[i] of the context's table (icg_set_cameras): the reference constructs a Tracking per camera
+// (tracking/tracking.h:51) and undistorts with that camera (tracking.cc:423, 520-524; Camera::undistortPoints, camera.cc:72-74)
+extern "C" int icg_lk_track_fb_cams(icg_ctx *ctx, int n, const int32_t *prev_slot, const int32_t *next_slot, const float *prev_pts,
+                                    const float *guess_pts, const int32_t *cam_idx, float *out_pts, uint8_t *status, float *out_undist,
+                                    int32_t *keep_idx, int32_t *n_keep) {
+    if (!ctx || n < 0) return ICG_ERR_INVALID;
+    if (ctx->cams.empty()) return icg_fail(ctx, ICG_ERR_INVALID, "icg_lk_track_fb_cams: no camera table (icg_set_cameras)");
+    if (!cam_idx) return icg_fail(ctx, ICG_ERR_INVALID, "icg_lk_track_fb_cams: NULL cam_idx");
+    return lk_track_fb_entry(ctx, n, prev_slot, next_slot, prev_pts, guess_pts, cam_idx, out_pts, status, out_undist, keep_idx, n_keep);
+}
+
 // Segmented launch for the device-resident tracker (tracker.hip): every array is device memory laid out as n_seg segments of seg_cap
 // entries, d_count[s] of them valid; asynchronous on the context's stream (the tracker's next stage kernel is stream-ordered behind it).
 int icg_lk_launch_segments(icg_ctx *ctx, int n_seg, int seg_cap, const int32_t *d_count, const int32_t *d_prev_slot, const int32_t *d_next_slot,
-                           const float2 *d_prev, const float2 *d_guess, float2 *d_out, uint8_t *d_status, float2 *d_undist) {
-    if (!ctx->has_cam) return icg_fail(ctx, ICG_ERR_INVALID, "camera not set");
+                           const float2 *d_prev, const float2 *d_guess, float2 *d_out, uint8_t *d_status, float2 *d_undist, const icg_camera *d_seg_cams) {
+    if (!d_seg_cams && !ctx->has_cam) return icg_fail(ctx, ICG_ERR_INVALID, "camera not set");
     if (n_seg < 1 || seg_cap < 1 || (unsigned long long) n_seg * seg_cap * seg_cap >= (1ull << 32)) // (icg_div_magic is exact for entry * seg_cap < 2^32)
         return icg_fail(ctx, ICG_ERR_INVALID, "%d segments of %d entries: the segment decode needs n_seg * seg_cap^2 < 2^32", n_seg, seg_cap);
-    lk_fb_launch(ctx, n_seg * seg_cap, seg_cap, d_count, true, d_prev_slot, d_next_slot, d_prev, d_guess, d_out, d_status, d_undist);
+    lk_fb_launch(ctx, n_seg * seg_cap, seg_cap, d_count, true, d_prev_slot, d_next_slot, d_prev, d_guess, d_out, d_status, d_undist, d_seg_cams);
     ICG_HIP(ctx, hipGetLastError());
     return ICG_OK;
 }

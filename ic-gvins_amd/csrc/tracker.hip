@@ -192,13 +192,28 @@ constexpr bool trk_uses_scratch(int stage) { return stage != 0 && stage != 6; }
 // are just above; but __launch_bounds__(64, 4), amdgpu_waves_per_eu(4) and amdgpu_num_vgpr(128) all leave their remarks as they are: with
 // 33.8 KB of LDS per wave the compiler counts one wave of this kernel per SIMD and sizes the register budget to that
 // (profiles/r12_tracker_stage_kernels.txt).
+// Per-stream cameras (icg_tracker_create_cams): `cams` holds one icg_camera per stream of the group and every instance forms the stream's
+// configuration — G with the camera of cams[s], image size kept — before any stage body runs; the bodies, build_rois, assemble_corners and
+// io_of see a tc::Cfg as before.  s is the same in all lanes of the wave (readfirstlane says so to the compiler), so the ten doubles
+// arrive through scalar loads into SGPRs as the kernel argument's do.  A null table: G is used as it is.
+__device__ __forceinline__ tc::Cfg trk_stream_cfg(const tc::Cfg &G, const icg_camera *cams, int s) {
+    tc::Cfg C = G;
+    if (cams) {
+        const icg_camera *k = cams + __builtin_amdgcn_readfirstlane(s);
+        C.cam.fx = k->fx, C.cam.fy = k->fy, C.cam.cx = k->cx, C.cam.cy = k->cy, C.cam.skew = k->skew;
+        C.cam.k1 = k->k1, C.cam.k2 = k->k2, C.cam.p1 = k->p1, C.cam.p2 = k->p2, C.cam.k3 = k->k3;
+    }
+    return C;
+}
+
 template <int STAGE>
-__global__ __launch_bounds__(64 * TRK_WAVES) void k_trk_stage(int n, tc::Stream *streams, TrkArena A, tc::Cfg C, const uint32_t *buckets_after,
-                                                              icg_tracker_result *results, const TrkInput *in) {
+__global__ __launch_bounds__(64 * TRK_WAVES) void k_trk_stage(int n, tc::Stream *streams, TrkArena A, tc::Cfg G, const uint32_t *buckets_after,
+                                                              icg_tracker_result *results, const TrkInput *in, const icg_camera *cams) {
     constexpr int BODY = trk_body_of(STAGE);
     const int wave = (int) (threadIdx.x >> 6);
     const int s = blockIdx.x * TRK_WAVES + wave;
     if (s >= n) return; // all 64 lanes run the stage body (track_core.h "execution model"): redundantly where it is sequential
+    const tc::Cfg C = trk_stream_cfg(G, cams, s);
     tc::Stream &S = streams[s];
     TC_MARK_START();
     if constexpr (STAGE == 0 || STAGE == 120) {
@@ -311,6 +326,7 @@ struct icg_tracker {
     icg_tracker_result *h_res  = nullptr; // pinned, written by k_trk_stage 6
     bool need_detect_a         = true;    // some stream starts its next frame with a detection
     hipEvent_t ev_done         = nullptr; // wait_mode 2
+    icg_camera *d_cams         = nullptr; // icg_tracker_create_cams: the streams' cameras, the tracker's own copy (null: cfg.cam for all)
     int wait_mode              = 0;       // 0 adaptive (sleep + query), 1 the context's wait mode, 2 blocking event; ICG_TRACKER_WAIT=adaptive|ctx|block
     double step_us_ema         = 0;       // running estimate of a step's issue-to-completion time
 };
@@ -336,21 +352,20 @@ extern "C" void icg_tracker_destroy(icg_tracker *t) {
     if (t->d_buckets) (void) hipFree(t->d_buckets);
     if (t->d_vh) (void) hipFree(t->d_vh);
     if (t->d_arena) (void) hipFree(t->d_arena);
+    if (t->d_cams) (void) hipFree(t->d_cams);
     if (t->h_in) (void) hipHostFree(t->h_in);
     if (t->h_res) (void) hipHostFree(t->h_res);
     if (t->ev_done) (void) hipEventDestroy(t->ev_done);
     delete t;
 }
 
-extern "C" int icg_tracker_create(icg_ctx *ctx, int n_streams, const icg_tracker_config *cfg, const uint32_t *buckets_after, int n_buckets_after,
-                                  icg_tracker **out) {
-    if (!ctx || !cfg || !buckets_after || !out || n_streams <= 0) return ICG_ERR_INVALID;
-    *out = nullptr;
+// icg_tracker_create and icg_tracker_create_cams: one body; stream_cams (host, one camera per stream) null is the single-camera entry
+static int tracker_create(icg_ctx *ctx, int n_streams, const icg_tracker_config *cfg, const icg_camera *stream_cams, const uint32_t *buckets_after,
+                          int n_buckets_after, icg_tracker **out) {
 #if defined(TC_TIMING)
     static std::once_flag tc_once;
     std::call_once(tc_once, [] { atexit(tc_timing_dump); });
 #endif
-    if (!ctx->has_cam) return icg_fail(ctx, ICG_ERR_INVALID, "icg_tracker_create: camera not set (icg_set_camera)");
     if (n_buckets_after < tc::MAX_ROWS + 2) return icg_fail(ctx, ICG_ERR_INVALID, "buckets_after must cover %d insertions", tc::MAX_ROWS + 1);
     if ((int) buckets_after[tc::MAX_ROWS + 1] > tc::MAX_BUCKETS) return icg_fail(ctx, ICG_ERR_CAPACITY, "bucket table larger than the block's");
     if (n_streams > ctx->cfg.max_batch) return icg_fail(ctx, ICG_ERR_CAPACITY, "%d streams > max_batch %d", n_streams, ctx->cfg.max_batch);
@@ -423,6 +438,10 @@ extern "C" int icg_tracker_create(icg_ctx *ctx, int n_streams, const icg_tracker
     }
     memset(t->h_in, 0, sizeof(TrkInput) * n);
     memset(t->h_res, 0, sizeof(icg_tracker_result) * n);
+    if (stream_cams) {
+        if (icg_hip_check(ctx, hipMalloc((void **) &t->d_cams, sizeof(icg_camera) * n), "hipMalloc tracker cameras")) return fail(ICG_ERR_NOMEM);
+        if (icg_hip_check(ctx, hipMemcpy(t->d_cams, stream_cams, sizeof(icg_camera) * n, hipMemcpyHostToDevice), "copy tracker cameras")) return fail(ICG_ERR_HIP);
+    }
     hipLaunchKernelGGL(k_trk_init, dim3((n_streams + 63) / 64), dim3(64), 0, ctx->stream, n_streams, t->d_streams);
     if (icg_hip_check(ctx, hipGetLastError(), "k_trk_init")) return fail(ICG_ERR_HIP);
     if (icg_hip_check(ctx, hipStreamSynchronize(ctx->stream), "tracker init")) return fail(ICG_ERR_HIP);
@@ -430,9 +449,36 @@ extern "C" int icg_tracker_create(icg_ctx *ctx, int n_streams, const icg_tracker
     return ICG_OK;
 }
 
+extern "C" int icg_tracker_create(icg_ctx *ctx, int n_streams, const icg_tracker_config *cfg, const uint32_t *buckets_after, int n_buckets_after,
+                                  icg_tracker **out) {
+    if (!ctx || !cfg || !buckets_after || !out || n_streams <= 0) return ICG_ERR_INVALID;
+    *out = nullptr;
+    if (!ctx->has_cam) return icg_fail(ctx, ICG_ERR_INVALID, "icg_tracker_create: camera not set (icg_set_camera)");
+    return tracker_create(ctx, n_streams, cfg, nullptr, buckets_after, n_buckets_after, out);
+}
+
+// A tracker whose stream s uses camera stream_cam[s] of the context's table (NULL: camera s): the reference constructs a Tracking per camera
+// (tracking/tracking.h:51, tracking/camera.h:88-93).  The cameras are copied: a later icg_set_cameras does not move a live tracker's.
+extern "C" int icg_tracker_create_cams(icg_ctx *ctx, int n_streams, const icg_tracker_config *cfg, const int32_t *stream_cam,
+                                       const uint32_t *buckets_after, int n_buckets_after, icg_tracker **out) {
+    if (!ctx || !cfg || !buckets_after || !out || n_streams <= 0) return ICG_ERR_INVALID;
+    *out             = nullptr;
+    const int n_cams = (int) ctx->cams.size();
+    if (n_cams == 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_tracker_create_cams: no camera table (icg_set_cameras)");
+    if (!stream_cam && n_cams < n_streams)
+        return icg_fail(ctx, ICG_ERR_INVALID, "icg_tracker_create_cams: NULL stream_cam needs a camera per stream (%d cameras, %d streams)", n_cams, n_streams);
+    std::vector<icg_camera> cams((size_t) n_streams);
+    for (int s = 0; s < n_streams; s++) {
+        const int k = stream_cam ? stream_cam[s] : s;
+        if (k < 0 || k >= n_cams) return icg_fail(ctx, ICG_ERR_INVALID, "stream_cam[%d] = %d outside the table of %d cameras", s, k, n_cams);
+        cams[(size_t) s] = ctx->cams[(size_t) k];
+    }
+    return tracker_create(ctx, n_streams, cfg, cams.data(), buckets_after, n_buckets_after, out);
+}
+
 template <int STAGE> static void launch_stage_instance(icg_tracker *t) {
     hipLaunchKernelGGL(k_trk_stage<STAGE>, dim3((t->n + TRK_WAVES - 1) / TRK_WAVES), dim3(64 * TRK_WAVES), 0, t->ctx->stream, t->n, t->d_streams, t->A, t->cfg,
-                       (const uint32_t *) t->d_buckets, t->h_res, (const TrkInput *) t->h_in);
+                       (const uint32_t *) t->d_buckets, t->h_res, (const TrkInput *) t->h_in, (const icg_camera *) t->d_cams);
 }
 
 static int launch_stage(icg_tracker *t, int stage, const char *name) {
@@ -486,7 +532,7 @@ extern "C" int icg_tracker_step(icg_tracker *t, const uint8_t *const *images, in
     } else if (!fused_begin) {
         if ((rc = launch_stage(t, 12, "trk_stage_predict"))) return rc;
     }
-    if ((rc = icg_lk_launch_segments(ctx, n, tc::MAX_ROWS, A.lk_count, A.lk_prev_slot, A.lk_next_slot, A.lk_prev, A.lk_guess, A.lk_out, A.lk_status, A.lk_undist)))
+    if ((rc = icg_lk_launch_segments(ctx, n, tc::MAX_ROWS, A.lk_count, A.lk_prev_slot, A.lk_next_slot, A.lk_prev, A.lk_guess, A.lk_out, A.lk_status, A.lk_undist, t->d_cams)))
         return rc;
     if ((rc = launch_stage(t, 3, "trk_stage_lk"))) return rc;
     if ((rc = icg_fm_ransac_launch_sets(ctx, n, tc::MAX_ROWS, A.rs_count, A.rs_p1, A.rs_p2, t->cfg.reprojection_error_std, 0.99, A.rs_mask))) return rc;

@@ -100,8 +100,10 @@ class StreamBatch:
     """ctypes driver of icgh_batch (host/capi_batch.cc): N independent streams tracked in lock-step on one device."""
 
     def __init__(self, lib_path, n_streams, width, height, cam10, max_features=300, window=10, min_parallax=20.0,
-                 max_interval=0.5, check_hist=False, reproj_std=1.5, device=0, host_threads=1, groups=1, engine=None):
-        """engine: None (ICG_TRACK_ENGINE or the default, the track table), "table" or "object" (the reference-shaped object graph
+                 max_interval=0.5, check_hist=False, reproj_std=1.5, device=0, host_threads=1, groups=1, engine=None, cams=None):
+        """cams: optional per-stream calibration, n_streams x 10 (the layout of cam10 per row; icgh_batch_create_cams) — cam10 is then not
+        used.  Cameras that differ need the HIP-backed library: the construction fails where the camera-table entries are missing.
+        engine: None (ICG_TRACK_ENGINE or the default, the track table), "table" or "object" (the reference-shaped object graph
         throughout; on the table engine the entry points that work on the tracker's icg::Map — culling, window refinement, landmark
         tables — get an object view of the table and write their results back)."""
         if not os.path.exists(lib_path):
@@ -116,17 +118,24 @@ class StreamBatch:
         self.lib.icgh_batch_destroy.argtypes = [C.c_void_p]
         self.n, self.w, self.h = n_streams, width, height
         err = ErrBuf()
+        create = self.lib.icgh_batch_create
         cam = np.asarray(cam10, np.float64)
-        self.h_ = self.lib.icgh_batch_create(device, n_streams, cam.ctypes.data_as(C.c_void_p), width, height, max_features,
-                                             C.c_double(min_parallax), C.c_double(max_interval), 1 if check_hist else 0,
-                                             C.c_double(reproj_std), window, host_threads, groups, *err.args)
+        if cams is not None:
+            cam = np.ascontiguousarray(cams, np.float64)
+            if cam.shape != (n_streams, 10):
+                raise ValueError(f"cams must be {n_streams} x 10, got {cam.shape}")
+            create = self.lib.icgh_batch_create_cams
+            create.restype = C.c_void_p
+        self.h_ = create(device, n_streams, cam.ctypes.data_as(C.c_void_p), width, height, max_features,
+                         C.c_double(min_parallax), C.c_double(max_interval), 1 if check_hist else 0,
+                         C.c_double(reproj_std), window, host_threads, groups, *err.args)
         if engine is not None:
             if old_engine is None:
                 del os.environ["ICG_TRACK_ENGINE"]
             else:
                 os.environ["ICG_TRACK_ENGINE"] = old_engine
         if not self.h_:
-            raise RuntimeError("icgh_batch_create failed: " + err.text())
+            raise RuntimeError(("icgh_batch_create_cams" if cams is not None else "icgh_batch_create") + " failed: " + err.text())
         self._err = err
 
     def engine(self):

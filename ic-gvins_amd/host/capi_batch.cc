@@ -21,7 +21,51 @@ using namespace icg;
 struct icgh_batch {
     std::unique_ptr<StreamGroups> tb;
     int w, h;
+    bool cams_differ{false}; // icgh_batch_create_cams with cameras that are not all bit-equal
 };
+
+namespace {
+TrackingConfig batch_config(int max_features, double min_parallax, double max_interval, int check_hist, double reproj_std) {
+    TrackingConfig cfg;
+    cfg.track_max_features     = max_features;
+    cfg.track_min_parallax     = min_parallax;
+    cfg.track_max_interval     = max_interval;
+    cfg.track_check_histogram  = check_hist != 0;
+    cfg.reprojection_error_std = reproj_std;
+    return cfg;
+}
+
+// A culling entry of the batch's stream s: its map, its list, and — in a batch with per-stream cameras — its camera and the index of that
+// camera in its group's table (the stream's local index; -1 where the group's cameras are all equal and the group keeps a single camera)
+WindowCulling::Stream culling_stream(icgh_batch *b, int s, const std::unordered_map<ulong, double> *list) {
+    WindowCulling::Stream S{b->tb->stream(s).objectMap(), list};
+    if (b->cams_differ) {
+        S.camera    = b->tb->stream(s).camera;
+        S.cam_index = b->tb->group(b->tb->groupOf(s)).device()->cameraTableSize() > 0 ? b->tb->localOf(s) : -1;
+    }
+    return S;
+}
+
+// One WindowCulling call for all streams on group 0's context, as ever, where the batch has one camera.  With per-stream cameras a
+// group's table lives on the group's own context and is indexed by the local stream: one call per group, on its context.
+// stream_of[k]: the batch's stream of streams[k].
+template <typename R, typename Fn>
+bool cull_by_context(icgh_batch *b, const vector<WindowCulling::Stream> &streams, const vector<int> &stream_of, vector<R> &out, std::string *e, Fn &&call) {
+    if (!b->cams_differ) return call(b->tb->group(0).device()->ctx(), streams, out, e);
+    out.assign(streams.size(), R());
+    for (int g = 0; g < b->tb->groups(); g++) {
+        vector<WindowCulling::Stream> part;
+        vector<size_t> at;
+        for (size_t k = 0; k < streams.size(); k++)
+            if (b->tb->groupOf(stream_of[k]) == g) part.push_back(streams[k]), at.push_back(k);
+        if (part.empty()) continue;
+        vector<R> r;
+        if (!call(b->tb->group(g).device()->ctx(), part, r, e)) return false;
+        for (size_t j = 0; j < at.size(); j++) out[at[j]] = r[j];
+    }
+    return true;
+}
+} // namespace
 
 
 extern "C" {
@@ -30,19 +74,38 @@ icgh_batch *icgh_batch_create(int device, int n_streams, const double *cam10, in
                               double min_parallax, double max_interval, int check_hist, double reproj_std, int window,
                               int host_threads, int n_groups, char *err, int errlen) {
     return guarded(err, errlen, (icgh_batch *) nullptr, [&] {
-        TrackingConfig cfg;
-        cfg.track_max_features     = max_features;
-        cfg.track_min_parallax     = min_parallax;
-        cfg.track_max_interval     = max_interval;
-        cfg.track_check_histogram  = check_hist != 0;
-        cfg.reprojection_error_std = reproj_std;
+        const TrackingConfig cfg = batch_config(max_features, min_parallax, max_interval, check_hist, reproj_std);
         vector<double> intr{cam10[0], cam10[1], cam10[2], cam10[3], cam10[4]};
         vector<double> dist{cam10[5], cam10[6], cam10[7], cam10[8], cam10[9]};
-        auto *b = new icgh_batch();
-        b->w    = w;
-        b->h    = h;
+        std::unique_ptr<icgh_batch> b(new icgh_batch());
+        b->w = w;
+        b->h = h;
         b->tb.reset(new StreamGroups(device, n_streams, n_groups, intr, dist, {w, h}, cfg, window, host_threads));
-        return b;
+        return b.release();
+    });
+}
+
+// icgh_batch_create with a calibration per stream: cams = n_streams x 10 doubles (fx, fy, cx, cy, skew, k1, k2, p1, p2, k3 per stream).
+// Fails (NULL, the reason in err) where the cameras differ and the C ABI underneath has no camera-table entries.
+icgh_batch *icgh_batch_create_cams(int device, int n_streams, const double *cams, int w, int h, int max_features, double min_parallax,
+                                   double max_interval, int check_hist, double reproj_std, int window, int host_threads, int n_groups, char *err,
+                                   int errlen) {
+    return guarded(err, errlen, (icgh_batch *) nullptr, [&] {
+        if (!cams || n_streams <= 0) throw std::runtime_error("icgh_batch_create_cams: no cameras");
+        const TrackingConfig cfg = batch_config(max_features, min_parallax, max_interval, check_hist, reproj_std);
+        vector<vector<double>> intr, dist;
+        for (int i = 0; i < n_streams; i++) {
+            const double *c = cams + 10 * (size_t) i;
+            intr.emplace_back(c, c + 5);
+            dist.emplace_back(c + 5, c + 10);
+        }
+        std::unique_ptr<icgh_batch> b(new icgh_batch());
+        b->w = w;
+        b->h = h;
+        b->cams_differ = false;
+        for (int i = 1; i < n_streams; i++) b->cams_differ |= memcmp(cams, cams + 10 * (size_t) i, 10 * sizeof(double)) != 0;
+        b->tb.reset(new StreamGroups(device, n_streams, n_groups, intr, dist, {w, h}, cfg, window, host_threads));
+        return b.release();
     });
 }
 
@@ -363,13 +426,16 @@ int icgh_batch_culling(icgh_batch *b, int mode, const int32_t *list_off, const u
         vector<WindowCulling::Stream> streams;
         for (int s = 0; s < n; s++) {
             for (int k = list_off[s]; k < list_off[s + 1]; k++) lists[(size_t) s][in_list[k]] = 0.0;
-            streams.push_back({b->tb->stream(s).objectMap(), &lists[(size_t) s]});
+            streams.push_back(culling_stream(b, s, &lists[(size_t) s]));
         }
-        icg_ctx *ctx = b->tb->group(0).device()->ctx();
+        vector<int> stream_of((size_t) n);
+        for (int s = 0; s < n; s++) stream_of[(size_t) s] = s;
         std::string e;
         if (mode == 0) {
             vector<CullingResult> R;
-            if (!WindowCulling::gvinsOutlierCulling(ctx, streams, reprojection_error_std, R, &e)) {
+            if (!cull_by_context(b, streams, stream_of, R, &e, [&](icg_ctx *ctx, const vector<WindowCulling::Stream> &part, vector<CullingResult> &r, std::string *pe) {
+                    return WindowCulling::gvinsOutlierCulling(ctx, part, reprojection_error_std, r, pe);
+                })) {
                 set_err(err, errlen, e.c_str());
                 return -2;
             }
@@ -380,7 +446,9 @@ int icgh_batch_culling(icgh_batch *b, int mode, const int32_t *list_off, const u
             }
         } else {
             vector<ReprojectionStatistics> R;
-            if (!WindowCulling::reprojectionStatistics(ctx, streams, R, &e)) {
+            if (!cull_by_context(b, streams, stream_of, R, &e, [&](icg_ctx *ctx, const vector<WindowCulling::Stream> &part, vector<ReprojectionStatistics> &r, std::string *pe) {
+                    return WindowCulling::reprojectionStatistics(ctx, part, r, pe);
+                })) {
                 set_err(err, errlen, e.c_str());
                 return -2;
             }
@@ -407,7 +475,6 @@ int icgh_batch_refine_windows(icgh_batch *b, const double *pose_b_c12, double td
         MapViewsGuard views(b);
         Pose pbc;
         pbc = poseFromArray12(pose_b_c12);
-        icg_ctx *ctx = b->tb->group(0).device()->ctx();
         const bool lockstep = getenv("ICG_REFINE_PER_STREAM") == nullptr; // default: all streams' windows in ONE WindowSolverBatch
         vector<std::unique_ptr<VisualWindow>> wins;
         vector<vector<vector<double>>> priors((size_t) n);
@@ -482,12 +549,14 @@ int icgh_batch_refine_windows(icgh_batch *b, const double *pose_b_c12, double td
         for (int s = 0; s < n; s++) {
             if (wins[(size_t) s]->numKeyFrames() < 2 || wins[(size_t) s]->numFactors() == 0) continue;
             wins[(size_t) s]->updateParametersFromOptimizer();
-            cull.push_back({b->tb->stream(s).objectMap(), &wins[(size_t) s]->invdepthlist()});
+            cull.push_back(culling_stream(b, s, &wins[(size_t) s]->invdepthlist()));
             cull_stream.push_back(s);
         }
         vector<CullingResult> R;
         std::string e;
-        if (!cull.empty() && !WindowCulling::gvinsOutlierCulling(ctx, cull, reprojection_error_std, R, &e)) {
+        if (!cull.empty() && !cull_by_context(b, cull, cull_stream, R, &e, [&](icg_ctx *c, const vector<WindowCulling::Stream> &part, vector<CullingResult> &r, std::string *pe) {
+                return WindowCulling::gvinsOutlierCulling(c, part, reprojection_error_std, r, pe);
+            })) {
             set_err(err, errlen, e.c_str());
             return -4;
         }

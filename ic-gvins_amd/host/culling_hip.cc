@@ -2,9 +2,14 @@
 #include "culling_hip.h"
 
 #include <cmath>
+#include <cstring>
 #include <numeric>
 
 #include "../../include/icgvins_hip.h"
+
+// A build of this layer on another implementation of the C ABI may not have the entry: the reference stays weak (null when absent) and
+// evaluate() reports it; the product library links libicgvins_hip.so, which defines it.
+#pragma weak icg_reproj_error_batch_cams
 
 namespace icg {
 
@@ -23,12 +28,21 @@ struct Flat {
     std::vector<std::vector<FlatLandmark>> landmarks; // per stream
     std::vector<FlatObs> obs;
     std::vector<int32_t> pose_idx, lm_idx;
+    std::vector<int32_t> pose_cam; // per pose: the camera-table index of its stream (WindowCulling::Stream::cam_index)
+    bool cameras_differ = false;
     std::vector<double> poses12, pw;
     std::vector<float> pix;
 };
 
 void flatten(const std::vector<WindowCulling::Stream> &streams, Flat &F) {
     F.landmarks.resize(streams.size());
+    for (size_t s = 1; s < streams.size() && !F.cameras_differ; s++) {
+        if (!streams[s].camera != !streams[0].camera) F.cameras_differ = true;
+        if (streams[s].camera && streams[0].camera) {
+            const icg_camera a = streams[0].camera->abi(), b = streams[s].camera->abi();
+            F.cameras_differ = memcmp(&a, &b, sizeof a) != 0;
+        }
+    }
     for (size_t s = 0; s < streams.size(); s++) {
         const auto &S = streams[s];
         if (S.map->keyframes().empty()) continue; // :1036-1038
@@ -53,6 +67,7 @@ void flatten(const std::vector<WindowCulling::Stream> &streams, Flat &F) {
                     double p12[12];
                     poseToArray12(p, p12);
                     F.poses12.insert(F.poses12.end(), p12, p12 + 12);
+                    F.pose_cam.push_back((int32_t) S.cam_index);
                 }
                 const Point2f pp = feat->keyPoint();
                 F.pose_idx.push_back(it->second);
@@ -72,6 +87,24 @@ bool evaluate(icg_ctx *ctx, const Flat &F, double max_error, std::vector<double>
     err.assign((size_t) n, 0.0);
     good.assign((size_t) n, 0);
     if (n == 0) return true;
+    if (F.cameras_differ) { // every pose with the camera of its stream
+        if (!icg_reproj_error_batch_cams) {
+            if (e) *e = "WindowCulling: the streams' cameras differ and this build of the C ABI has no icg_reproj_error_batch_cams";
+            return false;
+        }
+        for (int32_t c : F.pose_cam)
+            if (c < 0) {
+                if (e) *e = "WindowCulling: the streams' cameras differ and a stream names no camera-table entry";
+                return false;
+            }
+        if (icg_reproj_error_batch_cams(ctx, n, F.pose_idx.data(), F.lm_idx.data(), (int) (F.poses12.size() / 12), F.poses12.data(), F.pose_cam.data(),
+                                        (int) (F.pw.size() / 3), F.pw.data(), F.pix.data(), max_error, MapPoint::NEAREST_DEPTH,
+                                        MapPoint::FARTHEST_DEPTH * 1.0, err.data(), good.data()) != ICG_OK) {
+            if (e) *e = icg_last_error(ctx);
+            return false;
+        }
+        return true;
+    }
     if (icg_reproj_error_batch(ctx, n, F.pose_idx.data(), F.lm_idx.data(), (int) (F.poses12.size() / 12), F.poses12.data(), (int) (F.pw.size() / 3),
                                F.pw.data(), F.pix.data(), max_error, MapPoint::NEAREST_DEPTH, MapPoint::FARTHEST_DEPTH * 1.0, err.data(),
                                good.data()) != ICG_OK) {

@@ -28,10 +28,15 @@ struct ReprojectionStatistics { // parameters[4..7] of parametersStatistic: min 
 class WindowCulling {
 public:
     // one entry per stream: the map, the ids of the landmarks that took part in the optimization (invdepthlist_) and the
-    // reprojection std (pixels); `camera` is the one set on ctx (icg_set_camera)
+    // reprojection std (pixels).  camera / cam_index: the stream's camera and its index in ctx's camera table (icg_set_cameras); without
+    // them (null / -1) the camera is the one set on ctx (icg_set_camera).  Streams whose cameras are all bit-equal are evaluated with
+    // icg_set_camera's camera, as before; where they differ every pose is evaluated with its stream's table entry
+    // (icg_reproj_error_batch_cams) — then every stream must name its entry, and a C ABI without that entry is an error, never camera 0.
     struct Stream {
         Map::Ptr map;
         const std::unordered_map<ulong, double> *invdepthlist;
+        Camera::Ptr camera{};
+        int cam_index{-1};
     };
     // gvinsOutlierCulling for every stream with ONE device launch; results[s] as the reference's counters
     static bool gvinsOutlierCulling(icg_ctx *ctx, const std::vector<Stream> &streams, double reprojection_error_std,

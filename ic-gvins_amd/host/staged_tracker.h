@@ -59,6 +59,9 @@ struct StageBatch {
     vector<int32_t> lk_prev_slot, lk_next_slot;
     vector<float> lk_prev, lk_guess, lk_out, lk_undist;
     vector<uint8_t> lk_status;
+    // camera index per LK point into the context's camera table (DeviceContext::setCameras): filled by TrackingBatch::gather with the
+    // stream's local index, empty in a single stream's own batch
+    vector<int32_t> lk_cam;
     // lk_base: where this stream's points start in the concatenated call (set when results are split back)
     int lk_base{0};
     // F6 RANSAC
@@ -80,6 +83,12 @@ public:
     ~DeviceContext();
     icg_ctx *ctx() { return ctx_; }
     void setCamera(const Camera &cam);
+    // One camera per stream of the context (icg_set_cameras): execute() then undistorts every LK point with the camera StageBatch::lk_cam
+    // names.  A table of bit-equal cameras is the single camera (setCamera) and sets no table.  A build of this layer on an implementation
+    // of the C ABI without the camera-table entries refuses a heterogeneous table by name (std::runtime_error).
+    void setCameras(const vector<Camera::Ptr> &cams);
+    int cameraTableSize() const { return n_cams_; } // 0: single camera
+    static bool sameCameras(const vector<Camera::Ptr> &cams);
     // runs whatever the batch contains, one ABI call per kind of work; throws std::runtime_error on ABI failure
     void execute(StageBatch &b, const icg_detect_grid &grid, int max_per_job);
     int allocSlot();
@@ -108,6 +117,7 @@ private:
     bool recording_{false};
     vector<StageBatch> recorded_;
     icg_ctx *ctx_{nullptr};
+    int n_cams_{0};
     vector<int> free_slots_;
     std::mutex slot_mutex_;
 };

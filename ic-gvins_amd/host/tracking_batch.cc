@@ -9,11 +9,32 @@
 
 #include <atomic>
 
+// A build of this layer on another implementation of the C ABI may not have the entry: the reference stays weak (null when absent) and the
+// constructor refuses a heterogeneous batch by name; the product library links libicgvins_hip.so, which defines it.
+#pragma weak icg_tracker_create_cams
+
 namespace icg {
 
 TrackingBatch::TrackingBatch(int device, int n_streams, const vector<double> &intrinsic, const vector<double> &distortion,
                              const vector<int> &size, const TrackingConfig &cfg, int window_size, int host_threads, int engine)
     : host_threads_(host_threads < 1 ? 1 : host_threads) {
+    vector<Camera::Ptr> cameras;
+    for (int i = 0; i < n_streams; i++) cameras.push_back(Camera::createCamera(intrinsic, distortion, size));
+    init(device, cameras, size, cfg, window_size, engine);
+}
+
+TrackingBatch::TrackingBatch(int device, int n_streams, const vector<vector<double>> &intrinsics, const vector<vector<double>> &distortions,
+                             const vector<int> &size, const TrackingConfig &cfg, int window_size, int host_threads, int engine)
+    : host_threads_(host_threads < 1 ? 1 : host_threads) {
+    if ((int) intrinsics.size() != n_streams || (int) distortions.size() != n_streams)
+        throw std::runtime_error("TrackingBatch: per-stream calibration needs one intrinsic and one distortion vector per stream");
+    vector<Camera::Ptr> cameras;
+    for (int i = 0; i < n_streams; i++) cameras.push_back(Camera::createCamera(intrinsics[(size_t) i], distortions[(size_t) i], size));
+    init(device, cameras, size, cfg, window_size, engine);
+}
+
+void TrackingBatch::init(int device, const vector<Camera::Ptr> &cameras, const vector<int> &size, const TrackingConfig &cfg, int window_size, int engine) {
+    const int n_streams = (int) cameras.size();
     if (engine < 0) { // ICG_TRACK_ENGINE=object|table|core; the drawer hooks only exist in the object engine
         const char *e = getenv("ICG_TRACK_ENGINE");
         engine        = (e && e[0] == 'o') || cfg.is_use_visualization ? ENGINE_OBJECT : (e && e[0] == 'c') ? ENGINE_CORE : (e && e[0] == 'd') ? ENGINE_DEVICE : ENGINE_TABLE;
@@ -27,7 +48,7 @@ TrackingBatch::TrackingBatch(int device, int n_streams, const vector<double> &in
     streams_.resize((size_t) n_streams);
     for (int i = 0; i < n_streams; i++) {
         Stream &s  = streams_[(size_t) i];
-        s.camera   = Camera::createCamera(intrinsic, distortion, size);
+        s.camera   = cameras[(size_t) i];
         s.ids      = std::make_shared<IdSpace>();
         // tracking.txt (tracking.cc:309-315) per stream under $ICG_TRACKING_LOG_DIR/stream<i>/ when that is set
         std::string outputpath;
@@ -46,14 +67,20 @@ TrackingBatch::TrackingBatch(int device, int n_streams, const vector<double> &in
         }
     }
     if (host_threads_ > 1 && n_streams > 1) pool_.reset(new HostPool(std::min(host_threads_, n_streams)));
-    device_->setCamera(*streams_[0].camera);
+    // one camera for all: icg_set_camera and the single-camera entries; cameras that differ: the context's table, indexed by the stream's
+    // index in this batch (never a silent fall-back to camera 0: setCameras throws where the table entries are missing)
+    device_->setCameras(cameras);
+    const bool per_stream = device_->cameraTableSize() > 0;
     if (engine_ == ENGINE_DEVICE) {
         const tc::Cfg C = TableTracker::makeCoreCfg(*streams_[0].camera, cfg, (size_t) window_size);
         icg_tracker_config tcfg;
         static_assert(sizeof(tcfg) == sizeof(C), "icg_tracker_config mirrors tc::Cfg");
         memcpy(&tcfg, &C, sizeof tcfg);
-        const int rc = icg_tracker_create(device_->ctx(), n_streams, &tcfg, TableTracker::bucketsAfterTable(), tc::MAX_ROWS + 2, &tracker_);
-        if (rc != ICG_OK) throw std::runtime_error(std::string("icg_tracker_create failed: ") + icg_last_error(device_->ctx()));
+        if (per_stream && !icg_tracker_create_cams)
+            throw std::runtime_error("TrackingBatch: the streams' cameras differ and this build of the C ABI has no icg_tracker_create_cams");
+        const int rc = per_stream ? icg_tracker_create_cams(device_->ctx(), n_streams, &tcfg, nullptr, TableTracker::bucketsAfterTable(), tc::MAX_ROWS + 2, &tracker_)
+                                  : icg_tracker_create(device_->ctx(), n_streams, &tcfg, TableTracker::bucketsAfterTable(), tc::MAX_ROWS + 2, &tracker_);
+        if (rc != ICG_OK) throw std::runtime_error(std::string(per_stream ? "icg_tracker_create_cams failed: " : "icg_tracker_create failed: ") + icg_last_error(device_->ctx()));
         for (int i = 0; i < n_streams; i++) {
             streams_[(size_t) i].tracker       = tracker_;
             streams_[(size_t) i].tracker_index = i;
@@ -196,6 +223,7 @@ template <typename T> static void append(vector<T> &dst, const vector<T> &src) {
 void TrackingBatch::gather(int cur, StageBatch &g, vector<std::array<int, 8>> &bases) {
     g.clear();
     bases.assign(streams_.size(), {});
+    const bool per_stream = device_->cameraTableSize() > 0;
     for (size_t i = 0; i < streams_.size(); i++) {
         const StageBatch &b = streams_[i].box[cur];
         auto &B             = bases[i];
@@ -226,6 +254,7 @@ void TrackingBatch::gather(int cur, StageBatch &g, vector<std::array<int, 8>> &b
             append(g.lk_next_slot, b.lk_next_slot);
             append(g.lk_prev, b.lk_prev);
             append(g.lk_guess, b.lk_guess);
+            if (per_stream) g.lk_cam.insert(g.lk_cam.end(), b.lk_prev_slot.size(), (int32_t) i); // the stream's index in this batch = its camera
         }
         if (b.rs_off.size() > 1) {
             append(g.rs_p1, b.rs_p1);
@@ -442,6 +471,24 @@ StreamGroups::StreamGroups(int device, int n_streams, int n_groups, const vector
                            const vector<double> &distortion, const vector<int> &size, const TrackingConfig &cfg,
                            int window_size, int host_threads_per_group)
     : n_streams_(n_streams) {
+    partition(n_groups, [&](int, int cnt) { return new TrackingBatch(device, cnt, intrinsic, distortion, size, cfg, window_size, host_threads_per_group); });
+}
+
+StreamGroups::StreamGroups(int device, int n_streams, int n_groups, const vector<vector<double>> &intrinsics,
+                           const vector<vector<double>> &distortions, const vector<int> &size, const TrackingConfig &cfg, int window_size,
+                           int host_threads_per_group)
+    : n_streams_(n_streams) {
+    if ((int) intrinsics.size() != n_streams || (int) distortions.size() != n_streams)
+        throw std::runtime_error("StreamGroups: per-stream calibration needs one intrinsic and one distortion vector per stream");
+    partition(n_groups, [&](int begin, int cnt) { // the group's own cameras: its table is indexed by the LOCAL stream index
+        const vector<vector<double>> gi(intrinsics.begin() + begin, intrinsics.begin() + begin + cnt);
+        const vector<vector<double>> gd(distortions.begin() + begin, distortions.begin() + begin + cnt);
+        return new TrackingBatch(device, cnt, gi, gd, size, cfg, window_size, host_threads_per_group);
+    });
+}
+
+void StreamGroups::partition(int n_groups, const std::function<TrackingBatch *(int begin, int cnt)> &make) {
+    const int n_streams = n_streams_;
     if (n_groups < 1) n_groups = 1;
     if (n_groups > n_streams) n_groups = n_streams;
     group_of_.resize((size_t) n_streams);
@@ -450,7 +497,7 @@ StreamGroups::StreamGroups(int device, int n_streams, int n_groups, const vector
     for (int g = 0; g < n_groups; g++) {
         int cnt = n_streams / n_groups + (g < n_streams % n_groups ? 1 : 0);
         group_begin_.push_back(begin);
-        groups_.emplace_back(new TrackingBatch(device, cnt, intrinsic, distortion, size, cfg, window_size, host_threads_per_group));
+        groups_.emplace_back(make(begin, cnt));
         for (int k = 0; k < cnt; k++) {
             group_of_[(size_t) (begin + k)] = g;
             local_of_[(size_t) (begin + k)] = k;

@@ -73,6 +73,12 @@ public:
 
     TrackingBatch(int device, int n_streams, const vector<double> &intrinsic, const vector<double> &distortion,
                   const vector<int> &size, const TrackingConfig &cfg, int window_size, int host_threads = 1, int engine = -1);
+    // The same with a calibration per stream: intrinsics[i] / distortions[i] (5 values each, as above) are stream i's camera, as the
+    // reference constructs a Tracking per camera (tracking/tracking.h:51).  Image size and tracking configuration stay common.  Cameras that
+    // are all bit-equal give exactly the constructor above; otherwise the context holds a camera table indexed by the stream's index in
+    // THIS batch (DeviceContext::setCameras; throws where the C ABI underneath has no camera-table entries).
+    TrackingBatch(int device, int n_streams, const vector<vector<double>> &intrinsics, const vector<vector<double>> &distortions,
+                  const vector<int> &size, const TrackingConfig &cfg, int window_size, int host_threads = 1, int engine = -1);
     ~TrackingBatch();
 
     // one frame per stream (frames[i].valid == false idles a stream); returns per-stream states
@@ -102,6 +108,7 @@ public:
     static constexpr size_t kStepLogCap = 1 << 14;
 
 private:
+    void init(int device, const vector<Camera::Ptr> &cameras, const vector<int> &size, const TrackingConfig &cfg, int window_size, int engine);
     void stepDevice(const FrameInput *frames, vector<TrackState> &states);
     icg_tracker *tracker_{nullptr};
     double last_step_s_{0};
@@ -133,6 +140,9 @@ class StreamGroups {
 public:
     StreamGroups(int device, int n_streams, int n_groups, const vector<double> &intrinsic, const vector<double> &distortion,
                  const vector<int> &size, const TrackingConfig &cfg, int window_size, int host_threads_per_group);
+    // a calibration per stream (n_streams x 5 each): every group gets the cameras of its own streams, indexed by the stream's LOCAL index
+    StreamGroups(int device, int n_streams, int n_groups, const vector<vector<double>> &intrinsics, const vector<vector<double>> &distortions,
+                 const vector<int> &size, const TrackingConfig &cfg, int window_size, int host_threads_per_group);
     ~StreamGroups();
     void step(const vector<FrameInput> &frames, vector<TrackState> &states);
     // K consecutive steps without a cross-group barrier in between: every group walks through its own K frames at its
@@ -146,9 +156,12 @@ public:
     TrackingBatch &group(int g) { return *groups_[(size_t) g]; }
     // global stream index -> (group, local index)
     TrackingBatch::Stream &stream(int i) { return groups_[(size_t) group_of_[(size_t) i]]->stream(local_of_[(size_t) i]); }
+    int groupOf(int i) const { return group_of_[(size_t) i]; }
+    int localOf(int i) const { return local_of_[(size_t) i]; }
     std::string error() const { return error_; }
 
 private:
+    void partition(int n_groups, const std::function<TrackingBatch *(int begin, int cnt)> &make);
     void workerLoop(int g);
     int n_streams_;
     vector<std::unique_ptr<TrackingBatch>> groups_;

@@ -13,6 +13,11 @@
 #include "tracking.h"
 #include "hostprof.h"
 
+// A build of this layer on another implementation of the C ABI may not have the camera-table entries: the references stay weak (null when
+// absent) and DeviceContext::setCameras refuses a heterogeneous table by name; the product library links libicgvins_hip.so, which defines them.
+#pragma weak icg_set_cameras
+#pragma weak icg_lk_track_fb_cams
+
 namespace icg {
 
 // ---- configuration ---------------------------------------------------------------------------------------------
@@ -64,6 +69,7 @@ void StageBatch::clear() {
     lk_out.clear();
     lk_undist.clear();
     lk_status.clear();
+    lk_cam.clear();
     rs_off.assign(1, 0);
     rs_p1.clear();
     rs_p2.clear();
@@ -100,6 +106,28 @@ DeviceContext::~DeviceContext() { icg_ctx_destroy(ctx_); }
 void DeviceContext::setCamera(const Camera &cam) {
     icg_camera c = cam.abi();
     abi_check(ctx_, icg_set_camera(ctx_, &c), "icg_set_camera");
+}
+
+bool DeviceContext::sameCameras(const vector<Camera::Ptr> &cams) {
+    for (size_t k = 1; k < cams.size(); k++) {
+        const icg_camera a = cams[0]->abi(), b = cams[k]->abi();
+        if (memcmp(&a, &b, sizeof a) != 0) return false;
+    }
+    return true;
+}
+
+void DeviceContext::setCameras(const vector<Camera::Ptr> &cams) {
+    if (cams.empty()) throw std::runtime_error("DeviceContext::setCameras: no cameras");
+    setCamera(*cams[0]);
+    n_cams_ = 0;
+    if (sameCameras(cams)) return; // one camera: the single-camera entries, as before
+    if (!icg_set_cameras || !icg_lk_track_fb_cams)
+        throw std::runtime_error("DeviceContext::setCameras: the streams' cameras differ and this build of the C ABI has no icg_set_cameras / "
+                                 "icg_lk_track_fb_cams (per-stream calibration needs libicgvins_hip.so)");
+    vector<icg_camera> table;
+    for (const auto &c : cams) table.push_back(c->abi());
+    abi_check(ctx_, icg_set_cameras(ctx_, (int) table.size(), table.data()), "icg_set_cameras");
+    n_cams_ = (int) table.size();
 }
 
 int DeviceContext::allocSlot() {
@@ -141,10 +169,17 @@ void DeviceContext::execute(StageBatch &b, const icg_detect_grid &grid, int max_
         b.lk_out.assign((size_t) n * 2, 0.f);
         b.lk_undist.assign((size_t) n * 2, 0.f);
         b.lk_status.assign((size_t) n, 0);
-        abi_check(ctx_,
-                  icg_lk_track_fb(ctx_, n, b.lk_prev_slot.data(), b.lk_next_slot.data(), b.lk_prev.data(), b.lk_guess.data(), b.lk_out.data(),
-                                  b.lk_status.data(), b.lk_undist.data(), nullptr, nullptr),
-                  "icg_lk_track_fb");
+        if (n_cams_ > 0) { // per-stream cameras: every point is undistorted with the camera of its stream
+            if ((int) b.lk_cam.size() != n) throw std::runtime_error("DeviceContext::execute: a camera table is set and the batch names no camera per LK point");
+            abi_check(ctx_,
+                      icg_lk_track_fb_cams(ctx_, n, b.lk_prev_slot.data(), b.lk_next_slot.data(), b.lk_prev.data(), b.lk_guess.data(), b.lk_cam.data(),
+                                           b.lk_out.data(), b.lk_status.data(), b.lk_undist.data(), nullptr, nullptr),
+                      "icg_lk_track_fb_cams");
+        } else
+            abi_check(ctx_,
+                      icg_lk_track_fb(ctx_, n, b.lk_prev_slot.data(), b.lk_next_slot.data(), b.lk_prev.data(), b.lk_guess.data(), b.lk_out.data(),
+                                      b.lk_status.data(), b.lk_undist.data(), nullptr, nullptr),
+                      "icg_lk_track_fb");
     }
     if (b.rs_off.size() > 1) {
         hostprof::Scope hp(hostprof::DEV_RANSAC);

@@ -33,6 +33,7 @@ EXPORTS = [
     "icg_preint_set", "icg_preint_evaluate_resident", "icg_preint_fetch_resident", "icg_reproj_host_parts_build_preint",
     "icg_preint_odo_batch", "icg_preint_odo_evaluate_batch",
     "icg_preint_odo_set", "icg_preint_odo_evaluate_resident", "icg_preint_odo_fetch_resident", "icg_reproj_host_parts_build_preint_odo",
+    "icg_set_cameras", "icg_lk_track_fb_cams", "icg_reproj_error_batch_cams", "icg_tracker_create_cams",
     "icg_nav_set", "icg_nav_evaluate_resident", "icg_nav_correct_resident", "icg_nav_fetch_resident", "icg_reproj_host_parts_build_nav",
 ]
 
@@ -121,6 +122,11 @@ class Context:
     def set_camera(self, cam10):
         cam = Camera(*[float(v) for v in cam10])
         self._ck(self.lib.icg_set_camera(self.h, C.byref(cam)), "icg_set_camera")
+
+    def set_cameras(self, cams):
+        """the context's camera table (n x 10): what the *_cams entries index"""
+        cams = f64(cams).reshape(-1, 10)
+        self._ck(self.lib.icg_set_cameras(self.h, cams.shape[0], _p(cams)), "icg_set_cameras")
 
     def prof_enable(self, on=True):
         self._ck(self.lib.icg_prof_enable(self.h, 1 if on else 0), "icg_prof_enable")
@@ -221,6 +227,26 @@ class Context:
         if want_keep:
             res.append(keep[:int(nkeep[0])])
         return tuple(res)
+
+    def lk_track_fb_cams(self, prev_slot, next_slot, prev_pts, guess, cam_idx, want_keep=False, check=True, fill=0):
+        """icg_lk_track_fb_cams: (out, status, undist[, keep]).  check=False: (rc, out, status, undist, keep, n_keep) with every output
+        buffer pre-filled with `fill` (argument-error tests; cam_idx may be None)"""
+        prev_pts = f32(prev_pts).reshape(-1, 2)
+        guess = f32(guess).reshape(-1, 2)
+        n = prev_pts.shape[0]
+        out = np.full((n, 2), fill, np.float32)
+        st = np.full(n, fill, np.uint8)
+        und = np.full((n, 2), fill, np.float32)
+        keep = np.full(max(n, 1), fill, np.int32) if want_keep else None
+        nkeep = np.full(1, fill, np.int32) if want_keep else None
+        ps = i32(np.broadcast_to(prev_slot, (n,)))
+        ns = i32(np.broadcast_to(next_slot, (n,)))
+        ci = None if cam_idx is None else i32(cam_idx)
+        rc = self.lib.icg_lk_track_fb_cams(self.h, n, _p(ps), _p(ns), _p(prev_pts), _p(guess), _p(ci), _p(out), _p(st), _p(und), _p(keep), _p(nkeep))
+        if not check:
+            return rc, out, st, und, keep, nkeep
+        self._ck(rc, "icg_lk_track_fb_cams")
+        return (out, st, und, keep[:int(nkeep[0])]) if want_keep else (out, st, und)
 
     # ---- F4/F5
     def undistort(self, pts):
@@ -361,6 +387,21 @@ class Context:
         self._ck(self.lib.icg_reproj_error_batch(self.h, n, _p(i32(pose_idx)), _p(i32(lm_idx)), poses12.shape[0], _p(poses12), pw.shape[0],
                                                   _p(pw), _p(pix), C.c_double(max_error), C.c_double(min_depth), C.c_double(max_depth), _p(err),
                                                   _p(good)), "icg_reproj_error_batch")
+        return err, good
+
+    def reproj_error_batch_cams(self, pose_idx, lm_idx, poses12, pose_cam, pw, pix, max_error, min_depth=1.0, max_depth=200.0, check=True, fill=0):
+        """icg_reproj_error_batch_cams: (err, good); check=False: (rc, err, good) with the outputs pre-filled with `fill`"""
+        poses12 = f64(poses12).reshape(-1, 12)
+        pw = f64(pw).reshape(-1, 3)
+        pix = f32(pix).reshape(-1, 2)
+        n = pix.shape[0]
+        err, good = np.full(n, float(fill)), np.full(n, fill, np.uint8)
+        pc = None if pose_cam is None else i32(pose_cam)
+        rc = self.lib.icg_reproj_error_batch_cams(self.h, n, _p(i32(pose_idx)), _p(i32(lm_idx)), poses12.shape[0], _p(poses12), _p(pc), pw.shape[0],
+                                                  _p(pw), _p(pix), C.c_double(max_error), C.c_double(min_depth), C.c_double(max_depth), _p(err), _p(good))
+        if not check:
+            return rc, err, good
+        self._ck(rc, "icg_reproj_error_batch_cams")
         return err, good
 
     # ---- f1

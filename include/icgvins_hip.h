@@ -67,6 +67,13 @@ int icg_ctx_set_wait_mode(icg_ctx *ctx, int mode, int sleep_us);
 /* hipStream_t of the context (for callers that want to record their own HIP events on it). */
 void *icg_ctx_stream(icg_ctx *ctx);
 int icg_set_camera(icg_ctx *ctx, const icg_camera *cam);
+/* The context's camera TABLE: n_cams cameras resident on the device, one per camera stream the context serves — the reference constructs
+ * a Tracking (and a GVINS) per camera (tracking/tracking.h:51, tracking/camera.h:88-93); a context holds ONE image size and N cameras.
+ * Replaces the table the context held.  Read by the entries named *_cams (icg_lk_track_fb_cams, icg_reproj_error_batch_cams,
+ * icg_tracker_create_cams); icg_set_camera's camera and every entry that uses it are unaffected.  The stand-alone point entries
+ * (icg_undistort_points, icg_distort_points, icg_predict_mappoints, icg_predict_rotation) are not called by the host layer and stay on
+ * icg_set_camera's camera.  ICG_ERR_INVALID: n_cams <= 0 or cams NULL (the table the context held stays). */
+int icg_set_cameras(icg_ctx *ctx, int n_cams, const icg_camera *cams);
 const char *icg_version(void);
 /* number of pyramid levels built for the context's image size (== maxLevel+1 of calcOpticalFlowPyrLK). */
 int icg_pyramid_levels(const icg_ctx *ctx);
@@ -109,6 +116,14 @@ int icg_lk_track(icg_ctx *ctx, int n, const int32_t *prev_slot, const int32_t *n
 int icg_lk_track_fb(icg_ctx *ctx, int n, const int32_t *prev_slot, const int32_t *next_slot, const float *prev_pts,
                     const float *guess_pts, float *out_pts, uint8_t *status, float *out_undist, int32_t *keep_idx,
                     int32_t *n_keep);
+
+/* icg_lk_track_fb with one camera index per point: out_undist[i] = Camera::undistortPoints (camera.cc:72-74) of out_pts[i] under camera
+ * cam_idx[i] of the context's table (icg_set_cameras) — the points of several Tracking instances, each with its own camera
+ * (tracking/tracking.h:51), in one call.  out_pts, status, keep_idx and n_keep do not depend on the camera.
+ * ICG_ERR_INVALID, nothing launched and no output touched: no table set, cam_idx NULL, an index outside the table, and icg_lk_track_fb's. */
+int icg_lk_track_fb_cams(icg_ctx *ctx, int n, const int32_t *prev_slot, const int32_t *next_slot, const float *prev_pts,
+                         const float *guess_pts, const int32_t *cam_idx, float *out_pts, uint8_t *status, float *out_undist,
+                         int32_t *keep_idx, int32_t *n_keep);
 
 /* ---- F4: Camera point maps (tracking/camera.cc) -------------------------------------------------------- */
 int icg_undistort_points(icg_ctx *ctx, int n, float *pts);                 /* camera.cc:72-74  in place */
@@ -676,6 +691,13 @@ int icg_chol_solve_batch(icg_ctx *ctx, int n_systems, const int32_t *n, const do
 int icg_reproj_error_batch(icg_ctx *ctx, int n, const int32_t *pose_idx, const int32_t *lm_idx, int n_poses, const double *poses12,
                            int n_lm, const double *pw, const float *pix, double max_error, double min_depth, double max_depth,
                            double *err_out, uint8_t *good_out);
+/* The same with one camera index per POSE: an observation is projected with camera pose_cam[pose_idx[i]] of the context's table
+ * (icg_set_cameras) — the windows of several GVINS instances, each culled with its own camera_ (ic_gvins.cc:1068-1078, :985), in one launch.
+ * ICG_ERR_INVALID, nothing launched and no output touched: no table set, pose_cam NULL, an index outside the table, and
+ * icg_reproj_error_batch's. */
+int icg_reproj_error_batch_cams(icg_ctx *ctx, int n, const int32_t *pose_idx, const int32_t *lm_idx, int n_poses, const double *poses12,
+                                const int32_t *pose_cam, int n_lm, const double *pw, const float *pix, double max_error, double min_depth,
+                                double max_depth, double *err_out, uint8_t *good_out);
 
 /* ---- f4 (SURVEY.md §8 "next" row): the INS steps in front of the tracker, batched over independent streams -----------
  * Layouts: imu rows of 8 doubles (time, dt, dtheta[3], dvel[3]); state rows of 23 doubles (time, p3, q4 xyzw, v3, bg3, ba3,
@@ -740,6 +762,13 @@ typedef struct icg_tracker_result { /* per stream, after a step */
  * library (the reference container whose iteration order the feature rows keep); n_buckets_after must cover the row capacity + 2. */
 int icg_tracker_create(icg_ctx *ctx, int n_streams, const icg_tracker_config *cfg, const uint32_t *buckets_after, int n_buckets_after,
                        icg_tracker **out);
+/* A tracker with a camera per stream: stream s tracks with camera stream_cam[s] of the context's table (icg_set_cameras), as the Tracking
+ * the reference constructs for that camera would (tracking/tracking.h:51); stream_cam NULL means camera s and needs n_cams >= n_streams.
+ * The camera fields of cfg are ignored (width / height are not).  The tracker copies the cameras it uses: a later icg_set_cameras on the
+ * context does not move a live tracker's.  ICG_ERR_INVALID (no tracker is created): no table set, an index outside the table, NULL
+ * stream_cam with fewer cameras than streams, and icg_tracker_create's. */
+int icg_tracker_create_cams(icg_ctx *ctx, int n_streams, const icg_tracker_config *cfg, const int32_t *stream_cam,
+                            const uint32_t *buckets_after, int n_buckets_after, icg_tracker **out);
 void icg_tracker_destroy(icg_tracker *t);
 size_t icg_tracker_block_bytes(void);
 /* One frame per stream: images[k] (stride / channels as icg_frames_preprocess; NULL = stream k idles this step), its stamp and INS pose
