@@ -12,7 +12,9 @@
 // to the places k_host_part reads.  The same kernel serves a block that is a preintegration factor of the resident P2 set (preint.hip,
 // icg_reproj_host_parts_build_preint): its source matrix is the factor's whitened 15 x 32 Jacobian, its row stride 32; and a factor of the
 // resident odometer P2 set (preint_odo.hip, icg_reproj_host_parts_build_preint_odo): 19 x 34, row stride 34; and a member of the resident nav set
-// (nav.hip, icg_reproj_host_parts_build_nav): nr x width, row stride the member's block width.
+// (nav.hip, icg_reproj_host_parts_build_nav): nr x width, row stride the member's block width.  On the host side a family of resident blocks is
+// one line of hp_families (its rules, its gather code, its entry and the words of its messages); validation and staging loop over that table,
+// and the five exported entries hand hp_build the tables of the families they have.
 #include <array>
 
 #include "reproj_internal.h"
@@ -181,13 +183,20 @@ struct hp_args { // the arguments of a call as the stages read them; me: the ent
     const double *J, *r;
     double *host_s, *host_diag, *part_out;
 };
-// A family of device-resident blocks.  Its rules: may member idx of the family's resident set be block p of window w, B.nr residuals whose kept Jacobian
-// holds the columns pc[0 .. B.nf) of the member's source matrix (B.fill: gathered in this call)?  They fill in the member's source, residuals and row stride.
+// A family of device-resident blocks: what hp_families (below the rules) says of it once, and what a call brings for it.  Its rules: may member idx of the
+// family's resident set be block p of window w, B.nr residuals whose kept Jacobian holds the columns pc[0 .. B.nf) of the member's source matrix (B.fill:
+// gathered in this call)?  They fill in the member's source, residuals and row stride.
 typedef int hp_rules(icg_ctx *ctx, const char *me, int w, int p, int idx, const int32_t *pc, hp_prior &B);
 struct hp_family {
     hp_rules *rules;
-    const int32_t *of, *cols; // per block of the call its member of the set (< 0: none; NULL: no block of the call); the members' columns, block after block
-    int64_t gather;           // the jac_off that asks for the kept Jacobian to be gathered from the member's source
+    int64_t gather;     // the jac_off that asks for the kept Jacobian to be gathered from the member's source
+    const char *entry;  // the narrowest entry that takes the family's tables: a call's messages name the widest family whose table it was given
+    const char *member; // article and noun, as in "both a prior (0) and a navigation factor (1)"
+    // a block outside the family that asks for `gather` is refused as "<jac_name> for a block that is no <no_member>"; jac_name NULL: as "jac_off = <value>",
+    // and so it is with named_with_of in a call without the family's table (an older entry reports the value, as it always did)
+    const char *jac_name, *no_member;
+    bool named_with_of;
+    const int32_t *of, *cols; // the call's: per block its member of the set (< 0: none; NULL: no block of the call); the members' columns, block after block
     size_t at;                // walks cols over the family's blocks of ALL windows (a window that is not rebuilt still places the others')
 };
 
@@ -257,7 +266,14 @@ static int hp_rules_nav(icg_ctx *ctx, const char *me, int w, int p, int fp, cons
     return ICG_OK;
 }
 
-#define HP_FAMILIES 4 // marginalization priors, preintegration factors, odometer preintegration factors, navigation factors
+// The families, narrowest entry first: a new one is a line here, its rules above and its entry at the foot of the file.
+static const hp_family hp_families[] = {
+    {hp_rules_prior, ICG_HP_JAC_FROM_PRIOR, "icg_reproj_host_parts_build_prior", "a prior", nullptr, nullptr, false},
+    {hp_rules_preint, ICG_HP_JAC_FROM_PREINT, "icg_reproj_host_parts_build_preint", "a preintegration factor", "ICG_HP_JAC_FROM_PREINT", "preintegration factor", false},
+    {hp_rules_preint_odo, ICG_HP_JAC_FROM_PREINT_ODO, "icg_reproj_host_parts_build_preint_odo", "an odometer preintegration factor", "ICG_HP_JAC_FROM_PREINT_ODO",
+     "odometer preintegration factor", false},
+    {hp_rules_nav, ICG_HP_JAC_FROM_NAV, "icg_reproj_host_parts_build_nav", "a navigation factor", "ICG_HP_JAC_FROM_NAV", "navigation factor", true}};
+constexpr int HP_FAMILIES = (int) (sizeof(hp_families) / sizeof(hp_families[0]));
 struct hp_plan { // what validation leaves for the stages behind it
     bool drop_all, have_kept;
     std::vector<int32_t> r_off, c_off; // every block's place in the staged r and cols
@@ -283,11 +299,7 @@ static int hp_validate_block(icg_ctx *ctx, const hp_args &a, const hp_family (&F
     int fam = -1; // the family the block is resident in
     for (int f = 0; f < HP_FAMILIES; f++) {
         if (idx[f] < 0) continue;
-        if (fam >= 0 && f == 1) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both a prior (%d) and a preintegration factor (%d)", me, w, p, idx[0], idx[1]);
-        if (fam >= 0)
-            return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both %s (%d) and %s (%d)", me, w, p,
-                            fam == 0 ? "a prior" : fam == 1 ? "a preintegration factor" : "an odometer preintegration factor", idx[fam],
-                            f == 2 ? "an odometer preintegration factor" : "a navigation factor", idx[f]);
+        if (fam >= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: both %s (%d) and %s (%d)", me, w, p, F[fam].member, idx[fam], F[f].member, idx[f]);
         fam = f;
         hp_prior B{nullptr, nullptr, 0 /* its place among the kept Jacobians: hp_stage */, 0, plan.r_off[(size_t) b], (int32_t) c0[f], nr, nf, a.jac_off[b] == F[f].gather ? 1 : 0};
         if (int rc = F[f].rules(ctx, me, w, p, idx[f], F[f].cols ? F[f].cols + c0[f] : nullptr, B)) return rc;
@@ -299,12 +311,6 @@ static int hp_validate_block(icg_ctx *ctx, const hp_args &a, const hp_family (&F
         plan.ship_doubles += (size_t) nr * nf;
     } else if (fam >= 0 && a.jac_off[b] == F[fam].gather) {
         // gathered on the device: from the prior's J0, from the factor's resident Jacobian
-    } else if (a.jac_off[b] == ICG_HP_JAC_FROM_PREINT) {
-        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: ICG_HP_JAC_FROM_PREINT for a block that is no preintegration factor", me, w, p);
-    } else if (a.jac_off[b] == ICG_HP_JAC_FROM_PREINT_ODO) {
-        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: ICG_HP_JAC_FROM_PREINT_ODO for a block that is no odometer preintegration factor", me, w, p);
-    } else if (a.jac_off[b] == ICG_HP_JAC_FROM_NAV && F[3].of) { // (an entry without nav_of reports the value, as it always did)
-        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: ICG_HP_JAC_FROM_NAV for a block that is no navigation factor", me, w, p);
     } else if (a.jac_off[b] == -1) {
         any_keep = true;
         if (!kept || (size_t) p >= kept->size()) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no kept Jacobian", me, w, p);
@@ -312,6 +318,9 @@ static int hp_validate_block(icg_ctx *ctx, const hp_args &a, const hp_family (&F
         if (k.nr != nr || k.nf != nf)
             return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: the kept Jacobian is %d x %d, not %d x %d", me, w, p, k.nr, k.nf, nr, nf);
     } else {
+        for (const hp_family &G : F) // another family's gather code
+            if (a.jac_off[b] == G.gather && G.jac_name && (G.of || !G.named_with_of))
+                return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %s for a block that is no %s", me, w, p, G.jac_name, G.no_member);
         return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: jac_off = %lld", me, w, p, (long long) a.jac_off[b]);
     }
     return ICG_OK;
@@ -472,7 +481,7 @@ static int hp_stage(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[HP_FAMI
     S.d_cols   = c.in(a.cols, n_c);
     S.d_pr     = c.in(plan.res.data(), plan.res.size());
     S.d_pc     = plan.res.empty() ? nullptr : c.in(plan.res_cols.data(), plan.res_cols.size());
-    if (!F[0].of && !F[1].of && !F[2].of && !F[3].of) {
+    if (std::none_of(F, F + HP_FAMILIES, [](const hp_family &G) { return G.of != nullptr; })) {
         S.d_r = c.in(a.r, n_r);
     } else {
         // The slots of the resident blocks (of every window, rebuilt or not) are placed but not read from the caller: staged block by block,
@@ -482,8 +491,7 @@ static int hp_stage(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[HP_FAMI
         const size_t off = icg_arena_alloc(ctx, sizeof(double) * n_r);
         double *h        = icg_h<double>(ctx, off);
         for (int b = 0; b < nb; b++)
-            if ((!F[0].of || F[0].of[b] < 0) && (!F[1].of || F[1].of[b] < 0) && (!F[2].of || F[2].of[b] < 0) && (!F[3].of || F[3].of[b] < 0))
-                memcpy(h + plan.r_off[(size_t) b], a.r + plan.r_off[(size_t) b], sizeof(double) * (size_t) a.nr[b]);
+            if (std::none_of(F, F + HP_FAMILIES, [b](const hp_family &G) { return G.of && G.of[b] >= 0; })) memcpy(h + plan.r_off[(size_t) b], a.r + plan.r_off[(size_t) b], sizeof(double) * (size_t) a.nr[b]);
         c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * n_r);
         S.d_r = icg_d<double>(ctx, off);
     }
@@ -536,52 +544,21 @@ static int hp_launch(icg_ctx *ctx, const hp_args &a, const hp_plan &plan, std::v
     return ICG_OK;
 }
 
-extern "C" int icg_reproj_host_parts_build(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
-                                           const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s,
-                                           double *host_diag, double *part_out) {
-    return icg_reproj_host_parts_build_prior(ctx, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, nullptr, nullptr);
-}
+// ---- the exported entries (include/icgvins_hip.h): each hands hp_build what all of them take and an (of, cols) pair per family it has, in hp_families' order
+#define HP_PARAMS                                                                                                                                                     \
+    icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr, const int32_t *nf, const int32_t *cols,                 \
+        const int64_t *jac_off, const double *J, const double *r, double *host_s, double *host_diag, double *part_out
+#define HP_ARGS hp_args{nullptr, P, 0, Pw, blk_off, nr, nf, cols, rebuild, jac_off, J, r, host_s, host_diag, part_out}
+typedef const int32_t *hp_table;
 
-extern "C" int icg_reproj_host_parts_build_prior(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
-                                                 const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r,
-                                                 double *host_s, double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols) {
-    return icg_reproj_host_parts_build_preint(ctx, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, prior_of, prior_cols, nullptr,
-                                              nullptr);
-}
-
-extern "C" int icg_reproj_host_parts_build_preint(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
-                                                  const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r,
-                                                  double *host_s, double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols,
-                                                  const int32_t *preint_of, const int32_t *preint_cols) {
-    return icg_reproj_host_parts_build_preint_odo(ctx, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, prior_of, prior_cols, preint_of,
-                                                  preint_cols, nullptr, nullptr);
-}
-
-extern "C" int icg_reproj_host_parts_build_preint_odo(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
-                                                      const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r,
-                                                      double *host_s, double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols,
-                                                      const int32_t *preint_of, const int32_t *preint_cols, const int32_t *preint_odo_of,
-                                                      const int32_t *preint_odo_cols) {
-    return icg_reproj_host_parts_build_nav(ctx, P, Pw, rebuild, blk_off, nr, nf, cols, jac_off, J, r, host_s, host_diag, part_out, prior_of, prior_cols, preint_of,
-                                           preint_cols, preint_odo_of, preint_odo_cols, nullptr, nullptr);
-}
-
-extern "C" int icg_reproj_host_parts_build_nav(icg_ctx *ctx, int P, const int32_t *Pw, const uint8_t *rebuild, const int32_t *blk_off, const int32_t *nr,
-                                               const int32_t *nf, const int32_t *cols, const int64_t *jac_off, const double *J, const double *r, double *host_s,
-                                               double *host_diag, double *part_out, const int32_t *prior_of, const int32_t *prior_cols, const int32_t *preint_of,
-                                               const int32_t *preint_cols, const int32_t *preint_odo_of, const int32_t *preint_odo_cols, const int32_t *nav_of,
-                                               const int32_t *nav_cols) {
+// The families beyond `tables` have none, as in a call of a wider entry with NULL for them: the messages name the entry of the widest family that has one.
+static int hp_build(icg_ctx *ctx, hp_args a, std::initializer_list<std::array<hp_table, 2>> tables) {
     if (!ctx) return ICG_ERR_INVALID;
-    const char *me = nav_of          ? "icg_reproj_host_parts_build_nav"
-                     : preint_odo_of ? "icg_reproj_host_parts_build_preint_odo"
-                     : preint_of     ? "icg_reproj_host_parts_build_preint"
-                     : prior_of      ? "icg_reproj_host_parts_build_prior"
-                                     : "icg_reproj_host_parts_build";
-    const hp_args a{me, P, ctx->part_w.W, Pw, blk_off, nr, nf, cols, rebuild, jac_off, J, r, host_s, host_diag, part_out};
-    hp_family F[HP_FAMILIES] = {{hp_rules_prior, prior_of, prior_cols, ICG_HP_JAC_FROM_PRIOR, 0},
-                                {hp_rules_preint, preint_of, preint_cols, ICG_HP_JAC_FROM_PREINT, 0},
-                                {hp_rules_preint_odo, preint_odo_of, preint_odo_cols, ICG_HP_JAC_FROM_PREINT_ODO, 0},
-                                {hp_rules_nav, nav_of, nav_cols, ICG_HP_JAC_FROM_NAV, 0}};
+    hp_family F[HP_FAMILIES];
+    std::copy(hp_families, hp_families + HP_FAMILIES, F);
+    a.me = "icg_reproj_host_parts_build", a.W = ctx->part_w.W;
+    hp_family *G = F;
+    for (const std::array<hp_table, 2> &t : tables) G->of = t[0], G->cols = t[1], a.me = t[0] ? G->entry : a.me, G++;
     hp_plan plan;
     int rc, dst;
     if ((rc = hp_validate(ctx, a, F, plan))) return rc;
@@ -593,4 +570,22 @@ extern "C" int icg_reproj_host_parts_build_nav(icg_ctx *ctx, int P, const int32_
     hp_staged S;
     if ((rc = hp_stage(ctx, a, F, plan, next, c, S))) return rc;
     return hp_launch(ctx, a, plan, next, dst, c, S);
+}
+
+extern "C" int icg_reproj_host_parts_build(HP_PARAMS) { return hp_build(ctx, HP_ARGS, {}); }
+
+extern "C" int icg_reproj_host_parts_build_prior(HP_PARAMS, hp_table prior_of, hp_table prior_cols) { return hp_build(ctx, HP_ARGS, {{prior_of, prior_cols}}); }
+
+extern "C" int icg_reproj_host_parts_build_preint(HP_PARAMS, hp_table prior_of, hp_table prior_cols, hp_table preint_of, hp_table preint_cols) {
+    return hp_build(ctx, HP_ARGS, {{prior_of, prior_cols}, {preint_of, preint_cols}});
+}
+
+extern "C" int icg_reproj_host_parts_build_preint_odo(HP_PARAMS, hp_table prior_of, hp_table prior_cols, hp_table preint_of, hp_table preint_cols, hp_table preint_odo_of,
+                                                      hp_table preint_odo_cols) {
+    return hp_build(ctx, HP_ARGS, {{prior_of, prior_cols}, {preint_of, preint_cols}, {preint_odo_of, preint_odo_cols}});
+}
+
+extern "C" int icg_reproj_host_parts_build_nav(HP_PARAMS, hp_table prior_of, hp_table prior_cols, hp_table preint_of, hp_table preint_cols, hp_table preint_odo_of,
+                                               hp_table preint_odo_cols, hp_table nav_of, hp_table nav_cols) {
+    return hp_build(ctx, HP_ARGS, {{prior_of, prior_cols}, {preint_of, preint_cols}, {preint_odo_of, preint_odo_cols}, {nav_of, nav_cols}});
 }

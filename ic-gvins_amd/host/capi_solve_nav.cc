@@ -135,158 +135,13 @@ int icgh_backend_solve_nav_batch(int W, int variant, const int32_t *n_intervals,
                                  "preintegration) or 5 (mode 3 and device preintegration); variant 0 .. 3; device_nav 0 or 1 (+ 16)");
             return -1;
         }
-        const bool odo = variant >= 2, prior = mode == 3 || mode == 5, preint = mode >= 4;
-        const int mw = odo ? 10 : 9, sw = 7 + mw; // mix and state widths
         if (nav_on_device) *nav_on_device = 0;
-        // (the entry a mode adds is named first: a build without any of them says what that mode itself is missing)
-        const char *missing = device_nav && mode >= 1 ? WindowSolverBatch::deviceNavFactorsMissing() : nullptr;
-        if (!missing && preint && odo) missing = WindowSolverBatch::devicePreintegrationOdoMissing();
-        if (!missing && preint) missing = WindowSolverBatch::devicePreintegrationMissing();
-        if (!missing && prior && !WindowSolverBatch::devicePriorAvailable())
-            missing = MarginalizationPriorSet::residentAvailable() ? "icg_reproj_host_parts_build_prior" : "icg_marg_prior_evaluate_resident";
-        if (!missing && mode >= 2 && !WindowSolverBatch::deviceHostPartAvailable()) missing = "icg_reproj_host_parts_build";
-        if (!missing && mode >= 1 && !WindowSolverBatch::deviceReducedSolveAvailable()) missing = "icg_reproj_solve_windows";
-        if (missing) {
-            set_err(err, errlen, (std::string(missing) + " is not in this build").c_str());
-            return -4;
-        }
-        TempCtx T(0);
-        struct Win {
-            int K;
-            vector<double> pose, mix;
-            vector<std::shared_ptr<Preintegration>> pre;
-            vector<std::shared_ptr<PreintegrationOdo>> pre_odo;
-        };
-        vector<Win> wins((size_t) W);
-        vector<Preintegration *> raw;
-        auto p9 = odo ? nullptr : preint_params(params9);
-        auto p19 = odo ? odo_params19(params19) : nullptr;
-        for (int w = 0; w < W; w++) {
-            Win &V = wins[(size_t) w];
-            V.K    = n_intervals[w] + 1;
-            V.pose.resize((size_t) V.K * 7), V.mix.resize((size_t) V.K * mw);
-            for (int k = 0; k < V.K; k++)
-                memcpy(&V.pose[7 * (size_t) k], states[w] + sw * (size_t) k, sizeof(double) * 7),
-                    memcpy(&V.mix[(size_t) mw * k], states[w] + sw * (size_t) k + 7, sizeof(double) * (size_t) mw);
-            for (int k = 0; k < n_intervals[w]; k++) {
-                const size_t j = (size_t) k;
-                if (odo) {
-                    const int rows = variant == 3 && pn_off && pn_off[w] ? pn_off[w][k + 1] - pn_off[w][k] : 0;
-                    V.pre_odo.push_back(odo_from_result(p19, variant, delta[w] + 20 * j, jac[w] + 361 * j, cov[w] + 361 * j, dt[w][j],
-                                                        rows > 0 ? pn[w] + 4 * (size_t) pn_off[w][k] : nullptr, rows, iewn[w] + 3 * j));
-                } else {
-                    V.pre.push_back(preint_interval(variant, p9, offsets[w], imu[w], k, states[w] + 16 * j));
-                    raw.push_back(V.pre.back().get());
-                }
-            }
-        }
-        std::string e;
-        if (!odo && !Preintegration::integrateBatch(T.ctx, raw, &e)) {
-            set_err(err, errlen, e.c_str());
-            return -2;
-        }
-        vector<std::unique_ptr<ReprojectionFactor>> factors;
-        WindowSolverBatch solver(0, huber);
-        solver.setDeviceReducedSolve(mode >= 1);
-        solver.setDeviceHostPart(mode >= 2 && !without_parts);
-        solver.setDevicePrior(prior);
-        solver.setDevicePreintegration(preint);
-        solver.setDeviceNavFactors(device_nav != 0);
-        vector<int> prior_id((size_t) W, -1);
-        vector<double> std_w(10, 1.0 / prior_weight);
-        int n_nav = 0;
-        for (int w = 0; w < W; w++) {
-            const OnBatchWindow win{solver, solver.addWindow()};
-            Win &V      = wins[(size_t) w];
-            const int K = V.K;
-            double *P = V.pose.data(), *M = V.mix.data();
-            for (int k = 0; k < K; k++) win.addParameterBlock(P + 7 * (size_t) k, 7, true), win.addParameterBlock(M + (size_t) mw * k, mw);
-            win.addParameterBlock(ext[w], 7, true);
-            for (int l = 0; l < n_lm[w]; l++) win.addParameterBlock(invdepth[w] + l, 1);
-            win.addParameterBlock(td + w, 1);
-            win.setParameterBlockConstant(ext[w]);
-            win.setParameterBlockConstant(td + w);
-            for (int k = 0; state_const && state_const[w] && k < K; k++)
-                if (state_const[w][k]) win.setParameterBlockConstant(P + 7 * (size_t) k), win.setParameterBlockConstant(M + (size_t) mw * k);
-            reprojections_from_soa(obs_soa[w], n_fac[w], 0, n_fac[w], idx_i[w], idx_j[w], idx_lm[w], P, ext[w], invdepth[w], td + w, factors, window_add(solver, win.w));
-            for (int k = 0; k + 1 < K; k++) {
-                const vector<double *> blocks{P + 7 * (size_t) k, M + (size_t) mw * k, P + 7 * (size_t) (k + 1), M + (size_t) mw * (k + 1)};
-                if (odo)
-                    win.addResidualBlock(std::make_shared<PreintegrationOdoFactor>(V.pre_odo[(size_t) k]), nullptr, blocks);
-                else
-                    win.addResidualBlock(std::make_shared<PreintegrationFactor>(V.pre[(size_t) k]), nullptr, blocks);
-            }
-            if (nav_factors) {
-                double pose_std[6];
-                for (double &v : pose_std) v = 1.0 / prior_weight;
-                win.addResidualBlock(std::make_shared<ImuPosePriorFactor>(prior_pose0[w], pose_std), nullptr, {P}), n_nav++;
-            } else
-                pose_prior(win, P, prior_pose0[w], prior_weight);
-            if (prior_r && prior_r[w] > 0) {
-                // (between the two ordinary priors: a resident prior is not the window's last host block)
-                vector<double *> blocks;
-                for (int b = 0; b < prior_nb[w]; b++) {
-                    const int code = prior_param[w][b], k = code / 2;
-                    if (code < 0 || k >= K || prior_size[w][b] != (code % 2 ? mw : 7)) {
-                        set_err(err, errlen, ("window " + std::to_string(w) + ": prior block " + std::to_string(b) + " does not name a pose or mix block").c_str());
-                        return -1;
-                    }
-                    blocks.push_back(code % 2 ? M + (size_t) mw * k : P + 7 * (size_t) k);
-                }
-                prior_id[(size_t) w] = win.addResidualBlock(
-                    std::make_shared<ArrayPriorFactor>(prior_r[w], prior_nb[w], prior_size[w], prior_index[w], prior_x0[w], prior_J0[w], prior_e0[w]), nullptr, blocks);
-            }
-            if (!nav_factors) {
-                if (odo)
-                    win.addResidualBlock(std::make_shared<OdoMixPriorFactor>(prior_mix0[w], prior_weight), nullptr, {M});
-                else
-                    win.addResidualBlock(std::make_shared<MixPriorFactor>(prior_mix0[w], prior_weight), nullptr, {M});
-                continue;
-            }
-            win.addResidualBlock(std::make_shared<ImuMixPriorFactor>(prior_mix0[w], std_w.data(), variant), nullptr, {M}), n_nav++;
-            win.addResidualBlock(std::make_shared<ImuErrorFactor>(variant), nullptr, {M + (size_t) mw * (K - 1)}), n_nav++;
-            std::shared_ptr<ceres::LossFunction> loss;
-            if (gnss_huber && gnss_huber[w] != 0) loss = std::make_shared<ceres::HuberLoss>(gnss_huber[w]);
-            for (int k = 0; k < K; k++) {
-                GNSS g;
-                const double *b = gnss_blh[w] + 3 * (size_t) k;
-                g.blh = Vector3d(b[0], b[1], b[2]), g.std = Vector3d(gnss_std3[0], gnss_std3[1], gnss_std3[2]);
-                win.addResidualBlock(std::make_shared<GnssFactor>(g, Vector3d(gnss_lever3[0], gnss_lever3[1], gnss_lever3[2])), loss, {P + 7 * (size_t) k}), n_nav++;
-            }
-        }
-        auto prior_costs = [&](int at) {
-            for (int w = 0; w < W && prior_cost; w++) {
-                prior_cost[2 * (size_t) w + at] = 0.0;
-                if (prior_id[(size_t) w] >= 0 && !solver.evaluateResidualBlock(w, prior_id[(size_t) w], false, prior_cost + 2 * (size_t) w + at)) return false;
-            }
-            return true;
-        };
-        if (!solver.prepare() || !prior_costs(0)) {
-            set_err(err, errlen, solver.error().empty() ? "a prior failed to evaluate" : solver.error().c_str());
-            return -5;
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        WindowSolverBatch::Options opt;
-        vector<WindowSolverBatch::Summary> sum;
-        opt.max_num_iterations = iters;
-        if (!solver.solve(opt, &sum)) {
-            set_err(err, errlen, solver.error().c_str());
-            return -3;
-        }
-        if (solve_ms) *solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        if (nav_on_device) *nav_on_device = solver.navFactorsOnDevice();
-        if (!prior_costs(1)) {
-            set_err(err, errlen, "a prior failed to evaluate");
-            return -5;
-        }
-        for (int w = 0; w < W; w++) {
-            put_summary4(sum[(size_t) w], summary4 + 4 * (size_t) w);
-            const Win &V = wins[(size_t) w];
-            for (int k = 0; k < V.K; k++)
-                memcpy(states[w] + sw * (size_t) k, &V.pose[7 * (size_t) k], sizeof(double) * 7),
-                    memcpy(states[w] + sw * (size_t) k + 7, &V.mix[(size_t) mw * k], sizeof(double) * (size_t) mw);
-        }
-        return 0;
+        const VioBatchArgs a{W,       variant,  n_intervals, offsets,  imu,      params9,  delta,       jac,      cov,      dt,           iewn,
+                             pn_off,  pn,       params19,    states,   n_fac,    obs_soa,  idx_i,       idx_j,    idx_lm,   ext,          n_lm,
+                             invdepth, td,      prior_pose0, prior_mix0, prior_weight, huber, iters,    prior_r,  prior_nb, prior_size,   prior_index,
+                             prior_param, prior_x0, prior_J0, prior_e0, nullptr, nullptr,  state_const, nav_factors, gnss_blh, gnss_std3, gnss_lever3,
+                             gnss_huber, summary4, prior_cost, solve_ms, nullptr, nullptr, nav_on_device};
+        return solve_vio_windows(a, mode, without_parts, device_nav != 0, err, errlen);
     });
 }
 

@@ -1,7 +1,7 @@
 // C entry points of libicgvins_host.so: the preintegration factor with its trigonometric part split out (Preintegration::evaluateGiven), for
 // tests that feed the device's resident evaluation (icg_preint_set / icg_preint_evaluate_resident) from the host's own values.
 //
-// and WindowSolverBatch::setDevicePreintegration on the windows of icgh_backend_solve_prior_batch (solve_prior_windows, capi_solve_windows.h).
+// and WindowSolverBatch::setDevicePreintegration on the windows of icgh_backend_solve_prior_batch (solve_vio_windows, capi_solve_windows.h).
 #include <memory>
 #include <string>
 
@@ -99,33 +99,12 @@ int icgh_backend_solve_preint_batch(int W, const int32_t *n_intervals, const int
                                  "preintegration) or 5 (mode 3 and device preintegration); variant 0 (Normal) or 1 (Earth)");
             return -1;
         }
-        const bool prior = mode == 3 || mode == 5, preint = mode >= 4;
-        // (the entry a mode adds is named first: a build without any of them says what that mode itself is missing)
-        if (preint && !WindowSolverBatch::devicePreintegrationAvailable()) {
-            set_err(err, errlen, (std::string(WindowSolverBatch::devicePreintegrationMissing()) + " is not in this build").c_str());
-            return -4;
-        }
-        if (prior && !WindowSolverBatch::devicePriorAvailable()) {
-            set_err(err, errlen, MarginalizationPriorSet::residentAvailable() ? "icg_reproj_host_parts_build_prior is not in this build"
-                                                                              : "icg_marg_prior_evaluate_resident is not in this build");
-            return -4;
-        }
-        if (mode >= 2 && !WindowSolverBatch::deviceHostPartAvailable()) {
-            set_err(err, errlen, "icg_reproj_host_parts_build is not in this build");
-            return -4;
-        }
-        if (mode >= 1 && !WindowSolverBatch::deviceReducedSolveAvailable()) {
-            set_err(err, errlen, "icg_reproj_solve_windows is not in this build");
-            return -4;
-        }
-        const PriorWindowArgs a{W,        n_intervals, offsets,     imu,        params9,      states16, n_fac,       obs_soa,  idx_i,    idx_j,    idx_lm,
-                                ext,      n_lm,        invdepth,    td,         prior_pose0,  prior_mix0, prior_weight, huber,  iters,    prior_r,  prior_nb,
-                                prior_size, prior_index, prior_param, prior_x0, prior_J0,     prior_e0, prior_robust, state_const, summary4, prior_cost, solve_ms};
-        PriorWindowSwitches sw;
-        sw.reduced = mode >= 1, sw.host_part = mode >= 2 && !without_parts, sw.prior = prior, sw.preint = preint;
-        sw.variant = variant, sw.preint_robust = preint_robust, sw.preint_on_device = preint_on_device;
-        if (preint_on_device) *preint_on_device = 0;
-        return solve_prior_windows(a, sw, err, errlen);
+        const VioBatchArgs a{W,       variant,  n_intervals, offsets,  imu,      params9,  nullptr,     nullptr,  nullptr,  nullptr,      nullptr,
+                             nullptr, nullptr,  nullptr,     states16, n_fac,    obs_soa,  idx_i,       idx_j,    idx_lm,   ext,          n_lm,
+                             invdepth, td,      prior_pose0, prior_mix0, prior_weight, huber, iters,    prior_r,  prior_nb, prior_size,   prior_index,
+                             prior_param, prior_x0, prior_J0, prior_e0, prior_robust, preint_robust, state_const, 0, nullptr, nullptr,    nullptr,
+                             nullptr, summary4, prior_cost,  solve_ms, preint_on_device, nullptr, nullptr};
+        return solve_vio_windows(a, mode, without_parts, false, err, errlen);
     });
 }
 

@@ -61,7 +61,7 @@ int icgh_backend_preint_odo_eval_split(int n, const int32_t *variant, const doub
     });
 }
 
-// The visual-inertial windows of icgh_backend_solve_preint_batch (solve_prior_windows, capi_solve_windows.h: the same blocks and the same
+// The visual-inertial windows of icgh_backend_solve_preint_batch (solve_vio_windows, capi_solve_windows.h: the same blocks and the same
 // order of the residual blocks) with 17-wide states (p3, q4 xyzw, v3, bg3, ba3, sodo), 10-wide mix blocks and PreintegrationOdoFactors.
 // The integration results are GIVEN, per window w and interval k of it (n_intervals[w] intervals between its n_intervals[w] + 1 states):
 // delta[w] 20 per interval, jac[w] and cov[w] 361, dt[w] 1, iewn[w] 3, in icg_preint_odo_batch's layout; pn[w] rows of 4 with pn_off[w]
@@ -93,128 +93,13 @@ int icgh_backend_solve_preint_odo_batch(int W, const int32_t *n_intervals, const
                                  "preintegration) or 5 (mode 3 and device preintegration); variant 2 (Odo) or 3 (EarthOdo)");
             return -1;
         }
-        const bool prior = mode == 3 || mode == 5, preint = mode >= 4;
         if (odo_on_device) *odo_on_device = 0;
-        // (the entry a mode adds is named first: a build without any of them says what that mode itself is missing)
-        if (preint && WindowSolverBatch::devicePreintegrationOdoMissing()) {
-            set_err(err, errlen, (std::string(WindowSolverBatch::devicePreintegrationOdoMissing()) + " is not in this build").c_str());
-            return -4;
-        }
-        if (preint && !WindowSolverBatch::devicePreintegrationAvailable()) {
-            set_err(err, errlen, (std::string(WindowSolverBatch::devicePreintegrationMissing()) + " is not in this build").c_str());
-            return -4;
-        }
-        if (prior && !WindowSolverBatch::devicePriorAvailable()) {
-            set_err(err, errlen, MarginalizationPriorSet::residentAvailable() ? "icg_reproj_host_parts_build_prior is not in this build"
-                                                                              : "icg_marg_prior_evaluate_resident is not in this build");
-            return -4;
-        }
-        if (mode >= 2 && !WindowSolverBatch::deviceHostPartAvailable()) {
-            set_err(err, errlen, "icg_reproj_host_parts_build is not in this build");
-            return -4;
-        }
-        if (mode >= 1 && !WindowSolverBatch::deviceReducedSolveAvailable()) {
-            set_err(err, errlen, "icg_reproj_solve_windows is not in this build");
-            return -4;
-        }
-        auto params = odo_params19(params19);
-        TempCtx T(0);
-        struct Win {
-            int K;
-            vector<double> pose, mix;
-            vector<std::shared_ptr<PreintegrationOdo>> pre;
-        };
-        vector<Win> wins((size_t) W);
-        for (int w = 0; w < W; w++) {
-            Win &V = wins[(size_t) w];
-            V.K    = n_intervals[w] + 1;
-            V.pose.resize((size_t) V.K * 7), V.mix.resize((size_t) V.K * 10);
-            for (int k = 0; k < V.K; k++)
-                memcpy(&V.pose[7 * (size_t) k], states17[w] + 17 * (size_t) k, sizeof(double) * 7), memcpy(&V.mix[10 * (size_t) k], states17[w] + 17 * (size_t) k + 7, sizeof(double) * 10);
-            for (int k = 0; k < n_intervals[w]; k++) {
-                const size_t j = (size_t) k;
-                const int rows = variant == 3 && pn_off && pn_off[w] ? pn_off[w][k + 1] - pn_off[w][k] : 0;
-                V.pre.push_back(odo_from_result(params, variant, delta[w] + 20 * j, jac[w] + 361 * j, cov[w] + 361 * j, dt[w][j],
-                                                rows > 0 ? pn[w] + 4 * (size_t) pn_off[w][k] : nullptr, rows, iewn[w] + 3 * j));
-            }
-        }
-        vector<std::unique_ptr<ReprojectionFactor>> factors;
-        WindowSolverBatch solver(0, huber);
-        solver.setDeviceReducedSolve(mode >= 1);
-        solver.setDeviceHostPart(mode >= 2 && !without_parts);
-        solver.setDevicePrior(prior);
-        solver.setDevicePreintegration(preint);
-        vector<int> prior_id((size_t) W, -1);
-        for (int w = 0; w < W; w++) {
-            const OnBatchWindow win{solver, solver.addWindow()};
-            Win &V    = wins[(size_t) w];
-            const int K = V.K;
-            double *P = V.pose.data(), *M = V.mix.data();
-            for (int k = 0; k < K; k++) win.addParameterBlock(P + 7 * (size_t) k, 7, true), win.addParameterBlock(M + 10 * (size_t) k, 10);
-            win.addParameterBlock(ext[w], 7, true);
-            for (int l = 0; l < n_lm[w]; l++) win.addParameterBlock(invdepth[w] + l, 1);
-            win.addParameterBlock(td + w, 1);
-            win.setParameterBlockConstant(ext[w]);
-            win.setParameterBlockConstant(td + w);
-            for (int k = 0; state_const && state_const[w] && k < K; k++)
-                if (state_const[w][k]) win.setParameterBlockConstant(P + 7 * (size_t) k), win.setParameterBlockConstant(M + 10 * (size_t) k);
-            reprojections_from_soa(obs_soa[w], n_fac[w], 0, n_fac[w], idx_i[w], idx_j[w], idx_lm[w], P, ext[w], invdepth[w], td + w, factors, window_add(solver, win.w));
-            std::shared_ptr<ceres::LossFunction> preint_loss;
-            if (preint_robust && preint_robust[w] != 0) preint_loss = std::make_shared<HuberLossHip>(preint_robust[w]);
-            for (int k = 0; k + 1 < K; k++)
-                win.addResidualBlock(std::make_shared<PreintegrationOdoFactor>(V.pre[(size_t) k]), preint_loss,
-                                     {P + 7 * (size_t) k, M + 10 * (size_t) k, P + 7 * (size_t) (k + 1), M + 10 * (size_t) (k + 1)});
-            pose_prior(win, P, prior_pose0[w], prior_weight);
-            if (prior_r && prior_r[w] > 0) {
-                // (between the two ordinary priors: a resident prior is not the window's last host block)
-                vector<double *> blocks;
-                for (int b = 0; b < prior_nb[w]; b++) {
-                    const int code = prior_param[w][b], k = code / 2;
-                    if (code < 0 || k >= K || prior_size[w][b] != (code % 2 ? 10 : 7)) {
-                        set_err(err, errlen, ("window " + std::to_string(w) + ": prior block " + std::to_string(b) + " does not name a pose (7) or mix (10) block").c_str());
-                        return -1;
-                    }
-                    blocks.push_back(code % 2 ? M + 10 * (size_t) k : P + 7 * (size_t) k);
-                }
-                std::shared_ptr<ceres::LossFunction> loss;
-                if (prior_robust && prior_robust[w] != 0) loss = std::make_shared<HuberLossHip>(prior_robust[w]);
-                prior_id[(size_t) w] = win.addResidualBlock(
-                    std::make_shared<ArrayPriorFactor>(prior_r[w], prior_nb[w], prior_size[w], prior_index[w], prior_x0[w], prior_J0[w], prior_e0[w]), loss, blocks);
-            }
-            win.addResidualBlock(std::make_shared<OdoMixPriorFactor>(prior_mix0[w], prior_weight), nullptr, {M});
-        }
-        auto prior_costs = [&](int at) {
-            for (int w = 0; w < W && prior_cost; w++) {
-                prior_cost[2 * (size_t) w + at] = 0.0;
-                if (prior_id[(size_t) w] >= 0 && !solver.evaluateResidualBlock(w, prior_id[(size_t) w], false, prior_cost + 2 * (size_t) w + at)) return false;
-            }
-            return true;
-        };
-        if (!solver.prepare() || !prior_costs(0)) {
-            set_err(err, errlen, solver.error().empty() ? "a prior failed to evaluate" : solver.error().c_str());
-            return -5;
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        WindowSolverBatch::Options opt;
-        vector<WindowSolverBatch::Summary> sum;
-        opt.max_num_iterations = iters;
-        if (!solver.solve(opt, &sum)) {
-            set_err(err, errlen, solver.error().c_str());
-            return -3;
-        }
-        if (solve_ms) *solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        if (odo_on_device) *odo_on_device = solver.odometerPreintegrationsOnDevice();
-        if (!prior_costs(1)) {
-            set_err(err, errlen, "a prior failed to evaluate");
-            return -5;
-        }
-        for (int w = 0; w < W; w++) {
-            put_summary4(sum[(size_t) w], summary4 + 4 * (size_t) w);
-            const Win &V = wins[(size_t) w];
-            for (int k = 0; k < V.K; k++)
-                memcpy(states17[w] + 17 * (size_t) k, &V.pose[7 * (size_t) k], sizeof(double) * 7), memcpy(states17[w] + 17 * (size_t) k + 7, &V.mix[10 * (size_t) k], sizeof(double) * 10);
-        }
-        return 0;
+        const VioBatchArgs a{W,       variant,  n_intervals, nullptr,  nullptr,  nullptr,  delta,       jac,      cov,      dt,           iewn,
+                             pn_off,  pn,       params19,    states17, n_fac,    obs_soa,  idx_i,       idx_j,    idx_lm,   ext,          n_lm,
+                             invdepth, td,      prior_pose0, prior_mix0, prior_weight, huber, iters,    prior_r,  prior_nb, prior_size,   prior_index,
+                             prior_param, prior_x0, prior_J0, prior_e0, prior_robust, preint_robust, state_const, 0, nullptr, nullptr,    nullptr,
+                             nullptr, summary4, prior_cost,  solve_ms, nullptr,  odo_on_device, nullptr};
+        return solve_vio_windows(a, mode, without_parts, false, err, errlen);
     });
 }
 

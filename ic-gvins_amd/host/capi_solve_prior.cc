@@ -1,6 +1,7 @@
 // C entry point of libicgvins_host.so for WindowSolverBatch::setDevicePrior: a batch of visual-inertial windows, each optionally with a
 // marginalization prior given as plain arrays, solved with the prior on the host pool or resident on the device.  For tests and probes.
-// The windows are built and solved by solve_prior_windows (capi_solve_windows.h), shared with capi_solve_preint.cc.
+// The windows are built and solved by solve_vio_windows (capi_solve_windows.h), shared with the entries of capi_solve_preint.cc,
+// capi_solve_preint_odo.cc and capi_solve_nav.cc.
 #include "capi_solve_windows.h"
 
 using namespace icg;
@@ -34,26 +35,12 @@ int icgh_backend_solve_prior_batch(int W, const int32_t *n_intervals, const int3
             set_err(err, errlen, "mode must be 0 (host), 1 (device reduced solve), 2 (and device host part) or 3 (and device prior)");
             return -1;
         }
-        // (the entry a mode adds is named first: a build without any of them says what that mode itself is missing)
-        if (mode == 3 && !WindowSolverBatch::devicePriorAvailable()) {
-            set_err(err, errlen, MarginalizationPriorSet::residentAvailable() ? "icg_reproj_host_parts_build_prior is not in this build"
-                                                                              : "icg_marg_prior_evaluate_resident is not in this build");
-            return -4;
-        }
-        if (mode >= 2 && !WindowSolverBatch::deviceHostPartAvailable()) {
-            set_err(err, errlen, "icg_reproj_host_parts_build is not in this build");
-            return -4;
-        }
-        if (mode >= 1 && !WindowSolverBatch::deviceReducedSolveAvailable()) {
-            set_err(err, errlen, "icg_reproj_solve_windows is not in this build");
-            return -4;
-        }
-        const PriorWindowArgs a{W,        n_intervals, offsets,     imu,        params9,      states16, n_fac,       obs_soa,  idx_i,    idx_j,    idx_lm,
-                                ext,      n_lm,        invdepth,    td,         prior_pose0,  prior_mix0, prior_weight, huber,  iters,    prior_r,  prior_nb,
-                                prior_size, prior_index, prior_param, prior_x0, prior_J0,     prior_e0, prior_robust, state_const, summary4, prior_cost, solve_ms};
-        PriorWindowSwitches sw;
-        sw.reduced = mode >= 1, sw.host_part = mode >= 2 && !without_parts, sw.prior = mode == 3;
-        return solve_prior_windows(a, sw, err, errlen);
+        const VioBatchArgs a{W,       0,        n_intervals, offsets,  imu,      params9,  nullptr,     nullptr,  nullptr,  nullptr,      nullptr,
+                             nullptr, nullptr,  nullptr,     states16, n_fac,    obs_soa,  idx_i,       idx_j,    idx_lm,   ext,          n_lm,
+                             invdepth, td,      prior_pose0, prior_mix0, prior_weight, huber, iters,    prior_r,  prior_nb, prior_size,   prior_index,
+                             prior_param, prior_x0, prior_J0, prior_e0, prior_robust, nullptr, state_const, 0,     nullptr,  nullptr,      nullptr,
+                             nullptr, summary4, prior_cost,  solve_ms, nullptr,  nullptr,  nullptr};
+        return solve_vio_windows(a, mode, without_parts, false, err, errlen);
     });
 }
 

@@ -152,20 +152,22 @@ void reprojections_from_soa(const double *obs_soa, int n, int f0, int f1, const 
     }
 }
 
-// ---- the visual-inertial window: K = n_intervals + 1 states of a pose (7) and a mix (9: velocity, biases) block ------------------------
+// ---- the visual-inertial window: K = n_intervals + 1 states of a pose (7) and a mix block (mw = 9: velocity, biases; 10 with the odometer scale
+// behind them, the windows of the odometer factors) -----------------------------------------------------------------------------------------
 struct VioWindow {
-    int K = 0;
+    int K = 0, mw = 9;
     std::vector<double> pose, mix;
-    std::vector<std::shared_ptr<icg::Preintegration>> pre; // interval k from its start state
-    // states16: K rows of p3, q4 xyzw, v3, bg3, ba3
-    void take(const double *states16) {
-        pose.resize((size_t) K * 7), mix.resize((size_t) K * 9);
-        for (int k = 0; k < K; k++)
-            memcpy(&pose[7 * (size_t) k], states16 + 16 * (size_t) k, sizeof(double) * 7), memcpy(&mix[9 * (size_t) k], states16 + 16 * (size_t) k + 7, sizeof(double) * 9);
+    std::vector<std::shared_ptr<icg::Preintegration>> pre;        // interval k from its start state (mw = 9) ...
+    std::vector<std::shared_ptr<icg::PreintegrationOdo>> pre_odo; // ... or its given odometer integration result (mw = 10)
+    double *P(int k) { return &pose[7 * (size_t) k]; }
+    double *M(int k) { return &mix[(size_t) mw * k]; }
+    // states: K rows of p3, q4 xyzw and the mix block (v3, bg3, ba3[, sodo])
+    void take(const double *states) {
+        pose.resize((size_t) K * 7), mix.resize((size_t) K * mw);
+        for (int k = 0; k < K; k++) memcpy(P(k), states + (size_t) (7 + mw) * k, sizeof(double) * 7), memcpy(M(k), states + (size_t) (7 + mw) * k + 7, sizeof(double) * mw);
     }
-    void put(double *states16) const {
-        for (int k = 0; k < K; k++)
-            memcpy(states16 + 16 * (size_t) k, &pose[7 * (size_t) k], sizeof(double) * 7), memcpy(states16 + 16 * (size_t) k + 7, &mix[9 * (size_t) k], sizeof(double) * 9);
+    void put(double *states) {
+        for (int k = 0; k < K; k++) memcpy(states + (size_t) (7 + mw) * k, P(k), sizeof(double) * 7), memcpy(states + (size_t) (7 + mw) * k + 7, M(k), sizeof(double) * mw);
     }
 };
 // the window's states and its preintegration objects (imu rows of 8, interval k owns rows [offsets[k], offsets[k+1])), each also appended to
@@ -186,8 +188,8 @@ VioWindow vio_window(int n_intervals, const int32_t *offsets, const double *imu,
 template <class S>
 void vio_blocks(S &&s, VioWindow &W, double *ext, int n_lm, double *invdepth, double *td) {
     for (int k = 0; k < W.K; k++) {
-        s.addParameterBlock(&W.pose[7 * (size_t) k], 7, true);
-        s.addParameterBlock(&W.mix[9 * (size_t) k], 9);
+        s.addParameterBlock(W.P(k), 7, true);
+        s.addParameterBlock(W.M(k), W.mw);
     }
     s.addParameterBlock(ext, 7, true);
     for (int l = 0; l < n_lm; l++) s.addParameterBlock(invdepth + l, 1);
@@ -195,20 +197,31 @@ void vio_blocks(S &&s, VioWindow &W, double *ext, int n_lm, double *invdepth, do
     s.setParameterBlockConstant(ext);
     s.setParameterBlockConstant(td);
 }
-// The window's host factors come in two parts, so that an entry can put a block of its own between them or behind them: the preintegration
-// factors (optionally behind a loss function) and the pose prior on state 0, ...
+// The window's host factors come in parts, so that an entry can put a block of its own between them or behind them: the preintegration
+// factors of the window's kind (optionally behind a loss function), ...
+template <class S>
+void vio_preint_factors(S &&s, VioWindow &W, std::shared_ptr<ceres::LossFunction> preint_loss = nullptr) {
+    for (int k = 0; k + 1 < W.K; k++) {
+        const std::vector<double *> blocks{W.P(k), W.M(k), W.P(k + 1), W.M(k + 1)};
+        if (W.mw == 10)
+            s.addResidualBlock(std::make_shared<icg::PreintegrationOdoFactor>(W.pre_odo[(size_t) k]), preint_loss, blocks);
+        else
+            s.addResidualBlock(std::make_shared<icg::PreintegrationFactor>(W.pre[(size_t) k]), preint_loss, blocks);
+    }
+}
+// ... with the pose prior on state 0 behind them, ...
 template <class S>
 void vio_motion_factors(S &&s, VioWindow &W, const double *prior_pose0, double prior_weight, std::shared_ptr<ceres::LossFunction> preint_loss = nullptr) {
-    using icg::PreintegrationFactor;
-    for (int k = 0; k + 1 < W.K; k++)
-        s.addResidualBlock(std::make_shared<PreintegrationFactor>(W.pre[(size_t) k]), preint_loss,
-                           {&W.pose[7 * (size_t) k], &W.mix[9 * (size_t) k], &W.pose[7 * (size_t) (k + 1)], &W.mix[9 * (size_t) (k + 1)]});
-    pose_prior(s, &W.pose[0], prior_pose0, prior_weight);
+    vio_preint_factors(s, W, preint_loss);
+    pose_prior(s, W.P(0), prior_pose0, prior_weight);
 }
-// ... and the velocity / bias prior on state 0
+// ... and the velocity / bias (/ odometer scale) prior on state 0
 template <class S>
 void vio_mix_prior(S &&s, VioWindow &W, const double *prior_mix0, double prior_weight) {
-    s.addResidualBlock(std::make_shared<MixPriorFactor>(prior_mix0, prior_weight), nullptr, {&W.mix[0]});
+    if (W.mw == 10)
+        s.addResidualBlock(std::make_shared<OdoMixPriorFactor>(prior_mix0, prior_weight), nullptr, {W.M(0)});
+    else
+        s.addResidualBlock(std::make_shared<MixPriorFactor>(prior_mix0, prior_weight), nullptr, {W.M(0)});
 }
 
 // ---- views and summaries --------------------------------------------------------------------------------------------------------------

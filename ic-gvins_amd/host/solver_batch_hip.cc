@@ -26,20 +26,15 @@
 
 namespace icg {
 
+// the first entry a family lacks in this build: one of its set's, or its host-part entry
+template <class Set> static const char *missingFor(bool has_entry, const char *entry) { return !Set::available() ? Set::missingEntry() : has_entry ? nullptr : entry; }
 const char *WindowSolverBatch::devicePreintegrationMissing() {
-    if (!PreintegrationSet::available()) return PreintegrationSet::missingEntry();
-    return &icg_reproj_host_parts_build_preint == nullptr ? "icg_reproj_host_parts_build_preint" : nullptr;
+    return missingFor<PreintegrationSet>(&icg_reproj_host_parts_build_preint != nullptr, "icg_reproj_host_parts_build_preint");
 }
-
 const char *WindowSolverBatch::devicePreintegrationOdoMissing() {
-    if (!PreintegrationOdoSet::available()) return PreintegrationOdoSet::missingEntry();
-    return &icg_reproj_host_parts_build_preint_odo == nullptr ? "icg_reproj_host_parts_build_preint_odo" : nullptr;
+    return missingFor<PreintegrationOdoSet>(&icg_reproj_host_parts_build_preint_odo != nullptr, "icg_reproj_host_parts_build_preint_odo");
 }
-
-const char *WindowSolverBatch::deviceNavFactorsMissing() {
-    if (!NavFactorSet::available()) return NavFactorSet::missingEntry();
-    return &icg_reproj_host_parts_build_nav == nullptr ? "icg_reproj_host_parts_build_nav" : nullptr;
-}
+const char *WindowSolverBatch::deviceNavFactorsMissing() { return missingFor<NavFactorSet>(&icg_reproj_host_parts_build_nav != nullptr, "icg_reproj_host_parts_build_nav"); }
 
 bool WindowSolverBatch::devicePreintegrationAvailable() { return devicePreintegrationMissing() == nullptr; }
 
@@ -52,6 +47,21 @@ bool WindowSolverBatch::deviceReducedSolveAvailable() {
 bool WindowSolverBatch::deviceHostPartAvailable() { return &icg_reproj_host_parts_build != nullptr; }
 
 bool WindowSolverBatch::devicePriorAvailable() { return &icg_reproj_host_parts_build_prior != nullptr && MarginalizationPriorSet::residentAvailable(); }
+
+// What differs between the families of resident residuals; the table is rules(), behind Run.  A new family is an entry there, a value of Family, its set among
+// the members and the case for its C entry in buildHostParts().
+struct WindowSolverBatch::FamilyRules {
+    bool WindowSolverBatch::*enabled; // its switch
+    bool (*joins)(const solver_detail::Residual &R, int taken, std::string *err); // layout(): may R join, `taken` members being in its window already?  (*err set: no layout)
+    const int *(*firstColumns)(const solver_detail::Residual &R); // per parameter block of a member, where its columns begin in the member's source matrix
+    int64_t jac_from; // hostHalfOfWindow(): the jac_off of a resident block, ...
+    bool once;        // ... at the window's first rebuild of a solve only (its Jacobian is kept afterwards) or at every one
+    const char *entry;        // the narrowest host-part entry that serves it
+    const char *(*missing)(); // optional: what a solve with members of the family lacks in this build, asked at its head
+    bool (*set)(WindowSolverBatch &S, Run &R);                           // head of solve(): the members become resident
+    void (*pack)(WindowSolverBatch &S, size_t k, double *const *blocks); // member k's evaluation point from its parameter blocks
+    bool (*evaluate)(WindowSolverBatch &S, Run &R, bool want_jac);       // R.sq of the family, and whatever else the family does once it is evaluated
+};
 
 WindowSolverBatch::WindowSolverBatch(int device, double huber_delta, int host_threads)
     : factors_(device, host_threads, "WindowSolverBatch"), huber_(huber_delta) {}
@@ -135,46 +145,24 @@ bool WindowSolverBatch::layout() {
         W.host_blocks.clear(), W.host_cols.clear();
         W.resident_of_residual.assign(W.problem.residuals.size(), {}), W.resident_of_block.clear();
         for (std::vector<int32_t> &c : W.resident_cols) c.clear();
-        int count[kFamilies] = {0, 0, 0, 0}; // (the window's own: the set indices follow once all windows are laid out)
+        int count[kFamilies] = {}; // (the window's own: the set indices follow once all windows are laid out)
         std::vector<int> cols;
         for (size_t id = 0; id < W.problem.residuals.size(); id++) {
             const solver_detail::Residual &R = W.problem.residuals[id];
             if (R.removed) continue;
             Window::Resident &res = W.resident_of_residual[id];
-            // device prior: the window's first prior without a loss (a robustified prior and a second prior stay on the pool)
-            const MargPriorSource *src = device_prior_ && count[kPrior] == 0 && !R.loss ? dynamic_cast<const MargPriorSource *>(R.cost.get()) : nullptr;
-            const MargPriorView *v     = src ? &src->margPriorView() : nullptr;
-            if (v) {
-                const auto &sizes = R.cost->parameter_block_sizes();
-                bool fits         = v->r == R.cost->num_residuals() && v->n_blocks == (int) sizes.size();
-                for (int b = 0; fits && b < v->n_blocks; b++) fits = v->size[b] == sizes[(size_t) b];
-                if (!fits) {
-                    errs[w] = "a marginalization prior's view does not describe its residual block";
-                    return;
-                }
-                res = {kPrior, count[kPrior]++};
-            }
-            // device preintegration: a factor without a loss whose integration result is there and can be whitened
-            const PreintegrationFactor *pf = device_preint_ && !R.loss ? dynamic_cast<const PreintegrationFactor *>(R.cost.get()) : nullptr;
-            if (pf && pf->preintegration().ready() && R.blocks.size() == 4) res = {kPreint, count[kPreint]++};
-            // the odometer variants behind the same switch: their own resident set (19 residuals, a 19 x 34 Jacobian)
-            const PreintegrationOdoFactor *of = device_preint_ && !R.loss && !pf ? dynamic_cast<const PreintegrationOdoFactor *>(R.cost.get()) : nullptr;
-            if (of && of->preintegration().ready() && R.blocks.size() == 4) res = {kPreintOdo, count[kPreintOdo]++};
-            // device navigation factors: one parameter block of the factor's own width; a loss is allowed (corrected where the factor is evaluated)
-            const NavFactor *nf = device_nav_ && res.family == kNone ? dynamic_cast<const NavFactor *>(R.cost.get()) : nullptr;
-            if (nf && R.blocks.size() == 1 && R.cost->parameter_block_sizes().size() == 1 && R.cost->parameter_block_sizes()[0] == nf->navWidth() &&
-                R.cost->num_residuals() == nf->navResiduals())
-                res = {kNav, count[kNav]++};
+            for (int f = 0; f < kFamilies && res.family == kNone && errs[w].empty(); f++) // the first family, of those switched on, whose rule takes the residual
+                if (this->*rules(f).enabled && rules(f).joins(R, count[f], &errs[w])) res = {f, count[f]++};
+            if (!errs[w].empty()) return;
             solver_detail::hostBlockColumns(W.problem, R, cols);
             if (cols.empty()) continue;
             W.resident_of_block.push_back(res);
             // a resident block's columns of its source matrix: the free local columns of its non-constant parameter blocks in block order, the
-            // columns gatherHostBlock selects, counted in the prior's J0 or in the factor's 15 x 32 (7 | 9 | 7 | 9) or 19 x 34 (7 | 10 | 7 | 10) Jacobian
-            static const int preint_first[4] = {0, 7, 16, 23}, preint_odo_first[4] = {0, 7, 17, 24};
+            // columns gatherHostBlock selects, counted from where the family's source matrix holds the block
             for (size_t a = 0; res.family != kNone && a < R.blocks.size(); a++) {
                 const solver_detail::Block &A = W.problem.blocks[(size_t) W.problem.block_of.at(R.blocks[a])];
                 if (A.column < 0) continue;
-                const int first = res.family == kPrior ? v->index[a] : res.family == kPreint ? preint_first[a] : res.family == kPreintOdo ? preint_odo_first[a] : 0;
+                const int first = rules(res.family).firstColumns(R)[a];
                 for (int x = 0; x < A.local; x++) W.resident_cols[res.family].push_back(first + x);
             }
             W.host_blocks.push_back({(int) id, R.cost->num_residuals(), (int) cols.size(), 0, 0, 0});
@@ -199,39 +187,22 @@ bool WindowSolverBatch::layout() {
             hp_blk_off_.push_back((int32_t) hp_nr_.size());
         }
         // the resident sets: the windows' priors in window order, the preintegration factors in window and residual order
-        prior_views_.clear(), prior_where_.clear(), hp_prior_cols_.clear();
-        preint_list_.clear(), preint_where_.clear(), hp_preint_cols_.clear();
-        preint_odo_list_.clear(), preint_odo_where_.clear(), hp_preint_odo_cols_.clear();
-        nav_list_.clear(), nav_where_.clear(), hp_nav_cols_.clear();
-        hp_prior_of_.assign(hp_nr_.size(), -1), hp_preint_of_.assign(hp_nr_.size(), -1), hp_preint_odo_of_.assign(hp_nr_.size(), -1);
-        hp_nav_of_.assign(hp_nr_.size(), -1);
+        for (ResidentFamily &F : resident_) F.where.clear(), F.cols.clear(), F.of.assign(hp_nr_.size(), -1);
         for (size_t w = 0; w < windows_.size(); w++) {
-            Window &W                  = windows_[w];
-            const int base[kFamilies] = {(int) prior_views_.size(), (int) preint_list_.size(), (int) preint_odo_list_.size(), (int) nav_list_.size()};
+            Window &W = windows_[w];
+            int base[kFamilies];
+            for (int f = 0; f < kFamilies; f++) base[f] = members(f);
             for (size_t id = 0; id < W.resident_of_residual.size(); id++) {
                 Window::Resident &res = W.resident_of_residual[id];
                 if (res.family == kNone) continue;
                 res.index += base[res.family];
-                const ceres::CostFunction *cost = W.problem.residuals[id].cost.get();
-                if (res.family == kPrior)
-                    prior_views_.push_back(dynamic_cast<const MargPriorSource *>(cost)->margPriorView()), prior_where_.push_back({(int) w, (int) id});
-                else if (res.family == kPreint)
-                    preint_list_.push_back(&static_cast<const PreintegrationFactor *>(cost)->preintegration()), preint_where_.push_back({(int) w, (int) id});
-                else if (res.family == kPreintOdo)
-                    preint_odo_list_.push_back(&static_cast<const PreintegrationOdoFactor *>(cost)->preintegration()), preint_odo_where_.push_back({(int) w, (int) id});
-                else
-                    nav_list_.push_back(dynamic_cast<const NavFactor *>(cost)), nav_where_.push_back({(int) w, (int) id});
+                resident_[res.family].where.push_back({(int) w, (int) id});
             }
             for (size_t k = 0; k < W.resident_of_block.size(); k++) {
                 Window::Resident &res = W.resident_of_block[k];
-                if (res.family == kNone) continue;
-                std::vector<int32_t> &of = res.family == kPrior ? hp_prior_of_ : res.family == kPreint ? hp_preint_of_ : res.family == kPreintOdo ? hp_preint_odo_of_ : hp_nav_of_;
-                of[(size_t) W.blk_begin + k] = (res.index += base[res.family]);
+                if (res.family != kNone) resident_[res.family].of[(size_t) W.blk_begin + k] = (res.index += base[res.family]);
             }
-            hp_prior_cols_.insert(hp_prior_cols_.end(), W.resident_cols[kPrior].begin(), W.resident_cols[kPrior].end());
-            hp_preint_cols_.insert(hp_preint_cols_.end(), W.resident_cols[kPreint].begin(), W.resident_cols[kPreint].end());
-            hp_preint_odo_cols_.insert(hp_preint_odo_cols_.end(), W.resident_cols[kPreintOdo].begin(), W.resident_cols[kPreintOdo].end());
-            hp_nav_cols_.insert(hp_nav_cols_.end(), W.resident_cols[kNav].begin(), W.resident_cols[kNav].end());
+            for (int f = 0; f < kFamilies; f++) resident_[f].cols.insert(resident_[f].cols.end(), W.resident_cols[f].begin(), W.resident_cols[f].end());
         }
     }
     return P_ > 0;
@@ -294,7 +265,7 @@ struct WindowSolverBatch::Run {
     DeviceSolve dev;
     DeviceParts hp;
     // per family of resident residuals: on for this solve (its switch is set and its set has members); r . r of every member at the last evaluated point
-    bool on[kFamilies] = {false, false, false, false};
+    bool on[kFamilies] = {}, any_on = false;
     std::vector<double> sq[kFamilies]; // (a navigation factor with a loss: rho[0] of its r . r, what its place in the host cost takes)
     // navigation factors: the members that carry a loss and, at a linearization, their three corrector scalars
     std::vector<uint8_t> nav_robust;
@@ -304,7 +275,7 @@ struct WindowSolverBatch::Run {
     std::vector<std::vector<double>> res_cost; // deferred(): the cost of every residual of every window as the pool recorded it (a resident one's comes from sq)
     std::vector<uint8_t> gathered;             // the windows whose prior Jacobian was gathered on the device in this solve
     std::string resident_err;                  // what the evaluation of a family failed with (side thread: error_ takes it after the join)
-    bool deferred() const { return on[kPrior] || on[kPreint] || on[kPreintOdo] || on[kNav]; } // a device value takes a residual's place in the host cost: the pool records per residual
+    bool deferred() const { return any_on; } // a device value takes a residual's place in the host cost: the pool records per residual
     bool first = true;                                        // no window has its initial cost yet
     bool all_done = false, any_step = false, any_trial = false; // what solve() decides on after a phase
     BatchClock clk;
@@ -316,6 +287,84 @@ struct WindowSolverBatch::Run {
     bool deviceSolve() const { return path != ReducedPath::HostSolve; }
     bool deviceParts() const { return path == ReducedPath::DeviceSolveDeviceParts; }
 };
+
+// ---- the families, each described once ----------------------------------------------------------------------------------------------------
+using solver_detail::Residual;
+static const MargPriorView &viewOf(const Residual &R) { return dynamic_cast<const MargPriorSource *>(R.cost.get())->margPriorView(); }
+template <class Factor> static bool readyFactor(const Residual &R, int, std::string *) { // a preintegration factor of either kind: no loss, integrated and whitened
+    const auto *f = R.loss ? nullptr : dynamic_cast<const Factor *>(R.cost.get());
+    return f && f->preintegration().ready() && R.blocks.size() == 4;
+}
+template <class Factor> static auto integrationOf(const Residual &M) { return &static_cast<const Factor *>(M.cost.get())->preintegration(); }
+template <int... first> constexpr int kFirstColumns[] = {first...}; // (of a family whose members' blocks begin at the same columns of their source matrices)
+
+const WindowSolverBatch::FamilyRules &WindowSolverBatch::rules(int family) {
+    typedef WindowSolverBatch S;
+    static const auto listOf = [](const S &s, int f, auto get) { // the member list a set takes
+        std::vector<decltype(get(s.member(f, 0)))> list;
+        for (size_t k = 0; k < (size_t) s.members(f); k++) list.push_back(get(s.member(f, k)));
+        return list;
+    };
+    static const FamilyRules table[kFamilies] = {
+        // Marginalization priors: the window's first prior without a loss (a robustified or a second prior stays on the pool).  Source matrix: J0, shipped by set().
+        {&S::device_prior_,
+         [](const Residual &R, int taken, std::string *err) {
+             if (taken || R.loss || !dynamic_cast<const MargPriorSource *>(R.cost.get())) return false;
+             const MargPriorView &v = viewOf(R);
+             const auto &sizes      = R.cost->parameter_block_sizes();
+             if (v.r == R.cost->num_residuals() && v.n_blocks == (int) sizes.size() && std::equal(sizes.begin(), sizes.end(), v.size)) return true;
+             *err = "a marginalization prior's view does not describe its residual block";
+             return false;
+         },
+         [](const Residual &R) -> const int * { return viewOf(R).index; }, ICG_HP_JAC_FROM_PRIOR, true, "icg_reproj_host_parts_build_prior", nullptr,
+         [](S &s, Run &R) { return R.gathered.assign(R.NW, 0), s.prior_set_.set(s.factors_.ctx(), listOf(s, kPrior, [](const Residual &M) { return viewOf(M); }), &s.error_); },
+         [](S &s, size_t k, double *const *blocks) { s.prior_set_.pack(k, blocks); },
+         [](S &s, Run &R, bool) { return s.prior_set_.evaluateResident(R.sq[kPrior].data(), &R.resident_err); }},
+        // Preintegration factors.  Source matrix: the whitened 15 x 32 Jacobian (7 | 9 | 7 | 9).
+        {&S::device_preint_, readyFactor<PreintegrationFactor>, [](const Residual &) -> const int * { return kFirstColumns<0, 7, 16, 23>; }, ICG_HP_JAC_FROM_PREINT, false, "icg_reproj_host_parts_build_preint", nullptr,
+         [](S &s, Run &) { return s.preint_set_.set(s.factors_.ctx(), listOf(s, kPreint, integrationOf<PreintegrationFactor>), &s.error_); },
+         [](S &s, size_t k, double *const *blocks) { s.preint_set_.pack(k, blocks); },
+         [](S &s, Run &R, bool want_jac) { return s.preint_set_.evaluateResident(want_jac, R.sq[kPreint].data(), &R.resident_err); }},
+        // The odometer variants behind the same switch, in a set of their own: 19 x 34 (7 | 10 | 7 | 10).  A solve that holds such a factor needs their entries.
+        {&S::device_preint_, readyFactor<PreintegrationOdoFactor>, [](const Residual &) -> const int * { return kFirstColumns<0, 7, 17, 24>; },
+         ICG_HP_JAC_FROM_PREINT_ODO, false, "icg_reproj_host_parts_build_preint_odo", &S::devicePreintegrationOdoMissing,
+         [](S &s, Run &) { return s.preint_odo_set_.set(s.factors_.ctx(), listOf(s, kPreintOdo, integrationOf<PreintegrationOdoFactor>), &s.error_); },
+         [](S &s, size_t k, double *const *blocks) { s.preint_odo_set_.pack(k, blocks); },
+         [](S &s, Run &R, bool want_jac) { return s.preint_odo_set_.evaluateResident(want_jac, R.sq[kPreintOdo].data(), &R.resident_err); }},
+        // Navigation factors: one parameter block of the factor's own width, which is its source matrix's; a loss is allowed.
+        {&S::device_nav_,
+         [](const Residual &R, int, std::string *) {
+             const auto *nf = dynamic_cast<const NavFactor *>(R.cost.get());
+             return nf && R.blocks.size() == 1 && R.cost->parameter_block_sizes().size() == 1 && R.cost->parameter_block_sizes()[0] == nf->navWidth() &&
+                    R.cost->num_residuals() == nf->navResiduals();
+         },
+         [](const Residual &) -> const int * { return kFirstColumns<0>; }, ICG_HP_JAC_FROM_NAV, false, "icg_reproj_host_parts_build_nav", nullptr,
+         [](S &s, Run &R) { // the members with a loss are marked for the corrector
+             const size_t n = (size_t) s.members(kNav);
+             R.nav_robust.assign(n, 0), R.nav_loss.assign(n, nullptr), R.nav_corr.assign(3 * n, 0.0);
+             for (size_t k = 0; k < n; k++) R.nav_loss[k] = s.member(kNav, k).loss.get(), R.nav_robust[k] = R.nav_loss[k] ? 1 : 0, R.any_nav_robust |= R.nav_loss[k] != nullptr;
+             return s.nav_set_.set(s.factors_.ctx(), listOf(s, kNav, [](const Residual &M) { return dynamic_cast<const NavFactor *>(M.cost.get()); }), &s.error_);
+         },
+         [](S &s, size_t k, double *const *blocks) { s.nav_set_.pack(k, blocks[0]); },
+         [](S &s, Run &R, bool want_jac) {
+             // A member with a loss: rho on the host from its squared norm; rho[0] takes its place in the cost, and at a linearization the corrector's
+             // scalars go up for one correction of what the evaluation kept
+             std::vector<double> &sq = R.sq[kNav];
+             if (!s.nav_set_.evaluateResident(want_jac, sq.data(), &R.resident_err)) return false;
+             for (size_t k = 0; R.any_nav_robust && k < sq.size(); k++) {
+                 if (!R.nav_loss[k]) continue;
+                 double rho[3];
+                 R.nav_loss[k]->Evaluate(sq[k], rho);
+                 if (want_jac) {
+                     const CorrectorScalars cs = correctorScalars(sq[k], rho);
+                     R.nav_corr[3 * k] = cs.sqrt_rho1, R.nav_corr[3 * k + 1] = cs.alpha_sq_norm, R.nav_corr[3 * k + 2] = cs.residual_scaling;
+                 }
+                 sq[k] = rho[0];
+             }
+             return !(want_jac && R.any_nav_robust) || s.nav_set_.correct(R.nav_robust.data(), R.nav_corr.data(), &R.resident_err);
+         }}};
+    return table[family];
+}
 
 bool WindowSolverBatch::fail(const char *what) {
     error_ = std::string(what) + ": " + icg_last_error(factors_.ctx());
@@ -364,36 +413,12 @@ bool WindowSolverBatch::solve(const Options &o, std::vector<Summary> *summaries)
         H.jac_off.assign(hp_nr_.size(), 0), H.has_shipped.assign(hp_nr_.size(), 0);
         H.s.assign(NW * R.P, 0.0), H.diag.assign(NW * R.P, 0.0);
     }
-    if (device_prior_ && !prior_views_.empty()) {
-        // the priors become resident once per solve: J0 crosses the link here and not again
-        if (!prior_set_.set(factors_.ctx(), prior_views_, &error_)) return false;
-        R.on[kPrior] = true;
-        R.sq[kPrior].assign(prior_views_.size(), 0.0), R.gathered.assign(NW, 0);
-    }
-    if (device_preint_ && !preint_list_.empty()) {
-        // the integration results become resident once per solve
-        if (!preint_set_.set(factors_.ctx(), preint_list_, &error_)) return false;
-        R.on[kPreint] = true;
-        R.sq[kPreint].assign(preint_list_.size(), 0.0);
-    }
-    if (device_preint_ && !preint_odo_list_.empty()) {
-        // the odometer factors' integration results likewise, in their own set; a build without its entries refuses by name
-        if (devicePreintegrationOdoMissing()) return refuse(std::string(devicePreintegrationOdoMissing()) + " is not in this build");
-        if (!preint_odo_set_.set(factors_.ctx(), preint_odo_list_, &error_)) return false;
-        R.on[kPreintOdo] = true;
-        R.sq[kPreintOdo].assign(preint_odo_list_.size(), 0.0);
-    }
-    if (device_nav_ && !nav_list_.empty()) {
-        // the navigation factors' kinds and constants become resident once per solve; the members with a loss are marked for the corrector
-        if (!nav_set_.set(factors_.ctx(), nav_list_, &error_)) return false;
-        R.on[kNav] = true;
-        const size_t n = nav_list_.size();
-        R.sq[kNav].assign(n, 0.0), R.nav_robust.assign(n, 0), R.nav_loss.assign(n, nullptr), R.nav_corr.assign(3 * n, 0.0);
-        for (size_t k = 0; k < n; k++) {
-            R.nav_loss[k]   = windows_[(size_t) nav_where_[k].first].problem.residuals[(size_t) nav_where_[k].second].loss.get();
-            R.nav_robust[k] = R.nav_loss[k] ? 1 : 0;
-            R.any_nav_robust |= R.nav_loss[k] != nullptr;
-        }
+    for (int f = 0; f < kFamilies; f++) { // a family that is switched on and has members becomes resident once per solve; a build without its entries refuses by name
+        const FamilyRules &F = rules(f);
+        if (!(this->*F.enabled) || members(f) == 0) continue;
+        if (F.missing && F.missing()) return refuse(std::string(F.missing()) + " is not in this build");
+        if (!F.set(*this, R)) return false;
+        R.on[f] = R.any_on = true, R.sq[f].assign((size_t) members(f), 0.0);
     }
     if (R.deferred()) {
         R.res_cost.resize(NW);
@@ -531,13 +556,7 @@ bool WindowSolverBatch::hostHalfOfWindow(Run &R, size_t w) {
             if (R.deferred()) cost = &R.res_cost[w][id], *cost = 0.0; // per residual: the window's sum waits for the device values
             if (const int family = W.resident_of_residual[id].family; family != kNone) {
                 // evaluated where it is resident: placed only.  A prior's Jacobian is gathered from J0 at the window's first rebuild of the solve and kept, a factor's at every rebuild
-                if (has)
-                    H.jac_off[(size_t) W.blk_begin + next] = family == kPreint      ? ICG_HP_JAC_FROM_PREINT
-                                                             : family == kPreintOdo ? ICG_HP_JAC_FROM_PREINT_ODO
-                                                             : family == kNav       ? ICG_HP_JAC_FROM_NAV
-                                                             : R.gathered[w]        ? -1
-                                                                                    : ICG_HP_JAC_FROM_PRIOR,
-                                                    next++;
+                if (has) H.jac_off[(size_t) W.blk_begin + next++] = rules(family).once && R.gathered[w] ? -1 : rules(family).jac_from;
                 continue;
             }
             double *Jd = has ? &H.J[W.host_blocks[next].J_off] : nullptr;
@@ -565,61 +584,40 @@ bool WindowSolverBatch::hostHalfOfWindow(Run &R, size_t w) {
 // resident residuals: every member's parameter blocks at their places in its set's evaluation point (a preintegration factor's with its correction
 // quaternion), on the driving thread before the phase's device call
 void WindowSolverBatch::packResident(const Run &R) {
-    auto blocks = [&](const std::pair<int, int> &at) { return windows_[(size_t) at.first].problem.residuals[(size_t) at.second].blocks.data(); };
-    for (size_t k = 0; R.on[kPrior] && k < prior_where_.size(); k++) prior_set_.pack(k, blocks(prior_where_[k]));
-    for (size_t k = 0; R.on[kPreint] && k < preint_where_.size(); k++) preint_set_.pack(k, blocks(preint_where_[k]));
-    for (size_t k = 0; R.on[kPreintOdo] && k < preint_odo_where_.size(); k++) preint_odo_set_.pack(k, blocks(preint_odo_where_[k]));
-    for (size_t k = 0; R.on[kNav] && k < nav_where_.size(); k++) nav_set_.pack(k, blocks(nav_where_[k])[0]);
+    for (int f = 0; f < kFamilies; f++)
+        for (size_t k = 0; R.on[f] && k < (size_t) members(f); k++) rules(f).pack(*this, k, member(f, k).blocks.data());
 }
 
-// the resident evaluation of a phase (side thread), one squared norm per member: the priors, then, unless that failed, the preintegration factors,
-// with Jacobians at a linearization and the residual only at a trial point (the cost is all it needs)
+// the resident evaluation of a phase (side thread), one squared norm per member: family after family until one fails, with Jacobians at a
+// linearization and the residual only at a trial point (the cost is all it needs)
 bool WindowSolverBatch::evaluateResident(Run &R, bool want_jac) {
-    if (R.on[kPrior] && !prior_set_.evaluateResident(R.sq[kPrior].data(), &R.resident_err)) return false;
-    if (R.on[kPreint] && !preint_set_.evaluateResident(want_jac, R.sq[kPreint].data(), &R.resident_err)) return false;
-    if (R.on[kPreintOdo] && !preint_odo_set_.evaluateResident(want_jac, R.sq[kPreintOdo].data(), &R.resident_err)) return false;
-    if (!R.on[kNav]) return true;
-    // the navigation factors last.  A member with a loss: rho on the host from its squared norm; rho[0] takes its place in the cost, and at a
-    // linearization the corrector's scalars go up for one correction of what the evaluation kept
-    std::vector<double> &sq = R.sq[kNav];
-    if (!nav_set_.evaluateResident(want_jac, sq.data(), &R.resident_err)) return false;
-    for (size_t k = 0; R.any_nav_robust && k < sq.size(); k++) {
-        if (!R.nav_loss[k]) continue;
-        double rho[3];
-        R.nav_loss[k]->Evaluate(sq[k], rho);
-        if (want_jac) {
-            const CorrectorScalars cs = correctorScalars(sq[k], rho);
-            R.nav_corr[3 * k] = cs.sqrt_rho1, R.nav_corr[3 * k + 1] = cs.alpha_sq_norm, R.nav_corr[3 * k + 2] = cs.residual_scaling;
-        }
-        sq[k] = rho[0];
-    }
-    return !(want_jac && R.any_nav_robust) || nav_set_.correct(R.nav_robust.data(), R.nav_corr.data(), &R.resident_err);
+    for (int f = 0; f < kFamilies; f++)
+        if (R.on[f] && !rules(f).evaluate(*this, R, want_jac)) return false;
+    return true;
 }
 
 // The host-part call of a linearization, by the narrowest entry that serves the families that are on (a C ABI without the wider ones keeps working with the
 // narrower switches).  The resident blocks take their residuals where they are, and their Jacobians at every rebuild (factors) or a window's first (priors).
 bool WindowSolverBatch::buildHostParts(Run &R) {
     Run::DeviceParts &H     = R.hp;
-    const bool prior = R.on[kPrior], preint = R.on[kPreint], odo = R.on[kPreintOdo], nav = R.on[kNav];
-    const int32_t *prior_of = prior ? hp_prior_of_.data() : nullptr, *prior_cols = prior ? hp_prior_cols_.data() : nullptr;
-    const int32_t *preint_of = preint ? hp_preint_of_.data() : nullptr, *preint_cols = preint ? hp_preint_cols_.data() : nullptr;
-    auto call               = [&](auto entry, auto... resident) { // (every entry takes the narrowest one's arguments first)
+    int widest = kNone; // the last family that is on
+    const int32_t *of[kFamilies] = {}, *cols[kFamilies] = {};
+    for (int f = 0; f < kFamilies; f++)
+        if (R.on[f]) of[f] = resident_[f].of.data(), cols[f] = resident_[f].cols.data(), widest = f;
+    auto call = [&](auto entry, auto... resident) { // (every entry takes the narrowest one's arguments first)
         return entry(factors_.ctx(), R.P, R.dev.Pw.data(), R.reassemble.data(), hp_blk_off_.data(), hp_nr_.data(), hp_nf_.data(), hp_cols_.data(), H.jac_off.data(),
                      H.J.data(), H.r.data(), H.s.data(), H.diag.data(), nullptr, resident...);
     };
-    const int32_t *odo_of = odo ? hp_preint_odo_of_.data() : nullptr, *odo_cols = odo ? hp_preint_odo_cols_.data() : nullptr;
-    const int rc = nav      ? call(icg_reproj_host_parts_build_nav, prior_of, prior_cols, preint_of, preint_cols, odo_of, odo_cols, hp_nav_of_.data(), hp_nav_cols_.data())
-                   : odo    ? call(icg_reproj_host_parts_build_preint_odo, prior_of, prior_cols, preint_of, preint_cols, hp_preint_odo_of_.data(), hp_preint_odo_cols_.data())
-                   : preint ? call(icg_reproj_host_parts_build_preint, prior_of, prior_cols, preint_of, preint_cols)
-                   : prior  ? call(icg_reproj_host_parts_build_prior, prior_of, prior_cols)
-                            : call(icg_reproj_host_parts_build);
-    if (rc != ICG_OK)
-        return fail(nav      ? "icg_reproj_host_parts_build_nav"
-                    : odo    ? "icg_reproj_host_parts_build_preint_odo"
-                    : preint ? "icg_reproj_host_parts_build_preint"
-                    : prior  ? "icg_reproj_host_parts_build_prior"
-                             : "icg_reproj_host_parts_build");
-    for (size_t w = 0; w < R.NW && prior; w++) R.gathered[w] |= R.reassemble[w];
+    int rc;
+    switch (widest) { // (the one place outside rules() that names the families: the entries' signatures differ)
+    case kNav: rc = call(icg_reproj_host_parts_build_nav, of[kPrior], cols[kPrior], of[kPreint], cols[kPreint], of[kPreintOdo], cols[kPreintOdo], of[kNav], cols[kNav]); break;
+    case kPreintOdo: rc = call(icg_reproj_host_parts_build_preint_odo, of[kPrior], cols[kPrior], of[kPreint], cols[kPreint], of[kPreintOdo], cols[kPreintOdo]); break;
+    case kPreint: rc = call(icg_reproj_host_parts_build_preint, of[kPrior], cols[kPrior], of[kPreint], cols[kPreint]); break;
+    case kPrior: rc = call(icg_reproj_host_parts_build_prior, of[kPrior], cols[kPrior]); break;
+    default: rc = call(icg_reproj_host_parts_build);
+    }
+    if (rc != ICG_OK) return fail(widest == kNone ? "icg_reproj_host_parts_build" : rules(widest).entry);
+    for (size_t w = 0; w < R.gathered.size(); w++) R.gathered[w] |= R.reassemble[w]; // (sized by a family whose Jacobians are kept from a window's first rebuild)
     return true;
 }
 

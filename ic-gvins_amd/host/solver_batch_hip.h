@@ -98,13 +98,13 @@ public:
     bool devicePreintegration() const { return device_preint_; }
     static bool devicePreintegrationAvailable();
     static const char *devicePreintegrationMissing(); // the first entry the build lacks for it, nullptr when available
-    int preintegrationsOnDevice() const { return (int) preint_list_.size(); } // factors of the last layout that joined the resident set
+    int preintegrationsOnDevice() const { return members(kPreint); } // factors of the last layout that joined the resident set
     // The same switch serves the odometer variants: a residual block without a loss, with four parameter blocks, whose cost is a
     // PreintegrationOdoFactor with preintegration().ready() joins the resident ODOMETER set (PreintegrationOdoSet; 19 residuals, a 19 x 34
     // Jacobian, icg_reproj_host_parts_build_preint_odo) under the same rules and with the same place in the host cost.  A solve without such a
     // factor issues exactly the calls it issued before; one that holds such a factor needs the odometer entries (solve() names the first that
     // is missing).  The number of odometer factors of the last layout that joined their resident set:
-    int odometerPreintegrationsOnDevice() const { return (int) preint_odo_list_.size(); }
+    int odometerPreintegrationsOnDevice() const { return members(kPreintOdo); }
     static const char *devicePreintegrationOdoMissing(); // the first entry the build lacks for the odometer factors, nullptr when none
     // With the device host part: the navigation factors of every window (nav_factors.h: GnssFactor, ImuErrorFactor, ImuPosePriorFactor,
     // ImuMixPriorFactor, in both widths) are RESIDENT on the device for the solve (NavFactorSet: kinds and constants go up once per solve())
@@ -119,16 +119,24 @@ public:
     void setDeviceNavFactors(bool on) { device_nav_ = on; }
     bool deviceNavFactors() const { return device_nav_; }
     static const char *deviceNavFactorsMissing();                       // the first entry the build lacks for it, nullptr when available
-    int navFactorsOnDevice() const { return (int) nav_list_.size(); } // factors of the last layout that joined the resident set
+    int navFactorsOnDevice() const { return members(kNav); }         // factors of the last layout that joined the resident set
     bool solve(const Options &options, std::vector<Summary> *summaries);
     // removeReprojectionFactorsByChi2 (ic_gvins.cc:1269-1297) for every window; returns the number removed per window
     std::vector<int> removeReprojectionFactorsByChi2(double chi2);
     const std::string &error() const { return error_; }
 
 private:
-    // the families of residuals that may be resident on the device for a solve (setDevicePrior, setDevicePreintegration, setDeviceNavFactors), in the order they
-    // are evaluated
+    // The families of residuals that may be resident on the device for a solve, in the order of their precedence in layout() and of their evaluation.  What differs
+    // between them is written once per family in the table behind rules() (solver_batch_hip.cc); the rest loops over it and over what layout() derives, a ResidentFamily.
     enum Family { kNone = -1, kPrior = 0, kPreint = 1, kPreintOdo = 2, kNav = 3, kFamilies = 4 };
+    struct FamilyRules;
+    static const FamilyRules &rules(int family);
+    struct ResidentFamily {
+        std::vector<std::pair<int, int>> where; // the members, in window and residual order: (window, residual)
+        std::vector<int32_t> of, cols; // per block of the host-part list its member (-1: none); the resident blocks' columns of their members' source matrices
+    };
+    int members(int family) const { return (int) resident_[family].where.size(); }
+    const solver_detail::Residual &member(int f, size_t k) const { return windows_[(size_t) resident_[f].where[k].first].problem.residuals[(size_t) resident_[f].where[k].second]; }
     // a window beside its record in factors_: the host-evaluated part of its problem and its state across the steps of a solve
     struct Window {
         solver_detail::Problem problem{"WindowSolverBatch"};
@@ -164,9 +172,8 @@ private:
     // where the paths differ: the host half of a window's linearization, and the reduced solves
     bool hostHalfOfWindow(Run &R, size_t w);
     // resident residuals: the evaluation point of every member of the families that are on (driving thread), their evaluation in a phase (side
-    // thread: priors, then preintegration factors, then navigation factors with the correction of the robustified ones; Jacobians at a
-    // linearization only), the host-part call of the narrowest entry that serves
-    // them, and a window's host cost once the device values are there
+    // thread, family after family; Jacobians at a linearization only), the host-part call of the narrowest entry that serves them, and a
+    // window's host cost once the device values are there
     void packResident(const Run &R);
     bool evaluateResident(Run &R, bool want_jac);
     bool buildHostParts(Run &R);
@@ -188,14 +195,7 @@ private:
     // device host part (layout()): the block list of all windows as icg_reproj_host_parts_build takes it, and the sizes of a call's J and r
     std::vector<int32_t> hp_blk_off_, hp_nr_, hp_nf_, hp_cols_;
     size_t hp_J_total_{0}, hp_r_total_{0};
-    // resident residuals (layout()): per block of that list the prior / the factor of the resident sets it is (-1: none) and the resident blocks' columns
-    // of J0 / of the 15 x 32 Jacobian; the sets, their members (priors in window order, factors in window and residual order) and where each is
-    std::vector<int32_t> hp_prior_of_, hp_prior_cols_, hp_preint_of_, hp_preint_cols_, hp_preint_odo_of_, hp_preint_odo_cols_, hp_nav_of_, hp_nav_cols_;
-    std::vector<MargPriorView> prior_views_;
-    std::vector<const Preintegration *> preint_list_;
-    std::vector<const PreintegrationOdo *> preint_odo_list_;
-    std::vector<const NavFactor *> nav_list_;
-    std::vector<std::pair<int, int>> prior_where_, preint_where_, preint_odo_where_, nav_where_; // (window, residual)
+    ResidentFamily resident_[kFamilies]; // (layout())
     MarginalizationPriorSet prior_set_;
     PreintegrationSet preint_set_;
     PreintegrationOdoSet preint_odo_set_;

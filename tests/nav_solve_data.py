@@ -42,42 +42,18 @@ def solve_nav_batch(lib, wins, starts, priors, mode, variant=0, device_nav=0, na
     -> (rc, message, states, invdepth, summary W x 4, prior cost W x 2, navigation factors resident on the device)"""
     W = len(wins)
     odo = variant in (2, 3)  # (anything else is laid out at 16: the entry refuses what it does not know before it reads)
-    counts = [len(w["offsets"]) - 1 for w in wins]
-    nul = [None] * W
     offsets, imu = [i32(w["offsets"]) for w in wins], [f64(w["imu"]) for w in wins]
-    delta = jac = cov = dt = iewn = pn_off = pn = nul
-    if odo:
-        at = np.cumsum([0] + counts)
-        per = lambda key, shape: [f64(np.stack([np.asarray(r[key], np.float64).reshape(shape) for r in results[at[w]:at[w + 1]]])) for w in range(W)]
-        delta, jac, cov, dt = per("delta", 20), per("jac", 361), per("cov", 361), per("dt", ())
-        iewn = [f64(np.tile(osd.PARAMS25[6:9], (counts[w], 1))) for w in range(W)]
-        rows = [[np.asarray(r["pn"], np.float64).reshape(-1, 4) for r in results[at[w]:at[w + 1]]] for w in range(W)]
-        pn_off = [i32(np.cumsum([0] + [len(x) for x in rows[w]])) for w in range(W)]
-        pn = [f64(np.concatenate(rows[w] + [np.zeros((1, 4))])) for w in range(W)]
-        st = [f64(osd.odo_window(w, s)[1]).copy() for w, s in zip(wins, starts)]
-        mix0 = [f64(np.concatenate([w["states"][0, 7:], [od.SODO]])) for w in wins]
-    else:
-        st = [f64(s).copy() for s, _ in starts]
-        mix0 = [f64(w["states"][0, 7:]) for w in wins]
-    inv = [f64(v).copy() for _, v in starts]
-    obs, ii, jj, ll = ([f64(w["obs"]) for w in wins], [i32(w["ii"]) for w in wins], [i32(w["jj"]) for w in wins], [i32(w["ll"]) for w in wins])
-    ext, td = [f64(w["ext"]).copy() for w in wins], f64([w["td"] for w in wins])
-    pose0 = [f64(w["states"][0, :7]) for w in wins]
-    n_int, n_fac, n_lm = i32(counts), i32([o.shape[1] for o in obs]), i32([len(v) for v in inv])
-    priors = nul if priors is None else priors
-    pr = lambda key, conv: [None if p is None else conv(p[key]) for p in priors]
-    p_r, p_nb = i32([0 if p is None else p["r"] for p in priors]), i32([0 if p is None else len(p["size"]) for p in priors])
-    tables = [pr("size", i32), pr("index", i32), pr("param", i32), pr("x0", f64), pr("J0", f64), pr("e0", f64)]
-    consts = nul if state_const is None else [None if c is None else i32(c) for c in state_const]
+    given = osd.result_arrays(wins, results) if odo else [[None] * W] * 7
+    st, win, n_int = osd.window_arrays(wins, starts, odo)
+    p_r, p_nb, tables, consts = osd.prior_arrays(priors, W, state_const)
     blh = [gnss_fixes(w, 300 + k) for k, w in enumerate(wins)]
     gh = f64(np.broadcast_to(np.asarray(gnss_huber, np.float64), (W,)))
     summ, pcost, ms, err, n_dev = np.zeros((W, 4)), np.zeros((W, 2)), C.c_double(0), ErrBuf(), C.c_int32(-1)
     par9, par19 = f64(pd.PARAMS), f64(od.params19(osd.PARAMS25, od.ABV))
     rc = lib.icgh_backend_solve_nav_batch(
-        W, int(variant), ptr(n_int), ptrs(offsets), ptrs(imu), ptr(par9), ptrs(delta), ptrs(jac), ptrs(cov), ptrs(dt), ptrs(iewn), ptrs(pn_off), ptrs(pn),
-        ptr(par19), ptrs(st), ptr(n_fac), ptrs(obs), ptrs(ii), ptrs(jj), ptrs(ll), ptrs(ext), ptr(n_lm), ptrs(inv), ptr(td), ptrs(pose0), ptrs(mix0),
-        C.c_double(prior_weight), C.c_double(huber), int(iters), ptr(p_r), ptr(p_nb), *[ptrs(t) for t in tables], ptrs(consts), int(nav_factors), ptrs(blh),
-        ptr(f64(GNSS_STD)), ptr(f64(GNSS_LEVER)), ptr(gh), ptr(summ), ptr(pcost), C.byref(ms), C.byref(n_dev), int(mode), int(device_nav), *err.args)
+        W, int(variant), ptr(n_int), ptrs(offsets), ptrs(imu), ptr(par9), *osd.as_args(given), ptr(par19), ptrs(st), *osd.as_args(win), C.c_double(prior_weight),
+        C.c_double(huber), int(iters), ptr(p_r), ptr(p_nb), *osd.as_args(tables), ptrs(consts), int(nav_factors), ptrs(blh), ptr(f64(GNSS_STD)), ptr(f64(GNSS_LEVER)),
+        ptr(gh), ptr(summ), ptr(pcost), C.byref(ms), C.byref(n_dev), int(mode), int(device_nav), *err.args)
     if timer is not None:
         timer.append(ms.value)
-    return rc, err.text(), st, inv, summ, pcost, n_dev.value
+    return rc, err.text(), st, win[7], summ, pcost, n_dev.value

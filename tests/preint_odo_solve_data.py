@@ -71,40 +71,63 @@ def five_windows(oracle):
     return wins, starts, priors, const
 
 
+def result_arrays(wins, results):
+    """the integration results of every interval, window after window, as the per-window arrays the entries take
+    -> (delta, jac, cov, dt, iewn, pn_off, pn)"""
+    W = len(wins)
+    counts = [len(w["offsets"]) - 1 for w in wins]
+    at = np.cumsum([0] + counts)
+    per = lambda key, shape: [f64(np.stack([np.asarray(r[key], np.float64).reshape(shape) for r in results[at[w]:at[w + 1]]])) for w in range(W)]
+    iewn = [f64(np.tile(PARAMS25[6:9], (counts[w], 1))) for w in range(W)]
+    rows = [[np.asarray(r["pn"], np.float64).reshape(-1, 4) for r in results[at[w]:at[w + 1]]] for w in range(W)]
+    pn_off = [i32(np.cumsum([0] + [len(x) for x in rows[w]])) for w in range(W)]
+    pn = [f64(np.concatenate(rows[w] + [np.zeros((1, 4))])) for w in range(W)]
+    return [per("delta", 20), per("jac", 361), per("cov", 361), per("dt", ()), iewn, pn_off, pn]
+
+
+def window_arrays(wins, starts, odo):
+    """what the solve entries take of the windows themselves, in their order: states (K x 17 with odo, copies), n_fac .. invdepth (copies), td, the
+    targets of the priors on state 0 -> (states, [n_fac, obs, ii, jj, ll, ext, n_lm, invdepth, td, pose0, mix0], n_intervals)"""
+    st = [f64(odo_window(w, s)[1]).copy() for w, s in zip(wins, starts)] if odo else [f64(s).copy() for s, _ in starts]
+    inv = [f64(v).copy() for _, v in starts]
+    obs, ii, jj, ll = ([f64(w["obs"]) for w in wins], [i32(w["ii"]) for w in wins], [i32(w["jj"]) for w in wins], [i32(w["ll"]) for w in wins])
+    ext, td = [f64(w["ext"]).copy() for w in wins], f64([w["td"] for w in wins])
+    pose0 = [f64(w["states"][0, :7]) for w in wins]
+    mix0 = [f64(np.concatenate([w["states"][0, 7:], [od.SODO]]) if odo else w["states"][0, 7:]) for w in wins]
+    n_int, n_fac, n_lm = i32([len(w["offsets"]) - 1 for w in wins]), i32([o.shape[1] for o in obs]), i32([len(v) for v in inv])
+    return st, [n_fac, obs, ii, jj, ll, ext, n_lm, inv, td, pose0, mix0], n_int
+
+
+def prior_arrays(priors, W, state_const):
+    """prior_r, prior_nb, the six tables per window (None without a prior) and the constant-state flags"""
+    priors = [None] * W if priors is None else priors
+    pr = lambda key, conv: [None if p is None else conv(p[key]) for p in priors]
+    p_r, p_nb = i32([0 if p is None else p["r"] for p in priors]), i32([0 if p is None else len(p["size"]) for p in priors])
+    tables = [pr("size", i32), pr("index", i32), pr("param", i32), pr("x0", f64), pr("J0", f64), pr("e0", f64)]
+    return p_r, p_nb, tables, [None] * W if state_const is None else [None if c is None else i32(c) for c in state_const]
+
+
+def as_args(arrays):
+    """lists of per-window arrays as pointer tables, arrays as pointers"""
+    return [ptrs(a) if isinstance(a, list) else ptr(a) for a in arrays]
+
+
 def solve_preint_odo_batch(lib, wins, starts, results, priors, mode, variant=od.ODO, state_const=None, robust=None, preint_robust=None, iters=25,
                            prior_weight=100.0, huber=1.0, timer=None):
     """icgh_backend_solve_preint_odo_batch on vio_data windows from the given (states K x 16, invdepth) starts; results: the integration
     results of every interval, window after window (integrate_on_host / integrate_on_device); priors[w]: make_prior's dict or None
     -> (rc, message, states K x 17 per window, invdepth, summary W x 4, prior cost W x 2, odometer factors resident on the device)"""
     W = len(wins)
-    counts = [len(w["offsets"]) - 1 for w in wins]
-    at = np.cumsum([0] + counts)
-    per = lambda key, shape: [f64(np.stack([np.asarray(r[key], np.float64).reshape(shape) for r in results[at[w]:at[w + 1]]])) for w in range(W)]
-    delta, jac, cov, dt = per("delta", 20), per("jac", 361), per("cov", 361), per("dt", ())
-    iewn = [f64(np.tile(PARAMS25[6:9], (counts[w], 1))) for w in range(W)]
-    rows = [[np.asarray(r["pn"], np.float64).reshape(-1, 4) for r in results[at[w]:at[w + 1]]] for w in range(W)]
-    pn_off = [i32(np.cumsum([0] + [len(x) for x in rows[w]])) for w in range(W)]
-    pn = [f64(np.concatenate(rows[w] + [np.zeros((1, 4))])) for w in range(W)]
-    st = [f64(odo_window(w, s)[1]).copy() for w, s in zip(wins, starts)]
-    inv = [f64(v).copy() for _, v in starts]
-    obs, ii, jj, ll = ([f64(w["obs"]) for w in wins], [i32(w["ii"]) for w in wins], [i32(w["jj"]) for w in wins], [i32(w["ll"]) for w in wins])
-    ext, td = [f64(w["ext"]).copy() for w in wins], f64([w["td"] for w in wins])
-    pose0 = [f64(w["states"][0, :7]) for w in wins]
-    mix0 = [f64(np.concatenate([w["states"][0, 7:], [od.SODO]])) for w in wins]
-    n_int, n_fac, n_lm = i32(counts), i32([o.shape[1] for o in obs]), i32([len(v) for v in inv])
-    pr = lambda key, conv: [None if p is None else conv(p[key]) for p in priors]
-    p_r, p_nb = i32([0 if p is None else p["r"] for p in priors]), i32([0 if p is None else len(p["size"]) for p in priors])
-    tables = [pr("size", i32), pr("index", i32), pr("param", i32), pr("x0", f64), pr("J0", f64), pr("e0", f64)]
+    given = result_arrays(wins, results)
+    st, win, n_int = window_arrays(wins, starts, True)
+    p_r, p_nb, tables, consts = prior_arrays(priors, W, state_const)
     rob = f64(np.zeros(W) if robust is None else robust)
-    consts = [None] * W if state_const is None else [None if c is None else i32(c) for c in state_const]
     prob = f64(np.zeros(W) if preint_robust is None else preint_robust)
     summ, pcost, ms, err, n_dev = np.zeros((W, 4)), np.zeros((W, 2)), C.c_double(0), ErrBuf(), C.c_int32(-1)
     par19 = f64(od.params19(PARAMS25, od.ABV))
     rc = lib.icgh_backend_solve_preint_odo_batch(
-        W, ptr(n_int), ptrs(delta), ptrs(jac), ptrs(cov), ptrs(dt), ptrs(iewn), ptrs(pn_off), ptrs(pn), ptr(par19), ptrs(st), ptr(n_fac), ptrs(obs), ptrs(ii),
-        ptrs(jj), ptrs(ll), ptrs(ext), ptr(n_lm), ptrs(inv), ptr(td), ptrs(pose0), ptrs(mix0), C.c_double(prior_weight), C.c_double(huber), int(iters), ptr(p_r),
-        ptr(p_nb), *[ptrs(t) for t in tables], ptr(rob), ptrs(consts), ptr(summ), ptr(pcost), C.byref(ms), int(variant), ptr(prob), C.byref(n_dev), int(mode),
-        *err.args)
+        W, ptr(n_int), *as_args(given), ptr(par19), ptrs(st), *as_args(win), C.c_double(prior_weight), C.c_double(huber), int(iters), ptr(p_r), ptr(p_nb),
+        *as_args(tables), ptr(rob), ptrs(consts), ptr(summ), ptr(pcost), C.byref(ms), int(variant), ptr(prob), C.byref(n_dev), int(mode), *err.args)
     if timer is not None:
         timer.append(ms.value)
-    return rc, err.text(), st, inv, summ, pcost, n_dev.value
+    return rc, err.text(), st, win[7], summ, pcost, n_dev.value

@@ -12,8 +12,7 @@ import pytest
 import marg_factor_data as mf
 import preint_data as pd
 import preint_split_data as sd
-from test_gpu_host_part_preint import _arrays, _unit
-from test_gpu_marg_prior_resident import _partition
+from host_part_family_utils import _partition, arrays as _arrays, unit as _unit
 from ctypes_util import bits, i32
 
 pytestmark = pytest.mark.gpu

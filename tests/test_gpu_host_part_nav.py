@@ -13,18 +13,13 @@ import pytest
 
 import marg_factor_data as mf
 import nav_product_data as nd
-import test_gpu_host_part_preint_odo as todo
-from test_gpu_host_part_preint import ALL as ALL15
-from test_gpu_host_part_preint import _j32
-from test_gpu_marg_prior_resident import _columns, _gathered, _partition
-from ctypes_util import bits, i32
+import host_part_family_utils as hp
+from host_part_family_utils import ALL15, ALL34, CODE, FILL, _partition, _columns
+from ctypes_util import bits
 
 pytestmark = pytest.mark.gpu
 
-FILL = 7.0
 P = 64
-ALL34 = todo.ALL
-CODE = {"prior": -2, "preint": -3, "odo": -4, "nav": -5}
 # the nav set: nd.mixed_set() = kinds 0 3 1 2 5 4 0, then a second pose prior whose block is constant in every window (member 7: in no layout)
 KINDS = [0, 3, 1, 2, 5, 4, 0, 2]
 POSE_COLS, MIX9, MIX10 = np.arange(6, dtype=np.int32), np.arange(9, dtype=np.int32), np.arange(10, dtype=np.int32)
@@ -57,44 +52,11 @@ def _member(flat_r, flat_J, m):
 
 
 def _arrays(layout, Pw, rebuild):
-    """the raw arguments of icg_reproj_host_parts_build_nav.  A block is ("ord", J, r, cols), or (family, member, member_cols, cols, how[, nr])
-    with family "prior" / "preint" / "odo" / "nav" and how = "gather" / "keep"; the resident blocks' slots in r are NaN"""
-    blocks = [b for win in layout for b in win]
-    a = dict(Pw=i32(Pw), rebuild=np.ascontiguousarray(rebuild, np.uint8), blk_off=i32(np.concatenate([[0], np.cumsum([len(w) for w in layout])])))
-    nr, nf, cols, r, jac_off, Js, at = [], [], [], [], [], [], 0
-    of = {f: [] for f in CODE}
-    fc = {f: [] for f in CODE}
-    for b in blocks:
-        for f in CODE:
-            of[f].append(b[1] if b[0] == f else -1)
-        if b[0] == "ord":
-            nr.append(b[1].shape[0]), nf.append(b[1].shape[1]), cols.append(b[3]), r.append(b[2])
-            jac_off.append(at), Js.append(b[1].ravel())
-            at += b[1].size
-        else:
-            n = b[5] if b[0] == "prior" else 15 if b[0] == "preint" else 19 if b[0] == "odo" else nd.SHAPES[KINDS[b[1]]][0]
-            nr.append(n), nf.append(len(b[3])), cols.append(b[3]), r.append(np.full(n, np.nan))
-            fc[b[0]].append(b[2])
-            jac_off.append(-1 if b[4] == "keep" else CODE[b[0]])
-    cat = lambda xs, t: np.ascontiguousarray(np.concatenate(xs), t) if xs else None
-    a.update(nr=i32(nr), nf=i32(nf), cols=cat(cols, np.int32), r=cat(r, np.float64), jac_off=np.ascontiguousarray(jac_off, np.int64), J=cat(Js, np.float64))
-    for f in CODE:
-        a[f + "_of"], a[f + "_cols"] = i32(of[f]), cat(fc[f], np.int32)
-    return a
+    return hp.arrays(layout, Pw, rebuild, lambda b: nd.SHAPES[KINDS[b[1]]][0] if b[0] == "nav" else hp.nr_of(b))
 
 
 def _call(ctx, a, W, **over):
-    a = dict(a)
-    a.update(over)
-    sizes = [int(a["Pw"][w]) * (int(a["Pw"][w]) + 1) // 2 if a["rebuild"][w] else 0 for w in range(W)]
-    s, dg, part = np.full((W, P), FILL), np.full((W, P), FILL), np.full(max(1, sum(sizes)), FILL)
-    rc = ctx.reproj_host_parts_build_nav_raw(P, a["Pw"], a["rebuild"], a["blk_off"], a["nr"], a["nf"], a["cols"], a["jac_off"], a["J"], a["r"], s, dg, part,
-                                             a["prior_of"], a["prior_cols"], a["preint_of"], a["preint_cols"], a["odo_of"], a["odo_cols"], a["nav_of"], a["nav_cols"])
-    parts, at = [], 0
-    for w in range(W):
-        parts.append(part[at:at + sizes[w]].copy() if a["rebuild"][w] else None)
-        at += sizes[w]
-    return rc, ctx.lib.icg_last_error(ctx.h).decode(), (s, dg, parts), part
+    return hp.call(ctx, a, W, "nav", P=P, **over)
 
 
 def _layout(rng, prior, how):
@@ -111,29 +73,14 @@ def _layout(rng, prior, how):
 
 
 def _reference(ctx, layout, Pw, rebuild, nav, odo, fifteen, prior, prior_res, prior_jac):
-    """icg_reproj_host_parts_build fed what the resident blocks hold: the fetched residuals and the numpy-gathered columns"""
-    wins = []
-    for win in layout:
-        out = []
-        for b in win:
-            if b[0] == "ord":
-                out.append((b[1], b[2], b[3], False))
-            elif b[0] == "nav":
-                r, J = _member(nav[0], nav[1], b[1])
-                out.append((np.ascontiguousarray(J[:, b[2]]), r, b[3], False))
-            elif b[0] == "odo":
-                out.append((np.ascontiguousarray(todo._j34(odo[1][b[1]])[:, b[2]]), odo[0][b[1]], b[3], False))
-            elif b[0] == "preint":
-                out.append((np.ascontiguousarray(_j32(fifteen[1][b[1]])[:, b[2]]), fifteen[0][b[1]], b[3], False))
-            else:
-                out.append((_gathered(prior, prior_jac, _columns(prior)[1]), prior_res, b[3], False))
-        wins.append(out)
-    s, dg = np.full((len(layout), P), FILL), np.full((len(layout), P), FILL)
-    return ctx.reproj_host_parts_build(P, Pw, wins, rebuild=rebuild, host_s=s, host_diag=dg)
+    def member(b):
+        r, J = _member(nav[0], nav[1], b[1])
+        return J[:, b[2]], r
+    return hp.reference(ctx, layout, Pw, rebuild, dict(hp.sources(prior, prior_res, prior_jac, fifteen, odo), nav=member), P=P)
 
 
 def test_build_from_resident_members_equals_build_from_fetched_ones(ctx):
-    pts_o, qcs_o, prior, x = todo._everything_resident(ctx)
+    pts_o, qcs_o, prior, x = hp.everything_resident(ctx)
     (p1, off1), (p2, off2) = _nav_set(ctx)
     ctx.nav_evaluate_resident(p1, off1)
     _partition(ctx, 6)
@@ -148,7 +95,7 @@ def test_build_from_resident_members_equals_build_from_fetched_ones(ctx):
     assert rc == 0, msg
     rc, msg, alone, _ = _call(ctx, _arrays(layout, Pw, [1, 0, 0, 0, 0, 0]), 6)  # a window alone: the same bits
     assert rc == 0, msg
-    todo._same(alone, got1, [0])
+    hp.same(alone, got1, [0])
     assert alone[2][1] is None and (alone[0][1:] == FILL).all()
     # second rebuild at point 2, residual only: -1 keeps the Jacobian gathered at point 1
     ctx.nav_evaluate_resident(p2, off2, want_jac=False)
@@ -158,8 +105,8 @@ def test_build_from_resident_members_equals_build_from_fetched_ones(ctx):
     res, jac = ctx.marg_prior_evaluate(x, want_jac=True)[:2]
     ref1 = _reference(ctx, layout, Pw, rebuild, nav1, odo, fifteen, prior, res, jac)
     ref2 = _reference(ctx, layout, Pw, rebuild, (r2, nav1[1]), odo, fifteen, prior, res, jac)
-    todo._same(got1, ref1, rebuilt)
-    todo._same(got2, ref2, rebuilt)
+    hp.same(got1, ref1, rebuilt)
+    hp.same(got2, ref2, rebuilt)
     assert not np.array_equal(bits(nav1[0]), bits(r2))
     for w in (0, 1, 2, 5):
         assert np.array_equal(bits(got1[2][w]), bits(got2[2][w])) and not np.array_equal(bits(got1[0][w]), bits(got2[0][w])), w
@@ -171,7 +118,7 @@ def test_build_from_resident_members_equals_build_from_fetched_ones(ctx):
     ctx.nav_evaluate_resident(p1, off1)
     rc, msg, again, _ = _call(ctx, a, 6)
     assert rc == 0, msg
-    todo._same(again, ref1, rebuilt)  # a gather over a kept layout
+    hp.same(again, ref1, rebuilt)  # a gather over a kept layout
     ctx.sync()
     prof = ctx.prof()
     assert prof["host_part_prior"][0] == 1 and prof["host_part"][0] == 1  # no new kernel: the two launches of the older entries
@@ -197,7 +144,7 @@ def test_robustified_members_are_gathered_after_their_correction_only(ctx):
     assert np.array_equal(bits(corrected[0]), bits(h["r_corr"])) and np.array_equal(bits(corrected[1]), bits(h["J_corr"]))
     rc, msg, got, _ = _call(ctx, a, 2)
     assert rc == 0, msg
-    todo._same(got, _reference(ctx, layout, Pw, rebuild, corrected, None, None, prior, None, None), [0, 1])
+    hp.same(got, _reference(ctx, layout, Pw, rebuild, corrected, None, None, prior, None, None), [0, 1])
     uncorrected = _reference(ctx, layout, Pw, rebuild, plain, None, None, prior, None, None)
     assert not np.array_equal(bits(got[2][0]), bits(uncorrected[2][0])) and not np.array_equal(bits(got[0][1]), bits(uncorrected[0][1]))
     # the set now has robustified members: the next evaluation is gathered after its correction only
@@ -214,35 +161,35 @@ def test_robustified_members_are_gathered_after_their_correction_only(ctx):
     ctx.nav_correct_resident(huber != 0, h["corr"])
     rc, msg, again, _ = _call(ctx, a, 2)
     assert rc == 0, msg
-    todo._same(again, got, [0, 1])
+    hp.same(again, got, [0, 1])
 
 
 def test_the_older_entries_are_the_new_one_without_its_arguments(ctx):
     """the odometer test's own input (priors, 15-state and odometer factors, no nav block) through the new entry and through the old one"""
-    pts, qcs, prior, x = todo._everything_resident(ctx)
+    pts, qcs, prior, x = hp.everything_resident(ctx)
     _partition(ctx, 6)
-    layout, Pw, rebuild = todo._layout(np.random.RandomState(9), prior, "gather")
+    layout, Pw, rebuild = hp.layout_odo(np.random.RandomState(9), prior, "gather")
     rebuilt = [w for w in range(6) if rebuild[w]]
-    old_args = todo._arrays(layout, Pw, rebuild)
+    old_args = hp.arrays(layout, Pw, rebuild)
     a = _arrays(layout, Pw, rebuild)
     assert a["nav_cols"] is None and (a["nav_of"] < 0).all()
     for entry in ("odo", "preint", "prior", "plain"):
         keep = {"odo": ("ord", "prior", "preint", "odo"), "preint": ("ord", "prior", "preint"), "prior": ("ord", "prior"), "plain": ("ord",)}[entry]
         sub = [[b for b in win if b[0] in keep] for win in layout]
-        rc, msg, old, _ = todo._call(ctx, todo._arrays(sub, Pw, rebuild), 6, entry=entry)
+        rc, msg, old, _ = hp.call(ctx, hp.arrays(sub, Pw, rebuild), 6, entry)
         assert rc == 0, msg
         b = _arrays(sub, Pw, rebuild)
         drop = {f + "_of": None for f in CODE if f not in keep}
         for over in (dict(), dict(nav_of=None), dict(drop, nav_cols=None)):
             rc, msg, new, _ = _call(ctx, b, 6, **over)
             assert rc == 0, msg
-            todo._same(new, old, rebuilt)
+            hp.same(new, old, rebuilt)
         assert any(p is not None and p.any() for p in old[2])
     assert old_args["odo_cols"] is not None
 
 
 def test_argument_errors_name_window_and_block_and_launch_nothing(ctx):
-    pts_o, qcs_o, prior, x = todo._everything_resident(ctx)
+    pts_o, qcs_o, prior, x = hp.everything_resident(ctx)
     (p1, off1), _ = _nav_set(ctx)
     _partition(ctx, 6)
     layout, Pw, rebuild = _layout(np.random.RandomState(9), prior, "gather")

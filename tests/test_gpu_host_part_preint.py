@@ -10,17 +10,14 @@ import numpy as np
 import pytest
 
 import marg_factor_data as mf
-import preint_data as pd
-import preint_split_data as sd
-from test_gpu_marg_prior_resident import _columns, _gathered, _partition
-from ctypes_util import bits, i32
+import host_part_family_utils as hp
+from host_part_family_utils import FILL, _partition
+from host_part_family_utils import arrays as _arrays, layout15 as _layout, resident_set15 as _resident_set, same as _same
+from ctypes_util import bits
 
 pytestmark = pytest.mark.gpu
 
-FILL = 7.0
 P = 48
-ALL = np.array(list(range(0, 6)) + list(range(7, 16)) + list(range(16, 22)) + list(range(23, 32)), np.int32)  # all four blocks free
-SECOND = ALL[15:]  # the first state constant
 
 
 @pytest.fixture()
@@ -31,105 +28,12 @@ def ctx():
     c.close()
 
 
-def _unit(rng, n, scale):
-    q = np.concatenate([rng.normal(0, scale, (n, 3)), np.ones((n, 1))], axis=1)
-    return q / np.linalg.norm(q, axis=1, keepdims=True)
-
-
-def _resident_set(ctx):
-    """six factors (N E N E E N) of 21-sample intervals -> the two evaluations' arguments"""
-    n = 6
-    imus, states = sd.intervals([21] * n, seed0=70)
-    off = (np.arange(n + 1) * 21).astype(np.int32)
-    cur, delta, jac, cov, dt, pn = ctx.preint_batch(1, off, np.concatenate(imus), np.stack(states), pd.PARAMS)
-    pn_rows = pn.reshape(n, 21, 4)[:, :20].reshape(-1, 4)
-    pn_off = (np.arange(n + 1) * 20).astype(np.int32)
-    env = np.tile(pd.PARAMS[5:9], (n, 1))
-    pts = [np.stack([sd.eval_point(kind, states[i], cur[i]) for i in range(n)]) for kind in ("perturbed", "large_bias_step")]
-    _, _, S, status = ctx.preint_evaluate_batch(1, delta, jac, cov, dt, env, pts[0], pn_off, pn_rows)
-    assert np.all(status == 0)
-    rng = np.random.RandomState(3)
-    ctx.preint_set([0, 1, 0, 1, 1, 0], delta, jac, S, dt, env, _unit(rng, n, 1e-5), pn_off, pn_rows)
-    return pts, [_unit(rng, n, 1e-3), _unit(rng, n, 3e-2)]
-
-
-def _j32(J480):
-    return np.concatenate([J480[0:105].reshape(15, 7), J480[105:240].reshape(15, 9), J480[240:345].reshape(15, 7), J480[345:480].reshape(15, 9)], axis=1)
-
-
-def _arrays(layout, Pw, rebuild):
-    """the raw arguments of icg_reproj_host_parts_build_preint.  A block is ("ord", J, r, cols), ("prior", p, prior_cols, cols, how) or
-    ("preint", f, preint_cols, cols, how), how = "gather" / "keep"; the resident blocks' slots in r are NaN"""
-    blocks = [b for win in layout for b in win]
-    a = dict(Pw=i32(Pw), rebuild=np.ascontiguousarray(rebuild, np.uint8), blk_off=i32(np.concatenate([[0], np.cumsum([len(w) for w in layout])])))
-    nr, nf, cols, r, prior_of, preint_of, pc, qc, jac_off, Js, at = [], [], [], [], [], [], [], [], [], [], 0
-    for b in blocks:
-        if b[0] == "ord":
-            nr.append(b[1].shape[0]), nf.append(b[1].shape[1]), cols.append(b[3]), r.append(b[2]), prior_of.append(-1), preint_of.append(-1)
-            jac_off.append(at), Js.append(b[1].ravel())
-            at += b[1].size
-        else:
-            nr.append(b[5] if b[0] == "prior" else 15), nf.append(len(b[3])), cols.append(b[3]), r.append(np.full(nr[-1], np.nan))
-            prior_of.append(b[1] if b[0] == "prior" else -1), preint_of.append(b[1] if b[0] == "preint" else -1)
-            (pc if b[0] == "prior" else qc).append(b[2])
-            jac_off.append(-1 if b[4] == "keep" else (-2 if b[0] == "prior" else -3))
-    cat = lambda xs, t: np.ascontiguousarray(np.concatenate(xs), t) if xs else None
-    a.update(nr=i32(nr), nf=i32(nf), cols=cat(cols, np.int32), r=cat(r, np.float64), prior_of=i32(prior_of), preint_of=i32(preint_of), prior_cols=cat(pc, np.int32),
-             preint_cols=cat(qc, np.int32), jac_off=np.ascontiguousarray(jac_off, np.int64), J=cat(Js, np.float64))
-    return a
-
-
 def _call(ctx, a, W, entry="preint", **over):
-    a = dict(a)
-    a.update(over)
-    sizes = [int(a["Pw"][w]) * (int(a["Pw"][w]) + 1) // 2 if a["rebuild"][w] else 0 for w in range(W)]
-    s, dg, part = np.full((W, P), FILL), np.full((W, P), FILL), np.full(max(1, sum(sizes)), FILL)
-    lead = (P, a["Pw"], a["rebuild"], a["blk_off"], a["nr"], a["nf"], a["cols"], a["jac_off"], a["J"], a["r"], s, dg, part, a["prior_of"], a["prior_cols"])
-    if entry == "preint":
-        rc = ctx.reproj_host_parts_build_preint_raw(*lead, a["preint_of"], a["preint_cols"])
-    else:
-        rc = ctx.reproj_host_parts_build_prior_raw(*lead)
-    parts, at = [], 0
-    for w in range(W):
-        parts.append(part[at:at + sizes[w]].copy() if a["rebuild"][w] else None)
-        at += sizes[w]
-    return rc, ctx.lib.icg_last_error(ctx.h).decode(), (s, dg, parts), part
-
-
-def _same(got, ref, rebuilt):
-    (gs, gd, gp), (rs, rdg, rp) = got, ref
-    for w in rebuilt:
-        assert np.array_equal(bits(gp[w]), bits(rp[w])), ("part", w)
-        assert np.array_equal(bits(gs[w]), bits(rs[w])) and np.array_equal(bits(gd[w]), bits(rdg[w])), ("s / diag", w)
-
-
-def _layout(rng, prior, how):
-    mk = lambda nr, cols, scale=1.0: ("ord", rng.normal(0, scale, (nr, len(cols))), rng.normal(0, 1.0, nr), np.asarray(cols, np.int32))
-    pc = _columns(prior)[0]
-    layout = [[("preint", 3, ALL, np.arange(0, 30), how), ("preint", 1, ALL, np.arange(15, 45), how)],  # two factors sharing the middle state's columns
-              [("preint", 0, SECOND, np.arange(0, 15), how), mk(9, range(6, 15), 10.0)],  # the first state constant: nf = 15
-              [mk(6, range(0, 6), 30.0), ("preint", 4, ALL, 3 + rng.permutation(30), how), ("prior", 0, pc, np.arange(34, 40), how, prior["r"])],
-              [],  # rebuilt, no host block
-              [mk(3, [1, 5, 2]), ("preint", 5, ALL, np.arange(30), how)],  # not rebuilt: its block only places the others' columns
-              [("preint", 2, ALL, rng.permutation(30), how)]]
-    return layout, [45, 20, 40, 10, 30, 30], [1, 1, 1, 1, 0, 1]
+    return hp.call(ctx, a, W, entry, P=P, **over)
 
 
 def _reference(ctx, layout, Pw, rebuild, r_fetch, J_fetch, prior, prior_res, prior_jac):
-    """icg_reproj_host_parts_build fed what the resident blocks hold: the fetched residuals and the numpy-gathered columns"""
-    wins = []
-    for win in layout:
-        out = []
-        for b in win:
-            if b[0] == "ord":
-                out.append((b[1], b[2], b[3], False))
-            elif b[0] == "preint":
-                out.append((np.ascontiguousarray(_j32(J_fetch[b[1]])[:, b[2]]), r_fetch[b[1]], b[3], False))
-            else:
-                out.append((_gathered(prior, prior_jac, _columns(prior)[1]), prior_res, b[3], False))
-        wins.append(out)
-    s, dg = np.full((len(layout), P), FILL), np.full((len(layout), P), FILL)
-    return ctx.reproj_host_parts_build(P, Pw, wins, rebuild=rebuild, host_s=s, host_diag=dg)
+    return hp.reference(ctx, layout, Pw, rebuild, hp.sources(prior, prior_res, prior_jac, fifteen=(r_fetch, J_fetch)), P=P)
 
 
 def test_build_from_resident_factors_equals_build_from_fetched_ones(ctx):

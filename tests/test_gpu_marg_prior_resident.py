@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 
 import marg_factor_data as mf
-import reproj_data as rd
 from ctypes_util import bits, ptr
+from host_part_family_utils import _columns, _gathered, _partition
 
 pytestmark = pytest.mark.gpu
 
@@ -30,34 +30,6 @@ def _points(priors, seed):
     pts = [mf.make_x(p, seed + k, negate=(0, 2)) for k, p in enumerate(priors)]
     assert mf.dq_w(priors[1], pts[1])[0] < 0  # the single pose takes the dq.w < 0 branch
     return pts
-
-
-def _columns(prior, drop=()):
-    """the local columns of the prior's blocks in block order, without the blocks listed in drop -> (columns of J0, (block, local column) pairs)"""
-    pc, src = [], []
-    for b, (size, index) in enumerate(zip(prior["size"], prior["index"])):
-        if b in drop:
-            continue
-        for x in range(mf.local(int(size))):
-            pc.append(int(index) + x), src.append((b, x))
-    return np.array(pc, np.int32), src
-
-
-def _gathered(prior, jac, src):
-    """the dense Jacobian of those columns from the blocks icg_marg_prior_evaluate ships (block b: r x size[b] row-major, blocks concatenated)"""
-    r, off, blocks = prior["r"], 0, []
-    for size in prior["size"]:
-        blocks.append(jac[off:off + r * int(size)].reshape(r, int(size)))
-        off += r * int(size)
-    return np.ascontiguousarray(np.stack([blocks[b][:, x] for b, x in src], axis=1))
-
-
-def _partition(ctx, W):
-    w = rd.make_window(3, 2, seed=5)
-    n, K, L = w["obs_soa"].shape[1], w["poses"].shape[0], len(w["invdepth"])
-    ctx.reproj_set_factors(np.tile(w["obs_soa"], (1, W)), np.concatenate([w["idx_i"] + K * k for k in range(W)]),
-                           np.concatenate([w["idx_j"] + K * k for k in range(W)]), np.concatenate([w["idx_lm"] + L * k for k in range(W)]))
-    ctx.reproj_set_windows(n * np.arange(W + 1), L * np.arange(W + 1))
 
 
 @pytest.fixture()

@@ -81,7 +81,7 @@ def test_the_huber_loss_is_in_the_device_solve(lib, five):
     assert not np.array_equal(bits(a[2][0]), bits(b[2][0]))
 
 
-@pytest.mark.parametrize("mode", [0, 2, 5])
+@pytest.mark.parametrize("mode", [0, 1, 2, 3, 4, 5])
 def test_without_the_switch_the_results_are_the_older_entries(lib, five, mode):
     """device_nav off, the stand-in priors: the bits of icgh_backend_solve_preint_batch / icgh_backend_solve_preint_odo_batch on the same windows"""
     for variant in (1, 3):
