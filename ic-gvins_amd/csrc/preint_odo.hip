@@ -80,13 +80,16 @@ __device__ __forceinline__ m33 qleft_qright_br(dq a, dq b) {
 // rows of phi in descending order of their number of structural non-zeros: s (8), v (7), attitude (4), p (2), bg, ba, sodo (1)
 #define PO_ROWMAP(r) ((r) < 3 ? (r) + 15 : ((r) < 9 ? (r) : ((r) < 12 ? (r) - 9 : ((r) < 18 ? (r) - 3 : 18))))
 
+// params_stride: doubles between the parameter rows of two intervals (icg_preint_odo_batch_params: 25), 0 = one row for the whole launch
+// (icg_preint_odo_batch); wave-uniform like k_preint's, the row stays on the scalar path.
 __global__ __launch_bounds__(64) void k_preint_odo(int variant, const int32_t *offsets, const double *imu, const double *state0,
-                                                   const double *params, double *cur_state, double *delta_state, double *jac_out,
-                                                   double *cov_out, double *delta_time_out, double *pn_out) {
+                                                   const double *params_rows, int params_stride, double *cur_state, double *delta_state,
+                                                   double *jac_out, double *cov_out, double *delta_time_out, double *pn_out) {
     __shared__ double J[PO_NN], P[PO_NN], M[PO_NN], T1[PO_NN], T2[PO_NN], T3[PO_NN], PV[PO_N * PO_PV];
     __shared__ double GM[27], NZ[16]; // the blocks gv, gs0, gs12 of G of the current sample; the diagonal of the noise matrix
     const int s = blockIdx.x, lane = threadIdx.x;
     const int begin = offsets[s], n = offsets[s + 1] - offsets[s];
+    const double *params = params_rows + (size_t) s * (size_t) params_stride;
     const double gyr_arw = params[0], acc_vrw = params[1], gbstd = params[2], abstd = params[3], corr_time = params[4];
     const d3 gravity = mk3(0, 0, params[5]);
     const d3 iewn    = mk3(params[6], params[7], params[8]);
@@ -360,15 +363,71 @@ extern "C" int icg_preint_odo_batch(icg_ctx *ctx, int variant, int n_intervals, 
         }
     {
         icg_prof_scope ps(ctx, "preint_odo");
-        hipLaunchKernelGGL(k_preint_odo, dim3(n_intervals), dim3(64), 0, ctx->stream, variant, d_off, d_imu, d_s0, d_par, d_cur, d_del,
+        hipLaunchKernelGGL(k_preint_odo, dim3(n_intervals), dim3(64), 0, ctx->stream, variant, d_off, d_imu, d_s0, d_par, 0, d_cur, d_del,
                            d_jac, d_cov, d_dt, d_pn);
     }
     ICG_HIP(ctx, hipGetLastError());
     return c.finish();
 }
 
+__global__ __launch_bounds__(64) void k_preint_odo_sqrt_info(int n, const double *cov, double *sqrt_info, int32_t *status);
+
+// icg_preint_odo_batch with one parameter row per interval and (optionally) the square-root information of every result formed behind the
+// integration: the 19-state twin of icg_preint_batch_params (preint.hip), the same staging.
+extern "C" int icg_preint_odo_batch_params(icg_ctx *ctx, int variant, int n_intervals, const int32_t *offsets, const double *imu9,
+                                           const double *state0, const double *params25, double *cur_state, double *delta_state,
+                                           double *jac, double *cov, double *delta_time, double *pn, double *sqrt_info, int32_t *status) {
+    if (!ctx) return ICG_ERR_INVALID;
+    if (variant != 2 && variant != 3)
+        return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_batch_params: variant %d is neither 2 (Odo) nor 3 (EarthOdo)", variant);
+    if (n_intervals < 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_batch_params: n_intervals = %d", n_intervals);
+    if (n_intervals == 0) return ICG_OK;
+    if (!offsets || !imu9 || !state0 || !params25 || !cur_state || !delta_state || !jac || !cov || !delta_time)
+        return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_batch_params: NULL argument");
+    if (offsets[0] < 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_batch_params: interval 0: offsets[0] = %d", offsets[0]);
+    for (int s = 0; s < n_intervals; s++)
+        if (offsets[s + 1] - offsets[s] < 1) return icg_fail(ctx, ICG_ERR_INVALID, "icg_preint_odo_batch_params: interval %d has no IMU sample", s);
+    const int total   = offsets[n_intervals];
+    const size_t n    = (size_t) n_intervals;
+    const bool want_S = sqrt_info || status;
+    ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    icg_call c(ctx);
+    int rc = c.reserve((size_t) total * (72 + 32) + n * (8 * (17 + 25 + 16 + 20 + 1) + PO_NN * 8 * 3 + 8) + 16 * 256);
+    if (rc) return rc;
+    const int32_t *d_off = c.in(offsets, n + 1);
+    const double *d_imu  = c.in(imu9, 9 * (size_t) total);
+    const double *d_s0   = c.in(state0, 17 * n);
+    const double *d_par  = c.in(params25, 25 * n);
+    if ((rc = c.seal())) return rc;
+    double *d_cur = c.out_zc(cur_state, 16 * n);
+    double *d_del = c.out_zc(delta_state, 20 * n);
+    double *d_jac = c.out_zc(jac, PO_NN * n);
+    double *d_dt  = c.out_zc(delta_time, n);
+    double *d_pn  = (pn && variant == 3) ? c.out_zc(pn, 4 * (size_t) total) : nullptr; // (icg_preint_odo_batch's rule)
+    double *d_S   = want_S ? c.out_zc(sqrt_info, PO_NN * n) : nullptr;
+    int32_t *d_st = want_S ? c.out_zc(status, n) : nullptr;
+    double *d_cov = want_S ? c.out(cov, PO_NN * n) : c.out_zc(cov, PO_NN * n); // (last: no zero-copy region inside the span copied back)
+    ICG_LAUNCH_GUARD(c);
+    if (d_pn)
+        for (int s = 0; s < n_intervals; s++) {
+            const size_t last = 4 * ((size_t) offsets[s + 1] - 1);
+            memcpy(d_pn + last, pn + last, 4 * sizeof(double));
+        }
+    {
+        icg_prof_scope ps(ctx, "preint_odo");
+        hipLaunchKernelGGL(k_preint_odo, dim3(n_intervals), dim3(64), 0, ctx->stream, variant, d_off, d_imu, d_s0, d_par, 25, d_cur, d_del,
+                           d_jac, d_cov, d_dt, d_pn);
+    }
+    if (want_S) {
+        icg_prof_scope ps(ctx, "preint_odo_eval");
+        hipLaunchKernelGGL(k_preint_odo_sqrt_info, dim3(n_intervals), dim3(64), 0, ctx->stream, n_intervals, d_cov, d_S, d_st);
+    }
+    ICG_HIP(ctx, hipGetLastError());
+    return c.finish();
+}
+
 // ================================================================ P2 ================================================================
-#define POE_W 38         // row length of the augmented matrix
+#define POE_W 38        // row length of the augmented matrix
 #define POE_U 35         // row length of the unwhitened block: 34 Jacobian columns (7 | 10 | 7 | 10) + the residual
 #define POE_NOUT (19 + 646)
 

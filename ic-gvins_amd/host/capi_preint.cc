@@ -6,6 +6,7 @@
 #include "factors.h"
 #include "host_pool.h"
 #include "capi_util.h"
+#include "capi_preint_streams.h"
 
 using namespace icg;
 
@@ -31,6 +32,36 @@ struct Intervals {
         if (Preintegration::integrateBatch(ctx, raw, &e)) return true;
         set_err(err, errlen, e.c_str());
         return false;
+    }
+};
+
+// icgh_backend_preint_streams' family (capi_preint_streams.h).  Parameter row of 13: the 9 of icg_preint_batch, has_station, station[3]; with
+// has_station the interval's Earth rate comes from its own start position and [6..8] are not used.  Member row of 712: cur_state 16,
+// delta_state 16, delta_time, the time of the current state, the Earth rate 3, jac 225, cov 225, sqrt_info 225.
+struct StreamsFamily {
+    typedef Preintegration Obj;
+    static constexpr int IMU_W = 8, STATE_W = 16, PARAM_W = 13, MEMBER_W = 16 + 16 + 2 + 3 + 3 * 225;
+    static constexpr const char *P1 = "preint", *S = "preint_eval";
+    static std::shared_ptr<Obj> make(int variant, const double *row, const int32_t *offsets, const double *imu, int k, const double *state16) {
+        if (variant != 0 && variant != 1) throw std::runtime_error("variant " + std::to_string(variant) + " is neither 0 (Normal) nor 1 (Earth)");
+        auto P         = preint_params(row);
+        P->has_station = row[9] != 0;
+        P->station     = Vector3d(row[10], row[11], row[12]);
+        return preint_interval(variant, P, offsets, imu, k, state16);
+    }
+    static IntegrationState state(const double *row) { return preint_state(row); }
+    static void put(const Obj &p, double *o) {
+        preint_put_state(p.currentState(), o);
+        preint_put_state(p.deltaState(), o + 16);
+        o[32] = p.deltaTime(), o[33] = p.currentState().time;
+        for (int i = 0; i < 3; i++) o[34 + i] = p.earthRate()[i];
+        const vector<double> *m[3] = {&p.jacobian(), &p.covariance(), &p.sqrtInformation()};
+        for (int b = 0; b < 3; b++)
+            for (size_t i = 0; i < 225; i++) o[37 + 225 * b + i] = i < m[b]->size() ? (*m[b])[i] : 0.0;
+    }
+    static bool available(int mode) { return mode == 0 || Preintegration::integrateStreamsAvailable(); }
+    static bool integrate(int mode, icg_ctx *ctx, const vector<Obj *> &list, std::string *e) {
+        return mode == 0 ? Preintegration::integrateBatch(ctx, list, e) : Preintegration::integrateStreams(ctx, list, e);
     }
 };
 
@@ -104,6 +135,19 @@ int icgh_backend_preint_device(int variant, int n, const int32_t *offsets, const
         return 0;
     });
 }
+
+// The intervals of many streams, each with its own parameter set, through Preintegration::integrateBatch (mode 0) or ::integrateStreams
+// (mode 1): flow, outputs and return codes in capi_preint_streams.h, the rows in StreamsFamily above.  variant: per interval, 0 or 1.
+int icgh_backend_preint_streams(int n, const int32_t *variant, const int32_t *offsets, const double *imu, const double *state0, const double *params13,
+                                int mode, int passes, int profile, int n_redo, const int32_t *redo, const double *redo_state, double *members, int32_t *ready,
+                                double *pn, int32_t *pn_doubles, double *prof, double *seconds, char *err, int errlen) {
+    return guarded(err, errlen, [&] {
+        return preint_streams_entry<StreamsFamily>(n, variant, offsets, imu, state0, params13, mode, passes, profile, n_redo, redo, redo_state, members, ready, pn,
+                                                   pn_doubles, prof, seconds, err, errlen);
+    });
+}
+// 1 when Preintegration::integrateStreams has its C entry in this build
+int icgh_preint_streams_available(void) { return Preintegration::integrateStreamsAvailable() ? 1 : 0; }
 
 // Timing of P2 on one set of intervals (profiles/preint_eval_probe.py): integrated once (one icg_preint_batch launch), then evaluated `reps`
 // times (a) by PreintegrationFactor::Evaluate, one call per factor, on a HostPool of `threads` threads and (b) by one

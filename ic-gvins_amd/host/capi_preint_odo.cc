@@ -9,6 +9,7 @@
 #include "preintegration_odo.h"
 #include "host_pool.h"
 #include "capi_util.h"
+#include "capi_preint_streams.h"
 
 using namespace icg;
 
@@ -62,6 +63,37 @@ struct OdoIntervals {
         if (PreintegrationOdo::integrateBatch(ctx, raw, &e)) return true;
         set_err(err, errlen, e.c_str());
         return false;
+    }
+};
+
+// icgh_backend_preint_odo_streams' family (capi_preint_streams.h).  Parameter row of 23: params19, has_station, station[3].  Member row of
+// 1125: cur_state 16, its sodo, delta_state 20, delta_time, the time of the current state, the Earth rate 3, jac 361, cov 361, sqrt_info 361.
+struct OdoStreamsFamily {
+    typedef PreintegrationOdo Obj;
+    static constexpr int IMU_W = 9, STATE_W = 17, PARAM_W = 23, MEMBER_W = 17 + 20 + 2 + 3 + 3 * 361;
+    static constexpr const char *P1 = "preint_odo", *S = "preint_odo_eval";
+    static std::shared_ptr<Obj> make(int variant, const double *row, const int32_t *offsets, const double *imu9, int k, const double *state17) {
+        auto P         = odo_params(row);
+        P->has_station = row[19] != 0;
+        P->station     = Vector3d(row[20], row[21], row[22]);
+        auto p = std::make_shared<PreintegrationOdo>(P, odo_imu(imu9 + 9 * (size_t) offsets[k]), odo_state(state17), odo_variant(variant));
+        for (int r = offsets[k] + 1; r < offsets[k + 1]; r++) p->addNewImu(odo_imu(imu9 + 9 * (size_t) r));
+        return p;
+    }
+    static IntegrationState state(const double *row) { return odo_state(row); }
+    static void put(const Obj &p, double *o) {
+        preint_put_state(p.currentState(), o);
+        o[16] = p.currentState().sodo;
+        put_delta20(p.deltaState(), o + 17);
+        o[37] = p.deltaTime(), o[38] = p.currentState().time;
+        for (int i = 0; i < 3; i++) o[39 + i] = p.earthRate()[i];
+        const vector<double> *m[3] = {&p.jacobian(), &p.covariance(), &p.sqrtInformation()};
+        for (int b = 0; b < 3; b++)
+            for (size_t i = 0; i < 361; i++) o[42 + 361 * b + i] = i < m[b]->size() ? (*m[b])[i] : 0.0;
+    }
+    static bool available(int mode) { return mode == 0 ? PreintegrationOdo::integrateBatchAvailable() : PreintegrationOdo::integrateStreamsAvailable(); }
+    static bool integrate(int mode, icg_ctx *ctx, const vector<Obj *> &list, std::string *e) {
+        return mode == 0 ? PreintegrationOdo::integrateBatch(ctx, list, e) : PreintegrationOdo::integrateStreams(ctx, list, e);
     }
 };
 
@@ -140,6 +172,20 @@ int icgh_backend_preint_odo_device(int variant, int n, const int32_t *offsets, c
         return 0;
     });
 }
+
+// The intervals of many streams, each with its own parameter set, through PreintegrationOdo::integrateBatch (mode 0) or ::integrateStreams
+// (mode 1): flow, outputs and return codes in capi_preint_streams.h, the rows in OdoStreamsFamily above.  variant: per interval, 2 or 3.
+int icgh_backend_preint_odo_streams(int n, const int32_t *variant, const int32_t *offsets, const double *imu9, const double *state0,
+                                    const double *params23, int mode, int passes, int profile, int n_redo, const int32_t *redo, const double *redo_state,
+                                    double *members, int32_t *ready, double *pn, int32_t *pn_doubles, double *prof, double *seconds, char *err,
+                                    int errlen) {
+    return guarded(err, errlen, [&] {
+        return preint_streams_entry<OdoStreamsFamily>(n, variant, offsets, imu9, state0, params23, mode, passes, profile, n_redo, redo, redo_state, members, ready,
+                                                      pn, pn_doubles, prof, seconds, err, errlen);
+    });
+}
+// 1 when PreintegrationOdo::integrateStreams has its C entry in this build
+int icgh_preint_odo_streams_available(void) { return PreintegrationOdo::integrateStreamsAvailable() ? 1 : 0; }
 
 // Host P2 on a GIVEN integration result: the object is built from delta_state 20, jac 361, cov 361, delta_time, the pn rows (pn_rows x 4;
 // EarthOdo), the interval's Earth rate iewn3 and the parameters, then evaluated on the host at eval_point.  No device is touched.  Outputs:

@@ -53,8 +53,15 @@ public:
     void addNewImu(const IMU &imu) { imu_buffer_.push_back(imu); dirty_ = true; }
     void reintegration(const IntegrationState &state);
     const Vector3d &earthRate() const { return iewn_; }
-    // integrate every dirty interval of the list with a single icg_preint_batch launch
+    // integrate every dirty interval of the list: one icg_preint_batch launch per (variant, parameter values) group
     static bool integrateBatch(icg_ctx *ctx, const vector<Preintegration *> &list, std::string *err = nullptr);
+    // integrateBatch for the intervals of MANY streams: every dirty interval of the list in ONE icg_preint_batch_params call per variant
+    // present, whatever the parameter values (each interval brings its own row: its Earth rate, gravity, noise figures), and the
+    // square-root information comes down with the result (the device forms it behind the integration; updateSqrtInformation does not
+    // run).  Every member is afterwards what integrateBatch leaves, bit for bit.  The C entry is referenced weakly: without it
+    // integrateStreamsAvailable() is false and integrateStreams fails by the entry's name and integrates nothing.
+    static bool integrateStreams(icg_ctx *ctx, const vector<Preintegration *> &list, std::string *err = nullptr);
+    static bool integrateStreamsAvailable(); // icg_preint_batch_params is in this build
     // P2 on the device: residual 15 (and, unless `jacobians` is null, the Jacobians 480 = 15x7 | 15x9 | 15x7 | 15x9) of every factor of the
     // list at its evaluation point (points: n x 32 = pose0[7] mix0[9] pose1[7] mix1[9]) through icg_preint_evaluate_batch, one call per
     // variant present.  ok[k] = 0 (and zero rows) for a factor that is not integrated for its current buffer / start state or whose
@@ -82,7 +89,11 @@ public:
     const vector<double> &sqrtInformation() const { return sqrt_information_; } // 15x15 row-major; zeros while the covariance is singular
     // what a resident set packs besides deltaState(), deltaTime(), sqrtInformation() and earthRate()
     bool ready() const { return !dirty_ && sqrt_information_ok_; } // integrated for the current buffer / start state, covariance not singular
+    // forms the square-root information from the covariance on the host again, as integrateBatch does for every result it brings down (the
+    // same arithmetic on the same data: nothing changes); for probes that time that loop
+    void recomputeSqrtInformation() { updateSqrtInformation(); }
     const vector<double> &jacobian() const { return jacobian_; }   // 15x15 row-major
+    const vector<double> &covariance() const { return covariance_; } // 15x15 row-major
     double gravity() const { return parameters_->gravity; }
     const vector<double> &pnRows() const { return pn_; }           // Earth variant: rows of 4 (dt, position); evaluate() sums the complete rows
 

@@ -1,4 +1,6 @@
-// Preintegration on the HIP C ABI: P1 (the per-sample inner loop) runs batched on the device through icg_preint_batch;
+// Preintegration on the HIP C ABI: P1 (the per-sample inner loop) runs batched on the device through icg_preint_batch (integrateBatch: one
+// launch per group of equal parameter values, the square-root information formed here) or icg_preint_batch_params (integrateStreams: the
+// intervals of many streams in one call per variant, a parameter row per interval, the square-root information formed on the device);
 // P2 (residual + Jacobians, preintegration_normal.cc:38-142 / preintegration_earth.cc:37-164, wrapped by
 // preintegration_factor.h:45-69) is a handful of 3x3 / 15x15 operations per factor (<= 15 factors per solve) and stays
 // on the host, in the Ceres callback thread that asks for it.  evaluateBatch() is the same evaluation for MANY factors at once on the
@@ -15,6 +17,7 @@
 // A build of this layer on another implementation of the C ABI may not have the entry point: the reference stays weak (null when absent)
 // and evaluateBatch() reports it; the product library links libicgvins_hip.so, which defines it.
 #pragma weak icg_preint_evaluate_batch
+#pragma weak icg_preint_batch_params
 
 namespace icg {
 
@@ -205,6 +208,62 @@ bool Preintegration::integrateBatch(icg_ctx *ctx, const vector<Preintegration *>
             p->pn_.assign(pn.begin() + 4 * (long) b, pn.begin() + 4 * (long) (b + cnt - 1));
             p->updateSqrtInformation();
             p->dirty_ = false;
+        }
+    }
+    return true;
+}
+
+bool Preintegration::integrateStreamsAvailable() { return &icg_preint_batch_params != nullptr; }
+
+bool Preintegration::integrateStreams(icg_ctx *ctx, const vector<Preintegration *> &list, std::string *err) {
+    if (!integrateStreamsAvailable()) {
+        if (err) *err = "icg_preint_batch_params is not in this build";
+        return false;
+    }
+    // one call per variant present: every interval brings its own parameter row (its own Earth rate), and the device forms the square-root
+    // information behind the integration, so updateSqrtInformation does not run
+    for (int variant = 0; variant < 2; variant++) {
+        vector<Preintegration *> todo;
+        for (auto *p : list)
+            if (p->dirty_ && (int) p->variant_ == variant) todo.push_back(p);
+        if (todo.empty()) continue;
+        vector<int32_t> offsets{0};
+        vector<double> imu, state0, params;
+        for (auto *p : todo) {
+            for (const IMU &s : p->imu_buffer_) {
+                const double row[8] = {s.time, s.dt, s.dtheta[0], s.dtheta[1], s.dtheta[2], s.dvel[0], s.dvel[1], s.dvel[2]};
+                imu.insert(imu.end(), row, row + 8);
+            }
+            offsets.push_back((int32_t) (imu.size() / 8));
+            double a[16];
+            stateToArray(p->start_state_, a);
+            state0.insert(state0.end(), a, a + 16);
+            const IntegrationParameters &P = *p->parameters_;
+            const double v[9] = {P.gyr_arw, P.acc_vrw, P.gyr_bias_std, P.acc_bias_std, P.corr_time, P.gravity, p->iewn_[0], p->iewn_[1], p->iewn_[2]};
+            params.insert(params.end(), v, v + 9);
+        }
+        const size_t n = todo.size();
+        vector<double> cur(16 * n), del(16 * n), jac(225 * n), cov(225 * n), dt(n), pn(imu.size() / 2), S(225 * n);
+        vector<int32_t> status(n);
+        int rc = icg_preint_batch_params(ctx, variant, (int) n, offsets.data(), imu.data(), state0.data(), params.data(), cur.data(), del.data(),
+                                         jac.data(), cov.data(), dt.data(), pn.data(), S.data(), status.data());
+        if (rc != ICG_OK) {
+            if (err) *err = icg_last_error(ctx);
+            return false;
+        }
+        for (size_t k = 0; k < n; k++) {
+            Preintegration *p = todo[k];
+            stateFromArray(&cur[16 * k], p->current_state_);
+            stateFromArray(&del[16 * k], p->delta_state_);
+            p->current_state_.time = p->imu_buffer_.back().time;
+            p->jacobian_.assign(jac.begin() + 225 * (long) k, jac.begin() + 225 * (long) (k + 1));
+            p->covariance_.assign(cov.begin() + 225 * (long) k, cov.begin() + 225 * (long) (k + 1));
+            p->delta_time_ = dt[k];
+            const int b = offsets[k], cnt = offsets[k + 1] - offsets[k];
+            p->pn_.assign(pn.begin() + 4 * (long) b, pn.begin() + 4 * (long) (b + cnt - 1));
+            p->sqrt_information_.assign(S.begin() + 225 * (long) k, S.begin() + 225 * (long) (k + 1));
+            p->sqrt_information_ok_ = status[k] == 0;
+            p->dirty_               = false;
         }
     }
     return true;

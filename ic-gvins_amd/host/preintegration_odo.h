@@ -37,6 +37,12 @@ public:
     const Vector3d &earthRate() const { return iewn_; }
     // integrate every dirty interval of the list: one icg_preint_odo_batch launch per (variant, parameter values) group
     static bool integrateBatch(icg_ctx *ctx, const vector<PreintegrationOdo *> &list, std::string *err = nullptr);
+    // integrateBatch for the intervals of MANY streams: every dirty interval of the list in ONE icg_preint_odo_batch_params call per
+    // variant present, whatever the parameter values, with the square-root information formed on the device behind the integration
+    // (updateSqrtInformation does not run).  Every member is afterwards what integrateBatch leaves, bit for bit.  Without the (weakly
+    // referenced) C entry integrateStreamsAvailable() is false and integrateStreams fails by the entry's name and integrates nothing.
+    static bool integrateStreams(icg_ctx *ctx, const vector<PreintegrationOdo *> &list, std::string *err = nullptr);
+    static bool integrateStreamsAvailable(); // icg_preint_odo_batch_params is in this build
     // The object as if integrateBatch had returned this result (delta_state 20 and jac / cov 361 in icg_preint_odo_batch's layout, pn rows of
     // 4, iewn the interval's Earth rate): the host P2 can then be exercised, and pinned against the reference, without a device.
     void setIntegrationResult(const double *cur16, const double *delta20, const double *jac361, const double *cov361, double delta_time,
@@ -70,6 +76,9 @@ public:
     Variant variant() const { return variant_; }
     const vector<double> &sqrtInformation() const { return sqrt_information_; } // 19x19 row-major; zeros while the covariance is singular
     bool ready() const { return !dirty_ && sqrt_information_ok_; }
+    // forms the square-root information from the covariance on the host again, as integrateBatch does for every result it brings down (the
+    // same arithmetic on the same data: nothing changes); for probes that time that loop
+    void recomputeSqrtInformation() { updateSqrtInformation(); }
     const vector<double> &jacobian() const { return jacobian_; }     // 19x19 row-major
     const vector<double> &covariance() const { return covariance_; } // 19x19 row-major
     double gravity() const { return parameters_->gravity; }
@@ -84,6 +93,9 @@ private:
     IntegrationState start_state_, current_state_, delta_state_;
     double delta_time_{0};
     void updateSqrtInformation();
+    // setIntegrationResult without the square-root information (integrateStreams takes that from the device)
+    void storeIntegrationResult(const double *cur16, const double *delta20, const double *jac361, const double *cov361, double delta_time,
+                                const double *pn, int pn_rows, const Vector3d &iewn);
     vector<double> jacobian_, covariance_, pn_; // 19x19, 19x19, (n-1)x4
     vector<double> sqrt_information_;            // 19x19, of covariance_ (formed when an integration result arrives)
     bool sqrt_information_ok_{false};

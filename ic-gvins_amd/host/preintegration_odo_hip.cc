@@ -16,6 +16,7 @@
 // weak (null when absent) and the callers report it; the product library links libicgvins_hip.so, which defines them.
 #pragma weak icg_preint_odo_batch
 #pragma weak icg_preint_odo_evaluate_batch
+#pragma weak icg_preint_odo_batch_params
 
 namespace icg {
 
@@ -176,6 +177,13 @@ bool PreintegrationOdo::evaluateBatchAvailable() { return &icg_preint_odo_evalua
 
 void PreintegrationOdo::setIntegrationResult(const double *cur16, const double *delta20, const double *jac361, const double *cov361,
                                              double delta_time, const double *pn, int pn_rows, const Vector3d &iewn) {
+    storeIntegrationResult(cur16, delta20, jac361, cov361, delta_time, pn, pn_rows, iewn);
+    updateSqrtInformation();
+    dirty_ = false;
+}
+
+void PreintegrationOdo::storeIntegrationResult(const double *cur16, const double *delta20, const double *jac361, const double *cov361,
+                                               double delta_time, const double *pn, int pn_rows, const Vector3d &iewn) {
     stateFromArray16(cur16, current_state_);
     current_state_.sodo = start_state_.sodo;
     current_state_.time = imu_buffer_.back().time;
@@ -185,8 +193,6 @@ void PreintegrationOdo::setIntegrationResult(const double *cur16, const double *
     delta_time_ = delta_time;
     pn_.assign(pn, pn + (pn ? 4 * (size_t) (pn_rows > 0 ? pn_rows : 0) : 0));
     iewn_ = iewn;
-    updateSqrtInformation();
-    dirty_ = false;
 }
 
 bool PreintegrationOdo::integrateBatch(icg_ctx *ctx, const vector<PreintegrationOdo *> &list, std::string *err) {
@@ -244,6 +250,61 @@ bool PreintegrationOdo::integrateBatch(icg_ctx *ctx, const vector<Preintegration
             const int b = offsets[k], cnt = offsets[k + 1] - offsets[k];
             p->setIntegrationResult(&cur[16 * k], &del[20 * k], &jac[(size_t) NN * k], &cov[(size_t) NN * k], dt[k],
                                     variant == (int) EARTH_ODO ? &pn[4 * (size_t) b] : nullptr, cnt - 1, p->iewn_);
+        }
+    }
+    return true;
+}
+
+bool PreintegrationOdo::integrateStreamsAvailable() { return &icg_preint_odo_batch_params != nullptr; }
+
+bool PreintegrationOdo::integrateStreams(icg_ctx *ctx, const vector<PreintegrationOdo *> &list, std::string *err) {
+    if (!integrateStreamsAvailable()) {
+        if (err) *err = "icg_preint_odo_batch_params is not in this build";
+        return false;
+    }
+    // one call per variant present: every interval brings its own parameter row, and the device forms the square-root information behind
+    // the integration (Preintegration::integrateStreams at 19 states)
+    for (int variant = (int) ODO; variant <= (int) EARTH_ODO; variant++) {
+        vector<PreintegrationOdo *> todo;
+        for (auto *p : list)
+            if (p->dirty_ && (int) p->variant_ == variant) todo.push_back(p);
+        if (todo.empty()) continue;
+        vector<int32_t> offsets{0};
+        vector<double> imu, state0, params;
+        for (auto *p : todo) {
+            for (const IMU &s : p->imu_buffer_) {
+                const double row[9] = {s.time, s.dt, s.dtheta[0], s.dtheta[1], s.dtheta[2], s.dvel[0], s.dvel[1], s.dvel[2], s.odovel};
+                imu.insert(imu.end(), row, row + 9);
+            }
+            offsets.push_back((int32_t) (imu.size() / 9));
+            double a[17];
+            stateToArray16(p->start_state_, a);
+            a[16] = p->start_state_.sodo;
+            state0.insert(state0.end(), a, a + 17);
+            const IntegrationParameters &P = *p->parameters_;
+            double row25[25]               = {P.gyr_arw,   P.acc_vrw,   P.gyr_bias_std, P.acc_bias_std, P.corr_time, P.gravity, p->iewn_[0],
+                                              p->iewn_[1], p->iewn_[2], P.odo_std[0],   P.odo_std[1],   P.odo_std[2], P.odo_srw};
+            vehicleRotation(P.abv, row25 + 13);
+            row25[22] = P.lodo[0], row25[23] = P.lodo[1], row25[24] = P.lodo[2];
+            params.insert(params.end(), row25, row25 + 25);
+        }
+        const size_t n = todo.size(), total = imu.size() / 9;
+        vector<double> cur(16 * n), del(20 * n), jac((size_t) NN * n), cov((size_t) NN * n), dt(n), pn(4 * total), S((size_t) NN * n);
+        vector<int32_t> status(n);
+        int rc = icg_preint_odo_batch_params(ctx, variant, (int) n, offsets.data(), imu.data(), state0.data(), params.data(), cur.data(),
+                                             del.data(), jac.data(), cov.data(), dt.data(), pn.data(), S.data(), status.data());
+        if (rc != ICG_OK) {
+            if (err) *err = icg_last_error(ctx);
+            return false;
+        }
+        for (size_t k = 0; k < n; k++) {
+            PreintegrationOdo *p = todo[k];
+            const int b = offsets[k], cnt = offsets[k + 1] - offsets[k];
+            p->storeIntegrationResult(&cur[16 * k], &del[20 * k], &jac[(size_t) NN * k], &cov[(size_t) NN * k], dt[k],
+                                      variant == (int) EARTH_ODO ? &pn[4 * (size_t) b] : nullptr, cnt - 1, p->iewn_);
+            p->sqrt_information_.assign(S.begin() + NN * (long) k, S.begin() + NN * (long) (k + 1));
+            p->sqrt_information_ok_ = status[k] == 0;
+            p->dirty_               = false;
         }
     }
     return true;

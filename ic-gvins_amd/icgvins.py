@@ -35,6 +35,7 @@ EXPORTS = [
     "icg_preint_odo_set", "icg_preint_odo_evaluate_resident", "icg_preint_odo_fetch_resident", "icg_reproj_host_parts_build_preint_odo",
     "icg_set_cameras", "icg_lk_track_fb_cams", "icg_reproj_error_batch_cams", "icg_tracker_create_cams",
     "icg_nav_set", "icg_nav_evaluate_resident", "icg_nav_correct_resident", "icg_nav_fetch_resident", "icg_reproj_host_parts_build_nav",
+    "icg_preint_batch_params", "icg_preint_odo_batch_params",
 ]
 
 
@@ -634,6 +635,34 @@ class Context:
         self._ck(self.lib.icg_preint_batch(self.h, int(variant), n, _p(offsets), _p(imu), _p(state0), _p(f64(params)),
                                             _p(cur), _p(delta), _p(jac), _p(cov), _p(dt), _p(pn)), "icg_preint_batch")
         return cur, delta, jac, cov, dt, pn
+
+    def _preint_params_call(self, fn, name, widths, variant, offsets, imu, state0, params, want_pn, want_sqrt_info, want_status, fill):
+        """the shared body of preint_batch_params / preint_odo_batch_params; widths = (imu, state0, params, delta, N)"""
+        w_imu, w_s0, w_par, w_del, N = widths
+        offsets = i32(offsets)
+        n = len(offsets) - 1
+        imu = f64(imu).reshape(-1, w_imu)
+        state0 = f64(state0).reshape(n, w_s0)
+        params = f64(params).reshape(n, w_par)
+        mk = lambda *shape: np.full(shape, fill, np.float64)
+        cur, delta, jac, cov, dt = mk(n, 16), mk(n, w_del), mk(n, N, N), mk(n, N, N), mk(n)
+        pn = mk(imu.shape[0], 4) if want_pn else None
+        S = mk(n, N, N) if want_sqrt_info else None
+        status = np.full(n, -1, np.int32) if want_status else None
+        self._ck(fn(self.h, int(variant), n, _p(offsets), _p(imu), _p(state0), _p(params), _p(cur), _p(delta), _p(jac), _p(cov), _p(dt), _p(pn),
+                    _p(S), _p(status)), name)
+        return cur, delta, jac, cov, dt, pn, S, status
+
+    def preint_batch_params(self, variant, offsets, imu, state0, params, want_pn=True, want_sqrt_info=True, want_status=True, fill=0.0):
+        """icg_preint_batch_params (params n x 9, one row per interval) -> (cur n x 16, delta n x 16, jac, cov n x 15 x 15, dt n, pn total x 4
+        or None, sqrt_info n x 15 x 15 or None, status n or None); the output arrays start out filled with `fill`"""
+        return self._preint_params_call(self.lib.icg_preint_batch_params, "icg_preint_batch_params", (8, 16, 9, 16, 15), variant, offsets, imu, state0,
+                                        params, want_pn, want_sqrt_info, want_status, fill)
+
+    def preint_odo_batch_params(self, variant, offsets, imu9, state0, params25, want_pn=True, want_sqrt_info=True, want_status=True, fill=0.0):
+        """icg_preint_odo_batch_params (params25 n x 25) -> as preint_batch_params with delta n x 20 and 19 x 19 matrices"""
+        return self._preint_params_call(self.lib.icg_preint_odo_batch_params, "icg_preint_odo_batch_params", (9, 17, 25, 20, 19), variant, offsets, imu9,
+                                        state0, params25, want_pn, want_sqrt_info, want_status, fill)
 
     # ---- P2
     def preint_evaluate_batch(self, variant, delta, jac, cov, dt, env, points, pn_offsets=None, pn=None, want_jac=True):

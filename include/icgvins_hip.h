@@ -428,6 +428,19 @@ int icg_reproj_chi2_cull(icg_ctx *ctx, double chi2, uint8_t *active);
 int icg_preint_batch(icg_ctx *ctx, int variant, int n_intervals, const int32_t *offsets, const double *imu,
                      const double *state0, const double *params, double *cur_state, double *delta_state, double *jac,
                      double *cov, double *delta_time, double *pn);
+/* icg_preint_batch for MANY STREAMS in one call: params is n x 9, interval s is integrated with row s (its own Earth rate, gravity and
+ * noise figures), so intervals of different stations and estimators share one launch.  Every other argument, every layout and the pn rule
+ * are icg_preint_batch's, and cur_state, delta_state, jac, cov, delta_time and pn of interval s have the bits icg_preint_batch returns for
+ * that interval alone with that row.
+ * sqrt_info (optional, n x 225) / status (optional, n; each on its own): the square-root information of every result,
+ * LLT(cov^-1).matrixL()^T, formed by a second launch behind the integration on the device's cov: the bits and the status
+ * icg_preint_evaluate_batch returns for that cov (status 1 and a zero matrix: singular covariance, e.g. an interval of one sample), which
+ * are the host layer's Preintegration::updateSqrtInformation bit for bit.  Both NULL: the second launch is not made.
+ * ICG_ERR_INVALID (nothing is launched, no output is touched; the message names the interval where there is one): variant not 0 or 1,
+ * n_intervals < 0, a NULL required pointer, offsets[0] < 0, an interval without a sample.  n_intervals == 0 is ICG_OK and touches nothing. */
+int icg_preint_batch_params(icg_ctx *ctx, int variant, int n_intervals, const int32_t *offsets, const double *imu,
+                            const double *state0, const double *params, double *cur_state, double *delta_state, double *jac,
+                            double *cov, double *delta_time, double *pn, double *sqrt_info, int32_t *status);
 
 /* ---- P2: PreintegrationFactor::Evaluate (preintegration/preintegration_factor.h:45-69 -> PreintegrationNormal::evaluate /
  * ::residualJacobianPose0..Mix1, preintegration_normal.cc:38-142; PreintegrationEarth, preintegration_earth.cc:37-164), batched over
@@ -459,6 +472,14 @@ int icg_preint_evaluate_batch(icg_ctx *ctx, int variant, int n_factors, const do
 int icg_preint_odo_batch(icg_ctx *ctx, int variant, int n_intervals, const int32_t *offsets, const double *imu9,
                          const double *state0, const double *params25, double *cur_state, double *delta_state, double *jac,
                          double *cov, double *delta_time, double *pn);
+/* icg_preint_odo_batch for many streams in one call, the 19-state twin of icg_preint_batch_params: params25 is n x 25, interval s is
+ * integrated with row s; the integration outputs of interval s have the bits icg_preint_odo_batch returns for it alone with that row.
+ * sqrt_info (optional, n x 361) / status (optional, n): formed behind the integration on the device's cov, the bits and the status of
+ * icg_preint_odo_evaluate_batch for that cov (PreintegrationOdo::updateSqrtInformation bit for bit); both NULL: no second launch.
+ * ICG_ERR_INVALID as icg_preint_batch_params, with variant 2 or 3. */
+int icg_preint_odo_batch_params(icg_ctx *ctx, int variant, int n_intervals, const int32_t *offsets, const double *imu9,
+                                const double *state0, const double *params25, double *cur_state, double *delta_state, double *jac,
+                                double *cov, double *delta_time, double *pn, double *sqrt_info, int32_t *status);
 
 /* ---- P2 of the odometer variants: PreintegrationFactor::Evaluate (preintegration_factor.h:45-69) -> PreintegrationOdo::evaluate /
  * ::residualJacobianPose0..Mix1 (preintegration_odo.cc:40-159); PreintegrationEarthOdo (preintegration_earth_odo.cc:41-183): the 19-state
