@@ -231,7 +231,7 @@ static int hp_rules_preint(icg_ctx *ctx, const char *me, int w, int p, int fp, c
 }
 
 static int hp_rules_preint_odo(icg_ctx *ctx, const char *me, int w, int p, int fp, const int32_t *pc, hp_prior &B) {
-    const icg_preint_odo_resident &ps = ctx->preint_odo;
+    const icg_preint_resident &ps = ctx->preint_odo;
     if (!pc) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: an odometer preintegration block without preint_odo_cols", me, w, p);
     if (ps.n <= 0 || !ps.res_valid || (B.fill && !ps.jac_valid))
         return icg_fail(ctx, ICG_ERR_INVALID,

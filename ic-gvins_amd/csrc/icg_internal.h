@@ -79,25 +79,14 @@ struct icg_marg_set {
     std::vector<int64_t> h_j_off;
 };
 
-// Resident preintegration factors (preint.hip): everything icg_preint_evaluate_resident needs besides the evaluation points and the
-// correction quaternions, in one buffer that grows on demand and is freed with the context; n = 0: no set is resident.  The results of the
-// last evaluation stay in d_res (15 per factor) and d_jac (15 x 32 row-major per factor).
+// Resident preintegration factors (preint_shared.h): everything *_evaluate_resident needs besides the evaluation points and the correction
+// quaternions, in one buffer that grows on demand and is freed with the context; n = 0: no set is resident.  One type for both families, one
+// member of the context each (preint: N = 15, delta 16, point 32; preint_odo: N = 19, delta 20, point 34), so a context may hold one set of
+// each at once.  The results of the last evaluation stay in d_res (N per factor) and d_jac (N x point row-major per factor).
 struct icg_preint_resident {
     int n = 0;
     int64_t total_pn = 0; // rows of pn
-    char *d_set = nullptr; // delta_state 16n | jac 225n | sqrt_info 225n | delta_time n | env 4n | q_nn 4n | pn 4 total_pn | pn_offsets n+1 | variant n
-    size_t set_cap = 0;    // bytes
-    double *d_res = nullptr, *d_jac = nullptr;
-    size_t res_cap = 0, jac_cap = 0; // bytes
-    bool res_valid = false, jac_valid = false; // evaluated (with Jacobians) since the set was made resident
-};
-
-// Resident odometer preintegration factors (preint_odo.hip): the 19-state twin of icg_preint_resident, beside it (a context may hold one set
-// of each at once).  The results of the last evaluation stay in d_res (19 per factor) and d_jac (19 x 34 row-major per factor).
-struct icg_preint_odo_resident {
-    int n = 0;
-    int64_t total_pn = 0; // rows of pn
-    char *d_set = nullptr; // delta_state 20n | jac 361n | sqrt_info 361n | delta_time n | env 4n | q_nn 4n | pn 4 total_pn | pn_offsets n+1 | variant n
+    char *d_set = nullptr; // delta_state delta n | jac NN n | sqrt_info NN n | delta_time n | env 4n | q_nn 4n | pn 4 total_pn | pn_offsets n+1 | variant n
     size_t set_cap = 0;    // bytes
     double *d_res = nullptr, *d_jac = nullptr;
     size_t res_cap = 0, jac_cap = 0; // bytes
@@ -213,8 +202,7 @@ struct icg_ctx {
     size_t lmwin_cap = 0; // bytes
 
     icg_marg_set marg;
-    icg_preint_resident preint;
-    icg_preint_odo_resident preint_odo;
+    icg_preint_resident preint, preint_odo;
     icg_nav_resident nav;
     // M3 (marg_linearize.hip): per-window working memory of icg_marg_linearize_batch for the windows that do not fit in LDS; grows on demand
     double *d_lin_scratch = nullptr;

@@ -1,6 +1,6 @@
 // Preintegration of boundary B1 (P1 on device; P2 on host per factor, or batched on device): reference
 // preintegration/preintegration{,_base,_normal,_earth}.{h,cc}, preintegration_factor.h.  Implemented in preintegration_hip.cc
-// (PreintegrationSet in preint_set_hip.cc).
+// (the batch drivers and small-matrix helpers shared with PreintegrationOdo in preint_common.h; PreintegrationSetT in preint_set_hip.cc).
 #pragma once
 #include <memory>
 #include <string>
@@ -49,6 +49,10 @@ struct IntegrationParameters { // integration_state.h:67-88
 class Preintegration {
 public:
     enum Variant { NORMAL = 0, EARTH = 1 };
+    // widths: error state, mix block, delta_state row, evaluation point (pose0 mix0 pose1 mix1), whitened Jacobians of one factor
+    static constexpr int NUM_STATE = 15, NUM_MIX = 9, NUM_DELTA = 16, NUM_POINT = 2 * (7 + NUM_MIX), NUM_JAC = NUM_STATE * NUM_POINT;
+    static constexpr Variant EARTH_VARIANT = EARTH; // the variant with pn rows and an Earth-rate quaternion
+    static void deltaToArray(const IntegrationState &s, double *a); // the delta_state row of the C entries (NUM_DELTA)
     Preintegration(std::shared_ptr<IntegrationParameters> parameters, const IMU &imu0, const IntegrationState &state, Variant v);
     void addNewImu(const IMU &imu) { imu_buffer_.push_back(imu); dirty_ = true; }
     void reintegration(const IntegrationState &state);
@@ -104,6 +108,10 @@ private:
     IntegrationState start_state_, current_state_, delta_state_;
     double delta_time_{0};
     void updateSqrtInformation();
+    struct Traits; // what the shared batch drivers (preint_common.h) need of this class
+    // one integration result of the C entries into the members, without the square-root information
+    void storeIntegrationResult(const double *cur16, const double *delta16, const double *jac225, const double *cov225, double delta_time,
+                                const double *pn, int pn_rows);
     vector<double> jacobian_, covariance_, pn_; // 15x15, 15x15, (n-1)x4
     vector<double> sqrt_information_;            // 15x15, of covariance_ (formed when an integration result arrives)
     bool sqrt_information_ok_{false};
@@ -124,27 +132,30 @@ private:
     std::shared_ptr<Preintegration> preintegration_;
 };
 
-// The preintegration factors of many windows resident on the device for a solve (icg_preint_set / icg_preint_evaluate_resident): set() at the
-// head of the solve, pack() + evaluateResident() per LM point.  The device gets the host's square-root information and the two quaternions
-// of Preintegration::evaluate that need sin / cos (earthRateQuaternion with the set, correctionQuaternion with every point); its residuals,
-// Jacobians and squared norms are then the bits of Preintegration::evaluate.  The results stay on the device for
-// icg_reproj_host_parts_build_preint; only one squared norm per factor comes back.  The C entries are referenced weakly: in a build of this
-// layer on a C ABI without them available() is false, missingEntry() names the first that is absent and set() fails by that name.
-class PreintegrationSet {
+// The preintegration factors of many windows resident on the device for a solve (P = Preintegration: icg_preint_set /
+// icg_preint_evaluate_resident; P = PreintegrationOdo: icg_preint_odo_set / icg_preint_odo_evaluate_resident; each family has its own
+// resident set in the context, both may be resident at once): set() at the head of the solve, pack() + evaluateResident() per LM point.  The
+// device gets the host's square-root information and the two quaternions of P::evaluate that need sin / cos (earthRateQuaternion with the
+// set, correctionQuaternion with every point); its residuals, Jacobians and squared norms are then the bits of P::evaluate.  The results stay
+// on the device for icg_reproj_host_parts_build_preint*; only one squared norm per factor comes back.  The C entries are referenced weakly,
+// per family: in a build of this layer on a C ABI without them available() is false, missingEntry() names the first that is absent and set()
+// fails by that name.  Implemented, and instantiated for the two classes, in preint_set_hip.cc.
+template <class P> class PreintegrationSetT {
 public:
     static bool available();
     static const char *missingEntry(); // nullptr when available()
     // every factor must be ready() (integrated, covariance not singular); the objects must outlive the set's use
-    bool set(icg_ctx *ctx, const vector<const Preintegration *> &list, std::string *err = nullptr);
-    // factor f's evaluation point (pose0, mix0, pose1, mix1) and its correction quaternion to their places (any thread, before the call)
+    bool set(icg_ctx *ctx, const vector<const P *> &list, std::string *err = nullptr);
+    // factor f's evaluation point (pose0[7], mix0, pose1[7], mix1) and its correction quaternion to their places (any thread, before the call)
     void pack(size_t f, const double *const *parameters);
     bool evaluateResident(bool want_jac, double *sq_norm, std::string *err = nullptr);
     int factors() const { return (int) list_.size(); }
 
 private:
     icg_ctx *ctx_{nullptr};
-    vector<const Preintegration *> list_;
+    vector<const P *> list_;
     vector<double> points_, q_corr_;
 };
+using PreintegrationSet = PreintegrationSetT<Preintegration>;
 
 } // namespace icg

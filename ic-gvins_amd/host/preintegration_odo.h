@@ -30,7 +30,9 @@ inline void odoStateFromMix(const double mix[10], IntegrationState &s) {
 class PreintegrationOdo {
 public:
     enum Variant { ODO = 2, EARTH_ODO = 3 }; // the numbers of icg_preint_odo_batch (the reference's own enum numbers them 1 and 3)
-    static constexpr int NUM_STATE = 19, NUM_MIX = 10, NUM_JAC = 19 * (7 + 10 + 7 + 10);
+    static constexpr int NUM_STATE = 19, NUM_MIX = 10, NUM_DELTA = 20, NUM_POINT = 2 * (7 + NUM_MIX), NUM_JAC = NUM_STATE * NUM_POINT;
+    static constexpr Variant EARTH_VARIANT = EARTH_ODO; // the variant with pn rows and an Earth-rate quaternion
+    static void deltaToArray(const IntegrationState &s, double *a); // the delta_state row of the C entries (NUM_DELTA: the 16, s3, sodo)
     PreintegrationOdo(std::shared_ptr<IntegrationParameters> parameters, const IMU &imu0, const IntegrationState &state, Variant v);
     void addNewImu(const IMU &imu) { imu_buffer_.push_back(imu); dirty_ = true; }
     void reintegration(const IntegrationState &state);
@@ -93,6 +95,7 @@ private:
     IntegrationState start_state_, current_state_, delta_state_;
     double delta_time_{0};
     void updateSqrtInformation();
+    struct Traits; // what the shared batch drivers (preint_common.h) need of this class
     // setIntegrationResult without the square-root information (integrateStreams takes that from the device)
     void storeIntegrationResult(const double *cur16, const double *delta20, const double *jac361, const double *cov361, double delta_time,
                                 const double *pn, int pn_rows, const Vector3d &iewn);
@@ -115,28 +118,7 @@ private:
     std::shared_ptr<PreintegrationOdo> preintegration_;
 };
 
-// The odometer preintegration factors of many windows resident on the device (icg_preint_odo_set / icg_preint_odo_evaluate_resident): the
-// 19-state twin of PreintegrationSet, with its own resident set in the context (both may be resident at once).  set() once, pack() +
-// evaluateResident() per evaluation point.  The device gets the host's square-root information and the two quaternions of
-// PreintegrationOdo::evaluate that need sin / cos (earthRateQuaternion with the set, correctionQuaternion with every point); its residuals,
-// Jacobians and squared norms are then the bits of PreintegrationOdo::evaluate, and only one squared norm per factor comes back.  The C
-// entries are referenced weakly: in a build of this layer on a C ABI without them available() is false, missingEntry() names the first
-// that is absent and set() fails by that name.
-class PreintegrationOdoSet {
-public:
-    static bool available();
-    static const char *missingEntry(); // nullptr when available()
-    // every factor must be ready() (integrated, covariance not singular); the objects must outlive the set's use
-    bool set(icg_ctx *ctx, const vector<const PreintegrationOdo *> &list, std::string *err = nullptr);
-    // factor f's evaluation point (pose0[7], mix0[10], pose1[7], mix1[10]) and its correction quaternion to their places (any thread)
-    void pack(size_t f, const double *const *parameters);
-    bool evaluateResident(bool want_jac, double *sq_norm, std::string *err = nullptr);
-    int factors() const { return (int) list_.size(); }
-
-private:
-    icg_ctx *ctx_{nullptr};
-    vector<const PreintegrationOdo *> list_;
-    vector<double> points_, q_corr_;
-};
+// The odometer preintegration factors of many windows resident on the device: PreintegrationSetT (preintegration.h) for this class.
+using PreintegrationOdoSet = PreintegrationSetT<PreintegrationOdo>;
 
 } // namespace icg
