@@ -1,11 +1,11 @@
 // C entry points of libicgvins_host.so: the preintegration factor with its trigonometric part split out (Preintegration::evaluateGiven), for
-// tests that feed the device's resident evaluation (icg_preint_set / icg_preint_evaluate_resident) from the host's own values.
-//
-// and WindowSolverBatch::setDevicePreintegration on the windows of icgh_backend_solve_prior_batch (solve_vio_windows, capi_solve_windows.h).
+// tests that feed the device's resident evaluation (icg_preint_set / icg_preint_evaluate_resident) from the host's own values (the per-factor
+// body: preint_eval_split_factor, capi_preint_streams.h), and WindowSolverBatch::setDevicePreintegration on the windows of
+// icgh_backend_solve_prior_batch (solve_vio_windows, capi_solve_windows.h).
 #include <memory>
 #include <string>
 
-#include "factors.h"
+#include "capi_preint_streams.h"
 #include "capi_solve_windows.h"
 
 using namespace icg;
@@ -46,22 +46,14 @@ int icgh_backend_preint_eval_split(int variant, int n, const int32_t *offsets, c
         pn_offsets[0] = 0;
         for (size_t k = 0; k < N; k++) {
             const Preintegration &p = *pre[k];
-            const double *ep        = points + 32 * k;
-            const double *pp[4]     = {ep, ep + 7, ep + 16, ep + 23};
-            double *je[4] = {J_eval + 480 * k, J_eval + 480 * k + 105, J_eval + 480 * k + 240, J_eval + 480 * k + 345};
-            double *jg[4] = {J_given + 480 * k, J_given + 480 * k + 105, J_given + 480 * k + 240, J_given + 480 * k + 345};
-            p.correctionQuaternion(pp[1], q_corr + 4 * k);
-            p.earthRateQuaternion(q_nn + 4 * k);
-            const bool a = p.evaluate(pp, r_eval + 15 * k, je);
-            const bool b = p.evaluateGiven(pp, q_corr_in ? q_corr_in + 4 * k : q_corr + 4 * k, q_nn + 4 * k, r_given + 15 * k, jg);
-            ok[k]        = a && b ? 1 : 0;
-            memcpy(sqrt_info + 225 * k, p.sqrtInformation().data(), sizeof(double) * 225);
+            ok[k] = preint_eval_split_factor(p, points + 32 * k, q_corr_in ? q_corr_in + 4 * k : nullptr, nullptr, r_eval + 15 * k, J_eval + 480 * k, r_given + 15 * k,
+                                             J_given + 480 * k, q_corr + 4 * k, q_nn + 4 * k, sqrt_info + 225 * k, env + 4 * k)
+                        ? 1
+                        : 0;
             preint_put_state(p.currentState(), cur_state + 16 * k);
             preint_put_state(p.deltaState(), delta_state + 16 * k);
             memcpy(jac + 225 * k, p.jacobian().data(), sizeof(double) * 225);
             delta_time[k] = p.deltaTime();
-            env[4 * k]    = p.gravity();
-            for (int i = 0; i < 3; i++) env[4 * k + 1 + i] = p.earthRate()[i];
             const size_t rows = p.pnRows().size() / 4;
             if ((size_t) pn_offsets[k] + rows > (size_t) pn_cap) {
                 set_err(err, errlen, "pn does not fit");

@@ -1,12 +1,13 @@
 // C entry points of libicgvins_host.so: the odometer preintegration factor with its trigonometric part split out
 // (PreintegrationOdo::evaluateGiven), for tests that feed the device's resident evaluation (icg_preint_odo_set /
 // icg_preint_odo_evaluate_resident) from the host's own values, and WindowSolverBatch::setDevicePreintegration on visual-inertial windows
-// whose motion factors are PreintegrationOdoFactors.  The 19-state twin of capi_solve_preint.cc.
+// whose motion factors are PreintegrationOdoFactors.  The 19-state twin of capi_solve_preint.cc; the per-factor body of the split entry is shared
+// (preint_eval_split_factor, capi_preint_streams.h).
 #include <chrono>
 #include <memory>
 #include <string>
 
-#include "preintegration_odo.h"
+#include "capi_preint_streams.h"
 #include "capi_solve_windows.h"
 
 using namespace icg;
@@ -43,19 +44,10 @@ int icgh_backend_preint_odo_eval_split(int n, const int32_t *variant, const doub
             const int rows = variant[k] == 3 && pn_offsets ? pn_offsets[k + 1] - pn_offsets[k] : 0;
             const auto obj = odo_from_result(P, variant[k], delta_state + 20 * k, jac + 361 * k, cov + 361 * k, delta_time[k],
                                              rows > 0 ? pn + 4 * (size_t) pn_offsets[k] : nullptr, rows, iewn + 3 * k);
-            const PreintegrationOdo &p = *obj;
-            const double *ep    = points + 34 * k;
-            const double *pp[4] = {ep, ep + 7, ep + 17, ep + 24};
-            double *je[4] = {J_eval + 646 * k, J_eval + 646 * k + 133, J_eval + 646 * k + 323, J_eval + 646 * k + 456};
-            double *jg[4] = {J_given + 646 * k, J_given + 646 * k + 133, J_given + 646 * k + 323, J_given + 646 * k + 456};
-            p.correctionQuaternion(pp[1], q_corr + 4 * k);
-            p.earthRateQuaternion(q_nn + 4 * k);
-            const bool a = p.evaluate(pp, r_eval + 19 * k, je);
-            const bool b = p.evaluateGiven(pp, q_corr_in ? q_corr_in + 4 * k : q_corr + 4 * k, q_nn_in ? q_nn_in + 4 * k : q_nn + 4 * k, r_given + 19 * k, jg);
-            ok[k]        = a && b ? 1 : 0;
-            memcpy(sqrt_info + 361 * k, p.sqrtInformation().data(), sizeof(double) * 361);
-            env[4 * k] = p.gravity();
-            for (int i = 0; i < 3; i++) env[4 * k + 1 + i] = p.earthRate()[i];
+            ok[k] = preint_eval_split_factor(*obj, points + 34 * k, q_corr_in ? q_corr_in + 4 * k : nullptr, q_nn_in ? q_nn_in + 4 * k : nullptr, r_eval + 19 * k,
+                                             J_eval + 646 * k, r_given + 19 * k, J_given + 646 * k, q_corr + 4 * k, q_nn + 4 * k, sqrt_info + 361 * k, env + 4 * k)
+                        ? 1
+                        : 0;
         }
         return 0;
     });

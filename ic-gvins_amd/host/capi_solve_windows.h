@@ -43,34 +43,6 @@ private:
     icg::MargPriorView view_;
 };
 
-// ---- the odometer windows (capi_solve_preint_odo.cc, capi_solve_nav.cc): parameters of 19 and objects from GIVEN integration results
-std::shared_ptr<icg::IntegrationParameters> odo_params19(const double *params19) {
-    using icg::Vector3d;
-    auto P     = preint_params(params19);
-    P->odo_std = Vector3d(params19[9], params19[10], params19[11]);
-    P->odo_srw = params19[12];
-    P->abv     = Vector3d(params19[13], params19[14], params19[15]);
-    P->lodo    = Vector3d(params19[16], params19[17], params19[18]);
-    return P;
-}
-
-// a PreintegrationOdo as if integrateBatch had returned the given result (no device, no IMU samples)
-std::shared_ptr<icg::PreintegrationOdo> odo_from_result(const std::shared_ptr<icg::IntegrationParameters> &P, int variant, const double *delta20,
-                                                        const double *jac361, const double *cov361, double delta_time, const double *pn, int pn_rows,
-                                                        const double *iewn3) {
-    using namespace icg;
-    IntegrationState st;
-    st.bg   = Vector3d(delta20[10], delta20[11], delta20[12]);
-    st.ba   = Vector3d(delta20[13], delta20[14], delta20[15]);
-    st.sodo = delta20[19];
-    auto p  = std::make_shared<PreintegrationOdo>(P, IMU(), st, variant == 2 ? PreintegrationOdo::ODO : PreintegrationOdo::EARTH_ODO);
-    double cur16[16];
-    preint_put_state(st, cur16);
-    p->setIntegrationResult(cur16, delta20, jac361, cov361, delta_time, pn_rows > 0 ? pn : nullptr, pn_rows > 0 ? pn_rows : 0,
-                            Vector3d(iewn3[0], iewn3[1], iewn3[2]));
-    return p;
-}
-
 // ---- the batch of visual-inertial windows ---------------------------------------------------------------------------------------------
 // What the four entries take, each documented where it is exported; a group an entry does not have is NULL / 0.
 struct VioBatchArgs {

@@ -10,6 +10,7 @@
 
 #include "factors.h"
 #include "misc_hip.h"
+#include "preintegration_odo.h"
 
 namespace {
 
@@ -127,6 +128,33 @@ std::shared_ptr<icg::Preintegration> preint_interval(int variant, const std::sha
     auto p = std::make_shared<icg::Preintegration>(params, ins_imu(imu + 8 * (size_t) offsets[k]), preint_state(state16),
                                                    variant ? icg::Preintegration::EARTH : icg::Preintegration::NORMAL);
     for (int row = offsets[k] + 1; row < offsets[k + 1]; row++) p->addNewImu(ins_imu(imu + 8 * (size_t) row));
+    return p;
+}
+// ---- the odometer family: parameters of 19 ([0..8] as icg_preint_batch, [9..11] odo_std, [12] odo_srw, [13..15] abv, [16..18] lodo; the host
+// forms cvb from abv) and objects from GIVEN integration results
+std::shared_ptr<icg::IntegrationParameters> odo_params19(const double *params19) {
+    using icg::Vector3d;
+    auto P     = preint_params(params19);
+    P->odo_std = Vector3d(params19[9], params19[10], params19[11]);
+    P->odo_srw = params19[12];
+    P->abv     = Vector3d(params19[13], params19[14], params19[15]);
+    P->lodo    = Vector3d(params19[16], params19[17], params19[18]);
+    return P;
+}
+// a PreintegrationOdo as if integrateBatch had returned the given result (no device, no IMU samples)
+std::shared_ptr<icg::PreintegrationOdo> odo_from_result(const std::shared_ptr<icg::IntegrationParameters> &P, int variant, const double *delta20,
+                                                        const double *jac361, const double *cov361, double delta_time, const double *pn, int pn_rows,
+                                                        const double *iewn3) {
+    using namespace icg;
+    IntegrationState st;
+    st.bg   = Vector3d(delta20[10], delta20[11], delta20[12]);
+    st.ba   = Vector3d(delta20[13], delta20[14], delta20[15]);
+    st.sodo = delta20[19];
+    auto p  = std::make_shared<PreintegrationOdo>(P, IMU(), st, variant == 2 ? PreintegrationOdo::ODO : PreintegrationOdo::EARTH_ODO);
+    double cur16[16];
+    preint_put_state(st, cur16);
+    p->setIntegrationResult(cur16, delta20, jac361, cov361, delta_time, pn_rows > 0 ? pn : nullptr, pn_rows > 0 ? pn_rows : 0,
+                            Vector3d(iewn3[0], iewn3[1], iewn3[2]));
     return p;
 }
 // factor k of the 15 x n observation table (column c of factor k at obs_soa[c * n + k])

@@ -61,7 +61,7 @@ template <class P> bool PreintegrationSetT<P>::set(icg_ctx *ctx, const vector<co
         }
         variant[f] = (int32_t) p.variant();
         any_earth |= p.variant() == P::EARTH_VARIANT;
-        P::deltaToArray(p.deltaState(), &del[DELTA * f]);
+        P::deltaRow(p.deltaState(), &del[DELTA * f]);
         memcpy(&jac[NN * f], p.jacobian().data(), sizeof(double) * NN);
         memcpy(&S[NN * f], p.sqrtInformation().data(), sizeof(double) * NN);
         dt[f]      = p.deltaTime();

@@ -4,7 +4,7 @@
 //     lists and window live in HBM, a wave per stream runs the stage body between two device primitives, the primitives (preprocess, LK,
 //     RANSAC, triangulation, detection) read their work lists where the stage body left them; the host neither builds lists nor waits
 //     between stages (round 4);
-//   * by g++ (host/track_core_engine.cc): the same bodies behind the staged interface of TrackingBatch, on the oracle-backed checker build
+//   * by g++ (host/track_table_core.cc): the same bodies behind the staged interface of TrackingBatch, on the oracle-backed checker build
 //     and on the product's host layer — the CPU-side twin that pins the core against the track table (host/track_table.cc), which is
 //     itself pinned bit for bit against the reference's own tracking.cc (tests/golden/tracking_ref_*.npz).
 // The state is the track table's, member for member (track_table.h): 72-byte feature rows in insertion order with the reference
