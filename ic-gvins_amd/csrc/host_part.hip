@@ -200,69 +200,69 @@ struct hp_family {
     size_t at;                // walks cols over the family's blocks of ALL windows (a window that is not rebuilt still places the others')
 };
 
+// What every family asks first: is its set (n members, results o, made resident by <stem>_set and evaluated by <stem>_evaluate_resident) resident and
+// evaluated, with Jacobians when the block gathers them, and is member idx inside it?  what: the set's noun; member, set: the nouns of the second
+// refusal; pending: a refusal of the family's own that stands between the two (NULL: none).
+static int hp_require(icg_ctx *ctx, const char *me, int w, int p, const icg_resident_results &o, int n, bool need_jac, int idx, const char *what, const char *stem,
+                      const char *member, const char *set, const char *pending = nullptr) {
+    if (n <= 0 || !o.res_valid || (need_jac && !o.jac_valid))
+        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no %s set is resident and evaluated%s (%s_set, then %s_evaluate_resident)", me, w, p, what,
+                        need_jac ? " with Jacobians" : "", stem, stem);
+    if (pending) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %s", me, w, p, pending);
+    if (idx >= n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %s %d outside the resident %sset of %d", me, w, p, member, idx, set, n);
+    return ICG_OK;
+}
+
 static int hp_rules_prior(icg_ctx *ctx, const char *me, int w, int p, int pp, const int32_t *pc, hp_prior &B) {
     const icg_marg_set &ms = ctx->marg;
     if (!pc) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a prior block without prior_cols", me, w, p);
-    if (ms.n <= 0 || !ms.res_valid)
-        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no prior set is resident and evaluated (icg_marg_prior_set, then icg_marg_prior_evaluate_resident)",
-                        me, w, p);
-    if (pp >= ms.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: prior %d outside the resident set of %d", me, w, p, pp, ms.n);
+    if (int rc = hp_require(ctx, me, w, p, ms.out, ms.n, false, pp, "prior", "icg_marg_prior", "prior", "")) return rc; // (J0 is the set's own: no Jacobians to ask for)
     const int pr = ms.h_r[(size_t) pp];
     if (B.nr != pr) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, prior %d has %d", me, w, p, B.nr, pp, pr);
     for (int x = 0; x < B.nf; x++)
         if (pc[x] < 0 || pc[x] >= pr) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: prior column %d outside the prior (%d)", me, w, p, pc[x], pr);
-    B.J = ms.d_J + ms.h_j_off[(size_t) pp], B.res = ms.d_res + ms.h_e_off[(size_t) pp], B.stride = pr; // (J0 is r x r)
+    B.J = ms.d_J + ms.h_j_off[(size_t) pp], B.res = ms.out.d_res + ms.h_e_off[(size_t) pp], B.stride = pr; // (J0 is r x r)
     return ICG_OK;
 }
 
 static int hp_rules_preint(icg_ctx *ctx, const char *me, int w, int p, int fp, const int32_t *pc, hp_prior &B) {
     const icg_preint_resident &ps = ctx->preint;
     if (!pc) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a preintegration block without preint_cols", me, w, p);
-    if (ps.n <= 0 || !ps.res_valid || (B.fill && !ps.jac_valid))
-        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no preintegration set is resident and evaluated%s (icg_preint_set, then icg_preint_evaluate_resident)",
-                        me, w, p, B.fill ? " with Jacobians" : "");
-    if (fp >= ps.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: factor %d outside the resident set of %d", me, w, p, fp, ps.n);
+    if (int rc = hp_require(ctx, me, w, p, ps.out, ps.n, B.fill, fp, "preintegration", "icg_preint", "factor", "")) return rc;
     if (B.nr != 15) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, a preintegration factor has 15", me, w, p, B.nr);
     for (int x = 0; x < B.nf; x++)
         if (pc[x] < 0 || pc[x] >= 32 || pc[x] == 6 || pc[x] == 22)
             return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: preintegration column %d (0 .. 31 without 6 and 22)", me, w, p, pc[x]);
-    B.J = ps.d_jac ? ps.d_jac + 480 * (size_t) fp : nullptr, B.res = ps.d_res + 15 * (size_t) fp, B.stride = 32; // (the whitened 15 x 32 Jacobian)
+    B.J = ps.out.d_jac ? ps.out.d_jac + 480 * (size_t) fp : nullptr, B.res = ps.out.d_res + 15 * (size_t) fp, B.stride = 32; // (the whitened 15 x 32 Jacobian)
     return ICG_OK;
 }
 
 static int hp_rules_preint_odo(icg_ctx *ctx, const char *me, int w, int p, int fp, const int32_t *pc, hp_prior &B) {
     const icg_preint_resident &ps = ctx->preint_odo;
     if (!pc) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: an odometer preintegration block without preint_odo_cols", me, w, p);
-    if (ps.n <= 0 || !ps.res_valid || (B.fill && !ps.jac_valid))
-        return icg_fail(ctx, ICG_ERR_INVALID,
-                        "%s: window %d, block %d: no odometer preintegration set is resident and evaluated%s (icg_preint_odo_set, then icg_preint_odo_evaluate_resident)", me,
-                        w, p, B.fill ? " with Jacobians" : "");
-    if (fp >= ps.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: factor %d outside the resident odometer set of %d", me, w, p, fp, ps.n);
+    if (int rc = hp_require(ctx, me, w, p, ps.out, ps.n, B.fill, fp, "odometer preintegration", "icg_preint_odo", "factor", "odometer ")) return rc;
     if (B.nr != 19) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, an odometer preintegration factor has 19", me, w, p, B.nr);
     for (int x = 0; x < B.nf; x++)
         if (pc[x] < 0 || pc[x] >= 34 || pc[x] == 6 || pc[x] == 23)
             return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: odometer preintegration column %d (0 .. 33 without 6 and 23)", me, w, p, pc[x]);
-    B.J = ps.d_jac ? ps.d_jac + 646 * (size_t) fp : nullptr, B.res = ps.d_res + 19 * (size_t) fp, B.stride = 34; // (the whitened 19 x 34 Jacobian)
+    B.J = ps.out.d_jac ? ps.out.d_jac + 646 * (size_t) fp : nullptr, B.res = ps.out.d_res + 19 * (size_t) fp, B.stride = 34; // (the whitened 19 x 34 Jacobian)
     return ICG_OK;
 }
 
 static int hp_rules_nav(icg_ctx *ctx, const char *me, int w, int p, int fp, const int32_t *pc, hp_prior &B) {
     const icg_nav_resident &ns = ctx->nav;
     if (!pc) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: a navigation block without nav_cols", me, w, p);
-    if (ns.n <= 0 || !ns.res_valid || (B.fill && !ns.jac_valid))
-        return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: no nav set is resident and evaluated%s (icg_nav_set, then icg_nav_evaluate_resident)", me, w, p,
-                        B.fill ? " with Jacobians" : "");
-    if (B.fill && ns.any_robust && !ns.corrected)
-        return icg_fail(ctx, ICG_ERR_INVALID,
-                        "%s: window %d, block %d: the nav set has robustified members and its last evaluation is not corrected (icg_nav_correct_resident first)", me, w, p);
-    if (fp >= ns.n) return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: member %d outside the resident nav set of %d", me, w, p, fp, ns.n);
+    const char *uncorrected = B.fill && ns.any_robust && !ns.corrected
+                                  ? "the nav set has robustified members and its last evaluation is not corrected (icg_nav_correct_resident first)"
+                                  : nullptr;
+    if (int rc = hp_require(ctx, me, w, p, ns.out, ns.n, B.fill, fp, "nav", "icg_nav", "member", "nav ", uncorrected)) return rc;
     const int kind = ns.h_kind[(size_t) fp], width = icg_nav_width(kind);
     if (B.nr != icg_nav_nr(kind))
         return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: %d residuals, nav member %d (kind %d) has %d", me, w, p, B.nr, fp, kind, icg_nav_nr(kind));
     for (int x = 0; x < B.nf; x++)
         if (pc[x] < 0 || pc[x] >= width || (width == 7 && pc[x] == 6))
             return icg_fail(ctx, ICG_ERR_INVALID, "%s: window %d, block %d: navigation column %d (0 .. %d%s)", me, w, p, pc[x], width - 1, width == 7 ? " without 6" : "");
-    B.J = ns.d_jac ? ns.d_jac + ns.h_j_off[(size_t) fp] : nullptr, B.res = ns.d_res + ns.h_r_off[(size_t) fp], B.stride = width; // (row-major nr x width)
+    B.J = ns.out.d_jac ? ns.out.d_jac + ns.h_j_off[(size_t) fp] : nullptr, B.res = ns.out.d_res + ns.h_r_off[(size_t) fp], B.stride = width; // (row-major nr x width)
     return ICG_OK;
 }
 
@@ -448,7 +448,7 @@ struct hp_staged { // what hp_stage uploaded, as hp_launch passes it on
     const int32_t *d_cols, *d_pc;
     const hp_prior *d_pr;
     double *d_r;
-    const double *d_Jnew = nullptr;
+    double *d_Jnew = nullptr;
 };
 
 // Stage 3.  The tables of the kernels, the columns, r and the shipped Jacobians into the arena, and up in one copy.
@@ -488,21 +488,17 @@ static int hp_stage(icg_ctx *ctx, const hp_args &a, const hp_family (&F)[HP_FAMI
         // like the shipped Jacobians below.  Whatever bytes the arena holds there go up with the rest; for the rebuilt windows
         // k_host_part_prior overwrites them on the device, in stream order behind the upload and ahead of k_host_part, and the blocks of
         // the other windows are not consumed.
-        const size_t off = icg_arena_alloc(ctx, sizeof(double) * n_r);
-        double *h        = icg_h<double>(ctx, off);
+        double *h = c.stage<double>(n_r, &S.d_r);
+        if (!h) return c.overflowed();
         for (int b = 0; b < nb; b++)
             if (std::none_of(F, F + HP_FAMILIES, [b](const hp_family &G) { return G.of && G.of[b] >= 0; })) memcpy(h + plan.r_off[(size_t) b], a.r + plan.r_off[(size_t) b], sizeof(double) * (size_t) a.nr[b]);
-        c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * n_r);
-        S.d_r = icg_d<double>(ctx, off);
     }
     if (ship_doubles) { // the shipped Jacobians, block after block
-        const size_t off = icg_arena_alloc(ctx, sizeof(double) * ship_doubles);
-        double *h        = icg_h<double>(ctx, off);
+        double *h = c.stage<double>(ship_doubles, &S.d_Jnew);
+        if (!h) return c.overflowed();
         for (int w = 0; w < W; w++)
             for (int b = a.blk_off[w]; a.rebuild[w] && b < a.blk_off[w + 1]; b++)
                 if (a.jac_off[b] >= 0) memcpy(h, a.J + a.jac_off[b], sizeof(double) * (size_t) a.nr[b] * a.nf[b]), h += (size_t) a.nr[b] * a.nf[b];
-        c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + sizeof(double) * ship_doubles);
-        S.d_Jnew = icg_d<double>(ctx, off);
     }
     return c.seal();
 }

@@ -3,6 +3,7 @@
 #include <utility>
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -59,6 +60,16 @@ struct icg_partition {
     icg_asm_plan plan;
 };
 
+// What the evaluation of a resident factor set leaves on the device, and whether it may be read: the record every set below embeds, and
+// the one place its protocol is written.  The buffers grow on demand and are freed with the context.  A *_set entry invalidates first
+// (the old set is gone, also when the call then fails); an evaluation reserves, invalidates again behind its launch guard and ends after finish();
+// every reader asks icg_resident_require.  A flag left true over a replaced buffer would let a kernel read freed memory.
+struct icg_resident_results {
+    double *d_res = nullptr, *d_jac = nullptr;
+    size_t res_cap = 0, jac_cap = 0;           // bytes
+    bool res_valid = false, jac_valid = false; // evaluated (with Jacobians) since the set was made resident
+};
+
 // Resident marginalization priors (marg.hip): everything icg_marg_prior_evaluate needs besides x.  The buffers grow on demand and are
 // freed with the context; n = 0: no set is resident.
 struct icg_marg_set {
@@ -69,10 +80,7 @@ struct icg_marg_set {
     char *d_meta = nullptr; // offsets and block layout (marg.hip marg_view)
     size_t J_cap = 0, e0_cap = 0, x0_cap = 0, meta_cap = 0; // bytes
     std::vector<int64_t> h_meta;
-    // the residuals of the last icg_marg_prior_evaluate_resident (total_r), read in place by icg_reproj_host_parts_build_prior
-    double *d_res = nullptr;
-    size_t res_cap = 0;     // bytes
-    bool res_valid = false; // evaluated since the set was made resident
+    icg_resident_results out; // d_res: the residuals of the last icg_marg_prior_evaluate_resident (total_r), read in place by icg_reproj_host_parts_build_prior; the Jacobian half is never reserved
     // what the host-part entry validates and places a prior block by (n entries each, written by icg_marg_prior_set beside h_meta): the
     // retained size of window w, its first residual and the first element of its J0
     std::vector<int32_t> h_r, h_e_off;
@@ -82,19 +90,17 @@ struct icg_marg_set {
 // Resident preintegration factors (preint_shared.h): everything *_evaluate_resident needs besides the evaluation points and the correction
 // quaternions, in one buffer that grows on demand and is freed with the context; n = 0: no set is resident.  One type for both families, one
 // member of the context each (preint: N = 15, delta 16, point 32; preint_odo: N = 19, delta 20, point 34), so a context may hold one set of
-// each at once.  The results of the last evaluation stay in d_res (N per factor) and d_jac (N x point row-major per factor).
+// each at once.  The results of the last evaluation stay in out.d_res (N per factor) and out.d_jac (N x point row-major per factor).
 struct icg_preint_resident {
     int n = 0;
     int64_t total_pn = 0; // rows of pn
     char *d_set = nullptr; // delta_state delta n | jac NN n | sqrt_info NN n | delta_time n | env 4n | q_nn 4n | pn 4 total_pn | pn_offsets n+1 | variant n
     size_t set_cap = 0;    // bytes
-    double *d_res = nullptr, *d_jac = nullptr;
-    size_t res_cap = 0, jac_cap = 0; // bytes
-    bool res_valid = false, jac_valid = false; // evaluated (with Jacobians) since the set was made resident
+    icg_resident_results out;
 };
 
 // Resident navigation factors (nav.hip): kinds, offsets and constants of the members in one buffer that grows on demand and is freed with the
-// context; n = 0: no set is resident.  The results of the last evaluation stay in d_res (nr per member) and d_jac (nr x width row-major per
+// context; n = 0: no set is resident.  The results of the last evaluation stay in out.d_res (nr per member) and out.d_jac (nr x width row-major per
 // member), both concatenated in member order.
 struct icg_nav_resident {
     int n = 0;
@@ -102,9 +108,7 @@ struct icg_nav_resident {
     char *d_set = nullptr; // aux total_aux | kind n | aux_off n | r_off n+1 | j_off n+1 | p_off n+1
     size_t set_cap = 0;    // bytes
     std::vector<int32_t> h_kind, h_r_off, h_j_off, h_p_off; // host copies: widths place the points, offsets place a member for the host-part entry
-    double *d_res = nullptr, *d_jac = nullptr;
-    size_t res_cap = 0, jac_cap = 0; // bytes
-    bool res_valid = false, jac_valid = false; // evaluated (with Jacobians) since the set was made resident
+    icg_resident_results out;
     bool corrected = false;                    // icg_nav_correct_resident ran on what the last evaluation kept
     bool any_robust = false;                   // a correction of this set has marked a member: the host-part gather then waits for every evaluation's correction
 };
@@ -271,6 +275,36 @@ int icg_hip_check(icg_ctx *ctx, hipError_t e, const char *what);
 // contents has to be invalidated on it, before the return code is looked at.
 int icg_grow(icg_ctx *ctx, void **p, size_t *cap, size_t want, size_t alloc, bool *replaced = nullptr);
 
+// resident results (icg_resident_results) ------------------------------------------------------------------
+static inline void icg_resident_invalidate(icg_resident_results &o) { o.res_valid = o.jac_valid = false; }
+// room for an evaluation's results, without slack (a set's size changes rarely); jac_bytes = 0: the Jacobian half is left alone.  A buffer
+// that was replaced loses its flag before the return code is looked at.
+static inline int icg_resident_reserve(icg_ctx *ctx, icg_resident_results &o, size_t res_bytes, size_t jac_bytes) {
+    bool replaced = false;
+    int rc        = icg_grow(ctx, (void **) &o.d_res, &o.res_cap, res_bytes, res_bytes, &replaced);
+    if (replaced) o.res_valid = false;
+    if (rc || !jac_bytes) return rc;
+    replaced = false;
+    rc       = icg_grow(ctx, (void **) &o.d_jac, &o.jac_cap, jac_bytes, jac_bytes, &replaced);
+    if (replaced) o.jac_valid = false;
+    return rc;
+}
+// around the kernels that write the results: behind the launch guard icg_resident_invalidate (nothing is valid until they are through),
+// after finish() this
+static inline void icg_resident_end(icg_resident_results &o, bool want_jac) { o.res_valid = true, o.jac_valid = want_jac; }
+// The three questions every reader of a set asks, in this order, up to `need`.  n: the members of the set (0: none); the caller is the
+// entry <stem><entry>, the set is made resident by <stem>_set; what: the set's noun.
+enum icg_resident_need { ICG_NEED_SET, ICG_NEED_RESULTS, ICG_NEED_JACOBIANS };
+static inline int icg_resident_require(icg_ctx *ctx, const icg_resident_results &o, int n, icg_resident_need need, const char *stem, const char *entry,
+                                       const char *what) {
+    if (n <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s%s: no %s set is resident (%s_set first)", stem, entry, what, stem);
+    if (need >= ICG_NEED_RESULTS && !o.res_valid)
+        return icg_fail(ctx, ICG_ERR_INVALID, "%s%s: nothing was evaluated since the set was made resident", stem, entry);
+    if (need >= ICG_NEED_JACOBIANS && !o.jac_valid)
+        return icg_fail(ctx, ICG_ERR_INVALID, "%s%s: the last evaluation kept no Jacobians (want_jac = 0)", stem, entry);
+    return ICG_OK;
+}
+
 // large LDS --------------------------------------------------------------------------------------------------
 // gfx950 has 160 KiB of LDS per CU and one workgroup may own all of it (MI355X_MICROARCH.md, "LDS"); a launch with more dynamic LDS than the
 // default needs the function attribute.  The limit comes from the device the context runs on, so a build for a part with less LDS takes the
@@ -407,6 +441,15 @@ struct icg_call {
         if (off + sizeof(T) * n > mirror_hi) mirror_hi = off + sizeof(T) * n;
         return reinterpret_cast<T *>(ctx->d_arena + off);
     }
+    // a mirrored block the entry fills itself: the host pointer to write n elements through, *dev the block on the device after seal().
+    // nullptr when the allocation did not fit (nothing may be written through it): the caller returns overflowed()
+    template <typename T> T *stage(size_t n, T **dev) {
+        const size_t off = icg_arena_alloc(ctx, sizeof(T) * n);
+        if (ctx->arena_overflow) return nullptr;
+        mirror_lo = std::min(mirror_lo, off), mirror_hi = std::max(mirror_hi, off + sizeof(T) * n);
+        *dev = reinterpret_cast<T *>(ctx->d_arena + off);
+        return reinterpret_cast<T *>(ctx->h_arena + off);
+    }
     template <typename T> T *in_zc(const T *src, size_t n) {
         size_t off = icg_arena_alloc(ctx, sizeof(T) * n);
         if (n) memcpy(ctx->h_arena + off, src, sizeof(T) * n);
@@ -478,6 +521,27 @@ struct icg_call {
         return 0;
     }
 };
+
+// The upload of a resident set that lives in one device buffer (the *_set entries of preint_shared.h and nav.hip): *d_set grows with a
+// quarter of slack, a block of `bytes` is staged for fill(char *host) to write, goes up with the call's one copy and from the arena into
+// the set, device to device, under the profiler scope `scope`.  Invalidating the old set and recording the new one are the caller's.
+template <typename Fill>
+static inline __attribute__((always_inline)) int icg_resident_upload(icg_ctx *ctx, char **d_set, size_t *set_cap, size_t bytes, const char *scope, Fill fill) {
+    int rc;
+    if ((rc = icg_grow(ctx, (void **) d_set, set_cap, bytes, bytes + bytes / 4))) return rc;
+    icg_call c(ctx);
+    if ((rc = c.reserve(bytes + 4 * 256))) return rc;
+    char *dev, *host = c.stage<char>(bytes, &dev);
+    if (!host) return c.overflowed();
+    fill(host);
+    if ((rc = c.seal())) return rc;
+    ICG_LAUNCH_GUARD(c);
+    {
+        icg_prof_scope ps(ctx, scope);
+        ICG_HIP(ctx, hipMemcpyAsync(*d_set, dev, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    return c.finish();
+}
 
 // ---- batched Cholesky solve (chol.hip): one wave per system ---------------------------------------------------------------------------------
 // A system reads its matrix as A[A_off + i * ldA + k] (k <= i), optionally + the packed host part, optionally + dd on the diagonal, in that

@@ -170,7 +170,7 @@ int marg_set(const char *fn, bool from_kept, icg_ctx *ctx, uint64_t keep_id, int
     if (!ctx) return ICG_ERR_INVALID;
     icg_marg_set &s = ctx->marg;
     s.n             = 0; // whatever set the context held is gone, also when this call fails
-    s.res_valid     = false; // and so are the residuals it kept
+    icg_resident_invalidate(s.out); // and so are the residuals it kept
     if (n_windows <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s: n_windows = %d", fn, n_windows);
     if (n_windows > 65535) return icg_fail(ctx, ICG_ERR_CAPACITY, "%s: %d windows in one set (at most 65535)", fn, n_windows);
     if (!r || !block_off || !block_size || !block_index || !x0 || (from_kept ? !src : (!J0 || !e0))) return icg_fail(ctx, ICG_ERR_INVALID, "%s: NULL argument", fn);
@@ -313,7 +313,7 @@ extern "C" int icg_marg_prior_set_from_kept(icg_ctx *ctx, uint64_t keep_id, int 
 extern "C" int icg_marg_prior_evaluate(icg_ctx *ctx, const double *x, double *residuals, double *jacobians, double *gradient, double *sq_norm) {
     if (!ctx) return ICG_ERR_INVALID;
     const icg_marg_set &s = ctx->marg;
-    if (s.n <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_evaluate: no prior set is resident (icg_marg_prior_set first)");
+    if (int rc = icg_resident_require(ctx, s.out, s.n, ICG_NEED_SET, "icg_marg_prior", "_evaluate", "prior")) return rc;
     if (!residuals || (!x && s.total_x > 0)) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_evaluate: NULL argument");
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const size_t n = (size_t) s.n;
@@ -347,13 +347,11 @@ extern "C" int icg_marg_prior_evaluate(icg_ctx *ctx, const double *x, double *re
 extern "C" int icg_marg_prior_evaluate_resident(icg_ctx *ctx, const double *x, double *sq_norm) {
     if (!ctx) return ICG_ERR_INVALID;
     icg_marg_set &s = ctx->marg;
-    if (s.n <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_evaluate_resident: no prior set is resident (icg_marg_prior_set first)");
+    if (int rc = icg_resident_require(ctx, s.out, s.n, ICG_NEED_SET, "icg_marg_prior", "_evaluate_resident", "prior")) return rc;
     if (!sq_norm || (!x && s.total_x > 0)) return icg_fail(ctx, ICG_ERR_INVALID, "icg_marg_prior_evaluate_resident: NULL argument");
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const size_t n = (size_t) s.n, b_res = sizeof(double) * (size_t) s.total_r;
-    bool replaced = false;
-    int rc        = icg_grow(ctx, (void **) &s.d_res, &s.res_cap, b_res, b_res, &replaced);
-    if (replaced) s.res_valid = false;
+    int rc = icg_resident_reserve(ctx, s.out, b_res, 0);
     if (rc) return rc;
     icg_call c(ctx);
     if ((rc = c.reserve(sizeof(double) * (size_t) (s.total_x + (int64_t) n) + 4 * 256))) return rc;
@@ -361,13 +359,13 @@ extern "C" int icg_marg_prior_evaluate_resident(icg_ctx *ctx, const double *x, d
     if ((rc = c.seal())) return rc;
     double *d_sq = c.out(sq_norm, n);
     ICG_LAUNCH_GUARD(c);
-    s.res_valid = false; // (until the kernel below is through)
+    icg_resident_invalidate(s.out); // (until the kernel below is through)
     {
         icg_prof_scope ps(ctx, "marg_eval");
-        hipLaunchKernelGGL(k_marg_evaluate, dim3(s.n), dim3(MARG_THREADS), 0, ctx->stream, s.n, marg_view(s), d_x, s.d_res, (double *) nullptr, d_sq);
+        hipLaunchKernelGGL(k_marg_evaluate, dim3(s.n), dim3(MARG_THREADS), 0, ctx->stream, s.n, marg_view(s), d_x, s.out.d_res, (double *) nullptr, d_sq);
     }
     ICG_HIP(ctx, hipGetLastError());
     if ((rc = c.finish())) return rc;
-    s.res_valid = true;
+    icg_resident_end(s.out, false);
     return ICG_OK;
 }

@@ -176,7 +176,7 @@ extern "C" int icg_nav_set(icg_ctx *ctx, int n_members, const int32_t *kind, con
     if (!ctx) return ICG_ERR_INVALID;
     icg_nav_resident &s = ctx->nav;
     s.n                 = 0; // whatever nav set the context held is gone, also when this call fails
-    s.res_valid = s.jac_valid = s.corrected = s.any_robust = false;
+    icg_resident_invalidate(s.out), s.corrected = s.any_robust = false;
     if (n_members <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_set: n = %d", n_members);
     if (n_members > ICG_NAV_SET_MAX) // (before any array is read)
         return icg_fail(ctx, ICG_ERR_CAPACITY, "icg_nav_set: %d members in one set (at most %d)", n_members, ICG_NAV_SET_MAX);
@@ -199,14 +199,8 @@ extern "C" int icg_nav_set(icg_ctx *ctx, int n_members, const int32_t *kind, con
         s.h_p_off[f + 1] = s.h_p_off[f] + icg_nav_width(kind[f]);
     }
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    int rc;
-    if ((rc = icg_grow(ctx, (void **) &s.d_set, &s.set_cap, bytes, bytes + bytes / 4))) return rc;
-    icg_call c(ctx);
-    if ((rc = c.reserve(bytes + 4 * 256))) return rc;
-    const size_t off = icg_arena_alloc(ctx, bytes);
-    if ((rc = c.overflowed())) return rc; // (nothing may be written through an allocation that did not fit)
-    {
-        double *p = icg_h<double>(ctx, off);
+    const int rc = icg_resident_upload(ctx, &s.d_set, &s.set_cap, bytes, "nav_set", [&](char *host) {
+        double *p = reinterpret_cast<double *>(host);
         if (total_aux) memcpy(p, aux, 8 * total_aux);
         int32_t *q = reinterpret_cast<int32_t *>(p + total_aux);
         memcpy(q, kind, 4 * n), q += n;
@@ -214,15 +208,8 @@ extern "C" int icg_nav_set(icg_ctx *ctx, int n_members, const int32_t *kind, con
         memcpy(q, s.h_r_off.data(), 4 * (n + 1)), q += n + 1;
         memcpy(q, s.h_j_off.data(), 4 * (n + 1)), q += n + 1;
         memcpy(q, s.h_p_off.data(), 4 * (n + 1));
-    }
-    c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + bytes);
-    if ((rc = c.seal())) return rc;
-    ICG_LAUNCH_GUARD(c);
-    {
-        icg_prof_scope ps(ctx, "nav_set");
-        ICG_HIP(ctx, hipMemcpyAsync(s.d_set, icg_d<char>(ctx, off), bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if ((rc = c.finish())) return rc;
+    });
+    if (rc) return rc;
     s.total_aux = (int64_t) total_aux;
     s.n         = n_members;
     return ICG_OK;
@@ -231,76 +218,62 @@ extern "C" int icg_nav_set(icg_ctx *ctx, int n_members, const int32_t *kind, con
 extern "C" int icg_nav_evaluate_resident(icg_ctx *ctx, const double *points, const int32_t *point_off, int want_jac, double *sq_norm) {
     if (!ctx) return ICG_ERR_INVALID;
     icg_nav_resident &s = ctx->nav;
-    if (s.n <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_evaluate_resident: no nav set is resident (icg_nav_set first)");
+    if (int rc = icg_resident_require(ctx, s.out, s.n, ICG_NEED_SET, "icg_nav", "_evaluate_resident", "nav")) return rc;
     if (!points || !point_off || !sq_norm) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_evaluate_resident: NULL argument");
     const size_t n = (size_t) s.n;
     for (size_t f = 0; f < n; f++)
         if (point_off[f] < 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_evaluate_resident: member %zu: point_off = %d", f, point_off[f]);
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const size_t total_r = (size_t) s.h_r_off[n], total_j = (size_t) s.h_j_off[n], total_p = (size_t) s.h_p_off[n];
-    bool replaced = false;
-    int rc        = icg_grow(ctx, (void **) &s.d_res, &s.res_cap, 8 * total_r, 8 * total_r, &replaced);
-    if (replaced) s.res_valid = false;
+    int rc = icg_resident_reserve(ctx, s.out, 8 * total_r, want_jac ? 8 * total_j : 0);
     if (rc) return rc;
-    if (want_jac) {
-        replaced = false;
-        rc       = icg_grow(ctx, (void **) &s.d_jac, &s.jac_cap, 8 * total_j, 8 * total_j, &replaced);
-        if (replaced) s.jac_valid = false;
-        if (rc) return rc;
-    }
     icg_call c(ctx);
     if ((rc = c.reserve(8 * (total_p + n) + 4 * 256))) return rc;
     // the members' blocks, packed in member order: the kernel reads no address the caller's offsets name
-    const size_t off = icg_arena_alloc(ctx, 8 * total_p);
-    if ((rc = c.overflowed())) return rc;
-    {
-        double *p = icg_h<double>(ctx, off);
-        for (size_t f = 0; f < n; f++) memcpy(p + s.h_p_off[f], points + point_off[f], 8 * (size_t) (s.h_p_off[f + 1] - s.h_p_off[f]));
-    }
-    c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + 8 * total_p);
+    double *d_pts, *p = c.stage<double>(total_p, &d_pts);
+    if (!p) return c.overflowed();
+    for (size_t f = 0; f < n; f++) memcpy(p + s.h_p_off[f], points + point_off[f], 8 * (size_t) (s.h_p_off[f + 1] - s.h_p_off[f]));
     if ((rc = c.seal())) return rc;
     double *d_sq = c.out(sq_norm, n);
     ICG_LAUNCH_GUARD(c);
-    s.res_valid = s.jac_valid = s.corrected = false; // (until the kernel below is through)
+    icg_resident_invalidate(s.out), s.corrected = false; // (until the kernel below is through)
     const nav_view v = nav_set_view(s);
     {
         icg_prof_scope ps(ctx, "nav_eval");
         hipLaunchKernelGGL(k_nav_evaluate, dim3(nav_grid(s.n)), dim3(64), 0, ctx->stream, s.n, v.kind, v.aux_off, v.r_off, v.j_off, v.p_off, v.aux,
-                           icg_d<double>(ctx, off), s.d_res, want_jac ? s.d_jac : (double *) nullptr, d_sq);
+                           (const double *) d_pts, s.out.d_res, want_jac ? s.out.d_jac : (double *) nullptr, d_sq);
     }
     ICG_HIP(ctx, hipGetLastError());
     if ((rc = c.finish())) return rc;
-    s.res_valid = true;
-    s.jac_valid = want_jac != 0;
+    icg_resident_end(s.out, want_jac != 0);
     return ICG_OK;
 }
 
 extern "C" int icg_nav_correct_resident(icg_ctx *ctx, const uint8_t *robust, const double *corr) {
     if (!ctx) return ICG_ERR_INVALID;
     icg_nav_resident &s = ctx->nav;
-    if (s.n <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_correct_resident: no nav set is resident (icg_nav_set first)");
+    int rc;
+    if ((rc = icg_resident_require(ctx, s.out, s.n, ICG_NEED_SET, "icg_nav", "_correct_resident", "nav"))) return rc;
     if (!robust || !corr) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_correct_resident: NULL argument");
-    if (!s.res_valid) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_correct_resident: nothing was evaluated since the set was made resident");
-    if (!s.jac_valid) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_correct_resident: the last evaluation kept no Jacobians (want_jac = 0)");
+    if ((rc = icg_resident_require(ctx, s.out, s.n, ICG_NEED_JACOBIANS, "icg_nav", "_correct_resident", "nav"))) return rc;
     if (s.corrected) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_correct_resident: the last evaluation was corrected already");
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const size_t n = (size_t) s.n;
     icg_call c(ctx);
-    int rc = c.reserve(n * (1 + 24) + 4 * 256);
-    if (rc) return rc;
+    if ((rc = c.reserve(n * (1 + 24) + 4 * 256))) return rc;
     const uint8_t *d_rob = c.in(robust, n);
     const double *d_corr = c.in(corr, 3 * n);
     if ((rc = c.seal())) return rc;
     ICG_LAUNCH_GUARD(c);
-    s.res_valid = s.jac_valid = false; // (until the kernel below is through)
+    icg_resident_invalidate(s.out); // (until the kernel below is through)
     const nav_view v = nav_set_view(s);
     {
         icg_prof_scope ps(ctx, "nav_correct");
-        hipLaunchKernelGGL(k_nav_correct, dim3(nav_grid(s.n)), dim3(64), 0, ctx->stream, s.n, v.kind, v.r_off, v.j_off, d_rob, d_corr, s.d_res, s.d_jac);
+        hipLaunchKernelGGL(k_nav_correct, dim3(nav_grid(s.n)), dim3(64), 0, ctx->stream, s.n, v.kind, v.r_off, v.j_off, d_rob, d_corr, s.out.d_res, s.out.d_jac);
     }
     ICG_HIP(ctx, hipGetLastError());
     if ((rc = c.finish())) return rc;
-    s.res_valid = s.jac_valid = s.corrected = true;
+    icg_resident_end(s.out, true), s.corrected = true;
     for (size_t f = 0; f < n; f++) s.any_robust |= robust[f] != 0;
     return ICG_OK;
 }
@@ -308,14 +281,13 @@ extern "C" int icg_nav_correct_resident(icg_ctx *ctx, const uint8_t *robust, con
 extern "C" int icg_nav_fetch_resident(icg_ctx *ctx, double *residuals, double *jacobians) {
     if (!ctx) return ICG_ERR_INVALID;
     const icg_nav_resident &s = ctx->nav;
-    if (s.n <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_fetch_resident: no nav set is resident (icg_nav_set first)");
+    int rc;
+    if ((rc = icg_resident_require(ctx, s.out, s.n, ICG_NEED_SET, "icg_nav", "_fetch_resident", "nav"))) return rc;
     if (!residuals) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_fetch_resident: NULL residuals");
-    if (!s.res_valid) return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_fetch_resident: nothing was evaluated since the set was made resident");
-    if (jacobians && !s.jac_valid)
-        return icg_fail(ctx, ICG_ERR_INVALID, "icg_nav_fetch_resident: the last evaluation kept no Jacobians (want_jac = 0)");
+    if ((rc = icg_resident_require(ctx, s.out, s.n, jacobians ? ICG_NEED_JACOBIANS : ICG_NEED_RESULTS, "icg_nav", "_fetch_resident", "nav"))) return rc;
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const size_t n = (size_t) s.n;
-    ICG_HIP(ctx, hipMemcpyAsync(residuals, s.d_res, 8 * (size_t) s.h_r_off[n], hipMemcpyDeviceToHost, ctx->stream));
-    if (jacobians) ICG_HIP(ctx, hipMemcpyAsync(jacobians, s.d_jac, 8 * (size_t) s.h_j_off[n], hipMemcpyDeviceToHost, ctx->stream));
+    ICG_HIP(ctx, hipMemcpyAsync(residuals, s.out.d_res, 8 * (size_t) s.h_r_off[n], hipMemcpyDeviceToHost, ctx->stream));
+    if (jacobians) ICG_HIP(ctx, hipMemcpyAsync(jacobians, s.out.d_jac, 8 * (size_t) s.h_j_off[n], hipMemcpyDeviceToHost, ctx->stream));
     return icg_stream_wait(ctx);
 }

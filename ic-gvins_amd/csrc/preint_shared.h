@@ -547,7 +547,7 @@ int set_entry(icg_ctx *ctx, int n_factors, const int32_t *variant, const double 
     if (!ctx) return ICG_ERR_INVALID;
     icg_preint_resident &s = F::set_of(ctx);
     s.n                    = 0; // whatever set of this family the context held is gone, also when this call fails
-    s.res_valid = s.jac_valid = false;
+    icg_resident_invalidate(s.out);
     if (n_factors <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s_set: n_factors = %d", F::stem, n_factors);
     // before any array is read (the arrays of such a set are not looked at); the bound is also what keeps `bytes` and the grids in range
     if (n_factors > ICG_PREINT_SET_MAX)
@@ -574,14 +574,8 @@ int set_entry(icg_ctx *ctx, int n_factors, const int32_t *variant, const double 
     }
     const size_t n_dbl = (F::DELTA + NN + NN + 1 + 4 + 4) * n + 4 * (size_t) total_pn, bytes = 8 * n_dbl + 4 * (2 * n + 1);
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    int rc;
-    if ((rc = icg_grow(ctx, (void **) &s.d_set, &s.set_cap, bytes, bytes + bytes / 4))) return rc;
-    icg_call c(ctx);
-    if ((rc = c.reserve(bytes + 4 * 256))) return rc;
-    const size_t off = icg_arena_alloc(ctx, bytes);
-    if ((rc = c.overflowed())) return rc; // (nothing may be written through an allocation that did not fit)
-    {
-        double *p = icg_h<double>(ctx, off);
+    const int rc = icg_resident_upload(ctx, &s.d_set, &s.set_cap, bytes, F::scope_set, [&](char *host) {
+        double *p = reinterpret_cast<double *>(host);
         memcpy(p, delta_state, 8 * F::DELTA * n), p += F::DELTA * n;
         memcpy(p, jac, 8 * NN * n), p += NN * n;
         memcpy(p, sqrt_info, 8 * NN * n), p += NN * n;
@@ -595,15 +589,8 @@ int set_entry(icg_ctx *ctx, int n_factors, const int32_t *variant, const double 
         else
             memset(q, 0, 4 * (n + 1));
         memcpy(q + (n + 1), variant, 4 * n);
-    }
-    c.mirror_lo = std::min(c.mirror_lo, off), c.mirror_hi = std::max(c.mirror_hi, off + bytes);
-    if ((rc = c.seal())) return rc;
-    ICG_LAUNCH_GUARD(c);
-    {
-        icg_prof_scope ps(ctx, F::scope_set);
-        ICG_HIP(ctx, hipMemcpyAsync(s.d_set, icg_d<char>(ctx, off), bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if ((rc = c.finish())) return rc;
+    });
+    if (rc) return rc;
     s.total_pn = total_pn;
     s.n        = n_factors;
     return ICG_OK;
@@ -615,20 +602,12 @@ int evaluate_resident_entry(const kernels<N> &K, icg_ctx *ctx, const double *poi
     constexpr int NJ = widths<N>::NJ;
     if (!ctx) return ICG_ERR_INVALID;
     icg_preint_resident &s = F::set_of(ctx);
-    if (s.n <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s_evaluate_resident: no %s set is resident (%s_set first)", F::stem, F::what, F::stem);
+    if (int rc = icg_resident_require(ctx, s.out, s.n, ICG_NEED_SET, F::stem, "_evaluate_resident", F::what)) return rc;
     if (!points || !q_corr || !sq_norm) return icg_fail(ctx, ICG_ERR_INVALID, "%s_evaluate_resident: NULL argument", F::stem);
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const size_t n = (size_t) s.n;
-    bool replaced  = false;
-    int rc         = icg_grow(ctx, (void **) &s.d_res, &s.res_cap, 8 * N * n, 8 * N * n, &replaced);
-    if (replaced) s.res_valid = false;
+    int rc         = icg_resident_reserve(ctx, s.out, 8 * N * n, want_jac ? 8 * NJ * n : 0);
     if (rc) return rc;
-    if (want_jac) {
-        replaced = false;
-        rc       = icg_grow(ctx, (void **) &s.d_jac, &s.jac_cap, 8 * NJ * n, 8 * NJ * n, &replaced);
-        if (replaced) s.jac_valid = false;
-        if (rc) return rc;
-    }
     icg_call c(ctx);
     if ((rc = c.reserve(8 * (F::POINT + 4 + 1) * n + 4 * 256))) return rc;
     const double *d_pts = c.in(points, F::POINT * n);
@@ -636,17 +615,16 @@ int evaluate_resident_entry(const kernels<N> &K, icg_ctx *ctx, const double *poi
     if ((rc = c.seal())) return rc;
     double *d_sq = c.out(sq_norm, n);
     ICG_LAUNCH_GUARD(c);
-    s.res_valid = s.jac_valid = false; // (until the kernel below is through)
+    icg_resident_invalidate(s.out); // (until the kernel below is through)
     const set_view v = view_of<N>(s);
     {
         icg_prof_scope ps(ctx, F::scope_given);
         hipLaunchKernelGGL(K.given, dim3(s.n), dim3(64), 0, ctx->stream, s.n, v.variant, v.delta, v.jac, v.dt, v.env, v.pn_off, v.pn, d_pts, v.S, d_qc,
-                           v.qnn, s.d_res, want_jac ? s.d_jac : (double *) nullptr, d_sq);
+                           v.qnn, s.out.d_res, want_jac ? s.out.d_jac : (double *) nullptr, d_sq);
     }
     ICG_HIP(ctx, hipGetLastError());
     if ((rc = c.finish())) return rc;
-    s.res_valid = true;
-    s.jac_valid = want_jac != 0;
+    icg_resident_end(s.out, want_jac != 0);
     return ICG_OK;
 }
 
@@ -655,17 +633,16 @@ template <int N> int fetch_resident_entry(icg_ctx *ctx, double *residuals, doubl
     typedef widths<N> W;
     if (!ctx) return ICG_ERR_INVALID;
     const icg_preint_resident &s = F::set_of(ctx);
-    if (s.n <= 0) return icg_fail(ctx, ICG_ERR_INVALID, "%s_fetch_resident: no %s set is resident (%s_set first)", F::stem, F::what, F::stem);
+    int rc;
+    if ((rc = icg_resident_require(ctx, s.out, s.n, ICG_NEED_SET, F::stem, "_fetch_resident", F::what))) return rc;
     if (!residuals) return icg_fail(ctx, ICG_ERR_INVALID, "%s_fetch_resident: NULL residuals", F::stem);
-    if (!s.res_valid) return icg_fail(ctx, ICG_ERR_INVALID, "%s_fetch_resident: nothing was evaluated since the set was made resident", F::stem);
-    if (jacobians && !s.jac_valid)
-        return icg_fail(ctx, ICG_ERR_INVALID, "%s_fetch_resident: the last evaluation kept no Jacobians (want_jac = 0)", F::stem);
+    if ((rc = icg_resident_require(ctx, s.out, s.n, jacobians ? ICG_NEED_JACOBIANS : ICG_NEED_RESULTS, F::stem, "_fetch_resident", F::what))) return rc;
     ICG_HIP(ctx, hipSetDevice(ctx->cfg.device));
     const size_t n = (size_t) s.n;
     std::vector<double> JP(jacobians ? W::NJ * n : 0);
-    ICG_HIP(ctx, hipMemcpyAsync(residuals, s.d_res, 8 * N * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (jacobians) ICG_HIP(ctx, hipMemcpyAsync(JP.data(), s.d_jac, 8 * W::NJ * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (int rc = icg_stream_wait(ctx)) return rc;
+    ICG_HIP(ctx, hipMemcpyAsync(residuals, s.out.d_res, 8 * N * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (jacobians) ICG_HIP(ctx, hipMemcpyAsync(JP.data(), s.out.d_jac, 8 * W::NJ * n, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = icg_stream_wait(ctx))) return rc;
     if (jacobians) // N x POINT row-major -> N x 7 | N x MIX | N x 7 | N x MIX
         for (size_t f = 0; f < n; f++)
             for (int b = 0; b < 4; b++) {

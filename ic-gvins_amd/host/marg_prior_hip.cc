@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "factors.h"
+#include "resident_call.h"
 
 // A build of this layer on another implementation of the C ABI may not have the entry points: the references stay weak (null when absent)
 // and set() reports it; the product library links libicgvins_hip.so, which defines them.
@@ -116,20 +117,14 @@ bool MarginalizationPriorSet::set(icg_ctx *ctx, const vector<std::shared_ptr<Mar
 
 bool MarginalizationPriorSet::evaluate(const vector<const double *const *> &parameters, double *residuals, double *jacobians, double *gradient,
                                        double *sq_norm, std::string *err) {
-    if (!available()) {
-        if (err) *err = "icg_marg_prior_evaluate is not in this build";
+    if (available() && ctx_ && parameters.size() != r_.size()) {
+        if (err) *err = "MarginalizationPriorSet::evaluate: one parameter list per window";
         return false;
     }
-    if (!ctx_ || parameters.size() != r_.size()) {
-        if (err) *err = !ctx_ ? "MarginalizationPriorSet::evaluate: no set" : "MarginalizationPriorSet::evaluate: one parameter list per window";
-        return false;
-    }
-    for (size_t w = 0; w < r_.size(); w++) pack(w, parameters[w]);
-    if (icg_marg_prior_evaluate(ctx_, x_.data(), residuals, jacobians, gradient, sq_norm) != ICG_OK) {
-        if (err) *err = icg_last_error(ctx_);
-        return false;
-    }
-    return true;
+    return residentCall(available() ? nullptr : "icg_marg_prior_evaluate", ctx_, "MarginalizationPriorSet::evaluate: no set", err, [&] {
+        for (size_t w = 0; w < r_.size(); w++) pack(w, parameters[w]);
+        return icg_marg_prior_evaluate(ctx_, x_.data(), residuals, jacobians, gradient, sq_norm);
+    });
 }
 
 void MarginalizationPriorSet::pack(size_t w, const double *const *parameters) {
@@ -141,19 +136,8 @@ void MarginalizationPriorSet::pack(size_t w, const double *const *parameters) {
 }
 
 bool MarginalizationPriorSet::evaluateResident(double *sq_norm, std::string *err) {
-    if (!residentAvailable()) {
-        if (err) *err = "icg_marg_prior_evaluate_resident is not in this build";
-        return false;
-    }
-    if (!ctx_) {
-        if (err) *err = "MarginalizationPriorSet::evaluateResident: no set";
-        return false;
-    }
-    if (icg_marg_prior_evaluate_resident(ctx_, x_.data(), sq_norm) != ICG_OK) {
-        if (err) *err = icg_last_error(ctx_);
-        return false;
-    }
-    return true;
+    return residentCall(residentAvailable() ? nullptr : "icg_marg_prior_evaluate_resident", ctx_, "MarginalizationPriorSet::evaluateResident: no set", err,
+                        [&] { return icg_marg_prior_evaluate_resident(ctx_, x_.data(), sq_norm); });
 }
 
 } // namespace icg

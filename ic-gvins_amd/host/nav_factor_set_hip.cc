@@ -2,6 +2,7 @@
 #include <cstring>
 
 #include "nav_factor_set.h"
+#include "resident_call.h"
 
 // A build of this layer on another implementation of the C ABI may not have the entry points: the references stay weak (null when absent)
 // and set() reports it; the product library links libicgvins_hip.so, which defines them.
@@ -40,10 +41,7 @@ bool NavFactorSet::set(icg_ctx *ctx, const vector<const NavFactor *> &list, std:
         at += (size_t) list[f]->navWidth();
     }
     if (aux.empty()) aux.push_back(0.0); // (a set of error factors reads no constant; the entry still wants a pointer)
-    if (icg_nav_set(ctx, (int) n, kind.data(), aux_off.data(), aux.data()) != ICG_OK) {
-        if (err) *err = ctx ? icg_last_error(ctx) : "icg_nav_set: no context";
-        return false;
-    }
+    if (!residentCall(nullptr, ctx, "icg_nav_set: no context", err, [&] { return icg_nav_set(ctx, (int) n, kind.data(), aux_off.data(), aux.data()); })) return false;
     kind_.swap(kind), point_off_.swap(point_off);
     points_.assign(at, 0.0);
     ctx_ = ctx;
@@ -56,27 +54,12 @@ void NavFactorSet::pack(size_t f, const double *block) {
 }
 
 bool NavFactorSet::evaluateResident(bool want_jac, double *sq_norm, std::string *err) {
-    if (!available() || !ctx_) {
-        if (err) *err = !available() ? std::string(missingEntry()) + " is not in this build" : "NavFactorSet::evaluateResident: no set";
-        return false;
-    }
-    if (icg_nav_evaluate_resident(ctx_, points_.data(), point_off_.data(), want_jac ? 1 : 0, sq_norm) != ICG_OK) {
-        if (err) *err = icg_last_error(ctx_);
-        return false;
-    }
-    return true;
+    return residentCall(missingEntry(), ctx_, "NavFactorSet::evaluateResident: no set", err,
+                        [&] { return icg_nav_evaluate_resident(ctx_, points_.data(), point_off_.data(), want_jac ? 1 : 0, sq_norm); });
 }
 
 bool NavFactorSet::correct(const uint8_t *robust, const double *corr, std::string *err) {
-    if (!available() || !ctx_) {
-        if (err) *err = !available() ? std::string(missingEntry()) + " is not in this build" : "NavFactorSet::correct: no set";
-        return false;
-    }
-    if (icg_nav_correct_resident(ctx_, robust, corr) != ICG_OK) {
-        if (err) *err = icg_last_error(ctx_);
-        return false;
-    }
-    return true;
+    return residentCall(missingEntry(), ctx_, "NavFactorSet::correct: no set", err, [&] { return icg_nav_correct_resident(ctx_, robust, corr); });
 }
 
 } // namespace icg

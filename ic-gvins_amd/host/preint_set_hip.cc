@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "preintegration_odo.h"
+#include "resident_call.h"
 
 // A build of this layer on another implementation of the C ABI may not have the entry points: the references stay weak (null when absent)
 // and set() reports it; the product library links libicgvins_hip.so, which defines them.
@@ -71,11 +72,11 @@ template <class P> bool PreintegrationSetT<P>::set(icg_ctx *ctx, const vector<co
         if (p.variant() == P::EARTH_VARIANT) pn.insert(pn.end(), p.pnRows().begin(), p.pnRows().begin() + (long) (p.pnRows().size() / 4 * 4));
         pn_off[f + 1] = (int32_t) (pn.size() / 4);
     }
-    if (E::set()(ctx, (int) n, variant.data(), del.data(), jac.data(), S.data(), dt.data(), env.data(), qnn.data(), any_earth ? pn_off.data() : nullptr,
-                 pn.empty() ? nullptr : pn.data()) != ICG_OK) {
-        if (err) *err = ctx ? icg_last_error(ctx) : std::string(E::set_name) + ": no context";
+    if (!residentCall(nullptr, ctx, std::string(E::set_name) + ": no context", err, [&] {
+            return E::set()(ctx, (int) n, variant.data(), del.data(), jac.data(), S.data(), dt.data(), env.data(), qnn.data(), any_earth ? pn_off.data() : nullptr,
+                            pn.empty() ? nullptr : pn.data());
+        }))
         return false;
-    }
     list_ = list;
     points_.assign((size_t) P::NUM_POINT * n, 0.0), q_corr_.assign(4 * n, 0.0);
     ctx_ = ctx;
@@ -92,15 +93,8 @@ template <class P> void PreintegrationSetT<P>::pack(size_t f, const double *cons
 
 template <class P> bool PreintegrationSetT<P>::evaluateResident(bool want_jac, double *sq_norm, std::string *err) {
     typedef SetEntries<P> E;
-    if (!available() || !ctx_) {
-        if (err) *err = !available() ? std::string(missingEntry()) + " is not in this build" : std::string(E::cls) + "::evaluateResident: no set";
-        return false;
-    }
-    if (E::eval()(ctx_, points_.data(), q_corr_.data(), want_jac ? 1 : 0, sq_norm) != ICG_OK) {
-        if (err) *err = icg_last_error(ctx_);
-        return false;
-    }
-    return true;
+    return residentCall(missingEntry(), ctx_, std::string(E::cls) + "::evaluateResident: no set", err,
+                        [&] { return E::eval()(ctx_, points_.data(), q_corr_.data(), want_jac ? 1 : 0, sq_norm); });
 }
 
 template class PreintegrationSetT<Preintegration>;

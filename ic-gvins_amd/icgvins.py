@@ -619,22 +619,30 @@ class Context:
         self._ck(self.lib.icg_reproj_cost_windows(self.h, _p(act), _p(cost)), "icg_reproj_cost_windows")
         return cost
 
-    # ---- P1
-    def preint_batch(self, variant, offsets, imu, state0, params, want_pn=True):
-        """icg_preint_batch -> (cur n x 16, delta n x 16, jac n x 15 x 15, cov n x 15 x 15, dt n, pn total x 4 or None without want_pn)"""
+    # ---- P1 and P2 of both preintegration families: one body each over the family's widths, (imu, state0, params, delta, N, point); the entry is
+    # icg_<stem>_<call> and the resident count self._<stem>_n
+    _PREINT = ("preint", (8, 16, 9, 16, 15, 32))
+    _PREINT_ODO = ("preint_odo", (9, 17, 25, 20, 19, 34))
+
+    def _preint_batch_call(self, fam, variant, offsets, imu, state0, params, want_pn):
+        stem, (w_imu, w_s0, _, w_del, N, _) = fam
         offsets = i32(offsets)
         n = len(offsets) - 1
-        imu = f64(imu).reshape(-1, 8)
-        state0 = f64(state0).reshape(n, 16)
-        cur = np.zeros((n, 16))
-        delta = np.zeros((n, 16))
-        jac = np.zeros((n, 15, 15))
-        cov = np.zeros((n, 15, 15))
-        dt = np.zeros(n)
+        imu = f64(imu).reshape(-1, w_imu)
+        state0 = f64(state0).reshape(n, w_s0)
+        cur, delta, jac, cov, dt = np.zeros((n, 16)), np.zeros((n, w_del)), np.zeros((n, N, N)), np.zeros((n, N, N)), np.zeros(n)
         pn = np.zeros((imu.shape[0], 4)) if want_pn else None
-        self._ck(self.lib.icg_preint_batch(self.h, int(variant), n, _p(offsets), _p(imu), _p(state0), _p(f64(params)),
-                                            _p(cur), _p(delta), _p(jac), _p(cov), _p(dt), _p(pn)), "icg_preint_batch")
+        self._ck(getattr(self.lib, f"icg_{stem}_batch")(self.h, int(variant), n, _p(offsets), _p(imu), _p(state0), _p(params), _p(cur), _p(delta), _p(jac),
+                                                        _p(cov), _p(dt), _p(pn)), f"icg_{stem}_batch")
         return cur, delta, jac, cov, dt, pn
+
+    def preint_batch(self, variant, offsets, imu, state0, params, want_pn=True):
+        """icg_preint_batch -> (cur n x 16, delta n x 16, jac n x 15 x 15, cov n x 15 x 15, dt n, pn total x 4 or None without want_pn)"""
+        return self._preint_batch_call(self._PREINT, variant, offsets, imu, state0, f64(params), want_pn)
+
+    def preint_odo_batch(self, variant, offsets, imu9, state0, params25, want_pn=True):
+        """icg_preint_odo_batch (variant 2 = Odo, 3 = EarthOdo) -> as preint_batch with delta n x 20 and 19 x 19 matrices"""
+        return self._preint_batch_call(self._PREINT_ODO, variant, offsets, imu9, state0, f64(params25).reshape(25), want_pn)
 
     def _preint_params_call(self, fn, name, widths, variant, offsets, imu, state0, params, want_pn, want_sqrt_info, want_status, fill):
         """the shared body of preint_batch_params / preint_odo_batch_params; widths = (imu, state0, params, delta, N)"""
@@ -656,127 +664,93 @@ class Context:
     def preint_batch_params(self, variant, offsets, imu, state0, params, want_pn=True, want_sqrt_info=True, want_status=True, fill=0.0):
         """icg_preint_batch_params (params n x 9, one row per interval) -> (cur n x 16, delta n x 16, jac, cov n x 15 x 15, dt n, pn total x 4
         or None, sqrt_info n x 15 x 15 or None, status n or None); the output arrays start out filled with `fill`"""
-        return self._preint_params_call(self.lib.icg_preint_batch_params, "icg_preint_batch_params", (8, 16, 9, 16, 15), variant, offsets, imu, state0,
+        return self._preint_params_call(self.lib.icg_preint_batch_params, "icg_preint_batch_params", self._PREINT[1][:5], variant, offsets, imu, state0,
                                         params, want_pn, want_sqrt_info, want_status, fill)
 
     def preint_odo_batch_params(self, variant, offsets, imu9, state0, params25, want_pn=True, want_sqrt_info=True, want_status=True, fill=0.0):
         """icg_preint_odo_batch_params (params25 n x 25) -> as preint_batch_params with delta n x 20 and 19 x 19 matrices"""
-        return self._preint_params_call(self.lib.icg_preint_odo_batch_params, "icg_preint_odo_batch_params", (9, 17, 25, 20, 19), variant, offsets, imu9,
+        return self._preint_params_call(self.lib.icg_preint_odo_batch_params, "icg_preint_odo_batch_params", self._PREINT_ODO[1][:5], variant, offsets, imu9,
                                         state0, params25, want_pn, want_sqrt_info, want_status, fill)
 
     # ---- P2
-    def preint_evaluate_batch(self, variant, delta, jac, cov, dt, env, points, pn_offsets=None, pn=None, want_jac=True):
-        """icg_preint_evaluate_batch -> (residuals n x 15, jacobians n x 480 or None, sqrt_info n x 15 x 15, status n)"""
-        points = f64(points).reshape(-1, 32)
+    def _preint_evaluate_batch_call(self, fam, variant, delta, jac, cov, dt, env, points, pn_offsets, pn, want_jac):
+        stem, (_, _, _, w_del, N, point) = fam
+        points = f64(points).reshape(-1, point)
         n = points.shape[0]
-        delta, jac, cov = f64(delta).reshape(n, 16), f64(jac).reshape(n, 225), f64(cov).reshape(n, 225)
+        delta, jac, cov = f64(delta).reshape(n, w_del), f64(jac).reshape(n, N * N), f64(cov).reshape(n, N * N)
         dt, env = f64(dt).reshape(n), f64(env).reshape(n, 4)
         po = None if pn_offsets is None else i32(pn_offsets)
         pnr = None if pn is None else f64(pn).reshape(-1, 4)
-        res = np.zeros((n, 15))
-        J = np.zeros((n, 480)) if want_jac else None
-        S = np.zeros((n, 15, 15))
+        res = np.zeros((n, N))
+        J = np.zeros((n, N * point)) if want_jac else None
+        S = np.zeros((n, N, N))
         status = np.zeros(n, np.int32)
-        self._ck(self.lib.icg_preint_evaluate_batch(self.h, int(variant), n, _p(delta), _p(jac), _p(cov), _p(dt), _p(env), _p(po), _p(pnr),
-                                                     _p(points), _p(res), _p(J), _p(S), _p(status)), "icg_preint_evaluate_batch")
+        self._ck(getattr(self.lib, f"icg_{stem}_evaluate_batch")(self.h, int(variant), n, _p(delta), _p(jac), _p(cov), _p(dt), _p(env), _p(po), _p(pnr),
+                                                                 _p(points), _p(res), _p(J), _p(S), _p(status)), f"icg_{stem}_evaluate_batch")
         return res, J, S, status
 
-    # ---- P1 / P2 of the odometer variants (2 = Odo, 3 = EarthOdo)
-    def preint_odo_batch(self, variant, offsets, imu9, state0, params25, want_pn=True):
-        """icg_preint_odo_batch -> (cur n x 16, delta n x 20, jac n x 19 x 19, cov n x 19 x 19, dt n, pn total x 4 or None without want_pn)"""
-        offsets = i32(offsets)
-        n = len(offsets) - 1
-        imu9 = f64(imu9).reshape(-1, 9)
-        state0 = f64(state0).reshape(n, 17)
-        params25 = f64(params25).reshape(25)
-        cur = np.zeros((n, 16))
-        delta = np.zeros((n, 20))
-        jac = np.zeros((n, 19, 19))
-        cov = np.zeros((n, 19, 19))
-        dt = np.zeros(n)
-        pn = np.zeros((imu9.shape[0], 4)) if want_pn else None
-        self._ck(self.lib.icg_preint_odo_batch(self.h, int(variant), n, _p(offsets), _p(imu9), _p(state0), _p(params25),
-                                                _p(cur), _p(delta), _p(jac), _p(cov), _p(dt), _p(pn)), "icg_preint_odo_batch")
-        return cur, delta, jac, cov, dt, pn
+    def _preint_set_call(self, fam, variant, delta, jac, sqrt_info, dt, env, q_nn, pn_offsets, pn):
+        stem, (_, _, _, w_del, N, _) = fam
+        variant = i32(variant).reshape(-1)
+        n = len(variant)
+        delta, jac, sqrt_info = f64(delta).reshape(n, w_del), f64(jac).reshape(n, N * N), f64(sqrt_info).reshape(n, N * N)
+        dt, env, q_nn = f64(dt).reshape(n), f64(env).reshape(n, 4), f64(q_nn).reshape(n, 4)
+        po = None if pn_offsets is None else i32(pn_offsets)
+        pnr = None if pn is None else f64(pn).reshape(-1, 4)
+        setattr(self, f"_{stem}_n", 0)
+        self._ck(getattr(self.lib, f"icg_{stem}_set")(self.h, n, _p(variant), _p(delta), _p(jac), _p(sqrt_info), _p(dt), _p(env), _p(q_nn), _p(po), _p(pnr)),
+                 f"icg_{stem}_set")
+        setattr(self, f"_{stem}_n", n)
+
+    def _preint_evaluate_resident_call(self, fam, points, q_corr, want_jac):
+        stem, widths = fam
+        n = getattr(self, f"_{stem}_n", 0)
+        points, q_corr = f64(points).reshape(-1, widths[5]), f64(q_corr).reshape(-1, 4)
+        if n and (points.shape[0] != n or q_corr.shape[0] != n):
+            raise IcgError(f"{stem}_evaluate_resident: {points.shape[0]} points and {q_corr.shape[0]} quaternions, the resident set has {n} factors")
+        sq = np.zeros(max(n, 1))
+        self._ck(getattr(self.lib, f"icg_{stem}_evaluate_resident")(self.h, _p(points), _p(q_corr), 1 if want_jac else 0, _p(sq)), f"icg_{stem}_evaluate_resident")
+        return sq[:n]
+
+    def _preint_fetch_resident_call(self, fam, want_jac):
+        stem, (_, _, _, _, N, point) = fam
+        n = max(getattr(self, f"_{stem}_n", 0), 1)
+        res = np.zeros((n, N))
+        J = np.zeros((n, N * point)) if want_jac else None
+        self._ck(getattr(self.lib, f"icg_{stem}_fetch_resident")(self.h, _p(res), _p(J)), f"icg_{stem}_fetch_resident")
+        return res, J
+
+    def preint_evaluate_batch(self, variant, delta, jac, cov, dt, env, points, pn_offsets=None, pn=None, want_jac=True):
+        """icg_preint_evaluate_batch -> (residuals n x 15, jacobians n x 480 or None, sqrt_info n x 15 x 15, status n)"""
+        return self._preint_evaluate_batch_call(self._PREINT, variant, delta, jac, cov, dt, env, points, pn_offsets, pn, want_jac)
 
     def preint_odo_evaluate_batch(self, variant, delta, jac, cov, dt, env, points, pn_offsets=None, pn=None, want_jac=True):
         """icg_preint_odo_evaluate_batch -> (residuals n x 19, jacobians n x 646 or None, sqrt_info n x 19 x 19, status n)"""
-        points = f64(points).reshape(-1, 34)
-        n = points.shape[0]
-        delta, jac, cov = f64(delta).reshape(n, 20), f64(jac).reshape(n, 361), f64(cov).reshape(n, 361)
-        dt, env = f64(dt).reshape(n), f64(env).reshape(n, 4)
-        po = None if pn_offsets is None else i32(pn_offsets)
-        pnr = None if pn is None else f64(pn).reshape(-1, 4)
-        res = np.zeros((n, 19))
-        J = np.zeros((n, 646)) if want_jac else None
-        S = np.zeros((n, 19, 19))
-        status = np.zeros(n, np.int32)
-        self._ck(self.lib.icg_preint_odo_evaluate_batch(self.h, int(variant), n, _p(delta), _p(jac), _p(cov), _p(dt), _p(env), _p(po), _p(pnr),
-                                                         _p(points), _p(res), _p(J), _p(S), _p(status)), "icg_preint_odo_evaluate_batch")
-        return res, J, S, status
+        return self._preint_evaluate_batch_call(self._PREINT_ODO, variant, delta, jac, cov, dt, env, points, pn_offsets, pn, want_jac)
 
     def preint_set(self, variant, delta, jac, sqrt_info, dt, env, q_nn, pn_offsets=None, pn=None):
         """icg_preint_set: len(variant) factors become resident (variant per factor; sqrt_info and q_nn are the host's)"""
-        variant = i32(variant).reshape(-1)
-        n = len(variant)
-        delta, jac, sqrt_info = f64(delta).reshape(n, 16), f64(jac).reshape(n, 225), f64(sqrt_info).reshape(n, 225)
-        dt, env, q_nn = f64(dt).reshape(n), f64(env).reshape(n, 4), f64(q_nn).reshape(n, 4)
-        po = None if pn_offsets is None else i32(pn_offsets)
-        pnr = None if pn is None else f64(pn).reshape(-1, 4)
-        self._preint_n = 0
-        self._ck(self.lib.icg_preint_set(self.h, n, _p(variant), _p(delta), _p(jac), _p(sqrt_info), _p(dt), _p(env), _p(q_nn), _p(po), _p(pnr)),
-                 "icg_preint_set")
-        self._preint_n = n
-
-    def preint_evaluate_resident(self, points, q_corr, want_jac=True):
-        """icg_preint_evaluate_resident: residuals (and Jacobians) stay on the device -> sq_norm (r . r per factor)"""
-        n = getattr(self, "_preint_n", 0)
-        points, q_corr = f64(points).reshape(-1, 32), f64(q_corr).reshape(-1, 4)
-        if n and (points.shape[0] != n or q_corr.shape[0] != n):
-            raise IcgError(f"preint_evaluate_resident: {points.shape[0]} points and {q_corr.shape[0]} quaternions, the resident set has {n} factors")
-        sq = np.zeros(max(n, 1))
-        self._ck(self.lib.icg_preint_evaluate_resident(self.h, _p(points), _p(q_corr), 1 if want_jac else 0, _p(sq)), "icg_preint_evaluate_resident")
-        return sq[:n]
-
-    def preint_fetch_resident(self, want_jac=True):
-        """icg_preint_fetch_resident -> (residuals n x 15, jacobians n x 480 or None) of the last resident evaluation"""
-        n = max(getattr(self, "_preint_n", 0), 1)
-        res = np.zeros((n, 15))
-        J = np.zeros((n, 480)) if want_jac else None
-        self._ck(self.lib.icg_preint_fetch_resident(self.h, _p(res), _p(J)), "icg_preint_fetch_resident")
-        return res, J
+        self._preint_set_call(self._PREINT, variant, delta, jac, sqrt_info, dt, env, q_nn, pn_offsets, pn)
 
     def preint_odo_set(self, variant, delta, jac, sqrt_info, dt, env, q_nn, pn_offsets=None, pn=None):
         """icg_preint_odo_set: len(variant) odometer factors become resident (variant 2 / 3 per factor; sqrt_info and q_nn are the host's)"""
-        variant = i32(variant).reshape(-1)
-        n = len(variant)
-        delta, jac, sqrt_info = f64(delta).reshape(n, 20), f64(jac).reshape(n, 361), f64(sqrt_info).reshape(n, 361)
-        dt, env, q_nn = f64(dt).reshape(n), f64(env).reshape(n, 4), f64(q_nn).reshape(n, 4)
-        po = None if pn_offsets is None else i32(pn_offsets)
-        pnr = None if pn is None else f64(pn).reshape(-1, 4)
-        self._preint_odo_n = 0
-        self._ck(self.lib.icg_preint_odo_set(self.h, n, _p(variant), _p(delta), _p(jac), _p(sqrt_info), _p(dt), _p(env), _p(q_nn), _p(po), _p(pnr)),
-                 "icg_preint_odo_set")
-        self._preint_odo_n = n
+        self._preint_set_call(self._PREINT_ODO, variant, delta, jac, sqrt_info, dt, env, q_nn, pn_offsets, pn)
+
+    def preint_evaluate_resident(self, points, q_corr, want_jac=True):
+        """icg_preint_evaluate_resident: residuals (and Jacobians) stay on the device -> sq_norm (r . r per factor)"""
+        return self._preint_evaluate_resident_call(self._PREINT, points, q_corr, want_jac)
 
     def preint_odo_evaluate_resident(self, points, q_corr, want_jac=True):
         """icg_preint_odo_evaluate_resident: residuals (and Jacobians) stay on the device -> sq_norm (r . r per factor)"""
-        n = getattr(self, "_preint_odo_n", 0)
-        points, q_corr = f64(points).reshape(-1, 34), f64(q_corr).reshape(-1, 4)
-        if n and (points.shape[0] != n or q_corr.shape[0] != n):
-            raise IcgError(f"preint_odo_evaluate_resident: {points.shape[0]} points and {q_corr.shape[0]} quaternions, the resident set has {n} factors")
-        sq = np.zeros(max(n, 1))
-        self._ck(self.lib.icg_preint_odo_evaluate_resident(self.h, _p(points), _p(q_corr), 1 if want_jac else 0, _p(sq)),
-                 "icg_preint_odo_evaluate_resident")
-        return sq[:n]
+        return self._preint_evaluate_resident_call(self._PREINT_ODO, points, q_corr, want_jac)
+
+    def preint_fetch_resident(self, want_jac=True):
+        """icg_preint_fetch_resident -> (residuals n x 15, jacobians n x 480 or None) of the last resident evaluation"""
+        return self._preint_fetch_resident_call(self._PREINT, want_jac)
 
     def preint_odo_fetch_resident(self, want_jac=True):
         """icg_preint_odo_fetch_resident -> (residuals n x 19, jacobians n x 646 or None) of the last resident evaluation"""
-        n = max(getattr(self, "_preint_odo_n", 0), 1)
-        res = np.zeros((n, 19))
-        J = np.zeros((n, 646)) if want_jac else None
-        self._ck(self.lib.icg_preint_odo_fetch_resident(self.h, _p(res), _p(J)), "icg_preint_odo_fetch_resident")
-        return res, J
+        return self._preint_fetch_resident_call(self._PREINT_ODO, want_jac)
 
     # ---- navigation factors (host/nav_factors.h), resident
     def nav_set(self, kind, aux_off, aux):
